@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: ELAS stereo pairs/s on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--batch B] [--lanes L]
+  python bench.py --gpus N --steps K --warmup W [--batch B] [--lanes L] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes the
+outputs of the last timed step if --dump-outputs is given, and prints one JSON line (`value` pairs/s,
+`ms_per_step`, the configuration and the per-rank records).  --full adds everything else listed below:
+the roofline (HIP-event kernel timing, an isolated probe, the copy bandwidth), the self-check of the
+timed outputs against the reference's maps, the secondary legs and the CPU baseline.
+
+--dump-outputs DIR writes, after the timed steps, the maps the last timed step left in HBM: a fixed,
+seeded sample of the batch's pairs as DIR/D1.npy and DIR/D2.npy (float32, [n, H, W], at most 64 MB
+together) and their positions in the batch as DIR/pair_index.npy (float64).  The inputs depend only on
+the arguments, so two builds can be compared map for map.  With several ranks, rank 0's pairs.
 
 Workload (BASELINE.json configs[1]): the four KITTI-size 1242x375 crops of
 the reference's own urban{1..4} images (tests/golden/, offset x=51 y=8), tiled; full ELAS ROBOTICS
@@ -16,6 +27,8 @@ and no WORLD_SIZE in the environment makes this script start the N ranks itself 
 N>1 path is exercised on a 1-GPU box.
 
 Besides the contract fields the JSON line carries
+  ranks                    per rank: pairs/s, host cores used, workers, host-core ceiling
+and that of a --full run also
   roofline                 achieved algorithmic GB/s of the dominant kernel, from HIP events
                            recorded on the kernels' own streams (svh_profile_*), vs 8 TB/s
   cpu_baseline             the reference Elas::process (oracle/_ref) on this host: 1 thread, and
@@ -24,7 +37,6 @@ Besides the contract fields the JSON line carries
                            SURVEY 8b) through svh_elas_process_batch on pinned buffers --
                            PCIe-inclusive, never `value`
   value_synthetic          the same step on seeded synthetic pairs (round-1 headline workload)
-  ranks                    per rank: pairs/s, host cores used, workers, host-core ceiling
 torch is used only for device memory, pinned memory, the barrier and the result gather.
 """
 import argparse
@@ -616,6 +628,26 @@ def read_profile(S):
     return out
 
 
+DUMP_BYTES_MAX = 64 * 10 ** 6   # --dump-outputs: all files together, .npy headers included
+DUMP_PAIRS_MAX = 8
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirname, dD1, dD2):
+    """--dump-outputs: D1 / D2 of a fixed, seeded sample of the batch's pairs (float32, [n, H, W]) and the sampled
+    positions in the batch (float64).  The sample depends only on the batch size and the map size."""
+    import torch
+    B, h, w = dD1.shape
+    per_pair = 2 * h * w * 4
+    n = max(1, min(B, DUMP_PAIRS_MAX, (DUMP_BYTES_MAX - 4096) // per_pair))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+    it = torch.as_tensor(idx, dtype=torch.int64, device=dD1.device)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "D1.npy"), dD1.index_select(0, it).cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(dirname, "D2.npy"), dD2.index_select(0, it).cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(dirname, "pair_index.npy"), idx.astype(np.float64))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -687,7 +719,7 @@ def main():
     ap.add_argument("--spinup", type=float, default=1.0,
                     help="seconds of untimed steps before the warmup (GPU clocks, lane buffers)")
     ap.add_argument("--profile-in-timed-region", type=int, default=1,
-                    help="1: HIP-event kernel timing is on during the timed steps (roofline comes "
+                    help="--full: 1: HIP-event kernel timing is on during the timed steps (roofline comes "
                          "from exactly those launches); 0: a separate pass after them")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL, the default) or gloo (CPU collectives: lets several ranks "
@@ -707,10 +739,16 @@ def main():
                          "them, the lanes stay full across steps.  auto = stream for the workloads whose "
                          "step is shorter than the pipeline is deep (sequence, hd1080), batch for kitti")
     ap.add_argument("--depth", type=int, default=0, help="stream: pairs in flight (0: lanes x 2 groups)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, the self-check of the timed outputs against the "
+                         "reference's maps, the secondary legs and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps: D1 / D2 of a fixed, seeded sample of the last timed step's pairs "
+                         "as DIR/D1.npy, DIR/D2.npy (float32) and their positions in the batch as DIR/pair_index.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-bind", action="store_true", help="several ranks: do not bind a rank's threads to its GPU's NUMA node")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary legs (synthetic, host buffers, latency, Matcher, VO, map)")
+                    help="--full: skip the secondary legs (synthetic, host buffers, latency, Matcher, VO, map)")
     ap.add_argument("--cpu-budget", type=float, default=5.0, help="seconds per CPU baseline leg")
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)
     ap.add_argument("--devcount", default="",
@@ -948,10 +986,10 @@ def main():
     if api != "stream":
         for _ in range(args.warmup):
             step()
-    # which kernel dominates?  one profiled, untimed step with every kernel bracketed
-    in_region = bool(args.profile_in_timed_region) and rank == 0
+    # which kernel dominates?  one profiled, untimed step with every kernel bracketed (--full: the roofline)
+    in_region = args.full and bool(args.profile_in_timed_region) and rank == 0
     prof_all = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         S.lib().svh_profile_only.argtypes = [C.c_char_p]
         S.lib().svh_profile_only(None)
         S.lib().svh_profile_reset()
@@ -1016,6 +1054,8 @@ def main():
     if in_region:
         S.lib().svh_profile_enable(0)
         S.lib().svh_profile_only(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dD1, dD2)     # the maps of the last timed step, before anything reuses them
     # the only collective on the path: a small per-rank result record (RCCL over xGMI, or gloo)
     from svhip import shard
     my_pairs = B * args.steps
@@ -1023,7 +1063,7 @@ def main():
     # as the last timed step left them, with the reference's Elas::process run here on the same inputs
     # (oracle/_ref, the checker -- after the timed region), every pixel
     oracle_bad = -1.0
-    if args.workload == "hd1080" and data == "synthetic" and Hh.have_ref_elas():
+    if args.full and args.workload == "hd1080" and data == "synthetic" and Hh.have_ref_elas():
         oracle_bad = 0.0
         for k in sorted(set((0, min(1, B - 1)))):
             R1, R2 = Hh.ref_elas_process(params, I1[k % U], I2[k % U])
@@ -1062,7 +1102,7 @@ def main():
     #              the loaded library's): measured HBM bytes (`traffic`) and VALU instructions.
     # The machine-share model of round 3 stays as `modelled_share_normalised`, never as `frac`.
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         prof = read_profile(S) if in_region else prof_all
         pmc = load_pmc(build, "_hd1080" if args.workload == "hd1080" else "")
         if prof:
@@ -1247,9 +1287,9 @@ def main():
 
     # self-check of the timed region's outputs: the maps of the first unique pairs, as the last timed
     # step left them, against the reference's own results (tests/golden, made by make_goldens.py from
-    # oracle/_ref with the bench's parameters) -- bit for bit
+    # oracle/_ref with the bench's parameters) -- bit for bit (--full, and --soak)
     golden_check = None
-    if rank == 0 and args.workload in ("kitti", "sequence") and data == "urban crops":
+    if rank == 0 and (args.full or args.soak > 0) and args.workload in ("kitti", "sequence") and data == "urban crops":
         gold = ["urban1_robotics", "urban2_kitti", "urban3_kitti", "urban4_kitti"]
         first = getattr(args, "seq_first", 0)
         bad = []
@@ -1332,8 +1372,9 @@ def main():
                        "stage_groups_device_handed_back": list(S.stage_stats()),
                        "d1_valid_fraction": round(valid, 4)},
             "ranks": ranks,
-            "roofline": roofline,
         }
+        if args.full:
+            out["roofline"] = roofline
         if devcount is not None:
             out["devcount"] = devcount
         if args.workload == "hd1080" and all(r_["oracle_mismatch_px_first_two_pairs"] is not None for r_ in ranks):
@@ -1347,7 +1388,7 @@ def main():
         if use_dist:
             out["config"]["dist_backend"] = args.dist_backend
             out["config"]["dist_initialised"] = True
-        extras = world == 1 and not args.no_extras
+        extras = args.full and world == 1 and not args.no_extras
         if extras and args.workload != "hd1080":
             # SURVEY 8(b) ownership contract: host pointers in, host pointers out, through the
             # batch entry (pinned buffers; `lanes` workers x `group` pairs in flight).  PCIe-inclusive.
@@ -1461,7 +1502,7 @@ def main():
             out["visual_odometry"]["lockstep"] = vo_lockstep_bench()
             if args.workload == "kitti":
                 out["application_settings"] = settings_bench(S, torch, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(I1, I2, params, what, budget_s=args.cpu_budget,
                                                workers=int(avail) if args.workload == "kitti" else 0)
         print(json.dumps(out), flush=True)

@@ -32,7 +32,7 @@ cp $R/gpurun_out/devcount.json $R/profiles/${ROUND}_devcount.json
 GRAFT_REPO_ROOT=$R timeout 900 bash $R/tools/gpu_devcount.sh _hd1080 --workload hd1080 > $O/devcount_summary_hd1080.txt 2>&1
 cp $R/gpurun_out/devcount_hd1080.json $O/devcount_hd1080.json
 cd $R
-b() { name=$1; shift; timeout 600 python bench.py "$@" > $O/bench_line$name.json 2> $O/bench_line$name.err; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" > $O/bench_line$name.json 2> $O/bench_line$name.err; }
 b "" --gpus 1 --steps 20 --warmup 5
 Q="--no-extras --no-cpu-baseline"
 b _kitti_stream $Q --steps 10 --warmup 3 --api stream
@@ -59,7 +59,7 @@ b _8ranks_gloo_1gpu_hd1080 $Q --gpus 8 --dist-backend gloo --steps 8 --warmup 2 
 env -u GPU_MAX_HW_QUEUES timeout 300 stereo-vision_amd/bin/svh_shard --ranks 1 --gather rccl --pairs-per-rank 6144 --steps 20 --warmup 5 2> /dev/null | grep '^{' > $O/shard_driver_1rank_rccl.json
 env -u GPU_MAX_HW_QUEUES timeout 300 stereo-vision_amd/bin/svh_shard --ranks 4 --pairs-per-rank 1536 --steps 20 --warmup 5 2> /dev/null | grep '^{' > $O/shard_driver_4ranks_pipes_1gpu.json
 env -u GPU_MAX_HW_QUEUES timeout 300 stereo-vision_amd/bin/svh_shard --ranks 8 --total 430 --steps 20 --warmup 5 --lanes 2 2> /dev/null | grep '^{' > $O/shard_driver_8ranks_sequence_strong.json
-SVH_MATCH_LIST=0 timeout 300 python bench.py $Q --steps 10 --warmup 3 > $O/bench_line_keyed_matcher.json 2> /dev/null
+SVH_MATCH_LIST=0 timeout 300 python bench.py --full $Q --steps 10 --warmup 3 > $O/bench_line_keyed_matcher.json 2> /dev/null
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
 cd /tmp
 kt() {  # name cmd...
@@ -71,10 +71,10 @@ kt() {  # name cmd...
   DB=$(find /tmp/kt_$name -name "*.db" | head -1)
   [ -n "$DB" ] && python $R/tools/rocpd_summary.py $DB > $O/kernel_stats_$name.txt
 }
-kt kitti python $R/bench.py --no-extras --no-cpu-baseline --steps 12 --warmup 3
-kt hd1080 python $R/bench.py --workload hd1080 --no-extras --no-cpu-baseline --steps 20 --warmup 3
-kt hd1080_b8 python $R/bench.py --workload hd1080 --batch 8 --no-extras --no-cpu-baseline --steps 200 --warmup 10
-kt sequence python $R/bench.py --workload sequence --no-extras --no-cpu-baseline --steps 20 --warmup 3
+kt kitti python $R/bench.py --full --no-extras --no-cpu-baseline --steps 12 --warmup 3
+kt hd1080 python $R/bench.py --full --workload hd1080 --no-extras --no-cpu-baseline --steps 20 --warmup 3
+kt hd1080_b8 python $R/bench.py --full --workload hd1080 --batch 8 --no-extras --no-cpu-baseline --steps 200 --warmup 10
+kt sequence python $R/bench.py --full --workload sequence --no-extras --no-cpu-baseline --steps 20 --warmup 3
 kt matcher python $R/tools/gpu_legs.py matcher
 kt vo python $R/tools/gpu_legs.py vo
 LOCKSTEP_PIPELINED=0 kt vo_lockstep16 python $R/tools/gpu_legs.py lockstep1x16

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out; mkdir -p $O
-ISO="python $R/bench.py --steps 2 --warmup 1 --no-extras --no-cpu-baseline --batch 32 --lanes 1 --group 4 --spinup 0 --profile-in-timed-region 0"
+ISO="python $R/bench.py --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --batch 32 --lanes 1 --group 4 --spinup 0 --profile-in-timed-region 0"
 VARS=${@:-0 1 2 3 4 5 6 8}
 OUT=$O/match_split.txt
 python -c "import sys; sys.path.insert(0,'$R/stereo-vision_amd'); import svhip; print('#', svhip.lib().svh_version().decode())" > $OUT

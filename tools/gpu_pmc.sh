@@ -3,7 +3,7 @@
 #   tools/gpu_pmc.sh [kernel,list]   -> gpurun_out/pmc_sq.txt, gpurun_out/pmc_sq_[ab].db
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-CMD="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --batch 16 --no-extras --lanes 1 --group 4 --spinup 0 --profile-in-timed-region 0"
+CMD="python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --batch 16 --no-extras --lanes 1 --group 4 --spinup 0 --profile-in-timed-region 0"
 run() {  # name counters...
   local name=$1; shift
   for try in 1 2 3; do

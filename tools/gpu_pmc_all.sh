@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 # usage: gpu_pmc_all.sh [suffix [extra bench.py arguments]]   e.g.  gpu_pmc_all.sh _hd1080 --workload hd1080
 SUF=$1; [ $# -gt 0 ] && shift
-ISO="python $R/bench.py --steps 2 --warmup 1 --no-extras --no-cpu-baseline --batch 32 --lanes 1 --group 4 --spinup 0 --profile-in-timed-region 0 $@"
+ISO="python $R/bench.py --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --batch 32 --lanes 1 --group 4 --spinup 0 --profile-in-timed-region 0 $@"
 pmc() {  # name counters...
   local name=$1; shift
   for try in 1 2 3; do

@@ -4,9 +4,9 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-python $R/bench.py > $O/bench_full.json 2> $O/bench_full.err
-KT_LINES=60 $R/tools/gpu_ktrace.sh bench python $R/bench.py --no-cpu-baseline > /dev/null
-ISO="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --batch 32 --lanes 1 --group 4 --spinup 0 --profile-in-timed-region 0"
+python $R/bench.py --full > $O/bench_full.json 2> $O/bench_full.err
+KT_LINES=60 $R/tools/gpu_ktrace.sh bench python $R/bench.py --full --no-cpu-baseline > /dev/null
+ISO="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --batch 32 --lanes 1 --group 4 --spinup 0 --profile-in-timed-region 0"
 pmc() {  # name counter
   for try in 1 2 3; do
     rm -rf /tmp/pmc_$1
