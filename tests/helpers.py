@@ -8,6 +8,7 @@
 Nothing here reads /root/reference at run time.
 """
 import ctypes as C
+import hashlib
 import os
 import sys
 
@@ -959,3 +960,41 @@ def fuzz_vo_params(seed):
     m.outlier_flow_tolerance = int(rng.integers(3, 8))
     p.match = m
     return p
+
+
+# ----------------------------------------------------------------------------- full-size fixtures
+def _unfilter_rows(d):
+    """inverse of the horizontal difference filter the full-size image fixtures are stored with"""
+    return np.cumsum(d, axis=1, dtype=np.uint8)
+
+
+def full_image(name):
+    """one full-size gray image under tests/golden/full (make_goldens_full.py): uint8 (h, w)"""
+    with np.load(os.path.join(GOLDEN, "full", name + ".npz")) as z:
+        return _unfilter_rows(z["rows"])
+
+
+def full_pair(name):
+    """a full-size ELAS pair of the reference's (urban1-4, cones, aloe, raindeer)"""
+    return full_image(name + "_left"), full_image(name + "_right")
+
+
+def mono_frames():
+    """the seven frames I1_000000..6 of the reference's mono sequence, gray"""
+    return [full_image("I1_%06d" % k) for k in range(7)]
+
+
+def stage_sha256(a):
+    """sha256 of a stage's bytes; float arrays with -0.0 taken as +0.0 (the float compares are value compares)"""
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.float32:
+        a = np.where(a == 0, np.float32(0), a).astype(np.float32)
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+def full_case(case):
+    """golden record of one full-size ELAS case: (npz, params, left, right)"""
+    z = np.load(os.path.join(GOLDEN, "full", "elas_" + case + ".npz"))
+    prm = ElasParams.from_buffer_copy(z["params"].tobytes())
+    l, r = full_pair(str(z["pair"]))
+    return z, prm, l, r
