@@ -526,6 +526,43 @@ int32_t svh_vo_get_inliers(svh_vo* v, int32_t* out, int32_t cap);/* getInlierInd
 float   svh_vo_get_gain(svh_vo* v, const int32_t* inliers, int32_t n);
 svh_matcher* svh_vo_matcher(svh_vo* v);                          /* the owned Matcher (taps)   */
 
+/* ===========================================================================
+ * libviso2 VisualOdometryMono
+ *   VisualOdometryMono::parameters          libviso2/src/viso_mono.h:30-45
+ * A mono object is an svh_vo: svh_vo_process_matches, svh_vo_estimate_motion, svh_vo_get_motion / _matches /
+ * _inliers, svh_vo_num_matches, svh_vo_get_gain, svh_vo_set_private_rand, svh_vo_matcher and svh_vo_destroy work on
+ * it as on a stereo object; svh_vo_process and the batch, prefetch and next entries return SVH_ERR_BAD_ARG.
+ * =========================================================================== */
+typedef struct svh_vo_mono_params {
+    svh_matcher_params match;      /* parameters::match                                       */
+    int32_t bucket_max_features;   /* bucketing::max_features   (2)                           */
+    double  bucket_width;          /* bucketing::bucket_width   (50)                          */
+    double  bucket_height;         /* bucketing::bucket_height  (50)                          */
+    double  f, cu, cv;             /* calibration               (1, 0, 0)                     */
+    double  height;                /* camera height above ground in metres (1.0)              */
+    double  pitch;                 /* camera pitch in rad, negative = pointing down (0.0)     */
+    int32_t ransac_iters;          /* (2000)                                                  */
+    double  inlier_threshold;      /* fundamental matrix inlier threshold (1e-5)              */
+    double  motion_threshold;      /* return false on small motions (100)                     */
+} svh_vo_mono_params;
+void    svh_vo_mono_params_default(svh_vo_mono_params* p);
+/* VisualOdometryMono(param): creates the Matcher, Tr_delta = I and calls srand(0) like the reference
+ * (viso.cpp:28-37, viso_mono.cpp:26-27) */
+svh_vo* svh_vo_mono_create(const svh_vo_mono_params* p);
+/* bool VisualOdometryMono::process(I,dims,replace) -- viso_mono.cpp:32-38: pushBack of one image, matchFeatures(0),
+ * bucketFeatures, estimateMotion (RANSAC over 8-point fundamental matrices, chirality and the ground-plane scale on
+ * the device).  returns 1 (true), 0 (false: motion too small or estimate failed) or a negative SVH_ERR_*.
+ * One deliberate difference: where the reference exits the process (a plane distance |d| < 1e-20 in
+ * Matrix::operator/, matrix.cpp:497-503, or no R|t candidate with a point in front of both cameras) this returns 0. */
+int32_t svh_vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, int32_t replace);
+/* test tap: the inlier count of every RANSAC hypothesis of the last estimate that reached the RANSAC loop, in
+ * iteration order; copies up to cap, returns the count (0 for a stereo object) */
+int32_t svh_vo_mono_get_votes(svh_vo* v, int32_t* out, int32_t cap);
+/* device time of the three phases of the last estimate (RANSAC, chirality, plane vote) in ms from HIP events,
+ * recorded only after svh_vo_mono_set_timing(v, 1); returns the number of entries written (3) */
+void    svh_vo_mono_set_timing(svh_vo* v, int32_t on);
+int32_t svh_vo_mono_get_timing(svh_vo* v, double* ms3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,8 @@ public:
 
 protected:
     explicit VisualOdometry(const svh_vo_params& q) : _vo(svh_vo_create(&q)) {}
+    // adopts a handle made by another constructor of the C-ABI (svh_vo_mono_create, viso_mono.h)
+    explicit VisualOdometry(svh_vo* adopted) : _vo(adopted) {}
     svh_vo* _vo;
 
 private:

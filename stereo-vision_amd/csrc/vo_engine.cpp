@@ -65,6 +65,7 @@ struct svh_vo {
     double* d_J = nullptr;
     double* d_res = nullptr;
     int32_t j_cap = 0;
+    svh::MonoVo* mono = nullptr;   // a VisualOdometryMono (svh_vo_mono_create): its estimate replaces the stereo one
 };
 
 namespace {
@@ -204,6 +205,7 @@ int estimate_collect(svh_vo* v, double* tr6) {
 
 // estimateMotion: returns 1 + tr, 0 for the reference's empty vector, <0 on error
 int estimate(svh_vo* v, const svh_p_match* pm, int32_t N, double* tr6) {
+    if (v->mono) return mono_estimate(v->mono, pm, N, v->rng, v->inliers, tr6);   // viso_mono.cpp:40-159
     const int rc = estimate_prepare(v, pm, N);
     if (rc <= 0) return rc;
     estimate_enqueue(v, N);
@@ -283,6 +285,7 @@ svh_vo* svh_vo_create(const svh_vo_params* p) {
 
 void svh_vo_destroy(svh_vo* v) {
     if (!v) return;
+    mono_destroy(v->mono);
     if (v->stream) {
         (void)hipSetDevice(v->device);
         (void)hipStreamSynchronize(v->stream);
@@ -317,6 +320,7 @@ static int32_t process_after_push(svh_vo* v) {
 int32_t svh_vo_process(svh_vo* v, const uint8_t* I1, const uint8_t* I2, const int32_t* dims, int32_t replace) {
     svh::ActiveCaller active_;
     if (!v || !dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    if (v->mono) return svh::fail(SVH_ERR_BAD_ARG, "svh_vo_process on a mono object: use svh_vo_mono_process");
     const int32_t rc = svh_matcher_push_back(v->matcher, I1, I2, dims, replace);
     if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored -- viso_stereo.cpp:41-68 goes on; a missing or pending prefetched frame IS an error)   // bad dims: message printed, carry on like the reference
     return process_after_push(v);
@@ -338,6 +342,7 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
     bool lockstep = K > 1;
     for (int i = 0; i < K; i++) {
         if (!vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "null object in the batch");
+        if (vs[i]->mono) return svh::fail(SVH_ERR_BAD_ARG, "mono objects have no batch entries");
         for (int j = 0; j < i; j++)
             if (vs[j] == vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "the same object twice in one batch");
         lockstep = lockstep && vs[i]->Tr_valid && memcmp(&vs[i]->p, &vs[0]->p, sizeof(vs[0]->p)) == 0 &&
@@ -481,6 +486,7 @@ int32_t svh_vo_prefetch_batch(svh_vo* const* vs, int32_t K, const uint8_t* const
     std::vector<svh_matcher*> ms(K);
     for (int i = 0; i < K; i++) {
         if (!vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "null object in the batch");
+        if (vs[i]->mono) return svh::fail(SVH_ERR_BAD_ARG, "mono objects have no batch entries");
         ms[i] = vs[i]->matcher;
     }
     return svh_matcher_prefetch_batch(ms.data(), K, I1, I2, dims);
@@ -534,5 +540,85 @@ float svh_vo_get_gain(svh_vo* v, const int32_t* inliers, int32_t n) {
 }
 
 svh_matcher* svh_vo_matcher(svh_vo* v) { return v ? v->matcher : nullptr; }
+
+// ---------------------------------------------------------------------------------------------------------------
+// VisualOdometryMono   libviso2/src/viso_mono.h:30-45, viso_mono.cpp:26-38
+
+void svh_vo_mono_params_default(svh_vo_mono_params* p) {
+    if (!p) return;
+    svh_matcher_params_default(&p->match);
+    p->bucket_max_features = 2;      // viso.h:50-55
+    p->bucket_width = 50;
+    p->bucket_height = 50;
+    p->f = 1; p->cu = 0; p->cv = 0;  // viso.h:38-43
+    p->height = 1.0;                 // viso_mono.h:38-44
+    p->pitch = 0.0;
+    p->ransac_iters = 2000;
+    p->inlier_threshold = 0.00001;
+    p->motion_threshold = 100.0;
+}
+
+svh_vo* svh_vo_mono_create(const svh_vo_mono_params* p) {
+    if (!p) return nullptr;
+    svh_vo_params q;
+    svh_vo_params_default(&q);
+    q.match = p->match;
+    q.bucket_max_features = p->bucket_max_features;
+    q.bucket_width = p->bucket_width;
+    q.bucket_height = p->bucket_height;
+    q.f = p->f; q.cu = p->cu; q.cv = p->cv;
+    svh_vo* v = svh_vo_create(&q);   // Matcher, device, stereo kernels loaded, srand(0)
+    if (!v) return nullptr;
+    // the reference's mono constructor does not set the Matcher's intrinsics (viso_mono.cpp:26-27)
+    svh_matcher_set_intrinsics(v->matcher, p->match.f, p->match.cu, p->match.cv, p->match.base);
+    v->mono = mono_create(*p, v->device);
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) == hipSuccess && nd > 0) {
+        // load the mono kernels (the runtime may draw from libc rand() while it does) on a small synthetic scene
+        // with a private stream, then srand(0) again as the constructor does (viso.cpp:36)
+        svh_p_match pm[16];
+        memset(pm, 0, sizeof(pm));
+        for (int i = 0; i < 16; i++) {
+            pm[i].u1p = (float)(40 * (i % 4) + 3 * i);
+            pm[i].v1p = (float)(30 * (i / 4) + (i * i) % 7);
+            pm[i].u1c = pm[i].u1p + 2.f + 0.1f * (float)(i % 3);
+            pm[i].v1c = pm[i].v1p + 1.f;
+        }
+        RandStream rs;
+        rs.seed(1);
+        std::vector<int32_t> inl;
+        double tr[6];
+        (void)mono_estimate(v->mono, pm, 16, rs, inl, tr);
+        mono_clear(v->mono);
+    }
+    srand(0);
+    return v;
+}
+
+int32_t svh_vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, int32_t replace) {
+    svh::ActiveCaller active_;
+    if (!v || !dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    if (!v->mono) return svh::fail(SVH_ERR_BAD_ARG, "svh_vo_mono_process on a stereo object");
+    int32_t rc = svh_matcher_push_back(v->matcher, I, nullptr, dims, replace);
+    if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored)
+    rc = svh_matcher_match_features(v->matcher, 0, nullptr);
+    if (rc < 0) return rc;
+    const svh_vo_params& P = v->p;   // (the bucketing fields of the mono parameters)
+    bucket_features(v->matcher, P.bucket_max_features, (float)P.bucket_width, (float)P.bucket_height, v->rng);
+    fetch_matches(v);
+    return update_motion(v);
+}
+
+int32_t svh_vo_mono_get_votes(svh_vo* v, int32_t* out, int32_t cap) {
+    return v && v->mono ? mono_votes(v->mono, out, cap) : 0;
+}
+
+void svh_vo_mono_set_timing(svh_vo* v, int32_t on) {
+    if (v && v->mono) mono_set_timing(v->mono, on != 0);
+}
+
+int32_t svh_vo_mono_get_timing(svh_vo* v, double* ms3) {
+    return v && v->mono ? mono_timing(v->mono, ms3) : 0;
+}
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <vector>
+
 #include "../../include/svh.h"
 #include "svh_config.h"
 
@@ -83,6 +85,33 @@ void vlaunch_upload(void* stream, const uint8_t* pinned, uint8_t* dev, size_t by
 void vlaunch_estimate(void* stream, const svh_p_match* pm, int N, const int32_t* samples, int iters,
                       const VoCalib& c, double* hyp_tr, int32_t* hyp_count, uint8_t* hyp_flags, double* Jg,
                       double* resg, VoResult* out, int32_t* out_inliers);
+
+// VisualOdometryMono (vo_mono_engine.cpp, vo_mono_kernels.hip).  Matches go to the device as 4 floats each
+// (u1p, v1p, u1c, v1c), 16 bytes per match.
+// k_mono_hyp + k_mono_vote + k_mono_select: per-hypothesis counts, the winner {best, count} and its inlier flags
+// (out_* in pinned host memory)
+void mlaunch_ransac(void* stream, const float* q4, int32_t N, const int32_t* samples, int32_t iters, double thr,
+                    double* F, int32_t* counts, int32_t* out_sel, uint8_t* out_flags, int32_t* out_counts);
+// k_mono_chiral + k_mono_pick.  cams (device, 60 doubles): triangulateChieral's projection matrices, 3x4 row major
+// (viso_mono.cpp:369-375): P1 = K [I | 0], then P2 = K [R | t] of the four candidates of EtoRt, (Ra,t) (Ra,-t) (Rb,t)
+// (Rb,-t).  out_cand = {candidate or -1, 4 counts}, out_X = its points / 4th coordinate (4 x N)
+void mlaunch_chiral(void* stream, const float* m4, int32_t N, const double* cams, double* X, uint8_t* front,
+                    double* out_X, int32_t* out_cand);
+// k_mono_plane: sums[i] of the ground-plane vote (0 where d[i] <= thr)
+void mlaunch_plane(void* stream, const double* d, int32_t n, double weight, double thr, double* sums);
+
+// the state of a mono estimate behind an svh_vo (vo_mono_engine.cpp)
+struct MonoVo;
+MonoVo* mono_create(const svh_vo_mono_params& p, int device);
+void mono_destroy(MonoVo* M);
+// estimateMotion (viso_mono.cpp:40-159): 1 + tr6, 0 for the reference's empty vector, < 0 on error; `inliers` is the
+// object's getInlierIndices() state, cleared only where the reference clears it
+int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, std::vector<int32_t>& inliers,
+                  double* tr6);
+int32_t mono_votes(MonoVo* M, int32_t* out, int32_t cap);
+void mono_clear(MonoVo* M);   // forget the last estimate's votes and times
+void mono_set_timing(MonoVo* M, bool on);
+int32_t mono_timing(MonoVo* M, double* ms3);
 
 }  // namespace svh
 #endif

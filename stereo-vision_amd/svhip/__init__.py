@@ -418,3 +418,143 @@ def stage_stats():
 
 def device_count():
     return lib().svh_device_count()
+
+
+# ---------------------------------------------------------------------------
+# VisualOdometryMono (svh_vo_mono_*, include/svh.h; libviso2/src/viso_mono.h)
+# ---------------------------------------------------------------------------
+class MatcherParams(C.Structure):
+    """svh_matcher_params == Matcher::parameters (libviso2/src/matcher.h:41-69)"""
+    _fields_ = [
+        ("nms_n", C.c_int32), ("nms_tau", C.c_int32), ("match_binsize", C.c_int32),
+        ("match_radius", C.c_int32), ("match_disp_tolerance", C.c_int32),
+        ("outlier_disp_tolerance", C.c_int32), ("outlier_flow_tolerance", C.c_int32),
+        ("multi_stage", C.c_int32), ("half_resolution", C.c_int32), ("refinement", C.c_int32),
+        ("f", C.c_double), ("cu", C.c_double), ("cv", C.c_double), ("base", C.c_double),
+    ]
+
+
+class VoMonoParams(C.Structure):
+    """svh_vo_mono_params == VisualOdometryMono::parameters (libviso2/src/viso_mono.h:30-45)"""
+    _fields_ = [
+        ("match", MatcherParams), ("bucket_max_features", C.c_int32), ("bucket_width", C.c_double),
+        ("bucket_height", C.c_double), ("f", C.c_double), ("cu", C.c_double), ("cv", C.c_double),
+        ("height", C.c_double), ("pitch", C.c_double), ("ransac_iters", C.c_int32),
+        ("inlier_threshold", C.c_double), ("motion_threshold", C.c_double),
+    ]
+
+
+# Matcher::p_match (libviso2/src/matcher.h:87-102) == svh_p_match
+P_MATCH = np.dtype([("u1p", "f4"), ("v1p", "f4"), ("i1p", "i4"), ("u2p", "f4"), ("v2p", "f4"), ("i2p", "i4"),
+                    ("u1c", "f4"), ("v1c", "f4"), ("i1c", "i4"), ("u2c", "f4"), ("v2c", "f4"), ("i2c", "i4")])
+
+
+def vo_mono_params(**kw):
+    """VisualOdometryMono::parameters() (viso_mono.h:38-44) with the given fields replaced"""
+    p = VoMonoParams()
+    L = lib()
+    L.svh_vo_mono_params_default.argtypes = [C.POINTER(VoMonoParams)]
+    L.svh_vo_mono_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class VoMono:
+    """Drop-in for the reference class VisualOdometryMono (libviso2/src/viso_mono.h): process(I, replace) runs
+    pushBack, matchFeatures(0), bucketFeatures and the motion estimate on the device.  private_rand=seed: draw the
+    bucketing and RANSAC samples from a private generator with glibc's srand(seed) sequence instead of libc rand()."""
+
+    def __init__(self, params=None, private_rand=None):
+        L = self.lib = lib()
+        L.svh_vo_mono_create.restype = C.c_void_p
+        L.svh_vo_mono_create.argtypes = [C.POINTER(VoMonoParams)]
+        L.svh_vo_mono_process.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_vo_mono_get_votes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_vo_mono_set_timing.argtypes = [C.c_void_p, C.c_int32]
+        L.svh_vo_mono_get_timing.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_vo_destroy.argtypes = [C.c_void_p]
+        L.svh_vo_process_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_vo_estimate_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.svh_vo_get_motion.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_vo_get_inliers.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_vo_get_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_vo_num_matches.argtypes = [C.c_void_p]
+        L.svh_vo_set_private_rand.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
+        self.params = params if params is not None else vo_mono_params()
+        self.h = L.svh_vo_mono_create(C.byref(self.params))
+        if not self.h:
+            raise SvhError(ERR_BAD_ARG, last_error())
+        if private_rand is not None:
+            L.svh_vo_set_private_rand(self.h, 1, private_rand)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.svh_vo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc):
+        if rc < 0:
+            raise SvhError(rc, last_error())
+        return bool(rc)
+
+    def process(self, I, replace=False):
+        """bool VisualOdometryMono::process(I, dims, replace) -- viso_mono.cpp:32-38"""
+        I = np.ascontiguousarray(I, np.uint8)
+        dims = (C.c_int32 * 3)(I.shape[1], I.shape[0], I.shape[1])
+        return self._check(self.lib.svh_vo_mono_process(self.h, _ptr(I), dims, int(replace)))
+
+    def process_matches(self, matches):
+        """bool VisualOdometry::process(p_matched) -- viso.h:87-91"""
+        m = np.ascontiguousarray(matches, P_MATCH)
+        return self._check(self.lib.svh_vo_process_matches(self.h, _ptr(m), len(m)))
+
+    def estimate_motion(self, matches):
+        """estimateMotion(p_matched): (ok, [rx, ry, rz, tx, ty, tz])"""
+        m = np.ascontiguousarray(matches, P_MATCH)
+        tr = np.zeros(6, np.float64)
+        return self._check(self.lib.svh_vo_estimate_motion(self.h, _ptr(m), len(m), _ptr(tr))), tr
+
+    def motion(self):
+        """getDeltaMotion(): 4x4"""
+        T = np.zeros((4, 4), np.float64)
+        self.lib.svh_vo_get_motion(self.h, _ptr(T))
+        return T
+
+    def inliers(self):
+        n = self.lib.svh_vo_get_inliers(self.h, None, 0)
+        out = np.zeros(max(n, 1), np.int32)
+        self.lib.svh_vo_get_inliers(self.h, _ptr(out), n)
+        return out[:n]
+
+    def matches(self):
+        n = self.lib.svh_vo_get_matches(self.h, None, 0)
+        out = np.zeros(max(n, 1), P_MATCH)
+        self.lib.svh_vo_get_matches(self.h, _ptr(out), n)
+        return out[:n]
+
+    def num_matches(self):
+        return self.lib.svh_vo_num_matches(self.h)
+
+    def votes(self):
+        """inlier count of every RANSAC hypothesis of the last estimate (test tap)"""
+        n = self.lib.svh_vo_mono_get_votes(self.h, None, 0)
+        out = np.zeros(max(n, 1), np.int32)
+        self.lib.svh_vo_mono_get_votes(self.h, _ptr(out), n)
+        return out[:n]
+
+    def set_timing(self, on=True):
+        self.lib.svh_vo_mono_set_timing(self.h, int(on))
+
+    def timing(self):
+        """device ms of the last estimate's phases: RANSAC, chirality, plane vote"""
+        ms = np.zeros(3, np.float64)
+        self.lib.svh_vo_mono_get_timing(self.h, _ptr(ms))
+        return ms

@@ -1,0 +1,78 @@
+// CPU check of stereo-vision_amd/csrc/mono_core.h, built by tests/test_vo_mono.py with g++ -ffp-contract=off.
+// Replays the RANSAC loop of VisualOdometryMono::estimateMotion (viso_mono.cpp:45-70) with the core's functions:
+// srand(0), normalizeFeaturePoints, then per iteration getRandomSample(N, 8) (viso.cpp:130-153, libc rand()),
+// the 8x9 SVD, the rank-2 SVD and the Sampson vote.  The SVD state is interleaved with stride S (argv[3]) exactly
+// as a kernel lane keeps it in LDS, so the index arithmetic of the device layout is exercised too.
+//   mono_core_check <matches.bin> <ransac_iters> <S> <inlier_threshold>
+// matches.bin: int32 N, N x p_match (48 bytes).  Output (stdout, binary): int32 iters, iters x int32 votes,
+// int32 n, n x int32 (the inliers of the first hypothesis with the most votes, in index order).
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <vector>
+
+#include "../../stereo-vision_amd/csrc/mono_core.h"
+
+using namespace svh::mono;
+
+int main(int argc, char** argv) {
+    if (argc < 5) return 1;
+    FILE* f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    int32_t N;
+    if (fread(&N, 4, 1, f) != 1) return 2;
+    std::vector<float> raw((size_t)N * 12);
+    if (N && fread(raw.data(), 48, N, f) != (size_t)N) return 2;
+    fclose(f);
+    const int iters = atoi(argv[2]), S = atoi(argv[3]);
+    const double thr = atof(argv[4]);
+    std::vector<float> q((size_t)N * 4);
+    for (int i = 0; i < N; i++) {
+        q[4 * i + 0] = raw[12 * i + 0];
+        q[4 * i + 1] = raw[12 * i + 1];
+        q[4 * i + 2] = raw[12 * i + 6];
+        q[4 * i + 3] = raw[12 * i + 7];
+    }
+    std::vector<int32_t> votes, best;
+    double T[18];
+    srand(0);
+    if (N >= 10 && normalize(q.data(), N, T)) {
+        std::vector<double> slab((size_t)171 * S, 0.0);
+        const int lane = S - 1;   // the last lane of S: its elements at offsets (e * S + lane)
+        Mat U{slab.data() + lane, 9, S}, V{slab.data() + 72 * S + lane, 9, S};
+        Vec w{slab.data() + 153 * S + lane, S}, rv1{slab.data() + 162 * S + lane, S};
+        for (int k = 0; k < iters; k++) {
+            int32_t chosen[8];
+            std::vector<int32_t> total(N);
+            for (int i = 0; i < N; i++) total[i] = i;
+            for (int s = 0; s < 8; s++) {
+                const int j = rand() % (int)total.size();
+                chosen[s] = total[j];
+                total.erase(total.begin() + j);
+            }
+            for (int r = 0; r < 8; r++) {
+                const float* m = &q[4 * chosen[r]];
+                f_row(m[0], m[1], m[2], m[3], &U(r, 0), S);
+            }
+            svd(8, 9, U, V, w, rv1);
+            double F[9];
+            for (int i = 0; i < 9; i++) F[i] = V(i, 8);
+            Mat U3{slab.data() + lane, 3, S}, V3{slab.data() + 72 * S + lane, 3, S};
+            for (int i = 0; i < 9; i++) U3(i / 3, i % 3) = F[i];
+            svd(3, 3, U3, V3, w, rv1);
+            rank2(U3, V3, w, F);
+            std::vector<int32_t> cur;
+            for (int i = 0; i < N; i++)
+                if (sampson_inlier(F, q[4 * i], q[4 * i + 1], q[4 * i + 2], q[4 * i + 3], thr)) cur.push_back(i);
+            votes.push_back((int32_t)cur.size());
+            if (cur.size() > best.size()) best = cur;
+        }
+    }
+    int32_t n = (int32_t)votes.size();
+    fwrite(&n, 4, 1, stdout);
+    fwrite(votes.data(), 4, votes.size(), stdout);
+    n = (int32_t)best.size();
+    fwrite(&n, 4, 1, stdout);
+    fwrite(best.data(), 4, best.size(), stdout);
+    return 0;
+}

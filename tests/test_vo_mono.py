@@ -1,0 +1,112 @@
+"""CPU: VisualOdometryMono's golden fixture (tests/golden/vo_mono.npz, make_goldens_mono.py), the numeric core of the
+device estimate (stereo-vision_amd/csrc/mono_core.h) against it, a live run of the reference when its sources are
+present, and the drop-in header include/viso_mono.h.
+
+Anchors.  In all three sequence runs frame 0 returns false with no matches (it only fills the ring buffer).  With
+the demo's parameters (demo_viso_mono.m: f 645.2, cu 635.9, cv 194.1, height 1.6, pitch -0.08) every frame returns
+false, because the median point distance exceeds motion_threshold = 100, and demo_viso_mono.m's loop then keeps the
+first frame as the previous one (replace).  With motion_threshold = 1e6 every later frame returns true, which covers
+the plane vote and the scale.  (The issue that asked for this feature quoted match counts of a different decoding
+of the frames -- 348/272 ... on frame 1; on the frames the Matcher tests use, tests/golden/full/I1_*.npz, which equal
+a plain grayscale decode of the PNGs, the reference itself gives the counts recorded here.)"""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import helpers as H
+import mono_ref as R
+
+CORE_CHECK = os.path.join(H.ROOT, "tests", "mono", "mono_core_check.cpp")
+
+
+@pytest.fixture(scope="module")
+def Z():
+    with np.load(R.GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def seq(Z, name):
+    nm, ni = Z["seq_%s_nm" % name], Z["seq_%s_ni" % name]
+    om, oi = np.concatenate([[0], np.cumsum(nm)]), np.concatenate([[0], np.cumsum(ni)])
+    return [(int(Z["seq_%s_ok" % name][k]), Z["seq_%s_matches" % name][om[k]:om[k + 1]],
+             Z["seq_%s_inliers" % name][oi[k]:oi[k + 1]], Z["seq_%s_motion" % name][k]) for k in range(7)]
+
+
+def test_goldens_load_and_anchors_hold(Z):
+    assert os.path.getsize(R.GOLDEN) < 1536 * 1024
+    assert list(Z["seq_names"]) == ["demo", "still", "alt"]
+    for name in Z["seq_names"]:
+        frames = seq(Z, name)
+        assert frames[0][0] == 0 and len(frames[0][1]) == 0
+        for ok, m, inl, T in frames:
+            assert len(inl) <= len(m) and (len(inl) == 0 or (np.all(np.diff(inl) > 0) and inl[-1] < len(m)))
+    assert [f[0] for f in seq(Z, "demo")] == [0] * 7
+    assert all(np.array_equal(f[3], np.eye(4)) for f in seq(Z, "demo"))   # no estimate ever succeeded
+    assert [f[0] for f in seq(Z, "still")] == [0] + [1] * 6
+    assert [f[0] for f in seq(Z, "alt")] == [0] + [1] * 6
+    for name in ("still", "alt"):
+        for ok, m, inl, T in seq(Z, name)[1:]:
+            assert np.allclose(T[:3, :3] @ T[:3, :3].T, np.eye(3), atol=1e-9) and np.linalg.norm(T[:3, 3]) > 0
+    # estimate-only cases: the early returns and the plane-vote fall-back are all present
+    ok = {n: int(Z["est_%s_ok" % n]) for n in Z["est_names"]}
+    assert ok["syn9"] == 0 and len(Z["est_syn9_votes"]) == 0                  # N < 10
+    assert ok["identical"] == 0 and len(Z["est_identical_votes"]) == 0        # normalisation fails
+    assert ok["syn10"] == 0 and len(Z["est_syn10_inliers"]) < 10              # too few inliers
+    assert ok["few_positive"] == 0
+    assert all(ok["syn%d" % n] == 1 for n in (200, 2000, 5000)) and ok["syn350_alt"] == 1 and ok["no_plane"] == 1
+    for n in Z["est_names"]:
+        v = Z["est_%s_votes" % n]
+        if len(v):
+            assert len(Z["est_%s_inliers" % n]) == v.max()
+
+
+def run_core_check(exe, tmp, m, pvec, S):
+    path = os.path.join(tmp, "m.bin")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<i", len(m)) + np.ascontiguousarray(m, H.P_MATCH).tobytes())
+    b = subprocess.run([exe, path, str(int(pvec[5])), str(S), repr(float(pvec[6]))], check=True,
+                       capture_output=True).stdout
+    n = struct.unpack_from("<i", b)[0]
+    votes = np.frombuffer(b, np.int32, n, 4)
+    k = struct.unpack_from("<i", b, 4 + 4 * n)[0]
+    return votes, np.frombuffer(b, np.int32, k, 8 + 4 * n)
+
+
+def test_mono_core_reproduces_reference_votes_and_inliers(Z, tmp_path):
+    """mono_core.h built by g++ -ffp-contract=off: the count of every RANSAC hypothesis and the winner's inlier set
+    equal the reference's bit for bit, with the SVD state contiguous (S = 1) and interleaved as in LDS (S = 32)"""
+    exe = str(tmp_path / "mono_core_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-o", exe, CORE_CHECK])
+    for name in Z["est_names"]:
+        for S in (1, 32):
+            votes, inl = run_core_check(exe, str(tmp_path), Z["est_%s_matches" % name], Z["est_%s_params" % name], S)
+            assert np.array_equal(votes, Z["est_%s_votes" % name]), (name, S)
+            if len(votes):   # (the reference's inlier set when the loop ran: the first hypothesis with the most)
+                assert np.array_equal(inl, Z["est_%s_inliers" % name]), (name, S)
+
+
+@pytest.mark.skipif(not R.have_ref(), reason="the reference's sources are not on this machine")
+def test_live_reference_equals_goldens(Z):
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = R.build_harness(tmp)
+        R.write_frames(tmp)
+        for name, p, demo_replace in R.SEQUENCES:
+            got = R.run_sequence(exe, tmp, p, demo_replace)
+            for (ok, m, inl, T), (gok, gm, ginl, gT) in zip(got, seq(Z, name)):
+                assert ok == gok and m.tobytes() == gm.tobytes() and np.array_equal(inl, ginl)
+                assert T.tobytes() == gT.tobytes()
+        for name, pvec, m in R.estimate_cases():
+            assert m.tobytes() == Z["est_%s_matches" % name].tobytes(), name
+            ok, inl, T, votes = R.run_estimate(exe, tmp, pvec, m)
+            assert ok == Z["est_%s_ok" % name] and np.array_equal(inl, Z["est_%s_inliers" % name])
+            assert T.tobytes() == Z["est_%s_motion" % name].tobytes() and np.array_equal(votes, Z["est_%s_votes" % name])
+
+
+def test_dropin_compiles_against_include_alone(tmp_path):
+    """a caller written against libviso2/src/viso_mono.h (the MEX's sequence) compiles with include/ only"""
+    subprocess.check_call(["g++", "-O2", "-std=c++11", "-Wall", "-I" + os.path.join(H.ROOT, "include"), "-c",
+                           os.path.join(H.ROOT, "tests", "mono", "mono_dropin.cpp"), "-o", str(tmp_path / "d.o")])

@@ -154,6 +154,29 @@ void vlaunch_estimate(void*, const svh_p_match*, int N, const int32_t*, int, con
     for (int k = 0; k < 6; k++) out->tr[k] = 1e-3 * (k + 1);
     for (int i = 0; i < N / 2; i++) out_inliers[i] = 2 * i;
 }
+// VisualOdometryMono (vo_mono_engine.cpp): every second match an inlier of hypothesis 0, candidate 0 puts the points
+// in front at growing depth
+void mlaunch_ransac(void*, const float*, int32_t N, const int32_t*, int32_t iters, double, double*, int32_t*,
+                    int32_t* out_sel, uint8_t* out_flags, int32_t* out_counts) {
+    for (int32_t h = 0; h < iters; h++) out_counts[h] = h == 0 ? (N + 1) / 2 : 0;
+    for (int32_t i = 0; i < N; i++) out_flags[i] = i % 2 == 0;
+    out_sel[0] = 0;
+    out_sel[1] = (N + 1) / 2;
+}
+void mlaunch_chiral(void*, const float*, int32_t N, const double*, double*, uint8_t*, double* out_X,
+                    int32_t* out_cand) {
+    out_cand[0] = 0;
+    for (int k = 0; k < 4; k++) out_cand[1 + k] = k == 0 ? N : 0;
+    for (int32_t i = 0; i < N; i++) {
+        out_X[i] = 0.1 * i;
+        out_X[N + i] = 0.5;
+        out_X[2 * N + i] = 1.0 + i;
+        out_X[3 * N + i] = 1.0;
+    }
+}
+void mlaunch_plane(void*, const double* d, int32_t n, double, double, double* sums) {
+    for (int32_t i = 0; i < n; i++) sums[i] = 1.0 + (d[i] > 0);
+}
 }  // namespace svh
 
 // ---------------------------------------------------------------- driver
