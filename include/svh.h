@@ -563,6 +563,49 @@ int32_t svh_vo_mono_get_votes(svh_vo* v, int32_t* out, int32_t cap);
 void    svh_vo_mono_set_timing(svh_vo* v, int32_t on);
 int32_t svh_vo_mono_get_timing(svh_vo* v, double* ms3);
 
+/* ------------------------------------------------------------------------
+ * Reconstruction -- libviso2/src/reconstruction.h:35-69: multi-view 3-D points from monocular flow matches and the
+ * egomotion between the two frames.  The track bookkeeping (reconstruction.cpp:59-126) runs on the host; every
+ * track lost in an update is triangulated, classified, refined (Gauss-Newton over all its frames) and tested on the
+ * device, and the accepted points are appended, in the reference's order, to an array that stays on the device.
+ * ------------------------------------------------------------------------ */
+typedef struct svh_recon svh_recon;
+/* what became of a lost track, in the order update() tests (reconstruction.cpp:131-141) */
+enum {
+    SVH_RECON_TOO_SHORT = 0,      /* fewer than min_track_length frames                       */
+    SVH_RECON_INIT_FAILED = 1,    /* initPoint: point at infinity                             */
+    SVH_RECON_TYPE_BELOW = 2,     /* pointType below point_type (or not visible)              */
+    SVH_RECON_REFINE_FAILED = 3,  /* refinePoint: singular, or not converged after 22 updates */
+    SVH_RECON_TOO_FAR = 4,        /* pointDistance >= max_dist                                */
+    SVH_RECON_ANGLE_SMALL = 5,    /* rayAngle not above min_angle                             */
+    SVH_RECON_ACCEPTED = 6        /* appended to the points                                   */
+};
+svh_recon* svh_recon_create(void);                                   /* Reconstruction() */
+void       svh_recon_destroy(svh_recon*);
+/* setCalibration(f,cu,cv) -- reconstruction.cpp:40-57.  Once per object: a second call returns SVH_ERR_BAD_ARG (in
+ * the reference it pushes a second P_total[0] and misaligns every later frame). */
+int32_t    svh_recon_set_calibration(svh_recon*, double f, double cu, double cv);
+/* update(p_matched,Tr,point_type,min_track_length,max_dist,min_angle) -- reconstruction.cpp:59-151; of a match only
+ * u1p v1p i1p u1c v1c i1c are read; Tr: 4x4 row major (getDeltaMotion()); the reference's defaults are 1, 2, 30, 2.
+ * n == 0 is a valid update (every track is lost).  SVH_ERR_BAD_ARG before svh_recon_set_calibration (undefined in
+ * the reference: P_total is empty) and for a negative feature index.  After SVH_ERR_HIP the object is what it was
+ * before the call. */
+int32_t    svh_recon_update(svh_recon*, const svh_p_match* m, int32_t n, const double Tr[16],
+                            int32_t point_type, int32_t min_track_length, double max_dist, double min_angle);
+int32_t    svh_recon_num_points(svh_recon*);
+/* getPoints(): x y z per point.  _get_points copies up to cap points to the host and returns the number there are;
+ * _get_points_device hands out the resident array itself (no copy; valid until the next update) */
+int32_t    svh_recon_get_points(svh_recon*, float* xyz, int32_t cap);
+int32_t    svh_recon_get_points_device(svh_recon*, const float** xyz);
+int32_t    svh_recon_num_tracks(svh_recon*);                         /* active tracks */
+/* the tracks lost in the last update, in the reference's order: SVH_RECON_* code and the point as far as it got (0 0
+ * 0 before initPoint succeeded); copies up to cap, returns their number */
+int32_t    svh_recon_get_outcomes(svh_recon*, int32_t* code, float* xyz, int32_t cap);
+/* ms of the last update, recorded only after svh_recon_set_timing(r, 1): host bookkeeping up to the first launch,
+ * device time (uploads + kernels, HIP events), copy-back of the outcomes after the wait; returns 3 */
+void       svh_recon_set_timing(svh_recon*, int32_t on);
+int32_t    svh_recon_get_timing(svh_recon*, double* ms3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,5 +113,19 @@ void mono_clear(MonoVo* M);   // forget the last estimate's votes and times
 void mono_set_timing(MonoVo* M, bool on);
 int32_t mono_timing(MonoVo* M, double* ms3);
 
+// Reconstruction (recon_engine.cpp, recon_kernels.hip).  k_recon_tracks + k_recon_compact over the n_lost tracks
+// lost in one update: offs (n_lost + 1) / first (n_lost) / px (2 n_px floats) are the CSR of their pixels and first
+// frames, order an optional lane -> track permutation (NULL: identity), frames the per-frame records of recon_core.h
+// (FRAME_STRIDE doubles each).  code / xyz (device, n_lost): outcome and point per track; the ACCEPTED points are
+// appended in track order to points[3 n_points ...] (room for n_lost more); out_code, out_xyz, out_count = {new
+// number of points} are pinned host memory.
+namespace recon {
+struct Settings;
+}
+void rlaunch_tracks(void* stream, const int32_t* offs, const int32_t* first, const int32_t* order, const float* px,
+                    int32_t n_lost, int32_t n_px, const double* frames, int32_t n_frames, const recon::Settings& s,
+                    int32_t* code, float* xyz, float* points, int32_t n_points, int32_t* out_code, float* out_xyz,
+                    int32_t* out_count);
+
 }  // namespace svh
 #endif

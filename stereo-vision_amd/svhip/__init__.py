@@ -558,3 +558,96 @@ class VoMono:
         ms = np.zeros(3, np.float64)
         self.lib.svh_vo_mono_get_timing(self.h, _ptr(ms))
         return ms
+
+
+# ---------------------------------------------------------------------------
+# Reconstruction (svh_recon_*, include/svh.h; libviso2/src/reconstruction.h)
+# ---------------------------------------------------------------------------
+RECON_CODES = ["TOO_SHORT", "INIT_FAILED", "TYPE_BELOW", "REFINE_FAILED", "TOO_FAR", "ANGLE_SMALL", "ACCEPTED"]
+RECON_ACCEPTED = 6
+
+
+class Reconstruction:
+    """Drop-in for the reference class Reconstruction (libviso2/src/reconstruction.h): set_calibration(f, cu, cv)
+    once, update(matches, Tr, ...) per frame pair, points().  The tracks live on the host; every lost track is
+    triangulated, refined and tested on the device and the accepted points stay there."""
+
+    def __init__(self):
+        L = self.lib = lib()
+        L.svh_recon_create.restype = C.c_void_p
+        L.svh_recon_destroy.argtypes = [C.c_void_p]
+        L.svh_recon_set_calibration.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
+        L.svh_recon_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_double, C.c_double]
+        L.svh_recon_num_points.argtypes = [C.c_void_p]
+        L.svh_recon_get_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_recon_get_points_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.svh_recon_num_tracks.argtypes = [C.c_void_p]
+        L.svh_recon_get_outcomes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_recon_set_timing.argtypes = [C.c_void_p, C.c_int32]
+        L.svh_recon_get_timing.argtypes = [C.c_void_p, C.c_void_p]
+        self.h = L.svh_recon_create()
+        if not self.h:
+            raise SvhError(ERR_BAD_ARG, last_error())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.svh_recon_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _check(self, rc):
+        if rc < 0:
+            raise SvhError(rc, last_error())
+        return rc
+
+    def set_calibration(self, f, cu, cv):
+        """setCalibration(f, cu, cv); a second call is refused (SvhError, ERR_BAD_ARG)"""
+        self._check(self.lib.svh_recon_set_calibration(self.h, f, cu, cv))
+
+    def update(self, matches, Tr, point_type=1, min_track_length=2, max_dist=30.0, min_angle=2.0):
+        """update(p_matched, Tr, point_type, min_track_length, max_dist, min_angle) -- reconstruction.cpp:59-151"""
+        m = np.ascontiguousarray(matches, P_MATCH)
+        T = np.ascontiguousarray(Tr, np.float64)
+        if T.shape != (4, 4):
+            raise SvhError(ERR_BAD_ARG, "Tr must be 4x4")
+        self._check(self.lib.svh_recon_update(self.h, _ptr(m) if len(m) else None, len(m), _ptr(T), int(point_type),
+                                              int(min_track_length), float(max_dist), float(min_angle)))
+
+    def num_points(self):
+        return self.lib.svh_recon_num_points(self.h)
+
+    def num_tracks(self):
+        """active tracks"""
+        return self.lib.svh_recon_num_tracks(self.h)
+
+    def points(self):
+        """getPoints(): (n, 3) float32, copied from the device"""
+        n = self.num_points()
+        out = np.zeros((max(n, 1), 3), np.float32)
+        self._check(self.lib.svh_recon_get_points(self.h, _ptr(out), n))
+        return out[:n]
+
+    def points_device(self):
+        """(device address of the resident x y z array, number of points); valid until the next update"""
+        p = C.c_void_p()
+        n = self._check(self.lib.svh_recon_get_points_device(self.h, C.byref(p)))
+        return p.value, n
+
+    def outcomes(self):
+        """the tracks lost in the last update, in order: (codes int32, points (n, 3) float32)"""
+        n = self.lib.svh_recon_get_outcomes(self.h, None, None, 0)
+        code, xyz = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 3), np.float32)
+        self.lib.svh_recon_get_outcomes(self.h, _ptr(code), _ptr(xyz), n)
+        return code[:n], xyz[:n]
+
+    def set_timing(self, on=True):
+        self.lib.svh_recon_set_timing(self.h, int(on))
+
+    def timing(self):
+        """ms of the last update: host bookkeeping, device (uploads + kernels), copy-back of the outcomes"""
+        ms = np.zeros(3, np.float64)
+        self.lib.svh_recon_get_timing(self.h, _ptr(ms))
+        return ms

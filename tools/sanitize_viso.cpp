@@ -8,7 +8,8 @@
 //                                              -fsanitize=address,undefined and runs both, K = 16 sequences
 // What is checked: data races and memory errors of K VisualOdometryStereo objects driven from K threads at
 // once (SURVEY 8(e) "replicas only"), one thread that creates and destroys Matchers meanwhile, and two threads
-// that each drive K/2 objects in lockstep through svh_vo_process_batch (recorder, helper pool, phase barriers).
+// that each drive K/2 objects in lockstep through svh_vo_process_batch (recorder, helper pool, phase barriers), and
+// two threads that each drive a Reconstruction (track table, undo of a failed update, growth of the resident arrays).
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -177,6 +178,21 @@ void mlaunch_chiral(void*, const float*, int32_t N, const double*, double*, uint
 void mlaunch_plane(void*, const double* d, int32_t n, double, double, double* sums) {
     for (int32_t i = 0; i < n; i++) sums[i] = 1.0 + (d[i] > 0);
 }
+// Reconstruction (recon_engine.cpp): every third lost track of two or more frames is accepted at its first pixel
+void rlaunch_tracks(void*, const int32_t* offs, const int32_t*, const int32_t*, const float* px, int32_t n_lost, int32_t,
+                    const double*, int32_t, const recon::Settings&, int32_t* code, float* xyz, float* points,
+                    int32_t n_points, int32_t* out_code, float* out_xyz, int32_t* out_count) {
+    for (int32_t t = 0; t < n_lost; t++) {
+        const bool take = t % 3 == 0 && offs[t + 1] - offs[t] >= 2;
+        code[t] = out_code[t] = take ? 6 : 5;
+        for (int k = 0; k < 3; k++) xyz[3 * t + k] = out_xyz[3 * t + k] = k < 2 ? px[2 * offs[t] + k] : 1.f;
+        if (take) {
+            for (int k = 0; k < 3; k++) points[3 * (size_t)n_points + k] = xyz[3 * t + k];
+            n_points++;
+        }
+    }
+    out_count[0] = n_points;
+}
 }  // namespace svh
 
 // ---------------------------------------------------------------- driver
@@ -276,6 +292,34 @@ int main(int argc, char** argv) {
     };
     th.emplace_back(lockstep, 1);
     th.emplace_back(lockstep, 2);
+    // two Reconstruction objects on threads of their own: tracks that live one to five frames, an empty update
+    auto reconstruct = [&](int id) {
+        svh_recon* r = svh_recon_create();
+        if (!r) { bad++; return; }
+        const double Tr[16] = {1, 0, 0, 0.05, 0, 1, 0, 0, 0, 0, 1, -0.8, 0, 0, 0, 1};
+        if (svh_recon_update(r, nullptr, 0, Tr, 1, 2, 30, 2) != SVH_ERR_BAD_ARG) bad++;   // not calibrated yet
+        check(svh_recon_set_calibration(r, 645.2, 635.9, 194.1));
+        if (svh_recon_set_calibration(r, 645.2, 635.9, 194.1) != SVH_ERR_BAD_ARG) bad++;
+        const int n = 600;
+        for (int f = 0; f < 3 * frames; f++) {
+            std::vector<svh_p_match> m;
+            for (int i = 0; i < n && f % 7 != 5; i++) {
+                if (svh::mix((uint32_t)(i + 131 * f + 7 * id)) % 5u == 0) continue;   // this feature is not matched now
+                svh_p_match q;
+                memset(&q, 0, sizeof(q));
+                q.u1p = 10.f + i + f; q.v1p = 20.f + (i % 37); q.i1p = i;
+                q.u1c = q.u1p + 1.f;  q.v1c = q.v1p;           q.i1c = i;
+                m.push_back(q);
+            }
+            check(svh_recon_update(r, m.data(), (int32_t)m.size(), Tr, 1, 2, 30, 2));
+            std::vector<float> p(3 * (size_t)svh_recon_num_points(r) + 3);
+            check(svh_recon_get_points(r, p.data(), svh_recon_num_points(r)));
+            matches += svh_recon_num_tracks(r);
+        }
+        svh_recon_destroy(r);
+    };
+    th.emplace_back(reconstruct, 1);
+    th.emplace_back(reconstruct, 2);
     for (std::thread& t : th) t.join();
     printf("sanitize_viso: %d sequences x %d frames + 1 Matcher thread + 2 lockstep threads, %ld matches seen, %d failures"
            ", %ld injected HIP failures reported\n", K, frames, matches.load(), bad.load(), injected.load());
