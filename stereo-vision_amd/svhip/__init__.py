@@ -651,3 +651,150 @@ class Reconstruction:
         ms = np.zeros(3, np.float64)
         self.lib.svh_recon_get_timing(self.h, _ptr(ms))
         return ms
+
+
+# ---------------------------------------------------------------------------
+# PlaneEstimation (svh_plane_*, include/svh_plane.h; stereomapper/planeestimation.h)
+# ---------------------------------------------------------------------------
+PLANE_NO_POINTS, PLANE_FEW_INLIERS = 2, 3
+
+
+class PlaneParams(C.Structure):
+    """svh_plane_params (include/svh_plane.h): the reference's constants as parameters"""
+    _fields_ = [("num_samples", C.c_int32), ("step_size", C.c_int32), ("max_draws", C.c_int32),
+                ("roi", C.c_int32 * 4), ("min_dist", C.c_float), ("d_threshold", C.c_double)]
+
+
+def _plane_bind(L):
+    if getattr(L, "_plane_bound", False):
+        return
+    L.svh_plane_params_default.argtypes = [C.c_void_p]
+    L.svh_plane_params_default.restype = None
+    L.svh_plane_create.restype = C.c_void_p
+    L.svh_plane_create.argtypes = [C.c_void_p]
+    L.svh_plane_destroy.argtypes = [C.c_void_p]
+    L.svh_plane_destroy.restype = None
+    L.svh_plane_release.argtypes = [C.c_void_p]
+    L.svh_plane_release.restype = C.c_int64
+    L.svh_plane_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                     C.c_float, C.c_float, C.c_float, C.c_uint32]
+    L.svh_plane_estimate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    for name in ("svh_plane_get_plane_dsi", "svh_plane_get_plane_euclidean", "svh_plane_get_transformation"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+        getattr(L, name).restype = None
+    L.svh_plane_get_pitch.argtypes = [C.c_void_p]
+    L.svh_plane_get_pitch.restype = C.c_float
+    L.svh_plane_get_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.svh_plane_get_hypotheses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.svh_plane_get_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.svh_plane_set_timing.argtypes = [C.c_void_p, C.c_int32]
+    L.svh_plane_set_timing.restype = None
+    L.svh_plane_get_timing.argtypes = [C.c_void_p, C.c_void_p]
+    L._plane_bound = True
+
+
+class PlaneEstimation:
+    """Drop-in for the reference class PlaneEstimation (stereomapper/planeestimation.h): estimate(D, ...) is
+    computeTransformationFromDisparityMap with the draws of srand(seed); D is a host array or a device address."""
+
+    def __init__(self, **params):
+        L = self.lib = lib()
+        _plane_bind(L)
+        P = PlaneParams()
+        L.svh_plane_params_default(C.byref(P))
+        for k, v in params.items():
+            if k == "roi":
+                P.roi = (C.c_int32 * 4)(*[int(x) for x in v])
+            else:
+                setattr(P, k, v)
+        self.h = L.svh_plane_create(C.byref(P))
+        if not self.h:
+            raise SvhError(ERR_BAD_ARG, last_error())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.svh_plane_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def estimate(self, D, width=None, height=None, step=None, f=721.5, cu=609.6, cv=172.9, base=0.54, seed=0):
+        """D: (height, step) float32 host array, or an int device address (then width, height and step are needed).
+        Returns OK, PLANE_NO_POINTS or PLANE_FEW_INLIERS; raises SvhError on a negative status."""
+        if isinstance(D, (int, np.integer)):
+            addr, dev = int(D), 1
+        else:
+            self._keep = D = np.ascontiguousarray(D, np.float32)
+            height = D.shape[0] if height is None else height
+            step = D.shape[1] if step is None else step
+            width = step if width is None else width
+            addr, dev = D.ctypes.data, 0
+        rc = self.lib.svh_plane_estimate(self.h, addr, dev, int(width), int(height), int(step), f, cu, cv, base,
+                                         int(seed) & 0xFFFFFFFF)
+        if rc < 0:
+            raise SvhError(rc, last_error())
+        return rc
+
+    @staticmethod
+    def estimate_batch(objs, addrs, width, height, step, f=721.5, cu=609.6, cv=172.9, base=0.54, seeds=None):
+        """svh_plane_estimate_batch over device-resident maps; returns the list of statuses"""
+        n = len(objs)
+        L = objs[0].lib
+        hs = (C.c_void_p * n)(*[o.h for o in objs])
+        ds = (C.c_void_p * n)(*[int(a) for a in addrs])
+        sd = np.ascontiguousarray(seeds if seeds is not None else np.zeros(n), np.uint32)
+        st = np.zeros(n, np.int32)
+        rc = L.svh_plane_estimate_batch(hs, ds, n, int(width), int(height), int(step), f, cu, cv, base, _ptr(sd),
+                                        _ptr(st))
+        if rc < 0:
+            raise SvhError(rc, last_error())
+        return st.tolist()
+
+    def _vec(self, fn, n):
+        out = np.zeros(n, np.float64)
+        fn(self.h, _ptr(out))
+        return out
+
+    def plane_dsi(self):
+        return self._vec(self.lib.svh_plane_get_plane_dsi, 3)
+
+    def plane_euclidean(self):
+        return self._vec(self.lib.svh_plane_get_plane_euclidean, 3)
+
+    def transformation(self):
+        return self._vec(self.lib.svh_plane_get_transformation, 16).reshape(4, 4)
+
+    def pitch(self):
+        return np.float32(self.lib.svh_plane_get_pitch(self.h))
+
+    def taps(self):
+        """the last call as a dict shaped like the reference harness' record (tests/plane_ref.py)"""
+        L = self.lib
+        n = L.svh_plane_get_list(self.h, None, 0)
+        lst = np.zeros((max(n, 1), 3), np.float32)
+        L.svh_plane_get_list(self.h, _ptr(lst), n)
+        S = L.svh_plane_get_hypotheses(self.h, None, None, None, 0)
+        planes = np.zeros((max(S, 1), 3), np.float64)
+        draws, votes = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
+        L.svh_plane_get_hypotheses(self.h, _ptr(planes), _ptr(draws), _ptr(votes), S)
+        best = C.c_int32(-1)
+        nin = L.svh_plane_get_best(self.h, C.byref(best), None, 0)
+        inl = np.zeros(max(nin, 1), np.int32)
+        L.svh_plane_get_best(self.h, C.byref(best), _ptr(inl), nin)
+        return {"plane_d": self.plane_dsi(), "plane_e": self.plane_euclidean(), "H": self.transformation(),
+                "pitch": self.pitch(), "list": lst[:n], "planes": planes[:S], "draws": draws[:S], "votes": votes[:S],
+                "best": best.value, "inliers": inl[:nin]}
+
+    def release(self):
+        return self.lib.svh_plane_release(self.h)
+
+    def set_timing(self, on=True):
+        self.lib.svh_plane_set_timing(self.h, int(on))
+
+    def timing(self):
+        """ms of the last call: see svh_plane_get_timing (include/svh_plane.h)"""
+        ms = np.zeros(7, np.float64)
+        self.lib.svh_plane_get_timing(self.h, _ptr(ms))
+        return ms

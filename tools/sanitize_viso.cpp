@@ -9,7 +9,9 @@
 // What is checked: data races and memory errors of K VisualOdometryStereo objects driven from K threads at
 // once (SURVEY 8(e) "replicas only"), one thread that creates and destroys Matchers meanwhile, and two threads
 // that each drive K/2 objects in lockstep through svh_vo_process_batch (recorder, helper pool, phase barriers), and
-// two threads that each drive a Reconstruction (track table, undo of a failed update, growth of the resident arrays).
+// two threads that each drive a Reconstruction (track table, undo of a failed update, growth of the resident arrays),
+// and two threads that each drive PlaneEstimation objects (single calls on host maps and a batch of three; the cache
+// of raw draws, the transaction of a failed call, svh_plane_release).
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -23,7 +25,9 @@
 #include <thread>
 #include <vector>
 
+#include "../include/svh_plane.h"
 #include "../stereo-vision_amd/csrc/matcher_internal.h"
+#include "../stereo-vision_amd/csrc/plane_internal.h"
 #include "../stereo-vision_amd/csrc/vo_internal.h"
 
 // ---------------------------------------------------------------- stub HIP runtime
@@ -193,6 +197,45 @@ void rlaunch_tracks(void*, const int32_t* offs, const int32_t*, const int32_t*, 
     }
     out_count[0] = n_points;
 }
+// PlaneEstimation (plane_engine.cpp): the kernels' work with plane_core.h on the host ("device" memory is host memory)
+void planelaunch_grid(void*, const PlaneDev& P, int32_t nmaps, const plane::Lattice& L, int32_t step, int32_t row0) {
+    for (int32_t m = 0; m < nmaps; m++) {
+        int32_t n = 0;
+        for (int32_t t = 0; t < L.nu * L.nv; t++) {
+            const int32_t u = plane::cell_u(L, t), v = plane::cell_v(L, t);
+            const float d = P.maps[m][(size_t)(v - row0) * step + u];
+            if (!plane::cell_kept(d)) continue;
+            const size_t at = (size_t)m * P.cap + n++;
+            P.lu[at] = (float)u; P.lv[at] = (float)v; P.ld[at] = d;
+        }
+        P.n_list[m] = n;
+    }
+}
+void planelaunch_vote(void*, const PlaneDev& P, int32_t nmaps, int32_t, double thr) {
+    for (int32_t m = 0; m < nmaps; m++) {
+        const size_t o = (size_t)m * P.cap;
+        const int32_t n = P.n_list[m];
+        int32_t best = -1, best_count = 0;
+        for (int32_t h = 0; h < P.S; h++) {
+            const int32_t* s = P.samples + ((size_t)m * P.S + h) * 4;
+            double* abc = P.planes + ((size_t)m * P.S + h) * 3;
+            plane::fit_indexed(P.lu + o, P.lv + o, P.ld + o, s + 1, s[0], abc);
+            int32_t c = 0;
+            for (int32_t i = 0; i < n; i++)
+                c += plane::is_inlier(abc[0], abc[1], abc[2], P.lu[o + i], P.lv[o + i], P.ld[o + i], thr);
+            P.counts[(size_t)m * P.S + h] = c;
+            if (c > best_count) { best_count = c; best = h; }
+        }
+        int32_t k = 0;
+        if (best >= 0) {
+            const double* abc = P.planes + ((size_t)m * P.S + best) * 3;
+            for (int32_t i = 0; i < n; i++)
+                if (plane::is_inlier(abc[0], abc[1], abc[2], P.lu[o + i], P.lv[o + i], P.ld[o + i], thr)) P.inl[o + k++] = i;
+        }
+        P.sel[2 * m] = best;
+        P.sel[2 * m + 1] = k;
+    }
+}
 }  // namespace svh
 
 // ---------------------------------------------------------------- driver
@@ -320,6 +363,38 @@ int main(int argc, char** argv) {
     };
     th.emplace_back(reconstruct, 1);
     th.emplace_back(reconstruct, 2);
+    // two threads with PlaneEstimation objects: a road (d grows with v) with a hashed ripple, host maps, changing
+    // seeds, a batch of three objects over the same map, release in between
+    auto planes = [&](int id) {
+        const int w = 320, h = 120;
+        std::vector<float> D((size_t)w * h);
+        for (int v = 0; v < h; v++)
+            for (int u = 0; u < w; u++)
+                D[(size_t)v * w + u] =
+                    v < 50 ? 0.f : 0.3f * (v - 45) + 0.001f * (float)(svh::mix((uint32_t)(u + w * v + id)) % 1000u);
+        svh_plane_params prm;
+        svh_plane_params_default(&prm);
+        prm.num_samples = 200;
+        svh_plane* p[3] = {svh_plane_create(&prm), svh_plane_create(&prm), svh_plane_create(&prm)};
+        if (!p[0] || !p[1] || !p[2]) { bad++; return; }
+        if (svh_plane_estimate(p[0], D.data(), 0, w, h, w - 1, 700, 160, 60, 0.5f, 1) != SVH_ERR_BAD_ARG) bad++;
+        for (int f = 0; f < frames; f++) {
+            const int32_t rc = svh_plane_estimate(p[0], D.data(), 0, w, h, w, 700, 160, 60, 0.5f, (uint32_t)(f / 2 + id));
+            check(rc);
+            double abc[3];
+            svh_plane_get_plane_dsi(p[0], abc);
+            if (rc == SVH_OK && !(abc[1] > 0.2 && abc[1] < 0.4)) bad++;
+            const float* maps[3] = {D.data(), D.data(), D.data()};
+            const uint32_t seeds[3] = {1, 2, (uint32_t)f};
+            int32_t st[3];
+            check(svh_plane_estimate_batch(p, maps, 3, w, h, w, 700, 160, 60, 0.5f, seeds, st));
+            if (f % 4 == 3) (void)svh_plane_release(p[f % 3]);
+            matches += svh_plane_get_best(p[1], nullptr, nullptr, 0);
+        }
+        for (svh_plane* q : p) svh_plane_destroy(q);
+    };
+    th.emplace_back(planes, 1);
+    th.emplace_back(planes, 2);
     for (std::thread& t : th) t.join();
     printf("sanitize_viso: %d sequences x %d frames + 1 Matcher thread + 2 lockstep threads, %ld matches seen, %d failures"
            ", %ld injected HIP failures reported\n", K, frames, matches.load(), bad.load(), injected.load());
