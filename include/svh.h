@@ -531,7 +531,10 @@ svh_matcher* svh_vo_matcher(svh_vo* v);                          /* the owned Ma
  *   VisualOdometryMono::parameters          libviso2/src/viso_mono.h:30-45
  * A mono object is an svh_vo: svh_vo_process_matches, svh_vo_estimate_motion, svh_vo_get_motion / _matches /
  * _inliers, svh_vo_num_matches, svh_vo_get_gain, svh_vo_set_private_rand, svh_vo_matcher and svh_vo_destroy work on
- * it as on a stereo object; svh_vo_process and the batch, prefetch and next entries return SVH_ERR_BAD_ARG.
+ * it as on a stereo object; svh_vo_process and the stereo batch, prefetch and next entries (svh_vo_process_batch,
+ * svh_vo_prefetch_batch, svh_vo_process_next_batch) return SVH_ERR_BAD_ARG for it.  K mono objects run in lockstep
+ * through their own entries, svh_vo_mono_process_batch / _prefetch_batch / _process_next_batch /
+ * _process_matches_batch below, which in turn return SVH_ERR_BAD_ARG for a stereo object.
  * =========================================================================== */
 typedef struct svh_vo_mono_params {
     svh_matcher_params match;      /* parameters::match                                       */
@@ -562,6 +565,34 @@ int32_t svh_vo_mono_get_votes(svh_vo* v, int32_t* out, int32_t cap);
  * recorded only after svh_vo_mono_set_timing(v, 1); returns the number of entries written (3) */
 void    svh_vo_mono_set_timing(svh_vo* v, int32_t on);
 int32_t svh_vo_mono_get_timing(svh_vo* v, double* ms3);
+/* svh_vo_mono_process for K mono objects in lockstep, one frame each (the multi-sequence form of the loop of
+ * demo_viso_mono.m; no counterpart in the reference): batched Matcher steps with one camera, then the K estimates walk
+ * through their three device phases together -- per phase one launch per kernel over the objects still in the
+ * estimate and ONE stream wait, the host steps in between on the library's helper threads.  replace: K entries, one
+ * per object (the demo loop sets replace = !ok per sequence), or NULL for all 0.  ok[i] (optional) receives what
+ * svh_vo_mono_process would have returned for object i (1 / 0); the call returns the number of objects whose motion
+ * was updated, or the first negative SVH_ERR_*.  All random numbers of a mono frame (bucketing, RANSAC samples) are
+ * drawn on the host in front of the first device phase: with libc rand() object by object in batch order, which is
+ * the order of K svh_vo_mono_process calls, so with the same srand() the results are bit-identical to that loop;
+ * with private streams on all objects (svh_vo_set_private_rand) that preparation runs in parallel.  Objects that
+ * differ in parameters or device (or K = 1) are processed one after the other in batch order.  SVH_ERR_BAD_ARG for a
+ * null or stereo object, the same object twice, K < 0, null dims.  After SVH_ERR_HIP nothing of the call is in flight
+ * and every object is usable.  Every getter works afterwards as after the single call; svh_vo_mono_get_timing of an
+ * object that ran in lockstep reports the device time of each phase FOR THE WHOLE BATCH (the phases are shared
+ * launches), the same three values for every object that reached the phase. */
+int32_t svh_vo_mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I, const int32_t* dims,
+                                  const int32_t* replace, int32_t* ok);
+/* The pipelined loop, as svh_vo_prefetch_batch / svh_vo_process_next_batch: svh_vo_mono_prefetch_batch hands over the
+ * FIRST frame (returns without waiting; the images must stay unchanged until the frame is taken), then per frame
+ * svh_vo_mono_process_next_batch processes the frame handed over before and hands over the next one (next_I; NULL
+ * after the last frame).  svh_vo_mono_process_batch with I = NULL also takes a frame handed over before. */
+int32_t svh_vo_mono_prefetch_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I, const int32_t* dims);
+int32_t svh_vo_mono_process_next_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* next_I,
+                                       const int32_t* dims, const int32_t* replace, int32_t* ok);
+/* svh_vo_process_matches (VisualOdometry::process(p_matched)) for K mono objects, each with its own n[i] matches: the
+ * estimates alone in lockstep, for a caller with its own tracker.  ok and the return value as above. */
+int32_t svh_vo_mono_process_matches_batch(svh_vo* const* vs, int32_t K, const svh_p_match* const* matches,
+                                          const int32_t* n, int32_t* ok);
 
 /* ------------------------------------------------------------------------
  * Reconstruction -- libviso2/src/reconstruction.h:35-69: multi-view 3-D points from monocular flow matches and the

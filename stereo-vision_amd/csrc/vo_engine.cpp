@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <chrono>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -607,6 +608,176 @@ int32_t svh_vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, in
     bucket_features(v->matcher, P.bucket_max_features, (float)P.bucket_width, (float)P.bucket_height, v->rng);
     fetch_matches(v);
     return update_motion(v);
+}
+
+// ---- K mono objects in lockstep.  The Matcher steps go through the batched Matcher entries with one camera and
+// method 0 (flow); the K estimates walk through their three phases together (mono_run_batch).  The random numbers of a
+// mono frame -- the bucketing's shuffle and the RANSAC samples -- are all drawn on the host in front of the first
+// device phase, object by object, which is the order of K svh_vo_mono_process calls.
+static int32_t mono_batch_args(svh_vo* const* vs, int32_t K, bool* lockstep) {
+    if (!vs || K < 0) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    *lockstep = K > 1;
+    for (int i = 0; i < K; i++) {
+        if (!vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "null object in the batch");
+        if (!vs[i]->mono) return svh::fail(SVH_ERR_BAD_ARG, "a stereo object in a mono batch: use svh_vo_process_batch");
+        for (int j = 0; j < i; j++)
+            if (vs[j] == vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "the same object twice in one batch");
+        *lockstep = *lockstep && mono_same_params(vs[i]->mono, vs[0]->mono) &&
+                    memcmp(&vs[i]->p, &vs[0]->p, sizeof(vs[0]->p)) == 0 && vs[i]->device == vs[0]->device;
+    }
+    int nd = 0;
+    if (K > 0 && (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0))
+        return svh::fail(SVH_ERR_NO_DEVICE, "no HIP device visible: libsvhip has no CPU fallback");
+    return SVH_OK;
+}
+
+// the estimates of K objects whose matches are in v->matched: prepare (with `before(i)` in front of it, in draw
+// order), the three phases together, motion update.  Returns the number of motions updated or < 0.
+static int32_t mono_estimate_batch(svh_vo* const* vs, int32_t K, int32_t* ok, const std::function<void(int)>& before) {
+    std::vector<int> state(K, 0);
+    auto prepare = [&](int i) {
+        svh_vo* v = vs[i];
+        if (before) before(i);
+        state[i] = mono_prepare(v->mono, v->matched.data(), (int32_t)v->matched.size(), v->rng, v->inliers);
+    };
+    bool all_private = true;
+    for (int i = 0; i < K; i++) all_private = all_private && vs[i]->rng.is_private;
+    if (all_private) {
+        // every object draws from its own stream: no order to keep between them
+        batch_parallel_for(K, [&](int i) {
+            (void)hipSetDevice(vs[i]->device);
+            prepare(i);
+        });
+    } else {
+        for (int i = 0; i < K; i++) prepare(i);   // the process-wide rand(): in the order of K single calls
+    }
+    for (int i = 0; i < K; i++)
+        if (state[i] < 0) return state[i];
+    std::vector<MonoVo*> Ms(K);
+    std::vector<std::vector<int32_t>*> inl(K);
+    std::vector<double> tr((size_t)6 * K, 0.0);
+    for (int i = 0; i < K; i++) {
+        Ms[i] = vs[i]->mono;
+        inl[i] = &vs[i]->inliers;
+    }
+    const int rc = mono_run_batch(Ms.data(), K, state.data(), inl.data(), tr.data());
+    if (rc < 0) return rc;
+    int32_t good = 0;
+    for (int i = 0; i < K; i++) {
+        if (state[i] > 0) {   // updateMotion, viso.cpp:47-64
+            vector_to_matrix(&tr[6 * (size_t)i], vs[i]->Tr);
+            vs[i]->Tr_valid = true;
+        }
+        if (ok) ok[i] = state[i] > 0;
+        good += state[i] > 0;
+    }
+    return good;
+}
+
+static int32_t mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I, const int32_t* dims,
+                                  const int32_t* replace, int32_t* ok, const uint8_t* const* NI) {
+    svh::ActiveCaller active_;
+    if (!dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    bool lockstep = false;
+    int32_t rc = mono_batch_args(vs, K, &lockstep);
+    if (rc < 0) return rc;
+    if (K == 0) return 0;
+    std::vector<svh_matcher*> ms(K);
+    for (int i = 0; i < K; i++) ms[i] = vs[i]->matcher;
+    if (!lockstep) {
+        // one by one, in the order of K svh_vo_mono_process calls (pushBack draws no random numbers, so taking all K
+        // frames first -- which the hand-over of the next frame needs -- keeps the draw order)
+        for (int i = 0; i < K; i++) {
+            rc = svh_matcher_push_back(ms[i], I ? I[i] : nullptr, nullptr, dims, replace ? replace[i] : 0);
+            if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored)
+        }
+        if (NI) {
+            rc = svh_matcher_prefetch_batch(ms.data(), K, NI, nullptr, dims);
+            if (rc < 0) return rc;
+        }
+        int32_t good = 0;
+        for (int i = 0; i < K; i++) {
+            svh_vo* v = vs[i];
+            rc = svh_matcher_match_features(v->matcher, 0, nullptr);
+            if (rc < 0) return rc;
+            bucket_features(v->matcher, v->p.bucket_max_features, (float)v->p.bucket_width, (float)v->p.bucket_height, v->rng);
+            fetch_matches(v);
+            rc = update_motion(v);
+            if (rc < 0) return rc;
+            if (ok) ok[i] = rc;
+            good += rc > 0;
+        }
+        return good;
+    }
+    // pushBack in up to two sub-groups, the objects that keep their previous frame (replace) and those that do not:
+    // it draws no random numbers and the objects do not see each other, so the split changes nothing
+    for (int r = 0; r < 2; r++) {
+        std::vector<svh_matcher*> sub;
+        std::vector<const uint8_t*> img;
+        for (int i = 0; i < K; i++)
+            if (((replace ? replace[i] : 0) != 0) == (r != 0)) {
+                sub.push_back(ms[i]);
+                if (I) img.push_back(I[i]);
+            }
+        if (sub.empty()) continue;
+        rc = svh_matcher_push_back_batch(sub.data(), (int32_t)sub.size(), I ? img.data() : nullptr, nullptr, dims, r);
+        if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored)
+    }
+    if (NI) {   // the next frame goes out now: its packing, upload and features overlap everything below
+        rc = svh_matcher_prefetch_batch(ms.data(), K, NI, nullptr, dims);
+        if (rc < 0) return rc;
+    }
+    rc = svh_matcher_match_features_batch(ms.data(), K, 0, nullptr);
+    if (rc < 0) return rc;
+    const svh_vo_params& P = vs[0]->p;   // (the bucketing fields of the mono parameters)
+    return mono_estimate_batch(vs, K, ok, [&](int i) {
+        bucket_features(vs[i]->matcher, P.bucket_max_features, (float)P.bucket_width, (float)P.bucket_height, vs[i]->rng);
+        fetch_matches(vs[i]);
+    });
+}
+
+int32_t svh_vo_mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I, const int32_t* dims,
+                                  const int32_t* replace, int32_t* ok) {
+    return mono_process_batch(vs, K, I, dims, replace, ok, nullptr);
+}
+
+int32_t svh_vo_mono_process_next_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* next_I, const int32_t* dims,
+                                       const int32_t* replace, int32_t* ok) {
+    return mono_process_batch(vs, K, nullptr, dims, replace, ok, next_I);
+}
+
+int32_t svh_vo_mono_prefetch_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I, const int32_t* dims) {
+    if (!I || !dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    bool lockstep = false;
+    const int32_t rc = mono_batch_args(vs, K, &lockstep);
+    if (rc < 0) return rc;
+    if (K == 0) return SVH_OK;
+    std::vector<svh_matcher*> ms(K);
+    for (int i = 0; i < K; i++) ms[i] = vs[i]->matcher;
+    return svh_matcher_prefetch_batch(ms.data(), K, I, nullptr, dims);
+}
+
+int32_t svh_vo_mono_process_matches_batch(svh_vo* const* vs, int32_t K, const svh_p_match* const* matches,
+                                          const int32_t* n, int32_t* ok) {
+    svh::ActiveCaller active_;
+    if (K > 0 && (!matches || !n)) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    bool lockstep = false;
+    const int32_t rc = mono_batch_args(vs, K, &lockstep);
+    if (rc < 0) return rc;
+    for (int i = 0; i < K; i++)
+        if (n[i] < 0 || (n[i] > 0 && !matches[i])) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    for (int i = 0; i < K; i++) vs[i]->matched.assign(matches[i], matches[i] + n[i]);
+    if (!lockstep) {
+        int32_t good = 0;
+        for (int i = 0; i < K; i++) {
+            const int r = update_motion(vs[i]);
+            if (r < 0) return r;
+            if (ok) ok[i] = r;
+            good += r > 0;
+        }
+        return good;
+    }
+    return mono_estimate_batch(vs, K, ok, nullptr);
 }
 
 int32_t svh_vo_mono_get_votes(svh_vo* v, int32_t* out, int32_t cap) {

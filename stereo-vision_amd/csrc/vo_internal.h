@@ -108,6 +108,18 @@ void mono_destroy(MonoVo* M);
 // object's getInlierIndices() state, cleared only where the reference clears it
 int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, std::vector<int32_t>& inliers,
                   double* tr6);
+// The same estimate in steps, for K objects walked through it together (svh_vo_mono_*_batch).  mono_prepare is the host
+// part in front of the first device phase and the only step that draws random numbers (1: device work follows, 0: the
+// empty vector, < 0: error); mono_enqueue issues the upload and kernels of phase 0 / 1 / 2 (into t_rec when set);
+// mono_after is the host side behind the phase's wait (1: go on, or tr6 valid after phase 2; 0: the empty vector).
+int mono_prepare(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, std::vector<int32_t>& inliers);
+void mono_enqueue(MonoVo* M, int phase);
+int mono_after(MonoVo* M, int phase, std::vector<int32_t>& inliers, double* tr6);
+// the three phases of the objects with state[i] > 0 (what mono_prepare returned) in lockstep: per phase one recorded
+// pass, one stream wait, the host steps on the helper threads.  On return state[i] is mono_estimate's value for
+// object i and tr6[6 i ..] its motion; the function returns SVH_OK or the error.  Same parameters and device.
+int mono_run_batch(MonoVo* const* Ms, int32_t K, int* state, std::vector<int32_t>* const* inliers, double* tr6);
+bool mono_same_params(const MonoVo* a, const MonoVo* b);
 int32_t mono_votes(MonoVo* M, int32_t* out, int32_t cap);
 void mono_clear(MonoVo* M);   // forget the last estimate's votes and times
 void mono_set_timing(MonoVo* M, bool on);

@@ -10,6 +10,10 @@
 // candidates (between 1 and 2), the median and the plane distances (between 2 and 3), the scale and the angles
 // (after 3).  The matrix steps use the same mono_core.h functions as the kernels.  There is no CPU path for the
 // device phases.
+// The estimate is written as steps -- mono_prepare, then per phase mono_enqueue, the wait and mono_after -- which the
+// single call (mono_estimate) runs for one object and the lockstep entries (mono_run_batch) for K objects together:
+// per phase ONE recorded pass over the objects still alive (batch_rec.h: one launch per kernel, blockIdx.z = object),
+// one stream wait, then the host step of every live object on the helper threads.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -19,25 +23,34 @@
 #include <vector>
 
 #include "../../include/svh.h"
+#include "batch_rec.h"
 #include "mono_core.h"
 #include "vo_internal.h"
 
 namespace svh {
 int fail(int code, const std::string& msg);   // elas_engine.cpp: records svh_last_error()
+bool fi_armed();                              // elas_engine.cpp: fault injection (svh_internal.h)
+bool fi_hit(const char* expr_text);
 void report_hip_failure(const char* entry);
 
 namespace {
 
-int mono_hip_failed(const char* expr, hipError_t e) {
-    const int rc = svh::fail(SVH_ERR_HIP, std::string(expr) + ": " + hipGetErrorString(e));
+int mono_hip_failed(const char* expr, bool injected, hipError_t e) {
+    const int rc = svh::fail(SVH_ERR_HIP, std::string(expr) + ": " +
+                                              (injected ? "injected failure (SVH_TEST_FAIL_AT)" : hipGetErrorString(e)));
     svh::report_hip_failure("VisualOdometryMono");
     return rc;
 }
-#define MONO_TRY(expr)                                              \
-    do {                                                            \
-        hipError_t e_ = (expr);                                     \
-        if (e_ != hipSuccess) return mono_hip_failed(#expr, e_);    \
+#define MONO_TRY(expr)                                                                                  \
+    do {                                                                                                \
+        const bool inj_ = svh::fi_armed() && svh::fi_hit(#expr); /* svh_internal.h: fault injection */  \
+        hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                                \
+        if (e_ != hipSuccess) return mono_hip_failed(#expr, inj_, e_);                                  \
     } while (0)
+// (named so that the fault hook files them under "wait" and "copy": a lockstep phase's one copy is the recorder's
+// upload of its job tables, hipMemcpyAsync inside BatchRec::flush, which then issues the phase's launches)
+hipError_t stream_wait(hipStream_t s) { return (hipError_t)wait_stream(s); }
+hipError_t hipMemcpyAsync_jobs_and_launch(BatchRec& rec, hipStream_t s) { return rec.flush(s); }
 
 size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
@@ -69,6 +82,13 @@ struct MonoVo {
     uint8_t* d_front = nullptr;
     double* d_d = nullptr;
     int32_t cap_n = 0, cap_it = -1;
+    // the estimate in flight, from mono_prepare to the last mono_after
+    int32_t N = 0, iters = 0, n = 0;
+    std::vector<float> q;         // normalised matches, 4 N
+    double T[18];                 // Tp | Tc
+    double Ra[9], Rb[9], t[3];    // EtoRt's candidates: (Ra,t) (Ra,-t) (Rb,t) (Rb,-t)
+    int32_t cand = -1;            // the one with the most points in front
+    double weight = 0, thr = 0;   // of the plane vote
 };
 
 namespace {
@@ -124,7 +144,7 @@ void mark(MonoVo* M, int i) {
 
 // the stream wait that ends device phase `phase` (its events: ev[0] before, ev[1] after)
 int wait(MonoVo* M, int phase) {
-    MONO_TRY((hipError_t)wait_stream(M->stream));
+    MONO_TRY(stream_wait(M->stream));
     MONO_TRY(hipGetLastError());
     if (M->timing) {
         float ms = 0;
@@ -194,6 +214,10 @@ void mono_destroy(MonoVo* M) {
     delete M;
 }
 
+bool mono_same_params(const MonoVo* a, const MonoVo* b) {
+    return memcmp(&a->p, &b->p, sizeof(a->p)) == 0 && a->device == b->device;
+}
+
 int32_t mono_votes(MonoVo* M, int32_t* out, int32_t cap) {
     for (int32_t i = 0; i < (int32_t)M->votes.size() && i < cap && out; i++) out[i] = M->votes[i];
     return (int32_t)M->votes.size();
@@ -211,13 +235,14 @@ int32_t mono_timing(MonoVo* M, double* ms3) {
     return 3;
 }
 
-// estimateMotion: 1 + tr6 (rx, ry, rz, tx, ty, tz), 0 for the reference's empty vector, < 0 on error.
-// `inliers` is the object's getInlierIndices() state: cleared only where the reference clears it.
-int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, std::vector<int32_t>& inliers,
-                  double* tr6) {
+// The host part in front of phase 1: the early exits, buffers, the random samples, staging.  1: there is device work,
+// 0: the reference's empty vector, < 0 on error.  `inliers` is the object's getInlierIndices() state: cleared only
+// where the reference clears it.  The only step of an estimate that draws random numbers.
+int mono_prepare(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, std::vector<int32_t>& inliers) {
     const svh_vo_mono_params& P = M->p;
     if (N < 10) return 0;   // viso_mono.cpp:44-46: before inliers.clear()
-    std::vector<float> q((size_t)N * 4);
+    std::vector<float>& q = M->q;
+    q.resize((size_t)N * 4);
     for (int32_t i = 0; i < N; i++) {
         q[4 * i + 0] = pm[i].u1p;
         q[4 * i + 1] = pm[i].v1p;
@@ -225,14 +250,15 @@ int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, 
         q[4 * i + 3] = pm[i].v1c;
     }
     const std::vector<float> orig = q;
-    double T[18];   // Tp | Tc
-    if (!mono::normalize(q.data(), N, T)) return 0;
+    if (!mono::normalize(q.data(), N, M->T)) return 0;
     inliers.clear();
     M->votes.clear();
     M->ms[0] = M->ms[1] = M->ms[2] = 0;
     const int32_t iters = P.ransac_iters > 0 ? P.ransac_iters : 0;
-    int rc = ensure(M, N, iters);
+    const int rc = ensure(M, N, iters);
     if (rc) return rc;
+    M->N = N;
+    M->iters = iters;
 
     // ---- phase 1: RANSAC on the device.  getRandomSample(N, 8) per iteration (viso.cpp:130-153): eight draws
     // without replacement, each indexing the list of the indices not chosen yet
@@ -258,15 +284,39 @@ int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, 
             samples[8 * k + s] = idx;
         }
     }
+    return 1;
+}
+
+// The upload and the kernels of device phase 0 / 1 / 2 on the object's stream, or into the calling thread's recorder
+void mono_enqueue(MonoVo* M, int phase) {
+    const svh_vo_mono_params& P = M->p;
+    const int32_t N = M->N, iters = M->iters;
     const float* d_q = reinterpret_cast<const float*>(M->d_in);
     const float* d_m = reinterpret_cast<const float*>(M->d_in + 16 * (size_t)N);
-    mark(M, 0);
-    vlaunch_upload(M->stream, M->h_in, M->d_in, 32 * (size_t)N + up16(32 * (size_t)iters));
-    mlaunch_ransac(M->stream, d_q, N, reinterpret_cast<const int32_t*>(M->d_in + 32 * (size_t)N), iters,
-                   P.inlier_threshold, M->d_F, M->d_counts, M->h_sel, M->h_flags, M->h_counts);
-    mark(M, 1);
-    if ((rc = wait(M, 0))) return rc;
-    M->votes.assign(M->h_counts, M->h_counts + iters);
+    if (phase == 0) {
+        vlaunch_upload(M->stream, M->h_in, M->d_in, 32 * (size_t)N + up16(32 * (size_t)iters));
+        mlaunch_ransac(M->stream, d_q, N, reinterpret_cast<const int32_t*>(M->d_in + 32 * (size_t)N), iters,
+                       P.inlier_threshold, M->d_F, M->d_counts, M->h_sel, M->h_flags, M->h_counts);
+    } else if (phase == 1) {
+        vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_cams), reinterpret_cast<uint8_t*>(M->d_cams),
+                       60 * sizeof(double));
+        mlaunch_chiral(M->stream, d_m, N, M->d_cams, M->d_X, M->d_front, M->h_X, M->h_sel + 4);
+    } else {
+        vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_d), reinterpret_cast<uint8_t*>(M->d_d),
+                       up16(8 * (size_t)M->n));
+        mlaunch_plane(M->stream, M->d_d, M->n, M->weight, M->thr, M->h_sums);
+    }
+}
+
+namespace {
+
+// after phase 0: votes, the inlier list, then the refit, E, the four R|t and the cameras of phase 1
+int after_ransac(MonoVo* M, std::vector<int32_t>& inliers) {
+    const svh_vo_mono_params& P = M->p;
+    const int32_t N = M->N;
+    const std::vector<float>& q = M->q;
+    const double* T = M->T;
+    M->votes.assign(M->h_counts, M->h_counts + M->iters);
     for (int32_t i = 0; i < N; i++)
         if (M->h_flags[i]) inliers.push_back(i);
     if (inliers.size() < 10) return 0;   // :73-74
@@ -286,7 +336,8 @@ int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, 
         svd3(E, U, w, V);
         mono::rank2(mono::Mat{U, 3, 1}, mono::Mat{V, 3, 1}, mono::Vec{w, 1}, E);
     }
-    double U[9], S[3], V[9], VT[9], Ra[9], Rb[9], t[3];
+    double U[9], S[3], V[9], VT[9];
+    double *Ra = M->Ra, *Rb = M->Rb, *t = M->t;
     svd3(E, U, S, V);
     transpose3(V, VT);
     {
@@ -306,9 +357,9 @@ int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, 
         t[2] = Tm[3];
     }
     if (det3(Ra) < 0)
-        for (double& x : Ra) x = -x;
+        for (int i = 0; i < 9; i++) Ra[i] = -Ra[i];
     if (det3(Rb) < 0)
-        for (double& x : Rb) x = -x;
+        for (int i = 0; i < 9; i++) Rb[i] = -Rb[i];
     const double* Rc[4] = {Ra, Ra, Rb, Rb};
     const double sg[4] = {1, -1, 1, -1};
     double* cams = M->h_cams;
@@ -327,20 +378,17 @@ int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, 
                 cams[12 + 12 * c + 4 * i + j] = s;   // P2 = K * [R | t]
             }
     }
+    return 1;
+}
 
-    // ---- phase 2: chirality on the device
-    int32_t* cand = M->h_sel + 4;
-    mark(M, 0);
-    vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(cams), reinterpret_cast<uint8_t*>(M->d_cams),
-                   60 * sizeof(double));
-    mlaunch_chiral(M->stream, d_m, N, M->d_cams, M->d_X, M->d_front, M->h_X, cand);
-    mark(M, 1);
-    if ((rc = wait(M, 1))) return rc;
+// after phase 1 (chirality): the candidate, then the points in front, their median and the plane distances
+int after_chiral(MonoVo* M) {
+    const svh_vo_mono_params& P = M->p;
+    const int32_t N = M->N;
     // no candidate with a point in front of both cameras: the reference leaves X empty and exits in getMat
     // (matrix.cpp:127-137); here the estimate fails
-    if (cand[0] < 0) return 0;
-    const double* R = Rc[cand[0]];
-    const double ts = sg[cand[0]];
+    M->cand = M->h_sel[4];
+    if (M->cand < 0) return 0;
 
     // ---- points in front of the first camera, their median distance, plane distances (:88-122)
     const double* X = M->h_X;
@@ -364,16 +412,21 @@ int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, 
         d[i] = s;   // ~n * x_plane
     }
     const double sigma = median / 50.0;
-    const double weight = 1.0 / (2.0 * sigma * sigma);
-    const double thr = median / P.motion_threshold;
+    M->n = n;
+    M->weight = 1.0 / (2.0 * sigma * sigma);
+    M->thr = median / P.motion_threshold;
+    return 1;
+}
 
-    // ---- phase 3: the plane vote on the device
-    mark(M, 0);
-    vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(d), reinterpret_cast<uint8_t*>(M->d_d),
-                   up16(8 * (size_t)n));
-    mlaunch_plane(M->stream, M->d_d, n, weight, thr, M->h_sums);
-    mark(M, 1);
-    if ((rc = wait(M, 2))) return rc;
+// after phase 2 (the plane vote): the best plane point, scale, angles
+int after_plane(MonoVo* M, double* tr6) {
+    const svh_vo_mono_params& P = M->p;
+    const int32_t n = M->n;
+    const double* d = M->h_d;
+    const double thr = M->thr;
+    const double* R = M->cand < 2 ? M->Ra : M->Rb;
+    const double ts = (M->cand & 1) ? -1.0 : 1.0;
+    const double* t = M->t;
     double best_sum = 0;
     int32_t best_idx = 0;
     for (int32_t i = 0; i < n; i++)
@@ -397,6 +450,102 @@ int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, 
     tr6[4] = tt[1];
     tr6[5] = tt[2];
     return 1;
+}
+
+}  // namespace
+
+// The host side after the wait that ended `phase`: its results, its exits, and what the next phase needs.  1: go on
+// (after the last phase: tr6 is the motion), 0: the reference's empty vector.  Draws no random numbers.
+int mono_after(MonoVo* M, int phase, std::vector<int32_t>& inliers, double* tr6) {
+    return phase == 0 ? after_ransac(M, inliers) : (phase == 1 ? after_chiral(M) : after_plane(M, tr6));
+}
+
+// estimateMotion: 1 + tr6 (rx, ry, rz, tx, ty, tz), 0 for the reference's empty vector, < 0 on error.
+int mono_estimate(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, std::vector<int32_t>& inliers,
+                  double* tr6) {
+    int rc = mono_prepare(M, pm, N, rng, inliers);
+    for (int phase = 0; phase < 3 && rc > 0; phase++) {
+        mark(M, 0);
+        mono_enqueue(M, phase);
+        mark(M, 1);
+        if ((rc = wait(M, phase))) {
+            (void)hipStreamSynchronize(M->stream);   // (nothing of this estimate stays in flight behind an error)
+            return rc;
+        }
+        rc = mono_after(M, phase, inliers, tr6);
+    }
+    return rc;
+}
+
+// The device phases of K prepared objects in lockstep.  state[i] > 0 on entry: object i passed mono_prepare; on
+// return state[i] is what mono_estimate would have returned for it.  Objects share parameters and device (the
+// callers check); the recorded launches of a phase go to the first live object's stream.
+int mono_run_batch(MonoVo* const* Ms, int32_t K, int* state, std::vector<int32_t>* const* inliers, double* tr6) {
+    std::vector<int> live;
+    for (int i = 0; i < K; i++)
+        if (state[i] > 0) live.push_back(i);
+    if (live.empty()) return SVH_OK;
+    MonoVo* M0 = Ms[live[0]];
+    MONO_TRY(hipSetDevice(M0->device));
+    BatchRec& rec = batch_recorder(M0->device);
+    hipStream_t s = M0->stream;
+    // whatever way a phase fails: nothing stays in flight, the recorder is free again
+    struct Drain {
+        hipStream_t s;
+        BatchRec& rec;
+        bool armed;
+        ~Drain() {
+            if (!armed) return;
+            t_rec = nullptr;
+            (void)hipStreamSynchronize(s);
+            rec.reset();
+            rec.synced();
+        }
+    } drain{s, rec, true};
+    for (int phase = 0; phase < 3 && !live.empty(); phase++) {
+        bool timing = false;
+        for (int i : live) timing = timing || Ms[i]->timing;
+        rec.reset();
+        t_rec = &rec;
+        for (int i : live) {
+            rec.begin_object();
+            mono_enqueue(Ms[i], phase);
+        }
+        t_rec = nullptr;
+        if (rec.broken) {   // (not reachable with equal parameters) one by one on the objects' own streams
+            rec.reset();
+            for (int i : live) {
+                mark(Ms[i], 0);
+                mono_enqueue(Ms[i], phase);
+                mark(Ms[i], 1);
+                const int rc = wait(Ms[i], phase);
+                if (rc) {
+                    (void)hipStreamSynchronize(Ms[i]->stream);
+                    return rc;
+                }
+            }
+        } else {
+            if (timing) (void)hipEventRecord(M0->ev[0], s);
+            MONO_TRY(hipMemcpyAsync_jobs_and_launch(rec, s));
+            if (timing) (void)hipEventRecord(M0->ev[1], s);
+            MONO_TRY(stream_wait(s));
+            rec.synced();
+            MONO_TRY(hipGetLastError());
+            float ms = 0;
+            if (timing && hipEventElapsedTime(&ms, M0->ev[0], M0->ev[1]) == hipSuccess)
+                for (int i : live) Ms[i]->ms[phase] = ms;   // the phase's time for the whole batch
+        }
+        batch_parallel_for((int)live.size(), [&](int j) {
+            const int i = live[j];
+            state[i] = mono_after(Ms[i], phase, *inliers[i], tr6 + 6 * (size_t)i);
+        });
+        std::vector<int> next;
+        for (int i : live)
+            if (state[i] > 0) next.push_back(i);
+        live.swap(next);
+    }
+    drain.armed = false;   // (every phase was waited for)
+    return SVH_OK;
 }
 
 }  // namespace svh

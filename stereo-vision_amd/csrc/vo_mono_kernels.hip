@@ -17,9 +17,12 @@
 //                the sums can, and the plane chosen would differ only if two sums were that close (none is in the
 //                fixtures: the GPU tests compare best_idx through the motion).
 // All arithmetic is fp64 in the reference's operation order (mono_core.h), no FMA contraction (-ffp-contract=off).
+// Each kernel has a batched form k_mono_*_b for K objects driven in lockstep (svh_vo_mono_*_batch): one job per
+// object in a table in device memory, blockIdx.z = job.  The results of a job go to that object's own pinned buffers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "batch_rec.h"
 #include "mono_core.h"
 #include "vo_internal.h"
 
@@ -35,10 +38,31 @@ constexpr int HYP_SLAB = 171;     // U 72 | V 81 | w 9 | rv1 9
 constexpr int CHI_LANES = 64;     // lanes per workgroup of k_mono_chiral: 40 x 8 B x 64 = 20 KB LDS
 constexpr int CHI_SLAB = 40;      // J 16 | V 16 | w 4 | rv1 4
 
-__global__ __launch_bounds__(HYP_LANES) void k_mono_hyp(const float4* __restrict__ q, int32_t N,
-                                                         const int32_t* __restrict__ samples, int32_t iters,
-                                                         double* __restrict__ Fout) {
-    __shared__ double slab[HYP_SLAB * HYP_LANES];
+// Every kernel is a __device__ body with two entries (as in vo_kernels.hip): the plain form takes its job by value,
+// the batched form `_b` reads job blockIdx.z of a table in device memory (batch_rec.h), grid x is the largest job's and
+// blocks beyond a job's own extent return at once.  Both run the same body, so a batched lane computes bit for bit
+// what the single launch computes.  Pointers read from the table are told to be global memory (global_load instead
+// of flat_load).
+template <class T>
+__device__ __forceinline__ T* mgptr(T* p) {
+    __attribute__((address_space(1))) T* q = (__attribute__((address_space(1))) T*)p;
+    asm volatile("" : "+v"(q));
+    return (T*)q;
+}
+
+struct MonoHypJob { const float4* q; const int32_t* samples; double* F; int32_t N, iters; };
+struct MonoVoteJob { const float4* q; const double* F; int32_t* counts; double thr; int32_t N, iters; };
+struct MonoSelectJob {
+    const int32_t* counts; const double* F; const float4* q; int32_t* out_sel; uint8_t* out_flags; int32_t* out_counts;
+    double thr; int32_t N, iters;
+};
+struct MonoChiralJob { const float4* m; const double* cams; double* X; uint8_t* front; int32_t N; };
+struct MonoPickJob { const double* X; const uint8_t* front; double* out_X; int32_t* out_cand; int32_t N; };
+struct MonoPlaneJob { const double* d; double* sums; double weight, thr; int32_t n; };
+
+__device__ __forceinline__ void d_mono_hyp(double* slab, const float4* __restrict__ q, int32_t N,
+                                           const int32_t* __restrict__ samples, int32_t iters,
+                                           double* __restrict__ Fout) {
     const int lane = threadIdx.x;
     const int h = blockIdx.x * HYP_LANES + lane;
     if (h >= iters) return;
@@ -60,10 +84,19 @@ __global__ __launch_bounds__(HYP_LANES) void k_mono_hyp(const float4* __restrict
     mono::rank2(U3, V3, w, F);
     for (int i = 0; i < 9; i++) Fout[9 * (size_t)h + i] = F[i];
 }
+__global__ __launch_bounds__(HYP_LANES) void k_mono_hyp(MonoHypJob a) {
+    __shared__ double slab[HYP_SLAB * HYP_LANES];
+    d_mono_hyp(slab, a.q, a.N, a.samples, a.iters, a.F);
+}
+__global__ __launch_bounds__(HYP_LANES) void k_mono_hyp_b(const MonoHypJob* J) {
+    __shared__ double slab[HYP_SLAB * HYP_LANES];
+    const MonoHypJob& a = J[blockIdx.z];
+    if ((int)(blockIdx.x * HYP_LANES) >= a.iters) return;
+    d_mono_hyp(slab, mgptr(a.q), a.N, mgptr(a.samples), a.iters, mgptr(a.F));
+}
 
-__global__ __launch_bounds__(64) void k_mono_vote(const float4* __restrict__ q, int32_t N,
-                                                   const double* __restrict__ Fs, double thr,
-                                                   int32_t* __restrict__ counts) {
+__device__ __forceinline__ void d_mono_vote(const float4* __restrict__ q, int32_t N, const double* __restrict__ Fs,
+                                            double thr, int32_t* __restrict__ counts) {
     const int h = blockIdx.x;
     double F[9];
     for (int i = 0; i < 9; i++) F[i] = Fs[9 * (size_t)h + i];
@@ -79,12 +112,17 @@ __global__ __launch_bounds__(64) void k_mono_vote(const float4* __restrict__ q, 
     }
     if (threadIdx.x == 0) counts[h] = c;
 }
+__global__ __launch_bounds__(64) void k_mono_vote(MonoVoteJob a) { d_mono_vote(a.q, a.N, a.F, a.thr, a.counts); }
+__global__ __launch_bounds__(64) void k_mono_vote_b(const MonoVoteJob* J) {
+    const MonoVoteJob& a = J[blockIdx.z];
+    if ((int)blockIdx.x >= a.iters) return;
+    d_mono_vote(mgptr(a.q), a.N, mgptr(a.F), a.thr, mgptr(a.counts));
+}
 
-__global__ __launch_bounds__(256) void k_mono_select(const int32_t* __restrict__ counts, int32_t iters,
-                                                     const double* __restrict__ Fs, const float4* __restrict__ q,
-                                                     int32_t N, double thr, int32_t* __restrict__ out_sel,
-                                                     uint8_t* __restrict__ out_flags,
-                                                     int32_t* __restrict__ out_counts) {
+__device__ __forceinline__ void d_mono_select(const int32_t* __restrict__ counts, int32_t iters,
+                                              const double* __restrict__ Fs, const float4* __restrict__ q, int32_t N,
+                                              double thr, int32_t* __restrict__ out_sel,
+                                              uint8_t* __restrict__ out_flags, int32_t* __restrict__ out_counts) {
     __shared__ int32_t s_cnt[256], s_idx[256];
     int32_t bc = -1, bi = 0;
     for (int32_t h = threadIdx.x; h < iters; h += 256) {
@@ -119,11 +157,18 @@ __global__ __launch_bounds__(256) void k_mono_select(const int32_t* __restrict__
         out_sel[1] = most;
     }
 }
+__global__ __launch_bounds__(256) void k_mono_select(MonoSelectJob a) {
+    d_mono_select(a.counts, a.iters, a.F, a.q, a.N, a.thr, a.out_sel, a.out_flags, a.out_counts);
+}
+__global__ __launch_bounds__(256) void k_mono_select_b(const MonoSelectJob* J) {
+    const MonoSelectJob& a = J[blockIdx.z];
+    d_mono_select(mgptr(a.counts), a.iters, mgptr(a.F), mgptr(a.q), a.N, a.thr, mgptr(a.out_sel), mgptr(a.out_flags),
+                  mgptr(a.out_counts));
+}
 
-__global__ __launch_bounds__(CHI_LANES) void k_mono_chiral(const float4* __restrict__ m, int32_t N,
-                                                           const double* __restrict__ cams,
-                                                           double* __restrict__ X, uint8_t* __restrict__ front) {
-    __shared__ double slab[CHI_SLAB * CHI_LANES];
+__device__ __forceinline__ void d_mono_chiral(double* slab, const float4* __restrict__ m, int32_t N,
+                                              const double* __restrict__ cams, double* __restrict__ X,
+                                              uint8_t* __restrict__ front) {
     const int lane = threadIdx.x;
     const int32_t g = blockIdx.x * CHI_LANES + lane;
     if (g >= 4 * N) return;
@@ -137,10 +182,19 @@ __global__ __launch_bounds__(CHI_LANES) void k_mono_chiral(const float4* __restr
     for (int r = 0; r < 4; r++) X[((size_t)cand * 4 + r) * N + i] = x[r];
     front[g] = ok;
 }
+__global__ __launch_bounds__(CHI_LANES) void k_mono_chiral(MonoChiralJob a) {
+    __shared__ double slab[CHI_SLAB * CHI_LANES];
+    d_mono_chiral(slab, a.m, a.N, a.cams, a.X, a.front);
+}
+__global__ __launch_bounds__(CHI_LANES) void k_mono_chiral_b(const MonoChiralJob* J) {
+    __shared__ double slab[CHI_SLAB * CHI_LANES];
+    const MonoChiralJob& a = J[blockIdx.z];
+    if ((int)(blockIdx.x * CHI_LANES) >= 4 * a.N) return;
+    d_mono_chiral(slab, mgptr(a.m), a.N, mgptr(a.cams), mgptr(a.X), mgptr(a.front));
+}
 
-__global__ __launch_bounds__(256) void k_mono_pick(const double* __restrict__ X, const uint8_t* __restrict__ front,
-                                                   int32_t N, double* __restrict__ out_X,
-                                                   int32_t* __restrict__ out_cand) {
+__device__ __forceinline__ void d_mono_pick(const double* __restrict__ X, const uint8_t* __restrict__ front, int32_t N,
+                                            double* __restrict__ out_X, int32_t* __restrict__ out_cand) {
     __shared__ int32_t s[4][256];
     int32_t c[4] = {0, 0, 0, 0};
     for (int32_t i = threadIdx.x; i < N; i += 256)
@@ -169,9 +223,14 @@ __global__ __launch_bounds__(256) void k_mono_pick(const double* __restrict__ X,
         for (int r = 0; r < 4; r++) out_X[(size_t)r * N + i] = d != 0 ? Xc[(size_t)r * N + i] / d : 0.0;
     }
 }
+__global__ __launch_bounds__(256) void k_mono_pick(MonoPickJob a) { d_mono_pick(a.X, a.front, a.N, a.out_X, a.out_cand); }
+__global__ __launch_bounds__(256) void k_mono_pick_b(const MonoPickJob* J) {
+    const MonoPickJob& a = J[blockIdx.z];
+    d_mono_pick(mgptr(a.X), mgptr(a.front), a.N, mgptr(a.out_X), mgptr(a.out_cand));
+}
 
-__global__ __launch_bounds__(64) void k_mono_plane(const double* __restrict__ d, int32_t n, double weight,
-                                                   double thr, double* __restrict__ sums) {
+__device__ __forceinline__ void d_mono_plane(const double* __restrict__ d, int32_t n, double weight, double thr,
+                                             double* __restrict__ sums) {
     const int32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     const double di = d[i];
@@ -183,30 +242,72 @@ __global__ __launch_bounds__(64) void k_mono_plane(const double* __restrict__ d,
         }
     sums[i] = sum;
 }
+__global__ __launch_bounds__(64) void k_mono_plane(MonoPlaneJob a) { d_mono_plane(a.d, a.n, a.weight, a.thr, a.sums); }
+__global__ __launch_bounds__(64) void k_mono_plane_b(const MonoPlaneJob* J) {
+    const MonoPlaneJob& a = J[blockIdx.z];
+    if ((int)(blockIdx.x * 64) >= a.n) return;
+    d_mono_plane(mgptr(a.d), a.n, a.weight, a.thr, mgptr(a.sums));
+}
+
+#define MONO_BATCHED(name, Job, kernel, threads)                                                                  \
+    void name(const void* jobs, int njobs, unsigned gx, unsigned gy, size_t lds, hipStream_t s) {                 \
+        hipLaunchKernelGGL(kernel, dim3(gx, gy, (unsigned)njobs), dim3(threads), lds, s,                          \
+                           reinterpret_cast<const Job*>(jobs));                                                   \
+    }
+MONO_BATCHED(b_mono_hyp, MonoHypJob, k_mono_hyp_b, HYP_LANES)
+MONO_BATCHED(b_mono_vote, MonoVoteJob, k_mono_vote_b, 64)
+MONO_BATCHED(b_mono_select, MonoSelectJob, k_mono_select_b, 256)
+MONO_BATCHED(b_mono_chiral, MonoChiralJob, k_mono_chiral_b, CHI_LANES)
+MONO_BATCHED(b_mono_pick, MonoPickJob, k_mono_pick_b, 256)
+MONO_BATCHED(b_mono_plane, MonoPlaneJob, k_mono_plane_b, 64)
+#undef MONO_BATCHED
 
 }  // namespace
 
+// With a recorder installed on the calling thread (a lockstep call, batch_rec.h) the launchers append their jobs to
+// it instead of launching, exactly as the vlaunch_* launchers of vo_kernels.hip do.
 void mlaunch_ransac(void* stream, const float* q4, int32_t N, const int32_t* samples, int32_t iters, double thr,
                     double* F, int32_t* counts, int32_t* out_sel, uint8_t* out_flags, int32_t* out_counts) {
     hipStream_t s = (hipStream_t)stream;
     const float4* q = reinterpret_cast<const float4*>(q4);
-    if (iters > 0) {
-        k_mono_hyp<<<(iters + HYP_LANES - 1) / HYP_LANES, HYP_LANES, 0, s>>>(q, N, samples, iters, F);
-        k_mono_vote<<<iters, 64, 0, s>>>(q, N, F, thr, counts);
+    const MonoHypJob ah = {q, samples, F, N, iters};
+    const MonoVoteJob av = {q, F, counts, thr, N, iters};
+    const MonoSelectJob as = {counts, F, q, out_sel, out_flags, out_counts, thr, N, iters};
+    const unsigned gh = (unsigned)((iters + HYP_LANES - 1) / HYP_LANES);
+    if (t_rec) {
+        if (iters > 0) {
+            t_rec->add(b_mono_hyp, ah, gh);
+            t_rec->add(b_mono_vote, av, (unsigned)iters);
+        }
+        return t_rec->add(b_mono_select, as, 1);
     }
-    k_mono_select<<<1, 256, 0, s>>>(counts, iters, F, q, N, thr, out_sel, out_flags, out_counts);
+    if (iters > 0) {
+        k_mono_hyp<<<gh, HYP_LANES, 0, s>>>(ah);
+        k_mono_vote<<<iters, 64, 0, s>>>(av);
+    }
+    k_mono_select<<<1, 256, 0, s>>>(as);
 }
 
 void mlaunch_chiral(void* stream, const float* m4, int32_t N, const double* cams, double* X, uint8_t* front,
                     double* out_X, int32_t* out_cand) {
     hipStream_t s = (hipStream_t)stream;
     const float4* m = reinterpret_cast<const float4*>(m4);
-    k_mono_chiral<<<(4 * N + CHI_LANES - 1) / CHI_LANES, CHI_LANES, 0, s>>>(m, N, cams, X, front);
-    k_mono_pick<<<1, 256, 0, s>>>(X, front, N, out_X, out_cand);
+    const MonoChiralJob ac = {m, cams, X, front, N};
+    const MonoPickJob ap = {X, front, out_X, out_cand, N};
+    const unsigned gc = (unsigned)((4 * N + CHI_LANES - 1) / CHI_LANES);
+    if (t_rec) {
+        t_rec->add(b_mono_chiral, ac, gc);
+        return t_rec->add(b_mono_pick, ap, 1);
+    }
+    k_mono_chiral<<<gc, CHI_LANES, 0, s>>>(ac);
+    k_mono_pick<<<1, 256, 0, s>>>(ap);
 }
 
 void mlaunch_plane(void* stream, const double* d, int32_t n, double weight, double thr, double* sums) {
-    k_mono_plane<<<(n + 63) / 64, 64, 0, (hipStream_t)stream>>>(d, n, weight, thr, sums);
+    const MonoPlaneJob a = {d, sums, weight, thr, n};
+    const unsigned g = (unsigned)((n + 63) / 64);
+    if (t_rec) return t_rec->add(b_mono_plane, a, g);
+    k_mono_plane<<<g, 64, 0, (hipStream_t)stream>>>(a);
 }
 
 }  // namespace svh

@@ -550,6 +550,96 @@ class VoMono:
         self.lib.svh_vo_mono_get_votes(self.h, _ptr(out), n)
         return out[:n]
 
+    # ---- K objects in lockstep (svh_vo_mono_*_batch): static methods over a list of VoMono objects
+    @staticmethod
+    def _batch_args(objs):
+        L = objs[0].lib if objs else lib()
+        K = len(objs)
+        return L, K, (C.c_void_p * max(K, 1))(*[o.h for o in objs])
+
+    @staticmethod
+    def _frames(frames, hold):
+        """K contiguous uint8 images as a pointer array + dims; `hold` keeps the arrays alive (a frame handed over
+        early is read by the library until it is taken)"""
+        ims = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        hold[:] = ims
+        dims = (C.c_int32 * 3)(ims[0].shape[1], ims[0].shape[0], ims[0].shape[1])
+        return (C.c_void_p * len(ims))(*[a.ctypes.data for a in ims]), dims
+
+    @staticmethod
+    def _replace(replace, K):
+        if replace is None:
+            return None
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(replace, np.int32), (K,)))
+        return r
+
+    @staticmethod
+    def process_batch(objs, frames, replace=None, shape=None):
+        """svh_vo_mono_process_batch: one frame per object; replace: per object (or one value, or None).  frames=None
+        (+ shape=(h, w)): the objects take the frame handed over by prefetch_batch.  Returns the list of per-object
+        results (bool)."""
+        L, K, hs = VoMono._batch_args(objs)
+        hold = []
+        if frames is not None:
+            ptrs, dims = VoMono._frames(frames, hold)
+        else:
+            ptrs, dims = None, (C.c_int32 * 3)(shape[1], shape[0], shape[1])
+        r = VoMono._replace(replace, K)
+        ok = np.zeros(max(K, 1), np.int32)
+        L.svh_vo_mono_process_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = L.svh_vo_mono_process_batch(hs, K, ptrs, dims, None if r is None else _ptr(r), _ptr(ok))
+        if rc < 0:
+            raise SvhError(rc, last_error())
+        return [bool(x) for x in ok[:K]]
+
+    @staticmethod
+    def prefetch_batch(objs, frames):
+        """svh_vo_mono_prefetch_batch: the next frame of every object handed over early (returns at once)"""
+        L, K, hs = VoMono._batch_args(objs)
+        hold = []
+        ptrs, dims = VoMono._frames(frames, hold)
+        for o in objs:
+            o._next_frames = hold
+        L.svh_vo_mono_prefetch_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        rc = L.svh_vo_mono_prefetch_batch(hs, K, ptrs, dims)
+        if rc < 0:
+            raise SvhError(rc, last_error())
+
+    @staticmethod
+    def process_next_batch(objs, next_frames, shape, replace=None):
+        """svh_vo_mono_process_next_batch: process the frame handed over before, hand over next_frames (None after
+        the last frame); shape = (h, w) of the images"""
+        L, K, hs = VoMono._batch_args(objs)
+        hold = []
+        ptrs = None
+        dims = (C.c_int32 * 3)(shape[1], shape[0], shape[1])
+        if next_frames is not None:
+            ptrs, dims = VoMono._frames(next_frames, hold)
+        r = VoMono._replace(replace, K)
+        ok = np.zeros(max(K, 1), np.int32)
+        L.svh_vo_mono_process_next_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        rc = L.svh_vo_mono_process_next_batch(hs, K, ptrs, dims, None if r is None else _ptr(r), _ptr(ok))
+        for o in objs:   # (the frame taken by this call is no longer read; the new one is held instead)
+            o._next_frames = hold
+        if rc < 0:
+            raise SvhError(rc, last_error())
+        return [bool(x) for x in ok[:K]]
+
+    @staticmethod
+    def process_matches_batch(objs, matches):
+        """svh_vo_mono_process_matches_batch: VisualOdometry::process(p_matched) per object, each with its own list"""
+        L, K, hs = VoMono._batch_args(objs)
+        ms = [np.ascontiguousarray(m, P_MATCH) for m in matches]
+        ptrs = (C.c_void_p * max(K, 1))(*[m.ctypes.data if len(m) else None for m in ms])
+        n = np.array([len(m) for m in ms] + [0], np.int32)
+        ok = np.zeros(max(K, 1), np.int32)
+        L.svh_vo_mono_process_matches_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = L.svh_vo_mono_process_matches_batch(hs, K, ptrs, _ptr(n), _ptr(ok))
+        if rc < 0:
+            raise SvhError(rc, last_error())
+        return [bool(x) for x in ok[:K]]
+
     def set_timing(self, on=True):
         self.lib.svh_vo_mono_set_timing(self.h, int(on))
 

@@ -11,7 +11,10 @@
 // that each drive K/2 objects in lockstep through svh_vo_process_batch (recorder, helper pool, phase barriers), and
 // two threads that each drive a Reconstruction (track table, undo of a failed update, growth of the resident arrays),
 // and two threads that each drive PlaneEstimation objects (single calls on host maps and a batch of three; the cache
-// of raw draws, the transaction of a failed call, svh_plane_release).
+// of raw draws, the transaction of a failed call, svh_plane_release), and two threads that each drive three
+// VisualOdometryMono objects in lockstep (svh_vo_mono_process_batch with per-object replace, the pipelined loop and
+// svh_vo_mono_process_matches_batch with lists of different lengths: the per-phase live lists, the host steps on the
+// helper pool, the drain behind a failed phase).
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -395,6 +398,67 @@ int main(int argc, char** argv) {
     };
     th.emplace_back(planes, 1);
     th.emplace_back(planes, 2);
+    // two threads with three mono objects each in lockstep; thread 1 with private streams (parallel preparation),
+    // thread 2 with libc rand() and the pipelined loop
+    auto mono = [&](int id) {
+        svh_vo_mono_params p;
+        svh_vo_mono_params_default(&p);
+        p.f = 645.2; p.cu = 320.0; p.cv = 100.0; p.height = 1.6; p.pitch = -0.08;
+        p.ransac_iters = 50;
+        p.motion_threshold = 1e6;
+        svh_vo* vs[3];
+        for (int i = 0; i < 3; i++) {
+            vs[i] = svh_vo_mono_create(&p);
+            if (!vs[i]) { bad++; return; }
+            if (id == 1) svh_vo_set_private_rand(vs[i], 1, (uint32_t)i);
+        }
+        std::vector<std::vector<uint8_t>> I[2];
+        for (int q = 0; q < 2; q++) I[q].assign(3, std::vector<uint8_t>((size_t)W * H));
+        const uint8_t* ptr[3];
+        int32_t ok[3] = {0, 0, 0}, replace[3] = {0, 0, 0};
+        const int32_t dims[3] = {W, H, W};
+        for (int f = 0; f < frames; f++) {
+            for (int i = 0; i < 3; i++) {
+                std::vector<uint8_t>& img = I[f & 1][i];
+                for (size_t j = 0; j < img.size(); j++) img[j] = (uint8_t)(svh::mix((uint32_t)(j + 977 * f + 31 * i + 9001 * id)) >> 24);
+                ptr[i] = img.data();
+                replace[i] = f > 1 && (f + i) % 3 == 0;
+            }
+            if (id == 1) {
+                check(svh_vo_mono_process_batch(vs, 3, ptr, dims, replace, ok));
+            } else if (f == 0) {
+                check(svh_vo_mono_prefetch_batch(vs, 3, ptr, dims));
+            } else {
+                const int32_t rc = svh_vo_mono_process_next_batch(vs, 3, ptr, dims, replace, ok);
+                check(rc);
+                if (rc < 0 && inject) (void)svh_vo_mono_prefetch_batch(vs, 3, ptr, dims);
+            }
+            // the estimate alone: 9 (leaves at once), 40 and 300 matches side by side
+            std::vector<svh_p_match> m[3];
+            const int nm[3] = {9, 40, 300};
+            const svh_p_match* mp[3];
+            int32_t n[3];
+            for (int i = 0; i < 3; i++) {
+                for (int k = 0; k < nm[i]; k++) {
+                    svh_p_match q;
+                    memset(&q, 0, sizeof(q));
+                    q.u1p = (float)(svh::mix((uint32_t)(k + 17 * f + i)) % 600u); q.v1p = (float)(svh::mix((uint32_t)(3 * k + f)) % 180u);
+                    q.u1c = q.u1p + 2.f + (float)(k % 3); q.v1c = q.v1p + 1.f;
+                    m[i].push_back(q);
+                }
+                mp[i] = m[i].data();
+                n[i] = nm[i];
+            }
+            const int32_t rc = svh_vo_mono_process_matches_batch(vs, 3, mp, n, ok);
+            check(rc);
+            if (rc >= 0 && ok[0] != 0) bad++;   // (N < 10 never succeeds)
+            int32_t votes[64];
+            for (int i = 0; i < 3; i++) matches += svh_vo_mono_get_votes(vs[i], votes, 64) + svh_vo_get_inliers(vs[i], nullptr, 0);
+        }
+        for (svh_vo* v : vs) svh_vo_destroy(v);
+    };
+    th.emplace_back(mono, 1);
+    th.emplace_back(mono, 2);
     for (std::thread& t : th) t.join();
     printf("sanitize_viso: %d sequences x %d frames + 1 Matcher thread + 2 lockstep threads, %ld matches seen, %d failures"
            ", %ld injected HIP failures reported\n", K, frames, matches.load(), bad.load(), injected.load());
