@@ -4,8 +4,9 @@
  * class Reconstruction with the reference's public interface (:35-69): point3d, setCalibration(f,cu,cv),
  * update(p_matched,Tr,point_type=1,min_track_length=2,max_dist=30,min_angle=2) and getPoints(), over the svh_recon_*
  * entries of svh.h, so a caller written against the reference (e.g. matlab/reconstructionMex.cpp, the loop of
- * matlab/demo_structure_from_motion.m) compiles unchanged and runs on the MI355X: the tracks are kept on the host,
- * every lost track is triangulated, refined and tested on the device (reconstruction.cpp:131-349).
+ * matlab/demo_structure_from_motion.m) compiles unchanged and runs on the MI355X: the tracks are kept on the host
+ * (or, with the opt-in constructor argument, in device memory), every lost track is triangulated, refined and tested
+ * on the device (reconstruction.cpp:131-349).
  *
  * Two misuses the reference leaves undefined are refused (the call does nothing): update() before
  * setCalibration() (P_total is empty there) and a second setCalibration() (it would misalign P_total).
@@ -24,6 +25,9 @@
 class Reconstruction {
 public:
     Reconstruction() : _r(svh_recon_create()) {}
+    // extension: resident = true keeps the track table in device memory for the object's lifetime
+    // (svh_recon_create_resident, svh.h); such objects can be updated K at a time by svh_recon_update_batch(handle()s)
+    explicit Reconstruction(bool resident) : _r(resident ? svh_recon_create_resident() : svh_recon_create()) {}
     ~Reconstruction() { svh_recon_destroy(_r); }
 
     // a generic 3d point

@@ -596,9 +596,11 @@ int32_t svh_vo_mono_process_matches_batch(svh_vo* const* vs, int32_t K, const sv
 
 /* ------------------------------------------------------------------------
  * Reconstruction -- libviso2/src/reconstruction.h:35-69: multi-view 3-D points from monocular flow matches and the
- * egomotion between the two frames.  The track bookkeeping (reconstruction.cpp:59-126) runs on the host; every
- * track lost in an update is triangulated, classified, refined (Gauss-Newton over all its frames) and tested on the
- * device, and the accepted points are appended, in the reference's order, to an array that stays on the device.
+ * egomotion between the two frames.  The track bookkeeping (reconstruction.cpp:59-126) runs on the host, or on the
+ * device for an object of svh_recon_create_resident; every track lost in an update is triangulated, classified,
+ * refined (Gauss-Newton over all its frames) and tested on the device, and the accepted points are appended, in the
+ * reference's order, to an array that stays on the device.  Without a device the compute entries of a resident
+ * object return SVH_ERR_NO_DEVICE.
  * ------------------------------------------------------------------------ */
 typedef struct svh_recon svh_recon;
 /* what became of a lost track, in the order update() tests (reconstruction.cpp:131-141) */
@@ -612,6 +614,12 @@ enum {
     SVH_RECON_ACCEPTED = 6        /* appended to the points                                   */
 };
 svh_recon* svh_recon_create(void);                                   /* Reconstruction() */
+/* The same object with its track table RESIDENT in device memory, for its lifetime: the association of matches to
+ * tracks, the active / lost split and the compaction of the tracks run as kernels, an update is one copy of the
+ * matches, seven launches and one wait, and K such objects are updated in lockstep by svh_recon_update_batch.  The pose
+ * chain stays on the host.  Every entry below answers on such an object as on one of svh_recon_create; results are
+ * the same bit for bit.  A feature index must be below 2^26 (the index table is an array in device memory). */
+svh_recon* svh_recon_create_resident(void);
 void       svh_recon_destroy(svh_recon*);
 /* setCalibration(f,cu,cv) -- reconstruction.cpp:40-57.  Once per object: a second call returns SVH_ERR_BAD_ARG (in
  * the reference it pushes a second P_total[0] and misaligns every later frame). */
@@ -623,6 +631,23 @@ int32_t    svh_recon_set_calibration(svh_recon*, double f, double cu, double cv)
  * before the call. */
 int32_t    svh_recon_update(svh_recon*, const svh_p_match* m, int32_t n, const double Tr[16],
                             int32_t point_type, int32_t min_track_length, double max_dist, double min_angle);
+/* svh_recon_update on a resident object with the matches already in device memory (n svh_p_match records, complete
+ * before the call; they are read until it returns).  max_index: every i1p and i1c lies in [0, max_index); one that
+ * does not is found on the device, the call returns SVH_ERR_BAD_ARG and the object is what it was.  SVH_ERR_BAD_ARG
+ * on an object of svh_recon_create. */
+int32_t    svh_recon_update_device(svh_recon*, const svh_p_match* d_matches, int32_t n, int32_t max_index,
+                                   const double Tr[16], int32_t point_type, int32_t min_track_length,
+                                   double max_dist, double min_angle);
+/* K resident objects of one device updated in lockstep: object i gets the n[i] matches m[i] (host memory) and the
+ * motion Tr + 16 i; one launch per kernel for all of them and one wait, on the first object's stream.  m[i] == NULL:
+ * object i sits this update out (demo_structure_from_motion.m skips the reconstruction of a frame whose odometry
+ * failed); an empty update is a non-NULL m[i] with n[i] == 0.  status (K values, may be NULL) receives each object's
+ * own result: SVH_OK (also for one that sat out) or SVH_ERR_BAD_ARG for its matches, in which case it is unchanged
+ * and the others are updated.  Returns SVH_OK, or: SVH_ERR_BAD_ARG for a NULL, repeated, uncalibrated or host-table
+ * object or objects of different devices (nothing is done); SVH_ERR_HIP, after which every object is what it was. */
+int32_t    svh_recon_update_batch(svh_recon* const* r, const svh_p_match* const* m, const int32_t* n, const double* Tr,
+                                  int32_t K, int32_t point_type, int32_t min_track_length, double max_dist,
+                                  double min_angle, int32_t* status);
 int32_t    svh_recon_num_points(svh_recon*);
 /* getPoints(): x y z per point.  _get_points copies up to cap points to the host and returns the number there are;
  * _get_points_device hands out the resident array itself (no copy; valid until the next update) */

@@ -659,12 +659,20 @@ RECON_ACCEPTED = 6
 
 class Reconstruction:
     """Drop-in for the reference class Reconstruction (libviso2/src/reconstruction.h): set_calibration(f, cu, cv)
-    once, update(matches, Tr, ...) per frame pair, points().  The tracks live on the host; every lost track is
-    triangulated, refined and tested on the device and the accepted points stay there."""
+    once, update(matches, Tr, ...) per frame pair, points().  The tracks live on the host, or with resident=True in
+    device memory (svh_recon_create_resident: the association runs as kernels, and K such objects are updated in
+    lockstep by Reconstruction.update_batch); every lost track is triangulated, refined and tested on the device and
+    the accepted points stay there.  Both forms give the same results."""
 
-    def __init__(self):
+    def __init__(self, resident=False):
         L = self.lib = lib()
         L.svh_recon_create.restype = C.c_void_p
+        L.svh_recon_create_resident.restype = C.c_void_p
+        L.svh_recon_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.c_int32, C.c_double, C.c_double]
+        L.svh_recon_update_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_double, C.c_double, C.c_void_p]
+        self.resident = bool(resident)
         L.svh_recon_destroy.argtypes = [C.c_void_p]
         L.svh_recon_set_calibration.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
         L.svh_recon_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
@@ -676,7 +684,7 @@ class Reconstruction:
         L.svh_recon_get_outcomes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
         L.svh_recon_set_timing.argtypes = [C.c_void_p, C.c_int32]
         L.svh_recon_get_timing.argtypes = [C.c_void_p, C.c_void_p]
-        self.h = L.svh_recon_create()
+        self.h = L.svh_recon_create_resident() if resident else L.svh_recon_create()
         if not self.h:
             raise SvhError(ERR_BAD_ARG, last_error())
 
@@ -705,6 +713,40 @@ class Reconstruction:
             raise SvhError(ERR_BAD_ARG, "Tr must be 4x4")
         self._check(self.lib.svh_recon_update(self.h, _ptr(m) if len(m) else None, len(m), _ptr(T), int(point_type),
                                               int(min_track_length), float(max_dist), float(min_angle)))
+
+    def update_device(self, d_matches, n, max_index, Tr, point_type=1, min_track_length=2, max_dist=30.0,
+                      min_angle=2.0):
+        """svh_recon_update_device (resident objects): d_matches is the device address of n svh_p_match records whose
+        feature indices lie in [0, max_index)"""
+        T = np.ascontiguousarray(Tr, np.float64)
+        if T.shape != (4, 4):
+            raise SvhError(ERR_BAD_ARG, "Tr must be 4x4")
+        self._check(self.lib.svh_recon_update_device(self.h, d_matches, int(n), int(max_index), _ptr(T),
+                                                     int(point_type), int(min_track_length), float(max_dist),
+                                                     float(min_angle)))
+
+    @staticmethod
+    def update_batch(objs, matches, Trs, point_type=1, min_track_length=2, max_dist=30.0, min_angle=2.0):
+        """svh_recon_update_batch: K resident objects in lockstep.  matches[i]: the matches of object i, or None for an
+        object that sits this update out; Trs: K 4x4 motions (the entry of an object that sits out is not read).
+        Returns the per-object status list; raises SvhError when the call as a whole is refused or fails."""
+        L = objs[0].lib if objs else lib()
+        K = len(objs)
+        hs = (C.c_void_p * max(K, 1))(*[o.h for o in objs])
+        ms = [None if m is None else np.ascontiguousarray(m, P_MATCH) for m in matches]
+        hold = [np.zeros(1, P_MATCH) if m is not None and len(m) == 0 else m for m in ms]   # (empty: still non-NULL)
+        ptrs = (C.c_void_p * max(K, 1))(*[None if m is None else m.ctypes.data for m in hold])
+        n = np.array([0 if m is None else len(m) for m in ms] + [0], np.int32)
+        T = np.ascontiguousarray(np.stack([np.eye(4) if t is None else np.asarray(t, np.float64) for t in Trs])
+                                 if K else np.zeros((1, 4, 4)), np.float64)
+        if T.shape != (max(K, 1), 4, 4):
+            raise SvhError(ERR_BAD_ARG, "Trs must be K 4x4 matrices")
+        status = np.zeros(max(K, 1), np.int32)
+        rc = L.svh_recon_update_batch(hs, ptrs, _ptr(n), _ptr(T), K, int(point_type), int(min_track_length),
+                                      float(max_dist), float(min_angle), _ptr(status))
+        if rc < 0:
+            raise SvhError(rc, last_error())
+        return [int(x) for x in status[:K]]
 
     def num_points(self):
         return self.lib.svh_recon_num_points(self.h)

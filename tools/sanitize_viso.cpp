@@ -10,6 +10,8 @@
 // once (SURVEY 8(e) "replicas only"), one thread that creates and destroys Matchers meanwhile, and two threads
 // that each drive K/2 objects in lockstep through svh_vo_process_batch (recorder, helper pool, phase barriers), and
 // two threads that each drive a Reconstruction (track table, undo of a failed update, growth of the resident arrays),
+// one thread with a resident-table Reconstruction beside a host-table one and one with three resident objects in lockstep
+// (svh_recon_update_batch: double-buffered table, job table, an object sitting out, the way back from a failed batch),
 // and two threads that each drive PlaneEstimation objects (single calls on host maps and a batch of three; the cache
 // of raw draws, the transaction of a failed call, svh_plane_release), and two threads that each drive three
 // VisualOdometryMono objects in lockstep (svh_vo_mono_process_batch with per-object replace, the pipelined loop and
@@ -31,6 +33,7 @@
 #include "../include/svh_plane.h"
 #include "../stereo-vision_amd/csrc/matcher_internal.h"
 #include "../stereo-vision_amd/csrc/plane_internal.h"
+#include "../stereo-vision_amd/csrc/recon_internal.h"
 #include "../stereo-vision_amd/csrc/vo_internal.h"
 
 // ---------------------------------------------------------------- stub HIP runtime
@@ -200,6 +203,65 @@ void rlaunch_tracks(void*, const int32_t* offs, const int32_t*, const int32_t*, 
     }
     out_count[0] = n_points;
 }
+// the resident form (recon_internal.h): the seven kernels' work over each job, serially, with the outcome rule above
+void rlaunch_resident(void*, const ReconJob* jobs, int32_t K, int32_t, int32_t, int32_t, uint32_t) {
+    for (int32_t k = 0; k < K; k++) {
+        const ReconJob& a = jobs[k];
+        for (int seg = 0; seg < 2; seg++)
+            if (a.up_bytes[seg]) memcpy(a.up_dst[seg], a.up_src[seg], a.up_bytes[seg]);
+        for (int32_t i = 0; i < a.tbl; i++) a.track_idx[i] = -1;
+        for (int32_t t = 0; t < a.n_old; t++) a.claim[t] = INT32_MAX;
+        for (int i = 0; i < RT_HDR; i++) a.hdr[i] = 0;
+        for (int32_t t = 0; t < a.n_old; t++)
+            if (a.a_last[t] >= 0 && a.a_last[t] < a.tbl && a.track_idx[a.a_last[t]] < t) a.track_idx[a.a_last[t]] = t;
+        for (int32_t i = 0; i < a.n; i++) {
+            int32_t idx = -1;
+            if (a.m[i].i1p < 0 || a.m[i].i1p >= a.max_index || a.m[i].i1c < 0 || a.m[i].i1c >= a.max_index)
+                a.hdr[RT_ERROR] |= RT_BAD_INDEX;
+            else
+                idx = a.track_idx[a.m[i].i1p];
+            if (idx >= 0 && a.claim[idx] > i) a.claim[idx] = i;
+            a.midx[i] = idx;
+        }
+        int32_t nb = 0, px = 0, n_lost = 0, points = a.n_points;
+        if (!a.hdr[RT_ERROR]) {
+            auto put = [&](const float* from, int32_t len, const svh_p_match& q, int32_t first) {
+                a.b_offs[nb] = px;
+                if (from) memcpy(a.b_px + 2 * (size_t)px, from, 8 * (size_t)len);
+                px += len;
+                if (!from) { a.b_px[2 * (size_t)px] = q.u1p; a.b_px[2 * (size_t)px + 1] = q.v1p; px++; }
+                a.b_px[2 * (size_t)px] = q.u1c; a.b_px[2 * (size_t)px + 1] = q.v1c; px++;
+                a.b_first[nb] = first;
+                a.b_last[nb++] = q.i1c;
+            };
+            for (int32_t t = 0; t < a.n_old; t++) {
+                if (a.claim[t] != INT32_MAX)
+                    put(a.a_px + 2 * (size_t)a.a_offs[t], a.a_offs[t + 1] - a.a_offs[t], a.m[a.claim[t]], a.a_first[t]);
+                else
+                    a.lost[n_lost++] = t;
+            }
+            a.hdr[RT_EXTENDED] = nb;
+            for (int32_t i = 0; i < a.n; i++)
+                if (!(a.midx[i] >= 0 && a.claim[a.midx[i]] == i)) put(nullptr, 0, a.m[i], a.frame_prev);
+            a.b_offs[nb] = px;
+            a.hdr[RT_CREATED] = nb - a.hdr[RT_EXTENDED];
+            a.hdr[RT_LOST] = n_lost;
+            a.hdr[RT_PIXELS] = px;
+            for (int32_t g = 0; g < n_lost; g++) {
+                const int32_t t = a.lost[g];
+                const bool take = g % 3 == 0 && a.a_offs[t + 1] - a.a_offs[t] >= 2;
+                a.code[g] = a.out_code[g] = take ? 6 : 5;
+                for (int c = 0; c < 3; c++)
+                    a.xyz[3 * g + c] = a.out_xyz[3 * g + c] = c < 2 ? a.a_px[2 * (size_t)a.a_offs[t] + c] : 1.f;
+                if (take) {
+                    for (int c = 0; c < 3; c++) a.points[3 * (size_t)points + c] = a.xyz[3 * g + c];
+                    points++;
+                }
+            }
+        }
+        for (int i = 0; i < RT_HDR; i++) a.out_hdr[i] = i == RT_POINTS ? points : a.hdr[i];
+    }
+}
 // PlaneEstimation (plane_engine.cpp): the kernels' work with plane_core.h on the host ("device" memory is host memory)
 void planelaunch_grid(void*, const PlaneDev& P, int32_t nmaps, const plane::Lattice& L, int32_t step, int32_t row0) {
     for (int32_t m = 0; m < nmaps; m++) {
@@ -366,6 +428,79 @@ int main(int argc, char** argv) {
     };
     th.emplace_back(reconstruct, 1);
     th.emplace_back(reconstruct, 2);
+    // the resident form: one thread with a resident object next to a host-table object fed the same updates (their
+    // track and point counts must agree), one thread with three resident objects in lockstep, one of which sits every
+    // fourth update out, and a batch that is refused
+    auto recon_matches = [&](int f, int id, int n) {
+        std::vector<svh_p_match> m;
+        for (int i = 0; i < n && f % 7 != 5; i++) {
+            if (svh::mix((uint32_t)(i + 131 * f + 7 * id)) % 5u == 0) continue;
+            svh_p_match q;
+            memset(&q, 0, sizeof(q));
+            q.u1p = 10.f + i + f; q.v1p = 20.f + (i % 37); q.i1p = i;
+            q.u1c = q.u1p + 1.f;  q.v1c = q.v1p;           q.i1c = i % 3 ? i : i + 1;   // some tracks end on one index
+            m.push_back(q);
+        }
+        return m;
+    };
+    auto resident = [&](int id) {
+        const double Tr[16] = {1, 0, 0, 0.05, 0, 1, 0, 0, 0, 0, 1, -0.8, 0, 0, 0, 1};
+        svh_recon* r = svh_recon_create_resident();
+        svh_recon* h = svh_recon_create();
+        if (!r || !h) { bad++; return; }
+        if (svh_recon_update(r, nullptr, 0, Tr, 1, 2, 30, 2) != SVH_ERR_BAD_ARG) bad++;   // not calibrated yet
+        check(svh_recon_set_calibration(r, 645.2, 635.9, 194.1));
+        check(svh_recon_set_calibration(h, 645.2, 635.9, 194.1));
+        for (int f = 0; f < 3 * frames; f++) {
+            const std::vector<svh_p_match> m = recon_matches(f, id, 600);
+            int32_t a, b;
+            // (an update that failed is given again: both objects then stay in step)
+            for (int k = 0; k < 50 && (a = svh_recon_update(r, m.data(), (int32_t)m.size(), Tr, 1, 2, 30, 2)) == SVH_ERR_HIP; k++) {}
+            for (int k = 0; k < 50 && (b = svh_recon_update(h, m.data(), (int32_t)m.size(), Tr, 1, 2, 30, 2)) == SVH_ERR_HIP; k++) {}
+            check(a);
+            check(b);
+            if (a == SVH_OK && b == SVH_OK &&
+                (svh_recon_num_tracks(r) != svh_recon_num_tracks(h) || svh_recon_num_points(r) != svh_recon_num_points(h)))
+                bad++;
+            std::vector<float> p(3 * (size_t)svh_recon_num_points(r) + 3);
+            check(svh_recon_get_points(r, p.data(), svh_recon_num_points(r)));
+            matches += svh_recon_num_tracks(r);
+        }
+        svh_recon_destroy(r);
+        svh_recon_destroy(h);
+    };
+    th.emplace_back(resident, 3);
+    auto recon_batch = [&](int id) {
+        double Tr[3 * 16];
+        for (int i = 0; i < 3; i++) {
+            const double one[16] = {1, 0, 0, 0.05, 0, 1, 0, 0, 0, 0, 1, -0.8 - 0.1 * i, 0, 0, 0, 1};
+            memcpy(Tr + 16 * i, one, sizeof(one));
+        }
+        svh_recon* rs[3] = {svh_recon_create_resident(), svh_recon_create_resident(), svh_recon_create_resident()};
+        svh_recon* h = svh_recon_create();
+        if (!rs[0] || !rs[1] || !rs[2] || !h) { bad++; return; }
+        for (svh_recon* r : rs) check(svh_recon_set_calibration(r, 645.2, 635.9, 194.1));
+        check(svh_recon_set_calibration(h, 645.2, 635.9, 194.1));
+        for (int f = 0; f < 3 * frames; f++) {
+            std::vector<svh_p_match> m[3] = {recon_matches(f, id, 600), recon_matches(f, id + 1, 450), recon_matches(f, id + 2, 90)};
+            static const svh_p_match none = {};
+            const svh_p_match* mp[3];
+            for (int i = 0; i < 3; i++) mp[i] = m[i].empty() ? &none : m[i].data();   // (empty: an update all the same)
+            if (f % 4 == 3) mp[1] = nullptr;                                          // sits this one out
+            const int32_t n[3] = {(int32_t)m[0].size(), (int32_t)m[1].size(), (int32_t)m[2].size()};
+            int32_t st[3] = {0, 0, 0};
+            const int32_t before = svh_recon_num_tracks(rs[1]);
+            const int32_t rc = svh_recon_update_batch(rs, mp, n, Tr, 3, 1, 2, 30, 2, st);
+            check(rc);
+            if (rc == SVH_OK && f % 4 == 3 && svh_recon_num_tracks(rs[1]) != before) bad++;
+            svh_recon* mixed[2] = {rs[0], h};
+            if (svh_recon_update_batch(mixed, mp, n, Tr, 2, 1, 2, 30, 2, st) != SVH_ERR_BAD_ARG) bad++;
+            matches += svh_recon_num_tracks(rs[2]);
+        }
+        for (svh_recon* r : rs) svh_recon_destroy(r);
+        svh_recon_destroy(h);
+    };
+    th.emplace_back(recon_batch, 4);
     // two threads with PlaneEstimation objects: a road (d grows with v) with a hashed ripple, host maps, changing
     // seeds, a batch of three objects over the same map, release in between
     auto planes = [&](int id) {
