@@ -3,7 +3,8 @@
 // srand(0), normalizeFeaturePoints, then per iteration getRandomSample(N, 8) (viso.cpp:130-153, libc rand()),
 // the 8x9 SVD, the rank-2 SVD and the Sampson vote.  The SVD state is interleaved with stride S (argv[3]) exactly
 // as a kernel lane keeps it in LDS, so the index arithmetic of the device layout is exercised too.
-//   mono_core_check <matches.bin> <ransac_iters> <S> <inlier_threshold>
+//   mono_core_check <matches.bin> <ransac_iters> <S> <inlier_threshold> [first]
+// first (default 0): the winner is looked for among the hypotheses from `first` on; all votes are listed all the same.
 // matches.bin: int32 N, N x p_match (48 bytes).  Output (stdout, binary): int32 iters, iters x int32 votes,
 // int32 n, n x int32 (the inliers of the first hypothesis with the most votes, in index order).
 #include <stdio.h>
@@ -26,6 +27,7 @@ int main(int argc, char** argv) {
     fclose(f);
     const int iters = atoi(argv[2]), S = atoi(argv[3]);
     const double thr = atof(argv[4]);
+    const int first = argc > 5 ? atoi(argv[5]) : 0;
     std::vector<float> q((size_t)N * 4);
     for (int i = 0; i < N; i++) {
         q[4 * i + 0] = raw[12 * i + 0];
@@ -65,7 +67,7 @@ int main(int argc, char** argv) {
             for (int i = 0; i < N; i++)
                 if (sampson_inlier(F, q[4 * i], q[4 * i + 1], q[4 * i + 2], q[4 * i + 3], thr)) cur.push_back(i);
             votes.push_back((int32_t)cur.size());
-            if (cur.size() > best.size()) best = cur;
+            if (k >= first && cur.size() > best.size()) best = cur;
         }
     }
     int32_t n = (int32_t)votes.size();

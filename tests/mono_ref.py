@@ -169,3 +169,50 @@ def estimate_cases():
     cases.append(("no_plane", param_vector(dict(DEMO, pitch=0.0, motion_threshold=1e6)),
                   synth_scene(300, 9, above=True, outliers=0.0)))   # no d > median/threshold: best_idx stays 0
     return cases
+
+
+# ------------------------------------------------------------------------------------------------------------ edges
+# tests/golden/vo_mono_edges.npz (make_goldens_mono_edges.py): estimate-only cases at the sizes the kernels of
+# vo_mono_kernels.hip stride by, and cases in which several RANSAC hypotheses reach the largest inlier count.
+EDGE_GOLDEN = os.path.join(H.GOLDEN, "vo_mono_edges.npz")
+EDGE_N = (63, 64, 65, 255, 256, 257, 1024)          # k_mono_vote strides N by 64, k_mono_select / k_mono_pick by 256
+EDGE_ITERS = (0, 1, 31, 32, 33, 255, 256, 257)      # k_mono_hyp packs 32 hypotheses, k_mono_select strides by 256
+EDGE_ITERS_N = 300
+# (name, N, seed, inlier_threshold): noiseless inliers, half the matches random pairs.  The seeds were searched on the
+# reference (make_goldens_mono_edges.py --search) until its votes met tie_of() below and
+# tests/test_vo_mono_edges.py found the tied hypotheses' inlier sets different
+EDGE_TIES = (("tie_low", 200, 256, 1e-4), ("tie_high", 200, 161, 1e-4), ("tie_loose", 120, 168, 1e-3))
+
+
+def tie_of(votes):
+    """(h0, h1, count, how many reach it): h0 the first hypothesis with the most inliers, h1 the first later one with
+    as many in a lower lane of k_mono_select (h1 % 256 < h0 % 256); None when there is no such h1.  A reduction that
+    prefers the lower lane to the lower index returns h1."""
+    if len(votes) == 0:
+        return None
+    most = np.flatnonzero(votes == votes.max())
+    later = [int(h) for h in most[1:] if h % 256 < most[0] % 256]
+    return (int(most[0]), later[0], int(votes.max()), len(most)) if later else None
+
+
+def lane_winners(votes, lanes=256):
+    """what a reduction over `lanes` lanes returns when it breaks ties by lane instead of by index: every lane keeps
+    the first of its maxima, then the lowest lane wins, or the highest"""
+    most = np.flatnonzero(votes == votes.max())
+    kept = {}
+    for h in most:
+        kept.setdefault(int(h) % lanes, int(h))
+    return kept[min(kept)], kept[max(kept)]
+
+
+def edge_cases():
+    """(name, parameter vector, matches) of vo_mono_edges.npz"""
+    cases = []
+    for k, n in enumerate(EDGE_N):
+        cases.append(("n%d" % n, param_vector(DEMO), synth_scene(n, 40 + k)))
+    for it in EDGE_ITERS:
+        cases.append(("iters%d" % it, param_vector(dict(DEMO, ransac_iters=it)), synth_scene(EDGE_ITERS_N, 60, noise=0.1)))
+    for name, n, seed, thr in EDGE_TIES:
+        cases.append((name, param_vector(dict(DEMO, inlier_threshold=thr, motion_threshold=1e6)),
+                      synth_scene(n, seed, ground=0.3, noise=0.0, outliers=0.5)))
+    return cases

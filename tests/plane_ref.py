@@ -223,3 +223,58 @@ def same_result(got, want, where):
         assert g.tobytes() == w.tobytes(), (where, key, g, w)
     assert np.float32(got["pitch"]).tobytes() == np.float32(want["pitch"]).tobytes(), (where, "pitch", got["pitch"],
                                                                                          want["pitch"])
+
+
+# ------------------------------------------------------------------------------------------------------------ edges
+# tests/golden/plane_edges.npz (make_goldens_plane_edges.py): 640x240 maps whose lattice lists have exactly the lengths
+# at which k_plane_grid, k_plane_vote and k_plane_select change rounds, and noiseless planar roads on which votes tie.
+EDGE_GOLDEN = os.path.join(H.GOLDEN, "plane_edges.npz")
+EDGE_W, EDGE_H = 640, 240
+EDGE_NU, EDGE_NV = 128, 32                      # lattice of the region of interest (rows 80..235, every 5th pixel)
+EDGE_LENGTHS = (1, 1023, 1024, 1025, 2048)
+EDGE_SEED = 3
+EDGE_TIE_SEEDS = (2, 4, 8)                      # searched on the reference: make_goldens_plane_edges.py --search
+
+
+def edge_cells(k):
+    """(u, v) of k cells of the lattice, scattered over it: cell t is chosen when 7919 t mod 4096 < k (a bijection)"""
+    t = np.arange(EDGE_NU * EDGE_NV, dtype=np.int64)
+    t = t[(t * 7919) % (EDGE_NU * EDGE_NV) < k]
+    return 5 * (t // EDGE_NV), EDGE_H // 3 + 5 * (t % EDGE_NV)
+
+
+def list_map(k):
+    """an empty map with d >= 1 on exactly k lattice cells: a road with noise in [0, 14), so that no hypothesis gets
+    every point (d_threshold is 5)"""
+    v, u = np.mgrid[0:EDGE_H, 0:EDGE_W]
+    road = (np.float32(0.25) * (v - 70).astype(np.float32) + np.float32(14) * noise(EDGE_H, EDGE_W)).astype(np.float32)
+    D = np.zeros((EDGE_H, EDGE_W), np.float32)
+    cu, cv = edge_cells(k)
+    D[cv, cu] = road[cv, cu]
+    return D
+
+
+def planar_map(off_plane=0):
+    """a noiseless planar road over the whole map; `off_plane` lattice cells lie 40 above it"""
+    v, u = np.mgrid[0:EDGE_H, 0:EDGE_W]
+    D = (np.float32(0.25) * (v - 70).astype(np.float32) + np.float32(0.02) * u.astype(np.float32)).astype(np.float32)
+    cu, cv = edge_cells(off_plane)
+    D[cv, cu] += np.float32(40)
+    return D
+
+
+def tie_of(votes, lanes=1024):
+    """(h0, h1, count, how many reach it): h0 the first hypothesis with the most votes, h1 the first later one with as
+    many in a lower lane of k_plane_select; None when there is no such h1"""
+    most = np.flatnonzero(votes == votes.max())
+    later = [int(h) for h in most[1:] if h % lanes < most[0] % lanes]
+    return (int(most[0]), later[0], int(votes.max()), len(most)) if later else None
+
+
+def edge_cases():
+    """as cases(): [(name, [call, ...])]"""
+    out = [("list%d_s%d" % (k, EDGE_SEED), [(list_map(k), EDGE_W, EDGE_SEED)]) for k in EDGE_LENGTHS]
+    out.append(("planar_s%d" % EDGE_SEED, [(planar_map(), EDGE_W, EDGE_SEED)]))
+    for seed in EDGE_TIE_SEEDS:
+        out.append(("planar_out_s%d" % seed, [(planar_map(1024), EDGE_W, seed)]))
+    return out

@@ -291,3 +291,204 @@ def to_p_match(m):
     for k in M6.names:
         out[k] = m[k]
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------- collide
+# Scene `collide` (tests/golden/recon_collide.npz, make_goldens_recon_collide.py): the sizes and collisions at which the
+# resident track table's kernels (recon_track_kernels.hip) can go wrong.  The number of active tracks after an update is
+# that update's number of matches, so COLLIDE_N is also the n_old of the following update.
+COLLIDE_N = [1023, 1024, 1025, 2048, 2049, 3000, 0, 1, 1025, 2049, 1024, 2048, 0]
+COLLIDE_SETTINGS = [(0, 2, 30, 2), (1, 3, 30, 2), (2, 3, 30, 3)]
+COLLIDE_SHARE_AT = (1, 2, 3, 9, 10)  # updates in which matches are given the i1c of another match
+COLLIDE_QUIET = 5                       # the update in which every old track is extended
+COLLIDE_GROUPS = 16                     # collisions of either kind per update
+COLLIDE_SPARSE = 60000                  # feature indices of a sparse frame are drawn below this
+
+
+def sequential_update(last, length, m):
+    """reconstruction.cpp:75-145 on (last_idx, length) per track: the new table, the lost tracks' lengths, and per
+    match the number of its track in the new table"""
+    n_old = len(last)
+    slot = {}
+    for t, li in enumerate(last):
+        slot[li] = t                                  # a later track overwrites the slot
+    new_last, new_len, owner = list(last), list(length), [-1] * len(m)
+    extended = set()
+    for i, q in enumerate(m):
+        t = slot.get(int(q["i1p"]), -1)
+        if t >= 0 and t not in extended:
+            extended.add(t)
+            new_last[t], new_len[t] = int(q["i1c"]), length[t] + 1
+            owner[i] = t
+        else:
+            owner[i] = len(new_last)
+            new_last.append(int(q["i1c"]))
+            new_len.append(2)
+    keep = [t for t in range(len(new_last)) if t >= n_old or t in extended]
+    at = {t: j for j, t in enumerate(keep)}
+    return ([new_last[t] for t in keep], [new_len[t] for t in keep],
+            [length[t] for t in range(n_old) if t not in extended], [at[t] for t in owner])
+
+
+def collide_scene(seed=31, noise=0.2):
+    """a drive as synth_scene's whose updates have exactly COLLIDE_N matches, with, by construction:
+       * after each update of COLLIDE_SHARE_AT, COLLIDE_GROUPS feature indices on which two (every fourth: three)
+         tracks end whose numbers lie in different blocks of 256, each the i1p of a match of the following update;
+       * in each following update, COLLIDE_GROUPS i1p values named by two to four matches whose positions lie in
+         different blocks of 256, every third of them one of the shared indices above;
+       * update COLLIDE_QUIET extends every one of its 2049 old tracks; the update after it is empty (3000 lost);
+       * feature indices drawn below COLLIDE_SPARSE in frames 0, 1, 4, 5, ... and below the frame's number of
+         features in frames 2, 3, 6, 7, ...: the index table is far larger than n in some updates, about n in others."""
+    rng = np.random.default_rng(seed)
+    N, K = COLLIDE_N, len(COLLIDE_N)
+    nf = K + 1
+    Trs = [rigid(rot(*rng.normal(0, 0.004, 3)), [rng.normal(0, 0.03), rng.normal(0, 0.02), -rng.uniform(0.5, 1.1)])
+           for _ in range(K)]
+    W2C = [np.eye(4)]
+    for T in Trs:
+        W2C.append(T @ W2C[-1])
+    # which point is matched in which update, in match order
+    sets, prev, n_points = [], np.zeros(0, np.int64), 0
+    for k, n in enumerate(N):
+        c = len(prev) if k == COLLIDE_QUIET else min(len(prev), n) * 7 // 10
+        new = np.arange(n_points, n_points + n - c)
+        n_points += n - c
+        prev = rng.permutation(np.concatenate([rng.permutation(prev)[:c], new]))
+        sets.append(prev)
+    first, last = np.full(n_points, -1), np.full(n_points, -1)
+    for k, s in enumerate(sets):
+        first[s] = np.where(first[s] < 0, k, first[s])
+        last[s] = k
+    # a point inside the image of its first frame, far enough ahead to stay in front for its whole life
+    f, cu, cv = CALIB
+    z = rng.uniform(3, 28, n_points) + 1.2 * (last - first + 2)
+    uu, vv = rng.uniform(50, 1190, n_points), rng.uniform(20, 355, n_points)
+    Xc = np.stack([(uu - cu) / f * z, (vv - cv) / f * z, z], 1)
+    X = np.empty_like(Xc)
+    for k in range(K):
+        C2W = np.linalg.inv(W2C[k])
+        w = first == k
+        X[w] = Xc[w] @ C2W[:3, :3].T + C2W[:3, 3]
+    u = np.zeros((nf, n_points), np.float32)
+    v = np.zeros((nf, n_points), np.float32)
+    idx = np.full((nf, n_points), -1, np.int64)
+    for fr in range(nf):
+        seen = np.unique(np.concatenate([sets[k] for k in (fr - 1, fr) if 0 <= k < K]))
+        a, b, _ = project(W2C[fr], X[seen])
+        u[fr, seen] = (a + rng.normal(0, noise, len(seen))).astype(np.float32)
+        v[fr, seen] = (b + rng.normal(0, noise, len(seen))).astype(np.float32)
+        top = COLLIDE_SPARSE if fr % 4 < 2 else len(seen) + 7
+        idx[fr, seen] = rng.choice(top, len(seen), replace=False)
+    scene = []
+    for k, s in enumerate(sets):
+        m = np.zeros(len(s), M6)
+        m["u1p"], m["v1p"], m["i1p"] = u[k, s], v[k, s], idx[k, s]
+        m["u1c"], m["v1c"], m["i1c"] = u[k + 1, s], v[k + 1, s], idx[k + 1, s]
+        scene.append((Trs[k], m))
+
+    def pick(rng, pools, used, blocks=()):
+        """one index out of each pool, not used before, each in another block of 256 than the first of the group and,
+        while blocks last, than every other one of it (pools: (index, block); blocks: those the group has already)"""
+        got, blocks = [], list(blocks)
+        for pool in pools:
+            free = [pool[j] for j in rng.permutation(len(pool)) if pool[j][0] not in used]
+            hit = [c for c in free if c[1] not in blocks] or [c for c in free if c[1] != blocks[0]]
+            assert hit, "no candidate left"
+            got.append(hit[0][0])
+            blocks.append(hit[0][1])
+            used.add(hit[0][0])
+        return got
+
+    tbl_last, tbl_len, asked = [], [], []
+    for k, (T, m) in enumerate(scene):
+        goes_on = np.isin(sets[k], sets[k + 1]) if k + 1 < K else np.zeros(len(m), bool)
+        born = first[sets[k]] == k
+        used = set()
+        if k - 1 in COLLIDE_SHARE_AT:
+            # the same i1p in several matches: a match that extends a track and goes on, and matches of points seen
+            # for the first time that do not go on (whether they go on is not asked before an update in which every point does, or none)
+            old = [(i, i // 256) for i in np.flatnonzero(~born & (goes_on | ~goes_on.any()))]
+            fresh = [(i, i // 256) for i in np.flatnonzero(born & (~goes_on | goes_on.all()))]
+            for g in range(COLLIDE_GROUPS):
+                extra = 1 + g % 3
+                if g % 3 == 0:
+                    a = asked[g]                          # ... the match that asks for a shared index
+                    assert a not in used
+                    used.add(a)
+                    got = [a] + pick(rng, [fresh] * extra, used, [a // 256])
+                else:
+                    got = pick(rng, [old] + [fresh] * extra, used)
+                assert all(i // 256 != got[0] // 256 for i in got[1:])
+                m["i1p"][got[1:]] = m["i1p"][got[0]]
+        _, new_len, _, track = sequential_update(tbl_last, tbl_len, m)
+        track = np.array(track)
+        asked = []
+        if k in COLLIDE_SHARE_AT:
+            # the same i1c in several matches: one whose point goes on (the next update asks for the index) and one or
+            # two whose points do not; alternately the one that goes on is the longer track and the shorter
+            long_on = [(i, track[i] // 256) for i in np.flatnonzero(~born & goes_on) if i not in used]
+            short_on = [(i, track[i] // 256) for i in np.flatnonzero(born & goes_on) if i not in used]
+            long_off = [(i, track[i] // 256) for i in np.flatnonzero(~born & ~goes_on) if i not in used]
+            short_off = [(i, track[i] // 256) for i in np.flatnonzero(born & ~goes_on) if i not in used]
+            nxt = scene[k + 1][1]
+            for g in range(COLLIDE_GROUPS):
+                pools = [[long_on, short_off], [short_on, long_off], [long_on, long_off]][g % 3]
+                if g % 4 == 0:
+                    pools = pools + [short_off if g % 8 else long_off]
+                got = pick(rng, pools, used)
+                m["i1c"][got[1:]] = m["i1c"][got[0]]
+                hit = np.flatnonzero(sets[k + 1] == sets[k][got[0]])
+                assert len(hit) == 1 and nxt["i1p"][hit[0]] == m["i1c"][got[0]]
+                asked.append(int(hit[0]))
+        tbl_last, tbl_len, _, _ = sequential_update(tbl_last, tbl_len, m)
+    assert [len(m) for _, m in scene] == COLLIDE_N
+    return scene
+
+
+COLLIDE_GOLDEN = os.path.join(H.GOLDEN, "recon_collide.npz")
+COLLIDE_BOUNDARIES = (0, 1, 1023, 1024, 1025, 2048, 2049, 3000)
+
+
+def collide_properties(scene, update):
+    """what scene `collide` is there for, recomputed from its matches by `update` (sequential_update above, or the
+    parallel form of tests/test_recon_resident.py: the first three values of what it returns are used)"""
+    out = {"n": [], "n_old": [], "lost": [], "tbl": [], "shared": [], "three_way": [], "named": [], "both": []}
+    last, length = [], []
+    for k, (_, m) in enumerate(scene):
+        i1p = m["i1p"].astype(np.int64)
+        out["n"].append(len(m))
+        out["n_old"].append(len(last))
+        out["tbl"].append(int(max([-1] + list(last) + i1p.tolist() + m["i1c"].tolist())) + 1)
+        owners = {}
+        for t, li in enumerate(last):
+            owners.setdefault(li, []).append(t)
+        asked = set(i1p.tolist())
+        shared = {li for li, ts in owners.items() if li in asked and len({t // 256 for t in ts}) >= 2}
+        out["shared"] += [(k, li) for li in sorted(shared)]
+        out["three_way"] += [(k, li) for li in sorted(shared) if len({t // 256 for t in owners[li]}) >= 3]
+        at = {}
+        for i, p in enumerate(i1p.tolist()):
+            at.setdefault(p, []).append(i)
+        named = {p for p, ii in at.items() if 2 <= len(ii) <= 4 and len({i // 256 for i in ii}) >= 2}
+        out["named"] += [(k, p) for p in sorted(named)]
+        out["both"] += [(k, p) for p in sorted(named & shared)]
+        res = update(last, length, m)
+        last, length = res[0], res[1]
+        out["lost"].append(len(res[2]))
+    return out
+
+
+def check_collide_properties(p):
+    """conditions, not measurements: a scene that loses one of them is not `collide`"""
+    assert p["n"] == COLLIDE_N and p["n_old"] == [0] + COLLIDE_N[:-1]
+    for b in COLLIDE_BOUNDARIES:
+        assert b in p["n"] and b in p["n_old"], b
+    k = COLLIDE_QUIET
+    assert p["n_old"][k] >= 2049 and p["lost"][k] == 0 and p["n"][k] >= 3000           # a large update, nothing lost
+    assert p["n"][k + 1] == 0 and p["lost"][k + 1] == p["n_old"][k + 1] >= 12 * 250    # every track lost: 12 rounds of 256
+    assert p["n"][k + 2] == 1 and p["n_old"][k + 2] == 0
+    assert len(p["shared"]) >= 50 and len(p["three_way"]) >= 10, (len(p["shared"]), len(p["three_way"]))
+    assert len(p["named"]) >= 50 and len(p["both"]) >= 5, (len(p["named"]), len(p["both"]))
+    ratio = [t / n for t, n in zip(p["tbl"], p["n"]) if n >= 1000]
+    assert min(ratio) < 3 and max(ratio) > 20, ratio                                   # the index table: about n, far above n
+    assert max(p["tbl"]) > 50000

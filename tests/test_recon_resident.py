@@ -51,10 +51,11 @@ def Z():
         return out
 
 
-def parallel_update(last_idx, length, m, owner=max):
+def parallel_update(last_idx, length, m, owner=max, claim=min):
     """one update of the track table (last_idx, length per track) by the matches m: the new table and the lengths of
-    the lost tracks, in order"""
-    n_old = len(last_idx)
+    the lost tracks, in order.  owner / claim: the two rules, to be turned round by tests that show a scene tells
+    them apart"""
+    n_old, claim_rule = len(last_idx), claim
     table = {}
     for t in range(n_old):                                    # k_rt_scatter: atomicMax
         table[last_idx[t]] = owner(table.get(last_idx[t], t), t)
@@ -62,7 +63,7 @@ def parallel_update(last_idx, length, m, owner=max):
     claim = [NONE] * n_old
     for i, t in enumerate(idx):                               # k_rt_associate: atomicMin
         if t >= 0:
-            claim[t] = min(claim[t], i)
+            claim[t] = i if claim[t] == NONE else claim_rule(claim[t], i)
     extended = [t for t in range(n_old) if claim[t] != NONE]  # k_rt_scan
     lost = [t for t in range(n_old) if claim[t] == NONE]
     created = [i for i, t in enumerate(idx) if not (t >= 0 and claim[t] == i)]
@@ -112,13 +113,13 @@ def test_shared_fixture_asks_who_owns_a_shared_slot(Z):
     assert 3.0 in Z["shared_settings"][:, 1]                               # a setting under which lengths 2 and 3 differ
 
 
-def model_matches(Z, name, owner):
+def model_matches(Z, name, owner, claim=min):
     scene = R.unpack_scene(Z, name)
     for j, s in enumerate(Z["%s_settings" % name]):
         want = R.unpack_result(Z, "%s_%d" % (name, j))
         last, length = [], []
         for k, (_, m) in enumerate(scene):
-            last, length, lost_len = parallel_update(last, length, m, owner)
+            last, length, lost_len = parallel_update(last, length, m, owner, claim)
             active, _, codes = want[k]
             if len(last) != active or len(lost_len) != len(codes):
                 return (name, j, k, "counts")

@@ -64,11 +64,11 @@ def test_goldens_load_and_anchors_hold(Z):
             assert len(Z["est_%s_inliers" % n]) == v.max()
 
 
-def run_core_check(exe, tmp, m, pvec, S):
+def run_core_check(exe, tmp, m, pvec, S, first=0):
     path = os.path.join(tmp, "m.bin")
     with open(path, "wb") as f:
         f.write(struct.pack("<i", len(m)) + np.ascontiguousarray(m, H.P_MATCH).tobytes())
-    b = subprocess.run([exe, path, str(int(pvec[5])), str(S), repr(float(pvec[6]))], check=True,
+    b = subprocess.run([exe, path, str(int(pvec[5])), str(S), repr(float(pvec[6])), str(first)], check=True,
                        capture_output=True).stdout
     n = struct.unpack_from("<i", b)[0]
     votes = np.frombuffer(b, np.int32, n, 4)
