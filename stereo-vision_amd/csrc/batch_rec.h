@@ -16,6 +16,8 @@
 #include <functional>
 #include <vector>
 
+#include "hip_guard.h"
+
 namespace svh {
 
 // launches the batched form of one kernel: jobs = device copy of the job table
@@ -44,9 +46,9 @@ struct BatchRec {
     hipError_t reuse();
     hipError_t ensure_side();                 // creates them on first use (current device)
     hipError_t join_side(hipStream_t s);      // s waits for everything issued on the side streams so far
-    uint8_t* h_arena = nullptr;   // pinned staging of the job tables
-    uint8_t* d_arena = nullptr;
-    size_t cap = 0, used = 0;     // `used` advances per flush, reset by synced()
+    PinnedBuf<uint8_t> h_arena;   // pinned staging of the job tables
+    HipBuf<uint8_t> d_arena;      // (same size, or both empty)
+    size_t used = 0;              // advances per flush, reset by synced()
 
     void begin_object() { cursor = 0; }
     void reset() {   // forget recorded jobs (a new phase, or after a mismatch)

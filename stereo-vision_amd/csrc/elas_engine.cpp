@@ -39,76 +39,15 @@
 #include <thread>
 #include <vector>
 
+#include "hip_guard.h"
 #include "svh_internal.h"
 
 namespace svh {
 
-static thread_local std::string t_error;
 static thread_local int t_device = 0;
 
-// shared by the Elas and Matcher engines: text behind svh_last_error()
-int fail(int code, const std::string& msg) {
-    t_error = msg;
-    return code;
-}
-
-// ---- fault injection (svh_internal.h) --------------------------------------------------------------------------
-namespace {
-enum { FI_MALLOC, FI_LAUNCH, FI_COPY, FI_WAIT, FI_KINDS };
-std::atomic<int> g_fi_kind{-1};          // -1: nothing armed
-std::atomic<int64_t> g_fi_first{0}, g_fi_count{1};
-std::atomic<int64_t> g_fi_seen[FI_KINDS];
-int fi_kind_of(const char* t) {
-    if (strstr(t, "hipMalloc") || strstr(t, "hipHostMalloc")) return FI_MALLOC;
-    if (strstr(t, "hipMemcpy") || strstr(t, "hipMemset")) return FI_COPY;
-    if (strstr(t, "hipGetLastError")) return FI_LAUNCH;
-    if (strstr(t, "_wait") || strstr(t, "Synchronize") || strstr(t, "hipEventQuery")) return FI_WAIT;
-    return -1;
-}
-bool fi_parse(const char* spec) {
-    static const char* names[FI_KINDS] = {"malloc", "launch", "copy", "wait"};
-    g_fi_kind.store(-1);
-    if (!spec || !*spec) return true;
-    const char* colon = strchr(spec, ':');
-    if (!colon) return false;
-    int kind = -1;
-    for (int k = 0; k < FI_KINDS; k++)
-        if (strlen(names[k]) == (size_t)(colon - spec) && !strncmp(spec, names[k], colon - spec)) kind = k;
-    if (kind < 0) return false;
-    char* end = nullptr;
-    const long long n = strtoll(colon + 1, &end, 10);
-    long long cnt = 1;
-    if (end && *end == ':') cnt = strtoll(end + 1, nullptr, 10);
-    if (n < 1 || cnt < 0) return false;
-    for (auto& c : g_fi_seen) c.store(0);
-    g_fi_first.store(n);
-    g_fi_count.store(cnt);
-    g_fi_kind.store(kind);
-    return true;
-}
-}   // namespace
-bool fi_armed() { return g_fi_kind.load(std::memory_order_relaxed) >= 0; }
-bool fi_hit(const char* expr_text) {
-    const int kind = g_fi_kind.load(std::memory_order_relaxed);
-    if (kind < 0 || fi_kind_of(expr_text) != kind) return false;
-    const int64_t i = g_fi_seen[kind].fetch_add(1) + 1, first = g_fi_first.load(), cnt = g_fi_count.load();
-    return i >= first && (cnt == 0 || i < first + cnt);
-}
-void report_hip_failure(const char* entry) { fprintf(stderr, "svhip: %s: %s\n", entry, t_error.c_str()); }
-
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        const bool inj_ = fi_armed() && fi_hit(#expr);                                      \
-        hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                    \
-        if (e_ != hipSuccess)                                                               \
-            return fail(SVH_ERR_HIP, std::string(#expr) + ": " +                            \
-                                     (inj_ ? "injected failure (SVH_TEST_FAIL_AT)" : hipGetErrorString(e_))); \
-    } while (0)
-
-static double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
+// (null entry: the ELAS entries print the one stderr line themselves, not the point of failure)
+#define HIP_TRY(kind, expr) SVH_HIP_TRY(nullptr, kind, expr)
 
 // ---------------------------------------------------------------------------
 // per-kernel timing with HIP events recorded on the lane's own stream
@@ -254,8 +193,8 @@ struct Lane {
 
     int ensure(const svh_elas_params& p, int32_t w, int32_t h, int32_t g) {
         if (!stream) {
-            HIP_TRY(hipSetDevice(device));
-            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            HIP_TRY(none, hipSetDevice(device));
+            HIP_TRY(none, hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         }
         const int32_t st = p.candidate_stepsize + (p.subsampling ? p.candidate_stepsize % 2 : 0);
         if (w == W && h == H && p.disp_max == disp_max && st == step && p.grid_size == grid_size &&
@@ -266,36 +205,36 @@ struct Lane {
         stream = keep;
         d = make_dims(p, w, h);
         const size_t N = (size_t)w * h, DN = (size_t)d.DW * d.DH, G2 = (size_t)2 * g;
-        HIP_TRY(hipMalloc(&img, G2 * N));
-        HIP_TRY(hipMalloc(&desc, G2 * N * 16));
-        HIP_TRY(hipMalloc(&owner, G2 * N * sizeof(int32_t)));
-        HIP_TRY(hipMemset(owner, 0, G2 * N * sizeof(int32_t)));
+        HIP_TRY(malloc, hipMalloc(&img, G2 * N));
+        HIP_TRY(malloc, hipMalloc(&desc, G2 * N * 16));
+        HIP_TRY(malloc, hipMalloc(&owner, G2 * N * sizeof(int32_t)));
+        HIP_TRY(copy, hipMemset(owner, 0, G2 * N * sizeof(int32_t)));
         // SVH_TEST_OWNER_HI: start the moving base just below the int32 limit so that a test
         // reaches the (otherwise once-per-40 000-groups) re-clear path with its first groups
         owner_hi = svh::env("SVH_TEST_OWNER_HI") ? atoll(svh::env("SVH_TEST_OWNER_HI")) : 0;
-        HIP_TRY(hipMalloc(&Draw, G2 * DN * sizeof(float)));
-        HIP_TRY(hipMalloc(&D, G2 * DN * sizeof(float)));
-        HIP_TRY(hipMalloc(&tmp, G2 * DN * sizeof(float)));
-        HIP_TRY(hipMalloc(&labels, G2 * DN * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&counts, G2 * DN * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&seg_nroots, G2 * (size_t)((d.DW + 63) / 64) * ((d.DH + 15) / 16) * sizeof(int32_t)));   // one count per 64 x 16 tile
+        HIP_TRY(malloc, hipMalloc(&Draw, G2 * DN * sizeof(float)));
+        HIP_TRY(malloc, hipMalloc(&D, G2 * DN * sizeof(float)));
+        HIP_TRY(malloc, hipMalloc(&tmp, G2 * DN * sizeof(float)));
+        HIP_TRY(malloc, hipMalloc(&labels, G2 * DN * sizeof(int32_t)));
+        HIP_TRY(malloc, hipMalloc(&counts, G2 * DN * sizeof(int32_t)));
+        HIP_TRY(malloc, hipMalloc(&seg_nroots, G2 * (size_t)((d.DW + 63) / 64) * ((d.DH + 15) / 16) * sizeof(int32_t)));   // one count per 64 x 16 tile
         const size_t nc = (size_t)d.Wc * d.Hc;
-        HIP_TRY(hipMalloc(&dcan, g * nc * sizeof(int16_t)));
-        HIP_TRY(hipHostMalloc(&h_dcan, g * nc * sizeof(int16_t)));
-        HIP_TRY(hipHostMalloc(&h_img, G2 * N));
+        HIP_TRY(malloc, hipMalloc(&dcan, g * nc * sizeof(int16_t)));
+        HIP_TRY(malloc, hipHostMalloc(&h_dcan, g * nc * sizeof(int16_t)));
+        HIP_TRY(malloc, hipHostMalloc(&h_img, G2 * N));
         // worst case per pair: nc+6 support points, 2n+8 triangles per side
         const size_t nsup = nc + 6;
         ntri_max = 2 * nsup + 8;
         prior_cap = sizeof(GroupHdr) + (size_t)(p.disp_max + 1) * sizeof(int32_t) + 512 +
                     (size_t)g * (nsup * 3 + 2 * ntri_max * 3) * sizeof(int32_t);
-        HIP_TRY(hipMalloc(&prior_dev, prior_cap));
-        HIP_TRY(hipHostMalloc(&h_prior, prior_cap));
-        HIP_TRY(hipMalloc(&raster, G2 * ntri_max * sizeof(TriRaster)));
-        HIP_TRY(hipMalloc(&planes, G2 * ntri_max * 6 * sizeof(float)));
+        HIP_TRY(malloc, hipMalloc(&prior_dev, prior_cap));
+        HIP_TRY(malloc, hipHostMalloc(&h_prior, prior_cap));
+        HIP_TRY(malloc, hipMalloc(&raster, G2 * ntri_max * sizeof(TriRaster)));
+        HIP_TRY(malloc, hipMalloc(&planes, G2 * ntri_max * 6 * sizeof(float)));
         const size_t gw_bytes = G2 * d.gw * d.gh * d.gwords * sizeof(uint32_t);
-        HIP_TRY(hipMalloc(&seed, gw_bytes));
-        HIP_TRY(hipMalloc(&mask, gw_bytes));
-        if (d.gwords <= 8) HIP_TRY(hipMalloc(&lists, G2 * d.gw * d.gh * 32 * sizeof(uint16_t)));
+        HIP_TRY(malloc, hipMalloc(&seed, gw_bytes));
+        HIP_TRY(malloc, hipMalloc(&mask, gw_bytes));
+        if (d.gwords <= 8) HIP_TRY(malloc, hipMalloc(&lists, G2 * d.gw * d.gh * 32 * sizeof(uint16_t)));
         hp.resize(g);
         // fixed layout of the packed lists when the device builds them
         o_P = (sizeof(GroupHdr) + 63) & ~(size_t)63;
@@ -312,9 +251,9 @@ struct Lane {
             for (int k = 0; k < 11; k++) a_arr[k] = take(S2 * cap * 4);
             const size_t a_fl = take(S2 * 2 * cap * 4), a_fr = take(S2 * 2 * cap * 4);
             const size_t a_wl = take((size_t)g * 3 * nc * 4), a_cw = take((size_t)g * (nc / 4 + 1) * 4);
-            HIP_TRY(hipMalloc(&stage_blob, off));
-            HIP_TRY(hipMemset(stage_blob, 0, off));
-            HIP_TRY(hipHostMalloc(&h_counts, sizeof(StageCounts)));
+            HIP_TRY(malloc, hipMalloc(&stage_blob, off));
+            HIP_TRY(copy, hipMemset(stage_blob, 0, off));
+            HIP_TRY(malloc, hipHostMalloc(&h_counts, sizeof(StageCounts)));
             uint8_t* b = static_cast<uint8_t*>(stage_blob);
             stg.dcan = dcan;
             stg.sup_raw = reinterpret_cast<int32_t*>(b + a_sup);
@@ -337,7 +276,7 @@ struct Lane {
         }
         // the memsets above run on the null stream, which the lanes' non-blocking streams do not
         // wait for: they must have landed before the first kernel of this lane
-        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(wait, hipDeviceSynchronize());
         W = w; H = h; disp_max = p.disp_max; step = st; grid_size = p.grid_size; sub = p.subsampling;
         gcap = g;
         return SVH_OK;
@@ -529,9 +468,9 @@ static int tap_dev(Lane& L, Taps* taps, int stage, const T* dev, size_t count) {
     if (!taps || !taps->enabled) return SVH_OK;
     taps->data[stage].resize(count * sizeof(T));
     if (!count) return SVH_OK;
-    HIP_TRY(hipMemcpyAsync(taps->data[stage].data(), dev, count * sizeof(T), hipMemcpyDeviceToHost,
+    HIP_TRY(copy, hipMemcpyAsync(taps->data[stage].data(), dev, count * sizeof(T), hipMemcpyDeviceToHost,
                            L.stream));
-    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_TRY(wait, hipStreamSynchronize(L.stream));
     return SVH_OK;
 }
 
@@ -610,7 +549,7 @@ static int run_group(Lane& L, const svh_elas_params& p, const int32_t* dims, con
                      int32_t* status, Taps* taps, svh_elas* timing, int mode = RG_ALL, int prefer_device = 0) {
     const int rc = run_group_body(L, p, dims, io, status, taps, timing, mode, prefer_device);
     if (rc == SVH_ERR_HIP) {
-        const std::string keep = t_error;
+        const std::string keep = svh_last_error();
         if (L.stream) (void)hipStreamSynchronize(L.stream);
         if (L.copy_stream) (void)hipStreamSynchronize(L.copy_stream);
         (void)hipGetLastError();
@@ -618,7 +557,7 @@ static int run_group(Lane& L, const svh_elas_params& p, const int32_t* dims, con
         L.resident = false;
         L.force_host = false;
         L.P_key[0] = -1;      // the prior table may not have reached the device
-        t_error = keep;
+        fail(rc, keep);
     }
     return rc;
 }
@@ -629,7 +568,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     int rc = check_params(p, W, H);
     if (rc) return rc;
     if (g < 1 || g > kMaxGroup) return fail(SVH_ERR_BAD_ARG, "bad group size");
-    HIP_TRY(hipSetDevice(L.device));
+    HIP_TRY(none, hipSetDevice(L.device));
     // lanes are sized for the group at hand: a single Elas::process call holds buffers for one pair
     // (41 MB at KITTI size), not for the batch default; batch workers size theirs up front
     rc = L.ensure(p, W, H, g);
@@ -677,7 +616,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         // triangle ownership is stored as owner_base + 1 + index; the base moves above everything
         // written so far, so the 2 x N x g map is never cleared (one memset when int32 would overflow)
         if (L.owner_hi + 1 + tri_bound >= INT32_MAX) {
-            HIP_TRY(hipMemsetAsync(L.owner, 0, (size_t)2 * L.gcap * N * sizeof(int32_t), s));
+            HIP_TRY(copy, hipMemsetAsync(L.owner, 0, (size_t)2 * L.gcap * N * sizeof(int32_t), s));
             L.owner_hi = 0;
         }
         G.owner_base = (int32_t)L.owner_hi;
@@ -694,8 +633,8 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             rc = tap_dev(L, taps, SVH_ELAS_PLANES2, L.planes + (size_t)6 * n1, (size_t)6 * n2); if (rc) return rc;
             const size_t words = (size_t)d.gw * d.gh * d.gwords;
             std::vector<uint32_t> m(2 * words);
-            HIP_TRY(hipMemcpyAsync(m.data(), L.mask, m.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(lane_wait(L));
+            HIP_TRY(copy, hipMemcpyAsync(m.data(), L.mask, m.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(wait, lane_wait(L));
             for (int k = 0; k < 2; k++) {
                 std::vector<int32_t> gr;
                 expand_grid(p, d, m.data() + k * words, gr);
@@ -711,11 +650,11 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         early_d2 = !io.out_device && lr_done && !tapping && p.postprocess_only_left;
         if (early_d2) {
             if (!L.copy_stream) {
-                HIP_TRY(hipStreamCreateWithFlags(&L.copy_stream, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&L.match_ev, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&L.copy_ev, hipEventDisableTiming));
+                HIP_TRY(none, hipStreamCreateWithFlags(&L.copy_stream, hipStreamNonBlocking));
+                HIP_TRY(none, hipEventCreateWithFlags(&L.match_ev, hipEventDisableTiming));
+                HIP_TRY(none, hipEventCreateWithFlags(&L.copy_ev, hipEventDisableTiming));
             }
-            HIP_TRY(hipEventRecord(L.match_ev, s));
+            HIP_TRY(none, hipEventRecord(L.match_ev, s));
         }
         if (tapping) {
             rc = tap_dev(L, taps, SVH_ELAS_D1_RAW, L.Draw, DN); if (rc) return rc;
@@ -762,10 +701,10 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                 e++;
             const float* src = L.D + ((size_t)2 * j + k) * DN;
             if (e - j > 1)
-                HIP_TRY(hipMemcpy2DAsync(io.hD[k][j], bytes, src, 2 * bytes, bytes, (size_t)(e - j),
+                HIP_TRY(copy, hipMemcpy2DAsync(io.hD[k][j], bytes, src, 2 * bytes, bytes, (size_t)(e - j),
                                          hipMemcpyDeviceToHost, cs));
             else
-                HIP_TRY(hipMemcpyAsync(io.hD[k][j], src, bytes, hipMemcpyDeviceToHost, cs));
+                HIP_TRY(copy, hipMemcpyAsync(io.hD[k][j], src, bytes, hipMemcpyDeviceToHost, cs));
             j = e;
         }
         return SVH_OK;
@@ -773,16 +712,16 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     auto copy_out = [&](const int32_t* active) -> int {
         if (io.out_device) return SVH_OK;
         if (early_d2) {   // (issued after the post-processing launches: a pageable copy blocks this thread)
-            HIP_TRY(hipStreamWaitEvent(L.copy_stream, L.match_ev, 0));
+            HIP_TRY(none, hipStreamWaitEvent(L.copy_stream, L.match_ev, 0));
             rc = copy_map(1, L.copy_stream, active);
             if (rc) return rc;
-            HIP_TRY(hipEventRecord(L.copy_ev, L.copy_stream));
+            HIP_TRY(none, hipEventRecord(L.copy_ev, L.copy_stream));
         }
         for (int k = 0; k < (early_d2 ? 1 : 2); k++) {
             rc = copy_map(k, s, active);
             if (rc) return rc;
         }
-        if (early_d2) HIP_TRY(hipStreamWaitEvent(s, L.copy_ev, 0));   // the lane's stream ends after both
+        if (early_d2) HIP_TRY(none, hipStreamWaitEvent(s, L.copy_ev, 0));   // the lane's stream ends after both
         return SVH_OK;
     };
     // per-pair result of the device stage, from the counts it sent back
@@ -791,8 +730,8 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     };
 
     auto finish = [&]() -> int {
-        HIP_TRY(lane_wait(L));
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(wait, lane_wait(L));
+        HIP_TRY(launch, hipGetLastError());
         L.prof.collect();
         HP_MARK(HP_WAIT);
         if (!L.resident) return SVH_OK;
@@ -851,16 +790,16 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                     for (int32_t j = 0; j < g;) {
                         uint8_t* dst = L.img + ((size_t)2 * j + k) * N;
                         if (io.pitch != W) {
-                            HIP_TRY(hipMemcpy2DAsync(dst, W, io.hI[k][j], io.pitch, W, H, hipMemcpyHostToDevice, s));
+                            HIP_TRY(copy, hipMemcpy2DAsync(dst, W, io.hI[k][j], io.pitch, W, H, hipMemcpyHostToDevice, s));
                             j++;
                             continue;
                         }
                         int32_t e = j + 1;
                         while (strided_up && e < g && io.hI[k][e] == io.hI[k][e - 1] + N) e++;
                         if (e - j > 1)
-                            HIP_TRY(hipMemcpy2DAsync(dst, 2 * N, io.hI[k][j], N, N, (size_t)(e - j), hipMemcpyHostToDevice, s));
+                            HIP_TRY(copy, hipMemcpy2DAsync(dst, 2 * N, io.hI[k][j], N, N, (size_t)(e - j), hipMemcpyHostToDevice, s));
                         else
-                            HIP_TRY(hipMemcpyAsync(dst, io.hI[k][j], N, hipMemcpyHostToDevice, s));
+                            HIP_TRY(copy, hipMemcpyAsync(dst, io.hI[k][j], N, hipMemcpyHostToDevice, s));
                         j = e;
                     }
             } else {
@@ -872,7 +811,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                         else
                             for (int32_t v = 0; v < H; v++) memcpy(dst + (size_t)v * W, src + (size_t)v * io.pitch, W);
                     }
-                HIP_TRY(hipMemcpyAsync(L.img, L.h_img, (size_t)2 * g * N, hipMemcpyHostToDevice, s));
+                HIP_TRY(copy, hipMemcpyAsync(L.img, L.h_img, (size_t)2 * g * N, hipMemcpyHostToDevice, s));
             }
             img.I[0] = L.img; img.I[1] = L.img + N;
             img.stride = 2 * N; img.pitch = W;
@@ -894,7 +833,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             launch_descriptor(cx, img, g, W, H, p.subsampling, L.desc, false);
             int rc2 = tap_dev(L, taps, SVH_ELAS_DESC1, L.desc, N * 16); if (rc2) return rc2;
             rc2 = tap_dev(L, taps, SVH_ELAS_DESC2, L.desc + N * 16, N * 16); if (rc2) return rc2;
-            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(wait, hipStreamSynchronize(s));
         }
         launch_descriptor(cx, img, g, W, H, p.subsampling, L.desc, L.desc_fly);
         launch_support(cx, p, d, g, L.desc, L.dcan, L.desc_fly);
@@ -906,7 +845,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         // on a core that another rank may need (8 pairs of 1920x1080 per step: 4-7 cores -> < 1)
         if (L.resident && prefer_device) L.poll_wait = true;
         if (!L.resident || tapping)
-            HIP_TRY(hipMemcpyAsync(L.h_dcan, L.dcan, g * nc * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(copy, hipMemcpyAsync(L.h_dcan, L.dcan, g * nc * sizeof(int16_t), hipMemcpyDeviceToHost, s));
         if (L.resident) {
             // ---- E5-E7 on the device, then everything else right behind: no host round trip
             prior_table(p, L.P, &plane_radius);
@@ -914,13 +853,13 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             if (memcmp(key, L.P_key, sizeof(key)) != 0) {
                 // (the staging copy is reused right away: wait for it, once per parameter set)
                 memcpy(L.h_prior + L.o_P, L.P.data(), L.P.size() * sizeof(int32_t));
-                HIP_TRY(hipMemcpyAsync(L.prior_dev + L.o_P, L.h_prior + L.o_P, L.P.size() * sizeof(int32_t),
+                HIP_TRY(copy, hipMemcpyAsync(L.prior_dev + L.o_P, L.h_prior + L.o_P, L.P.size() * sizeof(int32_t),
                                        hipMemcpyHostToDevice, s));
-                HIP_TRY(hipStreamSynchronize(s));
+                HIP_TRY(wait, hipStreamSynchronize(s));
                 memcpy(L.P_key, key, sizeof(key));
             }
             if (tapping) {
-                HIP_TRY(hipStreamSynchronize(s));
+                HIP_TRY(wait, hipStreamSynchronize(s));
                 if (!L.desc_fly) {
                     rc = tap_dev(L, taps, SVH_ELAS_DESC1, L.desc, N * 16); if (rc) return rc;
                     rc = tap_dev(L, taps, SVH_ELAS_DESC2, L.desc + N * 16, N * 16); if (rc) return rc;
@@ -930,13 +869,13 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             launch_stage_device(cx, p, d, g, L.stg, reinterpret_cast<GroupHdr*>(L.prior_dev),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_sup),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_tri));
-            if (!L.stage_ev) HIP_TRY(hipEventCreateWithFlags(&L.stage_ev, hipEventDisableTiming));
-            HIP_TRY(hipMemcpyAsync(L.h_counts, L.stg.counts, sizeof(StageCounts), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipEventRecord(L.stage_ev, s));
+            if (!L.stage_ev) HIP_TRY(none, hipEventCreateWithFlags(&L.stage_ev, hipEventDisableTiming));
+            HIP_TRY(copy, hipMemcpyAsync(L.h_counts, L.stg.counts, sizeof(StageCounts), hipMemcpyDeviceToHost, s));
+            HIP_TRY(none, hipEventRecord(L.stage_ev, s));
             if (tapping) {
                 // host copies of the header and the lists the device built (g == 1)
-                HIP_TRY(hipMemcpyAsync(hdr, L.prior_dev, sizeof(GroupHdr), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
+                HIP_TRY(copy, hipMemcpyAsync(hdr, L.prior_dev, sizeof(GroupHdr), hipMemcpyDeviceToHost, s));
+                HIP_TRY(wait, hipStreamSynchronize(s));
                 if (hdr->active[0]) {
                     rc = tap_dev(L, taps, SVH_ELAS_SUPPORT, reinterpret_cast<int32_t*>(L.prior_dev + L.o_sup),
                                  (size_t)3 * hdr->total_sup); if (rc) return rc;
@@ -961,7 +900,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     if (L.resident) {
         if (!io.out_device) {
             // host outputs: only maps of pairs that went through may be copied out
-            HIP_TRY(event_wait(L, L.stage_ev));
+            HIP_TRY(wait, event_wait(L, L.stage_ev));
             HP_MARK(HP_WAIT);
             int32_t active[kMaxGroup];
             for (int32_t j = 0; j < g; j++) active[j] = active_of(j);
@@ -979,8 +918,8 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         bool on;
         ~WarmOff() { if (on) helpers_warm(0, 0); }
     } warm_off{warm};
-    HIP_TRY(lane_wait(L));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(wait, lane_wait(L));
+    HIP_TRY(launch, hipGetLastError());
     L.prof.collect();
     HP_MARK(HP_WAIT);
     if (g_hostprof) g_hp_pairs += g;
@@ -1066,7 +1005,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     HP_MARK(HP_PACK);
 
     // ---- phase B ---------------------------------------------------------
-    HIP_TRY(hipMemcpyAsync(L.prior_dev, L.h_prior, off, hipMemcpyHostToDevice, s));
+    HIP_TRY(copy, hipMemcpyAsync(L.prior_dev, L.h_prior, off, hipMemcpyHostToDevice, s));
     rc = enqueue_phase_b(o_P, o_sup, o_tri, total_sup, total_tri, total_tri);
     if (rc) return rc;
     rc = copy_out(hdr->active);
@@ -1183,7 +1122,6 @@ extern "C" {
 #define SVH_SRC_SHA "unstamped"
 #endif
 const char* svh_version(void) { return "svhip 0.2 (gfx950) src " SVH_SRC_SHA; }
-const char* svh_last_error(void) { return t_error.c_str(); }
 
 int32_t svh_device_count(void) {
     svh::ensure_init();
@@ -1411,7 +1349,7 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
         auto note = [&](const Job& j, int rcj) {
             if (rcj != SVH_OK && grc[j.gi] == SVH_OK) {
                 grc[j.gi] = rcj;
-                if (rcj < 0) errs[w] = t_error;
+                if (rcj < 0) errs[w] = svh_last_error();
             }
         };
         Job pending[2];   // group whose tail is still on slot k's stream
@@ -1481,7 +1419,7 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
         if (first_bad == SVH_OK && st[i] != SVH_OK) first_bad = st[i];
     }
     for (auto& m : errs)
-        if (!m.empty()) t_error = m;
+        if (!m.empty()) fail(first_bad, m);
     if (first_bad == SVH_ERR_HIP) report_hip_failure("svh_elas_process_batch");
     return first_bad;
 }
@@ -1570,7 +1508,7 @@ static void stream_worker(svh_elas_stream* s) {
     auto note = [&](StreamGroup& g, int rc) {
         if (rc != SVH_OK && g.rc == SVH_OK) {
             g.rc = rc;
-            if (rc < 0) g.err = t_error;
+            if (rc < 0) g.err = svh_last_error();
         }
     };
     std::shared_ptr<StreamGroup> pend[2];
@@ -1745,7 +1683,7 @@ int32_t svh_elas_stream_pop(svh_elas_stream* s, uint64_t* ticket, int32_t* statu
     if (ticket) *ticket = g->first + (uint64_t)j;
     if (status) *status = g->rc != SVH_OK ? g->rc : g->status[j];
     if (g->rc < 0) {
-        t_error = g->err;
+        fail(g->rc, g->err);
         if (g->rc == SVH_ERR_HIP && j == 0) report_hip_failure("svh_elas_stream (group)");
     }
     if (s->popped_in_head >= g->n) {
@@ -1846,9 +1784,6 @@ int32_t svh_elas_support_from_candidates(const svh_elas_params* p, int32_t width
     return n;
 }
 
-
-/* tests: arm / disarm the fault injection ("" or NULL disarms); see svh_internal.h */
-int32_t svh_test_fail_at(const char* spec) { return fi_parse(spec) ? SVH_OK : fail(SVH_ERR_BAD_ARG, "bad fault specification"); }
 
 int32_t svh_elas_set_stage(int32_t where) {
     g_stage_mode.store(where < 0 ? -1 : (where ? 1 : 0));

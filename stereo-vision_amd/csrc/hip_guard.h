@@ -1,0 +1,103 @@
+// What every host engine of libsvhip.so shares around a HIP call (svh_error.cpp): the text behind svh_last_error(), the
+// one guard macro with its fault hook, and the owner of a device or pinned buffer.  Host code only.
+#ifndef SVH_HIP_GUARD_H
+#define SVH_HIP_GUARD_H
+
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/svh.h"
+
+namespace svh {
+
+int fail(int code, const std::string& msg);   // records the text behind svh_last_error(), returns `code`
+double now_ms();                              // steady clock
+inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// ---------------------------------------------------------------- fault injection (tests)
+// TEST HOOK, not part of the public C-ABI (include/svh.h does not declare it; tests bind it by name, the sanitizer
+// drivers pass their SVH_TEST_FAIL_AT on): svh_test_fail_at("<kind>:<n>[:<count>]") arms it, "" / NULL disarms; the
+// library itself never reads a specification from the environment.  The n-th (1-based) guarded call of that kind in
+// this process, counted from the moment the specification is set, is NOT issued and reports an error instead, and so
+// do the count-1 calls of the kind after it (count 0: every one from the n-th on).  The kind of a call is GIVEN at its
+// call site, as the second argument of the guard, never matched from its text:
+//   malloc  an allocation: hipMalloc / hipHostMalloc, directly or through HipBuf::grow (only a grow that allocates)
+//   copy    hipMemcpy*Async / hipMemset*Async, and a recorder's flush (its one upload, then the phase's launches)
+//   launch  the hipGetLastError() after a phase's launches
+//   wait    stream / event waits (and queries in sleep-polls).  NOT every wait: the `(hipError_t)wait_stream(...)` sites
+//           of the Matcher, the stereo visual odometry and the host-table Reconstruction are `none` on purpose -- they
+//           never counted, and the positions the fault tests arm (n-th wait of a call) are fixed on that.  Do not
+//           "correct" them without re-deriving those positions
+//   none    everything else: guarded, never injected
+// Boundary behaviour under a failure (tests/test_faults_gpu.py): the entry returns SVH_ERR_HIP, svh_last_error()
+// names the call, one line goes to stderr, the lane / object is usable for the next call, nothing leaks.
+enum FiKind { FI_none = -1, FI_malloc, FI_launch, FI_copy, FI_wait, FI_KINDS };
+bool fi_armed();             // one relaxed load
+bool fi_hit(FiKind kind);    // counts the call; true: it is the one to fail
+// "svhip: <entry>: <last error>" on stderr, once per failing call
+void report_hip_failure(const char* entry);
+// a failed guarded call: svh_last_error() becomes "<expr>: <hipGetErrorString | injected failure (SVH_TEST_FAIL_AT)>",
+// the stderr line is printed here under `entry` (null: the caller reports at its own entry), returns SVH_ERR_HIP
+int hip_failed(const char* entry, const char* expr_text, bool injected, hipError_t e);
+
+// Owner of one device (Pinned = false) or pinned host buffer.  Pointer and capacity (bytes) change together, so a
+// growth that fails leaves "nothing allocated", which the next call repairs, never a stale pointer behind a capacity
+// that says "fits".  A grow() within the capacity issues no HIP call at all (hipFree synchronises the device).  The
+// destructor frees on the current device: an object's destroy selects its device and drains its stream first.
+template <typename T, bool Pinned = false>
+struct HipBuf {
+    T* p = nullptr;
+    size_t cap = 0;   // bytes
+    HipBuf() = default;
+    HipBuf(const HipBuf&) = delete;
+    HipBuf& operator=(const HipBuf&) = delete;
+    HipBuf(HipBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    HipBuf& operator=(HipBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~HipBuf() { release(); }
+    operator T*() const { return p; }
+    void release() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    // room for `bytes`; the contents are discarded when it has to allocate
+    hipError_t grow(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = Pinned ? hipHostMalloc((void**)&p, bytes) : hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) p = nullptr;
+        else cap = bytes;
+        return e;
+    }
+};
+template <typename T>
+using PinnedBuf = HipBuf<T, true>;
+
+}   // namespace svh
+extern "C" int32_t svh_test_fail_at(const char* spec);
+
+// The guard of every HIP call of the host engines: `kind` is one of none, malloc, copy, launch, wait (see above); a
+// disarmed hook costs one relaxed load.  Returns hip_failed(...) out of the enclosing function on failure.
+#define SVH_HIP_TRY(entry, kind, expr)                                                                  \
+    do {                                                                                                \
+        const bool inj_ = svh::FI_##kind != svh::FI_none && svh::fi_armed() && svh::fi_hit(svh::FI_##kind); \
+        const hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                          \
+        if (e_ != hipSuccess) return svh::hip_failed(entry, #expr, inj_, e_);                           \
+    } while (0)
+// ... and of a buffer's growth: counted (kind malloc) only when it allocates
+#define SVH_HIP_GROW(entry, buf, bytes)                                                                 \
+    do {                                                                                                \
+        if ((buf).cap < (size_t)(bytes)) SVH_HIP_TRY(entry, malloc, (buf).grow(bytes));                 \
+    } while (0)
+
+#endif

@@ -25,14 +25,8 @@
 #include "../../include/matrix.h"
 #include "../../include/svh.h"
 #include "../../include/svh_map.h"
+#include "hip_guard.h"
 #include "svh_config.h"
-
-namespace svh {
-int fail(int code, const std::string& msg);   // elas_engine.cpp: sets svh_last_error()
-bool fi_armed();                                    // elas_engine.cpp: fault injection (svh_internal.h)
-bool fi_hit(const char* expr_text);
-void report_hip_failure(const char* entry);
-}
 
 namespace {
 
@@ -318,17 +312,7 @@ struct svh_map {
     }
 };
 
-static int map_hip_failed(const char* expr, bool injected, hipError_t e) {
-    const int rc = svh::fail(SVH_ERR_HIP, std::string(expr) + ": " + (injected ? "injected failure (SVH_TEST_FAIL_AT)" : hipGetErrorString(e)));
-    svh::report_hip_failure("map");
-    return rc;
-}
-#define MAP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        const bool inj_ = svh::fi_armed() && svh::fi_hit(#expr);   /* svh_internal.h: fault injection */ \
-        hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                   \
-        if (e_ != hipSuccess) return map_hip_failed(#expr, inj_, e_);                      \
-    } while (0)
+#define MAP_TRY(kind, expr) SVH_HIP_TRY("map", kind, expr)
 
 static int32_t map_ensure(svh_map* m, int32_t w, int32_t h) {
     if (m->w == w && m->h == h) return SVH_OK;
@@ -337,18 +321,18 @@ static int32_t map_ensure(svh_map* m, int32_t w, int32_t h) {
     m->release();
     const size_t n = (size_t)w * h;
     for (int k = 0; k < 2; k++) {
-        MAP_TRY(hipMalloc(&m->pl[k].I, n * 4)); MAP_TRY(hipMalloc(&m->pl[k].D, n * 4));
-        MAP_TRY(hipMalloc(&m->pl[k].X, n * 4)); MAP_TRY(hipMalloc(&m->pl[k].Y, n * 4));
-        MAP_TRY(hipMalloc(&m->pl[k].Z, n * 4));
-        MAP_TRY(hipMalloc(&m->pts[k], n * sizeof(float4)));
+        MAP_TRY(malloc, hipMalloc(&m->pl[k].I, n * 4)); MAP_TRY(malloc, hipMalloc(&m->pl[k].D, n * 4));
+        MAP_TRY(malloc, hipMalloc(&m->pl[k].X, n * 4)); MAP_TRY(malloc, hipMalloc(&m->pl[k].Y, n * 4));
+        MAP_TRY(malloc, hipMalloc(&m->pl[k].Z, n * 4));
+        MAP_TRY(malloc, hipMalloc(&m->pts[k], n * sizeof(float4)));
     }
-    MAP_TRY(hipMalloc(&m->dD1, n * 4));
-    MAP_TRY(hipMalloc(&m->dI1, n));
-    MAP_TRY(hipMalloc(&m->head, n * 4));
-    MAP_TRY(hipMalloc(&m->next, n * 4));
-    MAP_TRY(hipMalloc(&m->state, n));
-    MAP_TRY(hipMalloc(&m->blockcnt, ((n + 1023) / 1024 + 1) * 4));
-    MAP_TRY(hipHostMalloc(&m->h_stage, n * 5));
+    MAP_TRY(malloc, hipMalloc(&m->dD1, n * 4));
+    MAP_TRY(malloc, hipMalloc(&m->dI1, n));
+    MAP_TRY(malloc, hipMalloc(&m->head, n * 4));
+    MAP_TRY(malloc, hipMalloc(&m->next, n * 4));
+    MAP_TRY(malloc, hipMalloc(&m->state, n));
+    MAP_TRY(malloc, hipMalloc(&m->blockcnt, ((n + 1023) / 1024 + 1) * 4));
+    MAP_TRY(malloc, hipHostMalloc(&m->h_stage, n * 5));
     m->w = w;
     m->h = h;
     m->have_prev = false;
@@ -397,18 +381,18 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     if (!m || !D1 || !I1 || !dims || !H_total) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
     const int32_t w = dims[0], h = dims[1], step = dims[2];
     if (w < 1 || h < 1 || step < w || (int64_t)w * h > (1 << 28)) return svh::fail(SVH_ERR_BAD_ARG, "bad dimensions");
-    MAP_TRY(hipSetDevice(m->device));
+    MAP_TRY(none, hipSetDevice(m->device));
     int32_t rc = map_ensure(m, w, h);
     if (rc) return rc;
     hipStream_t s = m->stream;
     const size_t n = (size_t)w * h;
     // inputs: the image rows are packed on the way into pinned memory
     for (int32_t v = 0; v < h; v++) memcpy(m->h_stage + (size_t)v * w, I1 + (size_t)v * step, w);
-    MAP_TRY(hipMemcpyAsync(m->dI1, m->h_stage, n, hipMemcpyHostToDevice, s));
+    MAP_TRY(copy, hipMemcpyAsync(m->dI1, m->h_stage, n, hipMemcpyHostToDevice, s));
     const float* dD = D1;
     if (!d1_on_device) {
         memcpy(m->h_stage + n, D1, n * 4);
-        MAP_TRY(hipMemcpyAsync(m->dD1, m->h_stage + n, n * 4, hipMemcpyHostToDevice, s));
+        MAP_TRY(copy, hipMemcpyAsync(m->dD1, m->h_stage + n, n * 4, hipMemcpyHostToDevice, s));
         dD = m->dD1;
     }
     // coefficients (stereothread.cpp:196-199, 306-314, 450-455) with the Matrix class of the boundary
@@ -443,7 +427,7 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     const int nb = (int)((n + 1023) / 1024);
     if (m->have_prev) {
         const int pn = m->pw * m->ph;   // == n: a geometry change resets the reconstruction
-        MAP_TRY(hipMemsetAsync(m->head, 0xFF, n * 4, s));
+        MAP_TRY(copy, hipMemsetAsync(m->head, 0xFF, n * 4, s));
         hipLaunchKernelGGL(k_map_project, dim3((pn + 255) / 256), dim3(256), 0, s, prev, m->pw, m->ph, w, h, c,
                            m->head, m->next, m->state);
         hipLaunchKernelGGL(k_map_fuse, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, prev, m->pw, m->ph, cur,
@@ -459,8 +443,8 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     hipLaunchKernelGGL(k_map_count<false>, dim3(nb), dim3(256), 0, s, m->state, cur, w, h, m->blockcnt);
     hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, s, m->blockcnt, nb, m->h_total + 1);
     hipLaunchKernelGGL(k_map_scatter<false>, dim3(nb), dim3(256), 0, s, m->state, cur, w, h, m->blockcnt, m->pts[1]);
-    MAP_TRY(hipStreamSynchronize(s));
-    MAP_TRY(hipGetLastError());
+    MAP_TRY(wait, hipStreamSynchronize(s));
+    MAP_TRY(launch, hipGetLastError());
     m->npts[0] = m->h_total[0];
     m->npts[1] = m->h_total[1];
     // the current map becomes the previous one (the intended ":432")
@@ -494,11 +478,11 @@ int32_t svh_disparity_colormap(const float* D, int32_t d_on_device, int64_t n, f
         float*& b;
         ~FreeBoth() { (void)hipFree(a); (void)hipFree(b); }
     } free_both_{dD, dC};
-    MAP_TRY(hipMalloc(&dC, (size_t)n * 12));
+    MAP_TRY(malloc, hipMalloc(&dC, (size_t)n * 12));
     const float* src = D;
     if (!d_on_device) {
-        MAP_TRY(hipMalloc(&dD, (size_t)n * 4));
-        MAP_TRY(hipMemcpy(dD, D, (size_t)n * 4, hipMemcpyHostToDevice));
+        MAP_TRY(malloc, hipMalloc(&dD, (size_t)n * 4));
+        MAP_TRY(copy, hipMemcpy(dD, D, (size_t)n * 4, hipMemcpyHostToDevice));
         src = dD;
     }
     hipLaunchKernelGGL(k_disp_color, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, src, (long long)n, dC);
@@ -511,10 +495,10 @@ int32_t svh_map_planes(svh_map* m, float* out5, size_t cap_floats) {
     if (!m || !out5 || !m->have_prev) return svh::fail(SVH_ERR_BAD_ARG, "no map yet");
     const size_t n = (size_t)m->w * m->h;
     if (cap_floats < 5 * n) return svh::fail(SVH_ERR_BAD_ARG, "buffer too small");
-    MAP_TRY(hipSetDevice(m->device));
+    MAP_TRY(none, hipSetDevice(m->device));
     const Planes& p = m->pl[1 - m->cur];   // the map of the last frame
     float* src[5] = {p.I, p.D, p.X, p.Y, p.Z};
-    for (int k = 0; k < 5; k++) MAP_TRY(hipMemcpy(out5 + k * n, src[k], n * 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 5; k++) MAP_TRY(copy, hipMemcpy(out5 + k * n, src[k], n * 4, hipMemcpyDeviceToHost));
     return SVH_OK;
 }
 

@@ -36,15 +36,12 @@
 #include <vector>
 
 #include "batch_rec.h"
+#include "hip_guard.h"
 #include "matcher_internal.h"
 #include "vo_internal.h"
 
 namespace svh {
 
-int fail(int code, const std::string& msg);   // elas_engine.cpp: sets svh_last_error()
-bool fi_armed();                                    // elas_engine.cpp: fault injection (svh_internal.h)
-bool fi_hit(const char* expr_text);
-void report_hip_failure(const char* entry);
 static int mfail(int code, const std::string& msg) { return fail(code, msg); }
 
 // Threads that are inside a compute entry of the Matcher / visual odometry right now (svh_matcher_push_back,
@@ -84,25 +81,18 @@ hipError_t BatchRec::flush(hipStream_t s) {
     auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
     size_t need = 0;
     for (const Slot& sl : slots) need += al(sl.jobs.size());
-    if (used + need > cap) {
-        // the arena may still be read by launches in flight: wait, then grow
+    if (used + need > d_arena.cap) {
+        // the arena may still be read by launches in flight: wait, then grow (a failed allocation leaves an arena of
+        // size 0: the next flush allocates again)
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) return e;
-        if (h_arena) (void)hipHostFree(h_arena);
-        if (d_arena) (void)hipFree(d_arena);
-        h_arena = d_arena = nullptr;
         const size_t want = std::max<size_t>(2 * (used + need), 256 * 1024);
-        cap = 0;      // (a failed allocation leaves an arena of size 0: the next flush allocates again)
         used = 0;
-        e = hipHostMalloc((void**)&h_arena, want);
-        if (e != hipSuccess) return e;
-        e = hipMalloc((void**)&d_arena, want);
-        if (e != hipSuccess) {
-            (void)hipHostFree(h_arena);
-            h_arena = nullptr;
+        if ((e = h_arena.grow(want)) != hipSuccess || (e = d_arena.grow(want)) != hipSuccess) {
+            h_arena.release();
+            d_arena.release();
             return e;
         }
-        cap = want;
     }
     size_t off = used;
     std::vector<size_t> at;
@@ -154,10 +144,8 @@ hipError_t BatchRec::join_side(hipStream_t s) {
 }
 
 void BatchRec::release() {
-    if (h_arena) (void)hipHostFree(h_arena);
-    if (d_arena) (void)hipFree(d_arena);
-    h_arena = d_arena = nullptr;
-    cap = 0;
+    h_arena.release();
+    d_arena.release();
     for (int i = 0; i < kSide; i++) {
         if (side[i]) (void)hipStreamDestroy(side[i]);
         if (side_done[i]) (void)hipEventDestroy(side_done[i]);
@@ -326,19 +314,8 @@ private:
 thread_local bool t_in_batch = false;   // inside a batch call: the outlier vote does not fork (the pool is the parallelism)
 }  // namespace
 
-// a failed HIP call: svh_last_error() names it, one line on stderr at the point of failure (the entries above it
-// only pass the code on), SVH_ERR_HIP
-static int hip_failed(const char* expr, bool injected, hipError_t e) {
-    const int rc = mfail(SVH_ERR_HIP, std::string(expr) + ": " + (injected ? "injected failure (SVH_TEST_FAIL_AT)" : hipGetErrorString(e)));
-    report_hip_failure("Matcher");
-    return rc;
-}
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        const bool inj_ = fi_armed() && fi_hit(#expr);   /* svh_internal.h: fault injection */ \
-        hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                     \
-        if (e_ != hipSuccess) return hip_failed(#expr, inj_, e_);                            \
-    } while (0)
+// (one line on stderr at the point of failure: the entries above it only pass the code on)
+#define HIP_TRY(kind, expr) SVH_HIP_TRY("Matcher", kind, expr)
 
 template <typename T>
 static hipError_t dalloc(T** p, size_t count) {
@@ -460,9 +437,6 @@ struct svh_matcher {
     double tdev[3] = {0, 0, 0};
 };
 
-static double mnow_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 // SVH_MATCHER_TIMING, evaluated at the first use (never while the library is loaded)
 static std::atomic<int> g_mtiming_api{0};   // svh_matcher_set_timing
 static bool mtiming_on() {
@@ -519,30 +493,30 @@ static int size_view(svh_matcher* m, DevView& V, int32_t w, int32_t h, int32_t b
         V.mw = w; V.mh = h; V.mbpl = bpl;
     }
     const size_t fn = (size_t)bpl * h, mn = (size_t)V.mbpl * V.mh;
-    HIP_TRY(dalloc(&V.I, fn));
-    HIP_TRY(dalloc(&V.du, mn));
-    HIP_TRY(dalloc(&V.dv, mn));
-    HIP_TRY(dalloc(&V.f1, mn));
-    HIP_TRY(dalloc(&V.f2, mn));
+    HIP_TRY(malloc, dalloc(&V.I, fn));
+    HIP_TRY(malloc, dalloc(&V.du, mn));
+    HIP_TRY(malloc, dalloc(&V.dv, mn));
+    HIP_TRY(malloc, dalloc(&V.f1, mn));
+    HIP_TRY(malloc, dalloc(&V.f2, mn));
     if (p.half_resolution) {
-        HIP_TRY(dalloc(&V.Ih, mn));
-        HIP_TRY(dalloc(&V.du_full, fn));
-        HIP_TRY(dalloc(&V.dv_full, fn));
+        HIP_TRY(malloc, dalloc(&V.Ih, mn));
+        HIP_TRY(malloc, dalloc(&V.du_full, fn));
+        HIP_TRY(malloc, dalloc(&V.dv_full, fn));
     }
     // one zero row past the image: getGain clamps its window to [0,H] INCLUSIVE like the reference
     // (matcher.cpp:362-371), whose read of row H is out of bounds; here it reads zeros
-    HIP_TRY(hipHostMalloc((void**)&V.stage, fn + bpl));
+    HIP_TRY(malloc, hipHostMalloc((void**)&V.stage, fn + bpl));
     memset(V.stage + fn, 0, bpl);
-    HIP_TRY(dalloc(&V.cnt, 2));
-    HIP_TRY(hipMemsetAsync(V.cnt, 0, 2 * sizeof(int32_t), m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));   // (re)allocation path only; the cameras use two streams
+    HIP_TRY(malloc, dalloc(&V.cnt, 2));
+    HIP_TRY(copy, hipMemsetAsync(V.cnt, 0, 2 * sizeof(int32_t), m->stream));
+    HIP_TRY(wait, hipStreamSynchronize(m->stream));   // (re)allocation path only; the cameras use two streams
     int32_t ns = p.nms_n * 3;
     if (ns > 10) ns = std::max(p.nms_n, 10);           // matcher.cpp:824-828
     const int32_t nn[2] = {ns, p.nms_n};
     for (int k = 0; k < 2; k++) {
         V.cap[k] = 4 * mnms_blocks(V.mw, nn[k], m->margin) * mnms_blocks(V.mh, nn[k], m->margin);
-        HIP_TRY(dalloc(&V.tab[k], (size_t)12 * V.cap[k]));
-        HIP_TRY(dalloc(&V.ids[k], (size_t)V.cap[k]));
+        HIP_TRY(malloc, dalloc(&V.tab[k], (size_t)12 * V.cap[k]));
+        HIP_TRY(malloc, dalloc(&V.ids[k], (size_t)V.cap[k]));
     }
     return SVH_OK;
 }
@@ -553,9 +527,9 @@ static int ensure_feature_scratch(svh_matcher* m, int32_t slot_need) {
     if (slot_need > m->slot_cap) {
         m->slot_cap = 0;
         for (int c = 0; c < 4; c++) {
-            HIP_TRY(drealloc(&m->slots[c], (size_t)slot_need));
-            HIP_TRY(drealloc(&m->flags[c], (size_t)slot_need + 4));
-            HIP_TRY(drealloc(&m->order[c], (size_t)slot_need));
+            HIP_TRY(malloc, drealloc(&m->slots[c], (size_t)slot_need));
+            HIP_TRY(malloc, drealloc(&m->flags[c], (size_t)slot_need + 4));
+            HIP_TRY(malloc, drealloc(&m->order[c], (size_t)slot_need));
         }
         m->slot_cap = slot_need;
     }
@@ -565,15 +539,15 @@ static int ensure_feature_scratch(svh_matcher* m, int32_t slot_need) {
 static int ensure_match_scratch(svh_matcher* m, int32_t pm_need, size_t owner_need) {
     if (pm_need > m->pm_cap) {
         m->pm_cap = 0;
-        HIP_TRY(drealloc(&m->pm_slots, (size_t)pm_need));
-        HIP_TRY(drealloc(&m->pm_out, (size_t)pm_need));
-        HIP_TRY(drealloc(&m->pm_flags, (size_t)pm_need));
+        HIP_TRY(malloc, drealloc(&m->pm_slots, (size_t)pm_need));
+        HIP_TRY(malloc, drealloc(&m->pm_out, (size_t)pm_need));
+        HIP_TRY(malloc, drealloc(&m->pm_flags, (size_t)pm_need));
         m->pm_cap = pm_need;
     }
-    if (!m->pm_count) HIP_TRY(dalloc(&m->pm_count, 2));
+    if (!m->pm_count) HIP_TRY(malloc, dalloc(&m->pm_count, 2));
     if (owner_need > m->owner_cap) {
         m->owner_cap = 0;
-        HIP_TRY(drealloc(&m->pixel_owner, owner_need));
+        HIP_TRY(malloc, drealloc(&m->pixel_owner, owner_need));
         m->owner_cap = owner_need;
     }
     return SVH_OK;
@@ -599,7 +573,7 @@ static int features_enqueue(svh_matcher* m, DevView& V, int cam, double* tf, boo
     hipStream_t s = on ? on : (cam == 1 ? m->stream2 : m->stream);
     const size_t fn = (size_t)V.bpl * V.h;
     const uint8_t* stage = V.stage;
-    auto ftick = [&](int i) { if (g_mtiming && tf) tf[i] = mnow_ms(); };
+    auto ftick = [&](int i) { if (g_mtiming && tf) tf[i] = now_ms(); };
     ftick(1);
     if (uploaded)
         ;   // (a lockstep call: issued by the thread that packed the image)
@@ -644,7 +618,7 @@ static int features_enqueue(svh_matcher* m, DevView& V, int cam, double* tf, boo
 
 static int compute_features(svh_matcher* m, DevView& V, int cam, const uint8_t* src, int32_t pitch) {
     double tf[6] = {0, 0, 0, 0, 0, 0};
-    if (g_mtiming) tf[0] = mnow_ms();
+    if (g_mtiming) tf[0] = now_ms();
     int rc = features_pack(m, V, cam, src, pitch);
     if (rc) return rc;
     rc = features_enqueue(m, V, cam, tf);
@@ -664,7 +638,7 @@ static int ensure_bins(svh_matcher* m, DevView* const* views, int nviews, int32_
         if (!V.valid || V.nbins == nb) continue;
         if (nb > V.off_cap) {   // (re)allocate only when the bin grid grows: hipFree synchronises the device
             V.off_cap = 0;
-            for (int k = 0; k < 2; k++) HIP_TRY(drealloc(&V.off[k], (size_t)nb + 1));
+            for (int k = 0; k < 2; k++) HIP_TRY(malloc, drealloc(&V.off[k], (size_t)nb + 1));
             V.off_cap = nb;
         }
         for (int k = 0; k < 2; k++) {
@@ -680,7 +654,7 @@ static int ensure_bins(svh_matcher* m, DevView* const* views, int nviews, int32_
     if (!nj) return SVH_OK;
     if (nb > m->cursor_cap) {
         m->cursor_cap = 0;
-        HIP_TRY(drealloc(&m->cursor, (size_t)nb));
+        HIP_TRY(malloc, drealloc(&m->cursor, (size_t)nb));
         m->cursor_cap = nb;
     }
     mlaunch_bin_index(m->stream, J, nj, nmax, ub, vb, m->p.match_binsize, m->cursor);
@@ -849,8 +823,8 @@ static int match_enqueue(svh_matcher* m, int dense, int32_t method, bool use_pri
     if (rc) return rc;
     if (nq > m->h_pm_cap || !m->h_cnt) {
         m->h_pm_cap = 0;
-        HIP_TRY(hrealloc(&m->h_pm, (size_t)std::max(nq, 1) * sizeof(svh_p_match)));
-        if (!m->h_cnt) HIP_TRY(hipHostMalloc((void**)&m->h_cnt, sizeof(int32_t)));
+        HIP_TRY(malloc, hrealloc(&m->h_pm, (size_t)std::max(nq, 1) * sizeof(svh_p_match)));
+        if (!m->h_cnt) HIP_TRY(malloc, hipHostMalloc((void**)&m->h_cnt, sizeof(int32_t)));
         m->h_pm_cap = std::max(nq, 1);
     }
     mlaunch_match(m->stream, P, view_of(m->prev[0], dense), view_of(m->prev[1], dense), view_of(m->cur[0], dense),
@@ -902,8 +876,8 @@ static int run_matching(svh_matcher* m, int dense, int32_t method, bool use_prio
             m->warm_on_wait = false;
             helpers_warm(7, 1500);
         }
-        HIP_TRY((hipError_t)wait_stream(m->stream));
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(none, (hipError_t)wait_stream(m->stream));
+        HIP_TRY(launch, hipGetLastError());
         match_collect(m, mp, dst);
         return SVH_OK;
     };
@@ -1080,9 +1054,9 @@ static int32_t push_take_prefetched(svh_matcher* m, int32_t replace, bool stream
         }
     }
     if (!stream_waited) {
-        HIP_TRY(hipSetDevice(m->device));
-        HIP_TRY((hipError_t)wait_stream(m->next_stream));
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(none, hipSetDevice(m->device));
+        HIP_TRY(none, (hipError_t)wait_stream(m->next_stream));
+        HIP_TRY(launch, hipGetLastError());
     }
     for (int k = 0; k < 2; k++) {
         if (!replace) {
@@ -1117,9 +1091,9 @@ static int32_t push_prepare(svh_matcher* m, const uint8_t* I1, const uint8_t* I2
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return mfail(SVH_ERR_NO_DEVICE, "no HIP device visible: libsvhip has no CPU fallback");
-    HIP_TRY(hipSetDevice(m->device));
-    if (!m->stream) HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-    if (!m->stream2) HIP_TRY(hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
+    HIP_TRY(none, hipSetDevice(m->device));
+    if (!m->stream) HIP_TRY(none, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    if (!m->stream2) HIP_TRY(none, hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
     if (!replace) {
         // ring buffer: current -> previous; the old previous buffers are recycled
         for (int k = 0; k < 2; k++) {
@@ -1133,7 +1107,7 @@ static int32_t push_prepare(svh_matcher* m, const uint8_t* I1, const uint8_t* I2
     m->dims_c[0] = w;
     m->dims_c[1] = h;
     m->dims_c[2] = w + 16 - w % 16;   // +16 even when w % 16 == 0 (matcher.cpp:173)
-    if (!m->h_n) HIP_TRY(hipHostMalloc((void**)&m->h_n, 8 * sizeof(int32_t)));   // [4..7]: a prefetched frame's
+    if (!m->h_n) HIP_TRY(malloc, hipHostMalloc((void**)&m->h_n, 8 * sizeof(int32_t)));   // [4..7]: a prefetched frame's
     const uint8_t* src[2] = {I1, I2};
     for (int k = 0; k < 2; k++) {
         if (!src[k]) continue;
@@ -1160,7 +1134,7 @@ int32_t svh_matcher_push_back(svh_matcher* m, const uint8_t* I1, const uint8_t* 
     if (rc) return rc;
     const uint8_t* src[2] = {I1, I2};
     const bool timed = g_mtiming;
-    const double t0 = timed ? mnow_ms() : 0;
+    const double t0 = timed ? now_ms() : 0;
     for (int k = 0; k < 2; k++) {
         if (!src[k]) continue;
         if (timed) tev_record(m, 2 * k, k == 1 ? m->stream2 : m->stream);
@@ -1168,14 +1142,14 @@ int32_t svh_matcher_push_back(svh_matcher* m, const uint8_t* I1, const uint8_t* 
         if (rc) return rc;
         if (timed) tev_record(m, 2 * k + 1, k == 1 ? m->stream2 : m->stream);
     }
-    const double t1 = timed ? mnow_ms() : 0;
-    HIP_TRY((hipError_t)wait_stream(m->stream));
-    HIP_TRY((hipError_t)wait_stream(m->stream2));
-    HIP_TRY(hipGetLastError());
+    const double t1 = timed ? now_ms() : 0;
+    HIP_TRY(none, (hipError_t)wait_stream(m->stream));
+    HIP_TRY(none, (hipError_t)wait_stream(m->stream2));
+    HIP_TRY(launch, hipGetLastError());
     push_finish(m, I1, I2);
     if (timed) {
         m->tacc[T_PACK] += t1 - t0;
-        m->tacc[T_PUSH_GPU] += mnow_ms() - t1;
+        m->tacc[T_PUSH_GPU] += now_ms() - t1;
         m->tcalls[0]++;
         // (the two cameras run on two streams side by side: the longer one is the phase's device time)
         const double a = src[0] ? tev_ms(m, 0, 1) : 0, b = src[1] ? tev_ms(m, 2, 3) : 0;
@@ -1194,10 +1168,10 @@ static int32_t prefetch_body(const std::vector<svh_matcher*>& ms, const std::vec
     const int K = (int)ms.size();
     for (int i = 0; i < K; i++) {
         svh_matcher* m = ms[i];
-        HIP_TRY(hipSetDevice(m->device));
-        if (!m->stream) HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        if (!m->stream2) HIP_TRY(hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
-        if (!m->h_n) HIP_TRY(hipHostMalloc((void**)&m->h_n, 8 * sizeof(int32_t)));
+        HIP_TRY(none, hipSetDevice(m->device));
+        if (!m->stream) HIP_TRY(none, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+        if (!m->stream2) HIP_TRY(none, hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
+        if (!m->h_n) HIP_TRY(malloc, hipHostMalloc((void**)&m->h_n, 8 * sizeof(int32_t)));
         m->dims_n[0] = w;
         m->dims_n[1] = h;
         m->dims_n[2] = w + 16 - w % 16;
@@ -1210,8 +1184,8 @@ static int32_t prefetch_body(const std::vector<svh_matcher*>& ms, const std::vec
     // The lockstep hand-over runs on a stream of the prefetch thread's own recorder: it outlives every Matcher, so the
     // recorder may wait for it before it reuses its arena whatever happened to the objects of the last hand-over.
     BatchRec& pr = prefetch_recorder(ms[0]->device);
-    HIP_TRY(pr.ensure_side());
-    HIP_TRY(pr.reuse());
+    HIP_TRY(none, pr.ensure_side());
+    HIP_TRY(none, pr.reuse());
     hipStream_t const pf_own = pr.side[0];
     std::vector<int> rcs((size_t)K * ncam, 0);
     // Lockstep hand-over: the K * ncam image uploads are recorded with the features (one k_upload_b launch per camera
@@ -1254,9 +1228,9 @@ static int32_t prefetch_body(const std::vector<svh_matcher*>& ms, const std::vec
                         DevView& V = ms[i]->next[cam];
                         mlaunch_upload(ms[i]->stream2, V.stage, V.I, (size_t)V.bpl * V.h);
                     }
-            HIP_TRY(hipStreamSynchronize(pf));
+            HIP_TRY(wait, hipStreamSynchronize(pf));
         } else {
-            HIP_TRY(pr.flush(pf));
+            HIP_TRY(copy, pr.flush(pf));
             for (int i = 0; i < K; i++) ms[i]->next_stream = pf;
         }
     }
@@ -1337,17 +1311,24 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
                 const int32_t rc = m->next_job.get();
                 m->next_job = std::shared_future<int32_t>();
                 if (rc) {
-                    m->has_next = false;
-                    return mfail(rc, "the hand-over of the prefetched frame failed on the prefetch thread: " + (m->next_why ? *m->next_why : std::string()));
+                    // the hand-over failed for every object it was made for: none of them keeps a pending frame (one
+                    // left pending would refuse the next hand-over of the batch for good)
+                    const std::shared_ptr<std::string> why = m->next_why;
+                    for (int j = 0; j < K; j++)
+                        if (ms[j]->next_why == why) {
+                            ms[j]->has_next = false;
+                            ms[j]->next_job = std::shared_future<int32_t>();
+                        }
+                    return mfail(rc, "the hand-over of the prefetched frame failed on the prefetch thread: " + (why ? *why : std::string()));
                 }
             }
             if (std::find(waited.begin(), waited.end(), m->next_stream) == waited.end()) {
-                HIP_TRY(hipSetDevice(m->device));
-                HIP_TRY((hipError_t)wait_stream(m->next_stream));
+                HIP_TRY(none, hipSetDevice(m->device));
+                HIP_TRY(none, (hipError_t)wait_stream(m->next_stream));
                 waited.push_back(m->next_stream);
             }
         }
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch, hipGetLastError());
         for (int i = 0; i < K; i++) {
             const int32_t rc = push_take_prefetched(ms[i], replace, true);
             if (rc) return rc;
@@ -1371,7 +1352,7 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
     };
     if (!lockstep) return serial();
     double tb[6] = {0, 0, 0, 0, 0, 0};
-    auto btick = [&](int i) { if (g_mtiming) tb[i] = mnow_ms(); };
+    auto btick = [&](int i) { if (g_mtiming) tb[i] = now_ms(); };
     btick(0);
     for (int i = 0; i < K; i++) {
         const int32_t rc = push_prepare(ms[i], I1[i], I2 ? I2[i] : nullptr, dims, replace);
@@ -1381,7 +1362,7 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
     const int ncam = (I2 && I2[0]) ? 2 : 1;
     std::vector<int> rcs((size_t)K * ncam, 0);
     BatchRec& up = batch_recorder(ms[0]->device);
-    HIP_TRY(up.ensure_side());
+    HIP_TRY(none, up.ensure_side());
     struct InBatch {     // (cleared on every exit, the error returns included)
         InBatch() { t_in_batch = true; }
         ~InBatch() { t_in_batch = false; }
@@ -1405,7 +1386,7 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
             mlaunch_upload(q == 0 ? ms[0]->stream : up.side[q - 1], V.stage, V.I, (size_t)V.bpl * V.h);
         }
     });
-    HIP_TRY(up.join_side(ms[0]->stream));
+    HIP_TRY(none, up.join_side(ms[0]->stream));
     for (int rc : rcs)
         if (rc) return rc;
     btick(2);
@@ -1425,22 +1406,22 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
     if (rec.broken) {
         // (not reachable with equal parameters and sizes; kept so that a future launcher change cannot corrupt a batch)
         rec.reset();
-        HIP_TRY((hipError_t)wait_stream(s));   // (the uploads issued above)
+        HIP_TRY(none, (hipError_t)wait_stream(s));   // (the uploads issued above)
         for (int i = 0; i < K; i++) {
             for (int cam = 0; cam < ncam; cam++) {
                 rc = features_enqueue(ms[i], ms[i]->cur[cam], cam, nullptr);
                 if (rc) return rc;
             }
-            HIP_TRY((hipError_t)wait_stream(ms[i]->stream));
-            HIP_TRY((hipError_t)wait_stream(ms[i]->stream2));
+            HIP_TRY(none, (hipError_t)wait_stream(ms[i]->stream));
+            HIP_TRY(none, (hipError_t)wait_stream(ms[i]->stream2));
             push_finish(ms[i], I1[i], I2 ? I2[i] : nullptr);
         }
         return SVH_OK;
     }
-    HIP_TRY(rec.flush(s));
+    HIP_TRY(copy, rec.flush(s));
     btick(4);
-    HIP_TRY((hipError_t)wait_stream(s));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(none, (hipError_t)wait_stream(s));
+    HIP_TRY(launch, hipGetLastError());
     rec.synced();
     for (int i = 0; i < K; i++) push_finish(ms[i], I1[i], I2 ? I2[i] : nullptr);
     btick(5);
@@ -1492,7 +1473,7 @@ static int32_t match_prepare(svh_matcher* m, int32_t ub, int32_t vb) {
     if (rc) return rc;
     if (ub * vb > m->ranges_cap) {
         m->ranges_cap = 0;
-        HIP_TRY(drealloc(&m->ranges_dev, (size_t)16 * ub * vb));
+        HIP_TRY(malloc, drealloc(&m->ranges_dev, (size_t)16 * ub * vb));
         m->ranges_cap = ub * vb;
     }
     return SVH_OK;
@@ -1505,13 +1486,13 @@ int32_t svh_matcher_match_features(svh_matcher* m, int32_t method, const double*
     if (!match_inputs_present(m, method)) return SVH_OK;
     if (method > 2) method = 2;
     KeepMatches keep_({m});
-    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(none, hipSetDevice(m->device));
     const int32_t ub = (int32_t)ceilf((float)m->dims_c[0] / (float)p.match_binsize);
     const int32_t vb = (int32_t)ceilf((float)m->dims_c[1] / (float)p.match_binsize);
     int rc = match_prepare(m, ub, vb);
     if (rc) return rc;
     double tm[6] = {0, 0, 0, 0, 0, 0};
-    auto tick = [&](int i) { if (g_mtiming) tm[i] = mnow_ms(); };
+    auto tick = [&](int i) { if (g_mtiming) tm[i] = now_ms(); };
     tick(0);
     // the dense vote of a frame like the last one will triangulate on helper threads: have them awake by then
     const bool warm = m->last_dense >= kVoteParMin && vote_par_depth() > 0;
@@ -1524,7 +1505,7 @@ int32_t svh_matcher_match_features(svh_matcher* m, int32_t method, const double*
         tick(2);
         if (m->taps) m->stage[SVH_M_SPARSE] = m->m1;
         prior_statistics(m, m->m1, method, ub, vb);
-        HIP_TRY(hipMemcpyAsync(m->ranges_dev, m->ranges.data(), m->ranges.size() * sizeof(float),
+        HIP_TRY(copy, hipMemcpyAsync(m->ranges_dev, m->ranges.data(), m->ranges.size() * sizeof(float),
                                hipMemcpyHostToDevice, m->stream));
         tick(3);
         m->warm_on_wait = warm;
@@ -1591,7 +1572,7 @@ int32_t svh_matcher_match_features_batch(svh_matcher* const* ms, int32_t K, int3
     KeepMatches keep_(part);
     const int n = (int)part.size();
     const svh_matcher_params& p = part[0]->p;
-    HIP_TRY(hipSetDevice(part[0]->device));
+    HIP_TRY(none, hipSetDevice(part[0]->device));
     const int32_t ub = (int32_t)ceilf((float)part[0]->dims_c[0] / (float)p.match_binsize);
     const int32_t vb = (int32_t)ceilf((float)part[0]->dims_c[1] / (float)p.match_binsize);
     hipStream_t s = part[0]->stream;
@@ -1599,7 +1580,7 @@ int32_t svh_matcher_match_features_batch(svh_matcher* const* ms, int32_t K, int3
     std::vector<MatchPass> mp(n);
     std::vector<int> rcs(n, 0);
     double t_wait = 0, tm[5] = {0, 0, 0, 0, 0};
-    auto mtick = [&](int i) { if (g_mtiming) tm[i] = mnow_ms(); };
+    auto mtick = [&](int i) { if (g_mtiming) tm[i] = now_ms(); };
     mtick(0); mtick(1); mtick(2);
     // record one device phase over all objects; on a sequence mismatch the objects run one by one instead
     // (an error exit from a recording pass: ensure_bins has marked the bin indices of the recorded objects as built
@@ -1625,17 +1606,17 @@ int32_t svh_matcher_match_features_batch(svh_matcher* const* ms, int32_t K, int3
                 for (int k = 0; k < 2; k++) part[i]->prev[k].nbins = part[i]->cur[k].nbins = 0;
                 rc = body(i);
                 if (rc) return rc;
-                HIP_TRY((hipError_t)wait_stream(part[i]->stream));
+                HIP_TRY(none, (hipError_t)wait_stream(part[i]->stream));
             }
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch, hipGetLastError());
             return SVH_OK;
         }
-        HIP_TRY(rec.flush(s));
-        const double tw = g_mtiming ? mnow_ms() : 0;
-        HIP_TRY((hipError_t)wait_stream(s));
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(copy, rec.flush(s));
+        const double tw = g_mtiming ? now_ms() : 0;
+        HIP_TRY(none, (hipError_t)wait_stream(s));
+        HIP_TRY(launch, hipGetLastError());
         rec.synced();
-        if (g_mtiming) t_wait += mnow_ms() - tw;
+        if (g_mtiming) t_wait += now_ms() - tw;
         return SVH_OK;
     };
     auto device_phase = [&](const std::function<int(int)>& body) -> int {
@@ -1680,7 +1661,7 @@ int32_t svh_matcher_match_features_batch(svh_matcher* const* ms, int32_t K, int3
             match_collect(m, mp[i], m->m1);
             if (nr > m->h_ranges_cap) {
                 m->h_ranges_cap = 0;
-                HIP_TRY(hrealloc(&m->h_ranges, nr * sizeof(float)));
+                HIP_TRY(malloc, hrealloc(&m->h_ranges, nr * sizeof(float)));
                 m->h_ranges_cap = nr;
             }
         }

@@ -21,46 +21,20 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <string>
 #include <vector>
 
 #include "../../include/svh_plane.h"
+#include "hip_guard.h"
 #include "plane_internal.h"
 #include "vo_internal.h"
-
-namespace svh {
-int fail(int code, const std::string& msg);   // elas_engine.cpp: records svh_last_error()
-bool fi_armed();                              // elas_engine.cpp: fault injection (svh_internal.h)
-bool fi_hit(const char* expr_text);
-void report_hip_failure(const char* entry);
-}  // namespace svh
 
 using namespace svh;
 
 namespace {
 
-int plane_hip_failed(const char* expr, bool injected, hipError_t e) {
-    const int rc = svh::fail(SVH_ERR_HIP, std::string(expr) + ": " +
-                                              (injected ? "injected failure (SVH_TEST_FAIL_AT)" : hipGetErrorString(e)));
-    svh::report_hip_failure("PlaneEstimation");
-    return rc;
-}
-#define PLANE_TRY(expr)                                                                                  \
-    do {                                                                                                 \
-        const bool inj_ = svh::fi_armed() && svh::fi_hit(#expr); /* svh_internal.h: fault injection */   \
-        hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                                 \
-        if (e_ != hipSuccess) return plane_hip_failed(#expr, inj_, e_);                                  \
-    } while (0)
-
-// (a name the fault injection files under `wait`)
-hipError_t stream_wait(hipStream_t s) { return (hipError_t)wait_stream(s); }
-
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+#define PLANE_TRY(kind, expr) SVH_HIP_TRY("PlaneEstimation", kind, expr)
+#define PLANE_GROW(buf, bytes) SVH_HIP_GROW("PlaneEstimation", buf, bytes)
 
 constexpr size_t RAW_KEEP = 1u << 20;   // raw draws an object keeps between calls (4 MB); a longer walk is not cached
 
@@ -118,48 +92,35 @@ struct svh_plane {
     // device side
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint8_t *d_all = nullptr, *h_all = nullptr;
-    size_t cap_all = 0;
-    float *d_map = nullptr, *h_map = nullptr;   // a host map on its way to the device
-    size_t cap_map = 0;
+    HipBuf<uint8_t> d_all;
+    PinnedBuf<uint8_t> h_all;
+    HipBuf<float> d_map;                        // a host map on its way to the device
+    PinnedBuf<float> h_map;
 };
 
 namespace {
 
 void release_buffers(svh_plane* p) {
-    p->cap_all = 0;
-    p->cap_map = 0;
-    (void)hipFree(p->d_all); p->d_all = nullptr;
-    (void)hipHostFree(p->h_all); p->h_all = nullptr;
-    (void)hipFree(p->d_map); p->d_map = nullptr;
-    (void)hipHostFree(p->h_map); p->h_map = nullptr;
+    p->d_all.release();
+    p->h_all.release();
+    p->d_map.release();
+    p->h_map.release();
 }
 
 int ensure(svh_plane* p, size_t all_bytes, size_t map_bytes) {
-    PLANE_TRY(hipSetDevice(p->device));
+    PLANE_TRY(none, hipSetDevice(p->device));
     if (!p->stream) {
         hipStream_t s = nullptr;
-        PLANE_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        PLANE_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         p->stream = s;
     }
     for (int i = 0; i < 4; i++)
-        if (!p->ev[i]) PLANE_TRY(hipEventCreate(&p->ev[i]));
-    if (all_bytes > p->cap_all) {
-        // (capacity goes to 0 before anything is freed and back up only when both buffers exist)
-        p->cap_all = 0;
-        (void)hipFree(p->d_all); p->d_all = nullptr;
-        (void)hipHostFree(p->h_all); p->h_all = nullptr;
-        PLANE_TRY(hipMalloc((void**)&p->d_all, all_bytes + 16));
-        PLANE_TRY(hipHostMalloc((void**)&p->h_all, all_bytes + 16));
-        p->cap_all = all_bytes;
-    }
-    if (map_bytes > p->cap_map) {
-        p->cap_map = 0;
-        (void)hipFree(p->d_map); p->d_map = nullptr;
-        (void)hipHostFree(p->h_map); p->h_map = nullptr;
-        PLANE_TRY(hipMalloc((void**)&p->d_map, map_bytes + 16));
-        PLANE_TRY(hipHostMalloc((void**)&p->h_map, map_bytes + 16));
-        p->cap_map = map_bytes;
+        if (!p->ev[i]) PLANE_TRY(none, hipEventCreate(&p->ev[i]));
+    PLANE_GROW(p->d_all, all_bytes + 16);
+    PLANE_GROW(p->h_all, all_bytes + 16);
+    if (map_bytes) {
+        PLANE_GROW(p->d_map, map_bytes + 16);
+        PLANE_GROW(p->h_map, map_bytes + 16);
     }
     return SVH_OK;
 }
@@ -258,13 +219,13 @@ int run(svh_plane* const* objs, const float* const* D, bool on_device, int32_t n
 
     // ---- phase 0: the list
     if (w->timing) (void)hipEventRecord(w->ev[0], w->stream);
-    if (!on_device) PLANE_TRY(hipMemcpyAsync(w->d_map, w->h_map, 4 * map_floats, hipMemcpyHostToDevice, w->stream));
-    PLANE_TRY(hipMemcpyAsync(d + lay.maps, h + lay.maps, 8 * (size_t)n, hipMemcpyHostToDevice, w->stream));
+    if (!on_device) PLANE_TRY(copy, hipMemcpyAsync(w->d_map, w->h_map, 4 * map_floats, hipMemcpyHostToDevice, w->stream));
+    PLANE_TRY(copy, hipMemcpyAsync(d + lay.maps, h + lay.maps, 8 * (size_t)n, hipMemcpyHostToDevice, w->stream));
     planelaunch_grid(w->stream, P, n, L, step, row0);
-    PLANE_TRY(hipGetLastError());
-    PLANE_TRY(hipMemcpyAsync(h + lay.n_list, d + lay.n_list, lay.sel - lay.n_list, hipMemcpyDeviceToHost, w->stream));
+    PLANE_TRY(launch, hipGetLastError());
+    PLANE_TRY(copy, hipMemcpyAsync(h + lay.n_list, d + lay.n_list, lay.sel - lay.n_list, hipMemcpyDeviceToHost, w->stream));
     if (w->timing) (void)hipEventRecord(w->ev[1], w->stream);
-    PLANE_TRY(stream_wait(w->stream));
+    PLANE_TRY(wait, (hipError_t)wait_stream(w->stream));
     const double t_list = now_ms();
     const int32_t* n_list = reinterpret_cast<const int32_t*>(h + lay.n_list);
     const float* lu = reinterpret_cast<const float*>(h + lay.lu);
@@ -300,13 +261,13 @@ int run(svh_plane* const* objs, const float* const* D, bool on_device, int32_t n
     if (max_n > 0) {
         // ---- phase 2: fits, votes, winner
         if (w->timing) (void)hipEventRecord(w->ev[2], w->stream);
-        PLANE_TRY(hipMemcpyAsync(d + lay.samples, h + lay.samples, 16 * (size_t)S * n, hipMemcpyHostToDevice, w->stream));
-        PLANE_TRY(hipMemsetAsync(d + lay.counts, 0, 4 * (size_t)S * n, w->stream));
+        PLANE_TRY(copy, hipMemcpyAsync(d + lay.samples, h + lay.samples, 16 * (size_t)S * n, hipMemcpyHostToDevice, w->stream));
+        PLANE_TRY(copy, hipMemsetAsync(d + lay.counts, 0, 4 * (size_t)S * n, w->stream));
         planelaunch_vote(w->stream, P, n, max_n, c.d_threshold);
-        PLANE_TRY(hipGetLastError());
-        PLANE_TRY(hipMemcpyAsync(h + lay.sel, d + lay.sel, lay.end - lay.sel, hipMemcpyDeviceToHost, w->stream));
+        PLANE_TRY(launch, hipGetLastError());
+        PLANE_TRY(copy, hipMemcpyAsync(h + lay.sel, d + lay.sel, lay.end - lay.sel, hipMemcpyDeviceToHost, w->stream));
         if (w->timing) (void)hipEventRecord(w->ev[3], w->stream);
-        PLANE_TRY(stream_wait(w->stream));
+        PLANE_TRY(wait, (hipError_t)wait_stream(w->stream));
         t_vote = now_ms();
 
         // ---- phase 3: refit in list order, planeDsiTo3d
@@ -409,13 +370,13 @@ void svh_plane_destroy(svh_plane* p) {
     }
     for (int i = 0; i < 4; i++)
         if (p->ev[i]) (void)hipEventDestroy(p->ev[i]);
-    release_buffers(p);
     delete p;
 }
 
 int64_t svh_plane_release(svh_plane* p) {
     if (!p) return 0;
-    const int64_t bytes = (int64_t)(2 * p->cap_all + 2 * p->cap_map + 4 * p->raw.capacity());
+    auto payload = [](size_t cap) { return cap ? cap - 16 : 0; };   // (without the slack every buffer carries)
+    const int64_t bytes = (int64_t)(2 * payload(p->d_all.cap) + 2 * payload(p->d_map.cap) + 4 * p->raw.capacity());
     if (p->stream) {
         (void)hipSetDevice(p->device);
         (void)hipStreamSynchronize(p->stream);

@@ -16,46 +16,22 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <numeric>
 #include <string>
 #include <vector>
 
 #include "../../include/matrix.h"
 #include "../../include/svh.h"
+#include "hip_guard.h"
 #include "recon_core.h"
 #include "recon_internal.h"
 #include "vo_internal.h"
-
-namespace svh {
-int fail(int code, const std::string& msg);   // elas_engine.cpp: records svh_last_error()
-bool fi_armed();                              // elas_engine.cpp: fault injection (svh_internal.h)
-bool fi_hit(const char* expr_text);
-void report_hip_failure(const char* entry);
-}  // namespace svh
 
 using namespace svh;
 
 namespace {
 
-int recon_hip_failed(const char* expr, bool injected, hipError_t e) {
-    const int rc = svh::fail(SVH_ERR_HIP, std::string(expr) + ": " +
-                                              (injected ? "injected failure (SVH_TEST_FAIL_AT)" : hipGetErrorString(e)));
-    svh::report_hip_failure("Reconstruction");
-    return rc;
-}
-#define RECON_TRY(expr)                                                                                  \
-    do {                                                                                                 \
-        const bool inj_ = svh::fi_armed() && svh::fi_hit(#expr); /* svh_internal.h: fault injection */   \
-        hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                                 \
-        if (e_ != hipSuccess) return recon_hip_failed(#expr, inj_, e_);                                  \
-    } while (0)
-
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+#define RECON_TRY(kind, expr) SVH_HIP_TRY("Reconstruction", kind, expr)
 
 struct Track {                  // Reconstruction::track (reconstruction.h:79-84)
     std::vector<float> px;      // u, v per frame
@@ -116,13 +92,13 @@ namespace {
 template <typename T>
 int regrow(svh_recon* r, T** p, size_t keep, size_t bytes) {
     T* q = nullptr;
-    RECON_TRY(hipMalloc((void**)&q, bytes + 16));
+    RECON_TRY(malloc, hipMalloc((void**)&q, bytes + 16));
     if (keep) {
         hipError_t e = hipMemcpyAsync(q, *p, keep, hipMemcpyDeviceToDevice, r->stream);
         if (e == hipSuccess) e = (hipError_t)wait_stream(r->stream);
         if (e != hipSuccess) {
             (void)hipFree(q);
-            return recon_hip_failed("hipMemcpyAsync(grow)", false, e);
+            return svh::hip_failed("Reconstruction", "hipMemcpyAsync(grow)", false, e);
         }
     }
     (void)hipFree(*p);
@@ -132,15 +108,15 @@ int regrow(svh_recon* r, T** p, size_t keep, size_t bytes) {
 
 // room for one update that may upload `new_frames` records and lose up to `lost` tracks with `px` pixels in all
 int ensure(svh_recon* r, int32_t total_frames, int32_t new_frames, size_t lost, size_t px) {
-    RECON_TRY(hipSetDevice(r->device));
+    RECON_TRY(none, hipSetDevice(r->device));
     if (!r->stream) {
         hipStream_t s = nullptr;
-        RECON_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        RECON_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         r->stream = s;
     }
     for (int i = 0; i < 2; i++)
-        if (!r->ev[i]) RECON_TRY(hipEventCreate(&r->ev[i]));
-    if (!r->h_count) RECON_TRY(hipHostMalloc((void**)&r->h_count, 64));
+        if (!r->ev[i]) RECON_TRY(none, hipEventCreate(&r->ev[i]));
+    if (!r->h_count) RECON_TRY(malloc, hipHostMalloc((void**)&r->h_count, 64));
     int rc;
     if (total_frames > r->cap_frames) {
         const int32_t cap = std::max(total_frames, std::max(64, 2 * r->cap_frames));
@@ -162,8 +138,8 @@ int ensure(svh_recon* r, int32_t total_frames, int32_t new_frames, size_t lost, 
         r->h_in = nullptr;
         (void)hipFree(r->d_in);
         r->d_in = nullptr;
-        RECON_TRY(hipHostMalloc((void**)&r->h_in, cap + 16));
-        RECON_TRY(hipMalloc((void**)&r->d_in, cap + 16));
+        RECON_TRY(malloc, hipHostMalloc((void**)&r->h_in, cap + 16));
+        RECON_TRY(malloc, hipMalloc((void**)&r->d_in, cap + 16));
         r->cap_in = cap;
     }
     if ((int64_t)lost > (int64_t)r->cap_lost) {
@@ -173,10 +149,10 @@ int ensure(svh_recon* r, int32_t total_frames, int32_t new_frames, size_t lost, 
         (void)hipFree(r->d_xyz); r->d_xyz = nullptr;
         (void)hipHostFree(r->h_code); r->h_code = nullptr;
         (void)hipHostFree(r->h_xyz); r->h_xyz = nullptr;
-        RECON_TRY(hipMalloc((void**)&r->d_code, 4 * cap + 16));
-        RECON_TRY(hipMalloc((void**)&r->d_xyz, 12 * cap + 16));
-        RECON_TRY(hipHostMalloc((void**)&r->h_code, 4 * cap + 16));
-        RECON_TRY(hipHostMalloc((void**)&r->h_xyz, 12 * cap + 16));
+        RECON_TRY(malloc, hipMalloc((void**)&r->d_code, 4 * cap + 16));
+        RECON_TRY(malloc, hipMalloc((void**)&r->d_xyz, 12 * cap + 16));
+        RECON_TRY(malloc, hipHostMalloc((void**)&r->h_code, 4 * cap + 16));
+        RECON_TRY(malloc, hipHostMalloc((void**)&r->h_xyz, 12 * cap + 16));
         r->cap_lost = (int32_t)cap;
     }
     return SVH_OK;
@@ -254,9 +230,9 @@ int run_lost(svh_recon* r, const std::vector<int32_t>& lost, size_t n_px, const 
                    r->d_frames, total_frames, s, r->d_code, r->d_xyz, r->d_points, r->n_points, r->h_code, r->h_xyz,
                    r->h_count);
     if (r->timing) (void)hipEventRecord(r->ev[1], r->stream);
-    RECON_TRY(hipGetLastError());
-    RECON_TRY((hipError_t)wait_stream(r->stream));
-    RECON_TRY(hipGetLastError());
+    RECON_TRY(launch, hipGetLastError());
+    RECON_TRY(none, (hipError_t)wait_stream(r->stream));
+    RECON_TRY(launch, hipGetLastError());
     const double t_done = now_ms();
     const int32_t count = r->h_count[0];
     if (count < r->n_points || count > r->n_points + n_lost)
@@ -282,8 +258,6 @@ int run_lost(svh_recon* r, const std::vector<int32_t>& lost, size_t n_px, const 
 // uploads its frame record behind the records that are counted, so a failure only has to take the pose chains back.
 constexpr int32_t MAX_FEATURE_INDEX = 1 << 26;   // track_idx is an array of max_index entries in device memory
 
-hipError_t recon_wait(hipStream_t s) { return (hipError_t)wait_stream(s); }
-
 bool have_device() {
     int nd = 0;
     return hipGetDeviceCount(&nd) == hipSuccess && nd > 0;
@@ -305,7 +279,7 @@ int ensure_resident(svh_recon* r, int32_t n, int32_t tbl, bool host_matches) {
     // the staging pair h_in / d_in -- its CSR part carries the matches here, 48 n bytes = 8 bytes x 6 n "pixels"
     int rc = ensure(r, total_frames, total_frames - r->dev_frames, (size_t)r->n_tracks, host_matches ? 6 * (size_t)n : 0);
     if (rc) return rc;
-    if (!r->d_hdr) RECON_TRY(hipMalloc((void**)&r->d_hdr, 4 * RT_HDR + 16));
+    if (!r->d_hdr) RECON_TRY(malloc, hipMalloc((void**)&r->d_hdr, 4 * RT_HDR + 16));
     const int64_t need_tracks = (int64_t)r->n_tracks + n, need_px = (int64_t)r->total_px + 2 * (int64_t)n;
     if (need_tracks > INT32_MAX / 4 || need_px > INT32_MAX / 4)
         return svh::fail(SVH_ERR_BAD_ARG, "Reconstruction: the track table would exceed 2^29 entries");
@@ -349,8 +323,8 @@ int ensure_jobs(svh_recon* lead, int32_t K) {
     lead->cap_jobs = 0;
     (void)hipHostFree(lead->h_jobs); lead->h_jobs = nullptr;
     (void)hipFree(lead->d_jobs); lead->d_jobs = nullptr;
-    RECON_TRY(hipHostMalloc((void**)&lead->h_jobs, sizeof(ReconJob) * (size_t)cap));
-    RECON_TRY(hipMalloc((void**)&lead->d_jobs, sizeof(ReconJob) * (size_t)cap));
+    RECON_TRY(malloc, hipHostMalloc((void**)&lead->h_jobs, sizeof(ReconJob) * (size_t)cap));
+    RECON_TRY(malloc, hipMalloc((void**)&lead->d_jobs, sizeof(ReconJob) * (size_t)cap));
     lead->cap_jobs = cap;
     return SVH_OK;
 }
@@ -409,13 +383,13 @@ int resident_device(svh_recon* lead, int32_t K, bool timing) {
         max_up = std::max(max_up, std::max(j.up_bytes[0], j.up_bytes[1]));
     }
     if (timing) (void)hipEventRecord(lead->ev[0], lead->stream);
-    RECON_TRY(hipMemcpyAsync(lead->d_jobs, lead->h_jobs, sizeof(ReconJob) * (size_t)K, hipMemcpyHostToDevice,
+    RECON_TRY(copy, hipMemcpyAsync(lead->d_jobs, lead->h_jobs, sizeof(ReconJob) * (size_t)K, hipMemcpyHostToDevice,
                              lead->stream));
     rlaunch_resident(lead->stream, lead->d_jobs, K, max_n, max_old, max_tbl, max_up);
     if (timing) (void)hipEventRecord(lead->ev[1], lead->stream);
-    RECON_TRY(hipGetLastError());
-    RECON_TRY(recon_wait(lead->stream));
-    RECON_TRY(hipGetLastError());
+    RECON_TRY(launch, hipGetLastError());
+    RECON_TRY(wait, (hipError_t)wait_stream(lead->stream));
+    RECON_TRY(launch, hipGetLastError());
     return SVH_OK;
 }
 
@@ -727,9 +701,9 @@ int32_t svh_recon_get_points(svh_recon* r, float* xyz, int32_t cap) {
     if (!r) return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_get_points: null object");
     const int32_t n = std::min(r->n_points, cap);
     if (xyz && n > 0) {
-        RECON_TRY(hipSetDevice(r->device));
-        RECON_TRY(hipMemcpyAsync(xyz, r->d_points, 12 * (size_t)n, hipMemcpyDeviceToHost, r->stream));
-        RECON_TRY((hipError_t)wait_stream(r->stream));
+        RECON_TRY(none, hipSetDevice(r->device));
+        RECON_TRY(copy, hipMemcpyAsync(xyz, r->d_points, 12 * (size_t)n, hipMemcpyDeviceToHost, r->stream));
+        RECON_TRY(none, (hipError_t)wait_stream(r->stream));
     }
     return r->n_points;
 }

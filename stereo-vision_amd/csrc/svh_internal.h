@@ -31,23 +31,8 @@ Dims make_dims(const svh_elas_params& p, int32_t W, int32_t H);
 // (64 measured in round 5: 33.7 k pairs/s at 32, 48 and 64 pairs per launch -- the device is full at 32)
 constexpr int kMaxGroup = 32;
 
-// ---------------------------------------------------------------- fault injection (tests)
-// TEST HOOK, not part of the public C-ABI (include/svh.h does not declare it; tests bind it by name, the sanitizer
-// drivers pass their SVH_TEST_FAIL_AT on): svh_test_fail_at("<kind>:<n>[:<count>]") arms it, "" / NULL disarms; the
-// library itself never reads a specification from the environment.  The n-th (1-based) HIP call of that kind in this process, counted from the moment the specification is set, is
-// NOT issued and reports an error instead, and so do the count-1 calls of the kind after it (count 0: every one from the
-// n-th on).  Kinds, as the engines' error macros see their calls:
-//   malloc  hipMalloc / hipHostMalloc              copy  hipMemcpy*Async / hipMemset*Async
-//   launch  the hipGetLastError() after a phase's launches      wait  stream / event waits (and queries in sleep-polls)
-// fi_filter() is what HIP_TRY / VO_TRY / MAP_TRY put in front of the call; when nothing is armed it costs one relaxed
-// load.  Boundary behaviour under a failure (tests/test_faults_gpu.py): the entry returns SVH_ERR_HIP, svh_last_error()
-// names the call, one line goes to stderr, the lane / object is usable for the next call, nothing leaks.
-bool fi_armed();
-bool fi_hit(const char* expr_text);
-void report_hip_failure(const char* entry);   // "svhip: <entry>: <last error>" on stderr, once per failing call
-}   // namespace svh
-extern "C" int32_t svh_test_fail_at(const char* spec);
-namespace svh {
+// (the error text, the guard of a HIP call with its fault hook -- kinds are given at the call site, not matched from
+// the call's text -- and the buffer owner of the host engines: hip_guard.h)
 
 // Per-pair header, uploaded with the support points and triangle lists after
 // the host stage.  Triangles of all pairs and both sides are packed in one

@@ -9,35 +9,19 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <chrono>
 #include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/svh.h"
 #include "batch_rec.h"
+#include "hip_guard.h"
 #include "vo_internal.h"
 
 using namespace svh;
 
-namespace svh {
-int fail(int code, const std::string& msg);   // elas_engine.cpp: records svh_last_error()
-bool fi_armed();                                    // elas_engine.cpp: fault injection (svh_internal.h)
-bool fi_hit(const char* expr_text);
-void report_hip_failure(const char* entry);
-}
-
-static int vo_hip_failed(const char* expr, bool injected, hipError_t e) {
-    const int rc = svh::fail(SVH_ERR_HIP, std::string(expr) + ": " + (injected ? "injected failure (SVH_TEST_FAIL_AT)" : hipGetErrorString(e)));
-    svh::report_hip_failure("VisualOdometry");
-    return rc;
-}
-#define VO_TRY(expr)                                                                             \
-    do {                                                                                         \
-        const bool inj_ = svh::fi_armed() && svh::fi_hit(#expr);   /* svh_internal.h: fault injection */ \
-        hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                         \
-        if (e_ != hipSuccess) return vo_hip_failed(#expr, inj_, e_);                             \
-    } while (0)
+#define VO_TRY(kind, expr) SVH_HIP_TRY("VisualOdometry", kind, expr)
+#define VO_GROW(buf, bytes) SVH_HIP_GROW("VisualOdometry", buf, bytes)
 
 struct svh_vo {
     svh_vo_params p;
@@ -50,84 +34,38 @@ struct svh_vo {
     int device = 0;
     hipStream_t stream = nullptr;
     // pinned host staging: [matches | samples] in, VoResult + inlier list out
-    uint8_t* h_in = nullptr;
-    size_t h_in_cap = 0;
-    VoResult* h_out = nullptr;
-    int32_t* h_inl = nullptr;
-    int32_t inl_cap = 0;
+    PinnedBuf<uint8_t> h_in;
+    PinnedBuf<VoResult> h_out;
+    PinnedBuf<int32_t> h_inl;
     // device scratch
-    uint8_t* d_in = nullptr;
-    size_t d_in_cap = 0;
-    double* d_hyp_tr = nullptr;
-    int32_t* d_hyp_count = nullptr;
-    int32_t hyp_cap = 0;
-    uint8_t* d_flags = nullptr;
-    size_t flags_cap = 0;
-    double* d_J = nullptr;
-    double* d_res = nullptr;
-    int32_t j_cap = 0;
+    HipBuf<uint8_t> d_in, d_flags;
+    HipBuf<double> d_hyp_tr, d_J, d_res;
+    HipBuf<int32_t> d_hyp_count;
     svh::MonoVo* mono = nullptr;   // a VisualOdometryMono (svh_vo_mono_create): its estimate replaces the stereo one
 };
 
 namespace {
-
-template <typename T>
-hipError_t grow(T** p, size_t n) {
-    (void)hipFree(*p);
-    *p = nullptr;
-    return hipMalloc((void**)p, n * sizeof(T));
-}
 
 int ensure(svh_vo* v, int32_t N, int32_t iters) {
     if (!v->stream) {
         int nd = 0;
         if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
             return svh::fail(SVH_ERR_NO_DEVICE, "no HIP device visible: libsvhip has no CPU fallback");
-        VO_TRY(hipSetDevice(v->device));
-        VO_TRY(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
+        VO_TRY(none, hipSetDevice(v->device));
+        VO_TRY(none, hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
     }
-    VO_TRY(hipSetDevice(v->device));
-    if (!v->h_out) VO_TRY(hipHostMalloc((void**)&v->h_out, sizeof(VoResult)));   // (its own check: a failure here must not be hidden behind the stream's)
+    VO_TRY(none, hipSetDevice(v->device));
+    VO_GROW(v->h_out, sizeof(VoResult));
     const size_t in_bytes = (((size_t)N * sizeof(svh_p_match) + 15) & ~(size_t)15) +
                             (((size_t)iters * 3 * sizeof(int32_t) + 15) & ~(size_t)15);
-    // (every capacity goes to 0 BEFORE its buffer is freed and back up only when the new one exists: a failed
-    // allocation must not leave a freed pointer behind a capacity that says "fits" to a later, smaller request)
-    if (in_bytes > v->h_in_cap) {
-        v->h_in_cap = 0;
-        (void)hipHostFree(v->h_in);
-        v->h_in = nullptr;
-        VO_TRY(hipHostMalloc((void**)&v->h_in, in_bytes));
-        v->h_in_cap = in_bytes;
-    }
-    if (in_bytes > v->d_in_cap) {
-        v->d_in_cap = 0;
-        VO_TRY(grow(&v->d_in, in_bytes));
-        v->d_in_cap = in_bytes;
-    }
-    if (N > v->inl_cap) {
-        v->inl_cap = 0;
-        (void)hipHostFree(v->h_inl);
-        v->h_inl = nullptr;
-        VO_TRY(hipHostMalloc((void**)&v->h_inl, (size_t)N * sizeof(int32_t)));
-        v->inl_cap = N;
-    }
-    if (iters > v->hyp_cap) {
-        v->hyp_cap = 0;
-        VO_TRY(grow(&v->d_hyp_tr, (size_t)6 * iters));
-        VO_TRY(grow(&v->d_hyp_count, (size_t)iters));
-        v->hyp_cap = iters;
-    }
-    if ((size_t)iters * N > v->flags_cap) {
-        v->flags_cap = 0;
-        VO_TRY(grow(&v->d_flags, (size_t)iters * N));
-        v->flags_cap = (size_t)iters * N;
-    }
-    if (N > v->j_cap) {
-        v->j_cap = 0;
-        VO_TRY(grow(&v->d_J, (size_t)24 * N));
-        VO_TRY(grow(&v->d_res, (size_t)4 * N));
-        v->j_cap = N;
-    }
+    VO_GROW(v->h_in, in_bytes);
+    VO_GROW(v->d_in, in_bytes);
+    VO_GROW(v->h_inl, (size_t)N * sizeof(int32_t));
+    VO_GROW(v->d_hyp_tr, (size_t)6 * iters * sizeof(double));
+    VO_GROW(v->d_hyp_count, (size_t)iters * sizeof(int32_t));
+    VO_GROW(v->d_flags, (size_t)iters * N);
+    VO_GROW(v->d_J, (size_t)24 * N * sizeof(double));
+    VO_GROW(v->d_res, (size_t)4 * N * sizeof(double));
     return SVH_OK;
 }
 
@@ -191,14 +129,14 @@ void estimate_enqueue(svh_vo* v, int32_t N) {
     c.f = P.f; c.cu = P.cu; c.cv = P.cv; c.base = P.base;
     c.inlier_threshold = P.inlier_threshold;
     c.reweighting = P.reweighting;
-    vlaunch_estimate(s, reinterpret_cast<const svh_p_match*>(v->d_in), N,
+    vlaunch_estimate(s, reinterpret_cast<const svh_p_match*>(v->d_in.p), N,
                      reinterpret_cast<const int32_t*>(v->d_in + m_bytes), iters, c, v->d_hyp_tr,
                      v->d_hyp_count, v->d_flags, v->d_J, v->d_res, v->h_out, v->h_inl);
 }
 
 int estimate_collect(svh_vo* v, double* tr6) {
     const VoResult& r = *v->h_out;
-    v->inliers.assign(v->h_inl, v->h_inl + r.n_inliers);
+    v->inliers.assign(v->h_inl.p, v->h_inl.p + r.n_inliers);
     if (!r.success) return 0;
     for (int i = 0; i < 6; i++) tr6[i] = r.tr[i];
     return 1;
@@ -210,8 +148,8 @@ int estimate(svh_vo* v, const svh_p_match* pm, int32_t N, double* tr6) {
     const int rc = estimate_prepare(v, pm, N);
     if (rc <= 0) return rc;
     estimate_enqueue(v, N);
-    VO_TRY((hipError_t)wait_stream(v->stream));
-    VO_TRY(hipGetLastError());
+    VO_TRY(none, (hipError_t)wait_stream(v->stream));
+    VO_TRY(launch, hipGetLastError());
     return estimate_collect(v, tr6);
 }
 
@@ -287,16 +225,13 @@ svh_vo* svh_vo_create(const svh_vo_params* p) {
 void svh_vo_destroy(svh_vo* v) {
     if (!v) return;
     mono_destroy(v->mono);
+    svh_matcher_destroy(v->matcher);
     if (v->stream) {
         (void)hipSetDevice(v->device);
         (void)hipStreamSynchronize(v->stream);
-        (void)hipFree(v->d_in); (void)hipFree(v->d_hyp_tr); (void)hipFree(v->d_hyp_count);
-        (void)hipFree(v->d_flags); (void)hipFree(v->d_J); (void)hipFree(v->d_res);
-        (void)hipHostFree(v->h_in); (void)hipHostFree(v->h_out); (void)hipHostFree(v->h_inl);
         (void)hipStreamDestroy(v->stream);
     }
-    svh_matcher_destroy(v->matcher);
-    delete v;
+    delete v;   // (its buffers free themselves, on the device selected above)
 }
 
 // VisualOdometryStereo::process after its pushBack   viso_stereo.cpp:47-68
@@ -382,9 +317,8 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
         }
     };
     static Acc acc;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tt[5] = {0, 0, 0, 0, 0};
-    if (timing) tt[0] = now();
+    if (timing) tt[0] = now_ms();
     const svh_vo_params& P = vs[0]->p;
     std::vector<const double*> trs(K);
     for (int i = 0; i < K; i++) trs[i] = vs[i]->Tr;
@@ -394,10 +328,10 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
         rc = svh_matcher_prefetch_batch(ms.data(), K, N1, N2, dims);
         if (rc < 0) return rc;
     }
-    if (timing) tt[1] = now();
+    if (timing) tt[1] = now_ms();
     rc = svh_matcher_match_features_batch(ms.data(), K, 2, trs.data());
     if (rc < 0) return rc;
-    if (timing) tt[2] = now();
+    if (timing) tt[2] = now_ms();
     std::vector<int> state(K, 0);
     auto select = [&](int i) {
         svh_vo* v = vs[i];
@@ -418,7 +352,7 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
     }
     for (int i = 0; i < K; i++)
         if (state[i] < 0) return state[i];
-    if (timing) tt[3] = now();
+    if (timing) tt[3] = now_ms();
     BatchRec& rec = batch_recorder(vs[0]->device);
     rec.reset();
     t_rec = &rec;
@@ -433,15 +367,15 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
         for (int i = 0; i < K; i++)
             if (state[i] > 0) {
                 estimate_enqueue(vs[i], (int32_t)vs[i]->matched.size());
-                VO_TRY((hipError_t)wait_stream(vs[i]->stream));
+                VO_TRY(none, (hipError_t)wait_stream(vs[i]->stream));
             }
     } else {
         hipStream_t s = vs[0]->stream;
-        VO_TRY(rec.flush(s));
-        VO_TRY((hipError_t)wait_stream(s));
+        VO_TRY(copy, rec.flush(s));
+        VO_TRY(none, (hipError_t)wait_stream(s));
         rec.synced();
     }
-    VO_TRY(hipGetLastError());
+    VO_TRY(launch, hipGetLastError());
     for (int i = 0; i < K; i++) {
         int32_t r = 0;
         if (state[i] > 0) {
@@ -456,7 +390,7 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
         good += r > 0;
     }
     if (timing) {
-        tt[4] = now();
+        tt[4] = now_ms();
         for (int i = 0; i < 4; i++) acc.t[i] += tt[i + 1] - tt[i];
         acc.calls++;
     }

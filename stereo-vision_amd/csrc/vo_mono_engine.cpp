@@ -24,37 +24,14 @@
 
 #include "../../include/svh.h"
 #include "batch_rec.h"
+#include "hip_guard.h"
 #include "mono_core.h"
 #include "vo_internal.h"
 
 namespace svh {
-int fail(int code, const std::string& msg);   // elas_engine.cpp: records svh_last_error()
-bool fi_armed();                              // elas_engine.cpp: fault injection (svh_internal.h)
-bool fi_hit(const char* expr_text);
-void report_hip_failure(const char* entry);
 
-namespace {
-
-int mono_hip_failed(const char* expr, bool injected, hipError_t e) {
-    const int rc = svh::fail(SVH_ERR_HIP, std::string(expr) + ": " +
-                                              (injected ? "injected failure (SVH_TEST_FAIL_AT)" : hipGetErrorString(e)));
-    svh::report_hip_failure("VisualOdometryMono");
-    return rc;
-}
-#define MONO_TRY(expr)                                                                                  \
-    do {                                                                                                \
-        const bool inj_ = svh::fi_armed() && svh::fi_hit(#expr); /* svh_internal.h: fault injection */  \
-        hipError_t e_ = inj_ ? hipErrorUnknown : (expr);                                                \
-        if (e_ != hipSuccess) return mono_hip_failed(#expr, inj_, e_);                                  \
-    } while (0)
-// (named so that the fault hook files them under "wait" and "copy": a lockstep phase's one copy is the recorder's
-// upload of its job tables, hipMemcpyAsync inside BatchRec::flush, which then issues the phase's launches)
-hipError_t stream_wait(hipStream_t s) { return (hipError_t)wait_stream(s); }
-hipError_t hipMemcpyAsync_jobs_and_launch(BatchRec& rec, hipStream_t s) { return rec.flush(s); }
-
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-}  // namespace
+#define MONO_TRY(kind, expr) SVH_HIP_TRY("VisualOdometryMono", kind, expr)
+#define MONO_GROW(buf, bytes) SVH_HIP_GROW("VisualOdometryMono", buf, bytes)
 
 struct MonoVo {
     svh_vo_mono_params p;
@@ -64,24 +41,19 @@ struct MonoVo {
     bool timing = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms[3] = {0, 0, 0};     // device time of the three phases of the last estimate (timing on)
-    // pinned host memory
-    uint8_t* h_in = nullptr;      // [normalised matches 16N | matches 16N | samples 32 iters] -> d_in
-    int32_t* h_sel = nullptr;     // {winner, its count} (2) | {candidate, 4 counts} (at +4)
-    uint8_t* h_flags = nullptr;   // N
-    int32_t* h_counts = nullptr;  // iters
-    double* h_cams = nullptr;     // 60 -> d_cams
-    double* h_X = nullptr;        // 4 N
-    double* h_d = nullptr;        // n -> d_d
-    double* h_sums = nullptr;     // n
+    // pinned host memory (every buffer carries 16 bytes of slack: the upload kernel moves whole 16-byte words)
+    PinnedBuf<uint8_t> h_in;      // [normalised matches 16N | matches 16N | samples 32 iters] -> d_in
+    PinnedBuf<int32_t> h_sel;     // {winner, its count} (2) | {candidate, 4 counts} (at +4)
+    PinnedBuf<uint8_t> h_flags;   // N
+    PinnedBuf<int32_t> h_counts;  // iters
+    PinnedBuf<double> h_cams;     // 60 -> d_cams
+    PinnedBuf<double> h_X;        // 4 N
+    PinnedBuf<double> h_d;        // n -> d_d
+    PinnedBuf<double> h_sums;     // n
     // device memory
-    uint8_t* d_in = nullptr;
-    double* d_F = nullptr;
-    int32_t* d_counts = nullptr;
-    double* d_cams = nullptr;
-    double* d_X = nullptr;
-    uint8_t* d_front = nullptr;
-    double* d_d = nullptr;
-    int32_t cap_n = 0, cap_it = -1;
+    HipBuf<uint8_t> d_in, d_front;
+    HipBuf<double> d_F, d_cams, d_X, d_d;
+    HipBuf<int32_t> d_counts;
     // the estimate in flight, from mono_prepare to the last mono_after
     int32_t N = 0, iters = 0, n = 0;
     std::vector<float> q;         // normalised matches, 4 N
@@ -93,48 +65,33 @@ struct MonoVo {
 
 namespace {
 
-template <typename T>
-hipError_t dev_grow(T** p, size_t n) {
-    (void)hipFree(*p);
-    *p = nullptr;
-    return hipMalloc((void**)p, n * sizeof(T) + 16);
-}
-template <typename T>
-hipError_t host_grow(T** p, size_t n) {
-    (void)hipHostFree(*p);
-    *p = nullptr;
-    return hipHostMalloc((void**)p, n * sizeof(T) + 16);
-}
+// room for `n` elements and the slack
+template <typename T, bool Pinned>
+size_t padded(const HipBuf<T, Pinned>&, size_t n) { return n * sizeof(T) + 16; }
+#define MONO_ROOM(buf, n) MONO_GROW(buf, padded(buf, n))
 
+// every item is checked on its own: a call that failed half way leaves nothing the next call would trust
 int ensure(MonoVo* M, int32_t N, int32_t iters) {
-    MONO_TRY(hipSetDevice(M->device));
-    if (!M->stream) {
-        MONO_TRY(hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
-        MONO_TRY(host_grow(&M->h_sel, 16));
-        MONO_TRY(host_grow(&M->h_cams, 60));
-        MONO_TRY(dev_grow(&M->d_cams, 60));
-        for (int i = 0; i < 2; i++) MONO_TRY(hipEventCreate(&M->ev[i]));
-    }
-    if (N > M->cap_n || iters > M->cap_it) {
-        // (capacities go to 0 before anything is freed and back up only when every buffer exists)
-        const int32_t n = std::max(N, M->cap_n), it = std::max(iters, std::max(M->cap_it, 0));
-        M->cap_n = 0;
-        M->cap_it = -1;
-        MONO_TRY(host_grow(&M->h_in, 32 * (size_t)n + 32 * (size_t)it));
-        MONO_TRY(dev_grow(&M->d_in, 32 * (size_t)n + 32 * (size_t)it));
-        MONO_TRY(host_grow(&M->h_flags, (size_t)n));
-        MONO_TRY(host_grow(&M->h_counts, (size_t)it));
-        MONO_TRY(host_grow(&M->h_X, 4 * (size_t)n));
-        MONO_TRY(host_grow(&M->h_d, (size_t)n));
-        MONO_TRY(host_grow(&M->h_sums, (size_t)n));
-        MONO_TRY(dev_grow(&M->d_F, 9 * (size_t)it));
-        MONO_TRY(dev_grow(&M->d_counts, (size_t)it));
-        MONO_TRY(dev_grow(&M->d_X, 16 * (size_t)n));
-        MONO_TRY(dev_grow(&M->d_front, 4 * (size_t)n));
-        MONO_TRY(dev_grow(&M->d_d, (size_t)n));
-        M->cap_n = n;
-        M->cap_it = it;
-    }
+    MONO_TRY(none, hipSetDevice(M->device));
+    if (!M->stream) MONO_TRY(none, hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking));
+    MONO_ROOM(M->h_sel, 16);
+    MONO_ROOM(M->h_cams, 60);
+    MONO_ROOM(M->d_cams, 60);
+    for (int i = 0; i < 2; i++)
+        if (!M->ev[i]) MONO_TRY(none, hipEventCreate(&M->ev[i]));
+    const size_t n = (size_t)N, it = (size_t)iters;
+    MONO_ROOM(M->h_in, 32 * n + 32 * it);
+    MONO_ROOM(M->d_in, 32 * n + 32 * it);
+    MONO_ROOM(M->h_flags, n);
+    MONO_ROOM(M->h_counts, it);
+    MONO_ROOM(M->h_X, 4 * n);
+    MONO_ROOM(M->h_d, n);
+    MONO_ROOM(M->h_sums, n);
+    MONO_ROOM(M->d_F, 9 * it);
+    MONO_ROOM(M->d_counts, it);
+    MONO_ROOM(M->d_X, 16 * n);
+    MONO_ROOM(M->d_front, 4 * n);
+    MONO_ROOM(M->d_d, n);
     return SVH_OK;
 }
 
@@ -144,8 +101,8 @@ void mark(MonoVo* M, int i) {
 
 // the stream wait that ends device phase `phase` (its events: ev[0] before, ev[1] after)
 int wait(MonoVo* M, int phase) {
-    MONO_TRY(stream_wait(M->stream));
-    MONO_TRY(hipGetLastError());
+    MONO_TRY(wait, (hipError_t)wait_stream(M->stream));
+    MONO_TRY(launch, hipGetLastError());
     if (M->timing) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, M->ev[0], M->ev[1]) == hipSuccess) M->ms[phase] = ms;
@@ -203,15 +160,11 @@ void mono_destroy(MonoVo* M) {
     if (M->stream) {
         (void)hipSetDevice(M->device);
         (void)hipStreamSynchronize(M->stream);
-        for (int i = 0; i < 2; i++) (void)hipEventDestroy(M->ev[i]);
-        (void)hipHostFree(M->h_in); (void)hipHostFree(M->h_sel); (void)hipHostFree(M->h_flags);
-        (void)hipHostFree(M->h_counts); (void)hipHostFree(M->h_cams); (void)hipHostFree(M->h_X);
-        (void)hipHostFree(M->h_d); (void)hipHostFree(M->h_sums);
-        (void)hipFree(M->d_in); (void)hipFree(M->d_F); (void)hipFree(M->d_counts); (void)hipFree(M->d_cams);
-        (void)hipFree(M->d_X); (void)hipFree(M->d_front); (void)hipFree(M->d_d);
+        for (int i = 0; i < 2; i++)
+            if (M->ev[i]) (void)hipEventDestroy(M->ev[i]);
         (void)hipStreamDestroy(M->stream);
     }
-    delete M;
+    delete M;   // (its buffers free themselves, on the device selected above)
 }
 
 bool mono_same_params(const MonoVo* a, const MonoVo* b) {
@@ -291,18 +244,18 @@ int mono_prepare(MonoVo* M, const svh_p_match* pm, int32_t N, RandStream& rng, s
 void mono_enqueue(MonoVo* M, int phase) {
     const svh_vo_mono_params& P = M->p;
     const int32_t N = M->N, iters = M->iters;
-    const float* d_q = reinterpret_cast<const float*>(M->d_in);
+    const float* d_q = reinterpret_cast<const float*>(M->d_in.p);
     const float* d_m = reinterpret_cast<const float*>(M->d_in + 16 * (size_t)N);
     if (phase == 0) {
         vlaunch_upload(M->stream, M->h_in, M->d_in, 32 * (size_t)N + up16(32 * (size_t)iters));
         mlaunch_ransac(M->stream, d_q, N, reinterpret_cast<const int32_t*>(M->d_in + 32 * (size_t)N), iters,
                        P.inlier_threshold, M->d_F, M->d_counts, M->h_sel, M->h_flags, M->h_counts);
     } else if (phase == 1) {
-        vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_cams), reinterpret_cast<uint8_t*>(M->d_cams),
+        vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_cams.p), reinterpret_cast<uint8_t*>(M->d_cams.p),
                        60 * sizeof(double));
         mlaunch_chiral(M->stream, d_m, N, M->d_cams, M->d_X, M->d_front, M->h_X, M->h_sel + 4);
     } else {
-        vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_d), reinterpret_cast<uint8_t*>(M->d_d),
+        vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_d.p), reinterpret_cast<uint8_t*>(M->d_d.p),
                        up16(8 * (size_t)M->n));
         mlaunch_plane(M->stream, M->d_d, M->n, M->weight, M->thr, M->h_sums);
     }
@@ -316,7 +269,7 @@ int after_ransac(MonoVo* M, std::vector<int32_t>& inliers) {
     const int32_t N = M->N;
     const std::vector<float>& q = M->q;
     const double* T = M->T;
-    M->votes.assign(M->h_counts, M->h_counts + M->iters);
+    M->votes.assign(M->h_counts.p, M->h_counts.p + M->iters);
     for (int32_t i = 0; i < N; i++)
         if (M->h_flags[i]) inliers.push_back(i);
     if (inliers.size() < 10) return 0;   // :73-74
@@ -486,7 +439,7 @@ int mono_run_batch(MonoVo* const* Ms, int32_t K, int* state, std::vector<int32_t
         if (state[i] > 0) live.push_back(i);
     if (live.empty()) return SVH_OK;
     MonoVo* M0 = Ms[live[0]];
-    MONO_TRY(hipSetDevice(M0->device));
+    MONO_TRY(none, hipSetDevice(M0->device));
     BatchRec& rec = batch_recorder(M0->device);
     hipStream_t s = M0->stream;
     // whatever way a phase fails: nothing stays in flight, the recorder is free again
@@ -526,11 +479,11 @@ int mono_run_batch(MonoVo* const* Ms, int32_t K, int* state, std::vector<int32_t
             }
         } else {
             if (timing) (void)hipEventRecord(M0->ev[0], s);
-            MONO_TRY(hipMemcpyAsync_jobs_and_launch(rec, s));
+            MONO_TRY(copy, rec.flush(s));   // (its one copy is the upload of the job tables)
             if (timing) (void)hipEventRecord(M0->ev[1], s);
-            MONO_TRY(stream_wait(s));
+            MONO_TRY(wait, (hipError_t)wait_stream(s));
             rec.synced();
-            MONO_TRY(hipGetLastError());
+            MONO_TRY(launch, hipGetLastError());
             float ms = 0;
             if (timing && hipEventElapsedTime(&ms, M0->ev[0], M0->ev[1]) == hipSuccess)
                 for (int i : live) Ms[i]->ms[phase] = ms;   // the phase's time for the whole batch

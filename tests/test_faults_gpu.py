@@ -452,6 +452,79 @@ def test_vo_lockstep_pipelined_loop(svhip, kind):
         assert rc >= K // 2, (kind, n, rc, ok)
 
 
+# ---------------------------------------------------------------- fresh objects: the first allocations of an object
+def expect_injected(svhip, capfd, call):
+    """call() fails with SVH_ERR_HIP (raised, or returned by the plain ctypes drivers), the message names an injected
+    failure, one line went to stderr"""
+    capfd.readouterr()
+    try:
+        rc = call()
+    except svhip.SvhError as err:
+        rc = err.code
+    assert rc == svhip.ERR_HIP, rc
+    assert "injected failure" in svhip.last_error(), svhip.last_error()
+    assert capfd.readouterr().err.count("svhip:") == 1
+
+
+def test_fresh_matcher_first_allocation(svhip, capfd):
+    """malloc:1 before the first pushBack of a new Matcher: the call fails, the same object then gives what a clean
+    one gives"""
+    prm = H.matcher_defaults()
+    im = quad()
+    clean = plain_matcher(prm)
+    clean.push_back(im[0], im[1])
+    clean.push_back(im[2], im[3])
+    clean.match(2)
+    want = clean.matches().copy()
+    m = plain_matcher(prm)
+    arm(svhip, "malloc:1")
+    expect_injected(svhip, capfd, lambda: m.push_back(im[0], im[1]))
+    arm(svhip, "")
+    m.push_back(im[0], im[1])
+    m.push_back(im[2], im[3])
+    m.match(2)
+    got = m.matches()
+    assert len(got) == len(want) and (got == want).all()
+
+
+def test_fresh_stereo_vo_first_allocation(svhip, capfd):
+    """malloc:1 before the first process of a new VisualOdometryStereo"""
+    im = quad()
+
+    def run(vo):
+        r = [vo.process(im[0], im[1]), vo.process(im[2], im[3])]
+        return r, vo.matches().tobytes(), vo.inliers().tolist(), vo.motion()
+
+    want = run(H.ProductVo(H.vo_defaults(), private_rand=0))
+    vo = H.ProductVo(H.vo_defaults(), private_rand=0)
+    arm(svhip, "malloc:1")
+    expect_injected(svhip, capfd, lambda: vo.process(im[0], im[1]))
+    arm(svhip, "")
+    got = run(vo)
+    assert got[:3] == want[:3] and (got[3] == want[3]).all()
+
+
+@pytest.mark.parametrize("n", [1, 2, 3])
+def test_fresh_mono_vo_first_allocations(svhip, capfd, n):
+    """malloc:1..3 before the first estimate of a new VisualOdometryMono: the second and third fail inside the
+    first-call block, after the stream exists; the next call must not trust anything of the failed one"""
+    import mono_ref as R
+    import test_vo_mono_gpu as T
+    with np.load(R.GOLDEN) as z:
+        prm, matches = T.params(svhip, z["est_syn2000_params"]), z["est_syn2000_matches"]
+
+    def run(vo):
+        return bool(vo.process_matches(matches)), vo.votes().tolist(), vo.inliers().tolist(), vo.motion()
+
+    want = run(svhip.VoMono(prm, private_rand=0))
+    vo = svhip.VoMono(prm, private_rand=0)
+    arm(svhip, "malloc:%d" % n)
+    expect_injected(svhip, capfd, lambda: vo.process_matches(matches))
+    arm(svhip, "")
+    got = run(vo)
+    assert got[:3] == want[:3] and (got[3] == want[3]).all()
+
+
 if __name__ == "__main__":
     import json
     import sys

@@ -120,7 +120,7 @@ void launch_segments_label(const LaunchCtx&, const svh_elas_params&, const Dims&
                            const DevMaps&, const PostScratch&) {}
 }  // namespace svh
 
-extern "C" int32_t svh_test_fail_at(const char* spec);   // test hook of the engines (csrc/svh_internal.h)
+extern "C" int32_t svh_test_fail_at(const char* spec);   // test hook of the engines (csrc/hip_guard.h)
 // ---------------------------------------------------------------- driver
 int main(int argc, char** argv) {
     const int rounds = argc > 1 ? atoi(argv[1]) : 12;

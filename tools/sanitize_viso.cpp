@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../include/svh_plane.h"
+#include "../stereo-vision_amd/csrc/hip_guard.h"
 #include "../stereo-vision_amd/csrc/matcher_internal.h"
 #include "../stereo-vision_amd/csrc/plane_internal.h"
 #include "../stereo-vision_amd/csrc/recon_internal.h"
@@ -77,19 +78,14 @@ hipError_t hipStreamQuery(hipStream_t s) {
 }
 
 namespace svh {
-static thread_local std::string t_err;
-int fail(int code, const std::string& msg) { t_err = msg; return code; }
 // fault injection under the sanitizers: SVH_SAN_FAIL_EVERY=n makes every n-th HIP call the engines check fail
 // (any kind), so that their error paths -- early returns out of recording passes, helper-pool phases, the prefetch
-// hand-over -- run under TSan / ASan with 16 threads around them
+// hand-over -- run under TSan / ASan with 16 threads around them.  This program's own policy behind the shared
+// declarations of hip_guard.h (the library's own hook, svh_fault_hook.cpp, is not linked)
 static const long g_fi_every = getenv("SVH_SAN_FAIL_EVERY") ? atol(getenv("SVH_SAN_FAIL_EVERY")) : 0;
 static std::atomic<long> g_fi_n{0};
 bool fi_armed() { return g_fi_every > 0; }
-bool fi_hit(const char*) { return g_fi_every > 0 && (g_fi_n.fetch_add(1) + 1) % g_fi_every == 0; }
-void report_hip_failure(const char*) {}
-}  // namespace svh
-extern "C" const char* svh_last_error(void) { return svh::t_err.c_str(); }
-namespace svh {
+bool fi_hit(FiKind) { return g_fi_every > 0 && (g_fi_n.fetch_add(1) + 1) % g_fi_every == 0; }
 
 // ---------------------------------------------------------------- stub launchers
 static uint32_t mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16; return x; }
@@ -308,6 +304,8 @@ int main(int argc, char** argv) {
     const int K = argc > 1 ? atoi(argv[1]) : 16, frames = argc > 2 ? atoi(argv[2]) : 12;
     const int W = 640, H = 200;
     std::atomic<int> bad{0};
+    // a check of this driver that did not hold: counted, and named on stderr by its line
+#define BAD() (fprintf(stderr, "sanitize_viso: check at line %d failed\n", __LINE__), bad++)
     std::atomic<long> matches{0}, injected{0};
     const bool inject = svh::fi_armed();
     // a negative return is a failure of the run -- unless failures are being injected: then it must be SVH_ERR_HIP
@@ -315,14 +313,53 @@ int main(int argc, char** argv) {
     auto check = [&](int32_t rc) {
         if (rc >= 0) return;
         if (inject && (rc == SVH_ERR_HIP || rc == SVH_ERR_BAD_ARG)) injected++;
-        else bad++;
+        else BAD();
     };
+    // Every 1st, 2nd or 3rd call fails: first, on this thread alone (the failing calls are then the same in every run), a
+    // fresh Matcher, a fresh stereo object and a fresh mono object, each driven eight times -- their first allocations
+    // fail one after the other, the mono engine's first-call block (stream, then three buffers) among them, and the
+    // calls after a failed one must not trust what it left behind
+    if (inject && svh::g_fi_every <= 3) {
+        std::vector<uint8_t> I((size_t)W * H);
+        for (size_t i = 0; i < I.size(); i++) I[i] = (uint8_t)(svh::mix((uint32_t)i) >> 24);
+        const int32_t dims[3] = {W, H, W};
+        svh_matcher_params mp;
+        svh_matcher_params_default(&mp);
+        svh_matcher* m = svh_matcher_create(&mp);
+        svh_vo_params sp;
+        svh_vo_params_default(&sp);
+        sp.f = 645.2; sp.cu = 320.0; sp.cv = 100.0; sp.base = 0.57;
+        svh_vo* st = svh_vo_create(&sp);
+        svh_vo_mono_params op;
+        svh_vo_mono_params_default(&op);
+        op.f = 645.2; op.cu = 320.0; op.cv = 100.0; op.height = 1.6; op.pitch = -0.08;
+        op.ransac_iters = 50;
+        op.motion_threshold = 1e6;
+        svh_vo* mono = svh_vo_mono_create(&op);
+        if (!m || !st || !mono) BAD();
+        std::vector<svh_p_match> pm(40);
+        for (int k = 0; k < 40; k++) {
+            memset(&pm[k], 0, sizeof(pm[k]));
+            pm[k].u1p = (float)(svh::mix((uint32_t)k) % 600u); pm[k].v1p = (float)(svh::mix((uint32_t)(3 * k)) % 180u);
+            pm[k].u1c = pm[k].u1p + 2.f + (float)(k % 3); pm[k].v1c = pm[k].v1p + 1.f;
+        }
+        for (int r = 0; r < 8 && m && st && mono; r++) {
+            check(svh_matcher_push_back(m, I.data(), I.data(), dims, 0));
+            check(svh_matcher_match_features(m, 2, nullptr));
+            check(svh_vo_process(st, I.data(), I.data(), dims, 0));
+            check(svh_vo_process_matches(mono, pm.data(), 40));
+            check(svh_vo_mono_process(mono, I.data(), dims, 0));
+        }
+        svh_matcher_destroy(m);
+        svh_vo_destroy(st);
+        svh_vo_destroy(mono);
+    }
     auto sequence = [&](int id) {
         svh_vo_params p;
         svh_vo_params_default(&p);
         p.f = 645.2; p.cu = 320.0; p.cv = 100.0; p.base = 0.57;
         svh_vo* vo = svh_vo_create(&p);
-        if (!vo) { bad++; return; }
+        if (!vo) { BAD(); return; }
         std::vector<uint8_t> I1((size_t)W * H), I2((size_t)W * H);
         const int32_t dims[3] = {W, H, W};
         for (int f = 0; f < frames; f++) {
@@ -403,11 +440,11 @@ int main(int argc, char** argv) {
     // two Reconstruction objects on threads of their own: tracks that live one to five frames, an empty update
     auto reconstruct = [&](int id) {
         svh_recon* r = svh_recon_create();
-        if (!r) { bad++; return; }
+        if (!r) { BAD(); return; }
         const double Tr[16] = {1, 0, 0, 0.05, 0, 1, 0, 0, 0, 0, 1, -0.8, 0, 0, 0, 1};
-        if (svh_recon_update(r, nullptr, 0, Tr, 1, 2, 30, 2) != SVH_ERR_BAD_ARG) bad++;   // not calibrated yet
+        if (svh_recon_update(r, nullptr, 0, Tr, 1, 2, 30, 2) != SVH_ERR_BAD_ARG) BAD();   // not calibrated yet
         check(svh_recon_set_calibration(r, 645.2, 635.9, 194.1));
-        if (svh_recon_set_calibration(r, 645.2, 635.9, 194.1) != SVH_ERR_BAD_ARG) bad++;
+        if (svh_recon_set_calibration(r, 645.2, 635.9, 194.1) != SVH_ERR_BAD_ARG) BAD();
         const int n = 600;
         for (int f = 0; f < 3 * frames; f++) {
             std::vector<svh_p_match> m;
@@ -447,10 +484,11 @@ int main(int argc, char** argv) {
         const double Tr[16] = {1, 0, 0, 0.05, 0, 1, 0, 0, 0, 0, 1, -0.8, 0, 0, 0, 1};
         svh_recon* r = svh_recon_create_resident();
         svh_recon* h = svh_recon_create();
-        if (!r || !h) { bad++; return; }
-        if (svh_recon_update(r, nullptr, 0, Tr, 1, 2, 30, 2) != SVH_ERR_BAD_ARG) bad++;   // not calibrated yet
+        if (!r || !h) { BAD(); return; }
+        if (svh_recon_update(r, nullptr, 0, Tr, 1, 2, 30, 2) != SVH_ERR_BAD_ARG) BAD();   // not calibrated yet
         check(svh_recon_set_calibration(r, 645.2, 635.9, 194.1));
         check(svh_recon_set_calibration(h, 645.2, 635.9, 194.1));
+        bool in_step = true;
         for (int f = 0; f < 3 * frames; f++) {
             const std::vector<svh_p_match> m = recon_matches(f, id, 600);
             int32_t a, b;
@@ -459,9 +497,13 @@ int main(int argc, char** argv) {
             for (int k = 0; k < 50 && (b = svh_recon_update(h, m.data(), (int32_t)m.size(), Tr, 1, 2, 30, 2)) == SVH_ERR_HIP; k++) {}
             check(a);
             check(b);
-            if (a == SVH_OK && b == SVH_OK &&
+            // (fifty failures in a row happen when every n-th call fails for a small n and this thread is the only one
+            // left counting: each attempt then fails at the same call.  One object missed an update the other took:
+            // their counts are no longer comparable)
+            if (a < 0 || b < 0) in_step = false;
+            if (in_step && a == SVH_OK && b == SVH_OK &&
                 (svh_recon_num_tracks(r) != svh_recon_num_tracks(h) || svh_recon_num_points(r) != svh_recon_num_points(h)))
-                bad++;
+                BAD();
             std::vector<float> p(3 * (size_t)svh_recon_num_points(r) + 3);
             check(svh_recon_get_points(r, p.data(), svh_recon_num_points(r)));
             matches += svh_recon_num_tracks(r);
@@ -478,7 +520,7 @@ int main(int argc, char** argv) {
         }
         svh_recon* rs[3] = {svh_recon_create_resident(), svh_recon_create_resident(), svh_recon_create_resident()};
         svh_recon* h = svh_recon_create();
-        if (!rs[0] || !rs[1] || !rs[2] || !h) { bad++; return; }
+        if (!rs[0] || !rs[1] || !rs[2] || !h) { BAD(); return; }
         for (svh_recon* r : rs) check(svh_recon_set_calibration(r, 645.2, 635.9, 194.1));
         check(svh_recon_set_calibration(h, 645.2, 635.9, 194.1));
         for (int f = 0; f < 3 * frames; f++) {
@@ -492,9 +534,9 @@ int main(int argc, char** argv) {
             const int32_t before = svh_recon_num_tracks(rs[1]);
             const int32_t rc = svh_recon_update_batch(rs, mp, n, Tr, 3, 1, 2, 30, 2, st);
             check(rc);
-            if (rc == SVH_OK && f % 4 == 3 && svh_recon_num_tracks(rs[1]) != before) bad++;
+            if (rc == SVH_OK && f % 4 == 3 && svh_recon_num_tracks(rs[1]) != before) BAD();
             svh_recon* mixed[2] = {rs[0], h};
-            if (svh_recon_update_batch(mixed, mp, n, Tr, 2, 1, 2, 30, 2, st) != SVH_ERR_BAD_ARG) bad++;
+            if (svh_recon_update_batch(mixed, mp, n, Tr, 2, 1, 2, 30, 2, st) != SVH_ERR_BAD_ARG) BAD();
             matches += svh_recon_num_tracks(rs[2]);
         }
         for (svh_recon* r : rs) svh_recon_destroy(r);
@@ -514,14 +556,14 @@ int main(int argc, char** argv) {
         svh_plane_params_default(&prm);
         prm.num_samples = 200;
         svh_plane* p[3] = {svh_plane_create(&prm), svh_plane_create(&prm), svh_plane_create(&prm)};
-        if (!p[0] || !p[1] || !p[2]) { bad++; return; }
-        if (svh_plane_estimate(p[0], D.data(), 0, w, h, w - 1, 700, 160, 60, 0.5f, 1) != SVH_ERR_BAD_ARG) bad++;
+        if (!p[0] || !p[1] || !p[2]) { BAD(); return; }
+        if (svh_plane_estimate(p[0], D.data(), 0, w, h, w - 1, 700, 160, 60, 0.5f, 1) != SVH_ERR_BAD_ARG) BAD();
         for (int f = 0; f < frames; f++) {
             const int32_t rc = svh_plane_estimate(p[0], D.data(), 0, w, h, w, 700, 160, 60, 0.5f, (uint32_t)(f / 2 + id));
             check(rc);
             double abc[3];
             svh_plane_get_plane_dsi(p[0], abc);
-            if (rc == SVH_OK && !(abc[1] > 0.2 && abc[1] < 0.4)) bad++;
+            if (rc == SVH_OK && !(abc[1] > 0.2 && abc[1] < 0.4)) BAD();
             const float* maps[3] = {D.data(), D.data(), D.data()};
             const uint32_t seeds[3] = {1, 2, (uint32_t)f};
             int32_t st[3];
@@ -544,7 +586,7 @@ int main(int argc, char** argv) {
         svh_vo* vs[3];
         for (int i = 0; i < 3; i++) {
             vs[i] = svh_vo_mono_create(&p);
-            if (!vs[i]) { bad++; return; }
+            if (!vs[i]) { BAD(); return; }
             if (id == 1) svh_vo_set_private_rand(vs[i], 1, (uint32_t)i);
         }
         std::vector<std::vector<uint8_t>> I[2];
@@ -586,7 +628,7 @@ int main(int argc, char** argv) {
             }
             const int32_t rc = svh_vo_mono_process_matches_batch(vs, 3, mp, n, ok);
             check(rc);
-            if (rc >= 0 && ok[0] != 0) bad++;   // (N < 10 never succeeds)
+            if (rc >= 0 && ok[0] != 0) BAD();   // (N < 10 never succeeds)
             int32_t votes[64];
             for (int i = 0; i < 3; i++) matches += svh_vo_mono_get_votes(vs[i], votes, 64) + svh_vo_get_inliers(vs[i], nullptr, 0);
         }
