@@ -48,6 +48,7 @@ static thread_local int t_device = 0;
 
 // (null entry: the ELAS entries print the one stderr line themselves, not the point of failure)
 #define HIP_TRY(kind, expr) SVH_HIP_TRY(nullptr, kind, expr)
+#define LANE_GROW(buf, bytes) SVH_HIP_GROW(nullptr, buf, bytes)
 
 // ---------------------------------------------------------------------------
 // per-kernel timing with HIP events recorded on the lane's own stream
@@ -105,7 +106,31 @@ struct EventProfiler : Profiler {
 // ---------------------------------------------------------------------------
 // lane: stream + buffers for a group of up to `gcap` pairs
 // ---------------------------------------------------------------------------
-struct Lane {
+// the buffers, all sized by the lane's geometry: a new geometry starts from a fresh set
+struct LaneBufs {
+    // device
+    HipBuf<uint8_t> img;           // [gcap][2][N]       staged host images
+    HipBuf<uint8_t> desc;          // [gcap][2][N*16]
+    HipBuf<int16_t> dcan;          // [gcap][nc]
+    HipBuf<int32_t> owner;         // [gcap][2][N]
+    HipBuf<uint8_t> prior_dev;     // packed upload: header, P, support, triangles
+    HipBuf<TriRaster> raster;      // [gcap*2*ntri_max]
+    HipBuf<float> planes;          // 6 per triangle
+    HipBuf<uint32_t> seed, mask;   // [gcap][2][cells][gwords]
+    HipBuf<uint16_t> lists;        // [gcap][2][cells][32] candidate records (k_grid_list)
+    HipBuf<float> Draw;            // [gcap][2][DN]
+    HipBuf<float> D;               // [gcap][2][DN]  (host-output mode)
+    HipBuf<float> tmp;             // [gcap][2][DN]
+    HipBuf<int32_t> labels, counts;
+    HipBuf<int32_t> seg_nroots;    // [2 * gcap][tiles] tile-local roots per 64 x 16 tile (k_seg_tile -> k_seg_sum)
+    HipBuf<uint8_t> stage_blob;    // one allocation behind the StageDev arrays
+    // pinned host
+    PinnedBuf<int16_t> h_dcan;
+    PinnedBuf<uint8_t> h_img, h_prior;
+    PinnedBuf<StageCounts> h_counts;
+};
+
+struct Lane : LaneBufs {
     EventProfiler prof;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -118,29 +143,8 @@ struct Lane {
     // geometry the buffers were sized for
     int32_t W = 0, H = 0, disp_max = -1, step = 0, grid_size = 0, sub = -1, gcap = 0;
     Dims d{};
-    // device
-    uint8_t* img = nullptr;        // [gcap][2][N]       staged host images
-    uint8_t* desc = nullptr;       // [gcap][2][N*16]
-    bool desc_fly = false;         // the group in flight left only the Sobel planes there (descriptors_on_the_fly)
-    int16_t* dcan = nullptr;       // [gcap][nc]
-    int32_t* owner = nullptr;      // [gcap][2][N]
+    bool desc_fly = false;         // the group in flight left only the Sobel planes in desc (descriptors_on_the_fly)
     int64_t owner_hi = 0;          // every value stored in owner[] so far is <= owner_hi
-    uint8_t* prior_dev = nullptr;  // packed upload: header, P, support, triangles
-    TriRaster* raster = nullptr;   // [gcap*2*ntri_max]
-    float* planes = nullptr;       // 6 per triangle
-    uint32_t* seed = nullptr;      // [gcap][2][cells][gwords]
-    uint32_t* mask = nullptr;
-    uint16_t* lists = nullptr;     // [gcap][2][cells][32] candidate records (k_grid_list)
-    float* Draw = nullptr;         // [gcap][2][DN]
-    float* D = nullptr;            // [gcap][2][DN]  (host-output mode)
-    float* tmp = nullptr;          // [gcap][2][DN]
-    int32_t* labels = nullptr;
-    int32_t* counts = nullptr;
-    int32_t* seg_nroots = nullptr;   // [2 * gcap][tiles] tile-local roots per 64 x 16 tile (k_seg_tile -> k_seg_sum)
-    // pinned host
-    int16_t* h_dcan = nullptr;
-    uint8_t* h_img = nullptr;
-    uint8_t* h_prior = nullptr;
     size_t prior_cap = 0;
     size_t ntri_max = 0;
     std::vector<HostPrior> hp;
@@ -148,8 +152,6 @@ struct Lane {
     // device-side E5-E7 (elas_stage_kernels.hip): scratch, counts read back through pinned memory
     StageDev stg{};
     bool stage_ok = false;          // the geometry fits the device stage and its scratch exists
-    void* stage_blob = nullptr;     // one allocation behind the StageDev arrays
-    StageCounts* h_counts = nullptr;
     hipEvent_t stage_ev = nullptr;  // the counts have arrived
     bool resident = false;          // the group on this lane runs the device stage
     bool force_host = false;        // rerun of a group the device stage handed back
@@ -159,16 +161,8 @@ struct Lane {
     void release() {
         if (!stream) return;
         (void)hipSetDevice(device);
-        (void)hipFree(img); (void)hipFree(desc); (void)hipFree(dcan); (void)hipFree(owner);
-        (void)hipFree(prior_dev); (void)hipFree(raster); (void)hipFree(planes); (void)hipFree(seed);
-        (void)hipFree(mask); (void)hipFree(lists); lists = nullptr; (void)hipFree(Draw); (void)hipFree(D); (void)hipFree(tmp);
-        (void)hipFree(labels); (void)hipFree(counts); (void)hipFree(seg_nroots); seg_nroots = nullptr;
-        img = desc = prior_dev = nullptr; dcan = nullptr; owner = nullptr; raster = nullptr;
-        planes = Draw = D = tmp = nullptr; seed = mask = nullptr; labels = counts = nullptr;
-        (void)hipHostFree(h_dcan); (void)hipHostFree(h_prior); (void)hipHostFree(h_img);
-        h_dcan = nullptr; h_prior = nullptr; h_img = nullptr;
-        (void)hipFree(stage_blob); (void)hipHostFree(h_counts);
-        stage_blob = nullptr; h_counts = nullptr; stage_ok = false; stg = StageDev{};
+        static_cast<LaneBufs&>(*this) = LaneBufs();
+        stage_ok = false; stg = StageDev{};
         P_key[0] = -1;
         W = H = 0;
     }
@@ -205,36 +199,36 @@ struct Lane {
         stream = keep;
         d = make_dims(p, w, h);
         const size_t N = (size_t)w * h, DN = (size_t)d.DW * d.DH, G2 = (size_t)2 * g;
-        HIP_TRY(malloc, hipMalloc(&img, G2 * N));
-        HIP_TRY(malloc, hipMalloc(&desc, G2 * N * 16));
-        HIP_TRY(malloc, hipMalloc(&owner, G2 * N * sizeof(int32_t)));
+        LANE_GROW(img, G2 * N);
+        LANE_GROW(desc, G2 * N * 16);
+        LANE_GROW(owner, G2 * N * sizeof(int32_t));
         HIP_TRY(copy, hipMemset(owner, 0, G2 * N * sizeof(int32_t)));
         // SVH_TEST_OWNER_HI: start the moving base just below the int32 limit so that a test
         // reaches the (otherwise once-per-40 000-groups) re-clear path with its first groups
         owner_hi = svh::env("SVH_TEST_OWNER_HI") ? atoll(svh::env("SVH_TEST_OWNER_HI")) : 0;
-        HIP_TRY(malloc, hipMalloc(&Draw, G2 * DN * sizeof(float)));
-        HIP_TRY(malloc, hipMalloc(&D, G2 * DN * sizeof(float)));
-        HIP_TRY(malloc, hipMalloc(&tmp, G2 * DN * sizeof(float)));
-        HIP_TRY(malloc, hipMalloc(&labels, G2 * DN * sizeof(int32_t)));
-        HIP_TRY(malloc, hipMalloc(&counts, G2 * DN * sizeof(int32_t)));
-        HIP_TRY(malloc, hipMalloc(&seg_nroots, G2 * (size_t)((d.DW + 63) / 64) * ((d.DH + 15) / 16) * sizeof(int32_t)));   // one count per 64 x 16 tile
+        LANE_GROW(Draw, G2 * DN * sizeof(float));
+        LANE_GROW(D, G2 * DN * sizeof(float));
+        LANE_GROW(tmp, G2 * DN * sizeof(float));
+        LANE_GROW(labels, G2 * DN * sizeof(int32_t));
+        LANE_GROW(counts, G2 * DN * sizeof(int32_t));
+        LANE_GROW(seg_nroots, G2 * (size_t)((d.DW + 63) / 64) * ((d.DH + 15) / 16) * sizeof(int32_t));   // one count per 64 x 16 tile
         const size_t nc = (size_t)d.Wc * d.Hc;
-        HIP_TRY(malloc, hipMalloc(&dcan, g * nc * sizeof(int16_t)));
-        HIP_TRY(malloc, hipHostMalloc(&h_dcan, g * nc * sizeof(int16_t)));
-        HIP_TRY(malloc, hipHostMalloc(&h_img, G2 * N));
+        LANE_GROW(dcan, g * nc * sizeof(int16_t));
+        LANE_GROW(h_dcan, g * nc * sizeof(int16_t));
+        LANE_GROW(h_img, G2 * N);
         // worst case per pair: nc+6 support points, 2n+8 triangles per side
         const size_t nsup = nc + 6;
         ntri_max = 2 * nsup + 8;
         prior_cap = sizeof(GroupHdr) + (size_t)(p.disp_max + 1) * sizeof(int32_t) + 512 +
                     (size_t)g * (nsup * 3 + 2 * ntri_max * 3) * sizeof(int32_t);
-        HIP_TRY(malloc, hipMalloc(&prior_dev, prior_cap));
-        HIP_TRY(malloc, hipHostMalloc(&h_prior, prior_cap));
-        HIP_TRY(malloc, hipMalloc(&raster, G2 * ntri_max * sizeof(TriRaster)));
-        HIP_TRY(malloc, hipMalloc(&planes, G2 * ntri_max * 6 * sizeof(float)));
+        LANE_GROW(prior_dev, prior_cap);
+        LANE_GROW(h_prior, prior_cap);
+        LANE_GROW(raster, G2 * ntri_max * sizeof(TriRaster));
+        LANE_GROW(planes, G2 * ntri_max * 6 * sizeof(float));
         const size_t gw_bytes = G2 * d.gw * d.gh * d.gwords * sizeof(uint32_t);
-        HIP_TRY(malloc, hipMalloc(&seed, gw_bytes));
-        HIP_TRY(malloc, hipMalloc(&mask, gw_bytes));
-        if (d.gwords <= 8) HIP_TRY(malloc, hipMalloc(&lists, G2 * d.gw * d.gh * 32 * sizeof(uint16_t)));
+        LANE_GROW(seed, gw_bytes);
+        LANE_GROW(mask, gw_bytes);
+        if (d.gwords <= 8) LANE_GROW(lists, G2 * d.gw * d.gh * 32 * sizeof(uint16_t));
         hp.resize(g);
         // fixed layout of the packed lists when the device builds them
         o_P = (sizeof(GroupHdr) + 63) & ~(size_t)63;
@@ -251,10 +245,10 @@ struct Lane {
             for (int k = 0; k < 11; k++) a_arr[k] = take(S2 * cap * 4);
             const size_t a_fl = take(S2 * 2 * cap * 4), a_fr = take(S2 * 2 * cap * 4);
             const size_t a_wl = take((size_t)g * 3 * nc * 4), a_cw = take((size_t)g * (nc / 4 + 1) * 4);
-            HIP_TRY(malloc, hipMalloc(&stage_blob, off));
+            LANE_GROW(stage_blob, off);
             HIP_TRY(copy, hipMemset(stage_blob, 0, off));
-            HIP_TRY(malloc, hipHostMalloc(&h_counts, sizeof(StageCounts)));
-            uint8_t* b = static_cast<uint8_t*>(stage_blob);
+            LANE_GROW(h_counts, sizeof(StageCounts));
+            uint8_t* b = stage_blob;
             stg.dcan = dcan;
             stg.sup_raw = reinterpret_cast<int32_t*>(b + a_sup);
             stg.counts = reinterpret_cast<StageCounts*>(b + a_cnt);
@@ -584,7 +578,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     double t0 = now_ms();
     uint64_t hp_t = g_hostprof ? cpu_ns() : 0;
 
-    GroupHdr* hdr = reinterpret_cast<GroupHdr*>(L.h_prior);   // host view of the header
+    GroupHdr* hdr = reinterpret_cast<GroupHdr*>(L.h_prior.p);   // host view of the header
     DevMaps out;
     if (io.out_device) {
         // the callers' maps live on the device: the post-processing chain runs in place on them
@@ -601,7 +595,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     auto enqueue_phase_b = [&](size_t o_P, size_t o_sup, size_t o_tri, int32_t total_sup, int32_t total_tri,
                                int32_t tri_bound) -> int {
         GroupDev G;
-        G.hdr = reinterpret_cast<const GroupHdr*>(L.prior_dev);
+        G.hdr = reinterpret_cast<const GroupHdr*>(L.prior_dev.p);
         G.P = reinterpret_cast<const int32_t*>(L.prior_dev + o_P);
         G.support = reinterpret_cast<const int32_t*>(L.prior_dev + o_sup);
         G.tri = reinterpret_cast<const int32_t*>(L.prior_dev + o_tri);
@@ -629,8 +623,8 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         launch_prior(cx, p, d, g, total_sup, total_tri, G);
         if (tapping) {
             const int32_t n1 = hdr->tri_end[0], n2 = hdr->tri_end[1] - hdr->tri_end[0];
-            rc = tap_dev(L, taps, SVH_ELAS_PLANES1, L.planes, (size_t)6 * n1); if (rc) return rc;
-            rc = tap_dev(L, taps, SVH_ELAS_PLANES2, L.planes + (size_t)6 * n1, (size_t)6 * n2); if (rc) return rc;
+            rc = tap_dev(L, taps, SVH_ELAS_PLANES1, L.planes.p, (size_t)6 * n1); if (rc) return rc;
+            rc = tap_dev(L, taps, SVH_ELAS_PLANES2, L.planes.p + (size_t)6 * n1, (size_t)6 * n2); if (rc) return rc;
             const size_t words = (size_t)d.gw * d.gh * d.gwords;
             std::vector<uint32_t> m(2 * words);
             HIP_TRY(copy, hipMemcpyAsync(m.data(), L.mask, m.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -657,8 +651,8 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             HIP_TRY(none, hipEventRecord(L.match_ev, s));
         }
         if (tapping) {
-            rc = tap_dev(L, taps, SVH_ELAS_D1_RAW, L.Draw, DN); if (rc) return rc;
-            rc = tap_dev(L, taps, SVH_ELAS_D2_RAW, L.Draw + DN, DN); if (rc) return rc;
+            rc = tap_dev(L, taps, SVH_ELAS_D1_RAW, L.Draw.p, DN); if (rc) return rc;
+            rc = tap_dev(L, taps, SVH_ELAS_D2_RAW, L.Draw.p + DN, DN); if (rc) return rc;
         }
         const PostScratch ps = {L.tmp, L.labels, L.counts, L.seg_nroots};
         const int nside = p.postprocess_only_left ? 1 : 2;
@@ -726,7 +720,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     };
     // per-pair result of the device stage, from the counts it sent back
     auto active_of = [&](int32_t j) {
-        return L.h_counts->nsup[j] >= 3 && !(L.h_counts->flags[j] & (STG_DUP | STG_OVERFLOW));
+        return L.h_counts.p->nsup[j] >= 3 && !(L.h_counts.p->flags[j] & (STG_DUP | STG_OVERFLOW));
     };
 
     auto finish = [&]() -> int {
@@ -737,7 +731,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         if (!L.resident) return SVH_OK;
         g_stage_dev_groups++;
         bool redo = false;
-        for (int32_t j = 0; j < g; j++) redo = redo || (L.h_counts->flags[j] & (STG_DUP | STG_OVERFLOW)) != 0;
+        for (int32_t j = 0; j < g; j++) redo = redo || (L.h_counts.p->flags[j] & (STG_DUP | STG_OVERFLOW)) != 0;
         if (redo) {
             // coincident support points (or more points than the scratch holds): which duplicate
             // survives is decided by Triangle's pivot stream -- the host path reproduces that.  The whole
@@ -752,7 +746,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             return rc;
         }
         for (int32_t j = 0; j < g; j++) {
-            if (L.h_counts->nsup[j] < 3) {
+            if (L.h_counts.p->nsup[j] < 3) {
                 // elas.cpp:69-75: message on stdout, outputs untouched
                 printf("ERROR: Need at least 3 support points!\n");
                 fflush(stdout);
@@ -831,8 +825,8 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         if (tapping && L.desc_fly) {
             // SVH_DESC_FLY=2 (tests): the descriptor taps come from the full kernel, then the planes replace them
             launch_descriptor(cx, img, g, W, H, p.subsampling, L.desc, false);
-            int rc2 = tap_dev(L, taps, SVH_ELAS_DESC1, L.desc, N * 16); if (rc2) return rc2;
-            rc2 = tap_dev(L, taps, SVH_ELAS_DESC2, L.desc + N * 16, N * 16); if (rc2) return rc2;
+            int rc2 = tap_dev(L, taps, SVH_ELAS_DESC1, L.desc.p, N * 16); if (rc2) return rc2;
+            rc2 = tap_dev(L, taps, SVH_ELAS_DESC2, L.desc.p + N * 16, N * 16); if (rc2) return rc2;
             HIP_TRY(wait, hipStreamSynchronize(s));
         }
         launch_descriptor(cx, img, g, W, H, p.subsampling, L.desc, L.desc_fly);
@@ -861,12 +855,12 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             if (tapping) {
                 HIP_TRY(wait, hipStreamSynchronize(s));
                 if (!L.desc_fly) {
-                    rc = tap_dev(L, taps, SVH_ELAS_DESC1, L.desc, N * 16); if (rc) return rc;
-                    rc = tap_dev(L, taps, SVH_ELAS_DESC2, L.desc + N * 16, N * 16); if (rc) return rc;
+                    rc = tap_dev(L, taps, SVH_ELAS_DESC1, L.desc.p, N * 16); if (rc) return rc;
+                    rc = tap_dev(L, taps, SVH_ELAS_DESC2, L.desc.p + N * 16, N * 16); if (rc) return rc;
                 }
-                tap_host(taps, SVH_ELAS_DCAN_RAW, L.h_dcan, nc);
+                tap_host(taps, SVH_ELAS_DCAN_RAW, L.h_dcan.p, nc);
             }
-            launch_stage_device(cx, p, d, g, L.stg, reinterpret_cast<GroupHdr*>(L.prior_dev),
+            launch_stage_device(cx, p, d, g, L.stg, reinterpret_cast<GroupHdr*>(L.prior_dev.p),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_sup),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_tri));
             if (!L.stage_ev) HIP_TRY(none, hipEventCreateWithFlags(&L.stage_ev, hipEventDisableTiming));
@@ -926,10 +920,10 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     t1 = now_ms();
     if (tapping) {
         if (!L.desc_fly) {
-            rc = tap_dev(L, taps, SVH_ELAS_DESC1, L.desc, N * 16); if (rc) return rc;
-            rc = tap_dev(L, taps, SVH_ELAS_DESC2, L.desc + N * 16, N * 16); if (rc) return rc;
+            rc = tap_dev(L, taps, SVH_ELAS_DESC1, L.desc.p, N * 16); if (rc) return rc;
+            rc = tap_dev(L, taps, SVH_ELAS_DESC2, L.desc.p + N * 16, N * 16); if (rc) return rc;
         }
-        tap_host(taps, SVH_ELAS_DCAN_RAW, L.h_dcan, nc);
+        tap_host(taps, SVH_ELAS_DCAN_RAW, L.h_dcan.p, nc);
     }
 
     // ---- host: lattice filters + Delaunay, then one packed upload ------------

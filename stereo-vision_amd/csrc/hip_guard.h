@@ -47,6 +47,9 @@ int hip_failed(const char* entry, const char* expr_text, bool injected, hipError
 // growth that fails leaves "nothing allocated", which the next call repairs, never a stale pointer behind a capacity
 // that says "fits".  A grow() within the capacity issues no HIP call at all (hipFree synchronises the device).  The
 // destructor frees on the current device: an object's destroy selects its device and drains its stream first.
+// Every device and pinned buffer of every host engine is one of these, and hipMalloc / hipHostMalloc / hipFree /
+// hipHostFree are called here only: an engine has no list of buffers to free.  A set of buffers that follows a geometry
+// (a Matcher view, a map, an ELAS lane) is a struct of owners, and "release" is the assignment of a fresh one.
 template <typename T, bool Pinned = false>
 struct HipBuf {
     T* p = nullptr;
@@ -99,5 +102,8 @@ extern "C" int32_t svh_test_fail_at(const char* spec);
     do {                                                                                                \
         if ((buf).cap < (size_t)(bytes)) SVH_HIP_TRY(entry, malloc, (buf).grow(bytes));                 \
     } while (0)
+// ... to `count` elements, at least one: kernels receive the pointer of an empty table too
+#define SVH_HIP_GROW_N(entry, buf, count) \
+    SVH_HIP_GROW(entry, buf, ((size_t)(count) > 0 ? (size_t)(count) : 1) * sizeof(*(buf).p))
 
 #endif

@@ -283,56 +283,47 @@ struct svh_map {
     int device = 0;
     hipStream_t stream = nullptr;
     int32_t w = 0, h = 0;            // geometry the buffers are sized for
-    Planes pl[2] = {};               // [cur], [prev] planes, swapped every frame
-    int cur = 0;
+    int cur = 0;                     // planes [cur], [1 - cur] = previous, swapped every frame
     bool have_prev = false;
     int32_t pw = 0, ph = 0;
-    float* dD1 = nullptr;            // staged disparity map when the caller's is on the host
-    uint8_t* dI1 = nullptr;
-    uint8_t* h_stage = nullptr;      // pinned: packed I1 rows, then D1
-    int32_t *head = nullptr, *next = nullptr, *blockcnt = nullptr;
-    uint8_t* state = nullptr;
-    float4* pts[2] = {nullptr, nullptr};
-    int64_t* h_total = nullptr;      // pinned: point counts of the two lists
+    struct Bufs {                    // everything sized by the geometry
+        svh::HipBuf<float> pl[2][5];         // I, D, X, Y, Z
+        svh::HipBuf<float4> pts[2];
+        svh::HipBuf<float> dD1;              // staged disparity map when the caller's is on the host
+        svh::HipBuf<uint8_t> dI1;
+        svh::HipBuf<int32_t> head, next;
+        svh::HipBuf<uint8_t> state;
+        svh::HipBuf<int32_t> blockcnt;
+        svh::PinnedBuf<uint8_t> h_stage;     // packed I1 rows, then D1
+    } b;
+    svh::PinnedBuf<int64_t> h_total; // point counts of the two lists
     int64_t npts[2] = {0, 0};
 
-    void release() {
-        for (int k = 0; k < 2; k++) {
-            (void)hipFree(pl[k].I); (void)hipFree(pl[k].D); (void)hipFree(pl[k].X);
-            (void)hipFree(pl[k].Y); (void)hipFree(pl[k].Z);
-            pl[k] = Planes{};
-            (void)hipFree(pts[k]);
-            pts[k] = nullptr;
-        }
-        (void)hipFree(dD1); (void)hipFree(dI1); (void)hipFree(head); (void)hipFree(next);
-        (void)hipFree(blockcnt); (void)hipFree(state);
-        (void)hipHostFree(h_stage);
-        dD1 = nullptr; dI1 = nullptr; head = next = blockcnt = nullptr; state = nullptr; h_stage = nullptr;
-        w = h = 0;
-    }
+    Planes planes(int k) const { return Planes{b.pl[k][0], b.pl[k][1], b.pl[k][2], b.pl[k][3], b.pl[k][4]}; }
 };
 
 #define MAP_TRY(kind, expr) SVH_HIP_TRY("map", kind, expr)
+#define MAP_GROW(buf, bytes) SVH_HIP_GROW("map", buf, bytes)
 
 static int32_t map_ensure(svh_map* m, int32_t w, int32_t h) {
     if (m->w == w && m->h == h) return SVH_OK;
     // a change of geometry starts a new reconstruction: the previous map cannot be addressed
     // with the new dimensions' buffers
-    m->release();
+    m->b = svh_map::Bufs();
+    m->w = m->h = 0;             // (until every buffer exists: a failure below is repaired by the next call)
     const size_t n = (size_t)w * h;
+    svh_map::Bufs& b = m->b;
     for (int k = 0; k < 2; k++) {
-        MAP_TRY(malloc, hipMalloc(&m->pl[k].I, n * 4)); MAP_TRY(malloc, hipMalloc(&m->pl[k].D, n * 4));
-        MAP_TRY(malloc, hipMalloc(&m->pl[k].X, n * 4)); MAP_TRY(malloc, hipMalloc(&m->pl[k].Y, n * 4));
-        MAP_TRY(malloc, hipMalloc(&m->pl[k].Z, n * 4));
-        MAP_TRY(malloc, hipMalloc(&m->pts[k], n * sizeof(float4)));
+        for (int i = 0; i < 5; i++) MAP_GROW(b.pl[k][i], n * 4);
+        MAP_GROW(b.pts[k], n * sizeof(float4));
     }
-    MAP_TRY(malloc, hipMalloc(&m->dD1, n * 4));
-    MAP_TRY(malloc, hipMalloc(&m->dI1, n));
-    MAP_TRY(malloc, hipMalloc(&m->head, n * 4));
-    MAP_TRY(malloc, hipMalloc(&m->next, n * 4));
-    MAP_TRY(malloc, hipMalloc(&m->state, n));
-    MAP_TRY(malloc, hipMalloc(&m->blockcnt, ((n + 1023) / 1024 + 1) * 4));
-    MAP_TRY(malloc, hipHostMalloc(&m->h_stage, n * 5));
+    MAP_GROW(b.dD1, n * 4);
+    MAP_GROW(b.dI1, n);
+    MAP_GROW(b.head, n * 4);
+    MAP_GROW(b.next, n * 4);
+    MAP_GROW(b.state, n);
+    MAP_GROW(b.blockcnt, ((n + 1023) / 1024 + 1) * 4);
+    MAP_GROW(b.h_stage, n * 5);
     m->w = w;
     m->h = h;
     m->have_prev = false;
@@ -354,7 +345,7 @@ svh_map* svh_map_create(const svh_map_params* p) {
     m->p = *p;
     (void)hipGetDevice(&m->device);
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc(&m->h_total, 2 * sizeof(int64_t)) != hipSuccess) {
+        m->h_total.grow(2 * sizeof(int64_t)) != hipSuccess) {
         delete m;
         return nullptr;
     }
@@ -364,10 +355,9 @@ svh_map* svh_map_create(const svh_map_params* p) {
 void svh_map_destroy(svh_map* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    m->release();
-    (void)hipHostFree(m->h_total);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
+    const hipStream_t s = m->stream;
+    delete m;   // the buffers free themselves, on the device selected above
+    if (s) (void)hipStreamDestroy(s);
 }
 
 void svh_map_clear(svh_map* m) {
@@ -386,14 +376,15 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     if (rc) return rc;
     hipStream_t s = m->stream;
     const size_t n = (size_t)w * h;
+    const svh_map::Bufs& b = m->b;
     // inputs: the image rows are packed on the way into pinned memory
-    for (int32_t v = 0; v < h; v++) memcpy(m->h_stage + (size_t)v * w, I1 + (size_t)v * step, w);
-    MAP_TRY(copy, hipMemcpyAsync(m->dI1, m->h_stage, n, hipMemcpyHostToDevice, s));
+    for (int32_t v = 0; v < h; v++) memcpy(b.h_stage + (size_t)v * w, I1 + (size_t)v * step, w);
+    MAP_TRY(copy, hipMemcpyAsync(b.dI1, b.h_stage, n, hipMemcpyHostToDevice, s));
     const float* dD = D1;
     if (!d1_on_device) {
-        memcpy(m->h_stage + n, D1, n * 4);
-        MAP_TRY(copy, hipMemcpyAsync(m->dD1, m->h_stage + n, n * 4, hipMemcpyHostToDevice, s));
-        dD = m->dD1;
+        memcpy(b.h_stage + n, D1, n * 4);
+        MAP_TRY(copy, hipMemcpyAsync(b.dD1, b.h_stage + n, n * 4, hipMemcpyHostToDevice, s));
+        dD = b.dD1;
     }
     // coefficients (stereothread.cpp:196-199, 306-314, 450-455) with the Matrix class of the boundary
     MapCoef c;
@@ -422,27 +413,27 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     c.gain_inv = 1;
     if (gain) c.gain_inv = 1.0 / gain;
 
-    const Planes cur = m->pl[m->cur], prev = m->pl[1 - m->cur];
-    hipLaunchKernelGGL(k_map_create, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, s, dD, m->dI1, w, h, w, c, cur);
+    const Planes cur = m->planes(m->cur), prev = m->planes(1 - m->cur);
+    hipLaunchKernelGGL(k_map_create, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, s, dD, b.dI1, w, h, w, c, cur);
     const int nb = (int)((n + 1023) / 1024);
     if (m->have_prev) {
         const int pn = m->pw * m->ph;   // == n: a geometry change resets the reconstruction
-        MAP_TRY(copy, hipMemsetAsync(m->head, 0xFF, n * 4, s));
+        MAP_TRY(copy, hipMemsetAsync(b.head, 0xFF, n * 4, s));
         hipLaunchKernelGGL(k_map_project, dim3((pn + 255) / 256), dim3(256), 0, s, prev, m->pw, m->ph, w, h, c,
-                           m->head, m->next, m->state);
+                           b.head, b.next, b.state);
         hipLaunchKernelGGL(k_map_fuse, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, prev, m->pw, m->ph, cur,
-                           (int)n, m->head, m->next, m->state);
+                           (int)n, b.head, b.next, b.state);
         const int pb = (pn + 1023) / 1024;
-        hipLaunchKernelGGL(k_map_count<true>, dim3(pb), dim3(256), 0, s, m->state, prev, m->pw, m->ph, m->blockcnt);
-        hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, s, m->blockcnt, pb, m->h_total);
-        hipLaunchKernelGGL(k_map_scatter<true>, dim3(pb), dim3(256), 0, s, m->state, prev, m->pw, m->ph, m->blockcnt,
-                           m->pts[0]);
+        hipLaunchKernelGGL(k_map_count<true>, dim3(pb), dim3(256), 0, s, b.state, prev, m->pw, m->ph, b.blockcnt);
+        hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, s, b.blockcnt, pb, m->h_total);
+        hipLaunchKernelGGL(k_map_scatter<true>, dim3(pb), dim3(256), 0, s, b.state, prev, m->pw, m->ph, b.blockcnt,
+                           b.pts[0]);
     } else {
         m->h_total[0] = 0;
     }
-    hipLaunchKernelGGL(k_map_count<false>, dim3(nb), dim3(256), 0, s, m->state, cur, w, h, m->blockcnt);
-    hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, s, m->blockcnt, nb, m->h_total + 1);
-    hipLaunchKernelGGL(k_map_scatter<false>, dim3(nb), dim3(256), 0, s, m->state, cur, w, h, m->blockcnt, m->pts[1]);
+    hipLaunchKernelGGL(k_map_count<false>, dim3(nb), dim3(256), 0, s, b.state, cur, w, h, b.blockcnt);
+    hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, s, b.blockcnt, nb, m->h_total + 1);
+    hipLaunchKernelGGL(k_map_scatter<false>, dim3(nb), dim3(256), 0, s, b.state, cur, w, h, b.blockcnt, b.pts[1]);
     MAP_TRY(wait, hipStreamSynchronize(s));
     MAP_TRY(launch, hipGetLastError());
     m->npts[0] = m->h_total[0];
@@ -461,7 +452,7 @@ int64_t svh_map_points(svh_map* m, int32_t which, float* xyzv, int64_t cap) {
     const int64_t n = m->npts[k];
     if (xyzv && n > 0 && cap > 0) {
         (void)hipSetDevice(m->device);
-        (void)hipMemcpy(xyzv, m->pts[k], (size_t)std::min(n, cap) * sizeof(float4), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(xyzv, m->b.pts[k], (size_t)std::min(n, cap) * sizeof(float4), hipMemcpyDeviceToHost);
     }
     return n;
 }
@@ -472,16 +463,11 @@ int32_t svh_disparity_colormap(const float* D, int32_t d_on_device, int64_t n, f
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
         return svh::fail(SVH_ERR_NO_DEVICE, "no HIP device visible: libsvhip has no CPU fallback");
-    float *dD = nullptr, *dC = nullptr;
-    struct FreeBoth {       // (the error returns below must not leak the two temporaries)
-        float*& a;
-        float*& b;
-        ~FreeBoth() { (void)hipFree(a); (void)hipFree(b); }
-    } free_both_{dD, dC};
-    MAP_TRY(malloc, hipMalloc(&dC, (size_t)n * 12));
+    svh::HipBuf<float> dD, dC;
+    MAP_GROW(dC, (size_t)n * 12);
     const float* src = D;
     if (!d_on_device) {
-        MAP_TRY(malloc, hipMalloc(&dD, (size_t)n * 4));
+        MAP_GROW(dD, (size_t)n * 4);
         MAP_TRY(copy, hipMemcpy(dD, D, (size_t)n * 4, hipMemcpyHostToDevice));
         src = dD;
     }
@@ -496,7 +482,7 @@ int32_t svh_map_planes(svh_map* m, float* out5, size_t cap_floats) {
     const size_t n = (size_t)m->w * m->h;
     if (cap_floats < 5 * n) return svh::fail(SVH_ERR_BAD_ARG, "buffer too small");
     MAP_TRY(none, hipSetDevice(m->device));
-    const Planes& p = m->pl[1 - m->cur];   // the map of the last frame
+    const Planes p = m->planes(1 - m->cur);   // the map of the last frame
     float* src[5] = {p.I, p.D, p.X, p.Y, p.Z};
     for (int k = 0; k < 5; k++) MAP_TRY(copy, hipMemcpy(out5 + k * n, src[k], n * 4, hipMemcpyDeviceToHost));
     return SVH_OK;

@@ -317,26 +317,7 @@ thread_local bool t_in_batch = false;   // inside a batch call: the outlier vote
 // (one line on stderr at the point of failure: the entries above it only pass the code on)
 #define HIP_TRY(kind, expr) SVH_HIP_TRY("Matcher", kind, expr)
 
-template <typename T>
-static hipError_t dalloc(T** p, size_t count) {
-    return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-}
-// Growing a buffer: the old one is freed and its pointer CLEARED before the new allocation is tried, and the callers
-// set the capacity they track to 0 first and to the new size only after every allocation of the set succeeded -- a
-// failure in the middle (found by the sanitizer run with injected failures, tools/sanitize_viso.cpp) then leaves
-// "nothing allocated", which the next call repairs, instead of a stale pointer behind a capacity that says "fits".
-template <typename T>
-static hipError_t drealloc(T** p, size_t count) {
-    (void)hipFree(*p);
-    *p = nullptr;
-    return dalloc(p, count);
-}
-template <typename T>
-static hipError_t hrealloc(T** p, size_t bytes) {
-    (void)hipHostFree(*p);
-    *p = nullptr;
-    return hipHostMalloc((void**)p, bytes);
-}
+#define GROW_N(buf, count) SVH_HIP_GROW_N("Matcher", buf, count)
 
 // device-resident data of one camera image of one frame
 struct DevView {
@@ -344,38 +325,16 @@ struct DevView {
     int32_t w = 0, h = 0, bpl = 0;       // full resolution
     int32_t mw = 0, mh = 0, mbpl = 0;    // matching resolution
     int32_t half = -1;
-    uint8_t *I = nullptr, *Ih = nullptr, *du = nullptr, *dv = nullptr, *du_full = nullptr,
-            *dv_full = nullptr;
-    int16_t *f1 = nullptr, *f2 = nullptr;
-    int32_t* tab[2] = {nullptr, nullptr};   // sparse, dense
+    HipBuf<uint8_t> I, Ih, du, dv, du_full, dv_full;
+    HipBuf<int16_t> f1, f2;
+    HipBuf<int32_t> tab[2];                 // sparse, dense
     int32_t cap[2] = {0, 0};
-    int32_t* cnt = nullptr;                 // device: n_sparse, n_dense
+    HipBuf<int32_t> cnt;                    // device: n_sparse, n_dense
     int32_t n[2] = {0, 0};                  // host copy
-    int32_t *off[2] = {nullptr, nullptr}, *ids[2] = {nullptr, nullptr};
+    HipBuf<int32_t> off[2], ids[2];         // off[] grows with the bin grid
     int32_t nbins = 0;
-    int32_t off_cap = 0;      // bins the off[] arrays were allocated for
-    uint8_t* stage = nullptr;               // pinned: the packed image (upload source, and getGain's host copy),
+    PinnedBuf<uint8_t> stage;               // the packed image (upload source, and getGain's host copy),
                                             // h rows of bpl bytes + one zero row
-
-    void release() {
-        (void)hipFree(I); (void)hipFree(Ih); (void)hipFree(du); (void)hipFree(dv); (void)hipFree(du_full);
-        (void)hipFree(dv_full); (void)hipFree(f1); (void)hipFree(f2); (void)hipFree(cnt);
-        (void)hipHostFree(stage);
-        stage = nullptr;
-        for (int k = 0; k < 2; k++) {
-            (void)hipFree(tab[k]); (void)hipFree(off[k]); (void)hipFree(ids[k]);
-            tab[k] = off[k] = ids[k] = nullptr;
-            cap[k] = 0;
-        }
-        I = Ih = du = dv = du_full = dv_full = nullptr;
-        f1 = f2 = nullptr;
-        cnt = nullptr;
-        w = h = 0;
-        half = -1;
-        nbins = 0;
-        off_cap = 0;
-        valid = false;
-    }
 };
 
 }  // namespace svh
@@ -399,26 +358,19 @@ struct svh_matcher {
     std::shared_ptr<std::string> next_why;    // ... and its error text, if it failed
     int32_t dims_p[3], dims_c[3];
     // scratch
-    int4* slots[4] = {nullptr, nullptr, nullptr, nullptr};      // NMS scratch, one set per camera (the cameras' feature
-    int32_t* flags[4] = {nullptr, nullptr, nullptr, nullptr};   // extraction runs on two streams) and, [2 + camera], a second
-    int32_t* order[4] = {nullptr, nullptr, nullptr, nullptr};   // one for the sparse table (both tables by the same launches)
-    int32_t slot_cap = 0;
+    HipBuf<int4> slots[4];                    // NMS scratch, one set per camera (the cameras' feature
+    HipBuf<int32_t> flags[4];                 // extraction runs on two streams) and, [2 + camera], a second
+    HipBuf<int32_t> order[4];                 // one for the sparse table (both tables by the same launches)
     hipStream_t stream2 = nullptr;            // camera 1 during pushBack
-    int32_t* cursor = nullptr;
-    int32_t cursor_cap = 0;
-    svh_p_match *pm_slots = nullptr, *pm_out = nullptr;
-    int32_t *pm_flags = nullptr, *pm_count = nullptr;
-    int32_t pm_cap = 0;
-    int32_t* pixel_owner = nullptr;
-    size_t owner_cap = 0;
-    float* ranges_dev = nullptr;
-    int32_t ranges_cap = 0;
-    float* h_ranges = nullptr;                  // pinned copy of `ranges` (batched calls upload it from a kernel)
-    size_t h_ranges_cap = 0;
-    svh_p_match* h_pm = nullptr;                // pinned download staging for match lists
-    int32_t* h_cnt = nullptr;                   // pinned: match count
-    int32_t* h_n = nullptr;                     // pinned: feature counts [camera][sparse, dense]
-    int32_t h_pm_cap = 0;
+    HipBuf<int32_t> cursor;
+    HipBuf<svh_p_match> pm_slots, pm_out;
+    HipBuf<int32_t> pm_flags, pm_count;
+    HipBuf<int32_t> pixel_owner;
+    HipBuf<float> ranges_dev;
+    PinnedBuf<float> h_ranges;                  // copy of `ranges` (batched calls upload it from a kernel)
+    PinnedBuf<svh_p_match> h_pm;                // download staging for match lists
+    PinnedBuf<int32_t> h_cnt;                   // match count
+    PinnedBuf<int32_t> h_n;                     // feature counts [camera][sparse, dense]
     bool taps = false;                          // keep every intermediate stage (parity tests)
     int32_t last_dense = 0;                     // matches of the last dense pass before the vote (predicts the next one)
     bool warm_on_wait = false;                  // wake the vote's helper threads once the dense pass is enqueued
@@ -476,9 +428,9 @@ namespace svh {
 static int size_view(svh_matcher* m, DevView& V, int32_t w, int32_t h, int32_t bpl);
 static int ensure_view(svh_matcher* m, DevView& V, int32_t w, int32_t h, int32_t bpl) {
     if (V.w == w && V.h == h && V.bpl == bpl && V.half == m->p.half_resolution) return SVH_OK;
-    V.release();
+    V = DevView();
     const int rc = size_view(m, V, w, h, bpl);
-    if (rc) V.release();     // (a half-sized view must not look like one of the right geometry to the next call)
+    if (rc) V = DevView();   // (a half-sized view must not look like one of the right geometry to the next call)
     return rc;
 }
 static int size_view(svh_matcher* m, DevView& V, int32_t w, int32_t h, int32_t bpl) {
@@ -493,21 +445,21 @@ static int size_view(svh_matcher* m, DevView& V, int32_t w, int32_t h, int32_t b
         V.mw = w; V.mh = h; V.mbpl = bpl;
     }
     const size_t fn = (size_t)bpl * h, mn = (size_t)V.mbpl * V.mh;
-    HIP_TRY(malloc, dalloc(&V.I, fn));
-    HIP_TRY(malloc, dalloc(&V.du, mn));
-    HIP_TRY(malloc, dalloc(&V.dv, mn));
-    HIP_TRY(malloc, dalloc(&V.f1, mn));
-    HIP_TRY(malloc, dalloc(&V.f2, mn));
+    GROW_N(V.I, fn);
+    GROW_N(V.du, mn);
+    GROW_N(V.dv, mn);
+    GROW_N(V.f1, mn);
+    GROW_N(V.f2, mn);
     if (p.half_resolution) {
-        HIP_TRY(malloc, dalloc(&V.Ih, mn));
-        HIP_TRY(malloc, dalloc(&V.du_full, fn));
-        HIP_TRY(malloc, dalloc(&V.dv_full, fn));
+        GROW_N(V.Ih, mn);
+        GROW_N(V.du_full, fn);
+        GROW_N(V.dv_full, fn);
     }
     // one zero row past the image: getGain clamps its window to [0,H] INCLUSIVE like the reference
     // (matcher.cpp:362-371), whose read of row H is out of bounds; here it reads zeros
-    HIP_TRY(malloc, hipHostMalloc((void**)&V.stage, fn + bpl));
+    GROW_N(V.stage, fn + bpl);
     memset(V.stage + fn, 0, bpl);
-    HIP_TRY(malloc, dalloc(&V.cnt, 2));
+    GROW_N(V.cnt, 2);
     HIP_TRY(copy, hipMemsetAsync(V.cnt, 0, 2 * sizeof(int32_t), m->stream));
     HIP_TRY(wait, hipStreamSynchronize(m->stream));   // (re)allocation path only; the cameras use two streams
     int32_t ns = p.nms_n * 3;
@@ -515,8 +467,8 @@ static int size_view(svh_matcher* m, DevView& V, int32_t w, int32_t h, int32_t b
     const int32_t nn[2] = {ns, p.nms_n};
     for (int k = 0; k < 2; k++) {
         V.cap[k] = 4 * mnms_blocks(V.mw, nn[k], m->margin) * mnms_blocks(V.mh, nn[k], m->margin);
-        HIP_TRY(malloc, dalloc(&V.tab[k], (size_t)12 * V.cap[k]));
-        HIP_TRY(malloc, dalloc(&V.ids[k], (size_t)V.cap[k]));
+        GROW_N(V.tab[k], (size_t)12 * V.cap[k]);
+        GROW_N(V.ids[k], (size_t)V.cap[k]);
     }
     return SVH_OK;
 }
@@ -524,32 +476,21 @@ static int size_view(svh_matcher* m, DevView& V, int32_t w, int32_t h, int32_t b
 // scratch of the feature extraction (may run on the prefetch thread) and of the matching (the caller's thread):
 // two functions, so that neither side reads the other's bookkeeping
 static int ensure_feature_scratch(svh_matcher* m, int32_t slot_need) {
-    if (slot_need > m->slot_cap) {
-        m->slot_cap = 0;
-        for (int c = 0; c < 4; c++) {
-            HIP_TRY(malloc, drealloc(&m->slots[c], (size_t)slot_need));
-            HIP_TRY(malloc, drealloc(&m->flags[c], (size_t)slot_need + 4));
-            HIP_TRY(malloc, drealloc(&m->order[c], (size_t)slot_need));
-        }
-        m->slot_cap = slot_need;
+    if (slot_need <= 0) return SVH_OK;
+    for (int c = 0; c < 4; c++) {
+        GROW_N(m->slots[c], (size_t)slot_need);
+        GROW_N(m->flags[c], (size_t)slot_need + 4);
+        GROW_N(m->order[c], (size_t)slot_need);
     }
     return SVH_OK;
 }
 
 static int ensure_match_scratch(svh_matcher* m, int32_t pm_need, size_t owner_need) {
-    if (pm_need > m->pm_cap) {
-        m->pm_cap = 0;
-        HIP_TRY(malloc, drealloc(&m->pm_slots, (size_t)pm_need));
-        HIP_TRY(malloc, drealloc(&m->pm_out, (size_t)pm_need));
-        HIP_TRY(malloc, drealloc(&m->pm_flags, (size_t)pm_need));
-        m->pm_cap = pm_need;
-    }
-    if (!m->pm_count) HIP_TRY(malloc, dalloc(&m->pm_count, 2));
-    if (owner_need > m->owner_cap) {
-        m->owner_cap = 0;
-        HIP_TRY(malloc, drealloc(&m->pixel_owner, owner_need));
-        m->owner_cap = owner_need;
-    }
+    GROW_N(m->pm_slots, (size_t)pm_need);
+    GROW_N(m->pm_out, (size_t)pm_need);
+    GROW_N(m->pm_flags, (size_t)pm_need);
+    GROW_N(m->pm_count, 2);
+    SVH_HIP_GROW("Matcher", m->pixel_owner, owner_need * sizeof(int32_t));   // (0: no owner map, nothing allocated)
     return SVH_OK;
 }
 
@@ -636,11 +577,8 @@ static int ensure_bins(svh_matcher* m, DevView* const* views, int nviews, int32_
     for (int v = 0; v < nviews; v++) {
         DevView& V = *views[v];
         if (!V.valid || V.nbins == nb) continue;
-        if (nb > V.off_cap) {   // (re)allocate only when the bin grid grows: hipFree synchronises the device
-            V.off_cap = 0;
-            for (int k = 0; k < 2; k++) HIP_TRY(malloc, drealloc(&V.off[k], (size_t)nb + 1));
-            V.off_cap = nb;
-        }
+        // (re)allocated only when the bin grid grows: hipFree synchronises the device
+        for (int k = 0; k < 2; k++) GROW_N(V.off[k], (size_t)nb + 1);
         for (int k = 0; k < 2; k++) {
             J.table[nj] = V.tab[k];
             J.count[nj] = V.cnt + k;
@@ -652,11 +590,7 @@ static int ensure_bins(svh_matcher* m, DevView* const* views, int nviews, int32_
         V.nbins = nb;
     }
     if (!nj) return SVH_OK;
-    if (nb > m->cursor_cap) {
-        m->cursor_cap = 0;
-        HIP_TRY(malloc, drealloc(&m->cursor, (size_t)nb));
-        m->cursor_cap = nb;
-    }
+    GROW_N(m->cursor, (size_t)nb);
     mlaunch_bin_index(m->stream, J, nj, nmax, ub, vb, m->p.match_binsize, m->cursor);
     return SVH_OK;
 }
@@ -821,12 +755,8 @@ static int match_enqueue(svh_matcher* m, int dense, int32_t method, bool use_pri
     const int32_t nq = q.n[dense];
     int rc = ensure_match_scratch(m, std::max(nq, 1), method < 2 ? (size_t)P.width * P.height : 0);
     if (rc) return rc;
-    if (nq > m->h_pm_cap || !m->h_cnt) {
-        m->h_pm_cap = 0;
-        HIP_TRY(malloc, hrealloc(&m->h_pm, (size_t)std::max(nq, 1) * sizeof(svh_p_match)));
-        if (!m->h_cnt) HIP_TRY(malloc, hipHostMalloc((void**)&m->h_cnt, sizeof(int32_t)));
-        m->h_pm_cap = std::max(nq, 1);
-    }
+    GROW_N(m->h_pm, (size_t)nq);
+    GROW_N(m->h_cnt, 1);
     mlaunch_match(m->stream, P, view_of(m->prev[0], dense), view_of(m->prev[1], dense), view_of(m->cur[0], dense),
                   view_of(m->cur[1], dense), nq, m->ranges_dev, use_prior ? 1 : 0, m->pm_slots, m->pm_flags,
                   m->pixel_owner, m->pm_out, m->pm_count, m->h_cnt);
@@ -859,7 +789,7 @@ static void download_enqueue(svh_matcher* m, const MatchPass& mp) {
 
 static void match_collect(svh_matcher* m, const MatchPass& mp, std::vector<svh_p_match>& dst) {
     const int32_t count = std::max(0, std::min(*m->h_cnt, mp.nq));
-    dst.assign(m->h_pm, m->h_pm + count);
+    dst.assign(m->h_pm.p, m->h_pm.p + count);
 }
 
 static int run_matching(svh_matcher* m, int dense, int32_t method, bool use_prior, const double* Tr,
@@ -1016,25 +946,11 @@ void svh_matcher_destroy(svh_matcher* m) {
         (void)hipSetDevice(m->device);
         (void)hipStreamSynchronize(m->stream);
         if (m->stream2) (void)hipStreamSynchronize(m->stream2);
-        for (int k = 0; k < 2; k++) {
-            m->prev[k].release();
-            m->cur[k].release();
-            m->next[k].release();
-        }
-        for (int c = 0; c < 4; c++) {
-            (void)hipFree(m->slots[c]); (void)hipFree(m->flags[c]); (void)hipFree(m->order[c]);
-        }
-        (void)hipFree(m->cursor);
-        (void)hipFree(m->pm_slots);
-        (void)hipFree(m->pm_out); (void)hipFree(m->pm_flags); (void)hipFree(m->pm_count);
-        (void)hipFree(m->pixel_owner); (void)hipFree(m->ranges_dev);
-        (void)hipHostFree(m->h_pm); (void)hipHostFree(m->h_cnt);
-        (void)hipHostFree(m->h_n);
-        (void)hipHostFree(m->h_ranges);
-        (void)hipStreamDestroy(m->stream);
-        if (m->stream2) (void)hipStreamDestroy(m->stream2);
     }
-    delete m;
+    const hipStream_t s1 = m->stream, s2 = m->stream2;
+    delete m;   // the views and the scratch free themselves, on the device selected above
+    if (s1) (void)hipStreamDestroy(s1);
+    if (s2) (void)hipStreamDestroy(s2);
 }
 
 void svh_matcher_set_intrinsics(svh_matcher* m, double f, double cu, double cv, double base) {
@@ -1107,7 +1023,7 @@ static int32_t push_prepare(svh_matcher* m, const uint8_t* I1, const uint8_t* I2
     m->dims_c[0] = w;
     m->dims_c[1] = h;
     m->dims_c[2] = w + 16 - w % 16;   // +16 even when w % 16 == 0 (matcher.cpp:173)
-    if (!m->h_n) HIP_TRY(malloc, hipHostMalloc((void**)&m->h_n, 8 * sizeof(int32_t)));   // [4..7]: a prefetched frame's
+    GROW_N(m->h_n, 8);   // [4..7]: a prefetched frame's
     const uint8_t* src[2] = {I1, I2};
     for (int k = 0; k < 2; k++) {
         if (!src[k]) continue;
@@ -1171,7 +1087,7 @@ static int32_t prefetch_body(const std::vector<svh_matcher*>& ms, const std::vec
         HIP_TRY(none, hipSetDevice(m->device));
         if (!m->stream) HIP_TRY(none, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
         if (!m->stream2) HIP_TRY(none, hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
-        if (!m->h_n) HIP_TRY(malloc, hipHostMalloc((void**)&m->h_n, 8 * sizeof(int32_t)));
+        GROW_N(m->h_n, 8);
         m->dims_n[0] = w;
         m->dims_n[1] = h;
         m->dims_n[2] = w + 16 - w % 16;
@@ -1471,11 +1387,7 @@ static int32_t match_prepare(svh_matcher* m, int32_t ub, int32_t vb) {
     DevView* views[4] = {&m->prev[0], &m->prev[1], &m->cur[0], &m->cur[1]};
     const int rc = ensure_bins(m, views, 4, ub, vb);
     if (rc) return rc;
-    if (ub * vb > m->ranges_cap) {
-        m->ranges_cap = 0;
-        HIP_TRY(malloc, drealloc(&m->ranges_dev, (size_t)16 * ub * vb));
-        m->ranges_cap = ub * vb;
-    }
+    GROW_N(m->ranges_dev, (size_t)16 * ub * vb);
     return SVH_OK;
 }
 
@@ -1659,11 +1571,7 @@ int32_t svh_matcher_match_features_batch(svh_matcher* const* ms, int32_t K, int3
         for (int i = 0; i < n; i++) {
             svh_matcher* m = part[i];
             match_collect(m, mp[i], m->m1);
-            if (nr > m->h_ranges_cap) {
-                m->h_ranges_cap = 0;
-                HIP_TRY(malloc, hrealloc(&m->h_ranges, nr * sizeof(float)));
-                m->h_ranges_cap = nr;
-            }
+            SVH_HIP_GROW("Matcher", m->h_ranges, nr * sizeof(float));
         }
         rc = host_phase([&](int i) {
             svh_matcher* m = part[i];

@@ -32,6 +32,7 @@ using namespace svh;
 namespace {
 
 #define RECON_TRY(kind, expr) SVH_HIP_TRY("Reconstruction", kind, expr)
+#define RECON_GROW(buf, bytes) SVH_HIP_GROW("Reconstruction", buf, bytes)
 
 struct Track {                  // Reconstruction::track (reconstruction.h:79-84)
     std::vector<float> px;      // u, v per frame
@@ -58,51 +59,50 @@ struct svh_recon {
     // device side
     hipStream_t stream = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    double* d_frames = nullptr;                     // resident per-frame records
+    // (the cap_* are element counts: what the buffers were last asked to hold, and the base of the doubling)
+    HipBuf<double> d_frames;                        // resident per-frame records
     int32_t cap_frames = 0, dev_frames = 0;         // capacity / frames uploaded so far
-    float* d_points = nullptr;                      // resident point array, 3 floats per point
+    HipBuf<float> d_points;                         // resident point array, 3 floats per point
     int64_t cap_points = 0;
-    uint8_t *h_in = nullptr, *d_in = nullptr;       // [new frame records | offs | first | order | px]
+    PinnedBuf<uint8_t> h_in;                        // [new frame records | offs | first | order | px]
+    HipBuf<uint8_t> d_in;
     size_t cap_in = 0;
-    int32_t *d_code = nullptr, *h_code = nullptr;   // per lost track
-    float *d_xyz = nullptr, *h_xyz = nullptr;
-    int32_t cap_lost = -1;
-    int32_t* h_count = nullptr;
+    HipBuf<int32_t> d_code;                         // per lost track
+    PinnedBuf<int32_t> h_code;
+    HipBuf<float> d_xyz;
+    PinnedBuf<float> h_xyz;
+    size_t cap_lost = 0;
+    PinnedBuf<int32_t> h_count;
     // the resident form (svh_recon_create_resident, recon_internal.h): the tracks are a CSR in device memory, tb[cur]
     // holds them and tb[cur ^ 1] is written by an update; `tracks` stays empty
     bool resident = false;
     struct TrackBuf {
-        int32_t *first = nullptr, *last = nullptr, *offs = nullptr;
-        float* px = nullptr;
+        HipBuf<int32_t> first, last, offs;
+        HipBuf<float> px;
     } tb[2];
     int cur = 0;
     int32_t n_tracks = 0, cap_tracks = 0;
     int64_t cap_px = 0;
     int32_t idx_bound = 0;                          // every last_idx of the table is below it
-    int32_t *d_tidx = nullptr, *d_claim = nullptr, *d_midx = nullptr, *d_src = nullptr, *d_lost = nullptr;
-    int32_t* d_hdr = nullptr;
+    HipBuf<int32_t> d_tidx, d_claim, d_midx, d_src, d_lost, d_hdr;
     int32_t cap_tidx = 0, cap_midx = 0;
-    ReconJob *h_jobs = nullptr, *d_jobs = nullptr;  // job table of the updates this object leads
-    int32_t cap_jobs = 0;
+    PinnedBuf<ReconJob> h_jobs;                     // job table of the updates this object leads
+    HipBuf<ReconJob> d_jobs;
 };
 
 namespace {
 
 // a larger device array with the first `keep` bytes of the old one; the old one stays in place on any failure
 template <typename T>
-int regrow(svh_recon* r, T** p, size_t keep, size_t bytes) {
-    T* q = nullptr;
-    RECON_TRY(malloc, hipMalloc((void**)&q, bytes + 16));
+int regrow(svh_recon* r, HipBuf<T>& p, size_t keep, size_t bytes) {
+    HipBuf<T> q;
+    RECON_GROW(q, bytes + 16);
     if (keep) {
-        hipError_t e = hipMemcpyAsync(q, *p, keep, hipMemcpyDeviceToDevice, r->stream);
+        hipError_t e = hipMemcpyAsync(q.p, p.p, keep, hipMemcpyDeviceToDevice, r->stream);
         if (e == hipSuccess) e = (hipError_t)wait_stream(r->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(q);
-            return svh::hip_failed("Reconstruction", "hipMemcpyAsync(grow)", false, e);
-        }
+        if (e != hipSuccess) return svh::hip_failed("Reconstruction", "hipMemcpyAsync(grow)", false, e);
     }
-    (void)hipFree(*p);
-    *p = q;
+    p = std::move(q);
     return SVH_OK;
 }
 
@@ -116,45 +116,30 @@ int ensure(svh_recon* r, int32_t total_frames, int32_t new_frames, size_t lost, 
     }
     for (int i = 0; i < 2; i++)
         if (!r->ev[i]) RECON_TRY(none, hipEventCreate(&r->ev[i]));
-    if (!r->h_count) RECON_TRY(malloc, hipHostMalloc((void**)&r->h_count, 64));
+    RECON_GROW(r->h_count, 64);
     int rc;
     if (total_frames > r->cap_frames) {
         const int32_t cap = std::max(total_frames, std::max(64, 2 * r->cap_frames));
         const size_t rec = recon::FRAME_STRIDE * sizeof(double);
-        if ((rc = regrow(r, &r->d_frames, rec * (size_t)r->dev_frames, rec * (size_t)cap))) return rc;
+        if ((rc = regrow(r, r->d_frames, rec * (size_t)r->dev_frames, rec * (size_t)cap))) return rc;
         r->cap_frames = cap;
     }
     if ((int64_t)r->n_points + (int64_t)lost > r->cap_points) {
         const int64_t cap = std::max<int64_t>(r->n_points + (int64_t)lost, std::max<int64_t>(4096, 2 * r->cap_points));
-        if ((rc = regrow(r, &r->d_points, 12 * (size_t)r->n_points, 12 * (size_t)cap))) return rc;
+        if ((rc = regrow(r, r->d_points, 12 * (size_t)r->n_points, 12 * (size_t)cap))) return rc;
         r->cap_points = cap;
     }
     const size_t in = up16(recon::FRAME_STRIDE * sizeof(double) * (size_t)new_frames) + up16(4 * (3 * lost + 1) + 8 * px);
-    if (in > r->cap_in) {
-        // (capacity goes to 0 before anything is freed and back up only when both buffers exist)
-        const size_t cap = std::max(in, 2 * r->cap_in);
-        r->cap_in = 0;
-        (void)hipHostFree(r->h_in);
-        r->h_in = nullptr;
-        (void)hipFree(r->d_in);
-        r->d_in = nullptr;
-        RECON_TRY(malloc, hipHostMalloc((void**)&r->h_in, cap + 16));
-        RECON_TRY(malloc, hipMalloc((void**)&r->d_in, cap + 16));
-        r->cap_in = cap;
-    }
-    if ((int64_t)lost > (int64_t)r->cap_lost) {
-        const size_t cap = std::max(lost, (size_t)std::max(1024, 2 * std::max(r->cap_lost, 0)));
-        r->cap_lost = -1;
-        (void)hipFree(r->d_code); r->d_code = nullptr;
-        (void)hipFree(r->d_xyz); r->d_xyz = nullptr;
-        (void)hipHostFree(r->h_code); r->h_code = nullptr;
-        (void)hipHostFree(r->h_xyz); r->h_xyz = nullptr;
-        RECON_TRY(malloc, hipMalloc((void**)&r->d_code, 4 * cap + 16));
-        RECON_TRY(malloc, hipMalloc((void**)&r->d_xyz, 12 * cap + 16));
-        RECON_TRY(malloc, hipHostMalloc((void**)&r->h_code, 4 * cap + 16));
-        RECON_TRY(malloc, hipHostMalloc((void**)&r->h_xyz, 12 * cap + 16));
-        r->cap_lost = (int32_t)cap;
-    }
+    // (a buffer that a failed growth left empty is allocated again here: the owners know what they hold)
+    if (in > r->cap_in) r->cap_in = std::max(in, 2 * r->cap_in);
+    RECON_GROW(r->h_in, r->cap_in + 16);
+    RECON_GROW(r->d_in, r->cap_in + 16);
+    const size_t want = std::max<size_t>(lost, 1024);   // (the first update allocates even when nothing is lost)
+    if (want > r->cap_lost) r->cap_lost = std::max(want, 2 * r->cap_lost);
+    RECON_GROW(r->d_code, 4 * r->cap_lost + 16);
+    RECON_GROW(r->d_xyz, 12 * r->cap_lost + 16);
+    RECON_GROW(r->h_code, 4 * r->cap_lost + 16);
+    RECON_GROW(r->h_xyz, 12 * r->cap_lost + 16);
     return SVH_OK;
 }
 
@@ -222,7 +207,7 @@ int run_lost(svh_recon* r, const std::vector<int32_t>& lost, size_t n_px, const 
     const float* d_px = reinterpret_cast<const float*>(d_order + n_lost);
     const double t_launch = now_ms();
     if (r->timing) (void)hipEventRecord(r->ev[0], r->stream);
-    vlaunch_upload(r->stream, h, reinterpret_cast<uint8_t*>(r->d_frames) + rec * (size_t)r->dev_frames,
+    vlaunch_upload(r->stream, h, reinterpret_cast<uint8_t*>(r->d_frames.p) + rec * (size_t)r->dev_frames,
                    rec * (size_t)new_frames);   // (44 doubles: a multiple of 16 bytes)
     vlaunch_upload(r->stream, h + frames_bytes, r->d_in + frames_bytes, csr_bytes);
     r->h_count[0] = -1;
@@ -237,8 +222,8 @@ int run_lost(svh_recon* r, const std::vector<int32_t>& lost, size_t n_px, const 
     const int32_t count = r->h_count[0];
     if (count < r->n_points || count > r->n_points + n_lost)
         return svh::fail(SVH_ERR_HIP, "Reconstruction: the device returned an impossible point count");
-    r->codes.assign(r->h_code, r->h_code + n_lost);
-    r->xyz.assign(r->h_xyz, r->h_xyz + 3 * (size_t)n_lost);
+    r->codes.assign(r->h_code.p, r->h_code.p + n_lost);
+    r->xyz.assign(r->h_xyz.p, r->h_xyz.p + 3 * (size_t)n_lost);
     r->n_points = count;
     r->dev_frames = total_frames;
     if (r->timing) {
@@ -279,7 +264,7 @@ int ensure_resident(svh_recon* r, int32_t n, int32_t tbl, bool host_matches) {
     // the staging pair h_in / d_in -- its CSR part carries the matches here, 48 n bytes = 8 bytes x 6 n "pixels"
     int rc = ensure(r, total_frames, total_frames - r->dev_frames, (size_t)r->n_tracks, host_matches ? 6 * (size_t)n : 0);
     if (rc) return rc;
-    if (!r->d_hdr) RECON_TRY(malloc, hipMalloc((void**)&r->d_hdr, 4 * RT_HDR + 16));
+    RECON_GROW(r->d_hdr, 4 * RT_HDR + 16);
     const int64_t need_tracks = (int64_t)r->n_tracks + n, need_px = (int64_t)r->total_px + 2 * (int64_t)n;
     if (need_tracks > INT32_MAX / 4 || need_px > INT32_MAX / 4)
         return svh::fail(SVH_ERR_BAD_ARG, "Reconstruction: the track table would exceed 2^29 entries");
@@ -289,43 +274,38 @@ int ensure_resident(svh_recon* r, int32_t n, int32_t tbl, bool host_matches) {
         for (int b = 0; b < 2; b++) {
             const bool a = b == r->cur;
             svh_recon::TrackBuf& t = r->tb[b];
-            if ((rc = regrow(r, &t.first, a ? keep : 0, 4 * cap))) return rc;
-            if ((rc = regrow(r, &t.last, a ? keep : 0, 4 * cap))) return rc;
-            if ((rc = regrow(r, &t.offs, a && r->n_tracks ? keep + 4 : 0, 4 * (cap + 1)))) return rc;
+            if ((rc = regrow(r, t.first, a ? keep : 0, 4 * cap))) return rc;
+            if ((rc = regrow(r, t.last, a ? keep : 0, 4 * cap))) return rc;
+            if ((rc = regrow(r, t.offs, a && r->n_tracks ? keep + 4 : 0, 4 * (cap + 1)))) return rc;
         }
-        if ((rc = regrow(r, &r->d_claim, 0, 4 * cap))) return rc;
-        if ((rc = regrow(r, &r->d_src, 0, 4 * cap))) return rc;
-        if ((rc = regrow(r, &r->d_lost, 0, 4 * cap))) return rc;
+        if ((rc = regrow(r, r->d_claim, 0, 4 * cap))) return rc;
+        if ((rc = regrow(r, r->d_src, 0, 4 * cap))) return rc;
+        if ((rc = regrow(r, r->d_lost, 0, 4 * cap))) return rc;
         r->cap_tracks = (int32_t)cap;
     }
     if (need_px > r->cap_px) {
         const int64_t cap = std::max<int64_t>(need_px, std::max<int64_t>(16384, 2 * r->cap_px));
         for (int b = 0; b < 2; b++)
-            if ((rc = regrow(r, &r->tb[b].px, b == r->cur ? 8 * r->total_px : 0, 8 * (size_t)cap))) return rc;
+            if ((rc = regrow(r, r->tb[b].px, b == r->cur ? 8 * r->total_px : 0, 8 * (size_t)cap))) return rc;
         r->cap_px = cap;
     }
     if (tbl > r->cap_tidx) {
         const int32_t cap = std::max(tbl, std::max(4096, 2 * r->cap_tidx));
-        if ((rc = regrow(r, &r->d_tidx, 0, 4 * (size_t)cap))) return rc;
+        if ((rc = regrow(r, r->d_tidx, 0, 4 * (size_t)cap))) return rc;
         r->cap_tidx = cap;
     }
     if (n > r->cap_midx) {
         const int32_t cap = std::max(n, std::max(4096, 2 * r->cap_midx));
-        if ((rc = regrow(r, &r->d_midx, 0, 4 * (size_t)cap))) return rc;
+        if ((rc = regrow(r, r->d_midx, 0, 4 * (size_t)cap))) return rc;
         r->cap_midx = cap;
     }
     return SVH_OK;
 }
 
 int ensure_jobs(svh_recon* lead, int32_t K) {
-    if (K <= lead->cap_jobs) return SVH_OK;
-    const int32_t cap = std::max(K, 16);
-    lead->cap_jobs = 0;
-    (void)hipHostFree(lead->h_jobs); lead->h_jobs = nullptr;
-    (void)hipFree(lead->d_jobs); lead->d_jobs = nullptr;
-    RECON_TRY(malloc, hipHostMalloc((void**)&lead->h_jobs, sizeof(ReconJob) * (size_t)cap));
-    RECON_TRY(malloc, hipMalloc((void**)&lead->d_jobs, sizeof(ReconJob) * (size_t)cap));
-    lead->cap_jobs = cap;
+    const size_t bytes = sizeof(ReconJob) * (size_t)std::max(K, 16);
+    RECON_GROW(lead->h_jobs, bytes);
+    RECON_GROW(lead->d_jobs, bytes);
     return SVH_OK;
 }
 
@@ -355,7 +335,7 @@ ReconJob make_job(const ResidentUpdate& u, const recon::Settings& s) {
     j.code = r->d_code; j.xyz = r->d_xyz; j.points = r->d_points;
     j.out_hdr = r->h_count; j.out_code = r->h_code; j.out_xyz = r->h_xyz;
     j.up_src[0] = r->h_in;
-    j.up_dst[0] = reinterpret_cast<uint8_t*>(r->d_frames) + rec * (size_t)r->dev_frames;
+    j.up_dst[0] = reinterpret_cast<uint8_t*>(r->d_frames.p) + rec * (size_t)r->dev_frames;
     j.up_bytes[0] = (uint32_t)(rec * (size_t)new_frames);   // (44 doubles: a multiple of 16 bytes)
     if (u.host && u.n > 0) {
         memcpy(r->h_in + frames_bytes, u.host, sizeof(svh_p_match) * (size_t)u.n);
@@ -417,8 +397,8 @@ void resident_commit(const ResidentUpdate& u) {
     r->n_tracks = h[RT_EXTENDED] + h[RT_CREATED];
     r->total_px = (size_t)h[RT_PIXELS];
     r->idx_bound = u.max_index;
-    r->codes.assign(r->h_code, r->h_code + n_lost);
-    r->xyz.assign(r->h_xyz, r->h_xyz + 3 * (size_t)n_lost);
+    r->codes.assign(r->h_code.p, r->h_code.p + n_lost);
+    r->xyz.assign(r->h_xyz.p, r->h_xyz.p + 3 * (size_t)n_lost);
     r->n_points = h[RT_POINTS];
     r->dev_frames = (int32_t)r->Tr_total.size();
 }
@@ -527,16 +507,7 @@ void svh_recon_destroy(svh_recon* r) {
     }
     for (int i = 0; i < 2; i++)
         if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
-    (void)hipFree(r->d_frames); (void)hipFree(r->d_points); (void)hipFree(r->d_in); (void)hipFree(r->d_code);
-    (void)hipFree(r->d_xyz);
-    for (int b = 0; b < 2; b++) {
-        (void)hipFree(r->tb[b].first); (void)hipFree(r->tb[b].last); (void)hipFree(r->tb[b].offs);
-        (void)hipFree(r->tb[b].px);
-    }
-    (void)hipFree(r->d_tidx); (void)hipFree(r->d_claim); (void)hipFree(r->d_midx); (void)hipFree(r->d_src);
-    (void)hipFree(r->d_lost); (void)hipFree(r->d_hdr); (void)hipFree(r->d_jobs); (void)hipHostFree(r->h_jobs);
-    (void)hipHostFree(r->h_in); (void)hipHostFree(r->h_code); (void)hipHostFree(r->h_xyz); (void)hipHostFree(r->h_count);
-    delete r;
+    delete r;   // the buffers free themselves, on the device selected above
 }
 
 int32_t svh_recon_set_calibration(svh_recon* r, double f, double cu, double cv) {

@@ -453,17 +453,42 @@ def test_vo_lockstep_pipelined_loop(svhip, kind):
 
 
 # ---------------------------------------------------------------- fresh objects: the first allocations of an object
-def expect_injected(svhip, capfd, call):
-    """call() fails with SVH_ERR_HIP (raised, or returned by the plain ctypes drivers), the message names an injected
-    failure, one line went to stderr"""
+def fails_injected(svhip, capfd, call):
+    """False: call() succeeded.  True: it failed as an injected failure must: SVH_ERR_HIP (raised, or returned by
+    the plain ctypes drivers), the message names an injected failure, one line went to stderr"""
     capfd.readouterr()
     try:
         rc = call()
     except svhip.SvhError as err:
         rc = err.code
+    if not rc:
+        return False
     assert rc == svhip.ERR_HIP, rc
     assert "injected failure" in svhip.last_error(), svhip.last_error()
     assert capfd.readouterr().err.count("svhip:") == 1
+    return True
+
+
+def expect_injected(svhip, capfd, call):
+    assert fails_injected(svhip, capfd, call)
+
+
+def walk_first_allocations(svhip, capfd, fresh, first_call, same_as_clean, floor, last):
+    """malloc:1, malloc:2, ... each before the first call of a new object, up to the first position at which the
+    armed call succeeds: every failing call fails as an injected failure must, and the same object, disarmed, then
+    gives what a clean one gives.  At least `floor` positions fail (read off the allocations of the first call), the
+    walk ends by n = `last`.  The hook does not issue the armed call: nothing here faults the device."""
+    for n in range(1, last + 1):
+        obj = fresh()
+        arm(svhip, "malloc:%d" % n)
+        failed = fails_injected(svhip, capfd, lambda: first_call(obj))
+        arm(svhip, "")
+        if not failed:
+            print("first allocations: %d failing positions" % (n - 1))
+            assert n - 1 >= floor, (n - 1, floor)
+            return
+        same_as_clean(obj, n)
+    pytest.fail("the first call still fails with malloc:%d armed" % last)
 
 
 def test_fresh_matcher_first_allocation(svhip, capfd):
@@ -485,6 +510,75 @@ def test_fresh_matcher_first_allocation(svhip, capfd):
     m.match(2)
     got = m.matches()
     assert len(got) == len(want) and (got == want).all()
+
+
+def test_fresh_matcher_walk_over_first_allocations(svhip, capfd):
+    """every allocation of a new Matcher's first pushBack.  Floor: its two views make at least 11 allocations each in
+    size_view (the image, four filter planes, the pinned stage, the counters, two tables with their ids)"""
+    prm = H.matcher_defaults()
+    im = quad()
+    clean = plain_matcher(prm)
+    clean.push_back(im[0], im[1])
+    clean.push_back(im[2], im[3])
+    clean.match(2)
+    want = clean.matches().copy()
+
+    def same_as_clean(m, n):
+        m.push_back(im[0], im[1])
+        m.push_back(im[2], im[3])
+        m.match(2)
+        got = m.matches()
+        assert len(got) == len(want) and (got == want).all(), n
+
+    walk_first_allocations(svhip, capfd, lambda: plain_matcher(prm), lambda m: m.push_back(im[0], im[1]),
+                           same_as_clean, floor=22, last=80)
+
+
+def test_fresh_map_walk_over_first_allocations(svhip, capfd):
+    """every allocation of a new map object's first svh_map_add.  Floor: map_ensure makes 2 x (5 planes + 1 point
+    list) + 7 others = 19"""
+    import test_map as M
+    from svhip import mapper
+    (f, cu, cv, base), frames = M.synth_frames(65, 33, 2, seed=4)
+
+    def fused(g):
+        for d, img, Ht, gain in frames:
+            g.add(d, img, Ht, gain)
+        return [g.points(which) for which in (0, 1)]
+
+    want = fused(mapper.Mapper(f, cu, cv, base, 20))
+    assert len(want[0]) > 0 and len(want[1]) > 0
+
+    def same_as_clean(g, n):
+        for a, b in zip(want, fused(g)):
+            assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32)), n
+
+    d, img, Ht, gain = frames[0]
+    walk_first_allocations(svhip, capfd, lambda: mapper.Mapper(f, cu, cv, base, 20),
+                           lambda g: g.add(d, img, Ht, gain), same_as_clean, floor=19, last=40)
+
+
+def test_fresh_recon_walk_over_first_allocations(svhip, capfd):
+    """every allocation of a new host-table Reconstruction's first update.  Floor: ensure makes 8 on a first call --
+    the pinned header, the frame records, the staging pair, and the four per-lost-track buffers (no point array
+    yet: nothing can be lost before there is a track)"""
+    import recon_ref as R
+    import test_recon_gpu as T
+    with np.load(R.GOLDEN) as z:
+        Z = {k: z[k] for k in z.files}
+
+    def first_update(run):
+        Tr, m = run.scene[0]
+        return run.rec.update(R.to_p_match(m), Tr, *[t(v) for t, v in zip((int, int, float, float), run.s)])
+
+    def same_as_clean(run, n):
+        assert (run.rec.num_tracks(), run.rec.num_points()) == (0, 0), n
+        run.run()     # (every step against the reference's run)
+        assert run.rec.points().tobytes() == Z["synth_1_points"].tobytes(), n
+        run.rec.close()
+
+    walk_first_allocations(svhip, capfd, lambda: T.Runner(svhip, Z, "synth", 1), first_update, same_as_clean,
+                           floor=8, last=20)
 
 
 def test_fresh_stereo_vo_first_allocation(svhip, capfd):
