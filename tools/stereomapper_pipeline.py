@@ -9,7 +9,12 @@ i.e. what ReadFromFilesThread, VisualOdometryThread and StereoThread do between 
 (readfromfilesthread.cpp:25-112, visualodometrythread.cpp:95-140, stereothread.cpp:62-170),
 without the GUI.  Usage:
 
-    python tools/stereomapper_pipeline.py <drive_dir> <calib_cam_to_cam.txt> [max_frames]
+    python tools/stereomapper_pipeline.py [--unrectified] <drive_dir> <calib_cam_to_cam.txt> [max_frames]
+
+--unrectified: the drive holds RAW frames (KITTI's "extract" drives, S_xx pixels).  They are uploaded once and rectified
+on the device with K_xx, D_xx, R_rect_xx, P_rect_xx of cameras 0 and 1 (include/svh_rectify.h; what
+framecapturethread.cpp:100-131, 328-349 does with OpenCV), ELAS reads the rectified pair where it lies, and one copy
+back feeds svh_vo_process, which takes host images.
 
 Python is glue here (ctypes over libsvhip.so); the pose accumulation H_total = H_total * inv(H_delta)
 uses numpy where the reference uses Matrix::solve."""
@@ -50,7 +55,7 @@ class DeviceBuffer:
 
 
 class Pipeline:
-    def __init__(self, f, cu, cv, base, elas_params=None, max_dist=20.0):
+    def __init__(self, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None):
         import helpers as Hh
         import svhip as S
         from svhip import mapper
@@ -61,13 +66,33 @@ class Pipeline:
         self.H_total = np.eye(4)
         self.buf = None
         self.poses = []
+        self.rect = None
+        if rectify_params is not None:
+            from svhip import rectify
+            self.rect = rectify.Rectifier(rectify_params)
+            self.raw = None
 
     def push(self, I1, I2):
         """one stereo frame; returns (vo_ok, points_prev, points_curr)"""
-        h, w = I1.shape
+        if self.rect is not None:
+            sh, sw = I1.shape
+            h, w = self.rect.dst_shape
+        else:
+            h, w = I1.shape
         n = w * h
         if self.buf is None or self.buf[0].nbytes != n:
             self.buf = [DeviceBuffer(n), DeviceBuffer(n), DeviceBuffer(4 * n), DeviceBuffer(4 * n)]
+        if self.rect is not None:
+            # framecapturethread.cpp:328-349: the raw pair goes up once, is rectified where ELAS will read it, and comes
+            # back once for the visual odometry
+            if self.raw is None:
+                self.raw = [DeviceBuffer(sw * sh), DeviceBuffer(sw * sh)]
+            self.raw[0].upload(I1)
+            self.raw[1].upload(I2)
+            self.rect.pairs_device(1, self.raw[0].ptr.value, self.raw[1].ptr.value, sw, sw * sh,
+                                   self.buf[0].ptr.value, self.buf[1].ptr.value, w, n)
+            I1 = self.buf[0].download(np.empty((h, w), np.uint8))
+            I2 = self.buf[1].download(np.empty((h, w), np.uint8))
         # visualodometrythread.cpp:100-137
         ok = self.vo.process(I1, I2) == 1
         gain = 0.0
@@ -81,8 +106,9 @@ class Pipeline:
         self.poses.append(self.H_total.copy())
         # stereothread.cpp:62-115: ELAS with the disparity maps left on the device
         dI1, dI2, dD1, dD2 = self.buf
-        dI1.upload(I1)
-        dI2.upload(I2)
+        if self.rect is None:
+            dI1.upload(I1)
+            dI2.upload(I2)
         st = self.elas.process_batch_device(1, dI1.ptr.value, dI2.ptr.value, n, dD1.ptr.value, dD2.ptr.value,
                                             4 * n, w, h, w)
         if st[0] != 0:
@@ -93,12 +119,19 @@ class Pipeline:
 
 
 def main():
+    unrectified = "--unrectified" in sys.argv
+    if unrectified:
+        sys.argv.remove("--unrectified")
     if len(sys.argv) < 3:
         raise SystemExit(__doc__)
     from svhip import kitti
     calib = kitti.read_cam_to_cam(sys.argv[2])
     limit = int(sys.argv[3]) if len(sys.argv) > 3 else 1 << 30
-    p = Pipeline(calib.f, calib.cu, calib.cv, calib.base)
+    rp = None
+    if unrectified:
+        from svhip import rectify
+        rp = rectify.params_from_kitti(calib, 0, 1)
+    p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp)
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
