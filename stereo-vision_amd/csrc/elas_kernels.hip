@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "dev_common.h"
 #include "svh_internal.h"
 
 namespace svh {
@@ -118,8 +119,6 @@ __device__ __forceinline__ uint32_t texture16(const uint4& a) {
     const uint4 mid = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
     return sad16(a, mid);
 }
-
-__device__ __forceinline__ int32_t sat_u8(int32_t x) { return x < 0 ? 0 : (x > 255 ? 255 : x); }
 
 // (uint32_t)f assigned to int32_t with x86 cvttss2si semantics (elas.cpp:1081-1082)
 __device__ __forceinline__ int32_t f2u2i(float f) { return (int32_t)(uint32_t)(long long)f; }
@@ -270,23 +269,10 @@ __global__ __launch_bounds__(256) void k_descriptor_stream(DevImages img, int W,
 // The planes live at the start of the pair's descriptor buffer: slot z = 2 pair + image holds du at +0 and dv at
 // + H * pitch, pitch = roundup(W, 4) + 16, column x at byte 8 + x (so the words x-4 .. x+7 of a row always exist).
 // ---------------------------------------------------------------------------
-typedef short s16x2 __attribute__((ext_vector_type(2)));
+// (s16x2 and the packed-pair helpers pk_* are dev_common.h's)
 typedef uint32_t u32_unaligned_t __attribute__((aligned(1)));
-__device__ __forceinline__ s16x2 dp_pair01(uint32_t w) { return __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, w, 0x0c010c00u)); }
-__device__ __forceinline__ s16x2 dp_pair23(uint32_t w) { return __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, w, 0x0c030c02u)); }
-// (a.hi, b.lo): the pair one column to the right of a, b being the next pair
-__device__ __forceinline__ s16x2 dp_mid(s16x2 a, s16x2 b) {
-    return __builtin_bit_cast(s16x2, __builtin_amdgcn_alignbyte(__builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, a), 2u));
-}
 __device__ __forceinline__ s16x2 dp_prev(s16x2 v) { return __builtin_bit_cast(s16x2, lane_prev(__builtin_bit_cast(int, v))); }
 __device__ __forceinline__ s16x2 dp_next(s16x2 v) { return __builtin_bit_cast(s16x2, lane_next(__builtin_bit_cast(int, v))); }
-__device__ __forceinline__ s16x2 dp_sobel_out(s16x2 v) {   // sat_u8((v >> 2) + 128)
-    const s16x2 lo = {0, 0}, hi = {255, 255}, off = {128, 128};
-    return __builtin_elementwise_min(__builtin_elementwise_max((v >> 2) + off, lo), hi);
-}
-__device__ __forceinline__ uint32_t dp_bytes(s16x2 lo, s16x2 hi) {   // low bytes of four 16-bit values -> one word
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x06040200u);
-}
 // v_perm_b32 selector bytes: 0..3 = bytes of `lo` (second operand), 4..7 = bytes of `hi` (first operand)
 #define DP_SEL(b0, b1, b2, b3) ((uint32_t)(b0) | (uint32_t)(b1) << 8 | (uint32_t)(b2) << 16 | (uint32_t)(b3) << 24)
 
@@ -330,17 +316,17 @@ __global__ __launch_bounds__(256) void k_sobel_planes(DevImages img, int W, int 
 #pragma unroll
         for (int k = 0; k < kChunk; k++) {
             const int r = r0 + k;
-            const s16x2 p0 = dp_pair01(px[k]), p1 = dp_pair23(px[k]);
+            const s16x2 p0 = pk_bytes01(px[k]), p1 = pk_bytes23(px[k]);
             const s16x2 two = {2, 2};
             const s16x2 S0 = a2[0] + two * a1[0] + p0, S1 = a2[1] + two * a1[1] + p1;
             const s16x2 T0 = a2[0] - p0, T1 = a2[1] - p1;
             a2[0] = a1[0]; a2[1] = a1[1];
             a1[0] = p0; a1[1] = p1;
             const s16x2 SL = dp_prev(S1), SR = dp_next(S0), TL = dp_prev(T1), TR = dp_next(T0);
-            const s16x2 Sm0 = dp_mid(SL, S0), Sm1 = dp_mid(S0, S1), Sm2 = dp_mid(S1, SR);
-            const s16x2 Tm0 = dp_mid(TL, T0), Tm1 = dp_mid(T0, T1), Tm2 = dp_mid(T1, TR);
-            const uint32_t Dw = dp_bytes(dp_sobel_out(Sm0 - Sm1), dp_sobel_out(Sm1 - Sm2));
-            const uint32_t Vw = dp_bytes(dp_sobel_out(Tm0 + two * T0 + Tm1), dp_sobel_out(Tm1 + two * T1 + Tm2));
+            const s16x2 Sm0 = pk_mid(SL, S0), Sm1 = pk_mid(S0, S1), Sm2 = pk_mid(S1, SR);
+            const s16x2 Tm0 = pk_mid(TL, T0), Tm1 = pk_mid(T0, T1), Tm2 = pk_mid(T1, TR);
+            const uint32_t Dw = pk_to_bytes(pk_sobel_out<2>(Sm0 - Sm1), pk_sobel_out<2>(Sm1 - Sm2));
+            const uint32_t Vw = pk_to_bytes(pk_sobel_out<2>(Tm0 + two * T0 + Tm1), pk_sobel_out<2>(Tm1 + two * T1 + Tm2));
             const int c = r - 1;
             if (writes && c >= ys && c < ys + SP_ROWS && c < H) {
                 *reinterpret_cast<uint32_t*>(du + (size_t)c * pitch) = Dw;

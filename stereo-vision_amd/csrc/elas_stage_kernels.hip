@@ -47,6 +47,7 @@
 
 #include <algorithm>
 
+#include "dev_common.h"
 #include "svh_internal.h"
 #include "dt_core.h"
 
@@ -55,30 +56,6 @@ namespace svh {
 namespace {
 
 constexpr int16_t kInv = -32768;   // lattice cell that never held a candidate
-
-// exclusive prefix sum over the block (kT threads); *total = sum of all.  s_tmp: kT/64 + 1 ints
-template <int kT>
-__device__ __forceinline__ int block_excl_scan(int v, int* s_tmp, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();   // s_tmp may still be read from a previous call
-    if (lane == 63) s_tmp[wave] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kT / 64; w++) {
-        const int t = s_tmp[w];
-        if (w < wave) base += t;
-        tot += t;
-    }
-    *total = tot;
-    return base + inc - v;
-}
 
 struct LatticeParams {
     int W, H, Wc, Hc, step, ws, thr, need, add_corners, sup_cap;
@@ -335,7 +312,7 @@ __global__ __launch_bounds__(512) void k_lattice(StageDev S, LatticeParams P) {
         mine += val[vc * Wc + uc] >= 0;
     }
     int n = 0;
-    int pos = block_excl_scan<512>(mine, s_scan, &n);
+    int pos = block_exclusive_scan<512>(mine, s_scan, &n);
     int32_t* sup = S.sup_raw + (size_t)pair * 3 * P.sup_cap;
     const bool room = n + (P.add_corners ? 6 : 0) <= P.sup_cap;
     if (room)
@@ -565,7 +542,7 @@ __global__ __launch_bounds__(kT) void k_delaunay(StageDev S, DtParams P) {
         int sum = 0;
         for (int i = a; i < b; i++) sum += h[i];
         int tot;
-        int run = block_excl_scan<kT>(sum, s_scan, &tot);
+        int run = block_exclusive_scan<kT>(sum, s_scan, &tot);
         for (int i = a; i < b; i++) {
             run += h[i];
             h[i] = run;
@@ -713,7 +690,7 @@ __global__ __launch_bounds__(kT) void k_delaunay(StageDev S, DtParams P) {
         }
         if (!__syncthreads_or(split)) break;
         int tot;
-        int run = block_excl_scan<kT>(cnt, s_scan, &tot);
+        int run = block_exclusive_scan<kT>(cnt, s_scan, &tot);
         for (int i = c0; i < c1; i++) {
             int s, n;
             dt_segment(m, depth, i, &s, &n);
@@ -806,7 +783,7 @@ __global__ __launch_bounds__(kT) void k_delaunay(StageDev S, DtParams P) {
         live += (v.x >= 0) & (v.y >= 0) & (v.z >= 0);
     }
     int tot;
-    block_excl_scan<kT>(live, s_scan, &tot);
+    block_exclusive_scan<kT>(live, s_scan, &tot);
     if (tid == 0) S.counts->ntri[slot] = tot;
     STAMP(30);
 #undef STAMP
@@ -868,7 +845,7 @@ __global__ __launch_bounds__(256) void k_stage_pack(StageDev S, DtParams P, int 
         live += (v.x >= 0) & (v.y >= 0) & (v.z >= 0);
     }
     int tot;
-    int pos = block_excl_scan<256>(live, s_scan, &tot);
+    int pos = block_exclusive_scan<256>(live, s_scan, &tot);
     int32_t* out = tri + 3 * (size_t)tri_off;
     for (int t = a; t < b; t++) {
         const int4 v = *reinterpret_cast<const int4*>(ids + 4 * (size_t)t);

@@ -37,6 +37,8 @@ struct MatchParams {
     double tr[12];                // rows 0..2 of Tr_delta
 };
 
+// pinned host -> device copy by a kernel (bytes is a multiple of 16); the visual-odometry and reconstruction engines
+// upload through it as well
 void mlaunch_upload(void* stream, const uint8_t* pinned, uint8_t* dev, size_t bytes);
 // small transfers (a multiple of 4 bytes) between pinned host and device memory: hipMemcpyAsync / hipMemsetAsync,
 // or -- while a batch is being recorded (batch_rec.h) -- jobs of one copy / fill kernel per phase

@@ -12,18 +12,34 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 
-#include "batch_rec.h"
+#include "job_kernel.h"
 #include "matcher_internal.h"
 
 namespace svh {
 
 namespace {
 
-__device__ __forceinline__ int32_t sat_u8(int32_t x) { return x < 0 ? 0 : (x > 255 ? 255 : x); }
+// Every kernel below is a job struct with its globalise, a __device__ body, and one SVH_JOB_KERNEL line (job_kernel.h)
+// that makes the plain and the batched entry.  A body keeps its own parameter list and is reached through an overload
+// that takes the job struct: __restrict__ holds on function parameters only (the compiler drops it on struct members
+// and on locals), and without it the single-object kernels come out differently (k_filters<true>: three instructions
+// more, one register fewer; k_nms, k_feature_records, k_match_dedupe, k_refine_parabolic likewise).
+__device__ __forceinline__ FeatView gview(const FeatView& v) {
+    FeatView o;
+    o.rec = as_global(v.rec); o.count = as_global(v.count); o.off = as_global(v.off); o.ids = as_global(v.ids);
+    return o;
+}
+__device__ __forceinline__ SobelView gview(const SobelView& v) {
+    SobelView o = v;
+    o.du = as_global(v.du); o.dv = as_global(v.dv);
+    return o;
+}
 
 // ---------------------------------------------------------------------------
 // M1  Matcher::createHalfResolutionImage   libviso2/src/matcher.cpp:760-776
 // ---------------------------------------------------------------------------
+struct HalfJob { const uint8_t* I; int bpl; uint8_t* out; int hw, hh, hbpl; };
+__device__ __forceinline__ HalfJob globalise(HalfJob a) { all_global(a.I, a.out); return a; }
 __device__ __forceinline__ void d_half(const uint8_t* __restrict__ I, int bpl,
                                               uint8_t* __restrict__ out, int hw, int hh, int hbpl, unsigned bx, unsigned by) {
     const int x = bx * 64 + threadIdx.x;
@@ -33,6 +49,10 @@ __device__ __forceinline__ void d_half(const uint8_t* __restrict__ I, int bpl,
     const uint8_t* r1 = r0 + bpl;
     out[(size_t)y * hbpl + x] = (uint8_t)(((int)r0[0] + r0[1] + r1[0] + r1[1]) / 4);
 }
+__device__ __forceinline__ void d_half(const HalfJob& a, unsigned bx, unsigned by) {
+    d_half(a.I, a.bpl, a.out, a.hw, a.hh, a.hbpl, bx, by);
+}
+SVH_JOB_KERNEL(kd_half, , k_half, k_half_b, HalfJob, 64, 4, d_half, true)
 
 // ---------------------------------------------------------------------------
 // M2  filter::sobel5x5   libviso2/src/filter.cpp:474 (+306-361, 154-222, 93-152)
@@ -48,23 +68,9 @@ __device__ __forceinline__ void d_half(const uint8_t* __restrict__ I, int bpl,
 // Defined on rows 2..h-3, cols 2..w-3 (0 elsewhere), which covers everything the matcher ever reads.
 // ---------------------------------------------------------------------------
 constexpr int FX = 64, FR = 8;   // a block of 64x4 threads covers 256 columns x 32 rows
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ s16x2 pk_bytes01(uint32_t w) { return __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, w, 0x0c010c00u)); }
-__device__ __forceinline__ s16x2 pk_bytes23(uint32_t w) { return __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, w, 0x0c030c02u)); }
-// (a.hi, b.lo): the pair one column to the right of a, given the next pair b
-__device__ __forceinline__ s16x2 pk_mid(s16x2 a, s16x2 b) {
-    return __builtin_bit_cast(s16x2, __builtin_amdgcn_alignbyte(__builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, a), 2u));
-}
-// four values in two pairs -> their low bytes in one word
-__device__ __forceinline__ uint32_t pk_to_bytes(s16x2 lo, s16x2 hi) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x06040200u);
-}
-__device__ __forceinline__ s16x2 pk_sobel_out(s16x2 v) {   // sat_u8((v >> 7) + 128)
-    const s16x2 lo = {0, 0}, hi = {255, 255}, off = {128, 128};
-    return __builtin_elementwise_min(__builtin_elementwise_max((v >> 7) + off, lo), hi);
-}
-
+// (the packed-pair helpers pk_* are dev_common.h's)
+struct FiltersJob { const uint8_t* I; int w, h, bpl; uint8_t *du, *dv; int16_t *f1, *f2; };
+__device__ __forceinline__ FiltersJob globalise(FiltersJob a) { all_global(a.I, a.du, a.dv, a.f1, a.f2); return a; }
 template <bool kFeatures>
 __device__ __forceinline__ void d_filters(const uint8_t* __restrict__ I, int w, int h, int bpl,
                                                  uint8_t* __restrict__ du, uint8_t* __restrict__ dv,
@@ -120,8 +126,8 @@ __device__ __forceinline__ void d_filters(const uint8_t* __restrict__ I, int w, 
         const s16x2 dv_a = (T[0] + T[2]) + four * (Tm01 + Tm12) + six * T[1];
         const s16x2 dv_b = (T[1] + T[3]) + four * (Tm12 + Tm23) + six * T[2];
         const size_t o = (size_t)y * bpl + x;
-        *reinterpret_cast<uint32_t*>(du + o) = pk_to_bytes(pk_sobel_out(du_a), pk_sobel_out(du_b)) & keep;
-        *reinterpret_cast<uint32_t*>(dv + o) = pk_to_bytes(pk_sobel_out(dv_a), pk_sobel_out(dv_b)) & keep;
+        *reinterpret_cast<uint32_t*>(du + o) = pk_to_bytes(pk_sobel_out<7>(du_a), pk_sobel_out<7>(du_b)) & keep;
+        *reinterpret_cast<uint32_t*>(dv + o) = pk_to_bytes(pk_sobel_out<7>(dv_a), pk_sobel_out<7>(dv_b)) & keep;
         if (kFeatures) {
             const s16x2 Am01 = pk_mid(V5[0], V5[1]), Am12 = pk_mid(V5[1], V5[2]), Am23 = pk_mid(V5[2], V5[3]);
             const s16x2 Bm01 = pk_mid(V3[0], V3[1]), Bm12 = pk_mid(V3[1], V3[2]), Bm23 = pk_mid(V3[2], V3[3]);
@@ -142,6 +148,26 @@ __device__ __forceinline__ void d_filters(const uint8_t* __restrict__ I, int w, 
             *reinterpret_cast<uint2*>(f1 + o) = o1;
             *reinterpret_cast<uint2*>(f2 + o) = o2;
         }
+    }
+}
+template <bool kFeatures>
+__device__ __forceinline__ void d_filters(const FiltersJob& a, unsigned bx, unsigned by) {
+    d_filters<kFeatures>(a.I, a.w, a.h, a.bpl, a.du, a.dv, a.f1, a.f2, bx, by);
+}
+template <bool kFeatures> __global__ void k_filters(FiltersJob a);
+template <bool kFeatures> __global__ void k_filters_b(const FiltersJob* J);
+SVH_JOB_KERNEL(kd_filters0, template <>, k_filters<false>, k_filters_b<false>, FiltersJob, FX, 4, d_filters<false>, true)
+SVH_JOB_KERNEL(kd_filters1, template <>, k_filters<true>, k_filters_b<true>, FiltersJob, FX, 4, d_filters<true>, true)
+
+// the half-resolution image and the full-resolution Sobel planes read the same uploaded image and nothing of each
+// other: one launch (single-object path), workgroups [0, gh) halve, the rest filter
+__global__ __launch_bounds__(256) void k_half_filters(HalfJob a, FiltersJob b, int ghx, int gh, int gfx) {
+    const int id = (int)blockIdx.x;
+    if (id < gh) {
+        d_half(a, (unsigned)(id % ghx), (unsigned)(id / ghx));
+    } else {
+        const int k = id - gh;
+        d_filters<false>(b, (unsigned)(k % gfx), (unsigned)(k / gfx));
     }
 }
 
@@ -175,11 +201,13 @@ __device__ __forceinline__ int group_max(int v) {
 template <int kG>
 __device__ __forceinline__ bool group_any(bool p) {
     const unsigned long long b = __ballot(p);
-    if (kG == 64) return b != 0;
+    if constexpr (kG == 64) return b != 0;
     const int sh = (int)(threadIdx.x & 63) / kG * kG;
     return ((b >> sh) & ((1ull << kG) - 1ull)) != 0;
 }
 
+struct NmsJob { const int16_t *f1, *f2; int w, h, bpl, n, tau, margin, ni, nj; int4* slots; int32_t* flags; };
+__device__ __forceinline__ NmsJob globalise(NmsJob a) { all_global(a.f1, a.f2, a.slots, a.flags); return a; }
 template <int kG>
 __device__ __forceinline__ void d_nms(const int16_t* __restrict__ f1,
                                              const int16_t* __restrict__ f2, int w, int h, int bpl,
@@ -230,41 +258,48 @@ __device__ __forceinline__ void d_nms(const int16_t* __restrict__ f1,
         }
     }
 }
+template <int kG>
+__device__ __forceinline__ void d_nms(const NmsJob& a, unsigned bx, unsigned) {
+    d_nms<kG>(a.f1, a.f2, a.w, a.h, a.bpl, a.n, a.tau, a.margin, a.ni, a.nj, a.slots, a.flags, bx);
+}
+template <int kG> __global__ void k_nms(NmsJob a);
+template <int kG> __global__ void k_nms_b(const NmsJob* J);
+SVH_JOB_KERNEL(kd_nms16, template <>, k_nms<16>, k_nms_b<16>, NmsJob, 256, 1, d_nms<16>, true)
+SVH_JOB_KERNEL(kd_nms64, template <>, k_nms<64>, k_nms_b<64>, NmsJob, 256, 1, d_nms<64>, true)
+
+// the sparse and the dense table of one camera image by the same three launches (single-object path: every launch is
+// on the frame's critical path, and the two tables have nothing to wait for in each other): workgroups [0, ga) belong
+// to job a, the rest to job b
+__global__ __launch_bounds__(256) void k_nms2(NmsJob a, NmsJob b, int ga, int small_a, int small_b) {
+    const bool first = (int)blockIdx.x < ga;
+    const NmsJob& j = first ? a : b;
+    const unsigned bx = first ? blockIdx.x : blockIdx.x - ga;
+    // (field by field here and in the two fused kernels below: through the job overload the compiler selects between
+    // a and b per field instead of once, 15 scalar instructions more on the single-object path)
+    if (first ? small_a : small_b)
+        d_nms<16>(j.f1, j.f2, j.w, j.h, j.bpl, j.n, j.tau, j.margin, j.ni, j.nj, j.slots, j.flags, bx);
+    else
+        d_nms<64>(j.f1, j.f2, j.w, j.h, j.bpl, j.n, j.tau, j.margin, j.ni, j.nj, j.slots, j.flags, bx);
+}
 
 // ---------------------------------------------------------------------------
 // Order-preserving compaction by one workgroup: thread t owns a contiguous
 // chunk of slots, an LDS scan of the per-thread counts gives its output base.
 // ---------------------------------------------------------------------------
-// (round 6: a scan inside each wave by lane shuffles, then the 16 wave totals through LDS -- two barriers instead of
-// the twenty of a 1024-wide Hillis-Steele scan, which were most of the 11-14 us these single-workgroup kernels took)
-__device__ __forceinline__ int block_exclusive_scan_1024(int value, int* total) {
-    __shared__ int s_wave[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int incl = value;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-        const int x = s_wave[w];
-        before += w < wave ? x : 0;
-        all += x;
-    }
-    __syncthreads();   // (s_wave may be written again by the caller's next scan)
-    *total = all;
-    return before + incl - value;
-}
+// (round 6: block_exclusive_scan of dev_common.h instead of a 1024-wide Hillis-Steele scan, whose twenty barriers were
+// most of the 11-14 us these single-workgroup kernels took)
 
 // ordered compaction of the surviving slots: order[k] = slot of the k-th feature
+struct CompactSlotsJob { const int32_t* flags; int nslots; int32_t *order, *count; };
+__device__ __forceinline__ CompactSlotsJob globalise(CompactSlotsJob a) {
+    all_global(a.flags, a.order, a.count);
+    return a;
+}
 __device__ __forceinline__ void d_compact_slots(const int32_t* __restrict__ flags, int nslots,
                                                         int32_t* __restrict__ order,
-                                                        int32_t* __restrict__ count, unsigned bx,
-                                                        int32_t* __restrict__ count_host = nullptr) {
+                                                        int32_t* __restrict__ count,
+                                                        int32_t* __restrict__ count_host) {
+    __shared__ int s_wave[16];
     const int t = threadIdx.x;
     const int chunk = ((nslots + 1023) / 1024 + 3) & ~3;   // multiple of 4: 16-byte flag loads
     const int lo = min(t * chunk, nslots), hi = min(lo + chunk, nslots);
@@ -298,7 +333,7 @@ __device__ __forceinline__ void d_compact_slots(const int32_t* __restrict__ flag
         }
     }
     int total;
-    int base = block_exclusive_scan_1024(mine, &total);
+    int base = block_exclusive_scan<1024>(mine, s_wave, &total);
     if (masked) {
         for (; bits; bits &= bits - 1) order[base++] = lo + __builtin_ctzll(bits);
     } else if (mine) {
@@ -310,10 +345,23 @@ __device__ __forceinline__ void d_compact_slots(const int32_t* __restrict__ flag
         if (count_host) *count_host = total;   // (pinned host memory: the count needs no copy launch of its own)
     }
 }
+__device__ __forceinline__ void d_compact_slots(const CompactSlotsJob& a, unsigned, unsigned) {
+    d_compact_slots(a.flags, a.nslots, a.order, a.count, nullptr);
+}
+SVH_JOB_KERNEL(kd_compact_slots, , k_compact_slots, k_compact_slots_b, CompactSlotsJob, 1024, 1, d_compact_slots, true)
+__global__ __launch_bounds__(1024) void k_compact_slots2(CompactSlotsJob a, CompactSlotsJob b, int32_t* host_a, int32_t* host_b) {
+    const CompactSlotsJob& j = blockIdx.x == 0 ? a : b;
+    d_compact_slots(j.flags, j.nslots, j.order, j.count, blockIdx.x == 0 ? host_a : host_b);
+}
 
 // M5  descriptor + record packing   matcher.cpp:534-579, 854-877
 // one thread per (feature, descriptor word): 16 (du,dv) pairs around (u, v-1),
 // rows -5,-3,-1,+1,+3,+5 relative to v
+struct FeatureRecordsJob { const int4* slots; const int32_t *order, *count; const uint8_t *du, *dv; int bpl, scale; int32_t* table; };
+__device__ __forceinline__ FeatureRecordsJob globalise(FeatureRecordsJob a) {
+    all_global(a.slots, a.order, a.count, a.du, a.dv, a.table);
+    return a;
+}
 __device__ __forceinline__ void d_feature_records(const int4* __restrict__ slots,
                                                          const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ count,
@@ -334,6 +382,15 @@ __device__ __forceinline__ void d_feature_records(const int4* __restrict__ slots
     const uint32_t w0 = du[a0], w1 = dv[a0], w2 = du[b0], w3 = dv[b0];
     rec[4 + q] = (int32_t)(w0 | (w1 << 8) | (w2 << 16) | (w3 << 24));
 }
+__device__ __forceinline__ void d_feature_records(const FeatureRecordsJob& a, unsigned bx, unsigned) {
+    d_feature_records(a.slots, a.order, a.count, a.du, a.dv, a.bpl, a.scale, a.table, bx);
+}
+SVH_JOB_KERNEL(kd_feature_records, , k_feature_records, k_feature_records_b, FeatureRecordsJob, 256, 1, d_feature_records, true)
+__global__ __launch_bounds__(256) void k_feature_records2(FeatureRecordsJob a, FeatureRecordsJob b, int ga) {
+    const bool first = (int)blockIdx.x < ga;
+    const FeatureRecordsJob& j = first ? a : b;
+    d_feature_records(j.slots, j.order, j.count, j.du, j.dv, j.bpl, j.scale, j.table, first ? blockIdx.x : blockIdx.x - ga);
+}
 
 // ---------------------------------------------------------------------------
 // M6  Matcher::createIndexVector   matcher.cpp:1036-1057
@@ -342,13 +399,28 @@ __device__ __forceinline__ void d_feature_records(const int4* __restrict__ slots
 // ---------------------------------------------------------------------------
 // LDS build: histogram, scan, scatter and the per-bin ascending sort all stay on chip;
 // used when 2*nb + 1 + n ints fit the LDS budget (launcher), else k_bin_index below.
-// (table / count / off / ids: the four pointers of the workgroup's table.  The callers pick them out of their BinJobs
-// -- a kernel argument in the single-object form, a row of the job table in the batched form -- so that the 32
-// pointers are never copied: round 4's batched form indexed a by-value copy and spilled 264 bytes of scratch)
+// (BinTable: the four pointers of the workgroup's table, picked out of the job's BinJobs -- a kernel argument in the
+// single-object form, a row of the job table in the batched form -- so that the 32 pointers are never copied: round
+// 4's batched form indexed a by-value copy and spilled 264 bytes of scratch.  globalise therefore hands the body the
+// picked table, and the body that takes the whole job only picks.)
+struct BinIndexJob { BinJobs J; int ub, vb, binsize, njobs; };
+struct BinTable { const int32_t *table, *count; int32_t *off, *ids; int ub, vb, binsize; };
+__device__ __forceinline__ BinTable bin_table(const BinIndexJob& a, unsigned bx) {
+    return {a.J.table[bx], a.J.count[bx], a.J.off[bx], a.J.ids[bx], a.ub, a.vb, a.binsize};
+}
+// The one globalise that does not return its own job type: it picks this workgroup's table (blockIdx.x) and
+// globalises those four pointers only, so the batched entry calls the BinTable body directly and the plain entry
+// reaches it through the BinIndexJob overload below, which only picks.
+__device__ __forceinline__ BinTable globalise(const BinIndexJob& a) {
+    BinTable r = bin_table(a, blockIdx.x);
+    all_global(r.table, r.count, r.off, r.ids);
+    return r;
+}
 __device__ __forceinline__ void d_bin_index_lds(const int32_t* __restrict__ table, const int32_t* __restrict__ count,
                                                 int32_t* __restrict__ off, int32_t* __restrict__ ids, int ub, int vb,
                                                 int binsize) {
     extern __shared__ int s_bin[];
+    __shared__ int s_wave[16];
     // one workgroup per table: the four tables of a stereo frame build concurrently
     const int n = *count, nb = 4 * ub * vb, t = threadIdx.x;
     int* s_off = s_bin;            // nb + 1
@@ -374,7 +446,7 @@ __device__ __forceinline__ void d_bin_index_lds(const int32_t* __restrict__ tabl
         int mine = 0;
         for (int b = lo; b < hi; b++) mine += s_off[b];
         int total;
-        int run = block_exclusive_scan_1024(mine, &total);
+        int run = block_exclusive_scan<1024>(mine, s_wave, &total);
         for (int b = lo; b < hi; b++) {
             run += s_off[b];
             s_off[b] = run;
@@ -417,6 +489,18 @@ __device__ __forceinline__ void d_bin_index_lds(const int32_t* __restrict__ tabl
     __syncthreads();
     for (int b = t; b <= nb; b += 1024) off[b] = s_off[b];
     for (int i = t; i < n; i += 1024) ids[i] = s_ids[i];
+}
+__device__ __forceinline__ void d_bin_index_lds(const BinTable& a, unsigned, unsigned) {
+    d_bin_index_lds(a.table, a.count, a.off, a.ids, a.ub, a.vb, a.binsize);
+}
+__device__ __forceinline__ void d_bin_index_lds(const BinIndexJob& a, unsigned bx, unsigned by) {
+    d_bin_index_lds(bin_table(a, bx), bx, by);
+}
+SVH_JOB_KERNEL(kd_bin_index, , k_bin_index_lds, k_bin_index_lds_b, BinIndexJob, 1024, 1, d_bin_index_lds,
+               (int)blockIdx.x < a.njobs)
+void bin_index_lds_opt_in() {
+    static const bool once = (allow_dynamic_lds(kd_bin_index, k_bin_index_lds_b, 156 * 1024), true);
+    (void)once;
 }
 
 __global__ __launch_bounds__(1024) void k_bin_index(const int32_t* __restrict__ table,
@@ -670,6 +754,19 @@ __device__ __forceinline__ svh_p_match mk(float u1p, float v1p, int i1p, float u
 // M8  Matcher::matching   matcher.cpp:1161-1379 -- one thread per query feature.
 // flags: 0 = no match, 1 = match.  For flow/stereo the "pixel not matched yet"
 // rule (first query in index order wins) is resolved by k_match_dedupe.
+struct MatchJob {
+    MatchParams P;
+    FeatView m1p, m2p, m1c, m2c;
+    const float* ranges;
+    int use_prior;
+    svh_p_match* out;
+    int32_t *flags, *pixel_owner;
+};
+__device__ __forceinline__ MatchJob globalise(MatchJob a) {
+    a.m1p = gview(a.m1p); a.m2p = gview(a.m2p); a.m1c = gview(a.m1c); a.m2c = gview(a.m2c);
+    all_global(a.ranges, a.out, a.flags, a.pixel_owner);
+    return a;
+}
 __device__ __forceinline__ void d_match(MatchParams P, FeatView m1p, FeatView m2p, FeatView m1c,
                                                FeatView m2c, const float* __restrict__ ranges,
                                                int use_prior, svh_p_match* __restrict__ out,
@@ -744,8 +841,14 @@ __device__ __forceinline__ void d_match(MatchParams P, FeatView m1p, FeatView m2
     flags[i] = ok;
     if (ok) out[i] = m;
 }
+__device__ __forceinline__ void d_match(const MatchJob& a, unsigned bx, unsigned) {
+    d_match(a.P, a.m1p, a.m2p, a.m1c, a.m2c, a.ranges, a.use_prior, a.out, a.flags, a.pixel_owner, bx);
+}
+SVH_JOB_KERNEL(kd_match, , k_match, k_match_b, MatchJob, 128, 1, d_match, true)
 
 // flow / stereo: keep a match only if its query is the first one on its pixel
+struct DedupeJob { const int32_t* n; int width; const svh_p_match* m; int32_t* flags; const int32_t* pixel_owner; };
+__device__ __forceinline__ DedupeJob globalise(DedupeJob a) { all_global(a.n, a.m, a.flags, a.pixel_owner); return a; }
 __device__ __forceinline__ void d_match_dedupe(const int32_t* __restrict__ n, int width,
                                                       const svh_p_match* __restrict__ m,
                                                       int32_t* __restrict__ flags,
@@ -755,14 +858,27 @@ __device__ __forceinline__ void d_match_dedupe(const int32_t* __restrict__ n, in
     const int u = (int)m[i].u1c, v = (int)m[i].v1c;
     if (pixel_owner[(size_t)v * width + u] != i) flags[i] = 0;
 }
+__device__ __forceinline__ void d_match_dedupe(const DedupeJob& a, unsigned bx, unsigned) {
+    d_match_dedupe(a.n, a.width, a.m, a.flags, a.pixel_owner, bx);
+}
+SVH_JOB_KERNEL(kd_dedupe, , k_match_dedupe, k_match_dedupe_b, DedupeJob, 256, 1, d_match_dedupe, true)
 
 constexpr int kCompactLds = 8192;   // survivors whose slot numbers fit the LDS list of d_compact_matches
+// (count_host: pinned host memory or null.  A recorded batch copies its counts with its other small transfers, so the
+// batched entry never writes one)
+struct CompactMatchesJob { const svh_p_match* in; const int32_t *flags, *nslots; svh_p_match* out; int32_t *count, *count_host; };
+__device__ __forceinline__ CompactMatchesJob globalise(CompactMatchesJob a) {
+    all_global(a.in, a.flags, a.nslots, a.out, a.count);
+    a.count_host = nullptr;
+    return a;
+}
 __device__ __forceinline__ void d_compact_matches(const svh_p_match* __restrict__ in,
                                                           const int32_t* __restrict__ flags,
                                                           const int32_t* __restrict__ nslots_ptr,
                                                           svh_p_match* __restrict__ out,
-                                                          int32_t* __restrict__ count, unsigned bx,
-                                                          int32_t* __restrict__ count_host = nullptr) {
+                                                          int32_t* __restrict__ count,
+                                                          int32_t* __restrict__ count_host) {
+    __shared__ int s_wave[16];
     const int nslots = *nslots_ptr;
     const int t = threadIdx.x;
     const int chunk = (nslots + 1023) / 1024;
@@ -779,7 +895,7 @@ __device__ __forceinline__ void d_compact_matches(const svh_p_match* __restrict_
         for (int s = lo; s < hi; s++) mine += flags[s];
     }
     int total;
-    int base = block_exclusive_scan_1024(mine, &total);
+    int base = block_exclusive_scan<1024>(mine, s_wave, &total);
     // the survivors' slot numbers go through LDS, then the whole workgroup moves the 48-byte records as 16-byte pieces
     // side by side (a thread copying its own records one after the other was 6 of the kernel's 10 us)
     __shared__ int s_src[kCompactLds];
@@ -801,9 +917,13 @@ __device__ __forceinline__ void d_compact_matches(const svh_p_match* __restrict_
     }
     if (t == 0) {
         *count = total;
-        if (count_host) *count_host = total;   // (pinned host memory: no copy launch for the count)
+        if (count_host) *count_host = total;   // (no copy launch for the count)
     }
 }
+__device__ __forceinline__ void d_compact_matches(const CompactMatchesJob& a, unsigned, unsigned) {
+    d_compact_matches(a.in, a.flags, a.nslots, a.out, a.count, a.count_host);
+}
+SVH_JOB_KERNEL(kd_compact_matches, , k_compact_matches, k_compact_matches_b, CompactMatchesJob, 1024, 1, d_compact_matches, true)
 
 // ---------------------------------------------------------------------------
 // M11  Matcher::relocateMinimum / refinement (refinement == 1)
@@ -867,6 +987,16 @@ __device__ __forceinline__ void relocate_group(const SobelView& s1, const SobelV
     *v2 = (float)((double)*v2 + ((double)(float)(best / 5) - 2.0));
 }
 
+struct RefineJob { svh_p_match* m; const int32_t* count; int method, margin; SobelView s1p, s2p, s1c, s2c; int32_t* flags; };
+__device__ __forceinline__ RefineJob globalise(const RefineJob& a) {
+    // (each pointer read from the table right before its round trip, in the order of the hand-written call this
+    // replaces: globalising a by-value copy made k_refine_parabolic_b 82 instructions longer)
+    RefineJob o = a;
+    o.m = as_global(a.m); o.count = as_global(a.count);
+    o.s1p = gview(a.s1p); o.s2p = gview(a.s2p); o.s1c = gview(a.s1c); o.s2c = gview(a.s2c);
+    o.flags = as_global(a.flags);
+    return o;
+}
 __device__ __forceinline__ void d_refine_group(svh_p_match* __restrict__ m,
                                                       const int32_t* __restrict__ count, int method, int margin,
                                                       SobelView s1p, SobelView s2p, SobelView s1c,
@@ -879,6 +1009,10 @@ __device__ __forceinline__ void d_refine_group(svh_p_match* __restrict__ m,
     if (method == 2) relocate_group(s1c, s2p, margin, q.u1c, q.v1c, &q.u2p, &q.v2p, lane);
     if (lane == 0) m[i] = q;
 }
+__device__ __forceinline__ void d_refine_group(const RefineJob& a, unsigned bx, unsigned) {
+    d_refine_group(a.m, a.count, a.method, a.margin, a.s1p, a.s2p, a.s1c, a.s2c, bx);
+}
+SVH_JOB_KERNEL(kd_refine_group, , k_refine_group, k_refine_group_b, RefineJob, 256, 1, d_refine_group, true)
 
 // Matrix::solve, 6x6 with one right-hand side   libviso2/src/matrix.cpp:648-760
 // The matrix of parabolicFitting is A^T A of a CONSTANT 9x6 design matrix (matcher.cpp:1725-1733), so
@@ -1036,173 +1170,11 @@ __device__ __forceinline__ void d_refine(svh_p_match* __restrict__ m,
     }
     if (ok) m[i] = q;
 }
-
-
-// ---------------------------------------------------------------------------
-// Kernels: every body above is a __device__ function of (arguments, block index); each gets a plain
-// __global__ form (one object: arguments by value) and a BATCHED form (K objects in lockstep, batch_rec.h:
-// arguments of job blockIdx.z read from a job table in device memory, grid = the largest job's).
-// ---------------------------------------------------------------------------
-// Pointers that arrive through a job table in memory have lost their address space: hipcc then reads and writes
-// through FLAT instructions (round 4: 913 of them in the lockstep kernels, 514 in k_refine_parabolic_b alone).  Every
-// buffer of a job is device (or device-mapped pinned host) memory: a round trip through address space 1 tells the
-// compiler so and the kernels use global_load / global_store like their single-object forms.
-template <class T>
-__device__ __forceinline__ T* gptr(T* p) {
-    // (the empty asm keeps the address-space-1 value opaque: a plain generic -> global -> generic cast pair is folded
-    // away before the compiler's address-space inference sees it; held in a vector register pair)
-    __attribute__((address_space(1))) T* q = (__attribute__((address_space(1))) T*)p;
-    asm volatile("" : "+v"(q));
-    return (T*)q;
+template <bool kParabolic>
+__device__ __forceinline__ void d_refine(const RefineJob& a, unsigned bx, unsigned) {
+    d_refine<kParabolic>(a.m, a.count, a.method, a.margin, a.s1p, a.s2p, a.s1c, a.s2c, a.flags, bx);
 }
-__device__ __forceinline__ FeatView gview(const FeatView& v) {
-    FeatView o;
-    o.rec = gptr(v.rec); o.count = gptr(v.count); o.off = gptr(v.off); o.ids = gptr(v.ids);
-    return o;
-}
-__device__ __forceinline__ SobelView gview(const SobelView& v) {
-    SobelView o = v;
-    o.du = gptr(v.du); o.dv = gptr(v.dv);
-    return o;
-}
-
-struct HalfJob { const uint8_t* I; int bpl; uint8_t* out; int hw, hh, hbpl; };
-__global__ __launch_bounds__(256) void k_half(HalfJob a) { d_half(a.I, a.bpl, a.out, a.hw, a.hh, a.hbpl, blockIdx.x, blockIdx.y); }
-__global__ __launch_bounds__(256) void k_half_b(const HalfJob* J) {
-    const HalfJob a = J[blockIdx.z];
-    d_half(gptr(a.I), a.bpl, gptr(a.out), a.hw, a.hh, a.hbpl, blockIdx.x, blockIdx.y);
-}
-
-struct FiltersJob { const uint8_t* I; int w, h, bpl; uint8_t *du, *dv; int16_t *f1, *f2; };
-template <bool kFeatures>
-__global__ __launch_bounds__(256) void k_filters(FiltersJob a) {
-    d_filters<kFeatures>(a.I, a.w, a.h, a.bpl, a.du, a.dv, a.f1, a.f2, blockIdx.x, blockIdx.y);
-}
-template <bool kFeatures>
-__global__ __launch_bounds__(256) void k_filters_b(const FiltersJob* J) {
-    const FiltersJob a = J[blockIdx.z];
-    d_filters<kFeatures>(gptr(a.I), a.w, a.h, a.bpl, gptr(a.du), gptr(a.dv), gptr(a.f1), gptr(a.f2), blockIdx.x, blockIdx.y);
-}
-
-// the half-resolution image and the full-resolution Sobel planes read the same uploaded image and nothing of each
-// other: one launch (single-object path), workgroups [0, gh) halve, the rest filter
-__global__ __launch_bounds__(256) void k_half_filters(HalfJob a, FiltersJob b, int ghx, int gh, int gfx) {
-    const int id = (int)blockIdx.x;
-    if (id < gh) {
-        d_half(a.I, a.bpl, a.out, a.hw, a.hh, a.hbpl, (unsigned)(id % ghx), (unsigned)(id / ghx));
-    } else {
-        const int k = id - gh;
-        d_filters<false>(b.I, b.w, b.h, b.bpl, b.du, b.dv, b.f1, b.f2, (unsigned)(k % gfx), (unsigned)(k / gfx));
-    }
-}
-
-struct NmsJob { const int16_t *f1, *f2; int w, h, bpl, n, tau, margin, ni, nj; int4* slots; int32_t* flags; };
-template <int kG>
-__global__ __launch_bounds__(256) void k_nms(NmsJob a) {
-    d_nms<kG>(a.f1, a.f2, a.w, a.h, a.bpl, a.n, a.tau, a.margin, a.ni, a.nj, a.slots, a.flags, blockIdx.x);
-}
-template <int kG>
-__global__ __launch_bounds__(256) void k_nms_b(const NmsJob* J) {
-    const NmsJob a = J[blockIdx.z];
-    d_nms<kG>(gptr(a.f1), gptr(a.f2), a.w, a.h, a.bpl, a.n, a.tau, a.margin, a.ni, a.nj, gptr(a.slots), gptr(a.flags), blockIdx.x);
-}
-
-// the sparse and the dense table of one camera image by the same three launches (single-object path: every launch is
-// on the frame's critical path, and the two tables have nothing to wait for in each other): workgroups [0, ga) belong
-// to job a, the rest to job b
-__global__ __launch_bounds__(256) void k_nms2(NmsJob a, NmsJob b, int ga, int small_a, int small_b) {
-    const bool first = (int)blockIdx.x < ga;
-    const NmsJob& j = first ? a : b;
-    const unsigned bx = first ? blockIdx.x : blockIdx.x - ga;
-    if (first ? small_a : small_b)
-        d_nms<16>(j.f1, j.f2, j.w, j.h, j.bpl, j.n, j.tau, j.margin, j.ni, j.nj, j.slots, j.flags, bx);
-    else
-        d_nms<64>(j.f1, j.f2, j.w, j.h, j.bpl, j.n, j.tau, j.margin, j.ni, j.nj, j.slots, j.flags, bx);
-}
-struct CompactSlotsJob { const int32_t* flags; int nslots; int32_t *order, *count; };
-__global__ __launch_bounds__(1024) void k_compact_slots(CompactSlotsJob a) { d_compact_slots(a.flags, a.nslots, a.order, a.count, 0u); }
-__global__ __launch_bounds__(1024) void k_compact_slots_b(const CompactSlotsJob* J) {
-    const CompactSlotsJob a = J[blockIdx.z];
-    d_compact_slots(gptr(a.flags), a.nslots, gptr(a.order), gptr(a.count), 0u);
-}
-
-__global__ __launch_bounds__(1024) void k_compact_slots2(CompactSlotsJob a, CompactSlotsJob b, int32_t* host_a, int32_t* host_b) {
-    const CompactSlotsJob& j = blockIdx.x == 0 ? a : b;
-    d_compact_slots(j.flags, j.nslots, j.order, j.count, 0u, blockIdx.x == 0 ? host_a : host_b);
-}
-struct FeatureRecordsJob { const int4* slots; const int32_t *order, *count; const uint8_t *du, *dv; int bpl, scale; int32_t* table; };
-__global__ __launch_bounds__(256) void k_feature_records(FeatureRecordsJob a) {
-    d_feature_records(a.slots, a.order, a.count, a.du, a.dv, a.bpl, a.scale, a.table, blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_feature_records2(FeatureRecordsJob a, FeatureRecordsJob b, int ga) {
-    const bool first = (int)blockIdx.x < ga;
-    const FeatureRecordsJob& j = first ? a : b;
-    d_feature_records(j.slots, j.order, j.count, j.du, j.dv, j.bpl, j.scale, j.table, first ? blockIdx.x : blockIdx.x - ga);
-}
-__global__ __launch_bounds__(256) void k_feature_records_b(const FeatureRecordsJob* J) {
-    const FeatureRecordsJob a = J[blockIdx.z];
-    d_feature_records(gptr(a.slots), gptr(a.order), gptr(a.count), gptr(a.du), gptr(a.dv), a.bpl, a.scale, gptr(a.table), blockIdx.x);
-}
-
-struct BinIndexJob { BinJobs J; int njobs, ub, vb, binsize; };
-__global__ __launch_bounds__(1024) void k_bin_index_lds(BinJobs J, int ub, int vb, int binsize) {
-    const unsigned bx = blockIdx.x;
-    d_bin_index_lds(J.table[bx], J.count[bx], J.off[bx], J.ids[bx], ub, vb, binsize);
-}
-__global__ __launch_bounds__(1024) void k_bin_index_lds_b(const BinIndexJob* J) {
-    const BinIndexJob& a = J[blockIdx.z];
-    const unsigned bx = blockIdx.x;
-    if ((int)bx >= a.njobs) return;
-    d_bin_index_lds(gptr(a.J.table[bx]), gptr(a.J.count[bx]), gptr(a.J.off[bx]), gptr(a.J.ids[bx]), a.ub, a.vb, a.binsize);
-}
-
-struct MatchJob {
-    MatchParams P;
-    FeatView m1p, m2p, m1c, m2c;
-    const float* ranges;
-    int use_prior;
-    svh_p_match* out;
-    int32_t *flags, *pixel_owner;
-};
-__global__ __launch_bounds__(128) void k_match(MatchJob a) {
-    d_match(a.P, a.m1p, a.m2p, a.m1c, a.m2c, a.ranges, a.use_prior, a.out, a.flags, a.pixel_owner, blockIdx.x);
-}
-__global__ __launch_bounds__(128) void k_match_b(const MatchJob* J) {
-    const MatchJob& a = J[blockIdx.z];
-    d_match(a.P, gview(a.m1p), gview(a.m2p), gview(a.m1c), gview(a.m2c), gptr(a.ranges), a.use_prior, gptr(a.out), gptr(a.flags),
-            gptr(a.pixel_owner), blockIdx.x);
-}
-
-struct DedupeJob { const int32_t* n; int width; const svh_p_match* m; int32_t* flags; const int32_t* pixel_owner; };
-__global__ __launch_bounds__(256) void k_match_dedupe(DedupeJob a) { d_match_dedupe(a.n, a.width, a.m, a.flags, a.pixel_owner, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_match_dedupe_b(const DedupeJob* J) {
-    const DedupeJob a = J[blockIdx.z];
-    d_match_dedupe(gptr(a.n), a.width, gptr(a.m), gptr(a.flags), gptr(a.pixel_owner), blockIdx.x);
-}
-
-struct CompactMatchesJob { const svh_p_match* in; const int32_t *flags, *nslots; svh_p_match* out; int32_t* count; };
-__global__ __launch_bounds__(1024) void k_compact_matches(CompactMatchesJob a, int32_t* count_host) { d_compact_matches(a.in, a.flags, a.nslots, a.out, a.count, 0u, count_host); }
-__global__ __launch_bounds__(1024) void k_compact_matches_b(const CompactMatchesJob* J) {
-    const CompactMatchesJob a = J[blockIdx.z];
-    d_compact_matches(gptr(a.in), gptr(a.flags), gptr(a.nslots), gptr(a.out), gptr(a.count), 0u);
-}
-
-struct RefineJob { svh_p_match* m; const int32_t* count; int method, margin; SobelView s1p, s2p, s1c, s2c; int32_t* flags; };
-__global__ __launch_bounds__(256) void k_refine_group(RefineJob a) {
-    d_refine_group(a.m, a.count, a.method, a.margin, a.s1p, a.s2p, a.s1c, a.s2c, blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_refine_group_b(const RefineJob* J) {
-    const RefineJob& a = J[blockIdx.z];
-    d_refine_group(gptr(a.m), gptr(a.count), a.method, a.margin, gview(a.s1p), gview(a.s2p), gview(a.s1c), gview(a.s2c), blockIdx.x);
-}
-__global__ __launch_bounds__(128) void k_refine_parabolic(RefineJob a) {
-    d_refine<true>(a.m, a.count, a.method, a.margin, a.s1p, a.s2p, a.s1c, a.s2c, a.flags, blockIdx.x);
-}
-__global__ __launch_bounds__(128) void k_refine_parabolic_b(const RefineJob* J) {
-    const RefineJob& a = J[blockIdx.z];
-    d_refine<true>(gptr(a.m), gptr(a.count), a.method, a.margin, gview(a.s1p), gview(a.s2p), gview(a.s1c), gview(a.s2c), gptr(a.flags),
-                   blockIdx.x);
-}
+SVH_JOB_KERNEL(kd_refine_parabolic, , k_refine_parabolic, k_refine_parabolic_b, RefineJob, 128, 1, d_refine<true>, true)
 
 // ---------------------------------------------------------------------------
 // Image upload: the rows were packed into PINNED host memory; the device reads
@@ -1212,53 +1184,25 @@ __global__ __launch_bounds__(128) void k_refine_parabolic_b(const RefineJob* J) 
 // pinned host memory, search ranges to the device): words of 4 bytes, any direction the device can address.
 // ---------------------------------------------------------------------------
 struct UploadJob { const uint4* host; uint4* dev; size_t n16; };
-__global__ __launch_bounds__(256) void k_upload(UploadJob a) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ UploadJob globalise(UploadJob a) { all_global(a.host, a.dev); return a; }
+__device__ __forceinline__ void d_upload(const UploadJob& a, unsigned bx, unsigned) {
+    const size_t i = (size_t)bx * 256 + threadIdx.x;
     if (i < a.n16) a.dev[i] = a.host[i];
 }
-__global__ __launch_bounds__(256) void k_upload_b(const UploadJob* J) {
-    const UploadJob a = J[blockIdx.z];
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < a.n16) gptr(a.dev)[i] = gptr(a.host)[i];
-}
+SVH_JOB_KERNEL(kd_upload, , k_upload, k_upload_b, UploadJob, 256, 1, d_upload, true)
 struct Copy4Job { uint32_t* dst; const uint32_t* src; size_t n4; };
-__global__ __launch_bounds__(256) void k_copy4(Copy4Job a) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * 256) a.dst[i] = a.src[i];
+__device__ __forceinline__ Copy4Job globalise(Copy4Job a) { all_global(a.dst, a.src); return a; }
+__device__ __forceinline__ void d_copy4(const Copy4Job& a, unsigned bx, unsigned) {
+    for (size_t i = (size_t)bx * 256 + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * 256) a.dst[i] = a.src[i];
 }
-__global__ __launch_bounds__(256) void k_copy4_b(const Copy4Job* J) {
-    const Copy4Job a = J[blockIdx.z];
-    uint32_t* const dst = gptr(a.dst);
-    const uint32_t* const src = gptr(a.src);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
+SVH_JOB_KERNEL(kd_copy4, , k_copy4, k_copy4_b, Copy4Job, 256, 1, d_copy4, true)
+// (no plain form: a single object's fill is hipMemsetAsync)
 struct Fill4Job { uint32_t* dst; uint32_t value; size_t n4; };
-__global__ __launch_bounds__(256) void k_fill4_b(const Fill4Job* J) {
-    const Fill4Job a = J[blockIdx.z];
-    uint32_t* const dst = gptr(a.dst);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * 256) dst[i] = a.value;
+__device__ __forceinline__ Fill4Job globalise(Fill4Job a) { all_global(a.dst); return a; }
+__device__ __forceinline__ void d_fill4(const Fill4Job& a, unsigned bx, unsigned) {
+    for (size_t i = (size_t)bx * 256 + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * 256) a.dst[i] = a.value;
 }
-
-// batched launch entries (BatchLaunchFn): jobs = device copy of the table, grid (gx, gy, njobs)
-#define SVH_BATCH_FN(name, kernel, Job, threads)                                                                   \
-    void name(const void* jobs, int njobs, unsigned gx, unsigned gy, size_t lds, hipStream_t s) {                  \
-        hipLaunchKernelGGL(kernel, dim3(gx, gy, (unsigned)njobs), threads, lds, s, reinterpret_cast<const Job*>(jobs)); \
-    }
-SVH_BATCH_FN(b_half, k_half_b, HalfJob, dim3(64, 4))
-SVH_BATCH_FN(b_filters0, k_filters_b<false>, FiltersJob, dim3(FX, 4))
-SVH_BATCH_FN(b_filters1, k_filters_b<true>, FiltersJob, dim3(FX, 4))
-SVH_BATCH_FN(b_nms16, k_nms_b<16>, NmsJob, dim3(256))
-SVH_BATCH_FN(b_nms64, k_nms_b<64>, NmsJob, dim3(256))
-SVH_BATCH_FN(b_compact_slots, k_compact_slots_b, CompactSlotsJob, dim3(1024))
-SVH_BATCH_FN(b_feature_records, k_feature_records_b, FeatureRecordsJob, dim3(256))
-SVH_BATCH_FN(b_bin_index, k_bin_index_lds_b, BinIndexJob, dim3(1024))
-SVH_BATCH_FN(b_match, k_match_b, MatchJob, dim3(128))
-SVH_BATCH_FN(b_dedupe, k_match_dedupe_b, DedupeJob, dim3(256))
-SVH_BATCH_FN(b_compact_matches, k_compact_matches_b, CompactMatchesJob, dim3(1024))
-SVH_BATCH_FN(b_refine_group, k_refine_group_b, RefineJob, dim3(256))
-SVH_BATCH_FN(b_refine_parabolic, k_refine_parabolic_b, RefineJob, dim3(128))
-SVH_BATCH_FN(b_upload, k_upload_b, UploadJob, dim3(256))
-SVH_BATCH_FN(b_copy4, k_copy4_b, Copy4Job, dim3(256))
-SVH_BATCH_FN(b_fill4, k_fill4_b, Fill4Job, dim3(256))
+SVH_BATCHED_KERNEL(kd_fill4, , k_fill4_b, Fill4Job, 256, 1, d_fill4, true)
 
 }  // namespace
 
@@ -1268,51 +1212,38 @@ SVH_BATCH_FN(b_fill4, k_fill4_b, Fill4Job, dim3(256))
 void mlaunch_upload(void* stream, const uint8_t* pinned, uint8_t* dev, size_t bytes) {
     const size_t n16 = bytes / 16;   // bpl is a multiple of 16
     const UploadJob a = {reinterpret_cast<const uint4*>(pinned), reinterpret_cast<uint4*>(dev), n16};
-    const unsigned gx = (unsigned)((n16 + 255) / 256);
-    if (t_rec) return t_rec->add(b_upload, a, gx);
-    hipLaunchKernelGGL(k_upload, dim3(gx), dim3(256), 0, (hipStream_t)stream, a);
+    launch_or_record(stream, kd_upload, a, dim3((unsigned)((n16 + 255) / 256)));
 }
 
 // small transfers between pinned host and device memory, either direction (bytes: a multiple of 4)
 void mlaunch_copy(void* stream, void* dst, const void* src, size_t bytes, int kind) {
     const Copy4Job a = {static_cast<uint32_t*>(dst), static_cast<const uint32_t*>(src), bytes / 4};
-    const unsigned gx = (unsigned)std::min<size_t>((bytes / 4 + 255) / 256, 64);
-    if (t_rec) return t_rec->add(b_copy4, a, gx);
     // Small transfers go by a kernel as well: both ends are device-addressable (pinned host memory), and a copy
     // kernel in the stream's own queue spares the hand-over to a DMA engine and back (~15 us per copy; a frame has
-    // five of them between kernels that wait for each other).
+    // five of them between kernels that wait for each other).  A recorded batch has the kernel only.
     static const bool by_kernel = !(svh::env("SVH_MATCHER_COPY_KERNEL") && atoi(svh::env("SVH_MATCHER_COPY_KERNEL")) == 0);
-    if (by_kernel && bytes % 4 == 0 && bytes > 0 && bytes <= ((size_t)1 << 20)) {
-        hipLaunchKernelGGL(k_copy4, dim3(gx), dim3(256), 0, (hipStream_t)stream, a);
-        return;
-    }
+    if (t_rec || (by_kernel && bytes % 4 == 0 && bytes > 0 && bytes <= ((size_t)1 << 20)))
+        return launch_or_record(stream, kd_copy4, a, dim3((unsigned)std::min<size_t>((bytes / 4 + 255) / 256, 64)));
     (void)hipMemcpyAsync(dst, src, bytes, (hipMemcpyKind)kind, (hipStream_t)stream);
 }
 void mlaunch_fill(void* stream, void* dst, int byte_value, size_t bytes) {
     if (t_rec) {
         const uint32_t b = (uint32_t)(byte_value & 0xFF);
         const Fill4Job a = {static_cast<uint32_t*>(dst), b | b << 8 | b << 16 | b << 24, bytes / 4};
-        return t_rec->add(b_fill4, a, (unsigned)std::min<size_t>((bytes / 4 + 255) / 256, 256));
+        return t_rec->add(kd_fill4_batch, a, (unsigned)std::min<size_t>((bytes / 4 + 255) / 256, 256));
     }
     (void)hipMemsetAsync(dst, byte_value, bytes, (hipStream_t)stream);
 }
 
 void mlaunch_half(void* stream, const uint8_t* I, int bpl, uint8_t* out, int hw, int hh, int hbpl) {
     const HalfJob a = {I, bpl, out, hw, hh, hbpl};
-    const unsigned gx = (hw + 63) / 64, gy = (hh + 3) / 4;
-    if (t_rec) return t_rec->add(b_half, a, gx, gy);
-    hipLaunchKernelGGL(k_half, dim3(gx, gy), dim3(64, 4), 0, (hipStream_t)stream, a);
+    launch_or_record(stream, kd_half, a, dim3((hw + 63) / 64, (hh + 3) / 4));
 }
 
 void mlaunch_filters(void* stream, const uint8_t* I, int w, int h, int bpl, uint8_t* du, uint8_t* dv,
                      int16_t* f1, int16_t* f2) {
     const FiltersJob a = {I, w, h, bpl, du, dv, f1, f2};
-    const dim3 grid((bpl / 4 + FX - 1) / FX, (h + 4 * FR - 1) / (4 * FR)), block(FX, 4);
-    if (t_rec) return t_rec->add(f1 ? b_filters1 : b_filters0, a, grid.x, grid.y);
-    if (f1)
-        hipLaunchKernelGGL(k_filters<true>, grid, block, 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_filters<false>, grid, block, 0, (hipStream_t)stream, a);
+    launch_or_record(stream, f1 ? kd_filters1 : kd_filters0, a, dim3((bpl / 4 + FX - 1) / FX, (h + 4 * FR - 1) / (4 * FR)));
 }
 
 // k_half on I -> Ih and the Sobel planes of I (no feature images) by one launch
@@ -1340,27 +1271,15 @@ int mnms_blocks(int extent, int n, int margin) {
 void mlaunch_features(void* stream, const int16_t* f1, const int16_t* f2, const uint8_t* du,
                       const uint8_t* dv, int w, int h, int bpl, int n, int tau, int margin, int scale,
                       int4* slots, int32_t* flags, int32_t* order, int32_t* table, int32_t* count) {
-    hipStream_t s = (hipStream_t)stream;
     const int ni = mnms_blocks(w, n, margin), nj = mnms_blocks(h, n, margin);
     const int nb = ni * nj;
     const NmsJob an = {f1, f2, w, h, bpl, n, tau, margin, ni, nj, slots, flags};
     const CompactSlotsJob ac = {flags, nb * 4, order, count};
     const FeatureRecordsJob af = {slots, order, count, du, dv, bpl, scale, table};
     const bool small = (n + 1) * (n + 1) <= 16;
-    if (t_rec) {
-        if (nb > 0) t_rec->add(small ? b_nms16 : b_nms64, an, small ? (nb + 15) / 16 : (nb + 3) / 4);
-        t_rec->add(b_compact_slots, ac, 1);
-        if (nb > 0) t_rec->add(b_feature_records, af, (nb * 4 * 8 + 255) / 256);
-        return;
-    }
-    if (nb > 0) {
-        if (small)
-            hipLaunchKernelGGL(k_nms<16>, dim3((nb + 15) / 16), dim3(256), 0, s, an);
-        else
-            hipLaunchKernelGGL(k_nms<64>, dim3((nb + 3) / 4), dim3(256), 0, s, an);
-    }
-    hipLaunchKernelGGL(k_compact_slots, dim3(1), dim3(1024), 0, s, ac);
-    if (nb > 0) hipLaunchKernelGGL(k_feature_records, dim3((nb * 4 * 8 + 255) / 256), dim3(256), 0, s, af);
+    if (nb > 0) launch_or_record(stream, small ? kd_nms16 : kd_nms64, an, dim3(small ? (nb + 15) / 16 : (nb + 3) / 4));
+    launch_or_record(stream, kd_compact_slots, ac, dim3(1));
+    if (nb > 0) launch_or_record(stream, kd_feature_records, af, dim3((nb * 4 * 8 + 255) / 256));
 }
 
 // both tables of a camera image (n_a: the sparse table's NMS radius, n_b: the dense one's); scratch set per table;
@@ -1396,18 +1315,12 @@ void mlaunch_bin_index(void* stream, const BinJobs& J, int njobs, int n_host_max
                        int32_t* cursor) {
     const int nb = 4 * ub * vb;
     const size_t lds = ((size_t)2 * nb + 1 + (size_t)std::max(n_host_max, 0)) * sizeof(int32_t);
-    if (t_rec) {
-        // (the batched form has the LDS build only, with the 160 KB opt-in: ~38 k features per table)
-        BinIndexJob a;
-        a.J = J; a.njobs = njobs; a.ub = ub; a.vb = vb; a.binsize = binsize;
-        static bool attr_once = ((void)hipFuncSetAttribute((const void*)k_bin_index_lds_b,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), true);
-        (void)attr_once;
-        if (lds > 156 * 1024) t_rec->broken = true;
-        return t_rec->add(b_bin_index, a, 8, 1, lds);
-    }
-    if (lds <= 56 * 1024) {
-        hipLaunchKernelGGL(k_bin_index_lds, dim3(njobs), dim3(1024), lds, (hipStream_t)stream, J, ub, vb, binsize);
+    // (a recorded batch has the LDS build only, with the 160 KB opt-in: ~38 k features per table)
+    if (t_rec && lds > 156 * 1024) t_rec->broken = true;
+    if (t_rec || lds <= 56 * 1024) {
+        bin_index_lds_opt_in();
+        const BinIndexJob a = {J, ub, vb, binsize, njobs};
+        launch_or_record(stream, kd_bin_index, a, dim3(t_rec ? 8 : njobs), lds);
     } else {
         for (int j = 0; j < njobs; j++)
             hipLaunchKernelGGL(k_bin_index, dim3(1), dim3(1024), 0, (hipStream_t)stream, J.table[j], J.count[j], ub,
@@ -1419,50 +1332,33 @@ void mlaunch_match(void* stream, const MatchParams& P, const FeatView& m1p, cons
                    const FeatView& m1c, const FeatView& m2c, int nquery_cap, const float* ranges,
                    int use_prior, svh_p_match* slots, int32_t* flags, int32_t* pixel_owner,
                    svh_p_match* out, int32_t* out_count, int32_t* out_count_host) {
-    hipStream_t s = (hipStream_t)stream;
     const FeatView& q = P.method == 2 ? m1p : m1c;
     if (P.method < 2) mlaunch_fill(stream, pixel_owner, 0x7F, (size_t)P.width * P.height * sizeof(int32_t));
     MatchJob am;
     am.P = P; am.m1p = m1p; am.m2p = m2p; am.m1c = m1c; am.m2c = m2c; am.ranges = ranges; am.use_prior = use_prior;
     am.out = slots; am.flags = flags; am.pixel_owner = pixel_owner;
     const DedupeJob ad = {q.count, P.width, slots, flags, pixel_owner};
-    const CompactMatchesJob ac = {slots, flags, q.count, out, out_count};
-    if (t_rec) {
-        if (nquery_cap > 0) {
-            t_rec->add(b_match, am, (nquery_cap * kQ + 127) / 128);
-            if (P.method < 2) t_rec->add(b_dedupe, ad, (nquery_cap + 255) / 256);
-        }
-        return t_rec->add(b_compact_matches, ac, 1);
-    }
+    const CompactMatchesJob ac = {slots, flags, q.count, out, out_count, out_count_host};
     if (nquery_cap > 0) {
-        hipLaunchKernelGGL(k_match, dim3((nquery_cap * kQ + 127) / 128), dim3(128), 0, s, am);
-        if (P.method < 2) hipLaunchKernelGGL(k_match_dedupe, dim3((nquery_cap + 255) / 256), dim3(256), 0, s, ad);
+        launch_or_record(stream, kd_match, am, dim3((nquery_cap * kQ + 127) / 128));
+        if (P.method < 2) launch_or_record(stream, kd_dedupe, ad, dim3((nquery_cap + 255) / 256));
     }
-    hipLaunchKernelGGL(k_compact_matches, dim3(1), dim3(1024), 0, s, ac, out_count_host);
+    launch_or_record(stream, kd_compact_matches, ac, dim3(1));
 }
 
 void mlaunch_refine(void* stream, svh_p_match* m, const int32_t* count, int cap, int method, int margin,
                     const SobelView& s1p, const SobelView& s2p, const SobelView& s1c,
                     const SobelView& s2c, int parabolic, int32_t* flags, svh_p_match* compacted,
                     int32_t* compacted_count) {
-    hipStream_t s = (hipStream_t)stream;
     const RefineJob ar = {m, count, method, margin, s1p, s2p, s1c, s2c, flags};
     if (!parabolic) {
-        if (cap > 0) {
-            const unsigned gx = (unsigned)(((size_t)cap * 32 + 255) / 256);
-            if (t_rec) return t_rec->add(b_refine_group, ar, gx);
-            hipLaunchKernelGGL(k_refine_group, dim3(gx), dim3(256), 0, s, ar);
-        }
+        if (cap > 0) launch_or_record(stream, kd_refine_group, ar, dim3((unsigned)(((size_t)cap * 32 + 255) / 256)));
         return;
     }
     // matches whose fit failed are dropped, order preserved (matcher.cpp:1766-1816)
-    const CompactMatchesJob ac = {m, flags, count, compacted, compacted_count};
-    if (t_rec) {
-        if (cap > 0) t_rec->add(b_refine_parabolic, ar, (cap + 127) / 128);
-        return t_rec->add(b_compact_matches, ac, 1);
-    }
-    if (cap > 0) hipLaunchKernelGGL(k_refine_parabolic, dim3((cap + 127) / 128), dim3(128), 0, s, ar);
-    hipLaunchKernelGGL(k_compact_matches, dim3(1), dim3(1024), 0, s, ac, (int32_t*)nullptr);
+    const CompactMatchesJob ac = {m, flags, count, compacted, compacted_count, nullptr};
+    if (cap > 0) launch_or_record(stream, kd_refine_parabolic, ar, dim3((cap + 127) / 128));
+    launch_or_record(stream, kd_compact_matches, ac, dim3(1));
 }
 
 }  // namespace svh

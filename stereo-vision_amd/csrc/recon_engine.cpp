@@ -23,6 +23,7 @@
 #include "../../include/matrix.h"
 #include "../../include/svh.h"
 #include "hip_guard.h"
+#include "matcher_internal.h"
 #include "recon_core.h"
 #include "recon_internal.h"
 #include "vo_internal.h"
@@ -207,9 +208,9 @@ int run_lost(svh_recon* r, const std::vector<int32_t>& lost, size_t n_px, const 
     const float* d_px = reinterpret_cast<const float*>(d_order + n_lost);
     const double t_launch = now_ms();
     if (r->timing) (void)hipEventRecord(r->ev[0], r->stream);
-    vlaunch_upload(r->stream, h, reinterpret_cast<uint8_t*>(r->d_frames.p) + rec * (size_t)r->dev_frames,
+    mlaunch_upload(r->stream, h, reinterpret_cast<uint8_t*>(r->d_frames.p) + rec * (size_t)r->dev_frames,
                    rec * (size_t)new_frames);   // (44 doubles: a multiple of 16 bytes)
-    vlaunch_upload(r->stream, h + frames_bytes, r->d_in + frames_bytes, csr_bytes);
+    mlaunch_upload(r->stream, h + frames_bytes, r->d_in + frames_bytes, csr_bytes);
     r->h_count[0] = -1;
     rlaunch_tracks(r->stream, d_offs, d_first, r->sort_by_length ? d_order : nullptr, d_px, n_lost, (int32_t)n_px,
                    r->d_frames, total_frames, s, r->d_code, r->d_xyz, r->d_points, r->n_points, r->h_code, r->h_xyz,

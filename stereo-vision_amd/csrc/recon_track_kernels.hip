@@ -12,6 +12,7 @@
 
 #include <algorithm>
 
+#include "dev_common.h"
 #include "recon_internal.h"
 
 namespace svh {
@@ -25,93 +26,63 @@ constexpr int RT_LANES = 64;   // k_rt_tracks: lanes (tracks) per workgroup, the
 constexpr int RT_SLAB = 40;    // J 16 | V 16 | w 4 | rv1 4
 constexpr int RT_NONE = INT_MAX;
 
-// a pointer out of the job table is device (or device-mapped pinned host) memory: say so, or the compiler goes
-// through FLAT instructions (see gptr in matcher_kernels.hip)
-template <class T>
-__device__ __forceinline__ T* gp(T* p) {
-    __attribute__((address_space(1))) T* q = (__attribute__((address_space(1))) T*)p;
-    asm volatile("" : "+v"(q));
-    return (T*)q;
-}
+// a pointer out of the job table is device (or device-mapped pinned host) memory: as_global (dev_common.h) says so
 
 __global__ __launch_bounds__(256) void k_rt_stage(const ReconJob* __restrict__ J) {
     const ReconJob& a = J[blockIdx.y];
     const int32_t at = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
     for (int seg = 0; seg < 2; seg++) {
-        const uint4* src = reinterpret_cast<const uint4*>(gp(a.up_src[seg]));
-        uint4* dst = reinterpret_cast<uint4*>(gp(a.up_dst[seg]));
+        const uint4* src = reinterpret_cast<const uint4*>(as_global(a.up_src[seg]));
+        uint4* dst = reinterpret_cast<uint4*>(as_global(a.up_dst[seg]));
         const int32_t n16 = (int32_t)(a.up_bytes[seg] / 16);
         for (int32_t k = at; k < n16; k += step) dst[k] = src[k];
     }
-    int32_t* tidx = gp(a.track_idx);
+    int32_t* tidx = as_global(a.track_idx);
     for (int32_t k = at; k < a.tbl; k += step) tidx[k] = -1;
-    int32_t* claim = gp(a.claim);
+    int32_t* claim = as_global(a.claim);
     for (int32_t k = at; k < a.n_old; k += step) claim[k] = RT_NONE;
-    if (at < RT_HDR) gp(a.hdr)[at] = 0;
+    if (at < RT_HDR) as_global(a.hdr)[at] = 0;
 }
 
 __global__ __launch_bounds__(256) void k_rt_scatter(const ReconJob* __restrict__ J) {
     const ReconJob& a = J[blockIdx.y];
     const int32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= a.n_old) return;
-    const int32_t li = gp(a.a_last)[t];
-    if (li >= 0 && li < a.tbl) atomicMax(gp(a.track_idx) + li, t);
+    const int32_t li = as_global(a.a_last)[t];
+    if (li >= 0 && li < a.tbl) atomicMax(as_global(a.track_idx) + li, t);
 }
 
 __global__ __launch_bounds__(256) void k_rt_associate(const ReconJob* __restrict__ J) {
     const ReconJob& a = J[blockIdx.y];
     const int32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
-    const svh_p_match* m = gp(a.m);
+    const svh_p_match* m = as_global(a.m);
     const int32_t ip = m[i].i1p, ic = m[i].i1c;
     int32_t idx = -1;
     if (ip < 0 || ip >= a.max_index || ic < 0 || ic >= a.max_index) {
-        atomicOr(gp(a.hdr) + RT_ERROR, RT_BAD_INDEX);
+        atomicOr(as_global(a.hdr) + RT_ERROR, RT_BAD_INDEX);
     } else {
-        idx = gp(a.track_idx)[ip];   // (max_index <= tbl)
+        idx = as_global(a.track_idx)[ip];   // (max_index <= tbl)
         if (idx >= a.n_old) idx = -1;
-        if (idx >= 0) atomicMin(gp(a.claim) + idx, i);
+        if (idx >= 0) atomicMin(as_global(a.claim) + idx, i);
     }
-    gp(a.midx)[i] = idx;
-}
-
-// exclusive prefix sum of `value` over the 1024 threads of the workgroup, in thread order
-__device__ __forceinline__ int32_t rt_scan_1024(int32_t value, int32_t* total) {
-    __shared__ int32_t s_wave[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int32_t incl = value;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-        const int32_t x = s_wave[w];
-        before += w < wave ? x : 0;
-        all += x;
-    }
-    __syncthreads();   // (s_wave is written again by the next scan)
-    *total = all;
-    return before + incl - value;
+    as_global(a.midx)[i] = idx;
 }
 
 // One workgroup per object; thread t owns a contiguous run of old tracks and a contiguous run of matches, so thread
 // order is track / match order.
 __global__ __launch_bounds__(1024) void k_rt_scan(const ReconJob* __restrict__ J) {
     const ReconJob& a = J[blockIdx.y];
+    __shared__ int32_t s_wave[16];
     const int t = threadIdx.x;
-    int32_t* hdr = gp(a.hdr);
+    int32_t* hdr = as_global(a.hdr);
     if ((int64_t)a.n_old + a.n > a.cap_tracks) {   // (uniform over the workgroup)
         if (t == 0) atomicOr(hdr + RT_ERROR, RT_NO_ROOM);
         return;
     }
-    const int32_t* claim = gp(a.claim);
-    const int32_t* a_offs = gp(a.a_offs);
-    int32_t *src = gp(a.src), *b_offs = gp(a.b_offs), *lost = gp(a.lost);
+    const int32_t* claim = as_global(a.claim);
+    const int32_t* a_offs = as_global(a.a_offs);
+    int32_t *src = as_global(a.src), *b_offs = as_global(a.b_offs), *lost = as_global(a.lost);
     // ---- old tracks: extended ones keep their order at the front of B, lost ones are listed in order
     const int32_t ct = (a.n_old + 1023) / 1024;
     const int32_t lo = min(t * ct, a.n_old), hi = min(lo + ct, a.n_old);
@@ -122,8 +93,8 @@ __global__ __launch_bounds__(1024) void k_rt_scan(const ReconJob* __restrict__ J
             px += a_offs[k + 1] - a_offs[k] + 1;
         }
     int32_t n_ext, ext_px;
-    int32_t at = rt_scan_1024(ext, &n_ext);
-    int32_t at_px = rt_scan_1024(px, &ext_px);
+    int32_t at = block_exclusive_scan<1024>(ext, s_wave, &n_ext);
+    int32_t at_px = block_exclusive_scan<1024>(px, s_wave, &ext_px);
     int32_t at_lost = lo - at;
     for (int32_t k = lo; k < hi; k++) {
         if (claim[k] != RT_NONE) {
@@ -136,7 +107,7 @@ __global__ __launch_bounds__(1024) void k_rt_scan(const ReconJob* __restrict__ J
         }
     }
     // ---- matches: one that did not win its track (or reached none) creates a track, in match order
-    const int32_t* midx = gp(a.midx);
+    const int32_t* midx = as_global(a.midx);
     const int32_t cm = (a.n + 1023) / 1024;
     const int32_t mlo = min(t * cm, a.n), mhi = min(mlo + cm, a.n);
     int32_t cr = 0;
@@ -145,7 +116,7 @@ __global__ __launch_bounds__(1024) void k_rt_scan(const ReconJob* __restrict__ J
         cr += !(idx >= 0 && claim[idx] == i);
     }
     int32_t n_cr;
-    int32_t at_cr = rt_scan_1024(cr, &n_cr);
+    int32_t at_cr = block_exclusive_scan<1024>(cr, s_wave, &n_cr);
     for (int32_t i = mlo; i < mhi; i++) {
         const int32_t idx = midx[i];
         if (!(idx >= 0 && claim[idx] == i)) {
@@ -168,27 +139,27 @@ __global__ __launch_bounds__(1024) void k_rt_scan(const ReconJob* __restrict__ J
 __global__ __launch_bounds__(256) void k_rt_gather(const ReconJob* __restrict__ J) {
     const ReconJob& a = J[blockIdx.y];
     const int32_t d = blockIdx.x * 256 + threadIdx.x;
-    const int32_t* hdr = gp(a.hdr);
+    const int32_t* hdr = as_global(a.hdr);
     if (hdr[RT_ERROR] || d >= hdr[RT_EXTENDED] + hdr[RT_CREATED]) return;
-    const svh_p_match* m = gp(a.m);
-    const int32_t s = gp(a.src)[d], o = gp(a.b_offs)[d];
-    float2* out = reinterpret_cast<float2*>(gp(a.b_px));
+    const svh_p_match* m = as_global(a.m);
+    const int32_t s = as_global(a.src)[d], o = as_global(a.b_offs)[d];
+    float2* out = reinterpret_cast<float2*>(as_global(a.b_px));
     if (s >= 0) {   // old track s, extended by match claim[s]
         if (s >= a.n_old) return;
-        const int32_t ao = gp(a.a_offs)[s], len = gp(a.a_offs)[s + 1] - ao, i = gp(a.claim)[s];
+        const int32_t ao = as_global(a.a_offs)[s], len = as_global(a.a_offs)[s + 1] - ao, i = as_global(a.claim)[s];
         if (i < 0 || i >= a.n || ao < 0 || len < 0 || ao + len > a.old_px || o < 0 || o + len + 1 > a.cap_px) return;
-        const float2* in = reinterpret_cast<const float2*>(gp(a.a_px));
+        const float2* in = reinterpret_cast<const float2*>(as_global(a.a_px));
         for (int32_t k = 0; k < len; k++) out[o + k] = in[ao + k];
         out[o + len] = make_float2(m[i].u1c, m[i].v1c);
-        gp(a.b_first)[d] = gp(a.a_first)[s];
-        gp(a.b_last)[d] = m[i].i1c;
+        as_global(a.b_first)[d] = as_global(a.a_first)[s];
+        as_global(a.b_last)[d] = m[i].i1c;
     } else {        // created by match ~s
         const int32_t i = ~s;
         if (i >= a.n || o < 0 || o + 2 > a.cap_px) return;
         out[o] = make_float2(m[i].u1p, m[i].v1p);
         out[o + 1] = make_float2(m[i].u1c, m[i].v1c);
-        gp(a.b_first)[d] = a.frame_prev;
-        gp(a.b_last)[d] = m[i].i1c;
+        as_global(a.b_first)[d] = a.frame_prev;
+        as_global(a.b_last)[d] = m[i].i1c;
     }
 }
 
@@ -198,22 +169,22 @@ __global__ __launch_bounds__(RT_LANES) void k_rt_tracks(const ReconJob* __restri
     const ReconJob& a = J[blockIdx.y];
     const int lane = threadIdx.x;
     const int32_t g = blockIdx.x * RT_LANES + lane;
-    const int32_t* hdr = gp(a.hdr);
+    const int32_t* hdr = as_global(a.hdr);
     if (hdr[RT_ERROR] || g >= hdr[RT_LOST]) return;
-    const int32_t t = gp(a.lost)[g];
+    const int32_t t = as_global(a.lost)[g];
     double* base = slab + lane;
     const Mat Jm{base, 4, RT_LANES}, V{base + 16 * RT_LANES, 4, RT_LANES};
     const Vec w{base + 32 * RT_LANES, RT_LANES}, rv1{base + 36 * RT_LANES, RT_LANES};
     float p[3] = {0.f, 0.f, 0.f};
     int32_t c = recon::INIT_FAILED;
     if (t >= 0 && t < a.n_old) {
-        const int32_t o = gp(a.a_offs)[t], nf = gp(a.a_offs)[t + 1] - o, f0 = gp(a.a_first)[t];
+        const int32_t o = as_global(a.a_offs)[t], nf = as_global(a.a_offs)[t + 1] - o, f0 = as_global(a.a_first)[t];
         // a track that would read outside the pixel or frame arrays is not evaluated
         if (nf >= 2 && o >= 0 && o + nf <= a.old_px && f0 >= 0 && f0 + nf <= a.n_frames)
-            c = recon::track_outcome(gp(a.frames), f0, gp(a.a_px) + 2 * (size_t)o, nf, a.s, Jm, V, w, rv1, p);
+            c = recon::track_outcome(as_global(a.frames), f0, as_global(a.a_px) + 2 * (size_t)o, nf, a.s, Jm, V, w, rv1, p);
     }
-    gp(a.code)[g] = c;
-    float* xyz = gp(a.xyz);
+    as_global(a.code)[g] = c;
+    float* xyz = as_global(a.xyz);
     xyz[3 * (size_t)g + 0] = p[0];
     xyz[3 * (size_t)g + 1] = p[1];
     xyz[3 * (size_t)g + 2] = p[2];
@@ -223,16 +194,16 @@ __global__ __launch_bounds__(RT_LANES) void k_rt_tracks(const ReconJob* __restri
 __global__ __launch_bounds__(256) void k_rt_compact(const ReconJob* __restrict__ J) {
     __shared__ int32_t s_wave[4];
     const ReconJob& a = J[blockIdx.y];
-    const int32_t* hdr = gp(a.hdr);
-    int32_t* out_hdr = gp(a.out_hdr);
+    const int32_t* hdr = as_global(a.hdr);
+    int32_t* out_hdr = as_global(a.out_hdr);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int32_t err = hdr[RT_ERROR];
     const int32_t n_lost = err ? 0 : min(hdr[RT_LOST], a.n_old);
-    const int32_t* code = gp(a.code);
-    const float* xyz = gp(a.xyz);
-    float* points = gp(a.points);
-    int32_t* out_code = gp(a.out_code);
-    float* out_xyz = gp(a.out_xyz);
+    const int32_t* code = as_global(a.code);
+    const float* xyz = as_global(a.xyz);
+    float* points = as_global(a.points);
+    int32_t* out_code = as_global(a.out_code);
+    float* out_xyz = as_global(a.out_xyz);
     int32_t running = a.n_points;
     for (int32_t b = 0; b < n_lost; b += 256) {
         const int32_t i = b + (int32_t)threadIdx.x;

@@ -16,6 +16,7 @@
 #include "../../include/svh.h"
 #include "batch_rec.h"
 #include "hip_guard.h"
+#include "matcher_internal.h"
 #include "vo_internal.h"
 
 using namespace svh;
@@ -124,7 +125,7 @@ void estimate_enqueue(svh_vo* v, int32_t N) {
     const size_t m_bytes = ((size_t)N * sizeof(svh_p_match) + 15) & ~(size_t)15;
     const size_t s_bytes = ((size_t)iters * 3 * sizeof(int32_t) + 15) & ~(size_t)15;
     hipStream_t s = v->stream;
-    vlaunch_upload(s, v->h_in, v->d_in, m_bytes + s_bytes);
+    mlaunch_upload(s, v->h_in, v->d_in, m_bytes + s_bytes);
     VoCalib c;
     c.f = P.f; c.cu = P.cu; c.cv = P.cv; c.base = P.base;
     c.inlier_threshold = P.inlier_threshold;

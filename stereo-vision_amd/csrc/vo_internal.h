@@ -80,8 +80,6 @@ struct RandStream {
 // bucketFeatures drawing from `rs` (matcher_engine.cpp)
 int32_t bucket_features(svh_matcher* m, int32_t max_features, float bw, float bh, RandStream& rs);
 
-// pinned host -> device copy by a kernel (bytes is a multiple of 16)
-void vlaunch_upload(void* stream, const uint8_t* pinned, uint8_t* dev, size_t bytes);
 void vlaunch_estimate(void* stream, const svh_p_match* pm, int N, const int32_t* samples, int iters,
                       const VoCalib& c, double* hyp_tr, int32_t* hyp_count, uint8_t* hyp_flags, double* Jg,
                       double* resg, VoResult* out, int32_t* out_inliers);

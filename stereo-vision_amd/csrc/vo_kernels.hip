@@ -16,7 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/svh.h"
-#include "batch_rec.h"
+#include "job_kernel.h"
 #include "vo_internal.h"
 
 namespace svh {
@@ -404,21 +404,7 @@ __device__ __forceinline__ void d_vo_refine(const svh_p_match* __restrict__ pm, 
         const int lo = min(t * chunk, N), hi = min(lo + chunk, N);
         int mine = 0;
         for (int i = lo; i < hi; i++) mine += fl[i];
-        // (scan inside each wave by shuffles, the four wave totals through LDS: two barriers instead of sixteen)
-        const int lane = t & 63, wave = t >> 6;
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) s_scan[wave] = incl;
-        __syncthreads();
-        int pos = incl - mine;
-        for (int w = 0; w < 4; w++) {
-            pos += w < wave ? s_scan[w] : 0;
-            nin += s_scan[w];
-        }
+        int pos = block_exclusive_scan<256>(mine, s_scan, &nin);   // (best is uniform: every thread is here)
         for (int i = lo; i < hi; i++)
             if (fl[i]) out_inliers[pos++] = i;
         if (t < 6) s_tr[t] = hyp_tr[6 * best + t];
@@ -441,87 +427,46 @@ __device__ __forceinline__ void d_vo_refine(const svh_p_match* __restrict__ pm, 
     }
 }
 
-// plain and batched forms (batch_rec.h: job blockIdx.z of a table in device memory)
-// (pointers read from the job table are told to be global memory: global_load instead of flat_load, see gptr in
-// matcher_kernels.hip)
-template <class T>
-__device__ __forceinline__ T* vgptr(T* p) {
-    __attribute__((address_space(1))) T* q = (__attribute__((address_space(1))) T*)p;
-    asm volatile("" : "+v"(q));
-    return (T*)q;
-}
+// plain and batched entries (job_kernel.h)
 struct VoRansacJob { const svh_p_match* pm; int N; const int32_t* samples; VoCalib c; double* hyp_tr; int32_t* hyp_count; uint8_t* hyp_flags; int iters; };
-__global__ __launch_bounds__(64) void k_vo_ransac(VoRansacJob a) {
-    d_vo_ransac(a.pm, a.N, a.samples, a.c, a.hyp_tr, a.hyp_count, a.hyp_flags, (int)blockIdx.x);
+__device__ __forceinline__ VoRansacJob globalise(VoRansacJob a) {
+    all_global(a.pm, a.samples, a.hyp_tr, a.hyp_count, a.hyp_flags);
+    return a;
 }
-__global__ __launch_bounds__(64) void k_vo_ransac_b(const VoRansacJob* J) {
-    const VoRansacJob& a = J[blockIdx.z];
-    if ((int)blockIdx.x >= a.iters) return;
-    d_vo_ransac(vgptr(a.pm), a.N, vgptr(a.samples), a.c, vgptr(a.hyp_tr), vgptr(a.hyp_count), vgptr(a.hyp_flags), (int)blockIdx.x);
+__device__ __forceinline__ void d_vo_ransac(const VoRansacJob& a, unsigned bx, unsigned) {
+    d_vo_ransac(a.pm, a.N, a.samples, a.c, a.hyp_tr, a.hyp_count, a.hyp_flags, (int)bx);
 }
+SVH_JOB_KERNEL(kd_vo_ransac, , k_vo_ransac, k_vo_ransac_b, VoRansacJob, 64, 1, d_vo_ransac, (int)blockIdx.x < a.iters)
+
 struct VoRefineJob {
     const svh_p_match* pm; int N, iters; VoCalib c; const double* hyp_tr; const int32_t* hyp_count; const uint8_t* hyp_flags;
     double *Jg, *resg; int lds_rows; VoResult* out; int32_t* out_inliers;
 };
-__global__ __launch_bounds__(256) void k_vo_refine(VoRefineJob a) {
+__device__ __forceinline__ VoRefineJob globalise(VoRefineJob a) {
+    all_global(a.pm, a.hyp_tr, a.hyp_count, a.hyp_flags, a.Jg, a.resg, a.out, a.out_inliers);
+    return a;
+}
+__device__ __forceinline__ void d_vo_refine(const VoRefineJob& a, unsigned, unsigned) {
     d_vo_refine(a.pm, a.N, a.iters, a.c, a.hyp_tr, a.hyp_count, a.hyp_flags, a.Jg, a.resg, a.lds_rows, a.out, a.out_inliers);
 }
-__global__ __launch_bounds__(256) void k_vo_refine_b(const VoRefineJob* J) {
-    const VoRefineJob& a = J[blockIdx.z];
-    d_vo_refine(vgptr(a.pm), a.N, a.iters, a.c, vgptr(a.hyp_tr), vgptr(a.hyp_count), vgptr(a.hyp_flags), vgptr(a.Jg), vgptr(a.resg),
-                a.lds_rows, vgptr(a.out), vgptr(a.out_inliers));
-}
-struct VoUploadJob { const uint4* host; uint4* dev; size_t n16; };
-__global__ __launch_bounds__(256) void k_vo_upload(VoUploadJob a) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < a.n16) a.dev[i] = a.host[i];
-}
-__global__ __launch_bounds__(256) void k_vo_upload_b(const VoUploadJob* J) {
-    const VoUploadJob a = J[blockIdx.z];
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < a.n16) vgptr(a.dev)[i] = vgptr(a.host)[i];
-}
-static void b_vo_ransac(const void* jobs, int njobs, unsigned gx, unsigned gy, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(k_vo_ransac_b, dim3(gx, gy, (unsigned)njobs), dim3(64), lds, s, reinterpret_cast<const VoRansacJob*>(jobs));
-}
-static void b_vo_refine(const void* jobs, int njobs, unsigned gx, unsigned gy, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(k_vo_refine_b, dim3(gx, gy, (unsigned)njobs), dim3(256), lds, s, reinterpret_cast<const VoRefineJob*>(jobs));
-}
-static void b_vo_upload(const void* jobs, int njobs, unsigned gx, unsigned gy, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(k_vo_upload_b, dim3(gx, gy, (unsigned)njobs), dim3(256), lds, s, reinterpret_cast<const VoUploadJob*>(jobs));
-}
-
-void vlaunch_upload(void* stream, const uint8_t* pinned, uint8_t* dev, size_t bytes) {
-    const size_t n16 = bytes / 16;
-    const VoUploadJob a = {reinterpret_cast<const uint4*>(pinned), reinterpret_cast<uint4*>(dev), n16};
-    const unsigned gx = (unsigned)((n16 + 255) / 256);
-    if (t_rec) return t_rec->add(b_vo_upload, a, gx);
-    hipLaunchKernelGGL(k_vo_upload, dim3(gx), dim3(256), 0, (hipStream_t)stream, a);
+SVH_JOB_KERNEL(kd_vo_refine, , k_vo_refine, k_vo_refine_b, VoRefineJob, 256, 1, d_vo_refine, true)
+// dynamic LDS for the refinement rows: 4 rows per match, 7 doubles per row, up to 144 KB
+static void vo_refine_lds_opt_in() {
+    static const bool once = (allow_dynamic_lds(kd_vo_refine, k_vo_refine_b, 144 * 1024), true);
+    (void)once;
 }
 
 void vlaunch_estimate(void* stream, const svh_p_match* pm, int N, const int32_t* samples, int iters,
                       const VoCalib& c, double* hyp_tr, int32_t* hyp_count, uint8_t* hyp_flags, double* Jg,
                       double* resg, VoResult* out, int32_t* out_inliers) {
-    hipStream_t s = (hipStream_t)stream;
-    // dynamic LDS for the refinement rows: 4 rows per match, 7 doubles per row, up to 144 KB
-    static bool attr_once = ((void)hipFuncSetAttribute((const void*)k_vo_refine,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       144 * 1024),
-                             (void)hipFuncSetAttribute((const void*)k_vo_refine_b,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       144 * 1024), true);
-    (void)attr_once;
+    vo_refine_lds_opt_in();
     int lds_rows = ((4 * N + 7) & ~7) + 8;   // (+ 8: the sums read one turn ahead)
     if ((size_t)lds_rows * 7 * sizeof(double) > 144 * 1024) lds_rows = 0;
     const VoRansacJob ar = {pm, N, samples, c, hyp_tr, hyp_count, hyp_flags, iters};
     const VoRefineJob af = {pm, N, iters, c, hyp_tr, hyp_count, hyp_flags, Jg, resg, lds_rows, out, out_inliers};
     const size_t lds = (size_t)lds_rows * 7 * sizeof(double);
-    if (t_rec) {
-        if (iters > 0) t_rec->add(b_vo_ransac, ar, (unsigned)iters);
-        return t_rec->add(b_vo_refine, af, 1, 1, lds);
-    }
-    if (iters > 0) hipLaunchKernelGGL(k_vo_ransac, dim3(iters), dim3(64), 0, s, ar);
-    hipLaunchKernelGGL(k_vo_refine, dim3(1), dim3(256), lds, s, af);
+    if (iters > 0) launch_or_record(stream, kd_vo_ransac, ar, dim3(iters));
+    launch_or_record(stream, kd_vo_refine, af, dim3(1), lds);
 }
 
 }  // namespace svh

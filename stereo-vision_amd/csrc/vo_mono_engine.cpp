@@ -25,6 +25,7 @@
 #include "../../include/svh.h"
 #include "batch_rec.h"
 #include "hip_guard.h"
+#include "matcher_internal.h"
 #include "mono_core.h"
 #include "vo_internal.h"
 
@@ -247,15 +248,15 @@ void mono_enqueue(MonoVo* M, int phase) {
     const float* d_q = reinterpret_cast<const float*>(M->d_in.p);
     const float* d_m = reinterpret_cast<const float*>(M->d_in + 16 * (size_t)N);
     if (phase == 0) {
-        vlaunch_upload(M->stream, M->h_in, M->d_in, 32 * (size_t)N + up16(32 * (size_t)iters));
+        mlaunch_upload(M->stream, M->h_in, M->d_in, 32 * (size_t)N + up16(32 * (size_t)iters));
         mlaunch_ransac(M->stream, d_q, N, reinterpret_cast<const int32_t*>(M->d_in + 32 * (size_t)N), iters,
                        P.inlier_threshold, M->d_F, M->d_counts, M->h_sel, M->h_flags, M->h_counts);
     } else if (phase == 1) {
-        vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_cams.p), reinterpret_cast<uint8_t*>(M->d_cams.p),
+        mlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_cams.p), reinterpret_cast<uint8_t*>(M->d_cams.p),
                        60 * sizeof(double));
         mlaunch_chiral(M->stream, d_m, N, M->d_cams, M->d_X, M->d_front, M->h_X, M->h_sel + 4);
     } else {
-        vlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_d.p), reinterpret_cast<uint8_t*>(M->d_d.p),
+        mlaunch_upload(M->stream, reinterpret_cast<const uint8_t*>(M->h_d.p), reinterpret_cast<uint8_t*>(M->d_d.p),
                        up16(8 * (size_t)M->n));
         mlaunch_plane(M->stream, M->d_d, M->n, M->weight, M->thr, M->h_sums);
     }

@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "batch_rec.h"
+#include "job_kernel.h"
 #include "mono_core.h"
 #include "vo_internal.h"
 
@@ -38,17 +38,10 @@ constexpr int HYP_SLAB = 171;     // U 72 | V 81 | w 9 | rv1 9
 constexpr int CHI_LANES = 64;     // lanes per workgroup of k_mono_chiral: 40 x 8 B x 64 = 20 KB LDS
 constexpr int CHI_SLAB = 40;      // J 16 | V 16 | w 4 | rv1 4
 
-// Every kernel is a __device__ body with two entries (as in vo_kernels.hip): the plain form takes its job by value,
-// the batched form `_b` reads job blockIdx.z of a table in device memory (batch_rec.h), grid x is the largest job's and
-// blocks beyond a job's own extent return at once.  Both run the same body, so a batched lane computes bit for bit
-// what the single launch computes.  Pointers read from the table are told to be global memory (global_load instead
-// of flat_load).
-template <class T>
-__device__ __forceinline__ T* mgptr(T* p) {
-    __attribute__((address_space(1))) T* q = (__attribute__((address_space(1))) T*)p;
-    asm volatile("" : "+v"(q));
-    return (T*)q;
-}
+// Every kernel is a __device__ body with two entries made by one SVH_JOB_KERNEL line (job_kernel.h): the plain form
+// takes its job by value, the batched form `_b` reads job blockIdx.z of a table in device memory, grid x is the largest
+// job's and blocks beyond a job's own extent return at once (the line's last argument).  Both run the same body, so a
+// batched lane computes bit for bit what the single launch computes.
 
 struct MonoHypJob { const float4* q; const int32_t* samples; double* F; int32_t N, iters; };
 struct MonoVoteJob { const float4* q; const double* F; int32_t* counts; double thr; int32_t N, iters; };
@@ -59,6 +52,18 @@ struct MonoSelectJob {
 struct MonoChiralJob { const float4* m; const double* cams; double* X; uint8_t* front; int32_t N; };
 struct MonoPickJob { const double* X; const uint8_t* front; double* out_X; int32_t* out_cand; int32_t N; };
 struct MonoPlaneJob { const double* d; double* sums; double weight, thr; int32_t n; };
+__device__ __forceinline__ MonoHypJob globalise(MonoHypJob a) { all_global(a.q, a.samples, a.F); return a; }
+__device__ __forceinline__ MonoVoteJob globalise(MonoVoteJob a) { all_global(a.q, a.F, a.counts); return a; }
+__device__ __forceinline__ MonoSelectJob globalise(MonoSelectJob a) {
+    all_global(a.counts, a.F, a.q, a.out_sel, a.out_flags, a.out_counts);
+    return a;
+}
+__device__ __forceinline__ MonoChiralJob globalise(MonoChiralJob a) { all_global(a.m, a.cams, a.X, a.front); return a; }
+__device__ __forceinline__ MonoPickJob globalise(MonoPickJob a) {
+    all_global(a.X, a.front, a.out_X, a.out_cand);
+    return a;
+}
+__device__ __forceinline__ MonoPlaneJob globalise(MonoPlaneJob a) { all_global(a.d, a.sums); return a; }
 
 __device__ __forceinline__ void d_mono_hyp(double* slab, const float4* __restrict__ q, int32_t N,
                                            const int32_t* __restrict__ samples, int32_t iters,
@@ -84,16 +89,12 @@ __device__ __forceinline__ void d_mono_hyp(double* slab, const float4* __restric
     mono::rank2(U3, V3, w, F);
     for (int i = 0; i < 9; i++) Fout[9 * (size_t)h + i] = F[i];
 }
-__global__ __launch_bounds__(HYP_LANES) void k_mono_hyp(MonoHypJob a) {
+__device__ __forceinline__ void d_mono_hyp(const MonoHypJob& a, unsigned, unsigned) {
     __shared__ double slab[HYP_SLAB * HYP_LANES];
     d_mono_hyp(slab, a.q, a.N, a.samples, a.iters, a.F);
 }
-__global__ __launch_bounds__(HYP_LANES) void k_mono_hyp_b(const MonoHypJob* J) {
-    __shared__ double slab[HYP_SLAB * HYP_LANES];
-    const MonoHypJob& a = J[blockIdx.z];
-    if ((int)(blockIdx.x * HYP_LANES) >= a.iters) return;
-    d_mono_hyp(slab, mgptr(a.q), a.N, mgptr(a.samples), a.iters, mgptr(a.F));
-}
+SVH_JOB_KERNEL(kd_mono_hyp, , k_mono_hyp, k_mono_hyp_b, MonoHypJob, HYP_LANES, 1, d_mono_hyp,
+               (int)(blockIdx.x * HYP_LANES) < a.iters)
 
 __device__ __forceinline__ void d_mono_vote(const float4* __restrict__ q, int32_t N, const double* __restrict__ Fs,
                                             double thr, int32_t* __restrict__ counts) {
@@ -112,12 +113,10 @@ __device__ __forceinline__ void d_mono_vote(const float4* __restrict__ q, int32_
     }
     if (threadIdx.x == 0) counts[h] = c;
 }
-__global__ __launch_bounds__(64) void k_mono_vote(MonoVoteJob a) { d_mono_vote(a.q, a.N, a.F, a.thr, a.counts); }
-__global__ __launch_bounds__(64) void k_mono_vote_b(const MonoVoteJob* J) {
-    const MonoVoteJob& a = J[blockIdx.z];
-    if ((int)blockIdx.x >= a.iters) return;
-    d_mono_vote(mgptr(a.q), a.N, mgptr(a.F), a.thr, mgptr(a.counts));
+__device__ __forceinline__ void d_mono_vote(const MonoVoteJob& a, unsigned, unsigned) {
+    d_mono_vote(a.q, a.N, a.F, a.thr, a.counts);
 }
+SVH_JOB_KERNEL(kd_mono_vote, , k_mono_vote, k_mono_vote_b, MonoVoteJob, 64, 1, d_mono_vote, (int)blockIdx.x < a.iters)
 
 __device__ __forceinline__ void d_mono_select(const int32_t* __restrict__ counts, int32_t iters,
                                               const double* __restrict__ Fs, const float4* __restrict__ q, int32_t N,
@@ -157,14 +156,10 @@ __device__ __forceinline__ void d_mono_select(const int32_t* __restrict__ counts
         out_sel[1] = most;
     }
 }
-__global__ __launch_bounds__(256) void k_mono_select(MonoSelectJob a) {
+__device__ __forceinline__ void d_mono_select(const MonoSelectJob& a, unsigned, unsigned) {
     d_mono_select(a.counts, a.iters, a.F, a.q, a.N, a.thr, a.out_sel, a.out_flags, a.out_counts);
 }
-__global__ __launch_bounds__(256) void k_mono_select_b(const MonoSelectJob* J) {
-    const MonoSelectJob& a = J[blockIdx.z];
-    d_mono_select(mgptr(a.counts), a.iters, mgptr(a.F), mgptr(a.q), a.N, a.thr, mgptr(a.out_sel), mgptr(a.out_flags),
-                  mgptr(a.out_counts));
-}
+SVH_JOB_KERNEL(kd_mono_select, , k_mono_select, k_mono_select_b, MonoSelectJob, 256, 1, d_mono_select, true)
 
 __device__ __forceinline__ void d_mono_chiral(double* slab, const float4* __restrict__ m, int32_t N,
                                               const double* __restrict__ cams, double* __restrict__ X,
@@ -182,16 +177,12 @@ __device__ __forceinline__ void d_mono_chiral(double* slab, const float4* __rest
     for (int r = 0; r < 4; r++) X[((size_t)cand * 4 + r) * N + i] = x[r];
     front[g] = ok;
 }
-__global__ __launch_bounds__(CHI_LANES) void k_mono_chiral(MonoChiralJob a) {
+__device__ __forceinline__ void d_mono_chiral(const MonoChiralJob& a, unsigned, unsigned) {
     __shared__ double slab[CHI_SLAB * CHI_LANES];
     d_mono_chiral(slab, a.m, a.N, a.cams, a.X, a.front);
 }
-__global__ __launch_bounds__(CHI_LANES) void k_mono_chiral_b(const MonoChiralJob* J) {
-    __shared__ double slab[CHI_SLAB * CHI_LANES];
-    const MonoChiralJob& a = J[blockIdx.z];
-    if ((int)(blockIdx.x * CHI_LANES) >= 4 * a.N) return;
-    d_mono_chiral(slab, mgptr(a.m), a.N, mgptr(a.cams), mgptr(a.X), mgptr(a.front));
-}
+SVH_JOB_KERNEL(kd_mono_chiral, , k_mono_chiral, k_mono_chiral_b, MonoChiralJob, CHI_LANES, 1, d_mono_chiral,
+               (int)(blockIdx.x * CHI_LANES) < 4 * a.N)
 
 __device__ __forceinline__ void d_mono_pick(const double* __restrict__ X, const uint8_t* __restrict__ front, int32_t N,
                                             double* __restrict__ out_X, int32_t* __restrict__ out_cand) {
@@ -223,11 +214,10 @@ __device__ __forceinline__ void d_mono_pick(const double* __restrict__ X, const 
         for (int r = 0; r < 4; r++) out_X[(size_t)r * N + i] = d != 0 ? Xc[(size_t)r * N + i] / d : 0.0;
     }
 }
-__global__ __launch_bounds__(256) void k_mono_pick(MonoPickJob a) { d_mono_pick(a.X, a.front, a.N, a.out_X, a.out_cand); }
-__global__ __launch_bounds__(256) void k_mono_pick_b(const MonoPickJob* J) {
-    const MonoPickJob& a = J[blockIdx.z];
-    d_mono_pick(mgptr(a.X), mgptr(a.front), a.N, mgptr(a.out_X), mgptr(a.out_cand));
+__device__ __forceinline__ void d_mono_pick(const MonoPickJob& a, unsigned, unsigned) {
+    d_mono_pick(a.X, a.front, a.N, a.out_X, a.out_cand);
 }
+SVH_JOB_KERNEL(kd_mono_pick, , k_mono_pick, k_mono_pick_b, MonoPickJob, 256, 1, d_mono_pick, true)
 
 __device__ __forceinline__ void d_mono_plane(const double* __restrict__ d, int32_t n, double weight, double thr,
                                              double* __restrict__ sums) {
@@ -242,72 +232,43 @@ __device__ __forceinline__ void d_mono_plane(const double* __restrict__ d, int32
         }
     sums[i] = sum;
 }
-__global__ __launch_bounds__(64) void k_mono_plane(MonoPlaneJob a) { d_mono_plane(a.d, a.n, a.weight, a.thr, a.sums); }
-__global__ __launch_bounds__(64) void k_mono_plane_b(const MonoPlaneJob* J) {
-    const MonoPlaneJob& a = J[blockIdx.z];
-    if ((int)(blockIdx.x * 64) >= a.n) return;
-    d_mono_plane(mgptr(a.d), a.n, a.weight, a.thr, mgptr(a.sums));
+__device__ __forceinline__ void d_mono_plane(const MonoPlaneJob& a, unsigned, unsigned) {
+    d_mono_plane(a.d, a.n, a.weight, a.thr, a.sums);
 }
-
-#define MONO_BATCHED(name, Job, kernel, threads)                                                                  \
-    void name(const void* jobs, int njobs, unsigned gx, unsigned gy, size_t lds, hipStream_t s) {                 \
-        hipLaunchKernelGGL(kernel, dim3(gx, gy, (unsigned)njobs), dim3(threads), lds, s,                          \
-                           reinterpret_cast<const Job*>(jobs));                                                   \
-    }
-MONO_BATCHED(b_mono_hyp, MonoHypJob, k_mono_hyp_b, HYP_LANES)
-MONO_BATCHED(b_mono_vote, MonoVoteJob, k_mono_vote_b, 64)
-MONO_BATCHED(b_mono_select, MonoSelectJob, k_mono_select_b, 256)
-MONO_BATCHED(b_mono_chiral, MonoChiralJob, k_mono_chiral_b, CHI_LANES)
-MONO_BATCHED(b_mono_pick, MonoPickJob, k_mono_pick_b, 256)
-MONO_BATCHED(b_mono_plane, MonoPlaneJob, k_mono_plane_b, 64)
-#undef MONO_BATCHED
+SVH_JOB_KERNEL(kd_mono_plane, , k_mono_plane, k_mono_plane_b, MonoPlaneJob, 64, 1, d_mono_plane,
+               (int)(blockIdx.x * 64) < a.n)
 
 }  // namespace
 
 // With a recorder installed on the calling thread (a lockstep call, batch_rec.h) the launchers append their jobs to
-// it instead of launching, exactly as the vlaunch_* launchers of vo_kernels.hip do.
+// it instead of launching (launch_or_record), exactly as vlaunch_estimate of vo_kernels.hip does.
 void mlaunch_ransac(void* stream, const float* q4, int32_t N, const int32_t* samples, int32_t iters, double thr,
                     double* F, int32_t* counts, int32_t* out_sel, uint8_t* out_flags, int32_t* out_counts) {
-    hipStream_t s = (hipStream_t)stream;
     const float4* q = reinterpret_cast<const float4*>(q4);
     const MonoHypJob ah = {q, samples, F, N, iters};
     const MonoVoteJob av = {q, F, counts, thr, N, iters};
     const MonoSelectJob as = {counts, F, q, out_sel, out_flags, out_counts, thr, N, iters};
     const unsigned gh = (unsigned)((iters + HYP_LANES - 1) / HYP_LANES);
-    if (t_rec) {
-        if (iters > 0) {
-            t_rec->add(b_mono_hyp, ah, gh);
-            t_rec->add(b_mono_vote, av, (unsigned)iters);
-        }
-        return t_rec->add(b_mono_select, as, 1);
-    }
     if (iters > 0) {
-        k_mono_hyp<<<gh, HYP_LANES, 0, s>>>(ah);
-        k_mono_vote<<<iters, 64, 0, s>>>(av);
+        launch_or_record(stream, kd_mono_hyp, ah, dim3(gh));
+        launch_or_record(stream, kd_mono_vote, av, dim3((unsigned)iters));
     }
-    k_mono_select<<<1, 256, 0, s>>>(as);
+    launch_or_record(stream, kd_mono_select, as, dim3(1));
 }
 
 void mlaunch_chiral(void* stream, const float* m4, int32_t N, const double* cams, double* X, uint8_t* front,
                     double* out_X, int32_t* out_cand) {
-    hipStream_t s = (hipStream_t)stream;
     const float4* m = reinterpret_cast<const float4*>(m4);
     const MonoChiralJob ac = {m, cams, X, front, N};
     const MonoPickJob ap = {X, front, out_X, out_cand, N};
     const unsigned gc = (unsigned)((4 * N + CHI_LANES - 1) / CHI_LANES);
-    if (t_rec) {
-        t_rec->add(b_mono_chiral, ac, gc);
-        return t_rec->add(b_mono_pick, ap, 1);
-    }
-    k_mono_chiral<<<gc, CHI_LANES, 0, s>>>(ac);
-    k_mono_pick<<<1, 256, 0, s>>>(ap);
+    launch_or_record(stream, kd_mono_chiral, ac, dim3(gc));
+    launch_or_record(stream, kd_mono_pick, ap, dim3(1));
 }
 
 void mlaunch_plane(void* stream, const double* d, int32_t n, double weight, double thr, double* sums) {
     const MonoPlaneJob a = {d, sums, weight, thr, n};
-    const unsigned g = (unsigned)((n + 63) / 64);
-    if (t_rec) return t_rec->add(b_mono_plane, a, g);
-    k_mono_plane<<<g, 64, 0, (hipStream_t)stream>>>(a);
+    launch_or_record(stream, kd_mono_plane, a, dim3((unsigned)((n + 63) / 64)));
 }
 
 }  // namespace svh

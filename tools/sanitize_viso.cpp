@@ -152,7 +152,6 @@ void mlaunch_refine(void*, svh_p_match* m, const int32_t* count, int, int, int, 
     memcpy(compacted, m, sizeof(svh_p_match) * (size_t)*count);
     *compacted_count = *count;
 }
-void vlaunch_upload(void*, const uint8_t* pinned, uint8_t* dev, size_t bytes) { memcpy(dev, pinned, bytes); }
 void vlaunch_estimate(void*, const svh_p_match*, int N, const int32_t*, int, const VoCalib&, double*, int32_t*, uint8_t*,
                       double*, double*, VoResult* out, int32_t* out_inliers) {
     out->success = N >= 6;
