@@ -43,7 +43,11 @@ void     svh_map_clear(svh_map* m);
  *   I1        left image on the host, dims[2] bytes per row
  *   H_total   4x4 camera pose, row major (StereoThread::_H_total)
  *   gain      VisualOdometryStereo::getGain of the frame (0: no gain correction)
- * Returns SVH_OK or a negative SVH_ERR_*.                                                      */
+ * A frame of another size than the one before starts a new reconstruction, exactly as if
+ * svh_map_clear had been called before it: the previous map cannot be addressed with the new
+ * dimensions, list 0 is empty after that frame and the next frame of the same size fuses again.
+ * Returns SVH_OK or a negative SVH_ERR_*.  SVH_ERR_BAD_ARG (a null pointer, w or h < 1, step < w,
+ * w * h > 2^28) is decided before anything is read and leaves the object as it was.            */
 int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uint8_t* I1,
                     const int32_t* dims, const double* H_total, float gain);
 
@@ -51,7 +55,8 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
  * reference's push_back order (columns left to right, each top to bottom):
  *   which 0   points of the previous map that were not merged into the current one
  *   which 1   points of the current map (after the fusion)
- * Copies up to cap points to `xyzv` (may be NULL) and returns the number of points.            */
+ * Copies min(number, cap) points to `xyzv` (may be NULL) and returns the number of points;
+ * any `which` other than 0 means 1.                                                            */
 int64_t svh_map_points(svh_map* m, int32_t which, float* xyzv, int64_t cap);
 
 /* The colour-coded disparity map StereoThread shows next to the image (stereothread.cpp:117-147):
@@ -59,7 +64,8 @@ int64_t svh_map_points(svh_map* m, int32_t which, float* xyzv, int64_t cap);
  * host or (d_on_device) on the device; rgb receives 3*n floats on the host, interleaved.           */
 int32_t svh_disparity_colormap(const float* D, int32_t d_on_device, int64_t n, float* rgb);
 
-/* Test access: the current map's planes I, D, X, Y, Z (5 x width*height floats) after the frame. */
+/* Test access: the current map's planes I, D, X, Y, Z (5 x width*height floats) after the frame.
+ * SVH_ERR_BAD_ARG, nothing written: before the first frame, after svh_map_clear, cap_floats too small. */
 int32_t svh_map_planes(svh_map* m, float* out5, size_t cap_floats);
 
 #ifdef __cplusplus

@@ -13,6 +13,12 @@
 // adds three floats; never-written X/Y/Z cells (malloc'ed, only read where D > 0) are 0.
 // What IS pinned: the coefficient computation (Matrix::inv, K * H[0:3,0:4]) against the
 // reference's own matrix.cpp through oracle/_ref (tests/test_map.py).
+// A frame of another size: this file keeps prev.w / prev.h and fuses across the change (as the
+// reference would); the library starts a new reconstruction there (include/svh_map.h), so a test
+// that changes the size calls orc_map_clear at the change.
+// The inputs that meet this file's thresholds exactly (z == float32(0.1), z == max_dist, a closeness
+// of float32(0.2), re-projections onto the image border, -0.0 and NaN through std::min / std::max)
+// are built and asserted on this file's output in tests/test_map_edges.py.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>

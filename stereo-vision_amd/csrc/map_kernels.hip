@@ -67,8 +67,11 @@ __global__ __launch_bounds__(256) void k_map_create(const float* __restrict__ D1
     }
     if (i >= 0) {
         const float g = (float)(((double)__fmul_rn((float)(m - i), c.gain_inv) + (double)(float)i * 1.0) / (double)(float)m);
+        // std::min(std::max(t, 0.f), 1.f) as its two comparisons: -0.0f and NaN pass through, which fmaxf / fminf
+        // do not promise
         const float t = __fmul_rn(g, I);
-        I = fminf(fmaxf(t, 0.f), 1.f);
+        const float lo = (t < 0.f) ? 0.f : t;
+        I = (1.f < lo) ? 1.f : lo;
     }
     float d = D1[a], X = 0.f, Y = 0.f, Z = 0.f;
     if (d > 0) {
@@ -256,7 +259,9 @@ __global__ __launch_bounds__(256) void k_map_scatter(const uint8_t* __restrict__
 __global__ __launch_bounds__(256) void k_disp_color(const float* __restrict__ D, long long n, float* __restrict__ rgb) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float val = fminf(__fdiv_rn(D[i], 200.f), 1.0f);
+    // std::min(D / d_max, 1.0f) as its comparison: a NaN disparity stays NaN and the pixel black (fminf gives 1: red)
+    const float q = __fdiv_rn(D[i], 200.f);
+    const float val = (1.0f < q) ? 1.0f : q;
     float r = 0.f, g = 0.f, b = 0.f;
     if (val > 0) {
         const float h2 = (float)(6.0 * (1.0 - (double)val));

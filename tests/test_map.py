@@ -262,3 +262,33 @@ def test_disparity_colormap_matches_oracle(oracle_lib):
     got = mapper.disparity_colormap(D)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
     assert np.all(got[D <= 0] == 0) and got[0, 3].tolist() == [1.0, 0.0, 0.0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_disparity_colormap_nonfinite_and_block_edges(n, oracle_lib):
+    """NaN, +inf, -inf and -0.0 (black, red, black, black) at the ends of 256-pixel blocks; the host entry and the
+    d_on_device entry on the same data"""
+    from svhip import mapper
+    rng = np.random.default_rng(40 + n)
+    D = rng.uniform(-20, 260, n).astype(np.float32)
+    odd = np.array([np.nan, np.inf, -np.inf, -0.0], np.float32)
+    odd[0] = np.array([0x7FC12345], np.uint32).view(np.float32)[0]
+    for k in range(min(n, 8)):
+        D[-1 - k] = odd[(k + n) % 4]            # the last pixels: the end of the last block
+    if n > 8:
+        D[:4] = odd
+    want = np.full((n, 3), 7, np.float32)
+    oracle_lib.orc_disparity_colormap.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    oracle_lib.orc_disparity_colormap(D.ctypes.data, D.size, want.ctypes.data)
+    assert np.all(want[~(D > 0)] == 0) and np.all(want[np.isposinf(D)] == [1, 0, 0])
+    got = mapper.disparity_colormap(D)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    hip = C.CDLL("libamdhip64.so")
+    dev = C.c_void_p()
+    assert hip.hipMalloc(C.byref(dev), C.c_size_t(D.nbytes)) == 0
+    assert hip.hipMemcpy(dev, C.c_void_p(D.ctypes.data), C.c_size_t(D.nbytes), 1) == 0   # hipMemcpyHostToDevice
+    out = np.full((n + 1, 3), 7, np.float32)
+    rc = mapper._bind().svh_disparity_colormap(dev, 1, n, out.ctypes.data)
+    hip.hipFree(dev)
+    assert rc == 0 and np.array_equal(out[:n].view(np.uint32), want.view(np.uint32)) and np.all(out[n] == 7)
