@@ -44,232 +44,7 @@ namespace svh {
 
 static int mfail(int code, const std::string& msg) { return fail(code, msg); }
 
-// Threads that are inside a compute entry of the Matcher / visual odometry right now (svh_matcher_push_back,
-// svh_matcher_match_features, svh_vo_process, svh_vo_estimate_motion).  One or two = a single sequence (the
-// latency path: spin on the stream, triangulate the outlier vote on the helper pool); more = several sequences
-// share this GPU and the host cores: waits sleep between polls and the helper pool is left alone.  What counts
-// is concurrent ACTIVITY, not how many objects exist (a process may hold many Matchers and drive one).
-// SVH_MATCHER_WAIT=0 (spin) / 1 (sleep-poll) overrides the choice.
-static std::atomic<int> g_active_callers{0};
-static thread_local int t_entry_depth = 0;   // svh_vo_process calls the Matcher's entries: a thread counts once
-ActiveCaller::ActiveCaller() {
-    if (t_entry_depth++ == 0) g_active_callers.fetch_add(1, std::memory_order_relaxed);
-}
-ActiveCaller::~ActiveCaller() {
-    if (--t_entry_depth == 0) g_active_callers.fetch_sub(1, std::memory_order_relaxed);
-}
-int wait_stream(void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    static const int forced = svh::env("SVH_MATCHER_WAIT") ? atoi(svh::env("SVH_MATCHER_WAIT")) : -1;   // 0 spin, 1 sleep-poll
-    const bool poll = forced >= 0 ? forced == 1 : g_active_callers.load(std::memory_order_relaxed) > 2;
-    if (!poll) return (int)hipStreamSynchronize(s);
-    for (;;) {
-        const hipError_t e = hipStreamQuery(s);
-        if (e != hipErrorNotReady) return (int)e;
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
-}
-
-// ---------------------------------------------------------------------------
-// batch recorder (batch_rec.h) and the host-side helpers of the batched entries
-// ---------------------------------------------------------------------------
-thread_local BatchRec* t_rec = nullptr;
-
-hipError_t BatchRec::flush(hipStream_t s) {
-    cursor = 0;
-    if (slots.empty()) return hipSuccess;
-    auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    size_t need = 0;
-    for (const Slot& sl : slots) need += al(sl.jobs.size());
-    if (used + need > d_arena.cap) {
-        // the arena may still be read by launches in flight: wait, then grow (a failed allocation leaves an arena of
-        // size 0: the next flush allocates again)
-        hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return e;
-        const size_t want = std::max<size_t>(2 * (used + need), 256 * 1024);
-        used = 0;
-        if ((e = h_arena.grow(want)) != hipSuccess || (e = d_arena.grow(want)) != hipSuccess) {
-            h_arena.release();
-            d_arena.release();
-            return e;
-        }
-    }
-    size_t off = used;
-    std::vector<size_t> at;
-    for (const Slot& sl : slots) {
-        memcpy(h_arena + off, sl.jobs.data(), sl.jobs.size());
-        at.push_back(off);
-        off += al(sl.jobs.size());
-    }
-    hipError_t e = hipMemcpyAsync(d_arena + used, h_arena + used, need, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return e;
-    for (size_t i = 0; i < slots.size(); i++) {
-        const Slot& sl = slots[i];
-        if (sl.njobs > 0) sl.fn(d_arena + at[i], sl.njobs, sl.gx, sl.gy, sl.lds, s);
-    }
-    used += need;
-    slots.clear();
-    if (track) {
-        last_stream = s;
-        flush_pending = true;
-    }
-    return hipGetLastError();
-}
-
-hipError_t BatchRec::ensure_side() {
-    for (int i = 0; i < kSide; i++) {
-        if (side[i]) continue;
-        hipError_t e = hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking);
-        if (e != hipSuccess) return e;
-        e = hipEventCreateWithFlags(&side_done[i], hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t BatchRec::join_side(hipStream_t s) {
-    for (int i = 0; i < kSide; i++) {
-        if (!side[i]) continue;
-        hipError_t e = hipEventRecord(side_done[i], side[i]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, side_done[i], 0);
-        if (e != hipSuccess) {
-            // (seen once in a while with several threads in the runtime: "event last recorded in a capturing
-            // stream"; the host waits for the side stream instead)
-            (void)hipGetLastError();
-            e = hipStreamSynchronize(side[i]);
-            if (e != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
-}
-
-void BatchRec::release() {
-    h_arena.release();
-    d_arena.release();
-    for (int i = 0; i < kSide; i++) {
-        if (side[i]) (void)hipStreamDestroy(side[i]);
-        if (side_done[i]) (void)hipEventDestroy(side_done[i]);
-        side[i] = nullptr;
-        side_done[i] = nullptr;
-    }
-    flush_pending = false;
-}
-
-// The calling thread's recorder FOR A DEVICE (arena, side streams and events live on the device that was current
-// when they were created; they are kept for the thread's lifetime).  Round 5: one recorder per (thread, device) --
-// a thread that drove a lockstep batch on GPU 0 and then one on GPU 1 used to launch the second batch's kernels with
-// a job table in GPU 0's memory.
 namespace {
-BatchRec& recorder_of(std::map<int, std::unique_ptr<BatchRec>>& recs, int device) {
-    std::unique_ptr<BatchRec>& r = recs[device];
-    if (!r) r.reset(new BatchRec());
-    return *r;
-}
-}   // namespace
-BatchRec& batch_recorder(int device) {
-    static thread_local std::map<int, std::unique_ptr<BatchRec>> recs;
-    return recorder_of(recs, device);
-}
-// a second one for svh_matcher_prefetch_batch: its launches are still in flight when the thread records the next
-// phases of the frame before
-BatchRec& prefetch_recorder(int device) {
-    static thread_local std::map<int, std::unique_ptr<BatchRec>> recs;
-    BatchRec& rec = recorder_of(recs, device);
-    rec.track = true;
-    return rec;
-}
-
-hipError_t BatchRec::reuse() {
-    // (a stream wait, not an event: events recorded on this thread and waited for on streams that another thread
-    // synchronises at the same moment came back as "event last recorded in a capturing stream" now and then)
-    if (flush_pending) {
-        const hipError_t e = hipStreamSynchronize(last_stream);
-        if (e != hipSuccess) return e;
-        flush_pending = false;
-    }
-    used = 0;
-    return hipSuccess;
-}
-
-// Parked helper threads for the per-object HOST work of a batch call (outlier votes, prior statistics, row packing):
-// parallel_for(n, fn) runs fn(0..n-1) on the helpers and the caller, returns when all are done.
-// Several calls may be in flight at once (the prefetch thread packing frame t+1 while the caller votes on frame t,
-// two calling threads with their own objects): every call is a job on the pool's list, the helpers take tasks from
-// the jobs in turn, a caller works on its OWN job only (it returns as soon as that job is done).  Until round 5's
-// last session the calls took turns on a mutex: the packing of the next frame and the votes of this one -- both on
-// the critical path of a pipelined lockstep call -- waited for each other with helpers idle in the tail of either.
-// SVH_POOL_SERIAL=1 keeps the take-turns form (A/B).
-namespace {
-class BatchPool {
-    struct Job {
-        const std::function<void(int)>* fn;
-        int n;
-        int next = 0, done = 0;
-    };
-
-public:
-    void parallel_for(int n, const std::function<void(int)>& fn) {
-        if (n <= 1) {
-            for (int i = 0; i < n; i++) fn(i);
-            return;
-        }
-        static const bool serial = svh::env("SVH_POOL_SERIAL") && atoi(svh::env("SVH_POOL_SERIAL")) != 0;
-        std::unique_lock<std::mutex> one_call(call_mu_, std::defer_lock);
-        if (serial) one_call.lock();
-        Job job{&fn, n};
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            const int want = std::min(n - 1, max_threads());
-            while ((int)threads_.size() < want) threads_.emplace_back(&BatchPool::run, this);
-            jobs_.push_back(&job);
-        }
-        cv_.notify_all();
-        std::unique_lock<std::mutex> lk(mu_);
-        while (job.next < job.n) {            // the caller's share of its own job
-            const int i = take(&job);
-            lk.unlock();
-            fn(i);
-            lk.lock();
-            job.done++;
-        }
-        cv_done_.wait(lk, [&] { return job.done == job.n; });   // (the job left the list with its last task)
-    }
-    static BatchPool& get() {
-        static BatchPool* p = new BatchPool();   // leaked on purpose: its threads outlive static destruction
-        return *p;
-    }
-
-private:
-    static int max_threads() {
-        static const int n = std::max(1, std::min(15, (int)std::thread::hardware_concurrency() - 1));
-        return n;
-    }
-    // mu_ held: next task of the job; a job whose tasks are all handed out leaves the list
-    int take(Job* j) {
-        const int i = j->next++;
-        if (j->next == j->n) jobs_.erase(std::find(jobs_.begin(), jobs_.end(), j));
-        return i;
-    }
-    void run() {
-        std::unique_lock<std::mutex> lk(mu_);
-        for (;;) {
-            cv_.wait(lk, [&] { return !jobs_.empty(); });
-            Job* j = jobs_[turn_++ % jobs_.size()];   // the jobs in turn: neither call starves the other
-            const int i = take(j);
-            const std::function<void(int)>* fn = j->fn;
-            lk.unlock();
-            (*fn)(i);
-            lk.lock();
-            // (the job lives on its caller's stack until done == n, and this is the helper's last touch of it)
-            if (++j->done == j->n) cv_done_.notify_all();
-        }
-    }
-    std::mutex mu_, call_mu_;
-    std::condition_variable cv_, cv_done_;
-    std::vector<std::thread> threads_;
-    std::vector<Job*> jobs_;      // jobs with tasks left to hand out
-    size_t turn_ = 0;
-};
 // One parked thread that runs the host side of svh_matcher_prefetch_batch (row packing on the helper threads,
 // uploads, the recorded feature extraction) while the caller goes on with the frame before.
 class PrefetchWorker {
@@ -311,7 +86,6 @@ private:
     std::deque<std::packaged_task<int32_t()>> q_;
     bool started_ = false;
 };
-thread_local bool t_in_batch = false;   // inside a batch call: the outlier vote does not fork (the pool is the parallelism)
 }  // namespace
 
 // (one line on stderr at the point of failure: the entries above it only pass the code on)
@@ -600,7 +374,7 @@ static int ensure_bins(svh_matcher* m, DevView* const* views, int nviews, int32_
 // be fought over; inside a batch call the pool of the batch is the parallelism)
 static int vote_par_depth() {
     static const int par = svh::env("SVH_DELAUNAY_PAR") ? atoi(svh::env("SVH_DELAUNAY_PAR")) : 3;
-    const bool alone = g_active_callers.load(std::memory_order_relaxed) <= 2 && !t_in_batch;
+    const bool alone = active_callers() <= 2 && !t_in_batch;
     return alone ? std::max(0, std::min(par, 3)) : 0;
 }
 static const int32_t kVoteParMin = 1500;
@@ -855,17 +629,6 @@ int32_t bucket_features(svh_matcher* m, int32_t max_features, float bw, float bh
     return (int32_t)m->m2.size();
 }
 
-void batch_parallel_for(int n, const std::function<void(int)>& fn) {
-    const bool was = t_in_batch;
-    t_in_batch = true;
-    BatchPool::get().parallel_for(n, [&](int i) {
-        const bool w = t_in_batch;
-        t_in_batch = true;
-        fn(i);
-        t_in_batch = w;
-    });
-    t_in_batch = was;
-}
 
 }  // namespace svh
 
@@ -1123,41 +886,28 @@ static int32_t prefetch_body(const std::vector<svh_matcher*>& ms, const std::vec
     });
     for (int rc : rcs)
         if (rc) return rc;
-    int rc = SVH_OK;
+    // the features of object i: recorded for the hand-over stream, or, without a recorder (the objects differ, or the
+    // recorded pass met a sequence mismatch), on the object's second stream.  An image whose upload was to be recorded
+    // is uploaded here, the others were uploaded by the packing threads
+    auto enqueue = [&](int i) -> int {
+        const bool recorded = t_rec != nullptr;
+        for (int cam = 0; cam < ncam; cam++) {
+            const int rc = features_enqueue(ms[i], ms[i]->next[cam], cam, nullptr, !upload_recorded,
+                                            ms[i]->h_n + 4, recorded ? nullptr : ms[i]->stream2);
+            if (rc) return rc;
+        }
+        ms[i]->next_stream = recorded ? pf_own : ms[i]->stream2;
+        return SVH_OK;
+    };
     if (lockstep) {
-        hipStream_t pf = pf_own;
-        pr.reset();
-        t_rec = &pr;
-        for (int i = 0; i < K && !rc; i++) {
-            pr.begin_object();
-            for (int cam = 0; cam < ncam && !rc; cam++)
-                rc = features_enqueue(ms[i], ms[i]->next[cam], cam, nullptr, !upload_recorded, ms[i]->h_n + 4);
-        }
-        t_rec = nullptr;
-        if (rc) return rc;
-        if (pr.broken) {
-            pr.reset();
-            lockstep = false;   // (not reachable with equal parameters and sizes) issue them one by one below
-            if (upload_recorded)
-                for (int i = 0; i < K; i++)
-                    for (int cam = 0; cam < ncam; cam++) {
-                        DevView& V = ms[i]->next[cam];
-                        mlaunch_upload(ms[i]->stream2, V.stage, V.I, (size_t)V.bpl * V.h);
-                    }
-            HIP_TRY(wait, hipStreamSynchronize(pf));
-        } else {
-            HIP_TRY(copy, pr.flush(pf));
-            for (int i = 0; i < K; i++) ms[i]->next_stream = pf;
-        }
+        Phase ph{"Matcher", FI_wait};
+        ph.wait = false;
+        const int rc = run_recorded(pr, pf_own, nullptr, K, ph, enqueue, [](int) { return (int)SVH_OK; }, no_undo);
+        return rc < 0 ? rc : SVH_OK;
     }
-    if (!lockstep) {
-        for (int i = 0; i < K; i++) {
-            for (int cam = 0; cam < ncam; cam++) {
-                rc = features_enqueue(ms[i], ms[i]->next[cam], cam, nullptr, true, ms[i]->h_n + 4, ms[i]->stream2);
-                if (rc) return rc;
-            }
-            ms[i]->next_stream = ms[i]->stream2;
-        }
+    for (int i = 0; i < K; i++) {
+        const int rc = enqueue(i);
+        if (rc) return rc;
     }
     return SVH_OK;
 }
@@ -1178,13 +928,14 @@ int32_t svh_matcher_prefetch_batch(svh_matcher* const* ms, int32_t K, const uint
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return mfail(SVH_ERR_NO_DEVICE, "no HIP device visible: libsvhip has no CPU fallback");
     const int ncam = (I2 && I2[0]) ? 2 : 1;
-    bool lockstep = K > 1;
+    bool lockstep = false;
+    const int32_t bad = check_batch(ms, K, "matcher", &lockstep,
+                                    [&](int i) { return memcmp(&ms[i]->p, &ms[0]->p, sizeof(ms[0]->p)) == 0; });
+    if (bad) return bad;
+    lockstep = lockstep && K > 1;
     for (int i = 0; i < K; i++) {
-        if (!ms[i] || !I1[i] || (ncam == 2 && !I2[i])) return mfail(SVH_ERR_BAD_ARG, "null matcher or image in the batch");
+        if (!I1[i] || (ncam == 2 && !I2[i])) return mfail(SVH_ERR_BAD_ARG, "null image in the batch");
         if (ms[i]->has_next) return mfail(SVH_ERR_BAD_ARG, "a prefetched frame is already pending");
-        for (int j = 0; j < i; j++)
-            if (ms[j] == ms[i]) return mfail(SVH_ERR_BAD_ARG, "the same matcher twice in one batch");
-        lockstep = lockstep && memcmp(&ms[i]->p, &ms[0]->p, sizeof(ms[0]->p)) == 0 && ms[i]->device == ms[0]->device;
     }
     // the rest runs on the prefetch thread (the caller's pointer arrays are copied, the images are read there:
     // they must stay unchanged until the frame is taken)
@@ -1252,12 +1003,12 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
         return SVH_OK;
     }
     bool lockstep = K > 1;
-    for (int i = 0; i < K && lockstep; i++) {
-        if (!ms[i]) return mfail(SVH_ERR_BAD_ARG, "null matcher in the batch");
-        for (int j = 0; j < i; j++)
-            if (ms[j] == ms[i]) return mfail(SVH_ERR_BAD_ARG, "the same matcher twice in one batch");
-        lockstep = memcmp(&ms[i]->p, &ms[0]->p, sizeof(ms[0]->p)) == 0 && !ms[i]->taps &&
-                   ms[i]->device == ms[0]->device && (!I2 || !I2[i]) == (!I2 || !I2[0]) && I1[i];
+    if (lockstep) {
+        const int32_t bad = check_batch(ms, K, "matcher", &lockstep, [&](int i) {
+            return memcmp(&ms[i]->p, &ms[0]->p, sizeof(ms[0]->p)) == 0 && !ms[i]->taps &&
+                   (!I2 || !I2[i]) == (!I2 || !I2[0]) && I1[i];
+        }, true);
+        if (bad) return bad;
     }
     auto serial = [&]() -> int32_t {
         for (int i = 0; i < K; i++) {
@@ -1279,17 +1030,13 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
     std::vector<int> rcs((size_t)K * ncam, 0);
     BatchRec& up = batch_recorder(ms[0]->device);
     HIP_TRY(none, up.ensure_side());
-    struct InBatch {     // (cleared on every exit, the error returns included)
-        InBatch() { t_in_batch = true; }
-        ~InBatch() { t_in_batch = false; }
-    };
-    InBatch in_batch_;
+    InBatchScope in_batch_;
     // The uploads are recorded with the features (one k_upload_b launch per camera over the K objects; they start when
     // every image is packed instead of overlapping the packing, which costs less than 2 K launches from the packing
     // threads did: 2 x 16 objects 7.8-8.6 -> 8.7-9.0 k frames/s, 1 x 32 6.1-6.2 -> 6.3-6.6 k, 1 x 16 unchanged).
     // SVH_UPLOAD_BATCH=0: every packing thread launches its image's upload, rotating over the side streams.
     static const bool upload_recorded = !(svh::env("SVH_UPLOAD_BATCH") && atoi(svh::env("SVH_UPLOAD_BATCH")) == 0);
-    BatchPool::get().parallel_for(K * ncam, [&](int j) {
+    batch_parallel_for(K * ncam, [&](int j) {
         (void)hipSetDevice(ms[0]->device);
         svh_matcher* m = ms[j / ncam];
         const int cam = j % ncam;
@@ -1306,39 +1053,24 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
     for (int rc : rcs)
         if (rc) return rc;
     btick(2);
-    BatchRec& rec = batch_recorder(ms[0]->device);
-    rec.reset();
-    t_rec = &rec;
-    int rc = SVH_OK;
-    for (int i = 0; i < K && !rc; i++) {
-        rec.begin_object();
-        for (int cam = 0; cam < ncam && !rc; cam++)
-            rc = features_enqueue(ms[i], ms[i]->cur[cam], cam, nullptr, !upload_recorded);
-    }
-    t_rec = nullptr;
-    if (rc) return rc;
-    btick(3);
-    hipStream_t s = ms[0]->stream;
-    if (rec.broken) {
-        // (not reachable with equal parameters and sizes; kept so that a future launcher change cannot corrupt a batch)
-        rec.reset();
-        HIP_TRY(none, (hipError_t)wait_stream(s));   // (the uploads issued above)
-        for (int i = 0; i < K; i++) {
+    Phase ph{"Matcher", FI_none};
+    ph.t_host = g_mtiming ? tb + 3 : nullptr;   // tb[3]: recorded, tb[4]: flushed
+    const int32_t rc = run_recorded(
+        up, ms[0]->stream, nullptr, K, ph,
+        [&](int i) -> int {   // (without a recorder: on the object's own streams, the image uploaded again)
             for (int cam = 0; cam < ncam; cam++) {
-                rc = features_enqueue(ms[i], ms[i]->cur[cam], cam, nullptr);
-                if (rc) return rc;
+                const int r = features_enqueue(ms[i], ms[i]->cur[cam], cam, nullptr, t_rec && !upload_recorded);
+                if (r) return r;
             }
+            return SVH_OK;
+        },
+        [&](int i) -> int {
             HIP_TRY(none, (hipError_t)wait_stream(ms[i]->stream));
             HIP_TRY(none, (hipError_t)wait_stream(ms[i]->stream2));
-            push_finish(ms[i], I1[i], I2 ? I2[i] : nullptr);
-        }
-        return SVH_OK;
-    }
-    HIP_TRY(copy, rec.flush(s));
-    btick(4);
-    HIP_TRY(none, (hipError_t)wait_stream(s));
-    HIP_TRY(launch, hipGetLastError());
-    rec.synced();
+            return SVH_OK;
+        },
+        no_undo);
+    if (rc < 0) return rc;
     for (int i = 0; i < K; i++) push_finish(ms[i], I1[i], I2 ? I2[i] : nullptr);
     btick(5);
     if (g_mtiming) {
@@ -1457,12 +1189,12 @@ int32_t svh_matcher_match_features_batch(svh_matcher* const* ms, int32_t K, int3
     if (!ms || K < 0) return mfail(SVH_ERR_BAD_ARG, "null argument");
     if (K == 0) return SVH_OK;
     bool lockstep = K > 1;
-    for (int i = 0; i < K && lockstep; i++) {
-        if (!ms[i]) return mfail(SVH_ERR_BAD_ARG, "null matcher in the batch");
-        for (int j = 0; j < i; j++)
-            if (ms[j] == ms[i]) return mfail(SVH_ERR_BAD_ARG, "the same matcher twice in one batch");
-        lockstep = memcmp(&ms[i]->p, &ms[0]->p, sizeof(ms[0]->p)) == 0 && !ms[i]->taps &&
-                   ms[i]->device == ms[0]->device && memcmp(ms[i]->dims_c, ms[0]->dims_c, sizeof(ms[0]->dims_c)) == 0;
+    if (lockstep) {
+        const int32_t bad = check_batch(ms, K, "matcher", &lockstep, [&](int i) {
+            return memcmp(&ms[i]->p, &ms[0]->p, sizeof(ms[0]->p)) == 0 && !ms[i]->taps &&
+                   memcmp(ms[i]->dims_c, ms[0]->dims_c, sizeof(ms[0]->dims_c)) == 0;
+        }, true);
+        if (bad) return bad;
     }
     auto serial = [&](const std::vector<svh_matcher*>& list, const std::vector<const double*>& trs) -> int32_t {
         for (size_t i = 0; i < list.size(); i++) {
@@ -1494,60 +1226,27 @@ int32_t svh_matcher_match_features_batch(svh_matcher* const* ms, int32_t K, int3
     double t_wait = 0, tm[5] = {0, 0, 0, 0, 0};
     auto mtick = [&](int i) { if (g_mtiming) tm[i] = now_ms(); };
     mtick(0); mtick(1); mtick(2);
-    // record one device phase over all objects; on a sequence mismatch the objects run one by one instead
-    // (an error exit from a recording pass: ensure_bins has marked the bin indices of the recorded objects as built
-    // although no index kernel ran -- they are marked unbuilt again, the next matchFeatures rebuilds them)
+    // One device phase over all objects.  The recording pass's ensure_bins marks the bin indices of the recorded
+    // objects as built although no index kernel ran: before the objects run one by one after a sequence mismatch, and
+    // after an error, they are marked unbuilt again (the next matchFeatures rebuilds them).
     auto unbuild = [&]() {
         for (int i = 0; i < n; i++)
             for (int k = 0; k < 2; k++) part[i]->prev[k].nbins = part[i]->cur[k].nbins = 0;
     };
-    auto device_phase_inner = [&](const std::function<int(int)>& body) -> int {
-        rec.reset();
-        t_rec = &rec;
-        int rc = SVH_OK;
-        for (int i = 0; i < n && !rc; i++) {
-            rec.begin_object();
-            rc = body(i);
-        }
-        t_rec = nullptr;
-        if (rc) return rc;
-        if (rec.broken) {
-            rec.reset();
-            for (int i = 0; i < n; i++) {
-                // (the recording pass marked the bin indices as built: build them for real)
-                for (int k = 0; k < 2; k++) part[i]->prev[k].nbins = part[i]->cur[k].nbins = 0;
-                rc = body(i);
-                if (rc) return rc;
-                HIP_TRY(none, (hipError_t)wait_stream(part[i]->stream));
-            }
-            HIP_TRY(launch, hipGetLastError());
-            return SVH_OK;
-        }
-        HIP_TRY(copy, rec.flush(s));
-        const double tw = g_mtiming ? now_ms() : 0;
-        HIP_TRY(none, (hipError_t)wait_stream(s));
-        HIP_TRY(launch, hipGetLastError());
-        rec.synced();
-        if (g_mtiming) t_wait += now_ms() - tw;
+    auto wait_own = [&](int i) -> int {
+        HIP_TRY(none, (hipError_t)wait_stream(part[i]->stream));
         return SVH_OK;
     };
-    auto device_phase = [&](const std::function<int(int)>& body) -> int {
-        const int rc = device_phase_inner(body);
-        if (rc) {
-            t_rec = nullptr;
-            rec.reset();
-            unbuild();
-        }
-        return rc;
+    double tp[3] = {0, 0, 0};
+    Phase ph{"Matcher", FI_none};
+    ph.t_host = g_mtiming ? tp : nullptr;
+    auto device_phase = [&](auto body) -> int {
+        const int rc = run_recorded(rec, s, nullptr, n, ph, body, wait_own, unbuild);
+        t_wait += tp[2] - tp[1];
+        return rc < 0 ? rc : SVH_OK;
     };
-    auto host_phase = [&](const std::function<int(int)>& body) -> int {
-        t_in_batch = true;
-        BatchPool::get().parallel_for(n, [&](int i) {
-            t_in_batch = true;
-            rcs[i] = body(i);
-            t_in_batch = false;
-        });
-        t_in_batch = false;
+    auto host_phase = [&](auto body) -> int {
+        batch_parallel_for(n, [&](int i) { rcs[i] = body(i); });
         for (int rc : rcs)
             if (rc) return rc;
         return SVH_OK;

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/svh_plane.h"
+#include "batch_rec.h"
 #include "hip_guard.h"
 #include "plane_internal.h"
 #include "vo_internal.h"
@@ -403,13 +404,14 @@ int32_t svh_plane_estimate_batch(svh_plane* const* p, const float* const* D, int
                                  const uint32_t* seeds, int32_t* status) {
     if (!p || !D || !seeds || n < 1 || n > 4096 || width < 1 || height < 1 || step < width)
         return svh::fail(SVH_ERR_BAD_ARG, "svh_plane_estimate_batch: bad arguments");
-    for (int32_t i = 0; i < n; i++) {
-        if (!p[i] || !D[i]) return svh::fail(SVH_ERR_BAD_ARG, "svh_plane_estimate_batch: null object or map");
-        if (memcmp(&p[i]->prm, &p[0]->prm, sizeof(svh_plane_params)) || p[i]->device != p[0]->device)
-            return svh::fail(SVH_ERR_BAD_ARG, "svh_plane_estimate_batch: the objects differ in parameters or device");
-        for (int32_t j = 0; j < i; j++)
-            if (p[j] == p[i]) return svh::fail(SVH_ERR_BAD_ARG, "svh_plane_estimate_batch: the same object twice");
-    }
+    bool uniform = true;
+    const int32_t bad = check_batch(p, n, "object", &uniform, [&](int i) {
+        return memcmp(&p[i]->prm, &p[0]->prm, sizeof(svh_plane_params)) == 0;
+    });
+    if (bad) return bad;
+    if (!uniform) return svh::fail(SVH_ERR_BAD_ARG, "svh_plane_estimate_batch: the objects differ in parameters or device");
+    for (int32_t i = 0; i < n; i++)
+        if (!D[i]) return svh::fail(SVH_ERR_BAD_ARG, "svh_plane_estimate_batch: null map");
     std::vector<Result> res;
     const int rc = run_guarded(p, D, true, n, width, height, step, f, cu, cv, base, seeds, res);
     if (rc < 0) return rc;

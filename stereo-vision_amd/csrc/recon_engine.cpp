@@ -22,6 +22,7 @@
 
 #include "../../include/matrix.h"
 #include "../../include/svh.h"
+#include "batch_rec.h"
 #include "hip_guard.h"
 #include "matcher_internal.h"
 #include "recon_core.h"
@@ -635,16 +636,15 @@ int32_t svh_recon_update_batch(svh_recon* const* rs, const svh_p_match* const* m
                                double min_angle, int32_t* status) {
     if (K < 0 || (K > 0 && (!rs || !m || !n || !Tr)))
         return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_update_batch: bad arguments");
+    bool one_device = true;
+    const int32_t bad = check_batch(rs, K, "object", &one_device, [](int) { return true; });
+    if (bad) return bad;
+    if (!one_device) return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_update_batch: objects of different devices");
     for (int32_t i = 0; i < K; i++) {
-        if (!rs[i]) return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_update_batch: null object in the batch");
         if (!rs[i]->resident)
             return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_update_batch: a host-table object in the batch (svh_recon_create)");
         if (!rs[i]->calibrated)
             return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_update_batch before svh_recon_set_calibration");
-        if (rs[i]->device != rs[0]->device)
-            return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_update_batch: objects of different devices");
-        for (int32_t j = 0; j < i; j++)
-            if (rs[j] == rs[i]) return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_update_batch: the same object twice");
         if (m[i] && n[i] < 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_recon_update_batch: negative match count");
     }
     if (K > 0 && !have_device())

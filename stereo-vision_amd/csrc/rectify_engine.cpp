@@ -18,6 +18,7 @@
 #include <string>
 
 #include "../../include/svh_rectify.h"
+#include "batch_rec.h"
 #include "hip_guard.h"
 #include "rectify_internal.h"
 #include "svh_config.h"

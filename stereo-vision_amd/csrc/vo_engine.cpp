@@ -276,15 +276,14 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
     svh::ActiveCaller active_;
     // I1 == I2 == NULL: the objects take the frame handed over by svh_vo_prefetch_batch
     if (!vs || K < 0 || (!I1 != !I2) || !dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
-    bool lockstep = K > 1;
-    for (int i = 0; i < K; i++) {
-        if (!vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "null object in the batch");
+    bool lockstep = false;
+    const int32_t bad = check_batch(vs, K, "object", &lockstep, [&](int i) {
+        return vs[i]->Tr_valid && memcmp(&vs[i]->p, &vs[0]->p, sizeof(vs[0]->p)) == 0;
+    });
+    if (bad) return bad;
+    lockstep = lockstep && K > 1;
+    for (int i = 0; i < K; i++)
         if (vs[i]->mono) return svh::fail(SVH_ERR_BAD_ARG, "mono objects have no batch entries");
-        for (int j = 0; j < i; j++)
-            if (vs[j] == vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "the same object twice in one batch");
-        lockstep = lockstep && vs[i]->Tr_valid && memcmp(&vs[i]->p, &vs[0]->p, sizeof(vs[0]->p)) == 0 &&
-                   vs[i]->device == vs[0]->device;
-    }
     int32_t good = 0;
     std::vector<svh_matcher*> ms(K);
     for (int i = 0; i < K; i++) ms[i] = vs[i]->matcher;
@@ -354,29 +353,21 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
     for (int i = 0; i < K; i++)
         if (state[i] < 0) return state[i];
     if (timing) tt[3] = now_ms();
-    BatchRec& rec = batch_recorder(vs[0]->device);
-    rec.reset();
-    t_rec = &rec;
+    std::vector<int> live;
     for (int i = 0; i < K; i++)
-        if (state[i] > 0) {
-            rec.begin_object();
+        if (state[i] > 0) live.push_back(i);
+    rc = run_recorded(
+        batch_recorder(vs[0]->device), vs[0]->stream, live.data(), (int)live.size(), Phase{"VisualOdometry", FI_none},
+        [&](int i) -> int {
             estimate_enqueue(vs[i], (int32_t)vs[i]->matched.size());
-        }
-    t_rec = nullptr;
-    if (rec.broken) {
-        rec.reset();
-        for (int i = 0; i < K; i++)
-            if (state[i] > 0) {
-                estimate_enqueue(vs[i], (int32_t)vs[i]->matched.size());
-                VO_TRY(none, (hipError_t)wait_stream(vs[i]->stream));
-            }
-    } else {
-        hipStream_t s = vs[0]->stream;
-        VO_TRY(copy, rec.flush(s));
-        VO_TRY(none, (hipError_t)wait_stream(s));
-        rec.synced();
-    }
-    VO_TRY(launch, hipGetLastError());
+            return SVH_OK;
+        },
+        [&](int i) -> int {
+            VO_TRY(none, (hipError_t)wait_stream(vs[i]->stream));
+            return SVH_OK;
+        },
+        no_undo);
+    if (rc < 0) return rc;
     for (int i = 0; i < K; i++) {
         int32_t r = 0;
         if (state[i] > 0) {
@@ -551,15 +542,14 @@ int32_t svh_vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, in
 // device phase, object by object, which is the order of K svh_vo_mono_process calls.
 static int32_t mono_batch_args(svh_vo* const* vs, int32_t K, bool* lockstep) {
     if (!vs || K < 0) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
-    *lockstep = K > 1;
-    for (int i = 0; i < K; i++) {
-        if (!vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "null object in the batch");
-        if (!vs[i]->mono) return svh::fail(SVH_ERR_BAD_ARG, "a stereo object in a mono batch: use svh_vo_process_batch");
-        for (int j = 0; j < i; j++)
-            if (vs[j] == vs[i]) return svh::fail(SVH_ERR_BAD_ARG, "the same object twice in one batch");
-        *lockstep = *lockstep && mono_same_params(vs[i]->mono, vs[0]->mono) &&
-                    memcmp(&vs[i]->p, &vs[0]->p, sizeof(vs[0]->p)) == 0 && vs[i]->device == vs[0]->device;
-    }
+    for (int i = 0; i < K; i++)
+        if (vs[i] && !vs[i]->mono)
+            return svh::fail(SVH_ERR_BAD_ARG, "a stereo object in a mono batch: use svh_vo_process_batch");
+    const int32_t bad = check_batch(vs, K, "object", lockstep, [&](int i) {
+        return mono_same_params(vs[i]->mono, vs[0]->mono) && memcmp(&vs[i]->p, &vs[0]->p, sizeof(vs[0]->p)) == 0;
+    });
+    if (bad) return bad;
+    *lockstep = *lockstep && K > 1;
     int nd = 0;
     if (K > 0 && (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0))
         return svh::fail(SVH_ERR_NO_DEVICE, "no HIP device visible: libsvhip has no CPU fallback");

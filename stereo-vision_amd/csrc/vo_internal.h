@@ -24,20 +24,6 @@ struct VoResult {          // written by k_vo_refine into pinned host memory
     int32_t pad_;
 };
 
-// Wait for a stream of a Matcher / visual-odometry object.  One or two threads inside the library's compute
-// entries at this moment: the driver's spinning wait (lowest latency for the single-sequence case of
-// stereomapper).  Three or more (K independent sequences driven concurrently on one GPU): polling with short
-// sleeps, so that K host threads do not burn K cores spinning on a GPU they share.  The count is of
-// concurrent callers (ActiveCaller below), not of objects that exist; SVH_MATCHER_WAIT=0/1 overrides.
-int wait_stream(void* stream);   // returns a hipError_t value
-// RAII marker of a thread inside a Matcher / visual-odometry compute entry (matcher_engine.cpp)
-struct ActiveCaller {
-    ActiveCaller();
-    ~ActiveCaller();
-    ActiveCaller(const ActiveCaller&) = delete;
-    ActiveCaller& operator=(const ActiveCaller&) = delete;
-};
-
 // Where bucketFeatures and getRandomSample draw from.  Default: libc rand(), the process-wide stream the reference
 // uses (matcher.cpp:297-343 via std::random_shuffle, viso.cpp:130-153).  An object switched to a PRIVATE stream
 // (svh_vo_set_private_rand) draws from its own generator instead, which reproduces glibc's srand(seed) / rand()

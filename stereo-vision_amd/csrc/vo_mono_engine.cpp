@@ -443,52 +443,30 @@ int mono_run_batch(MonoVo* const* Ms, int32_t K, int* state, std::vector<int32_t
     MONO_TRY(none, hipSetDevice(M0->device));
     BatchRec& rec = batch_recorder(M0->device);
     hipStream_t s = M0->stream;
-    // whatever way a phase fails: nothing stays in flight, the recorder is free again
-    struct Drain {
-        hipStream_t s;
-        BatchRec& rec;
-        bool armed;
-        ~Drain() {
-            if (!armed) return;
-            t_rec = nullptr;
-            (void)hipStreamSynchronize(s);
-            rec.reset();
-            rec.synced();
-        }
-    } drain{s, rec, true};
     for (int phase = 0; phase < 3 && !live.empty(); phase++) {
         bool timing = false;
         for (int i : live) timing = timing || Ms[i]->timing;
-        rec.reset();
-        t_rec = &rec;
-        for (int i : live) {
-            rec.begin_object();
-            mono_enqueue(Ms[i], phase);
-        }
-        t_rec = nullptr;
-        if (rec.broken) {   // (not reachable with equal parameters) one by one on the objects' own streams
-            rec.reset();
-            for (int i : live) {
-                mark(Ms[i], 0);
+        Phase ph{"VisualOdometryMono", FI_wait};
+        if (timing) ph.ev[0] = M0->ev[0], ph.ev[1] = M0->ev[1];
+        const int rc = run_recorded(
+            rec, s, live.data(), (int)live.size(), ph,
+            [&](int i) -> int {   // (without a recorder: on the object's own stream, between its own events)
+                const bool own = t_rec == nullptr;
+                if (own) mark(Ms[i], 0);
                 mono_enqueue(Ms[i], phase);
-                mark(Ms[i], 1);
-                const int rc = wait(Ms[i], phase);
-                if (rc) {
-                    (void)hipStreamSynchronize(Ms[i]->stream);
-                    return rc;
-                }
-            }
-        } else {
-            if (timing) (void)hipEventRecord(M0->ev[0], s);
-            MONO_TRY(copy, rec.flush(s));   // (its one copy is the upload of the job tables)
-            if (timing) (void)hipEventRecord(M0->ev[1], s);
-            MONO_TRY(wait, (hipError_t)wait_stream(s));
-            rec.synced();
-            MONO_TRY(launch, hipGetLastError());
-            float ms = 0;
-            if (timing && hipEventElapsedTime(&ms, M0->ev[0], M0->ev[1]) == hipSuccess)
-                for (int i : live) Ms[i]->ms[phase] = ms;   // the phase's time for the whole batch
-        }
+                if (own) mark(Ms[i], 1);
+                return SVH_OK;
+            },
+            [&](int i) -> int {
+                const int r = wait(Ms[i], phase);
+                if (r) (void)hipStreamSynchronize(Ms[i]->stream);
+                return r;
+            },
+            no_undo);
+        if (rc < 0) return rc;
+        float ms = 0;   // (one by one: every object has its own phase time)
+        if (timing && rc != kOneByOne && hipEventElapsedTime(&ms, M0->ev[0], M0->ev[1]) == hipSuccess)
+            for (int i : live) Ms[i]->ms[phase] = ms;   // the phase's time for the whole batch
         batch_parallel_for((int)live.size(), [&](int j) {
             const int i = live[j];
             state[i] = mono_after(Ms[i], phase, *inliers[i], tr6 + 6 * (size_t)i);
@@ -498,7 +476,6 @@ int mono_run_batch(MonoVo* const* Ms, int32_t K, int* state, std::vector<int32_t
             if (state[i] > 0) next.push_back(i);
         live.swap(next);
     }
-    drain.armed = false;   // (every phase was waited for)
     return SVH_OK;
 }
 

@@ -1,7 +1,7 @@
 // Sanitizer driver for the threaded HOST logic of the Matcher / visual-odometry engines
-// (matcher_engine.cpp, vo_engine.cpp: ring buffer, pinned count read-backs, sleep-polling waits chosen by the
+// (matcher_engine.cpp, vo_engine.cpp, batch_rec.cpp: ring buffer, pinned count read-backs, sleep-polling waits chosen by the
 // number of concurrent callers, helper-pool bypass of the outlier vote, bucketing, RANSAC bookkeeping) with
-// a STUB device layer: this file defines the HIP entry points those two files use (host memory, streams
+// a STUB device layer: this file defines the HIP entry points those files use (host memory, streams
 // that complete after a few queries) and their kernel launchers (deterministic synthetic feature tables,
 // matches and motion results of realistic sizes).  No GPU, no libamdhip64: CPU only.
 //   make -C stereo-vision_amd sanitize_viso    builds it with -fsanitize=thread and with
