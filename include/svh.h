@@ -285,6 +285,12 @@ int32_t svh_elas_set_stage(int32_t where);
  * many of them it handed back to the host path (coincident support points in a triangulation,
  * whose survivor depends on Triangle's pivot stream -- triangle.cpp:5446-5501, 6179-6196) */
 void svh_elas_stage_stats(int64_t* device_groups, int64_t* handed_back);
+/* diagnostics: how the device-stage groups finished so far had the launches behind their triangulations sized
+ * (planes, grid seeds, triangle ownership: they are enqueued before the group's counts exist).  out4[0]: by the
+ * bound (a lane's first group, and after every change of geometry, parameters or group size); out4[1]: by the
+ * counts of the lane's last groups; out4[2], out4[3]: of the latter, groups that held more triangles / more support
+ * points than the launch was sized for (the kernels stride over the rest: results do not depend on the size). */
+void svh_elas_sizing_stats(int64_t* out4);
 /* the engine settings in effect: out[0] workers (svh_elas_set_lanes), out[1] pairs per launch (0: automatic by image
  * size), out[2] stage (-1 / 0 / 1, svh_elas_set_stage), out[3] the workers' poll interval in microseconds */
 void svh_elas_get_settings(int32_t out[4]);

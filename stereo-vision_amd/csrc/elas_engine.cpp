@@ -156,6 +156,15 @@ struct Lane : LaneBufs {
     bool resident = false;          // the group on this lane runs the device stage
     bool force_host = false;        // rerun of a group the device stage handed back
     float P_key[5] = {-1, -1, -1, -1, -1};   // parameters the prior table on the device was built for
+    // Totals of the last device-stage groups this lane finished (from their StageCounts): phase B of the next group is
+    // enqueued before its own counts exist and sizes its launches by the largest of these (phase_b_size).  Valid
+    // for one geometry (release), one parameter set and one group size; without history the bound is used.
+    static constexpr int kHist = 4;
+    int32_t hist_sup[kHist] = {}, hist_tri[kHist] = {};
+    int hist_n = 0, hist_at = 0;
+    int32_t hist_g = 0;
+    svh_elas_params hist_p{};
+    PhaseBSize sized{};             // what the group in flight was launched with
     size_t o_P = 0, o_sup = 0, o_tri = 0;    // fixed layout of prior_dev in resident mode
 
     void release() {
@@ -164,6 +173,7 @@ struct Lane : LaneBufs {
         static_cast<LaneBufs&>(*this) = LaneBufs();
         stage_ok = false; stg = StageDev{};
         P_key[0] = -1;
+        hist_n = 0;
         W = H = 0;
     }
 
@@ -519,6 +529,9 @@ static int stage_mode_from_env() {   // (called by apply_config)
 }
 
 static std::atomic<int64_t> g_stage_dev_groups{0}, g_stage_redo_groups{0};
+// svh_elas_sizing_stats: device-stage groups whose phase B was sized by the bound / by the lane's history, and of the
+// latter those that held more triangles / more support points than the launch was sized for (the stride loops ran)
+static std::atomic<int64_t> g_sized_bound{0}, g_sized_hist{0}, g_short_tri{0}, g_short_sup{0};
 
 // sleep-poll (batch workers) or block on an event
 static hipError_t event_wait(Lane& L, hipEvent_t ev) {
@@ -593,7 +606,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
 
     // ---- everything after the triangulations (E8 .. E16); totals < 0: counts are on the device
     auto enqueue_phase_b = [&](size_t o_P, size_t o_sup, size_t o_tri, int32_t total_sup, int32_t total_tri,
-                               int32_t tri_bound) -> int {
+                               int32_t tri_bound, const PhaseBSize& size) -> int {
         GroupDev G;
         G.hdr = reinterpret_cast<const GroupHdr*>(L.prior_dev.p);
         G.P = reinterpret_cast<const int32_t*>(L.prior_dev + o_P);
@@ -620,7 +633,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         G.prior_absmax = 0;
         for (int32_t dd = 0; dd <= plane_radius && dd < (int32_t)L.P.size(); dd++)
             G.prior_absmax = std::max(G.prior_absmax, (int32_t)std::min<int64_t>(std::llabs((long long)L.P[dd]), INT32_MAX));
-        launch_prior(cx, p, d, g, total_sup, total_tri, G);
+        launch_prior(cx, p, d, g, total_sup, total_tri, G, size);
         if (tapping) {
             const int32_t n1 = hdr->tri_end[0], n2 = hdr->tri_end[1] - hdr->tri_end[0];
             rc = tap_dev(L, taps, SVH_ELAS_PLANES1, L.planes.p, (size_t)6 * n1); if (rc) return rc;
@@ -635,7 +648,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                 tap_host(taps, SVH_ELAS_GRID1 + k, gr.data(), gr.size());
             }
         }
-        launch_owner(cx, p, d, g, total_tri, G);
+        launch_owner(cx, p, d, g, total_tri, G, size);
         const bool tiles = !tapping && post_tiles_ok(p);   // gap + mean (+ speckle mask) tile kernels
         // the row kernel also applies the L/R check (its inputs are the row it just matched)
         const char* match_err = nullptr;
@@ -730,6 +743,30 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         HP_MARK(HP_WAIT);
         if (!L.resident) return SVH_OK;
         g_stage_dev_groups++;
+        {
+            // what this group held, for the launches of the lane's next groups (the counts arrived with the stream)
+            int32_t ts = 0, tt = 0;
+            for (int32_t j = 0; j < g; j++)
+                if (active_of(j)) {
+                    ts += L.h_counts.p->nsup[j];
+                    tt += L.h_counts.p->ntri[2 * j] + L.h_counts.p->ntri[2 * j + 1];
+                }
+            if (L.hist_n && (L.hist_g != g || memcmp(&L.hist_p, &p, sizeof(p)) != 0)) L.hist_n = 0;
+            if (!L.hist_n) L.hist_at = 0;
+            L.hist_g = g;
+            L.hist_p = p;
+            L.hist_sup[L.hist_at] = ts;
+            L.hist_tri[L.hist_at] = tt;
+            L.hist_at = (L.hist_at + 1) % Lane::kHist;
+            L.hist_n = std::min(L.hist_n + 1, (int)Lane::kHist);
+            if (L.sized.from_history) {
+                g_sized_hist++;
+                if (tt > L.sized.nt) g_short_tri++;
+                if (ts > L.sized.ns) g_short_sup++;
+            } else {
+                g_sized_bound++;
+            }
+        }
         bool redo = false;
         for (int32_t j = 0; j < g; j++) redo = redo || (L.h_counts.p->flags[j] & (STG_DUP | STG_OVERFLOW)) != 0;
         if (redo) {
@@ -860,11 +897,17 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                 }
                 tap_host(taps, SVH_ELAS_DCAN_RAW, L.h_dcan.p, nc);
             }
+            // k_stage_pack clears the grid bit sets of the group and writes the counts to the pinned h_counts itself
+            // (SVH_STAGE_BLITS=1, read per group: a hipMemsetAsync and a hipMemcpyAsync as before, for A/B runs).
+            // Either way h_counts is read only after stage_ev, or the whole stream, has completed.
+            const bool blits = svh::env("SVH_STAGE_BLITS") && atoi(svh::env("SVH_STAGE_BLITS")) != 0;
             launch_stage_device(cx, p, d, g, L.stg, reinterpret_cast<GroupHdr*>(L.prior_dev.p),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_sup),
-                                reinterpret_cast<int32_t*>(L.prior_dev + L.o_tri));
+                                reinterpret_cast<int32_t*>(L.prior_dev + L.o_tri),
+                                blits ? nullptr : L.seed.p, (size_t)2 * g * d.gw * d.gh * d.gwords,
+                                blits ? nullptr : L.h_counts.p);
             if (!L.stage_ev) HIP_TRY(none, hipEventCreateWithFlags(&L.stage_ev, hipEventDisableTiming));
-            HIP_TRY(copy, hipMemcpyAsync(L.h_counts, L.stg.counts, sizeof(StageCounts), hipMemcpyDeviceToHost, s));
+            if (blits) HIP_TRY(copy, hipMemcpyAsync(L.h_counts, L.stg.counts, sizeof(StageCounts), hipMemcpyDeviceToHost, s));
             HIP_TRY(none, hipEventRecord(L.stage_ev, s));
             if (tapping) {
                 // host copies of the header and the lists the device built (g == 1)
@@ -880,10 +923,21 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                                  (size_t)3 * (hdr->tri_end[1] - hdr->tri_end[0])); if (rc) return rc;
                 }
             }
+            L.sized = PhaseBSize{};
             if (!tapping || hdr->active[0]) {
                 // bound of the triangle count for the ownership base: 2 n - 5 per side
                 const int32_t tri_bound = 2 * g * 2 * L.stg.sup_cap;
-                rc = enqueue_phase_b(L.o_P, L.o_sup, L.o_tri, -1, -1, tri_bound);
+                // launch sizes from the lane's last groups (SVH_PHASEB_HISTORY=0, read per group: always the bound)
+                int32_t hint_sup = 0, hint_tri = 0;
+                const bool use_hist = !(svh::env("SVH_PHASEB_HISTORY") && atoi(svh::env("SVH_PHASEB_HISTORY")) == 0);
+                if (use_hist && L.hist_n && L.hist_g == g && memcmp(&L.hist_p, &p, sizeof(p)) == 0)
+                    for (int k = 0; k < L.hist_n; k++) {
+                        hint_sup = std::max(hint_sup, L.hist_sup[k]);
+                        hint_tri = std::max(hint_tri, L.hist_tri[k]);
+                    }
+                L.sized = phase_b_size(d, g, -1, -1, hint_sup, hint_tri);
+                L.sized.seed_cleared = !blits;
+                rc = enqueue_phase_b(L.o_P, L.o_sup, L.o_tri, -1, -1, tri_bound, L.sized);
                 if (rc) return rc;
             }
         }
@@ -1000,7 +1054,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
 
     // ---- phase B ---------------------------------------------------------
     HIP_TRY(copy, hipMemcpyAsync(L.prior_dev, L.h_prior, off, hipMemcpyHostToDevice, s));
-    rc = enqueue_phase_b(o_P, o_sup, o_tri, total_sup, total_tri, total_tri);
+    rc = enqueue_phase_b(o_P, o_sup, o_tri, total_sup, total_tri, total_tri, phase_b_size(d, g, total_sup, total_tri, 0, 0));
     if (rc) return rc;
     rc = copy_out(hdr->active);
     if (rc) return rc;
@@ -1793,6 +1847,14 @@ void svh_debug_stage_stamps(int64_t* out32) {
             (void)hipMemcpy(out32, l->stg.counts->dbg, 32 * sizeof(int64_t), hipMemcpyDeviceToHost);
             return;
         }
+}
+
+void svh_elas_sizing_stats(int64_t* out4) {
+    if (!out4) return;
+    out4[0] = svh::g_sized_bound.load();
+    out4[1] = svh::g_sized_hist.load();
+    out4[2] = svh::g_short_tri.load();
+    out4[3] = svh::g_short_sup.load();
 }
 
 void svh_elas_stage_stats(int64_t* device_groups, int64_t* handed_back) {

@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "dev_common.h"
+#include "prior_core.h"
 #include "svh_internal.h"
 
 namespace svh {
@@ -824,49 +825,10 @@ __global__ __launch_bounds__(kST) void k_support_lds(const uint8_t* __restrict__
 //                                  libelas/src/matrix.cpp:414-501
 //   triangle edges / validity      libelas/src/elas.cpp:1026-1072
 // fp64 with IEEE division and no contraction: the same operation sequence as
-// the reference's double code, so the float planes come out identical.
+// the reference's double code, so the float planes come out identical.  The
+// solver is svh::prior::solve3 (prior_core.h): the generic form's operations
+// with the pivot positions resolved into selects.
 // ---------------------------------------------------------------------------
-__device__ bool solve3(double A[3][3], double B[3]) {
-    bool used[3] = {false, false, false};
-    for (int it = 0; it < 3; it++) {
-        double big = 0.0;
-        int pr = 0, pc = 0;
-        for (int j = 0; j < 3; j++) {
-            if (used[j]) continue;
-            for (int k = 0; k < 3; k++)
-                if (!used[k] && fabs(A[j][k]) >= big) {  // ">=": the last maximum wins
-                    big = fabs(A[j][k]);
-                    pr = j;
-                    pc = k;
-                }
-        }
-        used[pc] = true;
-        if (pr != pc) {
-            for (int l = 0; l < 3; l++) {
-                double t = A[pr][l];
-                A[pr][l] = A[pc][l];
-                A[pc][l] = t;
-            }
-            double t = B[pr];
-            B[pr] = B[pc];
-            B[pc] = t;
-        }
-        if (fabs(A[pc][pc]) < 1e-20) return false;
-        const double inv = __ddiv_rn(1.0, A[pc][pc]);
-        A[pc][pc] = 1.0;
-        for (int l = 0; l < 3; l++) A[pc][l] = __dmul_rn(A[pc][l], inv);
-        B[pc] = __dmul_rn(B[pc], inv);
-        for (int r = 0; r < 3; r++) {
-            if (r == pc) continue;
-            const double f = A[r][pc];
-            A[r][pc] = 0.0;
-            for (int l = 0; l < 3; l++) A[r][l] = __dsub_rn(A[r][l], __dmul_rn(A[pc][l], f));
-            B[r] = __dsub_rn(B[r], __dmul_rn(B[pc], f));
-        }
-    }
-    return true;
-}
-
 __global__ __launch_bounds__(256) void k_prior(GroupDev G, int total_tri_arg) {
     // two lanes per triangle: lane rs = 0 fits the plane in left-image coordinates (t1a..c),
     // rs = 1 in right-image coordinates (t2a..c); the even lane then builds the raster record.
@@ -893,13 +855,14 @@ __global__ __launch_bounds__(256) void k_prior(GroupDev G, int total_tri_arg) {
     float mine[3];
     {
         double A[3][3], B[3];
+#pragma unroll
         for (int r = 0; r < 3; r++) {
             A[r][0] = (double)(rs ? su[r] - sd[r] : su[r]);
             A[r][1] = (double)sv[r];
             A[r][2] = 1.0;
             B[r] = (double)sd[r];
         }
-        if (solve3(A, B)) {
+        if (prior::solve3(A, B)) {
             mine[0] = (float)B[0];
             mine[1] = (float)B[1];
             mine[2] = (float)B[2];
@@ -2901,16 +2864,24 @@ void launch_support(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d
     }
 }
 
+PhaseBSize phase_b_size(const Dims& d, int32_t g, int32_t total_sup, int32_t total_tri, int32_t hint_sup, int32_t hint_tri) {
+    const int sup_bound = std::max(256, g * d.Wc * d.Hc / 6), tri_bound = 4 * sup_bound;
+    PhaseBSize z;
+    z.from_history = total_tri < 0 && total_sup < 0 && hint_sup > 0 && hint_tri > 0;
+    z.ns = total_sup >= 0 ? total_sup : z.from_history ? std::min(sup_bound, hint_sup + hint_sup / 8 + 1) : sup_bound;
+    z.nt = total_tri >= 0 ? total_tri : z.from_history ? std::min(tri_bound, hint_tri + hint_tri / 8 + 1) : tri_bound;
+    z.seed_cleared = false;
+    return z;
+}
+
 void launch_prior(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, int32_t g,
-                  int32_t total_sup, int32_t total_tri, const GroupDev& G) {
+                  int32_t total_sup, int32_t total_tri, const GroupDev& G, const PhaseBSize& size) {
     hipStream_t s = (hipStream_t)cx.stream;
     const int cells = d.gw * d.gh;
     const size_t words = (size_t)2 * g * cells * d.gwords;
-    (void)hipMemsetAsync(G.seed, 0, words * sizeof(uint32_t), s);
-    // device-built header: the launches are sized for a typical count (a lattice at ~15 % density)
-    // and stride over the rest
-    const int sup_bound = std::max(256, g * d.Wc * d.Hc / 6), tri_bound = 4 * sup_bound;
-    const int nt = total_tri >= 0 ? total_tri : tri_bound, ns = total_sup >= 0 ? total_sup : sup_bound;
+    // (device stage: k_stage_pack, the last kernel in front of this one on the stream, has cleared the words)
+    if (!size.seed_cleared) (void)hipMemsetAsync(G.seed, 0, words * sizeof(uint32_t), s);
+    const int nt = size.nt, ns = size.ns;
     if (nt > 0) LAUNCH("k_prior", k_prior, dim3((2 * nt + 255) / 256), dim3(256), G, total_tri);
     if (ns > 0)
         LAUNCH("k_grid_seed", k_grid_seed, dim3((ns + 255) / 256), dim3(256), G, total_sup,
@@ -2923,10 +2894,10 @@ void launch_prior(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, 
 }
 
 void launch_owner(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, int32_t g,
-                  int32_t total_tri, const GroupDev& G) {
+                  int32_t total_tri, const GroupDev& G, const PhaseBSize& size) {
     // no clearing: the engine hands every group a fresh owner_base above all values stored so far
     if (total_tri == 0) return;
-    const int nt = total_tri >= 0 ? total_tri : 4 * std::max(256, g * d.Wc * d.Hc / 6);   // see launch_prior
+    const int nt = size.nt;   // see phase_b_size
     // The span-ends form of the fix pass relies on two float evaluations a*u + b of one triangle edge
     // differing by less than one row (see k_owner).  |a*u| can reach H * (W + 2*disp_max) for an edge that
     // climbs the whole image within one column; beyond 2^22 one ulp of that product is half a row and the

@@ -791,11 +791,33 @@ __global__ __launch_bounds__(kT) void k_delaunay(StageDev S, DtParams P) {
 
 // ---------------------------------------------------------------------------
 // Packed lists + group header (what the host used to build and upload).  One block per slot.
+// Being the last kernel of the stage, it also takes over two jobs that were runtime blit kernels of their own:
+//   * all blocks together zero the grid bit sets of the group (`seed`, seed_words words; null: not asked), which
+//     k_grid_seed -- later on the same stream -- ORs into;
+//   * block 0 copies the counts to `h_counts` (pinned host memory; null: not asked).  They are final here: k_lattice
+//     and k_delaunay, which write them, ran before this kernel on the same stream.  The host memory is coherent
+//     (fine-grained): the stores are performed at system scope by the release at the end of this kernel, which comes
+//     before the kernel's completion signal; the engine records its event behind this kernel on the same stream and
+//     reads h_counts only after that event (or the whole stream) has completed.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_stage_pack(StageDev S, DtParams P, int g, GroupHdr* hdr, int32_t* support,
-                                                    int32_t* tri) {
+                                                    int32_t* tri, uint32_t* seed, size_t seed_words,
+                                                    StageCounts* h_counts) {
     __shared__ int s_scan[256 / 64 + 1];
     const int slot = blockIdx.x, pair = slot >> 1, side = slot & 1, tid = threadIdx.x;
+    if (seed) {
+        // 16 bytes per store where the words allow it (hipMalloc aligns `seed`), the tail word by word
+        const size_t quads = seed_words / 4;
+        uint4* q = reinterpret_cast<uint4*>(seed);
+        for (size_t i = (size_t)blockIdx.x * 256 + tid; i < quads; i += (size_t)gridDim.x * 256) q[i] = make_uint4(0, 0, 0, 0);
+        for (size_t i = 4 * quads + (size_t)blockIdx.x * 256 + tid; i < seed_words; i += (size_t)gridDim.x * 256) seed[i] = 0;
+    }
+    if (h_counts && slot == 0) {
+        static_assert(sizeof(StageCounts) % 4 == 0, "copied word by word");
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(S.counts);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(h_counts);
+        for (int i = tid; i < (int)(sizeof(StageCounts) / 4); i += 256) dst[i] = src[i];
+    }
     // offsets from the counts of all slots (<= 32 values)
     int sup_off = 0, tri_off = 0, total_sup = 0, total_tri = 0;
     bool active_me = false;
@@ -943,7 +965,8 @@ bool stage_device_preferred(const svh_elas_params& p, const Dims& d, bool deep_b
 }
 
 void launch_stage_device(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, int32_t g, const StageDev& S,
-                         GroupHdr* hdr, int32_t* support, int32_t* tri) {
+                         GroupHdr* hdr, int32_t* support, int32_t* tri, uint32_t* seed, size_t seed_words,
+                         StageCounts* h_counts) {
     hipStream_t s = (hipStream_t)cx.stream;
     LatticeParams L;
     L.W = d.W; L.H = d.H; L.Wc = d.Wc; L.Hc = d.Hc; L.step = d.step;
@@ -998,7 +1021,8 @@ void launch_stage_device(const LaunchCtx& cx, const svh_elas_params& p, const Di
     }
     {
         Timed t(cx, "k_stage_pack");
-        hipLaunchKernelGGL(k_stage_pack, dim3(2 * g), dim3(256), 0, s, S, D, g, hdr, support, tri);
+        hipLaunchKernelGGL(k_stage_pack, dim3(2 * g), dim3(256), 0, s, S, D, g, hdr, support, tri, seed,
+                           seed_words, h_counts);
     }
 }
 

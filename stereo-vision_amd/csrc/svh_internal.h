@@ -171,9 +171,12 @@ struct GroupDev {
 };
 
 // k_lattice + k_delaunay + k_stage_pack: from S.dcan to the packed support / triangle lists and
-// the group header in device memory
+// the group header in device memory.  k_stage_pack, the last of them, also does the two small jobs that used to be
+// runtime blit kernels of their own: it zeroes the `seed_words` words of the grid bit sets at `seed` (what
+// k_grid_seed of this group ORs into) and writes the counts to `h_counts` (pinned host memory, null: no copy).
 void launch_stage_device(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, int32_t g,
-                         const StageDev& S, GroupHdr* hdr, int32_t* support, int32_t* tri);
+                         const StageDev& S, GroupHdr* hdr, int32_t* support, int32_t* tri,
+                         uint32_t* seed, size_t seed_words, StageCounts* h_counts);
 
 // fly: E1 writes the two Sobel planes into `desc` instead of the descriptors (see descriptors_on_the_fly)
 void launch_descriptor(const LaunchCtx& cx, const DevImages& img, int32_t g, int32_t W, int32_t H,
@@ -183,13 +186,26 @@ bool descriptors_on_the_fly(const svh_elas_params& p, const Dims& d, int32_t pri
                             bool have_lists);
 void launch_support(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, int32_t g,
                     const uint8_t* desc, int16_t* dcan, bool fly);
+// Support points / triangles the launches of k_prior, k_grid_seed and the two k_owner passes are sized for.  Known
+// totals (host-built header) are taken as they are.  Device-built header (totals < 0): the kernels read the counts
+// from the header and stride over whatever is there, so ANY size is correct; hint_* > 0 -- the largest totals the
+// lane saw in its last groups -- plus a margin of 1/8 is used, capped by the bound that is used without a hint (a
+// lattice at ~15 % density).  The margin: an undershoot costs the blocks one more trip of their stride loop, an
+// overshoot costs waves that start, read the header and retire; 1/8 covers the drift between consecutive frames of
+// a sequence (support counts of the urban crops differ by 3-9 % between neighbours) and is exact for a batch of
+// repeated scenes.
+struct PhaseBSize {
+    int32_t ns, nt;
+    bool from_history;
+    bool seed_cleared;   // set by the engine when k_stage_pack of this group zeroed G.seed: launch_prior does not
+};
+PhaseBSize phase_b_size(const Dims& d, int32_t g, int32_t total_sup, int32_t total_tri, int32_t hint_sup, int32_t hint_tri);
 // planes + raster records + grid bit sets for the whole group.  total_sup / total_tri < 0: the
-// counts are in the device header (device-built), the launch is sized for `tri_bound` triangles
-// and the kernels stride over whatever is there
+// counts are in the device header (device-built).  G.seed is cleared here unless size.seed_cleared
 void launch_prior(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, int32_t g,
-                  int32_t total_sup, int32_t total_tri, const GroupDev& G);
+                  int32_t total_sup, int32_t total_tri, const GroupDev& G, const PhaseBSize& size);
 void launch_owner(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, int32_t g,
-                  int32_t total_tri, const GroupDev& G);
+                  int32_t total_tri, const GroupDev& G, const PhaseBSize& size);
 // dense matching; when `lr_out` is given and the row kernel applies, the L/R check is fused in
 // (returns true: the checked maps are in *lr_out, launch_lr must be skipped); `write_raw` keeps
 // the raw maps in G.Draw as well (parity taps)

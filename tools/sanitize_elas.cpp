@@ -78,7 +78,7 @@ namespace svh {
 bool stage_device_ok(const svh_elas_params&, const Dims&) { return true; }
 bool stage_device_preferred(const svh_elas_params&, const Dims&, bool) { return true; }
 void launch_stage_device(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t g, const StageDev& S, GroupHdr* hdr,
-                         int32_t*, int32_t*) {
+                         int32_t*, int32_t*, uint32_t* seed, size_t seed_words, StageCounts* h_counts) {
     // what k_lattice / k_delaunay / k_stage_pack leave behind: every third pair of a group has too few points
     memset(hdr, 0, sizeof(GroupHdr));
     hdr->npairs = g;
@@ -89,6 +89,9 @@ void launch_stage_device(const LaunchCtx&, const svh_elas_params&, const Dims&, 
         S.counts->flags[j] = few ? STG_FEW : 0;
         hdr->active[j] = few ? 0 : 1;
     }
+    // ... and the two small jobs k_stage_pack does on the way: the grid bit sets cleared, the counts in pinned memory
+    if (seed) memset(seed, 0, seed_words * sizeof(uint32_t));
+    if (h_counts) memcpy(h_counts, S.counts, sizeof(StageCounts));
 }
 void launch_descriptor(const LaunchCtx&, const DevImages&, int32_t, int32_t, int32_t, int32_t, uint8_t*, bool) {}
 bool descriptors_on_the_fly(const svh_elas_params&, const Dims&, int32_t, int32_t, bool) { return true; }
@@ -98,8 +101,13 @@ void launch_support(const LaunchCtx&, const svh_elas_params&, const Dims& d, int
     for (int32_t j = 0; j < g; j++)
         for (size_t i = 0; i < nc; i++) dcan[j * nc + i] = (int16_t)(j % 3 == 2 ? -1 : 20 + (int)(i % 3));
 }
-void launch_prior(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t, int32_t, int32_t, const GroupDev&) {}
-void launch_owner(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t, int32_t, const GroupDev&) {}
+PhaseBSize phase_b_size(const Dims&, int32_t, int32_t total_sup, int32_t total_tri, int32_t hint_sup, int32_t hint_tri) {
+    const bool hist = total_sup < 0 && total_tri < 0 && hint_sup > 0 && hint_tri > 0;
+    return PhaseBSize{hist ? hint_sup : total_sup, hist ? hint_tri : total_tri, hist, false};
+}
+void launch_prior(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t, int32_t, int32_t, const GroupDev&,
+                  const PhaseBSize&) {}
+void launch_owner(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t, int32_t, const GroupDev&, const PhaseBSize&) {}
 bool launch_match(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t, const GroupDev&, const DevMaps*, bool,
                   const char** error) {
     if (error) *error = nullptr;
