@@ -1,0 +1,86 @@
+/*
+ * svh_view.h -- the product of the stereomapper chain: the global map, accumulated on the device and rendered
+ * there.  The consumer of svh_map.h's point lists; a headless stand-in for the reference's OpenGL widget.
+ *
+ * Reference interfaces (paths relative to the reference checkout):
+ *   stereomapper/maindialog.cpp:602-606   onNewDisparityMapArrived: addPoints(getPoints()), addCamera(getHomographyTotal())
+ *   stereomapper/view3d.cpp:127-166       View3D::addCamera
+ *   stereomapper/view3d.cpp:174-254       View3D::addPoints
+ *   stereomapper/view3d.cpp:271-384       View3D::paintGL
+ *   stereomapper/view3d.cpp:388-399       View3D::resizeGL
+ *   stereomapper/view3d.cpp:403-463       View3D::recordHuman, playPoses
+ *
+ * View3D is a QGLWidget, and OpenGL leaves the rasterisation of points and lines partly to the implementation.
+ * The contract of this library is the arithmetic of stereo-vision_amd/csrc/view_core.h (restated in
+ * tests/view_ref.py and summarised in DESIGN.md): a 2-pixel point splat and lines under GL_LESS where the first
+ * drawn wins a tie, the camera outlines, track and axes laid over it, RGB8 out.  Equality with any OpenGL
+ * implementation is NOT verified.  Out of scope:
+ *   - the background wall quad (View3D::_bg_wall_flag, off by default in the reference),
+ *   - mouse interaction (mousePressEvent, mouseMoveEvent, wheelEvent): set the pose instead,
+ *   - multisampling (the widget asks for QGL::SampleBuffers): every pixel is one sample,
+ *   - PNG files: images are returned as bytes (include/view3d.h writes binary PPM).
+ *
+ * Plain C like svh_map.h.  An object has its own stream and every call returns when it is complete.  Calls return
+ * SVH_OK (or a count) or a negative SVH_ERR_*; svh_last_error() has the text.  SVH_ERR_BAD_ARG -- a null pointer, a
+ * width or height outside 1..16384, lists < 0, a negative count, n > 0 with a null array -- is decided before
+ * anything is read or changed.  After SVH_ERR_HIP the object renders what it held before the call; the one exception
+ * is svh_view_add_points / svh_view_add_map failing in a copy after the newest list had to be dropped: that list is
+ * then gone and nothing is appended.
+ */
+#ifndef SVH_VIEW_H
+#define SVH_VIEW_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "svh.h"       /* SVH_OK, SVH_ERR_*, svh_last_error */
+#include "svh_map.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct svh_view svh_view;
+typedef struct svh_view_pose  { float zoom, rotx, roty, tx, ty, tz; } svh_view_pose;   /* View3D::pose */
+typedef struct svh_view_flags { int32_t show_cams, show_grid, white; } svh_view_flags; /* defaults 1,1,0 */
+
+svh_view* svh_view_create(int32_t width, int32_t height);    /* NULL without a HIP device */
+void      svh_view_destroy(svh_view* v);
+void      svh_view_clear(svh_view* v);                       /* clearAll(): lists and cameras; pose and flags stay */
+int32_t   svh_view_resize(svh_view* v, int32_t width, int32_t height);
+void      svh_view_pose_default(svh_view_pose* p);           /* -1.5, 180, 0, 0, 0, -1.5 (view3d.cpp:13-18) */
+int32_t   svh_view_set_pose(svh_view* v, const svh_view_pose* p);
+int32_t   svh_view_set_flags(svh_view* v, const svh_view_flags* f);
+
+/* addPoints(p): `lists` arrays of (x,y,z,val) floats, n[i] points each, all on the host or all on the device.
+ * With more than one array the newest list of the object is dropped first; then the last two of the given arrays
+ * (or the only one) are appended, empty ones included.  SVH_ERR_UNSUPPORTED, nothing changed: the object would
+ * hold more than 2^31 - 4096 points (draw indices are 32 bits).                                              */
+int32_t   svh_view_add_points(svh_view* v, const float* const* xyzv, const int64_t* n, int32_t lists, int32_t on_device);
+
+/* addPoints(stereo_thread->getPoints()) for the frame svh_map_add has just processed, device to device: one list
+ * when that frame started a reconstruction (the first frame, one after svh_map_clear, one of another size), two
+ * -- list 0 may be empty -- when it fused.  SVH_ERR_BAD_ARG before the map's first frame.                    */
+int32_t   svh_view_add_map(svh_view* v, svh_map* m);
+
+/* addCamera(H_total, s, keyframe): the ten points of the outline, transformed on the host in double */
+int32_t   svh_view_add_camera(svh_view* v, const double* H_total /*4x4 row major*/, float s, int32_t keyframe);
+
+/* what: 0 lists, 1 points, 2 cameras, 3 points the store has room for (it grows geometrically) */
+int64_t   svh_view_count(svh_view* v, int32_t what);
+
+/* paintGL + grabFrameBuffer: width*height*3 bytes, row 0 = top, to the host or (rgb_on_device) a device pointer */
+int32_t   svh_view_render(svh_view* v, uint8_t* rgb, int32_t rgb_on_device);
+
+/* playPoses: one render per step of the reference's loop, 51 per pair of consecutive poses; returns the number of
+ * frames (0 for n < 2) and writes the first min(frames, cap) images back to back; rgb may be NULL with cap 0.  The
+ * object's pose afterwards is the last one rendered.  recordHuman is this with (pose, roty -45), (roty +45), (-45). */
+int64_t   svh_view_play_poses(svh_view* v, const svh_view_pose* poses, int32_t n, uint8_t* rgb, int64_t cap, int32_t rgb_on_device);
+
+/* the poses svh_view_play_poses renders, without rendering: writes min(frames, cap) poses, returns frames */
+int64_t   svh_view_play_sequence(const svh_view_pose* poses, int32_t n, svh_view_pose* out, int64_t cap);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -26,6 +26,7 @@
 #include "../../include/svh.h"
 #include "../../include/svh_map.h"
 #include "hip_guard.h"
+#include "map_internal.h"
 #include "svh_config.h"
 
 namespace {
@@ -283,29 +284,11 @@ __global__ __launch_bounds__(256) void k_disp_color(const float* __restrict__ D,
 // ---------------------------------------------------------------------------------------------
 // host engine
 // ---------------------------------------------------------------------------------------------
-struct svh_map {
-    svh_map_params p{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int32_t w = 0, h = 0;            // geometry the buffers are sized for
-    int cur = 0;                     // planes [cur], [1 - cur] = previous, swapped every frame
-    bool have_prev = false;
-    int32_t pw = 0, ph = 0;
-    struct Bufs {                    // everything sized by the geometry
-        svh::HipBuf<float> pl[2][5];         // I, D, X, Y, Z
-        svh::HipBuf<float4> pts[2];
-        svh::HipBuf<float> dD1;              // staged disparity map when the caller's is on the host
-        svh::HipBuf<uint8_t> dI1;
-        svh::HipBuf<int32_t> head, next;
-        svh::HipBuf<uint8_t> state;
-        svh::HipBuf<int32_t> blockcnt;
-        svh::PinnedBuf<uint8_t> h_stage;     // packed I1 rows, then D1
-    } b;
-    svh::PinnedBuf<int64_t> h_total; // point counts of the two lists
-    int64_t npts[2] = {0, 0};
-
-    Planes planes(int k) const { return Planes{b.pl[k][0], b.pl[k][1], b.pl[k][2], b.pl[k][3], b.pl[k][4]}; }
-};
+// struct svh_map: csrc/map_internal.h (the map view reads the point lists where they lie)
+static Planes planes_of(const svh_map* m, int k) {
+    const svh_map::Bufs& b = m->b;
+    return Planes{b.pl[k][0], b.pl[k][1], b.pl[k][2], b.pl[k][3], b.pl[k][4]};
+}
 
 #define MAP_TRY(kind, expr) SVH_HIP_TRY("map", kind, expr)
 #define MAP_GROW(buf, bytes) SVH_HIP_GROW("map", buf, bytes)
@@ -418,7 +401,7 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     c.gain_inv = 1;
     if (gain) c.gain_inv = 1.0 / gain;
 
-    const Planes cur = m->planes(m->cur), prev = m->planes(1 - m->cur);
+    const Planes cur = planes_of(m, m->cur), prev = planes_of(m, 1 - m->cur);
     hipLaunchKernelGGL(k_map_create, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, s, dD, b.dI1, w, h, w, c, cur);
     const int nb = (int)((n + 1023) / 1024);
     if (m->have_prev) {
@@ -441,6 +424,7 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     hipLaunchKernelGGL(k_map_scatter<false>, dim3(nb), dim3(256), 0, s, b.state, cur, w, h, b.blockcnt, b.pts[1]);
     MAP_TRY(wait, hipStreamSynchronize(s));
     MAP_TRY(launch, hipGetLastError());
+    m->last_fused = m->have_prev;
     m->npts[0] = m->h_total[0];
     m->npts[1] = m->h_total[1];
     // the current map becomes the previous one (the intended ":432")
@@ -487,7 +471,7 @@ int32_t svh_map_planes(svh_map* m, float* out5, size_t cap_floats) {
     const size_t n = (size_t)m->w * m->h;
     if (cap_floats < 5 * n) return svh::fail(SVH_ERR_BAD_ARG, "buffer too small");
     MAP_TRY(none, hipSetDevice(m->device));
-    const Planes p = m->planes(1 - m->cur);   // the map of the last frame
+    const Planes p = planes_of(m, 1 - m->cur);   // the map of the last frame
     float* src[5] = {p.I, p.D, p.X, p.Y, p.Z};
     for (int k = 0; k < 5; k++) MAP_TRY(copy, hipMemcpy(out5 + k * n, src[k], n * 4, hipMemcpyDeviceToHost));
     return SVH_OK;

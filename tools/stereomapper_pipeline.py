@@ -4,12 +4,17 @@
     drive (include/svh_kitti.h)  ->  VisualOdometryStereo::process  (pose, gain; include/svh.h svh_vo_*)
                                  ->  Elas::process                  (D1 on the device; svh_elas_*)
                                  ->  map fusion                     (point lists; include/svh_map.h)
+                                 ->  View3D::addCamera / addPoints  (the global map, on the device; include/svh_view.h)
 
-i.e. what ReadFromFilesThread, VisualOdometryThread and StereoThread do between them
-(readfromfilesthread.cpp:25-112, visualodometrythread.cpp:95-140, stereothread.cpp:62-170),
+i.e. what ReadFromFilesThread, VisualOdometryThread, StereoThread and MainDialog::onNewDisparityMapArrived do between
+them (readfromfilesthread.cpp:25-112, visualodometrythread.cpp:95-140, stereothread.cpp:62-170, maindialog.cpp:602-606),
 without the GUI.  Usage:
 
-    python tools/stereomapper_pipeline.py [--unrectified] <drive_dir> <calib_cam_to_cam.txt> [max_frames]
+    python tools/stereomapper_pipeline.py [--unrectified] [--render DIR] <drive_dir> <calib_cam_to_cam.txt> [max_frames]
+
+--render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
+DIR/frame_%06d.ppm, and at the end View3D::recordHuman's fly-through into DIR/img_320_480_%06d.ppm.  Without the flag
+the map is still accumulated on the device and the printed output is what it was.
 
 --unrectified: the drive holds RAW frames (KITTI's "extract" drives, S_xx pixels).  They are uploaded once and rectified
 on the device with K_xx, D_xx, R_rect_xx, P_rect_xx of cameras 0 and 1 (include/svh_rectify.h; what
@@ -55,14 +60,15 @@ class DeviceBuffer:
 
 
 class Pipeline:
-    def __init__(self, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None):
+    def __init__(self, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None, view_size=(320, 480)):
         import helpers as Hh
         import svhip as S
-        from svhip import mapper
+        from svhip import mapper, view
         self.S = S
         self.vo = Hh.ProductVo(Hh.vo_defaults(f=f, cu=cu, cv=cv, base=base))
         self.elas = S.Elas(elas_params if elas_params is not None else Hh.robotics())
         self.map = mapper.Mapper(f, cu, cv, base, max_dist)
+        self.view = view.View(*view_size)
         self.H_total = np.eye(4)
         self.buf = None
         self.poses = []
@@ -115,6 +121,9 @@ class Pipeline:
             return ok, 0, 0
         # stereothread.cpp:166-170
         self.map.add(None, I1, self.H_total, gain, device_ptr=dD1.ptr.value)
+        # maindialog.cpp:602-606: the lists go from the map to the view without leaving the device
+        self.view.add_camera(self.H_total, 0.1, True)
+        self.view.add_map(self.map)
         return ok, self.map._L.svh_map_points(self.map._h, 0, None, 0), self.map._L.svh_map_points(self.map._h, 1, None, 0)
 
 
@@ -122,9 +131,17 @@ def main():
     unrectified = "--unrectified" in sys.argv
     if unrectified:
         sys.argv.remove("--unrectified")
+    render_dir = None
+    if "--render" in sys.argv:
+        k = sys.argv.index("--render")
+        if k + 1 >= len(sys.argv):
+            raise SystemExit(__doc__)
+        render_dir = sys.argv[k + 1]
+        del sys.argv[k:k + 2]
+        os.makedirs(render_dir, exist_ok=True)
     if len(sys.argv) < 3:
         raise SystemExit(__doc__)
-    from svhip import kitti
+    from svhip import kitti, view
     calib = kitti.read_cam_to_cam(sys.argv[2])
     limit = int(sys.argv[3]) if len(sys.argv) > 3 else 1 << 30
     rp = None
@@ -139,10 +156,18 @@ def main():
         frames += 1
         print("frame %4d  t=%.3f  vo=%d  pose z=%.2f  points kept=%d new=%d" % (
             frames - 1, tl, ok, p.H_total[2, 3], n0, n1))
+        if render_dir:
+            view.write_ppm(os.path.join(render_dir, "frame_%06d.ppm" % (frames - 1)), p.view.render())
         if frames >= limit:
             break
     dt = time.perf_counter() - t0
     print("%d frames in %.2f s = %.1f frames/s (PNG decode included)" % (frames, dt, frames / max(dt, 1e-9)))
+    if render_dir:
+        n, images = p.view.record_human()
+        for k in range(n):
+            view.write_ppm(os.path.join(render_dir, "img_%d_%d_%06d.ppm" % (p.view.width, p.view.height, k)), images[k])
+        print("map of %d points in %d lists, %d cameras: %d frames and a fly-through of %d images in %s" % (
+            p.view.count(view.POINTS), p.view.count(view.LISTS), p.view.count(view.CAMERAS), frames, n, render_dir))
 
 
 if __name__ == "__main__":
