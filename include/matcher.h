@@ -99,6 +99,8 @@ public:
         report(svh_matcher_push_back(_h, I1, I2, dims, replace ? 1 : 0), "pushBack");
     }
     void pushBack(uint8_t* I1, int32_t* dims, const bool replace) { pushBack(I1, 0, dims, replace); }
+    // ---- extension (not in the reference): the frame is in DEVICE memory (svh_matcher_push_back_device; dI2 may be 0) ----
+    void pushBackDevice(const uint8_t* dI1, const uint8_t* dI2, int32_t* dims, const bool replace) { report(svh_matcher_push_back_device(_h, dI1, dI2, dims, replace ? 1 : 0), "pushBackDevice"); }
 
     // method: 0 = flow, 1 = stereo, 2 = quad matching
     void matchFeatures(int32_t method, Matrix* Tr_delta = 0) {

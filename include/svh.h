@@ -411,6 +411,24 @@ void svh_matcher_set_intrinsics(svh_matcher* m, double f, double cu, double cv, 
  * (single-image variant, matcher.h:118).  dims = {width,height,bytes_per_line}. */
 int32_t svh_matcher_push_back(svh_matcher* m, const uint8_t* I1, const uint8_t* I2,
                               const int32_t* dims, int32_t replace);
+/* pushBack of a frame that is already in DEVICE memory (the output of svh_rectify_pairs_device, the input of
+ * svh_elas_process_batch_device): no host packing, no upload.  No counterpart in the reference.
+ *   pointers  dI1 / dI2 are device pointers to dims[1] rows of dims[0] bytes, dims[2] bytes apart.  Any byte alignment
+ *             of the base and any pitch >= width are allowed (a rectified KITTI frame has pitch = width = 1242, so its
+ *             rows start unaligned).  dI2 may be NULL as in the host entry.  Only the aligned 4-byte words that hold
+ *             the frame's own bytes are read.
+ *   lifetime  the frame must be complete when the call is made (the call that produced it has returned, or the
+ *             caller has synchronised its stream); it is not read after the call returns.
+ *   errors    argument checks, SVH_ERR_BAD_DIMS with the reference's message, the ring-buffer rotation, `replace` and
+ *             "a prefetched frame is pending" (SVH_ERR_BAD_ARG) are those of svh_matcher_push_back; a HIP failure
+ *             returns SVH_ERR_HIP.
+ *   mixing    host and device pushes may alternate on one object.
+ * Every result -- feature tables, matches, svh_matcher_get_gain -- equals, bit for bit, that of the host entry given
+ * the same pixels.  svh_matcher_get_gain computes the window means on the device when one of the two left frames came
+ * through this entry (there is no host copy of it then) and adds the ratios on the host in inlier order, as the host
+ * loop does.  The lockstep and hand-over forms (*_batch) take host frames only: device frames there are out of scope. */
+int32_t svh_matcher_push_back_device(svh_matcher* m, const uint8_t* dI1, const uint8_t* dI2,
+                                     const int32_t* dims, int32_t replace);
 /* Matcher::matchFeatures(method, Tr_delta) -- matcher.cpp:209-293.  method 0 flow,
  * 1 stereo, 2 quad.  Tr_delta: 16 doubles row-major (4x4) or NULL.               */
 int32_t svh_matcher_match_features(svh_matcher* m, int32_t method, const double* Tr_delta);
@@ -492,6 +510,11 @@ void    svh_vo_destroy(svh_vo* v);
  * returns 1 (true), 0 (false: motion estimate failed) or a negative SVH_ERR_* */
 int32_t svh_vo_process(svh_vo* v, const uint8_t* I1, const uint8_t* I2, const int32_t* dims,
                        int32_t replace);
+/* svh_vo_process with the frame in device memory: pointers, lifetime, errors and mixing as documented at
+ * svh_matcher_push_back_device; return values, motion, inliers and gain equal those of svh_vo_process given the same
+ * pixels.  (dI1 = dI2 = NULL does not take a handed-over frame: the *_batch forms take host frames only.) */
+int32_t svh_vo_process_device(svh_vo* v, const uint8_t* dI1, const uint8_t* dI2, const int32_t* dims,
+                              int32_t replace);
 /* The random numbers of bucketFeatures (matcher.cpp:297-343) and getRandomSample (viso.cpp:130-153).  Default
  * (enable = 0): libc rand(), the process-wide stream the reference draws from after its srand(0) (viso.cpp:36).
  * enable = 1: the object draws from a PRIVATE generator that reproduces glibc's srand(seed) / rand() sequence,
@@ -564,6 +587,8 @@ svh_vo* svh_vo_mono_create(const svh_vo_mono_params* p);
  * One deliberate difference: where the reference exits the process (a plane distance |d| < 1e-20 in
  * Matrix::operator/, matrix.cpp:497-503, or no R|t candidate with a point in front of both cameras) this returns 0. */
 int32_t svh_vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, int32_t replace);
+/* ... with the frame in device memory (see svh_matcher_push_back_device); the lockstep forms below take host frames */
+int32_t svh_vo_mono_process_device(svh_vo* v, const uint8_t* dI, const int32_t* dims, int32_t replace);
 /* test tap: the inlier count of every RANSAC hypothesis of the last estimate that reached the RANSAC loop, in
  * iteration order; copies up to cap, returns the count (0 for a stereo object) */
 int32_t svh_vo_mono_get_votes(svh_vo* v, int32_t* out, int32_t cap);

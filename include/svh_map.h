@@ -51,6 +51,13 @@ void     svh_map_clear(svh_map* m);
 int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uint8_t* I1,
                     const int32_t* dims, const double* H_total, float gain);
 
+/* svh_map_add with BOTH inputs in device memory: dD1 as with d1_on_device, dI1 = dims[1] rows of dims[0] bytes,
+ * dims[2] bytes apart, any alignment and any pitch >= width.  The image is read where it lies (no host staging, no
+ * copy); both must be complete when the call is made and are not read after it returns.  Checks, errors and results
+ * (point lists, planes) are those of svh_map_add given the same pixels. */
+int32_t svh_map_add_device(svh_map* m, const float* dD1, const uint8_t* dI1, const int32_t* dims,
+                           const double* H_total, float gain);
+
 /* The two point lists StereoThread::_points holds after a frame, as (x, y, z, val) floats in the
  * reference's push_back order (columns left to right, each top to bottom):
  *   which 0   points of the previous map that were not merged into the current one

@@ -40,6 +40,8 @@ public:
         return svh_vo_mono_process(_vo, I, dims, replace ? 1 : 0) == 1;
     }
     using VisualOdometry::process;
+    // ---- extension (not in the reference): the image is in DEVICE memory (svh_vo_mono_process_device) ----
+    bool processDevice(const uint8_t* dI, int32_t* dims, bool replace = false) { return svh_vo_mono_process_device(_vo, dI, dims, replace ? 1 : 0) == 1; }
 
     // ---- extension (not in the reference) ----
     // bucketing / RANSAC samples from a private generator with glibc's srand(seed) sequence instead of the

@@ -37,6 +37,8 @@ public:
         return svh_vo_process(_vo, I1, I2, dims, replace ? 1 : 0) == 1;
     }
     using VisualOdometry::process;
+    // ---- extension (not in the reference): the pair is in DEVICE memory (svh_vo_process_device) ----
+    bool processDevice(const uint8_t* dI1, const uint8_t* dI2, int32_t* dims, bool replace = false) { return svh_vo_process_device(_vo, dI1, dI2, dims, replace ? 1 : 0) == 1; }
 
     // ---- extensions (not in the reference): K objects, one frame each, as ONE call (svh_vo_process_batch) ----
     // ok[i] (optional) = what process() of object i would have returned; returns the number of updated motions,

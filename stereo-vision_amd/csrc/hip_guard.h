@@ -88,6 +88,20 @@ using PinnedBuf = HipBuf<T, true>;
 
 }   // namespace svh
 extern "C" int32_t svh_test_fail_at(const char* spec);
+// TEST ACCESS to the device-frame path of the Matcher (matcher_engine.cpp), bound by name like the hook above:
+//   svh_test_pack_rows      k_pack_rows alone: src_dev = h rows of w bytes, pitch apart, in device memory; bpl * h bytes
+//                           (bpl a multiple of 16, >= w) come back in dst_host
+//   svh_test_matcher_image  the packed image of a view as it lies on the device, h rows of bpl bytes; view = 2 * current
+//                           + right (0 previous left .. 3 current right).  Returns the byte count (buf NULL: only that),
+//                           0 for a view without a frame, or a negative SVH_ERR_*
+//   svh_test_matcher_gain   Matcher::getGain over the object's two left frames for CALLER-GIVEN matches (real ones never
+//                           reach the window clamps); path 0 = the host loop (needs host-pushed frames), 1 = k_gain.
+//                           NaN, with svh_last_error() set, when it cannot run
+extern "C" int32_t svh_test_pack_rows(const uint8_t* src_dev, int32_t w, int32_t h, int32_t pitch, int32_t bpl,
+                                      uint8_t* dst_host);
+extern "C" int64_t svh_test_matcher_image(svh_matcher* m, int32_t view, uint8_t* buf, size_t cap);
+extern "C" float svh_test_matcher_gain(svh_matcher* m, const svh_p_match* matches, int32_t nm, const int32_t* inliers,
+                                       int32_t n, int32_t path);
 
 // The guard of every HIP call of the host engines: `kind` is one of none, malloc, copy, launch, wait (see above); a
 // disarmed hook costs one relaxed load.  Returns hip_failed(...) out of the enclosing function on failure.

@@ -354,8 +354,10 @@ void svh_map_clear(svh_map* m) {
     m->npts[0] = m->npts[1] = 0;
 }
 
-int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uint8_t* I1, const int32_t* dims,
-                    const double* H_total, float gain) {
+// svh_map_add / svh_map_add_device.  i1_on_device: I1 is read where it lies, at its own pitch (k_map_create takes
+// one), and D1 is on the device as well: no host staging at all
+static int32_t map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uint8_t* I1, bool i1_on_device,
+                       const int32_t* dims, const double* H_total, float gain) {
     if (!m || !D1 || !I1 || !dims || !H_total) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
     const int32_t w = dims[0], h = dims[1], step = dims[2];
     if (w < 1 || h < 1 || step < w || (int64_t)w * h > (1 << 28)) return svh::fail(SVH_ERR_BAD_ARG, "bad dimensions");
@@ -366,8 +368,14 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     const size_t n = (size_t)w * h;
     const svh_map::Bufs& b = m->b;
     // inputs: the image rows are packed on the way into pinned memory
-    for (int32_t v = 0; v < h; v++) memcpy(b.h_stage + (size_t)v * w, I1 + (size_t)v * step, w);
-    MAP_TRY(copy, hipMemcpyAsync(b.dI1, b.h_stage, n, hipMemcpyHostToDevice, s));
+    const uint8_t* dI = I1;
+    int32_t dstep = step;
+    if (!i1_on_device) {
+        for (int32_t v = 0; v < h; v++) memcpy(b.h_stage + (size_t)v * w, I1 + (size_t)v * step, w);
+        MAP_TRY(copy, hipMemcpyAsync(b.dI1, b.h_stage, n, hipMemcpyHostToDevice, s));
+        dI = b.dI1;
+        dstep = w;
+    }
     const float* dD = D1;
     if (!d1_on_device) {
         memcpy(b.h_stage + n, D1, n * 4);
@@ -402,7 +410,7 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     if (gain) c.gain_inv = 1.0 / gain;
 
     const Planes cur = planes_of(m, m->cur), prev = planes_of(m, 1 - m->cur);
-    hipLaunchKernelGGL(k_map_create, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, s, dD, b.dI1, w, h, w, c, cur);
+    hipLaunchKernelGGL(k_map_create, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, s, dD, dI, w, h, dstep, c, cur);
     const int nb = (int)((n + 1023) / 1024);
     if (m->have_prev) {
         const int pn = m->pw * m->ph;   // == n: a geometry change resets the reconstruction
@@ -433,6 +441,16 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
     m->ph = h;
     m->have_prev = true;
     return SVH_OK;
+}
+
+int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uint8_t* I1, const int32_t* dims,
+                    const double* H_total, float gain) {
+    return map_add(m, D1, d1_on_device, I1, false, dims, H_total, gain);
+}
+
+int32_t svh_map_add_device(svh_map* m, const float* dD1, const uint8_t* dI1, const int32_t* dims, const double* H_total,
+                           float gain) {
+    return map_add(m, dD1, 1, dI1, true, dims, H_total, gain);
 }
 
 int64_t svh_map_points(svh_map* m, int32_t which, float* xyzv, int64_t cap) {

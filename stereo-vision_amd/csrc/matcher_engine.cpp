@@ -109,6 +109,7 @@ struct DevView {
     int32_t nbins = 0;
     PinnedBuf<uint8_t> stage;               // the packed image (upload source, and getGain's host copy),
                                             // h rows of bpl bytes + one zero row
+    bool host_copy = false;                 // `stage` holds this frame (a host push); false after a device push
 };
 
 }  // namespace svh
@@ -145,6 +146,8 @@ struct svh_matcher {
     PinnedBuf<svh_p_match> h_pm;                // download staging for match lists
     PinnedBuf<int32_t> h_cnt;                   // match count
     PinnedBuf<int32_t> h_n;                     // feature counts [camera][sparse, dense]
+    PinnedBuf<float4> h_gain_in;                // k_gain: the inliers' (u1p, v1p, u1c, v1c) ...
+    PinnedBuf<GainOut> h_gain_out;              // ... and their ratios and flags
     bool taps = false;                          // keep every intermediate stage (parity tests)
     int32_t last_dense = 0;                     // matches of the last dense pass before the vote (predicts the next one)
     bool warm_on_wait = false;                  // wake the vote's helper threads once the dense pass is enqueued
@@ -272,6 +275,7 @@ static int ensure_match_scratch(svh_matcher* m, int32_t pm_need, size_t owner_ne
 // device work is enqueued (or, in a batched call, recorded)
 static int features_pack(svh_matcher* m, DevView& V, int cam, const uint8_t* src, int32_t pitch) {
     (void)m; (void)cam;
+    V.host_copy = true;
     // rows are packed at the aligned pitch into the view's pinned buffer (the ring buffer double-buffers it:
     // the previous frame's copy stays valid for getGain), then one linear DMA
     for (int32_t v = 0; v < V.h; v++) {
@@ -331,12 +335,20 @@ static int features_enqueue(svh_matcher* m, DevView& V, int cam, double* tf, boo
     return SVH_OK;   // the caller synchronises once after both cameras
 }
 
-static int compute_features(svh_matcher* m, DevView& V, int cam, const uint8_t* src, int32_t pitch) {
+// on_device: `src` is device memory (svh_matcher_push_back_device); the rows are packed by k_pack_rows on the camera's
+// stream straight into V.I, and the view has no host copy of this frame
+static int compute_features(svh_matcher* m, DevView& V, int cam, const uint8_t* src, int32_t pitch, bool on_device) {
     double tf[6] = {0, 0, 0, 0, 0, 0};
     if (g_mtiming) tf[0] = now_ms();
-    int rc = features_pack(m, V, cam, src, pitch);
+    int rc = SVH_OK;
+    if (on_device) {
+        V.host_copy = false;
+        mlaunch_pack_rows(cam == 1 ? m->stream2 : m->stream, src, V.w, V.h, pitch, V.I, V.bpl);
+    } else {
+        rc = features_pack(m, V, cam, src, pitch);
+    }
     if (rc) return rc;
-    rc = features_enqueue(m, V, cam, tf);
+    rc = features_enqueue(m, V, cam, tf, on_device);
     if (rc) return rc;
     if (g_mtiming)
         for (int i = 0; i < 5; i++) m->tfine[i] += tf[i + 1] - tf[i];
@@ -805,10 +817,9 @@ static void push_finish(svh_matcher* m, const uint8_t* I1, const uint8_t* I2) {
         }
 }
 
-int32_t svh_matcher_push_back(svh_matcher* m, const uint8_t* I1, const uint8_t* I2, const int32_t* dims,
-                              int32_t replace) {
-    svh::ActiveCaller active_;
-    if (m && !I1 && !I2 && m->has_next) return push_take_prefetched(m, replace);
+// pushBack of a frame in host (svh_matcher_push_back) or device memory (svh_matcher_push_back_device)
+static int32_t push_frame(svh_matcher* m, const uint8_t* I1, const uint8_t* I2, const int32_t* dims, int32_t replace,
+                          bool on_device) {
     int32_t rc = push_prepare(m, I1, I2, dims, replace);
     if (rc) return rc;
     const uint8_t* src[2] = {I1, I2};
@@ -817,7 +828,7 @@ int32_t svh_matcher_push_back(svh_matcher* m, const uint8_t* I1, const uint8_t* 
     for (int k = 0; k < 2; k++) {
         if (!src[k]) continue;
         if (timed) tev_record(m, 2 * k, k == 1 ? m->stream2 : m->stream);
-        rc = compute_features(m, m->cur[k], k, src[k], dims[2]);
+        rc = compute_features(m, m->cur[k], k, src[k], dims[2], on_device);
         if (rc) return rc;
         if (timed) tev_record(m, 2 * k + 1, k == 1 ? m->stream2 : m->stream);
     }
@@ -835,6 +846,21 @@ int32_t svh_matcher_push_back(svh_matcher* m, const uint8_t* I1, const uint8_t* 
         m->tdev[0] += a > b ? a : b;
     }
     return SVH_OK;
+}
+
+int32_t svh_matcher_push_back(svh_matcher* m, const uint8_t* I1, const uint8_t* I2, const int32_t* dims,
+                              int32_t replace) {
+    svh::ActiveCaller active_;
+    if (m && !I1 && !I2 && m->has_next) return push_take_prefetched(m, replace);
+    return push_frame(m, I1, I2, dims, replace, false);
+}
+
+// The same with the frame in device memory: k_pack_rows instead of the host packing and the upload.  (No images and a
+// pending prefetched frame: SVH_ERR_BAD_ARG from push_prepare -- the hand-over forms take host frames only.)
+int32_t svh_matcher_push_back_device(svh_matcher* m, const uint8_t* dI1, const uint8_t* dI2, const int32_t* dims,
+                                     int32_t replace) {
+    svh::ActiveCaller active_;
+    return push_frame(m, dI1, dI2, dims, replace, true);
 }
 
 }  // extern "C"
@@ -1324,9 +1350,14 @@ int32_t svh_matcher_get_matches(svh_matcher* m, svh_p_match* out, int32_t cap) {
     return (int32_t)m->m2.size();
 }
 
-// Matcher::getGain + mean   matcher.cpp:347-389, 1825-1837
-float svh_matcher_get_gain(svh_matcher* m, const int32_t* inliers, int32_t n) {
-    if (!m || !m->prev[0].valid || !m->cur[0].valid || m->m2.empty() || n == 0) return 1;
+// Matcher::getGain + mean   matcher.cpp:347-389, 1825-1837 over `nm` matches, in two forms with one result.
+// (the reference clamps both windows with dims_p; the views here are indexed by their own geometry, so the bound of a
+// view is never exceeded when the two frames differ)
+static GainView gain_view(const svh_matcher* m, const DevView& V) {
+    return GainView{V.I, V.bpl, V.h, std::min(m->dims_p[0], V.bpl - 1), std::min(m->dims_p[1], V.h)};
+}
+// the host loop over the views' pinned copies (both left frames were pushed from the host)
+static float gain_host(svh_matcher* m, const svh_p_match* matches, int32_t nm, const int32_t* inliers, int32_t n) {
     auto meanf = [](const DevView& V, int32_t u0, int32_t u1, int32_t v0, int32_t v1) {
         float s = 0;
         for (int32_t v = v0; v <= v1; v++)
@@ -1336,13 +1367,11 @@ float svh_matcher_get_gain(svh_matcher* m, const int32_t* inliers, int32_t n) {
     auto cl = [](int32_t x, int32_t hi) { return std::min(std::max(x, 0), hi); };
     float gain = 0;
     int32_t num = 0;
+    const GainView P = gain_view(m, m->prev[0]), Cv = gain_view(m, m->cur[0]);
     for (int32_t q = 0; q < n; q++) {
-        if (inliers[q] >= (int32_t)m->m2.size()) continue;
-        const svh_p_match& it = m->m2[inliers[q]];
-        // (the reference clamps both windows with dims_p; the views here are indexed by their
-        // own geometry, so the bound of a view is never exceeded when the two frames differ)
-        const int32_t W = std::min(m->dims_p[0], m->prev[0].bpl - 1), H = std::min(m->dims_p[1], m->prev[0].h);
-        const int32_t Wc = std::min(m->dims_p[0], m->cur[0].bpl - 1), Hc = std::min(m->dims_p[1], m->cur[0].h);
+        if (inliers[q] >= nm) continue;
+        const svh_p_match& it = matches[inliers[q]];
+        const int32_t W = P.W, H = P.H, Wc = Cv.W, Hc = Cv.H;
         const float mp = meanf(m->prev[0], cl((int32_t)it.u1p - 3, W), cl((int32_t)it.u1p + 3, W),
                                cl((int32_t)it.v1p - 3, H), cl((int32_t)it.v1p + 3, H));
         const float mc = meanf(m->cur[0], cl((int32_t)it.u1c - 3, Wc), cl((int32_t)it.u1c + 3, Wc),
@@ -1353,6 +1382,101 @@ float svh_matcher_get_gain(svh_matcher* m, const int32_t* inliers, int32_t n) {
         }
     }
     return num > 0 ? gain / (float)num : 1;
+}
+// k_gain over the packed device images, for frames without a host copy: the window means and their ratios on the
+// device, one lane per inlier; the ratios come back through pinned memory and are added here IN INLIER ORDER in float,
+// as the host loop adds them (a tree sum on the device would round differently)
+static int gain_device(svh_matcher* m, const svh_p_match* matches, int32_t nm, const int32_t* inliers, int32_t n,
+                       float* result) {
+    *result = 1;
+    HIP_TRY(none, hipSetDevice(m->device));
+    GROW_N(m->h_gain_in, (size_t)n);
+    GROW_N(m->h_gain_out, (size_t)n);
+    for (int32_t q = 0; q < n; q++) {
+        float4 c = {0.f, 0.f, 0.f, 0.f};
+        if (inliers[q] < nm) {
+            const svh_p_match& it = matches[inliers[q]];
+            c.x = it.u1p; c.y = it.v1p; c.z = it.u1c; c.w = it.v1c;
+        }
+        m->h_gain_in[q] = c;
+    }
+    mlaunch_gain(m->stream, gain_view(m, m->prev[0]), gain_view(m, m->cur[0]), m->h_gain_in, m->h_gain_out, n);
+    HIP_TRY(none, (hipError_t)wait_stream(m->stream));
+    HIP_TRY(launch, hipGetLastError());
+    float gain = 0;
+    int32_t num = 0;
+    for (int32_t q = 0; q < n; q++) {
+        if (inliers[q] >= nm || !m->h_gain_out[q].use) continue;
+        gain += m->h_gain_out[q].ratio;
+        num++;
+    }
+    if (num > 0) *result = gain / (float)num;
+    return SVH_OK;
+}
+
+float svh_matcher_get_gain(svh_matcher* m, const int32_t* inliers, int32_t n) {
+    if (!m || !m->prev[0].valid || !m->cur[0].valid || m->m2.empty() || n == 0) return 1;
+    if (m->prev[0].host_copy && m->cur[0].host_copy)
+        return gain_host(m, m->m2.data(), (int32_t)m->m2.size(), inliers, n);
+    float g = 1;
+    (void)gain_device(m, m->m2.data(), (int32_t)m->m2.size(), inliers, n, &g);   // (a HIP failure: reported, gain 1)
+    return g;
+}
+
+// ---- test access (declared in hip_guard.h next to svh_test_fail_at, not in the public header)
+// getGain over the object's two left frames for caller-given matches: real matches never come near the image border
+// (the non-maximum suppression's margin), so the clamps are reached through this entry only.  path 0: the host loop
+// (both frames pushed from the host), 1: k_gain.  NaN with svh_last_error() set when it cannot run.
+float svh_test_matcher_gain(svh_matcher* m, const svh_p_match* matches, int32_t nm, const int32_t* inliers, int32_t n,
+                            int32_t path) {
+    const float nan = nanf("");
+    if (!m || nm < 0 || n < 0 || (nm > 0 && !matches) || (n > 0 && !inliers) || (path != 0 && path != 1)) {
+        (void)mfail(SVH_ERR_BAD_ARG, "null argument");
+        return nan;
+    }
+    if (!m->prev[0].valid || !m->cur[0].valid) {
+        (void)mfail(SVH_ERR_BAD_ARG, "the object holds no two left frames");
+        return nan;
+    }
+    if (n == 0) return 1;
+    if (path == 0) {
+        if (!m->prev[0].host_copy || !m->cur[0].host_copy) {
+            (void)mfail(SVH_ERR_BAD_ARG, "the host loop needs frames pushed from the host");
+            return nan;
+        }
+        return gain_host(m, matches, nm, inliers, n);
+    }
+    float g = 1;
+    return gain_device(m, matches, nm, inliers, n, &g) ? nan : g;
+}
+
+// the packed image of a view as it lies on the device (h rows of bpl bytes): view = 2 * current + right.  Returns the
+// number of bytes (buf NULL: only that), 0 for a view without a frame, or a negative SVH_ERR_*
+int64_t svh_test_matcher_image(svh_matcher* m, int32_t view, uint8_t* buf, size_t cap) {
+    if (!m || view < 0 || view > 3) return mfail(SVH_ERR_BAD_ARG, "null argument");
+    const DevView& V = (view & 2 ? m->cur : m->prev)[view & 1];
+    if (!V.valid) return 0;
+    const size_t n = (size_t)V.bpl * V.h;
+    if (!buf) return (int64_t)n;
+    if (cap < n) return mfail(SVH_ERR_BAD_ARG, "image buffer too small");
+    HIP_TRY(none, hipSetDevice(m->device));
+    HIP_TRY(copy, hipMemcpy(buf, V.I, n, hipMemcpyDeviceToHost));
+    return (int64_t)n;
+}
+
+// k_pack_rows alone: `src_dev` (device memory; h rows of w bytes, pitch apart) -> bpl * h bytes in dst_host
+int32_t svh_test_pack_rows(const uint8_t* src_dev, int32_t w, int32_t h, int32_t pitch, int32_t bpl, uint8_t* dst_host) {
+    if (!src_dev || !dst_host) return mfail(SVH_ERR_BAD_ARG, "null argument");
+    if (w <= 0 || h <= 0 || pitch < w || bpl < w || bpl % 16 != 0) return mfail(SVH_ERR_BAD_DIMS, "image dimension mismatch");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return mfail(SVH_ERR_NO_DEVICE, "no HIP device visible: libsvhip has no CPU fallback");
+    HipBuf<uint8_t> d;
+    GROW_N(d, (size_t)bpl * h);
+    mlaunch_pack_rows(nullptr, src_dev, w, h, pitch, d, bpl);
+    HIP_TRY(launch, hipGetLastError());
+    HIP_TRY(copy, hipMemcpy(dst_host, d, (size_t)bpl * h, hipMemcpyDeviceToHost));
+    return SVH_OK;
 }
 
 int32_t svh_matcher_set_taps(svh_matcher* m, int32_t enable) {

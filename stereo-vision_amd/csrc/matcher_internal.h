@@ -40,6 +40,14 @@ struct MatchParams {
 // pinned host -> device copy by a kernel (bytes is a multiple of 16); the visual-odometry and reconstruction engines
 // upload through it as well
 void mlaunch_upload(void* stream, const uint8_t* pinned, uint8_t* dev, size_t bytes);
+// a frame in device memory (h rows of w bytes, `pitch` bytes apart, any alignment) -> dst: rows at bpl (a multiple of
+// 16, >= w) with bytes w .. bpl-1 zero; dst is 16-byte aligned.  The device form of features_pack + mlaunch_upload
+void mlaunch_pack_rows(void* stream, const uint8_t* src, int w, int h, int pitch, uint8_t* dst, int bpl);
+// Matcher::getGain on the packed device images, one lane per inlier: in[q] = (u1p, v1p, u1c, v1c), out[q] = the ratio
+// of the window means and whether it counts (mean_prev > 10); in / out: device-addressable (pinned host) memory
+struct GainView { const uint8_t* I; int bpl, h, W, H; };   // W, H: the inclusive clamps (W <= bpl - 1, H <= h)
+struct GainOut { float ratio; int32_t use; };
+void mlaunch_gain(void* stream, const GainView& prev, const GainView& cur, const float4* in, GainOut* out, int n);
 // small transfers (a multiple of 4 bytes) between pinned host and device memory: hipMemcpyAsync / hipMemsetAsync,
 // or -- while a batch is being recorded (batch_rec.h) -- jobs of one copy / fill kernel per phase
 void mlaunch_copy(void* stream, void* dst, const void* src, size_t bytes, int kind);

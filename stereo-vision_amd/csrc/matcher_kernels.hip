@@ -1204,6 +1204,71 @@ __device__ __forceinline__ void d_fill4(const Fill4Job& a, unsigned bx, unsigned
 }
 SVH_BATCHED_KERNEL(kd_fill4, , k_fill4_b, Fill4Job, 256, 1, d_fill4, true)
 
+// ---------------------------------------------------------------------------
+// A frame that is already in device memory (svh_matcher_push_back_device): its rows, at any pitch and any byte
+// alignment, are packed at the Matcher's aligned bpl with the bytes from w to bpl zero -- what features_pack and
+// k_upload leave in V.I for a host frame.  One thread per 16-byte chunk of the output: it reads the one to five
+// ALIGNED words that hold the chunk's own source bytes (never a word without a byte of the row in it, so never an
+// address outside the words the frame itself occupies), shifts them into place, clears what lies beyond w and
+// stores 16 bytes once.
+// ---------------------------------------------------------------------------
+struct PackRowsJob { const uint8_t* src; uint4* dst; int w, h, pitch, c16; };   // c16 = bpl / 16 chunks per row
+__device__ __forceinline__ PackRowsJob globalise(PackRowsJob a) { all_global(a.src, a.dst); return a; }
+__device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int k) {   // the low k bytes of v (k <= 0: none, >= 4: all)
+    return k >= 4 ? v : (k <= 0 ? 0u : v & ((1u << (8 * k)) - 1u));
+}
+__device__ __forceinline__ void d_pack_rows(const PackRowsJob& a, unsigned bx, unsigned) {
+    const unsigned i = bx * 256 + threadIdx.x;
+    if (i >= (unsigned)a.c16 * (unsigned)a.h) return;
+    const int row = (int)(i / (unsigned)a.c16), x0 = (int)(i - (unsigned)row * (unsigned)a.c16) * 16;
+    const int nv = min(a.w - x0, 16);   // bytes of the row in this chunk (<= 0: padding only)
+    uint4 o = {0u, 0u, 0u, 0u};
+    if (nv > 0) {
+        const uint8_t* p = a.src + (size_t)row * (size_t)a.pitch + x0;
+        const unsigned lead = (unsigned)((uintptr_t)p & 3u);
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p - lead);
+        const int nw = (int)(lead + (unsigned)nv + 3u) >> 2;   // 1..5 words hold bytes p[0 .. nv-1]
+        const uint32_t w0 = q[0];
+        const uint32_t w1 = nw > 1 ? q[1] : 0u, w2 = nw > 2 ? q[2] : 0u, w3 = nw > 3 ? q[3] : 0u, w4 = nw > 4 ? q[4] : 0u;
+        o.x = keep_bytes(__builtin_amdgcn_alignbyte(w1, w0, lead), nv);
+        o.y = keep_bytes(__builtin_amdgcn_alignbyte(w2, w1, lead), nv - 4);
+        o.z = keep_bytes(__builtin_amdgcn_alignbyte(w3, w2, lead), nv - 8);
+        o.w = keep_bytes(__builtin_amdgcn_alignbyte(w4, w3, lead), nv - 12);
+    }
+    a.dst[i] = o;
+}
+SVH_JOB_KERNEL(kd_pack_rows, , k_pack_rows, k_pack_rows_b, PackRowsJob, 256, 1, d_pack_rows, true)
+
+// ---------------------------------------------------------------------------
+// Matcher::getGain + mean   matcher.cpp:347-389, 1825-1837 on the packed device images, one lane per inlier: the
+// means of the two 7x7 windows, clamped INCLUSIVELY to [0, W] x [0, H] as svh_matcher_get_gain clamps them.  Row H
+// does not exist on the device and is not loaded (the host copy has a zero row there); columns w .. bpl-1 are the
+// zero padding of the packed image.  A window sums at most 49 bytes: exact in an integer and in float in any order,
+// so one conversion and one division give the host loop's mean bit for bit.  out[q] = (mean_curr / mean_prev,
+// mean_prev > 10); the ratios are added on the host, in inlier order.
+// ---------------------------------------------------------------------------
+struct GainJob { GainView prev, cur; const float4* in; GainOut* out; int n; };   // in: u1p v1p u1c v1c
+__device__ __forceinline__ GainJob globalise(GainJob a) { all_global(a.prev.I, a.cur.I, a.in, a.out); return a; }
+__device__ __forceinline__ float window_mean(const GainView& V, float u, float v) {
+    auto cl = [](int x, int hi) { return min(max(x, 0), hi); };
+    const int u0 = cl((int)u - 3, V.W), u1 = cl((int)u + 3, V.W), v0 = cl((int)v - 3, V.H), v1 = cl((int)v + 3, V.H);
+    uint32_t s = 0;
+    for (int y = v0; y <= v1 && y < V.h; y++)
+        for (int x = u0; x <= u1; x++) s += V.I[(size_t)y * V.bpl + x];
+    return __fdiv_rn((float)s, (float)((u1 - u0 + 1) * (v1 - v0 + 1)));
+}
+__device__ __forceinline__ void d_gain(const GainJob& a, unsigned bx, unsigned) {
+    const int q = (int)(bx * 64 + threadIdx.x);
+    if (q >= a.n) return;
+    const float4 c = a.in[q];
+    const float mp = window_mean(a.prev, c.x, c.y), mc = window_mean(a.cur, c.z, c.w);
+    GainOut o;
+    o.use = mp > 10 ? 1 : 0;
+    o.ratio = o.use ? __fdiv_rn(mc, mp) : 0.f;
+    a.out[q] = o;
+}
+SVH_JOB_KERNEL(kd_gain, , k_gain, k_gain_b, GainJob, 64, 1, d_gain, (int)blockIdx.x * 64 < a.n)
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1213,6 +1278,16 @@ void mlaunch_upload(void* stream, const uint8_t* pinned, uint8_t* dev, size_t by
     const size_t n16 = bytes / 16;   // bpl is a multiple of 16
     const UploadJob a = {reinterpret_cast<const uint4*>(pinned), reinterpret_cast<uint4*>(dev), n16};
     launch_or_record(stream, kd_upload, a, dim3((unsigned)((n16 + 255) / 256)));
+}
+
+void mlaunch_pack_rows(void* stream, const uint8_t* src, int w, int h, int pitch, uint8_t* dst, int bpl) {
+    const PackRowsJob a = {src, reinterpret_cast<uint4*>(dst), w, h, pitch, bpl / 16};   // bpl is a multiple of 16
+    launch_or_record(stream, kd_pack_rows, a, dim3((unsigned)(((size_t)(bpl / 16) * h + 255) / 256)));
+}
+
+void mlaunch_gain(void* stream, const GainView& prev, const GainView& cur, const float4* in, GainOut* out, int n) {
+    const GainJob a = {prev, cur, in, out, n};
+    if (n > 0) launch_or_record(stream, kd_gain, a, dim3((unsigned)((n + 63) / 64)));
 }
 
 // small transfers between pinned host and device memory, either direction (bytes: a multiple of 4)

@@ -254,13 +254,21 @@ static int32_t process_after_push(svh_vo* v) {
     return update_motion(v);
 }
 
-int32_t svh_vo_process(svh_vo* v, const uint8_t* I1, const uint8_t* I2, const int32_t* dims, int32_t replace) {
+// svh_vo_process / svh_vo_process_device: the frame in host or in device memory
+static int32_t vo_process(svh_vo* v, const uint8_t* I1, const uint8_t* I2, const int32_t* dims, int32_t replace,
+                          bool on_device) {
     svh::ActiveCaller active_;
     if (!v || !dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
     if (v->mono) return svh::fail(SVH_ERR_BAD_ARG, "svh_vo_process on a mono object: use svh_vo_mono_process");
-    const int32_t rc = svh_matcher_push_back(v->matcher, I1, I2, dims, replace);
+    const int32_t rc = (on_device ? svh_matcher_push_back_device : svh_matcher_push_back)(v->matcher, I1, I2, dims, replace);
     if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored -- viso_stereo.cpp:41-68 goes on; a missing or pending prefetched frame IS an error)   // bad dims: message printed, carry on like the reference
     return process_after_push(v);
+}
+int32_t svh_vo_process(svh_vo* v, const uint8_t* I1, const uint8_t* I2, const int32_t* dims, int32_t replace) {
+    return vo_process(v, I1, I2, dims, replace, false);
+}
+int32_t svh_vo_process_device(svh_vo* v, const uint8_t* dI1, const uint8_t* dI2, const int32_t* dims, int32_t replace) {
+    return vo_process(v, dI1, dI2, dims, replace, true);
 }
 
 // One frame of K sequences: K VisualOdometryStereo objects in lockstep.  The Matcher steps go through the batched
@@ -522,11 +530,11 @@ svh_vo* svh_vo_mono_create(const svh_vo_mono_params* p) {
     return v;
 }
 
-int32_t svh_vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, int32_t replace) {
+static int32_t vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, int32_t replace, bool on_device) {
     svh::ActiveCaller active_;
     if (!v || !dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
     if (!v->mono) return svh::fail(SVH_ERR_BAD_ARG, "svh_vo_mono_process on a stereo object");
-    int32_t rc = svh_matcher_push_back(v->matcher, I, nullptr, dims, replace);
+    int32_t rc = (on_device ? svh_matcher_push_back_device : svh_matcher_push_back)(v->matcher, I, nullptr, dims, replace);
     if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored)
     rc = svh_matcher_match_features(v->matcher, 0, nullptr);
     if (rc < 0) return rc;
@@ -534,6 +542,12 @@ int32_t svh_vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, in
     bucket_features(v->matcher, P.bucket_max_features, (float)P.bucket_width, (float)P.bucket_height, v->rng);
     fetch_matches(v);
     return update_motion(v);
+}
+int32_t svh_vo_mono_process(svh_vo* v, const uint8_t* I, const int32_t* dims, int32_t replace) {
+    return vo_mono_process(v, I, dims, replace, false);
+}
+int32_t svh_vo_mono_process_device(svh_vo* v, const uint8_t* dI, const int32_t* dims, int32_t replace) {
+    return vo_mono_process(v, dI, dims, replace, true);
 }
 
 // ---- K mono objects in lockstep.  The Matcher steps go through the batched Matcher entries with one camera and

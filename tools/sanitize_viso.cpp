@@ -92,6 +92,29 @@ static uint32_t mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; 
 // (the stub launchers run at once even while a batch is being recorded: the recorder stays empty, its flush is a no-op)
 void mlaunch_upload(void*, const uint8_t* pinned, uint8_t* dev, size_t bytes) { memcpy(dev, pinned, bytes); }
 void mlaunch_copy(void*, void* dst, const void* src, size_t bytes, int) { memcpy(dst, src, bytes); }
+// a "device" frame is host memory here: the rows at bpl, zero behind w -- what k_pack_rows writes
+void mlaunch_pack_rows(void*, const uint8_t* src, int w, int h, int pitch, uint8_t* dst, int bpl) {
+    for (int v = 0; v < h; v++) {
+        memcpy(dst + (size_t)v * bpl, src + (size_t)v * pitch, (size_t)w);
+        memset(dst + (size_t)v * bpl + w, 0, (size_t)(bpl - w));
+    }
+}
+// k_gain's indexing on the CPU (the sanitizers see every load of the two windows): row H is not loaded
+void mlaunch_gain(void*, const GainView& prev, const GainView& cur, const float4* in, GainOut* out, int n) {
+    auto mean = [](const GainView& V, float u, float v) {
+        auto cl = [](int x, int hi) { return x < 0 ? 0 : (x > hi ? hi : x); };
+        const int u0 = cl((int)u - 3, V.W), u1 = cl((int)u + 3, V.W), v0 = cl((int)v - 3, V.H), v1 = cl((int)v + 3, V.H);
+        uint32_t s = 0;
+        for (int y = v0; y <= v1 && y < V.h; y++)
+            for (int x = u0; x <= u1; x++) s += V.I[(size_t)y * V.bpl + x];
+        return (float)s / (float)((u1 - u0 + 1) * (v1 - v0 + 1));
+    };
+    for (int q = 0; q < n; q++) {
+        const float mp = mean(prev, in[q].x, in[q].y), mc = mean(cur, in[q].z, in[q].w);
+        out[q].use = mp > 10 ? 1 : 0;
+        out[q].ratio = out[q].use ? mc / mp : 0.f;
+    }
+}
 void mlaunch_fill(void*, void* dst, int v, size_t bytes) { memset(dst, v, bytes); }
 void mlaunch_half(void*, const uint8_t*, int, uint8_t*, int, int, int) {}
 void mlaunch_filters(void*, const uint8_t*, int, int, int, uint8_t*, uint8_t*, int16_t*, int16_t*) {}
@@ -366,8 +389,14 @@ int main(int argc, char** argv) {
                 I1[i] = (uint8_t)(svh::mix((uint32_t)(i + 977 * f + 31 * id)) >> 24);
                 I2[i] = (uint8_t)(svh::mix((uint32_t)(i + 977 * f + 31 * id + 5)) >> 24);
             }
-            check(svh_vo_process(vo, I1.data(), I2.data(), dims, 0));
+            // host and device pushes alternate on one object (a "device" frame is host memory under the stub layer);
+            // the gain then takes the host loop or the k_gain path, and a few indices lie past the match list
+            if (f & 1) check(svh_vo_process_device(vo, I1.data(), I2.data(), dims, 0));
+            else check(svh_vo_process(vo, I1.data(), I2.data(), dims, 0));
             matches += svh_vo_num_matches(vo);
+            std::vector<int32_t> inl((size_t)svh_vo_get_inliers(vo, nullptr, 0) + 2, 1 << 20);
+            (void)svh_vo_get_inliers(vo, inl.data(), (int32_t)inl.size() - 2);
+            matches += svh_vo_get_gain(vo, inl.data(), (int32_t)inl.size()) > 0 ? 1 : 0;
         }
         svh_vo_destroy(vo);
     };

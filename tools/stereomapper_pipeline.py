@@ -10,7 +10,7 @@ i.e. what ReadFromFilesThread, VisualOdometryThread, StereoThread and MainDialog
 them (readfromfilesthread.cpp:25-112, visualodometrythread.cpp:95-140, stereothread.cpp:62-170, maindialog.cpp:602-606),
 without the GUI.  Usage:
 
-    python tools/stereomapper_pipeline.py [--unrectified] [--render DIR] <drive_dir> <calib_cam_to_cam.txt> [max_frames]
+    python tools/stereomapper_pipeline.py [--unrectified] [--resident] [--render DIR] <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
 DIR/frame_%06d.ppm, and at the end View3D::recordHuman's fly-through into DIR/img_320_480_%06d.ppm.  Without the flag
@@ -20,6 +20,10 @@ the map is still accumulated on the device and the printed output is what it was
 on the device with K_xx, D_xx, R_rect_xx, P_rect_xx of cameras 0 and 1 (include/svh_rectify.h; what
 framecapturethread.cpp:100-131, 328-349 does with OpenCV), ELAS reads the rectified pair where it lies, and one copy
 back feeds svh_vo_process, which takes host images.
+
+--resident: the frame never returns to the host.  A rectified drive's pair is uploaded once, a raw pair is rectified in
+place (--unrectified), and the visual odometry (svh_vo_process_device), ELAS and the map fusion (svh_map_add_device) all
+read that one device copy: no download, no second or third upload.  Results are the same bit for bit.
 
 Python is glue here (ctypes over libsvhip.so); the pose accumulation H_total = H_total * inv(H_delta)
 uses numpy where the reference uses Matrix::solve."""
@@ -60,7 +64,8 @@ class DeviceBuffer:
 
 
 class Pipeline:
-    def __init__(self, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None, view_size=(320, 480)):
+    def __init__(self, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None, view_size=(320, 480),
+                 resident=False):
         import helpers as Hh
         import svhip as S
         from svhip import mapper, view
@@ -73,6 +78,7 @@ class Pipeline:
         self.buf = None
         self.poses = []
         self.rect = None
+        self.resident = resident
         if rectify_params is not None:
             from svhip import rectify
             self.rect = rectify.Rectifier(rectify_params)
@@ -97,10 +103,19 @@ class Pipeline:
             self.raw[1].upload(I2)
             self.rect.pairs_device(1, self.raw[0].ptr.value, self.raw[1].ptr.value, sw, sw * sh,
                                    self.buf[0].ptr.value, self.buf[1].ptr.value, w, n)
-            I1 = self.buf[0].download(np.empty((h, w), np.uint8))
-            I2 = self.buf[1].download(np.empty((h, w), np.uint8))
+            if not self.resident:
+                I1 = self.buf[0].download(np.empty((h, w), np.uint8))
+                I2 = self.buf[1].download(np.empty((h, w), np.uint8))
         # visualodometrythread.cpp:100-137
-        ok = self.vo.process(I1, I2) == 1
+        if self.resident:
+            # the pair is on the device once (uploaded here, or rectified there) and every stage reads that copy
+            from svhip import resident
+            if self.rect is None:
+                self.buf[0].upload(I1)
+                self.buf[1].upload(I2)
+            ok = resident.vo_process(self.vo, self.buf[0].ptr.value, self.buf[1].ptr.value, w, h, w) == 1
+        else:
+            ok = self.vo.process(I1, I2) == 1
         gain = 0.0
         if ok:
             Hd = self.vo.motion()
@@ -112,7 +127,7 @@ class Pipeline:
         self.poses.append(self.H_total.copy())
         # stereothread.cpp:62-115: ELAS with the disparity maps left on the device
         dI1, dI2, dD1, dD2 = self.buf
-        if self.rect is None:
+        if self.rect is None and not self.resident:
             dI1.upload(I1)
             dI2.upload(I2)
         st = self.elas.process_batch_device(1, dI1.ptr.value, dI2.ptr.value, n, dD1.ptr.value, dD2.ptr.value,
@@ -120,7 +135,10 @@ class Pipeline:
         if st[0] != 0:
             return ok, 0, 0
         # stereothread.cpp:166-170
-        self.map.add(None, I1, self.H_total, gain, device_ptr=dD1.ptr.value)
+        if self.resident:
+            resident.map_add(self.map, dD1.ptr.value, dI1.ptr.value, w, h, self.H_total, gain, pitch=w)
+        else:
+            self.map.add(None, I1, self.H_total, gain, device_ptr=dD1.ptr.value)
         # maindialog.cpp:602-606: the lists go from the map to the view without leaving the device
         self.view.add_camera(self.H_total, 0.1, True)
         self.view.add_map(self.map)
@@ -131,6 +149,9 @@ def main():
     unrectified = "--unrectified" in sys.argv
     if unrectified:
         sys.argv.remove("--unrectified")
+    resident = "--resident" in sys.argv
+    if resident:
+        sys.argv.remove("--resident")
     render_dir = None
     if "--render" in sys.argv:
         k = sys.argv.index("--render")
@@ -148,7 +169,7 @@ def main():
     if unrectified:
         from svhip import rectify
         rp = rectify.params_from_kitti(calib, 0, 1)
-    p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp)
+    p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident)
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
