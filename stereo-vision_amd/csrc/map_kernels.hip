@@ -28,6 +28,7 @@
 #include "hip_guard.h"
 #include "map_internal.h"
 #include "svh_config.h"
+#include "view2d_core.h"
 
 namespace {
 
@@ -260,23 +261,12 @@ __global__ __launch_bounds__(256) void k_map_scatter(const uint8_t* __restrict__
 __global__ __launch_bounds__(256) void k_disp_color(const float* __restrict__ D, long long n, float* __restrict__ rgb) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    // std::min(D / d_max, 1.0f) as its comparison: a NaN disparity stays NaN and the pixel black (fminf gives 1: red)
-    const float q = __fdiv_rn(D[i], 200.f);
-    const float val = (1.0f < q) ? 1.0f : q;
-    float r = 0.f, g = 0.f, b = 0.f;
-    if (val > 0) {
-        const float h2 = (float)(6.0 * (1.0 - (double)val));
-        const float x = (float)(1.0 * (1.0 - fabs((double)fmodf(h2, 2.0f) - 1.0)));
-        if (0 <= h2 && h2 < 1)       { r = 1; g = x; b = 0; }
-        else if (1 <= h2 && h2 < 2)  { r = x; g = 1; b = 0; }
-        else if (2 <= h2 && h2 < 3)  { r = 0; g = 1; b = x; }
-        else if (3 <= h2 && h2 < 4)  { r = 0; g = x; b = 1; }
-        else if (4 <= h2 && h2 < 5)  { r = x; g = 0; b = 1; }
-        else if (5 <= h2 && h2 <= 6) { r = 1; g = 0; b = x; }
-    }
-    rgb[3 * i + 0] = r;
-    rgb[3 * i + 1] = g;
-    rgb[3 * i + 2] = b;
+    // the arithmetic is shared with the disparity pane (k_view2d_texels): csrc/view2d_core.h
+    float c[3];
+    svh::view2d::disparity_colour(D[i], c);
+    rgb[3 * i + 0] = c[0];
+    rgb[3 * i + 1] = c[1];
+    rgb[3 * i + 2] = c[2];
 }
 
 }  // namespace

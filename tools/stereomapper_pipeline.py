@@ -5,16 +5,24 @@
                                  ->  Elas::process                  (D1 on the device; svh_elas_*)
                                  ->  map fusion                     (point lists; include/svh_map.h)
                                  ->  View3D::addCamera / addPoints  (the global map, on the device; include/svh_view.h)
+                                 ->  View2D x 3                     (the image panes, on the device; include/svh_view2d.h)
 
 i.e. what ReadFromFilesThread, VisualOdometryThread, StereoThread and MainDialog::onNewDisparityMapArrived do between
 them (readfromfilesthread.cpp:25-112, visualodometrythread.cpp:95-140, stereothread.cpp:62-170, maindialog.cpp:602-606),
 without the GUI.  Usage:
 
-    python tools/stereomapper_pipeline.py [--unrectified] [--resident] [--render DIR] <drive_dir> <calib_cam_to_cam.txt> [max_frames]
+    python tools/stereomapper_pipeline.py [--unrectified] [--resident] [--render DIR] [--panes DIR [--pane-size WxH]]
+                                          <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
 DIR/frame_%06d.ppm, and at the end View3D::recordHuman's fly-through into DIR/img_320_480_%06d.ppm.  Without the flag
 the map is still accumulated on the device and the printed output is what it was.
+
+--panes DIR: the window's three 2-D panes (maindialog.cpp:451-452, 506-511, 588-598) after every frame: the left and the
+right image with the matches over them (inliers coloured by disparity, outliers blue) into DIR/left_%06d.ppm and
+DIR/right_%06d.ppm, the colour-coded disparity map into DIR/disp_%06d.ppm.  A pane has the frame's size unless
+--pane-size WxH is given.  D1 is read where ELAS wrote it on the device, and with --resident so is the frame.  The
+printed output is what it is without the flag.
 
 --unrectified: the drive holds RAW frames (KITTI's "extract" drives, S_xx pixels).  They are uploaded once and rectified
 on the device with K_xx, D_xx, R_rect_xx, P_rect_xx of cameras 0 and 1 (include/svh_rectify.h; what
@@ -79,6 +87,8 @@ class Pipeline:
         self.poses = []
         self.rect = None
         self.resident = resident
+        self.frame = None      # what render_panes() shows: (I1, I2 or None when resident, w, h, vo ok, ELAS ok)
+        self.pane = None
         if rectify_params is not None:
             from svhip import rectify
             self.rect = rectify.Rectifier(rectify_params)
@@ -132,6 +142,7 @@ class Pipeline:
             dI2.upload(I2)
         st = self.elas.process_batch_device(1, dI1.ptr.value, dI2.ptr.value, n, dD1.ptr.value, dD2.ptr.value,
                                             4 * n, w, h, w)
+        self.frame = (None, None, w, h, ok, st[0] == 0) if self.resident else (I1, I2, w, h, ok, st[0] == 0)
         if st[0] != 0:
             return ok, 0, 0
         # stereothread.cpp:166-170
@@ -143,6 +154,30 @@ class Pipeline:
         self.view.add_camera(self.H_total, 0.1, True)
         self.view.add_map(self.map)
         return ok, self.map._L.svh_map_points(self.map._h, 0, None, 0), self.map._L.svh_map_points(self.map._h, 1, None, 0)
+
+    def render_panes(self, size=None):
+        """the three View2D panes of the frame push() has just processed, as [H, W, 3] uint8 images (left, right,
+        disparity); size = (W, H), the frame's size by default.  The frame is read on the device when it is resident,
+        D1 always; the matches are those of the visual odometry, none when it failed (setImage clears them)."""
+        from svhip import view2d
+        I1, I2, w, h, ok, have_d = self.frame
+        W, Ht = size if size is not None else (w, h)
+        if self.pane is None:
+            self.pane = [view2d.View2D(W, Ht) for _ in range(3)]
+        for pane in self.pane:
+            if (pane.width, pane.height) != (W, Ht):
+                pane.resize(W, Ht)
+        left, right, disp = self.pane
+        for k, (pane, I) in enumerate(((left, I1), (right, I2))):
+            if I is None:
+                pane.set_image_device(self.buf[k].ptr.value, w, h, w)
+            else:
+                pane.set_image(I)
+            if ok:
+                pane.set_matches_indexed(self.vo.matches(), self.vo.inliers(), left=(k == 0))
+        if have_d:
+            disp.set_disparity_device(self.buf[2].ptr.value, w, h)
+        return left.render(), right.render(), disp.render()
 
 
 def main():
@@ -160,6 +195,22 @@ def main():
         render_dir = sys.argv[k + 1]
         del sys.argv[k:k + 2]
         os.makedirs(render_dir, exist_ok=True)
+    panes_dir, pane_size = None, None
+    if "--pane-size" in sys.argv:
+        k = sys.argv.index("--pane-size")
+        try:
+            pane_size = tuple(int(v) for v in sys.argv[k + 1].lower().split("x"))
+            assert len(pane_size) == 2
+        except (IndexError, ValueError, AssertionError):
+            raise SystemExit(__doc__)
+        del sys.argv[k:k + 2]
+    if "--panes" in sys.argv:
+        k = sys.argv.index("--panes")
+        if k + 1 >= len(sys.argv):
+            raise SystemExit(__doc__)
+        panes_dir = sys.argv[k + 1]
+        del sys.argv[k:k + 2]
+        os.makedirs(panes_dir, exist_ok=True)
     if len(sys.argv) < 3:
         raise SystemExit(__doc__)
     from svhip import kitti, view
@@ -179,6 +230,9 @@ def main():
             frames - 1, tl, ok, p.H_total[2, 3], n0, n1))
         if render_dir:
             view.write_ppm(os.path.join(render_dir, "frame_%06d.ppm" % (frames - 1)), p.view.render())
+        if panes_dir:
+            for name, img in zip(("left", "right", "disp"), p.render_panes(pane_size)):
+                view.write_ppm(os.path.join(panes_dir, "%s_%06d.ppm" % (name, frames - 1)), img)
         if frames >= limit:
             break
     dt = time.perf_counter() - t0
