@@ -44,7 +44,7 @@ struct BatchRec {
     };
     std::vector<Slot> slots;
     int cursor = 0;           // call position of the object being recorded
-    bool broken = false;      // an object issued a different call sequence than the first one
+    bool broken = false;      // an object issued a different call sequence than the first one, or a job has no batched form
     // side streams (+ one event each) for work a lockstep call issues outside the recorded sequence: the image
     // uploads, several in flight at once
     static constexpr int kSide = 3;
@@ -158,9 +158,11 @@ inline int phase_wait(const Phase& ph, hipStream_t s) {
 //      code and issues the object's launcher calls -- into the recorder, or, called without one, on the object's own
 //      stream.  An error ends the phase.
 //   2. All objects issued the same sequence: flush(s) (kind copy), wait for s, synced().
-//      They did not (rec.broken; not reachable with equal parameters and sizes, kept so that a future launcher change
-//      cannot corrupt a batch): reset(), undo(), wait for s (work the caller issued on it outside the recorder), then
-//      object by object enqueue(i) outside the recorder and wait_own(i), the wait for object i's own stream(s).
+//      They did not, or a launcher found a job that has no batched form (rec.broken: mlaunch_bin_index sets it when a
+//      table's bin index needs more than the 156 KiB of LDS a recorded batch gets -- about 38 000 features, a 640 x 480
+//      frame at full resolution with nms_n = 2 has 45 000): reset(), undo(), wait for s (work the caller issued on it
+//      outside the recorder), then object by object enqueue(i) outside the recorder and wait_own(i), the wait for
+//      object i's own stream(s).
 //   3. hipGetLastError() (kind launch).
 // Returns SVH_OK, kOneByOne (> 0) after the one-by-one pass, or the error (< 0).
 // undo() takes back what the recording pass pretended (svh_matcher_match_features_batch: bin indices marked as built
