@@ -1035,16 +1035,17 @@ __global__ __launch_bounds__(256) void k_owner(GroupDev G, int total_tri_arg, in
     const int t = G.owner_base + 1 + (T - first);
     int32_t* owner = G.owner + (size_t)slot * W * H;
     const int cl = lane & 15, rp = lane >> 4;
-#pragma unroll
-    for (int part = 0; part < 2; part++) {
-        const int lo = part ? tr.uB : tr.uA, hi = part ? tr.uC : tr.uB;
-        if (lo == hi) continue;
-        const float ea = part ? tr.BCa : tr.ABa, eb = part ? tr.BCb : tr.ABb;
+    {
+        // The reference's two loops, [uA, uB) against edge AB and [uB, uC) against edge BC, as one walk: a lane takes
+        // the edge of the part its column lies in (uA == uB: no column lies below uB, uB == uC: none from uB on --
+        // the reference's two guards), so a triangle of a dozen columns is one step of 16 columns instead of two.
         // (the matchers return at once in the two columns at either end of a row -- elas.cpp:797-798 -- so those columns
         // are not written: their words stay stale = "no triangle", and k_match_list needs no column test of its own)
-        const int ulo = lo > 2 ? lo : 2, uhi = hi < W - 2 ? hi : W - 2;
+        const int ulo = tr.uA > 2 ? tr.uA : 2, uhi = tr.uC < W - 2 ? tr.uC : W - 2;
         for (int u = ulo + cl; u < uhi; u += 16) {
             if (sub && (u & 1)) continue;
+            const bool second = u >= tr.uB;
+            const float ea = second ? tr.BCa : tr.ABa, eb = second ? tr.BCb : tr.ABb;
             const float fu = (float)u;
             const int v1 = f2u2i(__fadd_rn(__fmul_rn(tr.ACa, fu), tr.ACb));
             const int v2 = f2u2i(__fadd_rn(__fmul_rn(ea, fu), eb));
