@@ -426,7 +426,9 @@ int32_t svh_matcher_push_back(svh_matcher* m, const uint8_t* I1, const uint8_t* 
  * Every result -- feature tables, matches, svh_matcher_get_gain -- equals, bit for bit, that of the host entry given
  * the same pixels.  svh_matcher_get_gain computes the window means on the device when one of the two left frames came
  * through this entry (there is no host copy of it then) and adds the ratios on the host in inlier order, as the host
- * loop does.  The lockstep and hand-over forms (*_batch) take host frames only: device frames there are out of scope. */
+ * loop does.  The lockstep forms have device entries of their own (svh_matcher_push_back_batch_device,
+ * svh_vo_process_batch_device, svh_vo_mono_process_batch_device); the hand-over forms (*_prefetch_batch,
+ * *_process_next_batch) take host frames only: device frames there are out of scope. */
 int32_t svh_matcher_push_back_device(svh_matcher* m, const uint8_t* dI1, const uint8_t* dI2,
                                      const int32_t* dims, int32_t replace);
 /* Matcher::matchFeatures(method, Tr_delta) -- matcher.cpp:209-293.  method 0 flow,
@@ -443,6 +445,15 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
                                     const uint8_t* const* I2, const int32_t* dims, int32_t replace);
 int32_t svh_matcher_match_features_batch(svh_matcher* const* ms, int32_t K, int32_t method,
                                          const double* const* Tr_delta);
+/* svh_matcher_push_back_batch with the K frames in device memory.  Pointers, lifetime and alignment per object are
+ * those of svh_matcher_push_back_device: every object has its own base pointer (dI1[i], dI2[i]) at any byte alignment;
+ * the pitch dims[2] >= dims[0] is shared.  Checks, return values and the one-by-one fallback (objects that differ,
+ * taps, K = 1 -- a loop over svh_matcher_push_back_device) are those of the host batch entry.  In lockstep no helper
+ * thread packs and nothing is uploaded: k_pack_rows is recorded in front of each camera's features, so the 2 K frames
+ * cost one launch per camera, and the views keep no host copy.  A pending prefetched frame is SVH_ERR_BAD_ARG (dI1 =
+ * NULL does not take it).  Host and device batch calls may alternate on the same objects, and with single calls. */
+int32_t svh_matcher_push_back_batch_device(svh_matcher* const* ms, int32_t K, const uint8_t* const* dI1,
+                                           const uint8_t* const* dI2, const int32_t* dims, int32_t replace);
 /* The NEXT frame of the K Matchers handed over early: its rows are packed, uploaded and its features computed into
  * a third set of per-frame buffers on the objects' second streams, and the call returns WITHOUT waiting -- that
  * work then overlaps the matchFeatures (and, under the visual odometry, the motion estimate) of the frame before
@@ -512,7 +523,8 @@ int32_t svh_vo_process(svh_vo* v, const uint8_t* I1, const uint8_t* I2, const in
                        int32_t replace);
 /* svh_vo_process with the frame in device memory: pointers, lifetime, errors and mixing as documented at
  * svh_matcher_push_back_device; return values, motion, inliers and gain equal those of svh_vo_process given the same
- * pixels.  (dI1 = dI2 = NULL does not take a handed-over frame: the *_batch forms take host frames only.) */
+ * pixels.  (dI1 = dI2 = NULL does not take a handed-over frame: the hand-over forms -- *_prefetch_batch,
+ * *_process_next_batch -- take host frames only.) */
 int32_t svh_vo_process_device(svh_vo* v, const uint8_t* dI1, const uint8_t* dI2, const int32_t* dims,
                               int32_t replace);
 /* The random numbers of bucketFeatures (matcher.cpp:297-343) and getRandomSample (viso.cpp:130-153).  Default
@@ -532,6 +544,12 @@ void svh_rand_sequence(uint32_t seed, int32_t* out, int32_t n);
  * still bootstrapping (viso_stereo.cpp:47-53) or differ in parameters are processed one after the other. */
 int32_t svh_vo_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I1, const uint8_t* const* I2,
                              const int32_t* dims, int32_t replace, int32_t* ok);
+/* svh_vo_process_batch with the K frames in device memory (svh_matcher_push_back_batch_device for the objects'
+ * Matchers): checks, return values, ok[], the draw order of rand() and the one-by-one fallback -- here a loop over the
+ * device entry of the single object -- are those of svh_vo_process_batch; results equal it bit for bit given the same
+ * pixels.  dI1 and dI2 are required: the hand-over forms below take host frames only. */
+int32_t svh_vo_process_batch_device(svh_vo* const* vs, int32_t K, const uint8_t* const* dI1, const uint8_t* const* dI2,
+                                    const int32_t* dims, int32_t replace, int32_t* ok);
 /* The pipelined frame loop.  svh_vo_prefetch_batch hands over the FIRST frame (svh_matcher_prefetch_batch for the
  * objects' Matchers; returns without waiting).  Then, per frame, svh_vo_process_next_batch processes the frame
  * handed over before and hands over the next one (next_I1 / next_I2; NULL after the last frame) as soon as the ring
@@ -553,6 +571,13 @@ int32_t svh_vo_get_matches(svh_vo* v, svh_p_match* out, int32_t cap);   /* _matc
 int32_t svh_vo_num_matches(svh_vo* v);                           /* getNumberOfMatches         */
 int32_t svh_vo_get_inliers(svh_vo* v, int32_t* out, int32_t cap);/* getInlierIndices           */
 float   svh_vo_get_gain(svh_vo* v, const int32_t* inliers, int32_t n);
+/* svh_vo_get_gain for K objects, stereo or mono: gain[i] is bit for bit svh_vo_get_gain(vs[i], inliers[i], n[i]),
+ * the 1 of an object without two frames or of n[i] == 0 included.  Objects whose two left frames both have host copies
+ * keep the host loop; all others share ONE launch and one wait, and their ratios are added on the host in inlier
+ * order.  SVH_ERR_BAD_ARG: a null table or object, the same object twice, K < 0, n[i] < 0, n[i] > 0 without
+ * inliers[i].  A HIP failure returns SVH_ERR_HIP and leaves the gains of the device objects at 1. */
+int32_t svh_vo_get_gain_batch(svh_vo* const* vs, int32_t K, const int32_t* const* inliers, const int32_t* n,
+                              float* gain);
 svh_matcher* svh_vo_matcher(svh_vo* v);                          /* the owned Matcher (taps)   */
 
 /* ===========================================================================
@@ -613,6 +638,11 @@ int32_t svh_vo_mono_get_timing(svh_vo* v, double* ms3);
  * launches), the same three values for every object that reached the phase. */
 int32_t svh_vo_mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I, const int32_t* dims,
                                   const int32_t* replace, int32_t* ok);
+/* The same with the K frames in device memory (svh_vo_mono_process_device per object; every object its own base
+ * pointer at any byte alignment, the pitch shared).  dI is required: the hand-over forms below take host frames
+ * only. */
+int32_t svh_vo_mono_process_batch_device(svh_vo* const* vs, int32_t K, const uint8_t* const* dI, const int32_t* dims,
+                                         const int32_t* replace, int32_t* ok);
 /* The pipelined loop, as svh_vo_prefetch_batch / svh_vo_process_next_batch: svh_vo_mono_prefetch_batch hands over the
  * FIRST frame (returns without waiting; the images must stay unchanged until the frame is taken), then per frame
  * svh_vo_mono_process_next_batch processes the frame handed over before and hands over the next one (next_I; NULL

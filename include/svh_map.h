@@ -58,6 +58,20 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
 int32_t svh_map_add_device(svh_map* m, const float* dD1, const uint8_t* dI1, const int32_t* dims,
                            const double* H_total, float gain);
 
+/* One frame of K maps in lockstep, every input in device memory: object i fuses (dD1[i], dI1[i]) with pose H_total[i]
+ * and gain[i], as svh_map_add_device(ms[i], dD1[i], dI1[i], dims, H_total[i], gain[i]) would -- point lists and planes
+ * are bit for bit those of K such calls, and svh_map_points, svh_map_planes and svh_view_add_map work per object
+ * afterwards.  `dims` (width, height, pitch of the images) is shared; the svh_map_params of the objects may differ.
+ * The maps that fuse with a previous map run as one recorded phase (one launch per kernel over all of them, one
+ * wait), the maps that start a reconstruction (first frame, after svh_map_clear, another geometry) as a second one;
+ * no object runs one by one because of its state.  Objects on different devices, or K = 1, run one after the other
+ * through svh_map_add_device.
+ * SVH_ERR_BAD_ARG, decided before anything is touched: a null table or a null entry of one, the same map twice,
+ * K < 0, bad dims.  K = 0: SVH_OK.  After SVH_ERR_HIP nothing is in flight and NO object has taken the frame: adding
+ * the same frames again gives the right result.  Host inputs have no batch form. */
+int32_t svh_map_add_batch_device(svh_map* const* ms, int32_t K, const float* const* dD1, const uint8_t* const* dI1,
+                                 const int32_t* dims, const double* const* H_total, const float* gain);
+
 /* The two point lists StereoThread::_points holds after a frame, as (x, y, z, val) floats in the
  * reference's push_back order (columns left to right, each top to bottom):
  *   which 0   points of the previous map that were not merged into the current one

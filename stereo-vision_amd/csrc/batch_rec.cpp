@@ -46,6 +46,9 @@ int active_callers() { return g_active_callers.load(std::memory_order_relaxed); 
 
 thread_local BatchRec* t_rec = nullptr;
 
+static std::atomic<int64_t> g_lockstep_counts[3];
+void lockstep_count(int which, int64_t by) { g_lockstep_counts[which].fetch_add(by, std::memory_order_relaxed); }
+
 hipError_t BatchRec::flush(hipStream_t s) {
     cursor = 0;
     if (slots.empty()) return hipSuccess;
@@ -74,10 +77,15 @@ hipError_t BatchRec::flush(hipStream_t s) {
     }
     hipError_t e = hipMemcpyAsync(d_arena + used, h_arena + used, need, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;
+    int64_t launches = 0;
     for (size_t i = 0; i < slots.size(); i++) {
         const Slot& sl = slots[i];
-        if (sl.njobs > 0) sl.fn(d_arena + at[i], sl.njobs, sl.gx, sl.gy, sl.lds, s);
+        if (sl.njobs > 0) {
+            sl.fn(d_arena + at[i], sl.njobs, sl.gx, sl.gy, sl.lds, s);
+            launches++;
+        }
     }
+    lockstep_count(2, launches);
     used += need;
     slots.clear();
     if (track) {
@@ -253,3 +261,8 @@ void batch_parallel_for(int n, const std::function<void(int)>& fn) {
 }
 
 }  // namespace svh
+
+extern "C" void svh_test_lockstep_counts(int64_t out[3]) {
+    if (!out) return;
+    for (int k = 0; k < 3; k++) out[k] = svh::g_lockstep_counts[k].load(std::memory_order_relaxed);
+}

@@ -153,6 +153,9 @@ inline int phase_wait(const Phase& ph, hipStream_t s) {
     return SVH_OK;
 }
 
+// the counters behind svh_test_lockstep_counts (hip_guard.h): 0 phases flushed, 1 phases one by one, 2 batched launches
+void lockstep_count(int which, int64_t by = 1);
+
 // One recorded device phase over the objects live[0..n-1] (null: 0..n-1) on stream `s`:
 //   1. rec.reset(); enqueue(i) of every object behind begin_object(), with `rec` installed.  enqueue returns an SVH_*
 //      code and issues the object's launcher calls -- into the recorder, or, called without one, on the object's own
@@ -205,6 +208,7 @@ int run_recorded(BatchRec& rec, hipStream_t s, const int* live, int n, const Pha
     if (ph.t_host) ph.t_host[0] = now_ms();
     const bool one_by_one = rec.broken;
     if (one_by_one) {
+        lockstep_count(1);
         rec.reset();
         undo();
         if ((rc = phase_wait(ph, s))) return rc;
@@ -217,6 +221,7 @@ int run_recorded(BatchRec& rec, hipStream_t s, const int* live, int n, const Pha
     } else {
         if (ph.ev[0]) (void)hipEventRecord(ph.ev[0], s);
         SVH_HIP_TRY(ph.entry, copy, rec.flush(s));   // (its one copy is the upload of the job tables)
+        lockstep_count(0);
         if (ph.ev[1]) (void)hipEventRecord(ph.ev[1], s);
         if (ph.t_host) ph.t_host[1] = now_ms();
         if (ph.wait) {

@@ -88,6 +88,12 @@ using PinnedBuf = HipBuf<T, true>;
 
 }   // namespace svh
 extern "C" int32_t svh_test_fail_at(const char* spec);
+// TEST TAP of the lockstep machinery (batch_rec.cpp), bound by name like the hook above; process-wide, never reset:
+//   out[0]  recorded phases that were flushed as batched launches (run_recorded)
+//   out[1]  recorded phases that fell back to one-by-one (a call-sequence mismatch, or a job without a batched form)
+//   out[2]  batched launches issued by BatchRec::flush
+// A loop over the single entries moves none of them, so a parity test that also reads these shows lockstep happened.
+extern "C" void svh_test_lockstep_counts(int64_t out[3]);
 // TEST ACCESS to the device-frame path of the Matcher (matcher_engine.cpp), bound by name like the hook above:
 //   svh_test_pack_rows      k_pack_rows alone: src_dev = h rows of w bytes, pitch apart, in device memory; bpl * h bytes
 //                           (bpl a multiple of 16, >= w) come back in dst_host

@@ -25,11 +25,18 @@
 #include "../../include/matrix.h"
 #include "../../include/svh.h"
 #include "../../include/svh_map.h"
+#include "batch_rec.h"
 #include "hip_guard.h"
+#include "job_kernel.h"
 #include "map_internal.h"
 #include "svh_config.h"
 #include "view2d_core.h"
 
+using namespace svh;
+
+// Every kernel of the fusion is a job struct with its globalise, a __device__ body and one SVH_JOB_KERNEL line
+// (job_kernel.h): the plain entry serves svh_map_add / svh_map_add_device, the batched one K maps in lockstep
+// (svh_map_add_batch_device).  Both run the same body.
 namespace {
 
 struct MapCoef {
@@ -44,6 +51,7 @@ struct MapCoef {
 struct Planes {
     float *I, *D, *X, *Y, *Z;
 };
+__device__ __forceinline__ void planes_global(Planes& p) { all_global(p.I, p.D, p.X, p.Y, p.Z); }
 
 // (int32_t)float as x86's cvttss2si does it: out of range / NaN -> INT_MIN
 __device__ __forceinline__ int32_t f2i_x86(float f) {
@@ -51,12 +59,30 @@ __device__ __forceinline__ int32_t f2i_x86(float f) {
 }
 
 // ---- createCurrentMap ---------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_map_create(const float* __restrict__ D1, const uint8_t* __restrict__ I1,
-                                                    int w, int h, int step, MapCoef c, Planes cur) {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
+// head (a lockstep batch only, else null): the target lists of the association start empty, head[a] = -1 -- what the
+// single call's memset leaves there
+struct MapCreateJob {
+    const float* D1;
+    const uint8_t* I1;
+    int w, h, step;
+    MapCoef c;
+    Planes cur;
+    int32_t* head;
+};
+__device__ __forceinline__ MapCreateJob globalise(MapCreateJob a) {
+    all_global(a.D1, a.I1, a.head);
+    planes_global(a.cur);
+    return a;
+}
+__device__ __forceinline__ void d_map_create(const MapCreateJob& j, unsigned bx, unsigned by) {
+    const int w = j.w, h = j.h;
+    const MapCoef& c = j.c;
+    const Planes& cur = j.cur;
+    const int u = (int)bx * 64 + (threadIdx.x & 63), v = (int)by * 4 + (threadIdx.x >> 6);
     if (u >= w || v >= h) return;
     const int a = v * w + u;
-    float I = (float)((double)(float)I1[(size_t)v * step + u] / 255.0);
+    if (j.head) j.head[a] = -1;
+    float I = (float)((double)(float)j.I1[(size_t)v * j.step + u] / 255.0);
     // gain ramp over the image border (:232-252): every pixel is touched by at most one (i, side)
     const int m = c.margin;
     int i = -1;
@@ -75,7 +101,7 @@ __global__ __launch_bounds__(256) void k_map_create(const float* __restrict__ D1
         const float lo = (t < 0.f) ? 0.f : t;
         I = (1.f < lo) ? 1.f : lo;
     }
-    float d = D1[a], X = 0.f, Y = 0.f, Z = 0.f;
+    float d = j.D1[a], X = 0.f, Y = 0.f, Z = 0.f;
     if (d > 0) {
         const float z = __fdiv_rn(__fmul_rn(c.f, c.base), d);
         if ((double)z > 0.1 && z < c.max_dist) {
@@ -94,14 +120,31 @@ __global__ __launch_bounds__(256) void k_map_create(const float* __restrict__ D1
     cur.Y[a] = Y;
     cur.Z[a] = Z;
 }
+SVH_JOB_KERNEL(kd_map_create, , k_map_create, k_map_create_b, MapCreateJob, 256, 1, d_map_create,
+               (int)blockIdx.x * 64 < a.w && (int)blockIdx.y * 4 < a.h)
 
 // ---- association, step 1: every valid previous point finds its target pixel -----------------
 // state: 0 = no point here, 1 = point that stays in the previous list, 2 = filed under a target
-__global__ __launch_bounds__(256) void k_map_project(Planes prev, int pw, int ph, int cw, int chh, MapCoef c,
-                                                     int32_t* __restrict__ head, int32_t* __restrict__ next,
-                                                     uint8_t* __restrict__ state) {
-    const int a = blockIdx.x * 256 + threadIdx.x;
-    if (a >= pw * ph) return;
+struct MapProjectJob {
+    Planes prev;
+    int pw, ph, cw, chh;
+    MapCoef c;
+    int32_t *head, *next;
+    uint8_t* state;
+};
+__device__ __forceinline__ MapProjectJob globalise(MapProjectJob a) {
+    planes_global(a.prev);
+    all_global(a.head, a.next, a.state);
+    return a;
+}
+__device__ __forceinline__ void d_map_project(const MapProjectJob& j, unsigned bx, unsigned) {
+    const Planes& prev = j.prev;
+    const MapCoef& c = j.c;
+    const int cw = j.cw, chh = j.chh;
+    int32_t* const head = j.head;
+    int32_t* const next = j.next;
+    const int a = (int)bx * 256 + threadIdx.x;
+    if (a >= j.pw * j.ph) return;
     uint8_t st = 0;
     if (prev.D[a] > 0) {
         st = 1;
@@ -117,15 +160,35 @@ __global__ __launch_bounds__(256) void k_map_project(Planes prev, int pw, int ph
             }
         }
     }
-    state[a] = st;
+    j.state[a] = st;
 }
+SVH_JOB_KERNEL(kd_map_project, , k_map_project, k_map_project_b, MapProjectJob, 256, 1, d_map_project,
+               (int)blockIdx.x * 256 < a.pw * a.ph)
 
 // ---- association, step 2: one thread per target pixel replays its points in scan order -------
-__global__ __launch_bounds__(256) void k_map_fuse(Planes prev, int pw, int ph, Planes cur, int cn,
-                                                  const int32_t* __restrict__ head,
-                                                  const int32_t* __restrict__ next, uint8_t* __restrict__ state) {
-    const int a2 = blockIdx.x * 256 + threadIdx.x;
-    if (a2 >= cn) return;
+struct MapFuseJob {
+    Planes prev;
+    int pw, ph;
+    Planes cur;
+    int cn;
+    const int32_t *head, *next;
+    uint8_t* state;
+};
+__device__ __forceinline__ MapFuseJob globalise(MapFuseJob a) {
+    planes_global(a.prev);
+    planes_global(a.cur);
+    all_global(a.head, a.next, a.state);
+    return a;
+}
+__device__ __forceinline__ void d_map_fuse(const MapFuseJob& j, unsigned bx, unsigned) {
+    const Planes& prev = j.prev;
+    const Planes& cur = j.cur;
+    const int pw = j.pw, ph = j.ph;
+    const int32_t* const head = j.head;
+    const int32_t* const next = j.next;
+    uint8_t* const state = j.state;
+    const int a2 = (int)bx * 256 + threadIdx.x;
+    if (a2 >= j.cn) return;
     int first = head[a2];
     if (first < 0) return;
     float D = cur.D[a2], X = cur.X[a2], Y = cur.Y[a2], Z = cur.Z[a2], I = cur.I[a2];
@@ -172,6 +235,7 @@ __global__ __launch_bounds__(256) void k_map_fuse(Planes prev, int pw, int ph, P
     cur.Z[a2] = Z;
     cur.I[a2] = I;
 }
+SVH_JOB_KERNEL(kd_map_fuse, , k_map_fuse, k_map_fuse_b, MapFuseJob, 256, 1, d_map_fuse, (int)blockIdx.x * 256 < a.cn)
 
 // ---- ordered compaction over the scan order e = u * h + v -------------------------------------
 // kFromState: element taken iff state == 1 (previous list); else iff D > 0 (current list)
@@ -180,29 +244,58 @@ __device__ __forceinline__ bool map_taken(const uint8_t* state, const float* D, 
     return kFromState ? state[a] == 1 : D[a] > 0;
 }
 
+// (the jobs of count and scatter: `aux` = the block counts written / the block offsets read, out = scatter's list)
+struct MapListJob {
+    const uint8_t* state;
+    Planes pl;
+    int w, h;
+    int32_t* aux;
+    float4* out;
+};
+__device__ __forceinline__ MapListJob globalise(MapListJob a) {
+    planes_global(a.pl);
+    all_global(a.state, a.aux, a.out);
+    return a;
+}
 template <bool kFromState>
-__global__ __launch_bounds__(256) void k_map_count(const uint8_t* __restrict__ state, Planes pl, int w, int h,
-                                                   int32_t* __restrict__ blockcnt) {
+__global__ void k_map_count(MapListJob a);
+template <bool kFromState>
+__global__ void k_map_count_b(const MapListJob* J);
+template <bool kFromState>
+__device__ __forceinline__ void d_map_count(const MapListJob& j, unsigned bx, unsigned) {
     __shared__ int s_sum[4];
+    const int w = j.w, h = j.h;
     const int n = w * h;
     int mine = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int e = blockIdx.x * 1024 + threadIdx.x * 4 + k;
+        const int e = (int)bx * 1024 + threadIdx.x * 4 + k;
         if (e < n) {
             const int u = e / h, v = e - u * h;
-            mine += map_taken<kFromState>(state, pl.D, v * w + u) ? 1 : 0;
+            mine += map_taken<kFromState>(j.state, j.pl.D, v * w + u) ? 1 : 0;
         }
     }
     for (int off = 32; off; off >>= 1) mine += __shfl_down(mine, off);
     if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = mine;
     __syncthreads();
-    if (threadIdx.x == 0) blockcnt[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    if (threadIdx.x == 0) j.aux[bx] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
 }
+SVH_JOB_KERNEL(kd_map_count0, template <>, k_map_count<false>, k_map_count_b<false>, MapListJob, 256, 1,
+               d_map_count<false>, (int)blockIdx.x * 1024 < a.w * a.h)
+SVH_JOB_KERNEL(kd_map_count1, template <>, k_map_count<true>, k_map_count_b<true>, MapListJob, 256, 1,
+               d_map_count<true>, (int)blockIdx.x * 1024 < a.w * a.h)
 
 // exclusive scan of the block counts in place (one workgroup); total -> *total
-__global__ __launch_bounds__(1024) void k_map_scan(int32_t* __restrict__ blockcnt, int nb, int64_t* __restrict__ total) {
+struct MapScanJob {
+    int32_t* blockcnt;
+    int nb;
+    int64_t* total;
+};
+__device__ __forceinline__ MapScanJob globalise(MapScanJob a) { all_global(a.blockcnt, a.total); return a; }
+__device__ __forceinline__ void d_map_scan(const MapScanJob& j, unsigned, unsigned) {
     __shared__ int s[1024];
+    int32_t* const blockcnt = j.blockcnt;
+    const int nb = j.nb;
     int carry = 0;
     for (int base = 0; base < nb; base += 1024) {
         const int i = base + threadIdx.x;
@@ -220,19 +313,26 @@ __global__ __launch_bounds__(1024) void k_map_scan(int32_t* __restrict__ blockcn
         __syncthreads();
         carry += chunk;
     }
-    if (threadIdx.x == 0) *total = carry;
+    if (threadIdx.x == 0) *j.total = carry;
 }
+SVH_JOB_KERNEL(kd_map_scan, , k_map_scan, k_map_scan_b, MapScanJob, 1024, 1, d_map_scan, blockIdx.x == 0)
 
 template <bool kFromState>
-__global__ __launch_bounds__(256) void k_map_scatter(const uint8_t* __restrict__ state, Planes pl, int w, int h,
-                                                     const int32_t* __restrict__ blockoff,
-                                                     float4* __restrict__ out) {
+__global__ void k_map_scatter(MapListJob a);
+template <bool kFromState>
+__global__ void k_map_scatter_b(const MapListJob* J);
+template <bool kFromState>
+__device__ __forceinline__ void d_map_scatter(const MapListJob& j, unsigned bx, unsigned) {
     __shared__ int s[256];
+    const uint8_t* const state = j.state;
+    const Planes& pl = j.pl;
+    float4* const out = j.out;
+    const int w = j.w, h = j.h;
     const int n = w * h;
     int addr[4], mine = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int e = blockIdx.x * 1024 + threadIdx.x * 4 + k;
+        const int e = (int)bx * 1024 + threadIdx.x * 4 + k;
         addr[k] = -1;
         if (e < n) {
             const int u = e / h, v = e - u * h;
@@ -251,11 +351,15 @@ __global__ __launch_bounds__(256) void k_map_scatter(const uint8_t* __restrict__
         s[threadIdx.x] += add;
         __syncthreads();
     }
-    int pos = blockoff[blockIdx.x] + s[threadIdx.x] - mine;
+    int pos = j.aux[bx] + s[threadIdx.x] - mine;
 #pragma unroll
     for (int k = 0; k < 4; k++)
         if (addr[k] >= 0) out[pos++] = make_float4(pl.X[addr[k]], pl.Y[addr[k]], pl.Z[addr[k]], pl.I[addr[k]]);
 }
+SVH_JOB_KERNEL(kd_map_scatter0, template <>, k_map_scatter<false>, k_map_scatter_b<false>, MapListJob, 256, 1,
+               d_map_scatter<false>, (int)blockIdx.x * 1024 < a.w * a.h)
+SVH_JOB_KERNEL(kd_map_scatter1, template <>, k_map_scatter<true>, k_map_scatter_b<true>, MapListJob, 256, 1,
+               d_map_scatter<true>, (int)blockIdx.x * 1024 < a.w * a.h)
 
 // ---- colour-coded disparity (stereothread.cpp:117-147) -------------------------------------------
 __global__ __launch_bounds__(256) void k_disp_color(const float* __restrict__ D, long long n, float* __restrict__ rgb) {
@@ -307,6 +411,84 @@ static int32_t map_ensure(svh_map* m, int32_t w, int32_t h) {
     m->have_prev = false;
     m->npts[0] = m->npts[1] = 0;
     return SVH_OK;
+}
+
+// coefficients (stereothread.cpp:196-199, 306-314, 450-455) with the Matrix class of the boundary
+static MapCoef map_coef(const svh_map* m, int32_t w, int32_t h, const double* H_total, float gain) {
+    MapCoef c;
+    {
+        Matrix Ht(4, 4, H_total);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 4; j++) c.hcf[4 * i + j] = (float)Ht._val[i][j];
+        Matrix Hi = Matrix::inv(Ht);
+        const bool ok = Hi._m == 4;
+        for (int j = 0; j < 4; j++) c.hfc[j] = ok ? (float)Hi._val[2][j] : 0.f;
+        Matrix K(3, 3);
+        K._val[0][0] = m->p.f; K._val[1][1] = m->p.f; K._val[0][2] = m->p.cu; K._val[1][2] = m->p.cv; K._val[2][2] = 1;
+        if (ok) {
+            Matrix top(3, 4);
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 4; j++) top._val[i][j] = Hi._val[i][j];
+            Matrix P = K * top;
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 4; j++) c.pfc[4 * i + j] = (float)P._val[i][j];
+        } else {
+            for (int i = 0; i < 12; i++) c.pfc[i] = 0.f;
+        }
+    }
+    c.f = m->p.f; c.cu = m->p.cu; c.cv = m->p.cv; c.base = m->p.base; c.max_dist = m->p.max_dist;
+    c.margin = std::min(std::min(200, w / 2), h / 2);
+    c.gain_inv = 1;
+    if (gain) c.gain_inv = 1.0 / gain;
+    return c;
+}
+
+// The device work of one frame of one map, launched on the map's stream or -- while the calling thread records a batch
+// (batch_rec.h) -- appended to the recorder.  A map without a previous one issues the shorter sequence.  The reset of
+// `head`: the single call's memset; a recorded frame has k_map_create write it (a memset cannot be recorded).
+// The point counts arrive in m->h_total ([0] only when the frame fuses).
+static int32_t map_enqueue(svh_map* m, const float* dD, const uint8_t* dI, int32_t w, int32_t h, int32_t dstep,
+                           const MapCoef& c) {
+    hipStream_t s = m->stream;
+    const size_t n = (size_t)w * h;
+    const svh_map::Bufs& b = m->b;
+    const bool fuse = m->have_prev;
+    const Planes cur = planes_of(m, m->cur), prev = planes_of(m, 1 - m->cur);
+    const MapCreateJob jc = {dD, dI, w, h, dstep, c, cur, fuse && t_rec ? (int32_t*)b.head : nullptr};
+    launch_or_record(s, kd_map_create, jc, dim3((w + 63) / 64, (h + 3) / 4));
+    const int nb = (int)((n + 1023) / 1024);
+    if (fuse) {
+        const int pn = m->pw * m->ph;   // == n: a geometry change resets the reconstruction
+        if (!t_rec) MAP_TRY(copy, hipMemsetAsync(b.head, 0xFF, n * 4, s));
+        const MapProjectJob jp = {prev, m->pw, m->ph, w, h, c, b.head, b.next, b.state};
+        launch_or_record(s, kd_map_project, jp, dim3((pn + 255) / 256));
+        const MapFuseJob jf = {prev, m->pw, m->ph, cur, (int)n, b.head, b.next, b.state};
+        launch_or_record(s, kd_map_fuse, jf, dim3((unsigned)((n + 255) / 256)));
+        const int pb = (pn + 1023) / 1024;
+        const MapListJob jl = {b.state, prev, m->pw, m->ph, b.blockcnt, b.pts[0]};
+        launch_or_record(s, kd_map_count1, jl, dim3(pb));
+        const MapScanJob js = {b.blockcnt, pb, m->h_total};
+        launch_or_record(s, kd_map_scan, js, dim3(1));
+        launch_or_record(s, kd_map_scatter1, jl, dim3(pb));
+    }
+    const MapListJob jl = {b.state, cur, w, h, b.blockcnt, b.pts[1]};
+    launch_or_record(s, kd_map_count0, jl, dim3(nb));
+    const MapScanJob js = {b.blockcnt, nb, m->h_total + 1};
+    launch_or_record(s, kd_map_scan, js, dim3(1));
+    launch_or_record(s, kd_map_scatter0, jl, dim3(nb));
+    return SVH_OK;
+}
+
+// the frame's device work is done: the object takes it
+static void map_take_frame(svh_map* m, int32_t w, int32_t h) {
+    m->last_fused = m->have_prev;
+    m->npts[0] = m->have_prev ? m->h_total[0] : 0;
+    m->npts[1] = m->h_total[1];
+    // the current map becomes the previous one (the intended ":432")
+    m->cur = 1 - m->cur;
+    m->pw = w;
+    m->ph = h;
+    m->have_prev = true;
 }
 
 extern "C" {
@@ -372,64 +554,12 @@ static int32_t map_add(svh_map* m, const float* D1, int32_t d1_on_device, const 
         MAP_TRY(copy, hipMemcpyAsync(b.dD1, b.h_stage + n, n * 4, hipMemcpyHostToDevice, s));
         dD = b.dD1;
     }
-    // coefficients (stereothread.cpp:196-199, 306-314, 450-455) with the Matrix class of the boundary
-    MapCoef c;
-    {
-        Matrix Ht(4, 4, H_total);
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 4; j++) c.hcf[4 * i + j] = (float)Ht._val[i][j];
-        Matrix Hi = Matrix::inv(Ht);
-        const bool ok = Hi._m == 4;
-        for (int j = 0; j < 4; j++) c.hfc[j] = ok ? (float)Hi._val[2][j] : 0.f;
-        Matrix K(3, 3);
-        K._val[0][0] = m->p.f; K._val[1][1] = m->p.f; K._val[0][2] = m->p.cu; K._val[1][2] = m->p.cv; K._val[2][2] = 1;
-        if (ok) {
-            Matrix top(3, 4);
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 4; j++) top._val[i][j] = Hi._val[i][j];
-            Matrix P = K * top;
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 4; j++) c.pfc[4 * i + j] = (float)P._val[i][j];
-        } else {
-            for (int i = 0; i < 12; i++) c.pfc[i] = 0.f;
-        }
-    }
-    c.f = m->p.f; c.cu = m->p.cu; c.cv = m->p.cv; c.base = m->p.base; c.max_dist = m->p.max_dist;
-    c.margin = std::min(std::min(200, w / 2), h / 2);
-    c.gain_inv = 1;
-    if (gain) c.gain_inv = 1.0 / gain;
-
-    const Planes cur = planes_of(m, m->cur), prev = planes_of(m, 1 - m->cur);
-    hipLaunchKernelGGL(k_map_create, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, s, dD, dI, w, h, dstep, c, cur);
-    const int nb = (int)((n + 1023) / 1024);
-    if (m->have_prev) {
-        const int pn = m->pw * m->ph;   // == n: a geometry change resets the reconstruction
-        MAP_TRY(copy, hipMemsetAsync(b.head, 0xFF, n * 4, s));
-        hipLaunchKernelGGL(k_map_project, dim3((pn + 255) / 256), dim3(256), 0, s, prev, m->pw, m->ph, w, h, c,
-                           b.head, b.next, b.state);
-        hipLaunchKernelGGL(k_map_fuse, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, prev, m->pw, m->ph, cur,
-                           (int)n, b.head, b.next, b.state);
-        const int pb = (pn + 1023) / 1024;
-        hipLaunchKernelGGL(k_map_count<true>, dim3(pb), dim3(256), 0, s, b.state, prev, m->pw, m->ph, b.blockcnt);
-        hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, s, b.blockcnt, pb, m->h_total);
-        hipLaunchKernelGGL(k_map_scatter<true>, dim3(pb), dim3(256), 0, s, b.state, prev, m->pw, m->ph, b.blockcnt,
-                           b.pts[0]);
-    } else {
-        m->h_total[0] = 0;
-    }
-    hipLaunchKernelGGL(k_map_count<false>, dim3(nb), dim3(256), 0, s, b.state, cur, w, h, b.blockcnt);
-    hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, s, b.blockcnt, nb, m->h_total + 1);
-    hipLaunchKernelGGL(k_map_scatter<false>, dim3(nb), dim3(256), 0, s, b.state, cur, w, h, b.blockcnt, b.pts[1]);
+    const MapCoef c = map_coef(m, w, h, H_total, gain);
+    rc = map_enqueue(m, dD, dI, w, h, dstep, c);
+    if (rc) return rc;
     MAP_TRY(wait, hipStreamSynchronize(s));
     MAP_TRY(launch, hipGetLastError());
-    m->last_fused = m->have_prev;
-    m->npts[0] = m->h_total[0];
-    m->npts[1] = m->h_total[1];
-    // the current map becomes the previous one (the intended ":432")
-    m->cur = 1 - m->cur;
-    m->pw = w;
-    m->ph = h;
-    m->have_prev = true;
+    map_take_frame(m, w, h);
     return SVH_OK;
 }
 
@@ -441,6 +571,54 @@ int32_t svh_map_add(svh_map* m, const float* D1, int32_t d1_on_device, const uin
 int32_t svh_map_add_device(svh_map* m, const float* dD1, const uint8_t* dI1, const int32_t* dims, const double* H_total,
                            float gain) {
     return map_add(m, dD1, 1, dI1, true, dims, H_total, gain);
+}
+
+// K maps in lockstep, one frame each, everything in device memory: the device work of all maps that fuse is recorded
+// and issued as ONE launch per kernel on ms[0]'s stream (batch_rec.h), and so is that of the maps that start a
+// reconstruction -- two recorded phases at the most, one wait each.  Results are those of K svh_map_add_device calls.
+int32_t svh_map_add_batch_device(svh_map* const* ms, int32_t K, const float* const* dD1, const uint8_t* const* dI1,
+                                 const int32_t* dims, const double* const* H_total, const float* gain) {
+    if (!ms || !dD1 || !dI1 || !dims || !H_total || !gain || K < 0) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    const int32_t w = dims[0], h = dims[1], step = dims[2];
+    if (w < 1 || h < 1 || step < w || (int64_t)w * h > (1 << 28)) return svh::fail(SVH_ERR_BAD_ARG, "bad dimensions");
+    for (int i = 0; i < K; i++)
+        if (!dD1[i] || !dI1[i] || !H_total[i]) return svh::fail(SVH_ERR_BAD_ARG, "null argument in the batch");
+    bool lockstep = false;
+    const int32_t bad = check_batch(ms, K, "map", &lockstep, [](int) { return true; });
+    if (bad) return bad;
+    if (K == 0) return SVH_OK;
+    if (!lockstep || K == 1) {
+        for (int i = 0; i < K; i++) {
+            const int32_t rc = svh_map_add_device(ms[i], dD1[i], dI1[i], dims, H_total[i], gain[i]);
+            if (rc) return rc;
+        }
+        return SVH_OK;
+    }
+    MAP_TRY(none, hipSetDevice(ms[0]->device));
+    std::vector<MapCoef> coef((size_t)K);
+    std::vector<int> group[2];   // 0: the maps that fuse, 1: those that start a reconstruction
+    for (int i = 0; i < K; i++) {
+        const int32_t rc = map_ensure(ms[i], w, h);   // (a change of geometry starts a new reconstruction)
+        if (rc) return rc;
+        coef[i] = map_coef(ms[i], w, h, H_total[i], gain[i]);
+        group[ms[i]->have_prev ? 0 : 1].push_back(i);
+    }
+    BatchRec& rec = batch_recorder(ms[0]->device);
+    hipStream_t s = ms[0]->stream;
+    for (int g = 0; g < 2; g++) {
+        if (group[g].empty()) continue;
+        const int32_t rc = run_recorded(
+            rec, s, group[g].data(), (int)group[g].size(), Phase{"map", FI_wait},
+            [&](int i) -> int { return map_enqueue(ms[i], dD1[i], dI1[i], w, h, step, coef[i]); },
+            [&](int i) -> int {
+                MAP_TRY(wait, hipStreamSynchronize(ms[i]->stream));
+                return SVH_OK;
+            },
+            no_undo);
+        if (rc < 0) return rc;   // (no object has taken the frame)
+    }
+    for (int i = 0; i < K; i++) map_take_frame(ms[i], w, h);
+    return SVH_OK;
 }
 
 int64_t svh_map_points(svh_map* m, int32_t which, float* xyzv, int64_t cap) {

@@ -987,11 +987,21 @@ int32_t svh_matcher_prefetch_batch(svh_matcher* const* ms, int32_t K, const uint
 // the device work of all K is recorded and issued as ONE launch per kernel (batch_rec.h) on ms[0]'s stream.
 // Results are those of K svh_matcher_push_back calls.  Objects must share parameters and image size;
 // otherwise (or with taps on) the call runs them one after the other.
-int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uint8_t* const* I1,
-                                    const uint8_t* const* I2, const int32_t* dims, int32_t replace) {
+// on_device (svh_matcher_push_back_batch_device): the frames are in device memory, every object's at its own base
+// pointer.  No helper thread packs and nothing is uploaded: k_pack_rows is recorded in front of each camera's features
+// (one k_pack_rows_b launch per camera over the K objects), and the views keep no host copy.
+static int32_t push_back_batch(svh_matcher* const* ms, int32_t K, const uint8_t* const* I1, const uint8_t* const* I2,
+                               const int32_t* dims, int32_t replace, bool on_device) {
     svh::ActiveCaller active_;
     if (!ms || K < 0 || !dims) return mfail(SVH_ERR_BAD_ARG, "null argument");
     if (K == 0) return SVH_OK;
+    if (!I1 && on_device) {
+        // (the hand-over forms take host frames only)
+        for (int i = 0; i < K; i++)
+            if (ms[i] && ms[i]->has_next)
+                return mfail(SVH_ERR_BAD_ARG, "a prefetched frame is pending: the device entries do not take it");
+        return mfail(SVH_ERR_BAD_ARG, "null argument");
+    }
     if (!I1) {
         // no images: every object takes the frame handed over by svh_matcher_prefetch_batch
         for (int i = 0; i < K; i++)
@@ -1038,7 +1048,8 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
     }
     auto serial = [&]() -> int32_t {
         for (int i = 0; i < K; i++) {
-            const int32_t rc = svh_matcher_push_back(ms[i], I1[i], I2 ? I2[i] : nullptr, dims, replace);
+            const int32_t rc = (on_device ? svh_matcher_push_back_device : svh_matcher_push_back)(
+                ms[i], I1[i], I2 ? I2[i] : nullptr, dims, replace);
             if (rc) return rc;
         }
         return SVH_OK;
@@ -1062,7 +1073,7 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
     // threads did: 2 x 16 objects 7.8-8.6 -> 8.7-9.0 k frames/s, 1 x 32 6.1-6.2 -> 6.3-6.6 k, 1 x 16 unchanged).
     // SVH_UPLOAD_BATCH=0: every packing thread launches its image's upload, rotating over the side streams.
     static const bool upload_recorded = !(svh::env("SVH_UPLOAD_BATCH") && atoi(svh::env("SVH_UPLOAD_BATCH")) == 0);
-    batch_parallel_for(K * ncam, [&](int j) {
+    if (!on_device) batch_parallel_for(K * ncam, [&](int j) {
         (void)hipSetDevice(ms[0]->device);
         svh_matcher* m = ms[j / ncam];
         const int cam = j % ncam;
@@ -1085,7 +1096,13 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
         up, ms[0]->stream, nullptr, K, ph,
         [&](int i) -> int {   // (without a recorder: on the object's own streams, the image uploaded again)
             for (int cam = 0; cam < ncam; cam++) {
-                const int r = features_enqueue(ms[i], ms[i]->cur[cam], cam, nullptr, t_rec && !upload_recorded);
+                DevView& V = ms[i]->cur[cam];
+                if (on_device) {
+                    V.host_copy = false;
+                    mlaunch_pack_rows(cam == 1 ? ms[i]->stream2 : ms[i]->stream, cam ? I2[i] : I1[i], V.w, V.h, dims[2],
+                                      V.I, V.bpl);
+                }
+                const int r = features_enqueue(ms[i], V, cam, nullptr, on_device || (t_rec && !upload_recorded));
                 if (r) return r;
             }
             return SVH_OK;
@@ -1104,6 +1121,16 @@ int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uin
         g_btime.calls[0]++;
     }
     return SVH_OK;
+}
+
+int32_t svh_matcher_push_back_batch(svh_matcher* const* ms, int32_t K, const uint8_t* const* I1,
+                                    const uint8_t* const* I2, const int32_t* dims, int32_t replace) {
+    return push_back_batch(ms, K, I1, I2, dims, replace, false);
+}
+
+int32_t svh_matcher_push_back_batch_device(svh_matcher* const* ms, int32_t K, const uint8_t* const* dI1,
+                                           const uint8_t* const* dI2, const int32_t* dims, int32_t replace) {
+    return push_back_batch(ms, K, dI1, dI2, dims, replace, true);
 }
 
 // matchFeatures' sanity checks (matcher.cpp:216-259): false = return silently, previous matches stay
@@ -1386,10 +1413,9 @@ static float gain_host(svh_matcher* m, const svh_p_match* matches, int32_t nm, c
 // k_gain over the packed device images, for frames without a host copy: the window means and their ratios on the
 // device, one lane per inlier; the ratios come back through pinned memory and are added here IN INLIER ORDER in float,
 // as the host loop adds them (a tree sum on the device would round differently)
-static int gain_device(svh_matcher* m, const svh_p_match* matches, int32_t nm, const int32_t* inliers, int32_t n,
-                       float* result) {
-    *result = 1;
-    HIP_TRY(none, hipSetDevice(m->device));
+// ... in three steps, so that K objects share the middle one (matcher_gain_batch): the inliers' coordinates into
+// pinned memory, the kernel (launched or recorded), the sum
+static int gain_stage(svh_matcher* m, const svh_p_match* matches, int32_t nm, const int32_t* inliers, int32_t n) {
     GROW_N(m->h_gain_in, (size_t)n);
     GROW_N(m->h_gain_out, (size_t)n);
     for (int32_t q = 0; q < n; q++) {
@@ -1400,9 +1426,12 @@ static int gain_device(svh_matcher* m, const svh_p_match* matches, int32_t nm, c
         }
         m->h_gain_in[q] = c;
     }
+    return SVH_OK;
+}
+static void gain_enqueue(svh_matcher* m, int32_t n) {
     mlaunch_gain(m->stream, gain_view(m, m->prev[0]), gain_view(m, m->cur[0]), m->h_gain_in, m->h_gain_out, n);
-    HIP_TRY(none, (hipError_t)wait_stream(m->stream));
-    HIP_TRY(launch, hipGetLastError());
+}
+static float gain_sum(const svh_matcher* m, int32_t nm, const int32_t* inliers, int32_t n) {
     float gain = 0;
     int32_t num = 0;
     for (int32_t q = 0; q < n; q++) {
@@ -1410,7 +1439,18 @@ static int gain_device(svh_matcher* m, const svh_p_match* matches, int32_t nm, c
         gain += m->h_gain_out[q].ratio;
         num++;
     }
-    if (num > 0) *result = gain / (float)num;
+    return num > 0 ? gain / (float)num : 1;
+}
+static int gain_device(svh_matcher* m, const svh_p_match* matches, int32_t nm, const int32_t* inliers, int32_t n,
+                       float* result) {
+    *result = 1;
+    HIP_TRY(none, hipSetDevice(m->device));
+    const int rc = gain_stage(m, matches, nm, inliers, n);
+    if (rc) return rc;
+    gain_enqueue(m, n);
+    HIP_TRY(none, (hipError_t)wait_stream(m->stream));
+    HIP_TRY(launch, hipGetLastError());
+    *result = gain_sum(m, nm, inliers, n);
     return SVH_OK;
 }
 
@@ -1422,6 +1462,49 @@ float svh_matcher_get_gain(svh_matcher* m, const int32_t* inliers, int32_t n) {
     (void)gain_device(m, m->m2.data(), (int32_t)m->m2.size(), inliers, n, &g);   // (a HIP failure: reported, gain 1)
     return g;
 }
+
+}  // extern "C"
+
+// svh_matcher_get_gain of K objects (svh_vo_get_gain_batch): gain[i] is bit for bit svh_matcher_get_gain(ms[i],
+// inliers[i], n[i]).  An object whose two left frames both have host copies keeps the host loop; all others on
+// ms[0]'s device share ONE recorded phase -- one k_gain_b launch, one wait -- and their ratios are added on the host in
+// inlier order, as gain_device adds them.  (An object on another device takes the single path.)  A HIP failure is
+// reported and leaves the gains of the device objects at 1, as in the single entry.
+int32_t svh::matcher_gain_batch(svh_matcher* const* ms, int32_t K, const int32_t* const* inliers, const int32_t* n,
+                                float* gain) {
+    std::vector<int> dev;
+    for (int i = 0; i < K; i++) {
+        svh_matcher* m = ms[i];
+        gain[i] = 1;
+        if (!m->prev[0].valid || !m->cur[0].valid || m->m2.empty() || n[i] == 0) continue;
+        if ((m->prev[0].host_copy && m->cur[0].host_copy) || m->device != ms[0]->device || !m->stream)
+            gain[i] = svh_matcher_get_gain(m, inliers[i], n[i]);
+        else
+            dev.push_back(i);
+    }
+    if (dev.empty()) return SVH_OK;
+    HIP_TRY(none, hipSetDevice(ms[0]->device));
+    for (int i : dev) {
+        const int rc = gain_stage(ms[i], ms[i]->m2.data(), (int32_t)ms[i]->m2.size(), inliers[i], n[i]);
+        if (rc) return rc;
+    }
+    const int rc = run_recorded(
+        batch_recorder(ms[0]->device), ms[dev[0]]->stream, dev.data(), (int)dev.size(), Phase{"Matcher", FI_none},
+        [&](int i) -> int {
+            gain_enqueue(ms[i], n[i]);
+            return SVH_OK;
+        },
+        [&](int i) -> int {
+            HIP_TRY(none, (hipError_t)wait_stream(ms[i]->stream));
+            return SVH_OK;
+        },
+        no_undo);
+    if (rc < 0) return rc;
+    for (int i : dev) gain[i] = gain_sum(ms[i], (int32_t)ms[i]->m2.size(), inliers[i], n[i]);
+    return SVH_OK;
+}
+
+extern "C" {
 
 // ---- test access (declared in hip_guard.h next to svh_test_fail_at, not in the public header)
 // getGain over the object's two left frames for caller-given matches: real matches never come near the image border

@@ -278,12 +278,14 @@ int32_t svh_vo_process_device(svh_vo* v, const uint8_t* dI1, const uint8_t* dI2,
 // (1 motion updated, 0 estimate failed); the call returns <0 on the first error, else the number of successes.
 // Objects that are still bootstrapping (no valid motion yet), or that differ in parameters, make the call run
 // them one after the other.
+// on_device (svh_vo_process_batch_device): I1 / I2 are device pointers; they go through the device entries of the
+// Matcher (lockstep: k_pack_rows recorded with the features; one by one: svh_matcher_push_back_device).
 static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I1, const uint8_t* const* I2,
                              const int32_t* dims, int32_t replace, int32_t* ok, const uint8_t* const* N1,
-                             const uint8_t* const* N2) {
+                             const uint8_t* const* N2, bool on_device = false) {
     svh::ActiveCaller active_;
-    // I1 == I2 == NULL: the objects take the frame handed over by svh_vo_prefetch_batch
-    if (!vs || K < 0 || (!I1 != !I2) || !dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    // I1 == I2 == NULL: the objects take the frame handed over by svh_vo_prefetch_batch (host frames only)
+    if (!vs || K < 0 || (!I1 != !I2) || !dims || (on_device && !I1)) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
     bool lockstep = false;
     const int32_t bad = check_batch(vs, K, "object", &lockstep, [&](int i) {
         return vs[i]->Tr_valid && memcmp(&vs[i]->p, &vs[0]->p, sizeof(vs[0]->p)) == 0;
@@ -299,7 +301,8 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
         // one by one, in the order of K svh_vo_process calls (pushBack draws no random numbers, so taking all
         // K frames first -- which the hand-over of the next frame needs -- keeps the draw order)
         for (int i = 0; i < K; i++) {
-            const int32_t rc = svh_matcher_push_back(ms[i], I1 ? I1[i] : nullptr, I2 ? I2[i] : nullptr, dims, replace);
+            const int32_t rc = (on_device ? svh_matcher_push_back_device : svh_matcher_push_back)(
+                ms[i], I1 ? I1[i] : nullptr, I2 ? I2[i] : nullptr, dims, replace);
             if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored -- viso_stereo.cpp:41-68 goes on; a missing or pending prefetched frame IS an error)
         }
         if (N1) {
@@ -330,7 +333,8 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
     const svh_vo_params& P = vs[0]->p;
     std::vector<const double*> trs(K);
     for (int i = 0; i < K; i++) trs[i] = vs[i]->Tr;
-    int32_t rc = svh_matcher_push_back_batch(ms.data(), K, I1, I2, dims, replace);
+    int32_t rc = (on_device ? svh_matcher_push_back_batch_device : svh_matcher_push_back_batch)(ms.data(), K, I1, I2,
+                                                                                               dims, replace);
     if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored -- viso_stereo.cpp:41-68 goes on; a missing or pending prefetched frame IS an error)
     if (N1) {   // the next frame goes out now: its packing, upload and features overlap everything below
         rc = svh_matcher_prefetch_batch(ms.data(), K, N1, N2, dims);
@@ -400,6 +404,14 @@ static int32_t process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const*
 int32_t svh_vo_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I1, const uint8_t* const* I2,
                              const int32_t* dims, int32_t replace, int32_t* ok) {
     return process_batch(vs, K, I1, I2, dims, replace, ok, nullptr, nullptr);
+}
+
+// The same with every frame in device memory (the contract of svh_matcher_push_back_device per object; the pitch is
+// shared).  The hand-over forms below stay host-only.
+int32_t svh_vo_process_batch_device(svh_vo* const* vs, int32_t K, const uint8_t* const* dI1, const uint8_t* const* dI2,
+                                    const int32_t* dims, int32_t replace, int32_t* ok) {
+    if (!dI1 || !dI2) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    return process_batch(vs, K, dI1, dI2, dims, replace, ok, nullptr, nullptr, true);
 }
 
 // The pipelined form: processes the frame handed over before (svh_vo_prefetch_batch, or the `next` images of the
@@ -472,6 +484,22 @@ int32_t svh_vo_get_inliers(svh_vo* v, int32_t* out, int32_t cap) {
 
 float svh_vo_get_gain(svh_vo* v, const int32_t* inliers, int32_t n) {
     return v ? svh_matcher_get_gain(v->matcher, inliers, n) : 1.f;
+}
+
+// svh_vo_get_gain of K objects (stereo or mono): the objects without host copies of their frames share one k_gain_b
+// launch and one wait (matcher_gain_batch)
+int32_t svh_vo_get_gain_batch(svh_vo* const* vs, int32_t K, const int32_t* const* inliers, const int32_t* n, float* gain) {
+    svh::ActiveCaller active_;
+    if (K < 0 || (K > 0 && (!vs || !inliers || !n || !gain))) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    bool same_device = false;
+    const int32_t bad = check_batch(vs, K, "object", &same_device, [](int) { return true; });
+    if (bad) return bad;
+    for (int i = 0; i < K; i++)
+        if (n[i] < 0 || (n[i] > 0 && !inliers[i])) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    if (K == 0) return SVH_OK;
+    std::vector<svh_matcher*> ms(K);
+    for (int i = 0; i < K; i++) ms[i] = vs[i]->matcher;
+    return matcher_gain_batch(ms.data(), K, inliers, n, gain);
 }
 
 svh_matcher* svh_vo_matcher(svh_vo* v) { return v ? v->matcher : nullptr; }
@@ -614,9 +642,9 @@ static int32_t mono_estimate_batch(svh_vo* const* vs, int32_t K, int32_t* ok, co
 }
 
 static int32_t mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I, const int32_t* dims,
-                                  const int32_t* replace, int32_t* ok, const uint8_t* const* NI) {
+                                  const int32_t* replace, int32_t* ok, const uint8_t* const* NI, bool on_device = false) {
     svh::ActiveCaller active_;
-    if (!dims) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
+    if (!dims || (on_device && !I)) return svh::fail(SVH_ERR_BAD_ARG, "null argument");
     bool lockstep = false;
     int32_t rc = mono_batch_args(vs, K, &lockstep);
     if (rc < 0) return rc;
@@ -627,7 +655,8 @@ static int32_t mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* c
         // one by one, in the order of K svh_vo_mono_process calls (pushBack draws no random numbers, so taking all K
         // frames first -- which the hand-over of the next frame needs -- keeps the draw order)
         for (int i = 0; i < K; i++) {
-            rc = svh_matcher_push_back(ms[i], I ? I[i] : nullptr, nullptr, dims, replace ? replace[i] : 0);
+            rc = (on_device ? svh_matcher_push_back_device : svh_matcher_push_back)(ms[i], I ? I[i] : nullptr, nullptr, dims,
+                                                                                    replace ? replace[i] : 0);
             if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored)
         }
         if (NI) {
@@ -659,7 +688,8 @@ static int32_t mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* c
                 if (I) img.push_back(I[i]);
             }
         if (sub.empty()) continue;
-        rc = svh_matcher_push_back_batch(sub.data(), (int32_t)sub.size(), I ? img.data() : nullptr, nullptr, dims, r);
+        rc = (on_device ? svh_matcher_push_back_batch_device : svh_matcher_push_back_batch)(
+            sub.data(), (int32_t)sub.size(), I ? img.data() : nullptr, nullptr, dims, r);
         if (rc < 0 && rc != SVH_ERR_BAD_DIMS) return rc;   // (bad dimensions: message printed, frame ignored)
     }
     if (NI) {   // the next frame goes out now: its packing, upload and features overlap everything below
@@ -678,6 +708,13 @@ static int32_t mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* c
 int32_t svh_vo_mono_process_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* I, const int32_t* dims,
                                   const int32_t* replace, int32_t* ok) {
     return mono_process_batch(vs, K, I, dims, replace, ok, nullptr);
+}
+
+// The same with every frame in device memory (svh_vo_mono_process_device per object; the pitch is shared).  The
+// hand-over forms below stay host-only.
+int32_t svh_vo_mono_process_batch_device(svh_vo* const* vs, int32_t K, const uint8_t* const* dI, const int32_t* dims,
+                                         const int32_t* replace, int32_t* ok) {
+    return mono_process_batch(vs, K, dI, dims, replace, ok, nullptr, true);
 }
 
 int32_t svh_vo_mono_process_next_batch(svh_vo* const* vs, int32_t K, const uint8_t* const* next_I, const int32_t* dims,

@@ -65,6 +65,9 @@ struct RandStream {
 
 // bucketFeatures drawing from `rs` (matcher_engine.cpp)
 int32_t bucket_features(svh_matcher* m, int32_t max_features, float bw, float bh, RandStream& rs);
+// svh_matcher_get_gain of K distinct, non-null Matchers, the device ones in one recorded phase (matcher_engine.cpp)
+int32_t matcher_gain_batch(svh_matcher* const* ms, int32_t K, const int32_t* const* inliers, const int32_t* n,
+                           float* gain);
 
 void vlaunch_estimate(void* stream, const svh_p_match* pm, int N, const int32_t* samples, int iters,
                       const VoCalib& c, double* hyp_tr, int32_t* hyp_count, uint8_t* hyp_flags, double* Jg,

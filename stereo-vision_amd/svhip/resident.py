@@ -1,7 +1,8 @@
 """ctypes binding of the device-frame entries of libsvhip.so: the Matcher, the visual odometry (stereo and mono) and the
 map fusion fed with frames that are already in device memory (include/svh.h svh_matcher_push_back_device,
-svh_vo_process_device, svh_vo_mono_process_device; include/svh_map.h svh_map_add_device), and the three test-access
-functions of that path (csrc/hip_guard.h).
+svh_vo_process_device, svh_vo_mono_process_device; include/svh_map.h svh_map_add_device), their lockstep forms for K
+objects (svh_matcher_push_back_batch_device, svh_vo_process_batch_device, svh_vo_mono_process_batch_device,
+svh_vo_get_gain_batch, svh_map_add_batch_device), and the test-access functions of that path (csrc/hip_guard.h).
 
 The functions work on the handles the existing wrappers hold: pass the wrapper (anything with a `.h` or `._h` handle:
 svhip.VoMono, svhip.mapper.Mapper, the test drivers over svh_matcher_* / svh_vo_*) or the raw handle.  Device pointers
@@ -17,6 +18,10 @@ GAIN_HOST, GAIN_DEVICE = 0, 1                           # svh_test_matcher_gain:
 
 SYMBOLS = ("svh_matcher_push_back_device", "svh_vo_process_device", "svh_vo_mono_process_device", "svh_map_add_device",
            "svh_test_pack_rows", "svh_test_matcher_image", "svh_test_matcher_gain")
+# the lockstep forms over device frames, and the tap that shows a call ran in lockstep
+LOCKSTEP_SYMBOLS = ("svh_matcher_push_back_batch_device", "svh_vo_process_batch_device",
+                    "svh_vo_mono_process_batch_device", "svh_vo_get_gain_batch", "svh_map_add_batch_device",
+                    "svh_test_lockstep_counts")
 
 
 def _bind():
@@ -34,6 +39,13 @@ def _bind():
         L.svh_test_matcher_gain.argtypes = [P, P, I, P, I, I]
         L.svh_matcher_get_gain.restype = C.c_float
         L.svh_matcher_get_gain.argtypes = [P, P, I]
+        L.svh_matcher_push_back_batch_device.argtypes = [P, I, P, P, P, I]
+        L.svh_vo_process_batch_device.argtypes = [P, I, P, P, P, I, P]
+        L.svh_vo_mono_process_batch_device.argtypes = [P, I, P, P, P, P]
+        L.svh_vo_get_gain_batch.argtypes = [P, I, P, P, P]
+        L.svh_map_add_batch_device.argtypes = [P, I, P, P, P, P, P]
+        L.svh_test_lockstep_counts.restype = None
+        L.svh_test_lockstep_counts.argtypes = [P]
         L._resident_bound = True
     return L
 
@@ -88,6 +100,66 @@ def matcher_gain(matcher, inliers):
     """svh_matcher_get_gain on a raw Matcher handle"""
     a = np.ascontiguousarray(inliers, np.int32)
     return float(_bind().svh_matcher_get_gain(_handle(matcher), a.ctypes.data, len(a)))
+
+
+# ---- K objects in lockstep
+def _table(items):
+    """K pointers (handles or device addresses; None stays NULL) as a C array"""
+    return (C.c_void_p * len(items))(*[None if x is None else _handle(x) for x in items])
+
+
+def matcher_push_back_batch(matchers, dI1, dI2, w, h, pitch=None, replace=False, check=True):
+    """svh_matcher_push_back_batch_device: dI1 / dI2 are K device addresses each (dI2 may be None)"""
+    rc = _bind().svh_matcher_push_back_batch_device(_table(matchers), len(matchers), _table(dI1),
+                                                    None if dI2 is None else _table(dI2), _dims(w, h, pitch),
+                                                    int(replace))
+    return _check(rc) if check else rc
+
+
+def vo_process_batch(vos, dI1, dI2, w, h, pitch=None, replace=False):
+    """svh_vo_process_batch_device: the per-object return values (1 motion updated, 0 estimate failed)"""
+    ok = (C.c_int32 * len(vos))()
+    _check(_bind().svh_vo_process_batch_device(_table(vos), len(vos), _table(dI1), _table(dI2), _dims(w, h, pitch),
+                                               int(replace), ok))
+    return list(ok)
+
+
+def vo_mono_process_batch(vos, dI, w, h, pitch=None, replace=None):
+    """svh_vo_mono_process_batch_device; replace: None or K flags"""
+    ok = (C.c_int32 * len(vos))()
+    rep = None if replace is None else (C.c_int32 * len(vos))(*[int(r) for r in replace])
+    _check(_bind().svh_vo_mono_process_batch_device(_table(vos), len(vos), _table(dI), _dims(w, h, pitch), rep, ok))
+    return list(ok)
+
+
+def vo_gain_batch(vos, inliers):
+    """svh_vo_get_gain_batch: inliers = K index lists; K float32 gains"""
+    arrs = [np.ascontiguousarray(a, np.int32) for a in inliers]
+    n = (C.c_int32 * len(vos))(*[len(a) for a in arrs])
+    gain = np.zeros(len(vos), np.float32)
+    _check(_bind().svh_vo_get_gain_batch(_table(vos), len(vos), _table([a.ctypes.data if len(a) else None for a in arrs]),
+                                         n, gain.ctypes.data))
+    return gain
+
+
+def map_add_batch(mappers, dD1, dI1, w, h, H_total, gain=None, pitch=None, check=True):
+    """svh_map_add_batch_device: K device disparity maps and images, K poses, K gains (None: no gain correction)"""
+    Hs = [np.ascontiguousarray(H, np.float64) for H in H_total]
+    g = np.zeros(len(mappers), np.float32) if gain is None else np.ascontiguousarray(gain, np.float32)
+    rc = _bind().svh_map_add_batch_device(_table(mappers), len(mappers), _table(dD1), _table(dI1), _dims(w, h, pitch),
+                                          _table([H.ctypes.data for H in Hs]), g.ctypes.data)
+    if rc >= 0:
+        for m in mappers:
+            if hasattr(m, "_shape"):
+                m._shape = (h, w)
+    return _check(rc) if check else rc
+
+
+def lockstep_counts():
+    """svh_test_lockstep_counts: (phases flushed as batched launches, phases run one by one, batched launches)"""
+    out = (C.c_int64 * 3)()
+    _bind().svh_test_lockstep_counts(out)
+    return tuple(out)
 
 
 # ---- test access (t_*: over svh_test_*)

@@ -12,7 +12,7 @@ them (readfromfilesthread.cpp:25-112, visualodometrythread.cpp:95-140, stereothr
 without the GUI.  Usage:
 
     python tools/stereomapper_pipeline.py [--unrectified] [--resident] [--render DIR] [--panes DIR [--pane-size WxH]]
-                                          <drive_dir> <calib_cam_to_cam.txt> [max_frames]
+                                          [--lockstep K] <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
 DIR/frame_%06d.ppm, and at the end View3D::recordHuman's fly-through into DIR/img_320_480_%06d.ppm.  Without the flag
@@ -32,6 +32,12 @@ back feeds svh_vo_process, which takes host images.
 --resident: the frame never returns to the host.  A rectified drive's pair is uploaded once, a raw pair is rectified in
 place (--unrectified), and the visual odometry (svh_vo_process_device), ELAS and the map fusion (svh_map_add_device) all
 read that one device copy: no download, no second or third upload.  Results are the same bit for bit.
+
+--lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
+pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
+svh_vo_get_gain_batch, svh_elas_process_batch_device and svh_map_add_batch_device run once for all K, then one view per
+drive.  Always resident.  The K drives are the given drive, drive i starting i frames in; per drive the results are
+those of `--resident` on that drive alone.  --render / --panes do not apply.
 
 Python is glue here (ctypes over libsvhip.so); the pose accumulation H_total = H_total * inv(H_delta)
 uses numpy where the reference uses Matrix::solve."""
@@ -180,7 +186,119 @@ class Pipeline:
         return left.render(), right.render(), disp.render()
 
 
+class LockstepPipeline:
+    """Pipeline(resident=True) for K drives in lockstep: push() takes one pair per drive.  Drive i's objects are vos[i],
+    maps[i], views[i], H_total[i], poses[i]; per drive every result equals that of a resident Pipeline of its own."""
+
+    def __init__(self, K, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None, view_size=(320, 480),
+                 private_rand=None):
+        import helpers as Hh
+        import svhip as S
+        from svhip import mapper, view
+        self.S, self.K = S, K
+        self.vos = [Hh.ProductVo(Hh.vo_defaults(f=f, cu=cu, cv=cv, base=base), private_rand=private_rand)
+                    for _ in range(K)]
+        self.elas = S.Elas(elas_params if elas_params is not None else Hh.robotics())
+        self.maps = [mapper.Mapper(f, cu, cv, base, max_dist) for _ in range(K)]
+        self.views = [view.View(*view_size) for _ in range(K)]
+        self.H_total = [np.eye(4) for _ in range(K)]
+        self.poses = [[] for _ in range(K)]
+        self.buf = None
+        self.rect = None
+        if rectify_params is not None:
+            from svhip import rectify
+            self.rect = rectify.Rectifier(rectify_params)
+            self.raw = None
+
+    def push(self, pairs):
+        """one stereo frame per drive: pairs = K (I1, I2); returns K (vo_ok, points_prev, points_curr)"""
+        from svhip import resident
+        K = self.K
+        assert len(pairs) == K
+        if self.rect is not None:
+            sh, sw = pairs[0][0].shape
+            h, w = self.rect.dst_shape
+        else:
+            h, w = pairs[0][0].shape
+        n = w * h
+        if self.buf is None or self.buf[0].nbytes != K * n:
+            self.buf = [DeviceBuffer(K * n), DeviceBuffer(K * n), DeviceBuffer(4 * K * n), DeviceBuffer(4 * K * n)]
+        dI1, dI2, dD1, dD2 = (b.ptr.value for b in self.buf)
+        if self.rect is not None:
+            # the K raw pairs go up once and are rectified in one launch where every later stage reads them
+            if self.raw is None:
+                self.raw = [DeviceBuffer(K * sw * sh), DeviceBuffer(K * sw * sh)]
+            self.raw[0].upload(np.stack([p[0] for p in pairs]))
+            self.raw[1].upload(np.stack([p[1] for p in pairs]))
+            self.rect.pairs_device(K, self.raw[0].ptr.value, self.raw[1].ptr.value, sw, sw * sh, dI1, dI2, w, n)
+        else:
+            self.buf[0].upload(np.stack([p[0] for p in pairs]))
+            self.buf[1].upload(np.stack([p[1] for p in pairs]))
+        a1 = [dI1 + i * n for i in range(K)]
+        a2 = [dI2 + i * n for i in range(K)]
+        # visualodometrythread.cpp:100-137 for the K drives
+        oks = [o == 1 for o in resident.vo_process_batch(self.vos, a1, a2, w, h, w)]
+        inl = [self.vos[i].inliers() if oks[i] else np.zeros(0, np.int32) for i in range(K)]
+        gains = resident.vo_gain_batch(self.vos, inl)
+        gain = [float(gains[i]) if oks[i] else 0.0 for i in range(K)]
+        for i in range(K):
+            if oks[i]:
+                try:
+                    self.H_total[i] = self.H_total[i] @ np.linalg.inv(self.vos[i].motion())
+                except np.linalg.LinAlgError:
+                    pass
+            self.poses[i].append(self.H_total[i].copy())
+        # stereothread.cpp:62-115: ELAS over the K pairs, the disparity maps left on the device
+        st = self.elas.process_batch_device(K, dI1, dI2, n, dD1, dD2, 4 * n, w, h, w)
+        live = [i for i in range(K) if st[i] == 0]
+        # stereothread.cpp:166-170 for the drives that have a disparity map
+        if live:
+            resident.map_add_batch([self.maps[i] for i in live], [dD1 + 4 * i * n for i in live], [a1[i] for i in live],
+                                   w, h, [self.H_total[i] for i in live], [gain[i] for i in live], pitch=w)
+        out = []
+        for i in range(K):
+            if st[i] != 0:
+                out.append((oks[i], 0, 0))
+                continue
+            self.views[i].add_camera(self.H_total[i], 0.1, True)
+            self.views[i].add_map(self.maps[i])
+            m = self.maps[i]
+            out.append((oks[i], m._L.svh_map_points(m._h, 0, None, 0), m._L.svh_map_points(m._h, 1, None, 0)))
+        return out
+
+
+def main_lockstep(K, drive_dir, calib, limit, rp):
+    import collections
+    from svhip import kitti
+    p = LockstepPipeline(K, calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp)
+    window = collections.deque(maxlen=K)
+    t0 = time.perf_counter()
+    steps = 0
+    for I1, I2, _ in kitti.Sequence(drive_dir):
+        window.append((I1, I2))
+        if len(window) < K:
+            continue
+        res = p.push(list(window))   # drive i is i frames ahead of drive 0
+        steps += 1
+        print("step %4d  " % (steps - 1) + "  ".join("[%d] vo=%d z=%.2f kept=%d new=%d" % (
+            i, ok, p.H_total[i][2, 3], n0, n1) for i, (ok, n0, n1) in enumerate(res)))
+        if steps >= limit:
+            break
+    dt = time.perf_counter() - t0
+    print("%d steps of %d drives in %.2f s = %.1f frames/s (PNG decode included)" % (
+        steps, K, dt, steps * K / max(dt, 1e-9)))
+
+
 def main():
+    lockstep = 0
+    if "--lockstep" in sys.argv:
+        k = sys.argv.index("--lockstep")
+        try:
+            lockstep = int(sys.argv[k + 1])
+            assert lockstep >= 1
+        except (IndexError, ValueError, AssertionError):
+            raise SystemExit(__doc__)
+        del sys.argv[k:k + 2]
     unrectified = "--unrectified" in sys.argv
     if unrectified:
         sys.argv.remove("--unrectified")
@@ -220,6 +338,8 @@ def main():
     if unrectified:
         from svhip import rectify
         rp = rectify.params_from_kitti(calib, 0, 1)
+    if lockstep:
+        return main_lockstep(lockstep, sys.argv[1], calib, limit, rp)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident)
     t0 = time.perf_counter()
     frames = 0
