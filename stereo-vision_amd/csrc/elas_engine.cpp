@@ -236,7 +236,7 @@ struct Lane : LaneBufs {
         LANE_GROW(raster, G2 * ntri_max * sizeof(TriRaster));
         LANE_GROW(planes, G2 * ntri_max * 6 * sizeof(float));
         const size_t gw_bytes = G2 * d.gw * d.gh * d.gwords * sizeof(uint32_t);
-        LANE_GROW(seed, gw_bytes);
+        LANE_GROW(seed, gw_bytes + G2 * sizeof(uint32_t));   // + the slots' flag words (seed_words_with_flags)
         LANE_GROW(mask, gw_bytes);
         if (d.gwords <= 8) LANE_GROW(lists, G2 * d.gw * d.gh * 32 * sizeof(uint16_t));
         hp.resize(g);
@@ -904,7 +904,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             launch_stage_device(cx, p, d, g, L.stg, reinterpret_cast<GroupHdr*>(L.prior_dev.p),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_sup),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_tri),
-                                blits ? nullptr : L.seed.p, (size_t)2 * g * d.gw * d.gh * d.gwords,
+                                blits ? nullptr : L.seed.p, seed_words_with_flags(d, g),
                                 blits ? nullptr : L.h_counts.p);
             if (!L.stage_ev) HIP_TRY(none, hipEventCreateWithFlags(&L.stage_ev, hipEventDisableTiming));
             if (blits) HIP_TRY(copy, hipMemcpyAsync(L.h_counts, L.stg.counts, sizeof(StageCounts), hipMemcpyDeviceToHost, s));

@@ -829,7 +829,7 @@ __global__ __launch_bounds__(kST) void k_support_lds(const uint8_t* __restrict__
 // solver is svh::prior::solve3 (prior_core.h): the generic form's operations
 // with the pivot positions resolved into selects.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_prior(GroupDev G, int total_tri_arg) {
+__global__ __launch_bounds__(256) void k_prior(GroupDev G, int total_tri_arg, uint32_t* __restrict__ oflag) {
     // two lanes per triangle: lane rs = 0 fits the plane in left-image coordinates (t1a..c),
     // rs = 1 in right-image coordinates (t2a..c); the even lane then builds the raster record.
     // total_tri_arg < 0: the header was built on the device and holds the count; the grid is a
@@ -919,7 +919,33 @@ __global__ __launch_bounds__(256) void k_prior(GroupDev G, int total_tri_arg) {
     r.valid = ((double)fabsf(pa) < 0.7 && (double)fabsf(pd) < 0.7) ? 1 : 0;
     r.slot = slot;      // k_owner takes these from the record instead of scanning tri_end[]
     r.first = first;
-    r.pad_[0] = 0;
+    // Orientation of the sorted corners and the per-triangle part of the corner fix pass's safety net: see
+    // k_owner_corner (conditions V and B).  Exact integers; the lines are evaluated exactly as k_owner does.
+    {
+        const long long cr = (long long)(r.uB - r.uA) * (long long)((int)Cv - (int)Av) -
+                             (long long)((int)Bv - (int)Av) * (long long)(r.uC - r.uA);
+        const int sgn = cr > 0 ? 1 : cr < 0 ? -1 : 0;
+        r.pad_[0] = sgn;
+        bool bad = false;
+        if (r.uA < r.uC) {
+            const int iAv = (int)Av, iBv = (int)Bv;
+            const int kAC = f2u2i(__fadd_rn(__fmul_rn(r.ACa, Au), r.ACb));
+            bad = kAC != iAv && kAC != iAv - 1;                                       // V: line AC at corner A
+            if (r.uA < r.uB) {
+                const int kAB = f2u2i(__fadd_rn(__fmul_rn(r.ABa, Au), r.ABb));
+                bad = bad || (kAB != iAv && kAB != iAv - 1);                          // V: line AB at corner A
+            }
+            if (r.uB < r.uC) {
+                const int kBC = f2u2i(__fadd_rn(__fmul_rn(r.BCa, Bu), r.BCb));
+                bad = bad || (kBC != iBv && kBC != iBv - 1);                          // V: line BC at corner B
+                if (r.uA < r.uB) {
+                    const int kACb = f2u2i(__fadd_rn(__fmul_rn(r.ACa, Bu), r.ACb));
+                    bad = bad || (sgn > 0 ? kACb < iBv : sgn < 0 ? kACb >= iBv : true);   // B: line AC against corner B
+                }
+            }
+        }
+        if (bad) oflag[slot] = 1u;
+    }
     G.raster[T] = r;
     }
 }
@@ -1015,8 +1041,13 @@ __global__ __launch_bounds__(256) void k_grid_list(GroupDev G, int ncells, int g
 // coverer lands); kFix = true: every triangle re-reads its pixels and raises the
 // ones a lower index won with atomicMax.  Per-pixel atomics are thereby limited
 // to the handful of contested pixels (4-53 per image in the survey's probes).
+// The product's fix pass is k_owner_corner below; kFix = true is kept as the exhaustive form (fix_all, the
+// default for `wide` geometries) and as the span-end walk (SVH_OWNER_FIX_ALL=2, for A/B runs and as a second oracle).
+// kFix = false also carries condition M of the corner form's safety net (`oflag`, one word per slot; fix_all != 0
+// there means SVH_OWNER_FORCE_WALK: set the flag regardless).
 template <bool kFix>
-__global__ __launch_bounds__(256) void k_owner(GroupDev G, int total_tri_arg, int W, int H, int sub, int fix_all) {
+__global__ __launch_bounds__(256) void k_owner(GroupDev G, int total_tri_arg, int W, int H, int sub, int fix_all,
+                                               uint32_t* __restrict__ oflag) {
     const int total_tri = total_tri_arg >= 0 ? total_tri_arg : G.hdr->total_tri;   // see k_prior
     const int lane = threadIdx.x & 63;
     // XCD-aware order (launched with a multiple of 8 workgroups): XCD k takes the k-th eighth of the triangles THERE
@@ -1035,6 +1066,8 @@ __global__ __launch_bounds__(256) void k_owner(GroupDev G, int total_tri_arg, in
     const int t = G.owner_base + 1 + (T - first);
     int32_t* owner = G.owner + (size_t)slot * W * H;
     const int cl = lane & 15, rp = lane >> 4;
+    // plain pass: fix_all != 0 (SVH_OWNER_FORCE_WALK) sets the slot's flag whatever the mesh
+    bool inverted = !kFix && fix_all != 0;
     {
         // The reference's two loops, [uA, uB) against edge AB and [uB, uC) against edge BC, as one walk: a lane takes
         // the edge of the part its column lies in (uA == uB: no column lies below uB, uB == uC: none from uB on --
@@ -1052,6 +1085,9 @@ __global__ __launch_bounds__(256) void k_owner(GroupDev G, int total_tri_arg, in
             int va = v1 < v2 ? v1 : v2, vb = v1 < v2 ? v2 : v1;
             va = va > 0 ? va : 0;
             vb = vb < H ? vb : H;
+            // condition M of k_owner_corner: the order of the two truncated lines contradicts the triangle's
+            // orientation (not in column uA, where both lines leave the corner and either order is right)
+            if (!kFix) inverted = inverted || (u != tr.uA && (v1 < v2 ? tr.pad_[0] >= 0 : (v1 > v2 && tr.pad_[0] <= 0)));
             if (kFix && !fix_all) {
                 // Only the ends of a column span can be contested.  The triangles partition the
                 // plane, so on the line x = u their exact spans [a, b] touch at most in a point; a
@@ -1081,6 +1117,85 @@ __global__ __launch_bounds__(256) void k_owner(GroupDev G, int total_tri_arg, in
             }
         }
     }
+    if (!kFix && inverted) oflag[slot] = 1u;   // (every writer stores the same value)
+    }
+}
+
+// The corner form of the fix pass (launched as "k_owner_fix").  Eight lanes per triangle -- two columns x four row
+// slots, 32 triangles per workgroup -- re-check the span-end rows va, va+1, vb-2, vb-1 of the columns uA and uB only,
+// with the walk's own line evaluations, conditions and read-then-atomicMax (the stale-read argument of k_owner holds
+// unchanged): the pixels looked at are a subset of the span-end walk's, same rows, fewer columns.
+//
+// Claim: in a slot whose flag word is clear, the highest-index coverer X of a multiply covered pixel (u, v) has
+// u == uA or u == uB, and v is the first or last row of X's span there.  All corners are integers, so a corner lies
+// exactly on its column.  Write k(e) for the truncated, unclamped value of edge line e at column u.  An edge that
+// crosses the column with an end point on either side is evaluated from a bit-identical line (a, b) by the two
+// triangles that share it (both start from its left end point), so both get the same k(e).  The flag collects three
+// conditions, and a clear flag means none holds for any triangle of the slot:
+//   M (k_owner<false>, every column it walks but uA): k(AC) and k(AB or BC) stand in the order that contradicts the
+//     orientation sign of the sorted corners (exact integer cross product, TriRaster::pad_) and differ;
+//   V (k_prior): a line through a corner P, evaluated at P's own column, is not Pv - 1 or Pv after truncation
+//     (AC and AB at uA, BC at uB -- also when uA == uB, where column uA is bounded by BC);
+//   B (k_prior, uA < uB < uC): k(AC) at column uB lies on the wrong side of the integer Bv for the orientation (B
+//     above AC: k(AC) < Bv; B below AC: k(AC) >= Bv; collinear corners: always).
+// Take the triangles the walk visits at column u in their exact order along the line x = u.  A triangle without a
+// corner on the column is bounded there by two crossing edges and is tested by M, so its span is [k(lower edge),
+// k(upper edge)) in the exact order.  Walking away from such a triangle X, each next triangle starts at the k() X or
+// its predecessor ended with and, by M, ends no lower: spans are disjoint as long as no corner is met.  The first
+// corner P met (towards larger v, say) is corner B of the last triangle N in front of it, because N's other bound is
+// a crossing edge: B gives k(AC of N) <= Pv - 1, so everything up to N ends at or before row Pv - 1, exclusive.  Every
+// triangle that has P as a corner starts, by V, at Pv - 1 or Pv on its P side; a triangle with P as corner A lies
+// between two lines through P, i.e. within row Pv - 1; the triangle behind P that has P as B reaches, by B, to
+// k(its AC) >= Pv, from where M carries on to the next corner.  So every span behind P starts at Pv - 1 or later: X is
+// disjoint from all of them, and the same holds mirrored towards smaller v (everything behind P ends at Pv,
+// exclusive, and N gives k(AC) >= Pv).  Hence a passer-by -- a triangle for which u is no corner column -- cannot
+// be a coverer of a multiply covered pixel at all, in particular not the top one, unless some triangle with a corner
+// of that column as B trips B or M at its uB: the tests at uB catch exactly the case of a passer-by edge that
+// evaluates across a vertex.  For X with a corner P on the column the same chain shows that X meets other spans only
+// in the one row at P: V puts X's end at P at Pv - 1 or Pv and every other span's end there too, while X's other
+// end, if it is a crossing edge, is protected by M and B as above.  That row is va or vb - 1; va + 1 and vb - 2 are
+// the margin the span-end walk has.  Column uC is never written: the walk is half open.
+// Where the flag is set the lane group walks all columns [ulo, uhi) of its triangle, two per step, with the same
+// four rows: the span-end walk itself, slow but exactly what SVH_OWNER_FIX_ALL=2 runs.
+// The flag has never been seen set: not on the goldens' triangulations (both sides), not on random lattice
+// triangulations, not on adversarial ones (collinear fans, strips, vertices almost on a long edge, widths up to
+// 9000) -- tests/test_owner_corner_zone.py restates the conditions in numpy and checks the claim on all of them.
+// Geometries beyond the `wide` bound of launch_owner take the exhaustive pass as before.
+__global__ __launch_bounds__(256) void k_owner_corner(GroupDev G, int total_tri_arg, int W, int H, int sub,
+                                                      const uint32_t* __restrict__ oflag) {
+    const int total_tri = total_tri_arg >= 0 ? total_tri_arg : G.hdr->total_tri;   // see k_prior
+    // XCD-aware order as in k_owner, 32 triangles per workgroup
+    const int need = (((total_tri + 31) >> 5) + 7) >> 3, have = (int)(gridDim.x >> 3);
+    const int per_xcd = need < have ? need : have;
+    if ((int)(blockIdx.x >> 3) >= per_xcd) return;
+    const int bid = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    const int col = (threadIdx.x >> 2) & 1, rp = threadIdx.x & 3;
+    for (int T = bid * 32 + (int)(threadIdx.x >> 3); T < total_tri; T += per_xcd * 256) {
+        const TriRaster tr = G.raster[T];
+        const int t = G.owner_base + 1 + (T - tr.first);
+        int32_t* owner = G.owner + (size_t)tr.slot * W * H;
+        const int ulo = tr.uA > 2 ? tr.uA : 2, uhi = tr.uC < W - 2 ? tr.uC : W - 2;
+        const bool walk = oflag[tr.slot] != 0;
+        // corner form: lane half 0 takes column uA, half 1 column uB (not a second time when the two are equal)
+        int u = walk ? ulo + col : col ? tr.uB : tr.uA;
+        const int uend = walk ? uhi : (col && tr.uB == tr.uA) || u < ulo ? u : (u + 1 < uhi ? u + 1 : uhi);
+        for (; u < uend; u += 2) {
+            if (sub && (u & 1)) continue;
+            const bool second = u >= tr.uB;
+            const float ea = second ? tr.BCa : tr.ABa, eb = second ? tr.BCb : tr.ABb;
+            const float fu = (float)u;
+            const int v1 = f2u2i(__fadd_rn(__fmul_rn(tr.ACa, fu), tr.ACb));
+            const int v2 = f2u2i(__fadd_rn(__fmul_rn(ea, fu), eb));
+            int va = v1 < v2 ? v1 : v2, vb = v1 < v2 ? v2 : v1;
+            va = va > 0 ? va : 0;
+            vb = vb < H ? vb : H;
+            const int v = rp < 2 ? va + rp : vb - 4 + rp;
+            const bool mine = v >= va && v < vb && (rp < 2 || v >= va + 2);
+            if (mine && !(sub && (v & 1))) {
+                int32_t* px = &owner[(size_t)v * W + u];
+                if (*px < t) atomicMax(px, t);   // (a stale read can only cause a redundant atomicMax: see k_owner)
+            }
+        }
     }
 }
 
@@ -2879,11 +2994,12 @@ void launch_prior(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, 
                   int32_t total_sup, int32_t total_tri, const GroupDev& G, const PhaseBSize& size) {
     hipStream_t s = (hipStream_t)cx.stream;
     const int cells = d.gw * d.gh;
-    const size_t words = (size_t)2 * g * cells * d.gwords;
-    // (device stage: k_stage_pack, the last kernel in front of this one on the stream, has cleared the words)
-    if (!size.seed_cleared) (void)hipMemsetAsync(G.seed, 0, words * sizeof(uint32_t), s);
+    const size_t words = seed_words(d, g);
+    // (device stage: k_stage_pack, the last kernel in front of this one on the stream, has cleared the words);
+    // the slots' ownership flags behind the bit sets are cleared with them
+    if (!size.seed_cleared) (void)hipMemsetAsync(G.seed, 0, seed_words_with_flags(d, g) * sizeof(uint32_t), s);
     const int nt = size.nt, ns = size.ns;
-    if (nt > 0) LAUNCH("k_prior", k_prior, dim3((2 * nt + 255) / 256), dim3(256), G, total_tri);
+    if (nt > 0) LAUNCH("k_prior", k_prior, dim3((2 * nt + 255) / 256), dim3(256), G, total_tri, G.seed + words);
     if (ns > 0)
         LAUNCH("k_grid_seed", k_grid_seed, dim3((ns + 255) / 256), dim3(256), G, total_sup,
                d.gw, d.gh, d.gwords, p.grid_size, p.disp_max);
@@ -2904,12 +3020,21 @@ void launch_owner(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, 
     // climbs the whole image within one column; beyond 2^22 one ulp of that product is half a row and the
     // margin is gone, so such geometries (not 1920x1080 at disp_max 255: 2.6e6) take the exhaustive pass.
     const bool wide = (double)d.H * ((double)d.W + 2.0 * p.disp_max) > 4194304.0;
-    const int fix_all = svh::env("SVH_OWNER_FIX_ALL") ? atoi(svh::env("SVH_OWNER_FIX_ALL")) : (wide ? 1 : 0);   // read per launch: tests toggle it
+    // SVH_OWNER_FIX_ALL, read per launch (tests toggle it): 0 the corner form (k_owner_corner), 1 the exhaustive
+    // form, 2 the span-end walk (for A/B runs and as a second oracle).  SVH_OWNER_FORCE_WALK=1: the plain pass sets
+    // every slot's flag, which sends the corner form down its fallback path.
+    const int fix_all = svh::env("SVH_OWNER_FIX_ALL") ? atoi(svh::env("SVH_OWNER_FIX_ALL")) : (wide ? 1 : 0);
+    const int force_walk = svh::env("SVH_OWNER_FORCE_WALK") && atoi(svh::env("SVH_OWNER_FORCE_WALK")) != 0 ? 1 : 0;
+    uint32_t* oflag = G.seed + seed_words(d, g);
     const dim3 go(xcd_blocks((nt + 3) / 4));   // (a multiple of 8: see the kernel's block order)
     LAUNCH("k_owner", k_owner<false>, go, dim3(256), G, total_tri, d.W, d.H,
-           p.subsampling, 0);
-    LAUNCH("k_owner_fix", k_owner<true>, go, dim3(256), G, total_tri, d.W, d.H,
-           p.subsampling, fix_all);
+           p.subsampling, force_walk, oflag);
+    if (fix_all == 0)
+        LAUNCH("k_owner_fix", k_owner_corner, dim3(xcd_blocks((nt + 31) / 32)), dim3(256), G, total_tri, d.W, d.H,
+               p.subsampling, oflag);
+    else
+        LAUNCH("k_owner_fix", k_owner<true>, go, dim3(256), G, total_tri, d.W, d.H,
+               p.subsampling, fix_all == 1 ? 1 : 0, oflag);
 }
 
 // Does the dense matcher take its list form (k_match_list) for these parameters?  Used by launch_match and -- before

@@ -55,7 +55,7 @@ struct alignas(16) TriRaster {
     float ABa, ABb;            // first part
     float BCa, BCb;            // second part
     int32_t slot, first;   // (pair, side) slot of the triangle and the index of the slot's first triangle
-    int32_t pad_[1];
+    int32_t pad_[1];       // [0]: sign (-1, 0, 1) of the sorted corners' orientation (B-A) x (C-A), see k_owner_corner
 };
 static_assert(sizeof(TriRaster) == 64, "TriRaster is one 64-byte record");
 
@@ -158,7 +158,7 @@ struct GroupDev {
     const int32_t* P;          // prior table
     TriRaster* raster;         // packed like tri
     float* planes;             // 6 floats per triangle (t1a..t2c), packed like tri
-    uint32_t* seed;            // [g][2][cells][gwords]
+    uint32_t* seed;            // [g][2][cells][gwords], then one flag word per (pair, side) slot: owner_flags()
     uint32_t* mask;            // [g][2][cells][gwords] dilated
     uint16_t* lists;           // [g][2][cells][32] candidate records of k_grid_list (disp_max <= 255), else null
     const uint8_t* desc;       // [g][2][N*16]
@@ -199,6 +199,11 @@ struct PhaseBSize {
     bool from_history;
     bool seed_cleared;   // set by the engine when k_stage_pack of this group zeroed G.seed: launch_prior does not
 };
+// The words behind the grid bit sets of a group of g pairs: one per (pair, side) slot, cleared with the bit sets
+// (k_stage_pack or launch_prior), set by k_prior / k_owner when the corner form of the ownership fix pass cannot be
+// trusted for the slot's mesh (see k_owner_corner).
+inline size_t seed_words(const Dims& d, int32_t g) { return (size_t)2 * g * d.gw * d.gh * d.gwords; }
+inline size_t seed_words_with_flags(const Dims& d, int32_t g) { return seed_words(d, g) + (size_t)2 * g; }
 PhaseBSize phase_b_size(const Dims& d, int32_t g, int32_t total_sup, int32_t total_tri, int32_t hint_sup, int32_t hint_tri);
 // planes + raster records + grid bit sets for the whole group.  total_sup / total_tri < 0: the
 // counts are in the device header (device-built).  G.seed is cleared here unless size.seed_cleared
