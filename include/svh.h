@@ -258,6 +258,49 @@ int32_t svh_elas_stream_pop_n(svh_elas_stream* s, int32_t n, int32_t* status, in
 int32_t svh_elas_stream_push_n(svh_elas_stream* s, int32_t n, const uint8_t* const* I1, const uint8_t* const* I2,
                                float* const* D1, float* const* D2, uint64_t* first_ticket);
 
+/* ---- what a host caller gets back: format and map selection ---------------------------------
+ * The host entries above always return two float maps: 8 bytes per pixel over PCIe, which is what
+ * bounds them.  The _out forms take a svh_elas_output and return less:
+ *   format  SVH_DISP_F32  float, -1 = invalid, as above
+ *           SVH_DISP_U16  uint16, value x 256, 0 = invalid: u16(d) = 0 when !(d >= 0) (negative, NaN),
+ *                         otherwise max(1, (uint32)min(d * 256.0f, 65535.0f)); -0 and 0 give 1, every
+ *                         d >= 255.99609375 (disp_max may exceed 255) saturates at 65535.  The float maps are
+ *                         computed as always and converted on the device before they are copied down.  This is
+ *                         the encoding of KITTI's stereo development kit as documented; unverified against
+ *                         the kit's own code.
+ *   maps    SVH_MAPS_BOTH D1 and D2
+ *           SVH_MAPS_LEFT D1 only: D2 (or, in the plural forms, the array D2) may be NULL and nothing is
+ *                         written to it (the right map is still computed: the left/right check needs it)
+ * D1 / D2 point at float or uint16_t maps according to `format`, tightly packed as above.  out == NULL or
+ * {SVH_DISP_F32, SVH_MAPS_BOTH} is the existing entry; a format or selection that is none of the above, or
+ * a NULL D2 with SVH_MAPS_BOTH, is SVH_ERR_BAD_ARG.  A pair that does not go through (fewer than three
+ * support points) leaves the buffers untouched and returns the same status, in every format.
+ * A stream has ONE output form, fixed by svh_elas_stream_open_out; push_out / push_out_n take its buffers
+ * (the float pushes above on such a stream, and push_out on a stream of svh_elas_stream_open, work as long as the
+ * form is {F32, BOTH}; otherwise SVH_ERR_BAD_ARG).  pop / pop_n / flush / close are the ones above.
+ * The device-resident entries (*_device) have no 16-bit form: their maps never cross PCIe; a device-side
+ * consumer converts with svh_disparity_pack_u16. */
+#define SVH_DISP_F32 0
+#define SVH_DISP_U16 1            /* value*256, 0 = invalid */
+#define SVH_MAPS_BOTH 0
+#define SVH_MAPS_LEFT 1           /* D2 may be NULL, nothing is written to it */
+typedef struct { int32_t format; int32_t maps; } svh_elas_output;
+int32_t svh_elas_process_out(svh_elas* e, const uint8_t* I1, const uint8_t* I2, void* D1, void* D2,
+                             const int32_t* dims, const svh_elas_output* out);
+int32_t svh_elas_process_batch_out(svh_elas* e, int32_t n, const uint8_t* const* I1, const uint8_t* const* I2,
+                                   void* const* D1, void* const* D2, const int32_t* dims, int32_t* status,
+                                   const svh_elas_output* out);
+svh_elas_stream* svh_elas_stream_open_out(svh_elas* e, const int32_t* dims, int32_t depth, const svh_elas_output* out);
+int32_t svh_elas_stream_push_out(svh_elas_stream* s, const uint8_t* I1, const uint8_t* I2, void* D1, void* D2,
+                                 uint64_t* ticket);
+int32_t svh_elas_stream_push_out_n(svh_elas_stream* s, int32_t n, const uint8_t* const* I1, const uint8_t* const* I2,
+                                   void* const* D1, void* const* D2, uint64_t* first_ticket);
+/* The conversion alone (k_disp_pack_u16): n floats at D (host, or device memory when d_on_device) to n uint16 at
+ * out (host, or device memory when out_on_device); any alignment; complete on return.  n == 0 is SVH_OK.  Needs a
+ * device.  svh_disparity_unpack_u16 is its inverse on the host: v ? v / 256.0f : -1.0f. */
+int32_t svh_disparity_pack_u16(const float* D, int32_t d_on_device, int64_t n, uint16_t* out, int32_t out_on_device);
+int32_t svh_disparity_unpack_u16(const uint16_t* v, int64_t n, float* out);
+
 /* Device buffers, pinned staging, streams and events live in a per-device pool of "lanes" that
  * outlives the svh_elas handles (callers build an Elas per frame).  svh_elas_trim() releases
  * every lane that is not in use at the moment -- e.g. after one large batch in a long-lived

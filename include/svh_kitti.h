@@ -56,6 +56,17 @@ int32_t svh_kitti_read_cam_to_cam(const char* path, svh_kitti_calib* out);
  * not a PNG, cap too small) or SVH_ERR_UNSUPPORTED (interlaced, palette, other depths).   */
 int32_t svh_png_read_gray(const char* path, uint8_t* buf, size_t cap, int32_t* width, int32_t* height);
 
+/* KITTI disparity images (the stereo benchmark's disp_* files): 16-bit gray PNG, sample = disparity x 256,
+ * 0 = invalid -- the form SVH_DISP_U16 of svh.h produces (this is the development kit's encoding as documented;
+ * unverified against the kit's own code).
+ *   write  v = width x height samples, rows packed.  Non-interlaced, big-endian samples, one IDAT (zlib compress2).
+ *          Returns 0 or SVH_ERR_BAD_ARG (null / empty / unwritable).
+ *   read   keeps all 16 bits (svh_png_read_gray above reduces them to 8).  dims receives {width, height}; out may
+ *          be NULL to query them; cap = samples available in out.  Returns 0, SVH_ERR_BAD_ARG (unreadable, not a
+ *          PNG, cap too small) or SVH_ERR_UNSUPPORTED (anything but non-interlaced 16-bit gray).              */
+int32_t svh_kitti_write_disp_png(const char* path, const uint16_t* v, int32_t width, int32_t height);
+int32_t svh_kitti_read_disp_png(const char* path, uint16_t* out, size_t cap, int32_t* dims);
+
 /* A drive directory played back frame by frame (StereoImageIOKITTI::setUpDataPath +
  * getNextImageDataSet).                                                                   */
 typedef struct svh_kitti_seq svh_kitti_seq;

@@ -121,6 +121,7 @@ struct LaneBufs {
     HipBuf<float> Draw;            // [gcap][2][DN]
     HipBuf<float> D;               // [gcap][2][DN]  (host-output mode)
     HipBuf<float> tmp;             // [gcap][2][DN]
+    HipBuf<uint16_t> U;            // [gcap][1 or 2][DN rounded up to 8]  16-bit maps (SVH_DISP_U16), allocated by the first such group
     HipBuf<int32_t> labels, counts;
     HipBuf<int32_t> seg_nroots;    // [2 * gcap][tiles] tile-local roots per 64 x 16 tile (k_seg_tile -> k_seg_sum)
     HipBuf<uint8_t> stage_blob;    // one allocation behind the StageDev arrays
@@ -457,8 +458,21 @@ struct GroupIO {
     bool out_device;
     float* dD[2];                    // device: map k of pair j at dD[k] + j*out_stride (floats)
     size_t out_stride;
-    float* const* hD[2];             // host: per-pair pointers
+    float* const* hD[2];             // host: per-pair pointers (uint16_t maps when format is SVH_DISP_U16)
+    // host outputs only (svh_elas_output): what is copied down.  The chain always runs on the lane's float maps
+    int32_t format = SVH_DISP_F32;   // SVH_DISP_U16: k_disp_pack_u16 converts them into the lane's 16-bit buffer first
+    int32_t maps = SVH_MAPS_BOTH;    // SVH_MAPS_LEFT: D2 is computed (the L/R check reads it), not converted, not copied
 };
+
+// svh_test_d2h_map_bytes (hip_guard.h)
+static std::atomic<int64_t> g_d2h_map_bytes{0}, g_d2h_map_copies{0};
+
+// a caller's svh_elas_output (null: the float pair) into a GroupIO; false: not a form there is
+static bool output_form(const svh_elas_output* out, int32_t* format, int32_t* maps) {
+    *format = out ? out->format : SVH_DISP_F32;
+    *maps = out ? out->maps : SVH_MAPS_BOTH;
+    return (*format == SVH_DISP_F32 || *format == SVH_DISP_U16) && (*maps == SVH_MAPS_BOTH || *maps == SVH_MAPS_LEFT);
+}
 
 static int check_params(const svh_elas_params& p, int32_t W, int32_t H) {
     if (W < 16 || H < 16) return fail(SVH_ERR_BAD_ARG, "image smaller than 16x16");
@@ -582,6 +596,12 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     if (rc) return rc;
     if (g > 1) taps = nullptr;
     const Dims& d = L.d;
+    // 16-bit host outputs: every map has a slot of DNu elements in L.U, so that each starts 16-byte aligned (DN is odd
+    // for sizes such as 401x177); the buffer comes with the lane's first such group, a float call never allocates it
+    const bool u16 = !io.out_device && io.format == SVH_DISP_U16;
+    const int nmaps = !io.out_device && io.maps == SVH_MAPS_LEFT ? 1 : 2;
+    const size_t DNu = ((size_t)d.DW * d.DH + 7) & ~(size_t)7;
+    if (u16) LANE_GROW(L.U, (size_t)L.gcap * 2 * DNu * sizeof(uint16_t));
     hipStream_t s = L.stream;
     L.prof.stream = s;
     const LaunchCtx cx = {s, g_prof_on.load() ? &L.prof : nullptr, L.lone_group};
@@ -654,7 +674,8 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         const char* match_err = nullptr;
         const bool lr_done = launch_match(cx, p, d, g, G, &out, tapping, &match_err);
         if (match_err) return fail(SVH_ERR_HIP, std::string("launch_match: ") + match_err);
-        early_d2 = !io.out_device && lr_done && !tapping && p.postprocess_only_left;
+        // (not in 16-bit form: the right map is converted with the left one, after the chain; nor when it stays here)
+        early_d2 = !io.out_device && lr_done && !tapping && p.postprocess_only_left && !u16 && nmaps == 2;
         if (early_d2) {
             if (!L.copy_stream) {
                 HIP_TRY(none, hipStreamCreateWithFlags(&L.copy_stream, hipStreamNonBlocking));
@@ -690,6 +711,15 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             if (p.filter_adaptive_mean) launch_adaptive_mean(cx, p, d, g, nside, G, out, ps);
             if (p.filter_median) launch_median(cx, d, g, nside, G, out, ps);
         }
+        if (u16) {
+            // one launch for the wanted maps of the whole group (pairs that did not go through are converted too:
+            // which ones they are may not be known yet, and their slots are never copied)
+            PackMap pm[2 * kMaxGroup];
+            for (int32_t j = 0; j < g; j++)
+                for (int k = 0; k < nmaps; k++)
+                    pm[j * nmaps + k] = {(int64_t)(((size_t)2 * j + k) * DN), (int64_t)(((size_t)j * nmaps + k) * DNu), (int64_t)DN};
+            launch_disp_pack(cx, L.D, L.U, pm, g * nmaps);
+        }
         return SVH_OK;
     };
 
@@ -698,20 +728,25 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     // one another (one big array, the usual case) go down as ONE strided copy (device maps of a pair are
     // interleaved D1, D2: source pitch 2 DN, destination pitch DN) instead of one copy per pair.
     static const bool strided = !(svh::env("SVH_D2H_STRIDED") && atoi(svh::env("SVH_D2H_STRIDED")) == 0);
+    // (16-bit form: the same from L.U, 2 bytes per pixel, source pitch = the nmaps slots of a pair)
     auto copy_map = [&](int k, hipStream_t cs, const int32_t* active) -> int {
-        const size_t bytes = DN * sizeof(float);
+        const size_t bytes = DN * (u16 ? sizeof(uint16_t) : sizeof(float));
+        const size_t spitch = u16 ? (size_t)nmaps * DNu * sizeof(uint16_t) : 2 * bytes;
         for (int32_t j = 0; j < g;) {
             if (!active[j]) { j++; continue; }
             int32_t e = j + 1;
             while (strided && e < g && active[e] &&
                    reinterpret_cast<const char*>(io.hD[k][e]) == reinterpret_cast<const char*>(io.hD[k][e - 1]) + bytes)
                 e++;
-            const float* src = L.D + ((size_t)2 * j + k) * DN;
+            const void* src = u16 ? (const void*)(L.U + ((size_t)j * nmaps + k) * DNu)
+                                  : (const void*)(L.D + ((size_t)2 * j + k) * DN);
             if (e - j > 1)
-                HIP_TRY(copy, hipMemcpy2DAsync(io.hD[k][j], bytes, src, 2 * bytes, bytes, (size_t)(e - j),
+                HIP_TRY(copy, hipMemcpy2DAsync(io.hD[k][j], bytes, src, spitch, bytes, (size_t)(e - j),
                                          hipMemcpyDeviceToHost, cs));
             else
                 HIP_TRY(copy, hipMemcpyAsync(io.hD[k][j], src, bytes, hipMemcpyDeviceToHost, cs));
+            g_d2h_map_bytes.fetch_add((int64_t)(bytes * (size_t)(e - j)), std::memory_order_relaxed);
+            g_d2h_map_copies.fetch_add(1, std::memory_order_relaxed);
             j = e;
         }
         return SVH_OK;
@@ -724,7 +759,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             if (rc) return rc;
             HIP_TRY(none, hipEventRecord(L.copy_ev, L.copy_stream));
         }
-        for (int k = 0; k < (early_d2 ? 1 : 2); k++) {
+        for (int k = 0; k < (early_d2 ? 1 : nmaps); k++) {
             rc = copy_map(k, s, active);
             if (rc) return rc;
         }
@@ -1102,6 +1137,7 @@ struct svh_elas_stream {
     int device = 0;
     int32_t dims[3] = {0, 0, 0};
     int32_t G = 1, depth = 0;
+    int32_t format = SVH_DISP_F32, maps = SVH_MAPS_BOTH;   // of its host pairs (svh_elas_stream_open_out)
     std::mutex mu;
     std::condition_variable cv_work, cv_done, cv_space, cv_push;
     std::deque<std::shared_ptr<StreamGroup>> order;   // every group with pairs that were not popped yet
@@ -1324,9 +1360,9 @@ static int32_t require_device(int device) {
     return SVH_OK;
 }
 
-int32_t svh_elas_process(svh_elas* e, const uint8_t* I1, const uint8_t* I2, float* D1, float* D2,
-                         const int32_t* dims) {
-    if (!e || !I1 || !I2 || !D1 || !D2 || !dims) return fail(SVH_ERR_BAD_ARG, "null argument");
+// (D1 / D2: float or uint16_t maps according to `format`; D2 may be null with SVH_MAPS_LEFT)
+static int32_t process_impl(svh_elas* e, const uint8_t* I1, const uint8_t* I2, float* D1, float* D2,
+                            const int32_t* dims, int32_t format, int32_t maps) {
     int32_t rc = require_device(e->device);
     if (rc) return rc;
     Lane* L = acquire_lane(e->device);
@@ -1336,11 +1372,26 @@ int32_t svh_elas_process(svh_elas* e, const uint8_t* I1, const uint8_t* I2, floa
     io.hI[0] = &I1; io.hI[1] = &I2; io.pitch = dims[2];
     io.out_device = false;
     io.hD[0] = &D1; io.hD[1] = &D2;
+    io.format = format; io.maps = maps;
     int32_t st = SVH_OK;
     rc = run_group(*L, e->p, dims, io, &st, &e->taps, e);
     release_lane(L);
     if (rc == SVH_ERR_HIP) report_hip_failure("svh_elas_process");
     return rc ? rc : st;
+}
+
+int32_t svh_elas_process(svh_elas* e, const uint8_t* I1, const uint8_t* I2, float* D1, float* D2,
+                         const int32_t* dims) {
+    if (!e || !I1 || !I2 || !D1 || !D2 || !dims) return fail(SVH_ERR_BAD_ARG, "null argument");
+    return process_impl(e, I1, I2, D1, D2, dims, SVH_DISP_F32, SVH_MAPS_BOTH);
+}
+
+int32_t svh_elas_process_out(svh_elas* e, const uint8_t* I1, const uint8_t* I2, void* D1, void* D2,
+                             const int32_t* dims, const svh_elas_output* out) {
+    int32_t format, maps;
+    if (!output_form(out, &format, &maps)) return fail(SVH_ERR_BAD_ARG, "bad output format / map selection");
+    if (!e || !I1 || !I2 || !D1 || (!D2 && maps == SVH_MAPS_BOTH) || !dims) return fail(SVH_ERR_BAD_ARG, "null argument");
+    return process_impl(e, I1, I2, static_cast<float*>(D1), static_cast<float*>(D2), dims, format, maps);
 }
 
 // n pairs -> groups of up to g_group consecutive pairs, spread over the lanes
@@ -1472,10 +1523,9 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
     return first_bad;
 }
 
-int32_t svh_elas_process_batch(svh_elas* e, int32_t n, const uint8_t* const* I1,
-                               const uint8_t* const* I2, float* const* D1, float* const* D2,
-                               const int32_t* dims, int32_t* status) {
-    if (!e || n < 0 || !I1 || !I2 || !D1 || !D2 || !dims) return fail(SVH_ERR_BAD_ARG, "null argument");
+static int32_t batch_host(svh_elas* e, int32_t n, const uint8_t* const* I1, const uint8_t* const* I2,
+                          float* const* D1, float* const* D2, const int32_t* dims, int32_t* status, int32_t format,
+                          int32_t maps) {
     if (n == 0) return SVH_OK;
     return batch_impl(e, n, dims, status, [&](int32_t first, int32_t cnt) {
         GroupIO io{};
@@ -1483,9 +1533,28 @@ int32_t svh_elas_process_batch(svh_elas* e, int32_t n, const uint8_t* const* I1,
         io.in_device = false;
         io.hI[0] = I1 + first; io.hI[1] = I2 + first; io.pitch = dims[2];
         io.out_device = false;
-        io.hD[0] = D1 + first; io.hD[1] = D2 + first;
+        io.hD[0] = D1 + first; io.hD[1] = D2 ? D2 + first : nullptr;
+        io.format = format; io.maps = maps;
         return io;
     });
+}
+
+int32_t svh_elas_process_batch(svh_elas* e, int32_t n, const uint8_t* const* I1,
+                               const uint8_t* const* I2, float* const* D1, float* const* D2,
+                               const int32_t* dims, int32_t* status) {
+    if (!e || n < 0 || !I1 || !I2 || !D1 || !D2 || !dims) return fail(SVH_ERR_BAD_ARG, "null argument");
+    return batch_host(e, n, I1, I2, D1, D2, dims, status, SVH_DISP_F32, SVH_MAPS_BOTH);
+}
+
+int32_t svh_elas_process_batch_out(svh_elas* e, int32_t n, const uint8_t* const* I1, const uint8_t* const* I2,
+                                   void* const* D1, void* const* D2, const int32_t* dims, int32_t* status,
+                                   const svh_elas_output* out) {
+    int32_t format, maps;
+    if (!output_form(out, &format, &maps)) return fail(SVH_ERR_BAD_ARG, "bad output format / map selection");
+    if (!e || n < 0 || !I1 || !I2 || !D1 || (!D2 && maps == SVH_MAPS_BOTH) || !dims)
+        return fail(SVH_ERR_BAD_ARG, "null argument");
+    return batch_host(e, n, I1, I2, reinterpret_cast<float* const*>(D1), reinterpret_cast<float* const*>(D2), dims,
+                      status, format, maps);
 }
 
 int32_t svh_elas_process_batch_device(svh_elas* e, int32_t n, const uint8_t* dI1, const uint8_t* dI2,
@@ -1509,10 +1578,11 @@ int32_t svh_elas_process_batch_device(svh_elas* e, int32_t n, const uint8_t* dI1
 }
 
 // ---- streaming submission ----------------------------------------------------------------
-static GroupIO stream_io(const StreamGroup& g, int32_t pitch) {
+static GroupIO stream_io(const svh_elas_stream* s, const StreamGroup& g) {
     GroupIO io{};
     io.g = g.n;
-    io.pitch = pitch;
+    io.pitch = s->dims[2];
+    io.format = s->format; io.maps = s->maps;
     io.in_device = io.out_device = g.device;
     if (g.device) {
         io.dI[0] = g.dI[0]; io.dI[1] = g.dI[1];
@@ -1563,7 +1633,7 @@ static void stream_worker(svh_elas_stream* s) {
     auto finish = [&](int q) {
         if (!pend[q]) return;
         StreamGroup& g = *pend[q];
-        note(g, run_group(*slot[q], s->p, s->dims, stream_io(g, s->dims[2]), g.status, nullptr, nullptr, RG_FINISH));
+        note(g, run_group(*slot[q], s->p, s->dims, stream_io(s, g), g.status, nullptr, nullptr, RG_FINISH));
         {
             std::lock_guard<std::mutex> lk(s->mu);
             g.done = true;
@@ -1582,16 +1652,16 @@ static void stream_worker(svh_elas_stream* s) {
             (void)L->ensure(s->p, s->dims[0], s->dims[1], s->G);   // (a failure is reported by the group's run_group)
         }
         int k = 0;
-        note(*cur, run_group(*slot[k], s->p, s->dims, stream_io(*cur, s->dims[2]), cur->status, nullptr, nullptr, RG_A, 2));
+        note(*cur, run_group(*slot[k], s->p, s->dims, stream_io(s, *cur), cur->status, nullptr, nullptr, RG_A, 2));
         while (cur) {
             std::shared_ptr<StreamGroup> nxt = take(false);
             if (nxt) {
                 finish(1 - k);
-                note(*nxt, run_group(*slot[1 - k], s->p, s->dims, stream_io(*nxt, s->dims[2]), nxt->status, nullptr,
+                note(*nxt, run_group(*slot[1 - k], s->p, s->dims, stream_io(s, *nxt), nxt->status, nullptr,
                                      nullptr, RG_A, 2));
             }
             if (cur->rc == SVH_OK)
-                note(*cur, run_group(*slot[k], s->p, s->dims, stream_io(*cur, s->dims[2]), cur->status, nullptr, nullptr,
+                note(*cur, run_group(*slot[k], s->p, s->dims, stream_io(s, *cur), cur->status, nullptr, nullptr,
                                      RG_HOST_B));
             pend[k] = cur;
             if (nxt) {
@@ -1613,12 +1683,23 @@ static void stream_worker(svh_elas_stream* s) {
 }
 
 svh_elas_stream* svh_elas_stream_open(svh_elas* e, const int32_t* dims, int32_t depth) {
+    return svh_elas_stream_open_out(e, dims, depth, nullptr);
+}
+
+svh_elas_stream* svh_elas_stream_open_out(svh_elas* e, const int32_t* dims, int32_t depth, const svh_elas_output* out) {
     if (!e || !dims) {
         fail(SVH_ERR_BAD_ARG, "null argument");
         return nullptr;
     }
+    int32_t format, maps;
+    if (!output_form(out, &format, &maps)) {
+        fail(SVH_ERR_BAD_ARG, "bad output format / map selection");
+        return nullptr;
+    }
     if (require_device(e->device) || check_params(e->p, dims[0], dims[1])) return nullptr;
     svh_elas_stream* s = new svh_elas_stream();
+    s->format = format;
+    s->maps = maps;
     s->p = e->p;
     s->device = e->device;
     for (int k = 0; k < 3; k++) s->dims[k] = dims[k];
@@ -1632,9 +1713,14 @@ svh_elas_stream* svh_elas_stream_open(svh_elas* e, const int32_t* dims, int32_t 
     return s;
 }
 
+// typed: the caller's maps are floats (the entries without _out); a stream whose host pairs come back in another form
+// refuses them.  Device pairs are always two float maps.
 static int32_t stream_push(svh_elas_stream* s, bool device, const uint8_t* I1, const uint8_t* I2, float* D1,
-                           float* D2, uint64_t* ticket) {
-    if (!s || !I1 || !I2 || !D1 || !D2) return fail(SVH_ERR_BAD_ARG, "null argument");
+                           float* D2, uint64_t* ticket, bool typed = true) {
+    if (!s || !I1 || !I2 || !D1) return fail(SVH_ERR_BAD_ARG, "null argument");
+    const bool plain = device || (s->format == SVH_DISP_F32 && s->maps == SVH_MAPS_BOTH);
+    if (!D2 && (device || s->maps == SVH_MAPS_BOTH)) return fail(SVH_ERR_BAD_ARG, "null argument");
+    if (typed && !plain) return fail(SVH_ERR_BAD_ARG, "the stream's output form is not two float maps: use push_out");
     std::unique_lock<std::mutex> lk(s->mu);
     if (s->stop || s->closing) return fail(SVH_ERR_BAD_ARG, "stream is closing");
     // (a producer blocked here while the stream is closed: close() wakes it, it leaves with an error, and
@@ -1703,6 +1789,11 @@ int32_t svh_elas_stream_push(svh_elas_stream* s, const uint8_t* I1, const uint8_
     return stream_push(s, false, I1, I2, D1, D2, ticket);
 }
 
+int32_t svh_elas_stream_push_out(svh_elas_stream* s, const uint8_t* I1, const uint8_t* I2, void* D1, void* D2,
+                                 uint64_t* ticket) {
+    return stream_push(s, false, I1, I2, static_cast<float*>(D1), static_cast<float*>(D2), ticket, false);
+}
+
 int32_t svh_elas_stream_push_device(svh_elas_stream* s, const uint8_t* dI1, const uint8_t* dI2, float* dD1,
                                     float* dD2, uint64_t* ticket) {
     return stream_push(s, true, dI1, dI2, dD1, dD2, ticket);
@@ -1765,6 +1856,20 @@ int32_t svh_elas_stream_push_n(svh_elas_stream* s, int32_t n, const uint8_t* con
     for (int32_t i = 0; i < n; i++) {
         uint64_t t = 0;
         const int32_t rc = stream_push(s, false, I1[i], I2[i], D1[i], D2[i], &t);
+        if (rc) return rc;
+        if (i == 0 && first_ticket) *first_ticket = t;
+    }
+    return SVH_OK;
+}
+
+int32_t svh_elas_stream_push_out_n(svh_elas_stream* s, int32_t n, const uint8_t* const* I1, const uint8_t* const* I2,
+                                   void* const* D1, void* const* D2, uint64_t* first_ticket) {
+    if (n < 0 || (n > 0 && (!I1 || !I2 || !D1 || (!D2 && !(s && s->maps == SVH_MAPS_LEFT)))))
+        return fail(SVH_ERR_BAD_ARG, "bad count / null pointer array");
+    for (int32_t i = 0; i < n; i++) {
+        uint64_t t = 0;
+        const int32_t rc = stream_push(s, false, I1[i], I2[i], static_cast<float*>(D1[i]),
+                                       D2 ? static_cast<float*>(D2[i]) : nullptr, &t, false);
         if (rc) return rc;
         if (i == 0 && first_ticket) *first_ticket = t;
     }
@@ -1847,6 +1952,17 @@ void svh_debug_stage_stamps(int64_t* out32) {
             (void)hipMemcpy(out32, l->stg.counts->dbg, 32 * sizeof(int64_t), hipMemcpyDeviceToHost);
             return;
         }
+}
+
+void svh_test_d2h_map_bytes(int64_t out[2], int32_t reset) {
+    if (out) {
+        out[0] = svh::g_d2h_map_bytes.load();
+        out[1] = svh::g_d2h_map_copies.load();
+    }
+    if (reset) {
+        svh::g_d2h_map_bytes.store(0);
+        svh::g_d2h_map_copies.store(0);
+    }
 }
 
 void svh_elas_sizing_stats(int64_t* out4) {

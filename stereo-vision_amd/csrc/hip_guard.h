@@ -94,6 +94,12 @@ extern "C" int32_t svh_test_fail_at(const char* spec);
 //   out[2]  batched launches issued by BatchRec::flush
 // A loop over the single entries moves none of them, so a parity test that also reads these shows lockstep happened.
 extern "C" void svh_test_lockstep_counts(int64_t out[3]);
+// TEST TAP of the ELAS engine's downward map copies (elas_engine.cpp, copy_map), bound by name like the hook above;
+// process-wide: out[0] = bytes, out[1] = number of device-to-host map copies issued since the start or the last reset
+// (a strided copy of several maps counts once); reset != 0 clears both after reading.  Parity of the 16-bit outputs
+// cannot show that fewer bytes crossed PCIe (a library that downloaded floats and converted on the host would pass);
+// this does.
+extern "C" void svh_test_d2h_map_bytes(int64_t out[2], int32_t reset);
 // TEST ACCESS to the device-frame path of the Matcher (matcher_engine.cpp), bound by name like the hook above:
 //   svh_test_pack_rows      k_pack_rows alone: src_dev = h rows of w bytes, pitch apart, in device memory; bpl * h bytes
 //                           (bpl a multiple of 16, >= w) come back in dst_host

@@ -242,6 +242,72 @@ int32_t svh_png_read_gray(const char* path, uint8_t* buf, size_t cap, int32_t* w
     }
 }
 
+// ---- KITTI disparity images: 16-bit grey PNG, value x 256, 0 = invalid (the form SVH_DISP_U16 of svh.h produces)
+int32_t svh_kitti_write_disp_png(const char* path, const uint16_t* v, int32_t width, int32_t height) {
+    try {
+    if (!path || !v || width <= 0 || height <= 0 || (uint64_t)width * (uint64_t)height > (1ull << 28)) return SVH_ERR_BAD_ARG;
+    // every row: filter byte 0 (None), then the samples high byte first
+    const size_t stride = (size_t)width * 2;
+    std::vector<uint8_t> flat((stride + 1) * height);
+    for (int32_t y = 0; y < height; y++) {
+        uint8_t* row = &flat[(stride + 1) * y];
+        *row++ = 0;
+        for (int32_t x = 0; x < width; x++) {
+            const uint16_t s = v[(size_t)y * width + x];
+            row[2 * x] = (uint8_t)(s >> 8);
+            row[2 * x + 1] = (uint8_t)(s & 255);
+        }
+    }
+    uLongf zn = compressBound((uLong)flat.size());
+    std::vector<uint8_t> z(zn);
+    if (compress2(z.data(), &zn, flat.data(), (uLong)flat.size(), Z_DEFAULT_COMPRESSION) != Z_OK) return SVH_ERR_BAD_ARG;
+    std::vector<uint8_t> file = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    auto put32 = [&](uint32_t x) { for (int sh = 24; sh >= 0; sh -= 8) file.push_back((uint8_t)(x >> sh)); };
+    auto chunk = [&](const char* type, const uint8_t* body, size_t len) {
+        put32((uint32_t)len);
+        const size_t at = file.size();
+        file.insert(file.end(), type, type + 4);
+        if (len) file.insert(file.end(), body, body + len);
+        put32((uint32_t)crc32(crc32(0, Z_NULL, 0), &file[at], (uInt)(len + 4)));
+    };
+    uint8_t ihdr[13] = {0, 0, 0, 0, 0, 0, 0, 0, 16, 0, 0, 0, 0};   // depth 16, colour type 0 (grey), deflate, filter 0, no interlace
+    for (int k = 0; k < 4; k++) {
+        ihdr[k] = (uint8_t)((uint32_t)width >> (24 - 8 * k));
+        ihdr[4 + k] = (uint8_t)((uint32_t)height >> (24 - 8 * k));
+    }
+    chunk("IHDR", ihdr, 13);
+    chunk("IDAT", z.data(), (size_t)zn);
+    chunk("IEND", nullptr, 0);
+    FILE* f = fopen(path, "wb");
+    if (!f) return SVH_ERR_BAD_ARG;
+    const bool ok = fwrite(file.data(), 1, file.size(), f) == file.size();
+    return (fclose(f) == 0 && ok) ? SVH_OK : SVH_ERR_BAD_ARG;
+    } catch (...) {   // std::bad_alloc etc. must not cross the C boundary
+        return SVH_ERR_BAD_ARG;
+    }
+}
+
+int32_t svh_kitti_read_disp_png(const char* path, uint16_t* out, size_t cap, int32_t* dims) {
+    try {
+    if (!path || !dims) return SVH_ERR_BAD_ARG;
+    std::vector<uint8_t> file, raw;
+    if (!read_file(path, file)) return SVH_ERR_BAD_ARG;
+    PngInfo info;
+    const int32_t rc = png_decode(file, info, raw);
+    if (rc != SVH_OK) return rc;
+    if (info.depth != 16 || info.colour != 0) return SVH_ERR_UNSUPPORTED;   // not a disparity image
+    dims[0] = info.w;
+    dims[1] = info.h;
+    if (!out) return SVH_OK;
+    const size_t n = (size_t)info.w * info.h;
+    if (cap < n) return SVH_ERR_BAD_ARG;
+    for (size_t i = 0; i < n; i++) out[i] = (uint16_t)((uint16_t)raw[2 * i] << 8 | raw[2 * i + 1]);
+    return SVH_OK;
+    } catch (...) {   // std::bad_alloc etc. must not cross the C boundary
+        return SVH_ERR_BAD_ARG;
+    }
+}
+
 svh_kitti_seq* svh_kitti_seq_open(const char* drive_dir) {
     try {
     if (!drive_dir) return nullptr;

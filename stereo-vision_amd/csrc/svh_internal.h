@@ -239,6 +239,14 @@ void launch_adaptive_mean(const LaunchCtx& cx, const svh_elas_params& p, const D
                           int32_t nside, const GroupDev& G, const DevMaps& out, const PostScratch& s);
 void launch_median(const LaunchCtx& cx, const Dims& d, int32_t g, int32_t nside, const GroupDev& G,
                    const DevMaps& out, const PostScratch& s);
+// Float maps -> their 16-bit form (csrc/disp_core.h, k_disp_pack_u16 of disp_kernels.hip), any number of maps per call:
+// map i reads n floats at src + maps[i].src and writes n uint16 at dst + maps[i].dst (element offsets).  Any alignment
+// of either side is correct; a destination on a 16-byte boundary whose source is on one too takes the vector path whole.
+struct PackMap {
+    int64_t src, dst, n;
+};
+constexpr int kPackMaps = 2 * kMaxGroup;   // maps per launch (the table travels as a kernel argument)
+void launch_disp_pack(const LaunchCtx& cx, const float* src, uint16_t* dst, const PackMap* maps, int32_t count);
 // speckle labelling (tile union-find, seam merge, component sizes) without the mask pass
 void launch_segments_label(const LaunchCtx& cx, const svh_elas_params& p, const Dims& d, int32_t g,
                            int32_t nside, const GroupDev& G, const DevMaps& in, const PostScratch& s);

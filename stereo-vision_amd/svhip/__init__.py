@@ -104,6 +104,24 @@ def runtime_info():
     return ri.as_dict()
 
 
+DISP_F32, DISP_U16 = 0, 1
+MAPS_BOTH, MAPS_LEFT = 0, 1
+
+
+class ElasOutput(C.Structure):
+    """svh_elas_output (include/svh.h): what a host entry returns"""
+    _fields_ = [("format", C.c_int32), ("maps", C.c_int32)]
+
+
+def _output(out, maps):
+    """(svh_elas_output, numpy dtype of a map, D2 wanted) of out = "f32" | "u16" and maps = "both" | "left" """
+    try:
+        o = ElasOutput({"f32": DISP_F32, "u16": DISP_U16}[out], {"both": MAPS_BOTH, "left": MAPS_LEFT}[maps])
+    except KeyError:
+        raise ValueError("out must be 'f32' or 'u16' and maps 'both' or 'left', not %r / %r" % (out, maps))
+    return o, (np.uint16 if o.format == DISP_U16 else np.float32), o.maps == MAPS_BOTH
+
+
 class SvhError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libsvhip error %d: %s" % (code, msg))
@@ -147,6 +165,14 @@ def lib():
                                          C.POINTER(C.c_size_t)]
         L.svh_elas_last_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
         L.svh_delaunay.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_elas_process_out.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(ElasOutput)]
+        L.svh_elas_process_batch_out.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(ElasOutput)]
+        L.svh_elas_stream_open_out.restype = C.c_void_p
+        L.svh_elas_stream_open_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ElasOutput)]
+        L.svh_elas_stream_push_out.argtypes = [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]
+        L.svh_elas_stream_push_out_n.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.POINTER(C.c_uint64)]
+        L.svh_disparity_pack_u16.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32]
+        L.svh_disparity_unpack_u16.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -163,18 +189,34 @@ class ElasStream:
     (include/svh.h).  Host arrays pushed here must stay alive until their pair is popped: the
     stream keeps a reference to them."""
 
-    def __init__(self, elas, w, h, pitch, depth=0):
+    def __init__(self, elas, w, h, pitch, depth=0, out="f32", maps="both"):
         dims = (C.c_int32 * 3)(w, h, pitch)
-        self._h = lib().svh_elas_stream_open(elas._h, dims, depth)
+        self._out, self.dtype, self._both = _output(out, maps)
+        self._plain = (out, maps) == ("f32", "both")
+        if self._plain:
+            self._h = lib().svh_elas_stream_open(elas._h, dims, depth)
+        else:
+            self._h = lib().svh_elas_stream_open_out(elas._h, dims, depth, C.byref(self._out))
         if not self._h:
             raise SvhError(-1, last_error())
         self._keep = {}
 
-    def push(self, I1, I2, D1, D2):
-        """host arrays (uint8 [H,W] with the stream's pitch; float32 maps written in place)"""
+    def _maps_ok(self, Ds):
+        for D in Ds:
+            if D is not None and np.asarray(D).dtype != self.dtype:
+                raise ValueError("this stream writes %s maps" % np.dtype(self.dtype).name)
+
+    def push(self, I1, I2, D1, D2=None):
+        """host arrays (uint8 [H,W] with the stream's pitch; maps of the stream's dtype -- float32, or uint16 with
+        out="u16" -- written in place; D2 may be None with maps="left")"""
         t = C.c_uint64(0)
-        rc = lib().svh_elas_stream_push(self._h, I1.ctypes.data, I2.ctypes.data, D1.ctypes.data,
-                                        D2.ctypes.data, C.byref(t))
+        self._maps_ok((D1, D2))
+        if self._plain:
+            rc = lib().svh_elas_stream_push(self._h, I1.ctypes.data, I2.ctypes.data, D1.ctypes.data,
+                                            D2.ctypes.data, C.byref(t))
+        else:
+            rc = lib().svh_elas_stream_push_out(self._h, I1.ctypes.data, I2.ctypes.data, D1.ctypes.data,
+                                                D2.ctypes.data if D2 is not None else None, C.byref(t))
         if rc < 0:
             raise SvhError(rc, last_error())
         self._keep[t.value] = (I1, I2, D1, D2)
@@ -196,14 +238,16 @@ class ElasStream:
             raise SvhError(rc, last_error())
         return t.value
 
-    def push_n(self, I1s, I2s, D1s, D2s):
-        """n host pairs in one call: arrays [n,H,W] (uint8 images, float32 maps written in place); they must stay
-        alive and unread until popped -- the stream keeps a reference"""
+    def push_n(self, I1s, I2s, D1s, D2s=None):
+        """n host pairs in one call: arrays [n,H,W] (uint8 images, maps of the stream's dtype written in place; D2s may
+        be None with maps="left"); they must stay alive and unread until popped -- the stream keeps a reference"""
         n = len(I1s)
         arr = C.c_void_p * n
-        a = [arr(*[int(X[i].ctypes.data) for i in range(n)]) for X in (I1s, I2s, D1s, D2s)]
+        self._maps_ok((D1s, D2s))
+        a = [arr(*[int(X[i].ctypes.data) for i in range(n)]) if X is not None else None for X in (I1s, I2s, D1s, D2s)]
         t = C.c_uint64(0)
-        rc = lib().svh_elas_stream_push_n(self._h, n, a[0], a[1], a[2], a[3], C.byref(t))
+        push = lib().svh_elas_stream_push_n if self._plain else lib().svh_elas_stream_push_out_n
+        rc = push(self._h, n, a[0], a[1], a[2], a[3], C.byref(t))
         if rc < 0:
             raise SvhError(rc, last_error())
         self._keep[("n", t.value)] = (I1s, I2s, D1s, D2s)
@@ -212,7 +256,8 @@ class ElasStream:
     def push_n_raw(self, n, a1, a2, d1, d2):
         """the same with ready-made ctypes pointer arrays (no per-call marshalling); the caller keeps the buffers alive"""
         t = C.c_uint64(0)
-        rc = lib().svh_elas_stream_push_n(self._h, n, a1, a2, d1, d2, C.byref(t))
+        push = lib().svh_elas_stream_push_n if self._plain else lib().svh_elas_stream_push_out_n
+        rc = push(self._h, n, a1, a2, d1, d2, C.byref(t))
         if rc < 0:
             raise SvhError(rc, last_error())
         return t.value
@@ -304,9 +349,12 @@ class Elas:
     def _dshape(self, h, w):
         return (h // 2, w // 2) if self._p.subsampling else (h, w)
 
-    def process(self, I1, I2, D1=None, D2=None):
+    def process(self, I1, I2, D1=None, D2=None, out="f32", maps="both"):
         """Elas::process(I1,I2,D1,D2,dims).  Returns (status, D1, D2); on status 1
-        (<3 support points) D1/D2 are left untouched, like the reference."""
+        (<3 support points) D1/D2 are left untouched, like the reference.
+        out="u16": the maps come back as uint16, value x 256, 0 = invalid (svh_elas_process_out); maps="left": only D1
+        is copied down, and the D2 returned is the one passed in (None by default)."""
+        o, dtype, both = _output(out, maps)
         I1 = np.asarray(I1, np.uint8)
         I2 = np.asarray(I2, np.uint8)
         assert I1.shape == I2.shape and I1.ndim == 2
@@ -318,37 +366,48 @@ class Elas:
             I2 = np.ascontiguousarray(I2)
         dims = (C.c_int32 * 3)(w, h, I1.strides[0])
         if D1 is None:
-            D1 = np.zeros(self._dshape(h, w), np.float32)
-        if D2 is None:
-            D2 = np.zeros(self._dshape(h, w), np.float32)
+            D1 = np.zeros(self._dshape(h, w), dtype)
+        if D2 is None and both:
+            D2 = np.zeros(self._dshape(h, w), dtype)
         for name, D in (("D1", D1), ("D2", D2)):
-            # the library writes h*w packed float32 through the raw pointer
-            if not (isinstance(D, np.ndarray) and D.dtype == np.float32 and D.flags.c_contiguous
+            # the library writes h*w packed maps through the raw pointer
+            if D is None and not both:
+                continue
+            if not (isinstance(D, np.ndarray) and D.dtype == dtype and D.flags.c_contiguous
                     and D.flags.writeable and D.shape == self._dshape(h, w)):
-                raise ValueError("%s must be a writable C-contiguous float32 array of shape %s"
-                                 % (name, (self._dshape(h, w),)))
-        rc = lib().svh_elas_process(self._h, I1.ctypes.data, I2.ctypes.data, D1.ctypes.data,
-                                    D2.ctypes.data, dims)
+                raise ValueError("%s must be a writable C-contiguous %s array of shape %s"
+                                 % (name, np.dtype(dtype).name, (self._dshape(h, w),)))
+        if (out, maps) == ("f32", "both"):
+            rc = lib().svh_elas_process(self._h, I1.ctypes.data, I2.ctypes.data, D1.ctypes.data,
+                                        D2.ctypes.data, dims)
+        else:
+            rc = lib().svh_elas_process_out(self._h, I1.ctypes.data, I2.ctypes.data, D1.ctypes.data,
+                                            D2.ctypes.data if D2 is not None else None, dims, C.byref(o))
         if rc < 0:
             raise SvhError(rc, last_error())
         return rc, D1, D2
 
-    def process_batch(self, I1s, I2s):
-        """n independent pairs (host arrays [n,H,W]) pipelined over the engine lanes."""
+    def process_batch(self, I1s, I2s, out="f32", maps="both"):
+        """n independent pairs (host arrays [n,H,W]) pipelined over the engine lanes.  Returns (statuses, D1, D2);
+        out="u16": uint16 maps (value x 256, 0 = invalid); maps="left": D2 is None."""
+        o, dtype, both = _output(out, maps)
         I1s = np.ascontiguousarray(I1s, np.uint8)
         I2s = np.ascontiguousarray(I2s, np.uint8)
         n, h, w = I1s.shape
         dh, dw = self._dshape(h, w)
-        D1 = np.zeros((n, dh, dw), np.float32)
-        D2 = np.zeros((n, dh, dw), np.float32)
+        D1 = np.zeros((n, dh, dw), dtype)
+        D2 = np.zeros((n, dh, dw), dtype) if both else None
         arr = C.c_void_p * n
         a1 = arr(*[I1s[i].ctypes.data for i in range(n)])
         a2 = arr(*[I2s[i].ctypes.data for i in range(n)])
         d1 = arr(*[D1[i].ctypes.data for i in range(n)])
-        d2 = arr(*[D2[i].ctypes.data for i in range(n)])
+        d2 = arr(*[D2[i].ctypes.data for i in range(n)]) if both else None
         st = (C.c_int32 * n)()
         dims = (C.c_int32 * 3)(w, h, w)
-        rc = lib().svh_elas_process_batch(self._h, n, a1, a2, d1, d2, dims, st)
+        if (out, maps) == ("f32", "both"):
+            rc = lib().svh_elas_process_batch(self._h, n, a1, a2, d1, d2, dims, st)
+        else:
+            rc = lib().svh_elas_process_batch_out(self._h, n, a1, a2, d1, d2, dims, st, C.byref(o))
         if rc < 0:
             raise SvhError(rc, last_error())
         return list(st), D1, D2
@@ -363,9 +422,9 @@ class Elas:
             raise SvhError(rc, last_error())
         return list(st)
 
-    def stream(self, w, h, pitch=None, depth=0):
+    def stream(self, w, h, pitch=None, depth=0, out="f32", maps="both"):
         """streaming submission (svh_elas_stream_*): pairs in one at a time, results in order"""
-        return ElasStream(self, w, h, pitch if pitch is not None else w, depth)
+        return ElasStream(self, w, h, pitch if pitch is not None else w, depth, out, maps)
 
     # ---- parity taps -----------------------------------------------------
     def set_taps(self, enable=True):
@@ -418,6 +477,26 @@ def stage_stats():
 
 def device_count():
     return lib().svh_device_count()
+
+
+def pack_u16(D):
+    """float disparities -> uint16, value x 256, 0 = invalid, on the device (svh_disparity_pack_u16, k_disp_pack_u16)"""
+    D = np.ascontiguousarray(D, np.float32)
+    out = np.empty(D.shape, np.uint16)
+    rc = lib().svh_disparity_pack_u16(D.ctypes.data, 0, D.size, out.ctypes.data, 0)
+    if rc < 0:
+        raise SvhError(rc, last_error())
+    return out
+
+
+def unpack_u16(v):
+    """the inverse on the host: v / 256 as float32, -1 where v == 0 (svh_disparity_unpack_u16)"""
+    v = np.ascontiguousarray(v, np.uint16)
+    out = np.empty(v.shape, np.float32)
+    rc = lib().svh_disparity_unpack_u16(v.ctypes.data, v.size, out.ctypes.data)
+    if rc < 0:
+        raise SvhError(rc, last_error())
+    return out
 
 
 # ---------------------------------------------------------------------------

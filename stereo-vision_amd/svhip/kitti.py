@@ -41,6 +41,8 @@ def _bind():
         L.svh_kitti_seq_count.argtypes = [C.c_void_p]
         L.svh_kitti_seq_seek.argtypes = [C.c_void_p, C.c_int32]
         L.svh_kitti_seq_next.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.svh_kitti_write_disp_png.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]
+        L.svh_kitti_read_disp_png.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L._kitti_bound = True
     return L
 
@@ -64,6 +66,31 @@ def read_png_gray(path):
     if rc:
         raise SvhError(rc, "cannot decode " + str(path))
     return img
+
+
+def write_disp_png(path, v):
+    """a uint16 map [H,W] (value x 256, 0 = invalid: Elas.process(out="u16"), svhip.pack_u16) as a KITTI disparity PNG"""
+    v = np.asarray(v)
+    if v.dtype != np.uint16 or v.ndim != 2:
+        raise ValueError("a disparity image is a 2-D uint16 array")
+    v = np.ascontiguousarray(v)
+    rc = _bind().svh_kitti_write_disp_png(str(path).encode(), v.ctypes.data, v.shape[1], v.shape[0])
+    if rc:
+        raise SvhError(rc, "cannot write " + str(path))
+
+
+def read_disp_png(path):
+    """a 16-bit gray PNG as uint16 [H,W], all 16 bits kept"""
+    L = _bind()
+    dims = (C.c_int32 * 2)()
+    rc = L.svh_kitti_read_disp_png(str(path).encode(), None, 0, dims)
+    if rc:
+        raise SvhError(rc, "cannot read " + str(path))
+    v = np.empty((dims[1], dims[0]), np.uint16)
+    rc = L.svh_kitti_read_disp_png(str(path).encode(), v.ctypes.data, v.size, dims)
+    if rc:
+        raise SvhError(rc, "cannot decode " + str(path))
+    return v
 
 
 class Sequence:

@@ -124,6 +124,7 @@ void launch_gap(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t, 
 void launch_adaptive_mean(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t, int32_t, const GroupDev&, const DevMaps&,
                           const PostScratch&) {}
 void launch_median(const LaunchCtx&, const Dims&, int32_t, int32_t, const GroupDev&, const DevMaps&, const PostScratch&) {}
+void launch_disp_pack(const LaunchCtx&, const float*, uint16_t*, const PackMap*, int32_t) {}
 void launch_segments_label(const LaunchCtx&, const svh_elas_params&, const Dims&, int32_t, int32_t, const GroupDev&,
                            const DevMaps&, const PostScratch&) {}
 }  // namespace svh
