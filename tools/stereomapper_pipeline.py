@@ -11,8 +11,9 @@ i.e. what ReadFromFilesThread, VisualOdometryThread, StereoThread and MainDialog
 them (readfromfilesthread.cpp:25-112, visualodometrythread.cpp:95-140, stereothread.cpp:62-170, maindialog.cpp:602-606),
 without the GUI.  Usage:
 
-    python tools/stereomapper_pipeline.py [--unrectified] [--resident] [--render DIR] [--panes DIR [--pane-size WxH]]
-                                          [--lockstep K] <drive_dir> <calib_cam_to_cam.txt> [max_frames]
+    python tools/stereomapper_pipeline.py [--unrectified] [--resident] [--normalize] [--render DIR]
+                                          [--panes DIR [--pane-size WxH]] [--lockstep K]
+                                          <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
 DIR/frame_%06d.ppm, and at the end View3D::recordHuman's fly-through into DIR/img_320_480_%06d.ppm.  Without the flag
@@ -32,6 +33,11 @@ back feeds svh_vo_process, which takes host images.
 --resident: the frame never returns to the host.  A rectified drive's pair is uploaded once, a raw pair is rectified in
 place (--unrectified), and the visual odometry (svh_vo_process_device), ELAS and the map fusion (svh_map_add_device) all
 read that one device copy: no download, no second or third upload.  Results are the same bit for bit.
+
+--normalize: StereoImage::histogramNormalization (stereoimage.cpp:94-134; include/svh_histnorm.h) on both images of
+every pair, on the device, in place where ELAS and the visual odometry read them, after the rectification if there is
+one.  The reference has the function and does not call it; neither does this tool without the flag.  Works with
+--resident and --lockstep K (one call for the K pairs).
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -79,7 +85,7 @@ class DeviceBuffer:
 
 class Pipeline:
     def __init__(self, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None, view_size=(320, 480),
-                 resident=False):
+                 resident=False, normalize=False):
         import helpers as Hh
         import svhip as S
         from svhip import mapper, view
@@ -93,6 +99,8 @@ class Pipeline:
         self.poses = []
         self.rect = None
         self.resident = resident
+        self.normalize = normalize
+        self.histnorm = None   # svhip.histnorm.HistNorm of the frame size, made on the first frame
         self.frame = None      # what render_panes() shows: (I1, I2 or None when resident, w, h, vo ok, ELAS ok)
         self.pane = None
         if rectify_params is not None:
@@ -119,16 +127,28 @@ class Pipeline:
             self.raw[1].upload(I2)
             self.rect.pairs_device(1, self.raw[0].ptr.value, self.raw[1].ptr.value, sw, sw * sh,
                                    self.buf[0].ptr.value, self.buf[1].ptr.value, w, n)
-            if not self.resident:
-                I1 = self.buf[0].download(np.empty((h, w), np.uint8))
-                I2 = self.buf[1].download(np.empty((h, w), np.uint8))
+        uploaded = self.rect is not None   # the pair ELAS will read lies in buf[0], buf[1]
+        if self.normalize:
+            # stereoimage.cpp:94-134 on both images, in place on the device
+            if not uploaded:
+                self.buf[0].upload(I1)
+                self.buf[1].upload(I2)
+                uploaded = True
+            if self.histnorm is None or (self.histnorm.width, self.histnorm.height) != (w, h):
+                from svhip import histnorm
+                self.histnorm = histnorm.HistNorm(w, h)
+            self.histnorm.pairs_device(1, self.buf[0].ptr.value, self.buf[1].ptr.value, w, n)
+        if uploaded and not self.resident:   # one copy back for svh_vo_process, which takes host images
+            I1 = self.buf[0].download(np.empty((h, w), np.uint8))
+            I2 = self.buf[1].download(np.empty((h, w), np.uint8))
         # visualodometrythread.cpp:100-137
         if self.resident:
             # the pair is on the device once (uploaded here, or rectified there) and every stage reads that copy
             from svhip import resident
-            if self.rect is None:
+            if not uploaded:
                 self.buf[0].upload(I1)
                 self.buf[1].upload(I2)
+                uploaded = True
             ok = resident.vo_process(self.vo, self.buf[0].ptr.value, self.buf[1].ptr.value, w, h, w) == 1
         else:
             ok = self.vo.process(I1, I2) == 1
@@ -143,7 +163,7 @@ class Pipeline:
         self.poses.append(self.H_total.copy())
         # stereothread.cpp:62-115: ELAS with the disparity maps left on the device
         dI1, dI2, dD1, dD2 = self.buf
-        if self.rect is None and not self.resident:
+        if not uploaded:
             dI1.upload(I1)
             dI2.upload(I2)
         st = self.elas.process_batch_device(1, dI1.ptr.value, dI2.ptr.value, n, dD1.ptr.value, dD2.ptr.value,
@@ -191,7 +211,7 @@ class LockstepPipeline:
     maps[i], views[i], H_total[i], poses[i]; per drive every result equals that of a resident Pipeline of its own."""
 
     def __init__(self, K, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None, view_size=(320, 480),
-                 private_rand=None):
+                 private_rand=None, normalize=False):
         import helpers as Hh
         import svhip as S
         from svhip import mapper, view
@@ -205,6 +225,8 @@ class LockstepPipeline:
         self.poses = [[] for _ in range(K)]
         self.buf = None
         self.rect = None
+        self.normalize = normalize
+        self.histnorm = None
         if rectify_params is not None:
             from svhip import rectify
             self.rect = rectify.Rectifier(rectify_params)
@@ -234,6 +256,12 @@ class LockstepPipeline:
         else:
             self.buf[0].upload(np.stack([p[0] for p in pairs]))
             self.buf[1].upload(np.stack([p[1] for p in pairs]))
+        if self.normalize:
+            # stereoimage.cpp:94-134 on the 2 K images in one call, each with its own table
+            if self.histnorm is None or (self.histnorm.width, self.histnorm.height) != (w, h):
+                from svhip import histnorm
+                self.histnorm = histnorm.HistNorm(w, h)
+            self.histnorm.pairs_device(K, dI1, dI2, w, n)
         a1 = [dI1 + i * n for i in range(K)]
         a2 = [dI2 + i * n for i in range(K)]
         # visualodometrythread.cpp:100-137 for the K drives
@@ -267,10 +295,10 @@ class LockstepPipeline:
         return out
 
 
-def main_lockstep(K, drive_dir, calib, limit, rp):
+def main_lockstep(K, drive_dir, calib, limit, rp, normalize=False):
     import collections
     from svhip import kitti
-    p = LockstepPipeline(K, calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp)
+    p = LockstepPipeline(K, calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, normalize=normalize)
     window = collections.deque(maxlen=K)
     t0 = time.perf_counter()
     steps = 0
@@ -305,6 +333,9 @@ def main():
     resident = "--resident" in sys.argv
     if resident:
         sys.argv.remove("--resident")
+    normalize = "--normalize" in sys.argv
+    if normalize:
+        sys.argv.remove("--normalize")
     render_dir = None
     if "--render" in sys.argv:
         k = sys.argv.index("--render")
@@ -339,8 +370,8 @@ def main():
         from svhip import rectify
         rp = rectify.params_from_kitti(calib, 0, 1)
     if lockstep:
-        return main_lockstep(lockstep, sys.argv[1], calib, limit, rp)
-    p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident)
+        return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize)
+    p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize)
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
