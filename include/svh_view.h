@@ -69,6 +69,28 @@ int32_t   svh_view_add_camera(svh_view* v, const double* H_total /*4x4 row major
 /* what: 0 lists, 1 points, 2 cameras, 3 points the store has room for (it grows geometrically) */
 int64_t   svh_view_count(svh_view* v, int32_t what);
 
+/* Voxel-grid thinning, the first step past the reference's widget: of all points of the store that fall into one cube
+ * of side `voxel` the one with the lowest store index (the first one drawn) stays; the survivors keep their order and
+ * their four floats bit for bit.  The cell of a coordinate is floorf(x / voxel) in fp32 (IEEE division); a point is
+ * placeable iff its three coordinates are finite and its three cells lie in [-2^20, 2^20).  An unplaceable point belongs
+ * to no voxel, is kept in place and counted in `unplaced`.  The number of lists stays; each list's length becomes its
+ * number of survivors (empty lists stay).  The result does not depend on scheduling, thinning twice is thinning once,
+ * and thin(thin(A) ++ B) = thin(A ++ B): "every N frames" equals "at the end".  svh_view_add_points / svh_view_add_map
+ * work on a thinned store as on any other.  SVH_ERR_BAD_ARG, nothing read or changed: a null view, a voxel that is not
+ * finite or not > 0.  An empty store: SVH_OK, all statistics zero, no launch.  The survivors are written to a second
+ * store and the two change places after the last wait, every allocation comes before: after SVH_ERR_HIP the object
+ * holds and renders what it held before.  The arithmetic is stereo-vision_amd/csrc/view_thin_core.h, restated in
+ * tests/view_thin_ref.py.  Not done: averaging the points of a voxel, a table kept between calls.            */
+typedef struct svh_view_thin_stats { int64_t before, after, unplaced; } svh_view_thin_stats;
+int32_t   svh_view_thin(svh_view* v, float voxel, svh_view_thin_stats* stats /* may be NULL */);
+
+/* The points themselves: copies the first min(number, cap) points (x,y,z,val) of list `list` -- -1: of the whole store,
+ * the lists back to back -- to host memory or (on_device) a device pointer and returns the number of points the list
+ * or the store holds; xyzv may be NULL with cap 0.  svh_view_list_len returns the length of one list.  Both:
+ * SVH_ERR_BAD_ARG for a list index out of range, cap < 0, or a null xyzv with cap > 0.                         */
+int64_t   svh_view_get_points(svh_view* v, int32_t list /* -1: the whole store */, float* xyzv, int64_t cap, int32_t on_device);
+int64_t   svh_view_list_len(svh_view* v, int32_t list);
+
 /* paintGL + grabFrameBuffer: width*height*3 bytes, row 0 = top, to the host or (rgb_on_device) a device pointer */
 int32_t   svh_view_render(svh_view* v, uint8_t* rgb, int32_t rgb_on_device);
 

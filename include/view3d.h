@@ -60,6 +60,25 @@ public:
     // the lists of the frame svh_map_add has just processed, without leaving the device
     void addPoints(svh_map* map) { svh_view_add_map(_view, map); }
 
+    // additions to the widget's interface (svh_view.h): keep the first-drawn point of every cube of side `voxel`;
+    // returns the number of points left or a negative SVH_ERR_*
+    int64_t thin(float voxel) {
+        svh_view_thin_stats st;
+        const int32_t rc = svh_view_thin(_view, voxel, &st);
+        return rc < 0 ? (int64_t)rc : st.after;
+    }
+    // ... and the map itself: the lists as they are held, empty ones included
+    std::vector<std::vector<point_3d>> getPoints() {
+        std::vector<std::vector<point_3d>> p((size_t)svh_view_count(_view, 0));
+        for (size_t i = 0; i < p.size(); i++) {
+            const int64_t n = svh_view_list_len(_view, (int32_t)i);
+            if (n <= 0) continue;
+            p[i].resize((size_t)n, point_3d(0, 0, 0, 0));
+            svh_view_get_points(_view, (int32_t)i, &p[i][0].x, n, 0);
+        }
+        return p;
+    }
+
     void clearAll() { svh_view_clear(_view); }
     void setBackgroundWallFlag(bool) {}        // out of scope, see svh_view.h
     void setBackgroundWallPosition(float) {}

@@ -114,6 +114,12 @@ extern "C" int32_t svh_test_pack_rows(const uint8_t* src_dev, int32_t w, int32_t
 extern "C" int64_t svh_test_matcher_image(svh_matcher* m, int32_t view, uint8_t* buf, size_t cap);
 extern "C" float svh_test_matcher_gain(svh_matcher* m, const svh_p_match* matches, int32_t nm, const int32_t* inliers,
                                        int32_t n, int32_t path);
+// TEST ACCESS to the arithmetic of the map view's thinning (view_engine.cpp), bound by name like the hook above; host code,
+// needs no device: csrc/view_thin_core.h evaluated on n points (x, y, z, val).  key[i] = the voxel key, all ones for a
+// point that falls into no voxel; home[i] = the slot its probe starts at in a table for n points, 0xFFFFFFFF for such a
+// point; *capacity = that table's slots.  Any of the three outputs may be NULL
+extern "C" int32_t svh_test_thin_keys(const float* xyzv, int64_t n, float voxel, uint64_t* key, uint32_t* home,
+                                      uint64_t* capacity);
 
 // The guard of every HIP call of the host engines: `kind` is one of none, malloc, copy, launch, wait (see above); a
 // disarmed hook costs one relaxed load.  Returns hip_failed(...) out of the enclosing function on failure.

@@ -2,7 +2,9 @@
 //
 // Host (this file): the sequence of point lists in ONE growing device buffer (addPoints' list semantics, :174-254),
 // the cameras (addCamera in double, :127-166), the matrices and the segment list of a render, playPoses' pose loop.
-// Device (view_kernels.hip): the render.  The object has its own stream; every entry returns when it is complete.
+// Device (view_kernels.hip): the render; (view_thin_kernels.hip): the voxel-grid thinning, whose survivors go to a second
+// store that changes places with the first after the last wait.  The object has its own stream; every entry returns when
+// it is complete.
 //
 // Draw index of a point = 162 + its position in the store, so the store holds the lists back to back in sequence
 // order and dropping the newest list is forgetting the tail.  A growth allocates the new store first and moves the
@@ -20,6 +22,7 @@
 #include "svh_config.h"
 #include "view_core.h"
 #include "view_internal.h"
+#include "view_thin_core.h"
 
 using namespace svh;
 
@@ -57,6 +60,14 @@ struct svh_view {
     PinnedBuf<uint8_t> h_rgb;
     PinnedBuf<float4> h_pts;     // host lists on their way to the store
     std::vector<view::Seg> segs;
+    // a thinning's table and scratch (they grow, nothing is allocated per call) and the store the survivors go to
+    HipBuf<unsigned long long> t_keys;
+    HipBuf<uint32_t> t_win, t_slot;
+    HipBuf<uint8_t> t_keep;
+    HipBuf<int32_t> t_blk;
+    HipBuf<int64_t> t_dev;       // the list boundaries, then ThinJob::out
+    PinnedBuf<int64_t> t_host;   // the same layout
+    HipBuf<float4> store2;
 
     int64_t capacity() const { return (int64_t)(store.cap / sizeof(float4)); }
 };
@@ -154,6 +165,71 @@ int render(svh_view* v, uint8_t* rgb, bool rgb_dev) {
     if (!rgb_dev) VIEW_TRY(copy, hipMemcpyAsync(v->h_rgb, v->d_rgb, npix * 3, hipMemcpyDeviceToHost, s));
     VIEW_TRY(wait, hipStreamSynchronize(s));
     if (!rgb_dev) memcpy(rgb, v->h_rgb, npix * 3);
+    return SVH_OK;
+}
+
+// svh_view_thin with arguments that have been checked and a store that is not empty
+int thin_store(svh_view* v, float voxel, svh_view_thin_stats* st) {
+    VIEW_TRY(none, hipSetDevice(v->device));
+    const int64_t n = v->total, room = v->capacity();
+    const size_t nl = v->lens.size(), nbounds = nl + 1, words = nbounds + 2 + nbounds;
+    const uint64_t cap = thin::capacity_for(n);
+    // every allocation before anything is written; the scratch follows the store's capacity, so it grows when that does
+    VIEW_GROW(v->t_keys, (size_t)cap * 8);
+    VIEW_GROW(v->t_win, (size_t)cap * 4);
+    VIEW_GROW(v->t_slot, (size_t)room * 4);
+    VIEW_GROW(v->t_keep, (size_t)room);
+    VIEW_GROW(v->t_blk, (size_t)((room + view::THIN_BLOCK - 1) / view::THIN_BLOCK) * 4);
+    VIEW_GROW(v->t_dev, words * 8);
+    VIEW_GROW(v->t_host, words * 8);
+    VIEW_GROW(v->store2, v->store.cap);
+    hipStream_t s = v->stream;
+    int64_t* const hb = v->t_host;
+    hb[0] = 0;
+    for (size_t k = 0; k < nl; k++) hb[k + 1] = hb[k] + v->lens[k];
+    VIEW_TRY(copy, hipMemsetAsync(v->t_keys, 0xFF, (size_t)cap * 8, s));
+    VIEW_TRY(copy, hipMemsetAsync(v->t_win, 0xFF, (size_t)cap * 4, s));
+    VIEW_TRY(copy, hipMemsetAsync(v->t_dev + nbounds, 0, (2 + nbounds) * 8, s));
+    VIEW_TRY(copy, hipMemcpyAsync(v->t_dev, hb, nbounds * 8, hipMemcpyHostToDevice, s));
+    view::ThinJob j;
+    j.pts = v->store;
+    j.n = (uint32_t)n;
+    j.voxel = voxel;
+    j.keys = v->t_keys;
+    j.win = v->t_win;
+    j.capacity = cap;
+    j.slot = v->t_slot;
+    j.keep = v->t_keep;
+    j.blockcnt = v->t_blk;
+    j.bounds = v->t_dev;
+    j.nbounds = (int32_t)nbounds;
+    j.out = v->t_dev + nbounds;
+    j.dst = v->store2;
+    VIEW_TRY(launch, (view::launch_thin(s, j), hipGetLastError()));
+    VIEW_TRY(copy, hipMemcpyAsync(hb + nbounds, j.out, (2 + nbounds) * 8, hipMemcpyDeviceToHost, s));
+    VIEW_TRY(wait, hipStreamSynchronize(s));
+    // from here on nothing can fail: the survivors become the store
+    const int64_t* out = hb + nbounds;
+    std::swap(v->store, v->store2);
+    for (size_t k = 0; k < nl; k++) v->lens[k] = out[2 + k + 1] - out[2 + k];
+    v->total = out[0];
+    if (st) st->before = n, st->after = out[0], st->unplaced = out[1];
+    return SVH_OK;
+}
+
+// the place of a list in the store (list -1: all of it); false for an index out of range
+bool list_range(const svh_view* v, int32_t list, int64_t* at, int64_t* n) {
+    if (list == -1) return *at = 0, *n = v->total, true;
+    if (list < 0 || (size_t)list >= v->lens.size()) return false;
+    int64_t a = 0;
+    for (int32_t i = 0; i < list; i++) a += v->lens[i];
+    return *at = a, *n = v->lens[list], true;
+}
+
+int get_points(svh_view* v, int64_t at, int64_t n, float* xyzv, bool on_device) {
+    VIEW_TRY(none, hipSetDevice(v->device));
+    VIEW_TRY(copy, hipMemcpyAsync(xyzv, v->store + at, (size_t)n * sizeof(float4), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, v->stream));
+    VIEW_TRY(wait, hipStreamSynchronize(v->stream));
     return SVH_OK;
 }
 
@@ -271,6 +347,45 @@ int64_t svh_view_count(svh_view* v, int32_t what) {
     case 3: return v->capacity();
     default: return 0;
     }
+}
+
+int32_t svh_view_thin(svh_view* v, float voxel, svh_view_thin_stats* stats) {
+    if (!v || !(voxel > 0.f) || !thin::finite_f(voxel)) return svh::fail(SVH_ERR_BAD_ARG, "svh_view_thin: a view and a finite voxel size > 0 are needed");
+    if (v->total == 0) {
+        if (stats) stats->before = stats->after = stats->unplaced = 0;
+        return SVH_OK;
+    }
+    return drained(v, thin_store(v, voxel, stats));
+}
+
+int64_t svh_view_list_len(svh_view* v, int32_t list) {
+    int64_t at, n;
+    if (!v || list < 0 || !list_range(v, list, &at, &n)) return svh::fail(SVH_ERR_BAD_ARG, "svh_view_list_len: no such list");
+    return n;
+}
+
+int64_t svh_view_get_points(svh_view* v, int32_t list, float* xyzv, int64_t cap, int32_t on_device) {
+    int64_t at, n;
+    if (!v || cap < 0 || (cap > 0 && !xyzv)) return svh::fail(SVH_ERR_BAD_ARG, "svh_view_get_points: bad arguments");
+    if (!list_range(v, list, &at, &n)) return svh::fail(SVH_ERR_BAD_ARG, "svh_view_get_points: no such list");
+    const int64_t m = std::min(n, cap);
+    if (m > 0) {
+        const int rc = drained(v, get_points(v, at, m, xyzv, on_device != 0));
+        if (rc) return rc;
+    }
+    return n;
+}
+
+int32_t svh_test_thin_keys(const float* xyzv, int64_t n, float voxel, uint64_t* key, uint32_t* home, uint64_t* capacity) {
+    if (n < 0 || (n > 0 && !xyzv) || !(voxel > 0.f) || !thin::finite_f(voxel)) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_thin_keys: bad arguments");
+    const uint64_t cap = thin::capacity_for(n);
+    if (capacity) *capacity = cap;
+    for (int64_t i = 0; i < n; i++) {
+        const uint64_t k = thin::key_of(xyzv[4 * i], xyzv[4 * i + 1], xyzv[4 * i + 2], voxel);
+        if (key) key[i] = k;
+        if (home) home[i] = k == thin::EMPTY_KEY ? thin::NO_HOME : thin::home_of(k, cap);
+    }
+    return SVH_OK;
 }
 
 int32_t svh_view_render(svh_view* v, uint8_t* rgb, int32_t rgb_on_device) {

@@ -28,6 +28,28 @@ struct RenderJob {
 // hipGetLastError() afterwards
 void launch_render(hipStream_t s, const RenderJob& j);
 
+// One voxel-grid thinning (csrc/view_thin_kernels.hip; the arithmetic is csrc/view_thin_core.h).  The compaction works
+// in blocks of THIN_BLOCK points.
+constexpr uint32_t THIN_BLOCK = 1024;
+struct ThinJob {
+    const float4* pts;          // the store, n points
+    uint32_t n;
+    float voxel;
+    unsigned long long* keys;   // `capacity` slots, all ones
+    uint32_t* win;              // `capacity` slots, all ones: the lowest store index that entered the slot's key
+    uint64_t capacity;          // thin::capacity_for(n)
+    uint32_t* slot;             // n: where a placeable point found its key
+    uint8_t* keep;              // n: 1 survivor, 0 removed (2 between the first two kernels: kept without a voxel)
+    int32_t* blockcnt;          // ceil(n / THIN_BLOCK): survivors per block, then survivors before the block
+    const int64_t* bounds;      // nbounds store positions, ascending, each in [0, n]: the list boundaries
+    int32_t nbounds;
+    int64_t* out;               // [0] survivors, [1] unplaceable points (zero on entry), [2 + k] survivors before bounds[k]
+    float4* dst;                // the second store: the survivors in store order
+};
+// insert, flag + count, scan, scatter, boundaries on stream `s`; the caller has set keys, win and out[1] on that stream
+// and checks hipGetLastError() afterwards
+void launch_thin(hipStream_t s, const ThinJob& j);
+
 }  // namespace view
 }  // namespace svh
 #endif

@@ -23,6 +23,14 @@ class Flags(C.Structure):
     _fields_ = [("show_cams", C.c_int32), ("show_grid", C.c_int32), ("white", C.c_int32)]
 
 
+class ThinStats(C.Structure):
+    """svh_view_thin_stats"""
+    _fields_ = [("before", C.c_int64), ("after", C.c_int64), ("unplaced", C.c_int64)]
+
+    def __repr__(self):
+        return "ThinStats(before=%d, after=%d, unplaced=%d)" % (self.before, self.after, self.unplaced)
+
+
 def _bind():
     L = lib()
     if not getattr(L, "_view_bound", False):
@@ -47,8 +55,27 @@ def _bind():
         L.svh_view_play_poses.restype = C.c_int64
         L.svh_view_play_sequence.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         L.svh_view_play_sequence.restype = C.c_int64
+        L.svh_view_thin.argtypes = [C.c_void_p, C.c_float, C.POINTER(ThinStats)]
+        L.svh_view_get_points.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32]
+        L.svh_view_get_points.restype = C.c_int64
+        L.svh_view_list_len.argtypes = [C.c_void_p, C.c_int32]
+        L.svh_view_list_len.restype = C.c_int64
+        L.svh_test_thin_keys.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L._view_bound = True
     return L
+
+
+def thin_keys(xyzv, voxel):
+    """(key uint64 [n], home uint32 [n], capacity): the thinning's arithmetic (csrc/view_thin_core.h) evaluated on the
+    host for n points -- the library's test entry svh_test_thin_keys; needs no device.  A point that falls into no voxel
+    has the key 2^64 - 1 and the home 2^32 - 1; the homes are those of the table a store of n points gets"""
+    L = _bind()
+    p = np.ascontiguousarray(xyzv, np.float32).reshape(-1, 4)
+    key, home, cap = np.zeros(len(p), np.uint64), np.zeros(len(p), np.uint32), C.c_uint64(0)
+    rc = L.svh_test_thin_keys(p.ctypes.data if len(p) else None, len(p), voxel, key.ctypes.data, home.ctypes.data, C.byref(cap))
+    if rc < 0:
+        raise SvhError(int(rc), last_error())
+    return key, home, int(cap.value)
 
 
 def default_pose():
@@ -144,6 +171,26 @@ class View:
     def clear(self):
         self._L.svh_view_clear(self._h)
 
+    def thin(self, voxel):
+        """keep the first-drawn point of every cube of side `voxel`; ThinStats (before, after, unplaced)"""
+        st = ThinStats()
+        self._check(self._L.svh_view_thin(self._h, voxel, C.byref(st)))
+        return st
+
+    def list_len(self, i):
+        return int(self._check(self._L.svh_view_list_len(self._h, i)))
+
+    def points(self, list=-1, cap=None, device_ptr=None):
+        """the points of one list, or (-1) of the whole store, as [n, 4] float32 (x, y, z, val); at most `cap` of them.
+        With device_ptr they are written there and their number in the list is returned"""
+        n = int(self._check(self._L.svh_view_get_points(self._h, list, None, 0, 0)))
+        m = n if cap is None else min(n, cap)
+        if device_ptr is not None:
+            return int(self._check(self._L.svh_view_get_points(self._h, list, device_ptr, m, 1)))
+        out = np.zeros((m, 4), np.float32)
+        self._check(self._L.svh_view_get_points(self._h, list, out.ctypes.data if m else None, m, 0))
+        return out
+
     def render(self, device_ptr=None):
         """[height, width, 3] uint8, row 0 on top; with device_ptr the image is written there and None returned"""
         if device_ptr is not None:
@@ -183,3 +230,12 @@ def write_ppm(path, img):
     with open(path, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
         f.write(img.tobytes())
+
+
+def write_ply(path, pts):
+    """binary little-endian PLY of [n, 4] float32 points: the float properties x, y, z, val"""
+    pts = np.ascontiguousarray(pts, "<f4").reshape(-1, 4)
+    with open(path, "wb") as f:
+        f.write(b"ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
+                b"property float z\nproperty float val\nend_header\n" % len(pts))
+        f.write(pts.tobytes())

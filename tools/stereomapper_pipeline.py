@@ -13,6 +13,7 @@ without the GUI.  Usage:
 
     python tools/stereomapper_pipeline.py [--unrectified] [--resident] [--normalize] [--render DIR]
                                           [--panes DIR [--pane-size WxH]] [--lockstep K]
+                                          [--thin S [--thin-every N]] [--ply FILE]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -38,6 +39,14 @@ read that one device copy: no download, no second or third upload.  Results are 
 every pair, on the device, in place where ELAS and the visual odometry read them, after the rectification if there is
 one.  The reference has the function and does not call it; neither does this tool without the flag.  Works with
 --resident and --lockstep K (one call for the K pairs).
+
+--thin S: voxel-grid thinning of the accumulated map (svh_view_thin): of the points that fall into one cube of side S
+(metres) the first one drawn stays.  It runs after every N-th append of the map's lists (--thin-every N, default 1) and
+once more at the end, which gives the map that thinning only at the end gives.  With --lockstep K every drive's view is
+thinned.  The per-frame lines are what they are without the flag; one line at the end states the map's size.
+
+--ply FILE: the map at the end (View.points(), after the last thinning if there is one) as a binary little-endian PLY
+with the float properties x y z val; with --lockstep K one file per drive, FILE with _<drive> before its extension.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -85,7 +94,7 @@ class DeviceBuffer:
 
 class Pipeline:
     def __init__(self, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None, view_size=(320, 480),
-                 resident=False, normalize=False):
+                 resident=False, normalize=False, thin=None, thin_every=1):
         import helpers as Hh
         import svhip as S
         from svhip import mapper, view
@@ -100,6 +109,7 @@ class Pipeline:
         self.rect = None
         self.resident = resident
         self.normalize = normalize
+        self.thin, self.thin_every, self.appends = thin, thin_every, 0
         self.histnorm = None   # svhip.histnorm.HistNorm of the frame size, made on the first frame
         self.frame = None      # what render_panes() shows: (I1, I2 or None when resident, w, h, vo ok, ELAS ok)
         self.pane = None
@@ -179,6 +189,9 @@ class Pipeline:
         # maindialog.cpp:602-606: the lists go from the map to the view without leaving the device
         self.view.add_camera(self.H_total, 0.1, True)
         self.view.add_map(self.map)
+        self.appends += 1
+        if self.thin and self.appends % self.thin_every == 0:
+            self.view.thin(self.thin)
         return ok, self.map._L.svh_map_points(self.map._h, 0, None, 0), self.map._L.svh_map_points(self.map._h, 1, None, 0)
 
     def render_panes(self, size=None):
@@ -211,7 +224,7 @@ class LockstepPipeline:
     maps[i], views[i], H_total[i], poses[i]; per drive every result equals that of a resident Pipeline of its own."""
 
     def __init__(self, K, f, cu, cv, base, elas_params=None, max_dist=20.0, rectify_params=None, view_size=(320, 480),
-                 private_rand=None, normalize=False):
+                 private_rand=None, normalize=False, thin=None, thin_every=1):
         import helpers as Hh
         import svhip as S
         from svhip import mapper, view
@@ -226,6 +239,7 @@ class LockstepPipeline:
         self.buf = None
         self.rect = None
         self.normalize = normalize
+        self.thin, self.thin_every, self.appends = thin, thin_every, [0] * K
         self.histnorm = None
         if rectify_params is not None:
             from svhip import rectify
@@ -290,15 +304,31 @@ class LockstepPipeline:
                 continue
             self.views[i].add_camera(self.H_total[i], 0.1, True)
             self.views[i].add_map(self.maps[i])
+            self.appends[i] += 1
+            if self.thin and self.appends[i] % self.thin_every == 0:
+                self.views[i].thin(self.thin)
             m = self.maps[i]
             out.append((oks[i], m._L.svh_map_points(m._h, 0, None, 0), m._L.svh_map_points(m._h, 1, None, 0)))
         return out
 
 
-def main_lockstep(K, drive_dir, calib, limit, rp, normalize=False):
+def finish_map(v, thin, ply, tag=""):
+    """the last thinning and the PLY file of one view; prints the one line --thin / --ply add"""
+    from svhip import view
+    if thin:
+        st = v.thin(thin)
+        print("%smap thinned at %g: %d points of %d left, %d without a voxel" % (tag, thin, st.after, st.before, st.unplaced))
+    if ply:
+        pts = v.points()
+        view.write_ply(ply, pts)
+        print("%smap of %d points in %d lists written to %s" % (tag, len(pts), v.count(view.LISTS), ply))
+
+
+def main_lockstep(K, drive_dir, calib, limit, rp, normalize=False, thin=None, thin_every=1, ply=None):
     import collections
     from svhip import kitti
-    p = LockstepPipeline(K, calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, normalize=normalize)
+    p = LockstepPipeline(K, calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, normalize=normalize, thin=thin,
+                         thin_every=thin_every)
     window = collections.deque(maxlen=K)
     t0 = time.perf_counter()
     steps = 0
@@ -315,6 +345,12 @@ def main_lockstep(K, drive_dir, calib, limit, rp, normalize=False):
     dt = time.perf_counter() - t0
     print("%d steps of %d drives in %.2f s = %.1f frames/s (PNG decode included)" % (
         steps, K, dt, steps * K / max(dt, 1e-9)))
+    for i in range(K):
+        name = None
+        if ply:
+            stem, ext = os.path.splitext(ply)
+            name = "%s_%d%s" % (stem, i, ext)
+        finish_map(p.views[i], thin, name, "[%d] " % i)
 
 
 def main():
@@ -336,6 +372,24 @@ def main():
     normalize = "--normalize" in sys.argv
     if normalize:
         sys.argv.remove("--normalize")
+    thin, thin_every, ply = None, 1, None
+    try:
+        if "--thin" in sys.argv:
+            k = sys.argv.index("--thin")
+            thin = float(sys.argv[k + 1])
+            assert thin > 0 and thin < float("inf")
+            del sys.argv[k:k + 2]
+        if "--thin-every" in sys.argv:
+            k = sys.argv.index("--thin-every")
+            thin_every = int(sys.argv[k + 1])
+            assert thin_every >= 1 and thin
+            del sys.argv[k:k + 2]
+        if "--ply" in sys.argv:
+            k = sys.argv.index("--ply")
+            ply = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+    except (IndexError, ValueError, AssertionError):
+        raise SystemExit(__doc__)
     render_dir = None
     if "--render" in sys.argv:
         k = sys.argv.index("--render")
@@ -370,8 +424,9 @@ def main():
         from svhip import rectify
         rp = rectify.params_from_kitti(calib, 0, 1)
     if lockstep:
-        return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize)
-    p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize)
+        return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
+    p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
+                 thin=thin, thin_every=thin_every)
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -388,6 +443,7 @@ def main():
             break
     dt = time.perf_counter() - t0
     print("%d frames in %.2f s = %.1f frames/s (PNG decode included)" % (frames, dt, frames / max(dt, 1e-9)))
+    finish_map(p.view, thin, ply)
     if render_dir:
         n, images = p.view.record_human()
         for k in range(n):
