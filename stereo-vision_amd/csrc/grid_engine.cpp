@@ -1,0 +1,395 @@
+// The ground grid behind the svh_grid_* entries of include/svh_grid.h: a 2.5-D bird's-eye grid over the road plane, binned
+// on the device from the map view's store or from a list of points.
+//
+// Host (this file): the parameters (T rounded to float once), the two frames, the statistics, the lazy clear and the lazy
+// finalise.  Device (grid_kernels.hip): the binning, the finalise, the render.  The arithmetic is csrc/grid_core.h.  The
+// object has its own stream; every entry returns when it is complete.
+//
+// The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
+// empty, and the next entry that touches the device fills the planes with the empty values first.  That is what makes
+// "after SVH_ERR_HIP inside an add the grid is empty" hold even when the failure was a lost device queue: no HIP call is
+// needed to get there.  The finished planes are derived lazily too, by the first get or render after a change.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "../../include/svh_grid.h"
+#include "grid_core.h"
+#include "grid_internal.h"
+#include "hip_guard.h"
+#include "svh_config.h"
+#include "view_internal.h"
+
+using namespace svh;
+
+namespace {
+
+#define GRID_TRY(kind, expr) SVH_HIP_TRY("Grid", kind, expr)
+#define GRID_GROW(buf, bytes) SVH_HIP_GROW("Grid", buf, bytes)
+
+constexpr int64_t kMaxPoints = ((int64_t)1 << 31) - 1;
+constexpr int64_t kHostChunk = (int64_t)1 << 22;   // points of a host array staged per copy
+constexpr size_t kFinalBytes = 14;                 // per cell: HMIN, HMAX, HMEAN, INTENSITY, CLASS
+
+bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
+// svh_grid_params -> grid::Params; false: out of range
+bool convert(const svh_grid_params* p, grid::Params* q) {
+    if (!p) return false;
+    q->nx = p->nx, q->nz = p->nz;
+    q->cell = p->cell, q->x0 = p->x0, q->z0 = p->z0;
+    for (int k = 0; k < 12; k++) {
+        if (!finite_d(p->T[k])) return false;
+        q->T[k] = (float)p->T[k];
+    }
+    q->min_points = p->min_points;
+    q->step = p->step, q->drop = p->drop, q->clearance = p->clearance;
+    q->h_lo = p->render_h_lo, q->h_hi = p->render_h_hi;
+    return grid::params_ok(*q);
+}
+
+}  // namespace
+
+struct svh_grid {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    grid::Params prm{};
+    size_t ncells = 0;
+    HipBuf<uint8_t> acc;        // CELL_BYTES per cell: kmin | kmax | count | overhead | hsum | vsum, a plane each
+    HipBuf<uint8_t> fin;        // kFinalBytes per cell: hmin | hmax | hmean | intensity | class
+    HipBuf<unsigned long long> d_stats;
+    PinnedBuf<unsigned long long> h_stats;
+    HipBuf<float4> d_pts;       // a host array on its way to the kernel
+    PinnedBuf<float4> h_pts;
+    HipBuf<uint8_t> d_rgb;      // a render bound for the host
+    PinnedBuf<uint8_t> h_out;
+    bool need_clear = true;     // the accumulators do not hold the empty grid yet
+    bool final_valid = false;   // `fin` is derived from the accumulators as they are
+    svh_grid_stats st{0, 0, 0, 0, 0};
+
+    grid::Cells cells() const {
+        uint8_t* b = acc.p;
+        const size_t n = ncells;
+        return grid::Cells{(uint32_t*)b, (uint32_t*)(b + 4 * n), (int32_t*)(b + 8 * n), (int32_t*)(b + 12 * n),
+                           (unsigned long long*)(b + 16 * n), (unsigned long long*)(b + 24 * n)};
+    }
+    float* fplane(int k) const { return (float*)(fin.p + 4 * ncells * (size_t)k); }
+    uint8_t* bplane(int k) const { return fin.p + 12 * ncells + ncells * (size_t)k; }
+};
+
+namespace {
+
+void mark_empty(svh_grid* g) {
+    g->need_clear = true;
+    g->final_valid = false;
+    g->st = svh_grid_stats{0, 0, 0, 0, 0};
+}
+
+// the buffers exist and the accumulators hold what the object says they hold
+int ready(svh_grid* g) {
+    GRID_TRY(none, hipSetDevice(g->device));
+    if (g->acc.cap < g->ncells * grid::CELL_BYTES) g->need_clear = true;
+    GRID_GROW(g->acc, g->ncells * grid::CELL_BYTES);
+    GRID_GROW(g->fin, g->ncells * kFinalBytes);
+    GRID_GROW(g->d_stats, 4 * sizeof(unsigned long long));
+    GRID_GROW(g->h_stats, 4 * sizeof(unsigned long long));
+    if (g->need_clear) {
+        GRID_TRY(copy, hipMemsetAsync(g->acc, 0xFF, 4 * g->ncells, g->stream));
+        GRID_TRY(copy, hipMemsetAsync(g->acc + 4 * g->ncells, 0, (grid::CELL_BYTES - 4) * g->ncells, g->stream));
+        GRID_TRY(copy, hipMemsetAsync(g->d_stats, 0, 4 * sizeof(unsigned long long), g->stream));
+        g->need_clear = false;   // in stream order before whatever the entry does next; every entry ends with a wait
+    }
+    return SVH_OK;
+}
+
+// n > 0 points, host or device, with arguments that have been checked
+int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    g->final_valid = false;
+    grid::BinJob j;
+    j.prm = g->prm;
+    j.cells = g->cells();
+    j.stats = g->d_stats;
+    hipStream_t s = g->stream;
+    if (on_device) {
+        j.pts = (const float4*)xyzv;
+        j.n = n;
+        GRID_TRY(launch, (grid::launch_bin(s, j), hipGetLastError()));
+    } else {
+        const int64_t room = std::min(n, kHostChunk);
+        GRID_GROW(g->h_pts, (size_t)room * sizeof(float4));
+        GRID_GROW(g->d_pts, (size_t)room * sizeof(float4));
+        for (int64_t at = 0; at < n; at += room) {
+            const int64_t m = std::min(room, n - at);
+            if (at > 0) GRID_TRY(wait, hipStreamSynchronize(s));   // the staging buffer is read until here
+            memcpy(g->h_pts, xyzv + 4 * at, (size_t)m * sizeof(float4));
+            GRID_TRY(copy, hipMemcpyAsync(g->d_pts, g->h_pts, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, s));
+            j.pts = g->d_pts;
+            j.n = m;
+            GRID_TRY(launch, (grid::launch_bin(s, j), hipGetLastError()));
+        }
+    }
+    GRID_TRY(copy, hipMemcpyAsync(g->h_stats, g->d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    const unsigned long long* h = g->h_stats;
+    g->st.added += n;
+    g->st.binned = (int64_t)h[grid::LOW], g->st.overhead = (int64_t)h[grid::OVERHEAD];
+    g->st.outside = (int64_t)h[grid::OUTSIDE], g->st.unplaced = (int64_t)h[grid::UNPLACED];
+    return SVH_OK;
+}
+
+// the finished planes, launched on the stream; the caller waits and then sets final_valid
+int finalise(svh_grid* g) {
+    if (g->final_valid) return SVH_OK;
+    grid::FinalJob j;
+    j.prm = g->prm;
+    j.cells = g->cells();
+    j.hmin = g->fplane(0), j.hmax = g->fplane(1), j.hmean = g->fplane(2);
+    j.intensity = g->bplane(0), j.cls = g->bplane(1);
+    GRID_TRY(launch, (grid::launch_finalise(g->stream, j), hipGetLastError()));
+    return SVH_OK;
+}
+
+// `bytes` from device memory `src` to `out` (host or device) and the wait
+int deliver(svh_grid* g, const void* src, size_t bytes, void* out, bool on_device) {
+    hipStream_t s = g->stream;
+    if (on_device) {
+        GRID_TRY(copy, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+    } else {
+        GRID_GROW(g->h_out, bytes);
+        GRID_TRY(copy, hipMemcpyAsync(g->h_out, src, bytes, hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        memcpy(out, g->h_out, bytes);
+    }
+    return SVH_OK;
+}
+
+int get(svh_grid* g, int32_t plane, void* out, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const grid::Cells c = g->cells();
+    const void* src;
+    size_t elem = 4;
+    switch (plane) {
+    case grid::P_COUNT: src = c.count; break;
+    case grid::P_OVERHEAD: src = c.overhead; break;
+    case grid::P_HMIN: src = g->fplane(0); break;
+    case grid::P_HMAX: src = g->fplane(1); break;
+    case grid::P_HMEAN: src = g->fplane(2); break;
+    case grid::P_INTENSITY: src = g->bplane(0), elem = 1; break;
+    default: src = g->bplane(1), elem = 1; break;
+    }
+    const bool derived = plane >= grid::P_HMIN;
+    if (derived && (rc = finalise(g))) return rc;
+    if ((rc = deliver(g, src, g->ncells * elem, out, on_device))) return rc;
+    if (derived) g->final_valid = true;
+    return SVH_OK;
+}
+
+int render(svh_grid* g, int32_t mode, uint8_t* rgb, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const size_t bytes = g->ncells * 3;
+    if (!on_device) {
+        GRID_GROW(g->d_rgb, bytes);
+        GRID_GROW(g->h_out, bytes);
+    }
+    if ((rc = finalise(g))) return rc;
+    grid::RenderJob j;
+    j.prm = g->prm;
+    j.mode = mode;
+    j.count = g->cells().count;
+    j.hmin = g->fplane(0), j.hmax = g->fplane(1), j.hmean = g->fplane(2);
+    j.intensity = g->bplane(0), j.cls = g->bplane(1);
+    j.rgb = on_device ? rgb : g->d_rgb.p;
+    GRID_TRY(launch, (grid::launch_render(g->stream, j), hipGetLastError()));
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+        return rc;
+    }
+    g->final_valid = true;
+    return SVH_OK;
+}
+
+// nothing of a failed call is in flight when the caller goes on
+int drained(svh_grid* g, int rc) {
+    if (rc == SVH_ERR_HIP && g->stream) {
+        (void)hipSetDevice(g->device);
+        (void)hipStreamSynchronize(g->stream);
+    }
+    return rc;
+}
+
+// ... and a failed add leaves the empty grid
+int added(svh_grid* g, int rc) {
+    if (rc == SVH_ERR_HIP) {
+        drained(g, rc);
+        mark_empty(g);
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t svh_grid_frame_camera(double cam_height, double T[12]) {
+    if (!T || !finite_d(cam_height)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_frame_camera: a finite height and T are needed");
+    const double t[12] = {1, 0, 0, 0, 0, 0, 1, 0, 0, -1, 0, cam_height};
+    memcpy(T, t, sizeof(t));
+    return SVH_OK;
+}
+
+int32_t svh_grid_frame_plane(const double plane_e[3], const double H[16], double T[12]) {
+    if (!plane_e || !H || !T) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_frame_plane: null argument");
+    for (int k = 0; k < 3; k++)
+        if (!finite_d(plane_e[k])) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_frame_plane: the plane is not finite");
+    for (int k = 0; k < 16; k++)
+        if (!finite_d(H[k])) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_frame_plane: the transformation is not finite");
+    const double norm = sqrt((plane_e[0] * plane_e[0] + plane_e[1] * plane_e[1]) + plane_e[2] * plane_e[2]);
+    if (!(norm > 0.0) || !finite_d(norm) || !finite_d(1.0 / norm))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_frame_plane: |e| == 0, the estimate found no plane");
+    for (int k = 0; k < 3; k++) {
+        T[k] = H[4 * k];                 // r1, the first column of H
+        T[4 + k] = H[4 * k + 2];         // r3, the third
+        T[8 + k] = -(plane_e[k] / norm); // -r2
+    }
+    T[3] = 0.0, T[7] = 0.0, T[11] = 1.0 / norm;
+    return SVH_OK;
+}
+
+void svh_grid_params_default(svh_grid_params* p) {
+    if (!p) return;
+    p->nx = 256, p->nz = 256;
+    p->cell = 0.2f, p->x0 = -25.6f, p->z0 = 0.f;
+    (void)svh_grid_frame_camera(1.65, p->T);
+    p->min_points = 3;
+    p->step = 0.2f, p->drop = 0.3f, p->clearance = 2.0f;
+    p->render_h_lo = 0.f, p->render_h_hi = 2.f;
+}
+
+svh_grid* svh_grid_create(const svh_grid_params* p) {
+    svh::ensure_init();
+    grid::Params q;
+    if (!convert(p, &q)) {
+        svh::fail(SVH_ERR_BAD_ARG, "svh_grid_create: parameters out of range (include/svh_grid.h)");
+        return nullptr;
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
+        svh::fail(SVH_ERR_NO_DEVICE, "no HIP device visible: libsvhip has no CPU fallback");
+        return nullptr;
+    }
+    svh_grid* g = new svh_grid();
+    g->prm = q;
+    g->ncells = (size_t)q.nx * (size_t)q.nz;
+    (void)hipGetDevice(&g->device);
+    if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete g;
+        svh::fail(SVH_ERR_HIP, "svh_grid_create: hipStreamCreateWithFlags failed");
+        return nullptr;
+    }
+    return g;
+}
+
+void svh_grid_destroy(svh_grid* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    const hipStream_t s = g->stream;
+    if (s) (void)hipStreamSynchronize(s);
+    delete g;   // the buffers free themselves, on the device selected above
+    if (s) (void)hipStreamDestroy(s);
+}
+
+int32_t svh_grid_clear(svh_grid* g) {
+    if (!g) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_clear: null argument");
+    mark_empty(g);
+    return SVH_OK;
+}
+
+int32_t svh_grid_set_window(svh_grid* g, float x0, float z0) {
+    if (!g || !grid::finite_f(x0) || !grid::finite_f(z0)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_window: a grid and a finite corner are needed");
+    g->prm.x0 = x0, g->prm.z0 = z0;
+    mark_empty(g);
+    return SVH_OK;
+}
+
+int32_t svh_grid_add_points(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device) {
+    if (!g || n < 0 || (n > 0 && !xyzv)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_points: bad arguments");
+    if (on_device && ((uintptr_t)xyzv & 15)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_points: a device array must be 16-byte aligned");
+    if (n > kMaxPoints - g->st.added) return svh::fail(SVH_ERR_UNSUPPORTED, "svh_grid_add_points: more than 2^31 - 1 points since the last clear");
+    if (n == 0) return SVH_OK;
+    return added(g, add(g, xyzv, n, on_device != 0));
+}
+
+int32_t svh_grid_add_view(svh_grid* g, svh_view* v) {
+    if (!g || !v) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_view: null argument");
+    const view::StoreRef r = view::store_of(v);
+    if (r.device != g->device) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_view: the view lives on another device");
+    if (r.n > kMaxPoints - g->st.added) return svh::fail(SVH_ERR_UNSUPPORTED, "svh_grid_add_view: more than 2^31 - 1 points since the last clear");
+    if (r.n == 0) return SVH_OK;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipSetDevice(g->device));
+        GRID_TRY(wait, hipStreamSynchronize(r.stream));   // the store is complete before this stream reads it
+        return add(g, (const float*)r.pts, r.n, true);
+    }();
+    return added(g, rc);
+}
+
+int32_t svh_grid_get_stats(svh_grid* g, svh_grid_stats* stats) {
+    if (!g || !stats) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_stats: null argument");
+    *stats = g->st;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::P_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get: a grid, a plane 0..6 and an output are needed");
+    return drained(g, get(g, plane, out, on_device != 0));
+}
+
+int32_t svh_grid_render(svh_grid* g, int32_t mode, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb || mode < 0 || mode >= grid::M_MODES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render: a grid, a mode 0..2 and an output are needed");
+    return drained(g, render(g, mode, rgb, on_device != 0));
+}
+
+int32_t svh_test_grid_points(const svh_grid_params* p, const float* xyzv, int64_t n, int32_t* fate, uint32_t* cell,
+                             uint32_t* key, int32_t* q, uint8_t* v) {
+    grid::Params prm;
+    if (!convert(p, &prm) || n < 0 || (n > 0 && !xyzv)) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_points: bad arguments");
+    for (int64_t i = 0; i < n; i++) {
+        const grid::Placed r = grid::place(prm, xyzv[4 * i], xyzv[4 * i + 1], xyzv[4 * i + 2], xyzv[4 * i + 3]);
+        if (fate) fate[i] = r.fate;
+        if (cell) cell[i] = r.cell;
+        if (key) key[i] = r.key;
+        if (q) q[i] = r.q;
+        if (v) v[i] = (uint8_t)r.v;
+    }
+    return SVH_OK;
+}
+
+int32_t svh_test_grid_finalise(const svh_grid_params* p, int64_t ncells, const int32_t* count, const int32_t* overhead,
+                               const uint32_t* kmin, const uint32_t* kmax, const int64_t* hsum, const uint64_t* vsum,
+                               float* hmin, float* hmax, float* hmean, uint8_t* intensity, uint8_t* cls, uint8_t* rgb) {
+    grid::Params prm;
+    if (!convert(p, &prm) || ncells < 0 || (ncells > 0 && (!count || !overhead || !kmin || !kmax || !hsum || !vsum)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_finalise: bad arguments");
+    for (int64_t i = 0; i < ncells; i++) {
+        const grid::Cell c{count[i], overhead[i], kmin[i], kmax[i], hsum[i], vsum[i]};
+        const grid::Final f = grid::finalise(prm, c);
+        if (hmin) hmin[i] = f.hmin;
+        if (hmax) hmax[i] = f.hmax;
+        if (hmean) hmean[i] = f.hmean;
+        if (intensity) intensity[i] = f.intensity;
+        if (cls) cls[i] = f.cls;
+        if (rgb)
+            for (int32_t m = 0; m < grid::M_MODES; m++) grid::colour(prm, m, c.count, f, rgb + 9 * i + 3 * m);
+    }
+    return SVH_OK;
+}
+
+}  // extern "C"

@@ -120,6 +120,20 @@ extern "C" float svh_test_matcher_gain(svh_matcher* m, const svh_p_match* matche
 // point; *capacity = that table's slots.  Any of the three outputs may be NULL
 extern "C" int32_t svh_test_thin_keys(const float* xyzv, int64_t n, float voxel, uint64_t* key, uint32_t* home,
                                       uint64_t* capacity);
+// TEST ACCESS to the arithmetic of the ground grid (grid_engine.cpp), bound by name like the hook above; host code, needs
+// no device: csrc/grid_core.h evaluated with the parameters `p` (checked as svh_grid_create checks them).
+//   svh_test_grid_points    per point (x, y, z, val): fate (0 low, 1 overhead, 2 outside, 3 unplaced), cell = ib * nx + ia
+//                           (all ones when outside or unplaced) and, for a low point (else 0), the key of its height, the
+//                           height in 1/1024 and the intensity byte.  Any output may be NULL
+//   svh_test_grid_finalise  per accumulated cell: HMIN, HMAX, HMEAN, INTENSITY, CLASS and rgb[9] = its colour in the modes
+//                           class, height, intensity.  Any output may be NULL
+struct svh_grid_params;
+extern "C" int32_t svh_test_grid_points(const svh_grid_params* p, const float* xyzv, int64_t n, int32_t* fate, uint32_t* cell,
+                                        uint32_t* key, int32_t* q, uint8_t* v);
+extern "C" int32_t svh_test_grid_finalise(const svh_grid_params* p, int64_t ncells, const int32_t* count,
+                                          const int32_t* overhead, const uint32_t* kmin, const uint32_t* kmax,
+                                          const int64_t* hsum, const uint64_t* vsum, float* hmin, float* hmax, float* hmean,
+                                          uint8_t* intensity, uint8_t* cls, uint8_t* rgb);
 
 // The guard of every HIP call of the host engines: `kind` is one of none, malloc, copy, launch, wait (see above); a
 // disarmed hook costs one relaxed load.  Returns hip_failed(...) out of the enclosing function on failure.

@@ -246,6 +246,8 @@ view::Pose to_pose(const svh_view_pose& p) { return view::Pose{p.zoom, p.rotx, p
 
 }  // namespace
 
+svh::view::StoreRef svh::view::store_of(const svh_view* v) { return StoreRef{v->store.p, v->total, v->device, v->stream}; }
+
 extern "C" {
 
 void svh_view_pose_default(svh_view_pose* p) {

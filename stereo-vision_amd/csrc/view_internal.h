@@ -7,8 +7,21 @@
 
 #include "view_core.h"
 
+struct svh_view;
+
 namespace svh {
 namespace view {
+
+// The point store of a view as it lies on the device, for a consumer inside the library (csrc/grid_engine.cpp): `n` points
+// (x, y, z, val), the lists back to back.  Every entry of the view returns when it is complete; a reader on another
+// stream waits on `stream` first.  Valid until the next call that changes the view.
+struct StoreRef {
+    const float4* pts;
+    int64_t n;
+    int device;
+    hipStream_t stream;
+};
+StoreRef store_of(const svh_view* v);
 
 struct RenderJob {
     Frame frame;

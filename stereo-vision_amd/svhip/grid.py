@@ -1,0 +1,204 @@
+"""ctypes binding of the ground grid in libsvhip.so (C-ABI: include/svh_grid.h): a 2.5-D bird's-eye grid over the road
+plane -- per cell how many points, how high, how bright, drivable or not -- binned on the device from the map view's store
+or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h."""
+import ctypes as C
+
+import numpy as np
+
+from . import ERR_BAD_ARG, SvhError, last_error, lib
+
+COUNT, OVERHEAD, HMIN, HMAX, HMEAN, INTENSITY, CLASS = range(7)
+RENDER_CLASS, RENDER_HEIGHT, RENDER_INTENSITY = range(3)
+UNKNOWN, FREE, OBSTACLE, DROP, OVERHANG = 0, 1, 2, 3, 0x80
+LOW, FATE_OVERHEAD, OUTSIDE, UNPLACED = range(4)
+PLANE_DTYPE = [np.int32, np.int32, np.float32, np.float32, np.float32, np.uint8, np.uint8]
+
+
+class Params(C.Structure):
+    """svh_grid_params"""
+    _fields_ = [("nx", C.c_int32), ("nz", C.c_int32), ("cell", C.c_float), ("x0", C.c_float), ("z0", C.c_float),
+                ("T", C.c_double * 12), ("min_points", C.c_int32), ("step", C.c_float), ("drop", C.c_float),
+                ("clearance", C.c_float), ("render_h_lo", C.c_float), ("render_h_hi", C.c_float)]
+
+    def copy(self, **kw):
+        q = Params.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            if k == "T":
+                q.T = (C.c_double * 12)(*np.asarray(v, np.float64).ravel())
+            else:
+                setattr(q, k, v)
+        return q
+
+
+class Stats(C.Structure):
+    """svh_grid_stats"""
+    _fields_ = [("added", C.c_int64), ("binned", C.c_int64), ("overhead", C.c_int64), ("outside", C.c_int64),
+                ("unplaced", C.c_int64)]
+
+    def asdict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+    def __repr__(self):
+        return "Stats(%s)" % ", ".join("%s=%d" % kv for kv in self.asdict().items())
+
+
+def _bind():
+    L = lib()
+    if not getattr(L, "_grid_bound", False):
+        L.svh_grid_params_default.argtypes = [C.POINTER(Params)]
+        L.svh_grid_params_default.restype = None
+        L.svh_grid_frame_camera.argtypes = [C.c_double, C.c_void_p]
+        L.svh_grid_frame_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svh_grid_create.restype = C.c_void_p
+        L.svh_grid_create.argtypes = [C.POINTER(Params)]
+        L.svh_grid_destroy.argtypes = [C.c_void_p]
+        L.svh_grid_destroy.restype = None
+        L.svh_grid_clear.argtypes = [C.c_void_p]
+        L.svh_grid_set_window.argtypes = [C.c_void_p, C.c_float, C.c_float]
+        L.svh_grid_add_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+        L.svh_grid_add_view.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
+        L.svh_grid_get.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_render.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_test_grid_points.argtypes = [C.POINTER(Params), C.c_void_p, C.c_int64] + [C.c_void_p] * 5
+        L.svh_test_grid_finalise.argtypes = [C.POINTER(Params), C.c_int64] + [C.c_void_p] * 12
+        L._grid_bound = True
+    return L
+
+
+def _check(rc):
+    if rc < 0:
+        raise SvhError(int(rc), last_error())
+    return rc
+
+
+def default_params(**kw):
+    p = Params()
+    _bind().svh_grid_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def frame_camera(cam_height):
+    """T [3, 4] of a level camera cam_height above the road: a = x, b = z, h = cam_height - y"""
+    T = np.zeros((3, 4), np.float64)
+    _check(_bind().svh_grid_frame_camera(cam_height, T.ctypes.data))
+    return T
+
+
+def frame_plane(plane_e, H):
+    """T [3, 4] from PlaneEstimation's plane_euclidean() and transformation(); SvhError when no plane was found"""
+    e = np.ascontiguousarray(plane_e, np.float64).reshape(3)
+    Hm = np.ascontiguousarray(H, np.float64).reshape(16)
+    T = np.zeros((3, 4), np.float64)
+    _check(_bind().svh_grid_frame_plane(e.ctypes.data, Hm.ctypes.data, T.ctypes.data))
+    return T
+
+
+def core_points(params, xyzv):
+    """csrc/grid_core.h on the host (svh_test_grid_points): (fate int32, cell uint32, key uint32, q int32, v uint8) per
+    point; needs no device"""
+    p = np.ascontiguousarray(xyzv, np.float32).reshape(-1, 4)
+    n = len(p)
+    out = (np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n, np.uint8))
+    _check(_bind().svh_test_grid_points(C.byref(params), p.ctypes.data if n else None, n, *[a.ctypes.data for a in out]))
+    return out
+
+
+def core_finalise(params, count, overhead, kmin, kmax, hsum, vsum):
+    """csrc/grid_core.h on the host (svh_test_grid_finalise): (hmin, hmax, hmean, intensity, class, rgb [n, 3, 3]) per
+    accumulated cell; needs no device"""
+    ins = [np.ascontiguousarray(a, t).ravel() for a, t in ((count, np.int32), (overhead, np.int32), (kmin, np.uint32),
+                                                            (kmax, np.uint32), (hsum, np.int64), (vsum, np.uint64))]
+    n = len(ins[0])
+    out = [np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8),
+           np.zeros(n, np.uint8), np.zeros((n, 3, 3), np.uint8)]
+    _check(_bind().svh_test_grid_finalise(C.byref(params), n, *[a.ctypes.data for a in ins + out]))
+    return tuple(out)
+
+
+
+
+class Grid:
+    """g = Grid(params); g.add_view(view) or g.add_points(xyzv); g.plane(CLASS); img = g.render(RENDER_CLASS)"""
+
+    def __init__(self, params=None, **kw):
+        self._L = _bind()
+        self.params = (params if params is not None else default_params()).copy(**kw)
+        self._h = self._L.svh_grid_create(C.byref(self.params))
+        if not self._h:
+            raise SvhError(ERR_BAD_ARG, last_error())
+        self.nx, self.nz = self.params.nx, self.params.nz
+
+    def clear(self):
+        _check(self._L.svh_grid_clear(self._h))
+
+    def set_window(self, x0, z0):
+        _check(self._L.svh_grid_set_window(self._h, x0, z0))
+        self.params.x0, self.params.z0 = x0, z0
+
+    def add_points(self, xyzv):
+        """[n, 4] float32 (x, y, z, val) on the host"""
+        p = np.ascontiguousarray(xyzv, np.float32).reshape(-1, 4)
+        _check(self._L.svh_grid_add_points(self._h, p.ctypes.data if len(p) else None, len(p), 0))
+
+    def add_points_device(self, ptr, n):
+        """the same from a raw device address (int), 16-byte aligned"""
+        _check(self._L.svh_grid_add_points(self._h, ptr, n, 1))
+
+    def add_view(self, view):
+        """the whole store of a svhip.view.View, device to device"""
+        _check(self._L.svh_grid_add_view(self._h, view._h))
+
+    def stats(self):
+        st = Stats()
+        _check(self._L.svh_grid_get_stats(self._h, C.byref(st)))
+        return st
+
+    def plane(self, which, device_ptr=None):
+        """[nz, nx] of the plane's type; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get(self._h, which, device_ptr, 1))
+            return None
+        if not 0 <= which < len(PLANE_DTYPE):
+            raise SvhError(ERR_BAD_ARG, "no such plane")
+        out = np.zeros((self.nz, self.nx), PLANE_DTYPE[which])
+        _check(self._L.svh_grid_get(self._h, which, out.ctypes.data, 0))
+        return out
+
+    def count(self):
+        return self.plane(COUNT)
+
+    def overhead(self):
+        return self.plane(OVERHEAD)
+
+    def hmin(self):
+        return self.plane(HMIN)
+
+    def hmax(self):
+        return self.plane(HMAX)
+
+    def hmean(self):
+        return self.plane(HMEAN)
+
+    def intensity(self):
+        return self.plane(INTENSITY)
+
+    def classes(self):
+        return self.plane(CLASS)
+
+    def render(self, mode=RENDER_CLASS, device_ptr=None):
+        """[nz, nx, 3] uint8, row 0 the farthest; with device_ptr the image is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render(self._h, mode, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render(self._h, mode, img.ctypes.data, 0))
+        return img
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.svh_grid_destroy(h)
+
+    def __del__(self):
+        self.close()

@@ -14,6 +14,7 @@ without the GUI.  Usage:
     python tools/stereomapper_pipeline.py [--unrectified] [--resident] [--normalize] [--render DIR]
                                           [--panes DIR [--pane-size WxH]] [--lockstep K]
                                           [--thin S [--thin-every N]] [--ply FILE]
+                                          [--grid DIR [--grid-cell S] [--grid-size NXxNZ] [--level]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -47,6 +48,15 @@ thinned.  The per-frame lines are what they are without the flag; one line at th
 
 --ply FILE: the map at the end (View.points(), after the last thinning if there is one) as a binary little-endian PLY
 with the float properties x y z val; with --lockstep K one file per drive, FILE with _<drive> before its extension.
+
+--grid DIR: the ground grid (include/svh_grid.h) after every frame into DIR/grid_%06d.ppm, forward up: unknown cells dark
+grey, free cells green by their intensity, obstacles red, drops blue, cells under an overhang with a full blue byte.  The
+map fusion revises the store, so the grid is cleared and rebuilt from the view's whole store (svh_grid_add_view, device to
+device) instead of accumulating.  --grid-cell S: the side of a cell in metres (0.2); --grid-size NXxNZ: cells across and
+along (256x256); the window is centred on the first camera and starts at it.  The frame is that of a level camera 1.65 m
+above the road unless --level is given: then the road plane is estimated once, from the first frame's D1 on the device
+(include/svh_plane.h), and levels the grid (svh_grid_frame_plane); if that estimate finds no plane the tool says so and
+falls back to the level camera.  The per-frame lines are what they are without the flag.  Not with --lockstep.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -111,12 +121,45 @@ class Pipeline:
         self.normalize = normalize
         self.thin, self.thin_every, self.appends = thin, thin_every, 0
         self.histnorm = None   # svhip.histnorm.HistNorm of the frame size, made on the first frame
+        self.grid = None       # svhip.grid.Grid once enable_grid() has been called
+        self.grid_level = False
+        self.grid_note = None
         self.frame = None      # what render_panes() shows: (I1, I2 or None when resident, w, h, vo ok, ELAS ok)
         self.pane = None
         if rectify_params is not None:
             from svhip import rectify
             self.rect = rectify.Rectifier(rectify_params)
             self.raw = None
+
+    def enable_grid(self, cell=0.2, size=(256, 256), level=False):
+        """a ground grid of size = (nx, nz) cells of side `cell`, centred on the first camera and starting at it;
+        level: the road plane of the first frame's D1 levels it (else a level camera 1.65 m above the road)"""
+        from svhip import grid
+        self.grid_kw = dict(nx=size[0], nz=size[1], cell=cell, x0=-0.5 * size[0] * cell, z0=0.0)
+        self.grid = grid.Grid(grid.default_params(**self.grid_kw))
+        self.grid_level = level
+
+    def level_grid(self, dD1, w, h):
+        """the road plane of this frame's D1 (on the device) becomes the grid's frame; the note says what happened"""
+        from svhip import grid
+        self.grid_level = False
+        c = self.vo.params
+        pe = self.S.PlaneEstimation()
+        status = pe.estimate(dD1, w, h, w, f=c.f, cu=c.cu, cv=c.cv, base=c.base, seed=0)
+        try:
+            T = grid.frame_plane(pe.plane_euclidean(), pe.transformation())
+        except self.S.SvhError:
+            self.grid_note = "grid: the road plane estimate found no plane (status %d): falls back to frame_camera(1.65)" % status
+            return
+        self.grid = grid.Grid(grid.default_params(T=T, **self.grid_kw))
+        self.grid_note = "grid levelled by the road plane of frame 0: camera %.3f m above the road, pitch %.4f rad" % (
+            T[2, 3], float(pe.pitch()))
+
+    def render_grid(self):
+        """the grid of the view's store as it is now, rebuilt: [nz, nx, 3] uint8, forward up"""
+        self.grid.clear()
+        self.grid.add_view(self.view)
+        return self.grid.render()
 
     def push(self, I1, I2):
         """one stereo frame; returns (vo_ok, points_prev, points_curr)"""
@@ -181,6 +224,8 @@ class Pipeline:
         self.frame = (None, None, w, h, ok, st[0] == 0) if self.resident else (I1, I2, w, h, ok, st[0] == 0)
         if st[0] != 0:
             return ok, 0, 0
+        if self.grid is not None and self.grid_level:
+            self.level_grid(dD1.ptr.value, w, h)
         # stereothread.cpp:166-170
         if self.resident:
             resident.map_add(self.map, dD1.ptr.value, dI1.ptr.value, w, h, self.H_total, gain, pitch=w)
@@ -373,7 +418,27 @@ def main():
     if normalize:
         sys.argv.remove("--normalize")
     thin, thin_every, ply = None, 1, None
+    grid_dir, grid_cell, grid_size = None, 0.2, (256, 256)
+    level = "--level" in sys.argv
+    if level:
+        sys.argv.remove("--level")
     try:
+        if "--grid-cell" in sys.argv:
+            k = sys.argv.index("--grid-cell")
+            grid_cell = float(sys.argv[k + 1])
+            assert grid_cell > 0 and grid_cell < float("inf")
+            del sys.argv[k:k + 2]
+        if "--grid-size" in sys.argv:
+            k = sys.argv.index("--grid-size")
+            grid_size = tuple(int(v) for v in sys.argv[k + 1].lower().split("x"))
+            assert len(grid_size) == 2 and all(1 <= v <= 8192 for v in grid_size)
+            del sys.argv[k:k + 2]
+        if "--grid" in sys.argv:
+            k = sys.argv.index("--grid")
+            grid_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        assert grid_dir or not level
+        assert not (grid_dir and lockstep)
         if "--thin" in sys.argv:
             k = sys.argv.index("--thin")
             thin = float(sys.argv[k + 1])
@@ -423,10 +488,14 @@ def main():
     if unrectified:
         from svhip import rectify
         rp = rectify.params_from_kitti(calib, 0, 1)
+    if grid_dir:
+        os.makedirs(grid_dir, exist_ok=True)
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
                  thin=thin, thin_every=thin_every)
+    if grid_dir:
+        p.enable_grid(grid_cell, grid_size, level)
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -439,11 +508,19 @@ def main():
         if panes_dir:
             for name, img in zip(("left", "right", "disp"), p.render_panes(pane_size)):
                 view.write_ppm(os.path.join(panes_dir, "%s_%06d.ppm" % (name, frames - 1)), img)
+        if grid_dir:
+            view.write_ppm(os.path.join(grid_dir, "grid_%06d.ppm" % (frames - 1)), p.render_grid())
         if frames >= limit:
             break
     dt = time.perf_counter() - t0
     print("%d frames in %.2f s = %.1f frames/s (PNG decode included)" % (frames, dt, frames / max(dt, 1e-9)))
     finish_map(p.view, thin, ply)
+    if grid_dir:
+        if p.grid_note:
+            print(p.grid_note)
+        st = p.grid.stats()
+        print("grid %d x %d cells of %g: %d of %d points binned, %d overhead, %d outside, %d unplaced; %d images in %s" % (
+            p.grid.nx, p.grid.nz, grid_cell, st.binned, st.added, st.overhead, st.outside, st.unplaced, frames, grid_dir))
     if render_dir:
         n, images = p.view.record_human()
         for k in range(n):
