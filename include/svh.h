@@ -172,6 +172,7 @@ typedef struct svh_elas svh_elas;
  *                          profiles/r05_delaunay_scalar_walk.txt)
  *   SVH_DESC_FLY_KEYED=0   subsampling / disp_max > 255 keep the stored descriptor maps
  *   SVH_HW_QUEUES=n        the count svh_init asks for when svh_config::hw_queues is 0 (default 20); 0: hands off
+ *   SVH_QUEUE_PLAN=n       the queue plan lanes are built with (0..4, see svh_elas_set_queue_plan; default: automatic)
  *   SVH_MATCH_WIDE768=0    rows of 1281-1920 px: 512-thread blocks (8 pixels per thread) in k_match_list instead of 768
  *   SVH_GAP_SEQ=1          wide interpolation gaps / add_corners: one thread per line (k_gap_lines) instead of the
  *                          per-row scan and the segmented column pass
@@ -310,6 +311,28 @@ int64_t svh_elas_trim(void);
 /* number of batch workers the engine runs per device (default 6; each is double-buffered: two HIP
  * streams and buffer sets, the host stage of one group overlaps the device stages of the next) */
 int32_t svh_elas_set_lanes(int32_t lanes);
+/* Queue plan: how a lane spreads the phases of a pipelined group over HIP streams of different priority classes.
+ * The runtime's cap on hardware queues (svh_config::hw_queues above, GPU_MAX_HW_QUEUES) holds per priority class,
+ * so a host program that cannot raise it -- the runtime was up before svh_init -- can still give the engine queues
+ * beyond it: streams created in the low and high classes draw from pools of their own.
+ *   -1  automatic (default): plan 0 where the cap (read from GPU_MAX_HW_QUEUES, unset = 4) provides a queue per lane
+ *       stream (2 x workers), else the layout the project's A/B kept ("Queue plans")
+ *    0  one normal-priority stream per lane
+ *    1  the stage chain (k_lattice_count .. k_stage_pack) on a high-priority stream of the lane
+ *    2  plan 1, and the main stream of every worker's second lane in the low class
+ *    3  by phase, the same for every lane: Sobel + support normal, stage chain high, planes .. mean low
+ *    4  every group on one stream; the stream of every worker's second lane is in the low class (what automatic
+ *       mode takes at a short cap: the only layout that measured faster than plan 0, +2.8 % at a cap of 4)
+ * Plans 1 to 3 measured 3 to 27 % slower than plan 0 and are kept only so that the A/B can be repeated.
+ * A device without three priority levels folds the missing classes into normal; a plan that would hold more than 12
+ * hardware queues at the cap in force becomes plan 0.  Single calls, batches of one group, tapping runs and groups
+ * on the host stage use one stream whatever the plan.  The setting belongs to the calling thread's device
+ * (svh_set_device); lanes are built with it when they are created -- from the cap and the worker count
+ * (svh_elas_set_lanes) of that moment -- so a change of either takes effect after svh_elas_trim().
+ * The process default can be overridden with SVH_QUEUE_PLAN=n.  set returns the value stored.  get reports what a
+ * lane created now gets: the plan in effect, the streams of a lane and the priority classes in use. */
+int32_t svh_elas_set_queue_plan(int32_t plan);
+int32_t svh_elas_get_queue_plan(int32_t* plan, int32_t* streams_per_lane, int32_t* classes);
 /* pairs a lane pushes through each kernel launch (1..32; default 32 for images up to ~1
  * Mpixel, proportionally fewer for larger ones -- 16 at 1920x1080 -- until this is called):
  * batches are cut into groups of this many consecutive pairs */

@@ -12,7 +12,8 @@
 //                    labelling, gap interpolation + adaptive mean tile kernels (or the
 //                    unfused kernels / median)  ->  D1, D2
 //
-// A "lane" owns one HIP stream, its device buffers (sized once per image
+// A "lane" owns one HIP stream (or, by its queue plan, one per stream priority
+// class it uses: queue_plan.h), its device buffers (sized once per image
 // geometry and reused: callers construct an Elas per frame,
 // stereomapper/stereothread.cpp:113) and its pinned staging.  A single
 // svh_elas_process() borrows a lane on the calling thread.  A batch runs G pairs
@@ -40,6 +41,7 @@
 #include <vector>
 
 #include "hip_guard.h"
+#include "queue_plan.h"
 #include "svh_internal.h"
 
 namespace svh {
@@ -103,6 +105,22 @@ struct EventProfiler : Profiler {
     }
 };
 
+// the timer as one phase of a group sees it: its events go onto the stream that phase's kernels are launched on
+struct PhaseProfiler : Profiler {
+    EventProfiler* to;
+    hipStream_t stream;
+    PhaseProfiler(EventProfiler* t, hipStream_t s) : to(t), stream(s) {}
+    void begin(const char* kernel) override {
+        to->stream = stream;
+        to->begin(kernel);
+    }
+    void end() override { to->end(); }
+};
+
+// settings the lanes' queue plan is made from (defined with the other engine settings below)
+static int queue_cap();
+static int worker_count();
+
 // ---------------------------------------------------------------------------
 // lane: stream + buffers for a group of up to `gcap` pairs
 // ---------------------------------------------------------------------------
@@ -134,7 +152,19 @@ struct LaneBufs {
 struct Lane : LaneBufs {
     EventProfiler prof;
     int device = 0;
-    hipStream_t stream = nullptr;
+    // Streams (queue_plan.h): one per priority class the lane's phases use, created on first use.  `stream` is the main
+    // stream -- phase A, the copies, and the one every other stream is joined into before a group ends, so lane_wait,
+    // the early-D2 copy and copy_out order as they did with one stream; `stage_stream` runs the stage chain and
+    // `post_stream` phase B (either may be `stream` itself).
+    hipStream_t stream = nullptr, stage_stream = nullptr, post_stream = nullptr;
+    hipStream_t cls_stream[QC_COUNT] = {nullptr, nullptr, nullptr};
+    int plan_req = QP_AUTO;         // the pool's setting when the lane was created (svh_elas_set_queue_plan)
+    int parity = 0;                 // first / second lane of its worker (set by acquire_lanes)
+    bool qp_known = false;
+    QueuePlan qp{};
+    int prio_least = 0, prio_greatest = 0;
+    bool split = false;             // the group in flight runs its phases on more than one stream
+    hipEvent_t a_ev = nullptr, b_ev = nullptr;   // k_support done (main stream), phase B done (post_stream)
     hipEvent_t wait_ev = nullptr;   // completion marker polled by lane_wait
     hipStream_t copy_stream = nullptr;   // early D2H of maps that are final before the stream is done
     hipEvent_t match_ev = nullptr, copy_ev = nullptr;
@@ -180,10 +210,11 @@ struct Lane : LaneBufs {
 
     // everything the lane holds, streams and events included (svh_elas_trim)
     void destroy() {
-        if (!stream) return;
+        // (by the class streams, not `stream`: a bind_streams that failed half way has created some and bound none)
+        if (!cls_stream[QC_NORMAL] && !cls_stream[QC_HIGH] && !cls_stream[QC_LOW]) return;
         (void)hipSetDevice(device);
         release();
-        for (hipEvent_t* e : {&wait_ev, &match_ev, &copy_ev, &stage_ev})
+        for (hipEvent_t* e : {&wait_ev, &match_ev, &copy_ev, &stage_ev, &a_ev, &b_ev})
             if (*e) {
                 (void)hipEventDestroy(*e);
                 *e = nullptr;
@@ -192,22 +223,51 @@ struct Lane : LaneBufs {
         prof.ev.clear();
         prof.names.clear();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        (void)hipStreamDestroy(stream);
-        copy_stream = stream = nullptr;
+        for (hipStream_t& cs : cls_stream)
+            if (cs) {
+                (void)hipStreamDestroy(cs);
+                cs = nullptr;
+            }
+        copy_stream = stream = stage_stream = post_stream = nullptr;
+    }
+
+    // the streams of the lane's plan for its parity.  The plan is fixed by the lane's first use, from the cap and the
+    // worker count of that moment: a later svh_elas_set_lanes reaches the lane with the next svh_elas_trim, like a
+    // change of the plan itself
+    int bind_streams() {
+        if (!qp_known) {
+            HIP_TRY(none, hipSetDevice(device));
+            if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) {
+                (void)hipGetLastError();
+                prio_least = prio_greatest = 0;
+            }
+            qp = make_queue_plan(prio_least, prio_greatest, queue_cap(), worker_count(), plan_req);
+            qp_known = true;
+        }
+        const QueueLane& ql = qp.lane[parity & 1];
+        for (int k = 0; k < ql.nstreams; k++) {
+            hipStream_t& cs = cls_stream[ql.cls[k]];
+            if (cs) continue;
+            HIP_TRY(none, hipSetDevice(device));
+            if (qp.plan == QP_ONE)
+                HIP_TRY(none, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+            else
+                HIP_TRY(none, hipStreamCreateWithPriority(&cs, hipStreamNonBlocking,
+                                                          queue_priority_of(ql.cls[k], prio_least, prio_greatest)));
+        }
+        stream = cls_stream[ql.cls[ql.phase_stream[QPH_A]]];
+        stage_stream = cls_stream[ql.cls[ql.phase_stream[QPH_S]]];
+        post_stream = cls_stream[ql.cls[ql.phase_stream[QPH_B]]];
+        return SVH_OK;
     }
 
     int ensure(const svh_elas_params& p, int32_t w, int32_t h, int32_t g) {
-        if (!stream) {
-            HIP_TRY(none, hipSetDevice(device));
-            HIP_TRY(none, hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        }
+        if (int rc = bind_streams()) return rc;
         const int32_t st = p.candidate_stepsize + (p.subsampling ? p.candidate_stepsize % 2 : 0);
         if (w == W && h == H && p.disp_max == disp_max && st == step && p.grid_size == grid_size &&
             p.subsampling == sub && g <= gcap)
             return SVH_OK;
-        hipStream_t keep = stream;
         release();
-        stream = keep;
         d = make_dims(p, w, h);
         const size_t N = (size_t)w * h, DN = (size_t)d.DW * d.DH, G2 = (size_t)2 * g;
         LANE_GROW(img, G2 * N);
@@ -320,26 +380,36 @@ struct Pool {
     std::vector<Lane*> lanes;
     std::vector<Lane*> free_list;
     int max_lanes = 4;
+    int queue_plan = -2;   // svh_elas_set_queue_plan on this device; -2: not called, the process default (g_queue_plan)
 };
 
 static std::mutex g_mu;
 // (the pools live as long as the process -- batch crew and stream workers may still be parked on them at exit -- and
 // stay reachable through this never-destroyed map, so that leak checkers do not report them)
-// (hardware queues: the ROCm runtime multiplexes HIP streams onto GPU_MAX_HW_QUEUES hardware queues, default 4, and the
-// kernels of one queue run one after the other -- a worker's stream then waits behind another worker's k_delaunay.  The
-// count the engine wants, 20, is asked for by svh_init / the implicit initialisation, see svh_init.cpp; round 5 set it
-// from a load-time constructor here.)
+// (hardware queues: the ROCm runtime multiplexes HIP streams onto GPU_MAX_HW_QUEUES hardware queues per stream priority
+// class, default 4, and the kernels of one queue run one after the other -- a worker's stream then waits behind another
+// worker's k_delaunay.  svh_init / the implicit initialisation asks for 20 (svh_init.cpp), which takes effect only when
+// the runtime has not started yet and the process has not set the variable: a host program that starts the runtime
+// first, or a launcher that sets the variable to 4, leaves the 12 lane streams on 4 queues.  What the engine can do
+// about that from the inside -- streams in other priority classes, which have queue pools of their own -- is the
+// queue plan: queue_plan.h, g_queue_plan below, DESIGN.md "Queue plans".)
 
 static std::map<int, Pool*>& g_pools = *new std::map<int, Pool*>();
 // Defaults = the settings the headline number is measured with (bench.py used to set them itself; a C++ caller
 // of the batch entries got 27-31 k pairs/s instead of 33.6-33.9 k with round 4's 8 workers x 16 pairs and 4 queues):
 // six workers (each double-buffered; more only stretches every kernel's in-run duration), 32 pairs per launch
-// for KITTI-size images, 16 hardware queues (below).
+// for KITTI-size images.  (Hardware queues are the host program's to give: see the note above g_pools.)
 static std::atomic<int> g_lanes{6};
 static std::atomic<int> g_group{32};
 static std::atomic<bool> g_group_set{false};   // svh_elas_set_group was called: take the value as is
 static std::atomic<int> g_stage_mode{-1};   // where E5-E7 run, see stage_mode_from_env() below
 static int stage_mode_from_env();
+// queue plan (queue_plan.h): the process default (SVH_QUEUE_PLAN, QP_AUTO otherwise) and the cap it is made for, read
+// from GPU_MAX_HW_QUEUES when the configuration is fixed; a device pool may hold a setting of its own
+static std::atomic<int> g_queue_plan{QP_AUTO};
+static std::atomic<int> g_queue_cap{kQueueCapDefault};
+static int queue_cap() { return g_queue_cap.load(); }
+static int worker_count() { return g_lanes.load(); }
 // svh_init / the implicit initialisation (svh_init.cpp): an explicit call applies its fields, then -- in either case, while
 // the environment is honoured -- the switches that used to be read when the library was loaded
 static void apply_config(const svh_config& c, int explicit_call) {
@@ -352,6 +422,12 @@ static void apply_config(const svh_config& c, int explicit_call) {
     if (const char* e = svh::env("SVH_WAIT_US")) g_wait_us = atoi(e);
     if (svh::env("SVH_STAGE")) g_stage_mode.store(stage_mode_from_env());
     g_hostprof = svh::env("SVH_HOST_PROF") != nullptr;
+    // (the runtime's own variable, only read: the one getenv that does not go through read_env, like svh_init's)
+    g_queue_cap = queue_cap_from_text(getenv("GPU_MAX_HW_QUEUES"));
+    if (const char* e = svh::env("SVH_QUEUE_PLAN")) {
+        const int v = atoi(e);
+        g_queue_plan = v >= 0 && v <= QP_LAST ? v : QP_AUTO;
+    }
 }
 namespace { struct ConfigHook { ConfigHook() { svh::on_config(apply_config); } } g_config_hook; }
 // pairs per launch for an image of N pixels: the default (32) is meant for KITTI-size pairs, whose
@@ -402,9 +478,11 @@ static void acquire_lanes(int device, int count, Lane** out) {
                 } else {
                     Lane* l = new Lane();
                     l->device = device;
+                    l->plan_req = p->queue_plan != -2 ? p->queue_plan : g_queue_plan.load();
                     p->lanes.push_back(l);
                     out[i] = l;
                 }
+                out[i]->parity = i;   // (a lone lane is a first lane)
             }
             return;
         }
@@ -571,7 +649,9 @@ static int run_group(Lane& L, const svh_elas_params& p, const int32_t* dims, con
     const int rc = run_group_body(L, p, dims, io, status, taps, timing, mode, prefer_device);
     if (rc == SVH_ERR_HIP) {
         const std::string keep = svh_last_error();
-        if (L.stream) (void)hipStreamSynchronize(L.stream);
+        for (hipStream_t cs : L.cls_stream)
+            if (cs) (void)hipStreamSynchronize(cs);
+        L.split = false;
         if (L.copy_stream) (void)hipStreamSynchronize(L.copy_stream);
         (void)hipGetLastError();
         L.prof.used = 0;
@@ -602,9 +682,14 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
     const int nmaps = !io.out_device && io.maps == SVH_MAPS_LEFT ? 1 : 2;
     const size_t DNu = ((size_t)d.DW * d.DH + 7) & ~(size_t)7;
     if (u16) LANE_GROW(L.U, (size_t)L.gcap * 2 * DNu * sizeof(uint16_t));
-    hipStream_t s = L.stream;
-    L.prof.stream = s;
-    const LaunchCtx cx = {s, g_prof_on.load() ? &L.prof : nullptr, L.lone_group};
+    // Phase A runs on the main stream.  The stage chain and phase B of a group that is split over the lane's streams
+    // (decided in phase A, below) run on `ss` and `sb`; everything else -- a lone group, a tapping run, the host stage,
+    // the redo of a group the device stage handed back -- stays on `s` whatever the plan.
+    hipStream_t s = L.stream, ss = s, sb = L.split ? L.post_stream : s;
+    const bool prof_on = g_prof_on.load() != 0;
+    PhaseProfiler prof_a(&L.prof, s), prof_s(&L.prof, s), prof_b(&L.prof, sb);
+    const LaunchCtx cx = {s, prof_on ? &prof_a : nullptr, L.lone_group};
+    LaunchCtx cx_s = cx, cx_b = {sb, prof_on ? &prof_b : nullptr, L.lone_group};
     const size_t N = (size_t)W * H, DN = (size_t)d.DW * d.DH;
     const size_t nc = (size_t)d.Wc * d.Hc;
     const bool tapping = taps && taps->enabled;
@@ -643,7 +728,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         // triangle ownership is stored as owner_base + 1 + index; the base moves above everything
         // written so far, so the 2 x N x g map is never cleared (one memset when int32 would overflow)
         if (L.owner_hi + 1 + tri_bound >= INT32_MAX) {
-            HIP_TRY(copy, hipMemsetAsync(L.owner, 0, (size_t)2 * L.gcap * N * sizeof(int32_t), s));
+            HIP_TRY(copy, hipMemsetAsync(L.owner, 0, (size_t)2 * L.gcap * N * sizeof(int32_t), sb));
             L.owner_hi = 0;
         }
         G.owner_base = (int32_t)L.owner_hi;
@@ -653,7 +738,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         G.prior_absmax = 0;
         for (int32_t dd = 0; dd <= plane_radius && dd < (int32_t)L.P.size(); dd++)
             G.prior_absmax = std::max(G.prior_absmax, (int32_t)std::min<int64_t>(std::llabs((long long)L.P[dd]), INT32_MAX));
-        launch_prior(cx, p, d, g, total_sup, total_tri, G, size);
+        launch_prior(cx_b, p, d, g, total_sup, total_tri, G, size);
         if (tapping) {
             const int32_t n1 = hdr->tri_end[0], n2 = hdr->tri_end[1] - hdr->tri_end[0];
             rc = tap_dev(L, taps, SVH_ELAS_PLANES1, L.planes.p, (size_t)6 * n1); if (rc) return rc;
@@ -668,11 +753,11 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                 tap_host(taps, SVH_ELAS_GRID1 + k, gr.data(), gr.size());
             }
         }
-        launch_owner(cx, p, d, g, total_tri, G, size);
+        launch_owner(cx_b, p, d, g, total_tri, G, size);
         const bool tiles = !tapping && post_tiles_ok(p);   // gap + mean (+ speckle mask) tile kernels
         // the row kernel also applies the L/R check (its inputs are the row it just matched)
         const char* match_err = nullptr;
-        const bool lr_done = launch_match(cx, p, d, g, G, &out, tapping, &match_err);
+        const bool lr_done = launch_match(cx_b, p, d, g, G, &out, tapping, &match_err);
         if (match_err) return fail(SVH_ERR_HIP, std::string("launch_match: ") + match_err);
         // (not in 16-bit form: the right map is converted with the left one, after the chain; nor when it stays here)
         early_d2 = !io.out_device && lr_done && !tapping && p.postprocess_only_left && !u16 && nmaps == 2;
@@ -682,7 +767,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                 HIP_TRY(none, hipEventCreateWithFlags(&L.match_ev, hipEventDisableTiming));
                 HIP_TRY(none, hipEventCreateWithFlags(&L.copy_ev, hipEventDisableTiming));
             }
-            HIP_TRY(none, hipEventRecord(L.match_ev, s));
+            HIP_TRY(none, hipEventRecord(L.match_ev, sb));
         }
         if (tapping) {
             rc = tap_dev(L, taps, SVH_ELAS_D1_RAW, L.Draw.p, DN); if (rc) return rc;
@@ -690,26 +775,26 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         }
         const PostScratch ps = {L.tmp, L.labels, L.counts, L.seg_nroots};
         const int nside = p.postprocess_only_left ? 1 : 2;
-        if (!lr_done) launch_lr(cx, p, d, g, G, out);
+        if (!lr_done) launch_lr(cx_b, p, d, g, G, out);
         if (tapping) {
             rc = tap_dev(L, taps, SVH_ELAS_D1_LR, out.D[0], DN); if (rc) return rc;
             rc = tap_dev(L, taps, SVH_ELAS_D2_LR, out.D[1], DN); if (rc) return rc;
         }
-        launch_segments(cx, p, d, g, nside, G, out, ps, /*mask=*/!tiles);
+        launch_segments(cx_b, p, d, g, nside, G, out, ps, /*mask=*/!tiles);
         if (tapping) {
             rc = tap_dev(L, taps, SVH_ELAS_D1_SEG, out.D[0], DN); if (rc) return rc;
             rc = tap_dev(L, taps, SVH_ELAS_D2_SEG, out.D[1], DN); if (rc) return rc;
         }
         if (tiles) {
-            launch_gap_mean_tiles(cx, p, d, g, nside, G, out, ps);   // gap + adaptive mean, two tile kernels
+            launch_gap_mean_tiles(cx_b, p, d, g, nside, G, out, ps);   // gap + adaptive mean, two tile kernels
         } else {
-            launch_gap(cx, p, d, g, nside, G, out, ps);
+            launch_gap(cx_b, p, d, g, nside, G, out, ps);
             if (tapping) {
                 rc = tap_dev(L, taps, SVH_ELAS_D1_GAP, out.D[0], DN); if (rc) return rc;
                 rc = tap_dev(L, taps, SVH_ELAS_D2_GAP, out.D[1], DN); if (rc) return rc;
             }
-            if (p.filter_adaptive_mean) launch_adaptive_mean(cx, p, d, g, nside, G, out, ps);
-            if (p.filter_median) launch_median(cx, d, g, nside, G, out, ps);
+            if (p.filter_adaptive_mean) launch_adaptive_mean(cx_b, p, d, g, nside, G, out, ps);
+            if (p.filter_median) launch_median(cx_b, d, g, nside, G, out, ps);
         }
         if (u16) {
             // one launch for the wanted maps of the whole group (pairs that did not go through are converted too:
@@ -718,7 +803,7 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             for (int32_t j = 0; j < g; j++)
                 for (int k = 0; k < nmaps; k++)
                     pm[j * nmaps + k] = {(int64_t)(((size_t)2 * j + k) * DN), (int64_t)(((size_t)j * nmaps + k) * DNu), (int64_t)DN};
-            launch_disp_pack(cx, L.D, L.U, pm, g * nmaps);
+            launch_disp_pack(cx_b, L.D, L.U, pm, g * nmaps);
         }
         return SVH_OK;
     };
@@ -910,6 +995,14 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
         // is done: it sleeps between polls also in a one-round (latency-bound) batch, instead of spinning
         // on a core that another rank may need (8 pairs of 1920x1080 per step: 4-7 cores -> < 1)
         if (L.resident && prefer_device) L.poll_wait = true;
+        // the lane's streams of other classes are used by a device-stage group of a pipelined run only
+        L.split = L.resident && !L.lone_group && !tapping && (L.stage_stream != s || L.post_stream != s);
+        ss = L.split ? L.stage_stream : s;
+        sb = L.split ? L.post_stream : s;
+        prof_s.stream = ss;
+        prof_b.stream = sb;
+        cx_s = LaunchCtx{ss, prof_on ? &prof_s : nullptr, L.lone_group};
+        cx_b = LaunchCtx{sb, prof_on ? &prof_b : nullptr, L.lone_group};
         if (!L.resident || tapping)
             HIP_TRY(copy, hipMemcpyAsync(L.h_dcan, L.dcan, g * nc * sizeof(int16_t), hipMemcpyDeviceToHost, s));
         if (L.resident) {
@@ -936,14 +1029,20 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
             // (SVH_STAGE_BLITS=1, read per group: a hipMemsetAsync and a hipMemcpyAsync as before, for A/B runs).
             // Either way h_counts is read only after stage_ev, or the whole stream, has completed.
             const bool blits = svh::env("SVH_STAGE_BLITS") && atoi(svh::env("SVH_STAGE_BLITS")) != 0;
-            launch_stage_device(cx, p, d, g, L.stg, reinterpret_cast<GroupHdr*>(L.prior_dev.p),
+            if (ss != s) {   // the stage chain starts behind k_support
+                if (!L.a_ev) HIP_TRY(none, hipEventCreateWithFlags(&L.a_ev, hipEventDisableTiming));
+                HIP_TRY(none, hipEventRecord(L.a_ev, s));
+                HIP_TRY(none, hipStreamWaitEvent(ss, L.a_ev, 0));
+            }
+            launch_stage_device(cx_s, p, d, g, L.stg, reinterpret_cast<GroupHdr*>(L.prior_dev.p),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_sup),
                                 reinterpret_cast<int32_t*>(L.prior_dev + L.o_tri),
                                 blits ? nullptr : L.seed.p, seed_words_with_flags(d, g),
                                 blits ? nullptr : L.h_counts.p);
             if (!L.stage_ev) HIP_TRY(none, hipEventCreateWithFlags(&L.stage_ev, hipEventDisableTiming));
-            if (blits) HIP_TRY(copy, hipMemcpyAsync(L.h_counts, L.stg.counts, sizeof(StageCounts), hipMemcpyDeviceToHost, s));
-            HIP_TRY(none, hipEventRecord(L.stage_ev, s));
+            if (blits) HIP_TRY(copy, hipMemcpyAsync(L.h_counts, L.stg.counts, sizeof(StageCounts), hipMemcpyDeviceToHost, ss));
+            HIP_TRY(none, hipEventRecord(L.stage_ev, ss));
+            if (sb != ss) HIP_TRY(none, hipStreamWaitEvent(sb, L.stage_ev, 0));   // phase B starts behind k_stage_pack
             if (tapping) {
                 // host copies of the header and the lists the device built (g == 1)
                 HIP_TRY(copy, hipMemcpyAsync(hdr, L.prior_dev, sizeof(GroupHdr), hipMemcpyDeviceToHost, s));
@@ -974,6 +1073,15 @@ static int run_group_body(Lane& L, const svh_elas_params& p, const int32_t* dims
                 L.sized.seed_cleared = !blits;
                 rc = enqueue_phase_b(L.o_P, L.o_sup, L.o_tri, -1, -1, tri_bound, L.sized);
                 if (rc) return rc;
+            }
+            // Every stream of the group ends in the main stream: the stage stream ended in phase B's above, and phase
+            // B's, where it is not the main stream itself, ends here.  What follows on `s` -- the copies to host
+            // buffers, lane_wait, phase A of the lane's next group, which overwrites what this phase B reads -- is
+            // ordered as it was with one stream.
+            if (sb != s) {
+                if (!L.b_ev) HIP_TRY(none, hipEventCreateWithFlags(&L.b_ev, hipEventDisableTiming));
+                HIP_TRY(none, hipEventRecord(L.b_ev, sb));
+                HIP_TRY(none, hipStreamWaitEvent(s, L.b_ev, 0));
             }
         }
         HP_MARK(HP_ENQ_A);
@@ -1984,6 +2092,37 @@ void svh_elas_get_settings(int32_t out[4]) {
     out[1] = g_group_set.load() ? g_group.load() : 0;
     out[2] = g_stage_mode.load();
     out[3] = g_wait_us;
+}
+
+int32_t svh_elas_set_queue_plan(int32_t plan) {
+    svh::ensure_init();
+    if (plan < 0 || plan > QP_LAST) plan = QP_AUTO;
+    Pool* p = pool_for(t_device);
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->queue_plan = plan;
+    return plan;
+}
+
+int32_t svh_elas_get_queue_plan(int32_t* plan, int32_t* streams_per_lane, int32_t* classes) {
+    svh::ensure_init();
+    Pool* p = pool_for(t_device);
+    int req;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        req = p->queue_plan != -2 ? p->queue_plan : g_queue_plan.load();
+    }
+    // what a lane created now is built with; without a device (or its priority range) that is the one-stream layout
+    int least = 0, greatest = 0, n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= t_device || hipSetDevice(t_device) != hipSuccess ||
+        hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) {
+        (void)hipGetLastError();
+        least = greatest = 0;
+    }
+    const QueuePlan q = make_queue_plan(least, greatest, queue_cap(), worker_count(), req);
+    if (plan) *plan = q.plan;
+    if (streams_per_lane) *streams_per_lane = q.streams_per_lane;
+    if (classes) *classes = q.classes;
+    return SVH_OK;
 }
 
 int32_t svh_elas_set_group(int32_t pairs) {

@@ -462,6 +462,20 @@ def set_stage(where):
     return lib().svh_elas_set_stage(where)
 
 
+def set_queue_plan(plan):
+    """svh_elas_set_queue_plan: -1 automatic (4 where GPU_MAX_HW_QUEUES is below 2 x workers, else 0), 0 one stream per
+    lane, 4 second lanes on a low-priority stream; 1 stage chain high, 2 plan 1 + second lanes low, 3 by phase (slower,
+    kept for A/B runs).  Lanes are built with it when created (trim() first for the idle ones).  Returns the value stored."""
+    return lib().svh_elas_set_queue_plan(int(plan))
+
+
+def queue_plan():
+    """svh_elas_get_queue_plan: what a lane created now gets"""
+    p, s, c = C.c_int32(-9), C.c_int32(-9), C.c_int32(-9)
+    lib().svh_elas_get_queue_plan(C.byref(p), C.byref(s), C.byref(c))
+    return dict(plan=p.value, streams_per_lane=s.value, classes=c.value)
+
+
 def trim():
     """release the pooled lanes that are idle (device + pinned memory, streams); returns the count"""
     lib().svh_elas_trim.restype = C.c_int64
