@@ -15,15 +15,30 @@
  * the multiset of points added since the last clear: never on their order, the launch shape or the scheduling.
  * The class of a cell (bits 0-1 of the class byte), tested in this order: 0 unknown (fewer than min_points low
  * points), 2 obstacle (HMAX > step), 3 drop (HMIN < -drop), 1 free.  Bit 7 (overhang): overhead >= min_points.
- * Not done: slope or neighbour-cell tests, ray-traced free space, a window that scrolls without clearing.
+ *
+ * A LOCAL MAP.  The window scrolls in whole cells and keeps what stays inside.  A point's global cell is (ga, gb) =
+ * (floorf((a - x0) / cell), floorf((b - z0) / cell)); the window holds ga in oa .. oa + nx - 1 and gb in ob .. ob + nz - 1,
+ * with the offsets (oa, ob) = (0, 0) at create and |oa|, |ob| <= 2^20 - 8192.  Every plane is in the window's order, index
+ * (gb - ob) * nx + (ga - oa).  svh_grid_scroll moves the offsets: cells that stay keep everything they accumulated, the
+ * strips that enter are empty, and the statistics go on counting since the last clear.
+ * Free space is ray-cast: svh_grid_add_*_from bins points as svh_grid_add_* does and, for each LOW point, walks the line
+ * from the origin's cell (ca, cb) to the point's cell (ea, eb): with dx = ea - ca, dz = eb - cb, n = max(|dx|, |dz|) and
+ * rdiv(p, n) = floor((2 p + n) / (2 n)) (nearest, halves up) the cells (ca + rdiv(k dx, n), cb + rdiv(k dz, n)) for
+ * k = 0 .. n - 1 -- the origin's cell is counted, the end cell is not.  Each gains one in the cell's PASS count.  The origin
+ * itself must be a low point of the window (finite, inside, not above clearance), so every cell of a ray is inside the
+ * window and below the clearance.  PASS is an integer sum too: it depends only on the multiset of (origin cell, end
+ * cell) pairs.  A cell is SEEN when PASS >= min_points: unknown and seen is "looked through and found empty", unknown
+ * and not seen is "never looked at".
+ * Not done: slope or neighbour-cell tests.
  *
  * Plain C like svh_view.h.  An object has its own stream and every call returns when it is complete.  Calls return
  * SVH_OK or a negative SVH_ERR_*; svh_last_error() has the text.  SVH_ERR_BAD_ARG -- a null pointer, parameters out of
  * the ranges below, n < 0, n > 0 with a null array, a device array that is not 16-byte aligned, an unknown plane or
  * mode -- is decided before anything is read or changed.  svh_grid_create returns NULL without a HIP device.
  * SVH_ERR_UNSUPPORTED, nothing changed: the object would have been given more than 2^31 - 1 points since the last
- * clear (counts are 32 bits).  After SVH_ERR_HIP inside svh_grid_add_* the grid is EMPTY (accumulation is in place, a
- * half-added call cannot be taken back): all statistics are zero and the next add starts afresh.  After SVH_ERR_HIP
+ * clear (counts are 32 bits).  After SVH_ERR_HIP inside svh_grid_add_* or svh_grid_scroll / svh_grid_follow the grid is
+ * EMPTY (accumulation is in place, a half-done call cannot be taken back): all statistics are zero, the next add starts
+ * afresh, and after a failed scroll the window stands at its new offsets.  After SVH_ERR_HIP
  * inside svh_grid_get or svh_grid_render the accumulated grid is untouched.
  */
 #ifndef SVH_GRID_H
@@ -83,12 +98,30 @@ int32_t   svh_grid_frame_plane(const double plane_e[3], const double H[16], doub
 svh_grid* svh_grid_create(const svh_grid_params* p);   /* NULL: bad parameters, or no HIP device */
 void      svh_grid_destroy(svh_grid* g);
 int32_t   svh_grid_clear(svh_grid* g);
-int32_t   svh_grid_set_window(svh_grid* g, float x0, float z0);   /* moves the window with the vehicle; clears */
+int32_t   svh_grid_set_window(svh_grid* g, float x0, float z0);   /* a new low corner; clears, and the offsets are 0 again */
+
+/* the window moves by (da, db) whole cells and keeps what stays inside; |da| >= nx or |db| >= nz empties the grid.
+ * SVH_ERR_BAD_ARG, nothing changed: an offset would leave -(2^20 - 8192) .. 2^20 - 8192 */
+int32_t   svh_grid_scroll(svh_grid* g, int32_t da, int32_t db);
+int32_t   svh_grid_get_window(svh_grid* g, int32_t off[2]);            /* (oa, ob) */
+/* the global cell (ga, gb) of a map-frame position (rounded to float once); SVH_ERR_BAD_ARG: not finite, or |ga| or |gb|
+ * not below 2^20 */
+int32_t   svh_grid_cell_of(svh_grid* g, const double xyz[3], int32_t cell[2]);
+/* scrolls so that the cell of xyz becomes window cell (ia, ib), 0 <= ia < nx, 0 <= ib < nz */
+int32_t   svh_grid_follow(svh_grid* g, const double xyz[3], int32_t ia, int32_t ib);
 
 /* n points (x, y, z, val), on the host or (on_device) in device memory, 16-byte aligned there */
 int32_t   svh_grid_add_points(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device);
 /* the view's whole store, device to device, no host copy; an empty view: SVH_OK, nothing changes */
 int32_t   svh_grid_add_view(svh_grid* g, svh_view* v);
+/* svh_grid_add_points, and one ray per low point from the cell of `origin` (a map-frame position, rounded to float once).
+ * SVH_ERR_BAD_ARG, before anything is read or changed: the origin is not a low point of the window */
+int32_t   svh_grid_add_points_from(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device, const double origin[3]);
+/* the same for the lists first_list .. first_list + n_lists - 1 of the view's sequence, device to device;
+ * SVH_ERR_BAD_ARG: the range is not inside the sequence */
+int32_t   svh_grid_add_view_lists_from(svh_grid* g, svh_view* v, int32_t first_list, int32_t n_lists, const double origin[3]);
+/* since the last clear: out[0] rays (the low points added through the _from entries), out[1] the sum of PASS increments */
+int32_t   svh_grid_get_ray_stats(svh_grid* g, int64_t out[2]);
 /* totals since the last clear; added = binned + overhead + outside + unplaced */
 int32_t   svh_grid_get_stats(svh_grid* g, svh_grid_stats* stats);
 
@@ -96,6 +129,14 @@ int32_t   svh_grid_get_stats(svh_grid* g, svh_grid_stats* stats);
 int32_t   svh_grid_get(svh_grid* g, int32_t plane, void* out, int32_t on_device);
 /* nx x nz RGB8; row 0 is the farthest row (ib = nz - 1): forward is up */
 int32_t   svh_grid_render(svh_grid* g, int32_t mode, uint8_t* rgb, int32_t on_device);
+
+
+/* planes of svh_grid_get_local, laid out as those of svh_grid_get */
+#define SVH_GRID_LOCAL_PASS   0   /* int32: rays that passed the cell */
+#define SVH_GRID_LOCAL_STATE  1   /* uint8: the byte of SVH_GRID_CLASS with bit 6 (seen) where PASS >= min_points */
+int32_t   svh_grid_get_local(svh_grid* g, int32_t plane, void* out, int32_t on_device);
+/* SVH_GRID_RENDER_CLASS, except that a cell that is unknown and seen is (96, 112, 96) instead of (32, 32, 32) */
+int32_t   svh_grid_render_local(svh_grid* g, uint8_t* rgb, int32_t on_device);
 
 #ifdef __cplusplus
 }

@@ -4,8 +4,11 @@
 //   * hipcc into the kernels of csrc/grid_kernels.hip,
 //   * the host compiler into csrc/grid_engine.cpp (the test entries svh_test_grid_points / svh_test_grid_finalise, which
 //     evaluate every function below on the host),
-//   * g++ -fsanitize=undefined into tests/cxx/grid_core_check.cpp, which guards the float-to-integer conversions,
-// and restated in numpy by tests/grid_ref.py, which tests/test_grid.py pins by hand and against the test entries.
+//   * g++ -fsanitize=undefined into tests/cxx/grid_core_check.cpp, which guards the float-to-integer conversions, and
+//     into tests/cxx/grid_line_check.cpp, which runs the line and the offset place() at their extremes,
+// and restated in numpy by tests/grid_ref.py, which tests/test_grid.py pins by hand and against the test entries; the
+// window's offsets, the line of a ray, the state byte and the local colour (svh_test_grid_points_at / svh_test_grid_line
+// / svh_test_grid_local) by tests/grid_local_ref.py and tests/test_grid_local.py.
 // fp32 in the order written, every operation rounded once (-ffp-contract=off on every build, no fast-math), the
 // divisions IEEE's (div_rn), denormals kept.  Every range decision is made on the float BEFORE a conversion to an
 // integer: an out-of-range conversion is undefined on the host and saturates on the device.
@@ -13,7 +16,8 @@
 // ORDER INDEPENDENCE.  Every quantity a cell accumulates is an integer under a commutative, associative update: two
 // counts (+), two keys (min, max), a sum of heights quantised to 1/1024 (+, int64) and a sum of intensity bytes (+,
 // uint64).  The grid after any set of adds therefore depends only on the MULTISET of points, never on their order, the
-// launch shape or the scheduling; add(A) then add(B) is add(A ++ B).
+// launch shape or the scheduling; add(A) then add(B) is add(A ++ B).  The pass count of the rays (below) is one more
+// integer sum: it depends only on the multiset of (origin cell, end cell) pairs.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -32,13 +36,18 @@ constexpr uint32_t KMIN_EMPTY = 0xFFFFFFFFu;       // the keys of a cell without
 constexpr uint32_t KMAX_EMPTY = 0u;
 constexpr uint32_t NO_CELL = 0xFFFFFFFFu;          // the cell of a point that is outside or unplaced
 constexpr uint32_t NAN_BITS = 0x7FC00000u;         // HMIN, HMAX, HMEAN of a cell without a low point
+constexpr int32_t OFFSET_LIMIT = (1 << 20) - MAX_SIDE;   // |oa|, |ob| <= this: every global cell of a window is below 2^20
+constexpr float CELL_LIMIT = 1048576.f;            // a position has a global cell iff |floorf(...)| < 2^20, both axes
 
 // what becomes of a point
 enum Fate : int32_t { LOW = 0, OVERHEAD = 1, OUTSIDE = 2, UNPLACED = 3 };
 // planes of svh_grid_get, modes of svh_grid_render, classes of a cell (bits 0-1 of the class byte; bit 7: overhang)
 enum Plane : int32_t { P_COUNT = 0, P_OVERHEAD, P_HMIN, P_HMAX, P_HMEAN, P_INTENSITY, P_CLASS, P_PLANES };
-enum Mode : int32_t { M_CLASS = 0, M_HEIGHT, M_INTENSITY, M_MODES };
-enum Class : uint8_t { C_UNKNOWN = 0, C_FREE = 1, C_OBSTACLE = 2, C_DROP = 3, C_OVERHANG = 0x80 };
+enum Mode : int32_t { M_CLASS = 0, M_HEIGHT, M_INTENSITY, M_MODES, M_LOCAL = M_MODES };   // M_LOCAL: svh_grid_render_local only
+enum Class : uint8_t { C_UNKNOWN = 0, C_FREE = 1, C_OBSTACLE = 2, C_DROP = 3, C_SEEN = 0x40, C_OVERHANG = 0x80 };
+// planes of svh_grid_get_local; the colour of a cell that is unknown and seen in svh_grid_render_local
+enum LocalPlane : int32_t { L_PASS = 0, L_STATE, L_PLANES };
+constexpr uint8_t SEEN_R = 96, SEEN_G = 112, SEEN_B = 96;
 
 // svh_grid_params with T rounded to float (once, at create)
 struct Params {
@@ -47,14 +56,16 @@ struct Params {
     float T[12];
     int32_t min_points;
     float step, drop, clearance, h_lo, h_hi;
+    int32_t oa = 0, ob = 0;   // the window's offsets in whole cells (svh_grid_scroll): it holds global cells oa .. oa + nx - 1
 };
 
 struct Placed {
     int32_t fate;
-    uint32_t cell;      // ib * nx + ia; NO_CELL when outside or unplaced
+    uint32_t cell;      // the logical index (gb - ob) * nx + (ga - oa); NO_CELL when outside or unplaced
     uint32_t key;       // LOW: key_of(h)
     int32_t q;          // LOW: rintf(h * 1024)
     uint32_t v;         // LOW: q8(val)
+    uint32_t slot;      // where the cell's accumulators lie (slot_at); the logical index while the offsets are zero
 };
 
 // what a cell has accumulated
@@ -101,18 +112,57 @@ MC_FN uint32_t q8(float val) {
     return (uint32_t)rintf(hi * 255.f);
 }
 
+// THE WINDOW.  A point's global cell is (ga, gb) = (floorf((a - x0) / cell), floorf((b - z0) / cell)); the window holds
+// ga in oa .. oa + nx - 1 and gb in ob .. ob + nz - 1.  |oa|, |ob| <= OFFSET_LIMIT, so every value compared below is an
+// integer of magnitude below 2^20 + 2^13 and exact in fp32.  The accumulators are addressed as a torus over the global
+// cell, slot = mod(gb, nz) * nx + mod(ga, nx) with the non-negative mod: a scroll (svh_grid_scroll) moves no data, cells
+// that stay keep their slot and the strips that enter take the slots of those that left.  The planes that leave the
+// object are in logical order.
+MC_FN int32_t mod_floor(int32_t v, int32_t n) {
+    const int32_t r = v % n;
+    return r < 0 ? r + n : r;
+}
+// window cell (ia, ib) -> slot.  mod(oa + ia, nx) without a division per cell: mod(oa, nx) is the same for every cell
+MC_FN uint32_t slot_at(const Params& p, int32_t ia, int32_t ib) {
+    int32_t sa = mod_floor(p.oa, p.nx) + ia, sb = mod_floor(p.ob, p.nz) + ib;
+    sa = sa >= p.nx ? sa - p.nx : sa;
+    sb = sb >= p.nz ? sb - p.nz : sb;
+    return (uint32_t)sb * (uint32_t)p.nx + (uint32_t)sa;
+}
+// logical index -> slot
+MC_FN uint32_t slot_of(const Params& p, uint32_t logical) {
+    const uint32_t ib = logical / (uint32_t)p.nx;
+    return slot_at(p, (int32_t)(logical - ib * (uint32_t)p.nx), (int32_t)ib);
+}
+MC_FN bool offsets_ok(int32_t oa, int32_t ob) {
+    return oa >= -OFFSET_LIMIT && oa <= OFFSET_LIMIT && ob >= -OFFSET_LIMIT && ob <= OFFSET_LIMIT;
+}
+
+// the global cell of a position, for svh_grid_cell_of; false: not placeable (not finite, or a cell not below 2^20)
+MC_FN bool global_cell(const Params& p, float x, float y, float z, int32_t* ga, int32_t* gb) {
+    const float a = row(p.T, x, y, z), b = row(p.T + 4, x, y, z);
+    if (!(finite_f(x) && finite_f(y) && finite_f(z) && finite_f(a) && finite_f(b))) return false;
+    const float ca = floorf(div_rn(a - p.x0, p.cell)), cb = floorf(div_rn(b - p.z0, p.cell));
+    if (!(fabsf(ca) < CELL_LIMIT && fabsf(cb) < CELL_LIMIT)) return false;
+    *ga = (int32_t)ca, *gb = (int32_t)cb;
+    return true;
+}
+
 MC_FN Placed place(const Params& p, float x, float y, float z, float val) {
-    Placed r{UNPLACED, NO_CELL, 0u, 0, 0u};
+    Placed r{UNPLACED, NO_CELL, 0u, 0, 0u, 0u};
     const float a = row(p.T, x, y, z), b = row(p.T + 4, x, y, z);
     float h = row(p.T + 8, x, y, z);
     if (!(finite_f(x) && finite_f(y) && finite_f(z) && finite_f(a) && finite_f(b) && finite_f(h))) return r;
     // a - x0 can overflow to +-Inf, and so can the quotient: both fail the comparisons below
     const float ca = floorf(div_rn(a - p.x0, p.cell)), cb = floorf(div_rn(b - p.z0, p.cell));
-    if (!(ca >= 0.f && ca < (float)p.nx && cb >= 0.f && cb < (float)p.nz && fabsf(h) < H_LIMIT)) {
+    if (!(ca >= (float)p.oa && ca < (float)(p.oa + p.nx) && cb >= (float)p.ob && cb < (float)(p.ob + p.nz) &&
+          fabsf(h) < H_LIMIT)) {
         r.fate = OUTSIDE;
         return r;
     }
-    r.cell = (uint32_t)(int32_t)cb * (uint32_t)p.nx + (uint32_t)(int32_t)ca;
+    const int32_t ia = (int32_t)ca - p.oa, ib = (int32_t)cb - p.ob;
+    r.cell = (uint32_t)ib * (uint32_t)p.nx + (uint32_t)ia;
+    r.slot = slot_at(p, ia, ib);
     if (h == 0.f) h = 0.f;   // -0.0f -> +0.0f
     if (h > p.clearance) {
         r.fate = OVERHEAD;
@@ -179,6 +229,40 @@ MC_FN void colour(const Params& p, int32_t mode, int32_t count, const Final& f, 
     }
 }
 
+// RAYS (svh_grid_add_*_from).  A low point casts one ray from the origin's cell (oa_c, ob_c) to its own (ea, eb), both
+// in the window: with dx = ea - oa_c, dz = eb - ob_c, n = max(|dx|, |dz|) the ray passes, for k = 0 .. n - 1, the cell
+// (oa_c + rdiv(k * dx, n), ob_c + rdiv(k * dz, n)): the origin's cell is counted, the end cell is not, a point in the
+// origin's cell casts nothing.  Both coordinates stay between the origin's and the end's, so every cell is in the window.
+// The line depends only on the two cells, so the pass plane depends only on the multiset of (origin cell, end cell).
+// rdiv(p, n) = floor((2 p + n) / (2 n)), n > 0: p / n rounded to the nearest integer, halves towards +infinity.  A true
+// floor: C's / truncates, which is wrong for a negative numerator.  |p| < 2^26 (k < 2^13, |dx| < 2^13): 32 bits suffice.
+MC_FN int32_t rdiv(int32_t p, int32_t n) {
+    const int32_t num = 2 * p + n, den = 2 * n;
+    const int32_t q = num / den;
+    return (num < 0 && q * den != num) ? q - 1 : q;
+}
+MC_FN int32_t line_len(int32_t dx, int32_t dz) {
+    const int32_t ax = dx < 0 ? -dx : dx, az = dz < 0 ? -dz : dz;
+    return ax > az ? ax : az;
+}
+// the k-th cell of the line as an offset from the origin's cell, 0 <= k < n = line_len(dx, dz)
+MC_FN void line_step(int32_t dx, int32_t dz, int32_t n, int32_t k, int32_t* sx, int32_t* sz) {
+    *sx = rdiv(k * dx, n), *sz = rdiv(k * dz, n);
+}
+
+// the state byte of svh_grid_get_local: the class byte with bit 6 where at least min_points rays passed the cell
+MC_FN uint8_t state_of(const Params& p, uint8_t cls, int32_t pass) {
+    return pass >= p.min_points ? (uint8_t)(cls | C_SEEN) : cls;
+}
+// svh_grid_render_local: the class colours, but a cell that is unknown and seen has the SEEN colour instead of the dark
+// grey (the overhang bit still fills its blue byte)
+MC_FN void colour_local(const Params& p, int32_t count, const Final& f, int32_t pass, uint8_t* rgb) {
+    colour(p, M_CLASS, count, f, rgb);
+    if ((f.cls & 3) == C_UNKNOWN && pass >= p.min_points) {
+        rgb[0] = SEEN_R, rgb[1] = SEEN_G, rgb[2] = (f.cls & C_OVERHANG) ? 255 : SEEN_B;
+    }
+}
+
 // the checks behind SVH_ERR_BAD_ARG of svh_grid_create
 MC_FN bool params_ok(const Params& p) {
     for (int k = 0; k < 12; k++)
@@ -186,7 +270,7 @@ MC_FN bool params_ok(const Params& p) {
     return p.nx >= 1 && p.nx <= MAX_SIDE && p.nz >= 1 && p.nz <= MAX_SIDE && finite_f(p.cell) && p.cell > 0.f &&
            finite_f(p.x0) && finite_f(p.z0) && p.min_points >= 1 && finite_f(p.step) && p.step >= 0.f && finite_f(p.drop) &&
            p.drop >= 0.f && finite_f(p.clearance) && p.clearance > p.step && finite_f(p.h_lo) && finite_f(p.h_hi) &&
-           p.h_lo < p.h_hi;
+           p.h_lo < p.h_hi && offsets_ok(p.oa, p.ob);
 }
 
 }  // namespace grid

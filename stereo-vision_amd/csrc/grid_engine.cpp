@@ -1,14 +1,18 @@
 // The ground grid behind the svh_grid_* entries of include/svh_grid.h: a 2.5-D bird's-eye grid over the road plane, binned
 // on the device from the map view's store or from a list of points.
 //
-// Host (this file): the parameters (T rounded to float once), the two frames, the statistics, the lazy clear and the lazy
-// finalise.  Device (grid_kernels.hip): the binning, the finalise, the render.  The arithmetic is csrc/grid_core.h.  The
+// Host (this file): the parameters (T rounded to float once), the two frames, the window's offsets, the statistics, the
+// lazy clear and the lazy finalise.  Device (grid_kernels.hip): the binning, the rays, the strips of a scroll, the
+// finalise, the render.  The arithmetic is csrc/grid_core.h.  The
 // object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
 // empty, and the next entry that touches the device fills the planes with the empty values first.  That is what makes
 // "after SVH_ERR_HIP inside an add the grid is empty" hold even when the failure was a lost device queue: no HIP call is
-// needed to get there.  The finished planes are derived lazily too, by the first get or render after a change.
+// needed to get there.  The finished planes are derived lazily too, by the first get or render after a change: the
+// accumulators lie at their slots (the torus of grid_core.h), the finished planes are in logical order, and every plane
+// that leaves the object is a finished one.  A scroll moves no data: it changes the offsets and resets the strips that
+// enter; on an empty grid it changes the offsets alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -31,7 +35,9 @@ namespace {
 
 constexpr int64_t kMaxPoints = ((int64_t)1 << 31) - 1;
 constexpr int64_t kHostChunk = (int64_t)1 << 22;   // points of a host array staged per copy
-constexpr size_t kFinalBytes = 14;                 // per cell: HMIN, HMAX, HMEAN, INTENSITY, CLASS
+constexpr size_t kFinalBytes = 27;                 // per cell: COUNT, OVERHEAD, PASS, HMIN, HMAX, HMEAN; INTENSITY, CLASS, STATE
+enum FinPlane { F_COUNT = 0, F_OVERHEAD, F_PASS, F_HMIN, F_HMAX, F_HMEAN, F_WORDS };   // the 4-byte planes of `fin`
+enum FinByte { B_INTENSITY = 0, B_CLASS, B_STATE };                                    // its byte planes
 
 bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
@@ -57,8 +63,10 @@ struct svh_grid {
     hipStream_t stream = nullptr;
     grid::Params prm{};
     size_t ncells = 0;
-    HipBuf<uint8_t> acc;        // CELL_BYTES per cell: kmin | kmax | count | overhead | hsum | vsum, a plane each
-    HipBuf<uint8_t> fin;        // kFinalBytes per cell: hmin | hmax | hmean | intensity | class
+    HipBuf<uint8_t> acc;        // CELL_BYTES per cell: kmin | kmax | count | overhead | hsum | vsum | pass, a plane each
+    HipBuf<uint8_t> fin;        // kFinalBytes per cell: the FinPlane planes, then the FinByte planes, logical order
+    HipBuf<int32_t> ends;       // svh_grid_add_*_from: the call's low points per cell; all zero between calls
+    bool ends_clean = false;    // ... and it is
     HipBuf<unsigned long long> d_stats;
     PinnedBuf<unsigned long long> h_stats;
     HipBuf<float4> d_pts;       // a host array on its way to the kernel
@@ -68,15 +76,17 @@ struct svh_grid {
     bool need_clear = true;     // the accumulators do not hold the empty grid yet
     bool final_valid = false;   // `fin` is derived from the accumulators as they are
     svh_grid_stats st{0, 0, 0, 0, 0};
+    int64_t rays = 0, ray_cells = 0;
 
     grid::Cells cells() const {
         uint8_t* b = acc.p;
         const size_t n = ncells;
         return grid::Cells{(uint32_t*)b, (uint32_t*)(b + 4 * n), (int32_t*)(b + 8 * n), (int32_t*)(b + 12 * n),
-                           (unsigned long long*)(b + 16 * n), (unsigned long long*)(b + 24 * n)};
+                           (unsigned long long*)(b + 16 * n), (unsigned long long*)(b + 24 * n), (int32_t*)(b + 32 * n)};
     }
     float* fplane(int k) const { return (float*)(fin.p + 4 * ncells * (size_t)k); }
-    uint8_t* bplane(int k) const { return fin.p + 12 * ncells + ncells * (size_t)k; }
+    int32_t* iplane(int k) const { return (int32_t*)(fin.p + 4 * ncells * (size_t)k); }
+    uint8_t* bplane(int k) const { return fin.p + 4 * F_WORDS * ncells + ncells * (size_t)k; }
 };
 
 namespace {
@@ -85,6 +95,14 @@ void mark_empty(svh_grid* g) {
     g->need_clear = true;
     g->final_valid = false;
     g->st = svh_grid_stats{0, 0, 0, 0, 0};
+    g->rays = g->ray_cells = 0;
+}
+
+// the accumulators become those of the empty grid; the statistics are not touched
+int fill_empty(svh_grid* g) {
+    GRID_TRY(copy, hipMemsetAsync(g->acc, 0xFF, 4 * g->ncells, g->stream));
+    GRID_TRY(copy, hipMemsetAsync(g->acc + 4 * g->ncells, 0, (grid::CELL_BYTES - 4) * g->ncells, g->stream));
+    return SVH_OK;
 }
 
 // the buffers exist and the accumulators hold what the object says they hold
@@ -93,19 +111,20 @@ int ready(svh_grid* g) {
     if (g->acc.cap < g->ncells * grid::CELL_BYTES) g->need_clear = true;
     GRID_GROW(g->acc, g->ncells * grid::CELL_BYTES);
     GRID_GROW(g->fin, g->ncells * kFinalBytes);
-    GRID_GROW(g->d_stats, 4 * sizeof(unsigned long long));
-    GRID_GROW(g->h_stats, 4 * sizeof(unsigned long long));
+    GRID_GROW(g->d_stats, grid::STAT_WORDS * sizeof(unsigned long long));
+    GRID_GROW(g->h_stats, grid::STAT_WORDS * sizeof(unsigned long long));
     if (g->need_clear) {
-        GRID_TRY(copy, hipMemsetAsync(g->acc, 0xFF, 4 * g->ncells, g->stream));
-        GRID_TRY(copy, hipMemsetAsync(g->acc + 4 * g->ncells, 0, (grid::CELL_BYTES - 4) * g->ncells, g->stream));
-        GRID_TRY(copy, hipMemsetAsync(g->d_stats, 0, 4 * sizeof(unsigned long long), g->stream));
+        const int rc = fill_empty(g);
+        if (rc) return rc;
+        GRID_TRY(copy, hipMemsetAsync(g->d_stats, 0, grid::STAT_WORDS * sizeof(unsigned long long), g->stream));
         g->need_clear = false;   // in stream order before whatever the entry does next; every entry ends with a wait
     }
     return SVH_OK;
 }
 
-// n > 0 points, host or device, with arguments that have been checked
-int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device) {
+// n > 0 points, host or device, with arguments that have been checked; origin >= 0: the logical index of the cell the
+// low points cast their rays from
+int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origin = -1) {
     int rc = ready(g);
     if (rc) return rc;
     g->final_valid = false;
@@ -114,6 +133,13 @@ int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device) {
     j.cells = g->cells();
     j.stats = g->d_stats;
     hipStream_t s = g->stream;
+    if (origin >= 0) {
+        if (g->ends.cap < g->ncells * sizeof(int32_t)) g->ends_clean = false;
+        GRID_GROW(g->ends, g->ncells * sizeof(int32_t));
+        if (!g->ends_clean) GRID_TRY(copy, hipMemsetAsync(g->ends, 0, g->ncells * sizeof(int32_t), s));
+        g->ends_clean = false;   // until the rays of this call have zeroed what its binning counts
+        j.ends = g->ends;
+    }
     if (on_device) {
         j.pts = (const float4*)xyzv;
         j.n = n;
@@ -132,9 +158,23 @@ int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device) {
             GRID_TRY(launch, (grid::launch_bin(s, j), hipGetLastError()));
         }
     }
-    GRID_TRY(copy, hipMemcpyAsync(g->h_stats, g->d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (origin >= 0) {
+        grid::RayJob r;
+        r.prm = g->prm;
+        r.origin = (uint32_t)origin;
+        r.ends = g->ends;
+        r.pass = j.cells.pass;
+        r.ray_cells = g->d_stats + grid::STAT_RAY_CELLS;
+        GRID_TRY(launch, (grid::launch_rays(s, r), hipGetLastError()));
+    }
+    GRID_TRY(copy, hipMemcpyAsync(g->h_stats, g->d_stats, grid::STAT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     GRID_TRY(wait, hipStreamSynchronize(s));
     const unsigned long long* h = g->h_stats;
+    if (origin >= 0) {
+        g->ends_clean = true;
+        g->rays += (int64_t)h[grid::LOW] - g->st.binned;
+        g->ray_cells = (int64_t)h[grid::STAT_RAY_CELLS];
+    }
     g->st.added += n;
     g->st.binned = (int64_t)h[grid::LOW], g->st.overhead = (int64_t)h[grid::OVERHEAD];
     g->st.outside = (int64_t)h[grid::OUTSIDE], g->st.unplaced = (int64_t)h[grid::UNPLACED];
@@ -147,8 +187,9 @@ int finalise(svh_grid* g) {
     grid::FinalJob j;
     j.prm = g->prm;
     j.cells = g->cells();
-    j.hmin = g->fplane(0), j.hmax = g->fplane(1), j.hmean = g->fplane(2);
-    j.intensity = g->bplane(0), j.cls = g->bplane(1);
+    j.count = g->iplane(F_COUNT), j.overhead = g->iplane(F_OVERHEAD), j.pass = g->iplane(F_PASS);
+    j.hmin = g->fplane(F_HMIN), j.hmax = g->fplane(F_HMAX), j.hmean = g->fplane(F_HMEAN);
+    j.intensity = g->bplane(B_INTENSITY), j.cls = g->bplane(B_CLASS), j.state = g->bplane(B_STATE);
     GRID_TRY(launch, (grid::launch_finalise(g->stream, j), hipGetLastError()));
     return SVH_OK;
 }
@@ -168,28 +209,18 @@ int deliver(svh_grid* g, const void* src, size_t bytes, void* out, bool on_devic
     return SVH_OK;
 }
 
-int get(svh_grid* g, int32_t plane, void* out, bool on_device) {
+// a finished plane: a 4-byte plane FinPlane k, or (bytes) the byte plane FinByte k
+int get(svh_grid* g, bool bytes, int k, void* out, bool on_device) {
     int rc = ready(g);
     if (rc) return rc;
-    const grid::Cells c = g->cells();
-    const void* src;
-    size_t elem = 4;
-    switch (plane) {
-    case grid::P_COUNT: src = c.count; break;
-    case grid::P_OVERHEAD: src = c.overhead; break;
-    case grid::P_HMIN: src = g->fplane(0); break;
-    case grid::P_HMAX: src = g->fplane(1); break;
-    case grid::P_HMEAN: src = g->fplane(2); break;
-    case grid::P_INTENSITY: src = g->bplane(0), elem = 1; break;
-    default: src = g->bplane(1), elem = 1; break;
-    }
-    const bool derived = plane >= grid::P_HMIN;
-    if (derived && (rc = finalise(g))) return rc;
-    if ((rc = deliver(g, src, g->ncells * elem, out, on_device))) return rc;
-    if (derived) g->final_valid = true;
+    const void* src = bytes ? (const void*)g->bplane(k) : (const void*)g->iplane(k);
+    if ((rc = finalise(g))) return rc;
+    if ((rc = deliver(g, src, g->ncells * (bytes ? 1 : 4), out, on_device))) return rc;
+    g->final_valid = true;
     return SVH_OK;
 }
 
+// mode: a grid::Mode, M_LOCAL included
 int render(svh_grid* g, int32_t mode, uint8_t* rgb, bool on_device) {
     int rc = ready(g);
     if (rc) return rc;
@@ -202,9 +233,9 @@ int render(svh_grid* g, int32_t mode, uint8_t* rgb, bool on_device) {
     grid::RenderJob j;
     j.prm = g->prm;
     j.mode = mode;
-    j.count = g->cells().count;
-    j.hmin = g->fplane(0), j.hmax = g->fplane(1), j.hmean = g->fplane(2);
-    j.intensity = g->bplane(0), j.cls = g->bplane(1);
+    j.count = g->iplane(F_COUNT), j.pass = g->iplane(F_PASS);
+    j.hmin = g->fplane(F_HMIN), j.hmax = g->fplane(F_HMAX), j.hmean = g->fplane(F_HMEAN);
+    j.intensity = g->bplane(B_INTENSITY), j.cls = g->bplane(B_CLASS);
     j.rgb = on_device ? rgb : g->d_rgb.p;
     GRID_TRY(launch, (grid::launch_render(g->stream, j), hipGetLastError()));
     if (on_device) {
@@ -232,6 +263,45 @@ int added(svh_grid* g, int rc) {
         mark_empty(g);
     }
     return rc;
+}
+
+// the window moves by (da, db) cells to offsets that have been checked, not both zero
+int scroll(svh_grid* g, int32_t da, int32_t db) {
+    g->prm.oa += da, g->prm.ob += db;
+    g->final_valid = false;
+    if (g->need_clear) return SVH_OK;   // the empty grid has no cell to reset
+    int rc = ready(g);
+    if (rc) return rc;
+    const int64_t ada = da < 0 ? -(int64_t)da : da, adb = db < 0 ? -(int64_t)db : db;
+    if (ada >= g->prm.nx || adb >= g->prm.nz) {
+        if ((rc = fill_empty(g))) return rc;
+    } else {
+        grid::EnterJob j;
+        j.prm = g->prm;
+        j.da = da, j.db = db;
+        j.cells = g->cells();
+        GRID_TRY(launch, (grid::launch_enter(g->stream, j), hipGetLastError()));
+    }
+    GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    return SVH_OK;
+}
+
+// xyz rounded to float once; false: a null pointer or a position that is not finite
+bool position(const double xyz[3], float p[3]) {
+    if (!xyz) return false;
+    for (int k = 0; k < 3; k++) {
+        if (!finite_d(xyz[k])) return false;
+        p[k] = (float)xyz[k];
+    }
+    return true;
+}
+
+// the logical index of the cell rays are cast from, or -1: the origin must be a LOW point of the window
+int64_t origin_cell(const svh_grid* g, const double origin[3]) {
+    float p[3];
+    if (!position(origin, p)) return -1;
+    const grid::Placed r = grid::place(g->prm, p[0], p[1], p[2], 0.f);
+    return r.fate == grid::LOW ? (int64_t)r.cell : -1;
 }
 
 }  // namespace
@@ -315,6 +385,7 @@ int32_t svh_grid_clear(svh_grid* g) {
 int32_t svh_grid_set_window(svh_grid* g, float x0, float z0) {
     if (!g || !grid::finite_f(x0) || !grid::finite_f(z0)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_window: a grid and a finite corner are needed");
     g->prm.x0 = x0, g->prm.z0 = z0;
+    g->prm.oa = g->prm.ob = 0;
     mark_empty(g);
     return SVH_OK;
 }
@@ -341,6 +412,85 @@ int32_t svh_grid_add_view(svh_grid* g, svh_view* v) {
     return added(g, rc);
 }
 
+int32_t svh_grid_add_points_from(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device, const double origin[3]) {
+    if (!g || n < 0 || (n > 0 && !xyzv) || !origin) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_points_from: bad arguments");
+    if (on_device && ((uintptr_t)xyzv & 15)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_points_from: a device array must be 16-byte aligned");
+    const int64_t oc = origin_cell(g, origin);
+    if (oc < 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_points_from: the origin must be finite, inside the window and not above the clearance");
+    if (n > kMaxPoints - g->st.added) return svh::fail(SVH_ERR_UNSUPPORTED, "svh_grid_add_points_from: more than 2^31 - 1 points since the last clear");
+    if (n == 0) return SVH_OK;
+    return added(g, add(g, xyzv, n, on_device != 0, oc));
+}
+
+int32_t svh_grid_add_view_lists_from(svh_grid* g, svh_view* v, int32_t first_list, int32_t n_lists, const double origin[3]) {
+    if (!g || !v || !origin) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_view_lists_from: null argument");
+    const view::StoreRef r = view::store_of(v);
+    if (r.device != g->device) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_view_lists_from: the view lives on another device");
+    int64_t at = 0, n = 0;
+    if (!view::list_range(v, first_list, n_lists, &at, &n))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_view_lists_from: the lists are not all in the view's sequence");
+    const int64_t oc = origin_cell(g, origin);
+    if (oc < 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_add_view_lists_from: the origin must be finite, inside the window and not above the clearance");
+    if (n > kMaxPoints - g->st.added) return svh::fail(SVH_ERR_UNSUPPORTED, "svh_grid_add_view_lists_from: more than 2^31 - 1 points since the last clear");
+    if (n == 0) return SVH_OK;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipSetDevice(g->device));
+        GRID_TRY(wait, hipStreamSynchronize(r.stream));   // the store is complete before this stream reads it
+        return add(g, (const float*)(r.pts + at), n, true, oc);
+    }();
+    return added(g, rc);
+}
+
+int32_t svh_grid_scroll(svh_grid* g, int32_t da, int32_t db) {
+    if (!g) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_scroll: null argument");
+    const int64_t ta = (int64_t)g->prm.oa + da, tb = (int64_t)g->prm.ob + db;
+    if (ta < -grid::OFFSET_LIMIT || ta > grid::OFFSET_LIMIT || tb < -grid::OFFSET_LIMIT || tb > grid::OFFSET_LIMIT)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_scroll: the offsets would leave -(2^20 - 8192) .. 2^20 - 8192");
+    if (da == 0 && db == 0) return SVH_OK;
+    return added(g, scroll(g, da, db));
+}
+
+int32_t svh_grid_get_window(svh_grid* g, int32_t off[2]) {
+    if (!g || !off) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_window: null argument");
+    off[0] = g->prm.oa, off[1] = g->prm.ob;
+    return SVH_OK;
+}
+
+int32_t svh_grid_cell_of(svh_grid* g, const double xyz[3], int32_t cell[2]) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || !cell || !position(xyz, p) || !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_cell_of: a grid, an output and a finite position with a cell below 2^20 are needed");
+    cell[0] = ga, cell[1] = gb;
+    return SVH_OK;
+}
+
+int32_t svh_grid_follow(svh_grid* g, const double xyz[3], int32_t ia, int32_t ib) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || ia < 0 || ia >= g->prm.nx || ib < 0 || ib >= g->prm.nz || !position(xyz, p) ||
+        !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_follow: a grid, a window cell and a finite position with a cell below 2^20 are needed");
+    const int64_t da = (int64_t)ga - ia - g->prm.oa, db = (int64_t)gb - ib - g->prm.ob;   // each within +-2^22
+    return svh_grid_scroll(g, (int32_t)da, (int32_t)db);
+}
+
+int32_t svh_grid_get_ray_stats(svh_grid* g, int64_t out[2]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_ray_stats: null argument");
+    out[0] = g->rays, out[1] = g->ray_cells;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_local(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::L_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_local: a grid, a plane 0..1 and an output are needed");
+    return drained(g, plane == grid::L_PASS ? get(g, false, F_PASS, out, on_device != 0) : get(g, true, B_STATE, out, on_device != 0));
+}
+
+int32_t svh_grid_render_local(svh_grid* g, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_local: a grid and an output are needed");
+    return drained(g, render(g, grid::M_LOCAL, rgb, on_device != 0));
+}
+
 int32_t svh_grid_get_stats(svh_grid* g, svh_grid_stats* stats) {
     if (!g || !stats) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_stats: null argument");
     *stats = g->st;
@@ -349,7 +499,9 @@ int32_t svh_grid_get_stats(svh_grid* g, svh_grid_stats* stats) {
 
 int32_t svh_grid_get(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
     if (!g || !out || plane < 0 || plane >= grid::P_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get: a grid, a plane 0..6 and an output are needed");
-    return drained(g, get(g, plane, out, on_device != 0));
+    static const int word[5] = {F_COUNT, F_OVERHEAD, F_HMIN, F_HMAX, F_HMEAN};
+    const bool bytes = plane >= grid::P_INTENSITY;
+    return drained(g, get(g, bytes, bytes ? (plane == grid::P_INTENSITY ? B_INTENSITY : B_CLASS) : word[plane], out, on_device != 0));
 }
 
 int32_t svh_grid_render(svh_grid* g, int32_t mode, uint8_t* rgb, int32_t on_device) {
@@ -368,6 +520,52 @@ int32_t svh_test_grid_points(const svh_grid_params* p, const float* xyzv, int64_
         if (key) key[i] = r.key;
         if (q) q[i] = r.q;
         if (v) v[i] = (uint8_t)r.v;
+    }
+    return SVH_OK;
+}
+
+// grid_core.h's place() under window offsets, on the host
+int32_t svh_test_grid_points_at(const svh_grid_params* p, int32_t oa, int32_t ob, const float* xyzv, int64_t n, int32_t* fate,
+                                uint32_t* cell, uint32_t* slot) {
+    grid::Params prm;
+    if (!convert(p, &prm) || !grid::offsets_ok(oa, ob) || n < 0 || (n > 0 && !xyzv))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_points_at: bad arguments");
+    prm.oa = oa, prm.ob = ob;
+    for (int64_t i = 0; i < n; i++) {
+        const grid::Placed r = grid::place(prm, xyzv[4 * i], xyzv[4 * i + 1], xyzv[4 * i + 2], xyzv[4 * i + 3]);
+        if (fate) fate[i] = r.fate;
+        if (cell) cell[i] = r.cell;
+        if (slot) slot[i] = r.cell == grid::NO_CELL ? grid::NO_CELL : r.slot;
+    }
+    return SVH_OK;
+}
+
+// grid_core.h's line on the host: *n = its length, and the first min(*n, cap) cells as (a, b) pairs
+int32_t svh_test_grid_line(int32_t oa, int32_t ob, int32_t ea, int32_t eb, int32_t* n, int32_t* cells, int32_t cap) {
+    const int64_t dx = (int64_t)ea - oa, dz = (int64_t)eb - ob;
+    if (!n || cap < 0 || (cap > 0 && !cells) || dx <= -grid::MAX_SIDE || dx >= grid::MAX_SIDE || dz <= -grid::MAX_SIDE ||
+        dz >= grid::MAX_SIDE)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_line: an output and two cells less than 8192 apart are needed");
+    const int32_t len = grid::line_len((int32_t)dx, (int32_t)dz);
+    for (int32_t k = 0; k < len && k < cap; k++) {
+        int32_t sx, sz;
+        grid::line_step((int32_t)dx, (int32_t)dz, len, k, &sx, &sz);
+        cells[2 * k] = oa + sx, cells[2 * k + 1] = ob + sz;
+    }
+    *n = len;
+    return SVH_OK;
+}
+
+// grid_core.h's state byte and local colour on the host, per cell
+int32_t svh_test_grid_local(const svh_grid_params* p, int64_t ncells, const uint8_t* cls, const uint8_t* intensity,
+                            const int32_t* pass, uint8_t* state, uint8_t* rgb) {
+    grid::Params prm;
+    if (!convert(p, &prm) || ncells < 0 || (ncells > 0 && (!cls || !intensity || !pass)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_local: bad arguments");
+    for (int64_t i = 0; i < ncells; i++) {
+        const grid::Final f{0.f, 0.f, 0.f, intensity[i], cls[i]};
+        if (state) state[i] = grid::state_of(prm, cls[i], pass[i]);
+        if (rgb) grid::colour_local(prm, 1, f, pass[i], rgb + 3 * i);
     }
     return SVH_OK;
 }

@@ -248,6 +248,15 @@ view::Pose to_pose(const svh_view_pose& p) { return view::Pose{p.zoom, p.rotx, p
 
 svh::view::StoreRef svh::view::store_of(const svh_view* v) { return StoreRef{v->store.p, v->total, v->device, v->stream}; }
 
+bool svh::view::list_range(const svh_view* v, int32_t first, int32_t n_lists, int64_t* at, int64_t* n) {
+    if (first < 0 || n_lists < 0 || (int64_t)first + n_lists > (int64_t)v->lens.size()) return false;
+    int64_t before = 0, in = 0;
+    for (int32_t i = 0; i < first; i++) before += v->lens[(size_t)i];
+    for (int32_t i = first; i < first + n_lists; i++) in += v->lens[(size_t)i];
+    *at = before, *n = in;
+    return true;
+}
+
 extern "C" {
 
 void svh_view_pose_default(svh_view_pose* p) {

@@ -22,6 +22,9 @@ struct StoreRef {
     hipStream_t stream;
 };
 StoreRef store_of(const svh_view* v);
+// the lists first .. first + n_lists - 1 of the sequence as a range of the store: *at points before it, *n points in it;
+// false, nothing written: first < 0, n_lists < 0, or the range ends past the view's last list
+bool list_range(const svh_view* v, int32_t first, int32_t n_lists, int64_t* at, int64_t* n);
 
 struct RenderJob {
     Frame frame;

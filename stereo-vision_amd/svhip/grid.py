@@ -12,6 +12,10 @@ RENDER_CLASS, RENDER_HEIGHT, RENDER_INTENSITY = range(3)
 UNKNOWN, FREE, OBSTACLE, DROP, OVERHANG = 0, 1, 2, 3, 0x80
 LOW, FATE_OVERHEAD, OUTSIDE, UNPLACED = range(4)
 PLANE_DTYPE = [np.int32, np.int32, np.float32, np.float32, np.float32, np.uint8, np.uint8]
+LOCAL_PASS, LOCAL_STATE = range(2)
+LOCAL_DTYPE = [np.int32, np.uint8]
+SEEN = 0x40
+SEEN_COLOUR = (96, 112, 96)
 
 
 class Params(C.Structure):
@@ -62,6 +66,18 @@ def _bind():
         L.svh_grid_render.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.svh_test_grid_points.argtypes = [C.POINTER(Params), C.c_void_p, C.c_int64] + [C.c_void_p] * 5
         L.svh_test_grid_finalise.argtypes = [C.POINTER(Params), C.c_int64] + [C.c_void_p] * 12
+        L.svh_grid_scroll.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.svh_grid_get_window.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_cell_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svh_grid_follow.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+        L.svh_grid_add_points_from.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.svh_grid_add_view_lists_from.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.svh_grid_get_ray_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_get_local.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_render_local.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_test_grid_points_at.argtypes = [C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
+        L.svh_test_grid_line.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_test_grid_local.argtypes = [C.POINTER(Params), C.c_int64] + [C.c_void_p] * 5
         L._grid_bound = True
     return L
 
@@ -116,6 +132,36 @@ def core_finalise(params, count, overhead, kmin, kmax, hsum, vsum):
     return tuple(out)
 
 
+def core_points_at(params, oa, ob, xyzv):
+    """place() of csrc/grid_core.h under window offsets (oa, ob), on the host: (fate int32, logical cell uint32, slot uint32)"""
+    p = np.ascontiguousarray(xyzv, np.float32).reshape(-1, 4)
+    n = len(p)
+    out = (np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32))
+    _check(_bind().svh_test_grid_points_at(C.byref(params), oa, ob, p.ctypes.data if n else None, n, *[a.ctypes.data for a in out]))
+    return out
+
+
+def core_line(oa, ob, ea, eb):
+    """the line of csrc/grid_core.h from cell (oa, ob) to cell (ea, eb), on the host: [n, 2] int32, the end cell excluded"""
+    n = C.c_int32(-1)
+    cap = max(abs(ea - oa), abs(eb - ob), 1)
+    cells = np.zeros((cap, 2), np.int32)
+    _check(_bind().svh_test_grid_line(oa, ob, ea, eb, C.addressof(n), cells.ctypes.data, cap))
+    return cells[:n.value].copy()
+
+
+def core_local(params, cls, intensity, pass_):
+    """state byte and local colour of csrc/grid_core.h on the host: (state uint8 [n], rgb uint8 [n, 3])"""
+    ins = [np.ascontiguousarray(cls, np.uint8).ravel(), np.ascontiguousarray(intensity, np.uint8).ravel(),
+           np.ascontiguousarray(pass_, np.int32).ravel()]
+    n = len(ins[0])
+    out = [np.zeros(n, np.uint8), np.zeros((n, 3), np.uint8)]
+    _check(_bind().svh_test_grid_local(C.byref(params), n, *[a.ctypes.data for a in ins + out]))
+    return tuple(out)
+
+
+def _xyz(p):
+    return np.ascontiguousarray(p, np.float64).reshape(3)
 
 
 class Grid:
@@ -133,7 +179,7 @@ class Grid:
         _check(self._L.svh_grid_clear(self._h))
 
     def set_window(self, x0, z0):
-        _check(self._L.svh_grid_set_window(self._h, x0, z0))
+        _check(self._L.svh_grid_set_window(self._h, x0, z0))   # the offsets are zero again
         self.params.x0, self.params.z0 = x0, z0
 
     def add_points(self, xyzv):
@@ -148,6 +194,65 @@ class Grid:
     def add_view(self, view):
         """the whole store of a svhip.view.View, device to device"""
         _check(self._L.svh_grid_add_view(self._h, view._h))
+
+    def scroll(self, da, db):
+        """the window moves by whole cells and keeps what stays inside"""
+        _check(self._L.svh_grid_scroll(self._h, da, db))
+
+    def follow(self, xyz, ia, ib):
+        """scrolls so that the cell of the map-frame position xyz becomes window cell (ia, ib)"""
+        _check(self._L.svh_grid_follow(self._h, _xyz(xyz).ctypes.data, ia, ib))
+
+    def window(self):
+        """the offsets (oa, ob) in cells"""
+        off = np.zeros(2, np.int32)
+        _check(self._L.svh_grid_get_window(self._h, off.ctypes.data))
+        return int(off[0]), int(off[1])
+
+    def cell_of(self, xyz):
+        """the global cell (ga, gb) of a map-frame position"""
+        cell = np.zeros(2, np.int32)
+        _check(self._L.svh_grid_cell_of(self._h, _xyz(xyz).ctypes.data, cell.ctypes.data))
+        return int(cell[0]), int(cell[1])
+
+    def add_points_from(self, xyzv, origin):
+        """add_points, and one ray per low point from the cell of the map-frame position `origin`"""
+        p = np.ascontiguousarray(xyzv, np.float32).reshape(-1, 4)
+        _check(self._L.svh_grid_add_points_from(self._h, p.ctypes.data if len(p) else None, len(p), 0, _xyz(origin).ctypes.data))
+
+    def add_points_device_from(self, ptr, n, origin):
+        """the same from a raw device address (int), 16-byte aligned"""
+        _check(self._L.svh_grid_add_points_from(self._h, ptr, n, 1, _xyz(origin).ctypes.data))
+
+    def add_view_lists_from(self, view, first_list, n_lists, origin):
+        """lists first_list .. first_list + n_lists - 1 of a svhip.view.View, device to device, with rays from `origin`"""
+        _check(self._L.svh_grid_add_view_lists_from(self._h, view._h, first_list, n_lists, _xyz(origin).ctypes.data))
+
+    def ray_stats(self):
+        """(rays, ray_cells) since the last clear"""
+        out = np.zeros(2, np.int64)
+        _check(self._L.svh_grid_get_ray_stats(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1])
+
+    def local_plane(self, which, device_ptr=None):
+        """LOCAL_PASS int32 or LOCAL_STATE uint8, [nz, nx]; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_local(self._h, which, device_ptr, 1))
+            return None
+        if not 0 <= which < len(LOCAL_DTYPE):
+            raise SvhError(ERR_BAD_ARG, "no such plane")
+        out = np.zeros((self.nz, self.nx), LOCAL_DTYPE[which])
+        _check(self._L.svh_grid_get_local(self._h, which, out.ctypes.data, 0))
+        return out
+
+    def render_local(self, device_ptr=None):
+        """render(RENDER_CLASS) with the cells that are unknown and seen in SEEN_COLOUR"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_local(self._h, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_local(self._h, img.ctypes.data, 0))
+        return img
 
     def stats(self):
         st = Stats()

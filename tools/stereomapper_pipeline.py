@@ -15,6 +15,7 @@ without the GUI.  Usage:
                                           [--panes DIR [--pane-size WxH]] [--lockstep K]
                                           [--thin S [--thin-every N]] [--ply FILE]
                                           [--grid DIR [--grid-cell S] [--grid-size NXxNZ] [--level]]
+                                          [--grid-local DIR [--grid-cell S] [--grid-size NXxNZ]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -57,6 +58,16 @@ along (256x256); the window is centred on the first camera and starts at it.  Th
 above the road unless --level is given: then the road plane is estimated once, from the first frame's D1 on the device
 (include/svh_plane.h), and levels the grid (svh_grid_frame_plane); if that estimate finds no plane the tool says so and
 falls back to the level camera.  The per-frame lines are what they are without the flag.  Not with --lockstep.
+
+--grid-local DIR: the ground grid as a local map, after every frame into DIR/local_%06d.ppm.  Nothing is cleared or
+rebuilt.  Per frame the window follows the camera centre (the translation of the pose given to add_camera) so that it
+stands in the middle cell (svh_grid_follow: what stays inside is kept, the strips that enter are empty), the NEWEST list
+the frame appended to the view is binned with one ray per low point from that centre
+(svh_grid_add_view_lists_from, device to device), and svh_grid_render_local colours the grid as --grid does, with the
+cells that are unknown but were looked through -- at least min_points rays passed -- in grey-green (96, 112, 96).  The
+list the map fusion revises (the one before the newest) is NOT added again: the local map keeps the points that list
+had when it was the newest.  --grid-cell and --grid-size apply; the frame is the level camera's.  --grid stays what it
+is and may be given too.  Not with --lockstep.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -122,6 +133,7 @@ class Pipeline:
         self.thin, self.thin_every, self.appends = thin, thin_every, 0
         self.histnorm = None   # svhip.histnorm.HistNorm of the frame size, made on the first frame
         self.grid = None       # svhip.grid.Grid once enable_grid() has been called
+        self.local = None      # svhip.grid.Grid once enable_grid_local() has been called
         self.grid_level = False
         self.grid_note = None
         self.frame = None      # what render_panes() shows: (I1, I2 or None when resident, w, h, vo ok, ELAS ok)
@@ -154,6 +166,23 @@ class Pipeline:
         self.grid = grid.Grid(grid.default_params(T=T, **self.grid_kw))
         self.grid_note = "grid levelled by the road plane of frame 0: camera %.3f m above the road, pitch %.4f rad" % (
             T[2, 3], float(pe.pitch()))
+
+    def enable_grid_local(self, cell=0.2, size=(256, 256)):
+        """a second ground grid of size = (nx, nz) cells that accumulates and follows the camera (local_step)"""
+        from svhip import grid
+        self.local = grid.Grid(grid.default_params(nx=size[0], nz=size[1], cell=cell, x0=-0.5 * size[0] * cell, z0=0.0))
+        self.local_appends = 0
+
+    def local_step(self):
+        """follow the camera centre to the middle cell, add the newest list with rays from it, render: [nz, nx, 3]"""
+        from svhip import view
+        g = self.local
+        if self.appends > self.local_appends:   # a frame whose ELAS failed appends nothing
+            self.local_appends = self.appends
+            centre = self.H_total[:3, 3].copy()
+            g.follow(centre, g.nx // 2, g.nz // 2)
+            g.add_view_lists_from(self.view, self.view.count(view.LISTS) - 1, 1, centre)
+        return g.render_local()
 
     def render_grid(self):
         """the grid of the view's store as it is now, rebuilt: [nz, nx, 3] uint8, forward up"""
@@ -419,6 +448,7 @@ def main():
         sys.argv.remove("--normalize")
     thin, thin_every, ply = None, 1, None
     grid_dir, grid_cell, grid_size = None, 0.2, (256, 256)
+    local_dir = None
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -437,8 +467,12 @@ def main():
             k = sys.argv.index("--grid")
             grid_dir = sys.argv[k + 1]
             del sys.argv[k:k + 2]
+        if "--grid-local" in sys.argv:
+            k = sys.argv.index("--grid-local")
+            local_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
         assert grid_dir or not level
-        assert not (grid_dir and lockstep)
+        assert not ((grid_dir or local_dir) and lockstep)
         if "--thin" in sys.argv:
             k = sys.argv.index("--thin")
             thin = float(sys.argv[k + 1])
@@ -490,12 +524,16 @@ def main():
         rp = rectify.params_from_kitti(calib, 0, 1)
     if grid_dir:
         os.makedirs(grid_dir, exist_ok=True)
+    if local_dir:
+        os.makedirs(local_dir, exist_ok=True)
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
                  thin=thin, thin_every=thin_every)
     if grid_dir:
         p.enable_grid(grid_cell, grid_size, level)
+    if local_dir:
+        p.enable_grid_local(grid_cell, grid_size)
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -510,6 +548,8 @@ def main():
                 view.write_ppm(os.path.join(panes_dir, "%s_%06d.ppm" % (name, frames - 1)), img)
         if grid_dir:
             view.write_ppm(os.path.join(grid_dir, "grid_%06d.ppm" % (frames - 1)), p.render_grid())
+        if local_dir:
+            view.write_ppm(os.path.join(local_dir, "local_%06d.ppm" % (frames - 1)), p.local_step())
         if frames >= limit:
             break
     dt = time.perf_counter() - t0
@@ -521,6 +561,10 @@ def main():
         st = p.grid.stats()
         print("grid %d x %d cells of %g: %d of %d points binned, %d overhead, %d outside, %d unplaced; %d images in %s" % (
             p.grid.nx, p.grid.nz, grid_cell, st.binned, st.added, st.overhead, st.outside, st.unplaced, frames, grid_dir))
+    if local_dir:
+        st, (rays, ray_cells), (oa, ob) = p.local.stats(), p.local.ray_stats(), p.local.window()
+        print("local grid %d x %d cells of %g at offsets (%d, %d): %d of %d points binned, %d rays over %d cells; %d images in %s" % (
+            p.local.nx, p.local.nz, grid_cell, oa, ob, st.binned, st.added, rays, ray_cells, frames, local_dir))
     if render_dir:
         n, images = p.view.record_human()
         for k in range(n):
