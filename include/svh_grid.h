@@ -29,7 +29,18 @@
  * window and below the clearance.  PASS is an integer sum too: it depends only on the multiset of (origin cell, end
  * cell) pairs.  A cell is SEEN when PASS >= min_points: unknown and seen is "looked through and found empty", unknown
  * and not seen is "never looked at".
- * Not done: slope or neighbour-cell tests.
+ *
+ * TRAVERSABILITY: what a planner reads, derived on the device from the finished planes (svh_grid_trav_params below).
+ * A free cell is STEEP if one of its up to eight neighbours inside the window is free too and fabsf(HMEAN - HMEAN') exceeds
+ * the rise: rise4 = max_slope * cell across an edge, rise8 = rise4 * 1.41421354f across a corner (one fp32 operation each).
+ * Only free-free pairs are tested -- an obstacle does not thicken through its neighbours -- and both cells of a steep pair
+ * are steep.  A cell is LETHAL if it matches a bit of the `lethal` mask: obstacle, drop, steep, unknown and not seen, unknown
+ * and seen.  DIST2 is the exact squared Euclidean distance in cells to the nearest lethal cell of the window where that is at
+ * most reach^2, reach = (int)ceil((double)inflate / (double)cell) in 1..256, else SVH_GRID_DIST2_FAR; a lethal cell has 0.
+ * COST is one byte, a function of DIST2 alone, from a table filled in double on the host: 254 for DIST2 0; with
+ * d = sqrt((double)DIST2) * (double)cell, 253 for d <= inscribed, 1 + (int)floor(251.0 * (inflate - d) / (inflate - inscribed))
+ * (1..252) for d < inflate, else 0, and 0 for FAR.  A cell that is unknown and not lethal has 255, "no information", where
+ * the table says 0.  The three planes are cached until the grid or the parameters change; a scroll needs nothing new.
  *
  * Plain C like svh_view.h.  An object has its own stream and every call returns when it is complete.  Calls return
  * SVH_OK or a negative SVH_ERR_*; svh_last_error() has the text.  SVH_ERR_BAD_ARG -- a null pointer, parameters out of
@@ -39,7 +50,8 @@
  * clear (counts are 32 bits).  After SVH_ERR_HIP inside svh_grid_add_* or svh_grid_scroll / svh_grid_follow the grid is
  * EMPTY (accumulation is in place, a half-done call cannot be taken back): all statistics are zero, the next add starts
  * afresh, and after a failed scroll the window stands at its new offsets.  After SVH_ERR_HIP
- * inside svh_grid_get or svh_grid_render the accumulated grid is untouched.
+ * inside svh_grid_get, svh_grid_render, svh_grid_get_trav, svh_grid_render_cost or svh_grid_set_traversability the
+ * accumulated grid is untouched.
  */
 #ifndef SVH_GRID_H
 #define SVH_GRID_H
@@ -137,6 +149,40 @@ int32_t   svh_grid_render(svh_grid* g, int32_t mode, uint8_t* rgb, int32_t on_de
 int32_t   svh_grid_get_local(svh_grid* g, int32_t plane, void* out, int32_t on_device);
 /* SVH_GRID_RENDER_CLASS, except that a cell that is unknown and seen is (96, 112, 96) instead of (32, 32, 32) */
 int32_t   svh_grid_render_local(svh_grid* g, uint8_t* rgb, int32_t on_device);
+
+
+/* bits of svh_grid_trav_params.lethal */
+#define SVH_GRID_LETHAL_OBSTACLE      1u    /* class obstacle */
+#define SVH_GRID_LETHAL_DROP          2u    /* class drop */
+#define SVH_GRID_LETHAL_STEEP         4u    /* steep */
+#define SVH_GRID_LETHAL_UNSEEN        8u    /* unknown and not seen */
+#define SVH_GRID_LETHAL_UNKNOWN_SEEN  16u   /* unknown and seen */
+#define SVH_GRID_DIST2_FAR  0x7FFFFFFF      /* DIST2 of a cell with no lethal cell within reach */
+
+typedef struct svh_grid_trav_params {
+    float    max_slope;        /* 0.35: rise over run between neighbouring free cells; finite, > 0 */
+    float    inscribed;        /* 0.4: metres; closer to a lethal cell than this is as good as lethal; finite, >= 0 */
+    float    inflate;          /* 1.5: metres; beyond this a lethal cell costs nothing; finite, > inscribed */
+    uint32_t lethal;           /* obstacle, drop, steep: a mask of SVH_GRID_LETHAL_*, no other bits */
+} svh_grid_trav_params;
+
+void      svh_grid_trav_params_default(svh_grid_trav_params* t);
+/* checks the parameters, derives rise4, rise8 and reach for the grid's cell and uploads the cost table.  SVH_ERR_BAD_ARG,
+ * nothing changed: a parameter out of its range, or a reach outside 1..256.  A grid is created with the defaults; if their
+ * reach is outside 1..256 for the grid's cell the object exists, and svh_grid_get_trav and svh_grid_render_cost return
+ * SVH_ERR_BAD_ARG until this call succeeds.  After SVH_ERR_HIP the parameters are set and the next svh_grid_get_trav or
+ * svh_grid_render_cost uploads the table again. */
+int32_t   svh_grid_set_traversability(svh_grid* g, const svh_grid_trav_params* t);
+/* the parameters in force and their reach in cells (0 while the defaults do not fit); either output may be NULL, not both */
+int32_t   svh_grid_get_traversability(svh_grid* g, svh_grid_trav_params* t, int32_t* reach);
+/* planes of svh_grid_get_trav, laid out as those of svh_grid_get */
+#define SVH_GRID_TRAV_FLAGS 0   /* uint8: bit 0 steep, bit 1 lethal */
+#define SVH_GRID_TRAV_DIST2 1   /* int32 */
+#define SVH_GRID_TRAV_COST  2   /* uint8 */
+int32_t   svh_grid_get_trav(svh_grid* g, int32_t plane, void* out, int32_t on_device);
+/* the cost as nx x nz RGB8, rows as svh_grid_render: 254 (255, 0, 0), 253 (255, 128, 0), c in 1..252 (c, 0, 255 - c),
+ * 0 (0, 96, 0), 255 (32, 32, 32); a steep cell has the green byte 255 */
+int32_t   svh_grid_render_cost(svh_grid* g, uint8_t* rgb, int32_t on_device);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,9 @@
 //     into tests/cxx/grid_line_check.cpp, which runs the line and the offset place() at their extremes,
 // and restated in numpy by tests/grid_ref.py, which tests/test_grid.py pins by hand and against the test entries; the
 // window's offsets, the line of a ray, the state byte and the local colour (svh_test_grid_points_at / svh_test_grid_line
-// / svh_test_grid_local) by tests/grid_local_ref.py and tests/test_grid_local.py.
+// / svh_test_grid_local) by tests/grid_local_ref.py and tests/test_grid_local.py; the traversability layer (the kernels of
+// csrc/grid_trav_kernels.hip, svh_test_grid_trav / svh_test_grid_cost_table, tests/cxx/grid_trav_check.cpp) by
+// tests/grid_trav_ref.py and tests/test_grid_trav.py.
 // fp32 in the order written, every operation rounded once (-ffp-contract=off on every build, no fast-math), the
 // divisions IEEE's (div_rn), denormals kept.  Every range decision is made on the float BEFORE a conversion to an
 // integer: an out-of-range conversion is undefined on the host and saturates on the device.
@@ -261,6 +263,142 @@ MC_FN void colour_local(const Params& p, int32_t count, const Final& f, int32_t 
     if ((f.cls & 3) == C_UNKNOWN && pass >= p.min_points) {
         rgb[0] = SEEN_R, rgb[1] = SEEN_G, rgb[2] = (f.cls & C_OVERHANG) ? 255 : SEEN_B;
     }
+}
+
+// TRAVERSABILITY (svh_grid_set_traversability, svh_grid_get_trav, svh_grid_render_cost): what a planner reads.  All of it
+// is computed from the finished planes CLASS, HMEAN and STATE in logical order; the torus plays no part.
+//   FLAGS  bit 0 steep: a free cell with a free neighbour (of its up to eight inside the window) whose HMEAN differs by
+//          more than the rise -- rise4 across an edge, rise8 across a corner.  Only free-free pairs are tested, and the
+//          relation is symmetric: both cells of a steep pair are steep.  Bit 1 lethal: the cell's state matches a bit of
+//          the lethal mask.
+//   DIST2  the exact squared distance, in cells, to the nearest lethal cell of the window where that is at most reach^2,
+//          else DIST2_FAR.  Separable: g(ia, ib) is the distance along ib to the nearest lethal cell of column ia, capped
+//          at reach + 1 (col_step, forwards and backwards); DIST2(ia, ib) is the least (ia - j)^2 + g(j, ib)^2 over
+//          |j - ia| <= reach with g(j, ib) <= reach (row_dist2).  A lethal cell within reach^2 is at most reach away on
+//          either axis, so the cap and the bound lose nothing.
+//   COST   one byte, table[DIST2] with the table of cost_of (reach^2 + 1 bytes, filled on the host in double), 0 for FAR;
+//          a cell that is unknown and not lethal says 255, "no information", where the table says 0.
+enum TravPlane : int32_t { TV_FLAGS = 0, TV_DIST2, TV_COST, TV_PLANES };
+enum TravFlag : uint8_t { TF_STEEP = 1, TF_LETHAL = 2 };
+enum Lethal : uint32_t { LETHAL_OBSTACLE = 1, LETHAL_DROP = 2, LETHAL_STEEP = 4, LETHAL_UNSEEN = 8, LETHAL_UNKNOWN_SEEN = 16,
+                         LETHAL_ALL = 31 };
+constexpr int32_t DIST2_FAR = 0x7FFFFFFF;
+constexpr int32_t MAX_REACH = 256;
+constexpr uint8_t COST_LETHAL = 254, COST_INSCRIBED = 253, COST_NO_INFORMATION = 255;
+
+// svh_grid_trav_params and what trav_derive derives from it for the grid's cell
+struct TravParams {
+    float max_slope, inscribed, inflate;
+    uint32_t lethal;
+    float rise4, rise8;   // the largest difference of HMEAN that is not steep, across an edge and across a corner
+    int32_t reach;        // cells; 0 until trav_derive succeeds
+};
+
+// the checks behind SVH_ERR_BAD_ARG of svh_grid_set_traversability, and the derived values.  The quotient is compared
+// as a double before it becomes an integer.
+MC_FN bool trav_derive(TravParams& t, float cell) {
+    t.reach = 0;
+    if (!(finite_f(t.max_slope) && t.max_slope > 0.f && finite_f(t.inscribed) && t.inscribed >= 0.f && finite_f(t.inflate) &&
+          t.inflate > t.inscribed && (t.lethal & ~(uint32_t)LETHAL_ALL) == 0u))
+        return false;
+    t.rise4 = t.max_slope * cell;
+    t.rise8 = t.rise4 * 1.41421354f;
+    const double r = ceil((double)t.inflate / (double)cell);
+    if (!(r >= 1.0 && r <= (double)MAX_REACH)) return false;
+    t.reach = (int32_t)r;
+    return true;
+}
+
+// the flags byte of window cell (ia, ib) from the finished planes
+MC_FN uint8_t trav_flags(const TravParams& t, int32_t nx, int32_t nz, const uint8_t* cls, const float* hmean,
+                         const uint8_t* state, int32_t ia, int32_t ib) {
+    const size_t i = (size_t)ib * (size_t)nx + (size_t)ia;
+    const uint8_t c = cls[i] & 3;
+    bool steep = false;
+    if (c == C_FREE) {
+        const float h = hmean[i];
+        for (int32_t db = -1; db <= 1; db++)
+            for (int32_t da = -1; da <= 1; da++) {
+                const int32_t ja = ia + da, jb = ib + db;
+                if ((da == 0 && db == 0) || ja < 0 || ja >= nx || jb < 0 || jb >= nz) continue;
+                const size_t j = (size_t)jb * (size_t)nx + (size_t)ja;
+                if ((cls[j] & 3) != C_FREE) continue;
+                steep = steep || fabsf(h - hmean[j]) > ((da != 0 && db != 0) ? t.rise8 : t.rise4);
+            }
+    }
+    const uint32_t is = c == C_OBSTACLE ? LETHAL_OBSTACLE : c == C_DROP ? LETHAL_DROP
+                        : c == C_UNKNOWN ? ((state[i] & C_SEEN) ? LETHAL_UNKNOWN_SEEN : LETHAL_UNSEEN) : 0u;
+    const bool lethal = ((is | (steep ? (uint32_t)LETHAL_STEEP : 0u)) & t.lethal) != 0u;
+    return (uint8_t)((steep ? TF_STEEP : 0) | (lethal ? TF_LETHAL : 0));
+}
+
+// one step of a column sweep: d is the capped distance at the cell before (reach + 1 in front of the first)
+MC_FN int32_t col_step(int32_t d, bool lethal, int32_t reach) { return lethal ? 0 : (d < reach ? d + 1 : reach + 1); }
+
+// DIST2 of column ia from one row of g: g[j - base] for the columns j = lo .. hi, which are those of the window within
+// reach of ia.  At most 2 * 256^2.
+MC_FN int32_t row_dist2(const uint16_t* g, int32_t base, int32_t ia, int32_t lo, int32_t hi, int32_t reach) {
+    int32_t best = DIST2_FAR;
+    for (int32_t j = lo; j <= hi; j++) {
+        const int32_t gv = (int32_t)g[j - base];
+        const int32_t d = (ia - j) * (ia - j) + gv * gv;
+        best = (gv <= reach && d < best) ? d : best;
+    }
+    return best <= reach * reach ? best : DIST2_FAR;
+}
+
+// the cost table's entry for a squared distance in cells: double, in the order written.  Host only: the device reads the table.
+inline uint8_t cost_of(int32_t d2, float cell, float inscribed, float inflate) {
+    if (d2 == 0) return COST_LETHAL;
+    if (d2 == DIST2_FAR) return 0;
+    const double d = sqrt((double)d2) * (double)cell;
+    if (d <= (double)inscribed) return COST_INSCRIBED;
+    if (d < (double)inflate) return (uint8_t)(1 + (int)floor(251.0 * ((double)inflate - d) / ((double)inflate - (double)inscribed)));
+    return 0;
+}
+
+// the cost byte of a cell from its table entry (0 for DIST2_FAR)
+MC_FN uint8_t cell_cost(uint8_t table_cost, uint8_t cls, uint8_t flags) {
+    return ((cls & 3) == C_UNKNOWN && !(flags & TF_LETHAL) && table_cost == 0) ? COST_NO_INFORMATION : table_cost;
+}
+
+// svh_grid_render_cost
+MC_FN void colour_cost(uint8_t cost, uint8_t flags, uint8_t* rgb) {
+    if (cost == COST_LETHAL) rgb[0] = 255, rgb[1] = 0, rgb[2] = 0;
+    else if (cost == COST_INSCRIBED) rgb[0] = 255, rgb[1] = 128, rgb[2] = 0;
+    else if (cost == COST_NO_INFORMATION) rgb[0] = rgb[1] = rgb[2] = 32;
+    else if (cost == 0) rgb[0] = 0, rgb[1] = 96, rgb[2] = 0;
+    else rgb[0] = cost, rgb[1] = 0, rgb[2] = (uint8_t)(255 - cost);
+    if (flags & TF_STEEP) rgb[1] = 255;
+}
+
+// The whole layer on the host (svh_test_grid_trav, tests/cxx/grid_trav_check.cpp): the planes of a window from CLASS,
+// HMEAN and STATE.  `table` has reach^2 + 1 bytes, `g` is nx * nz of scratch; any of dist2, cost may be null.
+inline void trav_window(const TravParams& t, int32_t nx, int32_t nz, const uint8_t* cls, const float* hmean, const uint8_t* state,
+                        const uint8_t* table, uint8_t* flags, uint16_t* g, int32_t* dist2, uint8_t* cost) {
+    for (int32_t ib = 0; ib < nz; ib++)
+        for (int32_t ia = 0; ia < nx; ia++) flags[(size_t)ib * nx + ia] = trav_flags(t, nx, nz, cls, hmean, state, ia, ib);
+    for (int32_t ia = 0; ia < nx; ia++) {
+        int32_t d = t.reach + 1;
+        for (int32_t ib = 0; ib < nz; ib++) {
+            const size_t i = (size_t)ib * nx + ia;
+            g[i] = (uint16_t)(d = col_step(d, (flags[i] & TF_LETHAL) != 0, t.reach));
+        }
+        d = t.reach + 1;
+        for (int32_t ib = nz - 1; ib >= 0; ib--) {
+            const size_t i = (size_t)ib * nx + ia;
+            d = col_step(d, (flags[i] & TF_LETHAL) != 0, t.reach);
+            g[i] = (uint16_t)(d < (int32_t)g[i] ? d : (int32_t)g[i]);
+        }
+    }
+    for (int32_t ib = 0; ib < nz; ib++)
+        for (int32_t ia = 0; ia < nx; ia++) {
+            const size_t i = (size_t)ib * nx + ia;
+            const int32_t lo = ia - t.reach < 0 ? 0 : ia - t.reach, hi = ia + t.reach > nx - 1 ? nx - 1 : ia + t.reach;
+            const int32_t d2 = row_dist2(g + (size_t)ib * nx, 0, ia, lo, hi, t.reach);
+            if (dist2) dist2[i] = d2;
+            if (cost) cost[i] = cell_cost(d2 == DIST2_FAR ? (uint8_t)0 : table[d2], cls[i], flags[i]);
+        }
 }
 
 // the checks behind SVH_ERR_BAD_ARG of svh_grid_create

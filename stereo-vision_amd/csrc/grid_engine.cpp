@@ -3,8 +3,8 @@
 //
 // Host (this file): the parameters (T rounded to float once), the two frames, the window's offsets, the statistics, the
 // lazy clear and the lazy finalise.  Device (grid_kernels.hip): the binning, the rays, the strips of a scroll, the
-// finalise, the render.  The arithmetic is csrc/grid_core.h.  The
-// object has its own stream; every entry returns when it is complete.
+// finalise, the render; (grid_trav_kernels.hip): the traversability layer -- flags, obstacle distance, cost, its render.
+// The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
 // empty, and the next entry that touches the device fills the planes with the empty values first.  That is what makes
@@ -12,12 +12,14 @@
 // needed to get there.  The finished planes are derived lazily too, by the first get or render after a change: the
 // accumulators lie at their slots (the torus of grid_core.h), the finished planes are in logical order, and every plane
 // that leaves the object is a finished one.  A scroll moves no data: it changes the offsets and resets the strips that
-// enter; on an empty grid it changes the offsets alone.
+// enter; on an empty grid it changes the offsets alone.  The traversability planes are derived from the finished ones, as
+// lazily, and kept until the accumulators or the traversability parameters change (trav_valid).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "../../include/svh_grid.h"
 #include "grid_core.h"
@@ -38,6 +40,7 @@ constexpr int64_t kHostChunk = (int64_t)1 << 22;   // points of a host array sta
 constexpr size_t kFinalBytes = 27;                 // per cell: COUNT, OVERHEAD, PASS, HMIN, HMAX, HMEAN; INTENSITY, CLASS, STATE
 enum FinPlane { F_COUNT = 0, F_OVERHEAD, F_PASS, F_HMIN, F_HMAX, F_HMEAN, F_WORDS };   // the 4-byte planes of `fin`
 enum FinByte { B_INTENSITY = 0, B_CLASS, B_STATE };                                    // its byte planes
+constexpr size_t kTravBytes = 8;                   // per cell: DIST2; g (uint16); FLAGS, COST
 
 bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
@@ -75,6 +78,14 @@ struct svh_grid {
     PinnedBuf<uint8_t> h_out;
     bool need_clear = true;     // the accumulators do not hold the empty grid yet
     bool final_valid = false;   // `fin` is derived from the accumulators as they are
+    grid::TravParams trv{};     // the traversability layer: parameters and what is derived from them; reach 0: the
+    bool trav_ok = false;       // defaults do not fit this grid's cell, and svh_grid_set_traversability has not succeeded
+    std::vector<uint8_t> table; // cost by DIST2, reach^2 + 1 bytes
+    bool table_sent = false;    // d_table holds it
+    HipBuf<uint8_t> d_table;
+    PinnedBuf<uint8_t> h_table;
+    HipBuf<uint8_t> trav;       // kTravBytes per cell: DIST2 | g | FLAGS | COST, logical order
+    bool trav_valid = false;    // ... derived from `fin` as it is, with the parameters as they are; implies final_valid
     svh_grid_stats st{0, 0, 0, 0, 0};
     int64_t rays = 0, ray_cells = 0;
 
@@ -87,13 +98,20 @@ struct svh_grid {
     float* fplane(int k) const { return (float*)(fin.p + 4 * ncells * (size_t)k); }
     int32_t* iplane(int k) const { return (int32_t*)(fin.p + 4 * ncells * (size_t)k); }
     uint8_t* bplane(int k) const { return fin.p + 4 * F_WORDS * ncells + ncells * (size_t)k; }
+    int32_t* t_dist2() const { return (int32_t*)trav.p; }
+    uint16_t* t_g() const { return (uint16_t*)(trav.p + 4 * ncells); }
+    uint8_t* t_flags() const { return trav.p + 6 * ncells; }
+    uint8_t* t_cost() const { return trav.p + 7 * ncells; }
 };
 
 namespace {
 
+// the accumulators change: what was derived from them is stale
+void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = false; }
+
 void mark_empty(svh_grid* g) {
     g->need_clear = true;
-    g->final_valid = false;
+    invalidate(g);
     g->st = svh_grid_stats{0, 0, 0, 0, 0};
     g->rays = g->ray_cells = 0;
 }
@@ -127,7 +145,7 @@ int ready(svh_grid* g) {
 int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origin = -1) {
     int rc = ready(g);
     if (rc) return rc;
-    g->final_valid = false;
+    invalidate(g);
     grid::BinJob j;
     j.prm = g->prm;
     j.cells = g->cells();
@@ -247,6 +265,84 @@ int render(svh_grid* g, int32_t mode, uint8_t* rgb, bool on_device) {
     return SVH_OK;
 }
 
+// svh_grid_trav_params -> grid::TravParams with the derived values and the cost table for a cell side; false: out of range
+bool convert_trav(const svh_grid_trav_params* t, float cell, grid::TravParams* q, std::vector<uint8_t>* table) {
+    if (!t) return false;
+    q->max_slope = t->max_slope, q->inscribed = t->inscribed, q->inflate = t->inflate, q->lethal = t->lethal;
+    if (!grid::trav_derive(*q, cell)) return false;
+    if (table) {
+        table->resize((size_t)q->reach * (size_t)q->reach + 1);
+        for (size_t d2 = 0; d2 < table->size(); d2++) (*table)[d2] = grid::cost_of((int32_t)d2, cell, q->inscribed, q->inflate);
+    }
+    return true;
+}
+
+// the cost table lies on the device
+int send_table(svh_grid* g) {
+    if (g->table_sent) return SVH_OK;
+    GRID_TRY(none, hipSetDevice(g->device));
+    const size_t bytes = g->table.size();
+    GRID_GROW(g->d_table, bytes);
+    GRID_GROW(g->h_table, bytes);
+    memcpy(g->h_table, g->table.data(), bytes);
+    GRID_TRY(copy, hipMemcpyAsync(g->d_table, g->h_table, bytes, hipMemcpyHostToDevice, g->stream));
+    GRID_TRY(wait, hipStreamSynchronize(g->stream));   // the staging buffer is free again
+    g->table_sent = true;
+    return SVH_OK;
+}
+
+// the finished planes and the three traversability planes, launched on the stream; the caller waits and then sets
+// final_valid and trav_valid
+int traverse(svh_grid* g) {
+    if (g->trav_valid) return SVH_OK;
+    GRID_GROW(g->trav, g->ncells * kTravBytes);
+    int rc = send_table(g);
+    if (rc) return rc;
+    if ((rc = finalise(g))) return rc;
+    grid::TravJob j;
+    j.trv = g->trv;
+    j.nx = g->prm.nx, j.nz = g->prm.nz;
+    j.cls = g->bplane(B_CLASS), j.hmean = g->fplane(F_HMEAN), j.state = g->bplane(B_STATE);
+    j.table = g->d_table.p;
+    j.flags = g->t_flags(), j.g = g->t_g(), j.dist2 = g->t_dist2(), j.cost = g->t_cost();
+    GRID_TRY(launch, (grid::launch_trav(g->stream, j), hipGetLastError()));
+    return SVH_OK;
+}
+
+int get_trav(svh_grid* g, int32_t plane, void* out, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = traverse(g))) return rc;
+    const void* src = plane == grid::TV_FLAGS ? (const void*)g->t_flags() : plane == grid::TV_DIST2 ? (const void*)g->t_dist2()
+                                                                                                   : (const void*)g->t_cost();
+    if ((rc = deliver(g, src, g->ncells * (plane == grid::TV_DIST2 ? 4 : 1), out, on_device))) return rc;
+    g->final_valid = g->trav_valid = true;
+    return SVH_OK;
+}
+
+int render_cost(svh_grid* g, uint8_t* rgb, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const size_t bytes = g->ncells * 3;
+    if (!on_device) {
+        GRID_GROW(g->d_rgb, bytes);
+        GRID_GROW(g->h_out, bytes);
+    }
+    if ((rc = traverse(g))) return rc;
+    grid::RenderCostJob j;
+    j.nx = g->prm.nx, j.nz = g->prm.nz;
+    j.cost = g->t_cost(), j.flags = g->t_flags();
+    j.rgb = on_device ? rgb : g->d_rgb.p;
+    GRID_TRY(launch, (grid::launch_render_cost(g->stream, j), hipGetLastError()));
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+        return rc;
+    }
+    g->final_valid = g->trav_valid = true;
+    return SVH_OK;
+}
+
 // nothing of a failed call is in flight when the caller goes on
 int drained(svh_grid* g, int rc) {
     if (rc == SVH_ERR_HIP && g->stream) {
@@ -268,7 +364,7 @@ int added(svh_grid* g, int rc) {
 // the window moves by (da, db) cells to offsets that have been checked, not both zero
 int scroll(svh_grid* g, int32_t da, int32_t db) {
     g->prm.oa += da, g->prm.ob += db;
-    g->final_valid = false;
+    invalidate(g);
     if (g->need_clear) return SVH_OK;   // the empty grid has no cell to reset
     int rc = ready(g);
     if (rc) return rc;
@@ -343,6 +439,12 @@ void svh_grid_params_default(svh_grid_params* p) {
     p->render_h_lo = 0.f, p->render_h_hi = 2.f;
 }
 
+void svh_grid_trav_params_default(svh_grid_trav_params* t) {
+    if (!t) return;
+    t->max_slope = 0.35f, t->inscribed = 0.4f, t->inflate = 1.5f;
+    t->lethal = SVH_GRID_LETHAL_OBSTACLE | SVH_GRID_LETHAL_DROP | SVH_GRID_LETHAL_STEEP;
+}
+
 svh_grid* svh_grid_create(const svh_grid_params* p) {
     svh::ensure_init();
     grid::Params q;
@@ -358,6 +460,9 @@ svh_grid* svh_grid_create(const svh_grid_params* p) {
     svh_grid* g = new svh_grid();
     g->prm = q;
     g->ncells = (size_t)q.nx * (size_t)q.nz;
+    svh_grid_trav_params t;
+    svh_grid_trav_params_default(&t);
+    g->trav_ok = convert_trav(&t, q.cell, &g->trv, &g->table);   // false: no traversability until it is set
     (void)hipGetDevice(&g->device);
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
         delete g;
@@ -507,6 +612,68 @@ int32_t svh_grid_get(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
 int32_t svh_grid_render(svh_grid* g, int32_t mode, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb || mode < 0 || mode >= grid::M_MODES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render: a grid, a mode 0..2 and an output are needed");
     return drained(g, render(g, mode, rgb, on_device != 0));
+}
+
+int32_t svh_grid_set_traversability(svh_grid* g, const svh_grid_trav_params* t) {
+    grid::TravParams q;
+    std::vector<uint8_t> table;
+    if (!g || !convert_trav(t, g->prm.cell, &q, &table))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_traversability: a grid and parameters in range, with a reach of 1..256 cells, are needed (include/svh_grid.h)");
+    g->trv = q;
+    g->table.swap(table);
+    g->trav_ok = true;
+    g->trav_valid = g->table_sent = false;
+    return drained(g, send_table(g));   // a failed upload is repeated by the next svh_grid_get_trav / svh_grid_render_cost
+}
+
+int32_t svh_grid_get_traversability(svh_grid* g, svh_grid_trav_params* t, int32_t* reach) {
+    if (!g || (!t && !reach)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_traversability: a grid and an output are needed");
+    if (t) t->max_slope = g->trv.max_slope, t->inscribed = g->trv.inscribed, t->inflate = g->trv.inflate, t->lethal = g->trv.lethal;
+    if (reach) *reach = g->trav_ok ? g->trv.reach : 0;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_trav(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::TV_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_trav: a grid, a plane 0..2 and an output are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_trav: the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)");
+    return drained(g, get_trav(g, plane, out, on_device != 0));
+}
+
+int32_t svh_grid_render_cost(svh_grid* g, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_cost: a grid and an output are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_cost: the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)");
+    return drained(g, render_cost(g, rgb, on_device != 0));
+}
+
+// grid_core.h's traversability layer on the host: the planes of a window of p->nx x p->nz cells from CLASS, HMEAN and STATE;
+// rgb[3] per cell is colour_cost (cell order, no row flip).  Any output may be NULL
+int32_t svh_test_grid_trav(const svh_grid_params* p, const svh_grid_trav_params* t, const uint8_t* cls, const float* hmean,
+                           const uint8_t* state, uint8_t* flags, int32_t* dist2, uint8_t* cost, uint8_t* rgb) {
+    grid::Params prm;
+    grid::TravParams trv;
+    std::vector<uint8_t> table;
+    if (!convert(p, &prm) || !convert_trav(t, prm.cell, &trv, &table) || !cls || !hmean || !state)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_trav: bad arguments");
+    const size_t n = (size_t)prm.nx * (size_t)prm.nz;
+    std::vector<uint8_t> f(n), c(n);
+    std::vector<uint16_t> gcol(n);
+    grid::trav_window(trv, prm.nx, prm.nz, cls, hmean, state, table.data(), f.data(), gcol.data(), dist2, c.data());
+    if (flags) memcpy(flags, f.data(), n);
+    if (cost) memcpy(cost, c.data(), n);
+    if (rgb)
+        for (size_t i = 0; i < n; i++) grid::colour_cost(c[i], f[i], rgb + 3 * i);
+    return SVH_OK;
+}
+
+// the cost table for a cell side: *reach, and the first min(reach^2 + 1, cap) bytes
+int32_t svh_test_grid_cost_table(float cell, const svh_grid_trav_params* t, int32_t* reach, uint8_t* table, int64_t cap) {
+    grid::TravParams trv;
+    std::vector<uint8_t> tb;
+    if (!(grid::finite_f(cell) && cell > 0.f) || !reach || cap < 0 || (cap > 0 && !table) || !convert_trav(t, cell, &trv, &tb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_cost_table: bad arguments");
+    *reach = trv.reach;
+    if (cap > 0) memcpy(table, tb.data(), std::min((size_t)cap, tb.size()));
+    return SVH_OK;
 }
 
 int32_t svh_test_grid_points(const svh_grid_params* p, const float* xyzv, int64_t n, int32_t* fate, uint32_t* cell,

@@ -1,4 +1,5 @@
-// Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip: the launches of the ground grid (include/svh_grid.h).
+// Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip: the launches of the ground
+// grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
 
@@ -90,6 +91,36 @@ struct RenderJob {
     uint8_t* rgb;               // nx * nz * 3 bytes, row 0 = ib nz - 1
 };
 void launch_render(hipStream_t s, const RenderJob& j);
+
+// The traversability layer (csrc/grid_trav_kernels.hip): finished planes in logical order -> FLAGS, DIST2, COST.
+constexpr uint32_t TRAV_BLOCK = 256;         // k_grid_trav_mask, k_grid_render_cost: one lane per cell; k_grid_dist_rows:
+                                             // one workgroup per 256 cells of a row
+constexpr uint32_t COLS_BLOCK = 64;          // k_grid_dist_cols: one lane per column and chunk of rows
+constexpr int32_t COLS_CHUNK = 32;           // ... of this many rows
+constexpr uint32_t ROWS_TILE = TRAV_BLOCK + 2 * (uint32_t)MAX_REACH;   // the tile of g and its halo, uint16 each
+
+struct TravJob {
+    TravParams trv;
+    int32_t nx, nz;
+    const uint8_t* cls;         // the finished planes
+    const float* hmean;
+    const uint8_t* state;
+    const uint8_t* table;       // reach^2 + 1 cost bytes
+    uint8_t* flags;             // nx * nz each
+    uint16_t* g;                // the column distances, scratch
+    int32_t* dist2;
+    uint8_t* cost;
+};
+// the three launches: mask, columns, rows
+void launch_trav(hipStream_t s, const TravJob& j);
+
+struct RenderCostJob {
+    int32_t nx, nz;
+    const uint8_t* cost;
+    const uint8_t* flags;
+    uint8_t* rgb;               // nx * nz * 3 bytes, row 0 = ib nz - 1
+};
+void launch_render_cost(hipStream_t s, const RenderCostJob& j);
 
 }  // namespace grid
 }  // namespace svh

@@ -134,6 +134,17 @@ extern "C" int32_t svh_test_grid_finalise(const svh_grid_params* p, int64_t ncel
                                           const int32_t* overhead, const uint32_t* kmin, const uint32_t* kmax,
                                           const int64_t* hsum, const uint64_t* vsum, float* hmin, float* hmax, float* hmean,
                                           uint8_t* intensity, uint8_t* cls, uint8_t* rgb);
+//   svh_test_grid_trav        the traversability layer of a window of p->nx x p->nz cells from its CLASS, HMEAN and STATE
+//                             planes: FLAGS, DIST2, COST and rgb[3] per cell = the cost colour (cell order).  Any output may
+//                             be NULL
+//   svh_test_grid_cost_table  the cost table of parameters `t` for a cell side: *reach, and the first min(reach^2 + 1, cap)
+//                             bytes
+struct svh_grid_trav_params;
+extern "C" int32_t svh_test_grid_trav(const svh_grid_params* p, const svh_grid_trav_params* t, const uint8_t* cls,
+                                      const float* hmean, const uint8_t* state, uint8_t* flags, int32_t* dist2, uint8_t* cost,
+                                      uint8_t* rgb);
+extern "C" int32_t svh_test_grid_cost_table(float cell, const svh_grid_trav_params* t, int32_t* reach, uint8_t* table,
+                                            int64_t cap);
 
 // The guard of every HIP call of the host engines: `kind` is one of none, malloc, copy, launch, wait (see above); a
 // disarmed hook costs one relaxed load.  Returns hip_failed(...) out of the enclosing function on failure.

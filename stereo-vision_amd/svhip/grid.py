@@ -16,6 +16,11 @@ LOCAL_PASS, LOCAL_STATE = range(2)
 LOCAL_DTYPE = [np.int32, np.uint8]
 SEEN = 0x40
 SEEN_COLOUR = (96, 112, 96)
+TRAV_FLAGS, TRAV_DIST2, TRAV_COST = range(3)
+TRAV_DTYPE = [np.uint8, np.int32, np.uint8]
+STEEP, LETHAL = 1, 2
+LETHAL_OBSTACLE, LETHAL_DROP, LETHAL_STEEP, LETHAL_UNSEEN, LETHAL_UNKNOWN_SEEN = 1, 2, 4, 8, 16
+DIST2_FAR = 0x7FFFFFFF
 
 
 class Params(C.Structure):
@@ -32,6 +37,20 @@ class Params(C.Structure):
             else:
                 setattr(q, k, v)
         return q
+
+
+class TravParams(C.Structure):
+    """svh_grid_trav_params"""
+    _fields_ = [("max_slope", C.c_float), ("inscribed", C.c_float), ("inflate", C.c_float), ("lethal", C.c_uint32)]
+
+    def copy(self, **kw):
+        q = TravParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -78,6 +97,14 @@ def _bind():
         L.svh_test_grid_points_at.argtypes = [C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
         L.svh_test_grid_line.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32]
         L.svh_test_grid_local.argtypes = [C.POINTER(Params), C.c_int64] + [C.c_void_p] * 5
+        L.svh_grid_trav_params_default.argtypes = [C.POINTER(TravParams)]
+        L.svh_grid_trav_params_default.restype = None
+        L.svh_grid_set_traversability.argtypes = [C.c_void_p, C.POINTER(TravParams)]
+        L.svh_grid_get_traversability.argtypes = [C.c_void_p, C.POINTER(TravParams), C.c_void_p]
+        L.svh_grid_get_trav.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_render_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_test_grid_trav.argtypes = [C.POINTER(Params), C.POINTER(TravParams)] + [C.c_void_p] * 7
+        L.svh_test_grid_cost_table.argtypes = [C.c_float, C.POINTER(TravParams), C.c_void_p, C.c_void_p, C.c_int64]
         L._grid_bound = True
     return L
 
@@ -158,6 +185,33 @@ def core_local(params, cls, intensity, pass_):
     out = [np.zeros(n, np.uint8), np.zeros((n, 3), np.uint8)]
     _check(_bind().svh_test_grid_local(C.byref(params), n, *[a.ctypes.data for a in ins + out]))
     return tuple(out)
+
+
+def default_trav(**kw):
+    t = TravParams()
+    _bind().svh_grid_trav_params_default(C.byref(t))
+    return t.copy(**kw)
+
+
+def core_trav(params, trav, cls, hmean, state):
+    """the traversability layer of csrc/grid_core.h on the host (svh_test_grid_trav) for a window of params.nx x params.nz
+    cells: (flags uint8, dist2 int32, cost uint8, each [nz, nx]; rgb uint8 [nz, nx, 3] in cell order); needs no device"""
+    sh = (params.nz, params.nx)
+    ins = [np.ascontiguousarray(cls, np.uint8).reshape(sh), np.ascontiguousarray(hmean, np.float32).reshape(sh),
+           np.ascontiguousarray(state, np.uint8).reshape(sh)]
+    out = [np.zeros(sh, np.uint8), np.zeros(sh, np.int32), np.zeros(sh, np.uint8), np.zeros(sh + (3,), np.uint8)]
+    _check(_bind().svh_test_grid_trav(C.byref(params), C.byref(trav), *[a.ctypes.data for a in ins + out]))
+    return tuple(out)
+
+
+def core_cost_table(cell, trav):
+    """the cost table of csrc/grid_core.h for a cell side (svh_test_grid_cost_table): uint8 [reach^2 + 1]; needs no device"""
+    reach = C.c_int32(0)
+    L = _bind()
+    _check(L.svh_test_grid_cost_table(cell, C.byref(trav), C.addressof(reach), None, 0))
+    table = np.zeros(reach.value ** 2 + 1, np.uint8)
+    _check(L.svh_test_grid_cost_table(cell, C.byref(trav), C.addressof(reach), table.ctypes.data, len(table)))
+    return table
 
 
 def _xyz(p):
@@ -252,6 +306,38 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_local(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_traversability(self, params=None, **kw):
+        """the parameters in force (or `params`) with the fields of kw replaced: max_slope, inscribed, inflate, lethal"""
+        t = (params if params is not None else self.traversability()[0]).copy(**kw)
+        _check(self._L.svh_grid_set_traversability(self._h, C.byref(t)))
+
+    def traversability(self):
+        """(TravParams in force, their reach in cells; 0 while the defaults do not fit the grid's cell)"""
+        t, reach = TravParams(), C.c_int32(0)
+        _check(self._L.svh_grid_get_traversability(self._h, C.byref(t), C.addressof(reach)))
+        return t, reach.value
+
+    def trav_plane(self, which, device_ptr=None):
+        """TRAV_FLAGS uint8, TRAV_DIST2 int32 or TRAV_COST uint8, [nz, nx]; with device_ptr it is written there and None
+        returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_trav(self._h, which, device_ptr, 1))
+            return None
+        if not 0 <= which < len(TRAV_DTYPE):
+            raise SvhError(ERR_BAD_ARG, "no such plane")
+        out = np.zeros((self.nz, self.nx), TRAV_DTYPE[which])
+        _check(self._L.svh_grid_get_trav(self._h, which, out.ctypes.data, 0))
+        return out
+
+    def render_cost(self, device_ptr=None):
+        """the cost map, [nz, nx, 3] uint8, row 0 the farthest; with device_ptr the image is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_cost(self._h, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_cost(self._h, img.ctypes.data, 0))
         return img
 
     def stats(self):

@@ -16,6 +16,7 @@ without the GUI.  Usage:
                                           [--thin S [--thin-every N]] [--ply FILE]
                                           [--grid DIR [--grid-cell S] [--grid-size NXxNZ] [--level]]
                                           [--grid-local DIR [--grid-cell S] [--grid-size NXxNZ]]
+                                          [--grid-cost DIR [--grid-slope S] [--grid-inscribed M] [--grid-inflate M]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -68,6 +69,12 @@ cells that are unknown but were looked through -- at least min_points rays passe
 list the map fusion revises (the one before the newest) is NOT added again: the local map keeps the points that list
 had when it was the newest.  --grid-cell and --grid-size apply; the frame is the level camera's.  --grid stays what it
 is and may be given too.  Not with --lockstep.
+
+--grid-cost DIR: needs --grid-local.  After every local step the cost map of the local grid (svh_grid_render_cost) into
+DIR/cost_%06d.ppm: lethal cells red, cells within the inscribed radius orange, the inflation ramp from red to blue, free
+space dark green, unknown cells dark grey, steep cells with a full green byte.  --grid-slope S: the largest rise over run
+between neighbouring free cells (0.35); --grid-inscribed M and --grid-inflate M: the two radii in metres (0.4, 1.5).  The
+inflation radius must be at most 256 cells.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -172,6 +179,10 @@ class Pipeline:
         from svhip import grid
         self.local = grid.Grid(grid.default_params(nx=size[0], nz=size[1], cell=cell, x0=-0.5 * size[0] * cell, z0=0.0))
         self.local_appends = 0
+
+    def set_grid_cost(self, **kw):
+        """the traversability parameters of the local grid: max_slope, inscribed, inflate"""
+        self.local.set_traversability(**kw)
 
     def local_step(self):
         """follow the camera centre to the middle cell, add the newest list with rays from it, render: [nz, nx, 3]"""
@@ -448,7 +459,7 @@ def main():
         sys.argv.remove("--normalize")
     thin, thin_every, ply = None, 1, None
     grid_dir, grid_cell, grid_size = None, 0.2, (256, 256)
-    local_dir = None
+    local_dir, cost_dir, cost_kw = None, None, {}
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -471,6 +482,17 @@ def main():
             k = sys.argv.index("--grid-local")
             local_dir = sys.argv[k + 1]
             del sys.argv[k:k + 2]
+        if "--grid-cost" in sys.argv:
+            k = sys.argv.index("--grid-cost")
+            cost_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        for flag, name in (("--grid-slope", "max_slope"), ("--grid-inscribed", "inscribed"), ("--grid-inflate", "inflate")):
+            if flag in sys.argv:
+                k = sys.argv.index(flag)
+                cost_kw[name] = float(sys.argv[k + 1])
+                del sys.argv[k:k + 2]
+        assert local_dir or not (cost_dir or cost_kw)
+        assert cost_dir or not cost_kw
         assert grid_dir or not level
         assert not ((grid_dir or local_dir) and lockstep)
         if "--thin" in sys.argv:
@@ -526,6 +548,8 @@ def main():
         os.makedirs(grid_dir, exist_ok=True)
     if local_dir:
         os.makedirs(local_dir, exist_ok=True)
+    if cost_dir:
+        os.makedirs(cost_dir, exist_ok=True)
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -534,6 +558,8 @@ def main():
         p.enable_grid(grid_cell, grid_size, level)
     if local_dir:
         p.enable_grid_local(grid_cell, grid_size)
+    if cost_dir:
+        p.set_grid_cost(**cost_kw)
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -550,6 +576,8 @@ def main():
             view.write_ppm(os.path.join(grid_dir, "grid_%06d.ppm" % (frames - 1)), p.render_grid())
         if local_dir:
             view.write_ppm(os.path.join(local_dir, "local_%06d.ppm" % (frames - 1)), p.local_step())
+        if cost_dir:
+            view.write_ppm(os.path.join(cost_dir, "cost_%06d.ppm" % (frames - 1)), p.local.render_cost())
         if frames >= limit:
             break
     dt = time.perf_counter() - t0
@@ -565,6 +593,10 @@ def main():
         st, (rays, ray_cells), (oa, ob) = p.local.stats(), p.local.ray_stats(), p.local.window()
         print("local grid %d x %d cells of %g at offsets (%d, %d): %d of %d points binned, %d rays over %d cells; %d images in %s" % (
             p.local.nx, p.local.nz, grid_cell, oa, ob, st.binned, st.added, rays, ray_cells, frames, local_dir))
+    if cost_dir:
+        t, reach = p.local.traversability()
+        print("cost map: slope %g, inscribed %g m, inflation %g m = %d cells; %d images in %s" % (
+            t.max_slope, t.inscribed, t.inflate, reach, frames, cost_dir))
     if render_dir:
         n, images = p.view.record_human()
         for k in range(n):
