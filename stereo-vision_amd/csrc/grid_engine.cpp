@@ -3,7 +3,8 @@
 //
 // Host (this file): the parameters (T rounded to float once), the two frames, the window's offsets, the statistics, the
 // lazy clear and the lazy finalise.  Device (grid_kernels.hip): the binning, the rays, the strips of a scroll, the
-// finalise, the render; (grid_trav_kernels.hip): the traversability layer -- flags, obstacle distance, cost, its render.
+// finalise, the render; (grid_trav_kernels.hip): the traversability layer -- flags, obstacle distance, cost, its render;
+// (grid_plan_kernels.hip): the planner -- the relaxation over active tiles, whose round loop is plan_rounds() here.
 // The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
@@ -13,12 +14,15 @@
 // accumulators lie at their slots (the torus of grid_core.h), the finished planes are in logical order, and every plane
 // that leaves the object is a finished one.  A scroll moves no data: it changes the offsets and resets the strips that
 // enter; on an empty grid it changes the offsets alone.  The traversability planes are derived from the finished ones, as
-// lazily, and kept until the accumulators or the traversability parameters change (trav_valid).
+// lazily, and kept until the accumulators or the traversability parameters change (trav_valid).  The planner's field (POT,
+// DIR; grid_plan_kernels.hip) is derived from COST and the goals, as lazily, and kept beside it (plan_valid) until the
+// accumulators, the offsets, the traversability, the plan parameters or the goals change.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "../../include/svh_grid.h"
@@ -34,6 +38,7 @@ namespace {
 
 #define GRID_TRY(kind, expr) SVH_HIP_TRY("Grid", kind, expr)
 #define GRID_GROW(buf, bytes) SVH_HIP_GROW("Grid", buf, bytes)
+#define GRID_GROW_N(buf, count) SVH_HIP_GROW_N("Grid", buf, count)
 
 constexpr int64_t kMaxPoints = ((int64_t)1 << 31) - 1;
 constexpr int64_t kHostChunk = (int64_t)1 << 22;   // points of a host array staged per copy
@@ -41,6 +46,14 @@ constexpr size_t kFinalBytes = 27;                 // per cell: COUNT, OVERHEAD,
 enum FinPlane { F_COUNT = 0, F_OVERHEAD, F_PASS, F_HMIN, F_HMAX, F_HMEAN, F_WORDS };   // the 4-byte planes of `fin`
 enum FinByte { B_INTENSITY = 0, B_CLASS, B_STATE };                                    // its byte planes
 constexpr size_t kTravBytes = 8;                   // per cell: DIST2; g (uint16); FLAGS, COST
+constexpr size_t kPlanBytes = 7;                   // per cell: POT; price (uint16); DIR
+// rounds of the relaxation enqueued per wait: a round whose list is empty costs one empty launch, a wait costs a round trip,
+// and the bound on the workgroups of a round grows with its distance from the last known length.  Measured alternating in one
+// process at 1, 2, 4, 8 and 16 (profiles/grid_plan_times.jsonl; ms on an open field of 256^2 / 1024^2 / 8192^2 cells):
+// 0.52 / 2.08 / 29.7 at 1, 0.37 / 1.48 / 27.8 at 4, 0.32 / 1.32 / 37.3 at 16 -- at 8192^2 the later rounds of a long batch launch
+// a workgroup for every tile.  4 is kept.  1..64; svh_test_grid_plan_rounds_per_wait changes it for that measurement
+// (tools/gpu_grid_plan.py)
+int g_rounds_per_wait = 4;
 
 bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
@@ -86,6 +99,20 @@ struct svh_grid {
     PinnedBuf<uint8_t> h_table;
     HipBuf<uint8_t> trav;       // kTravBytes per cell: DIST2 | g | FLAGS | COST, logical order
     bool trav_valid = false;    // ... derived from `fin` as it is, with the parameters as they are; implies final_valid
+    grid::PlanParams pln{50, -1, 0x7FFFFFFE};   // the planner: parameters, the goals as global cells
+    std::vector<int32_t> goals;
+    bool goals_sent = false;    // d_goals holds them
+    HipBuf<int32_t> d_goals;
+    PinnedBuf<int32_t> h_cells; // goals or a path on their way to the device
+    HipBuf<uint8_t> plan;       // kPlanBytes per cell: POT | price | DIR, logical order
+    HipBuf<uint32_t> plan_tiles;   // 4 per tile: the two lists, the two flags
+    HipBuf<uint32_t> plan_ctl;  // grid::CTL_WORDS
+    PinnedBuf<uint32_t> h_ctl;
+    bool plan_valid = false;    // ... derived from COST as it is, with the offsets, parameters and goals as they are; implies trav_valid
+    int64_t plan_counted = 0, plan_reached = 0, plan_rounds = 0;   // of the field that is valid
+    HipBuf<int32_t> d_path;     // the cells a walk writes, or a caller's path for the plan image
+    HipBuf<int64_t> d_walk;     // status, length, cost
+    PinnedBuf<int64_t> h_walk;
     svh_grid_stats st{0, 0, 0, 0, 0};
     int64_t rays = 0, ray_cells = 0;
 
@@ -102,12 +129,15 @@ struct svh_grid {
     uint16_t* t_g() const { return (uint16_t*)(trav.p + 4 * ncells); }
     uint8_t* t_flags() const { return trav.p + 6 * ncells; }
     uint8_t* t_cost() const { return trav.p + 7 * ncells; }
+    int32_t* p_pot() const { return (int32_t*)plan.p; }
+    uint16_t* p_price() const { return (uint16_t*)(plan.p + 4 * ncells); }
+    uint8_t* p_dir() const { return plan.p + 6 * ncells; }
 };
 
 namespace {
 
 // the accumulators change: what was derived from them is stale
-void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = false; }
+void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = g->plan_valid = false; }
 
 void mark_empty(svh_grid* g) {
     g->need_clear = true;
@@ -352,6 +382,151 @@ int drained(svh_grid* g, int rc) {
     return rc;
 }
 
+// ---- the planner ----------------------------------------------------------------------------------------------------------
+void forget_goals(svh_grid* g) {
+    g->goals.clear();
+    g->goals_sent = g->plan_valid = false;
+}
+
+// The rounds of the relaxation on a seeded job, until a round finds its list empty: g_rounds_per_wait launches, then the control
+// words come back through `h_ctl` (pinned) and the host waits.  The kernel strides over its list, so the number of workgroups
+// is a matter of speed alone: a tile of round r + k lies within k tiles of one of round r, so (2 k + 1)^2 times the known
+// length bounds the list.  Three bounds keep a bug from hanging: the sweeps of a tile, these rounds, the walk.
+int plan_rounds(hipStream_t s, const grid::PlanJob& j, uint32_t* h_ctl) {
+    const uint64_t tiles = (uint64_t)grid::plan_tiles_x(j) * grid::plan_tiles_y(j);
+    const uint64_t limit = (uint64_t)j.nx * (uint64_t)j.nz + 2;
+    uint64_t known = std::min<uint64_t>(tiles, 4 * (uint64_t)j.n_goals);   // a goal's 3 x 3 cells touch at most four tiles
+    for (uint64_t round = 0; known > 0;) {
+        if (round >= limit) return svh::fail(SVH_ERR_HIP, "Grid: the relaxation of the plan did not settle within nx * nz + 2 rounds");
+        for (int k = 0, per_wait = g_rounds_per_wait; k < per_wait; k++, round++) {
+            const uint64_t reach = (uint64_t)(2 * k + 1) * (uint64_t)(2 * k + 1);
+            grid::launch_plan_relax(s, j, (uint32_t)round, (uint32_t)std::min(tiles, known * reach));
+        }
+        GRID_TRY(launch, hipGetLastError());
+        GRID_TRY(copy, hipMemcpyAsync(h_ctl, j.ctl, grid::CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        known = h_ctl[grid::CTL_LEN + round % 3];   // the list of the round to come
+    }
+    return SVH_OK;
+}
+
+// seed, rounds, DIR on buffers that exist; the control words of the finished field are in h_ctl when it returns
+int plan_run(hipStream_t s, const grid::PlanJob& j, uint32_t* h_ctl) {
+    const size_t tiles = (size_t)grid::plan_tiles_x(j) * grid::plan_tiles_y(j);
+    GRID_TRY(copy, hipMemsetAsync(j.flags, 0, 2 * tiles * sizeof(uint32_t), s));
+    GRID_TRY(copy, hipMemsetAsync(j.ctl, 0, grid::CTL_WORDS * sizeof(uint32_t), s));
+    GRID_TRY(launch, (grid::launch_plan_seed(s, j), hipGetLastError()));
+    const int rc = plan_rounds(s, j, h_ctl);
+    if (rc) return rc;
+    GRID_TRY(launch, (grid::launch_plan_dir(s, j), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(h_ctl, j.ctl, grid::CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    return SVH_OK;
+}
+
+// `n` cells (pairs) from the host to `dst` through the pinned staging buffer, and the wait
+int send_cells(svh_grid* g, const int32_t* cells, int64_t n, HipBuf<int32_t>& dst) {
+    const size_t bytes = (size_t)n * 2 * sizeof(int32_t);
+    GRID_GROW(dst, bytes);
+    GRID_GROW(g->h_cells, bytes);
+    memcpy(g->h_cells, cells, bytes);
+    GRID_TRY(copy, hipMemcpyAsync(dst, g->h_cells, bytes, hipMemcpyHostToDevice, g->stream));
+    GRID_TRY(wait, hipStreamSynchronize(g->stream));   // the staging buffer is free again
+    return SVH_OK;
+}
+
+grid::PlanJob plan_job(const svh_grid* g) {
+    grid::PlanJob j;
+    const size_t tiles = ((size_t)(g->prm.nx + grid::PLAN_TILE - 1) / grid::PLAN_TILE) * ((size_t)(g->prm.nz + grid::PLAN_TILE - 1) / grid::PLAN_TILE);
+    j.pln = g->pln;
+    j.nx = g->prm.nx, j.nz = g->prm.nz, j.oa = g->prm.oa, j.ob = g->prm.ob;
+    j.cost = g->t_cost();
+    j.price = g->p_price(), j.pot = g->p_pot(), j.dir = g->p_dir();
+    j.goals = g->d_goals.p, j.n_goals = (int32_t)(g->goals.size() / 2);
+    j.lists = g->plan_tiles.p, j.flags = g->plan_tiles.p + 2 * tiles;
+    j.ctl = g->plan_ctl.p;
+    return j;
+}
+
+// the field is valid: the cost planes, then seed, rounds and DIR; complete when it returns
+int plan_field(svh_grid* g) {
+    if (g->plan_valid) return SVH_OK;
+    const size_t tiles = ((size_t)(g->prm.nx + grid::PLAN_TILE - 1) / grid::PLAN_TILE) * ((size_t)(g->prm.nz + grid::PLAN_TILE - 1) / grid::PLAN_TILE);
+    GRID_GROW(g->plan, g->ncells * kPlanBytes);
+    GRID_GROW(g->plan_tiles, 4 * tiles * sizeof(uint32_t));
+    GRID_GROW(g->plan_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+    GRID_GROW(g->h_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+    int rc;
+    if (!g->goals_sent && !g->goals.empty() && (rc = send_cells(g, g->goals.data(), (int64_t)(g->goals.size() / 2), g->d_goals))) return rc;
+    g->goals_sent = true;
+    if ((rc = traverse(g))) return rc;
+    if ((rc = plan_run(g->stream, plan_job(g), g->h_ctl))) return rc;
+    const uint32_t* h = g->h_ctl;
+    g->plan_counted = h[grid::CTL_COUNTED], g->plan_rounds = h[grid::CTL_ROUNDS];
+    g->plan_reached = (int64_t)((uint64_t)h[grid::CTL_REACHED] | ((uint64_t)h[grid::CTL_REACHED + 1] << 32));
+    g->final_valid = g->trav_valid = g->plan_valid = true;
+    return SVH_OK;
+}
+
+int get_plan(svh_grid* g, int32_t plane, void* out, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = plan_field(g))) return rc;
+    return plane == grid::PL_POT ? deliver(g, g->p_pot(), g->ncells * 4, out, on_device) : deliver(g, g->p_dir(), g->ncells, out, on_device);
+}
+
+// the walk from the window cell (a, b)
+int plan_path(svh_grid* g, int32_t a, int32_t b, int32_t* cells, int64_t cap, int64_t* len, int32_t* cost, int32_t* status) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = plan_field(g))) return rc;
+    const int64_t room = std::min<int64_t>(cap, (int64_t)g->ncells);   // a path has at most nx * nz cells
+    GRID_GROW_N(g->d_path, 2 * room);
+    GRID_GROW(g->d_walk, 3 * sizeof(int64_t));
+    GRID_GROW(g->h_walk, 3 * sizeof(int64_t));
+    GRID_TRY(launch, (grid::launch_plan_walk(g->stream, plan_job(g), a, b, g->d_path, room, g->d_walk), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(g->h_walk, g->d_walk, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    const int64_t n = g->h_walk[1], m = std::min(n, room);
+    if (m > 0 && (rc = deliver(g, g->d_path, (size_t)m * 2 * sizeof(int32_t), cells, false))) return rc;
+    *status = (int32_t)g->h_walk[0], *len = n, *cost = (int32_t)g->h_walk[2];
+    return SVH_OK;
+}
+
+int render_plan(svh_grid* g, const int32_t* cells, int64_t n, uint8_t* rgb, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const size_t bytes = g->ncells * 3;
+    if (!on_device) {
+        GRID_GROW(g->d_rgb, bytes);
+        GRID_GROW(g->h_out, bytes);
+    }
+    if ((rc = plan_field(g))) return rc;
+    if (n > 0 && (rc = send_cells(g, cells, n, g->d_path))) return rc;
+    grid::RenderCostJob j;
+    j.nx = g->prm.nx, j.nz = g->prm.nz;
+    j.cost = g->t_cost(), j.flags = g->t_flags();
+    j.rgb = on_device ? rgb : g->d_rgb.p;
+    const grid::PlanJob pj = plan_job(g);
+    grid::launch_render_cost(g->stream, j);
+    grid::launch_plan_overlay(g->stream, pj, pj.goals, pj.n_goals, true, j.rgb);
+    grid::launch_plan_overlay(g->stream, pj, g->d_path, n, false, j.rgb);
+    GRID_TRY(launch, hipGetLastError());
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+        return SVH_OK;
+    }
+    return deliver(g, g->d_rgb, bytes, rgb, false);
+}
+
+// a planning call that failed on the device: nothing in flight, the field is computed again by the next call
+int planned(svh_grid* g, int rc) {
+    if (rc == SVH_ERR_HIP) g->plan_valid = false;
+    return drained(g, rc);
+}
+
+const char* const kNoTrav = ": the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)";
+
 // ... and a failed add leaves the empty grid
 int added(svh_grid* g, int rc) {
     if (rc == SVH_ERR_HIP) {
@@ -483,6 +658,7 @@ void svh_grid_destroy(svh_grid* g) {
 
 int32_t svh_grid_clear(svh_grid* g) {
     if (!g) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_clear: null argument");
+    forget_goals(g);
     mark_empty(g);
     return SVH_OK;
 }
@@ -491,6 +667,7 @@ int32_t svh_grid_set_window(svh_grid* g, float x0, float z0) {
     if (!g || !grid::finite_f(x0) || !grid::finite_f(z0)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_window: a grid and a finite corner are needed");
     g->prm.x0 = x0, g->prm.z0 = z0;
     g->prm.oa = g->prm.ob = 0;
+    forget_goals(g);
     mark_empty(g);
     return SVH_OK;
 }
@@ -622,7 +799,7 @@ int32_t svh_grid_set_traversability(svh_grid* g, const svh_grid_trav_params* t) 
     g->trv = q;
     g->table.swap(table);
     g->trav_ok = true;
-    g->trav_valid = g->table_sent = false;
+    g->trav_valid = g->plan_valid = g->table_sent = false;
     return drained(g, send_table(g));   // a failed upload is repeated by the next svh_grid_get_trav / svh_grid_render_cost
 }
 
@@ -643,6 +820,175 @@ int32_t svh_grid_render_cost(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_cost: a grid and an output are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_cost: the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)");
     return drained(g, render_cost(g, rgb, on_device != 0));
+}
+
+void svh_grid_plan_params_default(svh_grid_plan_params* p) {
+    if (!p) return;
+    p->neutral = 50, p->unknown = -1, p->max_cost = 0x7FFFFFFE;
+}
+
+int32_t svh_grid_set_plan(svh_grid* g, const svh_grid_plan_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_plan: null argument");
+    const grid::PlanParams q{p->neutral, p->unknown, p->max_cost};
+    if (!grid::plan_ok(q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_plan: parameters out of range (include/svh_grid.h)");
+    g->pln = q;
+    g->plan_valid = false;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_plan(svh_grid* g, svh_grid_plan_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_plan: null argument");
+    p->neutral = g->pln.neutral, p->unknown = g->pln.unknown, p->max_cost = g->pln.max_cost;
+    return SVH_OK;
+}
+
+int32_t svh_grid_plan_set_goals(svh_grid* g, const int32_t* cells, int32_t n) {
+    if (!g || n < 0 || n > grid::PLAN_MAX_GOALS || (n > 0 && !cells))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_plan_set_goals: a grid and 0..65536 goals are needed");
+    for (int32_t k = 0; k < 2 * n; k++)
+        if (cells[k] <= -grid::PLAN_GOAL_LIMIT || cells[k] >= grid::PLAN_GOAL_LIMIT)
+            return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_plan_set_goals: a goal's cell is not below 2^20");
+    g->goals.assign(cells, cells + 2 * (size_t)n);
+    g->goals_sent = g->plan_valid = false;
+    return SVH_OK;
+}
+
+int32_t svh_grid_plan_set_goal(svh_grid* g, const double xyz[3]) {
+    float p[3];
+    int32_t cell[2];
+    if (!g || !position(xyz, p) || !grid::global_cell(g->prm, p[0], p[1], p[2], &cell[0], &cell[1]))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_plan_set_goal: a grid and a finite position with a cell below 2^20 are needed");
+    return svh_grid_plan_set_goals(g, cell, 1);
+}
+
+int32_t svh_grid_get_plan_plane(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::PL_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_plan_plane: a grid, a plane 0..1 and an output are needed");
+    if (on_device && plane == grid::PL_POT && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_plan_plane: a device array of POT must be 4-byte aligned");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_plan_plane") + kNoTrav);
+    return planned(g, get_plan(g, plane, out, on_device != 0));
+}
+
+int32_t svh_grid_get_plan_stats(svh_grid* g, int64_t out[4]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_plan_stats: null argument");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_plan_stats") + kNoTrav);
+    int rc = ready(g);
+    if (!rc) rc = plan_field(g);
+    if (rc) return planned(g, rc);
+    out[0] = (int64_t)(g->goals.size() / 2), out[1] = g->plan_counted, out[2] = g->plan_reached, out[3] = g->plan_rounds;
+    return SVH_OK;
+}
+
+int32_t svh_grid_plan_path(svh_grid* g, const double start_xyz[3], int32_t* cells, int64_t cap, int64_t* len, int32_t* cost) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || !len || !cost || cap < 0 || (cap > 0 && !cells) || !position(start_xyz, p) ||
+        !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_plan_path: a grid, outputs and a finite start with a cell below 2^20 are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_plan_path") + kNoTrav);
+    const int64_t a = (int64_t)ga - g->prm.oa, b = (int64_t)gb - g->prm.ob;
+    if (a < 0 || a >= g->prm.nx || b < 0 || b >= g->prm.nz) {
+        *len = 0, *cost = grid::PLAN_FAR;
+        return grid::PATH_OUTSIDE;
+    }
+    int64_t n = 0;
+    int32_t c = grid::PLAN_FAR, status = 0;
+    const int rc = planned(g, plan_path(g, (int32_t)a, (int32_t)b, cells, cap, &n, &c, &status));
+    if (rc) return rc;
+    *len = n, *cost = c;
+    return status;
+}
+
+int32_t svh_grid_render_plan(svh_grid* g, const int32_t* cells, int64_t n, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb || n < 0 || (n > 0 && !cells)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_plan: a grid, n >= 0 cells and an output are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_plan") + kNoTrav);
+    return planned(g, render_plan(g, cells, n, rgb, on_device != 0));
+}
+
+// grid_plan_core.h on the host: POT and DIR of a window of nx x nz cells from its COST plane and n goals (global cells under
+// the offsets oa, ob), by the heap Dijkstra of the header; returns the goals that count.  Needs no device
+int32_t svh_test_grid_plan(const svh_grid_plan_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost,
+                           const int32_t* goals, int32_t n, int32_t* pot, uint8_t* dir) {
+    if (!p || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) || !cost || n < 0 ||
+        n > grid::PLAN_MAX_GOALS || (n > 0 && !goals) || !pot || !dir)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_plan: bad arguments");
+    const grid::PlanParams q{p->neutral, p->unknown, p->max_cost};
+    if (!grid::plan_ok(q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_plan: parameters out of range");
+    for (int32_t k = 0; k < 2 * n; k++)
+        if (goals[k] <= -grid::PLAN_GOAL_LIMIT || goals[k] >= grid::PLAN_GOAL_LIMIT) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_plan: a goal's cell is not below 2^20");
+    return grid::plan_window(q, nx, nz, oa, ob, cost, goals, n, pot, dir);
+}
+
+// grid_plan_core.h's walk over a DIR plane from the window cell (a, b): *len cells (0: outside, or DIR leads nowhere), the
+// first min(*len, cap) of them as global cells.  Needs no device
+int32_t svh_test_grid_path(int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* dir, int32_t a, int32_t b, int32_t* cells,
+                           int64_t cap, int64_t* len) {
+    if (nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) || !dir || cap < 0 || (cap > 0 && !cells) || !len)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_path: bad arguments");
+    *len = grid::walk_window(nx, nz, oa, ob, dir, a, b, cells, cap);
+    return SVH_OK;
+}
+
+int32_t svh_test_grid_plan_tile(void) { return grid::PLAN_TILE; }
+
+// the rounds enqueued per wait become n (1..64; anything else only reads); returns what they were.  Not thread safe: a
+// measurement's switch
+int32_t svh_test_grid_plan_rounds_per_wait(int32_t n) {
+    const int32_t was = g_rounds_per_wait;
+    if (n >= 1 && n <= 64) g_rounds_per_wait = n;
+    return was;
+}
+
+// the planner's kernels and round loop on a caller's COST plane (host, nx x nz, offsets 0) and goals: POT and DIR to the
+// host, out[0] the goals that counted, out[1] the cells reached, out[2] the rounds
+int32_t svh_test_grid_plan_device(int32_t nx, int32_t nz, const svh_grid_plan_params* p, const uint8_t* cost, const int32_t* goals,
+                                  int32_t n, int32_t* pot, uint8_t* dir, int64_t out[3]) {
+    if (!p || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !cost || n < 0 || n > grid::PLAN_MAX_GOALS ||
+        (n > 0 && !goals) || !pot || !dir || !out)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_plan_device: bad arguments");
+    grid::PlanJob j;
+    j.pln = grid::PlanParams{p->neutral, p->unknown, p->max_cost};
+    if (!grid::plan_ok(j.pln)) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_plan_device: parameters out of range");
+    for (int32_t k = 0; k < 2 * n; k++)
+        if (goals[k] <= -grid::PLAN_GOAL_LIMIT || goals[k] >= grid::PLAN_GOAL_LIMIT) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_plan_device: a goal's cell is not below 2^20");
+    svh::ensure_init();
+    j.nx = nx, j.nz = nz, j.oa = j.ob = 0, j.n_goals = n;
+    const size_t cells = (size_t)nx * (size_t)nz, tiles = (size_t)grid::plan_tiles_x(j) * grid::plan_tiles_y(j);
+    HipBuf<uint8_t> d_cost, field;
+    HipBuf<int32_t> d_goals;
+    HipBuf<uint32_t> d_tiles, d_ctl;
+    PinnedBuf<uint32_t> h_ctl;
+    hipStream_t s = nullptr;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(d_cost, cells);
+        GRID_GROW(field, cells * kPlanBytes);
+        GRID_GROW_N(d_goals, 2 * (size_t)n);
+        GRID_GROW(d_tiles, 4 * tiles * sizeof(uint32_t));
+        GRID_GROW(d_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+        GRID_GROW(h_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+        GRID_TRY(copy, hipMemcpyAsync(d_cost, cost, cells, hipMemcpyHostToDevice, s));
+        if (n > 0) GRID_TRY(copy, hipMemcpyAsync(d_goals, goals, 2 * (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        j.cost = d_cost.p;
+        j.pot = (int32_t*)field.p, j.price = (uint16_t*)(field.p + 4 * cells), j.dir = field.p + 6 * cells;
+        j.goals = d_goals.p;
+        j.lists = d_tiles.p, j.flags = d_tiles.p + 2 * tiles;
+        j.ctl = d_ctl.p;
+        const int r = plan_run(s, j, h_ctl);
+        if (r) return r;
+        GRID_TRY(copy, hipMemcpyAsync(pot, j.pot, cells * 4, hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(dir, j.dir, cells, hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    out[0] = h_ctl.p[grid::CTL_COUNTED];
+    out[1] = (int64_t)((uint64_t)h_ctl.p[grid::CTL_REACHED] | ((uint64_t)h_ctl.p[grid::CTL_REACHED + 1] << 32));
+    out[2] = h_ctl.p[grid::CTL_ROUNDS];
+    return SVH_OK;
 }
 
 // grid_core.h's traversability layer on the host: the planes of a window of p->nx x p->nz cells from CLASS, HMEAN and STATE;

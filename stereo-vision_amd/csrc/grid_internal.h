@@ -1,5 +1,5 @@
-// Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip: the launches of the ground
-// grid (include/svh_grid.h).
+// Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip: the
+// launches of the ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
 
@@ -7,6 +7,7 @@
 #include <hip/hip_vector_types.h>
 
 #include "grid_core.h"
+#include "grid_plan_core.h"
 
 namespace svh {
 namespace grid {
@@ -121,6 +122,45 @@ struct RenderCostJob {
     uint8_t* rgb;               // nx * nz * 3 bytes, row 0 = ib nz - 1
 };
 void launch_render_cost(hipStream_t s, const RenderCostJob& j);
+
+// The planner (csrc/grid_plan_kernels.hip): the finished COST plane and the goals -> POT, DIR, a path.
+#ifndef SVH_PLAN_TILE
+#define SVH_PLAN_TILE 16
+#endif
+constexpr int32_t PLAN_TILE = SVH_PLAN_TILE;     // k_grid_plan_relax: one workgroup per active tile of this side; 16, 32 and 64
+                                                 // were measured (grid_plan_kernels.hip)
+constexpr uint32_t PLAN_BLOCK = 256;
+static_assert(PLAN_TILE == 16 || PLAN_TILE == 32 || PLAN_TILE == 64, "a tile is whole passes of 256 lanes");
+// the control words on the device: the lengths of the tile lists of rounds r, r + 1, r + 2 at [r % 3], the rounds whose list
+// was not empty, the goals that counted, and (64 bits at word 6) the cells whose POT is not FAR
+enum PlanCtl { CTL_LEN = 0, CTL_ROUNDS = 3, CTL_COUNTED = 4, CTL_REACHED = 6, CTL_WORDS = 8 };
+
+struct PlanJob {
+    PlanParams pln;
+    int32_t nx, nz, oa, ob;
+    const uint8_t* cost;        // the finished COST plane
+    uint16_t* price;            // nx * nz each, logical order
+    int32_t* pot;
+    uint8_t* dir;
+    const int32_t* goals;       // n_goals global cells (ga, gb)
+    int32_t n_goals;
+    uint32_t* lists;            // 2 * tiles: the tiles of this round and of the next
+    uint32_t* flags;            // 2 * tiles: a tile is in that list
+    uint32_t* ctl;              // CTL_WORDS
+};
+inline uint32_t plan_tiles_x(const PlanJob& j) { return ((uint32_t)j.nx + (uint32_t)PLAN_TILE - 1) / (uint32_t)PLAN_TILE; }
+inline uint32_t plan_tiles_y(const PlanJob& j) { return ((uint32_t)j.nz + (uint32_t)PLAN_TILE - 1) / (uint32_t)PLAN_TILE; }
+// the price plane and POT all FAR, then the goals: POT 0 where one counts, its tile and those it touches on list 0.  `flags`
+// and `ctl` are all zero before
+void launch_plan_seed(hipStream_t s, const PlanJob& j);
+// round `round` over the first `blocks` entries of its list (the kernel reads the list's true length; blocks >= 1)
+void launch_plan_relax(hipStream_t s, const PlanJob& j, uint32_t round, uint32_t blocks);
+void launch_plan_dir(hipStream_t s, const PlanJob& j);
+// the walk from the window cell (a, b): out[0] a PathStatus, out[1] the cells of the path, out[2] POT of the start; the first
+// min(out[1], cap) cells to `cells`
+void launch_plan_walk(hipStream_t s, const PlanJob& j, int32_t a, int32_t b, int32_t* cells, int64_t cap, int64_t* out);
+// n global cells drawn into an image of svh_grid_render_cost's layout: a path, or (goals) only those that count
+void launch_plan_overlay(hipStream_t s, const PlanJob& j, const int32_t* cells, int64_t n, bool goals, uint8_t* rgb);
 
 }  // namespace grid
 }  // namespace svh

@@ -146,6 +146,26 @@ extern "C" int32_t svh_test_grid_trav(const svh_grid_params* p, const svh_grid_t
 extern "C" int32_t svh_test_grid_cost_table(float cell, const svh_grid_trav_params* t, int32_t* reach, uint8_t* table,
                                             int64_t cap);
 
+//   svh_test_grid_plan         csrc/grid_plan_core.h on the host: POT and DIR of a window of nx x nz cells under the offsets
+//                              (oa, ob) from its COST plane and n goals (global cells), by the header's heap Dijkstra;
+//                              returns the number of goals that count
+//   svh_test_grid_path         the header's walk over a DIR plane from the window cell (a, b): *len cells, the first
+//                              min(*len, cap) of them as global cells
+//   svh_test_grid_plan_tile    the tile side the planner's kernels were built with
+//   svh_test_grid_plan_device  NEEDS A DEVICE: the planner's kernels and round loop on a caller's COST plane (offsets 0);
+//                              out[0] goals that counted, out[1] cells reached, out[2] rounds
+struct svh_grid_plan_params;
+extern "C" int32_t svh_test_grid_plan(const svh_grid_plan_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob,
+                                      const uint8_t* cost, const int32_t* goals, int32_t n, int32_t* pot, uint8_t* dir);
+extern "C" int32_t svh_test_grid_path(int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* dir, int32_t a, int32_t b,
+                                      int32_t* cells, int64_t cap, int64_t* len);
+extern "C" int32_t svh_test_grid_plan_tile(void);
+//   svh_test_grid_plan_rounds_per_wait  a measurement's switch: the rounds the host loop enqueues per wait become n (1..64,
+//                              anything else only reads); returns what they were (4 unless changed)
+extern "C" int32_t svh_test_grid_plan_rounds_per_wait(int32_t n);
+extern "C" int32_t svh_test_grid_plan_device(int32_t nx, int32_t nz, const svh_grid_plan_params* p, const uint8_t* cost,
+                                             const int32_t* goals, int32_t n, int32_t* pot, uint8_t* dir, int64_t out[3]);
+
 // The guard of every HIP call of the host engines: `kind` is one of none, malloc, copy, launch, wait (see above); a
 // disarmed hook costs one relaxed load.  Returns hip_failed(...) out of the enclosing function on failure.
 #define SVH_HIP_TRY(entry, kind, expr)                                                                  \

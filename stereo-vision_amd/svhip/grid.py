@@ -21,6 +21,12 @@ TRAV_DTYPE = [np.uint8, np.int32, np.uint8]
 STEEP, LETHAL = 1, 2
 LETHAL_OBSTACLE, LETHAL_DROP, LETHAL_STEEP, LETHAL_UNSEEN, LETHAL_UNKNOWN_SEEN = 1, 2, 4, 8, 16
 DIST2_FAR = 0x7FFFFFFF
+PLAN_POT, PLAN_DIR = range(2)
+PLAN_DTYPE = [np.int32, np.uint8]
+PLAN_FAR = 0x7FFFFFFF
+DIR_GOAL, DIR_NONE = 8, 9
+PATH_FOUND, PATH_UNREACHABLE, PATH_BLOCKED, PATH_OUTSIDE = range(4)
+GOAL_COLOUR, PATH_COLOUR = (255, 255, 0), (255, 255, 255)
 
 
 class Params(C.Structure):
@@ -51,6 +57,20 @@ class TravParams(C.Structure):
 
     def asdict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class PlanParams(C.Structure):
+    """svh_grid_plan_params"""
+    _fields_ = [("neutral", C.c_int32), ("unknown", C.c_int32), ("max_cost", C.c_int32)]
+
+    def copy(self, **kw):
+        q = PlanParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -105,6 +125,21 @@ def _bind():
         L.svh_grid_render_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.svh_test_grid_trav.argtypes = [C.POINTER(Params), C.POINTER(TravParams)] + [C.c_void_p] * 7
         L.svh_test_grid_cost_table.argtypes = [C.c_float, C.POINTER(TravParams), C.c_void_p, C.c_void_p, C.c_int64]
+        L.svh_grid_plan_params_default.argtypes = [C.POINTER(PlanParams)]
+        L.svh_grid_plan_params_default.restype = None
+        L.svh_grid_set_plan.argtypes = [C.c_void_p, C.POINTER(PlanParams)]
+        L.svh_grid_get_plan.argtypes = [C.c_void_p, C.POINTER(PlanParams)]
+        L.svh_grid_plan_set_goals.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_grid_plan_set_goal.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_get_plan_plane.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_get_plan_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_plan_path.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.svh_grid_render_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
+        L.svh_test_grid_plan.argtypes = [C.POINTER(PlanParams)] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.svh_test_grid_path.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_test_grid_plan_tile.argtypes = []
+        L.svh_test_grid_plan_device.argtypes = [C.c_int32, C.c_int32, C.POINTER(PlanParams), C.c_void_p, C.c_void_p, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
         L._grid_bound = True
     return L
 
@@ -212,6 +247,61 @@ def core_cost_table(cell, trav):
     table = np.zeros(reach.value ** 2 + 1, np.uint8)
     _check(L.svh_test_grid_cost_table(cell, C.byref(trav), C.addressof(reach), table.ctypes.data, len(table)))
     return table
+
+
+def default_plan(**kw):
+    p = PlanParams()
+    _bind().svh_grid_plan_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def _cells(cells):
+    c = np.ascontiguousarray(cells, np.int32).reshape(-1, 2)
+    return c, (c.ctypes.data if len(c) else None)
+
+
+def core_plan(params, plan, cost, goals, oa=0, ob=0):
+    """the planner of csrc/grid_plan_core.h on the host (svh_test_grid_plan), a heap Dijkstra, for a window of params.nx x
+    params.nz cells under the offsets (oa, ob): (pot int32, dir uint8, each [nz, nx]; the goals that count); needs no device"""
+    sh = (params.nz, params.nx)
+    c = np.ascontiguousarray(cost, np.uint8).reshape(sh)
+    g, gp = _cells(goals)
+    pot, dir_ = np.zeros(sh, np.int32), np.zeros(sh, np.uint8)
+    n = _check(_bind().svh_test_grid_plan(C.byref(plan), params.nx, params.nz, oa, ob, c.ctypes.data, gp, len(g), pot.ctypes.data,
+                                          dir_.ctypes.data))
+    return pot, dir_, n
+
+
+def core_path(dir_, a, b, oa=0, ob=0):
+    """the walk of csrc/grid_plan_core.h over a DIR plane [nz, nx] from the window cell (a, b), on the host: [n, 2] int32
+    global cells, n = 0 where DIR leads to no goal; needs no device"""
+    d = np.ascontiguousarray(dir_, np.uint8)
+    nz, nx = d.shape
+    cells, n = np.zeros((nx * nz, 2), np.int32), C.c_int64(-1)
+    _check(_bind().svh_test_grid_path(nx, nz, oa, ob, d.ctypes.data, a, b, cells.ctypes.data, nx * nz, C.addressof(n)))
+    return cells[:n.value].copy()
+
+
+def plan_tile():
+    """the tile side the planner's kernels were built with"""
+    return int(_bind().svh_test_grid_plan_tile())
+
+
+def device_plan(nx, nz, plan, cost, goals):
+    """TEST ENTRY: the planner's device kernels on a caller's cost plane (uint8 [nz, nx], window offsets 0):
+    (pot int32 [nz, nx], dir uint8 [nz, nx], rounds)"""
+    c = np.ascontiguousarray(cost, np.uint8).reshape(nz, nx)
+    g, gp = _cells(goals)
+    pot, dir_, out = np.zeros((nz, nx), np.int32), np.zeros((nz, nx), np.uint8), np.zeros(3, np.int64)
+    _check(_bind().svh_test_grid_plan_device(nx, nz, C.byref(plan), c.ctypes.data, gp, len(g), pot.ctypes.data, dir_.ctypes.data,
+                                             out.ctypes.data))
+    return pot, dir_, int(out[2])
+
+
+def __getattr__(name):
+    if name == "PLAN_TILE":
+        return plan_tile()
+    raise AttributeError(name)
 
 
 def _xyz(p):
@@ -338,6 +428,63 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_cost(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_plan(self, params=None, **kw):
+        """the plan parameters in force (or `params`) with the fields of kw replaced: neutral, unknown, max_cost"""
+        p = (params if params is not None else self.plan_params()).copy(**kw)
+        _check(self._L.svh_grid_set_plan(self._h, C.byref(p)))
+
+    def plan_params(self):
+        p = PlanParams()
+        _check(self._L.svh_grid_get_plan(self._h, C.byref(p)))
+        return p
+
+    def set_goals(self, cells):
+        """[n, 2] global cells (ga, gb); an empty list forgets the goals"""
+        c, ptr = _cells(cells)
+        _check(self._L.svh_grid_plan_set_goals(self._h, ptr, len(c)))
+
+    def set_goal(self, xyz):
+        """one goal, the cell of a map-frame position"""
+        _check(self._L.svh_grid_plan_set_goal(self._h, _xyz(xyz).ctypes.data))
+
+    def plan_plane(self, which, device_ptr=None):
+        """PLAN_POT int32 or PLAN_DIR uint8, [nz, nx]; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_plan_plane(self._h, which, device_ptr, 1))
+            return None
+        if not 0 <= which < len(PLAN_DTYPE):
+            raise SvhError(ERR_BAD_ARG, "no such plane")
+        out = np.zeros((self.nz, self.nx), PLAN_DTYPE[which])
+        _check(self._L.svh_grid_get_plan_plane(self._h, which, out.ctypes.data, 0))
+        return out
+
+    def plan_stats(self):
+        """(goals given, goals that count, cells with POT != FAR, relaxation rounds)"""
+        out = np.zeros(4, np.int64)
+        _check(self._L.svh_grid_get_plan_stats(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def path(self, start_xyz, cap=None):
+        """(status, cells [n, 2] int32 global, cost): the shortest path from the cell of a map-frame position; with cap only
+        its first cells, and n is still the length of the whole path in `path_len`"""
+        room = self.nx * self.nz if cap is None else int(cap)
+        cells = np.zeros((max(room, 1), 2), np.int32)
+        n, cost = C.c_int64(-1), C.c_int32(-1)
+        status = _check(self._L.svh_grid_plan_path(self._h, _xyz(start_xyz).ctypes.data, cells.ctypes.data if room else None, room,
+                                                   C.addressof(n), C.addressof(cost)))
+        self.path_len = n.value
+        return status, cells[:min(n.value, room)].copy(), cost.value
+
+    def render_plan(self, cells=(), device_ptr=None):
+        """render_cost with the goals that count in GOAL_COLOUR and the given global cells in PATH_COLOUR over them"""
+        c, ptr = _cells(cells)
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_plan(self._h, ptr, len(c), device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_plan(self._h, ptr, len(c), img.ctypes.data, 0))
         return img
 
     def stats(self):

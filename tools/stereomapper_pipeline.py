@@ -17,6 +17,7 @@ without the GUI.  Usage:
                                           [--grid DIR [--grid-cell S] [--grid-size NXxNZ] [--level]]
                                           [--grid-local DIR [--grid-cell S] [--grid-size NXxNZ]]
                                           [--grid-cost DIR [--grid-slope S] [--grid-inscribed M] [--grid-inflate M]]
+                                         [--grid-plan DIR [--grid-goal-ahead M]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -76,6 +77,13 @@ space dark green, unknown cells dark grey, steep cells with a full green byte.  
 between neighbouring free cells (0.35); --grid-inscribed M and --grid-inflate M: the two radii in metres (0.4, 1.5).  The
 inflation radius must be at most 256 cells.
 
+--grid-plan DIR: needs --grid-cost.  After every local step a route on the cost map (svh_grid_plan_*): the goals are all
+cells of the window row M metres (--grid-goal-ahead, 20) in front of the camera's cell -- the farthest row where the window
+ends sooner --, so a blocked cell ahead does not end the route; the start is the camera's position; unknown cells are
+passable at a price of 100 above the neutral one.  The plan image (svh_grid_render_plan: the cost map, the goals that count
+yellow, the path white) goes into DIR/plan_%06d.ppm and one line {"frame", "status", "length", "cost"} per frame is appended
+to DIR/plan.jsonl (status 0 found, 1 unreachable, 2 the camera's cell is impassable, 3 outside).
+
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
 svh_vo_get_gain_batch, svh_elas_process_batch_device and svh_map_add_batch_device run once for all K, then one view per
@@ -85,6 +93,7 @@ those of `--resident` on that drive alone.  --render / --panes do not apply.
 Python is glue here (ctypes over libsvhip.so); the pose accumulation H_total = H_total * inv(H_delta)
 uses numpy where the reference uses Matrix::solve."""
 import ctypes as C
+import json
 import os
 import sys
 import time
@@ -183,6 +192,17 @@ class Pipeline:
     def set_grid_cost(self, **kw):
         """the traversability parameters of the local grid: max_slope, inscribed, inflate"""
         self.local.set_traversability(**kw)
+
+    def plan_step(self, ahead=20.0):
+        """goals on the window row `ahead` metres in front of the camera's cell, the path from the camera's position:
+        (status, cells [n, 2], cost, the plan image [nz, nx, 3])"""
+        g = self.local
+        centre = self.H_total[:3, 3].copy()
+        (_, gb), (oa, ob) = g.cell_of(centre), g.window()
+        row = min(gb + int(round(ahead / g.params.cell)), ob + g.nz - 1)
+        g.set_goals([(oa + ia, row) for ia in range(g.nx)])
+        status, cells, cost = g.path(centre)
+        return status, cells, cost, g.render_plan(cells)
 
     def local_step(self):
         """follow the camera centre to the middle cell, add the newest list with rays from it, render: [nz, nx, 3]"""
@@ -460,6 +480,7 @@ def main():
     thin, thin_every, ply = None, 1, None
     grid_dir, grid_cell, grid_size = None, 0.2, (256, 256)
     local_dir, cost_dir, cost_kw = None, None, {}
+    plan_dir, goal_ahead = None, None
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -491,6 +512,17 @@ def main():
                 k = sys.argv.index(flag)
                 cost_kw[name] = float(sys.argv[k + 1])
                 del sys.argv[k:k + 2]
+        if "--grid-plan" in sys.argv:
+            k = sys.argv.index("--grid-plan")
+            plan_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-goal-ahead" in sys.argv:
+            k = sys.argv.index("--grid-goal-ahead")
+            goal_ahead = float(sys.argv[k + 1])
+            assert goal_ahead >= 0 and goal_ahead < float("inf")
+            del sys.argv[k:k + 2]
+        assert cost_dir or not plan_dir
+        assert plan_dir or goal_ahead is None
         assert local_dir or not (cost_dir or cost_kw)
         assert cost_dir or not cost_kw
         assert grid_dir or not level
@@ -550,6 +582,9 @@ def main():
         os.makedirs(local_dir, exist_ok=True)
     if cost_dir:
         os.makedirs(cost_dir, exist_ok=True)
+    if plan_dir:
+        os.makedirs(plan_dir, exist_ok=True)
+        open(os.path.join(plan_dir, "plan.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -560,6 +595,9 @@ def main():
         p.enable_grid_local(grid_cell, grid_size)
     if cost_dir:
         p.set_grid_cost(**cost_kw)
+    if plan_dir:
+        p.local.set_plan(unknown=100)
+    found = 0
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -578,6 +616,12 @@ def main():
             view.write_ppm(os.path.join(local_dir, "local_%06d.ppm" % (frames - 1)), p.local_step())
         if cost_dir:
             view.write_ppm(os.path.join(cost_dir, "cost_%06d.ppm" % (frames - 1)), p.local.render_cost())
+        if plan_dir:
+            status, cells, cost, img = p.plan_step(20.0 if goal_ahead is None else goal_ahead)
+            found += status == 0
+            view.write_ppm(os.path.join(plan_dir, "plan_%06d.ppm" % (frames - 1)), img)
+            with open(os.path.join(plan_dir, "plan.jsonl"), "a") as f:
+                f.write(json.dumps({"frame": frames - 1, "status": int(status), "length": int(len(cells)), "cost": int(cost)}) + "\n")
         if frames >= limit:
             break
     dt = time.perf_counter() - t0
@@ -597,6 +641,9 @@ def main():
         t, reach = p.local.traversability()
         print("cost map: slope %g, inscribed %g m, inflation %g m = %d cells; %d images in %s" % (
             t.max_slope, t.inscribed, t.inflate, reach, frames, cost_dir))
+    if plan_dir:
+        print("plan: goals %g m ahead, a route in %d of %d frames; %d images and plan.jsonl in %s" % (
+            20.0 if goal_ahead is None else goal_ahead, found, frames, frames, plan_dir))
     if render_dir:
         n, images = p.view.record_human()
         for k in range(n):
