@@ -4,7 +4,8 @@
 // Host (this file): the parameters (T rounded to float once), the two frames, the window's offsets, the statistics, the
 // lazy clear and the lazy finalise.  Device (grid_kernels.hip): the binning, the rays, the strips of a scroll, the
 // finalise, the render; (grid_trav_kernels.hip): the traversability layer -- flags, obstacle distance, cost, its render;
-// (grid_plan_kernels.hip): the planner -- the relaxation over active tiles, whose round loop is plan_rounds() here.
+// (grid_plan_kernels.hip): the planner -- the relaxation over active tiles, whose round loop is plan_rounds() here;
+// (grid_front_kernels.hip): the frontiers -- mask, union-find labelling, the table of components, run by front_run() here.
 // The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
@@ -16,7 +17,9 @@
 // enter; on an empty grid it changes the offsets alone.  The traversability planes are derived from the finished ones, as
 // lazily, and kept until the accumulators or the traversability parameters change (trav_valid).  The planner's field (POT,
 // DIR; grid_plan_kernels.hip) is derived from COST and the goals, as lazily, and kept beside it (plan_valid) until the
-// accumulators, the offsets, the traversability, the plan parameters or the goals change.
+// accumulators, the offsets, the traversability, the plan parameters or the goals change.  The frontier result (FRONT, LABEL,
+// the table) is derived from STATE and COST, as lazily, and kept (front_valid) until the accumulators, the offsets, the
+// traversability or the frontier parameters change.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -47,6 +50,7 @@ enum FinPlane { F_COUNT = 0, F_OVERHEAD, F_PASS, F_HMIN, F_HMAX, F_HMEAN, F_WORD
 enum FinByte { B_INTENSITY = 0, B_CLASS, B_STATE };                                    // its byte planes
 constexpr size_t kTravBytes = 8;                   // per cell: DIST2; g (uint16); FLAGS, COST
 constexpr size_t kPlanBytes = 7;                   // per cell: POT; price (uint16); DIR
+constexpr size_t kFrontBytes = 5;                  // per cell: LABEL; FRONT
 // rounds of the relaxation enqueued per wait: a round whose list is empty costs one empty launch, a wait costs a round trip,
 // and the bound on the workgroups of a round grows with its distance from the last known length.  Measured alternating in one
 // process at 1, 2, 4, 8 and 16 (profiles/grid_plan_times.jsonl; ms on an open field of 256^2 / 1024^2 / 8192^2 cells):
@@ -71,6 +75,15 @@ bool convert(const svh_grid_params* p, grid::Params* q) {
     q->h_lo = p->render_h_lo, q->h_hi = p->render_h_hi;
     return grid::params_ok(*q);
 }
+
+// what a frontier computation needs beside the two planes: the block counts of the ordered compactions, the control words and
+// their pinned copy, and what is sized by the components once their number is known
+struct FrontBufs {
+    HipBuf<int32_t> blocks, roots, recs;
+    HipBuf<uint8_t> acc;
+    HipBuf<unsigned long long> ctl;
+    PinnedBuf<unsigned long long> h_ctl;
+};
 
 }  // namespace
 
@@ -113,6 +126,11 @@ struct svh_grid {
     HipBuf<int32_t> d_path;     // the cells a walk writes, or a caller's path for the plan image
     HipBuf<int64_t> d_walk;     // status, length, cost
     PinnedBuf<int64_t> h_walk;
+    grid::FrontParams frp{252, 8, grid::LETHAL_UNSEEN, 0};   // the frontiers: parameters, planes, table
+    HipBuf<uint8_t> front;      // kFrontBytes per cell: LABEL | FRONT, logical order
+    FrontBufs front_bufs;
+    bool front_valid = false;   // ... derived from STATE and COST as they are, with the offsets and parameters as they are; implies trav_valid
+    int64_t front_stats[grid::FS_WORDS] = {0, 0, 0, 0, 0};   // of the result that is valid
     svh_grid_stats st{0, 0, 0, 0, 0};
     int64_t rays = 0, ray_cells = 0;
 
@@ -132,12 +150,14 @@ struct svh_grid {
     int32_t* p_pot() const { return (int32_t*)plan.p; }
     uint16_t* p_price() const { return (uint16_t*)(plan.p + 4 * ncells); }
     uint8_t* p_dir() const { return plan.p + 6 * ncells; }
+    int32_t* f_label() const { return (int32_t*)front.p; }
+    uint8_t* f_flags() const { return front.p + 4 * ncells; }
 };
 
 namespace {
 
 // the accumulators change: what was derived from them is stale
-void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = g->plan_valid = false; }
+void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = g->plan_valid = g->front_valid = false; }
 
 void mark_empty(svh_grid* g) {
     g->need_clear = true;
@@ -525,7 +545,120 @@ int planned(svh_grid* g, int rc) {
     return drained(g, rc);
 }
 
-const char* const kNoTrav = ": the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)";
+// ---- the frontiers --------------------------------------------------------------------------------------------------------
+const char* const kUnsettled = "Grid: the labelling of the frontiers did not settle within its bounds";
+
+// The whole computation on a job whose planes exist (state, cost, flags, label): FRONT_LAUNCHES launches whatever the scene, and
+// two waits -- the number of components sizes the accumulators, so it comes back through pinned memory before they are made;
+// the kept count comes back the same way at the end.  The table stays on the device.  Complete when it returns.
+int front_run(hipStream_t s, grid::FrontJob& j, FrontBufs& b, int64_t stats[grid::FS_WORDS]) {
+    const size_t ctl_bytes = grid::FC_WORDS * sizeof(unsigned long long);
+    GRID_GROW_N(b.blocks, grid::front_blocks(j));
+    GRID_GROW(b.ctl, ctl_bytes);
+    GRID_GROW(b.h_ctl, ctl_bytes);
+    j.blockcnt = b.blocks, j.ctl = b.ctl;
+    GRID_TRY(copy, hipMemsetAsync(j.ctl, 0, ctl_bytes, s));
+    int64_t launches = grid::launch_front_mask(s, j);
+    launches += grid::launch_front_label(s, j);
+    launches += grid::launch_front_count(s, j);
+    GRID_TRY(launch, hipGetLastError());
+    GRID_TRY(copy, hipMemcpyAsync(b.h_ctl, j.ctl, ctl_bytes, hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    const unsigned long long* h = b.h_ctl;
+    if (h[grid::FC_UNSETTLED]) return svh::fail(SVH_ERR_HIP, kUnsettled);
+    const size_t n = (size_t)h[grid::FC_COMPONENTS], room = n ? n : 1;
+    const size_t kept_cap = std::min<size_t>(n, (size_t)h[grid::FC_CELLS] / (size_t)j.frp.min_size);   // a kept component has min_size cells
+    GRID_GROW_N(b.roots, n);
+    GRID_GROW(b.acc, grid::FRONT_COMP_BYTES * room);
+    GRID_GROW_N(b.recs, (size_t)grid::FRONT_REC * kept_cap);
+    j.n_comp = (int32_t)n, j.roots = b.roots, j.acc = b.acc, j.recs = b.recs;
+    const grid::FrontAcc acc = grid::front_acc(j.acc, room);
+    GRID_TRY(copy, hipMemsetAsync(j.acc, 0, grid::FRONT_COMP_BYTES * room, s));
+    GRID_TRY(copy, hipMemsetAsync(acc.rep, 0xFF, 8 * room, s));
+    GRID_TRY(copy, hipMemsetAsync(acc.bmin, 0x7F, 8 * room, s));
+    launches += grid::launch_front_table(s, j);
+    GRID_TRY(launch, hipGetLastError());
+    GRID_TRY(copy, hipMemcpyAsync(b.h_ctl, j.ctl, ctl_bytes, hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    if (h[grid::FC_UNSETTLED]) return svh::fail(SVH_ERR_HIP, kUnsettled);
+    stats[grid::FS_CELLS] = (int64_t)h[grid::FC_CELLS], stats[grid::FS_COMPONENTS] = (int64_t)h[grid::FC_COMPONENTS];
+    stats[grid::FS_KEPT] = (int64_t)h[grid::FC_KEPT], stats[grid::FS_KEPT_CELLS] = (int64_t)h[grid::FC_KEPT_CELLS];
+    stats[grid::FS_LAUNCHES] = launches;
+    return SVH_OK;
+}
+
+// the frontier result is valid: the cost planes, then front_run
+int frontiers(svh_grid* g) {
+    if (g->front_valid) return SVH_OK;
+    GRID_GROW(g->front, g->ncells * kFrontBytes);
+    int rc = traverse(g);
+    if (rc) return rc;
+    grid::FrontJob j;
+    j.frp = g->frp;
+    j.nx = g->prm.nx, j.nz = g->prm.nz, j.oa = g->prm.oa, j.ob = g->prm.ob;
+    j.state = g->bplane(B_STATE), j.cost = g->t_cost();
+    j.flags = g->f_flags(), j.label = g->f_label();
+    int64_t stats[grid::FS_WORDS];
+    if ((rc = front_run(g->stream, j, g->front_bufs, stats))) return rc;
+    memcpy(g->front_stats, stats, sizeof(stats));
+    g->final_valid = g->trav_valid = g->front_valid = true;
+    return SVH_OK;
+}
+
+int get_front(svh_grid* g, int32_t plane, void* out, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = frontiers(g))) return rc;
+    return plane == grid::FP_LABEL ? deliver(g, g->f_label(), g->ncells * 4, out, on_device) : deliver(g, g->f_flags(), g->ncells, out, on_device);
+}
+
+// *n = the kept components, the first min(*n, cap) records to the host
+int get_frontiers(svh_grid* g, int32_t* recs, int64_t cap, int64_t* n) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = frontiers(g))) return rc;
+    const int64_t kept = g->front_stats[grid::FS_KEPT], m = std::min(kept, cap);
+    if (m > 0 && (rc = deliver(g, g->front_bufs.recs, (size_t)m * grid::FRONT_REC * sizeof(int32_t), recs, false))) return rc;
+    *n = kept;
+    return SVH_OK;
+}
+
+int render_frontiers(svh_grid* g, uint8_t* rgb, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const size_t bytes = g->ncells * 3;
+    if (!on_device) {
+        GRID_GROW(g->d_rgb, bytes);
+        GRID_GROW(g->h_out, bytes);
+    }
+    if ((rc = frontiers(g))) return rc;
+    grid::RenderCostJob j;
+    j.nx = g->prm.nx, j.nz = g->prm.nz;
+    j.cost = g->t_cost(), j.flags = g->t_flags();
+    j.rgb = on_device ? rgb : g->d_rgb.p;
+    grid::launch_render_cost(g->stream, j);
+    grid::launch_front_overlay(g->stream, j.nx, j.nz, g->f_flags(), j.rgb);
+    GRID_TRY(launch, hipGetLastError());
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+        return SVH_OK;
+    }
+    return deliver(g, g->d_rgb, bytes, rgb, false);
+}
+
+// a frontier call that failed on the device: nothing in flight, the result is computed again by the next call
+int fronted(svh_grid* g, int rc) {
+    if (rc == SVH_ERR_HIP) g->front_valid = false;
+    return drained(g, rc);
+}
+
+bool convert_front(const svh_grid_front_params* p, grid::FrontParams* q) {
+    if (!p) return false;
+    *q = grid::FrontParams{p->max_cell_cost, p->min_size, p->unexplored, p->border};
+    return grid::front_ok(*q);
+}
+
+const char* const kNoTrav =": the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)";
 
 // ... and a failed add leaves the empty grid
 int added(svh_grid* g, int rc) {
@@ -799,7 +932,7 @@ int32_t svh_grid_set_traversability(svh_grid* g, const svh_grid_trav_params* t) 
     g->trv = q;
     g->table.swap(table);
     g->trav_ok = true;
-    g->trav_valid = g->plan_valid = g->table_sent = false;
+    g->trav_valid = g->plan_valid = g->front_valid = g->table_sent = false;
     return drained(g, send_table(g));   // a failed upload is repeated by the next svh_grid_get_trav / svh_grid_render_cost
 }
 
@@ -902,6 +1035,178 @@ int32_t svh_grid_render_plan(svh_grid* g, const int32_t* cells, int64_t n, uint8
     if (!g || !rgb || n < 0 || (n > 0 && !cells)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_plan: a grid, n >= 0 cells and an output are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_plan") + kNoTrav);
     return planned(g, render_plan(g, cells, n, rgb, on_device != 0));
+}
+
+void svh_grid_front_params_default(svh_grid_front_params* p) {
+    if (!p) return;
+    p->max_cell_cost = 252, p->min_size = 8, p->unexplored = SVH_GRID_LETHAL_UNSEEN, p->border = 0;
+}
+
+int32_t svh_grid_set_frontier(svh_grid* g, const svh_grid_front_params* p) {
+    grid::FrontParams q;
+    if (!g || !convert_front(p, &q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_frontier: a grid and parameters in range are needed (include/svh_grid.h)");
+    g->frp = q;
+    g->front_valid = false;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_frontier(svh_grid* g, svh_grid_front_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_frontier: null argument");
+    p->max_cell_cost = g->frp.max_cell_cost, p->min_size = g->frp.min_size, p->unexplored = g->frp.unexplored, p->border = g->frp.border;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_front_plane(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::FP_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_front_plane: a grid, a plane 0..1 and an output are needed");
+    if (on_device && plane == grid::FP_LABEL && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_front_plane: a device array of LABEL must be 4-byte aligned");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_front_plane") + kNoTrav);
+    return fronted(g, get_front(g, plane, out, on_device != 0));
+}
+
+int32_t svh_grid_get_frontiers(svh_grid* g, int32_t* recs, int64_t cap, int64_t* n) {
+    if (!g || !n || cap < 0 || (cap > 0 && !recs)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_frontiers: a grid, a count and room for cap >= 0 records are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_frontiers") + kNoTrav);
+    return fronted(g, get_frontiers(g, recs, cap, n));
+}
+
+int32_t svh_grid_get_frontier_stats(svh_grid* g, int64_t out[5]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_frontier_stats: null argument");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_frontier_stats") + kNoTrav);
+    int rc = ready(g);
+    if (!rc) rc = frontiers(g);
+    if (rc) return fronted(g, rc);
+    memcpy(out, g->front_stats, sizeof(g->front_stats));
+    return SVH_OK;
+}
+
+int32_t svh_grid_plan_set_goals_frontiers(svh_grid* g) {
+    if (!g) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_plan_set_goals_frontiers: null argument");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_plan_set_goals_frontiers") + kNoTrav);
+    int64_t kept = 0;
+    std::vector<int32_t> recs;
+    int rc = ready(g);
+    if (!rc) rc = frontiers(g);
+    if (!rc) {
+        recs.resize((size_t)std::min<int64_t>(g->front_stats[grid::FS_KEPT], grid::PLAN_MAX_GOALS) * grid::FRONT_REC);
+        rc = get_frontiers(g, recs.data(), (int64_t)(recs.size() / grid::FRONT_REC), &kept);
+    }
+    if (rc) return fronted(g, rc);                     // the goals are as they were
+    const size_t m = recs.size() / grid::FRONT_REC;
+    g->goals.resize(2 * m);
+    for (size_t k = 0; k < m; k++)
+        g->goals[2 * k] = recs[k * grid::FRONT_REC + grid::FR_REP_GA], g->goals[2 * k + 1] = recs[k * grid::FRONT_REC + grid::FR_REP_GB];
+    g->goals_sent = g->plan_valid = false;
+    return (int32_t)m;
+}
+
+int32_t svh_grid_render_frontiers(svh_grid* g, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_frontiers: a grid and an output are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_frontiers") + kNoTrav);
+    return fronted(g, render_frontiers(g, rgb, on_device != 0));
+}
+
+// grid_front_core.h on the host.  Needs no device
+int32_t svh_test_grid_front(const svh_grid_front_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* state,
+                            const uint8_t* cost, uint8_t* flags, int32_t* label, int32_t* recs, int64_t cap, int64_t* n, int64_t* stats) {
+    grid::FrontParams q;
+    if (!convert_front(p, &q) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) || !state || !cost ||
+        cap < 0 || (cap > 0 && !recs))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_front: bad arguments");
+    const size_t cells = (size_t)nx * (size_t)nz;
+    std::vector<uint8_t> f(cells);
+    std::vector<int32_t> l(cells), r;
+    int64_t st[grid::FS_WORDS];
+    grid::front_window(q, nx, nz, oa, ob, state, cost, f.data(), l.data(), &r, st);
+    if (flags) memcpy(flags, f.data(), cells);
+    if (label) memcpy(label, l.data(), cells * sizeof(int32_t));
+    if (cap > 0) memcpy(recs, r.data(), std::min(r.size(), (size_t)cap * grid::FRONT_REC) * sizeof(int32_t));
+    if (n) *n = st[grid::FS_KEPT];
+    if (stats) memcpy(stats, st, sizeof(st));
+    return SVH_OK;
+}
+
+int32_t svh_test_grid_front_tile(void) { return grid::FRONT_TILE; }
+
+// the kernels of the frontiers on a caller's STATE and COST planes (host, nx x nz)
+int32_t svh_test_grid_front_device(const svh_grid_front_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* state,
+                                   const uint8_t* cost, uint8_t* flags, int32_t* label, int32_t* recs, int64_t cap, int64_t* n,
+                                   int64_t* stats) {
+    grid::FrontJob j;
+    if (!convert_front(p, &j.frp) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) || !state || !cost ||
+        cap < 0 || (cap > 0 && !recs))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_front_device: bad arguments");
+    svh::ensure_init();
+    j.nx = nx, j.nz = nz, j.oa = oa, j.ob = ob;
+    const size_t cells = (size_t)nx * (size_t)nz;
+    HipBuf<uint8_t> in, planes;
+    FrontBufs bufs;
+    int64_t st[grid::FS_WORDS] = {0, 0, 0, 0, 0};
+    hipStream_t s = nullptr;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(in, 2 * cells);
+        GRID_GROW(planes, cells * kFrontBytes);
+        GRID_TRY(copy, hipMemcpyAsync(in, state, cells, hipMemcpyHostToDevice, s));
+        GRID_TRY(copy, hipMemcpyAsync(in + cells, cost, cells, hipMemcpyHostToDevice, s));
+        j.state = in.p, j.cost = in.p + cells;
+        j.label = (int32_t*)planes.p, j.flags = planes.p + 4 * cells;
+        const int r = front_run(s, j, bufs, st);
+        if (r) return r;
+        const size_t m = (size_t)std::min<int64_t>(st[grid::FS_KEPT], cap);
+        if (flags) GRID_TRY(copy, hipMemcpyAsync(flags, j.flags, cells, hipMemcpyDeviceToHost, s));
+        if (label) GRID_TRY(copy, hipMemcpyAsync(label, j.label, cells * 4, hipMemcpyDeviceToHost, s));
+        if (m > 0) GRID_TRY(copy, hipMemcpyAsync(recs, j.recs, m * grid::FRONT_REC * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    if (n) *n = st[grid::FS_KEPT];
+    if (stats) memcpy(stats, st, sizeof(st));
+    return SVH_OK;
+}
+
+// the labelling stage alone on a mask (host, nx x nz, nonzero: a cell to label)
+int32_t svh_test_grid_front_label_device(int32_t nx, int32_t nz, const uint8_t* mask, int32_t* label, int64_t* launches) {
+    if (nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !mask || !label)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_front_label_device: bad arguments");
+    svh::ensure_init();
+    grid::FrontJob j{};
+    j.nx = nx, j.nz = nz;
+    const size_t cells = (size_t)nx * (size_t)nz;
+    for (size_t i = 0; i < cells; i++) label[i] = mask[i] ? (int32_t)i : -1;
+    HipBuf<int32_t> d_label;
+    HipBuf<unsigned long long> d_ctl;
+    PinnedBuf<unsigned long long> h_ctl;
+    const size_t ctl_bytes = grid::FC_WORDS * sizeof(unsigned long long);
+    int64_t launched = 0;
+    hipStream_t s = nullptr;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(d_label, cells * sizeof(int32_t));
+        GRID_GROW(d_ctl, ctl_bytes);
+        GRID_GROW(h_ctl, ctl_bytes);
+        GRID_TRY(copy, hipMemsetAsync(d_ctl, 0, ctl_bytes, s));
+        GRID_TRY(copy, hipMemcpyAsync(d_label, label, cells * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        j.label = d_label, j.ctl = d_ctl;
+        launched = grid::launch_front_label(s, j);
+        GRID_TRY(launch, hipGetLastError());
+        GRID_TRY(copy, hipMemcpyAsync(label, d_label, cells * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(h_ctl, d_ctl, ctl_bytes, hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        if (h_ctl.p[grid::FC_UNSETTLED]) return svh::fail(SVH_ERR_HIP, kUnsettled);
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    if (launches) *launches = launched;
+    return SVH_OK;
 }
 
 // grid_plan_core.h on the host: POT and DIR of a window of nx x nz cells from its COST plane and n goals (global cells under

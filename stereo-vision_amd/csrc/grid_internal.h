@@ -1,5 +1,5 @@
-// Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip: the
-// launches of the ground grid (include/svh_grid.h).
+// Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
+// csrc/grid_front_kernels.hip: the launches of the ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
 
@@ -7,6 +7,7 @@
 #include <hip/hip_vector_types.h>
 
 #include "grid_core.h"
+#include "grid_front_core.h"
 #include "grid_plan_core.h"
 
 namespace svh {
@@ -161,6 +162,64 @@ void launch_plan_dir(hipStream_t s, const PlanJob& j);
 void launch_plan_walk(hipStream_t s, const PlanJob& j, int32_t a, int32_t b, int32_t* cells, int64_t cap, int64_t* out);
 // n global cells drawn into an image of svh_grid_render_cost's layout: a path, or (goals) only those that count
 void launch_plan_overlay(hipStream_t s, const PlanJob& j, const int32_t* cells, int64_t n, bool goals, uint8_t* rgb);
+
+// The frontiers (csrc/grid_front_kernels.hip): the finished STATE and COST planes -> FRONT, LABEL and the table of components.
+#ifndef SVH_FRONT_TILE
+#define SVH_FRONT_TILE 16
+#endif
+constexpr int32_t FRONT_TILE = SVH_FRONT_TILE;   // k_grid_front_tile: one workgroup per tile of this side, one lane per cell
+constexpr uint32_t FRONT_BLOCK = 256;
+static_assert(FRONT_TILE * FRONT_TILE == (int32_t)FRONT_BLOCK, "a tile is one pass of 256 lanes");
+constexpr uint32_t FRONT_SCAN_BLOCK = 1024;      // the ordered compactions count and scatter in blocks of this many
+constexpr uint32_t FRONT_UNION_TRIES = 1024;     // a union gives up after this many lost atomics (each lost to another union's link)
+// the launches of one computation, a constant of the build: mask; tile, merge, flatten; roots counted, scanned | scattered;
+// accumulate, centroids, representatives; kept counted, scanned, records; flags
+constexpr int32_t FRONT_LABEL_LAUNCHES = 3, FRONT_LAUNCHES = 14;
+// the control words on the device, 64 bits each
+enum FrontCtl { FC_CELLS = 0, FC_COMPONENTS, FC_KEPT, FC_KEPT_CELLS, FC_UNSETTLED, FC_WORDS = 8 };
+// bytes per component of the accumulators: sum (2 x 64 bits), rep (64 bits), size, box max (2), box min (2), centroid (2)
+constexpr size_t FRONT_COMP_BYTES = 52;
+
+struct FrontJob {
+    FrontParams frp;
+    int32_t nx, nz, oa, ob;
+    const uint8_t* state;       // the finished planes
+    const uint8_t* cost;
+    uint8_t* flags;             // nx * nz each, logical order
+    int32_t* label;             // ... the parent plane of the union-find until it is flattened
+    int32_t* blockcnt;          // ceil(nx * nz / FRONT_SCAN_BLOCK) counts, then offsets; used again for the components
+    unsigned long long* ctl;    // FC_WORDS, all zero before
+    // what exists once the number of components is known (front_table)
+    int32_t n_comp = 0;
+    int32_t* roots = nullptr;   // n_comp labels, ascending
+    uint8_t* acc = nullptr;     // FRONT_COMP_BYTES per component, laid out by front_acc below
+    int32_t* recs = nullptr;    // FRONT_REC per kept component
+};
+inline uint32_t front_tiles_x(const FrontJob& j) { return ((uint32_t)j.nx + (uint32_t)FRONT_TILE - 1) / (uint32_t)FRONT_TILE; }
+inline uint32_t front_tiles_y(const FrontJob& j) { return ((uint32_t)j.nz + (uint32_t)FRONT_TILE - 1) / (uint32_t)FRONT_TILE; }
+inline size_t front_blocks(const FrontJob& j) { return ((size_t)j.nx * (size_t)j.nz + FRONT_SCAN_BLOCK - 1) / FRONT_SCAN_BLOCK; }
+struct FrontAcc {
+    unsigned long long* sum;    // 2 per component: ia, ib
+    unsigned long long* rep;    // the least front_key
+    int32_t* size;
+    int32_t* bmax;              // 2 per component
+    int32_t* bmin;
+    int32_t* cen;               // the centroid in window cells
+};
+inline FrontAcc front_acc(uint8_t* p, size_t n) {
+    return FrontAcc{(unsigned long long*)p, (unsigned long long*)(p + 16 * n), (int32_t*)(p + 24 * n), (int32_t*)(p + 28 * n),
+                    (int32_t*)(p + 36 * n), (int32_t*)(p + 44 * n)};
+}
+// Each returns the kernels it launched.  mask: the frontier bit, LABEL = own index or -1, the count of frontier cells.
+int32_t launch_front_mask(hipStream_t s, const FrontJob& j);
+// LABEL holding own index or -1 -> the lowest index of the component: tile, merge, flatten
+int32_t launch_front_label(hipStream_t s, const FrontJob& j);
+// the roots counted per block and scanned: ctl[FC_COMPONENTS]
+int32_t launch_front_count(hipStream_t s, const FrontJob& j);
+// with n_comp, roots, acc (sum, size and box max zero, rep all ones, box min 0x7F bytes) and recs: everything else
+int32_t launch_front_table(hipStream_t s, const FrontJob& j);
+// the frontier cells drawn over an image of svh_grid_render_cost's layout
+void launch_front_overlay(hipStream_t s, int32_t nx, int32_t nz, const uint8_t* flags, uint8_t* rgb);
 
 }  // namespace grid
 }  // namespace svh

@@ -166,6 +166,23 @@ extern "C" int32_t svh_test_grid_plan_rounds_per_wait(int32_t n);
 extern "C" int32_t svh_test_grid_plan_device(int32_t nx, int32_t nz, const svh_grid_plan_params* p, const uint8_t* cost,
                                              const int32_t* goals, int32_t n, int32_t* pot, uint8_t* dir, int64_t out[3]);
 
+//   svh_test_grid_front               csrc/grid_front_core.h on the host: FRONT and LABEL of a window of nx x nz cells under the
+//                              offsets (oa, ob) from its STATE and COST planes, the first min(*n, cap) records of the kept
+//                              components (*n of them) and stats[5]; flags, label, recs and stats may be NULL
+//   svh_test_grid_front_device        NEEDS A DEVICE: the same through the kernels of csrc/grid_front_kernels.hip
+//   svh_test_grid_front_label_device  NEEDS A DEVICE: the labelling stage alone (tile, merge, flatten) on an arbitrary mask
+//                              (uint8, nonzero: a cell to label): LABEL; *launches = the kernels launched
+//   svh_test_grid_front_tile   the tile side the labelling kernel was built with
+struct svh_grid_front_params;
+extern "C" int32_t svh_test_grid_front(const svh_grid_front_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* state,
+                                       const uint8_t* cost, uint8_t* flags, int32_t* label, int32_t* recs, int64_t cap, int64_t* n,
+                                       int64_t* stats);
+extern "C" int32_t svh_test_grid_front_device(const svh_grid_front_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob,
+                                              const uint8_t* state, const uint8_t* cost, uint8_t* flags, int32_t* label, int32_t* recs,
+                                              int64_t cap, int64_t* n, int64_t* stats);
+extern "C" int32_t svh_test_grid_front_label_device(int32_t nx, int32_t nz, const uint8_t* mask, int32_t* label, int64_t* launches);
+extern "C" int32_t svh_test_grid_front_tile(void);
+
 // The guard of every HIP call of the host engines: `kind` is one of none, malloc, copy, launch, wait (see above); a
 // disarmed hook costs one relaxed load.  Returns hip_failed(...) out of the enclosing function on failure.
 #define SVH_HIP_TRY(entry, kind, expr)                                                                  \

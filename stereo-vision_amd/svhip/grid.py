@@ -1,6 +1,6 @@
 """ctypes binding of the ground grid in libsvhip.so (C-ABI: include/svh_grid.h): a 2.5-D bird's-eye grid over the road
 plane -- per cell how many points, how high, how bright, drivable or not -- binned on the device from the map view's store
-or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h."""
+or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h, grid_plan_core.h and grid_front_core.h."""
 import ctypes as C
 
 import numpy as np
@@ -27,6 +27,12 @@ PLAN_FAR = 0x7FFFFFFF
 DIR_GOAL, DIR_NONE = 8, 9
 PATH_FOUND, PATH_UNREACHABLE, PATH_BLOCKED, PATH_OUTSIDE = range(4)
 GOAL_COLOUR, PATH_COLOUR = (255, 255, 0), (255, 255, 255)
+FRONT_FLAGS, FRONT_LABEL = range(2)
+FRONT_DTYPE = [np.uint8, np.int32]
+FRONTIER, FRONT_KEPT, FRONT_REP = 1, 2, 4
+FRONT_RECORD = 10
+FRONT_FIELDS = ("label", "size", "ga_min", "gb_min", "ga_max", "gb_max", "cen_ga", "cen_gb", "rep_ga", "rep_gb")
+FRONT_KEPT_COLOUR, FRONT_DROPPED_COLOUR, FRONT_REP_COLOUR = (0, 255, 255), (0, 96, 128), (255, 255, 0)
 
 
 class Params(C.Structure):
@@ -65,6 +71,20 @@ class PlanParams(C.Structure):
 
     def copy(self, **kw):
         q = PlanParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class FrontParams(C.Structure):
+    """svh_grid_front_params"""
+    _fields_ = [("max_cell_cost", C.c_int32), ("min_size", C.c_int32), ("unexplored", C.c_uint32), ("border", C.c_int32)]
+
+    def copy(self, **kw):
+        q = FrontParams.from_buffer_copy(bytes(self))
         for k, v in kw.items():
             setattr(q, k, v)
         return q
@@ -140,6 +160,20 @@ def _bind():
         L.svh_test_grid_plan_tile.argtypes = []
         L.svh_test_grid_plan_device.argtypes = [C.c_int32, C.c_int32, C.POINTER(PlanParams), C.c_void_p, C.c_void_p, C.c_int32,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svh_grid_front_params_default.argtypes = [C.POINTER(FrontParams)]
+        L.svh_grid_front_params_default.restype = None
+        L.svh_grid_set_frontier.argtypes = [C.c_void_p, C.POINTER(FrontParams)]
+        L.svh_grid_get_frontier.argtypes = [C.c_void_p, C.POINTER(FrontParams)]
+        L.svh_grid_get_front_plane.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_get_frontiers.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_grid_get_frontier_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_plan_set_goals_frontiers.argtypes = [C.c_void_p]
+        L.svh_grid_render_frontiers.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        front = [C.POINTER(FrontParams)] + [C.c_int32] * 4 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_void_p]
+        L.svh_test_grid_front.argtypes = front
+        L.svh_test_grid_front_device.argtypes = front
+        L.svh_test_grid_front_label_device.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svh_test_grid_front_tile.argtypes = []
         L._grid_bound = True
     return L
 
@@ -298,9 +332,55 @@ def device_plan(nx, nz, plan, cost, goals):
     return pot, dir_, int(out[2])
 
 
+def default_front(**kw):
+    p = FrontParams()
+    _bind().svh_grid_front_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def _front(entry, front, state, cost, oa, ob):
+    s = np.ascontiguousarray(state, np.uint8)
+    nz, nx = s.shape
+    c = np.ascontiguousarray(cost, np.uint8).reshape(nz, nx)
+    flags, label = np.zeros((nz, nx), np.uint8), np.zeros((nz, nx), np.int32)
+    cap = ((nx + 1) // 2) * ((nz + 1) // 2)             # components do not touch: at most one per 2 x 2 cells
+    recs, n, stats = np.zeros((cap, FRONT_RECORD), np.int32), C.c_int64(-1), np.zeros(5, np.int64)
+    _check(entry(C.byref(front), nx, nz, oa, ob, s.ctypes.data, c.ctypes.data, flags.ctypes.data, label.ctypes.data, recs.ctypes.data, cap,
+                 C.addressof(n), stats.ctypes.data))
+    return flags, label, recs[:n.value].copy(), tuple(int(v) for v in stats)
+
+
+def core_front(front, state, cost, oa=0, ob=0):
+    """the frontiers of csrc/grid_front_core.h on the host (svh_test_grid_front) for STATE and COST planes [nz, nx] under the
+    offsets (oa, ob): (flags uint8 [nz, nx], label int32 [nz, nx], records int32 [kept, 10], stats (5)); needs no device"""
+    return _front(_bind().svh_test_grid_front, front, state, cost, oa, ob)
+
+
+def device_front(front, state, cost, oa=0, ob=0):
+    """TEST ENTRY: the same through the device kernels on a caller's planes"""
+    return _front(_bind().svh_test_grid_front_device, front, state, cost, oa, ob)
+
+
+def device_front_label(mask):
+    """TEST ENTRY: the labelling stage of the frontiers alone on a mask [nz, nx] (nonzero: a cell to label):
+    (label int32 [nz, nx], kernel launches)"""
+    m = np.ascontiguousarray(mask, np.uint8)
+    nz, nx = m.shape
+    label, launches = np.zeros((nz, nx), np.int32), C.c_int64(-1)
+    _check(_bind().svh_test_grid_front_label_device(nx, nz, m.ctypes.data, label.ctypes.data, C.addressof(launches)))
+    return label, launches.value
+
+
+def front_tile():
+    """the tile side the labelling kernel of the frontiers was built with"""
+    return int(_bind().svh_test_grid_front_tile())
+
+
 def __getattr__(name):
     if name == "PLAN_TILE":
         return plan_tile()
+    if name == "FRONT_TILE":
+        return front_tile()
     raise AttributeError(name)
 
 
@@ -485,6 +565,59 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_plan(self._h, ptr, len(c), img.ctypes.data, 0))
+        return img
+
+    def set_frontier(self, params=None, **kw):
+        """the frontier parameters in force (or `params`) with the fields of kw replaced: max_cell_cost, min_size, unexplored,
+        border"""
+        p = (params if params is not None else self.frontier_params()).copy(**kw)
+        _check(self._L.svh_grid_set_frontier(self._h, C.byref(p)))
+
+    def frontier_params(self):
+        p = FrontParams()
+        _check(self._L.svh_grid_get_frontier(self._h, C.byref(p)))
+        return p
+
+    def front_plane(self, which, device_ptr=None):
+        """FRONT_FLAGS uint8 or FRONT_LABEL int32, [nz, nx]; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_front_plane(self._h, which, device_ptr, 1))
+            return None
+        if not 0 <= which < len(FRONT_DTYPE):
+            raise SvhError(ERR_BAD_ARG, "no such plane")
+        out = np.zeros((self.nz, self.nx), FRONT_DTYPE[which])
+        _check(self._L.svh_grid_get_front_plane(self._h, which, out.ctypes.data, 0))
+        return out
+
+    def frontiers(self, cap=None):
+        """the records of the kept components, int32 [n, 10] in the order of FRONT_FIELDS, ascending by label; with cap only
+        the first, and the count of all is in `frontier_count`"""
+        n = C.c_int64(-1)
+        if cap is None:
+            _check(self._L.svh_grid_get_frontiers(self._h, None, 0, C.addressof(n)))
+            cap = n.value
+        recs = np.zeros((max(int(cap), 1), FRONT_RECORD), np.int32)
+        _check(self._L.svh_grid_get_frontiers(self._h, recs.ctypes.data if cap else None, int(cap), C.addressof(n)))
+        self.frontier_count = n.value
+        return recs[:min(n.value, int(cap))].copy()
+
+    def frontier_stats(self):
+        """(frontier cells, components, kept components, cells in kept components, kernel launches of the last computation)"""
+        out = np.zeros(5, np.int64)
+        _check(self._L.svh_grid_get_frontier_stats(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def set_goals_frontiers(self):
+        """the representatives of the kept components become the planner's goals; returns how many"""
+        return _check(self._L.svh_grid_plan_set_goals_frontiers(self._h))
+
+    def render_frontiers(self, device_ptr=None):
+        """render_cost with the frontier cells over it: kept, dropped, representatives"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_frontiers(self._h, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_frontiers(self._h, img.ctypes.data, 0))
         return img
 
     def stats(self):

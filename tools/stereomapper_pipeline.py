@@ -18,6 +18,7 @@ without the GUI.  Usage:
                                           [--grid-local DIR [--grid-cell S] [--grid-size NXxNZ]]
                                           [--grid-cost DIR [--grid-slope S] [--grid-inscribed M] [--grid-inflate M]]
                                          [--grid-plan DIR [--grid-goal-ahead M]]
+                                          [--grid-frontiers DIR [--grid-unexplored unseen|seen|both] [--grid-frontier-min N]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -83,6 +84,16 @@ ends sooner --, so a blocked cell ahead does not end the route; the start is the
 passable at a price of 100 above the neutral one.  The plan image (svh_grid_render_plan: the cost map, the goals that count
 yellow, the path white) goes into DIR/plan_%06d.ppm and one line {"frame", "status", "length", "cost"} per frame is appended
 to DIR/plan.jsonl (status 0 found, 1 unreachable, 2 the camera's cell is impassable, 3 outside).
+
+--grid-frontiers DIR: needs --grid-cost.  After every local step the frontiers of the local grid (svh_grid_get_frontiers: the
+free cells beside ground that was never looked at, grouped into 8-connected components, those of fewer than 8 cells dropped),
+the representatives of the kept components as the planner's goals (svh_grid_plan_set_goals_frontiers) and the path from the
+camera's position to the cheapest of them; unknown cells are passable at a price of 100 above the neutral one.  The image
+(svh_grid_render_frontiers: the cost map, kept frontier cells cyan, dropped ones dark cyan, representatives yellow; the path
+white over it) goes into DIR/frontiers_%06d.ppm and one line {"frame", "frontier_cells", "components", "kept", "status",
+"length", "cost"} per frame is appended to DIR/frontiers.jsonl.  --grid-unexplored: which unknown cells count as unexplored:
+those no ray passed (unseen, the default), those that rays passed and that hold no ground (seen), or both.
+--grid-frontier-min N: components of fewer than N cells are dropped (8).  May be given with --grid-plan; it runs after it.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -203,6 +214,20 @@ class Pipeline:
         g.set_goals([(oa + ia, row) for ia in range(g.nx)])
         status, cells, cost = g.path(centre)
         return status, cells, cost, g.render_plan(cells)
+
+    def frontier_step(self):
+        """the frontiers of the local grid, goals from them, the path from the camera's position:
+        (stats, status, cells [n, 2], cost, the frontier image with the path over it [nz, nx, 3])"""
+        g = self.local
+        centre = self.H_total[:3, 3].copy()
+        stats = g.frontier_stats()
+        g.set_goals_frontiers()
+        status, cells, cost = g.path(centre)
+        img = g.render_frontiers()
+        oa, ob = g.window()
+        for ga, gb in cells:                                     # global cells of the window: row 0 is the farthest
+            img[g.nz - 1 - (gb - ob), ga - oa] = (255, 255, 255)
+        return stats, status, cells, cost, img
 
     def local_step(self):
         """follow the camera centre to the middle cell, add the newest list with rays from it, render: [nz, nx, 3]"""
@@ -480,7 +505,7 @@ def main():
     thin, thin_every, ply = None, 1, None
     grid_dir, grid_cell, grid_size = None, 0.2, (256, 256)
     local_dir, cost_dir, cost_kw = None, None, {}
-    plan_dir, goal_ahead = None, None
+    plan_dir, goal_ahead, front_dir, front_kw = None, None, None, {}
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -521,7 +546,22 @@ def main():
             goal_ahead = float(sys.argv[k + 1])
             assert goal_ahead >= 0 and goal_ahead < float("inf")
             del sys.argv[k:k + 2]
+        if "--grid-frontiers" in sys.argv:
+            k = sys.argv.index("--grid-frontiers")
+            front_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-unexplored" in sys.argv:
+            k = sys.argv.index("--grid-unexplored")
+            front_kw["unexplored"] = {"unseen": 8, "seen": 16, "both": 24}[sys.argv[k + 1]]
+            del sys.argv[k:k + 2]
+        if "--grid-frontier-min" in sys.argv:
+            k = sys.argv.index("--grid-frontier-min")
+            front_kw["min_size"] = int(sys.argv[k + 1])
+            assert 1 <= front_kw["min_size"] <= 1 << 26
+            del sys.argv[k:k + 2]
         assert cost_dir or not plan_dir
+        assert cost_dir or not front_dir
+        assert front_dir or not front_kw
         assert plan_dir or goal_ahead is None
         assert local_dir or not (cost_dir or cost_kw)
         assert cost_dir or not cost_kw
@@ -541,7 +581,7 @@ def main():
             k = sys.argv.index("--ply")
             ply = sys.argv[k + 1]
             del sys.argv[k:k + 2]
-    except (IndexError, ValueError, AssertionError):
+    except (IndexError, ValueError, KeyError, AssertionError):
         raise SystemExit(__doc__)
     render_dir = None
     if "--render" in sys.argv:
@@ -585,6 +625,9 @@ def main():
     if plan_dir:
         os.makedirs(plan_dir, exist_ok=True)
         open(os.path.join(plan_dir, "plan.jsonl"), "w").close()
+    if front_dir:
+        os.makedirs(front_dir, exist_ok=True)
+        open(os.path.join(front_dir, "frontiers.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -595,9 +638,11 @@ def main():
         p.enable_grid_local(grid_cell, grid_size)
     if cost_dir:
         p.set_grid_cost(**cost_kw)
-    if plan_dir:
+    if plan_dir or front_dir:
         p.local.set_plan(unknown=100)
-    found = 0
+    if front_kw:
+        p.local.set_frontier(**front_kw)
+    found = explored = 0
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -622,6 +667,13 @@ def main():
             view.write_ppm(os.path.join(plan_dir, "plan_%06d.ppm" % (frames - 1)), img)
             with open(os.path.join(plan_dir, "plan.jsonl"), "a") as f:
                 f.write(json.dumps({"frame": frames - 1, "status": int(status), "length": int(len(cells)), "cost": int(cost)}) + "\n")
+        if front_dir:
+            stats, status, cells, cost, img = p.frontier_step()
+            explored += status == 0
+            view.write_ppm(os.path.join(front_dir, "frontiers_%06d.ppm" % (frames - 1)), img)
+            with open(os.path.join(front_dir, "frontiers.jsonl"), "a") as f:
+                f.write(json.dumps({"frame": frames - 1, "frontier_cells": stats[0], "components": stats[1], "kept": stats[2],
+                                    "status": int(status), "length": int(len(cells)), "cost": int(cost)}) + "\n")
         if frames >= limit:
             break
     dt = time.perf_counter() - t0
@@ -644,6 +696,9 @@ def main():
     if plan_dir:
         print("plan: goals %g m ahead, a route in %d of %d frames; %d images and plan.jsonl in %s" % (
             20.0 if goal_ahead is None else goal_ahead, found, frames, frames, plan_dir))
+    if front_dir:
+        print("frontiers: goals from the kept components, a route in %d of %d frames; %d images and frontiers.jsonl in %s" % (
+            explored, frames, frames, front_dir))
     if render_dir:
         n, images = p.view.record_human()
         for k in range(n):
