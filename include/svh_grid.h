@@ -82,6 +82,37 @@
  * traversability is not set, as svh_grid_get_trav does.  After SVH_ERR_HIP in a frontier entry the accumulated grid, the cost
  * planes, the goals and the field are untouched; the frontier result is invalid and the next call computes it again.
  *
+ * ROLLOUT: what a controller asks every frame -- of these short motions, which keep the whole vehicle off the obstacles, and which
+ * ends nearest the goal?  The arithmetic is stereo-vision_amd/csrc/grid_roll_core.h (restated in tests/grid_roll_ref.py): integers
+ * on the finished COST and POT planes in the window's order.  HEADINGS are integer direction vectors, no trigonometric function
+ * appears: with m = headings_m there are H = 8 m of them, heading k the vector (ux, uz) in (lateral a, forward b) on the perimeter of
+ * the square [-m, m]^2, counter-clockwise from (m, 0): (m, k) for k in 0..m, (2m - k, m) for m..3m, (-m, 4m - k) for 3m..5m,
+ * (k - 6m, -m) for 5m..7m, (m, k - 8m) for 7m..8m; straight ahead is k = 2m.  The heading of a direction (ua, ub), in fp32 with one
+ * rounding per operation: if |ua| >= |ub|, q = (int)rintf(ub * (float)m / |ua|) and k = (q + 8m) mod 8m for ua > 0, 4m - q for
+ * ua < 0; otherwise q = (int)rintf(ua * (float)m / |ub|) and k = 2m - q for ub > 0, 6m + q for ub < 0; a direction that is not finite,
+ * zero, or whose quotient is not within [-m, m] has none.  The FOOTPRINT TABLE, filled on the host in double once per
+ * svh_grid_set_roll, has one list of cell offsets (da, db) per heading, the vehicle's reference point at the centre of its cell:
+ * with c = (double)cell, h = 0.5 c, rt = sqrt((double)(ux ux + uz uz)), l = da ux + db uz and t = db ux - da uz the offset is in the
+ * list iff (double)l c <= ((double)front + h) rt, -(double)l c <= ((double)rear + h) rt and fabs((double)t) c <= ((double)half_width
+ * + h) rt, each product one double operation; (0, 0) is always in, a point vehicle covers one cell at every heading.  Offsets are
+ * searched in [-R, R]^2, R = (int)ceil((max(front, rear) + half_width + c) / c) in 1..128; a list is ascending by (db, da).  The
+ * FOOTPRINT COST F of a pose (ga, gb, k), a global cell and a heading, is -1 if a footprint cell lies outside the window, else the
+ * maximum over the footprint cells of r(COST), r(c) = c for 0..254 and r(255) = unknown_cost.  CANDIDATES are a table of S sets x K
+ * candidates x T poses of three int32 (dga, dgb, k): offsets from an anchor cell and an absolute heading; k = -1 ends a candidate,
+ * its length n_c is the number of poses before the first -1 (what follows is not looked at).  S, K, T >= 1, T <= 1024, K <= 65536,
+ * S K T <= 2^22, |dga|, |dgb| <= 16384.  SCORING a set at an anchor: F_t at every t < n_c; the candidate is cut at the first t with
+ * F_t = -1 (status 2, the window) or F_t >= stop_cost (status 1, cost; 255 never cuts), else it is complete (status 0); n_c = 0 has
+ * status 3.  L is the number of poses before the cut.  The record is five int32: L, status, maxF over the L poses (-1 for L = 0),
+ * sumF over them, and pot_end, POT at the reference cell of pose L - 1 -- SVH_GRID_PLAN_FAR if L = 0 or w_pot = 0, when the field is
+ * neither computed nor read.  A candidate is feasible iff L >= 1 and (w_pot = 0 or pot_end != FAR); its score, int64, is w_pot pot_end
+ * + w_cost sumF + w_cut (n_c - L), INT64_MAX when infeasible; the best is the feasible candidate with the least (score, index), -1 if
+ * none.  F is a maximum, sumF an integer sum, the cut a first index, the best the minimum of unique keys: no byte depends on launch
+ * shape or scheduling.  Both tables are relative: they survive svh_grid_scroll, svh_grid_follow, svh_grid_add_*, svh_grid_clear
+ * and svh_grid_set_window; svh_grid_set_roll with another headings_m forgets the candidates, whose headings it renumbers.  A scoring
+ * is computed per call and not cached; it uses the cached cost planes and, for w_pot > 0, the cached field.  The scoring entries
+ * return SVH_ERR_BAD_ARG while the traversability is not set or the vehicle does not fit (below).  After SVH_ERR_HIP in a rollout
+ * entry the accumulated grid, the cost planes, the goals, the field, the frontier result and both tables are untouched.
+ *
  * Plain C like svh_view.h.  An object has its own stream and every call returns when it is complete.  Calls return
  * SVH_OK or a negative SVH_ERR_*; svh_last_error() has the text.  SVH_ERR_BAD_ARG -- a null pointer, parameters out of
  * the ranges below, n < 0, n > 0 with a null array, a device array that is not 16-byte aligned, an unknown plane or
@@ -288,6 +319,51 @@ int32_t   svh_grid_plan_set_goals_frontiers(svh_grid* g);
 /* svh_grid_render_cost with the frontier cells over it: of a kept component (0, 255, 255), of a dropped one (0, 96, 128),
  * representatives (255, 255, 0) */
 int32_t   svh_grid_render_frontiers(svh_grid* g, uint8_t* rgb, int32_t on_device);
+
+
+typedef struct svh_grid_roll_params {
+    float   front, rear, half_width;   /* 3.5, 1.0, 0.9: metres from the reference point to the front, the rear and either side; finite, >= 0 */
+    int32_t headings_m;                /* 8: 64 headings; 1..32 */
+    int32_t stop_cost;                 /* 253: a pose whose F is at least this cuts its candidate; 1..255, 255 never cuts */
+    int32_t unknown_cost;              /* 254: what a cell of COST 255 counts as under a footprint; 0..254 */
+    int32_t w_pot, w_cost, w_cut;      /* 1, 1, 0: the weights of the score; 0..65535 */
+} svh_grid_roll_params;
+
+#define SVH_GRID_ROLL_RECORD 5         /* int32 per record: L, status, maxF, sumF, pot_end */
+#define SVH_GRID_ROLL_COMPLETE    0
+#define SVH_GRID_ROLL_CUT_COST    1
+#define SVH_GRID_ROLL_CUT_WINDOW  2
+#define SVH_GRID_ROLL_EMPTY       3    /* a candidate of no poses */
+
+void      svh_grid_roll_params_default(svh_grid_roll_params* p);
+/* checks the parameters, fills the footprint table for the grid's cell and uploads it.  SVH_ERR_BAD_ARG, nothing changed: a
+ * parameter out of its range, or R outside 1..128.  A grid is created with the defaults; if their R does not fit the grid's cell the
+ * object exists, and svh_grid_roll_footprint, svh_grid_footprint_cost and svh_grid_roll_score return SVH_ERR_BAD_ARG until this call
+ * succeeds.  After SVH_ERR_HIP the parameters are set and the next call that needs the table uploads it again. */
+int32_t   svh_grid_set_roll(svh_grid* g, const svh_grid_roll_params* p);
+/* the parameters in force, their R (0 while the defaults do not fit) and the cells of all lists; any output may be NULL, not all */
+int32_t   svh_grid_get_roll(svh_grid* g, svh_grid_roll_params* p, int32_t* reach_R, int64_t* footprint_cells_total);
+/* the heading of a map-frame direction: rows a and b of T without the translation, the direction rounded to float once.
+ * SVH_ERR_BAD_ARG: it has none */
+int32_t   svh_grid_heading_of(svh_grid* g, const double dir_xyz[3], int32_t* k);
+/* the list of heading k: *n its cells, the first min(*n, cap) pairs (da, db) to offsets (host memory); offsets may be NULL with cap 0 */
+int32_t   svh_grid_roll_footprint(svh_grid* g, int32_t k, int32_t* offsets, int64_t cap, int64_t* n);
+/* F of n poses (ga, gb, k), n <= 2^26: poses and out both on the host or (on_device) both in device memory, 4-byte aligned there.  A
+ * heading outside 0..8 m - 1 is SVH_ERR_BAD_ARG on the host path and gives F = -1 on the device path */
+int32_t   svh_grid_footprint_cost(svh_grid* g, const int32_t* poses, int64_t n, int32_t on_device, int32_t* out);
+/* the table of S x K x T poses (host memory), copied, and to the device once.  After SVH_ERR_HIP the table is set and the next
+ * svh_grid_roll_score uploads it again */
+int32_t   svh_grid_roll_set_candidates(svh_grid* g, const int32_t* table, int32_t S, int32_t K, int32_t T);
+/* S, K and T of the table in force, (0, 0, 0) while there is none: what sizes the outputs of svh_grid_roll_score */
+int32_t   svh_grid_roll_get_candidates(svh_grid* g, int32_t skt[3]);
+/* scores set `set` at the cell of the map-frame position anchor_xyz: recs (5 K int32) and scores (K int64) on the host or
+ * (on_device) in device memory, 4- and 8-byte aligned there; each may be NULL; *best (host memory) = index or -1.  An anchor outside
+ * the window is no error: every candidate is cut at pose 0.  SVH_ERR_BAD_ARG: no candidates, no such set, an anchor with no cell */
+int32_t   svh_grid_roll_score(svh_grid* g, const double anchor_xyz[3], int32_t set, int32_t* recs, int64_t* scores, int32_t on_device, int32_t* best);
+/* svh_grid_render_cost with the reference cells of the poses before the cut of every candidate of the last svh_grid_roll_score drawn
+ * (0, 192, 255) and those of its best (255, 255, 255) over them; they are global cells, those outside the window now are skipped.
+ * SVH_ERR_BAD_ARG: nothing was scored since the tables were set, or the last scoring failed */
+int32_t   svh_grid_render_roll(svh_grid* g, uint8_t* rgb, int32_t on_device);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,8 @@
 // lazy clear and the lazy finalise.  Device (grid_kernels.hip): the binning, the rays, the strips of a scroll, the
 // finalise, the render; (grid_trav_kernels.hip): the traversability layer -- flags, obstacle distance, cost, its render;
 // (grid_plan_kernels.hip): the planner -- the relaxation over active tiles, whose round loop is plan_rounds() here;
-// (grid_front_kernels.hip): the frontiers -- mask, union-find labelling, the table of components, run by front_run() here.
+// (grid_front_kernels.hip): the frontiers -- mask, union-find labelling, the table of components, run by front_run() here;
+// (grid_roll_kernels.hip): the rollouts -- footprint costs, the scoring of a set of candidates and its best.
 // The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
@@ -19,12 +20,15 @@
 // DIR; grid_plan_kernels.hip) is derived from COST and the goals, as lazily, and kept beside it (plan_valid) until the
 // accumulators, the offsets, the traversability, the plan parameters or the goals change.  The frontier result (FRONT, LABEL,
 // the table) is derived from STATE and COST, as lazily, and kept (front_valid) until the accumulators, the offsets, the
-// traversability or the frontier parameters change.
+// traversability or the frontier parameters change.  The rollouts cache nothing but their two tables (the footprints and the
+// candidates), which are relative and survive everything but their own setters: a scoring reads COST and, for w_pot > 0, POT.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -85,6 +89,29 @@ struct FrontBufs {
     PinnedBuf<unsigned long long> h_ctl;
 };
 
+// the rollout parameters with what is derived from them for a cell side: the reach and the footprint table (grid_roll_core.h)
+struct RollTable {
+    grid::RollParams p{3.5f, 1.0f, 0.9f, 8, 253, 254, 1, 1, 0};
+    int32_t R = 0;
+    std::vector<int32_t> offs;      // pairs (da, db)
+    std::vector<int64_t> start;     // 8 m + 1
+    std::vector<int32_t> start32;   // the same for the device: at most 256 lists of at most 257^2 cells
+    int64_t longest = 0;
+    bool derive(float cell) {
+        R = grid::roll_table(p, cell, &offs, &start);
+        longest = 0;
+        for (size_t k = 0; R && k + 1 < start.size(); k++) longest = std::max(longest, start[k + 1] - start[k]);
+        start32.assign(start.begin(), start.end());
+        return R != 0;
+    }
+};
+
+// what the rollout kernels need on the device beside the planes: the footprint table, and the records, scores and best of a scoring
+struct RollBufs {
+    HipBuf<int32_t> offs, start, recs, best;
+    HipBuf<long long> scores;
+};
+
 }  // namespace
 
 struct svh_grid {
@@ -131,6 +158,17 @@ struct svh_grid {
     FrontBufs front_bufs;
     bool front_valid = false;   // ... derived from STATE and COST as they are, with the offsets and parameters as they are; implies trav_valid
     int64_t front_stats[grid::FS_WORDS] = {0, 0, 0, 0, 0};   // of the result that is valid
+    RollTable rol;              // the rollouts: parameters and the footprint table; R 0: the defaults do not fit this grid's cell
+    RollBufs roll_bufs;
+    bool roll_sent = false;     // roll_bufs.offs and .start hold the table
+    std::vector<int32_t> cands, cand_lens;   // the candidate table (S * K * T * 3) and the lengths of its S * K candidates
+    int32_t cand_S = 0, cand_K = 0, cand_T = 0;
+    bool cands_sent = false;    // d_cands and d_cand_lens hold them
+    HipBuf<int32_t> d_cands, d_cand_lens;
+    HipBuf<int32_t> d_poses, d_fcost;   // free poses of a host caller and their F
+    PinnedBuf<uint8_t> h_roll;  // records, scores and the best on their way to the host
+    bool roll_last = false;     // roll_bufs.recs holds the records of the last svh_grid_roll_score, for svh_grid_render_roll:
+    int32_t roll_last_set = 0, roll_last_ga = 0, roll_last_gb = 0, roll_last_best = -1;   // its set, anchor and best
     svh_grid_stats st{0, 0, 0, 0, 0};
     int64_t rays = 0, ray_cells = 0;
 
@@ -658,6 +696,249 @@ bool convert_front(const svh_grid_front_params* p, grid::FrontParams* q) {
     return grid::front_ok(*q);
 }
 
+// ---- the rollouts ---------------------------------------------------------------------------------------------------------
+bool convert_roll(const svh_grid_roll_params* p, grid::RollParams* q) {
+    if (!p) return false;
+    *q = grid::RollParams{p->front, p->rear, p->half_width, p->headings_m, p->stop_cost, p->unknown_cost, p->w_pot, p->w_cost, p->w_cut};
+    return grid::roll_ok(*q);
+}
+
+// the footprint table lies on the device; complete when it returns SVH_OK.  Both sources belong to `t`: they outlive a copy that
+// a failed call leaves in flight until its caller has drained the stream
+int send_roll_table(hipStream_t s, const RollTable& t, RollBufs& b) {
+    GRID_GROW_N(b.offs, t.offs.size());
+    GRID_GROW_N(b.start, t.start32.size());
+    GRID_TRY(copy, hipMemcpyAsync(b.offs, t.offs.data(), t.offs.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    GRID_TRY(copy, hipMemcpyAsync(b.start, t.start32.data(), t.start32.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    return SVH_OK;
+}
+
+// a job on planes and a table that lie on the device; the candidates and the outputs are the caller's to fill in
+grid::RollJob roll_job(const RollTable& t, const RollBufs& b, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost,
+                       const int32_t* pot) {
+    grid::RollJob j;
+    j.rp = t.p;
+    j.nx = nx, j.nz = nz, j.oa = oa, j.ob = ob;
+    j.cost = cost, j.pot = pot;
+    j.offs = (const int2*)b.offs.p, j.start = b.start.p;
+    j.group = grid::roll_group(t.longest);
+    return j;
+}
+
+// set `set` of a table of K x T on the device, anchored at the global cell (ga, gb), with the outputs of `b`, which exist
+void roll_candidates(grid::RollJob& j, const RollBufs& b, const int32_t* d_cands, const int32_t* d_lens, int32_t set, int32_t K, int32_t T,
+                     int32_t ga, int32_t gb) {
+    j.cands = d_cands + (size_t)set * (size_t)K * (size_t)T * 3, j.lens = d_lens + (size_t)set * (size_t)K;
+    j.K = K, j.T = T, j.ga0 = ga, j.gb0 = gb;
+    j.recs = b.recs.p, j.scores = b.scores.p, j.best = b.best.p;
+}
+
+int roll_outputs(RollBufs& b, int32_t K) {
+    GRID_GROW_N(b.recs, (size_t)grid::ROLL_REC * (size_t)K);
+    GRID_GROW_N(b.scores, K);
+    GRID_GROW_N(b.best, 1);
+    return SVH_OK;
+}
+
+// both tables lie on the device
+int roll_tables(svh_grid* g, bool candidates) {
+    GRID_TRY(none, hipSetDevice(g->device));
+    if (!g->roll_sent) {
+        const int rc = send_roll_table(g->stream, g->rol, g->roll_bufs);
+        if (rc) return rc;
+        g->roll_sent = true;
+    }
+    if (candidates && !g->cands_sent) {
+        GRID_GROW_N(g->d_cands, g->cands.size());
+        GRID_GROW_N(g->d_cand_lens, g->cand_lens.size());
+        GRID_TRY(copy, hipMemcpyAsync(g->d_cands, g->cands.data(), g->cands.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+        GRID_TRY(copy, hipMemcpyAsync(g->d_cand_lens, g->cand_lens.data(), g->cand_lens.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+        g->cands_sent = true;
+    }
+    return SVH_OK;
+}
+
+grid::RollJob roll_job(const svh_grid* g) {
+    return roll_job(g->rol, g->roll_bufs, g->prm.nx, g->prm.nz, g->prm.oa, g->prm.ob, g->t_cost(), g->rol.p.w_pot != 0 ? g->p_pot() : nullptr);
+}
+
+// F of n > 0 poses with arguments that have been checked
+int footprint_cost(svh_grid* g, const int32_t* poses, int64_t n, bool on_device, int32_t* out) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = roll_tables(g, false))) return rc;
+    if (!on_device) {
+        GRID_GROW_N(g->d_poses, 3 * n);
+        GRID_GROW_N(g->d_fcost, n);
+        GRID_GROW(g->h_out, (size_t)n * sizeof(int32_t));
+        GRID_TRY(copy, hipMemcpyAsync(g->d_poses, poses, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    }
+    if ((rc = traverse(g))) return rc;
+    grid::launch_footprint_cost(g->stream, roll_job(g), on_device ? poses : g->d_poses.p, n, on_device ? out : g->d_fcost.p);
+    GRID_TRY(launch, hipGetLastError());
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    } else if ((rc = deliver(g, g->d_fcost, (size_t)n * sizeof(int32_t), out, false))) {
+        return rc;
+    }
+    g->final_valid = g->trav_valid = true;
+    return SVH_OK;
+}
+
+// set `set` scored at the global cell (ga, gb); recs and scores may be null
+int roll_score(svh_grid* g, int32_t ga, int32_t gb, int32_t set, int32_t* recs, int64_t* scores, bool on_device, int32_t* best) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const int32_t K = g->cand_K;
+    const size_t rec_bytes = (size_t)K * grid::ROLL_REC * sizeof(int32_t), score_bytes = (size_t)K * sizeof(int64_t);
+    g->roll_last = false;
+    if ((rc = roll_outputs(g->roll_bufs, K))) return rc;
+    GRID_GROW(g->h_roll, score_bytes + rec_bytes + sizeof(int32_t));   // the scores first: they are the widest
+    if ((rc = roll_tables(g, true))) return rc;
+    if ((rc = g->rol.p.w_pot != 0 ? plan_field(g) : traverse(g))) return rc;
+    grid::RollJob j = roll_job(g);
+    roll_candidates(j, g->roll_bufs, g->d_cands, g->d_cand_lens, set, K, g->cand_T, ga, gb);
+    hipStream_t s = g->stream;
+    GRID_TRY(launch, (grid::launch_roll_score(s, j), hipGetLastError()));
+    uint8_t* h = g->h_roll;
+    if (scores) GRID_TRY(copy, hipMemcpyAsync(on_device ? (void*)scores : (void*)h, j.scores, score_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (recs) GRID_TRY(copy, hipMemcpyAsync(on_device ? (void*)recs : (void*)(h + score_bytes), j.recs, rec_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    GRID_TRY(copy, hipMemcpyAsync(h + score_bytes + rec_bytes, j.best, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    g->final_valid = g->trav_valid = true;
+    if (scores && !on_device) memcpy(scores, h, score_bytes);
+    if (recs && !on_device) memcpy(recs, h + score_bytes, rec_bytes);
+    memcpy(best, h + score_bytes + rec_bytes, sizeof(int32_t));
+    g->roll_last = true;
+    g->roll_last_set = set, g->roll_last_ga = ga, g->roll_last_gb = gb, g->roll_last_best = *best;
+    return SVH_OK;
+}
+
+int render_roll(svh_grid* g, uint8_t* rgb, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const size_t bytes = g->ncells * 3;
+    if (!on_device) {
+        GRID_GROW(g->d_rgb, bytes);
+        GRID_GROW(g->h_out, bytes);
+    }
+    if ((rc = traverse(g))) return rc;
+    grid::RenderCostJob c;
+    c.nx = g->prm.nx, c.nz = g->prm.nz;
+    c.cost = g->t_cost(), c.flags = g->t_flags();
+    c.rgb = on_device ? rgb : g->d_rgb.p;
+    grid::RollJob j = roll_job(g);
+    roll_candidates(j, g->roll_bufs, g->d_cands, g->d_cand_lens, g->roll_last_set, g->cand_K, g->cand_T, g->roll_last_ga, g->roll_last_gb);
+    grid::launch_render_cost(g->stream, c);
+    grid::launch_roll_overlay(g->stream, j, g->roll_last_best, c.rgb);
+    GRID_TRY(launch, hipGetLastError());
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+        return rc;
+    }
+    g->final_valid = g->trav_valid = true;
+    return SVH_OK;
+}
+
+// a rollout call that failed on the device: nothing in flight, and no records for svh_grid_render_roll to draw
+int rolled(svh_grid* g, int rc) {
+    if (rc == SVH_ERR_HIP) g->roll_last = false;
+    return drained(g, rc);
+}
+
+const char* const kNoRoll =": the default vehicle does not fit this grid's cell; set one (svh_grid_set_roll)";
+
+// the planes and the tables of a test entry on the device, and the kernels on them; the outputs as those of svh_test_grid_roll
+int roll_device(const grid::RollParams& q, const RollTable& t, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost, const int32_t* pot, const int32_t* table,
+                int32_t S, int32_t K, int32_t T, int32_t set, int32_t ga0, int32_t gb0, const int32_t* poses, int64_t n_poses, int32_t* fout,
+                int32_t* recs, int64_t* scores, int32_t* best) {
+    const size_t cells = (size_t)nx * (size_t)nz;
+    HipBuf<uint8_t> d_cost;
+    HipBuf<int32_t> d_pot, d_cands, d_lens, d_poses, d_f;
+    RollBufs b;
+    std::vector<int32_t> lens((size_t)S * (size_t)K);
+    for (size_t c = 0; c < lens.size(); c++) lens[c] = grid::roll_len(table + c * (size_t)T * 3, T);
+    hipStream_t s = nullptr;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(d_cost, cells);
+        GRID_TRY(copy, hipMemcpyAsync(d_cost, cost, cells, hipMemcpyHostToDevice, s));
+        if (q.w_pot != 0) {
+            GRID_GROW_N(d_pot, cells);
+            GRID_TRY(copy, hipMemcpyAsync(d_pot, pot, cells * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+        int r = send_roll_table(s, t, b);
+        if (r) return r;
+        grid::RollJob j = roll_job(t, b, nx, nz, oa, ob, d_cost, q.w_pot != 0 ? d_pot.p : nullptr);
+        j.rp = q;   // the table is that of the vehicle; the costs and the weights are this call's
+        if (n_poses > 0) {
+            GRID_GROW_N(d_poses, 3 * n_poses);
+            GRID_GROW_N(d_f, n_poses);
+            GRID_TRY(copy, hipMemcpyAsync(d_poses, poses, (size_t)n_poses * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            GRID_TRY(launch, (grid::launch_footprint_cost(s, j, d_poses, n_poses, d_f), hipGetLastError()));
+            GRID_TRY(copy, hipMemcpyAsync(fout, d_f, (size_t)n_poses * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        if (S > 0) {
+            const size_t words = (size_t)S * (size_t)K * (size_t)T * 3;
+            GRID_GROW_N(d_cands, words);
+            GRID_GROW_N(d_lens, lens.size());
+            if ((r = roll_outputs(b, K))) return r;
+            GRID_TRY(copy, hipMemcpyAsync(d_cands, table, words * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            GRID_TRY(copy, hipMemcpyAsync(d_lens, lens.data(), lens.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            roll_candidates(j, b, d_cands, d_lens, set, K, T, ga0, gb0);
+            GRID_TRY(launch, (grid::launch_roll_score(s, j), hipGetLastError()));
+            if (recs) GRID_TRY(copy, hipMemcpyAsync(recs, j.recs, (size_t)K * grid::ROLL_REC * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            if (scores) GRID_TRY(copy, hipMemcpyAsync(scores, j.scores, (size_t)K * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            GRID_TRY(copy, hipMemcpyAsync(best, j.best, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    return rc;
+}
+
+// The footprint table of a test entry.  A caller fills its table once, not per call, so the table of the last vehicle and cell
+// side asked for is kept: a call with the same front, rear, half_width, headings_m and cell gets it back without building it.
+// The weights and the two costs of the parameters play no part in it; nullptr: the reach is outside 1..128
+std::shared_ptr<const RollTable> roll_table_for(const grid::RollParams& q, float cell) {
+    static std::mutex mu;
+    static std::shared_ptr<const RollTable> last;
+    static float last_cell = 0.f;
+    std::lock_guard<std::mutex> lock(mu);
+    if (last && last_cell == cell && last->p.front == q.front && last->p.rear == q.rear && last->p.half_width == q.half_width && last->p.m == q.m)
+        return last;
+    std::shared_ptr<RollTable> t = std::make_shared<RollTable>();
+    t->p = q;
+    if (!t->derive(cell)) return nullptr;
+    last = t, last_cell = cell;
+    return last;
+}
+
+// the checks that svh_test_grid_roll and svh_test_grid_roll_device share; the parameters to `q`, their table to `t`
+bool roll_test_args(const svh_grid_roll_params* p, float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost,
+                    const int32_t* pot, const int32_t* table, int32_t S, int32_t K, int32_t T, int32_t set, int32_t ga0, int32_t gb0,
+                    const int32_t* poses, int64_t n_poses, const int32_t* fout, const int32_t* best, grid::RollParams* q,
+                    std::shared_ptr<const RollTable>* t) {
+    if (!convert_roll(p, q) || !(grid::finite_f(cell) && cell > 0.f) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE ||
+        !grid::offsets_ok(oa, ob) || !cost || (q->w_pot != 0 && !pot) || n_poses < 0 || n_poses > ((int64_t)1 << 26) ||
+        (n_poses > 0 && (!poses || !fout)))
+        return false;
+    if (table || S != 0) {
+        if (!grid::roll_table_ok(table, S, K, T, 8 * q->m) || set < 0 || set >= S || !best || ga0 <= -grid::PLAN_GOAL_LIMIT ||
+            ga0 >= grid::PLAN_GOAL_LIMIT || gb0 <= -grid::PLAN_GOAL_LIMIT || gb0 >= grid::PLAN_GOAL_LIMIT)
+            return false;
+    }
+    *t = roll_table_for(*q, cell);
+    return *t != nullptr;
+}
+
 const char* const kNoTrav =": the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)";
 
 // ... and a failed add leaves the empty grid
@@ -771,6 +1052,7 @@ svh_grid* svh_grid_create(const svh_grid_params* p) {
     svh_grid_trav_params t;
     svh_grid_trav_params_default(&t);
     g->trav_ok = convert_trav(&t, q.cell, &g->trv, &g->table);   // false: no traversability until it is set
+    (void)g->rol.derive(q.cell);                                 // R 0: no rollouts until svh_grid_set_roll succeeds
     (void)hipGetDevice(&g->device);
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
         delete g;
@@ -1104,6 +1386,174 @@ int32_t svh_grid_render_frontiers(svh_grid* g, uint8_t* rgb, int32_t on_device) 
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_frontiers") + kNoTrav);
     return fronted(g, render_frontiers(g, rgb, on_device != 0));
 }
+
+void svh_grid_roll_params_default(svh_grid_roll_params* p) {
+    if (!p) return;
+    p->front = 3.5f, p->rear = 1.0f, p->half_width = 0.9f;
+    p->headings_m = 8, p->stop_cost = 253, p->unknown_cost = 254;
+    p->w_pot = 1, p->w_cost = 1, p->w_cut = 0;
+}
+
+int32_t svh_grid_set_roll(svh_grid* g, const svh_grid_roll_params* p) {
+    RollTable t;
+    if (!g || !convert_roll(p, &t.p) || !t.derive(g->prm.cell))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_roll: a grid and parameters in range, with a reach of 1..128 cells, are needed (include/svh_grid.h)");
+    if (t.p.m != g->rol.p.m) {   // the headings of the candidates were those of the old enumeration
+        g->cands.clear(), g->cand_lens.clear();
+        g->cand_S = g->cand_K = g->cand_T = 0;
+        g->cands_sent = false;
+    }
+    g->rol = std::move(t);
+    g->roll_sent = g->roll_last = false;
+    return drained(g, roll_tables(g, false));   // a failed upload is repeated by the next call that needs the table
+}
+
+int32_t svh_grid_get_roll(svh_grid* g, svh_grid_roll_params* p, int32_t* reach_R, int64_t* footprint_cells_total) {
+    if (!g || (!p && !reach_R && !footprint_cells_total)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_roll: a grid and an output are needed");
+    const grid::RollParams& q = g->rol.p;
+    if (p) {
+        p->front = q.front, p->rear = q.rear, p->half_width = q.half_width;
+        p->headings_m = q.m, p->stop_cost = q.stop_cost, p->unknown_cost = q.unknown_cost;
+        p->w_pot = q.w_pot, p->w_cost = q.w_cost, p->w_cut = q.w_cut;
+    }
+    if (reach_R) *reach_R = g->rol.R;
+    if (footprint_cells_total) *footprint_cells_total = g->rol.R ? (int64_t)(g->rol.offs.size() / 2) : 0;
+    return SVH_OK;
+}
+
+int32_t svh_grid_heading_of(svh_grid* g, const double dir_xyz[3], int32_t* k) {
+    float d[3];
+    if (!g || !k || !position(dir_xyz, d)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_heading_of: a grid, an output and a finite direction are needed");
+    const float* T = g->prm.T;
+    const float ua = (T[0] * d[0] + T[1] * d[1]) + T[2] * d[2], ub = (T[4] * d[0] + T[5] * d[1]) + T[6] * d[2];
+    const int32_t h = grid::heading_of(g->rol.p.m, ua, ub);
+    if (h < 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_heading_of: the direction has no heading: it is zero on the ground, or not finite there");
+    *k = h;
+    return SVH_OK;
+}
+
+int32_t svh_grid_roll_footprint(svh_grid* g, int32_t k, int32_t* offsets, int64_t cap, int64_t* n) {
+    if (!g || !n || cap < 0 || (cap > 0 && !offsets) || k < 0 || k >= 8 * g->rol.p.m)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_footprint: a grid, a heading 0..8 m - 1, a count and room for cap >= 0 offsets are needed");
+    if (!g->rol.R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_roll_footprint") + kNoRoll);
+    const int64_t at = g->rol.start[k], len = g->rol.start[k + 1] - at;
+    if (cap > 0) memcpy(offsets, g->rol.offs.data() + 2 * at, (size_t)std::min(len, cap) * 2 * sizeof(int32_t));
+    *n = len;
+    return SVH_OK;
+}
+
+int32_t svh_grid_footprint_cost(svh_grid* g, const int32_t* poses, int64_t n, int32_t on_device, int32_t* out) {
+    if (!g || n < 0 || n > ((int64_t)1 << 26) || (n > 0 && (!poses || !out)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_footprint_cost: a grid and 0..2^26 poses with room for their costs are needed");
+    if (on_device && (((uintptr_t)poses | (uintptr_t)out) & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_footprint_cost: a device array must be 4-byte aligned");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_footprint_cost") + kNoTrav);
+    if (!g->rol.R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_footprint_cost") + kNoRoll);
+    if (!on_device)
+        for (int64_t i = 0; i < n; i++)
+            if (poses[3 * i + 2] < 0 || poses[3 * i + 2] >= 8 * g->rol.p.m) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_footprint_cost: a heading is not in 0..8 m - 1");
+    if (n == 0) return SVH_OK;
+    return drained(g, footprint_cost(g, poses, n, on_device != 0, out));
+}
+
+int32_t svh_grid_roll_set_candidates(svh_grid* g, const int32_t* table, int32_t S, int32_t K, int32_t T) {
+    if (!g || !grid::roll_table_ok(table, S, K, T, 8 * g->rol.p.m))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_set_candidates: a grid and a table within the limits are needed: S, K, T >= 1, T <= 1024, K <= 65536, S K T <= 2^22, offsets within +-16384, headings -1..8 m - 1");
+    const size_t n = (size_t)S * (size_t)K;
+    g->cands.assign(table, table + n * (size_t)T * 3);
+    g->cand_lens.resize(n);
+    for (size_t c = 0; c < n; c++) g->cand_lens[c] = grid::roll_len(table + c * (size_t)T * 3, T);
+    g->cand_S = S, g->cand_K = K, g->cand_T = T;
+    g->cands_sent = g->roll_last = false;
+    if (!g->rol.R) return SVH_OK;                  // no table to send yet; svh_grid_roll_score sends both
+    return drained(g, roll_tables(g, true));       // a failed upload is repeated by the next svh_grid_roll_score
+}
+
+int32_t svh_grid_roll_get_candidates(svh_grid* g, int32_t skt[3]) {
+    if (!g || !skt) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_get_candidates: null argument");
+    skt[0] = g->cand_S, skt[1] = g->cand_K, skt[2] = g->cand_T;
+    return SVH_OK;
+}
+
+int32_t svh_grid_roll_score(svh_grid* g, const double anchor_xyz[3], int32_t set, int32_t* recs, int64_t* scores, int32_t on_device, int32_t* best) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || !best || !position(anchor_xyz, p) || !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score: a grid, an output and a finite anchor with a cell below 2^20 are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_roll_score") + kNoTrav);
+    if (!g->rol.R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_roll_score") + kNoRoll);
+    if (g->cand_S == 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score: no candidates (svh_grid_roll_set_candidates)");
+    if (set < 0 || set >= g->cand_S) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score: no such set");
+    if (on_device && (((uintptr_t)recs & 3) || ((uintptr_t)scores & 7)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score: a device array of records must be 4-byte, one of scores 8-byte aligned");
+    return rolled(g, roll_score(g, ga, gb, set, recs, scores, on_device != 0, best));
+}
+
+int32_t svh_grid_render_roll(svh_grid* g, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_roll: a grid and an output are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_roll") + kNoTrav);
+    if (!g->roll_last) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_roll: nothing was scored since the tables were set (svh_grid_roll_score)");
+    return drained(g, render_roll(g, rgb, on_device != 0));
+}
+
+// grid_roll_core.h on the host.  The footprint table for a cell side: *R, *total cells of all lists, and (k >= 0) the list of heading
+// k: *n its cells, the first min(*n, cap) pairs (da, db).  Needs no device
+int32_t svh_test_grid_roll_table(float cell, const svh_grid_roll_params* p, int32_t* R, int64_t* total, int32_t k, int32_t* offsets, int64_t cap,
+                                 int64_t* n) {
+    RollTable t;
+    if (!convert_roll(p, &t.p) || !(grid::finite_f(cell) && cell > 0.f) || !R || cap < 0 || (cap > 0 && !offsets) || k < -1 || k >= 8 * t.p.m ||
+        (k >= 0 && !n) || !t.derive(cell))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_roll_table: bad arguments");
+    *R = t.R;
+    if (total) *total = (int64_t)(t.offs.size() / 2);
+    if (k >= 0) {
+        const int64_t at = t.start[k], len = t.start[k + 1] - at;
+        if (cap > 0) memcpy(offsets, t.offs.data() + 2 * at, (size_t)std::min(len, cap) * 2 * sizeof(int32_t));
+        *n = len;
+    }
+    return SVH_OK;
+}
+
+// the heading of a direction (*k, -1: none) and, where vec is given and there is one, its vector.  Needs no device
+int32_t svh_test_grid_roll_heading(int32_t m, float ua, float ub, int32_t* k, int32_t* vec) {
+    if (m < 1 || m > grid::ROLL_MAX_M || !k) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_roll_heading: bad arguments");
+    *k = grid::heading_of(m, ua, ub);
+    if (vec && *k >= 0) grid::heading_vec(m, *k, &vec[0], &vec[1]);
+    return SVH_OK;
+}
+
+// The header's host loops on a caller's COST and POT planes (nx x nz, offsets oa, ob; POT is read only when w_pot != 0), with the
+// footprint table of roll_table_for -- built by the first call for a vehicle and cell side, kept for those that follow: F of n_poses
+// free poses (global cells) to fout, and -- with a table of S x K x T -- set `set` scored at the global cell (ga0, gb0): recs (5 K) and
+// scores (K) may be NULL, *best.  table NULL with S = 0: the poses alone.  Needs no device
+int32_t svh_test_grid_roll(const svh_grid_roll_params* p, float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost,
+                           const int32_t* pot, const int32_t* table, int32_t S, int32_t K, int32_t T, int32_t set, int32_t ga0, int32_t gb0,
+                           const int32_t* poses, int64_t n_poses, int32_t* fout, int32_t* recs, int64_t* scores, int32_t* best) {
+    grid::RollParams q;
+    std::shared_ptr<const RollTable> t;
+    if (!roll_test_args(p, cell, nx, nz, oa, ob, cost, pot, table, S, K, T, set, ga0, gb0, poses, n_poses, fout, best, &q, &t))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_roll: bad arguments");
+    if (n_poses > 0) grid::footprint_window(q, nx, nz, oa, ob, cost, t->offs.data(), t->start.data(), poses, n_poses, fout);
+    if (S > 0)
+        *best = grid::roll_window(q, nx, nz, oa, ob, cost, pot, t->offs.data(), t->start.data(), table + (size_t)set * (size_t)K * (size_t)T * 3, K, T,
+                                  ga0, gb0, recs, scores);
+    return SVH_OK;
+}
+
+// the same through the kernels
+int32_t svh_test_grid_roll_device(const svh_grid_roll_params* p, float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost,
+                                  const int32_t* pot, const int32_t* table, int32_t S, int32_t K, int32_t T, int32_t set, int32_t ga0,
+                                  int32_t gb0, const int32_t* poses, int64_t n_poses, int32_t* fout, int32_t* recs, int64_t* scores,
+                                  int32_t* best) {
+    grid::RollParams q;
+    std::shared_ptr<const RollTable> t;
+    if (!roll_test_args(p, cell, nx, nz, oa, ob, cost, pot, table, S, K, T, set, ga0, gb0, poses, n_poses, fout, best, &q, &t))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_roll_device: bad arguments");
+    svh::ensure_init();
+    return roll_device(q, *t, nx, nz, oa, ob, cost, pot, table, S, K, T, set, ga0, gb0, poses, n_poses, fout, recs, scores, best);
+}
+
+// the lanes that share a pose in the kernels, for a longest footprint list
+int32_t svh_test_grid_roll_group(int64_t longest) { return grid::roll_group(longest); }
 
 // grid_front_core.h on the host.  Needs no device
 int32_t svh_test_grid_front(const svh_grid_front_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* state,

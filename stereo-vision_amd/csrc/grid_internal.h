@@ -1,5 +1,5 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
-// csrc/grid_front_kernels.hip: the launches of the ground grid (include/svh_grid.h).
+// csrc/grid_front_kernels.hip / csrc/grid_roll_kernels.hip: the launches of the ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
 
@@ -9,6 +9,7 @@
 #include "grid_core.h"
 #include "grid_front_core.h"
 #include "grid_plan_core.h"
+#include "grid_roll_core.h"
 
 namespace svh {
 namespace grid {
@@ -220,6 +221,36 @@ int32_t launch_front_count(hipStream_t s, const FrontJob& j);
 int32_t launch_front_table(hipStream_t s, const FrontJob& j);
 // the frontier cells drawn over an image of svh_grid_render_cost's layout
 void launch_front_overlay(hipStream_t s, int32_t nx, int32_t nz, const uint8_t* flags, uint8_t* rgb);
+
+// The rollouts (csrc/grid_roll_kernels.hip): the finished COST and POT planes, the footprint table and the candidates of one set ->
+// F of poses, the records, the scores and the best.
+constexpr uint32_t ROLL_BLOCK = 256;             // k_grid_roll_score: one workgroup per candidate, in groups of `group` lanes per pose
+constexpr uint32_t ROLL_BEST_BLOCK = 1024;       // k_grid_roll_best: one workgroup
+
+struct RollJob {
+    RollParams rp;
+    int32_t nx, nz, oa, ob;
+    const uint8_t* cost;        // the finished COST plane
+    const int32_t* pot;         // the finished POT plane; not read when w_pot == 0
+    const int2* offs;           // the footprint table: the lists of (da, db), one after the other
+    const int32_t* start;       // 8 m + 1: where the list of a heading begins
+    int32_t group;              // roll_group(the longest list)
+    const int32_t* cands = nullptr;   // the candidates of ONE set, K * T * 3
+    const int32_t* lens = nullptr;    // their lengths, K
+    int32_t K = 0, T = 0, ga0 = 0, gb0 = 0;   // the anchor, a global cell
+    int32_t* recs = nullptr;    // ROLL_REC per candidate
+    long long* scores = nullptr;
+    int32_t* best = nullptr;
+};
+// the lanes that share a pose: the smallest power of two that holds the longest list, at most 64
+int32_t roll_group(int64_t longest);
+// records and scores of the K candidates, then the best: two launches whatever the scene
+void launch_roll_score(hipStream_t s, const RollJob& j);
+// F of n free poses (ga, gb, k), global cells
+void launch_footprint_cost(hipStream_t s, const RollJob& j, const int32_t* poses, int64_t n, int32_t* out);
+// the reference cells of the poses before the cut of every candidate, then of `best` (>= 0) over them, drawn into an image of
+// svh_grid_render_cost's layout from the records in j.recs
+void launch_roll_overlay(hipStream_t s, const RollJob& j, int32_t best, uint8_t* rgb);
 
 }  // namespace grid
 }  // namespace svh

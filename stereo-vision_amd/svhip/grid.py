@@ -1,6 +1,7 @@
 """ctypes binding of the ground grid in libsvhip.so (C-ABI: include/svh_grid.h): a 2.5-D bird's-eye grid over the road
 plane -- per cell how many points, how high, how bright, drivable or not -- binned on the device from the map view's store
-or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h, grid_plan_core.h and grid_front_core.h."""
+or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h, grid_plan_core.h, grid_front_core.h and
+grid_roll_core.h."""
 import ctypes as C
 
 import numpy as np
@@ -33,6 +34,11 @@ FRONTIER, FRONT_KEPT, FRONT_REP = 1, 2, 4
 FRONT_RECORD = 10
 FRONT_FIELDS = ("label", "size", "ga_min", "gb_min", "ga_max", "gb_max", "cen_ga", "cen_gb", "rep_ga", "rep_gb")
 FRONT_KEPT_COLOUR, FRONT_DROPPED_COLOUR, FRONT_REP_COLOUR = (0, 255, 255), (0, 96, 128), (255, 255, 0)
+ROLL_RECORD = 5
+ROLL_FIELDS = ("len", "status", "max_f", "sum_f", "pot_end")
+ROLL_COMPLETE, ROLL_CUT_COST, ROLL_CUT_WINDOW, ROLL_EMPTY = range(4)
+ROLL_INFEASIBLE = 2 ** 63 - 1
+ROLL_COLOUR, ROLL_BEST_COLOUR = (0, 192, 255), (255, 255, 255)
 
 
 class Params(C.Structure):
@@ -91,6 +97,21 @@ class FrontParams(C.Structure):
 
     def asdict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class RollParams(C.Structure):
+    """svh_grid_roll_params"""
+    _fields_ = [("front", C.c_float), ("rear", C.c_float), ("half_width", C.c_float), ("headings_m", C.c_int32), ("stop_cost", C.c_int32),
+                ("unknown_cost", C.c_int32), ("w_pot", C.c_int32), ("w_cost", C.c_int32), ("w_cut", C.c_int32)]
+
+    def copy(self, **kw):
+        q = RollParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -174,6 +195,23 @@ def _bind():
         L.svh_test_grid_front_device.argtypes = front
         L.svh_test_grid_front_label_device.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.svh_test_grid_front_tile.argtypes = []
+        L.svh_grid_roll_params_default.argtypes = [C.POINTER(RollParams)]
+        L.svh_grid_roll_params_default.restype = None
+        L.svh_grid_set_roll.argtypes = [C.c_void_p, C.POINTER(RollParams)]
+        L.svh_grid_get_roll.argtypes = [C.c_void_p, C.POINTER(RollParams), C.c_void_p, C.c_void_p]
+        L.svh_grid_heading_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svh_grid_roll_footprint.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_grid_footprint_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.svh_grid_roll_set_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.svh_grid_roll_get_candidates.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_roll_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.svh_grid_render_roll.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_test_grid_roll_table.argtypes = [C.c_float, C.POINTER(RollParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_test_grid_roll_heading.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+        roll = [C.POINTER(RollParams), C.c_float] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+        L.svh_test_grid_roll.argtypes = roll
+        L.svh_test_grid_roll_device.argtypes = roll
+        L.svh_test_grid_roll_group.argtypes = [C.c_int64]
         L._grid_bound = True
     return L
 
@@ -374,6 +412,120 @@ def device_front_label(mask):
 def front_tile():
     """the tile side the labelling kernel of the frontiers was built with"""
     return int(_bind().svh_test_grid_front_tile())
+
+
+def default_roll(**kw):
+    p = RollParams()
+    _bind().svh_grid_roll_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def core_roll_table(cell, roll):
+    """the footprint table of csrc/grid_roll_core.h for a cell side (svh_test_grid_roll_table): (R, [int32 [n_k, 2] offsets (da, db) for
+    each of the 8 m headings]); needs no device"""
+    L, R, total, n = _bind(), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    _check(L.svh_test_grid_roll_table(cell, C.byref(roll), C.addressof(R), C.addressof(total), -1, None, 0, None))
+    lists = []
+    for k in range(8 * roll.headings_m):
+        _check(L.svh_test_grid_roll_table(cell, C.byref(roll), C.addressof(R), None, k, None, 0, C.addressof(n)))
+        offs = np.zeros((max(n.value, 1), 2), np.int32)
+        _check(L.svh_test_grid_roll_table(cell, C.byref(roll), C.addressof(R), None, k, offs.ctypes.data, n.value, C.addressof(n)))
+        lists.append(offs[:n.value].copy())
+    assert sum(len(l) for l in lists) == total.value
+    return R.value, lists
+
+
+def core_heading(m, ua, ub):
+    """the heading of a direction by csrc/grid_roll_core.h (svh_test_grid_roll_heading): (k, (ux, uz)), or (-1, None); needs no device"""
+    k, vec = C.c_int32(-9), np.zeros(2, np.int32)
+    _check(_bind().svh_test_grid_roll_heading(m, ua, ub, C.addressof(k), vec.ctypes.data))
+    return k.value, ((int(vec[0]), int(vec[1])) if k.value >= 0 else None)
+
+
+def headings_of(m, ua, ub):
+    """the same rule in numpy float32, elementwise: int32, -1 where a direction has no heading"""
+    ua, ub = np.broadcast_arrays(np.asarray(ua, np.float32), np.asarray(ub, np.float32))
+    aa, ab, fm = np.abs(ua), np.abs(ub), np.float32(m)
+    wide = aa >= ab
+    with np.errstate(all="ignore"):
+        q = np.rint(np.where(wide, ub * fm, ua * fm) / np.where(wide, aa, ab))
+    ok = np.isfinite(ua) & np.isfinite(ub) & ((ua != 0) | (ub != 0)) & (np.abs(q) <= fm)
+    q = np.where(ok, q, 0).astype(np.int64)
+    k = np.where(wide, np.where(ua > 0, (q + 8 * m) % (8 * m), 4 * m - q), np.where(ub > 0, 2 * m - q, 6 * m + q))
+    return np.where(ok, k, -1).astype(np.int32)
+
+
+def heading_vectors(m):
+    """int64 [8 m, 2]: the vector (ux, uz) of every heading"""
+    k = np.arange(8 * m)
+    ux = np.select([k <= m, k <= 3 * m, k <= 5 * m, k <= 7 * m], [m, 2 * m - k, -m, k - 6 * m], m)
+    uz = np.select([k <= m, k <= 3 * m, k <= 5 * m, k <= 7 * m], [k, m, 4 * m - k, -m], k - 8 * m)
+    return np.stack([ux, uz], axis=1).astype(np.int64)
+
+
+def arc_candidates(cell, m, curvatures, step_len, T):
+    """int32 [8 m, K, T, 3]: set s holds, for each of the K curvatures (1/m, positive turns towards rising headings), the arc that
+    starts at the anchor along heading s, sampled every step_len metres: pose t lies (t + 1) step_len along it.  numpy double; a cell
+    offset is floor(x / cell + 0.5), the heading that of the tangent.  A candidate ends (k = -1 from there on) where an offset would
+    leave +-16384.  Plumbing, not part of the contract"""
+    kap = np.asarray(curvatures, np.float64).reshape(1, -1, 1)
+    u = heading_vectors(m).astype(np.float64)
+    u /= np.sqrt((u * u).sum(axis=1, keepdims=True))
+    ua, ub = u[:, 0].reshape(-1, 1, 1), u[:, 1].reshape(-1, 1, 1)
+    s = (np.arange(T, dtype=np.float64) + 1.0).reshape(1, 1, -1) * float(step_len)
+    phi = kap * s
+    safe = np.where(kap == 0, 1.0, kap)
+    along = np.where(kap == 0, s, np.sin(phi) / safe)                 # along the start heading
+    left = np.where(kap == 0, 0.0, (1.0 - np.cos(phi)) / safe)        # along its left normal (-ub, ua)
+    xa, xb = along * ua - left * ub, along * ub + left * ua
+    ta, tb = np.cos(phi) * ua - np.sin(phi) * ub, np.cos(phi) * ub + np.sin(phi) * ua
+    da, db = np.floor(xa / float(cell) + 0.5), np.floor(xb / float(cell) + 0.5)
+    k = headings_of(m, ta.astype(np.float32), tb.astype(np.float32))
+    live = np.logical_and.accumulate((np.abs(da) <= 16384) & (np.abs(db) <= 16384) & (k >= 0), axis=2)
+    out = np.zeros(da.shape + (3,), np.int32)
+    out[..., 0], out[..., 1], out[..., 2] = np.where(live, da, 0), np.where(live, db, 0), np.where(live, k, -1)
+    return out
+
+
+def _roll(entry, roll, cell, cost, pot, table, set_, anchor, oa, ob, poses):
+    c = np.ascontiguousarray(cost, np.uint8)
+    nz, nx = c.shape
+    p = None if pot is None else np.ascontiguousarray(pot, np.int32).reshape(nz, nx)
+    out = {}
+    S = K = T = 0
+    tp = rp = sp = None
+    best = C.c_int32(-9)
+    if table is not None:
+        t = np.ascontiguousarray(table, np.int32)
+        S, K, T = t.shape[:3]
+        recs, scores = np.zeros((K, ROLL_RECORD), np.int32), np.zeros(K, np.int64)
+        tp, rp, sp = t.ctypes.data, recs.ctypes.data, scores.ctypes.data
+    q = np.ascontiguousarray(poses if poses is not None else np.zeros((0, 3)), np.int32).reshape(-1, 3)
+    f = np.zeros(len(q), np.int32)
+    _check(entry(C.byref(roll), cell, nx, nz, oa, ob, c.ctypes.data, None if p is None else p.ctypes.data, tp, S, K, T, set_, anchor[0], anchor[1],
+                 q.ctypes.data if len(q) else None, len(q), f.ctypes.data if len(q) else None, rp, sp, C.addressof(best)))
+    if table is not None:
+        out.update(recs=recs, scores=scores, best=best.value)
+    if poses is not None:
+        out.update(f=f)
+    return out
+
+
+def core_roll(roll, cell, cost, pot=None, table=None, set_=0, anchor=(0, 0), oa=0, ob=0, poses=None):
+    """the rollouts of csrc/grid_roll_core.h on the host (svh_test_grid_roll) on COST uint8 [nz, nx] and POT int32 [nz, nx] (needed when
+    w_pot != 0) under the offsets (oa, ob): with a table int32 [S, K, T, 3], set `set_` scored at the global cell `anchor` -- recs int32
+    [K, 5], scores int64 [K], best; with poses int32 [n, 3] (global cells, heading) their F as f int32 [n].  A dict; needs no device"""
+    return _roll(_bind().svh_test_grid_roll, roll, cell, cost, pot, table, set_, anchor, oa, ob, poses)
+
+
+def device_roll(roll, cell, cost, pot=None, table=None, set_=0, anchor=(0, 0), oa=0, ob=0, poses=None):
+    """TEST ENTRY: the same through the device kernels on a caller's planes"""
+    return _roll(_bind().svh_test_grid_roll_device, roll, cell, cost, pot, table, set_, anchor, oa, ob, poses)
+
+
+def roll_group(longest):
+    """the lanes that share a pose in the rollout kernels when the longest footprint list has `longest` cells"""
+    return int(_bind().svh_test_grid_roll_group(longest))
 
 
 def __getattr__(name):
@@ -618,6 +770,78 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_frontiers(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_roll(self, params=None, **kw):
+        """the rollout parameters in force (or `params`) with the fields of kw replaced: front, rear, half_width, headings_m, stop_cost,
+        unknown_cost, w_pot, w_cost, w_cut"""
+        p = (params if params is not None else self.roll_params()[0]).copy(**kw)
+        _check(self._L.svh_grid_set_roll(self._h, C.byref(p)))
+
+    def roll_params(self):
+        """(RollParams in force, their reach R in cells -- 0 while the defaults do not fit the grid's cell --, the cells of all lists)"""
+        p, R, total = RollParams(), C.c_int32(-1), C.c_int64(-1)
+        _check(self._L.svh_grid_get_roll(self._h, C.byref(p), C.addressof(R), C.addressof(total)))
+        return p, R.value, total.value
+
+    def heading_of(self, dir_xyz):
+        """the heading of a map-frame direction"""
+        k = C.c_int32(-1)
+        _check(self._L.svh_grid_heading_of(self._h, _xyz(dir_xyz).ctypes.data, C.addressof(k)))
+        return k.value
+
+    def roll_footprint(self, k):
+        """int32 [n, 2]: the cell offsets (da, db) under the vehicle at heading k, ascending by (db, da)"""
+        n = C.c_int64(-1)
+        _check(self._L.svh_grid_roll_footprint(self._h, k, None, 0, C.addressof(n)))
+        offs = np.zeros((max(n.value, 1), 2), np.int32)
+        _check(self._L.svh_grid_roll_footprint(self._h, k, offs.ctypes.data, n.value, C.addressof(n)))
+        return offs[:n.value].copy()
+
+    def footprint_cost(self, poses=None, device_ptrs=None, n=None):
+        """F int32 [n] of poses int32 [n, 3] (ga, gb, k); with device_ptrs = (poses, out) and n both lie on the device and None is
+        returned"""
+        if device_ptrs is not None:
+            _check(self._L.svh_grid_footprint_cost(self._h, device_ptrs[0], n, 1, device_ptrs[1]))
+            return None
+        q = np.ascontiguousarray(poses, np.int32).reshape(-1, 3)
+        out = np.zeros(len(q), np.int32)
+        _check(self._L.svh_grid_footprint_cost(self._h, q.ctypes.data if len(q) else None, len(q), 0, out.ctypes.data if len(q) else None))
+        return out
+
+    def set_candidates(self, table):
+        """int32 [S, K, T, 3]: S sets of K candidates of T poses (dga, dgb, k); k = -1 ends a candidate"""
+        t = np.ascontiguousarray(table, np.int32)
+        if t.ndim != 4 or t.shape[3] != 3:
+            raise SvhError(ERR_BAD_ARG, "a table [S, K, T, 3] is needed")
+        _check(self._L.svh_grid_roll_set_candidates(self._h, t.ctypes.data, t.shape[0], t.shape[1], t.shape[2]))
+
+    def candidates(self):
+        """(S, K, T) of the candidate table in force, (0, 0, 0) while there is none"""
+        skt = np.zeros(3, np.int32)
+        _check(self._L.svh_grid_roll_get_candidates(self._h, skt.ctypes.data))
+        return tuple(int(v) for v in skt)
+
+    def roll_score(self, anchor_xyz, set_=0, device_ptrs=None):
+        """(best, recs int32 [K, 5] in the order of ROLL_FIELDS, scores int64 [K]) of set `set_` anchored at the cell of a map-frame
+        position; with device_ptrs = (recs, scores), either may be None, they are written there and only best is returned"""
+        best = C.c_int32(-9)
+        if device_ptrs is not None:
+            _check(self._L.svh_grid_roll_score(self._h, _xyz(anchor_xyz).ctypes.data, set_, device_ptrs[0], device_ptrs[1], 1, C.addressof(best)))
+            return best.value
+        K = self.candidates()[1]                           # asked of the library: a table whose upload failed is in force all the same
+        recs, scores = np.zeros((max(K, 1), ROLL_RECORD), np.int32), np.zeros(max(K, 1), np.int64)
+        _check(self._L.svh_grid_roll_score(self._h, _xyz(anchor_xyz).ctypes.data, set_, recs.ctypes.data, scores.ctypes.data, 0, C.addressof(best)))
+        return best.value, recs[:K], scores[:K]
+
+    def render_roll(self, device_ptr=None):
+        """render_cost with the poses before the cut of every candidate of the last roll_score in ROLL_COLOUR, the best's in
+        ROLL_BEST_COLOUR over them"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_roll(self._h, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_roll(self._h, img.ctypes.data, 0))
         return img
 
     def stats(self):

@@ -18,6 +18,7 @@ without the GUI.  Usage:
                                           [--grid-local DIR [--grid-cell S] [--grid-size NXxNZ]]
                                           [--grid-cost DIR [--grid-slope S] [--grid-inscribed M] [--grid-inflate M]]
                                          [--grid-plan DIR [--grid-goal-ahead M]]
+                                         [--grid-roll DIR [--grid-roll-vehicle FRONT,REAR,HALFWIDTH] [--grid-roll-unknown N]]
                                           [--grid-frontiers DIR [--grid-unexplored unseen|seen|both] [--grid-frontier-min N]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
@@ -85,6 +86,16 @@ passable at a price of 100 above the neutral one.  The plan image (svh_grid_rend
 yellow, the path white) goes into DIR/plan_%06d.ppm and one line {"frame", "status", "length", "cost"} per frame is appended
 to DIR/plan.jsonl (status 0 found, 1 unreachable, 2 the camera's cell is impassable, 3 outside).
 
+--grid-roll DIR: needs --grid-plan, and runs after it on its goals.  After every local step short motions are scored on the device
+(svh_grid_roll_score): nine constant-curvature arcs (-0.2 .. 0.2 per metre) of 24 poses, one every two cells, that start at the
+camera's cell along the heading of its forward axis (svh_grid_heading_of); each is cut where the vehicle's rectangle (3.5 m to the
+front, 1.0 m to the rear, 0.9 m to either side; --grid-roll-vehicle FRONT,REAR,HALFWIDTH) first touches a cell of cost 253 or more,
+an unknown cell among them (--grid-roll-unknown N: an unknown cell counts as a cost of N, 0..254, instead of 254), or leaves the
+window, and scored by the field at its end plus the costs it collected.  The image
+(svh_grid_render_roll: the cost map, the poses before the cuts light blue, those of the best arc white) goes into
+DIR/roll_%06d.ppm and one line {"frame", "set", "best", "feasible", "length", "status", "score"} per frame is appended to
+DIR/roll.jsonl (length, status and score of the best arc; -1, -1, null when no arc is feasible).
+
 --grid-frontiers DIR: needs --grid-cost.  After every local step the frontiers of the local grid (svh_grid_get_frontiers: the
 free cells beside ground that was never looked at, grouped into 8-connected components, those of fewer than 8 cells dropped),
 the representatives of the kept components as the planner's goals (svh_grid_plan_set_goals_frontiers) and the path from the
@@ -114,6 +125,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "stereo-vision_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+ROLL_CURVATURES = (-0.2, -0.15, -0.1, -0.05, 0.0, 0.05, 0.1, 0.15, 0.2)   # --grid-roll: per metre; the arcs of one set
+ROLL_POSES = 24                                                            # ... of this many poses, one every two cells
 
 
 class DeviceBuffer:
@@ -214,6 +228,22 @@ class Pipeline:
         g.set_goals([(oa + ia, row) for ia in range(g.nx)])
         status, cells, cost = g.path(centre)
         return status, cells, cost, g.render_plan(cells)
+
+    def enable_roll(self, curvatures, step_len, poses, **kw):
+        """the vehicle (kw: front, rear, half_width, stop_cost, ...) and one set of constant-curvature arcs per start heading"""
+        from svhip import grid
+        g = self.local
+        if kw:
+            g.set_roll(**kw)
+        g.set_candidates(grid.arc_candidates(g.params.cell, g.roll_params()[0].headings_m, curvatures, step_len, poses))
+
+    def roll_step(self):
+        """the arcs that start along the camera's forward axis scored at the camera's cell on the cost map and the field as they
+        stand: (set, best, records [K, 5], scores [K], the rollout image [nz, nx, 3])"""
+        g = self.local
+        s = g.heading_of(self.H_total[:3, 2].copy())
+        best, recs, scores = g.roll_score(self.H_total[:3, 3].copy(), s)
+        return s, best, recs, scores, g.render_roll()
 
     def frontier_step(self):
         """the frontiers of the local grid, goals from them, the path from the camera's position:
@@ -506,6 +536,7 @@ def main():
     grid_dir, grid_cell, grid_size = None, 0.2, (256, 256)
     local_dir, cost_dir, cost_kw = None, None, {}
     plan_dir, goal_ahead, front_dir, front_kw = None, None, None, {}
+    roll_dir, roll_kw = None, {}
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -546,6 +577,21 @@ def main():
             goal_ahead = float(sys.argv[k + 1])
             assert goal_ahead >= 0 and goal_ahead < float("inf")
             del sys.argv[k:k + 2]
+        if "--grid-roll" in sys.argv:
+            k = sys.argv.index("--grid-roll")
+            roll_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-roll-vehicle" in sys.argv:
+            k = sys.argv.index("--grid-roll-vehicle")
+            dims = [float(v) for v in sys.argv[k + 1].split(",")]
+            assert len(dims) == 3 and all(0 <= v < float("inf") for v in dims)
+            roll_kw.update(front=dims[0], rear=dims[1], half_width=dims[2])
+            del sys.argv[k:k + 2]
+        if "--grid-roll-unknown" in sys.argv:
+            k = sys.argv.index("--grid-roll-unknown")
+            roll_kw["unknown_cost"] = int(sys.argv[k + 1])
+            assert 0 <= roll_kw["unknown_cost"] <= 254
+            del sys.argv[k:k + 2]
         if "--grid-frontiers" in sys.argv:
             k = sys.argv.index("--grid-frontiers")
             front_dir = sys.argv[k + 1]
@@ -563,6 +609,8 @@ def main():
         assert cost_dir or not front_dir
         assert front_dir or not front_kw
         assert plan_dir or goal_ahead is None
+        assert plan_dir or not roll_dir
+        assert roll_dir or not roll_kw
         assert local_dir or not (cost_dir or cost_kw)
         assert cost_dir or not cost_kw
         assert grid_dir or not level
@@ -628,6 +676,9 @@ def main():
     if front_dir:
         os.makedirs(front_dir, exist_ok=True)
         open(os.path.join(front_dir, "frontiers.jsonl"), "w").close()
+    if roll_dir:
+        os.makedirs(roll_dir, exist_ok=True)
+        open(os.path.join(roll_dir, "roll.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -642,7 +693,9 @@ def main():
         p.local.set_plan(unknown=100)
     if front_kw:
         p.local.set_frontier(**front_kw)
-    found = explored = 0
+    if roll_dir:
+        p.enable_roll(ROLL_CURVATURES, 2.0 * grid_cell, ROLL_POSES, **roll_kw)
+    found = explored = rolled = 0
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -667,6 +720,14 @@ def main():
             view.write_ppm(os.path.join(plan_dir, "plan_%06d.ppm" % (frames - 1)), img)
             with open(os.path.join(plan_dir, "plan.jsonl"), "a") as f:
                 f.write(json.dumps({"frame": frames - 1, "status": int(status), "length": int(len(cells)), "cost": int(cost)}) + "\n")
+        if roll_dir:
+            s, best, recs, scores, img = p.roll_step()
+            rolled += best >= 0
+            view.write_ppm(os.path.join(roll_dir, "roll_%06d.ppm" % (frames - 1)), img)
+            with open(os.path.join(roll_dir, "roll.jsonl"), "a") as f:
+                f.write(json.dumps({"frame": frames - 1, "set": int(s), "best": int(best), "feasible": int((scores != (1 << 63) - 1).sum()),
+                                    "length": int(recs[best, 0]) if best >= 0 else -1, "status": int(recs[best, 1]) if best >= 0 else -1,
+                                    "score": int(scores[best]) if best >= 0 else None}) + "\n")
         if front_dir:
             stats, status, cells, cost, img = p.frontier_step()
             explored += status == 0
@@ -696,6 +757,9 @@ def main():
     if plan_dir:
         print("plan: goals %g m ahead, a route in %d of %d frames; %d images and plan.jsonl in %s" % (
             20.0 if goal_ahead is None else goal_ahead, found, frames, frames, plan_dir))
+    if roll_dir:
+        print("rollouts: %d arcs of %d poses per heading, a feasible one in %d of %d frames; %d images and roll.jsonl in %s" % (
+            len(ROLL_CURVATURES), ROLL_POSES, rolled, frames, frames, roll_dir))
     if front_dir:
         print("frontiers: goals from the kept components, a route in %d of %d frames; %d images and frontiers.jsonl in %s" % (
             explored, frames, frames, front_dir))
