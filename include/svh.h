@@ -173,6 +173,8 @@ typedef struct svh_elas svh_elas;
  *   SVH_DESC_FLY_KEYED=0   subsampling / disp_max > 255 keep the stored descriptor maps
  *   SVH_HW_QUEUES=n        the count svh_init asks for when svh_config::hw_queues is 0 (default 20); 0: hands off
  *   SVH_QUEUE_PLAN=n       the queue plan lanes are built with (0..4, see svh_elas_set_queue_plan; default: automatic)
+ *   SVH_FEED=bits          read per batch call, for A/B runs: 1 = a lane's parity is set at acquisition, 2 = groups in
+ *                          fixed shares per worker, 4 = a worker refills its two lanes in strict alternation (default 0)
  *   SVH_MATCH_WIDE768=0    rows of 1281-1920 px: 512-thread blocks (8 pixels per thread) in k_match_list instead of 768
  *   SVH_GAP_SEQ=1          wide interpolation gaps / add_corners: one thread per line (k_gap_lines) instead of the
  *                          per-row scan and the segmented column pass
@@ -357,6 +359,15 @@ void svh_elas_stage_stats(int64_t* device_groups, int64_t* handed_back);
  * counts of the lane's last groups; out4[2], out4[3]: of the latter, groups that held more triangles / more support
  * points than the launch was sized for (the kernels stride over the rest: results do not depend on the size). */
 void svh_elas_sizing_stats(int64_t* out4);
+/* diagnostics: how the last batch call (svh_elas_process_batch*) fed its workers, and what the lane pool of the calling
+ * thread's device holds.  out[0] workers of the call, out[1] its groups, out[2] its duration in microseconds; out[3]
+ * over the process: groups a worker gave to the lane it had filled last, because that lane was free first; out[4]
+ * lanes in the pool, out[5..7] streams they hold in the normal, high and low priority class; then per worker w of
+ * the call, out[8 + 2 w] groups it took and out[9 + 2 w] microseconds from the start of the call to the end of its
+ * last group.  SVH_ELAS_FEED_STATS_LEN values in all. */
+#define SVH_ELAS_FEED_WORKERS 64
+#define SVH_ELAS_FEED_STATS_LEN (8 + 2 * SVH_ELAS_FEED_WORKERS)
+void svh_elas_feed_stats(int64_t* out);
 /* the engine settings in effect: out[0] workers (svh_elas_set_lanes), out[1] pairs per launch (0: automatic by image
  * size), out[2] stage (-1 / 0 / 1, svh_elas_set_stage), out[3] the workers' poll interval in microseconds */
 void svh_elas_get_settings(int32_t out[4]);

@@ -40,6 +40,7 @@
 #include <thread>
 #include <vector>
 
+#include "group_feed.h"
 #include "hip_guard.h"
 #include "queue_plan.h"
 #include "svh_internal.h"
@@ -159,13 +160,16 @@ struct Lane : LaneBufs {
     hipStream_t stream = nullptr, stage_stream = nullptr, post_stream = nullptr;
     hipStream_t cls_stream[QC_COUNT] = {nullptr, nullptr, nullptr};
     int plan_req = QP_AUTO;         // the pool's setting when the lane was created (svh_elas_set_queue_plan)
-    int parity = 0;                 // first / second lane of its worker (set by acquire_lanes)
+    int parity = 0;                 // first / second lane of a worker: fixed when the pool creates the lane (acquire_lanes)
+    uint64_t freed_at = 0;          // order of its last return to the pool (SVH_FEED bit 1: the lane released last goes out first)
+    std::atomic<int>* cls_count = nullptr;   // the pool's count of streams per class (svh_elas_feed_stats)
     bool qp_known = false;
     QueuePlan qp{};
     int prio_least = 0, prio_greatest = 0;
     bool split = false;             // the group in flight runs its phases on more than one stream
     hipEvent_t a_ev = nullptr, b_ev = nullptr;   // k_support done (main stream), phase B done (post_stream)
     hipEvent_t wait_ev = nullptr;   // completion marker polled by lane_wait
+    bool wait_marked = false;       // wait_ev already stands behind the group's last work (lane_mark): lane_wait polls it
     hipStream_t copy_stream = nullptr;   // early D2H of maps that are final before the stream is done
     hipEvent_t match_ev = nullptr, copy_ev = nullptr;
     bool poll_wait = false;         // batch workers sleep-poll; single calls spin (lowest latency)
@@ -223,10 +227,11 @@ struct Lane : LaneBufs {
         prof.ev.clear();
         prof.names.clear();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        for (hipStream_t& cs : cls_stream)
-            if (cs) {
-                (void)hipStreamDestroy(cs);
-                cs = nullptr;
+        for (int c = 0; c < QC_COUNT; c++)
+            if (cls_stream[c]) {
+                (void)hipStreamDestroy(cls_stream[c]);
+                cls_stream[c] = nullptr;
+                if (cls_count) cls_count[c].fetch_sub(1, std::memory_order_relaxed);
             }
         copy_stream = stream = stage_stream = post_stream = nullptr;
     }
@@ -254,6 +259,7 @@ struct Lane : LaneBufs {
             else
                 HIP_TRY(none, hipStreamCreateWithPriority(&cs, hipStreamNonBlocking,
                                                           queue_priority_of(ql.cls[k], prio_least, prio_greatest)));
+            if (cls_count) cls_count[ql.cls[k]].fetch_add(1, std::memory_order_relaxed);
         }
         stream = cls_stream[ql.cls[ql.phase_stream[QPH_A]]];
         stage_stream = cls_stream[ql.cls[ql.phase_stream[QPH_S]]];
@@ -357,19 +363,42 @@ struct Lane : LaneBufs {
 static std::atomic<int> g_wait_us{40};   // (SVH_WAIT_US / svh_config::wait_us: apply_config below)
 static std::atomic<bool> g_hostprof{false};   // SVH_HOST_PROF (apply_config)
 static hipError_t lane_wait(Lane& L) {
-    if (!L.poll_wait || g_wait_us <= 0) return hipStreamSynchronize(L.stream);
+    if (!L.poll_wait || g_wait_us <= 0) {
+        L.wait_marked = false;
+        return hipStreamSynchronize(L.stream);
+    }
     if (!L.wait_ev) {
         hipError_t e = hipEventCreateWithFlags(&L.wait_ev, hipEventDisableTiming);
         if (e != hipSuccess) return e;
     }
-    hipError_t e = hipEventRecord(L.wait_ev, L.stream);
-    if (e != hipSuccess) return e;
+    hipError_t e = hipSuccess;
+    if (L.wait_marked) {
+        L.wait_marked = false;
+    } else {
+        e = hipEventRecord(L.wait_ev, L.stream);
+        if (e != hipSuccess) return e;
+    }
     for (;;) {
         e = hipEventQuery(L.wait_ev);
         if (e != hipErrorNotReady) return e;
         std::this_thread::sleep_for(std::chrono::microseconds(g_wait_us.load(std::memory_order_relaxed)));
     }
 }
+
+// A batch worker that refills its lanes in completion order (batch_impl) puts the completion marker behind a group's
+// last work as soon as that is enqueued, and asks without blocking whether it has passed.  A lane that blocks in its
+// waits (a latency call), or that carries no marker, is "done" at once: RG_FINISH then waits as it always did.
+static void lane_mark(Lane& L) {
+    if (!L.poll_wait || g_wait_us <= 0) return;
+    if (!L.wait_ev && hipEventCreateWithFlags(&L.wait_ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        L.wait_ev = nullptr;
+        return;
+    }
+    if (hipEventRecord(L.wait_ev, L.stream) == hipSuccess) L.wait_marked = true;
+    else (void)hipGetLastError();
+}
+static bool lane_done(Lane& L) { return !L.wait_marked || hipEventQuery(L.wait_ev) != hipErrorNotReady; }
 
 // ---------------------------------------------------------------------------
 // per-device lane pool
@@ -378,7 +407,9 @@ struct Pool {
     std::mutex mu;
     std::condition_variable cv;
     std::vector<Lane*> lanes;
-    std::vector<Lane*> free_list;
+    std::vector<Lane*> free_list[2];   // by lane parity
+    uint64_t freed = 0;                // returns so far (Lane::freed_at)
+    std::atomic<int> streams[QC_COUNT] = {};   // streams the pool's lanes hold, per priority class
     int max_lanes = 4;
     int queue_plan = -2;   // svh_elas_set_queue_plan on this device; -2: not called, the process default (g_queue_plan)
 };
@@ -464,30 +495,93 @@ static Pool* pool_for(int device) {
 // takes `count` (1 or 2) lanes at once -- all or nothing, so two callers can never hold one
 // lane each while waiting for a second.  A batch worker is double-buffered (2 lanes), hence
 // the pool may grow to twice the configured number of workers.
-static void acquire_lanes(int device, int count, Lane** out) {
+//
+// A lane keeps the parity it was created with: the parity decides the priority class of its streams under QP_PARITY
+// (queue_plan.h), and a lane that changed sides from call to call ended up owning a stream in both classes -- 24
+// streams for six workers, an arbitrary 6 + 6 of them busy in any one call, three to a hardware queue here and none
+// there.  The pool keeps a free list per parity.  A pair is one lane of each; a lone lane (a single call, a batch of
+// one group) prefers parity 0 and takes a free parity-1 lane only where it would otherwise have to wait.  Where the
+// pool is full and holds no lane of a parity a pair needs (many single calls at once created first lanes only), an
+// idle lane of the other parity is retired for it.
+// SVH_FEED bit 1 (FEED_PARITY_AT_ACQUIRE, A/B runs) hands out the lanes released last, whatever their parity, and
+// sets the parity by the position in the acquisition, as the engine did before.
+static int feed_mode() { return feed_mode_from_text(svh::env("SVH_FEED")); }
+
+static Lane* make_lane(Pool* p, int device, int parity) {   // (p->mu held)
+    Lane* l = new Lane();
+    l->device = device;
+    l->parity = parity;
+    l->plan_req = p->queue_plan != -2 ? p->queue_plan : g_queue_plan.load();
+    l->cls_count = p->streams;
+    p->lanes.push_back(l);
+    return l;
+}
+
+static void acquire_lanes(int device, int count, Lane** out, int feed = -1) {
+    if (feed < 0) feed = feed_mode();
     Pool* p = pool_for(device);
-    std::unique_lock<std::mutex> lk(p->mu);
-    p->max_lanes = 2 * g_lanes.load() + 2;   // (+2: single calls still find a lane while a stream holds its workers' lanes)
-    for (;;) {
-        const int can_make = p->max_lanes - (int)p->lanes.size();
-        if ((int)p->free_list.size() + std::max(can_make, 0) >= count) {
-            for (int i = 0; i < count; i++) {
-                if (!p->free_list.empty()) {
-                    out[i] = p->free_list.back();
-                    p->free_list.pop_back();
-                } else {
-                    Lane* l = new Lane();
-                    l->device = device;
-                    l->plan_req = p->queue_plan != -2 ? p->queue_plan : g_queue_plan.load();
-                    p->lanes.push_back(l);
-                    out[i] = l;
+    Lane* retired[2] = {nullptr, nullptr};
+    {
+        std::unique_lock<std::mutex> lk(p->mu);
+        p->max_lanes = 2 * g_lanes.load() + 2;   // (+2: single calls still find a lane while a stream holds its workers' lanes)
+        std::vector<Lane*>* fl = p->free_list;
+        for (;; p->cv.wait(lk)) {
+            const int can_make = std::max(p->max_lanes - (int)p->lanes.size(), 0);
+            if (feed & FEED_PARITY_AT_ACQUIRE) {
+                if ((int)(fl[0].size() + fl[1].size()) + can_make < count) continue;
+                for (int i = 0; i < count; i++) {
+                    int q = -1;
+                    for (int c = 0; c < 2; c++)
+                        if (!fl[c].empty() && (q < 0 || fl[c].back()->freed_at > fl[q].back()->freed_at)) q = c;
+                    if (q >= 0) {
+                        out[i] = fl[q].back();
+                        fl[q].pop_back();
+                    } else {
+                        out[i] = make_lane(p, device, i);
+                    }
+                    out[i]->parity = i;   // (a lone lane is a first lane)
                 }
-                out[i]->parity = i;   // (a lone lane is a first lane)
+                break;
             }
-            return;
+            if (count == 1) {
+                const int q = !fl[0].empty() ? 0 : can_make > 0 ? -1 : !fl[1].empty() ? 1 : -2;
+                if (q == -2) continue;
+                if (q < 0) {
+                    out[0] = make_lane(p, device, 0);
+                } else {
+                    out[0] = fl[q].back();
+                    fl[q].pop_back();
+                }
+                break;
+            }
+            // a pair: what is missing is created, or made room for by retiring idle lanes the pair does not take
+            const int missing = (int)fl[0].empty() + (int)fl[1].empty();
+            int spare = 0;
+            for (int q = 0; q < 2; q++) spare += std::max((int)fl[q].size() - 1, 0);
+            if (missing > can_make + spare) continue;
+            for (int q = 0; q < 2; q++) {
+                if (!fl[q].empty()) {
+                    out[q] = fl[q].back();
+                    fl[q].pop_back();
+                    continue;
+                }
+                if (p->max_lanes <= (int)p->lanes.size()) {
+                    std::vector<Lane*>& from = fl[1 - q];   // (it holds a spare: the test above)
+                    Lane* victim = from.front();
+                    from.erase(from.begin());
+                    p->lanes.erase(std::find(p->lanes.begin(), p->lanes.end(), victim));
+                    retired[q] = victim;
+                }
+                out[q] = make_lane(p, device, q);
+            }
+            break;
         }
-        p->cv.wait(lk);
     }
+    for (Lane* l : retired)
+        if (l) {
+            l->destroy();
+            delete l;
+        }
 }
 
 static Lane* acquire_lane(int device) {
@@ -500,7 +594,8 @@ static void release_lane(Lane* l) {
     Pool* p = pool_for(l->device);
     {
         std::lock_guard<std::mutex> lk(p->mu);
-        p->free_list.push_back(l);
+        l->freed_at = ++p->freed;
+        p->free_list[l->parity & 1].push_back(l);
     }
     p->cv.notify_all();
 }
@@ -624,6 +719,11 @@ static std::atomic<int64_t> g_stage_dev_groups{0}, g_stage_redo_groups{0};
 // svh_elas_sizing_stats: device-stage groups whose phase B was sized by the bound / by the lane's history, and of the
 // latter those that held more triangles / more support points than the launch was sized for (the stride loops ran)
 static std::atomic<int64_t> g_sized_bound{0}, g_sized_hist{0}, g_short_tri{0}, g_short_sup{0};
+// svh_elas_feed_stats: the last batch call's workers, groups and duration, per worker the groups it took and when its
+// last group finished (microseconds from the start of the call); over the process, refills of a lane out of turn
+constexpr int kFeedWorkers = 64;   // (svh_elas_set_lanes allows no more)
+static std::atomic<int64_t> g_feed_workers{0}, g_feed_groups{0}, g_feed_call_us{0}, g_feed_out_of_turn{0};
+static std::atomic<int64_t> g_feed_taken[kFeedWorkers], g_feed_finish_us[kFeedWorkers];
 
 // sleep-poll (batch workers) or block on an event
 static hipError_t event_wait(Lane& L, hipEvent_t ev) {
@@ -652,6 +752,7 @@ static int run_group(Lane& L, const svh_elas_params& p, const int32_t* dims, con
         for (hipStream_t cs : L.cls_stream)
             if (cs) (void)hipStreamSynchronize(cs);
         L.split = false;
+        L.wait_marked = false;
         if (L.copy_stream) (void)hipStreamSynchronize(L.copy_stream);
         (void)hipGetLastError();
         L.prof.used = 0;
@@ -1374,7 +1475,9 @@ int64_t svh_elas_trim(void) {
         std::vector<Lane*> idle;
         {
             std::lock_guard<std::mutex> lk(p->mu);
-            idle.swap(p->free_list);
+            idle.swap(p->free_list[0]);
+            idle.insert(idle.end(), p->free_list[1].begin(), p->free_list[1].end());
+            p->free_list[1].clear();
             for (Lane* l : idle) p->lanes.erase(std::find(p->lanes.begin(), p->lanes.end(), l));
         }
         for (Lane* l : idle) {
@@ -1518,12 +1621,22 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
     std::vector<int32_t> st(n, SVH_OK);
     std::vector<int32_t> grc(ngroups, SVH_OK);
     std::vector<std::string> errs(std::max(lanes, 1));
+    // how the groups reach the workers and the workers' lanes (group_feed.h; SVH_FEED, read per call, for A/B runs)
+    const int feed_bits = feed_mode();
+    GroupFeed feed;
+    const auto call_t0 = std::chrono::steady_clock::now();
+    auto call_us = [&]() {
+        return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - call_t0).count();
+    };
+    g_feed_workers = std::max(lanes, 1);
+    g_feed_groups = ngroups;
+    for (int w = 0; w < kFeedWorkers; w++) g_feed_taken[w] = g_feed_finish_us[w] = 0;
     // Each worker owns TWO lanes (stream + buffers) and software-pipelines its groups: while it
     // filters and triangulates group i on the host, the device already runs descriptor + support
     // matching of group i+1 on the other lane, and the tail kernels of group i-1 behind that.
     auto worker = [&](int w) {
         Lane* slot[2] = {nullptr, nullptr};
-        acquire_lanes(e->device, ngroups > 1 ? 2 : 1, slot);
+        acquire_lanes(e->device, ngroups > 1 ? 2 : 1, slot, feed_bits);
         // size the lanes' buffers before taking work: allocation synchronises the
         // device and must not land in the middle of other lanes' launches later
         for (Lane* L : slot)
@@ -1539,14 +1652,18 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
                 if (hipSetDevice(L->device) == hipSuccess) (void)L->ensure(e->p, dims[0], dims[1], G);
             }
         struct Job { int32_t gi = -1; GroupIO io{}; int32_t first = 0; };
-        // static round-robin shares (groups cost the same): a worker that prefetches its next
-        // group never takes one away from a worker that has nothing to do yet
-        int32_t my_next = w;
+        // Groups cost the same, but the workers are not equally fast where their lanes share hardware queues unevenly:
+        // a worker draws its next group when one of its lanes is free for it (group_feed.h: its first group is
+        // group w, so a worker that prefetches never leaves one that has nothing to do yet without any)
+        const bool fixed = (feed_bits & FEED_FIXED_SHARES) != 0;
+        const int nworkers = std::max(lanes, 1);
+        FeedCursor cursor;
+        auto more = [&]() { return feed_peek(feed, cursor, fixed, w, nworkers, ngroups) >= 0; };
         auto take = [&]() {
             Job j;
-            const int32_t gi = my_next;
-            my_next += lanes;
-            if (gi < ngroups) {
+            const int32_t gi = feed_take(feed, cursor, fixed, w, nworkers, ngroups);
+            if (gi >= 0) {
+                if (w < kFeedWorkers) g_feed_taken[w].fetch_add(1, std::memory_order_relaxed);
                 j.gi = gi;
                 j.first = gi * G;
                 j.io = io_of(j.first, std::min(G, n - j.first));
@@ -1559,8 +1676,80 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
                 if (rcj < 0) errs[w] = svh_last_error();
             }
         };
+        auto finished = [&]() {
+            if (w < kFeedWorkers) g_feed_finish_us[w].store(call_us(), std::memory_order_relaxed);
+        };
         Job pending[2];   // group whose tail is still on slot k's stream
-        Job cur = take();
+        if (!(feed_bits & FEED_ALTERNATE)) {
+            // The worker as a state machine over its lanes: empty -> phase A enqueued (RG_HOST_B due) -> everything
+            // enqueued (RG_FINISH due) -> empty.  It does whichever step is ready and gives its next group to
+            // whichever lane is empty first, so a lane in the normal class is not held up by its partner in the low
+            // class, whose kernels stretch.  A lane is never more than one group deep: phase A of its next group
+            // overwrites what phase B of its last one reads, and h_counts and the sizing history are per lane.
+            //   * device stage, maps on the device: RG_HOST_B waits for nothing and follows phase A at once;
+            //   * device stage, maps to host buffers: RG_HOST_B is due when stage_ev has passed (polled);
+            //   * host stage (and a group whose phase A failed): RG_HOST_B is blocking host work meant to overlap the
+            //     other lane's phase A, so the calls keep the order they always had -- before it, the other lane is
+            //     finished (blocking) if a group is left for it, and refilled.
+            // Lanes that block in their waits (a one-round batch) are "ready" at once and wait inside the step.
+            enum { LS_EMPTY = 0, LS_A = 1, LS_ALL = 2 };
+            int state[2] = {LS_EMPTY, LS_EMPTY};
+            const int nl = slot[1] ? 2 : 1;
+            int last_filled = -1;
+            auto start = [&](int q) {   // phase A of the worker's next group on the empty lane q
+                Job j = take();
+                if (j.gi < 0) return false;
+                if (nl == 2 && q == last_filled) g_feed_out_of_turn.fetch_add(1, std::memory_order_relaxed);
+                last_filled = q;
+                note(j, run_group(*slot[q], e->p, dims, j.io, &st[j.first], nullptr, nullptr, RG_A, deep));
+                pending[q] = j;
+                state[q] = LS_A;
+                return true;
+            };
+            auto host_b = [&](int q) {
+                const Job& j = pending[q];
+                if (grc[j.gi] == SVH_OK) {
+                    note(j, run_group(*slot[q], e->p, dims, j.io, &st[j.first], nullptr, nullptr, RG_HOST_B));
+                    if (grc[j.gi] == SVH_OK) lane_mark(*slot[q]);
+                }
+                state[q] = LS_ALL;
+            };
+            auto finish = [&](int q) {
+                const Job& j = pending[q];
+                note(j, run_group(*slot[q], e->p, dims, j.io, &st[j.first], nullptr, nullptr, RG_FINISH));
+                finished();
+                pending[q].gi = -1;
+                state[q] = LS_EMPTY;
+            };
+            auto stage_ready = [&](Lane& L) {
+                return !L.poll_wait || g_wait_us <= 0 || hipEventQuery(L.stage_ev) != hipErrorNotReady;
+            };
+            for (;;) {
+                bool progress = false;
+                for (int q = 0; q < nl; q++) {
+                    if (state[q] == LS_ALL && lane_done(*slot[q])) {
+                        finish(q);
+                        progress = true;
+                    }
+                    if (state[q] == LS_EMPTY && start(q)) progress = true;
+                    if (state[q] != LS_A) continue;
+                    Lane& L = *slot[q];
+                    if (grc[pending[q].gi] != SVH_OK || !L.resident) {
+                        const int o = 1 - q;
+                        if (nl == 2 && state[o] == LS_ALL && more()) finish(o);
+                        if (nl == 2 && state[o] == LS_EMPTY) start(o);
+                        host_b(q);
+                        progress = true;
+                    } else if (pending[q].io.out_device || stage_ready(L)) {
+                        host_b(q);
+                        progress = true;
+                    }
+                }
+                if (state[0] == LS_EMPTY && state[nl - 1] == LS_EMPTY && !more()) break;
+                if (!progress) std::this_thread::sleep_for(std::chrono::microseconds(std::max(g_wait_us.load(std::memory_order_relaxed), 1)));
+            }
+        }
+        Job cur = (feed_bits & FEED_ALTERNATE) ? take() : Job();
         int k = 0;
         if (cur.gi >= 0) note(cur, run_group(*slot[0], e->p, dims, cur.io, &st[cur.first], nullptr, nullptr, RG_A, deep));
         while (cur.gi >= 0) {
@@ -1570,6 +1759,7 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
                 if (pending[o].gi >= 0) {
                     note(pending[o], run_group(*slot[o], e->p, dims, pending[o].io, &st[pending[o].first], nullptr,
                                                nullptr, RG_FINISH));
+                    finished();
                     pending[o].gi = -1;
                 }
                 note(nxt, run_group(*slot[o], e->p, dims, nxt.io, &st[nxt.first], nullptr, nullptr, RG_A, deep));
@@ -1579,6 +1769,7 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
             pending[k] = cur;
             if (!slot[1]) {   // single lane: finish right away and take the next group on it
                 note(cur, run_group(*slot[0], e->p, dims, cur.io, &st[cur.first], nullptr, nullptr, RG_FINISH));
+                finished();
                 pending[0].gi = -1;
                 nxt = take();
                 if (nxt.gi >= 0)
@@ -1590,9 +1781,11 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
         }
         for (int q = 0; q < 2; q++)
             if (slot[q]) {
-                if (pending[q].gi >= 0)
+                if (pending[q].gi >= 0) {
                     note(pending[q], run_group(*slot[q], e->p, dims, pending[q].io, &st[pending[q].first], nullptr,
                                                nullptr, RG_FINISH));
+                    finished();
+                }
                 slot[q]->poll_wait = false;
                 slot[q]->parallel_host = true;
                 slot[q]->lone_group = true;
@@ -1616,6 +1809,7 @@ static int32_t batch_impl(svh_elas* e, int32_t n, const int32_t* dims, int32_t* 
         worker(0);
         crew().wait(left);
     }
+    g_feed_call_us = call_us();
     int32_t first_bad = SVH_OK;
     for (int32_t gi = 0; gi < ngroups; gi++)
         if (grc[gi] != SVH_OK) {
@@ -2070,6 +2264,27 @@ void svh_test_d2h_map_bytes(int64_t out[2], int32_t reset) {
     if (reset) {
         svh::g_d2h_map_bytes.store(0);
         svh::g_d2h_map_copies.store(0);
+    }
+}
+
+void svh_elas_feed_stats(int64_t* out) {
+    if (!out) return;
+    for (int i = 0; i < SVH_ELAS_FEED_STATS_LEN; i++) out[i] = 0;
+    out[0] = svh::g_feed_workers.load();
+    out[1] = svh::g_feed_groups.load();
+    out[2] = svh::g_feed_call_us.load();
+    out[3] = svh::g_feed_out_of_turn.load();
+    {
+        Pool* p = pool_for(t_device);
+        std::lock_guard<std::mutex> lk(p->mu);
+        out[4] = (int64_t)p->lanes.size();
+        out[5] = p->streams[QC_NORMAL].load();
+        out[6] = p->streams[QC_HIGH].load();
+        out[7] = p->streams[QC_LOW].load();
+    }
+    for (int w = 0; w < svh::kFeedWorkers && w < SVH_ELAS_FEED_WORKERS; w++) {
+        out[8 + 2 * w] = svh::g_feed_taken[w].load();
+        out[9 + 2 * w] = svh::g_feed_finish_us[w].load();
     }
 }
 

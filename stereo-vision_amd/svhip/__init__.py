@@ -476,6 +476,18 @@ def queue_plan():
     return dict(plan=p.value, streams_per_lane=s.value, classes=c.value)
 
 
+def feed_stats():
+    """svh_elas_feed_stats: how the last batch call fed its workers and what the device's lane pool holds"""
+    nw = 64
+    out = (C.c_int64 * (8 + 2 * nw))()
+    lib().svh_elas_feed_stats(out)
+    w = int(out[0])
+    return dict(workers=w, groups=int(out[1]), call_us=int(out[2]), out_of_turn=int(out[3]), lanes=int(out[4]),
+                streams=dict(normal=int(out[5]), high=int(out[6]), low=int(out[7])),
+                taken=[int(out[8 + 2 * k]) for k in range(min(w, nw))],
+                finish_us=[int(out[9 + 2 * k]) for k in range(min(w, nw))])
+
+
 def trim():
     """release the pooled lanes that are idle (device + pinned memory, streams); returns the count"""
     lib().svh_elas_trim.restype = C.c_int64
