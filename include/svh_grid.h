@@ -113,6 +113,31 @@
  * return SVH_ERR_BAD_ARG while the traversability is not set or the vehicle does not fit (below).  After SVH_ERR_HIP in a rollout
  * entry the accumulated grid, the cost planes, the goals, the field, the frontier result and both tables are untouched.
  *
+ * EXPLORATION: which frontier to drive to -- what would be seen from it, and what it costs to get there.  The arithmetic is
+ * stereo-vision_amd/csrc/grid_explore_core.h (restated in tests/grid_explore_ref.py): integers on the finished STATE and COST planes
+ * in the window's order.  R = (int)floorf(range / cell), 1..128.  From a VIEWPOINT, a window cell (va, vb), one ray goes to each of
+ * the 8 R offsets (dx, dz) on the perimeter of the square [-R, R]^2; for k = 1..R it visits the offset (sx, sz) = (rdiv(k dx, R),
+ * rdiv(k dz, R)), rdiv(p, n) = floor((2 p + n) / (2 n)), the line of the free-space rays.  A ray ends before the first k at which
+ * sx^2 + sz^2 > R^2, the cell lies outside the window, or the cell's class is obstacle.  Unknown cells, drops, steep cells and the
+ * lethal inflation do not block; only visited cells block, so a viewpoint on an obstacle cell still casts its rays, and a diagonal
+ * step between two obstacle cells passes.  VIEW of a viewpoint, one byte per cell: 0 no ray visits the cell (the viewpoint's own
+ * cell included), 1 visited, 2 visited and UNEXPLORED under the frontier parameters in force.  GAIN is the number of cells with
+ * VIEW 2, each counted once however many rays visit it; -1 for a viewpoint outside the window.  In a window without obstacles the
+ * visited set is the disc 0 < sx^2 + sz^2 <= R^2 clipped to the window.  REACH of a cell from a start cell is POT of PLANNING under
+ * the plan parameters in force with the start as the only goal, read at the cell -- weights and the corner rule are symmetric, so
+ * it is the cost of the path from the start to the cell; SVH_GRID_PLAN_FAR when the start is outside the window or impassable, the
+ * cell unreachable or the cost beyond max_cost.  RANKING: for each kept frontier component, the first 65536 in ascending label, a
+ * record of five int32: label, rep_ga, rep_gb, the gain of the representative, its reach.  A record is feasible iff reach != FAR
+ * and gain >= min_gain; its int64 score is w_reach reach - w_gain gain, INT64_MAX when infeasible; the best is the feasible record
+ * with the least (score, index), -1 if none.  GAIN is the size of a set, REACH a value of the planner's fixed point, the best the
+ * minimum of unique keys: no byte depends on launch shape or scheduling.  Gains and VIEW planes are computed per call and not
+ * cached.  The reach field lives in buffers of its own beside the planner's: a ranking neither changes the goals nor touches or
+ * invalidates the planner's field.  It is cached until the start cell, the accumulators, the window's offsets, the
+ * traversability or the plan parameters change.  The exploration entries return SVH_ERR_BAD_ARG while the traversability is not
+ * set or the range does not fit the grid's cell (below).  After SVH_ERR_HIP in an exploration entry the accumulated grid, the
+ * cost planes, the goals, the field, the frontier result and the roll tables are untouched; the reach field is invalid and the
+ * next ranking computes it again.
+ *
  * Plain C like svh_view.h.  An object has its own stream and every call returns when it is complete.  Calls return
  * SVH_OK or a negative SVH_ERR_*; svh_last_error() has the text.  SVH_ERR_BAD_ARG -- a null pointer, parameters out of
  * the ranges below, n < 0, n > 0 with a null array, a device array that is not 16-byte aligned, an unknown plane or
@@ -364,6 +389,47 @@ int32_t   svh_grid_roll_score(svh_grid* g, const double anchor_xyz[3], int32_t s
  * (0, 192, 255) and those of its best (255, 255, 255) over them; they are global cells, those outside the window now are skipped.
  * SVH_ERR_BAD_ARG: nothing was scored since the tables were set, or the last scoring failed */
 int32_t   svh_grid_render_roll(svh_grid* g, uint8_t* rgb, int32_t on_device);
+
+
+typedef struct svh_grid_explore_params {
+    float   range;             /* 10.0: metres a viewpoint sees; finite, > 0, R = floor(range / cell) in 1..128 */
+    int32_t min_gain;          /* 1: a record with a smaller gain is infeasible; 0..2^26 */
+    int32_t w_gain;            /* 500: weight of the gain in the score; 0..65535 */
+    int32_t w_reach;           /* 1: weight of the reach in the score; 0..65535 */
+} svh_grid_explore_params;
+
+#define SVH_GRID_EXPLORE_RECORD 5      /* int32 per record: label, rep_ga, rep_gb, gain, reach */
+#define SVH_GRID_VIEW_NONE     0       /* bytes of a VIEW plane */
+#define SVH_GRID_VIEW_VISITED  1
+#define SVH_GRID_VIEW_COUNTED  2
+
+void      svh_grid_explore_params_default(svh_grid_explore_params* p);
+/* SVH_ERR_BAD_ARG, nothing changed: a parameter out of its range, or R outside 1..128.  A grid is created with the defaults; if
+ * their R does not fit the grid's cell the object exists, and svh_grid_view_gain, svh_grid_view_mask, svh_grid_explore_rank,
+ * svh_grid_plan_set_goal_explore and svh_grid_render_view return SVH_ERR_BAD_ARG until this call succeeds */
+int32_t   svh_grid_set_explore(svh_grid* g, const svh_grid_explore_params* p);
+/* the parameters in force and their R (0 while the defaults do not fit); either output may be NULL, not both */
+int32_t   svh_grid_get_explore(svh_grid* g, svh_grid_explore_params* p, int32_t* range_R);
+/* GAIN of n viewpoints, global cells (ga, gb), n <= 2^26: cells and out both on the host or (on_device) both in device memory,
+ * 4-byte aligned there.  Computed per call */
+int32_t   svh_grid_view_gain(svh_grid* g, const int32_t* cells, int64_t n, int32_t on_device, int32_t* out);
+/* the VIEW plane of the viewpoint (ga, gb), a global cell: nx * nz bytes laid out as the planes of svh_grid_get.
+ * SVH_ERR_BAD_ARG: the viewpoint is outside the window */
+int32_t   svh_grid_view_mask(svh_grid* g, int32_t ga, int32_t gb, uint8_t* out, int32_t on_device);
+/* ranks the kept frontier components from the cell of the map-frame position start_xyz: *n = the records (the kept components,
+ * at most 65536), the first min(*n, cap) records (5 int32 each) to recs and scores to scores (host memory; either may be NULL),
+ * *best = index or -1.  A start outside the window or on an impassable cell is no error: every reach is SVH_GRID_PLAN_FAR and
+ * *best is -1.  The planner's goals and field are not touched.  SVH_ERR_BAD_ARG: a start with no cell */
+int32_t   svh_grid_explore_rank(svh_grid* g, const double start_xyz[3], int32_t* recs, int64_t* scores, int64_t cap, int64_t* n, int32_t* best);
+/* ranks as above and makes the best record's representative the planner's only goal (svh_grid_plan_set_goals): returns 1, or 0
+ * when there is no best, and then leaves the goals alone; a negative error */
+int32_t   svh_grid_plan_set_goal_explore(svh_grid* g, const double start_xyz[3]);
+/* out[0] records of the last ranking, out[1] feasible records of it, out[2] reach fields computed since create, out[3] kernel
+ * launches of the last gain computation (svh_grid_view_gain or a ranking) */
+int32_t   svh_grid_get_explore_stats(svh_grid* g, int64_t out[4]);
+/* svh_grid_render_frontiers with the VIEW plane of the viewpoint (ga, gb) over it: counted cells (255, 0, 255), visited cells
+ * brightened (c + (255 - c) / 2 per byte), the viewpoint (255, 255, 255).  SVH_ERR_BAD_ARG: the viewpoint is outside the window */
+int32_t   svh_grid_render_view(svh_grid* g, int32_t ga, int32_t gb, uint8_t* rgb, int32_t on_device);
 
 #ifdef __cplusplus
 }

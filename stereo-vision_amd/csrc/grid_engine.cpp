@@ -6,7 +6,8 @@
 // finalise, the render; (grid_trav_kernels.hip): the traversability layer -- flags, obstacle distance, cost, its render;
 // (grid_plan_kernels.hip): the planner -- the relaxation over active tiles, whose round loop is plan_rounds() here;
 // (grid_front_kernels.hip): the frontiers -- mask, union-find labelling, the table of components, run by front_run() here;
-// (grid_roll_kernels.hip): the rollouts -- footprint costs, the scoring of a set of candidates and its best.
+// (grid_roll_kernels.hip): the rollouts -- footprint costs, the scoring of a set of candidates and its best;
+// (grid_explore_kernels.hip): the exploration layer -- the gain of viewpoints, the ranking of the frontiers, run by explore_rank() here.
 // The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
@@ -22,6 +23,9 @@
 // the table) is derived from STATE and COST, as lazily, and kept (front_valid) until the accumulators, the offsets, the
 // traversability or the frontier parameters change.  The rollouts cache nothing but their two tables (the footprints and the
 // candidates), which are relative and survive everything but their own setters: a scoring reads COST and, for w_pot > 0, POT.
+// The exploration layer caches one thing, the reach field: POT with the start of the last ranking as the only goal, in buffers of
+// its own beside the planner's (reach_valid), kept until the start cell, the accumulators, the offsets, the traversability or the
+// plan parameters change.  Gains and VIEW planes are computed per call.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -34,6 +38,7 @@
 
 #include "../../include/svh_grid.h"
 #include "grid_core.h"
+#include "grid_explore_core.h"
 #include "grid_internal.h"
 #include "hip_guard.h"
 #include "svh_config.h"
@@ -112,6 +117,13 @@ struct RollBufs {
     HipBuf<long long> scores;
 };
 
+// what a ranking needs on the device beside the planes: the gains of the representatives, the records, the scores, and the best
+// with the count of feasible records
+struct ExploreBufs {
+    HipBuf<int32_t> gain, recs, out;
+    HipBuf<long long> scores;
+};
+
 }  // namespace
 
 struct svh_grid {
@@ -169,6 +181,20 @@ struct svh_grid {
     PinnedBuf<uint8_t> h_roll;  // records, scores and the best on their way to the host
     bool roll_last = false;     // roll_bufs.recs holds the records of the last svh_grid_roll_score, for svh_grid_render_roll:
     int32_t roll_last_set = 0, roll_last_ga = 0, roll_last_gb = 0, roll_last_best = -1;   // its set, anchor and best
+    grid::ExploreParams exp{10.f, 1, 500, 1};   // the exploration layer: parameters and their R; 0: the defaults do not fit this grid's cell
+    int32_t exp_R = 0;
+    HipBuf<uint8_t> reach;      // kPlanBytes per cell: POT | price | DIR of the reach field, logical order
+    HipBuf<uint32_t> reach_tiles, reach_ctl;   // as plan_tiles and plan_ctl
+    PinnedBuf<uint32_t> h_reach_ctl;
+    HipBuf<int32_t> d_start;    // the start cell: the one goal of the reach field
+    PinnedBuf<int32_t> h_start;
+    bool reach_valid = false;   // `reach` is derived from COST as it is, with the offsets and plan parameters as they are, from the start
+    int32_t reach_ga = 0, reach_gb = 0;   // ... (reach_ga, reach_gb), a global cell; implies trav_valid
+    ExploreBufs ex_bufs;
+    PinnedBuf<uint8_t> h_explore;   // scores, records, best and feasible count of the last ranking on their way to the host
+    HipBuf<int32_t> d_vcells, d_vgain;   // viewpoints of a host caller and their GAIN
+    HipBuf<uint8_t> d_view;     // the VIEW plane of one viewpoint
+    int64_t ex_stats[grid::ES_WORDS] = {0, 0, 0, 0};
     svh_grid_stats st{0, 0, 0, 0, 0};
     int64_t rays = 0, ray_cells = 0;
 
@@ -188,6 +214,7 @@ struct svh_grid {
     int32_t* p_pot() const { return (int32_t*)plan.p; }
     uint16_t* p_price() const { return (uint16_t*)(plan.p + 4 * ncells); }
     uint8_t* p_dir() const { return plan.p + 6 * ncells; }
+    int32_t* r_pot() const { return (int32_t*)reach.p; }
     int32_t* f_label() const { return (int32_t*)front.p; }
     uint8_t* f_flags() const { return front.p + 4 * ncells; }
 };
@@ -195,7 +222,7 @@ struct svh_grid {
 namespace {
 
 // the accumulators change: what was derived from them is stale
-void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = g->plan_valid = g->front_valid = false; }
+void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = g->plan_valid = g->front_valid = g->reach_valid = false; }
 
 void mark_empty(svh_grid* g) {
     g->need_clear = true;
@@ -941,6 +968,209 @@ bool roll_test_args(const svh_grid_roll_params* p, float cell, int32_t nx, int32
 
 const char* const kNoTrav =": the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)";
 
+// ---- the exploration layer ------------------------------------------------------------------------------------------------
+const char* const kNoExplore =": the default range does not fit this grid's cell; set one (svh_grid_set_explore)";
+
+bool convert_explore(const svh_grid_explore_params* p, grid::ExploreParams* q) {
+    if (!p) return false;
+    *q = grid::ExploreParams{p->range, p->min_gain, p->w_gain, p->w_reach};
+    return grid::explore_ok(*q);
+}
+
+grid::ExploreJob explore_job(const grid::ExploreParams& e, const grid::FrontParams& f, int32_t R, int32_t nx, int32_t nz, int32_t oa, int32_t ob,
+                             const uint8_t* state) {
+    grid::ExploreJob j;
+    j.exp = e, j.frp = f, j.R = R;
+    j.nx = nx, j.nz = nz, j.oa = oa, j.ob = ob;
+    j.state = state;
+    return j;
+}
+
+grid::ExploreJob explore_job(const svh_grid* g) {
+    return explore_job(g->exp, g->frp, g->exp_R, g->prm.nx, g->prm.nz, g->prm.oa, g->prm.ob, g->bplane(B_STATE));
+}
+
+// room for a ranking of n records, and the job's pointers to it
+int explore_outputs(ExploreBufs& b, int32_t n, grid::ExploreJob& j) {
+    const size_t room = n > 0 ? (size_t)n : 1;
+    GRID_GROW_N(b.gain, room);
+    GRID_GROW_N(b.recs, (size_t)grid::EXPLORE_REC * room);
+    GRID_GROW_N(b.scores, room);
+    GRID_GROW_N(b.out, 2);
+    j.n = n, j.gain = b.gain.p, j.recs = b.recs.p, j.scores = b.scores.p, j.out = b.out.p;
+    return SVH_OK;
+}
+
+// the job of the reach field: the planner's kernels on buffers of their own, the start as the only goal
+grid::PlanJob reach_job(const svh_grid* g) {
+    grid::PlanJob j = plan_job(g);
+    const size_t tiles = (size_t)grid::plan_tiles_x(j) * grid::plan_tiles_y(j);
+    j.pot = g->r_pot(), j.price = (uint16_t*)(g->reach.p + 4 * g->ncells), j.dir = g->reach.p + 6 * g->ncells;
+    j.goals = g->d_start.p, j.n_goals = 1;
+    j.lists = g->reach_tiles.p, j.flags = g->reach_tiles.p + 2 * tiles;
+    j.ctl = g->reach_ctl.p;
+    return j;
+}
+
+// the reach field from the global cell (ga, gb) is valid: the cost planes, then seed, rounds and DIR on the second job; complete
+// when it returns.  The planner's goals, buffers and field play no part
+int reach_field(svh_grid* g, int32_t ga, int32_t gb) {
+    if (g->reach_valid && g->reach_ga == ga && g->reach_gb == gb) return SVH_OK;
+    g->reach_valid = false;
+    const size_t tiles = ((size_t)(g->prm.nx + grid::PLAN_TILE - 1) / grid::PLAN_TILE) * ((size_t)(g->prm.nz + grid::PLAN_TILE - 1) / grid::PLAN_TILE);
+    GRID_GROW(g->reach, g->ncells * kPlanBytes);
+    GRID_GROW(g->reach_tiles, 4 * tiles * sizeof(uint32_t));
+    GRID_GROW(g->reach_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+    GRID_GROW(g->h_reach_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+    GRID_GROW_N(g->d_start, 2);
+    GRID_GROW(g->h_start, 2 * sizeof(int32_t));
+    g->h_start[0] = ga, g->h_start[1] = gb;
+    GRID_TRY(copy, hipMemcpyAsync(g->d_start, g->h_start, 2 * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    int rc = traverse(g);
+    if (rc) return rc;
+    if ((rc = plan_run(g->stream, reach_job(g), g->h_reach_ctl))) return rc;
+    g->final_valid = g->trav_valid = g->reach_valid = true;
+    g->reach_ga = ga, g->reach_gb = gb;
+    g->ex_stats[grid::ES_FIELDS]++;
+    return SVH_OK;
+}
+
+// the ranking from the global cell (ga, gb): *n records, the first min(*n, cap) of them and of their scores to the host (either
+// array may be null), *best.  All of it stays in h_explore: the scores, then the records, then the best and the feasible count
+int explore_rank(svh_grid* g, int32_t ga, int32_t gb, int32_t* recs, int64_t* scores, int64_t cap, int64_t* n, int32_t* best) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = frontiers(g))) return rc;
+    const int32_t m = (int32_t)std::min<int64_t>(g->front_stats[grid::FS_KEPT], grid::EXPLORE_MAX_RECORDS);
+    if ((rc = reach_field(g, ga, gb))) return rc;
+    grid::ExploreJob j = explore_job(g);
+    if ((rc = explore_outputs(g->ex_bufs, m, j))) return rc;
+    const size_t score_bytes = (size_t)m * sizeof(int64_t), rec_bytes = (size_t)m * grid::EXPLORE_REC * sizeof(int32_t);
+    GRID_GROW(g->h_explore, score_bytes + rec_bytes + 2 * sizeof(int32_t));
+    j.front_recs = g->front_bufs.recs.p, j.pot = g->r_pot();
+    hipStream_t s = g->stream;
+    const int32_t launches = grid::launch_explore_rank(s, j);
+    GRID_TRY(launch, hipGetLastError());
+    uint8_t* h = g->h_explore;
+    if (m > 0) {
+        GRID_TRY(copy, hipMemcpyAsync(h, j.scores, score_bytes, hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(h + score_bytes, j.recs, rec_bytes, hipMemcpyDeviceToHost, s));
+    }
+    GRID_TRY(copy, hipMemcpyAsync(h + score_bytes + rec_bytes, j.out, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    int32_t out[2];
+    memcpy(out, h + score_bytes + rec_bytes, sizeof(out));
+    g->ex_stats[grid::ES_RECORDS] = m, g->ex_stats[grid::ES_FEASIBLE] = out[1], g->ex_stats[grid::ES_LAUNCHES] = launches;
+    const size_t give = (size_t)std::min<int64_t>(m, cap);
+    if (scores && give) memcpy(scores, h, give * sizeof(int64_t));
+    if (recs && give) memcpy(recs, h + score_bytes, give * grid::EXPLORE_REC * sizeof(int32_t));
+    *n = m, *best = out[0];
+    return SVH_OK;
+}
+
+// GAIN of n > 0 viewpoints with arguments that have been checked
+int view_gain(svh_grid* g, const int32_t* cells, int64_t n, bool on_device, int32_t* out) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if (!on_device) {
+        GRID_GROW_N(g->d_vcells, 2 * n);
+        GRID_GROW_N(g->d_vgain, n);
+        GRID_GROW(g->h_out, (size_t)n * sizeof(int32_t));
+        GRID_TRY(copy, hipMemcpyAsync(g->d_vcells, cells, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    }
+    if ((rc = finalise(g))) return rc;
+    const int32_t launches = grid::launch_view_gain(g->stream, explore_job(g), on_device ? cells : g->d_vcells.p, 2, n, on_device ? out : g->d_vgain.p);
+    GRID_TRY(launch, hipGetLastError());
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    } else if ((rc = deliver(g, g->d_vgain, (size_t)n * sizeof(int32_t), out, false))) {
+        return rc;
+    }
+    g->final_valid = true;
+    g->ex_stats[grid::ES_LAUNCHES] = launches;
+    return SVH_OK;
+}
+
+// the VIEW plane of the window viewpoint (va, vb) into d_view, launched on the stream
+int view_plane(svh_grid* g, int32_t va, int32_t vb) {
+    GRID_GROW(g->d_view, g->ncells);
+    const int rc = finalise(g);
+    if (rc) return rc;
+    GRID_TRY(copy, hipMemsetAsync(g->d_view, 0, g->ncells, g->stream));
+    GRID_TRY(launch, (grid::launch_view_mask(g->stream, explore_job(g), va, vb, g->d_view), hipGetLastError()));
+    return SVH_OK;
+}
+
+int view_mask(svh_grid* g, int32_t va, int32_t vb, uint8_t* out, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = view_plane(g, va, vb))) return rc;
+    if ((rc = deliver(g, g->d_view, g->ncells, out, on_device))) return rc;
+    g->final_valid = true;
+    return SVH_OK;
+}
+
+int render_view(svh_grid* g, int32_t va, int32_t vb, uint8_t* rgb, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const size_t bytes = g->ncells * 3;
+    if (!on_device) {
+        GRID_GROW(g->d_rgb, bytes);
+        GRID_GROW(g->h_out, bytes);
+    }
+    if ((rc = frontiers(g))) return rc;
+    if ((rc = view_plane(g, va, vb))) return rc;
+    grid::RenderCostJob j;
+    j.nx = g->prm.nx, j.nz = g->prm.nz;
+    j.cost = g->t_cost(), j.flags = g->t_flags();
+    j.rgb = on_device ? rgb : g->d_rgb.p;
+    grid::launch_render_cost(g->stream, j);
+    grid::launch_front_overlay(g->stream, j.nx, j.nz, g->f_flags(), j.rgb);
+    grid::launch_view_overlay(g->stream, j.nx, j.nz, g->d_view, va, vb, j.rgb);
+    GRID_TRY(launch, hipGetLastError());
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+        return SVH_OK;
+    }
+    return deliver(g, g->d_rgb, bytes, rgb, false);
+}
+
+// an exploration call that failed on the device: nothing in flight, the reach field is computed again by the next ranking
+int explored(svh_grid* g, int rc) {
+    if (rc == SVH_ERR_HIP) g->reach_valid = false;
+    return drained(g, rc);
+}
+
+// what svh_test_grid_explore and svh_test_grid_explore_device share: the arguments checked, the parameters converted, *R
+bool explore_test_args(const svh_grid_front_params* f, const svh_grid_plan_params* pl, const svh_grid_explore_params* e, float cell, int32_t nx,
+                       int32_t nz, int32_t oa, int32_t ob, const uint8_t* state, const uint8_t* cost, const int32_t* cells, int64_t n_cells,
+                       const int32_t* gains, const int32_t* view, const int32_t* start, const int32_t* recs, const int64_t* scores, int64_t cap,
+                       const int64_t* n, const int32_t* best, grid::FrontParams* fq, grid::PlanParams* pq, grid::ExploreParams* eq, int32_t* R) {
+    if (!convert_front(f, fq) || !convert_explore(e, eq) || !(grid::finite_f(cell) && cell > 0.f) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 ||
+        nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) || !state || n_cells < 0 || n_cells > ((int64_t)1 << 26) || (n_cells > 0 && (!cells || !gains)))
+        return false;
+    if (!(*R = grid::explore_range(eq->range, cell))) return false;
+    if (view) {
+        const int64_t va = (int64_t)view[0] - oa, vb = (int64_t)view[1] - ob;
+        if (va < 0 || va >= nx || vb < 0 || vb >= nz) return false;
+    }
+    if (start) {
+        if (!pl || !cost || !n || !best || cap < 0 || (cap > 0 && !recs && !scores)) return false;
+        *pq = grid::PlanParams{pl->neutral, pl->unknown, pl->max_cost};
+        if (!grid::plan_ok(*pq) || start[0] <= -grid::PLAN_GOAL_LIMIT || start[0] >= grid::PLAN_GOAL_LIMIT || start[1] <= -grid::PLAN_GOAL_LIMIT ||
+            start[1] >= grid::PLAN_GOAL_LIMIT)
+            return false;
+    }
+    return true;
+}
+
+// a VIEW plane and its viewpoint drawn over an image of svh_grid_render_cost's layout, on the host
+void view_overlay_host(int32_t nx, int32_t nz, const uint8_t* view, int32_t va, int32_t vb, uint8_t* rgb) {
+    for (int32_t b = 0; b < nz; b++)
+        for (int32_t a = 0; a < nx; a++)
+            (void)grid::colour_view(view[(size_t)b * nx + a], a == va && b == vb, rgb + 3 * ((size_t)(nz - 1 - b) * (size_t)nx + (size_t)a));
+}
+
 // ... and a failed add leaves the empty grid
 int added(svh_grid* g, int rc) {
     if (rc == SVH_ERR_HIP) {
@@ -1053,6 +1283,7 @@ svh_grid* svh_grid_create(const svh_grid_params* p) {
     svh_grid_trav_params_default(&t);
     g->trav_ok = convert_trav(&t, q.cell, &g->trv, &g->table);   // false: no traversability until it is set
     (void)g->rol.derive(q.cell);                                 // R 0: no rollouts until svh_grid_set_roll succeeds
+    g->exp_R = grid::explore_range(g->exp.range, q.cell);        // 0: no exploration until svh_grid_set_explore succeeds
     (void)hipGetDevice(&g->device);
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
         delete g;
@@ -1214,7 +1445,7 @@ int32_t svh_grid_set_traversability(svh_grid* g, const svh_grid_trav_params* t) 
     g->trv = q;
     g->table.swap(table);
     g->trav_ok = true;
-    g->trav_valid = g->plan_valid = g->front_valid = g->table_sent = false;
+    g->trav_valid = g->plan_valid = g->front_valid = g->reach_valid = g->table_sent = false;
     return drained(g, send_table(g));   // a failed upload is repeated by the next svh_grid_get_trav / svh_grid_render_cost
 }
 
@@ -1247,7 +1478,7 @@ int32_t svh_grid_set_plan(svh_grid* g, const svh_grid_plan_params* p) {
     const grid::PlanParams q{p->neutral, p->unknown, p->max_cost};
     if (!grid::plan_ok(q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_plan: parameters out of range (include/svh_grid.h)");
     g->pln = q;
-    g->plan_valid = false;
+    g->plan_valid = g->reach_valid = false;
     return SVH_OK;
 }
 
@@ -1493,6 +1724,226 @@ int32_t svh_grid_render_roll(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_roll") + kNoTrav);
     if (!g->roll_last) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_roll: nothing was scored since the tables were set (svh_grid_roll_score)");
     return drained(g, render_roll(g, rgb, on_device != 0));
+}
+
+void svh_grid_explore_params_default(svh_grid_explore_params* p) {
+    if (!p) return;
+    p->range = 10.f, p->min_gain = 1, p->w_gain = 500, p->w_reach = 1;
+}
+
+int32_t svh_grid_set_explore(svh_grid* g, const svh_grid_explore_params* p) {
+    grid::ExploreParams q;
+    int32_t R = 0;
+    if (!g || !convert_explore(p, &q) || !(R = grid::explore_range(q.range, g->prm.cell)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_explore: a grid and parameters in range, with a range of 1..128 cells, are needed (include/svh_grid.h)");
+    g->exp = q, g->exp_R = R;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_explore(svh_grid* g, svh_grid_explore_params* p, int32_t* range_R) {
+    if (!g || (!p && !range_R)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_explore: a grid and an output are needed");
+    if (p) p->range = g->exp.range, p->min_gain = g->exp.min_gain, p->w_gain = g->exp.w_gain, p->w_reach = g->exp.w_reach;
+    if (range_R) *range_R = g->exp_R;
+    return SVH_OK;
+}
+
+int32_t svh_grid_view_gain(svh_grid* g, const int32_t* cells, int64_t n, int32_t on_device, int32_t* out) {
+    if (!g || n < 0 || n > ((int64_t)1 << 26) || (n > 0 && (!cells || !out)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_view_gain: a grid and 0..2^26 viewpoints with room for their gains are needed");
+    if (on_device && (((uintptr_t)cells | (uintptr_t)out) & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_view_gain: a device array must be 4-byte aligned");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_view_gain") + kNoTrav);
+    if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_view_gain") + kNoExplore);
+    if (n == 0) {
+        g->ex_stats[grid::ES_LAUNCHES] = 0;
+        return SVH_OK;
+    }
+    return explored(g, view_gain(g, cells, n, on_device != 0, out));
+}
+
+int32_t svh_grid_view_mask(svh_grid* g, int32_t ga, int32_t gb, uint8_t* out, int32_t on_device) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_view_mask: a grid and an output are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_view_mask") + kNoTrav);
+    if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_view_mask") + kNoExplore);
+    const int64_t va = (int64_t)ga - g->prm.oa, vb = (int64_t)gb - g->prm.ob;
+    if (va < 0 || va >= g->prm.nx || vb < 0 || vb >= g->prm.nz) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_view_mask: the viewpoint is outside the window");
+    return explored(g, view_mask(g, (int32_t)va, (int32_t)vb, out, on_device != 0));
+}
+
+int32_t svh_grid_explore_rank(svh_grid* g, const double start_xyz[3], int32_t* recs, int64_t* scores, int64_t cap, int64_t* n, int32_t* best) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || !n || !best || cap < 0 || !position(start_xyz, p) || !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_explore_rank: a grid, outputs, cap >= 0 and a finite start with a cell below 2^20 are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_explore_rank") + kNoTrav);
+    if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_explore_rank") + kNoExplore);
+    return explored(g, explore_rank(g, ga, gb, recs, scores, cap, n, best));
+}
+
+int32_t svh_grid_plan_set_goal_explore(svh_grid* g, const double start_xyz[3]) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || !position(start_xyz, p) || !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_plan_set_goal_explore: a grid and a finite start with a cell below 2^20 are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_plan_set_goal_explore") + kNoTrav);
+    if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_plan_set_goal_explore") + kNoExplore);
+    int64_t n = 0;
+    int32_t best = -1;
+    const int rc = explored(g, explore_rank(g, ga, gb, nullptr, nullptr, 0, &n, &best));
+    if (rc) return rc;                                 // the goals are as they were
+    if (best < 0) return 0;
+    int32_t rec[grid::EXPLORE_REC];
+    memcpy(rec, g->h_explore.p + (size_t)n * sizeof(int64_t) + (size_t)best * sizeof(rec), sizeof(rec));
+    g->goals.assign(rec + grid::ER_REP_GA, rec + grid::ER_REP_GA + 2);
+    g->goals_sent = g->plan_valid = false;
+    return 1;
+}
+
+int32_t svh_grid_get_explore_stats(svh_grid* g, int64_t out[4]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_explore_stats: null argument");
+    memcpy(out, g->ex_stats, sizeof(g->ex_stats));
+    return SVH_OK;
+}
+
+int32_t svh_grid_render_view(svh_grid* g, int32_t ga, int32_t gb, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_view: a grid and an output are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_view") + kNoTrav);
+    if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_view") + kNoExplore);
+    const int64_t va = (int64_t)ga - g->prm.oa, vb = (int64_t)gb - g->prm.ob;
+    if (va < 0 || va >= g->prm.nx || vb < 0 || vb >= g->prm.nz) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_view: the viewpoint is outside the window");
+    return explored(g, render_view(g, (int32_t)va, (int32_t)vb, rgb, on_device != 0));
+}
+
+// grid_explore_core.h on the host, on a caller's STATE and COST planes (nx x nz, offsets oa, ob), with R from e->range and `cell`.
+// Three things, each optional: GAIN of n_cells global cells to gains; for the global cell view[2], inside the window, its VIEW
+// plane to mask (nx * nz) and drawn over rgb (nx * nz * 3, the layout of svh_grid_render_cost, changed in place); from the global
+// cell start[2] the ranking: *n records, the first min(*n, cap) to recs (5 each) and scores, *best, stats[0] the records and
+// stats[1] the feasible ones.  Needs no device
+int32_t svh_test_grid_explore(const svh_grid_front_params* f, const svh_grid_plan_params* pl, const svh_grid_explore_params* e, float cell, int32_t nx,
+                              int32_t nz, int32_t oa, int32_t ob, const uint8_t* state, const uint8_t* cost, const int32_t* cells, int64_t n_cells,
+                              int32_t* gains, const int32_t* view, uint8_t* mask, uint8_t* rgb, const int32_t* start, int32_t* recs,
+                              int64_t* scores, int64_t cap, int64_t* n, int32_t* best, int64_t* stats) {
+    grid::FrontParams fq;
+    grid::PlanParams pq{50, -1, 0x7FFFFFFE};
+    grid::ExploreParams eq;
+    int32_t R = 0;
+    if (!explore_test_args(f, pl, e, cell, nx, nz, oa, ob, state, cost, cells, n_cells, gains, view, start, recs, scores, cap, n, best, &fq, &pq, &eq, &R))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_explore: bad arguments");
+    if (n_cells > 0) grid::gain_window(fq, R, nx, nz, oa, ob, state, cells, n_cells, gains);
+    if (view && (mask || rgb)) {
+        std::vector<uint8_t> v((size_t)nx * (size_t)nz);
+        grid::view_window(fq, R, nx, nz, state, view[0] - oa, view[1] - ob, v.data());
+        if (mask) memcpy(mask, v.data(), v.size());
+        if (rgb) view_overlay_host(nx, nz, v.data(), view[0] - oa, view[1] - ob, rgb);
+    }
+    if (start) {
+        std::vector<int32_t> r;
+        std::vector<int64_t> sc;
+        int64_t feasible = 0;
+        *best = grid::explore_window(fq, pq, eq, R, nx, nz, oa, ob, state, cost, start[0], start[1], &r, &sc, &feasible);
+        const size_t give = std::min(sc.size(), (size_t)cap);
+        if (recs && give) memcpy(recs, r.data(), give * grid::EXPLORE_REC * sizeof(int32_t));
+        if (scores && give) memcpy(scores, sc.data(), give * sizeof(int64_t));
+        *n = (int64_t)sc.size();
+        if (stats) stats[0] = (int64_t)sc.size(), stats[1] = feasible;
+    }
+    return SVH_OK;
+}
+
+// the same through the kernels: the planes go to the device, the frontiers by front_run, the reach field by plan_run
+int32_t svh_test_grid_explore_device(const svh_grid_front_params* f, const svh_grid_plan_params* pl, const svh_grid_explore_params* e, float cell,
+                                     int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* state, const uint8_t* cost, const int32_t* cells,
+                                     int64_t n_cells, int32_t* gains, const int32_t* view, uint8_t* mask, uint8_t* rgb, const int32_t* start,
+                                     int32_t* recs, int64_t* scores, int64_t cap, int64_t* n, int32_t* best, int64_t* stats) {
+    grid::FrontParams fq;
+    grid::PlanParams pq{50, -1, 0x7FFFFFFE};
+    grid::ExploreParams eq;
+    int32_t R = 0;
+    if (!explore_test_args(f, pl, e, cell, nx, nz, oa, ob, state, cost, cells, n_cells, gains, view, start, recs, scores, cap, n, best, &fq, &pq, &eq, &R))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_explore_device: bad arguments");
+    svh::ensure_init();
+    const size_t ncells = (size_t)nx * (size_t)nz;
+    HipBuf<uint8_t> in, d_view, d_rgb, planes, field;
+    HipBuf<int32_t> d_cells, d_gain, d_start;
+    HipBuf<uint32_t> d_tiles, d_ctl;
+    PinnedBuf<uint32_t> h_ctl;
+    FrontBufs fbufs;
+    ExploreBufs ebufs;
+    int32_t out[2] = {-1, 0}, m = 0;
+    hipStream_t s = nullptr;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(in, 2 * ncells);
+        GRID_TRY(copy, hipMemcpyAsync(in, state, ncells, hipMemcpyHostToDevice, s));
+        if (cost) GRID_TRY(copy, hipMemcpyAsync(in + ncells, cost, ncells, hipMemcpyHostToDevice, s));
+        grid::ExploreJob j = explore_job(eq, fq, R, nx, nz, oa, ob, in.p);
+        if (n_cells > 0) {
+            GRID_GROW_N(d_cells, 2 * n_cells);
+            GRID_GROW_N(d_gain, n_cells);
+            GRID_TRY(copy, hipMemcpyAsync(d_cells, cells, (size_t)n_cells * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            GRID_TRY(launch, (grid::launch_view_gain(s, j, d_cells, 2, n_cells, d_gain), hipGetLastError()));
+            GRID_TRY(copy, hipMemcpyAsync(gains, d_gain, (size_t)n_cells * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        if (view && (mask || rgb)) {
+            const int32_t va = view[0] - oa, vb = view[1] - ob;
+            GRID_GROW(d_view, ncells);
+            GRID_TRY(copy, hipMemsetAsync(d_view, 0, ncells, s));
+            GRID_TRY(launch, (grid::launch_view_mask(s, j, va, vb, d_view), hipGetLastError()));
+            if (mask) GRID_TRY(copy, hipMemcpyAsync(mask, d_view, ncells, hipMemcpyDeviceToHost, s));
+            if (rgb) {
+                GRID_GROW(d_rgb, 3 * ncells);
+                GRID_TRY(copy, hipMemcpyAsync(d_rgb, rgb, 3 * ncells, hipMemcpyHostToDevice, s));
+                GRID_TRY(launch, (grid::launch_view_overlay(s, nx, nz, d_view, va, vb, d_rgb), hipGetLastError()));
+                GRID_TRY(copy, hipMemcpyAsync(rgb, d_rgb, 3 * ncells, hipMemcpyDeviceToHost, s));
+            }
+        }
+        if (start) {
+            grid::FrontJob fj;
+            fj.frp = fq;
+            fj.nx = nx, fj.nz = nz, fj.oa = oa, fj.ob = ob;
+            fj.state = in.p, fj.cost = in.p + ncells;
+            GRID_GROW(planes, ncells * kFrontBytes);
+            fj.label = (int32_t*)planes.p, fj.flags = planes.p + 4 * ncells;
+            int64_t st[grid::FS_WORDS] = {0, 0, 0, 0, 0};
+            int r = front_run(s, fj, fbufs, st);
+            if (r) return r;
+            m = (int32_t)std::min<int64_t>(st[grid::FS_KEPT], grid::EXPLORE_MAX_RECORDS);
+            grid::PlanJob pj;
+            pj.pln = pq;
+            pj.nx = nx, pj.nz = nz, pj.oa = oa, pj.ob = ob, pj.n_goals = 1;
+            const size_t tiles = (size_t)grid::plan_tiles_x(pj) * grid::plan_tiles_y(pj);
+            GRID_GROW(field, ncells * kPlanBytes);
+            GRID_GROW_N(d_start, 2);
+            GRID_GROW(d_tiles, 4 * tiles * sizeof(uint32_t));
+            GRID_GROW(d_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+            GRID_GROW(h_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+            GRID_TRY(copy, hipMemcpyAsync(d_start, start, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            pj.cost = in.p + ncells;
+            pj.pot = (int32_t*)field.p, pj.price = (uint16_t*)(field.p + 4 * ncells), pj.dir = field.p + 6 * ncells;
+            pj.goals = d_start.p;
+            pj.lists = d_tiles.p, pj.flags = d_tiles.p + 2 * tiles;
+            pj.ctl = d_ctl.p;
+            if ((r = plan_run(s, pj, h_ctl))) return r;
+            if ((r = explore_outputs(ebufs, m, j))) return r;
+            j.front_recs = fj.recs, j.pot = pj.pot;
+            GRID_TRY(launch, (grid::launch_explore_rank(s, j), hipGetLastError()));
+            const size_t give = (size_t)std::min<int64_t>(m, cap);
+            if (recs && give) GRID_TRY(copy, hipMemcpyAsync(recs, j.recs, give * grid::EXPLORE_REC * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            if (scores && give) GRID_TRY(copy, hipMemcpyAsync(scores, j.scores, give * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            GRID_TRY(copy, hipMemcpyAsync(out, j.out, sizeof(out), hipMemcpyDeviceToHost, s));
+        }
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    if (start) {
+        *n = m, *best = out[0];
+        if (stats) stats[0] = m, stats[1] = out[1];
+    }
+    return SVH_OK;
 }
 
 // grid_roll_core.h on the host.  The footprint table for a cell side: *R, *total cells of all lists, and (k >= 0) the list of heading

@@ -1,5 +1,6 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
-// csrc/grid_front_kernels.hip / csrc/grid_roll_kernels.hip: the launches of the ground grid (include/svh_grid.h).
+// csrc/grid_front_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_explore_kernels.hip: the launches of the ground grid
+// (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
 
@@ -7,6 +8,7 @@
 #include <hip/hip_vector_types.h>
 
 #include "grid_core.h"
+#include "grid_explore_core.h"
 #include "grid_front_core.h"
 #include "grid_plan_core.h"
 #include "grid_roll_core.h"
@@ -251,6 +253,36 @@ void launch_footprint_cost(hipStream_t s, const RollJob& j, const int32_t* poses
 // the reference cells of the poses before the cut of every candidate, then of `best` (>= 0) over them, drawn into an image of
 // svh_grid_render_cost's layout from the records in j.recs
 void launch_roll_overlay(hipStream_t s, const RollJob& j, int32_t best, uint8_t* rgb);
+
+// The exploration layer (csrc/grid_explore_kernels.hip): the finished STATE plane, the frontier table and the reach field -> GAIN of
+// viewpoints, the VIEW plane of one, the records, the scores and the best.
+constexpr uint32_t VIEW_BLOCK = 256;             // k_grid_view_gain: one workgroup per viewpoint, its rays dealt to the lanes
+constexpr int64_t VIEW_MAX_BLOCKS = 16384;       // ... the workgroups stride over the viewpoints beyond this many
+constexpr uint32_t EXPLORE_BEST_BLOCK = 1024;    // k_grid_explore_best: one workgroup
+
+struct ExploreJob {
+    ExploreParams exp;
+    FrontParams frp;            // what counts as unexplored
+    int32_t R;                  // explore_range(exp.range, cell), 1..128
+    int32_t nx, nz, oa, ob;
+    const uint8_t* state;       // the finished STATE plane
+    // a ranking
+    const int32_t* front_recs = nullptr;   // the frontier table, FRONT_REC per kept component
+    int32_t n = 0;              // its first min(kept, EXPLORE_MAX_RECORDS) records
+    const int32_t* pot = nullptr;   // the reach field: POT with the start as the only goal
+    int32_t* gain = nullptr;    // n
+    int32_t* recs = nullptr;    // EXPLORE_REC per record
+    long long* scores = nullptr;
+    int32_t* out = nullptr;     // [0] the best, [1] the feasible records
+};
+// GAIN of n viewpoints, global cells at cells[i * stride], cells[i * stride + 1]; returns the kernels it launched
+int32_t launch_view_gain(hipStream_t s, const ExploreJob& j, const int32_t* cells, int32_t stride, int64_t n, int32_t* out);
+// the VIEW plane of the window viewpoint (va, vb), inside the window, into a plane that is all zero
+void launch_view_mask(hipStream_t s, const ExploreJob& j, int32_t va, int32_t vb, uint8_t* view);
+// gains of the representatives, records and scores, the best: three launches (one when n == 0); returns those of the gains
+int32_t launch_explore_rank(hipStream_t s, const ExploreJob& j);
+// a VIEW plane and its viewpoint drawn over an image of svh_grid_render_cost's layout
+void launch_view_overlay(hipStream_t s, int32_t nx, int32_t nz, const uint8_t* view, int32_t va, int32_t vb, uint8_t* rgb);
 
 }  // namespace grid
 }  // namespace svh

@@ -1,7 +1,7 @@
 """ctypes binding of the ground grid in libsvhip.so (C-ABI: include/svh_grid.h): a 2.5-D bird's-eye grid over the road
 plane -- per cell how many points, how high, how bright, drivable or not -- binned on the device from the map view's store
 or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h, grid_plan_core.h, grid_front_core.h and
-grid_roll_core.h."""
+grid_roll_core.h; that of the exploration layer grid_explore_core.h."""
 import ctypes as C
 
 import numpy as np
@@ -39,6 +39,11 @@ ROLL_FIELDS = ("len", "status", "max_f", "sum_f", "pot_end")
 ROLL_COMPLETE, ROLL_CUT_COST, ROLL_CUT_WINDOW, ROLL_EMPTY = range(4)
 ROLL_INFEASIBLE = 2 ** 63 - 1
 ROLL_COLOUR, ROLL_BEST_COLOUR = (0, 192, 255), (255, 255, 255)
+EXPLORE_RECORD = 5
+EXPLORE_FIELDS = ("label", "rep_ga", "rep_gb", "gain", "reach")
+EXPLORE_INFEASIBLE = 2 ** 63 - 1
+VIEW_NONE, VIEW_VISITED, VIEW_COUNTED = range(3)
+VIEW_COLOUR, VIEWPOINT_COLOUR = (255, 0, 255), (255, 255, 255)
 
 
 class Params(C.Structure):
@@ -106,6 +111,20 @@ class RollParams(C.Structure):
 
     def copy(self, **kw):
         q = RollParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ExploreParams(C.Structure):
+    """svh_grid_explore_params"""
+    _fields_ = [("range", C.c_float), ("min_gain", C.c_int32), ("w_gain", C.c_int32), ("w_reach", C.c_int32)]
+
+    def copy(self, **kw):
+        q = ExploreParams.from_buffer_copy(bytes(self))
         for k, v in kw.items():
             setattr(q, k, v)
         return q
@@ -212,6 +231,20 @@ def _bind():
         L.svh_test_grid_roll.argtypes = roll
         L.svh_test_grid_roll_device.argtypes = roll
         L.svh_test_grid_roll_group.argtypes = [C.c_int64]
+        L.svh_grid_explore_params_default.argtypes = [C.POINTER(ExploreParams)]
+        L.svh_grid_explore_params_default.restype = None
+        L.svh_grid_set_explore.argtypes = [C.c_void_p, C.POINTER(ExploreParams)]
+        L.svh_grid_get_explore.argtypes = [C.c_void_p, C.POINTER(ExploreParams), C.c_void_p]
+        L.svh_grid_view_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.svh_grid_view_mask.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_explore_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.svh_grid_plan_set_goal_explore.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_get_explore_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_render_view.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        explore = ([C.POINTER(FrontParams), C.POINTER(PlanParams), C.POINTER(ExploreParams), C.c_float] + [C.c_int32] * 4 + [C.c_void_p] * 3 +
+                   [C.c_int64] + [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 3)
+        L.svh_test_grid_explore.argtypes = explore
+        L.svh_test_grid_explore_device.argtypes = explore
         L._grid_bound = True
     return L
 
@@ -528,6 +561,58 @@ def roll_group(longest):
     return int(_bind().svh_test_grid_roll_group(longest))
 
 
+def default_explore(**kw):
+    p = ExploreParams()
+    _bind().svh_grid_explore_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def _explore(entry, explore, cell, state, cost, front, plan, oa, ob, cells, view, rgb, start):
+    s = np.ascontiguousarray(state, np.uint8)
+    nz, nx = s.shape
+    c = None if cost is None else np.ascontiguousarray(cost, np.uint8).reshape(nz, nx)
+    front = front if front is not None else default_front()
+    plan = plan if plan is not None else default_plan()
+    out = {}
+    q = np.ascontiguousarray(cells if cells is not None else np.zeros((0, 2)), np.int32).reshape(-1, 2)
+    gains = np.zeros(len(q), np.int32)
+    v = None if view is None else np.ascontiguousarray(view, np.int32).reshape(2)
+    mask = None if view is None else np.zeros((nz, nx), np.uint8)
+    img = None if (view is None or rgb is None) else np.array(rgb, np.uint8).reshape(nz, nx, 3)
+    st = None if start is None else np.ascontiguousarray(start, np.int32).reshape(2)
+    cap = ((nx + 1) // 2) * ((nz + 1) // 2) if start is not None else 0
+    recs, scores = np.zeros((max(cap, 1), EXPLORE_RECORD), np.int32), np.zeros(max(cap, 1), np.int64)
+    n, best, stats = C.c_int64(-1), C.c_int32(-9), np.zeros(2, np.int64)
+    _check(entry(C.byref(front), C.byref(plan), C.byref(explore), cell, nx, nz, oa, ob, s.ctypes.data, None if c is None else c.ctypes.data,
+                 q.ctypes.data if len(q) else None, len(q), gains.ctypes.data if len(q) else None,
+                 None if v is None else v.ctypes.data, None if mask is None else mask.ctypes.data, None if img is None else img.ctypes.data,
+                 None if st is None else st.ctypes.data, recs.ctypes.data if cap else None, scores.ctypes.data if cap else None, cap,
+                 C.addressof(n), C.addressof(best), stats.ctypes.data))
+    if cells is not None:
+        out.update(gains=gains)
+    if view is not None:
+        out.update(mask=mask)
+        if img is not None:
+            out.update(image=img)
+    if start is not None:
+        out.update(recs=recs[:n.value].copy(), scores=scores[:n.value].copy(), best=best.value, stats=tuple(int(x) for x in stats))
+    return out
+
+
+def core_explore(explore, cell, state, cost=None, front=None, plan=None, oa=0, ob=0, cells=None, view=None, rgb=None, start=None):
+    """the exploration layer of csrc/grid_explore_core.h on the host (svh_test_grid_explore) on STATE and COST planes [nz, nx] under the
+    offsets (oa, ob), R from explore.range and `cell`.  A dict: with cells int32 [n, 2] (global) their GAIN as gains; with view, a
+    global cell inside the window, its VIEW plane as mask and (with rgb, an image [nz, nx, 3] whose row 0 is ib = nz - 1) the overlay as
+    image; with start, a global cell, the ranking: recs int32 [n, 5], scores int64 [n], best, stats (records, feasible).  Needs no
+    device"""
+    return _explore(_bind().svh_test_grid_explore, explore, cell, state, cost, front, plan, oa, ob, cells, view, rgb, start)
+
+
+def device_explore(explore, cell, state, cost=None, front=None, plan=None, oa=0, ob=0, cells=None, view=None, rgb=None, start=None):
+    """TEST ENTRY: the same through the device kernels on a caller's planes"""
+    return _explore(_bind().svh_test_grid_explore_device, explore, cell, state, cost, front, plan, oa, ob, cells, view, rgb, start)
+
+
 def __getattr__(name):
     if name == "PLAN_TILE":
         return plan_tile()
@@ -842,6 +927,71 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_roll(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_explore(self, params=None, **kw):
+        """the exploration parameters in force (or `params`) with the fields of kw replaced: range, min_gain, w_gain, w_reach"""
+        p = (params if params is not None else self.explore_params()[0]).copy(**kw)
+        _check(self._L.svh_grid_set_explore(self._h, C.byref(p)))
+
+    def explore_params(self):
+        """(ExploreParams in force, their range R in cells; 0 while the defaults do not fit the grid's cell)"""
+        p, R = ExploreParams(), C.c_int32(-1)
+        _check(self._L.svh_grid_get_explore(self._h, C.byref(p), C.addressof(R)))
+        return p, R.value
+
+    def view_gain(self, cells=None, device_ptrs=None, n=None):
+        """GAIN int32 [n] of viewpoints int32 [n, 2], global cells (-1: outside the window); with device_ptrs = (cells, out) and n both
+        lie on the device and None is returned"""
+        if device_ptrs is not None:
+            _check(self._L.svh_grid_view_gain(self._h, device_ptrs[0], n, 1, device_ptrs[1]))
+            return None
+        q = np.ascontiguousarray(cells, np.int32).reshape(-1, 2)
+        out = np.zeros(len(q), np.int32)
+        _check(self._L.svh_grid_view_gain(self._h, q.ctypes.data if len(q) else None, len(q), 0, out.ctypes.data if len(q) else None))
+        return out
+
+    def view_mask(self, ga, gb, device_ptr=None):
+        """the VIEW plane uint8 [nz, nx] of the viewpoint (ga, gb), a global cell inside the window: VIEW_NONE, VIEW_VISITED,
+        VIEW_COUNTED; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_view_mask(self._h, ga, gb, device_ptr, 1))
+            return None
+        out = np.zeros((self.nz, self.nx), np.uint8)
+        _check(self._L.svh_grid_view_mask(self._h, ga, gb, out.ctypes.data, 0))
+        return out
+
+    def explore_rank(self, start_xyz, cap=None):
+        """(best, recs int32 [n, 5] in the order of EXPLORE_FIELDS, scores int64 [n]) of the kept frontier components ranked from the
+        cell of a map-frame position; with cap only the first, and the count of all is in `explore_count`"""
+        n, best = C.c_int64(-1), C.c_int32(-9)
+        room = 65536 if cap is None else int(cap)
+        recs, scores = np.zeros((max(room, 1), EXPLORE_RECORD), np.int32), np.zeros(max(room, 1), np.int64)
+        _check(self._L.svh_grid_explore_rank(self._h, _xyz(start_xyz).ctypes.data, recs.ctypes.data if room else None,
+                                             scores.ctypes.data if room else None, room, C.addressof(n), C.addressof(best)))
+        self.explore_count = n.value
+        m = min(n.value, room)
+        return best.value, recs[:m].copy(), scores[:m].copy()
+
+    def set_goal_explore(self, start_xyz):
+        """ranks from the cell of a map-frame position and makes the best record's representative the planner's only goal: 1, or 0
+        when there is no best (the goals are then left alone)"""
+        return _check(self._L.svh_grid_plan_set_goal_explore(self._h, _xyz(start_xyz).ctypes.data))
+
+    def explore_stats(self):
+        """(records of the last ranking, feasible records, reach fields computed since create, launches of the last gain computation)"""
+        out = np.zeros(4, np.int64)
+        _check(self._L.svh_grid_get_explore_stats(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def render_view(self, ga, gb, device_ptr=None):
+        """render_frontiers with the VIEW plane of the viewpoint (ga, gb) over it: counted cells in VIEW_COLOUR, visited cells
+        brightened, the viewpoint in VIEWPOINT_COLOUR"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_view(self._h, ga, gb, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_view(self._h, ga, gb, img.ctypes.data, 0))
         return img
 
     def stats(self):

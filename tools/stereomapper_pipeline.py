@@ -20,6 +20,7 @@ without the GUI.  Usage:
                                          [--grid-plan DIR [--grid-goal-ahead M]]
                                          [--grid-roll DIR [--grid-roll-vehicle FRONT,REAR,HALFWIDTH] [--grid-roll-unknown N]]
                                           [--grid-frontiers DIR [--grid-unexplored unseen|seen|both] [--grid-frontier-min N]]
+                                          [--grid-explore DIR [--grid-explore-range M]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -105,6 +106,16 @@ white over it) goes into DIR/frontiers_%06d.ppm and one line {"frame", "frontier
 "length", "cost"} per frame is appended to DIR/frontiers.jsonl.  --grid-unexplored: which unknown cells count as unexplored:
 those no ray passed (unseen, the default), those that rays passed and that hold no ground (seen), or both.
 --grid-frontier-min N: components of fewer than N cells are dropped (8).  May be given with --grid-plan; it runs after it.
+
+--grid-explore DIR: needs --grid-cost; --grid-unexplored and --grid-frontier-min apply to it too.  After every local step the kept
+frontier components are ranked from the camera's cell (svh_grid_explore_rank: for each representative the unexplored cells it
+would see within --grid-explore-range M metres, 10 by default, and the cost of the path to it; score = reach - 500 gain), the
+best one becomes the planner's only goal (svh_grid_plan_set_goal_explore) and the path to it is walked.  The image
+(svh_grid_render_view of the chosen representative: the frontier image with the cells it would count magenta, the cells it sees
+brightened, itself white; the path white over it; the plain frontier image when nothing is feasible) goes into
+DIR/explore_%06d.ppm and one line {"frame", "kept", "records", "feasible", "best", "rep", "gain", "reach", "score", "status",
+"length", "cost"} per frame is appended to DIR/explore.jsonl (rep, gain, reach and score null, status -1 when there is no best).
+It runs last: the goal it sets is the one the next frame's --grid-plan replaces.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -258,6 +269,23 @@ class Pipeline:
         for ga, gb in cells:                                     # global cells of the window: row 0 is the farthest
             img[g.nz - 1 - (gb - ob), ga - oa] = (255, 255, 255)
         return stats, status, cells, cost, img
+
+    def explore_step(self):
+        """the kept frontier components ranked from the camera's cell, the best one as the planner's goal, the path to it:
+        (kept, best, recs [n, 5], scores [n], status, cells [n, 2], cost, the view image of the chosen representative with the path
+        over it [nz, nx, 3]); status -1, no cells: nothing is feasible"""
+        g = self.local
+        centre = self.H_total[:3, 3].copy()
+        kept = g.frontier_stats()[2]
+        best, recs, scores = g.explore_rank(centre)
+        status, cells, cost = -1, np.zeros((0, 2), np.int32), 0x7FFFFFFF
+        if g.set_goal_explore(centre):
+            status, cells, cost = g.path(centre)
+        img = g.render_view(int(recs[best, 1]), int(recs[best, 2])) if best >= 0 else g.render_frontiers()
+        oa, ob = g.window()
+        for ga, gb in cells:                                     # global cells of the window: row 0 is the farthest
+            img[g.nz - 1 - (gb - ob), ga - oa] = (255, 255, 255)
+        return kept, best, recs, scores, status, cells, cost, img
 
     def local_step(self):
         """follow the camera centre to the middle cell, add the newest list with rays from it, render: [nz, nx, 3]"""
@@ -536,6 +564,7 @@ def main():
     grid_dir, grid_cell, grid_size = None, 0.2, (256, 256)
     local_dir, cost_dir, cost_kw = None, None, {}
     plan_dir, goal_ahead, front_dir, front_kw = None, None, None, {}
+    explore_dir, explore_kw = None, {}
     roll_dir, roll_kw = None, {}
     level = "--level" in sys.argv
     if level:
@@ -605,9 +634,20 @@ def main():
             front_kw["min_size"] = int(sys.argv[k + 1])
             assert 1 <= front_kw["min_size"] <= 1 << 26
             del sys.argv[k:k + 2]
+        if "--grid-explore" in sys.argv:
+            k = sys.argv.index("--grid-explore")
+            explore_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-explore-range" in sys.argv:
+            k = sys.argv.index("--grid-explore-range")
+            explore_kw["range"] = float(sys.argv[k + 1])
+            assert 0 < explore_kw["range"] < float("inf")
+            del sys.argv[k:k + 2]
         assert cost_dir or not plan_dir
         assert cost_dir or not front_dir
-        assert front_dir or not front_kw
+        assert cost_dir or not explore_dir
+        assert front_dir or explore_dir or not front_kw
+        assert explore_dir or not explore_kw
         assert plan_dir or goal_ahead is None
         assert plan_dir or not roll_dir
         assert roll_dir or not roll_kw
@@ -679,6 +719,9 @@ def main():
     if roll_dir:
         os.makedirs(roll_dir, exist_ok=True)
         open(os.path.join(roll_dir, "roll.jsonl"), "w").close()
+    if explore_dir:
+        os.makedirs(explore_dir, exist_ok=True)
+        open(os.path.join(explore_dir, "explore.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -689,13 +732,15 @@ def main():
         p.enable_grid_local(grid_cell, grid_size)
     if cost_dir:
         p.set_grid_cost(**cost_kw)
-    if plan_dir or front_dir:
+    if plan_dir or front_dir or explore_dir:
         p.local.set_plan(unknown=100)
     if front_kw:
         p.local.set_frontier(**front_kw)
+    if explore_kw:
+        p.local.set_explore(**explore_kw)
     if roll_dir:
         p.enable_roll(ROLL_CURVATURES, 2.0 * grid_cell, ROLL_POSES, **roll_kw)
-    found = explored = rolled = 0
+    found = explored = rolled = ranked = 0
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -735,6 +780,16 @@ def main():
             with open(os.path.join(front_dir, "frontiers.jsonl"), "a") as f:
                 f.write(json.dumps({"frame": frames - 1, "frontier_cells": stats[0], "components": stats[1], "kept": stats[2],
                                     "status": int(status), "length": int(len(cells)), "cost": int(cost)}) + "\n")
+        if explore_dir:
+            kept, best, recs, scores, status, cells, cost, img = p.explore_step()
+            ranked += best >= 0
+            view.write_ppm(os.path.join(explore_dir, "explore_%06d.ppm" % (frames - 1)), img)
+            with open(os.path.join(explore_dir, "explore.jsonl"), "a") as f:
+                f.write(json.dumps({"frame": frames - 1, "kept": int(kept), "records": int(len(recs)), "feasible": int((scores != (1 << 63) - 1).sum()),
+                                    "best": int(best), "rep": [int(recs[best, 1]), int(recs[best, 2])] if best >= 0 else None,
+                                    "gain": int(recs[best, 3]) if best >= 0 else None, "reach": int(recs[best, 4]) if best >= 0 else None,
+                                    "score": int(scores[best]) if best >= 0 else None, "status": int(status), "length": int(len(cells)),
+                                    "cost": int(cost)}) + "\n")
         if frames >= limit:
             break
     dt = time.perf_counter() - t0
@@ -763,6 +818,9 @@ def main():
     if front_dir:
         print("frontiers: goals from the kept components, a route in %d of %d frames; %d images and frontiers.jsonl in %s" % (
             explored, frames, frames, front_dir))
+    if explore_dir:
+        print("exploration: the kept frontiers ranked within %d cells, a best one in %d of %d frames; %d images and explore.jsonl in %s" % (
+            p.local.explore_params()[1], ranked, frames, frames, explore_dir))
     if render_dir:
         n, images = p.view.record_human()
         for k in range(n):
