@@ -138,6 +138,47 @@
  * cost planes, the goals, the field, the frontier result and the roll tables are untouched; the reach field is invalid and the
  * next ranking computes it again.
  *
+ * ALIGN: where a frame's obstacle points fit the obstacle cells the window already holds -- correlative scan-to-map matching over a
+ * small window of pose corrections.  A FRAME IS ALIGNED BEFORE IT IS ADDED: a frame already in the grid matches itself.  The
+ * arithmetic is stereo-vision_amd/csrc/grid_align_core.h (restated in tests/grid_align_ref.py); after the fp32 placement of a point
+ * it is integer arithmetic on the finished STATE plane.
+ *   SUBS.  A sub is a quarter of a cell per axis.  The global sub of a ground position (a, b) is ua = (int)floorf(((a - x0) / cell)
+ *   * 4), ub likewise with z0, fp32 with one rounding per operation; a position has one iff |floorf((a - x0) / cell)| < 2^20 on
+ *   both axes, and ua >> 2 is its global cell.
+ *   PIVOT.  A map-frame position (the camera's), rounded to float once; its global sub is (Pa, Pb).  It need not lie inside the
+ *   window.  A pivot that is not finite or has no sub is SVH_ERR_BAD_ARG before anything is read or changed.
+ *   SCAN.  A point is a scan point iff x, y, z, a, b, h are finite, |h| < 2^20, step < h <= clearance -- what would make its cell
+ *   an obstacle -- and it has a global sub.  With Rg = floor(range / cell) in 1..256 it is kept iff |ua - Pa| <= 4 Rg and
+ *   |ub - Pb| <= 4 Rg.  The scan is the SET of distinct kept subs: it depends on neither order nor multiplicity.  n_scan is its
+ *   size, at most (8 Rg + 1)^2.  It may hold subs outside the window.
+ *   FIELD.  F, one byte per window cell: with reach_cells = ceil(reach / cell) in 1..32, R2 = reach_cells^2 and d2 the exact squared
+ *   distance in cells to the nearest obstacle cell (bits 0-1 of STATE) of the window, F = (255 (R2 + 1 - d2)) / (R2 + 1) in integer
+ *   division for d2 <= R2, else 0.  It reads neither the traversability nor the cost planes.  Cached until the accumulators, the
+ *   window's offsets or the align parameters change.
+ *   SAMPLE.  F at a global sub is bilinear between cell centres in eighths of a cell: pa = 2 ua - 3 - 8 oa, g0a = pa >> 3
+ *   (arithmetic), fa = pa - 8 g0a in {1, 3, 5, 7}, the b axis alike; the cells (g0a + i, g0b + j), i, j in {0, 1}, weigh
+ *   (i ? fa : 8 - fa) (j ? fb : 8 - fb), a cell outside the window contributes 0, and the sample is (sum + 32) >> 6, 0..255.
+ *   CANDIDATES (k, ta, tb): k in -K..K (K = rot_n), ta, tb in -W..W subs (W = trans_n).  Rotation k turns by the direction (D, k),
+ *   D = rot_den, from the a axis towards the b axis: n = sqrt(D D + k k), cq = rint(16384 D / n), sq = rint(16384 k / n) in double.
+ *   A scan sub with (ra, rb) = (ua - Pa, ub - Pb) is placed at (Pa + ((cq ra - sq rb + 8192) >> 14) + ta,
+ *   Pb + ((sq ra + cq rb + 8192) >> 14) + tb).  k = 0 is the identity.
+ *   VOLUME AND BEST.  SCORE(k, ta, tb) is the int32 sum of the samples over the scan, stored as [k + K][tb + W][ta + W].  The best
+ *   is the greatest score; among equal scores the least k^2 + ta^2 + tb^2, among those the lowest volume index.  `ties` counts the
+ *   candidates whose score equals the best: it is how a caller sees the aperture problem of a single straight wall.  A flat volume
+ *   returns the identity.  No byte depends on launch shape or scheduling.
+ *   RECORD, eight int32: status, k, ta, tb, score, SCORE(0, 0, 0), n_scan, ties.  SVH_GRID_ALIGN_FEW: n_scan < min_scan, no volume is
+ *   computed, k = ta = tb = score = identity = ties = 0.  SVH_GRID_ALIGN_FLAT: the best score is 0 -- the map has no obstacle within
+ *   reach of any candidate -- and the identity is returned.
+ *   CORRECTION.  svh_grid_align_correction turns (k, ta, tb) and the pivot into a map-frame transform M, on the host in double from
+ *   the float-rounded T and pivot: X' = p + Rot(X - p) + (ta cell / 4) e_a + (tb cell / 4) e_b, with e_a, e_b, e_h the first three
+ *   columns of T's rows and Rot turning the e_a / e_b components by (cos, sin) = (D / n, k / n).  Exact for a T with orthonormal
+ *   rows, which svh_grid_frame_camera and svh_grid_frame_plane give.  A caller multiplies its camera pose by M before it adds the
+ *   frame.
+ * The align entries return SVH_ERR_BAD_ARG while the align parameters are not set.  An alignment changes nothing else: the
+ * accumulators, the statistics, the cost planes, the goals, the planner's field, the frontier result, the roll tables and the reach
+ * field stay as they were.  After SVH_ERR_HIP in an align entry the same holds; the align field and the last volume are invalid and
+ * the next call computes them again.
+ *
  * Plain C like svh_view.h.  An object has its own stream and every call returns when it is complete.  Calls return
  * SVH_OK or a negative SVH_ERR_*; svh_last_error() has the text.  SVH_ERR_BAD_ARG -- a null pointer, parameters out of
  * the ranges below, n < 0, n > 0 with a null array, a device array that is not 16-byte aligned, an unknown plane or
@@ -430,6 +471,42 @@ int32_t   svh_grid_get_explore_stats(svh_grid* g, int64_t out[4]);
 /* svh_grid_render_frontiers with the VIEW plane of the viewpoint (ga, gb) over it: counted cells (255, 0, 255), visited cells
  * brightened (c + (255 - c) / 2 per byte), the viewpoint (255, 255, 255).  SVH_ERR_BAD_ARG: the viewpoint is outside the window */
 int32_t   svh_grid_render_view(svh_grid* g, int32_t ga, int32_t gb, uint8_t* rgb, int32_t on_device);
+
+typedef struct svh_grid_align_params {
+    float   reach;      /* 0.6: metres; the field is 0 beyond; ceil(reach / cell) in 1..32 */
+    float   range;      /* 25.6: metres; half side of the box of scan subs about the pivot; floor(range / cell) in 1..256 */
+    int32_t rot_den;    /* 256: D, 16..4096; rotation k is the direction (D, k) */
+    int32_t rot_n;      /* 8: K, 0..32 */
+    int32_t trans_n;    /* 8: W in subs (quarter cells), 0..32 */
+    int32_t min_scan;   /* 32: fewer distinct scan subs than this -> SVH_GRID_ALIGN_FEW; >= 1 */
+} svh_grid_align_params;
+
+#define SVH_GRID_ALIGN_RECORD 8        /* int32 per record: status, k, ta, tb, score, identity score, n_scan, ties */
+#define SVH_GRID_ALIGN_OK     0
+#define SVH_GRID_ALIGN_FEW    1
+#define SVH_GRID_ALIGN_FLAT   2
+
+void      svh_grid_align_params_default(svh_grid_align_params* p);
+/* SVH_ERR_BAD_ARG, nothing changed: a parameter out of its range for this grid's cell.  A grid is created WITHOUT align parameters:
+ * every other align entry returns SVH_ERR_BAD_ARG until this call succeeds.  A success forgets the last alignment */
+int32_t   svh_grid_set_align(svh_grid* g, const svh_grid_align_params* p);
+/* the field F: nx * nz bytes laid out as the planes of svh_grid_get */
+int32_t   svh_grid_get_align_field(svh_grid* g, uint8_t* out, int32_t on_device);
+/* aligns n >= 0 points (x, y, z, val), on the host or (on_device, 16-byte aligned) in device memory, about the map-frame position
+ * `pivot`: the record to rec (host memory).  Nothing is added to the grid */
+int32_t   svh_grid_align_points(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device, const double pivot[3], int32_t rec[8]);
+/* ... the points of n_lists lists of the view, from first_list on, as svh_grid_add_view_lists_from takes them */
+int32_t   svh_grid_align_view_lists(svh_grid* g, svh_view* v, int32_t first_list, int32_t n_lists, const double pivot[3], int32_t rec[8]);
+/* the volume of the last alignment, (2 K + 1) (2 W + 1)^2 int32 as [k + K][tb + W][ta + W]; SVH_ERR_BAD_ARG if there is none: no
+ * alignment since svh_grid_set_align, the last one failed or was SVH_GRID_ALIGN_FEW */
+int32_t   svh_grid_get_align_volume(svh_grid* g, int32_t* out, int32_t on_device);
+/* the scan of the last alignment: *n = n_scan, the first min(*n, cap) pairs (ua, ub), ascending by (ub, ua), to subs (host memory) */
+int32_t   svh_grid_get_align_scan(svh_grid* g, int32_t* subs, int64_t cap, int64_t* n);
+/* M, 4 x 4 row major, of the candidate (k, ta, tb) of the parameters in force about `pivot` (CORRECTION above).  Needs no device */
+int32_t   svh_grid_align_correction(svh_grid* g, int32_t k, int32_t ta, int32_t tb, const double pivot[3], double M[16]);
+/* svh_grid_render_local with the last alignment over it: the cells of the scan at the identity (255, 224, 0), then the cells of the
+ * scan placed at the best (0, 224, 255), then the pivot's cell (255, 255, 255); the later primitive wins */
+int32_t   svh_grid_render_align(svh_grid* g, uint8_t* rgb, int32_t on_device);
 
 #ifdef __cplusplus
 }

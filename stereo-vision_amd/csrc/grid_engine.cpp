@@ -7,7 +7,8 @@
 // (grid_plan_kernels.hip): the planner -- the relaxation over active tiles, whose round loop is plan_rounds() here;
 // (grid_front_kernels.hip): the frontiers -- mask, union-find labelling, the table of components, run by front_run() here;
 // (grid_roll_kernels.hip): the rollouts -- footprint costs, the scoring of a set of candidates and its best;
-// (grid_explore_kernels.hip): the exploration layer -- the gain of viewpoints, the ranking of the frontiers, run by explore_rank() here.
+// (grid_explore_kernels.hip): the exploration layer -- the gain of viewpoints, the ranking of the frontiers, run by explore_rank() here;
+// (grid_align_kernels.hip): the alignment layer -- the field, the scan of a frame's obstacle points, the volume of scores, run by align() here.
 // The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
@@ -26,6 +27,8 @@
 // The exploration layer caches one thing, the reach field: POT with the start of the last ranking as the only goal, in buffers of
 // its own beside the planner's (reach_valid), kept until the start cell, the accumulators, the offsets, the traversability or the
 // plan parameters change.  Gains and VIEW planes are computed per call.
+// The alignment layer caches its field F, derived from STATE (afield_valid), until the accumulators, the offsets or the align
+// parameters change, and keeps the scan, the volume and the record of the last alignment for the getters and the image.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -37,6 +40,7 @@
 #include <vector>
 
 #include "../../include/svh_grid.h"
+#include "grid_align_core.h"
 #include "grid_core.h"
 #include "grid_explore_core.h"
 #include "grid_internal.h"
@@ -67,6 +71,9 @@ constexpr size_t kFrontBytes = 5;                  // per cell: LABEL; FRONT
 // a workgroup for every tile.  4 is kept.  1..64; svh_test_grid_plan_rounds_per_wait changes it for that measurement
 // (tools/gpu_grid_plan.py)
 int g_rounds_per_wait = 4;
+// the form of the alignment's score kernel (grid::AlignForm); svh_test_grid_align_form changes it for the paired measurement
+// (tools/gpu_grid_align.py) and the tests
+int g_align_form = grid::ALIGN_FORM_CHUNK;
 
 bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
@@ -122,6 +129,15 @@ struct RollBufs {
 struct ExploreBufs {
     HipBuf<int32_t> gain, recs, out;
     HipBuf<long long> scores;
+};
+
+// what an alignment needs on the device beside STATE: the field and its column distances, the bitmap of the box with the counts of
+// its blocks, the list of the scan, the control words, the volume and the record
+struct AlignBufs {
+    HipBuf<uint8_t> field;
+    HipBuf<uint16_t> g;
+    HipBuf<uint32_t> bitmap, blockcnt, ctl;
+    HipBuf<int32_t> scan, volume, rec;
 };
 
 }  // namespace
@@ -195,6 +211,14 @@ struct svh_grid {
     HipBuf<int32_t> d_vcells, d_vgain;   // viewpoints of a host caller and their GAIN
     HipBuf<uint8_t> d_view;     // the VIEW plane of one viewpoint
     int64_t ex_stats[grid::ES_WORDS] = {0, 0, 0, 0};
+    grid::AlignParams alp{};    // the alignment layer: parameters with what is derived from them and the rotation table;
+    bool align_ok = false;      // false until svh_grid_set_align succeeds
+    int32_t align_rot[2 * grid::ALIGN_MAX_ROTS] = {0};
+    AlignBufs al;
+    PinnedBuf<int32_t> h_arec;
+    bool afield_valid = false;  // al.field is derived from STATE as it is, with the offsets and align parameters as they are; implies final_valid
+    bool align_last = false;    // al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment:
+    int32_t align_rec[grid::ALIGN_REC] = {0}, align_Pa = 0, align_Pb = 0;   // its record and pivot sub
     svh_grid_stats st{0, 0, 0, 0, 0};
     int64_t rays = 0, ray_cells = 0;
 
@@ -222,7 +246,7 @@ struct svh_grid {
 namespace {
 
 // the accumulators change: what was derived from them is stale
-void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = g->plan_valid = g->front_valid = g->reach_valid = false; }
+void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = g->plan_valid = g->front_valid = g->reach_valid = g->afield_valid = false; }
 
 void mark_empty(svh_grid* g) {
     g->need_clear = true;
@@ -1171,6 +1195,175 @@ void view_overlay_host(int32_t nx, int32_t nz, const uint8_t* view, int32_t va, 
             (void)grid::colour_view(view[(size_t)b * nx + a], a == va && b == vb, rgb + 3 * ((size_t)(nz - 1 - b) * (size_t)nx + (size_t)a));
 }
 
+// ---- the alignment layer ----------------------------------------------------------------------------------------------------
+bool position(const double xyz[3], float p[3]);
+
+const char* const kNoAlign =": the align parameters are not set (svh_grid_set_align)";
+
+bool convert_align(const svh_grid_align_params* p, float cell, grid::AlignParams* q) {
+    if (!p) return false;
+    *q = grid::AlignParams{p->reach, p->range, p->rot_den, p->rot_n, p->trans_n, p->min_scan, 0, 0};
+    return grid::align_derive(*q, cell);
+}
+
+// the job of an alignment of at most n points about the pivot sub (Pa, Pb), with room for everything it writes
+int align_job(AlignBufs& b, const grid::Params& prm, const grid::AlignParams& alp, const uint8_t* state, int32_t Pa, int32_t Pb, int64_t n,
+              grid::AlignJob* out) {
+    grid::AlignJob& j = *out;
+    j.prm = prm, j.alp = alp, j.Pa = Pa, j.Pb = Pb;
+    memset(j.rot, 0, sizeof(j.rot));
+    grid::align_rot_table(alp.rot_den, alp.rot_n, j.rot);
+    const size_t ncells = (size_t)prm.nx * (size_t)prm.nz;
+    const int64_t side = grid::align_side(alp.Rg);
+    j.scan_room = std::min<int64_t>(n, side * side);
+    GRID_GROW_N(b.field, ncells);
+    GRID_GROW_N(b.g, ncells);
+    GRID_GROW_N(b.bitmap, grid::align_words(j));
+    GRID_GROW_N(b.blockcnt, grid::align_count_blocks(j));
+    GRID_GROW_N(b.ctl, grid::AC_WORDS);
+    GRID_GROW_N(b.scan, 2 * j.scan_room);
+    GRID_GROW_N(b.volume, grid::align_volume_size(alp.rot_n, alp.trans_n));
+    GRID_GROW_N(b.rec, grid::ALIGN_REC);
+    j.state = state;
+    j.g = b.g, j.field = b.field, j.bitmap = b.bitmap, j.blockcnt = b.blockcnt, j.scan = b.scan, j.ctl = b.ctl, j.volume = b.volume, j.rec = b.rec;
+    return SVH_OK;
+}
+
+// the bitmap, the control words and the volume become zero: before the marks of an alignment
+int align_begin(hipStream_t s, const grid::AlignJob& j) {
+    GRID_TRY(copy, hipMemsetAsync(j.bitmap, 0, (size_t)grid::align_words(j) * sizeof(uint32_t), s));
+    GRID_TRY(copy, hipMemsetAsync(j.ctl, 0, grid::AC_WORDS * sizeof(uint32_t), s));
+    GRID_TRY(copy, hipMemsetAsync(j.volume, 0, (size_t)grid::align_volume_size(j.alp.rot_n, j.alp.trans_n) * sizeof(int32_t), s));
+    return SVH_OK;
+}
+
+// after the marks: the list of the scan, the volume, the record
+int align_finish(hipStream_t s, const grid::AlignJob& j) {
+    grid::launch_align_compact(s, j);
+    grid::launch_align_score(s, j, g_align_form & 3);
+    GRID_TRY(launch, hipGetLastError());
+    return SVH_OK;
+}
+
+// al.field is valid, launched on the stream; the caller waits and then sets final_valid and afield_valid
+int align_field(svh_grid* g, const grid::AlignJob& j) {
+    const int rc = finalise(g);
+    if (rc) return rc;
+    if (!g->afield_valid) GRID_TRY(launch, (grid::launch_align_field(g->stream, j, (g_align_form & grid::ALIGN_FORM_MASK) != 0), hipGetLastError()));
+    return SVH_OK;
+}
+
+int object_align_job(svh_grid* g, int32_t Pa, int32_t Pb, int64_t n, grid::AlignJob* j) {
+    const int rc = ready(g);
+    if (rc) return rc;
+    if (g->al.field.cap < g->ncells) g->afield_valid = false;
+    return align_job(g->al, g->prm, g->alp, g->bplane(B_STATE), Pa, Pb, n, j);
+}
+
+// n >= 0 points, host or device, about the pivot sub, with arguments that have been checked: the record
+int align(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int32_t Pa, int32_t Pb, int32_t* rec) {
+    g->align_last = false;
+    grid::AlignJob j;
+    int rc = object_align_job(g, Pa, Pb, n, &j);
+    if (rc) return rc;
+    GRID_GROW(g->h_arec, grid::ALIGN_REC * sizeof(int32_t));
+    hipStream_t s = g->stream;
+    if ((rc = align_field(g, j))) return rc;
+    if ((rc = align_begin(s, j))) return rc;
+    if (on_device || n == 0) {
+        GRID_TRY(launch, (grid::launch_align_mark(s, j, (const float4*)xyzv, nullptr, n), hipGetLastError()));
+    } else {
+        const int64_t room = std::min(n, kHostChunk);
+        GRID_GROW(g->h_pts, (size_t)room * sizeof(float4));
+        GRID_GROW(g->d_pts, (size_t)room * sizeof(float4));
+        for (int64_t at = 0; at < n; at += room) {
+            const int64_t m = std::min(room, n - at);
+            if (at > 0) GRID_TRY(wait, hipStreamSynchronize(s));   // the staging buffer is read until here
+            memcpy(g->h_pts, xyzv + 4 * at, (size_t)m * sizeof(float4));
+            GRID_TRY(copy, hipMemcpyAsync(g->d_pts, g->h_pts, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, s));
+            GRID_TRY(launch, (grid::launch_align_mark(s, j, g->d_pts, nullptr, m), hipGetLastError()));
+        }
+    }
+    if ((rc = align_finish(s, j))) return rc;
+    GRID_TRY(copy, hipMemcpyAsync(g->h_arec, j.rec, grid::ALIGN_REC * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    g->final_valid = g->afield_valid = g->align_last = true;
+    memcpy(g->align_rec, g->h_arec, sizeof(g->align_rec));
+    g->align_Pa = Pa, g->align_Pb = Pb;
+    memcpy(rec, g->align_rec, sizeof(g->align_rec));
+    return SVH_OK;
+}
+
+int get_align_field(svh_grid* g, uint8_t* out, bool on_device) {
+    grid::AlignJob j;
+    int rc = object_align_job(g, 0, 0, 0, &j);
+    if (rc) return rc;
+    if ((rc = align_field(g, j))) return rc;
+    if ((rc = deliver(g, j.field, g->ncells, out, on_device))) return rc;
+    g->final_valid = g->afield_valid = true;
+    return SVH_OK;
+}
+
+int render_align(svh_grid* g, uint8_t* rgb, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const size_t bytes = g->ncells * 3;
+    if (!on_device) {
+        GRID_GROW(g->d_rgb, bytes);
+        GRID_GROW(g->h_out, bytes);
+    }
+    if ((rc = finalise(g))) return rc;
+    grid::RenderJob r;
+    r.prm = g->prm;
+    r.mode = grid::M_LOCAL;
+    r.count = g->iplane(F_COUNT), r.pass = g->iplane(F_PASS);
+    r.hmin = g->fplane(F_HMIN), r.hmax = g->fplane(F_HMAX), r.hmean = g->fplane(F_HMEAN);
+    r.intensity = g->bplane(B_INTENSITY), r.cls = g->bplane(B_CLASS);
+    r.rgb = on_device ? rgb : g->d_rgb.p;
+    grid::launch_render(g->stream, r);
+    grid::AlignJob j{};   // the buffers are those of the last alignment: nothing grows
+    j.prm = g->prm, j.alp = g->alp, j.Pa = g->align_Pa, j.Pb = g->align_Pb;
+    memcpy(j.rot, g->align_rot, sizeof(j.rot));
+    j.scan = g->al.scan;
+    const int32_t* rec = g->align_rec;
+    grid::launch_align_overlay(g->stream, j, rec[grid::AR_SCAN], rec[grid::AR_K], rec[grid::AR_TA], rec[grid::AR_TB], r.rgb);
+    GRID_TRY(launch, hipGetLastError());
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+        return rc;
+    }
+    g->final_valid = true;
+    return SVH_OK;
+}
+
+// an align call that failed on the device: nothing in flight, the field and the last alignment are gone
+int aligned(svh_grid* g, int rc) {
+    if (rc == SVH_ERR_HIP) g->afield_valid = g->align_last = false;
+    return drained(g, rc);
+}
+
+// what svh_test_grid_align and svh_test_grid_align_device share: the arguments checked and converted, the pivot's sub
+bool align_test_args(const svh_grid_params* p, const svh_grid_align_params* a, int32_t oa, int32_t ob, const uint8_t* state, const float* xyzv,
+                     int64_t n_pts, const int32_t* subs, int64_t n_subs, const double pivot[3], const int32_t pivot_sub[2], const int32_t* scan,
+                     int64_t cap, const int32_t* rec, grid::Params* q, grid::AlignParams* aq, int32_t* Pa, int32_t* Pb) {
+    if (!convert(p, q) || !convert_align(a, q->cell, aq) || !grid::offsets_ok(oa, ob) || !state || !rec || cap < 0 || (cap > 0 && !scan)) return false;
+    q->oa = oa, q->ob = ob;
+    if (pivot_sub) {
+        if (n_subs < 0 || n_subs > kMaxPoints || (n_subs > 0 && !subs)) return false;
+        for (int64_t i = 0; i < 2 * n_subs; i++)
+            if (subs[i] <= -grid::ALIGN_SUB_LIMIT || subs[i] >= grid::ALIGN_SUB_LIMIT) return false;
+        if (pivot_sub[0] <= -grid::ALIGN_SUB_LIMIT || pivot_sub[0] >= grid::ALIGN_SUB_LIMIT || pivot_sub[1] <= -grid::ALIGN_SUB_LIMIT ||
+            pivot_sub[1] >= grid::ALIGN_SUB_LIMIT)
+            return false;
+        *Pa = pivot_sub[0], *Pb = pivot_sub[1];
+        return true;
+    }
+    float pv[3];
+    if (n_pts < 0 || n_pts > kMaxPoints || (n_pts > 0 && !xyzv) || !position(pivot, pv)) return false;
+    return grid::align_pivot(*q, pv[0], pv[1], pv[2], Pa, Pb);
+}
+
 // ... and a failed add leaves the empty grid
 int added(svh_grid* g, int rc) {
     if (rc == SVH_ERR_HIP) {
@@ -1813,6 +2006,106 @@ int32_t svh_grid_render_view(svh_grid* g, int32_t ga, int32_t gb, uint8_t* rgb, 
     return explored(g, render_view(g, (int32_t)va, (int32_t)vb, rgb, on_device != 0));
 }
 
+void svh_grid_align_params_default(svh_grid_align_params* p) {
+    if (!p) return;
+    p->reach = 0.6f, p->range = 25.6f, p->rot_den = 256, p->rot_n = 8, p->trans_n = 8, p->min_scan = 32;
+}
+
+int32_t svh_grid_set_align(svh_grid* g, const svh_grid_align_params* p) {
+    grid::AlignParams q;
+    if (!g || !convert_align(p, g->prm.cell, &q))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_align: a grid and parameters in range, with a reach of 1..32 and a range of 1..256 cells, are needed (include/svh_grid.h)");
+    g->alp = q;
+    memset(g->align_rot, 0, sizeof(g->align_rot));
+    grid::align_rot_table(q.rot_den, q.rot_n, g->align_rot);
+    g->align_ok = true;
+    g->afield_valid = g->align_last = false;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_align_field(svh_grid* g, uint8_t* out, int32_t on_device) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_field: a grid and an output are needed");
+    if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_align_field") + kNoAlign);
+    return aligned(g, get_align_field(g, out, on_device != 0));
+}
+
+int32_t svh_grid_align_points(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device, const double pivot[3], int32_t rec[8]) {
+    float pv[3];
+    int32_t Pa, Pb;
+    if (!g || n < 0 || n > kMaxPoints || (n > 0 && !xyzv) || !rec) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_points: bad arguments");
+    if (on_device && ((uintptr_t)xyzv & 15)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_points: a device array must be 16-byte aligned");
+    if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_align_points") + kNoAlign);
+    if (!position(pivot, pv) || !grid::align_pivot(g->prm, pv[0], pv[1], pv[2], &Pa, &Pb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_points: the pivot must be finite with a cell below 2^20");
+    return aligned(g, align(g, xyzv, n, on_device != 0, Pa, Pb, rec));
+}
+
+int32_t svh_grid_align_view_lists(svh_grid* g, svh_view* v, int32_t first_list, int32_t n_lists, const double pivot[3], int32_t rec[8]) {
+    float pv[3];
+    int32_t Pa, Pb;
+    if (!g || !v || !rec) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_view_lists: null argument");
+    if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_align_view_lists") + kNoAlign);
+    const view::StoreRef r = view::store_of(v);
+    if (r.device != g->device) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_view_lists: the view lives on another device");
+    int64_t at = 0, n = 0;
+    if (!view::list_range(v, first_list, n_lists, &at, &n))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_view_lists: the lists are not all in the view's sequence");
+    if (!position(pivot, pv) || !grid::align_pivot(g->prm, pv[0], pv[1], pv[2], &Pa, &Pb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_view_lists: the pivot must be finite with a cell below 2^20");
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipSetDevice(g->device));
+        GRID_TRY(wait, hipStreamSynchronize(r.stream));   // the store is complete before this stream reads it
+        return align(g, (const float*)(r.pts + at), n, true, Pa, Pb, rec);
+    }();
+    return aligned(g, rc);
+}
+
+int32_t svh_grid_get_align_volume(svh_grid* g, int32_t* out, int32_t on_device) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_volume: a grid and an output are needed");
+    if (on_device && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_volume: a device array must be 4-byte aligned");
+    if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_align_volume") + kNoAlign);
+    if (!g->align_last || g->align_rec[grid::AR_STATUS] == grid::ALIGN_FEW)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_volume: there is no volume: no alignment since the parameters were set, the last one failed or had too few subs");
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipSetDevice(g->device));
+        return deliver(g, g->al.volume, (size_t)grid::align_volume_size(g->alp.rot_n, g->alp.trans_n) * sizeof(int32_t), out, on_device != 0);
+    }();
+    return drained(g, rc);
+}
+
+int32_t svh_grid_get_align_scan(svh_grid* g, int32_t* subs, int64_t cap, int64_t* n) {
+    if (!g || !n || cap < 0 || (cap > 0 && !subs)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_scan: a grid, cap >= 0 with room and a count are needed");
+    if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_align_scan") + kNoAlign);
+    if (!g->align_last) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_scan: there is no scan: no alignment since the parameters were set, or the last one failed");
+    const int64_t have = g->align_rec[grid::AR_SCAN], give = std::min(have, cap);
+    if (give > 0) {
+        const int rc = [&]() -> int {
+            GRID_TRY(none, hipSetDevice(g->device));
+            return deliver(g, g->al.scan, (size_t)give * 2 * sizeof(int32_t), subs, false);
+        }();
+        if (rc) return drained(g, rc);
+    }
+    *n = have;
+    return SVH_OK;
+}
+
+int32_t svh_grid_align_correction(svh_grid* g, int32_t k, int32_t ta, int32_t tb, const double pivot[3], double M[16]) {
+    float pv[3];
+    if (!g || !M || !position(pivot, pv)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_correction: a grid, a finite pivot and an output are needed");
+    if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_align_correction") + kNoAlign);
+    if (k < -g->alp.rot_n || k > g->alp.rot_n || ta < -g->alp.trans_n || ta > g->alp.trans_n || tb < -g->alp.trans_n || tb > g->alp.trans_n)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_correction: (k, ta, tb) is no candidate of the parameters in force");
+    grid::align_correction(g->prm, g->alp.rot_den, k, ta, tb, pv, M);
+    return SVH_OK;
+}
+
+int32_t svh_grid_render_align(svh_grid* g, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_align: a grid and an output are needed");
+    if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_align") + kNoAlign);
+    if (!g->align_last) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_align: there is no alignment to draw: none since the parameters were set, or the last one failed");
+    return drained(g, render_align(g, rgb, on_device != 0));
+}
+
 // grid_explore_core.h on the host, on a caller's STATE and COST planes (nx x nz, offsets oa, ob), with R from e->range and `cell`.
 // Three things, each optional: GAIN of n_cells global cells to gains; for the global cell view[2], inside the window, its VIEW
 // plane to mask (nx * nz) and drawn over rgb (nx * nz * 3, the layout of svh_grid_render_cost, changed in place); from the global
@@ -1944,6 +2237,93 @@ int32_t svh_test_grid_explore_device(const svh_grid_front_params* f, const svh_g
         if (stats) stats[0] = m, stats[1] = out[1];
     }
     return SVH_OK;
+}
+
+// grid_align_core.h on the host, on a caller's STATE plane (p->nx x p->nz, offsets oa, ob) with the frame, cell, step and clearance of
+// `p`.  The frame is n_pts points (x, y, z, val) about the map-frame position `pivot`, or -- with pivot_sub, the pivot's global sub --
+// n_subs global subs (ua, ub), all of magnitude below 2^22.  field: F (nx * nz, may be null); counts[0] n_scan, counts[1] n_points
+// (may be null); the first min(n_scan, cap) pairs of the scan to `scan`; volume: (2 K + 1) (2 W + 1)^2 scores, not written with
+// too few subs (may be null); rec: the record.  Needs no device
+int32_t svh_test_grid_align(const svh_grid_params* p, const svh_grid_align_params* a, int32_t oa, int32_t ob, const uint8_t* state, const float* xyzv,
+                            int64_t n_pts, const int32_t* subs, int64_t n_subs, const double pivot[3], const int32_t pivot_sub[2], uint8_t* field,
+                            int32_t* scan, int64_t cap, int64_t* counts, int32_t* volume, int32_t* rec) {
+    grid::Params q;
+    grid::AlignParams aq;
+    int32_t Pa = 0, Pb = 0;
+    if (!align_test_args(p, a, oa, ob, state, xyzv, n_pts, subs, n_subs, pivot, pivot_sub, scan, cap, rec, &q, &aq, &Pa, &Pb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_align: bad arguments");
+    std::vector<uint8_t> F((size_t)q.nx * (size_t)q.nz);
+    grid::align_field_window(aq.reach_cells, q.nx, q.nz, state, F.data());
+    std::vector<int32_t> list;
+    const int64_t kept = pivot_sub ? grid::align_scan_subs(aq.Rg, Pa, Pb, subs, n_subs, &list) : grid::align_scan_points(q, aq.Rg, Pa, Pb, xyzv, n_pts, &list);
+    const int64_t n_scan = (int64_t)(list.size() / 2);
+    grid::align_window(aq, q.nx, q.nz, oa, ob, F.data(), Pa, Pb, list.data(), n_scan, volume, rec);
+    if (field) memcpy(field, F.data(), F.size());
+    if (counts) counts[0] = n_scan, counts[1] = kept;
+    const size_t give = (size_t)std::min(n_scan, cap);
+    if (give) memcpy(scan, list.data(), give * 2 * sizeof(int32_t));
+    return SVH_OK;
+}
+
+// the same through the kernels of csrc/grid_align_kernels.hip: the plane and the frame go to the device
+int32_t svh_test_grid_align_device(const svh_grid_params* p, const svh_grid_align_params* a, int32_t oa, int32_t ob, const uint8_t* state,
+                                   const float* xyzv, int64_t n_pts, const int32_t* subs, int64_t n_subs, const double pivot[3],
+                                   const int32_t pivot_sub[2], uint8_t* field, int32_t* scan, int64_t cap, int64_t* counts, int32_t* volume,
+                                   int32_t* rec) {
+    grid::Params q;
+    grid::AlignParams aq;
+    int32_t Pa = 0, Pb = 0;
+    if (!align_test_args(p, a, oa, ob, state, xyzv, n_pts, subs, n_subs, pivot, pivot_sub, scan, cap, rec, &q, &aq, &Pa, &Pb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_align_device: bad arguments");
+    svh::ensure_init();
+    const size_t ncells = (size_t)q.nx * (size_t)q.nz;
+    const int64_t n = pivot_sub ? n_subs : n_pts;
+    HipBuf<uint8_t> d_state, d_in;
+    AlignBufs bufs;
+    uint32_t ctl[grid::AC_WORDS] = {0, 0};
+    int32_t r[grid::ALIGN_REC];
+    hipStream_t s = nullptr;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(d_state, ncells);
+        GRID_TRY(copy, hipMemcpyAsync(d_state, state, ncells, hipMemcpyHostToDevice, s));
+        grid::AlignJob j;
+        int e = align_job(bufs, q, aq, d_state.p, Pa, Pb, n, &j);
+        if (e) return e;
+        const size_t in_bytes = (size_t)n * (pivot_sub ? 2 * sizeof(int32_t) : sizeof(float4));
+        GRID_GROW(d_in, in_bytes ? in_bytes : 16);
+        if (n > 0) GRID_TRY(copy, hipMemcpyAsync(d_in, pivot_sub ? (const void*)subs : (const void*)xyzv, in_bytes, hipMemcpyHostToDevice, s));
+        GRID_TRY(launch, (grid::launch_align_field(s, j, (g_align_form & grid::ALIGN_FORM_MASK) != 0), hipGetLastError()));
+        if ((e = align_begin(s, j))) return e;
+        GRID_TRY(launch, (grid::launch_align_mark(s, j, pivot_sub ? nullptr : (const float4*)d_in.p, pivot_sub ? (const int32_t*)d_in.p : nullptr, n), hipGetLastError()));
+        if ((e = align_finish(s, j))) return e;
+        GRID_TRY(copy, hipMemcpyAsync(r, j.rec, sizeof(r), hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(ctl, j.ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+        if (field) GRID_TRY(copy, hipMemcpyAsync(field, j.field, ncells, hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        const size_t give = (size_t)std::min<int64_t>(r[grid::AR_SCAN], cap);
+        if (give) GRID_TRY(copy, hipMemcpyAsync(scan, j.scan, give * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (volume && r[grid::AR_STATUS] != grid::ALIGN_FEW)
+            GRID_TRY(copy, hipMemcpyAsync(volume, j.volume, (size_t)grid::align_volume_size(aq.rot_n, aq.trans_n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    memcpy(rec, r, sizeof(r));
+    if (counts) counts[0] = ctl[grid::AC_SCAN], counts[1] = ctl[grid::AC_POINTS];
+    return SVH_OK;
+}
+
+// a measurement's and a test's switch: the form of the score kernel becomes `form` (0 chunk, 1 plain, 2 tiled; anything else only
+// reads), plus 4 for the field in three launches, the mask first, instead of two; returns what it was
+int32_t svh_test_grid_align_form(int32_t form) {
+    const int32_t was = g_align_form;
+    if (form >= 0 && form < 8 && (form & 3) < grid::ALIGN_FORMS) g_align_form = form;
+    return was;
 }
 
 // grid_roll_core.h on the host.  The footprint table for a cell side: *R, *total cells of all lists, and (k >= 0) the list of heading

@@ -1,12 +1,13 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
-// csrc/grid_front_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_explore_kernels.hip: the launches of the ground grid
-// (include/svh_grid.h).
+// csrc/grid_front_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip: the launches of the
+// ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
 
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
 
+#include "grid_align_core.h"
 #include "grid_core.h"
 #include "grid_explore_core.h"
 #include "grid_front_core.h"
@@ -283,6 +284,54 @@ void launch_view_mask(hipStream_t s, const ExploreJob& j, int32_t va, int32_t vb
 int32_t launch_explore_rank(hipStream_t s, const ExploreJob& j);
 // a VIEW plane and its viewpoint drawn over an image of svh_grid_render_cost's layout
 void launch_view_overlay(hipStream_t s, int32_t nx, int32_t nz, const uint8_t* view, int32_t va, int32_t vb, uint8_t* rgb);
+
+// The alignment layer (csrc/grid_align_kernels.hip): the finished STATE plane and the obstacle points of a frame -> the field F, the
+// scan, the volume of scores, the record of the best.
+constexpr uint32_t ALIGN_BLOCK = 256;            // every kernel of the layer but the best
+constexpr uint32_t ALIGN_MAX_BLOCKS = 2048;      // k_grid_align_mark: the lanes stride beyond 2048 * 256 points
+constexpr int32_t ALIGN_CHUNK = 1024;            // k_grid_align_score: scan subs a workgroup places at a time
+constexpr uint32_t ALIGN_MAX_SLICES = 64;        // ... the slices of the scan a launch has at most; a slice strides over its chunks
+constexpr uint32_t ALIGN_BEST_BLOCK = 1024;      // k_grid_align_best: one workgroup
+constexpr int32_t ALIGN_TILED_RUN = (2 * ALIGN_MAX_W) / 4 + 1;   // k_grid_align_score_tiled: translations a lane owns at most, 17
+constexpr uint32_t ALIGN_TILED_LDS = 160 * 1024;   // ... the LDS of a workgroup: the chunk and the staged cells of F
+constexpr uint32_t ALIGN_TILED_SLICES = 4;       // ... the slices of the scan a launch has at most
+enum AlignForm : int32_t { ALIGN_FORM_CHUNK = 0, ALIGN_FORM_PLAIN = 1, ALIGN_FORM_TILED = 2, ALIGN_FORMS = 3,   // of the score kernel
+                           ALIGN_FORM_MASK = 4 };   // added to one of them: the field in three launches, the mask first
+enum AlignCtl { AC_SCAN = 0, AC_POINTS = 1, AC_WORDS = 2 };   // the control words on the device
+
+struct AlignJob {
+    Params prm;                 // where a point goes; nx, nz, oa, ob of the window
+    AlignParams alp;
+    int32_t Pa, Pb;             // the pivot's global sub
+    int32_t rot[2 * ALIGN_MAX_ROTS];   // align_rot_table
+    const uint8_t* state;       // the finished STATE plane
+    uint16_t* g;                // the column distances, scratch, nx * nz
+    uint8_t* field;             // F, nx * nz
+    uint32_t* bitmap;           // ceil(side^2 / 32) words, all zero before the marks
+    uint32_t* blockcnt;         // one count per ALIGN_BLOCK words of the bitmap
+    int32_t* scan;              // pairs (ua, ub); room for min(points, side^2)
+    int64_t scan_room;          // ... that many: the bound of every loop over the scan
+    uint32_t* ctl;              // AC_WORDS, all zero before the marks
+    int32_t* volume;            // align_volume_size(K, W), all zero before the scores
+    int32_t* rec;               // ALIGN_REC
+};
+inline uint32_t align_words(const AlignJob& j) {
+    const uint64_t side = (uint64_t)align_side(j.alp.Rg);
+    return (uint32_t)((side * side + 31) / 32);
+}
+inline uint32_t align_count_blocks(const AlignJob& j) { return (align_words(j) + ALIGN_BLOCK - 1) / ALIGN_BLOCK; }
+// F from STATE: the column sweep and the row pass
+void launch_align_field(hipStream_t s, const AlignJob& j, bool mask);
+// the kept points of n points (x, y, z, val), or (subs) of n pairs (ua, ub), marked in the bitmap and counted into ctl[AC_POINTS]
+void launch_align_mark(hipStream_t s, const AlignJob& j, const float4* pts, const int32_t* subs, int64_t n);
+// the set bits in ascending order to `scan`, their number to ctl[AC_SCAN]: two launches
+void launch_align_compact(hipStream_t s, const AlignJob& j);
+// the volume (all zero before) and the record.  Every loop over the scan is bounded by scan_room; with fewer than min_scan subs
+// the volume is not written
+void launch_align_score(hipStream_t s, const AlignJob& j, int32_t form);
+// the cells of the scan at the identity, those of the scan placed at (k, ta, tb), the pivot's cell, drawn in that order over an
+// image of svh_grid_render_local's layout: three launches
+void launch_align_overlay(hipStream_t s, const AlignJob& j, int32_t n_scan, int32_t k, int32_t ta, int32_t tb, uint8_t* rgb);
 
 }  // namespace grid
 }  // namespace svh

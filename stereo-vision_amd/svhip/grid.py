@@ -1,7 +1,7 @@
 """ctypes binding of the ground grid in libsvhip.so (C-ABI: include/svh_grid.h): a 2.5-D bird's-eye grid over the road
 plane -- per cell how many points, how high, how bright, drivable or not -- binned on the device from the map view's store
 or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h, grid_plan_core.h, grid_front_core.h and
-grid_roll_core.h; that of the exploration layer grid_explore_core.h."""
+grid_roll_core.h; that of the exploration layer grid_explore_core.h, that of the alignment layer grid_align_core.h."""
 import ctypes as C
 
 import numpy as np
@@ -44,6 +44,11 @@ EXPLORE_FIELDS = ("label", "rep_ga", "rep_gb", "gain", "reach")
 EXPLORE_INFEASIBLE = 2 ** 63 - 1
 VIEW_NONE, VIEW_VISITED, VIEW_COUNTED = range(3)
 VIEW_COLOUR, VIEWPOINT_COLOUR = (255, 0, 255), (255, 255, 255)
+ALIGN_RECORD = 8
+ALIGN_FIELDS = ("status", "k", "ta", "tb", "score", "identity", "n_scan", "ties")
+ALIGN_OK, ALIGN_FEW, ALIGN_FLAT = range(3)
+ALIGN_SUB = 4
+ALIGN_SCAN_COLOUR, ALIGN_BEST_COLOUR, ALIGN_PIVOT_COLOUR = (255, 224, 0), (0, 224, 255), (255, 255, 255)
 
 
 class Params(C.Structure):
@@ -125,6 +130,21 @@ class ExploreParams(C.Structure):
 
     def copy(self, **kw):
         q = ExploreParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class AlignParams(C.Structure):
+    """svh_grid_align_params"""
+    _fields_ = [("reach", C.c_float), ("range", C.c_float), ("rot_den", C.c_int32), ("rot_n", C.c_int32), ("trans_n", C.c_int32),
+                ("min_scan", C.c_int32)]
+
+    def copy(self, **kw):
+        q = AlignParams.from_buffer_copy(bytes(self))
         for k, v in kw.items():
             setattr(q, k, v)
         return q
@@ -245,6 +265,21 @@ def _bind():
                    [C.c_int64] + [C.c_void_p] * 7 + [C.c_int64] + [C.c_void_p] * 3)
         L.svh_test_grid_explore.argtypes = explore
         L.svh_test_grid_explore_device.argtypes = explore
+        L.svh_grid_align_params_default.argtypes = [C.POINTER(AlignParams)]
+        L.svh_grid_align_params_default.restype = None
+        L.svh_grid_set_align.argtypes = [C.c_void_p, C.POINTER(AlignParams)]
+        L.svh_grid_get_align_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_grid_align_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.svh_grid_align_view_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.svh_grid_get_align_volume.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_grid_get_align_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_grid_align_correction.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.svh_grid_render_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        align = ([C.POINTER(Params), C.POINTER(AlignParams), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
+                 [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3)
+        L.svh_test_grid_align.argtypes = align
+        L.svh_test_grid_align_device.argtypes = align
+        L.svh_test_grid_align_form.argtypes = [C.c_int32]
         L._grid_bound = True
     return L
 
@@ -611,6 +646,54 @@ def core_explore(explore, cell, state, cost=None, front=None, plan=None, oa=0, o
 def device_explore(explore, cell, state, cost=None, front=None, plan=None, oa=0, ob=0, cells=None, view=None, rgb=None, start=None):
     """TEST ENTRY: the same through the device kernels on a caller's planes"""
     return _explore(_bind().svh_test_grid_explore_device, explore, cell, state, cost, front, plan, oa, ob, cells, view, rgb, start)
+
+
+def default_align(**kw):
+    p = AlignParams()
+    _bind().svh_grid_align_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def _align(entry, params, align, state, oa, ob, points, pivot, subs, pivot_sub):
+    s = np.ascontiguousarray(state, np.uint8)
+    nz, nx = s.shape
+    q = params.copy(nx=nx, nz=nz)
+    K, W = align.rot_n, align.trans_n
+    field = np.zeros((nz, nx), np.uint8)
+    volume = np.full((2 * K + 1, 2 * W + 1, 2 * W + 1), -1, np.int32)
+    rec, counts = np.zeros(ALIGN_RECORD, np.int32), np.zeros(2, np.int64)
+    if pivot_sub is not None:
+        u = np.ascontiguousarray(subs, np.int32).reshape(-1, 2)
+        ps = np.ascontiguousarray(pivot_sub, np.int32).reshape(2)
+        cap = len(u)
+        frame = (None, 0, u.ctypes.data if len(u) else None, len(u), None, ps.ctypes.data)
+    else:
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        cap = len(pts)
+        frame = (pts.ctypes.data if len(pts) else None, len(pts), None, 0, _xyz(pivot).ctypes.data, None)
+    scan = np.zeros((max(cap, 1), 2), np.int32)
+    _check(entry(C.byref(q), C.byref(align), oa, ob, s.ctypes.data, *frame, field.ctypes.data, scan.ctypes.data if cap else None, cap,
+                 counts.ctypes.data, volume.ctypes.data, rec.ctypes.data))
+    return dict(field=field, scan=scan[:int(counts[0])].copy(), n_points=int(counts[1]), volume=None if rec[0] == ALIGN_FEW else volume, rec=rec)
+
+
+def core_align(params, align, state, oa=0, ob=0, points=None, pivot=None, subs=None, pivot_sub=None):
+    """the alignment layer of csrc/grid_align_core.h on the host (svh_test_grid_align) on a STATE plane [nz, nx] under the offsets
+    (oa, ob) with the frame, cell, step and clearance of `params`: either points float32 [n, 4] about the map-frame position `pivot`, or
+    global subs int32 [n, 2] about the pivot's global sub `pivot_sub`.  A dict: field uint8 [nz, nx], scan int32 [n_scan, 2] ascending
+    by (ub, ua), n_points, volume int32 [2 K + 1, 2 W + 1, 2 W + 1] (None when the status is ALIGN_FEW), rec int32 [8] in the order of
+    ALIGN_FIELDS.  Needs no device"""
+    return _align(_bind().svh_test_grid_align, params, align, state, oa, ob, points, pivot, subs, pivot_sub)
+
+
+def device_align(params, align, state, oa=0, ob=0, points=None, pivot=None, subs=None, pivot_sub=None):
+    """TEST ENTRY: the same through the device kernels on a caller's plane"""
+    return _align(_bind().svh_test_grid_align_device, params, align, state, oa, ob, points, pivot, subs, pivot_sub)
+
+
+def align_form(form=-1):
+    """TEST ENTRY: the form of the alignment's score kernel becomes `form` (0 chunk, 1 plain, 2 tiled, plus 4 for the field in three launches instead of two; -1 only reads); what it was"""
+    return int(_bind().svh_test_grid_align_form(form))
 
 
 def __getattr__(name):
@@ -992,6 +1075,78 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_view(self._h, ga, gb, img.ctypes.data, 0))
+        return img
+
+    def set_align(self, params=None, **kw):
+        """the align parameters `params` (or the defaults) with the fields of kw replaced: reach, range, rot_den, rot_n, trans_n,
+        min_scan.  A grid has none until this succeeds"""
+        p = (params if params is not None else default_align()).copy(**kw)
+        _check(self._L.svh_grid_set_align(self._h, C.byref(p)))
+        self.align_params = p
+
+    def align_field(self, device_ptr=None):
+        """the field F uint8 [nz, nx]; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_align_field(self._h, device_ptr, 1))
+            return None
+        out = np.zeros((self.nz, self.nx), np.uint8)
+        _check(self._L.svh_grid_get_align_field(self._h, out.ctypes.data, 0))
+        return out
+
+    def align_points(self, xyzv, pivot):
+        """aligns [n, 4] float32 points on the host about the map-frame position `pivot`: the record int32 [8] in the order of
+        ALIGN_FIELDS.  Nothing is added"""
+        p = np.ascontiguousarray(xyzv, np.float32).reshape(-1, 4)
+        rec = np.zeros(ALIGN_RECORD, np.int32)
+        _check(self._L.svh_grid_align_points(self._h, p.ctypes.data if len(p) else None, len(p), 0, _xyz(pivot).ctypes.data, rec.ctypes.data))
+        return rec
+
+    def align_points_device(self, ptr, n, pivot):
+        """the same from a raw device address (int), 16-byte aligned"""
+        rec = np.zeros(ALIGN_RECORD, np.int32)
+        _check(self._L.svh_grid_align_points(self._h, ptr, n, 1, _xyz(pivot).ctypes.data, rec.ctypes.data))
+        return rec
+
+    def align_view_lists(self, view, first_list, n_lists, pivot):
+        """the same for lists first_list .. first_list + n_lists - 1 of a svhip.view.View, read where they lie"""
+        rec = np.zeros(ALIGN_RECORD, np.int32)
+        _check(self._L.svh_grid_align_view_lists(self._h, view._h, first_list, n_lists, _xyz(pivot).ctypes.data, rec.ctypes.data))
+        return rec
+
+    def align_volume(self, device_ptr=None):
+        """the scores of the last alignment, int32 [2 K + 1, 2 W + 1, 2 W + 1] indexed [k + K, tb + W, ta + W]"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_align_volume(self._h, device_ptr, 1))
+            return None
+        K, W = self.align_params.rot_n, self.align_params.trans_n
+        out = np.zeros((2 * K + 1, 2 * W + 1, 2 * W + 1), np.int32)
+        _check(self._L.svh_grid_get_align_volume(self._h, out.ctypes.data, 0))
+        return out
+
+    def align_scan(self, cap=None):
+        """the scan of the last alignment, int32 [n_scan, 2] global subs (ua, ub) ascending by (ub, ua); with cap only the first"""
+        n = C.c_int64(-1)
+        if cap is None:
+            _check(self._L.svh_grid_get_align_scan(self._h, None, 0, C.addressof(n)))
+            cap = n.value
+        out = np.zeros((max(cap, 1), 2), np.int32)
+        _check(self._L.svh_grid_get_align_scan(self._h, out.ctypes.data if cap else None, cap, C.addressof(n)))
+        return out[:min(n.value, cap)].copy()
+
+    def align_correction(self, k, ta, tb, pivot):
+        """the map-frame transform M float64 [4, 4] of the candidate (k, ta, tb) about `pivot`.  Needs no device"""
+        M = np.zeros((4, 4), np.float64)
+        _check(self._L.svh_grid_align_correction(self._h, k, ta, tb, _xyz(pivot).ctypes.data, M.ctypes.data))
+        return M
+
+    def render_align(self, device_ptr=None):
+        """render_local with the last alignment over it: the scan at the identity in ALIGN_SCAN_COLOUR, placed at the best in
+        ALIGN_BEST_COLOUR, the pivot's cell in ALIGN_PIVOT_COLOUR"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_align(self._h, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_align(self._h, img.ctypes.data, 0))
         return img
 
     def stats(self):

@@ -21,6 +21,7 @@ without the GUI.  Usage:
                                          [--grid-roll DIR [--grid-roll-vehicle FRONT,REAR,HALFWIDTH] [--grid-roll-unknown N]]
                                           [--grid-frontiers DIR [--grid-unexplored unseen|seen|both] [--grid-frontier-min N]]
                                           [--grid-explore DIR [--grid-explore-range M]]
+                                          [--grid-align DIR [--grid-align-apply] [--grid-align-window K,W]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -116,6 +117,15 @@ brightened, itself white; the path white over it; the plain frontier image when 
 DIR/explore_%06d.ppm and one line {"frame", "kept", "records", "feasible", "best", "rep", "gain", "reach", "score", "status",
 "length", "cost"} per frame is appended to DIR/explore.jsonl (rep, gain, reach and score null, status -1 when there is no best).
 It runs last: the goal it sets is the one the next frame's --grid-plan replaces.
+
+--grid-align DIR: needs --grid-local.  Before a frame's list goes into the local grid its obstacle points are aligned to the
+obstacle cells the grid already holds (svh_grid_align_view_lists, the camera's position as the pivot): every rotation of
+-K..K steps of 1/256 about the vertical through the camera and every translation of -W..W quarter cells (--grid-align-window K,W;
+8,8) is scored and the best taken.  One line {"frame", "status", "k", "ta", "tb", "score", "identity", "n_scan", "ties", "applied"}
+per frame is appended to DIR/align.jsonl and the image (svh_grid_render_align: the local image with the scan's cells yellow, the
+scan placed at the best cyan, the camera's cell white) goes into DIR/align_%06d.ppm.  With --grid-align-apply a frame whose status
+is 0 and whose best is unique (ties 1: no direction was left open) is added to the local grid under the correction M (svh_grid_align_correction), its rays cast from the corrected camera
+position; the map view and the odometry are left alone.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -224,6 +234,14 @@ class Pipeline:
         from svhip import grid
         self.local = grid.Grid(grid.default_params(nx=size[0], nz=size[1], cell=cell, x0=-0.5 * size[0] * cell, z0=0.0))
         self.local_appends = 0
+        self.align_apply = None    # False / True once enable_grid_align() has been called
+        self.align_last = None     # (record, applied, image) of the last local step that aligned a frame
+
+    def enable_grid_align(self, apply=False, window=(8, 8)):
+        """align every frame's list to the local grid before it is added (local_step); apply: add it under the correction"""
+        c = self.local.params.cell
+        self.local.set_align(reach=min(max(0.6, c), 32 * c), range=min(25.6, 256 * c), rot_n=window[0], trans_n=window[1])
+        self.align_apply = bool(apply)
 
     def set_grid_cost(self, **kw):
         """the traversability parameters of the local grid: max_slope, inscribed, inflate"""
@@ -295,7 +313,20 @@ class Pipeline:
             self.local_appends = self.appends
             centre = self.H_total[:3, 3].copy()
             g.follow(centre, g.nx // 2, g.nz // 2)
-            g.add_view_lists_from(self.view, self.view.count(view.LISTS) - 1, 1, centre)
+            last = self.view.count(view.LISTS) - 1
+            applied = False
+            if self.align_apply is not None:
+                rec = g.align_view_lists(self.view, last, 1, centre)
+                img = g.render_align()
+                if self.align_apply and rec[0] == 0 and rec[7] == 1 and rec[1:4].any():
+                    M = g.align_correction(int(rec[1]), int(rec[2]), int(rec[3]), centre)
+                    pts = self.view.points(last).copy()
+                    pts[:, :3] = (pts[:, :3].astype(np.float64) @ M[:3, :3].T + M[:3, 3]).astype(np.float32)
+                    g.add_points_from(pts, M[:3, :3] @ centre + M[:3, 3])
+                    applied = True
+                self.align_last = (rec, applied, img)
+            if not applied:
+                g.add_view_lists_from(self.view, last, 1, centre)
         return g.render_local()
 
     def render_grid(self):
@@ -565,6 +596,7 @@ def main():
     local_dir, cost_dir, cost_kw = None, None, {}
     plan_dir, goal_ahead, front_dir, front_kw = None, None, None, {}
     explore_dir, explore_kw = None, {}
+    align_dir, align_apply, align_window = None, False, None
     roll_dir, roll_kw = None, {}
     level = "--level" in sys.argv
     if level:
@@ -643,6 +675,20 @@ def main():
             explore_kw["range"] = float(sys.argv[k + 1])
             assert 0 < explore_kw["range"] < float("inf")
             del sys.argv[k:k + 2]
+        if "--grid-align" in sys.argv:
+            k = sys.argv.index("--grid-align")
+            align_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-align-apply" in sys.argv:
+            sys.argv.remove("--grid-align-apply")
+            align_apply = True
+        if "--grid-align-window" in sys.argv:
+            k = sys.argv.index("--grid-align-window")
+            align_window = tuple(int(v) for v in sys.argv[k + 1].split(","))
+            assert len(align_window) == 2 and 0 <= align_window[0] <= 32 and 0 <= align_window[1] <= 32
+            del sys.argv[k:k + 2]
+        assert local_dir or not align_dir
+        assert align_dir or not (align_apply or align_window)
         assert cost_dir or not plan_dir
         assert cost_dir or not front_dir
         assert cost_dir or not explore_dir
@@ -697,7 +743,7 @@ def main():
         os.makedirs(panes_dir, exist_ok=True)
     if len(sys.argv) < 3:
         raise SystemExit(__doc__)
-    from svhip import kitti, view
+    from svhip import grid, kitti, view
     calib = kitti.read_cam_to_cam(sys.argv[2])
     limit = int(sys.argv[3]) if len(sys.argv) > 3 else 1 << 30
     rp = None
@@ -722,6 +768,9 @@ def main():
     if explore_dir:
         os.makedirs(explore_dir, exist_ok=True)
         open(os.path.join(explore_dir, "explore.jsonl"), "w").close()
+    if align_dir:
+        os.makedirs(align_dir, exist_ok=True)
+        open(os.path.join(align_dir, "align.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -730,6 +779,8 @@ def main():
         p.enable_grid(grid_cell, grid_size, level)
     if local_dir:
         p.enable_grid_local(grid_cell, grid_size)
+    if align_dir:
+        p.enable_grid_align(align_apply, align_window or (8, 8))
     if cost_dir:
         p.set_grid_cost(**cost_kw)
     if plan_dir or front_dir or explore_dir:
@@ -740,7 +791,7 @@ def main():
         p.local.set_explore(**explore_kw)
     if roll_dir:
         p.enable_roll(ROLL_CURVATURES, 2.0 * grid_cell, ROLL_POSES, **roll_kw)
-    found = explored = rolled = ranked = 0
+    found = explored = rolled = ranked = aligned = 0
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -756,7 +807,14 @@ def main():
         if grid_dir:
             view.write_ppm(os.path.join(grid_dir, "grid_%06d.ppm" % (frames - 1)), p.render_grid())
         if local_dir:
+            p.align_last = None
             view.write_ppm(os.path.join(local_dir, "local_%06d.ppm" % (frames - 1)), p.local_step())
+        if align_dir and p.align_last is not None:
+            rec, applied, img = p.align_last
+            aligned += int(rec[0] == 0)
+            view.write_ppm(os.path.join(align_dir, "align_%06d.ppm" % (frames - 1)), img)
+            with open(os.path.join(align_dir, "align.jsonl"), "a") as f:
+                f.write(json.dumps(dict(zip(("frame",) + grid.ALIGN_FIELDS + ("applied",), [frames - 1] + [int(v) for v in rec] + [bool(applied)]))) + "\n")
         if cost_dir:
             view.write_ppm(os.path.join(cost_dir, "cost_%06d.ppm" % (frames - 1)), p.local.render_cost())
         if plan_dir:
@@ -821,6 +879,10 @@ def main():
     if explore_dir:
         print("exploration: the kept frontiers ranked within %d cells, a best one in %d of %d frames; %d images and explore.jsonl in %s" % (
             p.local.explore_params()[1], ranked, frames, frames, explore_dir))
+    if align_dir:
+        print("alignment: %d rotations x %d x %d translations per frame, a match in %d of %d frames%s; images and align.jsonl in %s" % (
+            2 * p.local.align_params.rot_n + 1, 2 * p.local.align_params.trans_n + 1, 2 * p.local.align_params.trans_n + 1, aligned, frames,
+            ", applied to the local grid" if align_apply else "", align_dir))
     if render_dir:
         n, images = p.view.record_human()
         for k in range(n):
