@@ -2191,9 +2191,10 @@ __device__ __forceinline__ float* post_map(const DevMaps& m, int z, int nside, i
 // speckle_sim_threshold: a symmetric relation, so segments are the connected
 // components of that graph and a parallel union-find gives the same sets.
 //
-//   k_seg_tile   : per 64x16 tile, union-find in LDS; label = tile-local root
-//   k_seg_border : global unions only across tile borders (path-halving finds)
-//   k_seg_sum    : local sizes of merged components added to their root
+//   k_seg_tile   : per 64x16 tile, union-find in LDS; label = tile-local root, or the verdict
+//                  where it is final inside the tile (kSegKeep / kSegRemove)
+//   k_seg_border : global unions only across tile borders, between undecided components
+//   k_seg_sum    : local sizes of merged undecided components added to their root
 //   k_seg_mask   : pixels of components below speckle_size become -10
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ int uf_find(const int32_t* L, int x) {
@@ -2300,8 +2301,17 @@ __device__ __forceinline__ bool tile_index(int tw, int th, int DW, int DH, int n
 }
 inline unsigned xcd_blocks(int total) { return (unsigned)(((total + 7) >> 3) << 3); }
 
+// Verdicts that are final inside the tile (min_size > 0).  The speckle stage only asks whether a component has
+// min_size pixels or more.  A tile-local component that large is kept whatever it joins across a seam (kSegKeep);
+// a smaller one that touches no border with another tile behind it is complete, and is removed (kSegRemove).  Only
+// small components on a seam stay undecided: they keep the label of their tile-local root, write their size and
+// enter the tile's root list, and k_seg_border / k_seg_sum work on them alone.  min_size == 0: every component is
+// undecided (the two-level labelling without the shortcut).
+constexpr int kSegInvalid = -1, kSegKeep = -2, kSegRemove = -3;
+constexpr int kSegTouch = 1 << 16;   // added to a root's LDS counter by a run on a seam (a tile has 1024 pixels)
+
 __global__ __launch_bounds__(256) void k_seg_tile(GroupDev G, DevMaps m, PostScratch S, int nside,
-                                                  int DW, int DH, float thr, int nz) {
+                                                  int DW, int DH, float thr, int min_size, int nz) {
     __shared__ float sD[CY][CX];
     __shared__ int sL[CX * CY];
     __shared__ int sC[CX * CY];
@@ -2362,13 +2372,16 @@ __global__ __launch_bounds__(256) void k_seg_tile(GroupDev G, DevMaps m, PostScr
         lds_union(sL, sL[i], sL[i - CX]);
     }
     __syncthreads();
-    // step 3: run starts find their root and add their length to it
+    // step 3: run starts find their root and add their length to it -- and, in the high bits of the same word,
+    // whether the run lies on a side of the tile that another tile lies beyond (an image edge is no seam)
 #pragma unroll
     for (int k = 0; k < CY / 4; k++) {
         const int ty = threadIdx.y + 4 * k, i = ty * CX + tx;
         if (len[k] > 0) {
             const int r = lds_find(sL, i);
-            atomicAdd(&sC[r], len[k]);
+            const bool touch = (ty == 0 && y0 > 0) || (ty == CY - 1 && y0 + CY < DH) ||
+                               (tx == 0 && x0 > 0) || (tx + len[k] == CX && x0 + CX < DW);
+            atomicAdd(&sC[r], len[k] + (touch ? kSegTouch : 0));
             len[k] = r;               // remembered for the compression below
         } else {
             len[k] = -1;
@@ -2385,17 +2398,24 @@ __global__ __launch_bounds__(256) void k_seg_tile(GroupDev G, DevMaps m, PostScr
         const int gx = x0 + tx, gy = y0 + ty;
         if (gx >= DW || gy >= DH) continue;
         const int gi = gy * DW + gx;
-        int label = -1, size = 0;
+        int label = kSegInvalid, size = 0;
         const int s = sL[i];
         if (s >= 0) {
             const int r = sL[s];      // pixel -> run start -> root (or start == root)
             const int root = sL[r] == r ? r : sL[r];
-            const int ry = root / CX, rx = root - ry * CX;
-            label = (y0 + ry) * DW + (x0 + rx);
-            if (root == i) size = sC[i];   // this pixel is the tile-local root
+            const int word = sC[root], n = word & (kSegTouch - 1);
+            if (min_size > 0 && n >= min_size) {
+                label = kSegKeep;
+            } else if (min_size > 0 && word < kSegTouch) {
+                label = kSegRemove;
+            } else {
+                const int ry = root / CX, rx = root - ry * CX;
+                label = (y0 + ry) * DW + (x0 + rx);
+                if (root == i) size = n;   // this pixel is the tile-local root of an undecided component
+            }
         }
-        S.labels[zo + gi] = label;
-        // The tile-local roots are listed per tile (in `tmp`, which is free until k_gap_tile; a tile's
+        S.labels[zo + gi] = label;        // (every pixel, whatever its class: the array is reused from group to group)
+        // The undecided tile-local roots are listed per tile (in `tmp`, which is free until k_gap_tile; a tile's
         // list starts where its pixels would start if the map were stored tile by tile, so it can hold
         // every pixel of the tile): k_seg_sum visits a few roots per tile instead of scanning the counts
         // of every pixel.  Positions from an LDS counter, the tile's count is written once.
@@ -2414,7 +2434,7 @@ __global__ __launch_bounds__(256) void k_seg_tile(GroupDev G, DevMaps m, PostScr
 
 // unions across tile borders: one thread per pixel of a tile's first row / column
 __global__ __launch_bounds__(256) void k_seg_border(GroupDev G, DevMaps m, PostScratch S, int nside,
-                                                    int DW, int DH, float thr, int nhor) {
+                                                    int DW, int DH, float thr, int nhor, int min_size) {
     int pair;
     const float* D = post_map(m, blockIdx.y, nside, &pair);
     if (!G.hdr->active[pair]) return;
@@ -2438,8 +2458,20 @@ __global__ __launch_bounds__(256) void k_seg_border(GroupDev G, DevMaps m, PostS
         if (y >= DH || x >= DW) return;
     }
     const int i = y * DW + x;
+    // The labels decide first.  An invalid pixel joins nothing; two components kept in their tiles gain nothing from
+    // a union (most joined pairs on a seam are of this kind, and they are what would make the forest deep).  A
+    // component removed in its tile touches no seam, so a negative label on a seam is either of the two.
+    const int la = L[i], lb = L[i - step];
+    if (la == kSegInvalid || lb == kSegInvalid) return;
+    if (la < 0 && lb < 0) return;
     const float d = D[i], q = D[i - step];
     if (!seg_joined(d, q, thr)) return;
+    if (la < 0 || lb < 0) {
+        // joined to a kept component: the undecided side is large too.  The mark goes to its tile-local root
+        // (idempotent, no overflow); k_seg_sum carries it into the global root.
+        atomicMax(S.counts + (size_t)blockIdx.y * DW * DH + (la < 0 ? lb : la), min_size);
+        return;
+    }
     // skip when the previous pixel along the border already joins the same two components
     const int along = step == 1 ? DW : 1;
     const bool has_prev = step == 1 ? (y % CY != 0) : (x % CX != 0);
@@ -2447,7 +2479,7 @@ __global__ __launch_bounds__(256) void k_seg_border(GroupDev G, DevMaps m, PostS
         const float dp = D[i - along], qp = D[i - step - along];
         if (seg_joined(d, dp, thr) && seg_joined(q, qp, thr) && seg_joined(dp, qp, thr)) return;
     }
-    uf_union(L, L[i], L[i - step]);
+    uf_union(L, la, lb);
 }
 
 // add the local size of every merged tile-local component to its global root: one wave per tile of
@@ -2467,7 +2499,8 @@ __global__ __launch_bounds__(256) void k_seg_sum(GroupDev G, PostScratch S, int 
     int32_t* L = S.labels + zo;
     for (int k = lane; k < nroots; k += 64) {
         // a tile-local root that is not a global root is never added to, so its entry still is the
-        // tile-local size written by k_seg_tile (the seam merges of k_seg_border changed labels only)
+        // tile-local size written by k_seg_tile (the seam merges of k_seg_border changed labels only), or
+        // min_size where k_seg_border found it joined to a component kept in its tile
         const int i = list[k];
         const int size = S.counts[zo + i];
         const int root = uf_find(L, i);
@@ -2475,8 +2508,10 @@ __global__ __launch_bounds__(256) void k_seg_sum(GroupDev G, PostScratch S, int 
             L[i] = root;
             int32_t* c = S.counts + zo + root;
             // only "below speckle_size or not" is ever asked of a count
-            if (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < min_size)
-                atomicAdd(c, size);
+            if (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < min_size) {
+                if (size >= min_size) atomicMax(c, min_size);   // (a mark: raised, not added, whatever min_size is)
+                else atomicAdd(c, size);
+            }
         }
     }
 }
@@ -2490,10 +2525,12 @@ __global__ __launch_bounds__(256) void k_seg_mask(GroupDev G, DevMaps m, PostScr
     if (!G.hdr->active[pair]) return;
     const size_t zo = (size_t)blockIdx.y * n;
     const int s = S.labels[zo + i];
-    if (s < 0) {
+    if (s == kSegInvalid) {
         // an invalid pixel is a segment of one pixel (elas.cpp:1244-1317)
         if (1 < min_size) D[i] = -10.f;
-    } else if (S.counts[zo + S.labels[zo + s]] < min_size) {
+    } else if (s == kSegRemove) {
+        D[i] = -10.f;
+    } else if (s >= 0 && S.counts[zo + S.labels[zo + s]] < min_size) {   // (kSegKeep: nothing to look up)
         D[i] = -10.f;
     }
 }
@@ -3226,17 +3263,20 @@ void launch_segments_label(const LaunchCtx& cx, const svh_elas_params& p, const 
     const dim3 lin((n + 255) / 256, z), b256(256);
     const dim3 tiles((d.DW + CX - 1) / CX, (d.DH + CY - 1) / CY, z);
     static const bool tile_xcd = !(svh::env("SVH_TILE_XCD") && atoi(svh::env("SVH_TILE_XCD")) == 0);
+    // SVH_SEG_SETTLE=0 (A/B and the equivalence test): k_seg_tile leaves every component undecided
+    static const bool settle = !(svh::env("SVH_SEG_SETTLE") && atoi(svh::env("SVH_SEG_SETTLE")) == 0);
+    const int tile_min = settle ? std::max(min_size, 1) : 0;   // (below 2 every valid pixel is kept)
     if (tile_xcd)
         LAUNCH("k_seg_tile", k_seg_tile, dim3(xcd_blocks((int)(tiles.x * tiles.y * tiles.z))), dim3(CX, 4), G, in, S, nside,
-               d.DW, d.DH, p.speckle_sim_threshold, z);
+               d.DW, d.DH, p.speckle_sim_threshold, tile_min, z);
     else
         LAUNCH("k_seg_tile", k_seg_tile, tiles, dim3(CX, 4), G, in, S, nside, d.DW, d.DH,
-               p.speckle_sim_threshold, 0);
+               p.speckle_sim_threshold, tile_min, 0);
     const int nhor = ((d.DH - 1) / CY) * d.DW;              // pixels on interior horizontal borders
     const int nver = ((d.DW - 1) / CX) * d.DH;              // ... and vertical ones
     if (nhor + nver > 0)
         LAUNCH("k_seg_border", k_seg_border, dim3((nhor + nver + 255) / 256, z), b256, G, in, S, nside,
-               d.DW, d.DH, p.speckle_sim_threshold, nhor);
+               d.DW, d.DH, p.speckle_sim_threshold, nhor, min_size);
     LAUNCH("k_seg_sum", k_seg_sum, dim3((tiles.x * tiles.y + 3) / 4, z), b256, G, S, nside, d.DW, d.DH, min_size);
 }
 
@@ -3344,15 +3384,25 @@ __global__ __launch_bounds__(256) void k_gap_tile(GroupDev G, DevMaps m, PostScr
             const int gy = y0 - HG + er[k], gx = x0 - HG + ec[k];
             const bool in = er[k] < AH && gy >= 0 && gy < DH && gx >= 0 && gx < DW;
             val[k] = in ? D[(size_t)gy * DW + gx] : -10.f;
-            lab[k] = (in && min_size > 0) ? L[(size_t)gy * DW + gx] : -1;
+            lab[k] = (in && min_size > 0) ? L[(size_t)gy * DW + gx] : kSegInvalid;
         }
         if (min_size > 0) {
+            // verdicts settled in the tile need no look-up (kSegKeep) or read as removed (kSegRemove); only the
+            // undecided pixels, a few per cent, walk label -> root -> size, and a wave without one skips both levels
+            bool need = false;
 #pragma unroll
-            for (int k = 0; k < NE; k++)
-                if (lab[k] >= 0) lab[k] = L[lab[k]];           // tile root -> component root
+            for (int k = 0; k < NE; k++) {
+                if (lab[k] == kSegRemove) val[k] = -10.f;
+                need |= lab[k] >= 0;
+            }
+            if (__any(need)) {
 #pragma unroll
-            for (int k = 0; k < NE; k++)
-                if (lab[k] >= 0 && Cn[lab[k]] < min_size) val[k] = -10.f;
+                for (int k = 0; k < NE; k++)
+                    if (lab[k] >= 0) lab[k] = L[lab[k]];           // tile root -> component root
+#pragma unroll
+                for (int k = 0; k < NE; k++)
+                    if (lab[k] >= 0 && Cn[lab[k]] < min_size) val[k] = -10.f;
+            }
         }
 #pragma unroll
         for (int k = 0; k < NE; k++)
