@@ -179,6 +179,37 @@
  * field stay as they were.  After SVH_ERR_HIP in an align entry the same holds; the align field and the last volume are invalid and
  * the next call computes them again.
  *
+ * DYNAMICS: the world moves.  Everything above accumulates since the last clear, so a car that crosses in front of the camera
+ * leaves a wall of obstacle cells along its track.  With the dynamics set (svh_grid_set_dynamics) a frame can be given as an
+ * OBSERVATION (svh_grid_observe_*) instead of an add: it clears obstacle cells that the frame's sight lines contradict, and ages
+ * cells that have not been seen for long.  The arithmetic is stereo-vision_amd/csrc/grid_dyn_core.h (restated in
+ * tests/grid_dyn_ref.py); integers after the placement of a point.  Observations are numbered by a STAMP, int32, 1 for the first
+ * after a clear; svh_grid_clear and svh_grid_set_window reset it.  An observation has three phases, each a pure function of its
+ * inputs, so the result depends only on the state before and the MULTISET of the frame's points:
+ *   1  FRAME RECORD.  Every point is placed as an add places it; the frame's low and overhead points are accumulated per cell into
+ *      a frame record (fcount, foverhead, fkmin, fkmax, fhsum, fvsum) beside the cell, not into it.  The statistics count as in an add.
+ *   2  SIGHT LINES.  For every end cell with fcount > 0 one line of weight fcount runs from the origin's cell: the cells of a
+ *      free-space ray, k = 0 .. n - 1.  Each gains fcount in PASS, so PASS and the ray statistics are what svh_grid_add_points_from
+ *      would have left.  The line has a height in 1/1024: q_k = q_o + rdiv64(k (q_e - q_o), n), rdiv64 being rdiv in 64 bits,
+ *      q_o = rintf(h * 1024) of the origin and q_e = rintf(fhmin * 1024), the frame's lowest low point of the end cell.  A stored
+ *      cell is TALL if COUNT > 0 and HMAX > step; its body is [rintf(HMIN * 1024), rintf(HMAX * 1024) - rintf(margin * 1024)].  A line
+ *      step in a tall cell goes THROUGH it iff q_k lies in the body, ends included.  A line above the body sees over the obstacle,
+ *      one below passes under it (a trailer); neither contradicts it.  THROUGH of a cell is the sum of the weights of the lines that
+ *      go through.
+ *   3  SETTLE, per window cell, in this order.  Confirm: fcount > 0 and the frame's highest low point > step: CONTRA = 0.  Otherwise,
+ *      if the cell is tall and THROUGH >= min_through: CONTRA += 1.  If clear_frames > 0 and CONTRA >= clear_frames the cell is
+ *      CLEARED: its low points are forgotten (OVERHEAD and PASS stay: a bridge over a cleared car is still a bridge), CONTRA = 0.
+ *      If max_age > 0, the cell stores a point and stamp - LAST > max_age it is AGED: everything but PASS is forgotten, CONTRA = 0; a
+ *      cell cleared in the same observation counts as cleared only.  Then the frame record is merged into the cell, and LAST = stamp
+ *      if the frame had a point in it.
+ * CONTRA and LAST (0 = never) belong to the cell: a scroll keeps them for cells that stay and empties them in the strips that
+ * enter, svh_grid_clear and svh_grid_set_window empty them.  With clear_frames = 0 and max_age = 0 an observation leaves every
+ * plane of svh_grid_get and svh_grid_get_local and the statistics bit-equal to svh_grid_add_points_from of the same arguments.
+ * The plain add entries stay legal with the layer set: they write the accumulators directly and leave CONTRA and LAST alone -- a
+ * cell filled only by adds has LAST 0 and, under max_age > 0, is aged by the first observation after stamp max_age.  An observation
+ * invalidates what an add invalidates.  After SVH_ERR_HIP inside svh_grid_observe_* the grid is EMPTY as after a failed add:
+ * statistics, stamp, CONTRA and LAST included; the parameters of the layer stay set and the next observation has stamp 1.
+ *
  * Plain C like svh_view.h.  An object has its own stream and every call returns when it is complete.  Calls return
  * SVH_OK or a negative SVH_ERR_*; svh_last_error() has the text.  SVH_ERR_BAD_ARG -- a null pointer, parameters out of
  * the ranges below, n < 0, n > 0 with a null array, a device array that is not 16-byte aligned, an unknown plane or
@@ -507,6 +538,38 @@ int32_t   svh_grid_align_correction(svh_grid* g, int32_t k, int32_t ta, int32_t 
 /* svh_grid_render_local with the last alignment over it: the cells of the scan at the identity (255, 224, 0), then the cells of the
  * scan placed at the best (0, 224, 255), then the pivot's cell (255, 255, 255); the later primitive wins */
 int32_t   svh_grid_render_align(svh_grid* g, uint8_t* rgb, int32_t on_device);
+
+
+typedef struct svh_grid_dyn_params {
+    int32_t clear_frames;      /* 2: contradicting observations in a row that clear a cell; 0..65535, 0 = never */
+    int32_t min_through;       /* 3: weight of through-lines that makes an observation contradict a cell; >= 1 */
+    float   margin;            /* 0.1: how far below the stored top a line must pass; finite, 0 <= margin < 2^20 */
+    int32_t max_age;           /* 0: observations without a point after which a cell is emptied; >= 0, 0 = never */
+} svh_grid_dyn_params;
+
+void      svh_grid_dyn_params_default(svh_grid_dyn_params* p);
+/* sets the layer and allocates its planes.  SVH_ERR_BAD_ARG, nothing changed: a parameter out of its range.  A grid is created
+ * WITHOUT the layer: the observe entries, svh_grid_get_dynamics, svh_grid_get_dyn and svh_grid_render_dyn return SVH_ERR_BAD_ARG until
+ * this call succeeds.  New parameters keep CONTRA and LAST.  p == NULL drops the layer and frees its planes; setting it again
+ * starts from empty planes (the stamp goes on).  After SVH_ERR_HIP the parameters are set and the planes are empty */
+int32_t   svh_grid_set_dynamics(svh_grid* g, const svh_grid_dyn_params* p);
+int32_t   svh_grid_get_dynamics(svh_grid* g, svh_grid_dyn_params* p);
+/* one observation: the arguments and the origin rule of svh_grid_add_points_from.  n may be 0: a frame without points still
+ * advances the stamp and ages.  SVH_ERR_BAD_ARG, before anything is read or changed: the origin is not a low point of the window,
+ * the dynamics are not set, or the stamp has reached 2^31 - 1.  One host wait per call (a host array: one more per 2^22 points) */
+int32_t   svh_grid_observe_points(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device, const double origin[3]);
+/* ... the points of n_lists lists of the view, from first_list on, as svh_grid_add_view_lists_from takes them */
+int32_t   svh_grid_observe_view_lists(svh_grid* g, svh_view* v, int32_t first_list, int32_t n_lists, const double origin[3]);
+/* planes of svh_grid_get_dyn, int32, laid out as those of svh_grid_get; a device array is 4-byte aligned */
+#define SVH_GRID_DYN_AGE     0   /* stamp - LAST: observations since the cell last had a point of a frame; -1 where LAST is 0 */
+#define SVH_GRID_DYN_CONTRA  1   /* contradicting observations in a row */
+#define SVH_GRID_DYN_THROUGH 2   /* THROUGH of the last observation; 0 in strips that entered since */
+int32_t   svh_grid_get_dyn(svh_grid* g, int32_t plane, void* out, int32_t on_device);
+/* since the last clear: out[0] observations (the stamp), out[1] cells cleared, out[2] cells aged, out[3] frames x cells confirmed */
+int32_t   svh_grid_get_dyn_stats(svh_grid* g, int64_t out[4]);
+/* svh_grid_render_local; a cell with CONTRA > 0 is tinted (red and green bytes c + (255 - c) / 2), a cell that the last
+ * observation cleared or aged is (255, 0, 255) */
+int32_t   svh_grid_render_dyn(svh_grid* g, uint8_t* rgb, int32_t on_device);
 
 #ifdef __cplusplus
 }

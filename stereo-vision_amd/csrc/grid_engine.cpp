@@ -8,7 +8,8 @@
 // (grid_front_kernels.hip): the frontiers -- mask, union-find labelling, the table of components, run by front_run() here;
 // (grid_roll_kernels.hip): the rollouts -- footprint costs, the scoring of a set of candidates and its best;
 // (grid_explore_kernels.hip): the exploration layer -- the gain of viewpoints, the ranking of the frontiers, run by explore_rank() here;
-// (grid_align_kernels.hip): the alignment layer -- the field, the scan of a frame's obstacle points, the volume of scores, run by align() here.
+// (grid_align_kernels.hip): the alignment layer -- the field, the scan of a frame's obstacle points, the volume of scores, run by align() here;
+// (grid_dyn_kernels.hip): the dynamics -- the sight lines and the settle of an observation, run by observe() here.
 // The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
@@ -29,6 +30,10 @@
 // plan parameters change.  Gains and VIEW planes are computed per call.
 // The alignment layer caches its field F, derived from STATE (afield_valid), until the accumulators, the offsets or the align
 // parameters change, and keeps the scan, the volume and the record of the last alignment for the getters and the image.
+// The dynamics keep CONTRA, LAST, the THROUGH and the events of the last observation and the bodies of the cells at the cells' slots
+// (they travel with the torus and are cleared as lazily as the accumulators, dyn_need_clear); the body plane is kept by the settle
+// and written anew (body_valid) after anything else wrote the accumulators.  The frame record and `ends` are scratch, empty between
+// observations (frame_clean, ends_clean).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -221,6 +226,16 @@ struct svh_grid {
     int32_t align_rec[grid::ALIGN_REC] = {0}, align_Pa = 0, align_Pb = 0;   // its record and pivot sub
     svh_grid_stats st{0, 0, 0, 0, 0};
     int64_t rays = 0, ray_cells = 0;
+    bool dyn_on = false;        // the dynamics: svh_grid_set_dynamics has succeeded and the layer has not been dropped
+    grid::DynParams dyn{};
+    HipBuf<uint8_t> dynp;       // DYN_BYTES per cell: body | CONTRA | LAST | kept THROUGH | THROUGH in flight | event, by slot
+    HipBuf<uint8_t> frame;      // FRAME_BYTES per cell: the frame record, kmin | kmax | count | overhead | hsum | vsum, by slot
+    bool body_valid = false;    // the body plane is that of the accumulators as they are, under the parameters in force
+    HipBuf<int32_t> d_dyn;      // a plane of svh_grid_get_dyn bound for the host
+    bool dyn_need_clear = true; // dynp does not hold the empty state yet
+    bool frame_clean = false;   // the frame record is empty and `ends` all zero: true between observations that succeeded
+    int32_t stamp = 0;          // of the last observation; 0 after a clear
+    int64_t dyn_stats[grid::DS_WORDS] = {0, 0, 0, 0};
 
     grid::Cells cells() const {
         uint8_t* b = acc.p;
@@ -241,6 +256,17 @@ struct svh_grid {
     int32_t* r_pot() const { return (int32_t*)reach.p; }
     int32_t* f_label() const { return (int32_t*)front.p; }
     uint8_t* f_flags() const { return front.p + 4 * ncells; }
+    grid::DynPlanes dplanes() const {
+        uint8_t* b = dynp.p;
+        const size_t n = ncells;
+        return grid::DynPlanes{(int2*)b, (int32_t*)(b + 8 * n), (int32_t*)(b + 12 * n), (int32_t*)(b + 16 * n), (int32_t*)(b + 20 * n), b + 24 * n};
+    }
+    grid::Cells fcells() const {
+        uint8_t* b = frame.p;
+        const size_t n = ncells;
+        return grid::Cells{(uint32_t*)b, (uint32_t*)(b + 4 * n), (int32_t*)(b + 8 * n), (int32_t*)(b + 12 * n),
+                           (unsigned long long*)(b + 16 * n), (unsigned long long*)(b + 24 * n), nullptr};
+    }
 };
 
 namespace {
@@ -253,6 +279,10 @@ void mark_empty(svh_grid* g) {
     invalidate(g);
     g->st = svh_grid_stats{0, 0, 0, 0, 0};
     g->rays = g->ray_cells = 0;
+    g->dyn_need_clear = true;
+    g->frame_clean = g->body_valid = false;
+    g->stamp = 0;
+    for (int k = 0; k < grid::DS_WORDS; k++) g->dyn_stats[k] = 0;
 }
 
 // the accumulators become those of the empty grid; the statistics are not touched
@@ -268,13 +298,38 @@ int ready(svh_grid* g) {
     if (g->acc.cap < g->ncells * grid::CELL_BYTES) g->need_clear = true;
     GRID_GROW(g->acc, g->ncells * grid::CELL_BYTES);
     GRID_GROW(g->fin, g->ncells * kFinalBytes);
-    GRID_GROW(g->d_stats, grid::STAT_WORDS * sizeof(unsigned long long));
-    GRID_GROW(g->h_stats, grid::STAT_WORDS * sizeof(unsigned long long));
+    GRID_GROW(g->d_stats, grid::STAT_ALL * sizeof(unsigned long long));
+    GRID_GROW(g->h_stats, grid::STAT_ALL * sizeof(unsigned long long));
     if (g->need_clear) {
         const int rc = fill_empty(g);
         if (rc) return rc;
-        GRID_TRY(copy, hipMemsetAsync(g->d_stats, 0, grid::STAT_WORDS * sizeof(unsigned long long), g->stream));
+        GRID_TRY(copy, hipMemsetAsync(g->d_stats, 0, grid::STAT_ALL * sizeof(unsigned long long), g->stream));
         g->need_clear = false;   // in stream order before whatever the entry does next; every entry ends with a wait
+    }
+    return SVH_OK;
+}
+
+// the binning of n > 0 points, host or device, by a job that is complete but for the points: a host array goes through the
+// staging buffers in chunks
+int bin_points(svh_grid* g, grid::BinJob& j, const float* xyzv, int64_t n, bool on_device) {
+    hipStream_t s = g->stream;
+    if (on_device) {
+        j.pts = (const float4*)xyzv;
+        j.n = n;
+        GRID_TRY(launch, (grid::launch_bin(s, j), hipGetLastError()));
+        return SVH_OK;
+    }
+    const int64_t room = std::min(n, kHostChunk);
+    GRID_GROW(g->h_pts, (size_t)room * sizeof(float4));
+    GRID_GROW(g->d_pts, (size_t)room * sizeof(float4));
+    for (int64_t at = 0; at < n; at += room) {
+        const int64_t m = std::min(room, n - at);
+        if (at > 0) GRID_TRY(wait, hipStreamSynchronize(s));   // the staging buffer is read until here
+        memcpy(g->h_pts, xyzv + 4 * at, (size_t)m * sizeof(float4));
+        GRID_TRY(copy, hipMemcpyAsync(g->d_pts, g->h_pts, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, s));
+        j.pts = g->d_pts;
+        j.n = m;
+        GRID_TRY(launch, (grid::launch_bin(s, j), hipGetLastError()));
     }
     return SVH_OK;
 }
@@ -285,6 +340,7 @@ int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origi
     int rc = ready(g);
     if (rc) return rc;
     invalidate(g);
+    g->body_valid = false;   // the dynamics: the accumulators change behind the layer
     grid::BinJob j;
     j.prm = g->prm;
     j.cells = g->cells();
@@ -297,24 +353,7 @@ int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origi
         g->ends_clean = false;   // until the rays of this call have zeroed what its binning counts
         j.ends = g->ends;
     }
-    if (on_device) {
-        j.pts = (const float4*)xyzv;
-        j.n = n;
-        GRID_TRY(launch, (grid::launch_bin(s, j), hipGetLastError()));
-    } else {
-        const int64_t room = std::min(n, kHostChunk);
-        GRID_GROW(g->h_pts, (size_t)room * sizeof(float4));
-        GRID_GROW(g->d_pts, (size_t)room * sizeof(float4));
-        for (int64_t at = 0; at < n; at += room) {
-            const int64_t m = std::min(room, n - at);
-            if (at > 0) GRID_TRY(wait, hipStreamSynchronize(s));   // the staging buffer is read until here
-            memcpy(g->h_pts, xyzv + 4 * at, (size_t)m * sizeof(float4));
-            GRID_TRY(copy, hipMemcpyAsync(g->d_pts, g->h_pts, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, s));
-            j.pts = g->d_pts;
-            j.n = m;
-            GRID_TRY(launch, (grid::launch_bin(s, j), hipGetLastError()));
-        }
-    }
+    if ((rc = bin_points(g, j, xyzv, n, on_device))) return rc;
     if (origin >= 0) {
         grid::RayJob r;
         r.prm = g->prm;
@@ -335,6 +374,80 @@ int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origi
     g->st.added += n;
     g->st.binned = (int64_t)h[grid::LOW], g->st.overhead = (int64_t)h[grid::OVERHEAD];
     g->st.outside = (int64_t)h[grid::OUTSIDE], g->st.unplaced = (int64_t)h[grid::UNPLACED];
+    return SVH_OK;
+}
+
+// ---- the dynamics ---------------------------------------------------------------------------------------------------------
+// the layer's planes exist and hold what the object says they hold; after ready()
+int dyn_ready(svh_grid* g) {
+    if (g->dynp.cap < g->ncells * grid::DYN_BYTES) g->dyn_need_clear = true;
+    GRID_GROW(g->dynp, g->ncells * grid::DYN_BYTES);
+    if (g->dyn_need_clear) {
+        g->body_valid = false;   // all zero is the body plane of the empty grid, which this one may not be
+        GRID_TRY(copy, hipMemsetAsync(g->dynp, 0, g->ncells * grid::DYN_BYTES, g->stream));
+        g->dyn_need_clear = false;   // in stream order before whatever the entry does next; every entry ends with a wait
+    }
+    return SVH_OK;
+}
+
+// One observation: n >= 0 points, host or device, with arguments that have been checked, from the origin's logical cell `origin`
+// at the height q_o.  Phase 1 bins into the frame record, phase 2 casts the sight lines, phase 3 settles; one wait at the end (a
+// host array of more than kHostChunk points waits once more per further chunk).  A frame without points still ages the cells.
+int observe(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origin, int32_t q_o) {
+    int rc = ready(g);
+    if (rc || (rc = dyn_ready(g))) return rc;
+    invalidate(g);
+    hipStream_t s = g->stream;
+    const size_t nc = g->ncells;
+    if (g->ends.cap < nc * sizeof(int32_t)) g->ends_clean = false;
+    if (g->frame.cap < nc * grid::FRAME_BYTES) g->frame_clean = false;
+    GRID_GROW(g->ends, nc * sizeof(int32_t));
+    GRID_GROW(g->frame, nc * grid::FRAME_BYTES);
+    if (!g->ends_clean) GRID_TRY(copy, hipMemsetAsync(g->ends, 0, nc * sizeof(int32_t), s));
+    if (!g->frame_clean) {
+        GRID_TRY(copy, hipMemsetAsync(g->frame, 0xFF, 4 * nc, s));
+        GRID_TRY(copy, hipMemsetAsync(g->frame + 4 * nc, 0, (grid::FRAME_BYTES - 4) * nc, s));
+        GRID_TRY(copy, hipMemsetAsync(g->dplanes().through, 0, 4 * nc, s));
+    }
+    g->ends_clean = g->frame_clean = false;   // until this observation has settled
+    const int32_t stamp = g->stamp + 1;
+    if (n > 0) {
+        grid::BinJob j;
+        j.prm = g->prm;
+        j.cells = g->fcells();
+        j.stats = g->d_stats;
+        j.ends = g->ends;
+        if ((rc = bin_points(g, j, xyzv, n, on_device))) return rc;
+        grid::SightJob v;
+        v.prm = g->prm, v.dyn = g->dyn;
+        v.origin = (uint32_t)origin, v.q_o = q_o;
+        v.ends = g->ends;
+        v.cells = g->cells(), v.frame = g->fcells();
+        v.write_body = !g->body_valid;
+        v.planes = g->dplanes();
+        v.ray_cells = g->d_stats + grid::STAT_RAY_CELLS;
+        GRID_TRY(launch, (grid::launch_sight(s, v), hipGetLastError()));
+    }
+    grid::SettleJob t;
+    t.prm = g->prm, t.dyn = g->dyn;
+    t.stamp = stamp;
+    t.cells = g->cells(), t.frame = g->fcells();
+    t.planes = g->dplanes();
+    t.stats = g->d_stats + grid::STAT_DYN - grid::DS_CLEARED;
+    GRID_TRY(launch, (grid::launch_settle(s, t), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(g->h_stats, g->d_stats, grid::STAT_ALL * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    const unsigned long long* h = g->h_stats;
+    g->ends_clean = g->frame_clean = true;
+    g->rays += (int64_t)h[grid::LOW] - g->st.binned;
+    g->ray_cells = (int64_t)h[grid::STAT_RAY_CELLS];
+    g->st.added += n;
+    g->st.binned = (int64_t)h[grid::LOW], g->st.overhead = (int64_t)h[grid::OVERHEAD];
+    g->st.outside = (int64_t)h[grid::OUTSIDE], g->st.unplaced = (int64_t)h[grid::UNPLACED];
+    if (n > 0) g->body_valid = true;   // k_grid_body wrote it or it was valid, and k_grid_settle kept it
+    g->stamp = stamp;
+    g->dyn_stats[grid::DS_OBSERVATIONS] = stamp;
+    for (int k = grid::DS_CLEARED; k < grid::DS_WORDS; k++) g->dyn_stats[k] = (int64_t)h[grid::STAT_DYN + k - grid::DS_CLEARED];
     return SVH_OK;
 }
 
@@ -395,6 +508,47 @@ int render(svh_grid* g, int32_t mode, uint8_t* rgb, bool on_device) {
     j.intensity = g->bplane(B_INTENSITY), j.cls = g->bplane(B_CLASS);
     j.rgb = on_device ? rgb : g->d_rgb.p;
     GRID_TRY(launch, (grid::launch_render(g->stream, j), hipGetLastError()));
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+        return rc;
+    }
+    g->final_valid = true;
+    return SVH_OK;
+}
+
+// a plane of the layer in logical order
+int get_dyn(svh_grid* g, int32_t plane, int32_t* out, bool on_device) {
+    int rc = ready(g);
+    if (rc || (rc = dyn_ready(g))) return rc;
+    if (!on_device) GRID_GROW(g->d_dyn, g->ncells * sizeof(int32_t));
+    int32_t* dst = on_device ? out : g->d_dyn.p;
+    GRID_TRY(launch, (grid::launch_dyn_get(g->stream, g->prm, plane, g->stamp, g->dplanes(), dst), hipGetLastError()));
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+        return SVH_OK;
+    }
+    return deliver(g, g->d_dyn, g->ncells * sizeof(int32_t), out, false);
+}
+
+// svh_grid_render_dyn: render()'s steps with the layer's kernel
+int render_dyn(svh_grid* g, uint8_t* rgb, bool on_device) {
+    int rc = ready(g);
+    if (rc || (rc = dyn_ready(g))) return rc;
+    const size_t bytes = g->ncells * 3;
+    if (!on_device) {
+        GRID_GROW(g->d_rgb, bytes);
+        GRID_GROW(g->h_out, bytes);
+    }
+    if ((rc = finalise(g))) return rc;
+    grid::RenderJob j;
+    j.prm = g->prm;
+    j.mode = grid::M_LOCAL;
+    j.count = g->iplane(F_COUNT), j.pass = g->iplane(F_PASS);
+    j.hmin = g->fplane(F_HMIN), j.hmax = g->fplane(F_HMAX), j.hmean = g->fplane(F_HMEAN);
+    j.intensity = g->bplane(B_INTENSITY), j.cls = g->bplane(B_CLASS);
+    j.rgb = on_device ? rgb : g->d_rgb.p;
+    GRID_TRY(launch, (grid::launch_render_dyn(g->stream, j, g->dplanes()), hipGetLastError()));
     if (on_device) {
         GRID_TRY(wait, hipStreamSynchronize(g->stream));
     } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
@@ -1381,14 +1535,17 @@ int scroll(svh_grid* g, int32_t da, int32_t db) {
     int rc = ready(g);
     if (rc) return rc;
     const int64_t ada = da < 0 ? -(int64_t)da : da, adb = db < 0 ? -(int64_t)db : db;
+    const bool dyn = g->dyn_on && !g->dyn_need_clear && g->dynp.cap >= g->ncells * grid::DYN_BYTES;   // the layer has cells to reset
     if (ada >= g->prm.nx || adb >= g->prm.nz) {
         if ((rc = fill_empty(g))) return rc;
+        if (dyn) GRID_TRY(copy, hipMemsetAsync(g->dynp, 0, g->ncells * grid::DYN_BYTES, g->stream));
     } else {
         grid::EnterJob j;
         j.prm = g->prm;
         j.da = da, j.db = db;
         j.cells = g->cells();
         GRID_TRY(launch, (grid::launch_enter(g->stream, j), hipGetLastError()));
+        if (dyn) GRID_TRY(launch, (grid::launch_dyn_enter(g->stream, g->prm, da, db, g->dplanes()), hipGetLastError()));
     }
     GRID_TRY(wait, hipStreamSynchronize(g->stream));
     return SVH_OK;
@@ -1405,12 +1562,15 @@ bool position(const double xyz[3], float p[3]) {
 }
 
 // the logical index of the cell rays are cast from, or -1: the origin must be a LOW point of the window
-int64_t origin_cell(const svh_grid* g, const double origin[3]) {
+int64_t origin_cell(const svh_grid* g, const double origin[3], int32_t* q = nullptr) {
     float p[3];
     if (!position(origin, p)) return -1;
     const grid::Placed r = grid::place(g->prm, p[0], p[1], p[2], 0.f);
+    if (q) *q = r.q;   // an observation's q_o
     return r.fate == grid::LOW ? (int64_t)r.cell : -1;
 }
+
+const char* const kNoDyn =": the dynamics are not set (svh_grid_set_dynamics)";
 
 }  // namespace
 
@@ -2104,6 +2264,187 @@ int32_t svh_grid_render_align(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_align") + kNoAlign);
     if (!g->align_last) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_align: there is no alignment to draw: none since the parameters were set, or the last one failed");
     return drained(g, render_align(g, rgb, on_device != 0));
+}
+
+void svh_grid_dyn_params_default(svh_grid_dyn_params* p) {
+    if (!p) return;
+    p->clear_frames = 2, p->min_through = 3, p->margin = 0.1f, p->max_age = 0;
+}
+
+int32_t svh_grid_set_dynamics(svh_grid* g, const svh_grid_dyn_params* p) {
+    if (!g) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_dynamics: null argument");
+    if (!p) {   // the layer and its planes go
+        (void)hipSetDevice(g->device);
+        if (g->stream) (void)hipStreamSynchronize(g->stream);
+        g->dyn_on = false;
+        g->dynp = HipBuf<uint8_t>();
+        g->frame = HipBuf<uint8_t>();
+        g->d_dyn = HipBuf<int32_t>();
+        g->dyn_need_clear = true;
+        g->frame_clean = g->body_valid = false;
+        return SVH_OK;
+    }
+    grid::DynParams q{p->clear_frames, p->min_through, p->margin, p->max_age, 0};
+    if (!grid::dyn_derive(q))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_dynamics: parameters out of range (include/svh_grid.h)");
+    g->dyn = q;   // CONTRA and LAST stay when the layer was set already; the bodies follow the margin
+    g->dyn_on = true;
+    g->body_valid = false;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipSetDevice(g->device));
+        if (g->dynp.cap < g->ncells * grid::DYN_BYTES) g->dyn_need_clear = true;   // a growth discards
+        GRID_GROW(g->dynp, g->ncells * grid::DYN_BYTES);
+        return SVH_OK;
+    }();
+    if (rc) g->dyn_need_clear = true;
+    return drained(g, rc);
+}
+
+int32_t svh_grid_get_dynamics(svh_grid* g, svh_grid_dyn_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_dynamics: null argument");
+    if (!g->dyn_on) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_dynamics") + kNoDyn);
+    p->clear_frames = g->dyn.clear_frames, p->min_through = g->dyn.min_through, p->margin = g->dyn.margin, p->max_age = g->dyn.max_age;
+    return SVH_OK;
+}
+
+int32_t svh_grid_observe_points(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device, const double origin[3]) {
+    if (!g || n < 0 || (n > 0 && !xyzv) || !origin) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_points: bad arguments");
+    if (on_device && ((uintptr_t)xyzv & 15)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_points: a device array must be 16-byte aligned");
+    if (!g->dyn_on) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_observe_points") + kNoDyn);
+    int32_t q_o = 0;
+    const int64_t oc = origin_cell(g, origin, &q_o);
+    if (oc < 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_points: the origin must be finite, inside the window and not above the clearance");
+    if (g->stamp == grid::STAMP_LIMIT) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_points: 2^31 - 1 observations since the last clear");
+    if (n > kMaxPoints - g->st.added) return svh::fail(SVH_ERR_UNSUPPORTED, "svh_grid_observe_points: more than 2^31 - 1 points since the last clear");
+    return added(g, observe(g, xyzv, n, on_device != 0, oc, q_o));
+}
+
+int32_t svh_grid_observe_view_lists(svh_grid* g, svh_view* v, int32_t first_list, int32_t n_lists, const double origin[3]) {
+    if (!g || !v || !origin) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_view_lists: null argument");
+    const view::StoreRef r = view::store_of(v);
+    if (r.device != g->device) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_view_lists: the view lives on another device");
+    int64_t at = 0, n = 0;
+    if (!view::list_range(v, first_list, n_lists, &at, &n))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_view_lists: the lists are not all in the view's sequence");
+    if (!g->dyn_on) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_observe_view_lists") + kNoDyn);
+    int32_t q_o = 0;
+    const int64_t oc = origin_cell(g, origin, &q_o);
+    if (oc < 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_view_lists: the origin must be finite, inside the window and not above the clearance");
+    if (g->stamp == grid::STAMP_LIMIT) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_observe_view_lists: 2^31 - 1 observations since the last clear");
+    if (n > kMaxPoints - g->st.added) return svh::fail(SVH_ERR_UNSUPPORTED, "svh_grid_observe_view_lists: more than 2^31 - 1 points since the last clear");
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipSetDevice(g->device));
+        GRID_TRY(wait, hipStreamSynchronize(r.stream));   // the store is complete before this stream reads it
+        return observe(g, (const float*)(r.pts + at), n, true, oc, q_o);
+    }();
+    return added(g, rc);
+}
+
+int32_t svh_grid_get_dyn(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::D_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_dyn: a grid, a plane 0..2 and an output are needed");
+    if (!g->dyn_on) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_dyn") + kNoDyn);
+    return drained(g, get_dyn(g, plane, (int32_t*)out, on_device != 0));
+}
+
+int32_t svh_grid_get_dyn_stats(svh_grid* g, int64_t out[4]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_dyn_stats: null argument");
+    for (int k = 0; k < grid::DS_WORDS; k++) out[k] = g->dyn_stats[k];
+    return SVH_OK;
+}
+
+int32_t svh_grid_render_dyn(svh_grid* g, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_dyn: a grid and an output are needed");
+    if (!g->dyn_on) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_dyn") + kNoDyn);
+    return drained(g, render_dyn(g, rgb, on_device != 0));
+}
+
+// grid_dyn_core.h on the host.  svh_test_grid_dyn_params: the checks of svh_grid_set_dynamics and *margin_q; SVH_ERR_BAD_ARG when
+// they fail
+int32_t svh_test_grid_dyn_params(const svh_grid_dyn_params* d, int32_t* margin_q) {
+    if (!d) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_params: null argument");
+    grid::DynParams q{d->clear_frames, d->min_through, d->margin, d->max_age, 0};
+    if (!grid::dyn_derive(q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_params: parameters out of range");
+    if (margin_q) *margin_q = q.margin_q;
+    return SVH_OK;
+}
+
+// per item i: rdiv[i] = rdiv64(p[i], n[i]) (n > 0, |p| < 2^60), and for line steps height[i] = line_height(q_o[i], q_e[i], len[i], k[i])
+// (0 <= k < len <= 8192, |q| <= 2^30).  Either group may be all NULL
+int32_t svh_test_grid_dyn_height(int64_t count, const int64_t* p, const int64_t* n, int64_t* rdiv, const int32_t* q_o, const int32_t* q_e,
+                                 const int32_t* len, const int32_t* k, int32_t* height) {
+    if (count < 0 || (rdiv && (!p || !n)) || (height && (!q_o || !q_e || !len || !k)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_height: bad arguments");
+    for (int64_t i = 0; i < count; i++) {
+        if (rdiv) {
+            if (n[i] <= 0 || p[i] <= -((int64_t)1 << 60) || p[i] >= ((int64_t)1 << 60) || n[i] >= ((int64_t)1 << 60))
+                return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_height: n > 0 and |p|, n < 2^60 are needed");
+            rdiv[i] = grid::rdiv64(p[i], n[i]);
+        }
+        if (height) {
+            const int32_t lim = 1 << 30;
+            if (len[i] < 1 || len[i] > grid::MAX_SIDE || k[i] < 0 || k[i] >= len[i] || q_o[i] < -lim || q_o[i] > lim || q_e[i] < -lim || q_e[i] > lim)
+                return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_height: 0 <= k < len <= 8192 and |q| <= 2^30 are needed");
+            height[i] = grid::line_height(q_o[i], q_e[i], len[i], k[i]);
+        }
+    }
+    return SVH_OK;
+}
+
+// per stored cell i: its body (lo[i], hi[i]) and through[i] = goes_through(body, q[i]); q and through may be NULL
+int32_t svh_test_grid_dyn_through(const svh_grid_params* p, const svh_grid_dyn_params* d, int64_t ncells, const int32_t* count,
+                                  const uint32_t* kmin, const uint32_t* kmax, const int32_t* q, int32_t* lo, int32_t* hi, uint8_t* through) {
+    grid::Params prm;
+    if (!convert(p, &prm) || !d || ncells < 0 || (ncells > 0 && (!count || !kmin || !kmax || !lo || !hi)) || (through && !q))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_through: bad arguments");
+    grid::DynParams dq{d->clear_frames, d->min_through, d->margin, d->max_age, 0};
+    if (!grid::dyn_derive(dq)) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_through: parameters out of range");
+    for (int64_t i = 0; i < ncells; i++) {
+        const grid::Body b = grid::body_of(prm, dq, count[i], kmin[i], kmax[i]);
+        lo[i] = b.lo, hi[i] = b.hi;
+        if (through) through[i] = grid::goes_through(b, q[i]) ? 1 : 0;
+    }
+    return SVH_OK;
+}
+
+// settle() per cell i, in place: cell[6] = count, overhead, kmin, kmax, hsum, vsum of the stored cells, contra and last their state,
+// frame[6] the frame records in the same order, through the plane of phase 2; event[i] = the DynEvent flags
+int32_t svh_test_grid_dyn_settle(const svh_grid_params* p, const svh_grid_dyn_params* d, int32_t stamp, int64_t ncells, void* const cell[6],
+                                 int32_t* contra, int32_t* last, const void* const frame[6], const int32_t* through, uint8_t* event) {
+    grid::Params prm;
+    if (!convert(p, &prm) || !d || stamp < 1 || ncells < 0 || !cell || !frame || (ncells > 0 && (!contra || !last || !through || !event)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_settle: bad arguments");
+    for (int k = 0; k < 6; k++)
+        if (ncells > 0 && (!cell[k] || !frame[k])) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_settle: a null plane");
+    grid::DynParams dq{d->clear_frames, d->min_through, d->margin, d->max_age, 0};
+    if (!grid::dyn_derive(dq)) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_settle: parameters out of range");
+    for (int64_t i = 0; i < ncells; i++) {
+        if (last[i] < 0 || last[i] > stamp || contra[i] < 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_settle: 0 <= last <= stamp and contra >= 0 are needed");
+        grid::Cell c{((int32_t*)cell[0])[i], ((int32_t*)cell[1])[i], ((uint32_t*)cell[2])[i], ((uint32_t*)cell[3])[i], ((int64_t*)cell[4])[i],
+                     ((uint64_t*)cell[5])[i]};
+        const grid::Cell f{((const int32_t*)frame[0])[i], ((const int32_t*)frame[1])[i], ((const uint32_t*)frame[2])[i],
+                           ((const uint32_t*)frame[3])[i], ((const int64_t*)frame[4])[i], ((const uint64_t*)frame[5])[i]};
+        event[i] = grid::settle(prm, dq, stamp, c, contra[i], last[i], f, through[i]);
+        ((int32_t*)cell[0])[i] = c.count, ((int32_t*)cell[1])[i] = c.overhead, ((uint32_t*)cell[2])[i] = c.kmin, ((uint32_t*)cell[3])[i] = c.kmax;
+        ((int64_t*)cell[4])[i] = c.hsum, ((uint64_t*)cell[5])[i] = c.vsum;
+    }
+    return SVH_OK;
+}
+
+// colour_dyn and age_of per cell: rgb[3 i] from the class byte, the intensity, PASS, CONTRA and the event byte (COUNT taken as 1);
+// age[i] from stamp and last[i].  Either group may be all NULL
+int32_t svh_test_grid_dyn_colour(const svh_grid_params* p, int64_t ncells, const uint8_t* cls, const uint8_t* intensity, const int32_t* pass,
+                                 const int32_t* contra, const uint8_t* event, uint8_t* rgb, int32_t stamp, const int32_t* last, int32_t* age) {
+    grid::Params prm;
+    if (!convert(p, &prm) || ncells < 0 || (rgb && (!cls || !intensity || !pass || !contra || !event)) || (age && !last))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_dyn_colour: bad arguments");
+    for (int64_t i = 0; i < ncells; i++) {
+        if (rgb) {
+            const grid::Final f{0.f, 0.f, 0.f, intensity[i], cls[i]};
+            grid::colour_dyn(prm, 1, f, pass[i], contra[i], event[i], rgb + 3 * i);
+        }
+        if (age) age[i] = grid::age_of(stamp, last[i]);
+    }
+    return SVH_OK;
 }
 
 // grid_explore_core.h on the host, on a caller's STATE and COST planes (nx x nz, offsets oa, ob), with R from e->range and `cell`.

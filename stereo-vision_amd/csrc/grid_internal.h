@@ -1,5 +1,6 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
-// csrc/grid_front_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip: the launches of the
+// csrc/grid_front_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip /
+// csrc/grid_dyn_kernels.hip: the launches of the
 // ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
@@ -9,6 +10,7 @@
 
 #include "grid_align_core.h"
 #include "grid_core.h"
+#include "grid_dyn_core.h"
 #include "grid_explore_core.h"
 #include "grid_front_core.h"
 #include "grid_plan_core.h"
@@ -37,6 +39,8 @@ constexpr uint32_t FIN_BLOCK = 256;          // k_grid_finalise, k_grid_render, 
 constexpr uint32_t RAY_BLOCK = 256;          // k_grid_rays: four waves
 constexpr int STAT_RAY_CELLS = 4;            // stats[4]: the sum of pass increments; stats[0..3] are per grid::Fate
 constexpr int STAT_WORDS = 5;
+constexpr int STAT_DYN = 5;                  // stats[5..7]: cells cleared, aged and confirmed by the observations (grid_dyn_core.h)
+constexpr int STAT_ALL = 8;                  // the words the engine allocates and clears
 
 struct BinJob {
     Params prm;
@@ -332,6 +336,53 @@ void launch_align_score(hipStream_t s, const AlignJob& j, int32_t form);
 // the cells of the scan at the identity, those of the scan placed at (k, ta, tb), the pivot's cell, drawn in that order over an
 // image of svh_grid_render_local's layout: three launches
 void launch_align_overlay(hipStream_t s, const AlignJob& j, int32_t n_scan, int32_t k, int32_t ta, int32_t tb, uint8_t* rgb);
+
+// The dynamics (csrc/grid_dyn_kernels.hip): the phases 2 and 3 of an observation; phase 1 is launch_bin on the frame record.
+// The layer's planes, nx * nz elements each, at the cell's SLOT: they travel with the torus.  All zero is the empty state.
+struct DynPlanes {
+    int2* body;                 // (q_lo, q_hi + 1) of the stored cell, (0, 0) where it is not tall: what a line step loads.  Kept by
+                                // k_grid_settle for the cells it writes; a plain add makes it stale and k_grid_body writes it anew
+    int32_t* contra;            // contradicting frames in a row
+    int32_t* last;              // the stamp of the last observation with a point in the cell, 0 = never
+    int32_t* kept;              // THROUGH of the last observation
+    int32_t* through;           // THROUGH of the observation in flight: scratch, all zero between observations
+    uint8_t* event;             // the DynEvent flags of the last observation
+};
+// bytes of the six planes of one cell; the engine lays them out in the order above
+constexpr size_t DYN_BYTES = 25;
+// bytes of the frame record of one cell: the accumulators of Cells without pass, kmin first
+constexpr size_t FRAME_BYTES = 32;
+
+struct SightJob {
+    Params prm;
+    DynParams dyn;
+    uint32_t origin;            // the logical index of the origin's cell
+    int32_t q_o;                // place(origin).q
+    int32_t* ends;              // this frame's low points per cell, logical order: read, and left all zero
+    Cells cells;                // the stored accumulators: count, kmin, kmax read where the bodies are stale, pass added to
+    Cells frame;                // the frame record, by slot (pass is null): kmin read
+    bool write_body;            // the bodies are stale: k_grid_body first
+    DynPlanes planes;           // body read, through added to
+    unsigned long long* ray_cells;   // the sum of pass increments, added to
+};
+// the bodies where they are stale, then the sight lines: one or two launches
+void launch_sight(hipStream_t s, const SightJob& j);
+
+struct SettleJob {
+    Params prm;
+    DynParams dyn;
+    int32_t stamp;
+    Cells cells, frame;         // the frame record is left empty
+    DynPlanes planes;
+    unsigned long long* stats;  // [DS_CLEARED], [DS_AGED], [DS_CONFIRMED] added to; [0] is not touched
+};
+void launch_settle(hipStream_t s, const SettleJob& j);
+// svh_grid_scroll with the layer set: the planes of the entering strips become empty; the arguments of launch_enter
+void launch_dyn_enter(hipStream_t s, const Params& prm, int32_t da, int32_t db, const DynPlanes& d);
+// a grid::DynPlane in logical order
+void launch_dyn_get(hipStream_t s, const Params& prm, int32_t plane, int32_t stamp, const DynPlanes& d, int32_t* out);
+// svh_grid_render_dyn: a RenderJob (its mode is not read) with the layer's planes
+void launch_render_dyn(hipStream_t s, const RenderJob& j, const DynPlanes& d);
 
 }  // namespace grid
 }  // namespace svh

@@ -1,7 +1,8 @@
 """ctypes binding of the ground grid in libsvhip.so (C-ABI: include/svh_grid.h): a 2.5-D bird's-eye grid over the road
 plane -- per cell how many points, how high, how bright, drivable or not -- binned on the device from the map view's store
 or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h, grid_plan_core.h, grid_front_core.h and
-grid_roll_core.h; that of the exploration layer grid_explore_core.h, that of the alignment layer grid_align_core.h."""
+grid_roll_core.h; that of the exploration layer grid_explore_core.h, that of the alignment layer grid_align_core.h, that of the
+dynamics grid_dyn_core.h."""
 import ctypes as C
 
 import numpy as np
@@ -49,6 +50,10 @@ ALIGN_FIELDS = ("status", "k", "ta", "tb", "score", "identity", "n_scan", "ties"
 ALIGN_OK, ALIGN_FEW, ALIGN_FLAT = range(3)
 ALIGN_SUB = 4
 ALIGN_SCAN_COLOUR, ALIGN_BEST_COLOUR, ALIGN_PIVOT_COLOUR = (255, 224, 0), (0, 224, 255), (255, 255, 255)
+DYN_AGE, DYN_CONTRA, DYN_THROUGH = range(3)
+DYN_CLEARED, DYN_AGED, DYN_CONFIRMED = 1, 2, 4
+DYN_STATS = ("observations", "cleared", "aged", "confirmed")
+DYN_EVENT_COLOUR = (255, 0, 255)
 
 
 class Params(C.Structure):
@@ -145,6 +150,20 @@ class AlignParams(C.Structure):
 
     def copy(self, **kw):
         q = AlignParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DynParams(C.Structure):
+    """svh_grid_dyn_params"""
+    _fields_ = [("clear_frames", C.c_int32), ("min_through", C.c_int32), ("margin", C.c_float), ("max_age", C.c_int32)]
+
+    def copy(self, **kw):
+        q = DynParams.from_buffer_copy(bytes(self))
         for k, v in kw.items():
             setattr(q, k, v)
         return q
@@ -280,6 +299,20 @@ def _bind():
         L.svh_test_grid_align.argtypes = align
         L.svh_test_grid_align_device.argtypes = align
         L.svh_test_grid_align_form.argtypes = [C.c_int32]
+        L.svh_grid_dyn_params_default.argtypes = [C.POINTER(DynParams)]
+        L.svh_grid_dyn_params_default.restype = None
+        L.svh_grid_set_dynamics.argtypes = [C.c_void_p, C.POINTER(DynParams)]
+        L.svh_grid_get_dynamics.argtypes = [C.c_void_p, C.POINTER(DynParams)]
+        L.svh_grid_observe_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.svh_grid_observe_view_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.svh_grid_get_dyn.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_get_dyn_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_render_dyn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_test_grid_dyn_params.argtypes = [C.POINTER(DynParams), C.c_void_p]
+        L.svh_test_grid_dyn_height.argtypes = [C.c_int64] + [C.c_void_p] * 8
+        L.svh_test_grid_dyn_through.argtypes = [C.POINTER(Params), C.POINTER(DynParams), C.c_int64] + [C.c_void_p] * 7
+        L.svh_test_grid_dyn_settle.argtypes = [C.POINTER(Params), C.POINTER(DynParams), C.c_int32, C.c_int64] + [C.c_void_p] * 6
+        L.svh_test_grid_dyn_colour.argtypes = [C.POINTER(Params), C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_void_p]
         L._grid_bound = True
     return L
 
@@ -694,6 +727,82 @@ def device_align(params, align, state, oa=0, ob=0, points=None, pivot=None, subs
 def align_form(form=-1):
     """TEST ENTRY: the form of the alignment's score kernel becomes `form` (0 chunk, 1 plain, 2 tiled, plus 4 for the field in three launches instead of two; -1 only reads); what it was"""
     return int(_bind().svh_test_grid_align_form(form))
+
+
+def default_dyn(**kw):
+    p = DynParams()
+    _bind().svh_grid_dyn_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def core_dyn_margin_q(dyn):
+    """the checks of svh_grid_set_dynamics on the host: margin_q, or SvhError"""
+    q = C.c_int32(0)
+    _check(_bind().svh_test_grid_dyn_params(C.byref(dyn), C.addressof(q)))
+    return q.value
+
+
+def core_dyn_rdiv64(p, n):
+    """rdiv64 of csrc/grid_dyn_core.h on the host, elementwise: int64"""
+    p, n = np.ascontiguousarray(p, np.int64).ravel(), np.ascontiguousarray(n, np.int64).ravel()
+    out = np.zeros(len(p), np.int64)
+    _check(_bind().svh_test_grid_dyn_height(len(p), p.ctypes.data, n.ctypes.data, out.ctypes.data, None, None, None, None, None))
+    return out
+
+
+def core_dyn_height(q_o, q_e, n, k):
+    """line_height of csrc/grid_dyn_core.h on the host, elementwise: int32"""
+    a = [np.ascontiguousarray(v, np.int32).ravel() for v in np.broadcast_arrays(q_o, q_e, n, k)]
+    out = np.zeros(len(a[0]), np.int32)
+    _check(_bind().svh_test_grid_dyn_height(len(out), None, None, None, *[v.ctypes.data for v in a], out.ctypes.data))
+    return out
+
+
+def core_dyn_through(params, dyn, count, kmin, kmax, q=None):
+    """body_of and goes_through of csrc/grid_dyn_core.h on the host, per stored cell: (lo int32, hi int32, through uint8 or None)"""
+    ins = [np.ascontiguousarray(count, np.int32).ravel(), np.ascontiguousarray(kmin, np.uint32).ravel(), np.ascontiguousarray(kmax, np.uint32).ravel()]
+    n = len(ins[0])
+    qq = None if q is None else np.ascontiguousarray(q, np.int32).ravel()
+    lo, hi, thr = np.zeros(n, np.int32), np.zeros(n, np.int32), None if q is None else np.zeros(n, np.uint8)
+    _check(_bind().svh_test_grid_dyn_through(C.byref(params), C.byref(dyn), n, *[a.ctypes.data for a in ins], None if q is None else qq.ctypes.data,
+                                             lo.ctypes.data, hi.ctypes.data, None if q is None else thr.ctypes.data))
+    return lo, hi, thr
+
+
+_CELL_DTYPES = (np.int32, np.int32, np.uint32, np.uint32, np.int64, np.uint64)
+
+
+def core_dyn_settle(params, dyn, stamp, cell, contra, last, frame, through):
+    """settle of csrc/grid_dyn_core.h on the host, per cell: cell and frame are (count, overhead, kmin, kmax, hsum, vsum); returns
+    (cell', contra', last', event uint8); the inputs are not changed"""
+    cell = [np.array(a, t).ravel() for a, t in zip(cell, _CELL_DTYPES)]
+    frame = [np.ascontiguousarray(a, t).ravel() for a, t in zip(frame, _CELL_DTYPES)]
+    contra, last = np.array(contra, np.int32).ravel(), np.array(last, np.int32).ravel()
+    through = np.ascontiguousarray(through, np.int32).ravel()
+    n = len(contra)
+    event = np.zeros(n, np.uint8)
+    cp, fp = (C.c_void_p * 6)(*[a.ctypes.data for a in cell]), (C.c_void_p * 6)(*[a.ctypes.data for a in frame])
+    _check(_bind().svh_test_grid_dyn_settle(C.byref(params), C.byref(dyn), stamp, n, C.addressof(cp), contra.ctypes.data, last.ctypes.data, C.addressof(fp),
+                                            through.ctypes.data, event.ctypes.data))
+    return cell, contra, last, event
+
+
+def core_dyn_colour(params, cls, intensity, pass_, contra, event):
+    """colour_dyn of csrc/grid_dyn_core.h on the host: rgb uint8 [n, 3]"""
+    ins = [np.ascontiguousarray(cls, np.uint8).ravel(), np.ascontiguousarray(intensity, np.uint8).ravel(), np.ascontiguousarray(pass_, np.int32).ravel(),
+           np.ascontiguousarray(contra, np.int32).ravel(), np.ascontiguousarray(event, np.uint8).ravel()]
+    n = len(ins[0])
+    rgb = np.zeros((n, 3), np.uint8)
+    _check(_bind().svh_test_grid_dyn_colour(C.byref(params), n, *[a.ctypes.data for a in ins], rgb.ctypes.data, 0, None, None))
+    return rgb
+
+
+def core_dyn_age(params, stamp, last):
+    """age_of of csrc/grid_dyn_core.h on the host: int32"""
+    last = np.ascontiguousarray(last, np.int32).ravel()
+    age = np.zeros(len(last), np.int32)
+    _check(_bind().svh_test_grid_dyn_colour(C.byref(params), len(last), None, None, None, None, None, None, stamp, last.ctypes.data, age.ctypes.data))
+    return age
 
 
 def __getattr__(name):
@@ -1147,6 +1256,64 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_align(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_dynamics(self, params=None, **kw):
+        """the dynamics: the parameters in force, else the defaults (or `params`), with the fields of kw replaced: clear_frames,
+        min_through, margin, max_age"""
+        if params is None:
+            try:
+                params = self.dynamics()
+            except SvhError:
+                params = default_dyn()
+        p = params.copy(**kw)
+        _check(self._L.svh_grid_set_dynamics(self._h, C.byref(p)))
+        return p
+
+    def drop_dynamics(self):
+        """the layer and its planes go"""
+        _check(self._L.svh_grid_set_dynamics(self._h, None))
+
+    def dynamics(self):
+        p = DynParams()
+        _check(self._L.svh_grid_get_dynamics(self._h, C.byref(p)))
+        return p
+
+    def observe_points(self, xyzv, origin):
+        """one observation: [n, 4] float32 (x, y, z, val) on the host, seen from the map-frame position `origin`"""
+        p = np.ascontiguousarray(xyzv, np.float32).reshape(-1, 4)
+        _check(self._L.svh_grid_observe_points(self._h, p.ctypes.data if len(p) else None, len(p), 0, _xyz(origin).ctypes.data))
+
+    def observe_points_device(self, ptr, n, origin):
+        """the same from a raw device address (int), 16-byte aligned"""
+        _check(self._L.svh_grid_observe_points(self._h, ptr, n, 1, _xyz(origin).ctypes.data))
+
+    def observe_view_lists(self, view, first_list, n_lists, origin):
+        """lists first_list .. first_list + n_lists - 1 of a svhip.view.View as one observation, device to device"""
+        _check(self._L.svh_grid_observe_view_lists(self._h, view._h, first_list, n_lists, _xyz(origin).ctypes.data))
+
+    def dyn_plane(self, which, device_ptr=None):
+        """DYN_AGE, DYN_CONTRA or DYN_THROUGH, int32 [nz, nx]; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_dyn(self._h, which, device_ptr, 1))
+            return None
+        out = np.zeros((self.nz, self.nx), np.int32)
+        _check(self._L.svh_grid_get_dyn(self._h, which, out.ctypes.data, 0))
+        return out
+
+    def dyn_stats(self):
+        """dict of observations, cleared, aged, confirmed since the last clear"""
+        out = np.zeros(4, np.int64)
+        _check(self._L.svh_grid_get_dyn_stats(self._h, out.ctypes.data))
+        return dict(zip(DYN_STATS, (int(v) for v in out)))
+
+    def render_dyn(self, device_ptr=None):
+        """render_local with the cells of CONTRA > 0 tinted and those the last observation cleared or aged in DYN_EVENT_COLOUR"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_dyn(self._h, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_dyn(self._h, img.ctypes.data, 0))
         return img
 
     def stats(self):

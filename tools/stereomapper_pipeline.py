@@ -22,6 +22,7 @@ without the GUI.  Usage:
                                           [--grid-frontiers DIR [--grid-unexplored unseen|seen|both] [--grid-frontier-min N]]
                                           [--grid-explore DIR [--grid-explore-range M]]
                                           [--grid-align DIR [--grid-align-apply] [--grid-align-window K,W]]
+                                          [--grid-dynamic DIR [--grid-dynamic-params CLEAR,THROUGH,MARGIN,AGE]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -126,6 +127,14 @@ per frame is appended to DIR/align.jsonl and the image (svh_grid_render_align: t
 scan placed at the best cyan, the camera's cell white) goes into DIR/align_%06d.ppm.  With --grid-align-apply a frame whose status
 is 0 and whose best is unique (ties 1: no direction was left open) is added to the local grid under the correction M (svh_grid_align_correction), its rays cast from the corrected camera
 position; the map view and the odometry are left alone.
+
+--grid-dynamic DIR: needs --grid-local.  The local step takes a frame as an OBSERVATION (svh_grid_observe_view_lists) instead of an
+add: the frame's sight lines contradict obstacle cells they pass through at the height of their body, CLEAR contradicting frames in a row
+forget a cell's points, and a cell that AGE frames have not seen is emptied (--grid-dynamic-params CLEAR,THROUGH,MARGIN,AGE: clear_frames,
+min_through, margin in metres and max_age of svh_grid_dyn_params; 2,3,0.1,0).  After every local step the image (svh_grid_render_dyn: the
+local image, cells under contradiction tinted, cells the frame cleared or aged magenta) goes into DIR/dyn_%06d.ppm and one line {"frame",
+"observations", "cleared", "aged", "confirmed"}, the totals so far, is appended to DIR/dyn.jsonl.  With --grid-align-apply a corrected
+frame is observed under its correction.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -236,6 +245,12 @@ class Pipeline:
         self.local_appends = 0
         self.align_apply = None    # False / True once enable_grid_align() has been called
         self.align_last = None     # (record, applied, image) of the last local step that aligned a frame
+        self.dynamic = False       # True once enable_grid_dynamic() has been called: frames are observations
+
+    def enable_grid_dynamic(self, **kw):
+        """the local step observes (svh_grid_observe_*) instead of adding; kw: clear_frames, min_through, margin, max_age"""
+        self.local.set_dynamics(**kw)
+        self.dynamic = True
 
     def enable_grid_align(self, apply=False, window=(8, 8)):
         """align every frame's list to the local grid before it is added (local_step); apply: add it under the correction"""
@@ -306,7 +321,8 @@ class Pipeline:
         return kept, best, recs, scores, status, cells, cost, img
 
     def local_step(self):
-        """follow the camera centre to the middle cell, add the newest list with rays from it, render: [nz, nx, 3]"""
+        """follow the camera centre to the middle cell, add (or, with the dynamics, observe) the newest list with rays from it, render:
+        [nz, nx, 3]"""
         from svhip import view
         g = self.local
         if self.appends > self.local_appends:   # a frame whose ELAS failed appends nothing
@@ -322,11 +338,11 @@ class Pipeline:
                     M = g.align_correction(int(rec[1]), int(rec[2]), int(rec[3]), centre)
                     pts = self.view.points(last).copy()
                     pts[:, :3] = (pts[:, :3].astype(np.float64) @ M[:3, :3].T + M[:3, 3]).astype(np.float32)
-                    g.add_points_from(pts, M[:3, :3] @ centre + M[:3, 3])
+                    (g.observe_points if self.dynamic else g.add_points_from)(pts, M[:3, :3] @ centre + M[:3, 3])
                     applied = True
                 self.align_last = (rec, applied, img)
             if not applied:
-                g.add_view_lists_from(self.view, last, 1, centre)
+                (g.observe_view_lists if self.dynamic else g.add_view_lists_from)(self.view, last, 1, centre)
         return g.render_local()
 
     def render_grid(self):
@@ -598,6 +614,7 @@ def main():
     explore_dir, explore_kw = None, {}
     align_dir, align_apply, align_window = None, False, None
     roll_dir, roll_kw = None, {}
+    dyn_dir, dyn_kw = None, {}
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -687,6 +704,19 @@ def main():
             align_window = tuple(int(v) for v in sys.argv[k + 1].split(","))
             assert len(align_window) == 2 and 0 <= align_window[0] <= 32 and 0 <= align_window[1] <= 32
             del sys.argv[k:k + 2]
+        if "--grid-dynamic" in sys.argv:
+            k = sys.argv.index("--grid-dynamic")
+            dyn_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-dynamic-params" in sys.argv:
+            k = sys.argv.index("--grid-dynamic-params")
+            v = sys.argv[k + 1].split(",")
+            assert len(v) == 4
+            dyn_kw = dict(clear_frames=int(v[0]), min_through=int(v[1]), margin=float(v[2]), max_age=int(v[3]))
+            assert 0 <= dyn_kw["clear_frames"] <= 65535 and dyn_kw["min_through"] >= 1 and 0 <= dyn_kw["margin"] < 2 ** 20 and dyn_kw["max_age"] >= 0
+            del sys.argv[k:k + 2]
+        assert local_dir or not dyn_dir
+        assert dyn_dir or not dyn_kw
         assert local_dir or not align_dir
         assert align_dir or not (align_apply or align_window)
         assert cost_dir or not plan_dir
@@ -771,6 +801,9 @@ def main():
     if align_dir:
         os.makedirs(align_dir, exist_ok=True)
         open(os.path.join(align_dir, "align.jsonl"), "w").close()
+    if dyn_dir:
+        os.makedirs(dyn_dir, exist_ok=True)
+        open(os.path.join(dyn_dir, "dyn.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -781,6 +814,8 @@ def main():
         p.enable_grid_local(grid_cell, grid_size)
     if align_dir:
         p.enable_grid_align(align_apply, align_window or (8, 8))
+    if dyn_dir:
+        p.enable_grid_dynamic(**dyn_kw)
     if cost_dir:
         p.set_grid_cost(**cost_kw)
     if plan_dir or front_dir or explore_dir:
@@ -809,6 +844,10 @@ def main():
         if local_dir:
             p.align_last = None
             view.write_ppm(os.path.join(local_dir, "local_%06d.ppm" % (frames - 1)), p.local_step())
+        if dyn_dir:
+            view.write_ppm(os.path.join(dyn_dir, "dyn_%06d.ppm" % (frames - 1)), p.local.render_dyn())
+            with open(os.path.join(dyn_dir, "dyn.jsonl"), "a") as f:
+                f.write(json.dumps(dict(p.local.dyn_stats(), frame=frames - 1)) + "\n")
         if align_dir and p.align_last is not None:
             rec, applied, img = p.align_last
             aligned += int(rec[0] == 0)
@@ -863,6 +902,10 @@ def main():
         st, (rays, ray_cells), (oa, ob) = p.local.stats(), p.local.ray_stats(), p.local.window()
         print("local grid %d x %d cells of %g at offsets (%d, %d): %d of %d points binned, %d rays over %d cells; %d images in %s" % (
             p.local.nx, p.local.nz, grid_cell, oa, ob, st.binned, st.added, rays, ray_cells, frames, local_dir))
+    if dyn_dir:
+        d, ds = p.local.dynamics(), p.local.dyn_stats()
+        print("dynamics: clear after %d frames of %d through-lines, margin %g m, age %d: %d observations, %d cells cleared, %d aged; %d images and dyn.jsonl in %s" % (
+            d.clear_frames, d.min_through, d.margin, d.max_age, ds["observations"], ds["cleared"], ds["aged"], frames, dyn_dir))
     if cost_dir:
         t, reach = p.local.traversability()
         print("cost map: slope %g, inscribed %g m, inflation %g m = %d cells; %d images in %s" % (
