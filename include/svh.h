@@ -656,6 +656,13 @@ float   svh_vo_get_gain(svh_vo* v, const int32_t* inliers, int32_t n);
 int32_t svh_vo_get_gain_batch(svh_vo* const* vs, int32_t K, const int32_t* const* inliers, const int32_t* n,
                               float* gain);
 svh_matcher* svh_vo_matcher(svh_vo* v);                          /* the owned Matcher (taps)   */
+/* test tap (stereo objects; the mono one is svh_vo_mono_get_votes): every RANSAC hypothesis of the last
+ * estimateMotion that reached the device, in iteration order -- votes[k] = its inlier count, -1 where its Gauss-Newton
+ * FAILED (viso_stereo.cpp:104-118), tr6[6 k ..] = its motion vector (whatever the failed step left, for a FAILED one).
+ * Copies up to cap entries (either array may be NULL) and returns the count: 0 for a mono object, before the first
+ * estimate, and after an estimate that returned early (fewer than 6 matches) or ran with ransac_iters <= 0.  Read
+ * from device memory on request: the estimate itself is unchanged.  A negative SVH_ERR_* if that copy fails. */
+int32_t svh_vo_get_hypotheses(svh_vo* v, int32_t* votes, double* tr6, int32_t cap);
 
 /* ===========================================================================
  * libviso2 VisualOdometryMono

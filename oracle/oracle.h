@@ -109,6 +109,14 @@ int32_t orc_vo_get_inliers(orc_vo* v, int32_t* out, int32_t cap);
 int32_t orc_vo_num_matches(orc_vo* v);
 int32_t orc_vo_get_matches(orc_vo* v, svh_p_match* out, int32_t cap);
 float   orc_vo_get_gain(orc_vo* v, const int32_t* inliers, int32_t n);
+/* svh_vo_get_hypotheses: votes (-1 = FAILED) and 6-vector of every RANSAC hypothesis of the last estimate that
+ * reached the RANSAC loop, in iteration order; copies up to cap, returns the count (0 after the N < 6 return) */
+int32_t orc_vo_get_hypotheses(orc_vo* v, int32_t* votes, double* tr6, int32_t cap);
+/* No counterpart in the product.  Moves every sine and cosine of the stereo linearisation (computeResidualsAndJacobian,
+ * viso_stereo.cpp:352-357; nothing else) by one ulp, which is what another libm may do: 0 exact (the default),
+ * 1 all up, 2 all down, 3 up / down / exact drawn per value from a private generator started at `seed`.  Tests use
+ * it to tell the inputs whose answer survives such a change from those that a parity check cannot use. */
+void    orc_vo_set_trig_mode(orc_vo* v, int32_t mode, uint32_t seed);
 
 /* ---- map fusion (stereomapper/stereothread.cpp:180-437), see map_oracle.cpp ---------------- */
 typedef svh_map_params orc_map_params;

@@ -869,6 +869,12 @@ struct orc_vo {
     bool Tr_valid;
     std::vector<int32_t> inliers;
     std::vector<PM> matched;
+    // test taps: every hypothesis of the last estimateMotion that reached the RANSAC loop (orc_vo_get_hypotheses),
+    // and the last-bit perturbation of the linearisation's sines and cosines (orc_vo_set_trig_mode)
+    std::vector<int32_t> hyp_votes;
+    std::vector<double> hyp_tr;
+    int32_t trig_mode;
+    uint32_t trig_state;
 };
 
 namespace {
@@ -878,16 +884,36 @@ typedef orc_vo VoState;
 enum VoResult { VO_UPDATED, VO_FAILED, VO_CONVERGED };
 
 struct VoWork {
+    VoState* st;
     const PM* pm;
     int32_t n;
     std::vector<double> X, Y, Z, J, predict, observe, residual;
 };
 
+// orc_vo_set_trig_mode: a sine or cosine moved by one ulp -- what another libm may return for the same argument.
+// Mode 3 draws up / down / exact from the object's own xorshift32 stream (never libc rand(): the samples use that).
+double vo_trig(VoState* s, double x) {
+    int dir = 0;
+    if (s->trig_mode == 1) dir = 1;
+    else if (s->trig_mode == 2) dir = -1;
+    else if (s->trig_mode == 3) {
+        uint32_t z = s->trig_state;
+        z ^= z << 13; z ^= z >> 17; z ^= z << 5;
+        s->trig_state = z;
+        dir = (int)(z % 3u) - 1;
+    }
+    return dir == 0 ? x : nextafter(x, dir > 0 ? INFINITY : -INFINITY);
+}
+
 // viso_stereo.cpp:327-337 + :341-485: observations, predictions, residuals and Jacobian rows
 // of the `active` matches for the motion tr = (rx,ry,rz,tx,ty,tz)
 void vo_linearise(const svh_vo_params& P, VoWork& w, const double* tr, const std::vector<int32_t>& active) {
     const double rx = tr[0], ry = tr[1], rz = tr[2], tx = tr[3], ty = tr[4], tz = tr[5];
-    const double sx = sin(rx), cx = cos(rx), sy = sin(ry), cy = cos(ry), sz = sin(rz), cz = cos(rz);
+    double sx = sin(rx), cx = cos(rx), sy = sin(ry), cy = cos(ry), sz = sin(rz), cz = cos(rz);
+    if (w.st->trig_mode != 0) {   // (mode 0, the default: untouched)
+        sx = vo_trig(w.st, sx); cx = vo_trig(w.st, cx); sy = vo_trig(w.st, sy);
+        cy = vo_trig(w.st, cy); sz = vo_trig(w.st, sz); cz = vo_trig(w.st, cz);
+    }
     // R = Rx * Ry * Rz and its partial derivatives
     const double r00 = +cy * cz, r01 = -cy * sz, r02 = +sy;
     const double r10 = +sx * sy * cz + cx * sz, r11 = -sx * sy * sz + cx * cz, r12 = -sx * cy;
@@ -973,8 +999,11 @@ VoResult vo_update(const svh_vo_params& P, VoWork& w, const std::vector<int32_t>
 // for its empty vector; `inliers` is left as the reference leaves _inliers.
 bool vo_estimate(VoState* s, const PM* pm, int32_t N, double* tr_out) {
     const svh_vo_params& P = s->p;
+    s->hyp_votes.clear();
+    s->hyp_tr.clear();
     if (N < 6) return false;               // _inliers is NOT cleared on this path (:91-94)
     VoWork w;
+    w.st = s;
     w.pm = pm; w.n = N;
     w.X.resize(N); w.Y.resize(N); w.Z.resize(N);
     w.J.assign((size_t)4 * N * 6, 0.0);
@@ -1007,6 +1036,8 @@ bool vo_estimate(VoState* s, const PM* pm, int32_t N, double* tr_out) {
             res = vo_update(P, w, active, cur, 1, 1e-6);
             if (iter++ > 20 || res == VO_CONVERGED) break;
         }
+        s->hyp_votes.push_back(-1);        // (tap: -1 stays for a FAILED hypothesis)
+        s->hyp_tr.insert(s->hyp_tr.end(), cur, cur + 6);
         if (res != VO_FAILED) {
             // getInlier, :232-255
             vo_linearise(P, w, cur, all);
@@ -1019,6 +1050,7 @@ bool vo_estimate(VoState* s, const PM* pm, int32_t N, double* tr_out) {
                 const double e3 = w.observe[4 * i + 3] - w.predict[4 * i + 3];
                 if (e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3 < thr) in.push_back(i);
             }
+            s->hyp_votes.back() = (int32_t)in.size();
             if (in.size() > s->inliers.size()) {
                 s->inliers = in;
                 best.assign(cur, cur + 6);
@@ -1085,6 +1117,8 @@ orc_vo* orc_vo_create(const svh_vo_params* p) {
     orc_matcher_set_intrinsics(s->matcher, p->f, p->cu, p->cv, p->base);
     for (int i = 0; i < 16; i++) s->Tr[i] = (i % 5 == 0) ? 1.0 : 0.0;
     s->Tr_valid = false;
+    s->trig_mode = 0;
+    s->trig_state = 1;
     srand(0);                                                                  // viso.cpp:36
     return s;
 }
@@ -1117,6 +1151,18 @@ void orc_vo_get_motion(orc_vo* s, double* Tr16) { memcpy(Tr16, s->Tr, sizeof(s->
 int32_t orc_vo_get_inliers(orc_vo* s, int32_t* out, int32_t cap) {
     for (int32_t i = 0; i < (int32_t)s->inliers.size() && i < cap && out; i++) out[i] = s->inliers[i];
     return (int32_t)s->inliers.size();
+}
+int32_t orc_vo_get_hypotheses(orc_vo* s, int32_t* votes, double* tr6, int32_t cap) {
+    const int32_t n = (int32_t)s->hyp_votes.size();
+    for (int32_t i = 0; i < n && i < cap; i++) {
+        if (votes) votes[i] = s->hyp_votes[i];
+        if (tr6) memcpy(tr6 + 6 * i, &s->hyp_tr[6 * (size_t)i], 6 * sizeof(double));
+    }
+    return n;
+}
+void orc_vo_set_trig_mode(orc_vo* s, int32_t mode, uint32_t seed) {
+    s->trig_mode = mode >= 0 && mode <= 3 ? mode : 0;
+    s->trig_state = seed ? seed : 0x9E3779B9u;   // (xorshift32 has no zero state)
 }
 int32_t orc_vo_num_matches(orc_vo* s) { return (int32_t)s->matched.size(); }
 int32_t orc_vo_get_matches(orc_vo* s, svh_p_match* out, int32_t cap) { return orc_matcher_get_matches(s->matcher, out, cap); }

@@ -42,6 +42,7 @@ struct svh_vo {
     HipBuf<uint8_t> d_in, d_flags;
     HipBuf<double> d_hyp_tr, d_J, d_res;
     HipBuf<int32_t> d_hyp_count;
+    int32_t hyp_n = 0;   // hypotheses of the last stereo estimate that reached the device (svh_vo_get_hypotheses)
     svh::MonoVo* mono = nullptr;   // a VisualOdometryMono (svh_vo_mono_create): its estimate replaces the stereo one
 };
 
@@ -86,10 +87,12 @@ void vector_to_matrix(const double* tr, double* T) {
 // estimate_prepare returns 1 when there is device work, 0 for the reference's early return (N < 6), <0 on error
 int estimate_prepare(svh_vo* v, const svh_p_match* pm, int32_t N) {
     const svh_vo_params& P = v->p;
+    v->hyp_n = 0;
     if (N < 6) return 0;   // viso_stereo.cpp:91-94: returns before _inliers is cleared
     const int32_t iters = P.ransac_iters > 0 ? P.ransac_iters : 0;
     int rc = ensure(v, N, iters);
     if (rc) return rc;
+    v->hyp_n = iters;
     v->inliers.clear();
     // getRandomSample(N, 3) for every iteration, viso.cpp:130-153: three libc rand() draws
     // without replacement (the draw indexes the list of the not yet chosen indices)
@@ -211,6 +214,7 @@ svh_vo* svh_vo_create(const svh_vo_params* p) {
         double tr[6];
         (void)estimate(v, dummy, 8, tr);           // launches (and so loads) the kernels
         v->inliers.clear();
+        v->hyp_n = 0;
         const int32_t wd[3] = {64, 32, 64};
         std::vector<uint8_t> blank((size_t)64 * 32, 0);
         svh_matcher* tmp = svh_matcher_create(&p->match);     // a scratch Matcher: streams, kernels
@@ -480,6 +484,21 @@ int32_t svh_vo_get_inliers(svh_vo* v, int32_t* out, int32_t cap) {
     if (!v) return 0;
     for (int32_t i = 0; i < (int32_t)v->inliers.size() && i < cap && out; i++) out[i] = v->inliers[i];
     return (int32_t)v->inliers.size();
+}
+
+// test tap: what k_vo_ransac left in d_hyp_count / d_hyp_tr, copied down on request (the estimate itself never reads
+// them back: only the winner travels, in VoResult)
+int32_t svh_vo_get_hypotheses(svh_vo* v, int32_t* votes, double* tr6, int32_t cap) {
+    svh::ActiveCaller active_;
+    if (!v || v->mono || v->hyp_n <= 0 || !v->stream) return 0;
+    const int32_t n = v->hyp_n, k = cap < n ? (cap > 0 ? cap : 0) : n;
+    if (k > 0 && (votes || tr6)) {
+        VO_TRY(none, hipSetDevice(v->device));
+        VO_TRY(none, (hipError_t)wait_stream(v->stream));
+        if (votes) VO_TRY(none, hipMemcpy(votes, v->d_hyp_count.p, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (tr6) VO_TRY(none, hipMemcpy(tr6, v->d_hyp_tr.p, (size_t)6 * k * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return n;
 }
 
 float svh_vo_get_gain(svh_vo* v, const int32_t* inliers, int32_t n) {

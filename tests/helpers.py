@@ -701,6 +701,18 @@ class VoBase:
         inl = np.ascontiguousarray(inliers, np.int32)
         return float(self._f("get_gain")(self.h, _p(inl), len(inl)))
 
+    def hypotheses(self):
+        """(votes [n] int32, -1 = FAILED; vectors [n, 6]) of every RANSAC hypothesis of the last stereo estimate
+        (svh_vo_get_hypotheses / orc_vo_get_hypotheses; the reference has no such tap)"""
+        f = self._f("get_hypotheses")
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        n = f(self.h, None, None, 0)
+        assert n >= 0, n
+        votes = np.full(max(n, 1), -99, np.int32)
+        tr = np.full((max(n, 1), 6), np.nan, np.float64)
+        assert f(self.h, _p(votes), _p(tr), n) == n
+        return votes[:n], tr[:n]
+
 
 class RefVo(VoBase):
     def __init__(self, params):
@@ -719,6 +731,11 @@ class OracleVo(VoBase):
         lib.orc_vo_set_triangulator.argtypes = [C.c_void_p, C.c_void_p]
         lib.orc_vo_set_triangulator(self.h, tri_fn if isinstance(tri_fn, C.c_void_p)
                                     else C.cast(tri_fn, C.c_void_p))
+
+    def set_trig_mode(self, mode, seed=1):
+        """orc_vo_set_trig_mode: the linearisation's sines / cosines exact (0), one ulp up (1), down (2), mixed (3)"""
+        self.lib.orc_vo_set_trig_mode.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
+        self.lib.orc_vo_set_trig_mode(self.h, mode, seed)
 
 
 class ProductVo(VoBase):
