@@ -36,6 +36,10 @@ inline int32_t texture16(const uint8_t* a) {
 // (elas.cpp:1081-1082): convert through int64 and wrap.
 inline int32_t f2u2i(float f) { return (int32_t)(uint32_t)(int64_t)f; }
 
+// tie counters of the last orc_elas_run (orc_elas_tie_stats, oracle.h): how often the two arg-min searches met equal
+// values.  Written beside the searches, read by none of them.
+int64_t g_tie[6];
+
 }  // namespace
 
 extern "C" {
@@ -147,6 +151,8 @@ static int32_t matching_disparity(const svh_elas_params* p, int32_t u, int32_t v
             d2 = d;
         }
     }
+    g_tie[0]++;
+    if (d1 >= 0 && d2 >= 0 && e1 == e2) g_tie[1]++;
     if (d1 >= 0 && d2 >= 0 && (float)e1 < p->support_threshold * (float)e2) return d1;
     return -1;
 }
@@ -420,6 +426,7 @@ static void find_match(const svh_elas_params* p, int32_t u, int32_t v, float pa,
     const int32_t* d_grid = cell + 1;
 
     int32_t min_val = 10000, min_d = -1;
+    int32_t at_min = 0, lowest = -1;   // tie tap: candidates that attain min_val so far, the smallest d among them
     for (int32_t i = 0; i < num_grid; i++) {
         int32_t dc = d_grid[i];
         if (dc < d_plane_min || dc > d_plane_max) {
@@ -429,6 +436,11 @@ static void find_match(const svh_elas_params* p, int32_t u, int32_t v, float pa,
             if (val < min_val) {
                 min_val = val;
                 min_d = dc;
+                at_min = 1;
+                lowest = dc;
+            } else if (val == min_val && min_d >= 0) {
+                at_min++;
+                lowest = std::min(lowest, dc);
             }
         }
     }
@@ -439,7 +451,19 @@ static void find_match(const svh_elas_params* p, int32_t u, int32_t v, float pa,
         if (val < min_val) {
             min_val = val;
             min_d = dc;
+            at_min = 1;
+            lowest = dc;
+        } else if (val == min_val && min_d >= 0) {
+            at_min++;
+            lowest = std::min(lowest, dc);
         }
+    }
+    if (min_d >= 0) {
+        g_tie[2]++;
+        if (at_min > 1) g_tie[3]++;
+        if (lowest != min_d) g_tie[4]++;
+    } else {
+        g_tie[5]++;
     }
     D[d_addr] = min_d >= 0 ? (float)min_d : -1.f;
 }
@@ -758,6 +782,7 @@ struct orc_run {
 orc_run* orc_elas_run(const svh_elas_params* p, const uint8_t* I1_, const uint8_t* I2_,
                       const int32_t* dims, orc_triangulate_fn tri_fn) {
     orc_run* r = new orc_run();
+    memset(g_tie, 0, sizeof(g_tie));
     const int32_t W = dims[0], H = dims[1];
     const int32_t bpl = W + 15 - (W - 1) % 16;  // elas.cpp:37
     std::vector<uint8_t> I1((size_t)bpl * H, 0), I2((size_t)bpl * H, 0);
@@ -841,6 +866,7 @@ orc_run* orc_elas_run(const svh_elas_params* p, const uint8_t* I1_, const uint8_
 
 int32_t orc_elas_run_status(orc_run* r) { return r->status; }
 void orc_elas_run_free(orc_run* r) { delete r; }
+void orc_elas_tie_stats(int64_t out[6]) { memcpy(out, g_tie, sizeof(g_tie)); }
 
 int64_t orc_elas_run_get(orc_run* r, int32_t stage, void* buf, int64_t cap) {
     const void* src = 0;

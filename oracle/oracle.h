@@ -70,6 +70,11 @@ orc_run* orc_elas_run(const svh_elas_params* p, const uint8_t* I1, const uint8_t
 int32_t  orc_elas_run_status(orc_run* r);
 int64_t  orc_elas_run_get(orc_run* r, int32_t stage, void* buf, int64_t cap);
 void     orc_elas_run_free(orc_run* r);
+/* Tie counters of the last orc_elas_run of this process (left and right pass summed; counting changes no result):
+ *   out[0] support searches that ran their disparity loop      out[1] of those, d1 >= 0 && d2 >= 0 && e1 == e2
+ *   out[2] dense pixels with a match (min_d >= 0)              out[3] of those, the minimum attained by > 1 candidate
+ *   out[4] of those, the winner is not the smallest such d     out[5] dense pixels where no candidate was evaluated */
+void     orc_elas_tie_stats(int64_t out[6]);
 /* final maps only; returns status (0 ok, 1 = <3 support points, D untouched) */
 int32_t  orc_elas_process(const svh_elas_params* p, const uint8_t* I1, const uint8_t* I2,
                           float* D1, float* D2, const int32_t* dims, orc_triangulate_fn tri_fn);

@@ -4,6 +4,7 @@
 // Triangle.  Both record storages (MeshG: 32-bit rows, MeshL: 24-byte records) and both forms of the seam step
 // (kShort on / off) are run; with kShort every shortcut is compared with the fresh read it replaces.
 //   usage: dt_core_check [rounds] [seed]        exit 0 = identical everywhere
+//          dt_core_check --points FILE [xoff]   one point set from a file (a support list), same comparison
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -89,7 +90,73 @@ static std::vector<Pt> make_points(std::mt19937& rng, int kind, int n) {
     return p;
 }
 
+// the four forms (two storages, shortcut on / off) on one set of distinct points against csrc/delaunay.cpp on the same
+// points in input order (= ids); the cores see x + xoff, as k_delaunay does (elas_stage_kernels.hip: D.xoff), so that
+// right-image points left of column 0 fit the packed coordinates.  Returns the forms that differ, *nt = triangles
+static int check_set(const std::vector<Pt>& P, int xoff, int32_t* nt_out, int r, int kind) {
+    const int m = (int)P.size();
+    std::vector<float> pts(2 * (size_t)m);
+    for (const Pt& p : P) { pts[2 * p.id] = (float)p.x; pts[2 * p.id + 1] = (float)p.y; }
+    std::vector<int32_t> want(3 * (2 * (size_t)m + 16));
+    const int32_t nt = delaunay(pts.data(), m, want.data(), 2 * m + 16, 0);
+    want.resize(3 * (size_t)std::max(nt, 0));
+    *nt_out = nt;
+    std::vector<Pt> Q = P;
+    for (Pt& q : Q) q.x += xoff;
+    kd(Q.data(), m, 0);
+    const size_t nrec = 2 * (size_t)m + 2;
+    int bad = 0;
+    for (int form = 0; form < 4; form++) {
+        std::vector<int32_t> got;
+        if (form < 2) {
+            std::vector<int> ids(4 * nrec, 0x5a5a5a5a), xys(4 * nrec, 0x5a5a5a5a);
+            std::vector<unsigned> nbr(4 * nrec, 0x5a5a5a5au);
+            MeshG g{ids.data(), xys.data(), nbr.data()};
+            auto ids_of = [&](int t, int v[3]) { v[0] = ids[4 * t]; v[1] = ids[4 * t + 1]; v[2] = ids[4 * t + 2]; };
+            got = form == 0 ? run_mesh<false>(g, Q, ids_of) : run_mesh<true>(g, Q, ids_of);
+        } else {
+            if (m > 8000) continue;
+            std::vector<uint64_t> mem(3 * nrec, 0x5a5a5a5a5a5a5a5aull);
+            MeshL l{reinterpret_cast<unsigned char*>(mem.data())};
+            auto ids_of = [&](int t, int v[3]) {
+                const Rec rc = l.load((unsigned)t * 4u);
+                v[0] = rc.id0; v[1] = rc.id1; v[2] = rc.id2;
+            };
+            got = form == 2 ? run_mesh<false>(l, Q, ids_of) : run_mesh<true>(l, Q, ids_of);
+        }
+        if (got != want) {
+            bad++;
+            fprintf(stderr, "MISMATCH round %d kind %d m %d form %d: %zu vs %zu triangles\n", r, kind, m, form,
+                    got.size() / 3, want.size() / 3);
+        }
+    }
+    return bad;
+}
+
+// dt_core_check --points FILE [xoff]: "n" and n lines "x y" of distinct integer points (a support list in left- or
+// right-image coordinates), ids in file order
+static int check_file(const char* path, int xoff) {
+    FILE* f = fopen(path, "r");
+    int n = 0;
+    if (!f || fscanf(f, "%d", &n) != 1 || n < 2) { fprintf(stderr, "cannot read points from %s\n", path); return 2; }
+    std::vector<Pt> P((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (fscanf(f, "%d %d", &P[i].x, &P[i].y) != 2) { fprintf(stderr, "%s: point %d missing\n", path, i); return 2; }
+        P[i].id = i;
+        if (P[i].x + xoff < 0 || P[i].x + xoff > 0xffff || P[i].y < 0 || P[i].y > 0x7fff) {
+            fprintf(stderr, "%s: point %d outside the packed range\n", path, i);
+            return 2;
+        }
+    }
+    fclose(f);
+    int32_t nt = 0;
+    const int bad = check_set(P, xoff, &nt, 0, -1);
+    printf("dt_core_check: points %d, triangles %d, mismatches %d, shortcuts wrong %ld\n", n, nt, bad, g_short_bad);
+    return bad || g_short_bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 2 && strcmp(argv[1], "--points") == 0) return check_file(argv[2], argc > 3 ? atoi(argv[3]) : 0);
     const int rounds = argc > 1 ? atoi(argv[1]) : 300;
     std::mt19937 rng(argc > 2 ? (unsigned)atoi(argv[2]) : 20260929u);
     long sets = 0, tris = 0, bad = 0;
@@ -99,40 +166,8 @@ int main(int argc, char** argv) {
         std::vector<Pt> P = make_points(rng, kind, 2 + (int)(rng() % (unsigned)nmax));
         const int m = (int)P.size();
         if (m < 2) continue;
-        // expected: csrc/delaunay.cpp on the same points (input order = ids)
-        std::vector<float> pts(2 * (size_t)m);
-        for (const Pt& p : P) { pts[2 * p.id] = (float)p.x; pts[2 * p.id + 1] = (float)p.y; }
-        std::vector<int32_t> want(3 * (2 * (size_t)m + 16));
-        const int32_t nt = delaunay(pts.data(), m, want.data(), 2 * m + 16, 0);
-        want.resize(3 * (size_t)std::max(nt, 0));
-        std::vector<Pt> Q = P;
-        kd(Q.data(), m, 0);
-        const size_t nrec = 2 * (size_t)m + 2;
-        for (int form = 0; form < 4; form++) {
-            std::vector<int32_t> got;
-            if (form < 2) {
-                std::vector<int> ids(4 * nrec, 0x5a5a5a5a), xys(4 * nrec, 0x5a5a5a5a);
-                std::vector<unsigned> nbr(4 * nrec, 0x5a5a5a5au);
-                MeshG g{ids.data(), xys.data(), nbr.data()};
-                auto ids_of = [&](int t, int v[3]) { v[0] = ids[4 * t]; v[1] = ids[4 * t + 1]; v[2] = ids[4 * t + 2]; };
-                got = form == 0 ? run_mesh<false>(g, Q, ids_of) : run_mesh<true>(g, Q, ids_of);
-            } else {
-                if (m > 8000) continue;
-                std::vector<uint64_t> mem(3 * nrec, 0x5a5a5a5a5a5a5a5aull);
-                MeshL l{reinterpret_cast<unsigned char*>(mem.data())};
-                auto ids_of = [&](int t, int v[3]) {
-                    const Rec rc = l.load((unsigned)t * 4u);
-                    v[0] = rc.id0; v[1] = rc.id1; v[2] = rc.id2;
-                };
-                got = form == 2 ? run_mesh<false>(l, Q, ids_of) : run_mesh<true>(l, Q, ids_of);
-            }
-            if (got != want) {
-                bad++;
-                if (bad <= 10)
-                    fprintf(stderr, "MISMATCH round %d kind %d m %d form %d: %zu vs %zu triangles\n", r, kind, m, form,
-                            got.size() / 3, want.size() / 3);
-            }
-        }
+        int32_t nt = 0;
+        bad += check_set(P, 0, &nt, r, kind);
         sets++;
         tris += nt;
     }

@@ -323,6 +323,16 @@ def oracle_elas_run(params, I1, I2, tri_fn=None):
         lib.orc_elas_run_free(h)
 
 
+TIE_FIELDS = ("support_searches", "support_ties", "dense_matched", "dense_ties", "dense_not_lowest", "dense_unevaluated")
+
+
+def oracle_tie_stats():
+    """orc_elas_tie_stats: the tie counters of the last oracle_elas_run (oracle/oracle.h), as a dict"""
+    out = (C.c_int64 * 6)()
+    oracle().orc_elas_tie_stats(out)
+    return dict(zip(TIE_FIELDS, [int(x) for x in out]))
+
+
 STAGE_NAMES = {
     DESC1: "desc1", DESC2: "desc2", DCAN_RAW: "dcan_raw", SUPPORT: "support", TRI1: "tri1",
     TRI2: "tri2", PLANES1: "planes1", PLANES2: "planes2", GRID1: "grid1", GRID2: "grid2",
