@@ -15,25 +15,18 @@
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
 // empty, and the next entry that touches the device fills the planes with the empty values first.  That is what makes
 // "after SVH_ERR_HIP inside an add the grid is empty" hold even when the failure was a lost device queue: no HIP call is
-// needed to get there.  The finished planes are derived lazily too, by the first get or render after a change: the
-// accumulators lie at their slots (the torus of grid_core.h), the finished planes are in logical order, and every plane
-// that leaves the object is a finished one.  A scroll moves no data: it changes the offsets and resets the strips that
-// enter; on an empty grid it changes the offsets alone.  The traversability planes are derived from the finished ones, as
-// lazily, and kept until the accumulators or the traversability parameters change (trav_valid).  The planner's field (POT,
-// DIR; grid_plan_kernels.hip) is derived from COST and the goals, as lazily, and kept beside it (plan_valid) until the
-// accumulators, the offsets, the traversability, the plan parameters or the goals change.  The frontier result (FRONT, LABEL,
-// the table) is derived from STATE and COST, as lazily, and kept (front_valid) until the accumulators, the offsets, the
-// traversability or the frontier parameters change.  The rollouts cache nothing but their two tables (the footprints and the
-// candidates), which are relative and survive everything but their own setters: a scoring reads COST and, for w_pot > 0, POT.
-// The exploration layer caches one thing, the reach field: POT with the start of the last ranking as the only goal, in buffers of
-// its own beside the planner's (reach_valid), kept until the start cell, the accumulators, the offsets, the traversability or the
-// plan parameters change.  Gains and VIEW planes are computed per call.
-// The alignment layer caches its field F, derived from STATE (afield_valid), until the accumulators, the offsets or the align
-// parameters change, and keeps the scan, the volume and the record of the last alignment for the getters and the image.
+// needed to get there.  The accumulators lie at their slots (the torus of grid_core.h); everything derived from them is in
+// logical order, and every plane that leaves the object is a derived one.  A scroll moves no data: it changes the offsets
+// and resets the strips that enter; on an empty grid it changes the offsets alone.
+// Everything derived is computed lazily, by the first entry that needs it, and kept.  What is kept, what each kept layer is
+// computed from and what each change makes stale is one table, below beside the struct (Kept, kNeeds, kDrops): a setter says
+// what it changed (touch), a function that launches a layer says so (pending), and the entry that has waited for the launches
+// makes them count (settle); a failed entry makes nothing count (failed).  The reach field has a key beside its bit: the start
+// cell of the ranking it was computed for.  Gains and VIEW planes are computed per call.
 // The dynamics keep CONTRA, LAST, the THROUGH and the events of the last observation and the bodies of the cells at the cells' slots
 // (they travel with the torus and are cleared as lazily as the accumulators, dyn_need_clear); the body plane is kept by the settle
-// and written anew (body_valid) after anything else wrote the accumulators.  The frame record and `ends` are scratch, empty between
-// observations (frame_clean, ends_clean).
+// kernel and written anew (body_valid) after anything else wrote the accumulators.  The frame record and `ends` are scratch, empty
+// between observations (frame_clean, ends_clean).  These describe the accumulators' side and are not part of the table.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -145,6 +138,57 @@ struct AlignBufs {
     HipBuf<int32_t> scan, volume, rec;
 };
 
+// ---- what the object keeps, and what makes it stale ---------------------------------------------------------------------------
+// One bit each in svh_grid::valid.  A derived layer's bit: its planes are those of the state as it is.  An upload's: the device
+// holds the host's table.  A last result's: the buffers hold the records of the last scoring or alignment, for the getters and images
+enum Kept : uint32_t {
+    FINAL = 1u << 0,      // `fin`, from the accumulators and the offsets
+    TRAV = 1u << 1,       // `trav`, from `fin` and the traversability parameters
+    PLAN = 1u << 2,       // `plan`, from COST, the plan parameters and the goals
+    FRONT = 1u << 3,      // `front` and the table, from STATE, COST and the frontier parameters
+    REACH = 1u << 4,      // `reach`, from COST and the plan parameters, for the start (reach_ga, reach_gb)
+    AFIELD = 1u << 5,     // al.field, from STATE and the align parameters
+    UP_TABLE = 1u << 6,   // d_table holds `table`
+    UP_GOALS = 1u << 7,   // d_goals holds `goals`
+    UP_ROLL = 1u << 8,    // roll_bufs.offs and .start hold the footprint table
+    UP_CANDS = 1u << 9,   // d_cands and d_cand_lens hold the candidates
+    ROLL_LAST = 1u << 10, // roll_bufs.recs holds the records of the last svh_grid_roll_score
+    ALIGN_LAST = 1u << 11 // al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
+};
+constexpr int kLayers = 6;
+constexpr uint32_t kAllLayers = (1u << kLayers) - 1;
+// the layers each derived layer is computed from, by the layer's bit number
+constexpr uint32_t kNeeds[kLayers] = {0, FINAL, TRAV, TRAV, TRAV, FINAL};
+// what changes, and what it makes stale directly; the layers computed from a stale layer follow by closure()
+enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, SOURCES };
+constexpr uint32_t kDrops[SOURCES] = {
+    FINAL,                    // ACC: the accumulators or the window's offsets
+    TRAV | UP_TABLE,          // TRAV_PARAMS
+    PLAN | REACH,             // PLAN_PARAMS
+    PLAN | UP_GOALS,          // GOALS
+    FRONT,                    // FRONT_PARAMS
+    UP_ROLL | ROLL_LAST,      // ROLL_PARAMS
+    UP_CANDS | ROLL_LAST,     // CANDS: the candidate table
+    AFIELD | ALIGN_LAST,      // ALIGN_PARAMS
+};
+constexpr uint32_t closure(uint32_t m) {
+    for (int pass = 0; pass < kLayers; pass++)
+        for (int k = 0; k < kLayers; k++)
+            if (kNeeds[k] & m) m |= 1u << k;
+    return m;
+}
+struct StaleTable {
+    uint32_t of[SOURCES];
+};
+constexpr StaleTable stale_table() {
+    StaleTable t{};
+    for (int s = 0; s < SOURCES; s++) t.of[s] = closure(kDrops[s]);
+    return t;
+}
+constexpr StaleTable kStale = stale_table();
+static_assert((kStale.of[ACC] & kAllLayers) == kAllLayers, "a derived layer without a path to FINAL in kNeeds would survive a change of the accumulators");
+static_assert(kStale.of[TRAV_PARAMS] == (TRAV | PLAN | FRONT | REACH | UP_TABLE), "the closure of kNeeds");
+
 }  // namespace
 
 struct svh_grid {
@@ -163,25 +207,22 @@ struct svh_grid {
     HipBuf<uint8_t> d_rgb;      // a render bound for the host
     PinnedBuf<uint8_t> h_out;
     bool need_clear = true;     // the accumulators do not hold the empty grid yet
-    bool final_valid = false;   // `fin` is derived from the accumulators as they are
+    uint32_t valid = 0;         // Kept bits: what is current
+    uint32_t pending = 0;       // layers launched by this entry and not waited for yet: settle() makes them valid
     grid::TravParams trv{};     // the traversability layer: parameters and what is derived from them; reach 0: the
     bool trav_ok = false;       // defaults do not fit this grid's cell, and svh_grid_set_traversability has not succeeded
     std::vector<uint8_t> table; // cost by DIST2, reach^2 + 1 bytes
-    bool table_sent = false;    // d_table holds it
     HipBuf<uint8_t> d_table;
     PinnedBuf<uint8_t> h_table;
     HipBuf<uint8_t> trav;       // kTravBytes per cell: DIST2 | g | FLAGS | COST, logical order
-    bool trav_valid = false;    // ... derived from `fin` as it is, with the parameters as they are; implies final_valid
     grid::PlanParams pln{50, -1, 0x7FFFFFFE};   // the planner: parameters, the goals as global cells
     std::vector<int32_t> goals;
-    bool goals_sent = false;    // d_goals holds them
     HipBuf<int32_t> d_goals;
     PinnedBuf<int32_t> h_cells; // goals or a path on their way to the device
     HipBuf<uint8_t> plan;       // kPlanBytes per cell: POT | price | DIR, logical order
     HipBuf<uint32_t> plan_tiles;   // 4 per tile: the two lists, the two flags
     HipBuf<uint32_t> plan_ctl;  // grid::CTL_WORDS
     PinnedBuf<uint32_t> h_ctl;
-    bool plan_valid = false;    // ... derived from COST as it is, with the offsets, parameters and goals as they are; implies trav_valid
     int64_t plan_counted = 0, plan_reached = 0, plan_rounds = 0;   // of the field that is valid
     HipBuf<int32_t> d_path;     // the cells a walk writes, or a caller's path for the plan image
     HipBuf<int64_t> d_walk;     // status, length, cost
@@ -189,19 +230,15 @@ struct svh_grid {
     grid::FrontParams frp{252, 8, grid::LETHAL_UNSEEN, 0};   // the frontiers: parameters, planes, table
     HipBuf<uint8_t> front;      // kFrontBytes per cell: LABEL | FRONT, logical order
     FrontBufs front_bufs;
-    bool front_valid = false;   // ... derived from STATE and COST as they are, with the offsets and parameters as they are; implies trav_valid
     int64_t front_stats[grid::FS_WORDS] = {0, 0, 0, 0, 0};   // of the result that is valid
     RollTable rol;              // the rollouts: parameters and the footprint table; R 0: the defaults do not fit this grid's cell
     RollBufs roll_bufs;
-    bool roll_sent = false;     // roll_bufs.offs and .start hold the table
     std::vector<int32_t> cands, cand_lens;   // the candidate table (S * K * T * 3) and the lengths of its S * K candidates
     int32_t cand_S = 0, cand_K = 0, cand_T = 0;
-    bool cands_sent = false;    // d_cands and d_cand_lens hold them
     HipBuf<int32_t> d_cands, d_cand_lens;
     HipBuf<int32_t> d_poses, d_fcost;   // free poses of a host caller and their F
     PinnedBuf<uint8_t> h_roll;  // records, scores and the best on their way to the host
-    bool roll_last = false;     // roll_bufs.recs holds the records of the last svh_grid_roll_score, for svh_grid_render_roll:
-    int32_t roll_last_set = 0, roll_last_ga = 0, roll_last_gb = 0, roll_last_best = -1;   // its set, anchor and best
+    int32_t roll_last_set = 0, roll_last_ga = 0, roll_last_gb = 0, roll_last_best = -1;   // ROLL_LAST: the set, anchor and best of that scoring
     grid::ExploreParams exp{10.f, 1, 500, 1};   // the exploration layer: parameters and their R; 0: the defaults do not fit this grid's cell
     int32_t exp_R = 0;
     HipBuf<uint8_t> reach;      // kPlanBytes per cell: POT | price | DIR of the reach field, logical order
@@ -209,8 +246,7 @@ struct svh_grid {
     PinnedBuf<uint32_t> h_reach_ctl;
     HipBuf<int32_t> d_start;    // the start cell: the one goal of the reach field
     PinnedBuf<int32_t> h_start;
-    bool reach_valid = false;   // `reach` is derived from COST as it is, with the offsets and plan parameters as they are, from the start
-    int32_t reach_ga = 0, reach_gb = 0;   // ... (reach_ga, reach_gb), a global cell; implies trav_valid
+    int32_t reach_ga = 0, reach_gb = 0;   // REACH: the start the field was computed from, a global cell
     ExploreBufs ex_bufs;
     PinnedBuf<uint8_t> h_explore;   // scores, records, best and feasible count of the last ranking on their way to the host
     HipBuf<int32_t> d_vcells, d_vgain;   // viewpoints of a host caller and their GAIN
@@ -221,9 +257,7 @@ struct svh_grid {
     int32_t align_rot[2 * grid::ALIGN_MAX_ROTS] = {0};
     AlignBufs al;
     PinnedBuf<int32_t> h_arec;
-    bool afield_valid = false;  // al.field is derived from STATE as it is, with the offsets and align parameters as they are; implies final_valid
-    bool align_last = false;    // al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment:
-    int32_t align_rec[grid::ALIGN_REC] = {0}, align_Pa = 0, align_Pb = 0;   // its record and pivot sub
+    int32_t align_rec[grid::ALIGN_REC] = {0}, align_Pa = 0, align_Pb = 0;   // ALIGN_LAST: the record and pivot sub of that alignment
     svh_grid_stats st{0, 0, 0, 0, 0};
     int64_t rays = 0, ray_cells = 0;
     bool dyn_on = false;        // the dynamics: svh_grid_set_dynamics has succeeded and the layer has not been dropped
@@ -271,12 +305,39 @@ struct svh_grid {
 
 namespace {
 
-// the accumulators change: what was derived from them is stale
-void invalidate(svh_grid* g) { g->final_valid = g->trav_valid = g->plan_valid = g->front_valid = g->reach_valid = g->afield_valid = false; }
+bool has(const svh_grid* g, uint32_t kept) { return (g->valid & kept) == kept; }
+
+// `kept` is not current any more, whatever was launched
+void drop(svh_grid* g, uint32_t kept) { g->valid &= ~kept, g->pending &= ~kept; }
+
+// `s` changes: what the table derives from it is stale
+void touch(svh_grid* g, Source s) { drop(g, kStale.of[s]); }
+
+// the entry has waited for everything it launched: the layers among it count
+void settle(svh_grid* g) {
+    g->valid |= g->pending;
+    g->pending = 0;
+}
+
+// The one exit of an entry that may have failed: whatever was launched and not settled does not count, and after SVH_ERR_HIP nothing
+// of the call is in flight when the caller goes on and `kept`, what the entry's family computes, is computed again by the next call
+int failed(svh_grid* g, int rc, uint32_t kept = 0) {
+    g->pending = 0;
+    if (rc == SVH_ERR_HIP) {
+        drop(g, kept);
+        if (g->stream) {
+            (void)hipSetDevice(g->device);
+            (void)hipStreamSynchronize(g->stream);
+        }
+    }
+    return rc;
+}
+// what each family of entries drops there
+constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST;
 
 void mark_empty(svh_grid* g) {
     g->need_clear = true;
-    invalidate(g);
+    touch(g, ACC);
     g->st = svh_grid_stats{0, 0, 0, 0, 0};
     g->rays = g->ray_cells = 0;
     g->dyn_need_clear = true;
@@ -334,12 +395,35 @@ int bin_points(svh_grid* g, grid::BinJob& j, const float* xyzv, int64_t n, bool 
     return SVH_OK;
 }
 
+// `ends` exists and is all zero; it counts as dirty until the rays of the call have zeroed what its binning counts
+int zero_ends(svh_grid* g) {
+    const size_t bytes = g->ncells * sizeof(int32_t);
+    if (g->ends.cap < bytes) g->ends_clean = false;
+    GRID_GROW(g->ends, bytes);
+    if (!g->ends_clean) GRID_TRY(copy, hipMemsetAsync(g->ends, 0, bytes, g->stream));
+    g->ends_clean = false;
+    return SVH_OK;
+}
+
+// the statistics of a call of n points that is complete, from h_stats; rays: the call cast them, and `ends` is zero again
+void read_stats(svh_grid* g, int64_t n, bool rays) {
+    const unsigned long long* h = g->h_stats;
+    if (rays) {
+        g->ends_clean = true;
+        g->rays += (int64_t)h[grid::LOW] - g->st.binned;
+        g->ray_cells = (int64_t)h[grid::STAT_RAY_CELLS];
+    }
+    g->st.added += n;
+    g->st.binned = (int64_t)h[grid::LOW], g->st.overhead = (int64_t)h[grid::OVERHEAD];
+    g->st.outside = (int64_t)h[grid::OUTSIDE], g->st.unplaced = (int64_t)h[grid::UNPLACED];
+}
+
 // n > 0 points, host or device, with arguments that have been checked; origin >= 0: the logical index of the cell the
 // low points cast their rays from
 int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origin = -1) {
     int rc = ready(g);
     if (rc) return rc;
-    invalidate(g);
+    touch(g, ACC);
     g->body_valid = false;   // the dynamics: the accumulators change behind the layer
     grid::BinJob j;
     j.prm = g->prm;
@@ -347,10 +431,7 @@ int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origi
     j.stats = g->d_stats;
     hipStream_t s = g->stream;
     if (origin >= 0) {
-        if (g->ends.cap < g->ncells * sizeof(int32_t)) g->ends_clean = false;
-        GRID_GROW(g->ends, g->ncells * sizeof(int32_t));
-        if (!g->ends_clean) GRID_TRY(copy, hipMemsetAsync(g->ends, 0, g->ncells * sizeof(int32_t), s));
-        g->ends_clean = false;   // until the rays of this call have zeroed what its binning counts
+        if ((rc = zero_ends(g))) return rc;
         j.ends = g->ends;
     }
     if ((rc = bin_points(g, j, xyzv, n, on_device))) return rc;
@@ -365,15 +446,7 @@ int add(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origi
     }
     GRID_TRY(copy, hipMemcpyAsync(g->h_stats, g->d_stats, grid::STAT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     GRID_TRY(wait, hipStreamSynchronize(s));
-    const unsigned long long* h = g->h_stats;
-    if (origin >= 0) {
-        g->ends_clean = true;
-        g->rays += (int64_t)h[grid::LOW] - g->st.binned;
-        g->ray_cells = (int64_t)h[grid::STAT_RAY_CELLS];
-    }
-    g->st.added += n;
-    g->st.binned = (int64_t)h[grid::LOW], g->st.overhead = (int64_t)h[grid::OVERHEAD];
-    g->st.outside = (int64_t)h[grid::OUTSIDE], g->st.unplaced = (int64_t)h[grid::UNPLACED];
+    read_stats(g, n, origin >= 0);
     return SVH_OK;
 }
 
@@ -396,20 +469,18 @@ int dyn_ready(svh_grid* g) {
 int observe(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t origin, int32_t q_o) {
     int rc = ready(g);
     if (rc || (rc = dyn_ready(g))) return rc;
-    invalidate(g);
+    touch(g, ACC);
     hipStream_t s = g->stream;
     const size_t nc = g->ncells;
-    if (g->ends.cap < nc * sizeof(int32_t)) g->ends_clean = false;
+    if ((rc = zero_ends(g))) return rc;
     if (g->frame.cap < nc * grid::FRAME_BYTES) g->frame_clean = false;
-    GRID_GROW(g->ends, nc * sizeof(int32_t));
     GRID_GROW(g->frame, nc * grid::FRAME_BYTES);
-    if (!g->ends_clean) GRID_TRY(copy, hipMemsetAsync(g->ends, 0, nc * sizeof(int32_t), s));
     if (!g->frame_clean) {
         GRID_TRY(copy, hipMemsetAsync(g->frame, 0xFF, 4 * nc, s));
         GRID_TRY(copy, hipMemsetAsync(g->frame + 4 * nc, 0, (grid::FRAME_BYTES - 4) * nc, s));
         GRID_TRY(copy, hipMemsetAsync(g->dplanes().through, 0, 4 * nc, s));
     }
-    g->ends_clean = g->frame_clean = false;   // until this observation has settled
+    g->frame_clean = false;   // as `ends`: until this observation has settled
     const int32_t stamp = g->stamp + 1;
     if (n > 0) {
         grid::BinJob j;
@@ -438,12 +509,8 @@ int observe(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t o
     GRID_TRY(copy, hipMemcpyAsync(g->h_stats, g->d_stats, grid::STAT_ALL * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     GRID_TRY(wait, hipStreamSynchronize(s));
     const unsigned long long* h = g->h_stats;
-    g->ends_clean = g->frame_clean = true;
-    g->rays += (int64_t)h[grid::LOW] - g->st.binned;
-    g->ray_cells = (int64_t)h[grid::STAT_RAY_CELLS];
-    g->st.added += n;
-    g->st.binned = (int64_t)h[grid::LOW], g->st.overhead = (int64_t)h[grid::OVERHEAD];
-    g->st.outside = (int64_t)h[grid::OUTSIDE], g->st.unplaced = (int64_t)h[grid::UNPLACED];
+    read_stats(g, n, true);
+    g->frame_clean = true;
     if (n > 0) g->body_valid = true;   // k_grid_body wrote it or it was valid, and k_grid_settle kept it
     g->stamp = stamp;
     g->dyn_stats[grid::DS_OBSERVATIONS] = stamp;
@@ -451,9 +518,9 @@ int observe(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int64_t o
     return SVH_OK;
 }
 
-// the finished planes, launched on the stream; the caller waits and then sets final_valid
+// the finished planes, launched on the stream and pending until the caller has waited and settles
 int finalise(svh_grid* g) {
-    if (g->final_valid) return SVH_OK;
+    if (has(g, FINAL)) return SVH_OK;
     grid::FinalJob j;
     j.prm = g->prm;
     j.cells = g->cells();
@@ -461,6 +528,7 @@ int finalise(svh_grid* g) {
     j.hmin = g->fplane(F_HMIN), j.hmax = g->fplane(F_HMAX), j.hmean = g->fplane(F_HMEAN);
     j.intensity = g->bplane(B_INTENSITY), j.cls = g->bplane(B_CLASS), j.state = g->bplane(B_STATE);
     GRID_TRY(launch, (grid::launch_finalise(g->stream, j), hipGetLastError()));
+    g->pending |= FINAL;
     return SVH_OK;
 }
 
@@ -486,76 +554,76 @@ int get(svh_grid* g, bool bytes, int k, void* out, bool on_device) {
     const void* src = bytes ? (const void*)g->bplane(k) : (const void*)g->iplane(k);
     if ((rc = finalise(g))) return rc;
     if ((rc = deliver(g, src, g->ncells * (bytes ? 1 : 4), out, on_device))) return rc;
-    g->final_valid = true;
+    settle(g);
     return SVH_OK;
 }
 
-// mode: a grid::Mode, M_LOCAL included
-int render(svh_grid* g, int32_t mode, uint8_t* rgb, bool on_device) {
+// The end of an entry whose kernels wrote `bytes` to the caller's device array, or to the scratch `src` on their way to the host
+// array `out`: the wait, or the copy and the wait; then what the entry launched counts
+int finish(svh_grid* g, const void* src, size_t bytes, void* out, bool on_device) {
+    if (on_device) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    } else {
+        const int rc = deliver(g, src, bytes, out, false);
+        if (rc) return rc;
+    }
+    settle(g);
+    return SVH_OK;
+}
+
+// Every image: the buffers, room for an image bound for the host, then draw(dst), which makes the layers it reads current and
+// enqueues its launches into `dst` (their one check follows here), then finish().  dyn: the image reads the planes of the dynamics
+template <typename Draw>
+int render_with(svh_grid* g, uint8_t* rgb, bool on_device, bool dyn, Draw draw) {
     int rc = ready(g);
-    if (rc) return rc;
+    if (rc || (dyn && (rc = dyn_ready(g)))) return rc;
     const size_t bytes = g->ncells * 3;
     if (!on_device) {
         GRID_GROW(g->d_rgb, bytes);
         GRID_GROW(g->h_out, bytes);
     }
-    if ((rc = finalise(g))) return rc;
+    if ((rc = draw(on_device ? rgb : g->d_rgb.p))) return rc;
+    GRID_TRY(launch, hipGetLastError());
+    return finish(g, g->d_rgb, bytes, rgb, on_device);
+}
+
+// the job of an image of the finished planes in `mode` (a grid::Mode, M_LOCAL included)
+grid::RenderJob render_job(const svh_grid* g, int32_t mode, uint8_t* dst) {
     grid::RenderJob j;
     j.prm = g->prm;
     j.mode = mode;
     j.count = g->iplane(F_COUNT), j.pass = g->iplane(F_PASS);
     j.hmin = g->fplane(F_HMIN), j.hmax = g->fplane(F_HMAX), j.hmean = g->fplane(F_HMEAN);
     j.intensity = g->bplane(B_INTENSITY), j.cls = g->bplane(B_CLASS);
-    j.rgb = on_device ? rgb : g->d_rgb.p;
-    GRID_TRY(launch, (grid::launch_render(g->stream, j), hipGetLastError()));
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+    j.rgb = dst;
+    return j;
+}
+
+int render(svh_grid* g, int32_t mode, uint8_t* rgb, bool on_device) {
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        const int rc = finalise(g);
+        if (!rc) grid::launch_render(g->stream, render_job(g, mode, dst));
         return rc;
-    }
-    g->final_valid = true;
-    return SVH_OK;
+    });
 }
 
 // a plane of the layer in logical order
 int get_dyn(svh_grid* g, int32_t plane, int32_t* out, bool on_device) {
     int rc = ready(g);
     if (rc || (rc = dyn_ready(g))) return rc;
-    if (!on_device) GRID_GROW(g->d_dyn, g->ncells * sizeof(int32_t));
+    const size_t bytes = g->ncells * sizeof(int32_t);
+    if (!on_device) GRID_GROW(g->d_dyn, bytes);
     int32_t* dst = on_device ? out : g->d_dyn.p;
     GRID_TRY(launch, (grid::launch_dyn_get(g->stream, g->prm, plane, g->stamp, g->dplanes(), dst), hipGetLastError()));
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-        return SVH_OK;
-    }
-    return deliver(g, g->d_dyn, g->ncells * sizeof(int32_t), out, false);
+    return finish(g, g->d_dyn, bytes, out, on_device);
 }
 
-// svh_grid_render_dyn: render()'s steps with the layer's kernel
 int render_dyn(svh_grid* g, uint8_t* rgb, bool on_device) {
-    int rc = ready(g);
-    if (rc || (rc = dyn_ready(g))) return rc;
-    const size_t bytes = g->ncells * 3;
-    if (!on_device) {
-        GRID_GROW(g->d_rgb, bytes);
-        GRID_GROW(g->h_out, bytes);
-    }
-    if ((rc = finalise(g))) return rc;
-    grid::RenderJob j;
-    j.prm = g->prm;
-    j.mode = grid::M_LOCAL;
-    j.count = g->iplane(F_COUNT), j.pass = g->iplane(F_PASS);
-    j.hmin = g->fplane(F_HMIN), j.hmax = g->fplane(F_HMAX), j.hmean = g->fplane(F_HMEAN);
-    j.intensity = g->bplane(B_INTENSITY), j.cls = g->bplane(B_CLASS);
-    j.rgb = on_device ? rgb : g->d_rgb.p;
-    GRID_TRY(launch, (grid::launch_render_dyn(g->stream, j, g->dplanes()), hipGetLastError()));
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+    return render_with(g, rgb, on_device, true, [&](uint8_t* dst) {
+        const int rc = finalise(g);
+        if (!rc) grid::launch_render_dyn(g->stream, render_job(g, grid::M_LOCAL, dst), g->dplanes());
         return rc;
-    }
-    g->final_valid = true;
-    return SVH_OK;
+    });
 }
 
 // svh_grid_trav_params -> grid::TravParams with the derived values and the cost table for a cell side; false: out of range
@@ -572,7 +640,7 @@ bool convert_trav(const svh_grid_trav_params* t, float cell, grid::TravParams* q
 
 // the cost table lies on the device
 int send_table(svh_grid* g) {
-    if (g->table_sent) return SVH_OK;
+    if (has(g, UP_TABLE)) return SVH_OK;
     GRID_TRY(none, hipSetDevice(g->device));
     const size_t bytes = g->table.size();
     GRID_GROW(g->d_table, bytes);
@@ -580,14 +648,13 @@ int send_table(svh_grid* g) {
     memcpy(g->h_table, g->table.data(), bytes);
     GRID_TRY(copy, hipMemcpyAsync(g->d_table, g->h_table, bytes, hipMemcpyHostToDevice, g->stream));
     GRID_TRY(wait, hipStreamSynchronize(g->stream));   // the staging buffer is free again
-    g->table_sent = true;
+    g->valid |= UP_TABLE;
     return SVH_OK;
 }
 
-// the finished planes and the three traversability planes, launched on the stream; the caller waits and then sets
-// final_valid and trav_valid
+// the finished planes and the three traversability planes, launched on the stream and pending until the caller has waited and settles
 int traverse(svh_grid* g) {
-    if (g->trav_valid) return SVH_OK;
+    if (has(g, TRAV)) return SVH_OK;
     GRID_GROW(g->trav, g->ncells * kTravBytes);
     int rc = send_table(g);
     if (rc) return rc;
@@ -599,6 +666,7 @@ int traverse(svh_grid* g) {
     j.table = g->d_table.p;
     j.flags = g->t_flags(), j.g = g->t_g(), j.dist2 = g->t_dist2(), j.cost = g->t_cost();
     GRID_TRY(launch, (grid::launch_trav(g->stream, j), hipGetLastError()));
+    g->pending |= TRAV;
     return SVH_OK;
 }
 
@@ -609,46 +677,35 @@ int get_trav(svh_grid* g, int32_t plane, void* out, bool on_device) {
     const void* src = plane == grid::TV_FLAGS ? (const void*)g->t_flags() : plane == grid::TV_DIST2 ? (const void*)g->t_dist2()
                                                                                                    : (const void*)g->t_cost();
     if ((rc = deliver(g, src, g->ncells * (plane == grid::TV_DIST2 ? 4 : 1), out, on_device))) return rc;
-    g->final_valid = g->trav_valid = true;
+    settle(g);
     return SVH_OK;
 }
 
-int render_cost(svh_grid* g, uint8_t* rgb, bool on_device) {
-    int rc = ready(g);
-    if (rc) return rc;
-    const size_t bytes = g->ncells * 3;
-    if (!on_device) {
-        GRID_GROW(g->d_rgb, bytes);
-        GRID_GROW(g->h_out, bytes);
-    }
-    if ((rc = traverse(g))) return rc;
+// the job of the image of COST, which the images of the layers above it draw over
+grid::RenderCostJob cost_job(const svh_grid* g, uint8_t* dst) {
     grid::RenderCostJob j;
     j.nx = g->prm.nx, j.nz = g->prm.nz;
     j.cost = g->t_cost(), j.flags = g->t_flags();
-    j.rgb = on_device ? rgb : g->d_rgb.p;
-    GRID_TRY(launch, (grid::launch_render_cost(g->stream, j), hipGetLastError()));
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
-        return rc;
-    }
-    g->final_valid = g->trav_valid = true;
-    return SVH_OK;
+    j.rgb = dst;
+    return j;
 }
 
-// nothing of a failed call is in flight when the caller goes on
-int drained(svh_grid* g, int rc) {
-    if (rc == SVH_ERR_HIP && g->stream) {
-        (void)hipSetDevice(g->device);
-        (void)hipStreamSynchronize(g->stream);
-    }
-    return rc;
+int render_cost(svh_grid* g, uint8_t* rgb, bool on_device) {
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        const int rc = traverse(g);
+        if (!rc) grid::launch_render_cost(g->stream, cost_job(g, dst));
+        return rc;
+    });
 }
 
 // ---- the planner ----------------------------------------------------------------------------------------------------------
 void forget_goals(svh_grid* g) {
     g->goals.clear();
-    g->goals_sent = g->plan_valid = false;
+    touch(g, GOALS);
+}
+
+size_t plan_tiles(const grid::Params& p) {
+    return ((size_t)(p.nx + grid::PLAN_TILE - 1) / grid::PLAN_TILE) * ((size_t)(p.nz + grid::PLAN_TILE - 1) / grid::PLAN_TILE);
 }
 
 // The rounds of the relaxation on a seeded job, until a round finds its list empty: g_rounds_per_wait launches, then the control
@@ -700,7 +757,7 @@ int send_cells(svh_grid* g, const int32_t* cells, int64_t n, HipBuf<int32_t>& ds
 
 grid::PlanJob plan_job(const svh_grid* g) {
     grid::PlanJob j;
-    const size_t tiles = ((size_t)(g->prm.nx + grid::PLAN_TILE - 1) / grid::PLAN_TILE) * ((size_t)(g->prm.nz + grid::PLAN_TILE - 1) / grid::PLAN_TILE);
+    const size_t tiles = plan_tiles(g->prm);
     j.pln = g->pln;
     j.nx = g->prm.nx, j.nz = g->prm.nz, j.oa = g->prm.oa, j.ob = g->prm.ob;
     j.cost = g->t_cost();
@@ -713,21 +770,22 @@ grid::PlanJob plan_job(const svh_grid* g) {
 
 // the field is valid: the cost planes, then seed, rounds and DIR; complete when it returns
 int plan_field(svh_grid* g) {
-    if (g->plan_valid) return SVH_OK;
-    const size_t tiles = ((size_t)(g->prm.nx + grid::PLAN_TILE - 1) / grid::PLAN_TILE) * ((size_t)(g->prm.nz + grid::PLAN_TILE - 1) / grid::PLAN_TILE);
+    if (has(g, PLAN)) return SVH_OK;
+    const size_t tiles = plan_tiles(g->prm);
     GRID_GROW(g->plan, g->ncells * kPlanBytes);
     GRID_GROW(g->plan_tiles, 4 * tiles * sizeof(uint32_t));
     GRID_GROW(g->plan_ctl, grid::CTL_WORDS * sizeof(uint32_t));
     GRID_GROW(g->h_ctl, grid::CTL_WORDS * sizeof(uint32_t));
     int rc;
-    if (!g->goals_sent && !g->goals.empty() && (rc = send_cells(g, g->goals.data(), (int64_t)(g->goals.size() / 2), g->d_goals))) return rc;
-    g->goals_sent = true;
+    if (!has(g, UP_GOALS) && !g->goals.empty() && (rc = send_cells(g, g->goals.data(), (int64_t)(g->goals.size() / 2), g->d_goals))) return rc;
+    g->valid |= UP_GOALS;
     if ((rc = traverse(g))) return rc;
     if ((rc = plan_run(g->stream, plan_job(g), g->h_ctl))) return rc;
     const uint32_t* h = g->h_ctl;
     g->plan_counted = h[grid::CTL_COUNTED], g->plan_rounds = h[grid::CTL_ROUNDS];
     g->plan_reached = (int64_t)((uint64_t)h[grid::CTL_REACHED] | ((uint64_t)h[grid::CTL_REACHED + 1] << 32));
-    g->final_valid = g->trav_valid = g->plan_valid = true;
+    g->pending |= PLAN;
+    settle(g);
     return SVH_OK;
 }
 
@@ -757,35 +815,15 @@ int plan_path(svh_grid* g, int32_t a, int32_t b, int32_t* cells, int64_t cap, in
 }
 
 int render_plan(svh_grid* g, const int32_t* cells, int64_t n, uint8_t* rgb, bool on_device) {
-    int rc = ready(g);
-    if (rc) return rc;
-    const size_t bytes = g->ncells * 3;
-    if (!on_device) {
-        GRID_GROW(g->d_rgb, bytes);
-        GRID_GROW(g->h_out, bytes);
-    }
-    if ((rc = plan_field(g))) return rc;
-    if (n > 0 && (rc = send_cells(g, cells, n, g->d_path))) return rc;
-    grid::RenderCostJob j;
-    j.nx = g->prm.nx, j.nz = g->prm.nz;
-    j.cost = g->t_cost(), j.flags = g->t_flags();
-    j.rgb = on_device ? rgb : g->d_rgb.p;
-    const grid::PlanJob pj = plan_job(g);
-    grid::launch_render_cost(g->stream, j);
-    grid::launch_plan_overlay(g->stream, pj, pj.goals, pj.n_goals, true, j.rgb);
-    grid::launch_plan_overlay(g->stream, pj, g->d_path, n, false, j.rgb);
-    GRID_TRY(launch, hipGetLastError());
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-        return SVH_OK;
-    }
-    return deliver(g, g->d_rgb, bytes, rgb, false);
-}
-
-// a planning call that failed on the device: nothing in flight, the field is computed again by the next call
-int planned(svh_grid* g, int rc) {
-    if (rc == SVH_ERR_HIP) g->plan_valid = false;
-    return drained(g, rc);
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        int rc = plan_field(g);
+        if (rc || (n > 0 && (rc = send_cells(g, cells, n, g->d_path)))) return rc;
+        const grid::PlanJob pj = plan_job(g);
+        grid::launch_render_cost(g->stream, cost_job(g, dst));
+        grid::launch_plan_overlay(g->stream, pj, pj.goals, pj.n_goals, true, dst);
+        grid::launch_plan_overlay(g->stream, pj, g->d_path, n, false, dst);
+        return rc;
+    });
 }
 
 // ---- the frontiers --------------------------------------------------------------------------------------------------------
@@ -832,7 +870,7 @@ int front_run(hipStream_t s, grid::FrontJob& j, FrontBufs& b, int64_t stats[grid
 
 // the frontier result is valid: the cost planes, then front_run
 int frontiers(svh_grid* g) {
-    if (g->front_valid) return SVH_OK;
+    if (has(g, FRONT)) return SVH_OK;
     GRID_GROW(g->front, g->ncells * kFrontBytes);
     int rc = traverse(g);
     if (rc) return rc;
@@ -844,7 +882,8 @@ int frontiers(svh_grid* g) {
     int64_t stats[grid::FS_WORDS];
     if ((rc = front_run(g->stream, j, g->front_bufs, stats))) return rc;
     memcpy(g->front_stats, stats, sizeof(stats));
-    g->final_valid = g->trav_valid = g->front_valid = true;
+    g->pending |= FRONT;
+    settle(g);
     return SVH_OK;
 }
 
@@ -867,32 +906,13 @@ int get_frontiers(svh_grid* g, int32_t* recs, int64_t cap, int64_t* n) {
 }
 
 int render_frontiers(svh_grid* g, uint8_t* rgb, bool on_device) {
-    int rc = ready(g);
-    if (rc) return rc;
-    const size_t bytes = g->ncells * 3;
-    if (!on_device) {
-        GRID_GROW(g->d_rgb, bytes);
-        GRID_GROW(g->h_out, bytes);
-    }
-    if ((rc = frontiers(g))) return rc;
-    grid::RenderCostJob j;
-    j.nx = g->prm.nx, j.nz = g->prm.nz;
-    j.cost = g->t_cost(), j.flags = g->t_flags();
-    j.rgb = on_device ? rgb : g->d_rgb.p;
-    grid::launch_render_cost(g->stream, j);
-    grid::launch_front_overlay(g->stream, j.nx, j.nz, g->f_flags(), j.rgb);
-    GRID_TRY(launch, hipGetLastError());
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-        return SVH_OK;
-    }
-    return deliver(g, g->d_rgb, bytes, rgb, false);
-}
-
-// a frontier call that failed on the device: nothing in flight, the result is computed again by the next call
-int fronted(svh_grid* g, int rc) {
-    if (rc == SVH_ERR_HIP) g->front_valid = false;
-    return drained(g, rc);
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        const int rc = frontiers(g);
+        if (rc) return rc;
+        grid::launch_render_cost(g->stream, cost_job(g, dst));
+        grid::launch_front_overlay(g->stream, g->prm.nx, g->prm.nz, g->f_flags(), dst);
+        return rc;
+    });
 }
 
 bool convert_front(const svh_grid_front_params* p, grid::FrontParams* q) {
@@ -949,18 +969,18 @@ int roll_outputs(RollBufs& b, int32_t K) {
 // both tables lie on the device
 int roll_tables(svh_grid* g, bool candidates) {
     GRID_TRY(none, hipSetDevice(g->device));
-    if (!g->roll_sent) {
+    if (!has(g, UP_ROLL)) {
         const int rc = send_roll_table(g->stream, g->rol, g->roll_bufs);
         if (rc) return rc;
-        g->roll_sent = true;
+        g->valid |= UP_ROLL;
     }
-    if (candidates && !g->cands_sent) {
+    if (candidates && !has(g, UP_CANDS)) {
         GRID_GROW_N(g->d_cands, g->cands.size());
         GRID_GROW_N(g->d_cand_lens, g->cand_lens.size());
         GRID_TRY(copy, hipMemcpyAsync(g->d_cands, g->cands.data(), g->cands.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
         GRID_TRY(copy, hipMemcpyAsync(g->d_cand_lens, g->cand_lens.data(), g->cand_lens.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
         GRID_TRY(wait, hipStreamSynchronize(g->stream));
-        g->cands_sent = true;
+        g->valid |= UP_CANDS;
     }
     return SVH_OK;
 }
@@ -983,13 +1003,7 @@ int footprint_cost(svh_grid* g, const int32_t* poses, int64_t n, bool on_device,
     if ((rc = traverse(g))) return rc;
     grid::launch_footprint_cost(g->stream, roll_job(g), on_device ? poses : g->d_poses.p, n, on_device ? out : g->d_fcost.p);
     GRID_TRY(launch, hipGetLastError());
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-    } else if ((rc = deliver(g, g->d_fcost, (size_t)n * sizeof(int32_t), out, false))) {
-        return rc;
-    }
-    g->final_valid = g->trav_valid = true;
-    return SVH_OK;
+    return finish(g, g->d_fcost, (size_t)n * sizeof(int32_t), out, on_device);
 }
 
 // set `set` scored at the global cell (ga, gb); recs and scores may be null
@@ -998,7 +1012,7 @@ int roll_score(svh_grid* g, int32_t ga, int32_t gb, int32_t set, int32_t* recs, 
     if (rc) return rc;
     const int32_t K = g->cand_K;
     const size_t rec_bytes = (size_t)K * grid::ROLL_REC * sizeof(int32_t), score_bytes = (size_t)K * sizeof(int64_t);
-    g->roll_last = false;
+    drop(g, ROLL_LAST);
     if ((rc = roll_outputs(g->roll_bufs, K))) return rc;
     GRID_GROW(g->h_roll, score_bytes + rec_bytes + sizeof(int32_t));   // the scores first: they are the widest
     if ((rc = roll_tables(g, true))) return rc;
@@ -1012,46 +1026,25 @@ int roll_score(svh_grid* g, int32_t ga, int32_t gb, int32_t set, int32_t* recs, 
     if (recs) GRID_TRY(copy, hipMemcpyAsync(on_device ? (void*)recs : (void*)(h + score_bytes), j.recs, rec_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     GRID_TRY(copy, hipMemcpyAsync(h + score_bytes + rec_bytes, j.best, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     GRID_TRY(wait, hipStreamSynchronize(s));
-    g->final_valid = g->trav_valid = true;
+    settle(g);
     if (scores && !on_device) memcpy(scores, h, score_bytes);
     if (recs && !on_device) memcpy(recs, h + score_bytes, rec_bytes);
     memcpy(best, h + score_bytes + rec_bytes, sizeof(int32_t));
-    g->roll_last = true;
+    g->valid |= ROLL_LAST;
     g->roll_last_set = set, g->roll_last_ga = ga, g->roll_last_gb = gb, g->roll_last_best = *best;
     return SVH_OK;
 }
 
 int render_roll(svh_grid* g, uint8_t* rgb, bool on_device) {
-    int rc = ready(g);
-    if (rc) return rc;
-    const size_t bytes = g->ncells * 3;
-    if (!on_device) {
-        GRID_GROW(g->d_rgb, bytes);
-        GRID_GROW(g->h_out, bytes);
-    }
-    if ((rc = traverse(g))) return rc;
-    grid::RenderCostJob c;
-    c.nx = g->prm.nx, c.nz = g->prm.nz;
-    c.cost = g->t_cost(), c.flags = g->t_flags();
-    c.rgb = on_device ? rgb : g->d_rgb.p;
-    grid::RollJob j = roll_job(g);
-    roll_candidates(j, g->roll_bufs, g->d_cands, g->d_cand_lens, g->roll_last_set, g->cand_K, g->cand_T, g->roll_last_ga, g->roll_last_gb);
-    grid::launch_render_cost(g->stream, c);
-    grid::launch_roll_overlay(g->stream, j, g->roll_last_best, c.rgb);
-    GRID_TRY(launch, hipGetLastError());
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        const int rc = traverse(g);
+        if (rc) return rc;
+        grid::RollJob j = roll_job(g);
+        roll_candidates(j, g->roll_bufs, g->d_cands, g->d_cand_lens, g->roll_last_set, g->cand_K, g->cand_T, g->roll_last_ga, g->roll_last_gb);
+        grid::launch_render_cost(g->stream, cost_job(g, dst));
+        grid::launch_roll_overlay(g->stream, j, g->roll_last_best, dst);
         return rc;
-    }
-    g->final_valid = g->trav_valid = true;
-    return SVH_OK;
-}
-
-// a rollout call that failed on the device: nothing in flight, and no records for svh_grid_render_roll to draw
-int rolled(svh_grid* g, int rc) {
-    if (rc == SVH_ERR_HIP) g->roll_last = false;
-    return drained(g, rc);
+    });
 }
 
 const char* const kNoRoll =": the default vehicle does not fit this grid's cell; set one (svh_grid_set_roll)";
@@ -1182,7 +1175,7 @@ int explore_outputs(ExploreBufs& b, int32_t n, grid::ExploreJob& j) {
 // the job of the reach field: the planner's kernels on buffers of their own, the start as the only goal
 grid::PlanJob reach_job(const svh_grid* g) {
     grid::PlanJob j = plan_job(g);
-    const size_t tiles = (size_t)grid::plan_tiles_x(j) * grid::plan_tiles_y(j);
+    const size_t tiles = plan_tiles(g->prm);
     j.pot = g->r_pot(), j.price = (uint16_t*)(g->reach.p + 4 * g->ncells), j.dir = g->reach.p + 6 * g->ncells;
     j.goals = g->d_start.p, j.n_goals = 1;
     j.lists = g->reach_tiles.p, j.flags = g->reach_tiles.p + 2 * tiles;
@@ -1193,9 +1186,9 @@ grid::PlanJob reach_job(const svh_grid* g) {
 // the reach field from the global cell (ga, gb) is valid: the cost planes, then seed, rounds and DIR on the second job; complete
 // when it returns.  The planner's goals, buffers and field play no part
 int reach_field(svh_grid* g, int32_t ga, int32_t gb) {
-    if (g->reach_valid && g->reach_ga == ga && g->reach_gb == gb) return SVH_OK;
-    g->reach_valid = false;
-    const size_t tiles = ((size_t)(g->prm.nx + grid::PLAN_TILE - 1) / grid::PLAN_TILE) * ((size_t)(g->prm.nz + grid::PLAN_TILE - 1) / grid::PLAN_TILE);
+    if (has(g, REACH) && g->reach_ga == ga && g->reach_gb == gb) return SVH_OK;
+    drop(g, REACH);
+    const size_t tiles = plan_tiles(g->prm);
     GRID_GROW(g->reach, g->ncells * kPlanBytes);
     GRID_GROW(g->reach_tiles, 4 * tiles * sizeof(uint32_t));
     GRID_GROW(g->reach_ctl, grid::CTL_WORDS * sizeof(uint32_t));
@@ -1207,7 +1200,8 @@ int reach_field(svh_grid* g, int32_t ga, int32_t gb) {
     int rc = traverse(g);
     if (rc) return rc;
     if ((rc = plan_run(g->stream, reach_job(g), g->h_reach_ctl))) return rc;
-    g->final_valid = g->trav_valid = g->reach_valid = true;
+    g->pending |= REACH;
+    settle(g);
     g->reach_ga = ga, g->reach_gb = gb;
     g->ex_stats[grid::ES_FIELDS]++;
     return SVH_OK;
@@ -1259,12 +1253,7 @@ int view_gain(svh_grid* g, const int32_t* cells, int64_t n, bool on_device, int3
     if ((rc = finalise(g))) return rc;
     const int32_t launches = grid::launch_view_gain(g->stream, explore_job(g), on_device ? cells : g->d_vcells.p, 2, n, on_device ? out : g->d_vgain.p);
     GRID_TRY(launch, hipGetLastError());
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-    } else if ((rc = deliver(g, g->d_vgain, (size_t)n * sizeof(int32_t), out, false))) {
-        return rc;
-    }
-    g->final_valid = true;
+    if ((rc = finish(g, g->d_vgain, (size_t)n * sizeof(int32_t), out, on_device))) return rc;
     g->ex_stats[grid::ES_LAUNCHES] = launches;
     return SVH_OK;
 }
@@ -1284,39 +1273,19 @@ int view_mask(svh_grid* g, int32_t va, int32_t vb, uint8_t* out, bool on_device)
     if (rc) return rc;
     if ((rc = view_plane(g, va, vb))) return rc;
     if ((rc = deliver(g, g->d_view, g->ncells, out, on_device))) return rc;
-    g->final_valid = true;
+    settle(g);
     return SVH_OK;
 }
 
 int render_view(svh_grid* g, int32_t va, int32_t vb, uint8_t* rgb, bool on_device) {
-    int rc = ready(g);
-    if (rc) return rc;
-    const size_t bytes = g->ncells * 3;
-    if (!on_device) {
-        GRID_GROW(g->d_rgb, bytes);
-        GRID_GROW(g->h_out, bytes);
-    }
-    if ((rc = frontiers(g))) return rc;
-    if ((rc = view_plane(g, va, vb))) return rc;
-    grid::RenderCostJob j;
-    j.nx = g->prm.nx, j.nz = g->prm.nz;
-    j.cost = g->t_cost(), j.flags = g->t_flags();
-    j.rgb = on_device ? rgb : g->d_rgb.p;
-    grid::launch_render_cost(g->stream, j);
-    grid::launch_front_overlay(g->stream, j.nx, j.nz, g->f_flags(), j.rgb);
-    grid::launch_view_overlay(g->stream, j.nx, j.nz, g->d_view, va, vb, j.rgb);
-    GRID_TRY(launch, hipGetLastError());
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-        return SVH_OK;
-    }
-    return deliver(g, g->d_rgb, bytes, rgb, false);
-}
-
-// an exploration call that failed on the device: nothing in flight, the reach field is computed again by the next ranking
-int explored(svh_grid* g, int rc) {
-    if (rc == SVH_ERR_HIP) g->reach_valid = false;
-    return drained(g, rc);
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        int rc = frontiers(g);
+        if (rc || (rc = view_plane(g, va, vb))) return rc;
+        grid::launch_render_cost(g->stream, cost_job(g, dst));
+        grid::launch_front_overlay(g->stream, g->prm.nx, g->prm.nz, g->f_flags(), dst);
+        grid::launch_view_overlay(g->stream, g->prm.nx, g->prm.nz, g->d_view, va, vb, dst);
+        return rc;
+    });
 }
 
 // what svh_test_grid_explore and svh_test_grid_explore_device share: the arguments checked, the parameters converted, *R
@@ -1399,24 +1368,25 @@ int align_finish(hipStream_t s, const grid::AlignJob& j) {
     return SVH_OK;
 }
 
-// al.field is valid, launched on the stream; the caller waits and then sets final_valid and afield_valid
+// the finished planes and al.field, launched on the stream and pending until the caller has waited and settles
 int align_field(svh_grid* g, const grid::AlignJob& j) {
     const int rc = finalise(g);
-    if (rc) return rc;
-    if (!g->afield_valid) GRID_TRY(launch, (grid::launch_align_field(g->stream, j, (g_align_form & grid::ALIGN_FORM_MASK) != 0), hipGetLastError()));
+    if (rc || has(g, AFIELD)) return rc;
+    GRID_TRY(launch, (grid::launch_align_field(g->stream, j, (g_align_form & grid::ALIGN_FORM_MASK) != 0), hipGetLastError()));
+    g->pending |= AFIELD;
     return SVH_OK;
 }
 
 int object_align_job(svh_grid* g, int32_t Pa, int32_t Pb, int64_t n, grid::AlignJob* j) {
     const int rc = ready(g);
     if (rc) return rc;
-    if (g->al.field.cap < g->ncells) g->afield_valid = false;
+    if (g->al.field.cap < g->ncells) drop(g, AFIELD);   // a growth that failed left no field
     return align_job(g->al, g->prm, g->alp, g->bplane(B_STATE), Pa, Pb, n, j);
 }
 
 // n >= 0 points, host or device, about the pivot sub, with arguments that have been checked: the record
 int align(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int32_t Pa, int32_t Pb, int32_t* rec) {
-    g->align_last = false;
+    drop(g, ALIGN_LAST);
     grid::AlignJob j;
     int rc = object_align_job(g, Pa, Pb, n, &j);
     if (rc) return rc;
@@ -1441,7 +1411,8 @@ int align(svh_grid* g, const float* xyzv, int64_t n, bool on_device, int32_t Pa,
     if ((rc = align_finish(s, j))) return rc;
     GRID_TRY(copy, hipMemcpyAsync(g->h_arec, j.rec, grid::ALIGN_REC * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     GRID_TRY(wait, hipStreamSynchronize(s));
-    g->final_valid = g->afield_valid = g->align_last = true;
+    settle(g);
+    g->valid |= ALIGN_LAST;
     memcpy(g->align_rec, g->h_arec, sizeof(g->align_rec));
     g->align_Pa = Pa, g->align_Pb = Pb;
     memcpy(rec, g->align_rec, sizeof(g->align_rec));
@@ -1454,47 +1425,23 @@ int get_align_field(svh_grid* g, uint8_t* out, bool on_device) {
     if (rc) return rc;
     if ((rc = align_field(g, j))) return rc;
     if ((rc = deliver(g, j.field, g->ncells, out, on_device))) return rc;
-    g->final_valid = g->afield_valid = true;
+    settle(g);
     return SVH_OK;
 }
 
 int render_align(svh_grid* g, uint8_t* rgb, bool on_device) {
-    int rc = ready(g);
-    if (rc) return rc;
-    const size_t bytes = g->ncells * 3;
-    if (!on_device) {
-        GRID_GROW(g->d_rgb, bytes);
-        GRID_GROW(g->h_out, bytes);
-    }
-    if ((rc = finalise(g))) return rc;
-    grid::RenderJob r;
-    r.prm = g->prm;
-    r.mode = grid::M_LOCAL;
-    r.count = g->iplane(F_COUNT), r.pass = g->iplane(F_PASS);
-    r.hmin = g->fplane(F_HMIN), r.hmax = g->fplane(F_HMAX), r.hmean = g->fplane(F_HMEAN);
-    r.intensity = g->bplane(B_INTENSITY), r.cls = g->bplane(B_CLASS);
-    r.rgb = on_device ? rgb : g->d_rgb.p;
-    grid::launch_render(g->stream, r);
-    grid::AlignJob j{};   // the buffers are those of the last alignment: nothing grows
-    j.prm = g->prm, j.alp = g->alp, j.Pa = g->align_Pa, j.Pb = g->align_Pb;
-    memcpy(j.rot, g->align_rot, sizeof(j.rot));
-    j.scan = g->al.scan;
-    const int32_t* rec = g->align_rec;
-    grid::launch_align_overlay(g->stream, j, rec[grid::AR_SCAN], rec[grid::AR_K], rec[grid::AR_TA], rec[grid::AR_TB], r.rgb);
-    GRID_TRY(launch, hipGetLastError());
-    if (on_device) {
-        GRID_TRY(wait, hipStreamSynchronize(g->stream));
-    } else if ((rc = deliver(g, g->d_rgb, bytes, rgb, false))) {
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        const int rc = finalise(g);
+        if (rc) return rc;
+        grid::launch_render(g->stream, render_job(g, grid::M_LOCAL, dst));
+        grid::AlignJob j{};   // the buffers are those of the last alignment: nothing grows
+        j.prm = g->prm, j.alp = g->alp, j.Pa = g->align_Pa, j.Pb = g->align_Pb;
+        memcpy(j.rot, g->align_rot, sizeof(j.rot));
+        j.scan = g->al.scan;
+        const int32_t* rec = g->align_rec;
+        grid::launch_align_overlay(g->stream, j, rec[grid::AR_SCAN], rec[grid::AR_K], rec[grid::AR_TA], rec[grid::AR_TB], dst);
         return rc;
-    }
-    g->final_valid = true;
-    return SVH_OK;
-}
-
-// an align call that failed on the device: nothing in flight, the field and the last alignment are gone
-int aligned(svh_grid* g, int rc) {
-    if (rc == SVH_ERR_HIP) g->afield_valid = g->align_last = false;
-    return drained(g, rc);
+    });
 }
 
 // what svh_test_grid_align and svh_test_grid_align_device share: the arguments checked and converted, the pivot's sub
@@ -1520,17 +1467,14 @@ bool align_test_args(const svh_grid_params* p, const svh_grid_align_params* a, i
 
 // ... and a failed add leaves the empty grid
 int added(svh_grid* g, int rc) {
-    if (rc == SVH_ERR_HIP) {
-        drained(g, rc);
-        mark_empty(g);
-    }
+    if (failed(g, rc) == SVH_ERR_HIP) mark_empty(g);
     return rc;
 }
 
 // the window moves by (da, db) cells to offsets that have been checked, not both zero
 int scroll(svh_grid* g, int32_t da, int32_t db) {
     g->prm.oa += da, g->prm.ob += db;
-    invalidate(g);
+    touch(g, ACC);
     if (g->need_clear) return SVH_OK;   // the empty grid has no cell to reset
     int rc = ready(g);
     if (rc) return rc;
@@ -1764,12 +1708,12 @@ int32_t svh_grid_get_ray_stats(svh_grid* g, int64_t out[2]) {
 
 int32_t svh_grid_get_local(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
     if (!g || !out || plane < 0 || plane >= grid::L_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_local: a grid, a plane 0..1 and an output are needed");
-    return drained(g, plane == grid::L_PASS ? get(g, false, F_PASS, out, on_device != 0) : get(g, true, B_STATE, out, on_device != 0));
+    return failed(g, plane == grid::L_PASS ? get(g, false, F_PASS, out, on_device != 0) : get(g, true, B_STATE, out, on_device != 0));
 }
 
 int32_t svh_grid_render_local(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_local: a grid and an output are needed");
-    return drained(g, render(g, grid::M_LOCAL, rgb, on_device != 0));
+    return failed(g, render(g, grid::M_LOCAL, rgb, on_device != 0));
 }
 
 int32_t svh_grid_get_stats(svh_grid* g, svh_grid_stats* stats) {
@@ -1782,12 +1726,12 @@ int32_t svh_grid_get(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
     if (!g || !out || plane < 0 || plane >= grid::P_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get: a grid, a plane 0..6 and an output are needed");
     static const int word[5] = {F_COUNT, F_OVERHEAD, F_HMIN, F_HMAX, F_HMEAN};
     const bool bytes = plane >= grid::P_INTENSITY;
-    return drained(g, get(g, bytes, bytes ? (plane == grid::P_INTENSITY ? B_INTENSITY : B_CLASS) : word[plane], out, on_device != 0));
+    return failed(g, get(g, bytes, bytes ? (plane == grid::P_INTENSITY ? B_INTENSITY : B_CLASS) : word[plane], out, on_device != 0));
 }
 
 int32_t svh_grid_render(svh_grid* g, int32_t mode, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb || mode < 0 || mode >= grid::M_MODES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render: a grid, a mode 0..2 and an output are needed");
-    return drained(g, render(g, mode, rgb, on_device != 0));
+    return failed(g, render(g, mode, rgb, on_device != 0));
 }
 
 int32_t svh_grid_set_traversability(svh_grid* g, const svh_grid_trav_params* t) {
@@ -1798,8 +1742,8 @@ int32_t svh_grid_set_traversability(svh_grid* g, const svh_grid_trav_params* t) 
     g->trv = q;
     g->table.swap(table);
     g->trav_ok = true;
-    g->trav_valid = g->plan_valid = g->front_valid = g->reach_valid = g->table_sent = false;
-    return drained(g, send_table(g));   // a failed upload is repeated by the next svh_grid_get_trav / svh_grid_render_cost
+    touch(g, TRAV_PARAMS);
+    return failed(g, send_table(g));   // a failed upload is repeated by the next svh_grid_get_trav / svh_grid_render_cost
 }
 
 int32_t svh_grid_get_traversability(svh_grid* g, svh_grid_trav_params* t, int32_t* reach) {
@@ -1812,13 +1756,13 @@ int32_t svh_grid_get_traversability(svh_grid* g, svh_grid_trav_params* t, int32_
 int32_t svh_grid_get_trav(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
     if (!g || !out || plane < 0 || plane >= grid::TV_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_trav: a grid, a plane 0..2 and an output are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_trav: the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)");
-    return drained(g, get_trav(g, plane, out, on_device != 0));
+    return failed(g, get_trav(g, plane, out, on_device != 0));
 }
 
 int32_t svh_grid_render_cost(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_cost: a grid and an output are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_cost: the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)");
-    return drained(g, render_cost(g, rgb, on_device != 0));
+    return failed(g, render_cost(g, rgb, on_device != 0));
 }
 
 void svh_grid_plan_params_default(svh_grid_plan_params* p) {
@@ -1831,7 +1775,7 @@ int32_t svh_grid_set_plan(svh_grid* g, const svh_grid_plan_params* p) {
     const grid::PlanParams q{p->neutral, p->unknown, p->max_cost};
     if (!grid::plan_ok(q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_plan: parameters out of range (include/svh_grid.h)");
     g->pln = q;
-    g->plan_valid = g->reach_valid = false;
+    touch(g, PLAN_PARAMS);
     return SVH_OK;
 }
 
@@ -1848,7 +1792,7 @@ int32_t svh_grid_plan_set_goals(svh_grid* g, const int32_t* cells, int32_t n) {
         if (cells[k] <= -grid::PLAN_GOAL_LIMIT || cells[k] >= grid::PLAN_GOAL_LIMIT)
             return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_plan_set_goals: a goal's cell is not below 2^20");
     g->goals.assign(cells, cells + 2 * (size_t)n);
-    g->goals_sent = g->plan_valid = false;
+    touch(g, GOALS);
     return SVH_OK;
 }
 
@@ -1864,7 +1808,7 @@ int32_t svh_grid_get_plan_plane(svh_grid* g, int32_t plane, void* out, int32_t o
     if (!g || !out || plane < 0 || plane >= grid::PL_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_plan_plane: a grid, a plane 0..1 and an output are needed");
     if (on_device && plane == grid::PL_POT && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_plan_plane: a device array of POT must be 4-byte aligned");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_plan_plane") + kNoTrav);
-    return planned(g, get_plan(g, plane, out, on_device != 0));
+    return failed(g, get_plan(g, plane, out, on_device != 0), kPlanner);
 }
 
 int32_t svh_grid_get_plan_stats(svh_grid* g, int64_t out[4]) {
@@ -1872,7 +1816,7 @@ int32_t svh_grid_get_plan_stats(svh_grid* g, int64_t out[4]) {
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_plan_stats") + kNoTrav);
     int rc = ready(g);
     if (!rc) rc = plan_field(g);
-    if (rc) return planned(g, rc);
+    if (rc) return failed(g, rc, kPlanner);
     out[0] = (int64_t)(g->goals.size() / 2), out[1] = g->plan_counted, out[2] = g->plan_reached, out[3] = g->plan_rounds;
     return SVH_OK;
 }
@@ -1891,7 +1835,7 @@ int32_t svh_grid_plan_path(svh_grid* g, const double start_xyz[3], int32_t* cell
     }
     int64_t n = 0;
     int32_t c = grid::PLAN_FAR, status = 0;
-    const int rc = planned(g, plan_path(g, (int32_t)a, (int32_t)b, cells, cap, &n, &c, &status));
+    const int rc = failed(g, plan_path(g, (int32_t)a, (int32_t)b, cells, cap, &n, &c, &status), kPlanner);
     if (rc) return rc;
     *len = n, *cost = c;
     return status;
@@ -1900,7 +1844,7 @@ int32_t svh_grid_plan_path(svh_grid* g, const double start_xyz[3], int32_t* cell
 int32_t svh_grid_render_plan(svh_grid* g, const int32_t* cells, int64_t n, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb || n < 0 || (n > 0 && !cells)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_plan: a grid, n >= 0 cells and an output are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_plan") + kNoTrav);
-    return planned(g, render_plan(g, cells, n, rgb, on_device != 0));
+    return failed(g, render_plan(g, cells, n, rgb, on_device != 0), kPlanner);
 }
 
 void svh_grid_front_params_default(svh_grid_front_params* p) {
@@ -1912,7 +1856,7 @@ int32_t svh_grid_set_frontier(svh_grid* g, const svh_grid_front_params* p) {
     grid::FrontParams q;
     if (!g || !convert_front(p, &q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_frontier: a grid and parameters in range are needed (include/svh_grid.h)");
     g->frp = q;
-    g->front_valid = false;
+    touch(g, FRONT_PARAMS);
     return SVH_OK;
 }
 
@@ -1926,13 +1870,13 @@ int32_t svh_grid_get_front_plane(svh_grid* g, int32_t plane, void* out, int32_t 
     if (!g || !out || plane < 0 || plane >= grid::FP_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_front_plane: a grid, a plane 0..1 and an output are needed");
     if (on_device && plane == grid::FP_LABEL && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_front_plane: a device array of LABEL must be 4-byte aligned");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_front_plane") + kNoTrav);
-    return fronted(g, get_front(g, plane, out, on_device != 0));
+    return failed(g, get_front(g, plane, out, on_device != 0), kFrontier);
 }
 
 int32_t svh_grid_get_frontiers(svh_grid* g, int32_t* recs, int64_t cap, int64_t* n) {
     if (!g || !n || cap < 0 || (cap > 0 && !recs)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_frontiers: a grid, a count and room for cap >= 0 records are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_frontiers") + kNoTrav);
-    return fronted(g, get_frontiers(g, recs, cap, n));
+    return failed(g, get_frontiers(g, recs, cap, n), kFrontier);
 }
 
 int32_t svh_grid_get_frontier_stats(svh_grid* g, int64_t out[5]) {
@@ -1940,7 +1884,7 @@ int32_t svh_grid_get_frontier_stats(svh_grid* g, int64_t out[5]) {
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_frontier_stats") + kNoTrav);
     int rc = ready(g);
     if (!rc) rc = frontiers(g);
-    if (rc) return fronted(g, rc);
+    if (rc) return failed(g, rc, kFrontier);
     memcpy(out, g->front_stats, sizeof(g->front_stats));
     return SVH_OK;
 }
@@ -1956,19 +1900,19 @@ int32_t svh_grid_plan_set_goals_frontiers(svh_grid* g) {
         recs.resize((size_t)std::min<int64_t>(g->front_stats[grid::FS_KEPT], grid::PLAN_MAX_GOALS) * grid::FRONT_REC);
         rc = get_frontiers(g, recs.data(), (int64_t)(recs.size() / grid::FRONT_REC), &kept);
     }
-    if (rc) return fronted(g, rc);                     // the goals are as they were
+    if (rc) return failed(g, rc, kFrontier);                     // the goals are as they were
     const size_t m = recs.size() / grid::FRONT_REC;
     g->goals.resize(2 * m);
     for (size_t k = 0; k < m; k++)
         g->goals[2 * k] = recs[k * grid::FRONT_REC + grid::FR_REP_GA], g->goals[2 * k + 1] = recs[k * grid::FRONT_REC + grid::FR_REP_GB];
-    g->goals_sent = g->plan_valid = false;
+    touch(g, GOALS);
     return (int32_t)m;
 }
 
 int32_t svh_grid_render_frontiers(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_frontiers: a grid and an output are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_frontiers") + kNoTrav);
-    return fronted(g, render_frontiers(g, rgb, on_device != 0));
+    return failed(g, render_frontiers(g, rgb, on_device != 0), kFrontier);
 }
 
 void svh_grid_roll_params_default(svh_grid_roll_params* p) {
@@ -1985,11 +1929,11 @@ int32_t svh_grid_set_roll(svh_grid* g, const svh_grid_roll_params* p) {
     if (t.p.m != g->rol.p.m) {   // the headings of the candidates were those of the old enumeration
         g->cands.clear(), g->cand_lens.clear();
         g->cand_S = g->cand_K = g->cand_T = 0;
-        g->cands_sent = false;
+        touch(g, CANDS);
     }
     g->rol = std::move(t);
-    g->roll_sent = g->roll_last = false;
-    return drained(g, roll_tables(g, false));   // a failed upload is repeated by the next call that needs the table
+    touch(g, ROLL_PARAMS);
+    return failed(g, roll_tables(g, false));   // a failed upload is repeated by the next call that needs the table
 }
 
 int32_t svh_grid_get_roll(svh_grid* g, svh_grid_roll_params* p, int32_t* reach_R, int64_t* footprint_cells_total) {
@@ -2036,7 +1980,7 @@ int32_t svh_grid_footprint_cost(svh_grid* g, const int32_t* poses, int64_t n, in
         for (int64_t i = 0; i < n; i++)
             if (poses[3 * i + 2] < 0 || poses[3 * i + 2] >= 8 * g->rol.p.m) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_footprint_cost: a heading is not in 0..8 m - 1");
     if (n == 0) return SVH_OK;
-    return drained(g, footprint_cost(g, poses, n, on_device != 0, out));
+    return failed(g, footprint_cost(g, poses, n, on_device != 0, out));
 }
 
 int32_t svh_grid_roll_set_candidates(svh_grid* g, const int32_t* table, int32_t S, int32_t K, int32_t T) {
@@ -2047,9 +1991,9 @@ int32_t svh_grid_roll_set_candidates(svh_grid* g, const int32_t* table, int32_t 
     g->cand_lens.resize(n);
     for (size_t c = 0; c < n; c++) g->cand_lens[c] = grid::roll_len(table + c * (size_t)T * 3, T);
     g->cand_S = S, g->cand_K = K, g->cand_T = T;
-    g->cands_sent = g->roll_last = false;
+    touch(g, CANDS);
     if (!g->rol.R) return SVH_OK;                  // no table to send yet; svh_grid_roll_score sends both
-    return drained(g, roll_tables(g, true));       // a failed upload is repeated by the next svh_grid_roll_score
+    return failed(g, roll_tables(g, true));       // a failed upload is repeated by the next svh_grid_roll_score
 }
 
 int32_t svh_grid_roll_get_candidates(svh_grid* g, int32_t skt[3]) {
@@ -2069,14 +2013,14 @@ int32_t svh_grid_roll_score(svh_grid* g, const double anchor_xyz[3], int32_t set
     if (set < 0 || set >= g->cand_S) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score: no such set");
     if (on_device && (((uintptr_t)recs & 3) || ((uintptr_t)scores & 7)))
         return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score: a device array of records must be 4-byte, one of scores 8-byte aligned");
-    return rolled(g, roll_score(g, ga, gb, set, recs, scores, on_device != 0, best));
+    return failed(g, roll_score(g, ga, gb, set, recs, scores, on_device != 0, best), kRollouts);
 }
 
 int32_t svh_grid_render_roll(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_roll: a grid and an output are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_roll") + kNoTrav);
-    if (!g->roll_last) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_roll: nothing was scored since the tables were set (svh_grid_roll_score)");
-    return drained(g, render_roll(g, rgb, on_device != 0));
+    if (!has(g, ROLL_LAST)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_roll: nothing was scored since the tables were set (svh_grid_roll_score)");
+    return failed(g, render_roll(g, rgb, on_device != 0));
 }
 
 void svh_grid_explore_params_default(svh_grid_explore_params* p) {
@@ -2110,7 +2054,7 @@ int32_t svh_grid_view_gain(svh_grid* g, const int32_t* cells, int64_t n, int32_t
         g->ex_stats[grid::ES_LAUNCHES] = 0;
         return SVH_OK;
     }
-    return explored(g, view_gain(g, cells, n, on_device != 0, out));
+    return failed(g, view_gain(g, cells, n, on_device != 0, out), kExploration);
 }
 
 int32_t svh_grid_view_mask(svh_grid* g, int32_t ga, int32_t gb, uint8_t* out, int32_t on_device) {
@@ -2119,7 +2063,7 @@ int32_t svh_grid_view_mask(svh_grid* g, int32_t ga, int32_t gb, uint8_t* out, in
     if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_view_mask") + kNoExplore);
     const int64_t va = (int64_t)ga - g->prm.oa, vb = (int64_t)gb - g->prm.ob;
     if (va < 0 || va >= g->prm.nx || vb < 0 || vb >= g->prm.nz) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_view_mask: the viewpoint is outside the window");
-    return explored(g, view_mask(g, (int32_t)va, (int32_t)vb, out, on_device != 0));
+    return failed(g, view_mask(g, (int32_t)va, (int32_t)vb, out, on_device != 0), kExploration);
 }
 
 int32_t svh_grid_explore_rank(svh_grid* g, const double start_xyz[3], int32_t* recs, int64_t* scores, int64_t cap, int64_t* n, int32_t* best) {
@@ -2129,7 +2073,7 @@ int32_t svh_grid_explore_rank(svh_grid* g, const double start_xyz[3], int32_t* r
         return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_explore_rank: a grid, outputs, cap >= 0 and a finite start with a cell below 2^20 are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_explore_rank") + kNoTrav);
     if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_explore_rank") + kNoExplore);
-    return explored(g, explore_rank(g, ga, gb, recs, scores, cap, n, best));
+    return failed(g, explore_rank(g, ga, gb, recs, scores, cap, n, best), kExploration);
 }
 
 int32_t svh_grid_plan_set_goal_explore(svh_grid* g, const double start_xyz[3]) {
@@ -2141,13 +2085,13 @@ int32_t svh_grid_plan_set_goal_explore(svh_grid* g, const double start_xyz[3]) {
     if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_plan_set_goal_explore") + kNoExplore);
     int64_t n = 0;
     int32_t best = -1;
-    const int rc = explored(g, explore_rank(g, ga, gb, nullptr, nullptr, 0, &n, &best));
+    const int rc = failed(g, explore_rank(g, ga, gb, nullptr, nullptr, 0, &n, &best), kExploration);
     if (rc) return rc;                                 // the goals are as they were
     if (best < 0) return 0;
     int32_t rec[grid::EXPLORE_REC];
     memcpy(rec, g->h_explore.p + (size_t)n * sizeof(int64_t) + (size_t)best * sizeof(rec), sizeof(rec));
     g->goals.assign(rec + grid::ER_REP_GA, rec + grid::ER_REP_GA + 2);
-    g->goals_sent = g->plan_valid = false;
+    touch(g, GOALS);
     return 1;
 }
 
@@ -2163,7 +2107,7 @@ int32_t svh_grid_render_view(svh_grid* g, int32_t ga, int32_t gb, uint8_t* rgb, 
     if (!g->exp_R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_view") + kNoExplore);
     const int64_t va = (int64_t)ga - g->prm.oa, vb = (int64_t)gb - g->prm.ob;
     if (va < 0 || va >= g->prm.nx || vb < 0 || vb >= g->prm.nz) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_view: the viewpoint is outside the window");
-    return explored(g, render_view(g, (int32_t)va, (int32_t)vb, rgb, on_device != 0));
+    return failed(g, render_view(g, (int32_t)va, (int32_t)vb, rgb, on_device != 0), kExploration);
 }
 
 void svh_grid_align_params_default(svh_grid_align_params* p) {
@@ -2179,14 +2123,14 @@ int32_t svh_grid_set_align(svh_grid* g, const svh_grid_align_params* p) {
     memset(g->align_rot, 0, sizeof(g->align_rot));
     grid::align_rot_table(q.rot_den, q.rot_n, g->align_rot);
     g->align_ok = true;
-    g->afield_valid = g->align_last = false;
+    touch(g, ALIGN_PARAMS);
     return SVH_OK;
 }
 
 int32_t svh_grid_get_align_field(svh_grid* g, uint8_t* out, int32_t on_device) {
     if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_field: a grid and an output are needed");
     if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_align_field") + kNoAlign);
-    return aligned(g, get_align_field(g, out, on_device != 0));
+    return failed(g, get_align_field(g, out, on_device != 0), kAlign);
 }
 
 int32_t svh_grid_align_points(svh_grid* g, const float* xyzv, int64_t n, int32_t on_device, const double pivot[3], int32_t rec[8]) {
@@ -2197,7 +2141,7 @@ int32_t svh_grid_align_points(svh_grid* g, const float* xyzv, int64_t n, int32_t
     if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_align_points") + kNoAlign);
     if (!position(pivot, pv) || !grid::align_pivot(g->prm, pv[0], pv[1], pv[2], &Pa, &Pb))
         return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_align_points: the pivot must be finite with a cell below 2^20");
-    return aligned(g, align(g, xyzv, n, on_device != 0, Pa, Pb, rec));
+    return failed(g, align(g, xyzv, n, on_device != 0, Pa, Pb, rec), kAlign);
 }
 
 int32_t svh_grid_align_view_lists(svh_grid* g, svh_view* v, int32_t first_list, int32_t n_lists, const double pivot[3], int32_t rec[8]) {
@@ -2217,33 +2161,33 @@ int32_t svh_grid_align_view_lists(svh_grid* g, svh_view* v, int32_t first_list, 
         GRID_TRY(wait, hipStreamSynchronize(r.stream));   // the store is complete before this stream reads it
         return align(g, (const float*)(r.pts + at), n, true, Pa, Pb, rec);
     }();
-    return aligned(g, rc);
+    return failed(g, rc, kAlign);
 }
 
 int32_t svh_grid_get_align_volume(svh_grid* g, int32_t* out, int32_t on_device) {
     if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_volume: a grid and an output are needed");
     if (on_device && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_volume: a device array must be 4-byte aligned");
     if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_align_volume") + kNoAlign);
-    if (!g->align_last || g->align_rec[grid::AR_STATUS] == grid::ALIGN_FEW)
+    if (!has(g, ALIGN_LAST) || g->align_rec[grid::AR_STATUS] == grid::ALIGN_FEW)
         return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_volume: there is no volume: no alignment since the parameters were set, the last one failed or had too few subs");
     const int rc = [&]() -> int {
         GRID_TRY(none, hipSetDevice(g->device));
         return deliver(g, g->al.volume, (size_t)grid::align_volume_size(g->alp.rot_n, g->alp.trans_n) * sizeof(int32_t), out, on_device != 0);
     }();
-    return drained(g, rc);
+    return failed(g, rc);
 }
 
 int32_t svh_grid_get_align_scan(svh_grid* g, int32_t* subs, int64_t cap, int64_t* n) {
     if (!g || !n || cap < 0 || (cap > 0 && !subs)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_scan: a grid, cap >= 0 with room and a count are needed");
     if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_align_scan") + kNoAlign);
-    if (!g->align_last) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_scan: there is no scan: no alignment since the parameters were set, or the last one failed");
+    if (!has(g, ALIGN_LAST)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_align_scan: there is no scan: no alignment since the parameters were set, or the last one failed");
     const int64_t have = g->align_rec[grid::AR_SCAN], give = std::min(have, cap);
     if (give > 0) {
         const int rc = [&]() -> int {
             GRID_TRY(none, hipSetDevice(g->device));
             return deliver(g, g->al.scan, (size_t)give * 2 * sizeof(int32_t), subs, false);
         }();
-        if (rc) return drained(g, rc);
+        if (rc) return failed(g, rc);
     }
     *n = have;
     return SVH_OK;
@@ -2262,8 +2206,8 @@ int32_t svh_grid_align_correction(svh_grid* g, int32_t k, int32_t ta, int32_t tb
 int32_t svh_grid_render_align(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_align: a grid and an output are needed");
     if (!g->align_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_align") + kNoAlign);
-    if (!g->align_last) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_align: there is no alignment to draw: none since the parameters were set, or the last one failed");
-    return drained(g, render_align(g, rgb, on_device != 0));
+    if (!has(g, ALIGN_LAST)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_align: there is no alignment to draw: none since the parameters were set, or the last one failed");
+    return failed(g, render_align(g, rgb, on_device != 0));
 }
 
 void svh_grid_dyn_params_default(svh_grid_dyn_params* p) {
@@ -2297,7 +2241,7 @@ int32_t svh_grid_set_dynamics(svh_grid* g, const svh_grid_dyn_params* p) {
         return SVH_OK;
     }();
     if (rc) g->dyn_need_clear = true;
-    return drained(g, rc);
+    return failed(g, rc);
 }
 
 int32_t svh_grid_get_dynamics(svh_grid* g, svh_grid_dyn_params* p) {
@@ -2343,7 +2287,7 @@ int32_t svh_grid_observe_view_lists(svh_grid* g, svh_view* v, int32_t first_list
 int32_t svh_grid_get_dyn(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
     if (!g || !out || plane < 0 || plane >= grid::D_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_dyn: a grid, a plane 0..2 and an output are needed");
     if (!g->dyn_on) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_dyn") + kNoDyn);
-    return drained(g, get_dyn(g, plane, (int32_t*)out, on_device != 0));
+    return failed(g, get_dyn(g, plane, (int32_t*)out, on_device != 0));
 }
 
 int32_t svh_grid_get_dyn_stats(svh_grid* g, int64_t out[4]) {
@@ -2355,7 +2299,7 @@ int32_t svh_grid_get_dyn_stats(svh_grid* g, int64_t out[4]) {
 int32_t svh_grid_render_dyn(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_dyn: a grid and an output are needed");
     if (!g->dyn_on) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_dyn") + kNoDyn);
-    return drained(g, render_dyn(g, rgb, on_device != 0));
+    return failed(g, render_dyn(g, rgb, on_device != 0));
 }
 
 // grid_dyn_core.h on the host.  svh_test_grid_dyn_params: the checks of svh_grid_set_dynamics and *margin_q; SVH_ERR_BAD_ARG when

@@ -1,6 +1,6 @@
-"""GPU: the part of the ground grid's engine that decides whether a kernel runs at all (stereo-vision_amd/csrc/grid_engine.cpp: seven
-validity flags, four "already on the device" flags, two "last result" holders) pinned from outside, against the tables of
-tests/grid_cache_cases.py, which tests/test_grid_cache.py pins on the CPU.
+"""GPU: the part of the ground grid's engine that decides whether a kernel runs at all (stereo-vision_amd/csrc/grid_engine.cpp: the
+`valid` mask of six derived layers, four uploads and two last results with its table of needs and drops, and `body_valid`) pinned
+from outside, against the tables of tests/grid_cache_cases.py, which tests/test_grid_cache.py pins on the CPU.
 
 The rule under test: a read through a cache is indistinguishable from a read computed from the state as it is.  So every test keeps
 three things under one history of state-changing calls: `warm`, an object that was read in between; `fresh`, a new object that
@@ -89,6 +89,25 @@ def test_matrix(G, hip, m):
     rig.g.close()
 
 
+@pytest.mark.parametrize("n", [n for n, r in CC.READERS.items() if r.cached])
+def test_a_getter_keeps_what_it_computed(G, hip, n):
+    """After a plain add every derived plane is stale and this getter is the first entry to find it so: it computes what it returns.
+    The same read again, under the simulated error launch:1:0, must then be served without a launch, with the same bytes.  The
+    matrix cannot see a getter that computes and forgets to say so: every read-out of it starts with svh_grid_render_roll, which
+    makes COST and the finished planes valid for all that follow, and a second computation returns the same bytes."""
+    rig = CC.Rig(G, hip)
+    assert not rig.apply("add_points")
+    first = CC.READERS[n].dev(rig.g)
+    G.lib().svh_test_fail_at(b"launch:1:0")
+    try:
+        again = CC.READERS[n].dev(rig.g)
+    except G.SvhError as e:
+        raise AssertionError("%s computed its planes and did not keep them: the second read launched a kernel (%s)" % (n, e))
+    G.lib().svh_test_fail_at(None)
+    assert again == first, n
+    rig.g.close()
+
+
 # ---- read order ------------------------------------------------------------------------------------------------------------------
 LAST = [n for n in CC.READERS][:5]
 REST = [n for n in CC.READERS if n not in LAST]
@@ -97,7 +116,7 @@ REST = [n for n in CC.READERS if n not in LAST]
 def orders():
     """The FIRST read after the mutator finds every derived plane stale, so it is what differs between the orders: lowest layer
     first; svh_grid_explore_rank first, which needs the frontiers, the reach field, COST and the finished planes at once; the
-    planner, the frontiers, a scoring and the alignment field first, each of which sets several flags in one call; three seeded
+    planner, the frontiers, a scoring and the alignment field first, each of which settles several layers in one call; three seeded
     permutations.  The readers of a last result (svh_grid_render_roll and svh_grid_render_align among them, which would make COST
     and the finished planes valid before anything else ran) come LAST in every order, after the three state-bearing readers have
     all run: then they show the same scoring, ranking and alignment whatever the order was"""
