@@ -210,6 +210,10 @@
  * invalidates what an add invalidates.  After SVH_ERR_HIP inside svh_grid_observe_* the grid is EMPTY as after a failed add:
  * statistics, stamp, CONTRA and LAST included; the parameters of the layer stay set and the next observation has stamp 1.
  *
+ * OBJECTS: the obstacle cells grouped into things, and their tracks from frame to frame (svh_grid_set_objects, svh_grid_get_objects,
+ * svh_grid_objects_step, svh_grid_get_tracks, svh_grid_render_objects).  The text and the entries are in svh_grid_obj.h, which this
+ * header includes at its end.
+ *
  * Plain C like svh_view.h.  An object has its own stream and every call returns when it is complete.  Calls return
  * SVH_OK or a negative SVH_ERR_*; svh_last_error() has the text.  SVH_ERR_BAD_ARG -- a null pointer, parameters out of
  * the ranges below, n < 0, n > 0 with a null array, a device array that is not 16-byte aligned, an unknown plane or
@@ -574,4 +578,6 @@ int32_t   svh_grid_render_dyn(svh_grid* g, uint8_t* rgb, int32_t on_device);
 #ifdef __cplusplus
 }
 #endif
+
+#include "svh_grid_obj.h"   /* OBJECTS: obstacle components as things and their tracks from frame to frame */
 #endif

@@ -7,6 +7,8 @@
 // (grid_plan_kernels.hip): the planner -- the relaxation over active tiles, whose round loop is plan_rounds() here;
 // (grid_front_kernels.hip): the frontiers -- mask, union-find labelling, the table of components, run by front_run() here;
 // (grid_roll_kernels.hip): the rollouts -- footprint costs, the scoring of a set of candidates and its best;
+// (grid_obj_kernels.hip): the objects and their tracks -- obstacle components labelled by the frontier layer's kernels, the table of
+// kept ones, and the step that associates them with the tracks of the step before, run by obj_run() and objects_step() here;
 // (grid_explore_kernels.hip): the exploration layer -- the gain of viewpoints, the ranking of the frontiers, run by explore_rank() here;
 // (grid_align_kernels.hip): the alignment layer -- the field, the scan of a frame's obstacle points, the volume of scores, run by align() here;
 // (grid_dyn_kernels.hip): the dynamics -- the sight lines and the settle of an observation, run by observe() here.
@@ -99,6 +101,23 @@ struct FrontBufs {
     PinnedBuf<unsigned long long> h_ctl;
 };
 
+// the same for the objects: the ranks of the kept components (`slot`) stay with the roots, for the steps of the tracks
+struct ObjBufs {
+    HipBuf<int32_t> blocks, roots, slot, recs;
+    HipBuf<uint8_t> acc;
+    HipBuf<unsigned long long> ctl;
+    PinnedBuf<unsigned long long> h_ctl;
+};
+
+// the tracks: two track tables and two ID planes (a step reads one and writes the other), the scratch of a step, and the control
+// words with the first records of ASSIGN on their way to the host
+struct TrackBufs {
+    HipBuf<int32_t> table[2], id[2], assign, counts;
+    HipBuf<unsigned long long> keys, ctl;
+    HipBuf<uint8_t> zero, ones;
+    PinnedBuf<uint8_t> h_out;
+};
+
 // the rollout parameters with what is derived from them for a cell side: the reach and the footprint table (grid_roll_core.h)
 struct RollTable {
     grid::RollParams p{3.5f, 1.0f, 0.9f, 8, 253, 254, 1, 1, 0};
@@ -148,19 +167,20 @@ enum Kept : uint32_t {
     FRONT = 1u << 3,      // `front` and the table, from STATE, COST and the frontier parameters
     REACH = 1u << 4,      // `reach`, from COST and the plan parameters, for the start (reach_ga, reach_gb)
     AFIELD = 1u << 5,     // al.field, from STATE and the align parameters
-    UP_TABLE = 1u << 6,   // d_table holds `table`
-    UP_GOALS = 1u << 7,   // d_goals holds `goals`
-    UP_ROLL = 1u << 8,    // roll_bufs.offs and .start hold the footprint table
-    UP_CANDS = 1u << 9,   // d_cands and d_cand_lens hold the candidates
-    ROLL_LAST = 1u << 10, // roll_bufs.recs holds the records of the last svh_grid_roll_score
-    ALIGN_LAST = 1u << 11 // al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
+    OBJ = 1u << 6,        // `obj`, the object table and its statistics, from STATE, HMAX, COUNT and the object parameters
+    UP_TABLE = 1u << 7,   // d_table holds `table`
+    UP_GOALS = 1u << 8,   // d_goals holds `goals`
+    UP_ROLL = 1u << 9,    // roll_bufs.offs and .start hold the footprint table
+    UP_CANDS = 1u << 10,  // d_cands and d_cand_lens hold the candidates
+    ROLL_LAST = 1u << 11, // roll_bufs.recs holds the records of the last svh_grid_roll_score
+    ALIGN_LAST = 1u << 12 // al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
 };
-constexpr int kLayers = 6;
+constexpr int kLayers = 7;
 constexpr uint32_t kAllLayers = (1u << kLayers) - 1;
 // the layers each derived layer is computed from, by the layer's bit number
-constexpr uint32_t kNeeds[kLayers] = {0, FINAL, TRAV, TRAV, TRAV, FINAL};
+constexpr uint32_t kNeeds[kLayers] = {0, FINAL, TRAV, TRAV, TRAV, FINAL, FINAL};
 // what changes, and what it makes stale directly; the layers computed from a stale layer follow by closure()
-enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, SOURCES };
+enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, OBJ_PARAMS, SOURCES };
 constexpr uint32_t kDrops[SOURCES] = {
     FINAL,                    // ACC: the accumulators or the window's offsets
     TRAV | UP_TABLE,          // TRAV_PARAMS
@@ -170,6 +190,7 @@ constexpr uint32_t kDrops[SOURCES] = {
     UP_ROLL | ROLL_LAST,      // ROLL_PARAMS
     UP_CANDS | ROLL_LAST,     // CANDS: the candidate table
     AFIELD | ALIGN_LAST,      // ALIGN_PARAMS
+    OBJ,                      // OBJ_PARAMS
 };
 constexpr uint32_t closure(uint32_t m) {
     for (int pass = 0; pass < kLayers; pass++)
@@ -188,6 +209,9 @@ constexpr StaleTable stale_table() {
 constexpr StaleTable kStale = stale_table();
 static_assert((kStale.of[ACC] & kAllLayers) == kAllLayers, "a derived layer without a path to FINAL in kNeeds would survive a change of the accumulators");
 static_assert(kStale.of[TRAV_PARAMS] == (TRAV | PLAN | FRONT | REACH | UP_TABLE), "the closure of kNeeds");
+static_assert(kStale.of[OBJ_PARAMS] == OBJ && (kStale.of[ACC] & OBJ), "the objects follow the accumulators and their own parameters");
+static_assert(!((kStale.of[TRAV_PARAMS] | kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[ROLL_PARAMS] |
+                 kStale.of[CANDS] | kStale.of[ALIGN_PARAMS]) & OBJ), "no other layer's source makes the objects stale");
 
 }  // namespace
 
@@ -270,6 +294,15 @@ struct svh_grid {
     bool frame_clean = false;   // the frame record is empty and `ends` all zero: true between observations that succeeded
     int32_t stamp = 0;          // of the last observation; 0 after a clear
     int64_t dyn_stats[grid::DS_WORDS] = {0, 0, 0, 0};
+    grid::ObjParams obp{4, 4096, 0.3f, 1024, 1, 4, 2, 3, 2, 1};   // the objects: parameters, planes, table
+    HipBuf<uint8_t> obj;        // kFrontBytes per cell: LABEL | FLAGS, logical order
+    ObjBufs obj_bufs;
+    int64_t obj_stats[grid::OS_WORDS] = {0, 0, 0, 0, 0, 0, 0};   // of the result that is valid
+    TrackBufs trk;              // the tracks: state that only svh_grid_objects_step advances
+    int trk_cur = 0;            // which of the two tables and ID planes is current
+    bool trk_plane = false;     // a step has written the current ID plane; false: it counts as all -1
+    int32_t trk_n = 0, trk_next = 0, trk_oa = 0, trk_ob = 0;   // the tracks, the next id, the offsets of the ID plane
+    int64_t trk_stats[grid::TS_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     grid::Cells cells() const {
         uint8_t* b = acc.p;
@@ -290,6 +323,8 @@ struct svh_grid {
     int32_t* r_pot() const { return (int32_t*)reach.p; }
     int32_t* f_label() const { return (int32_t*)front.p; }
     uint8_t* f_flags() const { return front.p + 4 * ncells; }
+    int32_t* o_label() const { return (int32_t*)obj.p; }
+    uint8_t* o_flags() const { return obj.p + 4 * ncells; }
     grid::DynPlanes dplanes() const {
         uint8_t* b = dynp.p;
         const size_t n = ncells;
@@ -333,7 +368,14 @@ int failed(svh_grid* g, int rc, uint32_t kept = 0) {
     return rc;
 }
 // what each family of entries drops there
-constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST;
+constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST, kObjects = OBJ;
+
+// the tracks are empty and the ids start again at 0
+void forget_tracks(svh_grid* g) {
+    g->trk_plane = false;
+    g->trk_n = g->trk_next = 0;
+    for (int k = 0; k < grid::TS_WORDS; k++) g->trk_stats[k] = 0;
+}
 
 void mark_empty(svh_grid* g) {
     g->need_clear = true;
@@ -919,6 +961,188 @@ bool convert_front(const svh_grid_front_params* p, grid::FrontParams* q) {
     if (!p) return false;
     *q = grid::FrontParams{p->max_cell_cost, p->min_size, p->unexplored, p->border};
     return grid::front_ok(*q);
+}
+
+// ---- the objects and their tracks -------------------------------------------------------------------------------------------
+const char* const kObjUnsettled = "Grid: the labelling of the objects did not settle within its bounds";
+const char* const kStepUnsettled = "Grid: the table of overlap pairs of a step overflowed its probe bound";
+
+bool convert_obj(const svh_grid_obj_params* p, grid::ObjParams* q) {
+    if (!p) return false;
+    *q = grid::ObjParams{p->min_size,   p->max_size, p->min_height, p->max_tracks, p->min_overlap,
+                         p->gate,       p->max_missed, p->min_age,  p->move_cells, p->smooth_shift};
+    return grid::obj_ok(*q);
+}
+
+// The whole computation on a job whose planes exist (state, hmax, count, flags, label): OBJ_LAUNCHES launches whatever the scene
+// and two waits, as front_run.  The table, the roots and the ranks stay on the device.  Complete when it returns.
+int obj_run(hipStream_t s, grid::ObjJob& j, ObjBufs& b, int64_t stats[grid::OS_WORDS]) {
+    const size_t ctl_bytes = grid::FC_WORDS * sizeof(unsigned long long);
+    GRID_GROW_N(b.blocks, ((size_t)j.nx * (size_t)j.nz + grid::FRONT_SCAN_BLOCK - 1) / grid::FRONT_SCAN_BLOCK);
+    GRID_GROW(b.ctl, ctl_bytes);
+    GRID_GROW(b.h_ctl, ctl_bytes);
+    j.blockcnt = b.blocks, j.ctl = b.ctl;
+    GRID_TRY(copy, hipMemsetAsync(j.ctl, 0, ctl_bytes, s));
+    int64_t launches = grid::launch_obj_mask(s, j);
+    launches += grid::launch_obj_label(s, j);
+    GRID_TRY(launch, hipGetLastError());
+    GRID_TRY(copy, hipMemcpyAsync(b.h_ctl, j.ctl, ctl_bytes, hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    const unsigned long long* h = b.h_ctl;
+    if (h[grid::FC_UNSETTLED]) return svh::fail(SVH_ERR_HIP, kObjUnsettled);
+    const size_t n = (size_t)h[grid::FC_COMPONENTS], room = n ? n : 1;
+    const size_t kept_cap = std::min<size_t>(n, (size_t)h[grid::FC_CELLS] / (size_t)j.op.min_size);   // a kept component has min_size cells
+    GRID_GROW_N(b.roots, n);
+    GRID_GROW_N(b.slot, n);
+    GRID_GROW(b.acc, grid::OBJ_COMP_BYTES * room);
+    GRID_GROW_N(b.recs, (size_t)grid::OBJ_REC * kept_cap);
+    j.n_comp = (int32_t)n, j.roots = b.roots, j.slot = b.slot, j.acc = b.acc, j.recs = b.recs;
+    const grid::ObjAcc acc = grid::obj_acc(j.acc, room);
+    GRID_TRY(copy, hipMemsetAsync(j.acc, 0, grid::OBJ_COMP_BYTES * room, s));
+    GRID_TRY(copy, hipMemsetAsync(acc.bmin, 0x7F, 8 * room, s));
+    launches += grid::launch_obj_table(s, j);
+    GRID_TRY(launch, hipGetLastError());
+    GRID_TRY(copy, hipMemcpyAsync(b.h_ctl, j.ctl, ctl_bytes, hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    if (h[grid::FC_UNSETTLED]) return svh::fail(SVH_ERR_HIP, kObjUnsettled);
+    stats[grid::OS_CELLS] = (int64_t)h[grid::FC_CELLS], stats[grid::OS_COMPONENTS] = (int64_t)h[grid::FC_COMPONENTS];
+    stats[grid::OS_KEPT] = (int64_t)h[grid::FC_KEPT], stats[grid::OS_KEPT_CELLS] = (int64_t)h[grid::FC_KEPT_CELLS];
+    stats[grid::OS_LARGE] = (int64_t)h[grid::OC_LARGE], stats[grid::OS_LOW] = (int64_t)h[grid::OC_LOW];
+    stats[grid::OS_LAUNCHES] = launches;
+    return SVH_OK;
+}
+
+// the objects are valid: the finished planes, then obj_run
+int objects(svh_grid* g) {
+    if (has(g, OBJ)) return SVH_OK;
+    GRID_GROW(g->obj, g->ncells * kFrontBytes);
+    int rc = finalise(g);
+    if (rc) return rc;
+    grid::ObjJob j;
+    j.op = g->obp;
+    j.nx = g->prm.nx, j.nz = g->prm.nz, j.oa = g->prm.oa, j.ob = g->prm.ob;
+    j.state = g->bplane(B_STATE), j.hmax = g->fplane(F_HMAX), j.count = g->iplane(F_COUNT);
+    j.flags = g->o_flags(), j.label = g->o_label();
+    int64_t stats[grid::OS_WORDS];
+    if ((rc = obj_run(g->stream, j, g->obj_bufs, stats))) return rc;
+    memcpy(g->obj_stats, stats, sizeof(stats));
+    g->pending |= OBJ;
+    settle(g);
+    return SVH_OK;
+}
+
+int get_obj(svh_grid* g, int32_t plane, void* out, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = objects(g))) return rc;
+    return plane == grid::OP_LABEL ? deliver(g, g->o_label(), g->ncells * 4, out, on_device) : deliver(g, g->o_flags(), g->ncells, out, on_device);
+}
+
+// *n = the kept components, the first min(*n, cap) records to the host
+int get_objects(svh_grid* g, int32_t* recs, int64_t cap, int64_t* n) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = objects(g))) return rc;
+    const int64_t kept = g->obj_stats[grid::OS_KEPT], m = std::min(kept, cap);
+    if (m > 0 && (rc = deliver(g, g->obj_bufs.recs, (size_t)m * grid::OBJ_REC * sizeof(int32_t), recs, false))) return rc;
+    *n = kept;
+    return SVH_OK;
+}
+
+// The scratch of a step on a job that is complete but for it: the table of pairs all ones, its counts and the claims zero, the
+// picks and matches all ones, the control words zero
+int step_scratch(hipStream_t s, grid::ObjStepJob& j, TrackBufs& b, int64_t kept_cells) {
+    const size_t no = (size_t)j.n_obj, nt = (size_t)j.n_prev;
+    j.capacity = grid::obj_step_capacity(kept_cells, j.n_obj, j.n_prev);
+    const size_t zero = grid::OBJ_STEP_ZERO_OBJ * no + grid::OBJ_STEP_ZERO_TRK * nt, ones = grid::OBJ_STEP_ONES_OBJ * no + grid::OBJ_STEP_ONES_TRK * nt;
+    GRID_GROW_N(b.keys, j.capacity);
+    GRID_GROW_N(b.counts, j.capacity);
+    GRID_GROW(b.zero, zero ? zero : 8);
+    GRID_GROW(b.ones, ones ? ones : 8);
+    GRID_GROW_N(b.assign, no);
+    GRID_GROW(b.ctl, grid::SC_WORDS * sizeof(unsigned long long));
+    j.keys = b.keys, j.counts = b.counts, j.zero = b.zero, j.ones = b.ones, j.assign = b.assign, j.ctl = b.ctl;
+    GRID_TRY(copy, hipMemsetAsync(j.keys, 0xFF, (size_t)j.capacity * sizeof(unsigned long long), s));
+    GRID_TRY(copy, hipMemsetAsync(j.counts, 0, (size_t)j.capacity * sizeof(int32_t), s));
+    if (zero) GRID_TRY(copy, hipMemsetAsync(j.zero, 0, zero, s));
+    if (ones) GRID_TRY(copy, hipMemsetAsync(j.ones, 0xFF, ones, s));
+    GRID_TRY(copy, hipMemsetAsync(j.ctl, 0, grid::SC_WORDS * sizeof(unsigned long long), s));
+    return SVH_OK;
+}
+
+// One step: the objects made current, then the overlap, the claims, the gate, the update and the new ID plane in 5 or 7 launches
+// and one wait, with the control words and the first min(kept, cap) of ASSIGN coming back through pinned memory
+int objects_step(svh_grid* g, int32_t* assign, int64_t cap, int64_t* n_obj) {
+    int rc = ready(g);
+    if (rc || (rc = objects(g))) return rc;
+    hipStream_t s = g->stream;
+    TrackBufs& b = g->trk;
+    const int cur = g->trk_cur, nxt = 1 - cur;
+    for (int k = 0; k < 2; k++) {
+        GRID_GROW_N(b.table[k], (size_t)g->obp.max_tracks * grid::TRACK_REC);
+        GRID_GROW_N(b.id[k], g->ncells);
+    }
+    grid::ObjStepJob j;
+    j.op = g->obp;
+    j.nx = g->prm.nx, j.nz = g->prm.nz, j.oa = g->prm.oa, j.ob = g->prm.ob, j.poa = g->trk_oa, j.pob = g->trk_ob;
+    j.flags = g->o_flags(), j.label = g->o_label();
+    j.roots = g->obj_bufs.roots, j.slot = g->obj_bufs.slot, j.n_comp = (int32_t)g->obj_stats[grid::OS_COMPONENTS];
+    j.recs = g->obj_bufs.recs, j.n_obj = (int32_t)g->obj_stats[grid::OS_KEPT];
+    j.prev_id = b.id[cur], j.prev = b.table[cur];
+    j.n_prev = g->trk_plane ? g->trk_n : 0, j.next_id = g->trk_next;
+    j.tracks = b.table[nxt], j.id = b.id[nxt];
+    if ((rc = step_scratch(s, j, b, g->obj_stats[grid::OS_KEPT_CELLS]))) return rc;
+    const size_t ctl_bytes = grid::SC_WORDS * sizeof(unsigned long long);
+    const size_t m = (size_t)std::min<int64_t>(j.n_obj, cap);
+    GRID_GROW(b.h_out, ctl_bytes + m * sizeof(int32_t));
+    GRID_TRY(launch, (grid::launch_obj_step(s, j), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(b.h_out, j.ctl, ctl_bytes, hipMemcpyDeviceToHost, s));
+    if (m > 0) GRID_TRY(copy, hipMemcpyAsync(b.h_out + ctl_bytes, j.assign, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    const unsigned long long* h = (const unsigned long long*)b.h_out.p;
+    if (h[grid::SC_UNSETTLED]) return svh::fail(SVH_ERR_HIP, kStepUnsettled);
+    if (m > 0) memcpy(assign, b.h_out + ctl_bytes, m * sizeof(int32_t));
+    g->trk_cur = nxt, g->trk_plane = true;
+    g->trk_n = (int32_t)h[grid::SC_TRACKS], g->trk_next += (int32_t)h[grid::SC_NEW];
+    g->trk_oa = j.oa, g->trk_ob = j.ob;
+    g->trk_stats[grid::TS_STEPS]++;
+    g->trk_stats[grid::TS_TRACKS] = g->trk_n;
+    g->trk_stats[grid::TS_BY_OVERLAP] = (int64_t)h[grid::SC_BY_OVERLAP], g->trk_stats[grid::TS_BY_GATE] = (int64_t)h[grid::SC_BY_GATE];
+    g->trk_stats[grid::TS_NEW] = (int64_t)h[grid::SC_NEW], g->trk_stats[grid::TS_MISSED] = (int64_t)h[grid::SC_MISSED];
+    g->trk_stats[grid::TS_DROPPED] = (int64_t)h[grid::SC_DROPPED], g->trk_stats[grid::TS_UNTRACKED] = (int64_t)h[grid::SC_UNTRACKED];
+    *n_obj = j.n_obj;
+    return SVH_OK;
+}
+
+int get_tracks(svh_grid* g, int32_t* recs, int64_t cap, int64_t* n) {
+    const int64_t m = std::min<int64_t>(g->trk_n, cap);
+    if (m > 0) {
+        GRID_TRY(none, hipSetDevice(g->device));
+        const int rc = deliver(g, g->trk.table[g->trk_cur], (size_t)m * grid::TRACK_REC * sizeof(int32_t), recs, false);
+        if (rc) return rc;
+    }
+    *n = g->trk_n;
+    return SVH_OK;
+}
+
+int get_track_plane(svh_grid* g, int32_t* out, bool on_device) {
+    GRID_TRY(none, hipSetDevice(g->device));
+    const size_t bytes = g->ncells * sizeof(int32_t);
+    GRID_GROW_N(g->trk.id[g->trk_cur], g->ncells);
+    if (!g->trk_plane) GRID_TRY(copy, hipMemsetAsync(g->trk.id[g->trk_cur], 0xFF, bytes, g->stream));
+    return deliver(g, g->trk.id[g->trk_cur], bytes, out, on_device);
+}
+
+int render_objects(svh_grid* g, uint8_t* rgb, bool on_device) {
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        const int rc = objects(g);
+        if (rc) return rc;
+        const TrackBufs& b = g->trk;
+        grid::launch_render(g->stream, render_job(g, grid::M_CLASS, dst));
+        grid::launch_obj_overlay(g->stream, g->prm.nx, g->prm.nz, g->prm.oa, g->prm.ob, g->o_flags(), g->trk_plane ? b.id[g->trk_cur].p : nullptr,
+                                 g->trk_oa, g->trk_ob, b.table[g->trk_cur].p, g->trk_plane ? g->trk_n : 0, dst);
+        return rc;
+    });
 }
 
 // ---- the rollouts ---------------------------------------------------------------------------------------------------------
@@ -1611,6 +1835,7 @@ int32_t svh_grid_set_window(svh_grid* g, float x0, float z0) {
     g->prm.x0 = x0, g->prm.z0 = z0;
     g->prm.oa = g->prm.ob = 0;
     forget_goals(g);
+    forget_tracks(g);
     mark_empty(g);
     return SVH_OK;
 }
@@ -1913,6 +2138,87 @@ int32_t svh_grid_render_frontiers(svh_grid* g, uint8_t* rgb, int32_t on_device) 
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_frontiers: a grid and an output are needed");
     if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_frontiers") + kNoTrav);
     return failed(g, render_frontiers(g, rgb, on_device != 0), kFrontier);
+}
+
+void svh_grid_obj_params_default(svh_grid_obj_params* p) {
+    if (!p) return;
+    p->min_size = 4, p->max_size = 4096, p->min_height = 0.3f, p->max_tracks = 1024, p->min_overlap = 1;
+    p->gate = 4, p->max_missed = 2, p->min_age = 3, p->move_cells = 2, p->smooth_shift = 1;
+}
+
+int32_t svh_grid_set_objects(svh_grid* g, const svh_grid_obj_params* p) {
+    grid::ObjParams q;
+    if (!g || !convert_obj(p, &q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_objects: a grid and parameters in range are needed (include/svh_grid_obj.h)");
+    g->obp = q;
+    touch(g, OBJ_PARAMS);
+    forget_tracks(g);
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_objects_params(svh_grid* g, svh_grid_obj_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_objects_params: null argument");
+    const grid::ObjParams& q = g->obp;
+    p->min_size = q.min_size, p->max_size = q.max_size, p->min_height = q.min_height, p->max_tracks = q.max_tracks, p->min_overlap = q.min_overlap;
+    p->gate = q.gate, p->max_missed = q.max_missed, p->min_age = q.min_age, p->move_cells = q.move_cells, p->smooth_shift = q.smooth_shift;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_obj_plane(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::OP_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_obj_plane: a grid, a plane 0..1 and an output are needed");
+    if (on_device && plane == grid::OP_LABEL && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_obj_plane: a device array of LABEL must be 4-byte aligned");
+    return failed(g, get_obj(g, plane, out, on_device != 0), kObjects);
+}
+
+int32_t svh_grid_get_objects(svh_grid* g, int32_t* recs, int64_t cap, int64_t* n) {
+    if (!g || !n || cap < 0 || (cap > 0 && !recs)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_objects: a grid, a count and room for cap >= 0 records are needed");
+    return failed(g, get_objects(g, recs, cap, n), kObjects);
+}
+
+int32_t svh_grid_get_object_stats(svh_grid* g, int64_t out[7]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_object_stats: null argument");
+    int rc = ready(g);
+    if (!rc) rc = objects(g);
+    if (rc) return failed(g, rc, kObjects);
+    memcpy(out, g->obj_stats, sizeof(g->obj_stats));
+    return SVH_OK;
+}
+
+int32_t svh_grid_objects_step(svh_grid* g, int32_t* assign, int64_t cap, int64_t* n_obj) {
+    if (!g || !n_obj || cap < 0 || (cap > 0 && !assign)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_objects_step: a grid, a count and room for cap >= 0 ids are needed");
+    if (g->trk_stats[grid::TS_STEPS] >= 0x7FFFFFFF) return svh::fail(SVH_ERR_UNSUPPORTED, "svh_grid_objects_step: 2^31 - 1 steps since the tracks were last emptied");
+    const int rc = failed(g, objects_step(g, assign, cap, n_obj), kObjects);
+    if (rc == SVH_ERR_HIP) forget_tracks(g);   // a half-done step cannot be taken back
+    return rc;
+}
+
+int32_t svh_grid_objects_reset(svh_grid* g) {
+    if (!g) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_objects_reset: null argument");
+    forget_tracks(g);
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_tracks(svh_grid* g, int32_t* recs, int64_t cap, int64_t* n) {
+    if (!g || !n || cap < 0 || (cap > 0 && !recs)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_tracks: a grid, a count and room for cap >= 0 records are needed");
+    return failed(g, get_tracks(g, recs, cap, n));
+}
+
+int32_t svh_grid_get_track_plane(svh_grid* g, int32_t* out, int32_t on_device, int32_t off[2]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_track_plane: a grid and an output are needed");
+    if (on_device && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_track_plane: a device array must be 4-byte aligned");
+    const int rc = failed(g, get_track_plane(g, out, on_device != 0));
+    if (!rc && off) off[0] = g->trk_plane ? g->trk_oa : g->prm.oa, off[1] = g->trk_plane ? g->trk_ob : g->prm.ob;
+    return rc;
+}
+
+int32_t svh_grid_get_track_stats(svh_grid* g, int64_t out[8]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_track_stats: null argument");
+    memcpy(out, g->trk_stats, sizeof(g->trk_stats));
+    return SVH_OK;
+}
+
+int32_t svh_grid_render_objects(svh_grid* g, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_objects: a grid and an output are needed");
+    return failed(g, render_objects(g, rgb, on_device != 0), kObjects);
 }
 
 void svh_grid_roll_params_default(svh_grid_roll_params* p) {
@@ -2772,6 +3078,99 @@ int32_t svh_test_grid_front_label_device(int32_t nx, int32_t nz, const uint8_t* 
     }
     if (rc) return rc;
     if (launches) *launches = launched;
+    return SVH_OK;
+}
+
+// grid_obj_core.h's objects on the host.  Needs no device
+int32_t svh_test_grid_obj(const svh_grid_obj_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* state, const float* hmax,
+                          const int32_t* count, uint8_t* flags, int32_t* label, int32_t* recs, int64_t cap, int64_t* n, int64_t* stats) {
+    grid::ObjParams q;
+    if (!convert_obj(p, &q) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) || !state || !hmax ||
+        !count || cap < 0 || (cap > 0 && !recs))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_obj: bad arguments");
+    const size_t cells = (size_t)nx * (size_t)nz;
+    std::vector<uint8_t> f(cells);
+    std::vector<int32_t> l(cells), r;
+    int64_t st[grid::OS_WORDS];
+    grid::obj_window(q, nx, nz, oa, ob, state, hmax, count, f.data(), l.data(), &r, st);
+    if (flags) memcpy(flags, f.data(), cells);
+    if (label) memcpy(label, l.data(), cells * sizeof(int32_t));
+    if (cap > 0) memcpy(recs, r.data(), std::min(r.size(), (size_t)cap * grid::OBJ_REC) * sizeof(int32_t));
+    if (n) *n = st[grid::OS_KEPT];
+    if (stats) memcpy(stats, st, sizeof(st));
+    return SVH_OK;
+}
+
+// the kernels of the objects on a caller's STATE, HMAX and COUNT planes (host, nx x nz)
+int32_t svh_test_grid_obj_device(const svh_grid_obj_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* state,
+                                 const float* hmax, const int32_t* count, uint8_t* flags, int32_t* label, int32_t* recs, int64_t cap, int64_t* n,
+                                 int64_t* stats) {
+    grid::ObjJob j;
+    if (!convert_obj(p, &j.op) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) || !state || !hmax ||
+        !count || cap < 0 || (cap > 0 && !recs))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_obj_device: bad arguments");
+    svh::ensure_init();
+    j.nx = nx, j.nz = nz, j.oa = oa, j.ob = ob;
+    const size_t cells = (size_t)nx * (size_t)nz;
+    HipBuf<uint8_t> in, planes;
+    ObjBufs bufs;
+    int64_t st[grid::OS_WORDS] = {0, 0, 0, 0, 0, 0, 0};
+    hipStream_t s = nullptr;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(in, 9 * cells);
+        GRID_GROW(planes, cells * kFrontBytes);
+        GRID_TRY(copy, hipMemcpyAsync(in, hmax, 4 * cells, hipMemcpyHostToDevice, s));
+        GRID_TRY(copy, hipMemcpyAsync(in + 4 * cells, count, 4 * cells, hipMemcpyHostToDevice, s));
+        GRID_TRY(copy, hipMemcpyAsync(in + 8 * cells, state, cells, hipMemcpyHostToDevice, s));
+        j.hmax = (const float*)in.p, j.count = (const int32_t*)(in.p + 4 * cells), j.state = in.p + 8 * cells;
+        j.label = (int32_t*)planes.p, j.flags = planes.p + 4 * cells;
+        const int r = obj_run(s, j, bufs, st);
+        if (r) return r;
+        const size_t m = (size_t)std::min<int64_t>(st[grid::OS_KEPT], cap);
+        if (flags) GRID_TRY(copy, hipMemcpyAsync(flags, j.flags, cells, hipMemcpyDeviceToHost, s));
+        if (label) GRID_TRY(copy, hipMemcpyAsync(label, j.label, cells * 4, hipMemcpyDeviceToHost, s));
+        if (m > 0) GRID_TRY(copy, hipMemcpyAsync(recs, j.recs, m * grid::OBJ_REC * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    if (n) *n = st[grid::OS_KEPT];
+    if (stats) memcpy(stats, st, sizeof(st));
+    return SVH_OK;
+}
+
+// grid_obj_core.h's step on the host: the inputs of obj_step; tracks has room for p->max_tracks records.  *n_tracks = the records of
+// the new table, stats[TS_WORDS] (TS_STEPS is not touched), *next_out = the next id afterwards.  Needs no device
+int32_t svh_test_grid_obj_step(const svh_grid_obj_params* p, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const int32_t* recs, int32_t n_obj,
+                               const int32_t* label, int32_t poa, int32_t pob, const int32_t* prev_id, const int32_t* prev, int32_t n_prev,
+                               int32_t next_id, int32_t* tracks, int32_t* n_tracks, int32_t* assign, int32_t* id, int64_t* stats,
+                               int32_t* next_out) {
+    grid::ObjParams q;
+    if (!convert_obj(p, &q) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) ||
+        !grid::offsets_ok(poa, pob) || n_obj < 0 || (n_obj > 0 && (!recs || !assign)) || !label || n_prev < 0 || n_prev > q.max_tracks ||
+        (n_prev > 0 && (!prev || !prev_id)) || next_id < 0 || !tracks || !n_tracks || !id)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_obj_step: bad arguments");
+    std::vector<int32_t> t;
+    int64_t st[grid::TS_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int32_t next = grid::obj_step(q, nx, nz, oa, ob, recs, n_obj, label, poa, pob, prev_id, prev, n_prev, next_id, &t, assign, id, st);
+    memcpy(tracks, t.data(), t.size() * sizeof(int32_t));
+    *n_tracks = (int32_t)(t.size() / grid::TRACK_REC);
+    if (stats)
+        for (int k = grid::TS_TRACKS; k < grid::TS_WORDS; k++) stats[k] = st[k];
+    if (next_out) *next_out = next;
+    return SVH_OK;
+}
+
+// grid_obj_core.h's colours on the host: rgb[3] per cell from FLAGS, the track id of the cell (-1: none) and whether that track moves;
+// cells that keep their colour are not written
+int32_t svh_test_grid_obj_colour(int64_t ncells, const uint8_t* flags, const int32_t* id, const uint8_t* moving, uint8_t* rgb) {
+    if (ncells < 0 || (ncells > 0 && (!flags || !id || !moving || !rgb))) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_obj_colour: bad arguments");
+    for (int64_t i = 0; i < ncells; i++) (void)grid::colour_obj(flags[i], id[i], moving[i] != 0, rgb + 3 * i);
     return SVH_OK;
 }
 

@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_common.h"
+#include "grid_comp_dev.h"
 #include "grid_front_core.h"
 #include "grid_internal.h"
 
@@ -196,6 +197,10 @@ struct IsKept {
     int32_t min_size;
     __device__ __forceinline__ bool operator()(uint32_t i) const { return size[i] >= min_size; }
 };
+struct IsMarked {
+    const int32_t* mark;
+    __device__ __forceinline__ bool operator()(uint32_t i) const { return mark[i] != 0; }
+};
 
 template <class Pred>
 __global__ __launch_bounds__(kScan) void k_front_count(uint32_t n, Pred pred, int32_t* __restrict__ blockcnt) {
@@ -251,47 +256,13 @@ __global__ __launch_bounds__(kScan) void k_front_roots(uint32_t cells, const int
     if (at >= 0 && at < n_comp) roots[at] = (int32_t)(blockIdx.x * (uint32_t)kScan + threadIdx.x);
 }
 
-// the rank of a label among the n ascending roots; every label of a finished plane is one of them
-__device__ __forceinline__ int32_t rank_of(const int32_t* __restrict__ roots, int32_t n, int32_t label) {
-    int32_t lo = 0, hi = n - 1;
-    while (lo < hi) {                                   // at most 26 halvings
-        const int32_t mid = (lo + hi) >> 1;
-        if (roots[mid] < label) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// One value per wave from one per lane.  Every lane of the wave calls them.
-__device__ __forceinline__ int32_t wave_sum(int32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ int32_t wave_min(int32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const int32_t o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ int32_t wave_max(int32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const int32_t o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t hi = (uint32_t)__shfl_xor((int32_t)(uint32_t)(v >> 32), off, 64), lo = (uint32_t)__shfl_xor((int32_t)(uint32_t)v, off, 64);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
+// slot[i] = the position of element i among the marked ones, -1 when it is not marked
+__global__ __launch_bounds__(kScan) void k_front_slots(uint32_t n, const int32_t* __restrict__ mark, const int32_t* __restrict__ blockoff,
+                                                      int32_t* __restrict__ slot) {
+    __shared__ int s_cnt[kScanWaves];
+    const int32_t at = ordered_slot(n, IsMarked{mark}, blockoff, s_cnt);
+    const uint32_t i = blockIdx.x * (uint32_t)kScan + threadIdx.x;
+    if (i < n) slot[i] = at;
 }
 
 // the component (rank among the roots) of cell i and its window cell; -1 off the frontier
@@ -439,12 +410,26 @@ int32_t launch_front_count(hipStream_t s, const FrontJob& j) {
     return 2;
 }
 
+int32_t launch_front_roots(hipStream_t s, const FrontJob& j) {
+    const unsigned cells = (unsigned)j.nx * (unsigned)j.nz;
+    hipLaunchKernelGGL(k_front_roots, dim3((unsigned)front_blocks(j)), dim3(kScan), 0, s, cells, (const int32_t*)j.label, (const int32_t*)j.blockcnt,
+                       j.n_comp, j.roots);
+    return 1;
+}
+
+int32_t launch_front_rank(hipStream_t s, uint32_t n, const int32_t* mark, int32_t* blockcnt, unsigned long long* total, int32_t* slot) {
+    const unsigned sb = blocks_of(n, FRONT_SCAN_BLOCK);
+    hipLaunchKernelGGL(k_front_count<IsMarked>, dim3(sb), dim3(kScan), 0, s, n, IsMarked{mark}, blockcnt);
+    hipLaunchKernelGGL(k_front_scan, dim3(1), dim3(kScan), 0, s, blockcnt, sb, total);
+    hipLaunchKernelGGL(k_front_slots, dim3(sb), dim3(kScan), 0, s, n, mark, (const int32_t*)blockcnt, slot);
+    return 3;
+}
+
 int32_t launch_front_table(hipStream_t s, const FrontJob& j) {
     const unsigned cells = (unsigned)j.nx * (unsigned)j.nz, n = (unsigned)j.n_comp;
     const FrontAcc acc = front_acc(j.acc, n ? n : 1);
     const unsigned cb = blocks_of(n, FRONT_BLOCK), sb = blocks_of(n, FRONT_SCAN_BLOCK);
-    hipLaunchKernelGGL(k_front_roots, dim3((unsigned)front_blocks(j)), dim3(kScan), 0, s, cells, (const int32_t*)j.label, (const int32_t*)j.blockcnt,
-                       j.n_comp, j.roots);
+    launch_front_roots(s, j);
     hipLaunchKernelGGL(k_grid_front_accum, dim3(per_cell(j)), dim3(FRONT_BLOCK), 0, s, j.nx, cells, (const int32_t*)j.label, (const int32_t*)j.roots,
                        j.n_comp, acc);
     hipLaunchKernelGGL(k_grid_front_centroid, dim3(cb), dim3(FRONT_BLOCK), 0, s, j.n_comp, j.frp.min_size, acc, j.ctl);

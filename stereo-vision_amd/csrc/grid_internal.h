@@ -1,5 +1,5 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
-// csrc/grid_front_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip /
+// csrc/grid_front_kernels.hip / csrc/grid_obj_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip /
 // csrc/grid_dyn_kernels.hip: the launches of the
 // ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
@@ -13,6 +13,7 @@
 #include "grid_dyn_core.h"
 #include "grid_explore_core.h"
 #include "grid_front_core.h"
+#include "grid_obj_core.h"
 #include "grid_plan_core.h"
 #include "grid_roll_core.h"
 
@@ -228,6 +229,109 @@ int32_t launch_front_count(hipStream_t s, const FrontJob& j);
 int32_t launch_front_table(hipStream_t s, const FrontJob& j);
 // the frontier cells drawn over an image of svh_grid_render_cost's layout
 void launch_front_overlay(hipStream_t s, int32_t nx, int32_t nz, const uint8_t* flags, uint8_t* rgb);
+// The labelling and the ordered compaction serve any plane of the form "own index or -1" (the objects use them too): of a job
+// they read nx, nz, label, blockcnt, ctl, n_comp and roots alone.  The roots scattered in ascending order, after
+// launch_front_count; one launch
+int32_t launch_front_roots(hipStream_t s, const FrontJob& j);
+// slot[i] = the position of element i among those of n with mark[i] != 0, -1 for the others; *total = how many are marked.
+// blockcnt has room for ceil(n / FRONT_SCAN_BLOCK) counts.  Three launches
+int32_t launch_front_rank(hipStream_t s, uint32_t n, const int32_t* mark, int32_t* blockcnt, unsigned long long* total, int32_t* slot);
+
+// The objects and their tracks (csrc/grid_obj_kernels.hip): the finished STATE, HMAX and COUNT planes -> FLAGS, LABEL and the table
+// of kept components; then, per step, the overlap of the components with the ID plane of the step before -> the track table.
+constexpr uint32_t OBJ_BLOCK = 256;
+constexpr unsigned OBJ_MASK_BLOCKS = 2048;       // k_grid_obj_mask: the launch is capped here; beyond 2048 * 256 cells the lanes stride
+constexpr uint32_t OBJ_UPDATE_BLOCK = 1024;      // k_grid_obj_update: one workgroup
+// the launches of one computation of the objects, a constant of the build: mask; tile, merge, flatten; roots counted, scanned |
+// scattered; accumulate, verdicts; kept counted, scanned, ranked; records; flags
+constexpr int32_t OBJ_LAUNCHES = 14;
+// the control words beside those of FrontCtl, which the shared kernels write
+enum ObjCtl { OC_LARGE = 5, OC_LOW = 6 };
+// bytes per component of the accumulators: sum (2 x 64 bits), points (64 bits), size, box max (2), box min (2), biased HMAX bits, mark
+constexpr size_t OBJ_COMP_BYTES = 52;
+struct ObjAcc {
+    unsigned long long* sum;    // 2 per component: ia, ib
+    unsigned long long* pts;    // the sum of COUNT
+    int32_t* size;
+    int32_t* bmax;              // 2 per component
+    int32_t* bmin;
+    uint32_t* hbits;            // the greatest bits of HMAX ^ 0x80000000: int32 order as unsigned, all zero is below every value
+    int32_t* mark;              // 1: kept
+};
+inline ObjAcc obj_acc(uint8_t* p, size_t n) {
+    return ObjAcc{(unsigned long long*)p, (unsigned long long*)(p + 16 * n), (int32_t*)(p + 24 * n), (int32_t*)(p + 28 * n),
+                  (int32_t*)(p + 36 * n), (uint32_t*)(p + 44 * n), (int32_t*)(p + 48 * n)};
+}
+struct ObjJob {
+    ObjParams op;
+    int32_t nx, nz, oa, ob;
+    const uint8_t* state;       // the finished planes
+    const float* hmax;
+    const int32_t* count;
+    uint8_t* flags;             // nx * nz each, logical order
+    int32_t* label;
+    int32_t* blockcnt;          // ceil(nx * nz / FRONT_SCAN_BLOCK) counts, as FrontJob's
+    unsigned long long* ctl;    // FC_WORDS, all zero before
+    // what exists once the number of components is known
+    int32_t n_comp = 0;
+    int32_t* roots = nullptr;   // n_comp labels, ascending
+    uint8_t* acc = nullptr;     // OBJ_COMP_BYTES per component: all zero but box min, 0x7F bytes
+    int32_t* slot = nullptr;    // n_comp: the rank of a kept component, -1 for the others
+    int32_t* recs = nullptr;    // OBJ_REC per kept component
+};
+// Each returns the kernels it launched.  mask: FLAGS bit 0, LABEL = own index or -1, the object cells counted
+int32_t launch_obj_mask(hipStream_t s, const ObjJob& j);
+// the frontier layer's labelling and root count on LABEL: ctl[FC_COMPONENTS]
+int32_t launch_obj_label(hipStream_t s, const ObjJob& j);
+// with n_comp, roots, acc, slot and recs: everything else
+int32_t launch_obj_table(hipStream_t s, const ObjJob& j);
+
+// the control words of a step, 64 bits each
+enum ObjStepCtl { SC_TRACKS = 0, SC_BY_OVERLAP, SC_BY_GATE, SC_NEW, SC_MISSED, SC_DROPPED, SC_UNTRACKED, SC_UNSETTLED, SC_WORDS };
+// bytes of scratch per object and per track: claim (64 bits), counting pairs | gate pick (64 bits), match; a track has its `how` too
+constexpr size_t OBJ_STEP_ZERO_OBJ = 12, OBJ_STEP_ONES_OBJ = 12, OBJ_STEP_ZERO_TRK = 16, OBJ_STEP_ONES_TRK = 12;
+struct ObjStepJob {
+    ObjParams op;
+    int32_t nx, nz, oa, ob, poa, pob;
+    const uint8_t* flags;       // of the objects that are current
+    const int32_t* label;
+    const int32_t* roots;
+    const int32_t* slot;
+    int32_t n_comp;
+    const int32_t* recs;
+    int32_t n_obj;
+    const int32_t* prev_id;     // the ID plane of the step before
+    const int32_t* prev;        // its n_prev track records
+    int32_t n_prev, next_id;
+    unsigned long long* keys;   // the table of pairs: `capacity` slots (a power of two), all ones before
+    int32_t* counts;            // ... all zero before
+    uint32_t capacity;
+    uint8_t* zero;              // OBJ_STEP_ZERO_OBJ * n_obj + OBJ_STEP_ZERO_TRK * n_prev bytes, all zero before (obj_step_scratch)
+    uint8_t* ones;              // OBJ_STEP_ONES_OBJ * n_obj + OBJ_STEP_ONES_TRK * n_prev bytes, all ones before
+    int32_t* tracks;            // the new table: room for max_tracks records
+    int32_t* assign;            // n_obj
+    int32_t* id;                // the new ID plane, nx * nz
+    unsigned long long* ctl;    // SC_WORDS, all zero before
+};
+struct ObjStepScratch {
+    unsigned long long *claim_obj, *claim_trk, *pick_obj, *pick_trk;
+    int32_t *cnt_obj, *cnt_trk, *how, *obj_trk, *trk_obj;
+};
+inline ObjStepScratch obj_step_scratch(const ObjStepJob& j) {
+    const size_t no = (size_t)j.n_obj, nt = (size_t)j.n_prev;
+    uint8_t *z = j.zero, *o = j.ones;
+    return ObjStepScratch{(unsigned long long*)z, (unsigned long long*)(z + 8 * no), (unsigned long long*)o, (unsigned long long*)(o + 8 * no),
+                          (int32_t*)(z + 8 * (no + nt)), (int32_t*)(z + 8 * (no + nt) + 4 * no), (int32_t*)(z + 8 * (no + nt) + 4 * (no + nt)),
+                          (int32_t*)(o + 8 * (no + nt)), (int32_t*)(o + 8 * (no + nt) + 4 * no)};
+}
+// the slots of the table of pairs for a step: a power of two, at least twice the pairs that can occur
+uint32_t obj_step_capacity(int64_t kept_cells, int64_t n_obj, int64_t n_prev);
+// the whole step; returns the kernels it launched: 5, and 2 more when the gate is on
+int32_t launch_obj_step(hipStream_t s, const ObjStepJob& j);
+// the objects and tracks drawn over an image of svh_grid_render's layout: the cells by colour_obj, then the two marks per
+// track with a label
+void launch_obj_overlay(hipStream_t s, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* flags, const int32_t* id, int32_t id_oa,
+                        int32_t id_ob, const int32_t* tracks, int32_t n_tracks, uint8_t* rgb);
 
 // The rollouts (csrc/grid_roll_kernels.hip): the finished COST and POT planes, the footprint table and the candidates of one set ->
 // F of poses, the records, the scores and the best.

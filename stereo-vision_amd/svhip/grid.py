@@ -1,7 +1,7 @@
 """ctypes binding of the ground grid in libsvhip.so (C-ABI: include/svh_grid.h): a 2.5-D bird's-eye grid over the road
 plane -- per cell how many points, how high, how bright, drivable or not -- binned on the device from the map view's store
 or from a list of points.  The arithmetic is stereo-vision_amd/csrc/grid_core.h, grid_plan_core.h, grid_front_core.h and
-grid_roll_core.h; that of the exploration layer grid_explore_core.h, that of the alignment layer grid_align_core.h, that of the
+grid_roll_core.h; that of the objects and their tracks grid_obj_core.h, that of the exploration layer grid_explore_core.h, that of the alignment layer grid_align_core.h, that of the
 dynamics grid_dyn_core.h."""
 import ctypes as C
 
@@ -54,6 +54,18 @@ DYN_AGE, DYN_CONTRA, DYN_THROUGH = range(3)
 DYN_CLEARED, DYN_AGED, DYN_CONFIRMED = 1, 2, 4
 DYN_STATS = ("observations", "cleared", "aged", "confirmed")
 DYN_EVENT_COLOUR = (255, 0, 255)
+OBJ_FLAGS, OBJ_LABEL = range(2)
+OBJ_DTYPE = [np.uint8, np.int32]
+OBJ_CELL, OBJ_KEPT, OBJ_LARGE = 1, 2, 4
+OBJ_RECORD = 10
+OBJ_FIELDS = ("label", "size", "ga_min", "gb_min", "ga_max", "gb_max", "c16_a", "c16_b", "hmax_bits", "points")
+OBJ_STATS = ("cells", "components", "kept", "kept_cells", "large", "low", "launches")
+TRACK_RECORD = 14
+TRACK_FIELDS = ("id", "flags", "age", "missed", "label", "size", "c16_a", "c16_b", "v16_a", "v16_b", "birth_a", "birth_b", "overlap", "hmax_bits")
+TRACK_NEW, TRACK_BY_OVERLAP, TRACK_BY_GATE, TRACK_MISSED, TRACK_MOVING, TRACK_MERGED, TRACK_SPLIT = 1, 2, 4, 8, 16, 32, 64
+TRACK_STATS = ("steps", "tracks", "by_overlap", "by_gate", "new", "missed", "dropped", "untracked")
+ASSIGN_UNTRACKED = -2
+OBJ_LARGE_COLOUR, OBJ_UNTRACKED_COLOUR, OBJ_CENTRE_COLOUR, OBJ_AHEAD_COLOUR = (128, 128, 128), (128, 0, 0), (255, 255, 255), (255, 255, 0)
 
 
 class Params(C.Structure):
@@ -112,6 +124,21 @@ class FrontParams(C.Structure):
 
     def asdict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class ObjParams(C.Structure):
+    """svh_grid_obj_params"""
+    _fields_ = [("min_size", C.c_int32), ("max_size", C.c_int32), ("min_height", C.c_float), ("max_tracks", C.c_int32), ("min_overlap", C.c_int32),
+                ("gate", C.c_int32), ("max_missed", C.c_int32), ("min_age", C.c_int32), ("move_cells", C.c_int32), ("smooth_shift", C.c_int32)]
+
+    def copy(self, **kw):
+        q = ObjParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class RollParams(C.Structure):
@@ -253,6 +280,25 @@ def _bind():
         L.svh_test_grid_front_device.argtypes = front
         L.svh_test_grid_front_label_device.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.svh_test_grid_front_tile.argtypes = []
+        L.svh_grid_obj_params_default.argtypes = [C.POINTER(ObjParams)]
+        L.svh_grid_obj_params_default.restype = None
+        L.svh_grid_set_objects.argtypes = [C.c_void_p, C.POINTER(ObjParams)]
+        L.svh_grid_get_objects_params.argtypes = [C.c_void_p, C.POINTER(ObjParams)]
+        L.svh_grid_get_obj_plane.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_get_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_grid_get_object_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_objects_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_grid_objects_reset.argtypes = [C.c_void_p]
+        L.svh_grid_get_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_grid_get_track_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.svh_grid_get_track_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_render_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        obj = [C.POINTER(ObjParams)] + [C.c_int32] * 4 + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p]
+        L.svh_test_grid_obj.argtypes = obj
+        L.svh_test_grid_obj_device.argtypes = obj
+        L.svh_test_grid_obj_step.argtypes = ([C.POINTER(ObjParams)] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6)
+        L.svh_test_grid_obj_colour.argtypes = [C.c_int64] + [C.c_void_p] * 4
         L.svh_grid_roll_params_default.argtypes = [C.POINTER(RollParams)]
         L.svh_grid_roll_params_default.restype = None
         L.svh_grid_set_roll.argtypes = [C.c_void_p, C.POINTER(RollParams)]
@@ -513,6 +559,61 @@ def device_front_label(mask):
 def front_tile():
     """the tile side the labelling kernel of the frontiers was built with"""
     return int(_bind().svh_test_grid_front_tile())
+
+
+def default_obj(**kw):
+    p = ObjParams()
+    _bind().svh_grid_obj_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def _obj(entry, obj, state, hmax, count, oa, ob):
+    s = np.ascontiguousarray(state, np.uint8)
+    nz, nx = s.shape
+    h, c = np.ascontiguousarray(hmax, np.float32).reshape(nz, nx), np.ascontiguousarray(count, np.int32).reshape(nz, nx)
+    flags, label = np.zeros((nz, nx), np.uint8), np.zeros((nz, nx), np.int32)
+    cap = ((nx + 1) // 2) * ((nz + 1) // 2)             # components do not touch: at most one per 2 x 2 cells
+    recs, n, stats = np.zeros((cap, OBJ_RECORD), np.int32), C.c_int64(-1), np.zeros(7, np.int64)
+    _check(entry(C.byref(obj), nx, nz, oa, ob, s.ctypes.data, h.ctypes.data, c.ctypes.data, flags.ctypes.data, label.ctypes.data,
+                 recs.ctypes.data, cap, C.addressof(n), stats.ctypes.data))
+    return flags, label, recs[:n.value].copy(), tuple(int(v) for v in stats)
+
+
+def core_obj(obj, state, hmax, count, oa=0, ob=0):
+    """the objects of csrc/grid_obj_core.h on the host (svh_test_grid_obj) for STATE, HMAX and COUNT planes [nz, nx] under the offsets
+    (oa, ob): (flags uint8 [nz, nx], label int32 [nz, nx], records int32 [kept, 10], stats (7)); needs no device"""
+    return _obj(_bind().svh_test_grid_obj, obj, state, hmax, count, oa, ob)
+
+
+def device_obj(obj, state, hmax, count, oa=0, ob=0):
+    """TEST ENTRY: the same through the device kernels on a caller's planes"""
+    return _obj(_bind().svh_test_grid_obj_device, obj, state, hmax, count, oa, ob)
+
+
+def core_obj_step(obj, recs, label, off, prev_id, prev_off, prev, next_id):
+    """one step of the tracks of csrc/grid_obj_core.h on the host (svh_test_grid_obj_step): the object records [n, 10] and LABEL plane
+    [nz, nx] of a window under off = (oa, ob), the ID plane of the step before (or None) under prev_off, its track records [m, 14] and
+    the next id -> (tracks int32 [k, 14], assign int32 [n], id int32 [nz, nx], stats (8; steps is 0), next id); needs no device"""
+    lab = np.ascontiguousarray(label, np.int32)
+    nz, nx = lab.shape
+    r = np.ascontiguousarray(recs, np.int32).reshape(-1, OBJ_RECORD)
+    t = np.ascontiguousarray(prev, np.int32).reshape(-1, TRACK_RECORD)
+    pid = None if prev_id is None else np.ascontiguousarray(prev_id, np.int32).reshape(nz, nx)
+    tracks, n_tracks = np.zeros((obj.max_tracks, TRACK_RECORD), np.int32), C.c_int32(-1)
+    assign, ids, stats, nxt = np.zeros(max(len(r), 1), np.int32), np.zeros((nz, nx), np.int32), np.zeros(8, np.int64), C.c_int32(-1)
+    _check(_bind().svh_test_grid_obj_step(C.byref(obj), nx, nz, off[0], off[1], r.ctypes.data if len(r) else None, len(r), lab.ctypes.data,
+                                          prev_off[0], prev_off[1], None if pid is None else pid.ctypes.data, t.ctypes.data if len(t) else None,
+                                          len(t), next_id, tracks.ctypes.data, C.addressof(n_tracks), assign.ctypes.data, ids.ctypes.data,
+                                          stats.ctypes.data, C.addressof(nxt)))
+    return tracks[:n_tracks.value].copy(), assign[:len(r)].copy(), ids, tuple(int(v) for v in stats), nxt.value
+
+
+def core_obj_colour(flags, ids, moving):
+    """colour_obj of csrc/grid_obj_core.h on the host, per cell: (rgb uint8 [n, 3], zero where the cell keeps its colour)"""
+    f, i, m = np.ascontiguousarray(flags, np.uint8).ravel(), np.ascontiguousarray(ids, np.int32).ravel(), np.ascontiguousarray(moving, np.uint8).ravel()
+    rgb = np.zeros((len(f), 3), np.uint8)
+    _check(_bind().svh_test_grid_obj_colour(len(f), f.ctypes.data, i.ctypes.data, m.ctypes.data, rgb.ctypes.data))
+    return rgb
 
 
 def default_roll(**kw):
@@ -1047,6 +1148,96 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_frontiers(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_objects(self, params=None, **kw):
+        """the object parameters in force (or `params`) with the fields of kw replaced; the tracks are emptied"""
+        p = (params if params is not None else self.objects_params()).copy(**kw)
+        _check(self._L.svh_grid_set_objects(self._h, C.byref(p)))
+
+    def objects_params(self):
+        p = ObjParams()
+        _check(self._L.svh_grid_get_objects_params(self._h, C.byref(p)))
+        return p
+
+    def obj_plane(self, which, device_ptr=None):
+        """OBJ_FLAGS uint8 or OBJ_LABEL int32, [nz, nx]; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_obj_plane(self._h, which, device_ptr, 1))
+            return None
+        if not 0 <= which < len(OBJ_DTYPE):
+            raise SvhError(ERR_BAD_ARG, "no such plane")
+        out = np.zeros((self.nz, self.nx), OBJ_DTYPE[which])
+        _check(self._L.svh_grid_get_obj_plane(self._h, which, out.ctypes.data, 0))
+        return out
+
+    def objects(self, cap=None):
+        """the records of the kept components, int32 [n, 10] in the order of OBJ_FIELDS, ascending by label; with cap only the first,
+        and the count of all is in `object_count`"""
+        n = C.c_int64(0)
+        if cap is None:
+            _check(self._L.svh_grid_get_objects(self._h, None, 0, C.addressof(n)))
+            cap = n.value
+        recs = np.zeros((max(int(cap), 1), OBJ_RECORD), np.int32)
+        _check(self._L.svh_grid_get_objects(self._h, recs.ctypes.data if cap else None, int(cap), C.addressof(n)))
+        self.object_count = n.value
+        return recs[:min(n.value, int(cap))].copy()
+
+    def object_stats(self):
+        """(object cells, components, kept, cells in kept components, too large, too low, kernel launches of the computation)"""
+        out = np.zeros(7, np.int64)
+        _check(self._L.svh_grid_get_object_stats(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def objects_step(self, cap=None):
+        """one step of the tracks: assign int32 [n], per kept object by rank the id of its track or ASSIGN_UNTRACKED; with cap only the
+        first, and the count of all is in `object_count`"""
+        n = C.c_int64(0)
+        if cap is None:
+            cap = self.object_stats()[2]
+        assign = np.zeros(max(int(cap), 1), np.int32)
+        _check(self._L.svh_grid_objects_step(self._h, assign.ctypes.data if cap else None, int(cap), C.addressof(n)))
+        self.object_count = n.value
+        return assign[:min(n.value, int(cap))].copy()
+
+    def objects_reset(self):
+        _check(self._L.svh_grid_objects_reset(self._h))
+
+    def tracks(self, cap=None):
+        """the track records, int32 [n, 14] in the order of TRACK_FIELDS, ascending by id"""
+        n = C.c_int64(0)
+        if cap is None:
+            _check(self._L.svh_grid_get_tracks(self._h, None, 0, C.addressof(n)))
+            cap = n.value
+        recs = np.zeros((max(int(cap), 1), TRACK_RECORD), np.int32)
+        _check(self._L.svh_grid_get_tracks(self._h, recs.ctypes.data if cap else None, int(cap), C.addressof(n)))
+        self.track_count = n.value
+        return recs[:min(n.value, int(cap))].copy()
+
+    def track_plane(self, device_ptr=None):
+        """(the ID plane of the last step int32 [nz, nx], the offsets (oa, ob) it was written under); with device_ptr the plane is
+        written there and (None, offsets) returned"""
+        off = np.zeros(2, np.int32)
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_track_plane(self._h, device_ptr, 1, off.ctypes.data))
+            return None, (int(off[0]), int(off[1]))
+        out = np.zeros((self.nz, self.nx), np.int32)
+        _check(self._L.svh_grid_get_track_plane(self._h, out.ctypes.data, 0, off.ctypes.data))
+        return out, (int(off[0]), int(off[1]))
+
+    def track_stats(self):
+        """TRACK_STATS: steps, tracks; of the last step: by overlap, by gate, new, missed, dropped, untracked"""
+        out = np.zeros(8, np.int64)
+        _check(self._L.svh_grid_get_track_stats(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def render_objects(self, device_ptr=None):
+        """render(RENDER_CLASS) with the objects over it, coloured by track"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_objects(self._h, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_objects(self._h, img.ctypes.data, 0))
         return img
 
     def set_roll(self, params=None, **kw):

@@ -23,6 +23,7 @@ without the GUI.  Usage:
                                           [--grid-explore DIR [--grid-explore-range M]]
                                           [--grid-align DIR [--grid-align-apply] [--grid-align-window K,W]]
                                           [--grid-dynamic DIR [--grid-dynamic-params CLEAR,THROUGH,MARGIN,AGE]]
+                                          [--grid-objects DIR [--grid-objects-params MIN,MAX,HEIGHT,GATE,MISSED]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -127,6 +128,13 @@ per frame is appended to DIR/align.jsonl and the image (svh_grid_render_align: t
 scan placed at the best cyan, the camera's cell white) goes into DIR/align_%06d.ppm.  With --grid-align-apply a frame whose status
 is 0 and whose best is unique (ties 1: no direction was left open) is added to the local grid under the correction M (svh_grid_align_correction), its rays cast from the corrected camera
 position; the map view and the odometry are left alone.
+
+--grid-objects DIR: needs --grid-local; works with --grid-dynamic.  After every local step the obstacle cells of the local grid are
+grouped into objects and one step of their tracks is taken (svh_grid_objects_step; --grid-objects-params MIN,MAX,HEIGHT,GATE,MISSED:
+min_size, max_size, min_height in metres, gate in cells and max_missed of svh_grid_obj_params; 4,4096,0.3,4,2).  The image
+(svh_grid_render_objects: the class image, the kept cells in the colour of their track, bright when it moves, structure grey, the
+centroid and the cell eight steps ahead marked) goes into DIR/objects_%06d.ppm and one line {"frame", "window", "stats", "tracks"} with
+the track table (the fields of svhip.grid.TRACK_FIELDS) is appended to DIR/tracks.jsonl.
 
 --grid-dynamic DIR: needs --grid-local.  The local step takes a frame as an OBSERVATION (svh_grid_observe_view_lists) instead of an
 add: the frame's sight lines contradict obstacle cells they pass through at the height of their body, CLEAR contradicting frames in a row
@@ -615,6 +623,7 @@ def main():
     align_dir, align_apply, align_window = None, False, None
     roll_dir, roll_kw = None, {}
     dyn_dir, dyn_kw = None, {}
+    obj_dir, obj_kw = None, {}
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -715,6 +724,20 @@ def main():
             dyn_kw = dict(clear_frames=int(v[0]), min_through=int(v[1]), margin=float(v[2]), max_age=int(v[3]))
             assert 0 <= dyn_kw["clear_frames"] <= 65535 and dyn_kw["min_through"] >= 1 and 0 <= dyn_kw["margin"] < 2 ** 20 and dyn_kw["max_age"] >= 0
             del sys.argv[k:k + 2]
+        if "--grid-objects" in sys.argv:
+            k = sys.argv.index("--grid-objects")
+            obj_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-objects-params" in sys.argv:
+            k = sys.argv.index("--grid-objects-params")
+            v = sys.argv[k + 1].split(",")
+            assert len(v) == 5
+            obj_kw = dict(min_size=int(v[0]), max_size=int(v[1]), min_height=float(v[2]), gate=int(v[3]), max_missed=int(v[4]))
+            assert 1 <= obj_kw["min_size"] <= obj_kw["max_size"] <= 2 ** 26 and obj_kw["min_height"] >= 0 and 0 <= obj_kw["gate"] <= 64
+            assert 0 <= obj_kw["max_missed"] <= 255
+            del sys.argv[k:k + 2]
+        assert local_dir or not obj_dir
+        assert obj_dir or not obj_kw
         assert local_dir or not dyn_dir
         assert dyn_dir or not dyn_kw
         assert local_dir or not align_dir
@@ -804,6 +827,9 @@ def main():
     if dyn_dir:
         os.makedirs(dyn_dir, exist_ok=True)
         open(os.path.join(dyn_dir, "dyn.jsonl"), "w").close()
+    if obj_dir:
+        os.makedirs(obj_dir, exist_ok=True)
+        open(os.path.join(obj_dir, "tracks.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -816,6 +842,8 @@ def main():
         p.enable_grid_align(align_apply, align_window or (8, 8))
     if dyn_dir:
         p.enable_grid_dynamic(**dyn_kw)
+    if obj_dir:
+        p.local.set_objects(**obj_kw)
     if cost_dir:
         p.set_grid_cost(**cost_kw)
     if plan_dir or front_dir or explore_dir:
@@ -848,6 +876,12 @@ def main():
             view.write_ppm(os.path.join(dyn_dir, "dyn_%06d.ppm" % (frames - 1)), p.local.render_dyn())
             with open(os.path.join(dyn_dir, "dyn.jsonl"), "a") as f:
                 f.write(json.dumps(dict(p.local.dyn_stats(), frame=frames - 1)) + "\n")
+        if obj_dir:
+            p.local.objects_step(0)
+            view.write_ppm(os.path.join(obj_dir, "objects_%06d.ppm" % (frames - 1)), p.local.render_objects())
+            with open(os.path.join(obj_dir, "tracks.jsonl"), "a") as f:
+                f.write(json.dumps(dict(frame=frames - 1, window=list(p.local.window()), stats=list(p.local.track_stats()),
+                                        tracks=p.local.tracks().tolist())) + "\n")
         if align_dir and p.align_last is not None:
             rec, applied, img = p.align_last
             aligned += int(rec[0] == 0)
@@ -906,6 +940,10 @@ def main():
         d, ds = p.local.dynamics(), p.local.dyn_stats()
         print("dynamics: clear after %d frames of %d through-lines, margin %g m, age %d: %d observations, %d cells cleared, %d aged; %d images and dyn.jsonl in %s" % (
             d.clear_frames, d.min_through, d.margin, d.max_age, ds["observations"], ds["cleared"], ds["aged"], frames, dyn_dir))
+    if obj_dir:
+        o, os_, ts = p.local.objects_params(), p.local.object_stats(), p.local.track_stats()
+        print("objects: size %d..%d, height %g m, gate %d cells, %d misses: %d kept of %d components in the last frame, %d tracks after %d steps; "
+              "%d images and tracks.jsonl in %s" % (o.min_size, o.max_size, o.min_height, o.gate, o.max_missed, os_[2], os_[1], ts[1], ts[0], frames, obj_dir))
     if cost_dir:
         t, reach = p.local.traversability()
         print("cost map: slope %g, inscribed %g m, inflation %g m = %d cells; %d images in %s" % (
