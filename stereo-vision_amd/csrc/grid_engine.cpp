@@ -9,6 +9,8 @@
 // (grid_roll_kernels.hip): the rollouts -- footprint costs, the scoring of a set of candidates and its best;
 // (grid_obj_kernels.hip): the objects and their tracks -- obstacle components labelled by the frontier layer's kernels, the table of
 // kept ones, and the step that associates them with the tracks of the step before, run by obj_run() and objects_step() here;
+// (grid_pred_kernels.hip): the prediction -- the tracks carried ahead into the slots of PRED, run by predict() here, and the
+// footprint masks and the scoring of a set of candidates against it;
 // (grid_explore_kernels.hip): the exploration layer -- the gain of viewpoints, the ranking of the frontiers, run by explore_rank() here;
 // (grid_align_kernels.hip): the alignment layer -- the field, the scan of a frame's obstacle points, the volume of scores, run by align() here;
 // (grid_dyn_kernels.hip): the dynamics -- the sight lines and the settle of an observation, run by observe() here.
@@ -24,7 +26,8 @@
 // computed from and what each change makes stale is one table, below beside the struct (Kept, kNeeds, kDrops): a setter says
 // what it changed (touch), a function that launches a layer says so (pending), and the entry that has waited for the launches
 // makes them count (settle); a failed entry makes nothing count (failed).  The reach field has a key beside its bit: the start
-// cell of the ranking it was computed for.  Gains and VIEW planes are computed per call.
+// cell of the ranking it was computed for.  Gains and VIEW planes are computed per call.  PRED has a bit of its own outside the
+// derived layers: it is computed from the tracks, which are state, and from its parameters, never from the accumulators.
 // The dynamics keep CONTRA, LAST, the THROUGH and the events of the last observation and the bodies of the cells at the cells' slots
 // (they travel with the torus and are cleared as lazily as the accumulators, dyn_need_clear); the body plane is kept by the settle
 // kernel and written anew (body_valid) after anything else wrote the accumulators.  The frame record and `ends` are scratch, empty
@@ -141,6 +144,19 @@ struct RollBufs {
     HipBuf<long long> scores;
 };
 
+// the prediction: PRED and the scratch of its inflation, the displacements and flags of the tracks, the control words with their pinned
+// copy (the statistics of the PRED that is valid are read there), and the outputs of a scoring with prediction, which leave those of
+// svh_grid_roll_score alone
+struct PredBufs {
+    HipBuf<uint32_t> plane, rows, d_mask;
+    HipBuf<int2> disp;
+    HipBuf<int32_t> predicts, recs, best, d_poses;
+    HipBuf<long long> scores;
+    HipBuf<unsigned long long> ctl;
+    PinnedBuf<unsigned long long> h_ctl;
+    PinnedBuf<uint8_t> h_roll;
+};
+
 // what a ranking needs on the device beside the planes: the gains of the representatives, the records, the scores, and the best
 // with the count of feasible records
 struct ExploreBufs {
@@ -173,14 +189,16 @@ enum Kept : uint32_t {
     UP_ROLL = 1u << 9,    // roll_bufs.offs and .start hold the footprint table
     UP_CANDS = 1u << 10,  // d_cands and d_cand_lens hold the candidates
     ROLL_LAST = 1u << 11, // roll_bufs.recs holds the records of the last svh_grid_roll_score
-    ALIGN_LAST = 1u << 12 // al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
+    ALIGN_LAST = 1u << 12,// al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
+    PRED = 1u << 13       // pred.plane and its statistics, from the track state and the prediction parameters: not a derived layer, the
+                          // accumulators do not reach it
 };
 constexpr int kLayers = 7;
 constexpr uint32_t kAllLayers = (1u << kLayers) - 1;
 // the layers each derived layer is computed from, by the layer's bit number
 constexpr uint32_t kNeeds[kLayers] = {0, FINAL, TRAV, TRAV, TRAV, FINAL, FINAL};
 // what changes, and what it makes stale directly; the layers computed from a stale layer follow by closure()
-enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, OBJ_PARAMS, SOURCES };
+enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, OBJ_PARAMS, TRACKS, PRED_PARAMS, SOURCES };
 constexpr uint32_t kDrops[SOURCES] = {
     FINAL,                    // ACC: the accumulators or the window's offsets
     TRAV | UP_TABLE,          // TRAV_PARAMS
@@ -191,6 +209,8 @@ constexpr uint32_t kDrops[SOURCES] = {
     UP_CANDS | ROLL_LAST,     // CANDS: the candidate table
     AFIELD | ALIGN_LAST,      // ALIGN_PARAMS
     OBJ,                      // OBJ_PARAMS
+    PRED,                     // TRACKS: the track table or the ID plane: a step, or anything that empties the tracks
+    PRED,                     // PRED_PARAMS
 };
 constexpr uint32_t closure(uint32_t m) {
     for (int pass = 0; pass < kLayers; pass++)
@@ -212,6 +232,9 @@ static_assert(kStale.of[TRAV_PARAMS] == (TRAV | PLAN | FRONT | REACH | UP_TABLE)
 static_assert(kStale.of[OBJ_PARAMS] == OBJ && (kStale.of[ACC] & OBJ), "the objects follow the accumulators and their own parameters");
 static_assert(!((kStale.of[TRAV_PARAMS] | kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[ROLL_PARAMS] |
                  kStale.of[CANDS] | kStale.of[ALIGN_PARAMS]) & OBJ), "no other layer's source makes the objects stale");
+static_assert(kStale.of[TRACKS] == PRED && kStale.of[PRED_PARAMS] == PRED, "the prediction follows the tracks and its own parameters");
+static_assert(!((kStale.of[ACC] | kStale.of[TRAV_PARAMS] | kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[ROLL_PARAMS] |
+                 kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[OBJ_PARAMS]) & PRED), "nothing else makes the prediction stale");
 
 }  // namespace
 
@@ -303,6 +326,9 @@ struct svh_grid {
     bool trk_plane = false;     // a step has written the current ID plane; false: it counts as all -1
     int32_t trk_n = 0, trk_next = 0, trk_oa = 0, trk_ob = 0;   // the tracks, the next id, the offsets of the ID plane
     int64_t trk_stats[grid::TS_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    grid::PredParams prp{8, 1, 1, 1, 0, 1};   // the prediction: parameters, PRED
+    PredBufs pred;
+    int32_t pred_launches = 0;  // PRED: the launches of the computation that produced it
 
     grid::Cells cells() const {
         uint8_t* b = acc.p;
@@ -368,10 +394,11 @@ int failed(svh_grid* g, int rc, uint32_t kept = 0) {
     return rc;
 }
 // what each family of entries drops there
-constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST, kObjects = OBJ;
+constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST, kObjects = OBJ, kPrediction = PRED;
 
 // the tracks are empty and the ids start again at 0
 void forget_tracks(svh_grid* g) {
+    touch(g, TRACKS);
     g->trk_plane = false;
     g->trk_n = g->trk_next = 0;
     for (int k = 0; k < grid::TS_WORDS; k++) g->trk_stats[k] = 0;
@@ -1102,6 +1129,7 @@ int objects_step(svh_grid* g, int32_t* assign, int64_t cap, int64_t* n_obj) {
     const unsigned long long* h = (const unsigned long long*)b.h_out.p;
     if (h[grid::SC_UNSETTLED]) return svh::fail(SVH_ERR_HIP, kStepUnsettled);
     if (m > 0) memcpy(assign, b.h_out + ctl_bytes, m * sizeof(int32_t));
+    touch(g, TRACKS);
     g->trk_cur = nxt, g->trk_plane = true;
     g->trk_n = (int32_t)h[grid::SC_TRACKS], g->trk_next += (int32_t)h[grid::SC_NEW];
     g->trk_oa = j.oa, g->trk_ob = j.ob;
@@ -1267,6 +1295,149 @@ int render_roll(svh_grid* g, uint8_t* rgb, bool on_device) {
         roll_candidates(j, g->roll_bufs, g->d_cands, g->d_cand_lens, g->roll_last_set, g->cand_K, g->cand_T, g->roll_last_ga, g->roll_last_gb);
         grid::launch_render_cost(g->stream, cost_job(g, dst));
         grid::launch_roll_overlay(g->stream, j, g->roll_last_best, dst);
+        return rc;
+    });
+}
+
+// ---- the prediction ---------------------------------------------------------------------------------------------------------
+bool convert_pred(const svh_grid_pred_params* p, grid::PredParams* q) {
+    if (!p) return false;
+    *q = grid::PredParams{p->slots, p->stride, p->poses_per_step, p->margin, p->grow16, p->only_moving};
+    return grid::pred_ok(*q);
+}
+
+// the offsets PRED lies under: those of the ID plane, the window's while no step has written one (PRED is all 0 then)
+int32_t pred_oa(const svh_grid* g) { return g->trk_plane ? g->trk_oa : g->prm.oa; }
+int32_t pred_ob(const svh_grid* g) { return g->trk_plane ? g->trk_ob : g->prm.ob; }
+
+// a job on a track table and an ID plane that lie on the device, with the buffers of `b`, which this grows; PRED and the control
+// words are cleared on the stream
+int pred_job(hipStream_t s, const grid::PredParams& pp, int32_t nx, int32_t nz, const int32_t* id, const int32_t* tracks, int32_t n_tracks, PredBufs& b,
+             grid::PredJob* j) {
+    const size_t cells = (size_t)nx * (size_t)nz, ctl_bytes = grid::PRED_CTL_WORDS * sizeof(unsigned long long);
+    j->pp = pp;
+    j->nx = nx, j->nz = nz;
+    j->id = id, j->tracks = tracks, j->n_tracks = n_tracks;
+    for (int32_t r = 0; r <= grid::PRED_MAX_RADIUS; r++) j->ge[r] = grid::pred_ge(pp, r);
+    j->max_r = grid::pred_radius(pp, pp.slots - 1);
+    GRID_GROW_N(b.plane, cells);
+    GRID_GROW(b.ctl, ctl_bytes);
+    GRID_GROW(b.h_ctl, ctl_bytes);
+    if (n_tracks > 0) {
+        GRID_GROW_N(b.disp, (size_t)n_tracks * grid::PRED_MAX_SLOTS);
+        GRID_GROW_N(b.predicts, n_tracks);
+        if (j->max_r > 0) GRID_GROW_N(b.rows, cells);
+    }
+    j->disp = b.disp, j->predicts = b.predicts, j->pred = b.plane, j->rows = b.rows, j->ctl = b.ctl;
+    GRID_TRY(copy, hipMemsetAsync(b.plane, 0, cells * sizeof(uint32_t), s));
+    GRID_TRY(copy, hipMemsetAsync(b.ctl, 0, ctl_bytes, s));
+    return SVH_OK;
+}
+
+// PRED is valid or launched: from the track state as it is, pending until the caller has waited and settles.  The control words
+// follow to pinned memory on the stream, where the statistics are read once PRED counts.  An empty table is a fill
+int predict(svh_grid* g) {
+    if (has(g, PRED) || (g->pending & PRED)) return SVH_OK;
+    hipStream_t s = g->stream;
+    PredBufs& b = g->pred;
+    const int32_t n = g->trk_plane ? g->trk_n : 0;
+    grid::PredJob j;
+    const int rc = pred_job(s, g->prp, g->prm.nx, g->prm.nz, n ? g->trk.id[g->trk_cur].p : nullptr, n ? g->trk.table[g->trk_cur].p : nullptr, n, b, &j);
+    if (rc) return rc;
+    g->pred_launches = 0;
+    if (n > 0) GRID_TRY(launch, (g->pred_launches = grid::launch_pred(s, j), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(b.h_ctl, b.ctl, grid::PRED_CTL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    g->pending |= PRED;
+    return SVH_OK;
+}
+
+int get_pred_plane(svh_grid* g, uint32_t* out, bool on_device) {
+    int rc = ready(g);
+    if (rc || (rc = predict(g))) return rc;
+    if ((rc = deliver(g, g->pred.plane, g->ncells * sizeof(uint32_t), out, on_device))) return rc;
+    settle(g);
+    return SVH_OK;
+}
+
+int get_pred_stats(svh_grid* g, int64_t out[4]) {
+    int rc = ready(g);
+    if (rc || (rc = predict(g))) return rc;
+    if (g->pending) {
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+        settle(g);
+    }
+    const unsigned long long* h = g->pred.h_ctl;
+    out[grid::PS_TRACKS] = (int64_t)h[grid::PS_TRACKS], out[grid::PS_SOURCES] = (int64_t)h[grid::PS_SOURCES];
+    out[grid::PS_CELLS] = (int64_t)h[grid::PS_CELLS], out[grid::PS_LAUNCHES] = g->pred_launches;
+    return SVH_OK;
+}
+
+grid::RollPredJob roll_pred_job(const svh_grid* g) {
+    grid::RollPredJob j;
+    j.r = roll_job(g);
+    j.pp = g->prp;
+    j.poa = pred_oa(g), j.pob = pred_ob(g);
+    j.pred = g->pred.plane;
+    return j;
+}
+
+// the footprint predictions of n > 0 poses with arguments that have been checked
+int footprint_pred(svh_grid* g, const int32_t* poses, int64_t n, bool on_device, uint32_t* out) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = roll_tables(g, false))) return rc;
+    PredBufs& b = g->pred;
+    if (!on_device) {
+        GRID_GROW_N(b.d_poses, 3 * n);
+        GRID_GROW_N(b.d_mask, n);
+        GRID_GROW(g->h_out, (size_t)n * sizeof(uint32_t));
+        GRID_TRY(copy, hipMemcpyAsync(b.d_poses, poses, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    }
+    if ((rc = predict(g))) return rc;
+    grid::launch_footprint_pred(g->stream, roll_pred_job(g), on_device ? poses : b.d_poses.p, n, on_device ? out : b.d_mask.p);
+    GRID_TRY(launch, hipGetLastError());
+    return finish(g, b.d_mask, (size_t)n * sizeof(uint32_t), out, on_device);
+}
+
+// set `set` scored at the global cell (ga, gb) with the prediction; recs and scores may be null.  The outputs are the layer's own:
+// those of the last svh_grid_roll_score stay
+int roll_score_pred(svh_grid* g, int32_t ga, int32_t gb, int32_t set, int32_t* recs, int64_t* scores, bool on_device, int32_t* best) {
+    int rc = ready(g);
+    if (rc) return rc;
+    PredBufs& b = g->pred;
+    const int32_t K = g->cand_K;
+    const size_t rec_bytes = (size_t)K * grid::ROLL_PRED_REC * sizeof(int32_t), score_bytes = (size_t)K * sizeof(int64_t);
+    GRID_GROW_N(b.recs, (size_t)grid::ROLL_PRED_REC * (size_t)K);
+    GRID_GROW_N(b.scores, K);
+    GRID_GROW_N(b.best, 1);
+    GRID_GROW(b.h_roll, score_bytes + rec_bytes + sizeof(int32_t));   // the scores first: they are the widest
+    if ((rc = roll_tables(g, true))) return rc;
+    if ((rc = g->rol.p.w_pot != 0 ? plan_field(g) : traverse(g))) return rc;
+    if ((rc = predict(g))) return rc;
+    grid::RollPredJob j = roll_pred_job(g);
+    j.r.cands = g->d_cands + (size_t)set * (size_t)K * (size_t)g->cand_T * 3, j.r.lens = g->d_cand_lens + (size_t)set * (size_t)K;
+    j.r.K = K, j.r.T = g->cand_T, j.r.ga0 = ga, j.r.gb0 = gb;
+    j.r.recs = b.recs, j.r.scores = b.scores, j.r.best = b.best;
+    hipStream_t s = g->stream;
+    GRID_TRY(launch, (grid::launch_roll_score_pred(s, j), hipGetLastError()));
+    uint8_t* h = b.h_roll;
+    if (scores) GRID_TRY(copy, hipMemcpyAsync(on_device ? (void*)scores : (void*)h, j.r.scores, score_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (recs) GRID_TRY(copy, hipMemcpyAsync(on_device ? (void*)recs : (void*)(h + score_bytes), j.r.recs, rec_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    GRID_TRY(copy, hipMemcpyAsync(h + score_bytes + rec_bytes, j.r.best, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    settle(g);
+    if (scores && !on_device) memcpy(scores, h, score_bytes);
+    if (recs && !on_device) memcpy(recs, h + score_bytes, rec_bytes);
+    memcpy(best, h + score_bytes + rec_bytes, sizeof(int32_t));
+    return SVH_OK;
+}
+
+int render_pred(svh_grid* g, int32_t mode, uint8_t* rgb, bool on_device) {
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        int rc = finalise(g);
+        if (rc || (rc = predict(g))) return rc;
+        grid::launch_render(g->stream, render_job(g, mode, dst));
+        grid::launch_pred_overlay(g->stream, g->prm.nx, g->prm.nz, g->prm.oa, g->prm.ob, pred_oa(g), pred_ob(g), g->pred.plane, dst);
         return rc;
     });
 }
@@ -2221,6 +2392,70 @@ int32_t svh_grid_render_objects(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     return failed(g, render_objects(g, rgb, on_device != 0), kObjects);
 }
 
+void svh_grid_pred_params_default(svh_grid_pred_params* p) {
+    if (!p) return;
+    p->slots = 8, p->stride = 1, p->poses_per_step = 1, p->margin = 1, p->grow16 = 0, p->only_moving = 1;
+}
+
+int32_t svh_grid_set_predict(svh_grid* g, const svh_grid_pred_params* p) {
+    grid::PredParams q;
+    if (!g || !convert_pred(p, &q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_predict: a grid and parameters in range are needed (include/svh_grid_pred.h)");
+    g->prp = q;
+    touch(g, PRED_PARAMS);
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_predict(svh_grid* g, svh_grid_pred_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_predict: null argument");
+    const grid::PredParams& q = g->prp;
+    p->slots = q.slots, p->stride = q.stride, p->poses_per_step = q.poses_per_step, p->margin = q.margin, p->grow16 = q.grow16, p->only_moving = q.only_moving;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_pred_plane(svh_grid* g, uint32_t* out, int32_t on_device, int32_t off[2]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_pred_plane: a grid and an output are needed");
+    if (on_device && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_pred_plane: a device array must be 4-byte aligned");
+    const int rc = failed(g, get_pred_plane(g, out, on_device != 0), kPrediction);
+    if (!rc && off) off[0] = pred_oa(g), off[1] = pred_ob(g);
+    return rc;
+}
+
+int32_t svh_grid_get_pred_stats(svh_grid* g, int64_t out[4]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_pred_stats: null argument");
+    return failed(g, get_pred_stats(g, out), kPrediction);
+}
+
+int32_t svh_grid_footprint_pred(svh_grid* g, const int32_t* poses, int64_t n, int32_t on_device, uint32_t* out) {
+    if (!g || n < 0 || n > ((int64_t)1 << 26) || (n > 0 && (!poses || !out)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_footprint_pred: a grid and 0..2^26 poses with room for their masks are needed");
+    if (on_device && (((uintptr_t)poses | (uintptr_t)out) & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_footprint_pred: a device array must be 4-byte aligned");
+    if (!g->rol.R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_footprint_pred") + kNoRoll);
+    if (!on_device)
+        for (int64_t i = 0; i < n; i++)
+            if (poses[3 * i + 2] < 0 || poses[3 * i + 2] >= 8 * g->rol.p.m) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_footprint_pred: a heading is not in 0..8 m - 1");
+    if (n == 0) return SVH_OK;
+    return failed(g, footprint_pred(g, poses, n, on_device != 0, out), kPrediction);
+}
+
+int32_t svh_grid_roll_score_pred(svh_grid* g, const double anchor_xyz[3], int32_t set, int32_t* recs, int64_t* scores, int32_t on_device, int32_t* best) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || !best || !position(anchor_xyz, p) || !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score_pred: a grid, an output and a finite anchor with a cell below 2^20 are needed");
+    if (!g->trav_ok) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_roll_score_pred") + kNoTrav);
+    if (!g->rol.R) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_roll_score_pred") + kNoRoll);
+    if (g->cand_S == 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score_pred: no candidates (svh_grid_roll_set_candidates)");
+    if (set < 0 || set >= g->cand_S) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score_pred: no such set");
+    if (on_device && (((uintptr_t)recs & 3) || ((uintptr_t)scores & 7)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_roll_score_pred: a device array of records must be 4-byte, one of scores 8-byte aligned");
+    return failed(g, roll_score_pred(g, ga, gb, set, recs, scores, on_device != 0, best), kPrediction);
+}
+
+int32_t svh_grid_render_pred(svh_grid* g, int32_t mode, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb || mode < 0 || mode >= grid::M_MODES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_pred: a grid, a mode 0..2 and an output are needed");
+    return failed(g, render_pred(g, mode, rgb, on_device != 0), kPrediction);
+}
+
 void svh_grid_roll_params_default(svh_grid_roll_params* p) {
     if (!p) return;
     p->front = 3.5f, p->rear = 1.0f, p->half_width = 0.9f;
@@ -3171,6 +3406,102 @@ int32_t svh_test_grid_obj_step(const svh_grid_obj_params* p, int32_t nx, int32_t
 int32_t svh_test_grid_obj_colour(int64_t ncells, const uint8_t* flags, const int32_t* id, const uint8_t* moving, uint8_t* rgb) {
     if (ncells < 0 || (ncells > 0 && (!flags || !id || !moving || !rgb))) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_obj_colour: bad arguments");
     for (int64_t i = 0; i < ncells; i++) (void)grid::colour_obj(flags[i], id[i], moving[i] != 0, rgb + 3 * i);
+    return SVH_OK;
+}
+
+// grid_pred_core.h's PRED on the host: the ID plane [nz * nx] (NULL: all -1) and n_tracks track records in ascending order of id ->
+// pred [nz * nx], stats[4] (the launches are 0).  Needs no device
+int32_t svh_test_grid_pred(const svh_grid_pred_params* p, int32_t nx, int32_t nz, const int32_t* id, const int32_t* tracks, int32_t n_tracks,
+                           uint32_t* pred, int64_t* stats) {
+    grid::PredParams q;
+    if (!convert_pred(p, &q) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || n_tracks < 0 || n_tracks > grid::OBJ_MAX_TRACKS ||
+        (n_tracks > 0 && !tracks) || !pred)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pred: bad arguments");
+    for (int32_t t = 1; t < n_tracks; t++)
+        if (tracks[(size_t)t * grid::TRACK_REC] <= tracks[(size_t)(t - 1) * grid::TRACK_REC])
+            return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pred: the track table is not in ascending order of id");
+    grid::pred_window(q, nx, nz, id, tracks, n_tracks, pred, stats);
+    return SVH_OK;
+}
+
+// the kernels of the prediction on a caller's ID plane and track table (host); stats[3] the launches
+int32_t svh_test_grid_pred_device(const svh_grid_pred_params* p, int32_t nx, int32_t nz, const int32_t* id, const int32_t* tracks, int32_t n_tracks,
+                                  uint32_t* pred, int64_t* stats) {
+    grid::PredParams q;
+    if (!convert_pred(p, &q) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || n_tracks < 0 || n_tracks > grid::OBJ_MAX_TRACKS ||
+        (n_tracks > 0 && (!tracks || !id)) || !pred)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pred_device: bad arguments");
+    for (int32_t t = 1; t < n_tracks; t++)
+        if (tracks[(size_t)t * grid::TRACK_REC] <= tracks[(size_t)(t - 1) * grid::TRACK_REC])
+            return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pred_device: the track table is not in ascending order of id");
+    svh::ensure_init();
+    const size_t cells = (size_t)nx * (size_t)nz;
+    HipBuf<int32_t> d_id, d_tracks;
+    PredBufs b;
+    hipStream_t s = nullptr;
+    int32_t launches = 0;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        if (n_tracks > 0) {
+            GRID_GROW_N(d_id, cells);
+            GRID_GROW_N(d_tracks, (size_t)n_tracks * grid::TRACK_REC);
+            GRID_TRY(copy, hipMemcpyAsync(d_id, id, cells * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            GRID_TRY(copy, hipMemcpyAsync(d_tracks, tracks, (size_t)n_tracks * grid::TRACK_REC * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+        grid::PredJob j;
+        const int r = pred_job(s, q, nx, nz, d_id, d_tracks, n_tracks, b, &j);
+        if (r) return r;
+        if (n_tracks > 0) GRID_TRY(launch, (launches = grid::launch_pred(s, j), hipGetLastError()));
+        GRID_TRY(copy, hipMemcpyAsync(pred, b.plane, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(b.h_ctl, b.ctl, grid::PRED_CTL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    if (stats) {
+        for (int k = 0; k < grid::PS_LAUNCHES; k++) stats[k] = (int64_t)b.h_ctl[k];
+        stats[grid::PS_LAUNCHES] = launches;
+    }
+    return SVH_OK;
+}
+
+// grid_pred_core.h's slots, radii and displacements on the host: slot[t] = the slot of pose t for t < T, radius[s] and ge[r] for
+// s < 32 and r <= 16, and (n > 0) disp[i * 32 + s] = D(s) of the velocity v16[i] on one axis.  Any output may be NULL.  Needs no device
+int32_t svh_test_grid_pred_slots(const svh_grid_pred_params* p, int32_t T, int32_t* slot, int32_t* radius, uint32_t* ge, const int32_t* v16, int32_t n,
+                                 int32_t* disp) {
+    grid::PredParams q;
+    if (!convert_pred(p, &q) || T < 0 || T > grid::ROLL_MAX_T || n < 0 || (n > 0 && (!v16 || !disp)))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pred_slots: bad arguments");
+    for (int32_t t = 0; slot && t < T; t++) slot[t] = grid::pred_slot(q, t);
+    for (int32_t s = 0; radius && s < grid::PRED_MAX_SLOTS; s++) radius[s] = grid::pred_radius(q, s);
+    for (int32_t r = 0; ge && r <= grid::PRED_MAX_RADIUS; r++) ge[r] = grid::pred_ge(q, r);
+    for (int32_t i = 0; i < n; i++)
+        for (int32_t s = 0; s < grid::PRED_MAX_SLOTS; s++) disp[(size_t)i * grid::PRED_MAX_SLOTS + s] = grid::pred_disp(q, v16[i], s);
+    return SVH_OK;
+}
+
+// grid_pred_core.h's scoring on the host, with the footprint table of roll_table_for: the arguments of svh_test_grid_roll, the
+// prediction parameters and a PRED plane of the window's size under the offsets (poa, pob); mout[n_poses] the footprint predictions
+// of the free poses, recs 6 per candidate.  Needs no device
+int32_t svh_test_grid_pred_roll(const svh_grid_roll_params* p, const svh_grid_pred_params* pp, float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob,
+                                const uint8_t* cost, const int32_t* pot, int32_t poa, int32_t pob, const uint32_t* pred, const int32_t* table, int32_t S,
+                                int32_t K, int32_t T, int32_t set, int32_t ga0, int32_t gb0, const int32_t* poses, int64_t n_poses, uint32_t* mout,
+                                int32_t* recs, int64_t* scores, int32_t* best) {
+    grid::RollParams q;
+    grid::PredParams qp;
+    std::shared_ptr<const RollTable> t;
+    int32_t fdummy = 0;
+    if (!convert_pred(pp, &qp) || !pred || !grid::offsets_ok(poa, pob) || (n_poses > 0 && !mout) ||
+        !roll_test_args(p, cell, nx, nz, oa, ob, cost, pot, table, S, K, T, set, ga0, gb0, poses, n_poses, n_poses > 0 ? &fdummy : nullptr, best, &q, &t))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pred_roll: bad arguments");
+    if (n_poses > 0) grid::footprint_pred_window(q, nx, nz, poa, pob, pred, t->offs.data(), t->start.data(), poses, n_poses, mout);
+    if (table)
+        *best = grid::roll_pred_window(q, qp, nx, nz, oa, ob, cost, pot, nx, nz, poa, pob, pred, t->offs.data(), t->start.data(),
+                                       table + (size_t)set * (size_t)K * (size_t)T * 3, K, T, ga0, gb0, recs, scores);
     return SVH_OK;
 }
 

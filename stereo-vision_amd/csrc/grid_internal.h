@@ -1,6 +1,6 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
-// csrc/grid_front_kernels.hip / csrc/grid_obj_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip /
-// csrc/grid_dyn_kernels.hip: the launches of the
+// csrc/grid_front_kernels.hip / csrc/grid_obj_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_pred_kernels.hip /
+// csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip / csrc/grid_dyn_kernels.hip: the launches of the
 // ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
@@ -15,6 +15,7 @@
 #include "grid_front_core.h"
 #include "grid_obj_core.h"
 #include "grid_plan_core.h"
+#include "grid_pred_core.h"
 #include "grid_roll_core.h"
 
 namespace svh {
@@ -362,6 +363,51 @@ void launch_footprint_cost(hipStream_t s, const RollJob& j, const int32_t* poses
 // the reference cells of the poses before the cut of every candidate, then of `best` (>= 0) over them, drawn into an image of
 // svh_grid_render_cost's layout from the records in j.recs
 void launch_roll_overlay(hipStream_t s, const RollJob& j, int32_t best, uint8_t* rgb);
+
+// The prediction (csrc/grid_pred_kernels.hip): the track table and the ID plane of the last step -> PRED; PRED, the finished COST and
+// POT planes, the footprint table and the candidates of one set -> the records with the object cut, the scores and the best.
+constexpr uint32_t PRED_BLOCK = 256;             // every kernel of the layer but the column pass
+constexpr unsigned PRED_MAX_BLOCKS = 2048;       // k_grid_pred_scatter: the lanes stride over the ID frame beyond 2048 * 256 cells
+constexpr int32_t PRED_ROWS_TILE = (int32_t)PRED_BLOCK + 2 * PRED_MAX_RADIUS;   // k_grid_pred_rows: 256 cells of a row and their halo
+constexpr int32_t PRED_COLS_X = 64, PRED_COLS_Y = 32;   // k_grid_pred_cols: the cells a workgroup of 64 x 4 lanes writes
+// the launches of one computation, a constant of the build: displacements, scatter, rows, columns; without the last two when every
+// radius is 0
+constexpr int32_t PRED_LAUNCHES = 4, PRED_LAUNCHES_FLAT = 2;
+// the control words on the device, 64 bits each: a grid::PredStat without the launches
+constexpr int32_t PRED_CTL_WORDS = 4;
+
+struct PredJob {
+    PredParams pp;
+    int32_t nx, nz;             // the ID frame
+    const int32_t* id;          // the ID plane of the last step
+    const int32_t* tracks;      // its n_tracks records, ascending by id; 1..4096
+    int32_t n_tracks;
+    int2* disp;                 // n_tracks * 32: D_i(s)
+    int32_t* predicts;          // n_tracks: the track predicts
+    uint32_t* pred;             // nx * nz, all zero before
+    uint32_t* rows;             // nx * nz, scratch of the inflation; not touched when the largest radius is 0
+    unsigned long long* ctl;    // PRED_CTL_WORDS, all zero before
+    uint32_t ge[PRED_MAX_RADIUS + 1];   // pred_ge(pp, r)
+    int32_t max_r;              // the radius of the last slot, the largest
+};
+// the whole computation; returns the kernels it launched
+int32_t launch_pred(hipStream_t s, const PredJob& j);
+
+// a RollJob with PRED: the frame has the window's size and its own offsets
+struct RollPredJob {
+    RollJob r;                  // recs: ROLL_PRED_REC per candidate
+    PredParams pp;
+    int32_t poa, pob;
+    const uint32_t* pred;
+};
+// records and scores of the K candidates, then the best: two launches whatever the scene
+void launch_roll_score_pred(hipStream_t s, const RollPredJob& j);
+// the footprint predictions of n free poses (ga, gb, k), global cells
+void launch_footprint_pred(hipStream_t s, const RollPredJob& j, const int32_t* poses, int64_t n, uint32_t* out);
+// the window cells whose PRED word is not zero, drawn over an image of svh_grid_render's layout
+void launch_pred_overlay(hipStream_t s, int32_t nx, int32_t nz, int32_t oa, int32_t ob, int32_t poa, int32_t pob, const uint32_t* pred, uint8_t* rgb);
+// k_grid_roll_best of csrc/grid_roll_kernels.hip
+void launch_roll_best(hipStream_t s, const long long* scores, int32_t K, int32_t* best);
 
 // The exploration layer (csrc/grid_explore_kernels.hip): the finished STATE plane, the frontier table and the reach field -> GAIN of
 // viewpoints, the VIEW plane of one, the records, the scores and the best.

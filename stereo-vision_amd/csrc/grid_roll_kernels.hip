@@ -163,6 +163,10 @@ void launch_roll_score(hipStream_t s, const RollJob& j) {
     hipLaunchKernelGGL(k_grid_roll_best, dim3(1), dim3(ROLL_BEST_BLOCK), 0, s, (const long long*)j.scores, j.K, j.best);
 }
 
+void launch_roll_best(hipStream_t s, const long long* scores, int32_t K, int32_t* best) {
+    hipLaunchKernelGGL(k_grid_roll_best, dim3(1), dim3(ROLL_BEST_BLOCK), 0, s, scores, K, best);
+}
+
 void launch_footprint_cost(hipStream_t s, const RollJob& j, const int32_t* poses, int64_t n, int32_t* out) {
     if (n <= 0) return;
     const int64_t per_block = (int64_t)ROLL_BLOCK / j.group;

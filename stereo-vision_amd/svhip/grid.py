@@ -66,6 +66,11 @@ TRACK_NEW, TRACK_BY_OVERLAP, TRACK_BY_GATE, TRACK_MISSED, TRACK_MOVING, TRACK_ME
 TRACK_STATS = ("steps", "tracks", "by_overlap", "by_gate", "new", "missed", "dropped", "untracked")
 ASSIGN_UNTRACKED = -2
 OBJ_LARGE_COLOUR, OBJ_UNTRACKED_COLOUR, OBJ_CENTRE_COLOUR, OBJ_AHEAD_COLOUR = (128, 128, 128), (128, 0, 0), (255, 255, 255), (255, 255, 0)
+ROLL_CUT_OBJECT = 4
+ROLL_PRED_RECORD = 6
+ROLL_PRED_FIELDS = ROLL_FIELDS + ("slot",)
+PRED_STATS = ("tracks", "sources", "cells", "launches")
+PRED_MAX_SLOTS, PRED_MAX_RADIUS = 32, 16
 
 
 class Params(C.Structure):
@@ -133,6 +138,21 @@ class ObjParams(C.Structure):
 
     def copy(self, **kw):
         q = ObjParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class PredParams(C.Structure):
+    """svh_grid_pred_params"""
+    _fields_ = [("slots", C.c_int32), ("stride", C.c_int32), ("poses_per_step", C.c_int32), ("margin", C.c_int32), ("grow16", C.c_int32),
+                ("only_moving", C.c_int32)]
+
+    def copy(self, **kw):
+        q = PredParams.from_buffer_copy(bytes(self))
         for k, v in kw.items():
             setattr(q, k, v)
         return q
@@ -299,6 +319,21 @@ def _bind():
         L.svh_test_grid_obj_step.argtypes = ([C.POINTER(ObjParams)] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6)
         L.svh_test_grid_obj_colour.argtypes = [C.c_int64] + [C.c_void_p] * 4
+        L.svh_grid_pred_params_default.argtypes = [C.POINTER(PredParams)]
+        L.svh_grid_pred_params_default.restype = None
+        L.svh_grid_set_predict.argtypes = [C.c_void_p, C.POINTER(PredParams)]
+        L.svh_grid_get_predict.argtypes = [C.c_void_p, C.POINTER(PredParams)]
+        L.svh_grid_get_pred_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.svh_grid_get_pred_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_footprint_pred.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.svh_grid_roll_score_pred.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.svh_grid_render_pred.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        pred = [C.POINTER(PredParams), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.svh_test_grid_pred.argtypes = pred
+        L.svh_test_grid_pred_device.argtypes = pred
+        L.svh_test_grid_pred_slots.argtypes = [C.POINTER(PredParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.svh_test_grid_pred_roll.argtypes = ([C.POINTER(RollParams), C.POINTER(PredParams), C.c_float] + [C.c_int32] * 4 + [C.c_void_p] * 2 +
+                                              [C.c_int32] * 2 + [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
         L.svh_grid_roll_params_default.argtypes = [C.POINTER(RollParams)]
         L.svh_grid_roll_params_default.restype = None
         L.svh_grid_set_roll.argtypes = [C.c_void_p, C.POINTER(RollParams)]
@@ -723,6 +758,72 @@ def core_roll(roll, cell, cost, pot=None, table=None, set_=0, anchor=(0, 0), oa=
 def device_roll(roll, cell, cost, pot=None, table=None, set_=0, anchor=(0, 0), oa=0, ob=0, poses=None):
     """TEST ENTRY: the same through the device kernels on a caller's planes"""
     return _roll(_bind().svh_test_grid_roll_device, roll, cell, cost, pot, table, set_, anchor, oa, ob, poses)
+
+
+def default_pred(**kw):
+    p = PredParams()
+    _bind().svh_grid_pred_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def _pred(entry, pred, ids, tracks, shape):
+    t = np.ascontiguousarray(tracks, np.int32).reshape(-1, TRACK_RECORD)
+    i = None if ids is None else np.ascontiguousarray(ids, np.int32)
+    nz, nx = shape if i is None else i.shape
+    out, stats = np.zeros((nz, nx), np.uint32), np.zeros(4, np.int64)
+    _check(entry(C.byref(pred), nx, nz, None if i is None else i.ctypes.data, t.ctypes.data if len(t) else None, len(t), out.ctypes.data,
+                 stats.ctypes.data))
+    return out, tuple(int(v) for v in stats)
+
+
+def core_pred(pred, ids, tracks, shape=None):
+    """PRED of csrc/grid_pred_core.h on the host (svh_test_grid_pred) from the ID plane int32 [nz, nx] (None with shape = (nz, nx): all
+    -1) and the track records [n, 14]: (pred uint32 [nz, nx], stats (4; the launches are 0)); needs no device"""
+    return _pred(_bind().svh_test_grid_pred, pred, ids, tracks, shape)
+
+
+def device_pred(pred, ids, tracks, shape=None):
+    """TEST ENTRY: the same through the device kernels on a caller's plane and table; stats[3] the launches"""
+    return _pred(_bind().svh_test_grid_pred_device, pred, ids, tracks, shape)
+
+
+def core_pred_slots(pred, T=0, v16=()):
+    """the small functions of csrc/grid_pred_core.h on the host (svh_test_grid_pred_slots): (slot int32 [T] of the poses, radius int32
+    [32] of the slots, ge uint32 [17] the slots whose radius is at least r, disp int32 [n, 32] of the velocities v16 on one axis)"""
+    v = np.ascontiguousarray(v16, np.int32).ravel()
+    slot, radius, ge, disp = np.zeros(max(T, 1), np.int32), np.zeros(32, np.int32), np.zeros(17, np.uint32), np.zeros((max(len(v), 1), 32), np.int32)
+    _check(_bind().svh_test_grid_pred_slots(C.byref(pred), T, slot.ctypes.data, radius.ctypes.data, ge.ctypes.data, v.ctypes.data if len(v) else None,
+                                            len(v), disp.ctypes.data if len(v) else None))
+    return slot[:T].copy(), radius, ge, disp[:len(v)].copy()
+
+
+def core_pred_roll(roll, pred, cell, cost, plane, pot=None, table=None, set_=0, anchor=(0, 0), oa=0, ob=0, pred_off=(0, 0), poses=None):
+    """the scoring with prediction of csrc/grid_pred_core.h on the host (svh_test_grid_pred_roll): the arguments of core_roll, the
+    prediction parameters and the PRED plane uint32 [nz, nx] under pred_off.  With a table: recs int32 [K, 6], scores int64 [K], best;
+    with poses int32 [n, 3] their footprint predictions as mask uint32 [n].  A dict; needs no device"""
+    c = np.ascontiguousarray(cost, np.uint8)
+    nz, nx = c.shape
+    p = None if pot is None else np.ascontiguousarray(pot, np.int32).reshape(nz, nx)
+    w = np.ascontiguousarray(plane, np.uint32).reshape(nz, nx)
+    out = {}
+    S = K = T = 0
+    tp = rp = sp = None
+    best = C.c_int32(-9)
+    if table is not None:
+        t = np.ascontiguousarray(table, np.int32)
+        S, K, T = t.shape[:3]
+        recs, scores = np.zeros((K, ROLL_PRED_RECORD), np.int32), np.zeros(K, np.int64)
+        tp, rp, sp = t.ctypes.data, recs.ctypes.data, scores.ctypes.data
+    q = np.ascontiguousarray(poses if poses is not None else np.zeros((0, 3)), np.int32).reshape(-1, 3)
+    m = np.zeros(len(q), np.uint32)
+    _check(_bind().svh_test_grid_pred_roll(C.byref(roll), C.byref(pred), cell, nx, nz, oa, ob, c.ctypes.data, None if p is None else p.ctypes.data,
+                                           pred_off[0], pred_off[1], w.ctypes.data, tp, S, K, T, set_, anchor[0], anchor[1],
+                                           q.ctypes.data if len(q) else None, len(q), m.ctypes.data if len(q) else None, rp, sp, C.addressof(best)))
+    if table is not None:
+        out.update(recs=recs, scores=scores, best=best.value)
+    if poses is not None:
+        out.update(mask=m)
+    return out
 
 
 def roll_group(longest):
@@ -1238,6 +1339,68 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_objects(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_predict(self, params=None, **kw):
+        """the prediction parameters in force (or `params`) with the fields of kw replaced: slots, stride, poses_per_step, margin,
+        grow16, only_moving"""
+        p = (params if params is not None else self.get_predict()).copy(**kw)
+        _check(self._L.svh_grid_set_predict(self._h, C.byref(p)))
+
+    def get_predict(self):
+        p = PredParams()
+        _check(self._L.svh_grid_get_predict(self._h, C.byref(p)))
+        return p
+
+    def pred_plane(self, device_ptr=None):
+        """(PRED uint32 [nz, nx], the offsets (oa, ob) of the ID frame it lies under); with device_ptr the plane is written there and
+        (None, offsets) returned"""
+        off = np.zeros(2, np.int32)
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_pred_plane(self._h, device_ptr, 1, off.ctypes.data))
+            return None, (int(off[0]), int(off[1]))
+        out = np.zeros((self.nz, self.nx), np.uint32)
+        _check(self._L.svh_grid_get_pred_plane(self._h, out.ctypes.data, 0, off.ctypes.data))
+        return out, (int(off[0]), int(off[1]))
+
+    def pred_stats(self):
+        """PRED_STATS: predicting tracks, source cells, PRED cells with a bit set, launches of the computation"""
+        out = np.zeros(4, np.int64)
+        _check(self._L.svh_grid_get_pred_stats(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def footprint_pred(self, poses=None, device_ptrs=None, n=None):
+        """the slot masks uint32 [n] of poses int32 [n, 3] (ga, gb, k); with device_ptrs = (poses, out) and n both lie on the device
+        and None is returned"""
+        if device_ptrs is not None:
+            _check(self._L.svh_grid_footprint_pred(self._h, device_ptrs[0], n, 1, device_ptrs[1]))
+            return None
+        q = np.ascontiguousarray(poses, np.int32).reshape(-1, 3)
+        out = np.zeros(len(q), np.uint32)
+        _check(self._L.svh_grid_footprint_pred(self._h, q.ctypes.data if len(q) else None, len(q), 0, out.ctypes.data if len(q) else None))
+        return out
+
+    def roll_score_pred(self, anchor_xyz, set_=0, device_ptrs=None, want=(True, True)):
+        """(best, recs int32 [K, 6] in the order of ROLL_PRED_FIELDS, scores int64 [K]) of set `set_` anchored at the cell of a map-frame
+        position, cut by the prediction too; want = (recs, scores): False passes NULL and returns None in its place; with device_ptrs =
+        (recs, scores), either may be None, they are written there and only best is returned"""
+        best = C.c_int32(-9)
+        if device_ptrs is not None:
+            _check(self._L.svh_grid_roll_score_pred(self._h, _xyz(anchor_xyz).ctypes.data, set_, device_ptrs[0], device_ptrs[1], 1, C.addressof(best)))
+            return best.value
+        K = self.candidates()[1]
+        recs, scores = np.zeros((max(K, 1), ROLL_PRED_RECORD), np.int32), np.zeros(max(K, 1), np.int64)
+        _check(self._L.svh_grid_roll_score_pred(self._h, _xyz(anchor_xyz).ctypes.data, set_, recs.ctypes.data if want[0] else None,
+                                                scores.ctypes.data if want[1] else None, 0, C.addressof(best)))
+        return best.value, (recs[:K] if want[0] else None), (scores[:K] if want[1] else None)
+
+    def render_pred(self, mode=RENDER_CLASS, device_ptr=None):
+        """render(mode) with the window cells that PRED covers over it, coloured by their lowest slot"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_pred(self._h, mode, device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_pred(self._h, mode, img.ctypes.data, 0))
         return img
 
     def set_roll(self, params=None, **kw):

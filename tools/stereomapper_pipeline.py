@@ -24,6 +24,7 @@ without the GUI.  Usage:
                                           [--grid-align DIR [--grid-align-apply] [--grid-align-window K,W]]
                                           [--grid-dynamic DIR [--grid-dynamic-params CLEAR,THROUGH,MARGIN,AGE]]
                                           [--grid-objects DIR [--grid-objects-params MIN,MAX,HEIGHT,GATE,MISSED]]
+                                          [--grid-predict DIR [--grid-predict-params SLOTS,STRIDE,MARGIN,GROW16]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -135,6 +136,13 @@ min_size, max_size, min_height in metres, gate in cells and max_missed of svh_gr
 (svh_grid_render_objects: the class image, the kept cells in the colour of their track, bright when it moves, structure grey, the
 centroid and the cell eight steps ahead marked) goes into DIR/objects_%06d.ppm and one line {"frame", "window", "stats", "tracks"} with
 the track table (the fields of svhip.grid.TRACK_FIELDS) is appended to DIR/tracks.jsonl.
+
+--grid-predict DIR: needs --grid-objects and --grid-roll.  After the rollouts of a frame the same nine arcs are scored once more
+against where the tracked objects will be (svh_grid_roll_score_pred; --grid-predict-params SLOTS,STRIDE,MARGIN,GROW16: slots, stride,
+margin and grow16 of svh_grid_pred_params; 8,1,1,0; a pose per track step, moving tracks only).  The image (svh_grid_render_pred: the
+class image with the predicted cells over it, coloured by their first slot) goes into DIR/predict_%06d.ppm and one line {"frame",
+"set", "best", "best_pred", "cut_by_object", "score", "score_pred", "pred_stats"} -- both bests, without and with the prediction, and
+how many arcs a predicted object cut -- is appended to DIR/predict.jsonl.
 
 --grid-dynamic DIR: needs --grid-local.  The local step takes a frame as an OBSERVATION (svh_grid_observe_view_lists) instead of an
 add: the frame's sight lines contradict obstacle cells they pass through at the height of their body, CLEAR contradicting frames in a row
@@ -624,6 +632,7 @@ def main():
     roll_dir, roll_kw = None, {}
     dyn_dir, dyn_kw = None, {}
     obj_dir, obj_kw = None, {}
+    pred_dir, pred_kw = None, {}
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -736,6 +745,19 @@ def main():
             assert 1 <= obj_kw["min_size"] <= obj_kw["max_size"] <= 2 ** 26 and obj_kw["min_height"] >= 0 and 0 <= obj_kw["gate"] <= 64
             assert 0 <= obj_kw["max_missed"] <= 255
             del sys.argv[k:k + 2]
+        if "--grid-predict" in sys.argv:
+            k = sys.argv.index("--grid-predict")
+            pred_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-predict-params" in sys.argv:
+            k = sys.argv.index("--grid-predict-params")
+            v = [int(x) for x in sys.argv[k + 1].split(",")]
+            assert len(v) == 4
+            pred_kw = dict(slots=v[0], stride=v[1], margin=v[2], grow16=v[3])
+            assert 1 <= pred_kw["slots"] <= 32 and 1 <= pred_kw["stride"] <= 64 and 0 <= pred_kw["margin"] <= 16 and 0 <= pred_kw["grow16"] <= 256
+            del sys.argv[k:k + 2]
+        assert (obj_dir and roll_dir) or not pred_dir
+        assert pred_dir or not pred_kw
         assert local_dir or not obj_dir
         assert obj_dir or not obj_kw
         assert local_dir or not dyn_dir
@@ -830,6 +852,9 @@ def main():
     if obj_dir:
         os.makedirs(obj_dir, exist_ok=True)
         open(os.path.join(obj_dir, "tracks.jsonl"), "w").close()
+    if pred_dir:
+        os.makedirs(pred_dir, exist_ok=True)
+        open(os.path.join(pred_dir, "predict.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -854,7 +879,9 @@ def main():
         p.local.set_explore(**explore_kw)
     if roll_dir:
         p.enable_roll(ROLL_CURVATURES, 2.0 * grid_cell, ROLL_POSES, **roll_kw)
-    found = explored = rolled = ranked = aligned = 0
+    if pred_kw:
+        p.local.set_predict(**pred_kw)
+    found = explored = rolled = ranked = aligned = cut_frames = 0
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -904,6 +931,15 @@ def main():
                 f.write(json.dumps({"frame": frames - 1, "set": int(s), "best": int(best), "feasible": int((scores != (1 << 63) - 1).sum()),
                                     "length": int(recs[best, 0]) if best >= 0 else -1, "status": int(recs[best, 1]) if best >= 0 else -1,
                                     "score": int(scores[best]) if best >= 0 else None}) + "\n")
+        if pred_dir:
+            best_p, recs_p, scores_p = p.local.roll_score_pred(p.H_total[:3, 3].copy(), s)
+            cut = int((recs_p[:, 1] == grid.ROLL_CUT_OBJECT).sum())
+            cut_frames += cut > 0
+            view.write_ppm(os.path.join(pred_dir, "predict_%06d.ppm" % (frames - 1)), p.local.render_pred())
+            with open(os.path.join(pred_dir, "predict.jsonl"), "a") as f:
+                f.write(json.dumps({"frame": frames - 1, "set": int(s), "best": int(best), "best_pred": int(best_p), "cut_by_object": cut,
+                                    "score": int(scores[best]) if best >= 0 else None, "score_pred": int(scores_p[best_p]) if best_p >= 0 else None,
+                                    "pred_stats": list(p.local.pred_stats())}) + "\n")
         if front_dir:
             stats, status, cells, cost, img = p.frontier_step()
             explored += status == 0
@@ -954,6 +990,10 @@ def main():
     if roll_dir:
         print("rollouts: %d arcs of %d poses per heading, a feasible one in %d of %d frames; %d images and roll.jsonl in %s" % (
             len(ROLL_CURVATURES), ROLL_POSES, rolled, frames, frames, roll_dir))
+    if pred_dir:
+        q = p.local.get_predict()
+        print("prediction: %d slots of %d steps, margin %d cells growing %d/16 per slot: an arc cut by a predicted object in %d of %d frames; "
+              "%d images and predict.jsonl in %s" % (q.slots, q.stride, q.margin, q.grow16, cut_frames, frames, frames, pred_dir))
     if front_dir:
         print("frontiers: goals from the kept components, a route in %d of %d frames; %d images and frontiers.jsonl in %s" % (
             explored, frames, frames, front_dir))
