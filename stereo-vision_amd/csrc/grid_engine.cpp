@@ -67,6 +67,7 @@ enum FinByte { B_INTENSITY = 0, B_CLASS, B_STATE };                             
 constexpr size_t kTravBytes = 8;                   // per cell: DIST2; g (uint16); FLAGS, COST
 constexpr size_t kPlanBytes = 7;                   // per cell: POT; price (uint16); DIR
 constexpr size_t kFrontBytes = 5;                  // per cell: LABEL; FRONT
+constexpr size_t kPoseBytes = 8;                   // per state: PPOT; price (uint16); PDIR; CF
 // rounds of the relaxation enqueued per wait: a round whose list is empty costs one empty launch, a wait costs a round trip,
 // and the bound on the workgroups of a round grows with its distance from the last known length.  Measured alternating in one
 // process at 1, 2, 4, 8 and 16 (profiles/grid_plan_times.jsonl; ms on an open field of 256^2 / 1024^2 / 8192^2 cells):
@@ -184,33 +185,39 @@ enum Kept : uint32_t {
     REACH = 1u << 4,      // `reach`, from COST and the plan parameters, for the start (reach_ga, reach_gb)
     AFIELD = 1u << 5,     // al.field, from STATE and the align parameters
     OBJ = 1u << 6,        // `obj`, the object table and its statistics, from STATE, HMAX, COUNT and the object parameters
-    UP_TABLE = 1u << 7,   // d_table holds `table`
-    UP_GOALS = 1u << 8,   // d_goals holds `goals`
-    UP_ROLL = 1u << 9,    // roll_bufs.offs and .start hold the footprint table
-    UP_CANDS = 1u << 10,  // d_cands and d_cand_lens hold the candidates
-    ROLL_LAST = 1u << 11, // roll_bufs.recs holds the records of the last svh_grid_roll_score
-    ALIGN_LAST = 1u << 12,// al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
-    PRED = 1u << 13       // pred.plane and its statistics, from the track state and the prediction parameters: not a derived layer, the
+    POSE_CF = 1u << 7,    // the CF planes of `pose`, from COST and the footprint table: a bit of its own, so that new goals or pose
+                          // parameters do not run k_grid_pose_foot again
+    POSE = 1u << 8,       // PPOT, the prices and PDIR of `pose` and their statistics, from CF, the pose parameters and the pose goals
+    UP_TABLE = 1u << 9,   // d_table holds `table`
+    UP_GOALS = 1u << 10,  // d_goals holds `goals`
+    UP_ROLL = 1u << 11,   // roll_bufs.offs and .start hold the footprint table
+    UP_CANDS = 1u << 12,  // d_cands and d_cand_lens hold the candidates
+    ROLL_LAST = 1u << 13, // roll_bufs.recs holds the records of the last svh_grid_roll_score
+    ALIGN_LAST = 1u << 14,// al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
+    PRED = 1u << 15,      // pred.plane and its statistics, from the track state and the prediction parameters: not a derived layer, the
                           // accumulators do not reach it
+    UP_POSE_GOALS = 1u << 16   // d_pose_goals holds `pose_goals`
 };
-constexpr int kLayers = 7;
+constexpr int kLayers = 9;
 constexpr uint32_t kAllLayers = (1u << kLayers) - 1;
 // the layers each derived layer is computed from, by the layer's bit number
-constexpr uint32_t kNeeds[kLayers] = {0, FINAL, TRAV, TRAV, TRAV, FINAL, FINAL};
+constexpr uint32_t kNeeds[kLayers] = {0, FINAL, TRAV, TRAV, TRAV, FINAL, FINAL, TRAV, POSE_CF};
 // what changes, and what it makes stale directly; the layers computed from a stale layer follow by closure()
-enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, OBJ_PARAMS, TRACKS, PRED_PARAMS, SOURCES };
+enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, OBJ_PARAMS, TRACKS, PRED_PARAMS, POSE_PARAMS, POSE_GOALS, SOURCES };
 constexpr uint32_t kDrops[SOURCES] = {
     FINAL,                    // ACC: the accumulators or the window's offsets
     TRAV | UP_TABLE,          // TRAV_PARAMS
     PLAN | REACH,             // PLAN_PARAMS
     PLAN | UP_GOALS,          // GOALS
     FRONT,                    // FRONT_PARAMS
-    UP_ROLL | ROLL_LAST,      // ROLL_PARAMS
+    UP_ROLL | ROLL_LAST | POSE_CF,   // ROLL_PARAMS: the footprint table, stop_cost and unknown_cost reach CF and the prices
     UP_CANDS | ROLL_LAST,     // CANDS: the candidate table
     AFIELD | ALIGN_LAST,      // ALIGN_PARAMS
     OBJ,                      // OBJ_PARAMS
     PRED,                     // TRACKS: the track table or the ID plane: a step, or anything that empties the tracks
     PRED,                     // PRED_PARAMS
+    POSE,                     // POSE_PARAMS
+    POSE | UP_POSE_GOALS,     // POSE_GOALS
 };
 constexpr uint32_t closure(uint32_t m) {
     for (int pass = 0; pass < kLayers; pass++)
@@ -228,13 +235,17 @@ constexpr StaleTable stale_table() {
 }
 constexpr StaleTable kStale = stale_table();
 static_assert((kStale.of[ACC] & kAllLayers) == kAllLayers, "a derived layer without a path to FINAL in kNeeds would survive a change of the accumulators");
-static_assert(kStale.of[TRAV_PARAMS] == (TRAV | PLAN | FRONT | REACH | UP_TABLE), "the closure of kNeeds");
+static_assert(kStale.of[TRAV_PARAMS] == (TRAV | PLAN | FRONT | REACH | POSE_CF | POSE | UP_TABLE), "the closure of kNeeds");
+static_assert(kStale.of[ROLL_PARAMS] == (UP_ROLL | ROLL_LAST | POSE_CF | POSE) && kStale.of[POSE_PARAMS] == POSE && kStale.of[POSE_GOALS] == (POSE | UP_POSE_GOALS),
+              "the pose field follows the vehicle, its own parameters and its own goals");
+static_assert(!((kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[OBJ_PARAMS] |
+                 kStale.of[TRACKS] | kStale.of[PRED_PARAMS]) & (POSE | POSE_CF)), "the planner, the candidates, the objects and the prediction leave the pose field alone");
 static_assert(kStale.of[OBJ_PARAMS] == OBJ && (kStale.of[ACC] & OBJ), "the objects follow the accumulators and their own parameters");
 static_assert(!((kStale.of[TRAV_PARAMS] | kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[ROLL_PARAMS] |
-                 kStale.of[CANDS] | kStale.of[ALIGN_PARAMS]) & OBJ), "no other layer's source makes the objects stale");
+                 kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[POSE_PARAMS] | kStale.of[POSE_GOALS]) & OBJ), "no other layer's source makes the objects stale");
 static_assert(kStale.of[TRACKS] == PRED && kStale.of[PRED_PARAMS] == PRED, "the prediction follows the tracks and its own parameters");
 static_assert(!((kStale.of[ACC] | kStale.of[TRAV_PARAMS] | kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[ROLL_PARAMS] |
-                 kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[OBJ_PARAMS]) & PRED), "nothing else makes the prediction stale");
+                 kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[OBJ_PARAMS] | kStale.of[POSE_PARAMS] | kStale.of[POSE_GOALS]) & PRED), "nothing else makes the prediction stale");
 
 }  // namespace
 
@@ -329,6 +340,14 @@ struct svh_grid {
     grid::PredParams prp{8, 1, 1, 1, 0, 1};   // the prediction: parameters, PRED
     PredBufs pred;
     int32_t pred_launches = 0;  // PRED: the launches of the computation that produced it
+    grid::PoseParams pose_prm{50, 0x7FFFFFFE, 100, -1, -1};   // the pose planner: parameters, the goal triples as global cells
+    std::vector<int32_t> pose_goals;
+    HipBuf<int32_t> d_pose_goals;
+    HipBuf<uint8_t> pose;       // kPoseBytes per state, 8 states per cell: PPOT | price | PDIR | CF, heading-major planes; first use
+    HipBuf<uint32_t> pose_tiles, pose_ctl;   // as plan_tiles and plan_ctl
+    PinnedBuf<uint32_t> h_pose_ctl;
+    int64_t pose_counted = 0, pose_reached = 0, pose_rounds = 0;   // of the field that is valid
+    HipBuf<int32_t> d_pose_path;   // the poses a walk writes, or a caller's for the pose image
 
     grid::Cells cells() const {
         uint8_t* b = acc.p;
@@ -349,6 +368,10 @@ struct svh_grid {
     int32_t* r_pot() const { return (int32_t*)reach.p; }
     int32_t* f_label() const { return (int32_t*)front.p; }
     uint8_t* f_flags() const { return front.p + 4 * ncells; }
+    int32_t* q_pot() const { return (int32_t*)pose.p; }
+    uint16_t* q_price() const { return (uint16_t*)(pose.p + 32 * ncells); }
+    uint8_t* q_dir() const { return pose.p + 48 * ncells; }
+    uint8_t* q_cf() const { return pose.p + 56 * ncells; }
     int32_t* o_label() const { return (int32_t*)obj.p; }
     uint8_t* o_flags() const { return obj.p + 4 * ncells; }
     grid::DynPlanes dplanes() const {
@@ -394,7 +417,7 @@ int failed(svh_grid* g, int rc, uint32_t kept = 0) {
     return rc;
 }
 // what each family of entries drops there
-constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST, kObjects = OBJ, kPrediction = PRED;
+constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST, kObjects = OBJ, kPrediction = PRED, kPose = POSE | POSE_CF;
 
 // the tracks are empty and the ids start again at 0
 void forget_tracks(svh_grid* g) {
@@ -771,6 +794,8 @@ int render_cost(svh_grid* g, uint8_t* rgb, bool on_device) {
 void forget_goals(svh_grid* g) {
     g->goals.clear();
     touch(g, GOALS);
+    g->pose_goals.clear();   // the pose planner's too: svh_grid_clear and svh_grid_set_window end a scene for both
+    touch(g, POSE_GOALS);
 }
 
 size_t plan_tiles(const grid::Params& p) {
@@ -781,22 +806,30 @@ size_t plan_tiles(const grid::Params& p) {
 // words come back through `h_ctl` (pinned) and the host waits.  The kernel strides over its list, so the number of workgroups
 // is a matter of speed alone: a tile of round r + k lies within k tiles of one of round r, so (2 k + 1)^2 times the known
 // length bounds the list.  Three bounds keep a bug from hanging: the sweeps of a tile, these rounds, the walk.
-int plan_rounds(hipStream_t s, const grid::PlanJob& j, uint32_t* h_ctl) {
-    const uint64_t tiles = (uint64_t)grid::plan_tiles_x(j) * grid::plan_tiles_y(j);
-    const uint64_t limit = (uint64_t)j.nx * (uint64_t)j.nz + 2;
-    uint64_t known = std::min<uint64_t>(tiles, 4 * (uint64_t)j.n_goals);   // a goal's 3 x 3 cells touch at most four tiles
+// The loop serves the planner and the pose planner alike: `relax(round, blocks)` launches one round of whichever, over `tiles`
+// tiles seeded by `n_goals` goals, with the control words `ctl` (PlanCtl) and at most `limit` rounds; `unsettled` is what it says of a
+// relaxation that goes beyond them.
+template <typename Relax>
+int relax_rounds(hipStream_t s, uint64_t tiles, uint64_t limit, uint64_t n_goals, const uint32_t* ctl, uint32_t* h_ctl, const char* unsettled, Relax relax) {
+    uint64_t known = std::min<uint64_t>(tiles, 4 * n_goals);   // a goal's 3 x 3 cells touch at most four tiles
     for (uint64_t round = 0; known > 0;) {
-        if (round >= limit) return svh::fail(SVH_ERR_HIP, "Grid: the relaxation of the plan did not settle within nx * nz + 2 rounds");
+        if (round >= limit) return svh::fail(SVH_ERR_HIP, unsettled);
         for (int k = 0, per_wait = g_rounds_per_wait; k < per_wait; k++, round++) {
             const uint64_t reach = (uint64_t)(2 * k + 1) * (uint64_t)(2 * k + 1);
-            grid::launch_plan_relax(s, j, (uint32_t)round, (uint32_t)std::min(tiles, known * reach));
+            relax((uint32_t)round, (uint32_t)std::min(tiles, known * reach));
         }
         GRID_TRY(launch, hipGetLastError());
-        GRID_TRY(copy, hipMemcpyAsync(h_ctl, j.ctl, grid::CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(h_ctl, ctl, grid::CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         GRID_TRY(wait, hipStreamSynchronize(s));
         known = h_ctl[grid::CTL_LEN + round % 3];   // the list of the round to come
     }
     return SVH_OK;
+}
+
+int plan_rounds(hipStream_t s, const grid::PlanJob& j, uint32_t* h_ctl) {
+    return relax_rounds(s, (uint64_t)grid::plan_tiles_x(j) * grid::plan_tiles_y(j), (uint64_t)j.nx * (uint64_t)j.nz + 2, (uint64_t)j.n_goals, j.ctl, h_ctl,
+                        "Grid: the relaxation of the plan did not settle within nx * nz + 2 rounds",
+                        [&](uint32_t round, uint32_t blocks) { grid::launch_plan_relax(s, j, round, blocks); });
 }
 
 // seed, rounds, DIR on buffers that exist; the control words of the finished field are in h_ctl when it returns
@@ -1299,6 +1332,202 @@ int render_roll(svh_grid* g, uint8_t* rgb, bool on_device) {
     });
 }
 
+// ---- the pose planner -------------------------------------------------------------------------------------------------------
+size_t pose_tiles(int32_t nx, int32_t nz) {
+    return ((size_t)(nx + grid::POSE_TILE - 1) / grid::POSE_TILE) * ((size_t)(nz + grid::POSE_TILE - 1) / grid::POSE_TILE);
+}
+
+// a job on a footprint table that lies on the device, with the bounding boxes of the eight lists a planning heading has; the planes,
+// the goals and the lists are the caller's to fill in
+grid::PoseJob pose_job(const grid::PoseParams& pp, const RollTable& t, const RollBufs& b, int32_t nx, int32_t nz, int32_t oa, int32_t ob) {
+    grid::PoseJob j{};
+    j.pp = pp;
+    j.stop_cost = t.p.stop_cost, j.unknown_cost = t.p.unknown_cost, j.m = t.p.m;
+    j.nx = nx, j.nz = nz, j.oa = oa, j.ob = ob;
+    j.offs = (const int2*)b.offs.p, j.start = b.start.p;
+    for (int32_t d = 0; d < grid::POSE_HEADINGS; d++) {
+        int32_t* box = j.box[d];
+        box[0] = box[1] = box[2] = box[3] = 0;      // (0, 0) is in every list
+        for (int64_t i = t.start[(size_t)d * t.p.m]; i < t.start[(size_t)d * t.p.m + 1]; i++) {
+            const int32_t da = t.offs[2 * i], db = t.offs[2 * i + 1];
+            box[0] = std::min(box[0], da), box[1] = std::max(box[1], da), box[2] = std::min(box[2], db), box[3] = std::max(box[3], db);
+        }
+    }
+    return j;
+}
+
+// the planes of a job in one buffer of kPoseBytes per state, and the tile lists
+void pose_planes(grid::PoseJob& j, uint8_t* field, uint32_t* tiles, uint32_t* ctl) {
+    const size_t cells = (size_t)j.nx * (size_t)j.nz, n_tiles = pose_tiles(j.nx, j.nz);
+    j.pot = (int32_t*)field, j.price = (uint16_t*)(field + 32 * cells), j.dir = field + 48 * cells, j.cf = field + 56 * cells;
+    j.lists = tiles, j.flags = tiles + 2 * n_tiles;
+    j.ctl = ctl;
+}
+
+// seed, rounds, PDIR on a job whose CF planes are written (in stream order); the control words of the finished field are in h_ctl
+// when it returns
+int pose_run(hipStream_t s, const grid::PoseJob& j, uint32_t* h_ctl) {
+    const size_t tiles = pose_tiles(j.nx, j.nz);
+    GRID_TRY(copy, hipMemsetAsync(j.flags, 0, 2 * tiles * sizeof(uint32_t), s));
+    GRID_TRY(copy, hipMemsetAsync(j.ctl, 0, grid::CTL_WORDS * sizeof(uint32_t), s));
+    GRID_TRY(launch, (grid::launch_pose_seed(s, j), hipGetLastError()));
+    const int rc = relax_rounds(s, tiles, (uint64_t)grid::POSE_HEADINGS * (uint64_t)j.nx * (uint64_t)j.nz + 2, (uint64_t)j.n_goals, j.ctl, h_ctl,
+                                "Grid: the relaxation of the pose field did not settle within 8 * nx * nz + 2 rounds",
+                                [&](uint32_t round, uint32_t blocks) { grid::launch_pose_relax(s, j, round, blocks); });
+    if (rc) return rc;
+    GRID_TRY(launch, (grid::launch_pose_dir(s, j), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(h_ctl, j.ctl, grid::CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    return SVH_OK;
+}
+
+grid::PoseJob pose_job(const svh_grid* g) {
+    grid::PoseJob j = pose_job(g->pose_prm, g->rol, g->roll_bufs, g->prm.nx, g->prm.nz, g->prm.oa, g->prm.ob);
+    j.cost = g->t_cost();
+    pose_planes(j, g->pose.p, g->pose_tiles.p, g->pose_ctl.p);
+    j.goals = g->d_pose_goals.p, j.n_goals = (int32_t)(g->pose_goals.size() / 3);
+    return j;
+}
+
+// the buffers of the layer exist
+int pose_ready(svh_grid* g) {
+    GRID_GROW(g->pose, g->ncells * grid::POSE_HEADINGS * kPoseBytes);
+    GRID_GROW(g->pose_tiles, 4 * pose_tiles(g->prm.nx, g->prm.nz) * sizeof(uint32_t));
+    GRID_GROW(g->pose_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+    GRID_GROW(g->h_pose_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+    return SVH_OK;
+}
+
+// CF is valid or launched: the cost planes and the footprint table, then one launch, pending until the caller has waited and settles
+int pose_foot(svh_grid* g) {
+    if (has(g, POSE_CF) || (g->pending & POSE_CF)) return SVH_OK;
+    int rc = pose_ready(g);
+    if (rc || (rc = roll_tables(g, false)) || (rc = traverse(g))) return rc;
+    GRID_TRY(launch, (grid::launch_pose_foot(g->stream, pose_job(g)), hipGetLastError()));
+    g->pending |= POSE_CF;
+    return SVH_OK;
+}
+
+// the field is valid: CF, then seed, rounds and PDIR; complete when it returns
+int pose_field(svh_grid* g) {
+    if (has(g, POSE)) return SVH_OK;
+    int rc = pose_foot(g);
+    if (rc) return rc;
+    const size_t n = g->pose_goals.size();
+    if (!has(g, UP_POSE_GOALS) && n > 0) {
+        GRID_GROW_N(g->d_pose_goals, n);
+        GRID_GROW(g->h_cells, n * sizeof(int32_t));
+        memcpy(g->h_cells, g->pose_goals.data(), n * sizeof(int32_t));
+        GRID_TRY(copy, hipMemcpyAsync(g->d_pose_goals, g->h_cells, n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));   // the staging buffer is free again
+    }
+    g->valid |= UP_POSE_GOALS;
+    if ((rc = pose_run(g->stream, pose_job(g), g->h_pose_ctl))) return rc;
+    const uint32_t* h = g->h_pose_ctl;
+    g->pose_counted = h[grid::CTL_COUNTED], g->pose_rounds = h[grid::CTL_ROUNDS];
+    g->pose_reached = (int64_t)((uint64_t)h[grid::CTL_REACHED] | ((uint64_t)h[grid::CTL_REACHED + 1] << 32));
+    g->pending |= POSE;
+    settle(g);
+    return SVH_OK;
+}
+
+int get_pose_plane(svh_grid* g, int32_t plane, void* out, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    const size_t states = g->ncells * grid::POSE_HEADINGS;
+    if (plane == grid::PP_CF) {
+        if ((rc = pose_foot(g)) || (rc = deliver(g, g->q_cf(), states, out, on_device))) return rc;
+        settle(g);
+        return SVH_OK;
+    }
+    if ((rc = pose_field(g))) return rc;
+    return plane == grid::PP_POT ? deliver(g, g->q_pot(), states * 4, out, on_device) : deliver(g, g->q_dir(), states, out, on_device);
+}
+
+// the walk from the window state (a, b, d)
+int pose_path(svh_grid* g, int32_t a, int32_t b, int32_t d, int32_t* poses, int64_t cap, int64_t* len, int32_t* cost, int32_t* status) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = pose_field(g))) return rc;
+    const int64_t room = std::min<int64_t>(cap, (int64_t)g->ncells * grid::POSE_HEADINGS);   // a path has at most 8 nx nz poses
+    GRID_GROW_N(g->d_pose_path, 3 * room);
+    GRID_GROW(g->d_walk, 3 * sizeof(int64_t));
+    GRID_GROW(g->h_walk, 3 * sizeof(int64_t));
+    GRID_TRY(launch, (grid::launch_pose_walk(g->stream, pose_job(g), a, b, d, g->d_pose_path, room, g->d_walk), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(g->h_walk, g->d_walk, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    const int64_t n = g->h_walk[1], m = std::min(n, room);
+    if (m > 0 && (rc = deliver(g, g->d_pose_path, (size_t)m * 3 * sizeof(int32_t), poses, false))) return rc;
+    *status = (int32_t)g->h_walk[0], *len = n, *cost = (int32_t)g->h_walk[2];
+    return SVH_OK;
+}
+
+int render_pose(svh_grid* g, const int32_t* poses, int64_t n, uint8_t* rgb, bool on_device) {
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        int rc = pose_field(g);
+        if (rc) return rc;
+        if (n > 0) {
+            const size_t bytes = (size_t)n * 3 * sizeof(int32_t);
+            GRID_GROW(g->d_pose_path, bytes);
+            GRID_GROW(g->h_cells, bytes);
+            memcpy(g->h_cells, poses, bytes);
+            GRID_TRY(copy, hipMemcpyAsync(g->d_pose_path, g->h_cells, bytes, hipMemcpyHostToDevice, g->stream));
+            GRID_TRY(wait, hipStreamSynchronize(g->stream));   // the staging buffer is free again
+        }
+        const grid::PoseJob pj = pose_job(g);
+        grid::launch_render_cost(g->stream, cost_job(g, dst));
+        grid::launch_pose_overlay(g->stream, pj, pj.goals, pj.n_goals, true, dst);
+        grid::launch_pose_overlay(g->stream, pj, g->d_pose_path, n, false, dst);
+        return rc;
+    });
+}
+
+// the planes of a test entry on the device and the kernels on them: CF, PPOT and PDIR to the host, out as svh_grid_get_pose_stats
+// without the goals given
+int pose_device(const grid::PoseParams& pp, const RollTable& t, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost, const int32_t* goals,
+                int32_t n, uint8_t* cf, int32_t* pot, uint8_t* dir, int64_t out[3]) {
+    const size_t cells = (size_t)nx * (size_t)nz, states = cells * grid::POSE_HEADINGS, tiles = pose_tiles(nx, nz);
+    HipBuf<uint8_t> d_cost, field;
+    HipBuf<int32_t> d_goals;
+    HipBuf<uint32_t> d_tiles, d_ctl;
+    PinnedBuf<uint32_t> h_ctl;
+    RollBufs b;
+    hipStream_t s = nullptr;
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(d_cost, cells);
+        GRID_GROW(field, states * kPoseBytes);
+        GRID_GROW_N(d_goals, 3 * (size_t)n);
+        GRID_GROW(d_tiles, 4 * tiles * sizeof(uint32_t));
+        GRID_GROW(d_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+        GRID_GROW(h_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+        GRID_TRY(copy, hipMemcpyAsync(d_cost, cost, cells, hipMemcpyHostToDevice, s));
+        if (n > 0) GRID_TRY(copy, hipMemcpyAsync(d_goals, goals, 3 * (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        int r = send_roll_table(s, t, b);
+        if (r) return r;
+        grid::PoseJob j = pose_job(pp, t, b, nx, nz, oa, ob);
+        j.cost = d_cost.p;
+        pose_planes(j, field.p, d_tiles.p, d_ctl.p);
+        j.goals = d_goals.p, j.n_goals = n;
+        GRID_TRY(launch, (grid::launch_pose_foot(s, j), hipGetLastError()));
+        if ((r = pose_run(s, j, h_ctl))) return r;
+        GRID_TRY(copy, hipMemcpyAsync(cf, j.cf, states, hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(pot, j.pot, states * 4, hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(dir, j.dir, states, hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    out[0] = h_ctl.p[grid::CTL_COUNTED];
+    out[1] = (int64_t)((uint64_t)h_ctl.p[grid::CTL_REACHED] | ((uint64_t)h_ctl.p[grid::CTL_REACHED + 1] << 32));
+    out[2] = h_ctl.p[grid::CTL_ROUNDS];
+    return SVH_OK;
+}
+
 // ---- the prediction ---------------------------------------------------------------------------------------------------------
 bool convert_pred(const svh_grid_pred_params* p, grid::PredParams* q) {
     if (!p) return false;
@@ -1533,6 +1762,30 @@ bool roll_test_args(const svh_grid_roll_params* p, float cell, int32_t nx, int32
 }
 
 const char* const kNoTrav =": the default traversability does not fit this grid's cell; set one (svh_grid_set_traversability)";
+
+// what every entry that computes the pose planner's layer refuses; nullptr: nothing
+const char* pose_refusal(const svh_grid* g) {
+    if (!g->trav_ok) return kNoTrav;
+    if (!g->rol.R) return kNoRoll;
+    if ((int64_t)g->ncells > grid::POSE_MAX_CELLS) return ": the window has more than 2^24 cells, PPOT would exceed 512 MiB";
+    return nullptr;
+}
+
+// the checks that svh_test_grid_pose and svh_test_grid_pose_device share; the parameters to `q` and `pp`, the vehicle's table to `t`
+bool pose_test_args(const svh_grid_roll_params* r, const svh_grid_pose_params* p, float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob,
+                    const uint8_t* cost, const int32_t* goals, int32_t n, const void* cf, const void* pot, const void* dir, grid::RollParams* q,
+                    grid::PoseParams* pp, std::shared_ptr<const RollTable>* t) {
+    if (!p || !convert_roll(r, q) || !(grid::finite_f(cell) && cell > 0.f) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE ||
+        (int64_t)nx * nz > grid::POSE_MAX_CELLS || !grid::offsets_ok(oa, ob) || !cost || n < 0 || n > grid::POSE_MAX_GOALS || (n > 0 && !goals) || !cf ||
+        !pot || !dir)
+        return false;
+    *pp = grid::PoseParams{p->neutral, p->max_cost, p->turn, p->reverse, p->spin};
+    if (!grid::pose_ok(*pp)) return false;
+    for (int32_t k = 0; k < n; k++)
+        if (!grid::pose_goal_ok(goals + 3 * k)) return false;
+    *t = roll_table_for(*q, cell);
+    return *t != nullptr;
+}
 
 // ---- the exploration layer ------------------------------------------------------------------------------------------------
 const char* const kNoExplore =": the default range does not fit this grid's cell; set one (svh_grid_set_explore)";
@@ -2564,6 +2817,102 @@ int32_t svh_grid_render_roll(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     return failed(g, render_roll(g, rgb, on_device != 0));
 }
 
+void svh_grid_pose_params_default(svh_grid_pose_params* p) {
+    if (!p) return;
+    p->neutral = 50, p->max_cost = 0x7FFFFFFE, p->turn = 100, p->reverse = -1, p->spin = -1;
+}
+
+int32_t svh_grid_set_pose(svh_grid* g, const svh_grid_pose_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_pose: null argument");
+    const grid::PoseParams q{p->neutral, p->max_cost, p->turn, p->reverse, p->spin};
+    if (!grid::pose_ok(q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_pose: parameters out of range (include/svh_grid_pose.h)");
+    g->pose_prm = q;
+    touch(g, POSE_PARAMS);
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_pose(svh_grid* g, svh_grid_pose_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_pose: null argument");
+    const grid::PoseParams& q = g->pose_prm;
+    p->neutral = q.neutral, p->max_cost = q.max_cost, p->turn = q.turn, p->reverse = q.reverse, p->spin = q.spin;
+    return SVH_OK;
+}
+
+int32_t svh_grid_pose_set_goals(svh_grid* g, const int32_t* triples, int32_t n) {
+    if (!g || n < 0 || n > grid::POSE_MAX_GOALS || (n > 0 && !triples))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_pose_set_goals: a grid and 0..65536 goals are needed");
+    for (int32_t k = 0; k < n; k++)
+        if (!grid::pose_goal_ok(triples + 3 * k))
+            return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_pose_set_goals: a goal's cell is not below 2^20, or its heading not in -1..7");
+    g->pose_goals.assign(triples, triples + 3 * (size_t)n);
+    touch(g, POSE_GOALS);
+    return SVH_OK;
+}
+
+int32_t svh_grid_pose_set_goal(svh_grid* g, const double xyz[3], int32_t d) {
+    float p[3];
+    int32_t t[3];
+    if (!g || !position(xyz, p) || !grid::global_cell(g->prm, p[0], p[1], p[2], &t[0], &t[1]))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_pose_set_goal: a grid and a finite position with a cell below 2^20 are needed");
+    t[2] = d;
+    return svh_grid_pose_set_goals(g, t, 1);
+}
+
+int32_t svh_grid_get_pose_plane(svh_grid* g, int32_t plane, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::PP_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_pose_plane: a grid, a plane 0..2 and an output are needed");
+    if (on_device && plane == grid::PP_POT && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_pose_plane: a device array of PPOT must be 4-byte aligned");
+    if (const char* why = pose_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_pose_plane") + why);
+    return failed(g, get_pose_plane(g, plane, out, on_device != 0), kPose);
+}
+
+int32_t svh_grid_get_pose_stats(svh_grid* g, int64_t out[4]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_pose_stats: null argument");
+    if (const char* why = pose_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_pose_stats") + why);
+    int rc = ready(g);
+    if (!rc) rc = pose_field(g);
+    if (rc) return failed(g, rc, kPose);
+    out[0] = (int64_t)(g->pose_goals.size() / 3), out[1] = g->pose_counted, out[2] = g->pose_reached, out[3] = g->pose_rounds;
+    return SVH_OK;
+}
+
+int32_t svh_grid_pose_heading_of(svh_grid* g, const double dir_xyz[3], int32_t* d) {
+    float v[3];
+    if (!g || !d || !position(dir_xyz, v)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_pose_heading_of: a grid, an output and a finite direction are needed");
+    const float* T = g->prm.T;
+    const float ua = (T[0] * v[0] + T[1] * v[1]) + T[2] * v[2], ub = (T[4] * v[0] + T[5] * v[1]) + T[6] * v[2];
+    const int32_t h = grid::heading_of(1, ua, ub);
+    if (h < 0) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_pose_heading_of: the direction has no heading: it is zero on the ground, or not finite there");
+    *d = h;
+    return SVH_OK;
+}
+
+int32_t svh_grid_pose_path(svh_grid* g, const double start_xyz[3], int32_t d, int32_t* poses, int64_t cap, int64_t* len, int32_t* cost) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || !len || !cost || cap < 0 || (cap > 0 && !poses) || d < 0 || d >= grid::POSE_HEADINGS || !position(start_xyz, p) ||
+        !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_pose_path: a grid, outputs, a heading 0..7 and a finite start with a cell below 2^20 are needed");
+    if (const char* why = pose_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_pose_path") + why);
+    const int64_t a = (int64_t)ga - g->prm.oa, b = (int64_t)gb - g->prm.ob;
+    if (a < 0 || a >= g->prm.nx || b < 0 || b >= g->prm.nz) {
+        *len = 0, *cost = grid::PLAN_FAR;
+        return grid::PATH_OUTSIDE;
+    }
+    int64_t n = 0;
+    int32_t c = grid::PLAN_FAR, status = 0;
+    const int rc = failed(g, pose_path(g, (int32_t)a, (int32_t)b, d, poses, cap, &n, &c, &status), kPose);
+    if (rc) return rc;
+    *len = n, *cost = c;
+    return status;
+}
+
+int32_t svh_grid_render_pose(svh_grid* g, const int32_t* poses, int64_t n, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb || n < 0 || n > (int64_t)grid::POSE_HEADINGS * (int64_t)g->ncells || (n > 0 && !poses))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_pose: a grid, 0..8 nx nz poses (the longest path) and an output are needed");
+    if (const char* why = pose_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_pose") + why);
+    return failed(g, render_pose(g, poses, n, rgb, on_device != 0), kPose);
+}
+
 void svh_grid_explore_params_default(svh_grid_explore_params* p) {
     if (!p) return;
     p->range = 10.f, p->min_gain = 1, p->w_gain = 500, p->w_reach = 1;
@@ -3590,6 +3939,47 @@ int32_t svh_test_grid_plan_device(int32_t nx, int32_t nz, const svh_grid_plan_pa
     out[1] = (int64_t)((uint64_t)h_ctl.p[grid::CTL_REACHED] | ((uint64_t)h_ctl.p[grid::CTL_REACHED + 1] << 32));
     out[2] = h_ctl.p[grid::CTL_ROUNDS];
     return SVH_OK;
+}
+
+// grid_pose_core.h on the host: CF, PPOT and PDIR (8 planes each, heading-major) of a window of nx x nz cells from its COST plane,
+// the vehicle of `r` on cells of side `cell` and n goal triples (global cells under the offsets oa, ob), by the loops of the header;
+// *counted the goal states that count.  Needs no device
+int32_t svh_test_grid_pose(const svh_grid_roll_params* r, const svh_grid_pose_params* p, float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob,
+                           const uint8_t* cost, const int32_t* goals, int32_t n, uint8_t* cf, int32_t* pot, uint8_t* dir, int64_t* counted) {
+    grid::RollParams q;
+    grid::PoseParams pp;
+    std::shared_ptr<const RollTable> t;
+    if (!counted || !pose_test_args(r, p, cell, nx, nz, oa, ob, cost, goals, n, cf, pot, dir, &q, &pp, &t))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pose: bad arguments");
+    grid::pose_cf_window(nx, nz, cost, t->offs.data(), t->start.data(), q.m, q.unknown_cost, cf);
+    *counted = grid::pose_window(pp, q.stop_cost, nx, nz, oa, ob, cf, goals, n, pot, dir);
+    return SVH_OK;
+}
+
+// grid_pose_core.h's walk over a PDIR field from the window state (a, b, d): *len poses (0: outside, or PDIR leads nowhere), the
+// first min(*len, cap) of them as (global cell, d m).  Needs no device
+int32_t svh_test_grid_pose_walk(int32_t nx, int32_t nz, int32_t oa, int32_t ob, int32_t m, const uint8_t* dir, int32_t a, int32_t b, int32_t d,
+                                int32_t* poses, int64_t cap, int64_t* len) {
+    if (nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || !grid::offsets_ok(oa, ob) || m < 1 || m > grid::ROLL_MAX_M || !dir || cap < 0 ||
+        (cap > 0 && !poses) || !len)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pose_walk: bad arguments");
+    *len = grid::pose_walk(nx, nz, oa, ob, m, dir, a, b, d, poses, cap);
+    return SVH_OK;
+}
+
+// the same field through the kernels and the round loop: out[0] the goal states that counted, out[1] the states reached, out[2] the rounds
+int32_t svh_test_grid_pose_device(const svh_grid_roll_params* r, const svh_grid_pose_params* p, float cell, int32_t nx, int32_t nz, int32_t oa,
+                                  int32_t ob, const uint8_t* cost, const int32_t* goals, int32_t n, uint8_t* cf, int32_t* pot, uint8_t* dir,
+                                  int64_t out[3]) {
+    grid::RollParams q;
+    grid::PoseParams pp;
+    std::shared_ptr<const RollTable> t;
+    if (!out || !pose_test_args(r, p, cell, nx, nz, oa, ob, cost, goals, n, cf, pot, dir, &q, &pp, &t))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_pose_device: bad arguments");
+    svh::ensure_init();
+    RollTable own = *t;   // the table is that of the vehicle; the costs are this call's
+    own.p = q;
+    return pose_device(pp, own, nx, nz, oa, ob, cost, goals, n, cf, pot, dir, out);
 }
 
 // grid_core.h's traversability layer on the host: the planes of a window of p->nx x p->nz cells from CLASS, HMEAN and STATE;

@@ -1,6 +1,6 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
 // csrc/grid_front_kernels.hip / csrc/grid_obj_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_pred_kernels.hip /
-// csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip / csrc/grid_dyn_kernels.hip: the launches of the
+// csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip / csrc/grid_dyn_kernels.hip / csrc/grid_pose_kernels.hip: the launches of the
 // ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
@@ -15,6 +15,7 @@
 #include "grid_front_core.h"
 #include "grid_obj_core.h"
 #include "grid_plan_core.h"
+#include "grid_pose_core.h"
 #include "grid_pred_core.h"
 #include "grid_roll_core.h"
 
@@ -172,6 +173,49 @@ void launch_plan_dir(hipStream_t s, const PlanJob& j);
 void launch_plan_walk(hipStream_t s, const PlanJob& j, int32_t a, int32_t b, int32_t* cells, int64_t cap, int64_t* out);
 // n global cells drawn into an image of svh_grid_render_cost's layout: a path, or (goals) only those that count
 void launch_plan_overlay(hipStream_t s, const PlanJob& j, const int32_t* cells, int64_t n, bool goals, uint8_t* rgb);
+
+// The pose planner (csrc/grid_pose_kernels.hip): the finished COST plane, the footprint table and the goal states -> CF, PPOT, PDIR,
+// a pose path.  The tile lists, their flags and the control words are the planner's (PlanCtl), over tiles of POSE_TILE x POSE_TILE
+// cells x 8 headings.
+constexpr int32_t POSE_TILE = 16;                // k_grid_pose_relax: one workgroup per active tile, one lane per cell, 8 states each
+constexpr uint32_t POSE_BLOCK = 256;
+static_assert(POSE_TILE * POSE_TILE == (int32_t)POSE_BLOCK, "a tile is one pass of 256 lanes");
+constexpr int32_t FOOT_TILE = 16;                // k_grid_pose_foot: one workgroup per tile of cells and heading, one lane per cell
+constexpr uint32_t FOOT_LDS = 32 * 1024;         // ... the bytes of r(COST) it stages at most (grid_pose_kernels.hip)
+
+struct PoseJob {
+    PoseParams pp;
+    int32_t stop_cost, unknown_cost, m;   // of the rollouts
+    int32_t nx, nz, oa, ob;
+    const uint8_t* cost;        // the finished COST plane
+    const int2* offs;           // the footprint table on the device
+    const int32_t* start;
+    int32_t box[POSE_HEADINGS][4];   // per planning heading the bounding box of its list: min da, max da, min db, max db
+    uint8_t* cf;                // 8 * nx * nz each, heading-major
+    uint16_t* price;
+    int32_t* pot;
+    uint8_t* dir;
+    const int32_t* goals;       // n_goals triples (ga, gb, d)
+    int32_t n_goals;
+    uint32_t* lists;            // 2 * tiles
+    uint32_t* flags;            // 2 * tiles
+    uint32_t* ctl;              // CTL_WORDS
+};
+inline uint32_t pose_tiles_x(const PoseJob& j) { return ((uint32_t)j.nx + (uint32_t)POSE_TILE - 1) / (uint32_t)POSE_TILE; }
+inline uint32_t pose_tiles_y(const PoseJob& j) { return ((uint32_t)j.nz + (uint32_t)POSE_TILE - 1) / (uint32_t)POSE_TILE; }
+// the eight CF planes: one launch
+void launch_pose_foot(hipStream_t s, const PoseJob& j);
+// the price planes from CF and PPOT all FAR, then the goals: PPOT 0 where one counts, its tile and those it touches on list 0.
+// `flags` and `ctl` are all zero before
+void launch_pose_seed(hipStream_t s, const PoseJob& j);
+// round `round` over the first `blocks` entries of its list (the kernel reads the list's true length; blocks >= 1)
+void launch_pose_relax(hipStream_t s, const PoseJob& j, uint32_t round, uint32_t blocks);
+void launch_pose_dir(hipStream_t s, const PoseJob& j);
+// the walk from the window state (a, b, d): out[0] a PathStatus, out[1] the poses of the path, out[2] PPOT of the start; the first
+// min(out[1], cap) poses to `poses`
+void launch_pose_walk(hipStream_t s, const PoseJob& j, int32_t a, int32_t b, int32_t d, int32_t* poses, int64_t cap, int64_t* out);
+// n triples drawn into an image of svh_grid_render_cost's layout by their cells: a path, or (goals) only the goals that count
+void launch_pose_overlay(hipStream_t s, const PoseJob& j, const int32_t* triples, int64_t n, bool goals, uint8_t* rgb);
 
 // The frontiers (csrc/grid_front_kernels.hip): the finished STATE and COST planes -> FRONT, LABEL and the table of components.
 #ifndef SVH_FRONT_TILE

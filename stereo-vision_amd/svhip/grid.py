@@ -66,6 +66,10 @@ TRACK_NEW, TRACK_BY_OVERLAP, TRACK_BY_GATE, TRACK_MISSED, TRACK_MOVING, TRACK_ME
 TRACK_STATS = ("steps", "tracks", "by_overlap", "by_gate", "new", "missed", "dropped", "untracked")
 ASSIGN_UNTRACKED = -2
 OBJ_LARGE_COLOUR, OBJ_UNTRACKED_COLOUR, OBJ_CENTRE_COLOUR, OBJ_AHEAD_COLOUR = (128, 128, 128), (128, 0, 0), (255, 255, 255), (255, 255, 0)
+POSE_CF, POSE_POT, POSE_DIR = 0, 1, 2
+POSE_DTYPE = [np.uint8, np.int32, np.uint8]
+POSE_HEADINGS = 8
+POSE_DIR_GOAL, POSE_DIR_NONE = 8, 9
 ROLL_CUT_OBJECT = 4
 ROLL_PRED_RECORD = 6
 ROLL_PRED_FIELDS = ROLL_FIELDS + ("slot",)
@@ -109,6 +113,20 @@ class PlanParams(C.Structure):
 
     def copy(self, **kw):
         q = PlanParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class PoseParams(C.Structure):
+    """svh_grid_pose_params"""
+    _fields_ = [("neutral", C.c_int32), ("max_cost", C.c_int32), ("turn", C.c_int32), ("reverse", C.c_int32), ("spin", C.c_int32)]
+
+    def copy(self, **kw):
+        q = PoseParams.from_buffer_copy(bytes(self))
         for k, v in kw.items():
             setattr(q, k, v)
         return q
@@ -351,6 +369,22 @@ def _bind():
         L.svh_test_grid_roll.argtypes = roll
         L.svh_test_grid_roll_device.argtypes = roll
         L.svh_test_grid_roll_group.argtypes = [C.c_int64]
+        L.svh_grid_pose_params_default.argtypes = [C.POINTER(PoseParams)]
+        L.svh_grid_pose_params_default.restype = None
+        L.svh_grid_set_pose.argtypes = [C.c_void_p, C.POINTER(PoseParams)]
+        L.svh_grid_get_pose.argtypes = [C.c_void_p, C.POINTER(PoseParams)]
+        L.svh_grid_pose_set_goals.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_grid_pose_set_goal.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.svh_grid_get_pose_plane.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_get_pose_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_pose_heading_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svh_grid_pose_path.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.svh_grid_render_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
+        pose = ([C.POINTER(RollParams), C.POINTER(PoseParams), C.c_float] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32] +
+                [C.c_void_p] * 4)
+        L.svh_test_grid_pose.argtypes = pose
+        L.svh_test_grid_pose_device.argtypes = pose
+        L.svh_test_grid_pose_walk.argtypes = [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int64, C.c_void_p]
         L.svh_grid_explore_params_default.argtypes = [C.POINTER(ExploreParams)]
         L.svh_grid_explore_params_default.restype = None
         L.svh_grid_set_explore.argtypes = [C.c_void_p, C.POINTER(ExploreParams)]
@@ -758,6 +792,53 @@ def core_roll(roll, cell, cost, pot=None, table=None, set_=0, anchor=(0, 0), oa=
 def device_roll(roll, cell, cost, pot=None, table=None, set_=0, anchor=(0, 0), oa=0, ob=0, poses=None):
     """TEST ENTRY: the same through the device kernels on a caller's planes"""
     return _roll(_bind().svh_test_grid_roll_device, roll, cell, cost, pot, table, set_, anchor, oa, ob, poses)
+
+
+def default_pose(**kw):
+    p = PoseParams()
+    _bind().svh_grid_pose_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def _triples(triples):
+    t = np.ascontiguousarray(triples, np.int32).reshape(-1, 3)
+    return t, (t.ctypes.data if len(t) else None)
+
+
+def _pose(entry, roll, pose, cell, cost, goals, oa, ob):
+    c = np.ascontiguousarray(cost, np.uint8)
+    nz, nx = c.shape
+    g, gp = _triples(goals)
+    sh = (POSE_HEADINGS, nz, nx)
+    cf, pot, dir_, out = np.zeros(sh, np.uint8), np.zeros(sh, np.int32), np.zeros(sh, np.uint8), np.zeros(3, np.int64)
+    _check(entry(C.byref(roll), C.byref(pose), cell, nx, nz, oa, ob, c.ctypes.data, gp, len(g), cf.ctypes.data, pot.ctypes.data,
+                 dir_.ctypes.data, out.ctypes.data))
+    return cf, pot, dir_, out
+
+
+def core_pose(roll, pose, cell, cost, goals, oa=0, ob=0):
+    """the pose planner of csrc/grid_pose_core.h on the host (svh_test_grid_pose) for the vehicle of `roll` on cells of side `cell`, a
+    COST plane uint8 [nz, nx] under the offsets (oa, ob) and goal triples (ga, gb, d): (cf uint8, pot int32, dir uint8, each
+    [8, nz, nx]; the goal states that count); needs no device"""
+    cf, pot, dir_, out = _pose(_bind().svh_test_grid_pose, roll, pose, cell, cost, goals, oa, ob)
+    return cf, pot, dir_, int(out[0])
+
+
+def device_pose(roll, pose, cell, cost, goals, oa=0, ob=0):
+    """TEST ENTRY: the same through the kernels of csrc/grid_pose_kernels.hip: (cf, pot, dir, (counted, reached, rounds))"""
+    cf, pot, dir_, out = _pose(_bind().svh_test_grid_pose_device, roll, pose, cell, cost, goals, oa, ob)
+    return cf, pot, dir_, tuple(int(v) for v in out)
+
+
+def core_pose_walk(dir_, a, b, d, m=1, oa=0, ob=0, cap=None):
+    """the walk of csrc/grid_pose_core.h over a PDIR field [8, nz, nx] from the window state (a, b, d), on the host: (poses [n, 3]
+    int32 (ga, gb, d m), the length of the whole path; 0 where PDIR leads to no goal); needs no device"""
+    f = np.ascontiguousarray(dir_, np.uint8)
+    _, nz, nx = f.shape
+    room = POSE_HEADINGS * nx * nz if cap is None else int(cap)
+    poses, n = np.zeros((max(room, 1), 3), np.int32), C.c_int64(-1)
+    _check(_bind().svh_test_grid_pose_walk(nx, nz, oa, ob, m, f.ctypes.data, a, b, d, poses.ctypes.data if room else None, room, C.addressof(n)))
+    return poses[:min(n.value, room)].copy(), n.value
 
 
 def default_pred(**kw):
@@ -1473,6 +1554,70 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_roll(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_pose(self, params=None, **kw):
+        """the pose planner's parameters in force (or `params`) with the fields of kw replaced: neutral, max_cost, turn, reverse, spin"""
+        p = (params if params is not None else self.pose_params()).copy(**kw)
+        _check(self._L.svh_grid_set_pose(self._h, C.byref(p)))
+
+    def pose_params(self):
+        p = PoseParams()
+        _check(self._L.svh_grid_get_pose(self._h, C.byref(p)))
+        return p
+
+    def pose_set_goals(self, triples):
+        """[n, 3] goal states (ga, gb, d), global cells; d = -1: every passable heading; an empty list forgets the goals"""
+        t, ptr = _triples(triples)
+        _check(self._L.svh_grid_pose_set_goals(self._h, ptr, len(t)))
+
+    def pose_set_goal(self, xyz, d=-1):
+        """one goal, the cell of a map-frame position at heading d"""
+        _check(self._L.svh_grid_pose_set_goal(self._h, _xyz(xyz).ctypes.data, d))
+
+    def pose_plane(self, which, device_ptr=None):
+        """POSE_CF uint8, POSE_POT int32 or POSE_DIR uint8, [8, nz, nx]; with device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_pose_plane(self._h, which, device_ptr, 1))
+            return None
+        if not 0 <= which < len(POSE_DTYPE):
+            raise SvhError(ERR_BAD_ARG, "no such plane")
+        out = np.zeros((POSE_HEADINGS, self.nz, self.nx), POSE_DTYPE[which])
+        _check(self._L.svh_grid_get_pose_plane(self._h, which, out.ctypes.data, 0))
+        return out
+
+    def pose_stats(self):
+        """(goals given, goal states that count, states with PPOT != FAR, relaxation rounds)"""
+        out = np.zeros(4, np.int64)
+        _check(self._L.svh_grid_get_pose_stats(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def pose_heading_of(self, dir_xyz):
+        """the planning heading 0..7 nearest to a map-frame direction"""
+        d = C.c_int32(-1)
+        _check(self._L.svh_grid_pose_heading_of(self._h, _xyz(dir_xyz).ctypes.data, C.addressof(d)))
+        return d.value
+
+    def pose_path(self, start_xyz, d, cap=None):
+        """(status, poses [n, 3] int32 (ga, gb, k = d headings_m), cost): the cheapest pose sequence from the cell of a map-frame
+        position at heading d; with cap only its first poses, and the length of the whole path is in `pose_path_len`"""
+        room = POSE_HEADINGS * self.nx * self.nz if cap is None else int(cap)
+        poses = np.zeros((max(room, 1), 3), np.int32)
+        n, cost = C.c_int64(-1), C.c_int32(-1)
+        status = _check(self._L.svh_grid_pose_path(self._h, _xyz(start_xyz).ctypes.data, d, poses.ctypes.data if room else None, room,
+                                                   C.addressof(n), C.addressof(cost)))
+        self.pose_path_len = n.value
+        return status, poses[:min(n.value, room)].copy(), cost.value
+
+    def render_pose(self, poses=(), device_ptr=None):
+        """render_cost with the cells of the goals that count in GOAL_COLOUR and the reference cells of the given poses in
+        PATH_COLOUR over them"""
+        t, ptr = _triples(poses)
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_pose(self._h, ptr, len(t), device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_pose(self._h, ptr, len(t), img.ctypes.data, 0))
         return img
 
     def set_explore(self, params=None, **kw):

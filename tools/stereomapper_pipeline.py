@@ -18,6 +18,7 @@ without the GUI.  Usage:
                                           [--grid-local DIR [--grid-cell S] [--grid-size NXxNZ]]
                                           [--grid-cost DIR [--grid-slope S] [--grid-inscribed M] [--grid-inflate M]]
                                          [--grid-plan DIR [--grid-goal-ahead M]]
+                                         [--grid-pose DIR [--grid-pose-params TURN,REVERSE,SPIN]]
                                          [--grid-roll DIR [--grid-roll-vehicle FRONT,REAR,HALFWIDTH] [--grid-roll-unknown N]]
                                           [--grid-frontiers DIR [--grid-unexplored unseen|seen|both] [--grid-frontier-min N]]
                                           [--grid-explore DIR [--grid-explore-range M]]
@@ -90,6 +91,14 @@ ends sooner --, so a blocked cell ahead does not end the route; the start is the
 passable at a price of 100 above the neutral one.  The plan image (svh_grid_render_plan: the cost map, the goals that count
 yellow, the path white) goes into DIR/plan_%06d.ppm and one line {"frame", "status", "length", "cost"} per frame is appended
 to DIR/plan.jsonl (status 0 found, 1 unreachable, 2 the camera's cell is impassable, 3 outside).
+
+--grid-pose DIR: needs --grid-cost.  After every local step a pose sequence for the vehicle's rectangle (svh_grid_pose_*): the goals
+are every heading of the cells of the row that --grid-plan aims at (--grid-goal-ahead), the start the camera's cell at the planning
+heading of its forward axis (svh_grid_pose_heading_of); the vehicle and what an unknown cell counts as are the rollouts'
+(--grid-roll-vehicle, --grid-roll-unknown).  --grid-pose-params TURN,REVERSE,SPIN: what a turning move, a reverse move and a spin on
+the spot add (100,-1,-1: no reverse, no spin).  The image (svh_grid_render_pose: the cost map, the goal cells that count yellow, the
+poses' cells white) goes into DIR/pose_%06d.ppm and one line {"frame", "heading", "status", "length", "cost", "poses"} per frame is
+appended to DIR/pose.jsonl.
 
 --grid-roll DIR: needs --grid-plan, and runs after it on its goals.  After every local step short motions are scored on the device
 (svh_grid_roll_score): nine constant-curvature arcs (-0.2 .. 0.2 per metre) of 24 poses, one every two cells, that start at the
@@ -288,6 +297,19 @@ class Pipeline:
         g.set_goals([(oa + ia, row) for ia in range(g.nx)])
         status, cells, cost = g.path(centre)
         return status, cells, cost, g.render_plan(cells)
+
+    def pose_step(self, ahead=20.0):
+        """every heading of the cells of the window row `ahead` metres in front of the camera's cell a goal of the pose planner, the
+        pose sequence from the camera's cell at the heading of its forward axis: (heading, status, poses [n, 3], cost, the pose image
+        [nz, nx, 3])"""
+        g = self.local
+        centre = self.H_total[:3, 3].copy()
+        (_, gb), (oa, ob) = g.cell_of(centre), g.window()
+        row = min(gb + int(round(ahead / g.params.cell)), ob + g.nz - 1)
+        g.pose_set_goals([(oa + ia, row, -1) for ia in range(g.nx)])
+        d = g.pose_heading_of(self.H_total[:3, 2].copy())
+        status, poses, cost = g.pose_path(centre, d)
+        return d, status, poses, cost, g.render_pose(poses)
 
     def enable_roll(self, curvatures, step_len, poses, **kw):
         """the vehicle (kw: front, rear, half_width, stop_cost, ...) and one set of constant-curvature arcs per start heading"""
@@ -630,6 +652,7 @@ def main():
     explore_dir, explore_kw = None, {}
     align_dir, align_apply, align_window = None, False, None
     roll_dir, roll_kw = None, {}
+    pose_dir, pose_kw = None, {}
     dyn_dir, dyn_kw = None, {}
     obj_dir, obj_kw = None, {}
     pred_dir, pred_kw = None, {}
@@ -672,6 +695,15 @@ def main():
             k = sys.argv.index("--grid-goal-ahead")
             goal_ahead = float(sys.argv[k + 1])
             assert goal_ahead >= 0 and goal_ahead < float("inf")
+            del sys.argv[k:k + 2]
+        if "--grid-pose" in sys.argv:
+            k = sys.argv.index("--grid-pose")
+            pose_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-pose-params" in sys.argv:
+            k = sys.argv.index("--grid-pose-params")
+            turn, reverse, spin = (int(v) for v in sys.argv[k + 1].split(","))
+            pose_kw = dict(turn=turn, reverse=reverse, spin=spin)
             del sys.argv[k:k + 2]
         if "--grid-roll" in sys.argv:
             k = sys.argv.index("--grid-roll")
@@ -769,9 +801,11 @@ def main():
         assert cost_dir or not explore_dir
         assert front_dir or explore_dir or not front_kw
         assert explore_dir or not explore_kw
-        assert plan_dir or goal_ahead is None
+        assert plan_dir or pose_dir or goal_ahead is None
         assert plan_dir or not roll_dir
-        assert roll_dir or not roll_kw
+        assert roll_dir or pose_dir or not roll_kw
+        assert cost_dir or not pose_dir
+        assert pose_dir or not pose_kw
         assert local_dir or not (cost_dir or cost_kw)
         assert cost_dir or not cost_kw
         assert grid_dir or not level
@@ -834,6 +868,9 @@ def main():
     if plan_dir:
         os.makedirs(plan_dir, exist_ok=True)
         open(os.path.join(plan_dir, "plan.jsonl"), "w").close()
+    if pose_dir:
+        os.makedirs(pose_dir, exist_ok=True)
+        open(os.path.join(pose_dir, "pose.jsonl"), "w").close()
     if front_dir:
         os.makedirs(front_dir, exist_ok=True)
         open(os.path.join(front_dir, "frontiers.jsonl"), "w").close()
@@ -881,7 +918,11 @@ def main():
         p.enable_roll(ROLL_CURVATURES, 2.0 * grid_cell, ROLL_POSES, **roll_kw)
     if pred_kw:
         p.local.set_predict(**pred_kw)
-    found = explored = rolled = ranked = aligned = cut_frames = 0
+    if pose_dir:
+        if roll_kw and not roll_dir:
+            p.local.set_roll(**roll_kw)
+        p.local.set_pose(**pose_kw)
+    found = explored = rolled = ranked = aligned = cut_frames = posed = 0
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -923,6 +964,13 @@ def main():
             view.write_ppm(os.path.join(plan_dir, "plan_%06d.ppm" % (frames - 1)), img)
             with open(os.path.join(plan_dir, "plan.jsonl"), "a") as f:
                 f.write(json.dumps({"frame": frames - 1, "status": int(status), "length": int(len(cells)), "cost": int(cost)}) + "\n")
+        if pose_dir:
+            d, status, poses, cost, img = p.pose_step(20.0 if goal_ahead is None else goal_ahead)
+            posed += status == 0
+            view.write_ppm(os.path.join(pose_dir, "pose_%06d.ppm" % (frames - 1)), img)
+            with open(os.path.join(pose_dir, "pose.jsonl"), "a") as f:
+                f.write(json.dumps({"frame": frames - 1, "heading": int(d), "status": int(status), "length": int(len(poses)), "cost": int(cost),
+                                    "poses": poses.tolist()}) + "\n")
         if roll_dir:
             s, best, recs, scores, img = p.roll_step()
             rolled += best >= 0
@@ -987,6 +1035,10 @@ def main():
     if plan_dir:
         print("plan: goals %g m ahead, a route in %d of %d frames; %d images and plan.jsonl in %s" % (
             20.0 if goal_ahead is None else goal_ahead, found, frames, frames, plan_dir))
+    if pose_dir:
+        q = p.local.pose_params()
+        print("pose plan: goals %g m ahead, turn %d, reverse %d, spin %d: a pose sequence in %d of %d frames; %d images and pose.jsonl in %s" % (
+            20.0 if goal_ahead is None else goal_ahead, q.turn, q.reverse, q.spin, posed, frames, frames, pose_dir))
     if roll_dir:
         print("rollouts: %d arcs of %d poses per heading, a feasible one in %d of %d frames; %d images and roll.jsonl in %s" % (
             len(ROLL_CURVATURES), ROLL_POSES, rolled, frames, frames, roll_dir))
