@@ -13,7 +13,8 @@
 // footprint masks and the scoring of a set of candidates against it;
 // (grid_explore_kernels.hip): the exploration layer -- the gain of viewpoints, the ranking of the frontiers, run by explore_rank() here;
 // (grid_align_kernels.hip): the alignment layer -- the field, the scan of a frame's obstacle points, the volume of scores, run by align() here;
-// (grid_dyn_kernels.hip): the dynamics -- the sight lines and the settle of an observation, run by observe() here.
+// (grid_dyn_kernels.hip): the dynamics -- the sight lines and the settle of an observation, run by observe() here;
+// (grid_archive_kernels.hip): the archive -- the leaving and entering passes of a scroll, run by scroll() here, and the region reader.
 // The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
@@ -32,6 +33,9 @@
 // (they travel with the torus and are cleared as lazily as the accumulators, dyn_need_clear); the body plane is kept by the settle
 // kernel and written anew (body_valid) after anything else wrote the accumulators.  The frame record and `ends` are scratch, empty
 // between observations (frame_clean, ends_clean).  These describe the accumulators' side and are not part of the table.
+// The archive (svh_grid_set_archive) is state beside the accumulators too: the cells outside the window.  It is emptied as lazily as
+// they are (arch_need_clear), by everything that empties them; nothing cached is computed from it, so its mutators touch no source of
+// the table, and a scroll, which restores from it, drops ACC as it always did.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -44,6 +48,7 @@
 
 #include "../../include/svh_grid.h"
 #include "grid_align_core.h"
+#include "grid_archive_core.h"
 #include "grid_core.h"
 #include "grid_explore_core.h"
 #include "grid_internal.h"
@@ -348,6 +353,14 @@ struct svh_grid {
     PinnedBuf<uint32_t> h_pose_ctl;
     int64_t pose_counted = 0, pose_reached = 0, pose_rounds = 0;   // of the field that is valid
     HipBuf<int32_t> d_pose_path;   // the poses a walk writes, or a caller's for the pose image
+    int32_t arch_tiles = 0;     // the archive: max_tiles, 0 = off
+    HipBuf<uint8_t> arch_pool;  // PAGE_BYTES per tile: kmin | kmax | count | overhead | hsum | vsum | pass | CONTRA | LAST, a plane each; first use
+    HipBuf<unsigned long long> arch_keys, arch_ctl, arch_skeys;   // the table's keys, the control words, the kept keys of a trim
+    HipBuf<int32_t> arch_page, arch_stack, arch_claims, arch_spages;
+    PinnedBuf<unsigned long long> h_arch_ctl;
+    HipBuf<uint8_t> d_region;   // a region bound for the host
+    bool arch_need_clear = true;   // the table and the stack do not hold the empty archive yet
+    int64_t arch_stats[grid::AS_WORDS] = {0, 0, 0, 0, 0, 0};   // since the archive was last emptied
 
     grid::Cells cells() const {
         uint8_t* b = acc.p;
@@ -378,6 +391,18 @@ struct svh_grid {
         uint8_t* b = dynp.p;
         const size_t n = ncells;
         return grid::DynPlanes{(int2*)b, (int32_t*)(b + 8 * n), (int32_t*)(b + 12 * n), (int32_t*)(b + 16 * n), (int32_t*)(b + 20 * n), b + 24 * n};
+    }
+    // the archive as the kernels see it; without buffers that hold it, one in which every lookup finds nothing
+    grid::Archive archive() const {
+        grid::Archive a;
+        if (arch_tiles <= 0 || arch_need_clear || !arch_pool.p) return a;
+        const size_t n = (size_t)arch_tiles * (size_t)grid::TILE_CELLS;
+        uint8_t* b = arch_pool.p;
+        a.keys = arch_keys.p, a.page = arch_page.p, a.stack = arch_stack.p, a.claims = arch_claims.p, a.ctl = arch_ctl.p;
+        a.table = grid::archive_table_size(arch_tiles), a.max_tiles = arch_tiles;
+        a.pages = grid::Pages{(uint32_t*)b, (uint32_t*)(b + 4 * n), (int32_t*)(b + 8 * n), (int32_t*)(b + 12 * n), (unsigned long long*)(b + 16 * n),
+                              (unsigned long long*)(b + 24 * n), (int32_t*)(b + 32 * n), (int32_t*)(b + 36 * n), (int32_t*)(b + 40 * n)};
+        return a;
     }
     grid::Cells fcells() const {
         uint8_t* b = frame.p;
@@ -427,7 +452,14 @@ void forget_tracks(svh_grid* g) {
     for (int k = 0; k < grid::TS_WORDS; k++) g->trk_stats[k] = 0;
 }
 
+// the archive holds no tile, and its counts start again
+void forget_archive(svh_grid* g) {
+    g->arch_need_clear = true;
+    for (int k = 0; k < grid::AS_WORDS; k++) g->arch_stats[k] = 0;
+}
+
 void mark_empty(svh_grid* g) {
+    forget_archive(g);   // the stamp restarts, and a new corner renumbers the global cells
     g->need_clear = true;
     touch(g, ACC);
     g->st = svh_grid_stats{0, 0, 0, 0, 0};
@@ -2119,13 +2151,65 @@ int added(svh_grid* g, int rc) {
     return rc;
 }
 
+// the archive's buffers exist and hold what the object says they hold; the layer is on
+int archive_ready(svh_grid* g) {
+    const size_t tiles = (size_t)g->arch_tiles, table = grid::archive_table_size(g->arch_tiles);
+    if (g->arch_pool.cap < tiles * grid::PAGE_BYTES || g->arch_keys.cap < table * sizeof(unsigned long long)) g->arch_need_clear = true;
+    GRID_GROW(g->arch_pool, tiles * grid::PAGE_BYTES);
+    GRID_GROW_N(g->arch_keys, table);
+    GRID_GROW_N(g->arch_page, table);
+    GRID_GROW_N(g->arch_claims, table);
+    GRID_GROW_N(g->arch_stack, tiles);
+    GRID_GROW_N(g->arch_ctl, grid::AR_WORDS);
+    GRID_GROW_N(g->h_arch_ctl, grid::AR_WORDS);
+    if (g->arch_need_clear) {
+        GRID_TRY(copy, hipMemsetAsync(g->arch_keys, 0xFF, table * sizeof(unsigned long long), g->stream));
+        GRID_TRY(copy, hipMemsetAsync(g->arch_page, 0xFF, table * sizeof(int32_t), g->stream));
+        g->arch_need_clear = false;   // in stream order before whatever the entry does next; every entry ends with a wait
+        GRID_TRY(launch, (grid::launch_archive_reset(g->stream, g->archive()), hipGetLastError()));
+    }
+    return SVH_OK;
+}
+
+// the counts of the archive from the control words, which the entry has copied to h_arch_ctl and waited for
+void read_archive_stats(svh_grid* g) {
+    const unsigned long long* h = g->h_arch_ctl;
+    g->arch_stats[grid::AS_PAGES] = (int64_t)g->arch_tiles - (int64_t)h[grid::AR_FREE];
+    g->arch_stats[grid::AS_SAVED] = (int64_t)h[grid::AR_SAVED], g->arch_stats[grid::AS_RESTORED] = (int64_t)h[grid::AR_RESTORED];
+    g->arch_stats[grid::AS_LOST] = (int64_t)h[grid::AR_LOST], g->arch_stats[grid::AS_REFUSED] = (int64_t)h[grid::AR_REFUSED];
+}
+
+// scroll() with the archive on: the leaving pass with the old offsets, then the entering pass with the new ones; one wait
+int scroll_archived(svh_grid* g, int32_t da, int32_t db) {
+    int rc = archive_ready(g);
+    if (rc) return rc;
+    if (g->dyn_on && (rc = dyn_ready(g))) return rc;
+    grid::ArchScrollJob j;
+    j.prm = g->prm;
+    j.prm.oa -= da, j.prm.ob -= db;   // the old offsets
+    j.da = da, j.db = db;
+    j.cells = g->cells();
+    j.dyn = g->dyn_on;
+    if (j.dyn) j.planes = g->dplanes();
+    j.ar = g->archive();
+    GRID_TRY(launch, (grid::launch_archive_leave(g->stream, j), hipGetLastError()));
+    j.prm = g->prm;
+    GRID_TRY(launch, (grid::launch_archive_enter(g->stream, j), hipGetLastError()));
+    g->body_valid = false;   // a restored cell has its accumulators and an empty body
+    GRID_TRY(copy, hipMemcpyAsync(g->h_arch_ctl, g->arch_ctl, grid::AR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
+    GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    read_archive_stats(g);
+    return SVH_OK;
+}
+
 // the window moves by (da, db) cells to offsets that have been checked, not both zero
 int scroll(svh_grid* g, int32_t da, int32_t db) {
     g->prm.oa += da, g->prm.ob += db;
     touch(g, ACC);
-    if (g->need_clear) return SVH_OK;   // the empty grid has no cell to reset
+    if (g->need_clear) return SVH_OK;   // the empty grid has no cell to reset, and its archive is as empty
     int rc = ready(g);
     if (rc) return rc;
+    if (g->arch_tiles > 0) return scroll_archived(g, da, db);
     const int64_t ada = da < 0 ? -(int64_t)da : da, adb = db < 0 ? -(int64_t)db : db;
     const bool dyn = g->dyn_on && !g->dyn_need_clear && g->dynp.cap >= g->ncells * grid::DYN_BYTES;   // the layer has cells to reset
     if (ada >= g->prm.nx || adb >= g->prm.nz) {
@@ -3190,6 +3274,153 @@ int32_t svh_grid_render_dyn(svh_grid* g, uint8_t* rgb, int32_t on_device) {
     if (!g || !rgb) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_dyn: a grid and an output are needed");
     if (!g->dyn_on) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_dyn") + kNoDyn);
     return failed(g, render_dyn(g, rgb, on_device != 0));
+}
+
+// ---- the archive ----------------------------------------------------------------------------------------------------------
+void svh_grid_archive_params_default(svh_grid_archive_params* p) {
+    if (p) p->max_tiles = grid::ARCHIVE_DEFAULT_TILES;
+}
+
+int32_t svh_grid_set_archive(svh_grid* g, const svh_grid_archive_params* p) {
+    if (!g || !p || p->max_tiles < 0 || p->max_tiles > grid::ARCHIVE_MAX_TILES)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_archive: a grid and max_tiles in 0 .. 2^20 are needed");
+    if (p->max_tiles == g->arch_tiles) return SVH_OK;
+    (void)hipSetDevice(g->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    g->arch_pool = HipBuf<uint8_t>();   // another size is another pool, allocated at first use; 0 frees it
+    g->arch_keys = HipBuf<unsigned long long>(), g->arch_skeys = HipBuf<unsigned long long>();
+    g->arch_page = HipBuf<int32_t>(), g->arch_stack = HipBuf<int32_t>(), g->arch_claims = HipBuf<int32_t>(), g->arch_spages = HipBuf<int32_t>();
+    g->arch_tiles = p->max_tiles;
+    forget_archive(g);
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_archive(svh_grid* g, svh_grid_archive_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_archive: null argument");
+    p->max_tiles = g->arch_tiles;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_archive_stats(svh_grid* g, int64_t out[6]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_archive_stats: null argument");
+    for (int k = 0; k < grid::AS_WORDS; k++) out[k] = g->arch_stats[k];
+    out[grid::AS_MAX_TILES] = g->arch_tiles;
+    return SVH_OK;
+}
+
+int32_t svh_grid_archive_clear(svh_grid* g) {
+    if (!g) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_archive_clear: null argument");
+    forget_archive(g);
+    return SVH_OK;
+}
+
+int32_t svh_grid_archive_trim(svh_grid* g, int32_t ga0, int32_t gb0, int32_t ga1, int32_t gb1) {
+    if (!g || !grid::trim_ok(ga0, gb0, ga1, gb1))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_archive_trim: a grid and a box ga0 <= ga1, gb0 <= gb1 of global cells below 2^20 are needed");
+    const grid::Archive ar = g->archive();
+    if (ar.table == 0) return SVH_OK;   // no tile to drop
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipSetDevice(g->device));
+        GRID_GROW_N(g->arch_skeys, ar.max_tiles);
+        GRID_GROW_N(g->arch_spages, ar.max_tiles);
+        hipStream_t s = g->stream;
+        GRID_TRY(launch, (grid::launch_archive_trim_collect(s, ar, ga0, gb0, ga1, gb1, g->arch_skeys, g->arch_spages), hipGetLastError()));
+        GRID_TRY(copy, hipMemsetAsync(ar.keys, 0xFF, (size_t)ar.table * sizeof(unsigned long long), s));
+        GRID_TRY(copy, hipMemsetAsync(ar.page, 0xFF, (size_t)ar.table * sizeof(int32_t), s));
+        GRID_TRY(launch, (grid::launch_archive_trim_insert(s, ar, g->arch_skeys, g->arch_spages), hipGetLastError()));
+        GRID_TRY(copy, hipMemsetAsync(ar.ctl + grid::AR_CLAIMS, 0, sizeof(unsigned long long), s));
+        GRID_TRY(copy, hipMemcpyAsync(g->h_arch_ctl, ar.ctl, grid::AR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        read_archive_stats(g);
+        return SVH_OK;
+    }();
+    if (failed(g, rc) == SVH_ERR_HIP) forget_archive(g);   // a table half rebuilt is no archive; the window is untouched
+    return rc;
+}
+
+int32_t svh_grid_archive_tiles(svh_grid* g, int32_t* keys, int64_t cap, int64_t* n) {
+    if (!g || !n || cap < 0 || (cap > 0 && !keys)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_archive_tiles: bad arguments");
+    *n = 0;
+    const grid::Archive ar = g->archive();
+    if (ar.table == 0) return SVH_OK;
+    const size_t bytes = (size_t)ar.table * sizeof(unsigned long long);
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipSetDevice(g->device));
+        GRID_GROW(g->h_out, bytes);
+        GRID_TRY(copy, hipMemcpyAsync(g->h_out, ar.keys, bytes, hipMemcpyDeviceToHost, g->stream));
+        GRID_TRY(wait, hipStreamSynchronize(g->stream));
+        return SVH_OK;
+    }();
+    if (rc) return failed(g, rc);
+    const unsigned long long* k = (const unsigned long long*)g->h_out.p;
+    std::vector<unsigned long long> live;
+    for (uint32_t i = 0; i < ar.table; i++)
+        if (k[i] != grid::TILE_NONE) live.push_back(k[i]);
+    std::sort(live.begin(), live.end());   // tb is the high word: ascending by (tb, ta)
+    *n = (int64_t)live.size();
+    for (int64_t i = 0; i < std::min(*n, cap); i++) keys[2 * i] = grid::key_ta(live[(size_t)i]), keys[2 * i + 1] = grid::key_tb(live[(size_t)i]);
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_region(svh_grid* g, int32_t plane_kind, int32_t plane, int32_t ga0, int32_t gb0, int32_t w, int32_t h, void* out, int32_t on_device) {
+    if (!g || !out || plane_kind < 0 || plane_kind >= grid::RK_KINDS || plane < 0 || plane >= (plane_kind == grid::RK_GRID ? (int32_t)grid::P_PLANES : (int32_t)grid::L_PLANES) ||
+        !grid::region_ok(ga0, gb0, w, h))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_region: a grid, a plane of svh_grid_get (kind 0) or svh_grid_get_local (kind 1), a box of 1..8192 x 1..8192 global cells below 2^20 and an output are needed");
+    const bool bytes = plane_kind == grid::RK_GRID ? plane >= grid::P_INTENSITY : plane == grid::L_STATE;
+    if (on_device && !bytes && ((uintptr_t)out & 3)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_region: a device array of a 4-byte plane must be 4-byte aligned");
+    const size_t size = (size_t)w * (size_t)h * (bytes ? 1 : 4);
+    const int rc = [&]() -> int {
+        const int r0 = ready(g);
+        if (r0) return r0;
+        grid::RegionJob j{g->prm, g->cells(), g->archive(), plane_kind, plane, ga0, gb0, w, h};
+        if (!on_device) GRID_GROW(g->d_region, size);
+        void* dst = on_device ? out : (void*)g->d_region.p;
+        GRID_TRY(launch, (grid::launch_archive_region(g->stream, j, dst), hipGetLastError()));
+        return finish(g, dst, size, out, on_device != 0);
+    }();
+    return failed(g, rc);
+}
+
+int32_t svh_grid_render_region(svh_grid* g, int32_t mode, int32_t ga0, int32_t gb0, int32_t w, int32_t h, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb || mode < 0 || mode > grid::M_LOCAL || !grid::region_ok(ga0, gb0, w, h))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_region: a grid, a mode 0..3, a box of 1..8192 x 1..8192 global cells below 2^20 and an output are needed");
+    const size_t size = (size_t)w * (size_t)h * 3;
+    const int rc = [&]() -> int {
+        const int r0 = ready(g);
+        if (r0) return r0;
+        grid::RegionJob j{g->prm, g->cells(), g->archive(), grid::RK_GRID, 0, ga0, gb0, w, h};
+        if (!on_device) GRID_GROW(g->d_region, size);
+        uint8_t* dst = on_device ? rgb : g->d_region.p;
+        GRID_TRY(launch, (grid::launch_archive_render_region(g->stream, j, mode, dst), hipGetLastError()));
+        return finish(g, dst, size, rgb, on_device != 0);
+    }();
+    return failed(g, rc);
+}
+
+// grid_archive_core.h on the host.  svh_test_grid_archive_key: per global cell the tile key, the tile (ta, tb) read back from it and the
+// index inside the tile; *table = archive_table_size(max_tiles) when table is given
+int32_t svh_test_grid_archive_key(int64_t n, const int32_t* ga, const int32_t* gb, uint64_t* key, int32_t* tile, uint32_t* index, int32_t max_tiles,
+                                  uint32_t* table) {
+    if (n < 0 || (n > 0 && (!ga || !gb || !key || !tile || !index)) || max_tiles < 0 || max_tiles > grid::ARCHIVE_MAX_TILES)
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_archive_key: bad arguments");
+    for (int64_t i = 0; i < n; i++) {
+        if (!grid::region_ok(ga[i], gb[i], 1, 1)) return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_archive_key: a global cell lies below 2^20");
+        key[i] = grid::cell_key(ga[i], gb[i]);
+        tile[2 * i] = grid::key_ta(key[i]), tile[2 * i + 1] = grid::key_tb(key[i]);
+        index[i] = grid::tile_index(ga[i], gb[i]);
+    }
+    if (table) *table = grid::archive_table_size(max_tiles);
+    return SVH_OK;
+}
+
+// strip_count and strip_cell: *count cells, the first min(*count, cap) as pairs (ia, ib) in lane order.  A scroll by (da, db) leaves the
+// strip of (da, db) in the old window's cells and enters the strip of (-da, -db) in the new window's
+int32_t svh_test_grid_archive_strip(int32_t nx, int32_t nz, int32_t da, int32_t db, int32_t* cells, int64_t cap, int64_t* count) {
+    if (nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE || (da == 0 && db == 0) || !count || cap < 0 || (cap > 0 && !cells))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_archive_strip: bad arguments");
+    *count = (int64_t)grid::strip_count(nx, nz, da, db);
+    for (int64_t t = 0; t < std::min(*count, cap); t++) grid::strip_cell(nx, nz, da, db, (uint32_t)t, &cells[2 * t], &cells[2 * t + 1]);
+    return SVH_OK;
 }
 
 // grid_dyn_core.h on the host.  svh_test_grid_dyn_params: the checks of svh_grid_set_dynamics and *margin_q; SVH_ERR_BAD_ARG when

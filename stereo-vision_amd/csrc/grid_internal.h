@@ -1,6 +1,7 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
 // csrc/grid_front_kernels.hip / csrc/grid_obj_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_pred_kernels.hip /
-// csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip / csrc/grid_dyn_kernels.hip / csrc/grid_pose_kernels.hip: the launches of the
+// csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip / csrc/grid_dyn_kernels.hip / csrc/grid_pose_kernels.hip /
+// csrc/grid_archive_kernels.hip: the launches of the
 // ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
@@ -9,6 +10,7 @@
 #include <hip/hip_vector_types.h>
 
 #include "grid_align_core.h"
+#include "grid_archive_core.h"
 #include "grid_core.h"
 #include "grid_dyn_core.h"
 #include "grid_explore_core.h"
@@ -577,6 +579,65 @@ void launch_dyn_enter(hipStream_t s, const Params& prm, int32_t da, int32_t db, 
 void launch_dyn_get(hipStream_t s, const Params& prm, int32_t plane, int32_t stamp, const DynPlanes& d, int32_t* out);
 // svh_grid_render_dyn: a RenderJob (its mode is not read) with the layer's planes
 void launch_render_dyn(hipStream_t s, const RenderJob& j, const DynPlanes& d);
+
+// The archive (csrc/grid_archive_kernels.hip): the cells a scroll takes out of the window stored in pages by tile, the cells it brings
+// in restored from them, and the finished planes over any box of global cells from the window and the pages together.
+constexpr uint32_t ARCH_BLOCK = 256;             // every kernel of the layer; k_grid_arch_assign: one workgroup per claim, one lane per record
+static_assert(ARCH_BLOCK == (uint32_t)TILE_CELLS, "a workgroup initialises one page");
+// the control words on the device, 64 bits each: the tiles claimed by the leaving pass in flight (zero between calls), a claim that
+// found the table full (zero between calls), the unused pages, and the four counts of grid::ArchiveStat
+enum ArchCtl { AR_CLAIMS = 0, AR_OVERFLOW, AR_FREE, AR_SAVED, AR_RESTORED, AR_LOST, AR_REFUSED, AR_WORDS = 8 };
+// the pool: max_tiles * 256 elements per plane, the record of cell i of page p at p * 256 + i
+struct Pages {
+    uint32_t* kmin;
+    uint32_t* kmax;
+    int32_t* count;
+    int32_t* overhead;
+    unsigned long long* hsum;
+    unsigned long long* vsum;
+    int32_t* pass;
+    int32_t* contra;
+    int32_t* last;
+};
+struct Archive {
+    unsigned long long* keys = nullptr;   // `table` slots: a tile_key or TILE_NONE
+    int32_t* page = nullptr;              // ... the tile's page, -1 while a claim is pending and in every empty slot
+    uint32_t table = 0;                   // a power of two; 0: there is no archive, every lookup finds nothing
+    int32_t max_tiles = 0;
+    int32_t* stack = nullptr;             // max_tiles: the unused pages at [0, ctl[AR_FREE])
+    int32_t* claims = nullptr;            // `table`: the slots claimed by the leaving pass in flight
+    unsigned long long* ctl = nullptr;    // AR_WORDS
+    Pages pages{};
+};
+// keys and page are all ones before: the stack holds every page, the control words are zero but AR_FREE
+void launch_archive_reset(hipStream_t s, const Archive& ar);
+// One scroll by (da, db), not both zero.  leave: `prm` has the OLD offsets; three launches -- claim, assign or withdraw, store.
+// enter: `prm` has the NEW offsets; one launch, which replaces launch_enter and launch_dyn_enter.  dyn: the planes exist
+struct ArchScrollJob {
+    Params prm;
+    int32_t da, db;
+    Cells cells;
+    bool dyn;
+    DynPlanes planes;
+    Archive ar;
+};
+void launch_archive_leave(hipStream_t s, const ArchScrollJob& j);
+void launch_archive_enter(hipStream_t s, const ArchScrollJob& j);
+// a plane of svh_grid_get (kind RK_GRID) or svh_grid_get_local (RK_LOCAL) over the box of w x h global cells from (ga0, gb0), row major
+struct RegionJob {
+    Params prm;
+    Cells cells;
+    Archive ar;
+    int32_t kind, plane, ga0, gb0, w, h;
+};
+void launch_archive_region(hipStream_t s, const RegionJob& j, void* out);
+// the image of a grid::Mode (M_LOCAL included) over the box, row 0 = gb0 + h - 1
+void launch_archive_render_region(hipStream_t s, const RegionJob& j, int32_t mode, uint8_t* rgb);
+// svh_grid_archive_trim in two halves, keys and page filled with ones between them: the tiles that meet the box to (skeys, spages),
+// room for max_tiles, their number to ctl[AR_CLAIMS]; the pages of the others back on the stack.  Then the kept tiles inserted again
+void launch_archive_trim_collect(hipStream_t s, const Archive& ar, int32_t ga0, int32_t gb0, int32_t ga1, int32_t gb1, unsigned long long* skeys,
+                                 int32_t* spages);
+void launch_archive_trim_insert(hipStream_t s, const Archive& ar, const unsigned long long* skeys, const int32_t* spages);
 
 }  // namespace grid
 }  // namespace svh

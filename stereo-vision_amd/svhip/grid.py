@@ -75,6 +75,11 @@ ROLL_PRED_RECORD = 6
 ROLL_PRED_FIELDS = ROLL_FIELDS + ("slot",)
 PRED_STATS = ("tracks", "sources", "cells", "launches")
 PRED_MAX_SLOTS, PRED_MAX_RADIUS = 32, 16
+REGION_GRID, REGION_LOCAL = range(2)
+RENDER_LOCAL = 3
+ARCHIVE_STATS = ("pages", "max_tiles", "stored", "restored", "lost", "refused")
+ARCHIVE_TILE, ARCHIVE_MAX_TILES, ARCHIVE_DEFAULT_TILES, ARCHIVE_PAGE_BYTES = 16, 2 ** 20, 16384, 11264
+REGION_MAX_SIDE = 8192
 
 
 class Params(C.Structure):
@@ -235,6 +240,20 @@ class DynParams(C.Structure):
 
     def asdict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ArchiveParams(C.Structure):
+    """svh_grid_archive_params"""
+    _fields_ = [("max_tiles", C.c_int32)]
+
+    def copy(self, **kw):
+        q = ArchiveParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -428,6 +447,18 @@ def _bind():
         L.svh_test_grid_dyn_through.argtypes = [C.POINTER(Params), C.POINTER(DynParams), C.c_int64] + [C.c_void_p] * 7
         L.svh_test_grid_dyn_settle.argtypes = [C.POINTER(Params), C.POINTER(DynParams), C.c_int32, C.c_int64] + [C.c_void_p] * 6
         L.svh_test_grid_dyn_colour.argtypes = [C.POINTER(Params), C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_void_p]
+        L.svh_grid_archive_params_default.argtypes = [C.POINTER(ArchiveParams)]
+        L.svh_grid_archive_params_default.restype = None
+        L.svh_grid_set_archive.argtypes = [C.c_void_p, C.POINTER(ArchiveParams)]
+        L.svh_grid_get_archive.argtypes = [C.c_void_p, C.POINTER(ArchiveParams)]
+        L.svh_grid_get_archive_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_archive_clear.argtypes = [C.c_void_p]
+        L.svh_grid_archive_trim.argtypes = [C.c_void_p] + [C.c_int32] * 4
+        L.svh_grid_archive_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.svh_grid_get_region.argtypes = [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_int32]
+        L.svh_grid_render_region.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32]
+        L.svh_test_grid_archive_key.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]
+        L.svh_test_grid_archive_strip.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_int64, C.c_void_p]
         L._grid_bound = True
     return L
 
@@ -1086,6 +1117,34 @@ def core_dyn_age(params, stamp, last):
     age = np.zeros(len(last), np.int32)
     _check(_bind().svh_test_grid_dyn_colour(C.byref(params), len(last), None, None, None, None, None, None, stamp, last.ctypes.data, age.ctypes.data))
     return age
+
+
+def default_archive(**kw):
+    p = ArchiveParams()
+    _bind().svh_grid_archive_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def core_archive_key(ga, gb, max_tiles=0):
+    """cell_key, the tile read back from it and tile_index of csrc/grid_archive_core.h on the host, per global cell: (key uint64,
+    tile int32 [n, 2] as (ta, tb), index uint32, archive_table_size(max_tiles))"""
+    ga, gb = np.ascontiguousarray(ga, np.int32).ravel(), np.ascontiguousarray(gb, np.int32).ravel()
+    n = len(ga)
+    key, tile, index, table = np.zeros(n, np.uint64), np.zeros((n, 2), np.int32), np.zeros(n, np.uint32), C.c_uint32(0)
+    _check(_bind().svh_test_grid_archive_key(n, ga.ctypes.data, gb.ctypes.data, key.ctypes.data, tile.ctypes.data, index.ctypes.data, max_tiles,
+                                             C.addressof(table)))
+    return key, tile, index, table.value
+
+
+def core_archive_strip(nx, nz, da, db):
+    """strip_cell of csrc/grid_archive_core.h on the host for every lane: int32 [n, 2] window cells (ia, ib) in lane order.  A scroll by
+    (da, db) leaves the strip of (da, db) in the old window and enters the strip of (-da, -db) in the new one"""
+    n = C.c_int64(0)
+    L = _bind()
+    _check(L.svh_test_grid_archive_strip(nx, nz, da, db, None, 0, C.addressof(n)))
+    cells = np.zeros((n.value, 2), np.int32)
+    _check(L.svh_test_grid_archive_strip(nx, nz, da, db, cells.ctypes.data, n.value, C.addressof(n)))
+    return cells
 
 
 def __getattr__(name):
@@ -1813,6 +1872,65 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_dyn(self._h, img.ctypes.data, 0))
+        return img
+
+    def set_archive(self, params=None, **kw):
+        """the archive: the parameters in force (or `params`) with the fields of kw replaced: max_tiles, 0 = off.  The cells that scroll
+        out of the window are kept by tiles of 16 x 16 and put back when the window returns"""
+        p = (params if params is not None else self.archive()).copy(**kw)
+        _check(self._L.svh_grid_set_archive(self._h, C.byref(p)))
+        return p
+
+    def archive(self):
+        p = ArchiveParams()
+        _check(self._L.svh_grid_get_archive(self._h, C.byref(p)))
+        return p
+
+    def archive_stats(self):
+        """dict of pages, max_tiles, stored, restored, lost, refused since the archive was last emptied"""
+        out = np.zeros(6, np.int64)
+        _check(self._L.svh_grid_get_archive_stats(self._h, out.ctypes.data))
+        return dict(zip(ARCHIVE_STATS, (int(v) for v in out)))
+
+    def archive_clear(self):
+        _check(self._L.svh_grid_archive_clear(self._h))
+
+    def archive_trim(self, ga0, gb0, ga1, gb1):
+        """drops every tile without a cell in the box of global cells, bounds inclusive"""
+        _check(self._L.svh_grid_archive_trim(self._h, ga0, gb0, ga1, gb1))
+
+    def archive_tiles(self, cap=None):
+        """int32 [n, 2]: the tiles (ta, tb) that have a page, ascending by (tb, ta)"""
+        n = C.c_int64(0)
+        if cap is None:
+            _check(self._L.svh_grid_archive_tiles(self._h, None, 0, C.addressof(n)))
+            cap = n.value
+        keys = np.zeros((max(cap, 1), 2), np.int32)
+        _check(self._L.svh_grid_archive_tiles(self._h, keys.ctypes.data, cap, C.addressof(n)))
+        return keys[:min(cap, n.value)].copy()
+
+    def region(self, which, ga0, gb0, w, h, kind=REGION_GRID, device_ptr=None):
+        """[h, w] of the plane's type over the box of global cells from (ga0, gb0), from the window and the archive together; kind
+        REGION_GRID: a plane of plane(), REGION_LOCAL: one of local_plane().  With device_ptr it is written there and None returned"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_region(self._h, kind, which, ga0, gb0, w, h, device_ptr, 1))
+            return None
+        dtypes = PLANE_DTYPE if kind == REGION_GRID else LOCAL_DTYPE
+        if kind not in (REGION_GRID, REGION_LOCAL) or not 0 <= which < len(dtypes) or not (1 <= w <= REGION_MAX_SIDE and 1 <= h <= REGION_MAX_SIDE):
+            raise SvhError(ERR_BAD_ARG, "no such plane or box")
+        out = np.zeros((h, w), dtypes[which])
+        _check(self._L.svh_grid_get_region(self._h, kind, which, ga0, gb0, w, h, out.ctypes.data, 0))
+        return out
+
+    def render_region(self, ga0, gb0, w, h, mode=RENDER_LOCAL, device_ptr=None):
+        """[h, w, 3] uint8 over the box, row 0 the farthest: render(mode), or render_local() with RENDER_LOCAL"""
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_region(self._h, mode, ga0, gb0, w, h, device_ptr, 1))
+            return None
+        if not (1 <= w <= REGION_MAX_SIDE and 1 <= h <= REGION_MAX_SIDE):
+            raise SvhError(ERR_BAD_ARG, "no such box")
+        img = np.zeros((h, w, 3), np.uint8)
+        _check(self._L.svh_grid_render_region(self._h, mode, ga0, gb0, w, h, img.ctypes.data, 0))
         return img
 
     def stats(self):

@@ -24,6 +24,7 @@ without the GUI.  Usage:
                                           [--grid-explore DIR [--grid-explore-range M]]
                                           [--grid-align DIR [--grid-align-apply] [--grid-align-window K,W]]
                                           [--grid-dynamic DIR [--grid-dynamic-params CLEAR,THROUGH,MARGIN,AGE]]
+                                         [--grid-archive DIR [--grid-archive-tiles N]]
                                           [--grid-objects DIR [--grid-objects-params MIN,MAX,HEIGHT,GATE,MISSED]]
                                           [--grid-predict DIR [--grid-predict-params SLOTS,STRIDE,MARGIN,GROW16]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
@@ -160,6 +161,12 @@ min_through, margin in metres and max_age of svh_grid_dyn_params; 2,3,0.1,0).  A
 local image, cells under contradiction tinted, cells the frame cleared or aged magenta) goes into DIR/dyn_%06d.ppm and one line {"frame",
 "observations", "cleared", "aged", "confirmed"}, the totals so far, is appended to DIR/dyn.jsonl.  With --grid-align-apply a corrected
 frame is observed under its correction.
+
+--grid-archive DIR: needs --grid-local; works with --grid-dynamic.  The local grid keeps the cells that scroll out of its window in
+tiles of 16 x 16 and puts them back when the window returns (svh_grid_set_archive; --grid-archive-tiles N: max_tiles, 16384).  After
+every local step one line {"frame", "window", "pages", "max_tiles", "stored", "restored", "lost", "refused"} is appended to
+DIR/archive.jsonl; at the end the mosaic -- svh_grid_render_region in the local colours over the bounding box of the window and of
+every tile that has a page, clipped to 8192 x 8192 cells round the window -- goes into DIR/mosaic.ppm.
 
 --lockstep K: K drives on one GPU, one frame of each per step, through the lockstep entries (LockstepPipeline): the K
 pairs are uploaded (or rectified, --unrectified) into one device buffer, then svh_vo_process_batch_device,
@@ -626,6 +633,21 @@ def main_lockstep(K, drive_dir, calib, limit, rp, normalize=False, thin=None, th
         finish_map(p.views[i], thin, name, "[%d] " % i)
 
 
+def mosaic_box(g):
+    """(ga0, gb0, w, h): the bounding box of the window and of every tile that has a page, clipped to 8192 x 8192 cells round the window"""
+    (oa, ob), tiles = g.window(), g.archive_tiles()
+    lo = [oa, ob]
+    hi = [oa + g.nx - 1, ob + g.nz - 1]
+    for axis, n in ((0, g.nx), (1, g.nz)):
+        if len(tiles):
+            lo[axis] = min(lo[axis], 16 * int(tiles[:, axis].min()))
+            hi[axis] = max(hi[axis], 16 * int(tiles[:, axis].max()) + 15)
+        if hi[axis] - lo[axis] + 1 > 8192:                # the cells beside the window are shared between its two sides
+            lo[axis] = max(lo[axis], (oa, ob)[axis] - (8192 - n) // 2)
+            hi[axis] = min(hi[axis], lo[axis] + 8191)
+    return lo[0], lo[1], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1
+
+
 def main():
     lockstep = 0
     if "--lockstep" in sys.argv:
@@ -654,6 +676,7 @@ def main():
     roll_dir, roll_kw = None, {}
     pose_dir, pose_kw = None, {}
     dyn_dir, dyn_kw = None, {}
+    archive_dir, archive_tiles = None, None
     obj_dir, obj_kw = None, {}
     pred_dir, pred_kw = None, {}
     level = "--level" in sys.argv
@@ -765,6 +788,15 @@ def main():
             dyn_kw = dict(clear_frames=int(v[0]), min_through=int(v[1]), margin=float(v[2]), max_age=int(v[3]))
             assert 0 <= dyn_kw["clear_frames"] <= 65535 and dyn_kw["min_through"] >= 1 and 0 <= dyn_kw["margin"] < 2 ** 20 and dyn_kw["max_age"] >= 0
             del sys.argv[k:k + 2]
+        if "--grid-archive" in sys.argv:
+            k = sys.argv.index("--grid-archive")
+            archive_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-archive-tiles" in sys.argv:
+            k = sys.argv.index("--grid-archive-tiles")
+            archive_tiles = int(sys.argv[k + 1])
+            assert 1 <= archive_tiles <= 2 ** 20
+            del sys.argv[k:k + 2]
         if "--grid-objects" in sys.argv:
             k = sys.argv.index("--grid-objects")
             obj_dir = sys.argv[k + 1]
@@ -793,6 +825,8 @@ def main():
         assert local_dir or not obj_dir
         assert obj_dir or not obj_kw
         assert local_dir or not dyn_dir
+        assert local_dir or not archive_dir
+        assert archive_dir or archive_tiles is None
         assert dyn_dir or not dyn_kw
         assert local_dir or not align_dir
         assert align_dir or not (align_apply or align_window)
@@ -883,6 +917,9 @@ def main():
     if align_dir:
         os.makedirs(align_dir, exist_ok=True)
         open(os.path.join(align_dir, "align.jsonl"), "w").close()
+    if archive_dir:
+        os.makedirs(archive_dir, exist_ok=True)
+        open(os.path.join(archive_dir, "archive.jsonl"), "w").close()
     if dyn_dir:
         os.makedirs(dyn_dir, exist_ok=True)
         open(os.path.join(dyn_dir, "dyn.jsonl"), "w").close()
@@ -904,6 +941,8 @@ def main():
         p.enable_grid_align(align_apply, align_window or (8, 8))
     if dyn_dir:
         p.enable_grid_dynamic(**dyn_kw)
+    if archive_dir:
+        p.local.set_archive(max_tiles=archive_tiles or grid.ARCHIVE_DEFAULT_TILES)
     if obj_dir:
         p.local.set_objects(**obj_kw)
     if cost_dir:
@@ -944,6 +983,9 @@ def main():
             view.write_ppm(os.path.join(dyn_dir, "dyn_%06d.ppm" % (frames - 1)), p.local.render_dyn())
             with open(os.path.join(dyn_dir, "dyn.jsonl"), "a") as f:
                 f.write(json.dumps(dict(p.local.dyn_stats(), frame=frames - 1)) + "\n")
+        if archive_dir:
+            with open(os.path.join(archive_dir, "archive.jsonl"), "a") as f:
+                f.write(json.dumps(dict(p.local.archive_stats(), frame=frames - 1, window=list(p.local.window()))) + "\n")
         if obj_dir:
             p.local.objects_step(0)
             view.write_ppm(os.path.join(obj_dir, "objects_%06d.ppm" % (frames - 1)), p.local.render_objects())
@@ -1024,6 +1066,11 @@ def main():
         d, ds = p.local.dynamics(), p.local.dyn_stats()
         print("dynamics: clear after %d frames of %d through-lines, margin %g m, age %d: %d observations, %d cells cleared, %d aged; %d images and dyn.jsonl in %s" % (
             d.clear_frames, d.min_through, d.margin, d.max_age, ds["observations"], ds["cleared"], ds["aged"], frames, dyn_dir))
+    if archive_dir:
+        box, st = mosaic_box(p.local), p.local.archive_stats()
+        view.write_ppm(os.path.join(archive_dir, "mosaic.ppm"), p.local.render_region(*box))
+        print("archive: %d of %d pages in use, %d cells stored, %d restored, %d lost in %d refused calls; archive.jsonl and a mosaic of %d x %d cells from (%d, %d) in %s" % (
+            st["pages"], st["max_tiles"], st["stored"], st["restored"], st["lost"], st["refused"], box[2], box[3], box[0], box[1], archive_dir))
     if obj_dir:
         o, os_, ts = p.local.objects_params(), p.local.object_stats(), p.local.track_stats()
         print("objects: size %d..%d, height %g m, gate %d cells, %d misses: %d kept of %d components in the last frame, %d tracks after %d steps; "
