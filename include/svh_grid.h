@@ -583,4 +583,5 @@ int32_t   svh_grid_render_dyn(svh_grid* g, uint8_t* rgb, int32_t on_device);
 #include "svh_grid_pred.h"  /* PREDICTION: the tracks carried ahead in time slots, and the rollouts scored against them */
 #include "svh_grid_pose.h"  /* POSE PLANNING: cost-to-go and paths over cell x heading under the vehicle's footprint */
 #include "svh_grid_archive.h"   /* ARCHIVE: cells that scroll out are kept and restored on return; planes over any box of global cells */
+#include "svh_grid_time.h"  /* TIME: cost-to-go and paths over cell x time that wait for the predicted objects */
 #endif

@@ -22,7 +22,7 @@
  * them -- no add, observation, scroll, follow or clear, and no other layer's parameters, goals or candidates.  After SVH_ERR_HIP in
  * an entry of this layer the accumulated grid, the tracks and every other layer are untouched; PRED is invalid and computed again by
  * the next call.  svh_grid_render_roll keeps drawing the last svh_grid_roll_score only.
- * A moving object's present cells stay lethal in COST: this layer does not release them.
+ * A moving object's present cells stay lethal in COST: this layer does not release them (svh_grid_time.h does, in a cost map of its own).
  */
 #ifndef SVH_GRID_PRED_H
 #define SVH_GRID_PRED_H

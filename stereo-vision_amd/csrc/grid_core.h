@@ -374,31 +374,38 @@ MC_FN void colour_cost(uint8_t cost, uint8_t flags, uint8_t* rgb) {
 
 // The whole layer on the host (svh_test_grid_trav, tests/cxx/grid_trav_check.cpp): the planes of a window from CLASS,
 // HMEAN and STATE.  `table` has reach^2 + 1 bytes, `g` is nx * nz of scratch; any of dist2, cost may be null.
-inline void trav_window(const TravParams& t, int32_t nx, int32_t nz, const uint8_t* cls, const float* hmean, const uint8_t* state,
-                        const uint8_t* table, uint8_t* flags, uint16_t* g, int32_t* dist2, uint8_t* cost) {
-    for (int32_t ib = 0; ib < nz; ib++)
-        for (int32_t ia = 0; ia < nx; ia++) flags[(size_t)ib * nx + ia] = trav_flags(t, nx, nz, cls, hmean, state, ia, ib);
+// The column and row passes alone, on a FLAGS plane that exists: DIST2 -> table -> cell_cost.  The time layer
+// (grid_time_core.h) runs them on a FLAGS plane of its own.
+inline void dist_window(int32_t reach, int32_t nx, int32_t nz, const uint8_t* cls, const uint8_t* table, const uint8_t* flags, uint16_t* g,
+                        int32_t* dist2, uint8_t* cost) {
     for (int32_t ia = 0; ia < nx; ia++) {
-        int32_t d = t.reach + 1;
+        int32_t d = reach + 1;
         for (int32_t ib = 0; ib < nz; ib++) {
             const size_t i = (size_t)ib * nx + ia;
-            g[i] = (uint16_t)(d = col_step(d, (flags[i] & TF_LETHAL) != 0, t.reach));
+            g[i] = (uint16_t)(d = col_step(d, (flags[i] & TF_LETHAL) != 0, reach));
         }
-        d = t.reach + 1;
+        d = reach + 1;
         for (int32_t ib = nz - 1; ib >= 0; ib--) {
             const size_t i = (size_t)ib * nx + ia;
-            d = col_step(d, (flags[i] & TF_LETHAL) != 0, t.reach);
+            d = col_step(d, (flags[i] & TF_LETHAL) != 0, reach);
             g[i] = (uint16_t)(d < (int32_t)g[i] ? d : (int32_t)g[i]);
         }
     }
     for (int32_t ib = 0; ib < nz; ib++)
         for (int32_t ia = 0; ia < nx; ia++) {
             const size_t i = (size_t)ib * nx + ia;
-            const int32_t lo = ia - t.reach < 0 ? 0 : ia - t.reach, hi = ia + t.reach > nx - 1 ? nx - 1 : ia + t.reach;
-            const int32_t d2 = row_dist2(g + (size_t)ib * nx, 0, ia, lo, hi, t.reach);
+            const int32_t lo = ia - reach < 0 ? 0 : ia - reach, hi = ia + reach > nx - 1 ? nx - 1 : ia + reach;
+            const int32_t d2 = row_dist2(g + (size_t)ib * nx, 0, ia, lo, hi, reach);
             if (dist2) dist2[i] = d2;
             if (cost) cost[i] = cell_cost(d2 == DIST2_FAR ? (uint8_t)0 : table[d2], cls[i], flags[i]);
         }
+}
+
+inline void trav_window(const TravParams& t, int32_t nx, int32_t nz, const uint8_t* cls, const float* hmean, const uint8_t* state,
+                        const uint8_t* table, uint8_t* flags, uint16_t* g, int32_t* dist2, uint8_t* cost) {
+    for (int32_t ib = 0; ib < nz; ib++)
+        for (int32_t ia = 0; ia < nx; ia++) flags[(size_t)ib * nx + ia] = trav_flags(t, nx, nz, cls, hmean, state, ia, ib);
+    dist_window(t.reach, nx, nz, cls, table, flags, g, dist2, cost);
 }
 
 // the checks behind SVH_ERR_BAD_ARG of svh_grid_create

@@ -14,7 +14,9 @@
 // (grid_explore_kernels.hip): the exploration layer -- the gain of viewpoints, the ranking of the frontiers, run by explore_rank() here;
 // (grid_align_kernels.hip): the alignment layer -- the field, the scan of a frame's obstacle points, the volume of scores, run by align() here;
 // (grid_dyn_kernels.hip): the dynamics -- the sight lines and the settle of an observation, run by observe() here;
-// (grid_archive_kernels.hip): the archive -- the leaving and entering passes of a scroll, run by scroll() here, and the region reader.
+// (grid_archive_kernels.hip): the archive -- the leaving and entering passes of a scroll, run by scroll() here, and the region reader;
+// (grid_time_kernels.hip): the time layer -- the release of the predicting tracks' cells, the sweep over cell x layer, run by
+// time_static() and time_field() here.
 // The arithmetic is csrc/grid_core.h.  The object has its own stream; every entry returns when it is complete.
 //
 // The accumulators are cleared lazily: svh_grid_clear, svh_grid_set_window and an add that failed only mark the grid
@@ -73,6 +75,8 @@ constexpr size_t kTravBytes = 8;                   // per cell: DIST2; g (uint16
 constexpr size_t kPlanBytes = 7;                   // per cell: POT; price (uint16); DIR
 constexpr size_t kFrontBytes = 5;                  // per cell: LABEL; FRONT
 constexpr size_t kPoseBytes = 8;                   // per state: PPOT; price (uint16); PDIR; CF
+constexpr size_t kTimeStaticBytes = 11;            // per cell: RPOT; price (uint16); g (uint16); RDIR, RCOST, FLAGS'
+constexpr size_t kTimeBytes = 5;                   // per state: TPOT; TDIR
 // rounds of the relaxation enqueued per wait: a round whose list is empty costs one empty launch, a wait costs a round trip,
 // and the bound on the workgroups of a round grows with its distance from the last known length.  Measured alternating in one
 // process at 1, 2, 4, 8 and 16 (profiles/grid_plan_times.jsonl; ms on an open field of 256^2 / 1024^2 / 8192^2 cells):
@@ -193,22 +197,26 @@ enum Kept : uint32_t {
     POSE_CF = 1u << 7,    // the CF planes of `pose`, from COST and the footprint table: a bit of its own, so that new goals or pose
                           // parameters do not run k_grid_pose_foot again
     POSE = 1u << 8,       // PPOT, the prices and PDIR of `pose` and their statistics, from CF, the pose parameters and the pose goals
-    UP_TABLE = 1u << 9,   // d_table holds `table`
-    UP_GOALS = 1u << 10,  // d_goals holds `goals`
-    UP_ROLL = 1u << 11,   // roll_bufs.offs and .start hold the footprint table
-    UP_CANDS = 1u << 12,  // d_cands and d_cand_lens hold the candidates
-    ROLL_LAST = 1u << 13, // roll_bufs.recs holds the records of the last svh_grid_roll_score
-    ALIGN_LAST = 1u << 14,// al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
-    PRED = 1u << 15,      // pred.plane and its statistics, from the track state and the prediction parameters: not a derived layer, the
+    TIME_STATIC = 1u << 9,// RCOST, RPOT, RDIR of `tstat` and the released count, from FLAGS and COST and the planner's field (whatever makes
+                          // PLAN stale makes them stale) and, only when release = 1, from the tracks and the prediction parameters
+                          // (kDropsReleased below)
+    TIME = 1u << 10,      // TPOT, TDIR of `tfield` and their statistics, from the static planes, PRED and the time parameters
+    UP_TABLE = 1u << 11,  // d_table holds `table`
+    UP_GOALS = 1u << 12,  // d_goals holds `goals`
+    UP_ROLL = 1u << 13,   // roll_bufs.offs and .start hold the footprint table
+    UP_CANDS = 1u << 14,  // d_cands and d_cand_lens hold the candidates
+    ROLL_LAST = 1u << 15, // roll_bufs.recs holds the records of the last svh_grid_roll_score
+    ALIGN_LAST = 1u << 16,// al.scan and al.volume hold the scan and (unless FEW) the volume of the last alignment
+    PRED = 1u << 17,      // pred.plane and its statistics, from the track state and the prediction parameters: not a derived layer, the
                           // accumulators do not reach it
-    UP_POSE_GOALS = 1u << 16   // d_pose_goals holds `pose_goals`
+    UP_POSE_GOALS = 1u << 18   // d_pose_goals holds `pose_goals`
 };
-constexpr int kLayers = 9;
+constexpr int kLayers = 11;
 constexpr uint32_t kAllLayers = (1u << kLayers) - 1;
 // the layers each derived layer is computed from, by the layer's bit number
-constexpr uint32_t kNeeds[kLayers] = {0, FINAL, TRAV, TRAV, TRAV, FINAL, FINAL, TRAV, POSE_CF};
+constexpr uint32_t kNeeds[kLayers] = {0, FINAL, TRAV, TRAV, TRAV, FINAL, FINAL, TRAV, POSE_CF, TRAV | PLAN, TIME_STATIC};
 // what changes, and what it makes stale directly; the layers computed from a stale layer follow by closure()
-enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, OBJ_PARAMS, TRACKS, PRED_PARAMS, POSE_PARAMS, POSE_GOALS, SOURCES };
+enum Source { ACC, TRAV_PARAMS, PLAN_PARAMS, GOALS, FRONT_PARAMS, ROLL_PARAMS, CANDS, ALIGN_PARAMS, OBJ_PARAMS, TRACKS, PRED_PARAMS, POSE_PARAMS, POSE_GOALS, TIME_PARAMS, SOURCES };
 constexpr uint32_t kDrops[SOURCES] = {
     FINAL,                    // ACC: the accumulators or the window's offsets
     TRAV | UP_TABLE,          // TRAV_PARAMS
@@ -219,11 +227,16 @@ constexpr uint32_t kDrops[SOURCES] = {
     UP_CANDS | ROLL_LAST,     // CANDS: the candidate table
     AFIELD | ALIGN_LAST,      // ALIGN_PARAMS
     OBJ,                      // OBJ_PARAMS
-    PRED,                     // TRACKS: the track table or the ID plane: a step, or anything that empties the tracks
-    PRED,                     // PRED_PARAMS
+    PRED | TIME,              // TRACKS: the track table or the ID plane: a step, or anything that empties the tracks
+    PRED | TIME,              // PRED_PARAMS
     POSE,                     // POSE_PARAMS
     POSE | UP_POSE_GOALS,     // POSE_GOALS
+    TIME,                     // TIME_PARAMS; a new `release` drops kDropsNewRelease too (svh_grid_set_time)
 };
+// what a source makes stale beside that while the time layer's release = 1: the released cells are those of the predicting tracks
+constexpr uint32_t kDropsReleased[SOURCES] = {0, 0, 0, 0, 0, 0, 0, 0, 0, TIME_STATIC, TIME_STATIC, 0, 0, 0};
+// what svh_grid_set_time drops beside kDrops[TIME_PARAMS] when `release` itself changes
+constexpr uint32_t kDropsNewRelease = TIME_STATIC;
 constexpr uint32_t closure(uint32_t m) {
     for (int pass = 0; pass < kLayers; pass++)
         for (int k = 0; k < kLayers; k++)
@@ -240,7 +253,7 @@ constexpr StaleTable stale_table() {
 }
 constexpr StaleTable kStale = stale_table();
 static_assert((kStale.of[ACC] & kAllLayers) == kAllLayers, "a derived layer without a path to FINAL in kNeeds would survive a change of the accumulators");
-static_assert(kStale.of[TRAV_PARAMS] == (TRAV | PLAN | FRONT | REACH | POSE_CF | POSE | UP_TABLE), "the closure of kNeeds");
+static_assert(kStale.of[TRAV_PARAMS] == (TRAV | PLAN | FRONT | REACH | POSE_CF | POSE | TIME_STATIC | TIME | UP_TABLE), "the closure of kNeeds");
 static_assert(kStale.of[ROLL_PARAMS] == (UP_ROLL | ROLL_LAST | POSE_CF | POSE) && kStale.of[POSE_PARAMS] == POSE && kStale.of[POSE_GOALS] == (POSE | UP_POSE_GOALS),
               "the pose field follows the vehicle, its own parameters and its own goals");
 static_assert(!((kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[OBJ_PARAMS] |
@@ -248,9 +261,16 @@ static_assert(!((kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PAR
 static_assert(kStale.of[OBJ_PARAMS] == OBJ && (kStale.of[ACC] & OBJ), "the objects follow the accumulators and their own parameters");
 static_assert(!((kStale.of[TRAV_PARAMS] | kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[ROLL_PARAMS] |
                  kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[POSE_PARAMS] | kStale.of[POSE_GOALS]) & OBJ), "no other layer's source makes the objects stale");
-static_assert(kStale.of[TRACKS] == PRED && kStale.of[PRED_PARAMS] == PRED, "the prediction follows the tracks and its own parameters");
+static_assert(kStale.of[TRACKS] == (PRED | TIME) && kStale.of[PRED_PARAMS] == (PRED | TIME), "the prediction follows the tracks and its own parameters, and TIME follows it");
+static_assert(kStale.of[PLAN_PARAMS] == (PLAN | REACH | TIME_STATIC | TIME) && kStale.of[GOALS] == (PLAN | UP_GOALS | TIME_STATIC | TIME) && kStale.of[TIME_PARAMS] == TIME,
+              "the time layer follows the planner's field and its own parameters; its setter makes no other layer stale");
+static_assert(!((kStale.of[FRONT_PARAMS] | kStale.of[ROLL_PARAMS] | kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[OBJ_PARAMS] | kStale.of[POSE_PARAMS] |
+                 kStale.of[POSE_GOALS]) & (TIME | TIME_STATIC)), "the frontiers, the rollouts, the candidates, the alignment, the object parameters and the pose planner leave TIME alone");
+static_assert(!((kStale.of[TRACKS] | kStale.of[PRED_PARAMS]) & TIME_STATIC) && kDropsReleased[TRACKS] == TIME_STATIC && kDropsReleased[PRED_PARAMS] == TIME_STATIC,
+              "with release = 0 a step keeps the static planes; with release = 1 it drops them");
+static_assert(kDropsReleased[TIME_PARAMS] == 0 && closure(kDropsNewRelease) == (TIME_STATIC | TIME), "a new wait or L keeps the static planes; a new release drops them and the field, nothing else");
 static_assert(!((kStale.of[ACC] | kStale.of[TRAV_PARAMS] | kStale.of[PLAN_PARAMS] | kStale.of[GOALS] | kStale.of[FRONT_PARAMS] | kStale.of[ROLL_PARAMS] |
-                 kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[OBJ_PARAMS] | kStale.of[POSE_PARAMS] | kStale.of[POSE_GOALS]) & PRED), "nothing else makes the prediction stale");
+                 kStale.of[CANDS] | kStale.of[ALIGN_PARAMS] | kStale.of[OBJ_PARAMS] | kStale.of[POSE_PARAMS] | kStale.of[POSE_GOALS] | kStale.of[TIME_PARAMS]) & PRED), "nothing else makes the prediction stale");
 
 }  // namespace
 
@@ -353,6 +373,19 @@ struct svh_grid {
     PinnedBuf<uint32_t> h_pose_ctl;
     int64_t pose_counted = 0, pose_reached = 0, pose_rounds = 0;   // of the field that is valid
     HipBuf<int32_t> d_pose_path;   // the poses a walk writes, or a caller's for the pose image
+    bool time_on = false;       // the time layer: svh_grid_set_time has succeeded
+    grid::TimeParams tmp{32, 100, 1};
+    HipBuf<uint8_t> tstat;      // kTimeStaticBytes per cell: RPOT | price | g | RDIR | RCOST | FLAGS', logical order; written only when cells are released
+    HipBuf<uint32_t> tstat_tiles, tstat_ctl;   // as plan_tiles and plan_ctl
+    PinnedBuf<uint32_t> h_tstat_ctl;
+    HipBuf<uint8_t> tfield;     // kTimeBytes per state: TPOT | TDIR, layer-major planes.  While TIME is stale the first plane of TPOT is also the
+                                // DIST2 scratch of time_static's distance pass: TIME is stale whenever TIME_STATIC is (kNeeds)
+    HipBuf<unsigned long long> time_ctl;   // grid::TC_WORDS
+    PinnedBuf<unsigned long long> h_time_ctl;
+    bool time_own = false;      // TIME_STATIC: the static planes are those of `tstat`; false: the planner's
+    int64_t time_released = 0, time_rounds = 0;   // TIME_STATIC: the released cells, the rounds of RPOT
+    int64_t time_stats[grid::TM_WORDS] = {0, 0, 0, 0, 0, 0};   // TIME
+    HipBuf<int32_t> d_time_path;   // the triples a walk writes, or a caller's for the time image
     int32_t arch_tiles = 0;     // the archive: max_tiles, 0 = off
     HipBuf<uint8_t> arch_pool;  // PAGE_BYTES per tile: kmin | kmax | count | overhead | hsum | vsum | pass | CONTRA | LAST, a plane each; first use
     HipBuf<unsigned long long> arch_keys, arch_ctl, arch_skeys;   // the table's keys, the control words, the kept keys of a trim
@@ -385,6 +418,14 @@ struct svh_grid {
     uint16_t* q_price() const { return (uint16_t*)(pose.p + 32 * ncells); }
     uint8_t* q_dir() const { return pose.p + 48 * ncells; }
     uint8_t* q_cf() const { return pose.p + 56 * ncells; }
+    int32_t* s_pot() const { return (int32_t*)tstat.p; }
+    uint16_t* s_price() const { return (uint16_t*)(tstat.p + 4 * ncells); }
+    uint16_t* s_g() const { return (uint16_t*)(tstat.p + 6 * ncells); }
+    uint8_t* s_dir() const { return tstat.p + 8 * ncells; }
+    uint8_t* s_cost() const { return tstat.p + 9 * ncells; }
+    uint8_t* s_flags() const { return tstat.p + 10 * ncells; }
+    int32_t* t_pot() const { return (int32_t*)tfield.p; }
+    uint8_t* t_dir() const { return tfield.p + 4 * ncells * (size_t)tmp.layers; }
     int32_t* o_label() const { return (int32_t*)obj.p; }
     uint8_t* o_flags() const { return obj.p + 4 * ncells; }
     grid::DynPlanes dplanes() const {
@@ -420,7 +461,8 @@ bool has(const svh_grid* g, uint32_t kept) { return (g->valid & kept) == kept; }
 void drop(svh_grid* g, uint32_t kept) { g->valid &= ~kept, g->pending &= ~kept; }
 
 // `s` changes: what the table derives from it is stale
-void touch(svh_grid* g, Source s) { drop(g, kStale.of[s]); }
+// while the time layer is on with release = 1, what kDropsReleased adds (TIME_STATIC is never set while the layer is off)
+void touch(svh_grid* g, Source s) { drop(g, kStale.of[s] | ((g->time_on && g->tmp.release) ? closure(kDropsReleased[s]) : 0u)); }
 
 // the entry has waited for everything it launched: the layers among it count
 void settle(svh_grid* g) {
@@ -442,7 +484,7 @@ int failed(svh_grid* g, int rc, uint32_t kept = 0) {
     return rc;
 }
 // what each family of entries drops there
-constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST, kObjects = OBJ, kPrediction = PRED, kPose = POSE | POSE_CF;
+constexpr uint32_t kPlanner = PLAN, kFrontier = FRONT, kRollouts = ROLL_LAST, kExploration = REACH, kAlign = AFIELD | ALIGN_LAST, kObjects = OBJ, kPrediction = PRED, kPose = POSE | POSE_CF, kTime = TIME | TIME_STATIC;
 
 // the tracks are empty and the ids start again at 0
 void forget_tracks(svh_grid* g) {
@@ -1819,6 +1861,319 @@ bool pose_test_args(const svh_grid_roll_params* r, const svh_grid_pose_params* p
     return *t != nullptr;
 }
 
+// ---- the time layer -----------------------------------------------------------------------------------------------------------
+bool convert_time(const svh_grid_time_params* p, grid::TimeParams* q) {
+    if (!p) return false;
+    *q = grid::TimeParams{p->layers, p->wait, p->release};
+    return grid::time_ok(*q);
+}
+
+const char* time_refusal(const svh_grid* g) {
+    if (!g->time_on) return ": the time layer is off; switch it on (svh_grid_set_time)";
+    if (!g->trav_ok) return kNoTrav;
+    if (!grid::time_fits(g->tmp, g->prm.nx, g->prm.nz)) return ": layers * nx * nz exceeds 2^28";
+    return nullptr;
+}
+
+// FLAGS' and the released cells on buffers that exist: one launch and one wait, the count through `h_ctl` (pinned)
+int time_release_run(hipStream_t s, const grid::TimeReleaseJob& j, unsigned long long* h_ctl, int64_t* released) {
+    GRID_TRY(copy, hipMemsetAsync(j.ctl, 0, grid::TC_WORDS * sizeof(unsigned long long), s));
+    GRID_TRY(launch, (grid::launch_time_release(s, j), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(h_ctl, j.ctl, grid::TC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    *released = (int64_t)h_ctl[grid::TC_RELEASED];
+    return SVH_OK;
+}
+
+// RCOST over FLAGS' by the two distance launches, then the planner on it, a job with buffers of its own; complete when it returns
+int time_static_run(hipStream_t s, const grid::TravJob& tj, const grid::PlanJob& pj, uint32_t* h_ctl) {
+    GRID_TRY(launch, (grid::launch_trav_dist(s, tj), hipGetLastError()));
+    return plan_run(s, pj, h_ctl);
+}
+
+// the sweep on static planes and a PRED plane that are written in stream order; the control words of the statistics are in `h_ctl`
+// (pinned) when it returns
+int time_sweep_run(hipStream_t s, const grid::TimeJob& j, unsigned long long* h_ctl) {
+    GRID_TRY(copy, hipMemsetAsync(j.ctl + grid::TC_REACHED, 0, (grid::TC_WORDS - grid::TC_REACHED) * sizeof(unsigned long long), s));
+    GRID_TRY(launch, ((void)grid::launch_time_sweep(s, j), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(h_ctl, j.ctl, grid::TC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    GRID_TRY(wait, hipStreamSynchronize(s));
+    return SVH_OK;
+}
+
+// the buffers of the layer exist
+int time_ready(svh_grid* g) {
+    GRID_GROW(g->tfield, g->ncells * (size_t)g->tmp.layers * kTimeBytes);
+    GRID_GROW(g->time_ctl, grid::TC_WORDS * sizeof(unsigned long long));
+    GRID_GROW(g->h_time_ctl, grid::TC_WORDS * sizeof(unsigned long long));
+    return SVH_OK;
+}
+
+// The static planes are valid; complete when it returns.  The planner's field comes first, always: while no cell is released it IS
+// RPOT and RDIR and nothing is computed twice, and it must be current whenever they are read.  With cells to release: FLAGS', the two
+// distance launches on it, and the planner's seed, rounds and DIR on a job of the layer's own, as the reach field's.  DIST2 of that
+// pass is scratch and goes where TPOT will be written.
+int time_static(svh_grid* g) {
+    int rc = plan_field(g);
+    if (rc || has(g, TIME_STATIC)) return rc;
+    bool own = false;
+    int64_t released = 0, rounds = g->plan_rounds;
+    const int32_t n = (g->tmp.release && g->trk_plane) ? g->trk_n : 0;
+    if (n > 0) {
+        if ((rc = time_ready(g))) return rc;
+        GRID_GROW(g->tstat, g->ncells * kTimeStaticBytes);
+        grid::TimeReleaseJob rj;
+        rj.pp = g->prp;
+        rj.nx = g->prm.nx, rj.nz = g->prm.nz, rj.oa = g->prm.oa, rj.ob = g->prm.ob, rj.poa = pred_oa(g), rj.pob = pred_ob(g);
+        rj.id = g->trk.id[g->trk_cur].p, rj.tracks = g->trk.table[g->trk_cur].p, rj.n_tracks = n;
+        rj.flags = g->t_flags(), rj.out = g->s_flags(), rj.ctl = g->time_ctl.p;
+        if ((rc = time_release_run(g->stream, rj, g->h_time_ctl, &released))) return rc;
+    }
+    if (released > 0) {
+        const size_t tiles = plan_tiles(g->prm);
+        GRID_GROW(g->tstat_tiles, 4 * tiles * sizeof(uint32_t));
+        GRID_GROW(g->tstat_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+        GRID_GROW(g->h_tstat_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+        grid::TravJob tj;
+        tj.trv = g->trv;
+        tj.nx = g->prm.nx, tj.nz = g->prm.nz;
+        tj.cls = g->bplane(B_CLASS), tj.hmean = nullptr, tj.state = nullptr;
+        tj.table = g->d_table.p;
+        static_assert(kTimeBytes >= sizeof(int32_t) && (kNeeds[10] & TIME_STATIC), "DIST2 of this pass is scratch in TPOT: the field has room for it and is stale with the static planes");
+        drop(g, TIME);   // ... and says so itself: what is written below overwrites layer 0 of TPOT
+        tj.flags = g->s_flags(), tj.g = g->s_g(), tj.dist2 = g->t_pot(), tj.cost = g->s_cost();
+        grid::PlanJob pj = plan_job(g);
+        pj.cost = g->s_cost();
+        pj.price = g->s_price(), pj.pot = g->s_pot(), pj.dir = g->s_dir();
+        pj.lists = g->tstat_tiles.p, pj.flags = g->tstat_tiles.p + 2 * tiles;
+        pj.ctl = g->tstat_ctl.p;
+        if ((rc = time_static_run(g->stream, tj, pj, g->h_tstat_ctl))) return rc;
+        own = true, rounds = g->h_tstat_ctl[grid::CTL_ROUNDS];
+    }
+    g->time_own = own, g->time_released = released, g->time_rounds = rounds;
+    g->pending |= TIME_STATIC;
+    settle(g);
+    return SVH_OK;
+}
+
+grid::TimeJob time_job(const svh_grid* g) {
+    grid::TimeJob j;
+    j.pln = g->pln, j.tp = g->tmp, j.pp = g->prp;
+    j.nx = g->prm.nx, j.nz = g->prm.nz, j.oa = g->prm.oa, j.ob = g->prm.ob, j.poa = pred_oa(g), j.pob = pred_ob(g);
+    j.price = g->time_own ? g->s_price() : g->p_price(), j.rpot = g->time_own ? g->s_pot() : g->p_pot(), j.rdir = g->time_own ? g->s_dir() : g->p_dir();
+    j.pred = g->pred.plane;
+    j.tpot = g->t_pot(), j.tdir = g->t_dir();
+    j.ctl = g->time_ctl.p;
+    return j;
+}
+
+// the field is valid: the static planes, PRED, then the sweep; complete when it returns
+int time_field(svh_grid* g) {
+    int rc = time_static(g);
+    if (rc || has(g, TIME)) return rc;
+    if ((rc = time_ready(g)) || (rc = predict(g))) return rc;
+    if ((rc = time_sweep_run(g->stream, time_job(g), g->h_time_ctl))) return rc;
+    const unsigned long long* h = g->h_time_ctl;
+    g->time_stats[grid::TM_LAYERS] = g->tmp.layers, g->time_stats[grid::TM_REACHED] = (int64_t)h[grid::TC_REACHED];
+    g->time_stats[grid::TM_BLOCKED] = (int64_t)h[grid::TC_BLOCKED], g->time_stats[grid::TM_WAITS] = (int64_t)h[grid::TC_WAITS];
+    g->pending |= TIME;
+    settle(g);
+    return SVH_OK;
+}
+
+int get_time_plane(svh_grid* g, int32_t plane, int32_t t0, int32_t count, void* out, bool on_device) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if (plane == grid::TP_RCOST || plane == grid::TP_RPOT) {
+        if ((rc = time_static(g))) return rc;
+        return plane == grid::TP_RCOST ? deliver(g, g->time_own ? g->s_cost() : g->t_cost(), g->ncells, out, on_device)
+                                       : deliver(g, g->time_own ? g->s_pot() : g->p_pot(), g->ncells * 4, out, on_device);
+    }
+    if ((rc = time_field(g))) return rc;
+    return plane == grid::TP_TPOT ? deliver(g, g->t_pot() + (size_t)t0 * g->ncells, (size_t)count * g->ncells * 4, out, on_device)
+                                  : deliver(g, g->t_dir() + (size_t)t0 * g->ncells, (size_t)count * g->ncells, out, on_device);
+}
+
+// `n` triples from the host to d_time_path through the pinned staging buffer, and the wait
+int send_triples(svh_grid* g, const int32_t* triples, int64_t n) {
+    const size_t bytes = (size_t)n * 3 * sizeof(int32_t);
+    GRID_GROW(g->d_time_path, bytes);
+    GRID_GROW(g->h_cells, bytes);
+    memcpy(g->h_cells, triples, bytes);
+    GRID_TRY(copy, hipMemcpyAsync(g->d_time_path, g->h_cells, bytes, hipMemcpyHostToDevice, g->stream));
+    GRID_TRY(wait, hipStreamSynchronize(g->stream));   // the staging buffer is free again
+    return SVH_OK;
+}
+
+// the walk from the window cell (a, b) at layer 0
+int time_path(svh_grid* g, int32_t a, int32_t b, int32_t* triples, int64_t cap, int64_t* len, int32_t* cost, int32_t* status) {
+    int rc = ready(g);
+    if (rc) return rc;
+    if ((rc = time_field(g))) return rc;
+    const int64_t room = std::min<int64_t>(cap, (int64_t)g->ncells + g->tmp.layers);   // a path has at most L + nx * nz entries
+    GRID_GROW_N(g->d_time_path, 3 * room);
+    GRID_GROW(g->d_walk, 3 * sizeof(int64_t));
+    GRID_GROW(g->h_walk, 3 * sizeof(int64_t));
+    GRID_TRY(launch, (grid::launch_time_walk(g->stream, time_job(g), a, b, g->d_time_path, room, g->d_walk), hipGetLastError()));
+    GRID_TRY(copy, hipMemcpyAsync(g->h_walk, g->d_walk, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    GRID_TRY(wait, hipStreamSynchronize(g->stream));
+    const int64_t n = g->h_walk[1], m = std::min(n, room);
+    if (m > 0 && (rc = deliver(g, g->d_time_path, (size_t)m * 3 * sizeof(int32_t), triples, false))) return rc;
+    *status = (int32_t)g->h_walk[0], *len = n, *cost = (int32_t)g->h_walk[2];
+    return SVH_OK;
+}
+
+int render_time(svh_grid* g, int32_t t, const int32_t* triples, int64_t n, uint8_t* rgb, bool on_device) {
+    return render_with(g, rgb, on_device, false, [&](uint8_t* dst) {
+        int rc = time_field(g);
+        if (rc || (n > 0 && (rc = send_triples(g, triples, n)))) return rc;
+        const grid::TimeJob tj = time_job(g);
+        grid::RenderCostJob cj = cost_job(g, dst);
+        if (g->time_own) cj.cost = g->s_cost(), cj.flags = g->s_flags();
+        grid::launch_render_cost(g->stream, cj);
+        grid::launch_time_overlay(g->stream, tj, t, g->d_goals.p, (int32_t)(g->goals.size() / 2), g->d_time_path, n, dst);
+        return rc;
+    });
+}
+
+// the arguments of the two test entries of the layer, checked and converted
+struct TimeTestArgs {
+    grid::PlanParams pln;
+    grid::PredParams pp;
+    grid::TimeParams tp;
+    grid::TravParams trv;       // reach 0: nothing can be released
+    std::vector<uint8_t> table;
+    int32_t n_tracks;           // 0 unless release = 1 and an ID plane and tracks are given
+};
+
+// the static planes of a test entry on the host: RCOST, RPOT, RDIR and the released cells
+void time_static_host(const TimeTestArgs& q, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost, const uint8_t* flags, const uint8_t* cls,
+                      const int32_t* goals, int32_t n_goals, int32_t poa, int32_t pob, const int32_t* id, const int32_t* tracks, uint8_t* rcost, int32_t* rpot,
+                      uint8_t* rdir, int64_t* released) {
+    const size_t cells = (size_t)nx * (size_t)nz;
+    std::vector<uint8_t> f2(cells);
+    *released = q.n_tracks > 0 ? grid::time_release_window(q.pp, nx, nz, oa, ob, poa, pob, id, tracks, q.n_tracks, flags, f2.data()) : 0;
+    if (*released > 0) {
+        std::vector<uint16_t> gcol(cells);
+        grid::dist_window(q.trv.reach, nx, nz, cls, q.table.data(), f2.data(), gcol.data(), nullptr, rcost);
+    } else {
+        memcpy(rcost, cost, cells);
+    }
+    (void)grid::plan_window(q.pln, nx, nz, oa, ob, rcost, goals, n_goals, rpot, rdir);
+}
+
+// the same on the device, and the sweep and the walk there: the planes to the host, stats as svh_grid_get_time_stats, walk[3] the
+// status, the entries and the cost of the path from the window cell (a, b) (a < 0: no walk)
+int time_device(const TimeTestArgs& q, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost, const uint8_t* flags, const uint8_t* cls,
+                const int32_t* goals, int32_t n_goals, const uint32_t* pred, int32_t poa, int32_t pob, const int32_t* id, const int32_t* tracks, int32_t* tpot,
+                uint8_t* tdir, uint8_t* rcost, int32_t* rpot, uint8_t* rdir, int64_t* stats, int32_t a, int32_t b, int32_t* triples, int64_t cap, int64_t* walk) {
+    const size_t cells = (size_t)nx * (size_t)nz, states = cells * (size_t)q.tp.layers, tiles = ((size_t)(nx + grid::PLAN_TILE - 1) / grid::PLAN_TILE) * ((size_t)(nz + grid::PLAN_TILE - 1) / grid::PLAN_TILE);
+    HipBuf<uint8_t> d_cost, d_flags, d_cls, d_table, stat, field;
+    HipBuf<int32_t> d_goals, d_id, d_tracks, d_path;
+    HipBuf<uint32_t> d_pred, d_tiles, d_ctl;
+    HipBuf<unsigned long long> t_ctl;
+    HipBuf<int64_t> d_walk;
+    PinnedBuf<uint32_t> h_ctl;
+    PinnedBuf<unsigned long long> h_tctl;
+    PinnedBuf<int64_t> h_walk;
+    hipStream_t s = nullptr;
+    int64_t released = 0;
+    const int64_t room = std::min<int64_t>(cap, (int64_t)cells + q.tp.layers);
+    const int rc = [&]() -> int {
+        GRID_TRY(none, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        GRID_GROW(d_cost, cells);
+        GRID_GROW(d_flags, cells);
+        GRID_GROW(stat, cells * kTimeStaticBytes);
+        GRID_GROW(field, states * kTimeBytes);
+        GRID_GROW_N(d_goals, 2 * (size_t)n_goals);
+        GRID_GROW_N(d_pred, cells);
+        GRID_GROW(d_tiles, 4 * tiles * sizeof(uint32_t));
+        GRID_GROW(d_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+        GRID_GROW(h_ctl, grid::CTL_WORDS * sizeof(uint32_t));
+        GRID_GROW(t_ctl, grid::TC_WORDS * sizeof(unsigned long long));
+        GRID_GROW(h_tctl, grid::TC_WORDS * sizeof(unsigned long long));
+        GRID_GROW(d_walk, 3 * sizeof(int64_t));
+        GRID_GROW(h_walk, 3 * sizeof(int64_t));
+        GRID_GROW_N(d_path, 3 * room);
+        GRID_TRY(copy, hipMemcpyAsync(d_cost, cost, cells, hipMemcpyHostToDevice, s));
+        GRID_TRY(copy, hipMemcpyAsync(d_flags, flags, cells, hipMemcpyHostToDevice, s));
+        GRID_TRY(copy, hipMemcpyAsync(d_pred, pred, cells * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (n_goals > 0) GRID_TRY(copy, hipMemcpyAsync(d_goals, goals, 2 * (size_t)n_goals * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        uint8_t* st = stat.p;
+        uint8_t *s_cost = st + 9 * cells, *s_flags = st + 10 * cells;
+        if (q.n_tracks > 0) {
+            GRID_GROW(d_cls, cells);
+            GRID_GROW(d_table, q.table.size());
+            GRID_GROW_N(d_id, cells);
+            GRID_GROW_N(d_tracks, (size_t)q.n_tracks * grid::TRACK_REC);
+            GRID_TRY(copy, hipMemcpyAsync(d_cls, cls, cells, hipMemcpyHostToDevice, s));
+            GRID_TRY(copy, hipMemcpyAsync(d_table, q.table.data(), q.table.size(), hipMemcpyHostToDevice, s));
+            GRID_TRY(copy, hipMemcpyAsync(d_id, id, cells * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            GRID_TRY(copy, hipMemcpyAsync(d_tracks, tracks, (size_t)q.n_tracks * grid::TRACK_REC * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            grid::TimeReleaseJob rj;
+            rj.pp = q.pp;
+            rj.nx = nx, rj.nz = nz, rj.oa = oa, rj.ob = ob, rj.poa = poa, rj.pob = pob;
+            rj.id = d_id.p, rj.tracks = d_tracks.p, rj.n_tracks = q.n_tracks;
+            rj.flags = d_flags.p, rj.out = s_flags, rj.ctl = t_ctl.p;
+            const int r = time_release_run(s, rj, h_tctl, &released);
+            if (r) return r;
+        }
+        grid::PlanJob pj;
+        pj.pln = q.pln;
+        pj.nx = nx, pj.nz = nz, pj.oa = oa, pj.ob = ob;
+        pj.cost = released > 0 ? s_cost : d_cost.p;
+        pj.pot = (int32_t*)st, pj.price = (uint16_t*)(st + 4 * cells), pj.dir = st + 8 * cells;
+        pj.goals = d_goals.p, pj.n_goals = n_goals;
+        pj.lists = d_tiles.p, pj.flags = d_tiles.p + 2 * tiles;
+        pj.ctl = d_ctl.p;
+        int r;
+        if (released > 0) {
+            grid::TravJob tj;
+            tj.trv = q.trv;
+            tj.nx = nx, tj.nz = nz;
+            tj.cls = d_cls.p, tj.hmean = nullptr, tj.state = nullptr;
+            tj.table = d_table.p;
+            tj.flags = s_flags, tj.g = (uint16_t*)(st + 6 * cells), tj.dist2 = (int32_t*)field.p, tj.cost = s_cost;
+            r = time_static_run(s, tj, pj, h_ctl);
+        } else {
+            r = plan_run(s, pj, h_ctl);
+        }
+        if (r) return r;
+        grid::TimeJob j;
+        j.pln = q.pln, j.tp = q.tp, j.pp = q.pp;
+        j.nx = nx, j.nz = nz, j.oa = oa, j.ob = ob, j.poa = poa, j.pob = pob;
+        j.price = pj.price, j.rpot = pj.pot, j.rdir = pj.dir;
+        j.pred = d_pred.p;
+        j.tpot = (int32_t*)field.p, j.tdir = field.p + 4 * states;
+        j.ctl = t_ctl.p;
+        if ((r = time_sweep_run(s, j, h_tctl))) return r;
+        if (a >= 0) {
+            GRID_TRY(launch, (grid::launch_time_walk(s, j, a, b, d_path, room, d_walk), hipGetLastError()));
+            GRID_TRY(copy, hipMemcpyAsync(h_walk, d_walk, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            GRID_TRY(wait, hipStreamSynchronize(s));
+            const int64_t m = std::min<int64_t>(h_walk.p[1], room);
+            if (m > 0) GRID_TRY(copy, hipMemcpyAsync(triples, d_path, (size_t)m * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        GRID_TRY(copy, hipMemcpyAsync(tpot, j.tpot, states * 4, hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(tdir, j.tdir, states, hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(rcost, pj.cost, cells, hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(rpot, pj.pot, cells * 4, hipMemcpyDeviceToHost, s));
+        GRID_TRY(copy, hipMemcpyAsync(rdir, pj.dir, cells, hipMemcpyDeviceToHost, s));
+        GRID_TRY(wait, hipStreamSynchronize(s));
+        return SVH_OK;
+    }();
+    if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (rc) return rc;
+    stats[grid::TM_LAYERS] = q.tp.layers, stats[grid::TM_REACHED] = (int64_t)h_tctl.p[grid::TC_REACHED];
+    stats[grid::TM_BLOCKED] = (int64_t)h_tctl.p[grid::TC_BLOCKED], stats[grid::TM_WAITS] = (int64_t)h_tctl.p[grid::TC_WAITS];
+    stats[grid::TM_RELEASED] = released, stats[grid::TM_ROUNDS] = h_ctl.p[grid::CTL_ROUNDS];
+    if (a >= 0) walk[0] = h_walk.p[0], walk[1] = h_walk.p[1], walk[2] = h_walk.p[2];
+    return SVH_OK;
+}
+
 // ---- the exploration layer ------------------------------------------------------------------------------------------------
 const char* const kNoExplore =": the default range does not fit this grid's cell; set one (svh_grid_set_explore)";
 
@@ -2995,6 +3350,74 @@ int32_t svh_grid_render_pose(svh_grid* g, const int32_t* poses, int64_t n, uint8
         return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_pose: a grid, 0..8 nx nz poses (the longest path) and an output are needed");
     if (const char* why = pose_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_pose") + why);
     return failed(g, render_pose(g, poses, n, rgb, on_device != 0), kPose);
+}
+
+void svh_grid_time_params_default(svh_grid_time_params* p) {
+    if (!p) return;
+    p->layers = 32, p->wait = 100, p->release = 1;
+}
+
+int32_t svh_grid_set_time(svh_grid* g, const svh_grid_time_params* p) {
+    grid::TimeParams q;
+    if (!g || !convert_time(p, &q)) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_set_time: a grid and parameters in range are needed (include/svh_grid_time.h)");
+    if (q.release != g->tmp.release) drop(g, closure(kDropsNewRelease));
+    g->tmp = q;
+    g->time_on = true;
+    touch(g, TIME_PARAMS);
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_time(svh_grid* g, svh_grid_time_params* p) {
+    if (!g || !p) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_time: null argument");
+    p->layers = g->tmp.layers, p->wait = g->tmp.wait, p->release = g->tmp.release;
+    return SVH_OK;
+}
+
+int32_t svh_grid_get_time_plane(svh_grid* g, int32_t plane, int32_t t0, int32_t count, void* out, int32_t on_device) {
+    if (!g || !out || plane < 0 || plane >= grid::TP_PLANES) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_time_plane: a grid, a plane 0..3 and an output are needed");
+    const int32_t layers = (plane == grid::TP_RCOST || plane == grid::TP_RPOT) ? 1 : g->tmp.layers;
+    if (t0 < 0 || count < 1 || t0 > layers - count) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_time_plane: the layers t0 .. t0 + count - 1 are not all in 0 .. layers - 1 (one layer for RCOST and RPOT)");
+    if (on_device && (plane == grid::TP_TPOT || plane == grid::TP_RPOT) && ((uintptr_t)out & 3))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_time_plane: a device array of TPOT or RPOT must be 4-byte aligned");
+    if (const char* why = time_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_time_plane") + why);
+    return failed(g, get_time_plane(g, plane, t0, count, out, on_device != 0), kTime);
+}
+
+int32_t svh_grid_get_time_stats(svh_grid* g, int64_t out[6]) {
+    if (!g || !out) return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_get_time_stats: null argument");
+    if (const char* why = time_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_get_time_stats") + why);
+    int rc = ready(g);
+    if (!rc) rc = time_field(g);
+    if (rc) return failed(g, rc, kTime);
+    for (int k = 0; k < grid::TM_WORDS; k++) out[k] = g->time_stats[k];
+    out[grid::TM_RELEASED] = g->time_released, out[grid::TM_ROUNDS] = g->time_rounds;
+    return SVH_OK;
+}
+
+int32_t svh_grid_time_path(svh_grid* g, const double start_xyz[3], int32_t* triples, int64_t cap, int64_t* len, int32_t* cost) {
+    float p[3];
+    int32_t ga, gb;
+    if (!g || !len || !cost || cap < 0 || (cap > 0 && !triples) || !position(start_xyz, p) || !grid::global_cell(g->prm, p[0], p[1], p[2], &ga, &gb))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_time_path: a grid, outputs and a finite start with a cell below 2^20 are needed");
+    if (const char* why = time_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_time_path") + why);
+    const int64_t a = (int64_t)ga - g->prm.oa, b = (int64_t)gb - g->prm.ob;
+    if (a < 0 || a >= g->prm.nx || b < 0 || b >= g->prm.nz) {
+        *len = 0, *cost = grid::PLAN_FAR;
+        return grid::PATH_OUTSIDE;
+    }
+    int64_t n = 0;
+    int32_t c = grid::PLAN_FAR, status = 0;
+    const int rc = failed(g, time_path(g, (int32_t)a, (int32_t)b, triples, cap, &n, &c, &status), kTime);
+    if (rc) return rc;
+    *len = n, *cost = c;
+    return status;
+}
+
+int32_t svh_grid_render_time(svh_grid* g, int32_t t, const int32_t* triples, int64_t n, uint8_t* rgb, int32_t on_device) {
+    if (!g || !rgb || t < 0 || t >= g->tmp.layers || n < 0 || n > (int64_t)g->ncells + g->tmp.layers || (n > 0 && !triples))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_grid_render_time: a grid, a layer 0 .. layers - 1, 0 .. layers + nx nz triples (the longest path) and an output are needed");
+    if (const char* why = time_refusal(g)) return svh::fail(SVH_ERR_BAD_ARG, std::string("svh_grid_render_time") + why);
+    return failed(g, render_time(g, t, triples, n, rgb, on_device != 0), kTime);
 }
 
 void svh_grid_explore_params_default(svh_grid_explore_params* p) {
@@ -4211,6 +4634,83 @@ int32_t svh_test_grid_pose_device(const svh_grid_roll_params* r, const svh_grid_
     RollTable own = *t;   // the table is that of the vehicle; the costs are this call's
     own.p = q;
     return pose_device(pp, own, nx, nz, oa, ob, cost, goals, n, cf, pot, dir, out);
+}
+
+// the tile side of k_grid_time_sweep, and the layers of a chunk to *k
+int32_t svh_test_grid_time_tile(int32_t* k) {
+    if (k) *k = grid::TIME_K;
+    return grid::TIME_TILE;
+}
+
+// the checks that svh_test_grid_time and svh_test_grid_time_device share.  The ID plane and the tracks count only with release = 1,
+// and then CLASS and the traversability parameters are needed for the distance passes
+static bool time_test_args(const svh_grid_plan_params* pl, const svh_grid_pred_params* pp, const svh_grid_time_params* tp, const svh_grid_trav_params* tv,
+                           float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost, const uint8_t* flags, const uint8_t* cls,
+                           const int32_t* goals, int32_t n_goals, const uint32_t* pred, int32_t poa, int32_t pob, const int32_t* id, const int32_t* tracks,
+                           int32_t n_tracks, const void* tpot, const void* tdir, const void* rcost, const void* rpot, const void* rdir, const void* stats,
+                           int32_t a, int32_t b, const int32_t* triples, int64_t cap, const void* walk, TimeTestArgs* q) {
+    if (!pl || !convert_pred(pp, &q->pp) || !convert_time(tp, &q->tp) || nx < 1 || nx > grid::MAX_SIDE || nz < 1 || nz > grid::MAX_SIDE ||
+        !grid::time_fits(q->tp, nx, nz) || !grid::offsets_ok(oa, ob) || !grid::offsets_ok(poa, pob) || !cost || !flags || !pred || n_goals < 0 ||
+        n_goals > grid::PLAN_MAX_GOALS || (n_goals > 0 && !goals) || n_tracks < 0 || n_tracks > grid::OBJ_MAX_TRACKS || (n_tracks > 0 && (!tracks || !id)) ||
+        !tpot || !tdir || !rcost || !rpot || !rdir || !stats || cap < 0 || (a >= 0 && (a >= nx || b < 0 || b >= nz || !walk || (cap > 0 && !triples))))
+        return false;
+    q->pln = grid::PlanParams{pl->neutral, pl->unknown, pl->max_cost};
+    if (!grid::plan_ok(q->pln)) return false;
+    for (int32_t k = 0; k < 2 * n_goals; k++)
+        if (goals[k] <= -grid::PLAN_GOAL_LIMIT || goals[k] >= grid::PLAN_GOAL_LIMIT) return false;
+    for (int32_t t = 1; t < n_tracks; t++)
+        if (tracks[(size_t)t * grid::TRACK_REC] <= tracks[(size_t)(t - 1) * grid::TRACK_REC]) return false;
+    q->n_tracks = q->tp.release ? n_tracks : 0;
+    q->trv.reach = 0;
+    if (q->n_tracks > 0 && (!cls || !(grid::finite_f(cell) && cell > 0.f) || !convert_trav(tv, cell, &q->trv, &q->table))) return false;
+    return true;
+}
+
+// grid_time_core.h on the host: the window of nx x nz cells under (oa, ob) with its COST and FLAGS planes (and CLASS, for the distance
+// passes of release = 1), the planner's goals, PRED of the frame of nx x nz cells under (poa, pob), the ID plane of that frame and
+// n_tracks track records in ascending order of id -> tpot, tdir [layers * nz * nx], rcost, rpot, rdir [nz * nx], stats[6] (the rounds
+// are 0).  With a >= 0 the path from the window cell (a, b): walk[0] the status, walk[1] the entries, walk[2] the cost, the first
+// min(walk[1], cap) triples.  Needs no device
+int32_t svh_test_grid_time(const svh_grid_plan_params* pl, const svh_grid_pred_params* pp, const svh_grid_time_params* tp, const svh_grid_trav_params* tv,
+                           float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost, const uint8_t* flags, const uint8_t* cls,
+                           const int32_t* goals, int32_t n_goals, const uint32_t* pred, int32_t poa, int32_t pob, const int32_t* id, const int32_t* tracks,
+                           int32_t n_tracks, int32_t* tpot, uint8_t* tdir, uint8_t* rcost, int32_t* rpot, uint8_t* rdir, int64_t* stats, int32_t a,
+                           int32_t b, int32_t* triples, int64_t cap, int64_t* walk) {
+    TimeTestArgs q;
+    if (!time_test_args(pl, pp, tp, tv, cell, nx, nz, oa, ob, cost, flags, cls, goals, n_goals, pred, poa, pob, id, tracks, n_tracks, tpot, tdir, rcost, rpot,
+                        rdir, stats, a, b, triples, cap, walk, &q))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_time: bad arguments");
+    const size_t cells = (size_t)nx * (size_t)nz;
+    int64_t released = 0;
+    time_static_host(q, nx, nz, oa, ob, cost, flags, cls, goals, n_goals, poa, pob, id, tracks, rcost, rpot, rdir, &released);
+    std::vector<uint16_t> price(cells);
+    for (size_t i = 0; i < cells; i++) price[i] = grid::price_of(q.pln, rcost[i]);
+    grid::time_window(q.pln, q.tp, q.pp, nx, nz, oa, ob, price.data(), rpot, rdir, pred, poa, pob, tpot, tdir, stats);
+    stats[grid::TM_RELEASED] = released, stats[grid::TM_ROUNDS] = 0;
+    if (a >= 0) {
+        const size_t i = (size_t)b * (size_t)nx + (size_t)a;
+        const grid::TimeBlock B{pred, nx, nz, oa, ob, poa, pob};
+        int32_t status = grid::time_start_status(price[i], B(a, b), tpot[i]);
+        int64_t len = 0;
+        if (status == grid::PATH_FOUND && (len = grid::time_walk(nx, nz, oa, ob, q.tp.layers, tdir, rdir, a, b, triples, cap)) == 0) status = grid::PATH_UNREACHABLE;
+        walk[0] = status, walk[1] = len, walk[2] = tpot[i];
+    }
+    return SVH_OK;
+}
+
+// the same through the kernels of csrc/grid_time_kernels.hip, the distance launches and the planner's round loop; stats[5] the rounds
+int32_t svh_test_grid_time_device(const svh_grid_plan_params* pl, const svh_grid_pred_params* pp, const svh_grid_time_params* tp,
+                                  const svh_grid_trav_params* tv, float cell, int32_t nx, int32_t nz, int32_t oa, int32_t ob, const uint8_t* cost,
+                                  const uint8_t* flags, const uint8_t* cls, const int32_t* goals, int32_t n_goals, const uint32_t* pred, int32_t poa,
+                                  int32_t pob, const int32_t* id, const int32_t* tracks, int32_t n_tracks, int32_t* tpot, uint8_t* tdir, uint8_t* rcost,
+                                  int32_t* rpot, uint8_t* rdir, int64_t* stats, int32_t a, int32_t b, int32_t* triples, int64_t cap, int64_t* walk) {
+    TimeTestArgs q;
+    if (!time_test_args(pl, pp, tp, tv, cell, nx, nz, oa, ob, cost, flags, cls, goals, n_goals, pred, poa, pob, id, tracks, n_tracks, tpot, tdir, rcost, rpot,
+                        rdir, stats, a, b, triples, cap, walk, &q))
+        return svh::fail(SVH_ERR_BAD_ARG, "svh_test_grid_time_device: bad arguments");
+    svh::ensure_init();
+    return time_device(q, nx, nz, oa, ob, cost, flags, cls, goals, n_goals, pred, poa, pob, id, tracks, tpot, tdir, rcost, rpot, rdir, stats, a, b, triples, cap,
+                       walk);
 }
 
 // grid_core.h's traversability layer on the host: the planes of a window of p->nx x p->nz cells from CLASS, HMEAN and STATE;

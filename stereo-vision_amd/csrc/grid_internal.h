@@ -1,7 +1,7 @@
 // Between csrc/grid_engine.cpp (host) and csrc/grid_kernels.hip / csrc/grid_trav_kernels.hip / csrc/grid_plan_kernels.hip /
 // csrc/grid_front_kernels.hip / csrc/grid_obj_kernels.hip / csrc/grid_roll_kernels.hip / csrc/grid_pred_kernels.hip /
 // csrc/grid_explore_kernels.hip / csrc/grid_align_kernels.hip / csrc/grid_dyn_kernels.hip / csrc/grid_pose_kernels.hip /
-// csrc/grid_archive_kernels.hip: the launches of the
+// csrc/grid_archive_kernels.hip / csrc/grid_time_kernels.hip: the launches of the
 // ground grid (include/svh_grid.h).
 #ifndef SVH_GRID_INTERNAL_H
 #define SVH_GRID_INTERNAL_H
@@ -20,6 +20,7 @@
 #include "grid_pose_core.h"
 #include "grid_pred_core.h"
 #include "grid_roll_core.h"
+#include "grid_time_core.h"
 
 namespace svh {
 namespace grid {
@@ -128,6 +129,8 @@ struct TravJob {
 };
 // the three launches: mask, columns, rows
 void launch_trav(hipStream_t s, const TravJob& j);
+// the last two of them on the FLAGS plane the job names: of the job they read trv.reach, nx, nz, cls, table, flags, g, dist2 and cost
+void launch_trav_dist(hipStream_t s, const TravJob& j);
 
 struct RenderCostJob {
     int32_t nx, nz;
@@ -454,6 +457,56 @@ void launch_footprint_pred(hipStream_t s, const RollPredJob& j, const int32_t* p
 void launch_pred_overlay(hipStream_t s, int32_t nx, int32_t nz, int32_t oa, int32_t ob, int32_t poa, int32_t pob, const uint32_t* pred, uint8_t* rgb);
 // k_grid_roll_best of csrc/grid_roll_kernels.hip
 void launch_roll_best(hipStream_t s, const long long* scores, int32_t K, int32_t* best);
+
+// The time layer (csrc/grid_time_kernels.hip): FLAGS and the tracks -> FLAGS'; the static planes RPRICE, RPOT, RDIR and PRED -> TPOT and
+// TDIR over cell x layer, a path through them.
+constexpr uint32_t TIME_BLOCK = 256;             // every kernel of the layer but the walk: one lane per cell
+// the control words on the device, 64 bits each: the released cells, then a grid::TimeStat's REACHED, BLOCKED and WAITS
+enum TimeCtl { TC_RELEASED = 0, TC_REACHED, TC_BLOCKED, TC_WAITS, TC_WORDS };
+
+struct TimeReleaseJob {
+    PredParams pp;
+    int32_t nx, nz, oa, ob, poa, pob;   // the window and the offsets of the ID frame
+    const int32_t* id;          // the ID plane of the last step
+    const int32_t* tracks;      // its n_tracks records, ascending by id; 1..4096
+    int32_t n_tracks;
+    const uint8_t* flags;       // FLAGS
+    uint8_t* out;               // FLAGS'
+    unsigned long long* ctl;    // [TC_RELEASED] added to
+};
+void launch_time_release(hipStream_t s, const TimeReleaseJob& j);
+
+struct TimeJob {
+    PlanParams pln;
+    TimeParams tp;
+    PredParams pp;
+    int32_t nx, nz, oa, ob, poa, pob;
+    const uint16_t* price;      // RPRICE, RPOT, RDIR: nx * nz each, logical order
+    const int32_t* rpot;
+    const uint8_t* rdir;
+    const uint32_t* pred;       // PRED of the frame of nx x nz cells under (poa, pob)
+    int32_t* tpot;              // layers * nx * nz each, layer-major
+    uint8_t* tdir;
+    unsigned long long* ctl;    // TC_WORDS: [TC_REACHED ..] all zero before the sweep, added to
+};
+// k_grid_time_sweep: a workgroup owns TIME_TILE x TIME_TILE cells and TIME_K layers; it stages a box with a halo of TIME_K cells
+#ifndef SVH_TIME_TILE
+#define SVH_TIME_TILE 32
+#endif
+#ifndef SVH_TIME_K
+#define SVH_TIME_K 8
+#endif
+constexpr int32_t TIME_TILE = SVH_TIME_TILE, TIME_K = SVH_TIME_K, TIME_BOX = TIME_TILE + 2 * TIME_K;
+static_assert(TIME_K >= 1 && (size_t)TIME_BOX * TIME_BOX * 14 <= 64 * 1024, "the box of k_grid_time_sweep is static LDS: 14 bytes per cell");
+// the whole sweep, layer L - 1 first: 1 + ceil((L - 1) / TIME_K) launches; returns the kernels it launched
+int32_t launch_time_sweep(hipStream_t s, const TimeJob& j);
+// the walk from the window cell (a, b) at layer 0: out[0] a PathStatus, out[1] the entries of the path, out[2] TPOT of the start; the
+// first min(out[1], cap) triples to `triples`
+void launch_time_walk(hipStream_t s, const TimeJob& j, int32_t a, int32_t b, int32_t* triples, int64_t cap, int64_t* out);
+// over an image of svh_grid_render_cost's layout: the cells with BLOCK at layer t, then (two more launches) the goals that count and the
+// cells of n triples
+void launch_time_overlay(hipStream_t s, const TimeJob& j, int32_t t, const int32_t* goals, int32_t n_goals, const int32_t* triples, int64_t n,
+                         uint8_t* rgb);
 
 // The exploration layer (csrc/grid_explore_kernels.hip): the finished STATE plane, the frontier table and the reach field -> GAIN of
 // viewpoints, the VIEW plane of one, the records, the scores and the best.

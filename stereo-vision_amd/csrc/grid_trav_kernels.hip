@@ -106,6 +106,11 @@ void launch_trav(hipStream_t s, const TravJob& j) {
     const unsigned nx = (unsigned)j.nx, nz = (unsigned)j.nz, cells = nx * nz;
     hipLaunchKernelGGL(k_grid_trav_mask, dim3((cells + TRAV_BLOCK - 1) / TRAV_BLOCK), dim3(TRAV_BLOCK), 0, s, j.trv, j.nx, j.nz,
                        j.cls, j.hmean, j.state, j.flags);
+    launch_trav_dist(s, j);
+}
+
+void launch_trav_dist(hipStream_t s, const TravJob& j) {
+    const unsigned nx = (unsigned)j.nx, nz = (unsigned)j.nz;
     hipLaunchKernelGGL(k_grid_dist_cols, dim3((nx + COLS_BLOCK - 1) / COLS_BLOCK, (nz + (unsigned)COLS_CHUNK - 1) / (unsigned)COLS_CHUNK),
                        dim3(COLS_BLOCK), 0, s, j.trv.reach, j.nx, j.nz, (const uint8_t*)j.flags, j.g);
     hipLaunchKernelGGL(k_grid_dist_rows, dim3((nx + TRAV_BLOCK - 1) / TRAV_BLOCK, nz), dim3(TRAV_BLOCK), 0, s, j.trv.reach, j.nx,

@@ -74,6 +74,10 @@ ROLL_CUT_OBJECT = 4
 ROLL_PRED_RECORD = 6
 ROLL_PRED_FIELDS = ROLL_FIELDS + ("slot",)
 PRED_STATS = ("tracks", "sources", "cells", "launches")
+TIME_TPOT, TIME_TDIR, TIME_RCOST, TIME_RPOT = 0, 1, 2, 3
+TIME_DTYPE = [np.int32, np.uint8, np.uint8, np.int32]
+TIME_WAIT = 10
+TIME_STATS = ("layers", "reached", "blocked", "waits", "released", "rounds")
 PRED_MAX_SLOTS, PRED_MAX_RADIUS = 32, 16
 REGION_GRID, REGION_LOCAL = range(2)
 RENDER_LOCAL = 3
@@ -132,6 +136,20 @@ class PoseParams(C.Structure):
 
     def copy(self, **kw):
         q = PoseParams.from_buffer_copy(bytes(self))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def asdict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class TimeParams(C.Structure):
+    """svh_grid_time_params"""
+    _fields_ = [("layers", C.c_int32), ("wait", C.c_int32), ("release", C.c_int32)]
+
+    def copy(self, **kw):
+        q = TimeParams.from_buffer_copy(bytes(self))
         for k, v in kw.items():
             setattr(q, k, v)
         return q
@@ -403,6 +421,19 @@ def _bind():
                 [C.c_void_p] * 4)
         L.svh_test_grid_pose.argtypes = pose
         L.svh_test_grid_pose_device.argtypes = pose
+        L.svh_grid_time_params_default.argtypes = [C.POINTER(TimeParams)]
+        L.svh_grid_time_params_default.restype = None
+        L.svh_grid_set_time.argtypes = [C.c_void_p, C.POINTER(TimeParams)]
+        L.svh_grid_get_time.argtypes = [C.c_void_p, C.POINTER(TimeParams)]
+        L.svh_grid_get_time_plane.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        L.svh_grid_get_time_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.svh_grid_time_path.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.svh_grid_render_time.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
+        time_ = ([C.POINTER(PlanParams), C.POINTER(PredParams), C.POINTER(TimeParams), C.POINTER(TravParams), C.c_float] + [C.c_int32] * 4 +
+                 [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 +
+                 [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p])
+        L.svh_test_grid_time.argtypes = time_
+        L.svh_test_grid_time_device.argtypes = time_
         L.svh_test_grid_pose_walk.argtypes = [C.c_int32] * 5 + [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int64, C.c_void_p]
         L.svh_grid_explore_params_default.argtypes = [C.POINTER(ExploreParams)]
         L.svh_grid_explore_params_default.restype = None
@@ -870,6 +901,55 @@ def core_pose_walk(dir_, a, b, d, m=1, oa=0, ob=0, cap=None):
     poses, n = np.zeros((max(room, 1), 3), np.int32), C.c_int64(-1)
     _check(_bind().svh_test_grid_pose_walk(nx, nz, oa, ob, m, f.ctypes.data, a, b, d, poses.ctypes.data if room else None, room, C.addressof(n)))
     return poses[:min(n.value, room)].copy(), n.value
+
+
+def default_time(**kw):
+    p = TimeParams()
+    _bind().svh_grid_time_params_default(C.byref(p))
+    return p.copy(**kw)
+
+
+def _time(entry, plan, pred, time, cost, flags, goals, plane, oa, ob, pred_off, ids, tracks, cls, trav, cell, start, cap):
+    c = np.ascontiguousarray(cost, np.uint8)
+    nz, nx = c.shape
+    f = np.ascontiguousarray(flags if flags is not None else np.zeros((nz, nx)), np.uint8).reshape(nz, nx)
+    w = np.ascontiguousarray(plane if plane is not None else np.zeros((nz, nx)), np.uint32).reshape(nz, nx)
+    g = np.ascontiguousarray(goals, np.int32).reshape(-1, 2)
+    i = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(nz, nx)
+    t = np.ascontiguousarray(tracks if tracks is not None else np.zeros((0, TRACK_RECORD)), np.int32).reshape(-1, TRACK_RECORD)
+    k = None if cls is None else np.ascontiguousarray(cls, np.uint8).reshape(nz, nx)
+    L = time.layers
+    tpot, tdir = np.zeros((max(L, 1), nz, nx), np.int32), np.zeros((max(L, 1), nz, nx), np.uint8)
+    rcost, rpot, rdir = np.zeros((nz, nx), np.uint8), np.zeros((nz, nx), np.int32), np.zeros((nz, nx), np.uint8)
+    stats, walk = np.zeros(6, np.int64), np.zeros(3, np.int64)
+    a, b = start if start is not None else (-1, -1)
+    room = (max(L, 0) + nx * nz if cap is None else int(cap)) if start is not None else 0
+    triples = np.zeros((max(room, 1), 3), np.int32)
+    _check(entry(C.byref(plan), C.byref(pred), C.byref(time), None if trav is None else C.byref(trav), cell, nx, nz, oa, ob, c.ctypes.data,
+                 f.ctypes.data, None if k is None else k.ctypes.data, g.ctypes.data if len(g) else None, len(g), w.ctypes.data, pred_off[0],
+                 pred_off[1], None if i is None else i.ctypes.data, t.ctypes.data if len(t) else None, len(t), tpot.ctypes.data, tdir.ctypes.data,
+                 rcost.ctypes.data, rpot.ctypes.data, rdir.ctypes.data, stats.ctypes.data, a, b, triples.ctypes.data if room else None, room,
+                 walk.ctypes.data))
+    out = dict(tpot=tpot, tdir=tdir, rcost=rcost, rpot=rpot, rdir=rdir, stats=tuple(int(v) for v in stats))
+    if start is not None:
+        out.update(status=int(walk[0]), path_len=int(walk[1]), cost=int(walk[2]), path=triples[:min(int(walk[1]), room)].copy())
+    return out
+
+
+def core_time(plan, pred, time, cost, flags=None, goals=(), plane=None, oa=0, ob=0, pred_off=(0, 0), ids=None, tracks=None, cls=None, trav=None,
+              cell=0.0, start=None, cap=None):
+    """the time layer of csrc/grid_time_core.h on the host (svh_test_grid_time): the COST and FLAGS planes uint8 [nz, nx] of a window under
+    (oa, ob), the planner's goals (global cells), the PRED plane uint32 [nz, nx] under pred_off (None: all 0) and, for release = 1, the ID
+    plane of that frame, the track records [n, 14], the CLASS plane and the traversability parameters on cells of side `cell`.  A dict:
+    tpot int32 and tdir uint8 [L, nz, nx], rcost, rpot, rdir [nz, nx], stats (6; the rounds are 0) and, with start = (a, b) a window
+    cell, status, path int32 [n, 3], path_len, cost.  Needs no device"""
+    return _time(_bind().svh_test_grid_time, plan, pred, time, cost, flags, goals, plane, oa, ob, pred_off, ids, tracks, cls, trav, cell, start, cap)
+
+
+def device_time(plan, pred, time, cost, flags=None, goals=(), plane=None, oa=0, ob=0, pred_off=(0, 0), ids=None, tracks=None, cls=None, trav=None,
+                cell=0.0, start=None, cap=None):
+    """TEST ENTRY: the same through the kernels of csrc/grid_time_kernels.hip; stats[5] the rounds of RPOT"""
+    return _time(_bind().svh_test_grid_time_device, plan, pred, time, cost, flags, goals, plane, oa, ob, pred_off, ids, tracks, cls, trav, cell, start, cap)
 
 
 def default_pred(**kw):
@@ -1677,6 +1757,58 @@ class Grid:
             return None
         img = np.zeros((self.nz, self.nx, 3), np.uint8)
         _check(self._L.svh_grid_render_pose(self._h, ptr, len(t), img.ctypes.data, 0))
+        return img
+
+    def set_time(self, params=None, **kw):
+        """switches the time layer on with the parameters in force (or `params`) and the fields of kw replaced: layers, wait, release"""
+        p = (params if params is not None else self.time_params()).copy(**kw)
+        _check(self._L.svh_grid_set_time(self._h, C.byref(p)))
+
+    def time_params(self):
+        p = TimeParams()
+        _check(self._L.svh_grid_get_time(self._h, C.byref(p)))
+        return p
+
+    def time_plane(self, which, t0=0, count=None, device_ptr=None):
+        """TIME_TPOT int32 or TIME_TDIR uint8, [count, nz, nx] from layer t0 (count None: all that follow); TIME_RCOST uint8 or TIME_RPOT
+        int32, [nz, nx]; with device_ptr it is written there and None returned"""
+        if not 0 <= which < len(TIME_DTYPE):
+            raise SvhError(ERR_BAD_ARG, "no such plane")
+        static = which in (TIME_RCOST, TIME_RPOT)
+        n = (1 if static else self.time_params().layers - t0) if count is None else int(count)
+        if device_ptr is not None:
+            _check(self._L.svh_grid_get_time_plane(self._h, which, t0, n, device_ptr, 1))
+            return None
+        out = np.zeros((max(n, 1), self.nz, self.nx), TIME_DTYPE[which])
+        _check(self._L.svh_grid_get_time_plane(self._h, which, t0, n, out.ctypes.data, 0))
+        return out[0] if static else out
+
+    def time_stats(self):
+        """(layers, states with TPOT != FAR, passable states with BLOCK, states whose TDIR is wait, released cells, rounds of RPOT)"""
+        out = np.zeros(6, np.int64)
+        _check(self._L.svh_grid_get_time_stats(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
+    def time_path(self, start_xyz, cap=None):
+        """(status, triples [n, 3] int32 (ga, gb, t), cost): the cheapest sequence from the cell of a map-frame position at layer 0; a
+        wait repeats the cell.  With cap only its first entries, and the length of the whole path is in `time_path_len`"""
+        room = self.time_params().layers + self.nx * self.nz if cap is None else int(cap)
+        triples = np.zeros((max(room, 1), 3), np.int32)
+        n, cost = C.c_int64(-1), C.c_int32(-1)
+        status = _check(self._L.svh_grid_time_path(self._h, _xyz(start_xyz).ctypes.data, triples.ctypes.data if room else None, room,
+                                                   C.addressof(n), C.addressof(cost)))
+        self.time_path_len = n.value
+        return status, triples[:min(n.value, room)].copy(), cost.value
+
+    def render_time(self, t=0, triples=(), device_ptr=None):
+        """the image of RCOST with the cells blocked at layer t in the prediction's colour of its slot, the goals that count in
+        GOAL_COLOUR and the cells of the given triples in PATH_COLOUR over it"""
+        q, ptr = _triples(triples)
+        if device_ptr is not None:
+            _check(self._L.svh_grid_render_time(self._h, t, ptr, len(q), device_ptr, 1))
+            return None
+        img = np.zeros((self.nz, self.nx, 3), np.uint8)
+        _check(self._L.svh_grid_render_time(self._h, t, ptr, len(q), img.ctypes.data, 0))
         return img
 
     def set_explore(self, params=None, **kw):

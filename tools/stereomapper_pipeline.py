@@ -27,6 +27,7 @@ without the GUI.  Usage:
                                          [--grid-archive DIR [--grid-archive-tiles N]]
                                           [--grid-objects DIR [--grid-objects-params MIN,MAX,HEIGHT,GATE,MISSED]]
                                           [--grid-predict DIR [--grid-predict-params SLOTS,STRIDE,MARGIN,GROW16]]
+                                          [--grid-time DIR [--grid-time-params L,WAIT,RELEASE]]
                                           <drive_dir> <calib_cam_to_cam.txt> [max_frames]
 
 --render DIR: the accumulated map is drawn after every frame (320 x 480, the reference's recording size) into
@@ -153,6 +154,13 @@ margin and grow16 of svh_grid_pred_params; 8,1,1,0; a pose per track step, movin
 class image with the predicted cells over it, coloured by their first slot) goes into DIR/predict_%06d.ppm and one line {"frame",
 "set", "best", "best_pred", "cut_by_object", "score", "score_pred", "pred_stats"} -- both bests, without and with the prediction, and
 how many arcs a predicted object cut -- is appended to DIR/predict.jsonl.
+
+--grid-time DIR: needs --grid-objects and --grid-predict.  After the prediction of a frame a path over cell x time from the camera's
+cell to the planner's goals that waits for the predicted objects (svh_grid_time_path; --grid-time-params L,WAIT,RELEASE: layers, wait
+and release of svh_grid_time_params; 32,100,1).  The images of the layers 0 and L / 2 (svh_grid_render_time: the cost map without
+the released objects, the cells blocked at that layer, the goals, the path) go into DIR/time_%06d_t%03d.ppm and one line {"frame",
+"status", "length", "cost", "waits", "triples", "time_stats"} -- the path's triples (ga, gb, t) and how many of its moves are waits --
+is appended to DIR/time.jsonl.
 
 --grid-dynamic DIR: needs --grid-local.  The local step takes a frame as an OBSERVATION (svh_grid_observe_view_lists) instead of an
 add: the frame's sight lines contradict obstacle cells they pass through at the height of their body, CLEAR contradicting frames in a row
@@ -679,6 +687,7 @@ def main():
     archive_dir, archive_tiles = None, None
     obj_dir, obj_kw = None, {}
     pred_dir, pred_kw = None, {}
+    time_dir, time_kw = None, {}
     level = "--level" in sys.argv
     if level:
         sys.argv.remove("--level")
@@ -820,6 +829,19 @@ def main():
             pred_kw = dict(slots=v[0], stride=v[1], margin=v[2], grow16=v[3])
             assert 1 <= pred_kw["slots"] <= 32 and 1 <= pred_kw["stride"] <= 64 and 0 <= pred_kw["margin"] <= 16 and 0 <= pred_kw["grow16"] <= 256
             del sys.argv[k:k + 2]
+        if "--grid-time" in sys.argv:
+            k = sys.argv.index("--grid-time")
+            time_dir = sys.argv[k + 1]
+            del sys.argv[k:k + 2]
+        if "--grid-time-params" in sys.argv:
+            k = sys.argv.index("--grid-time-params")
+            v = [int(x) for x in sys.argv[k + 1].split(",")]
+            assert len(v) == 3
+            time_kw = dict(layers=v[0], wait=v[1], release=v[2])
+            assert 1 <= time_kw["layers"] <= 256 and (time_kw["wait"] == -1 or 1 <= time_kw["wait"] <= 65535) and time_kw["release"] in (0, 1)
+            del sys.argv[k:k + 2]
+        assert (obj_dir and pred_dir) or not time_dir
+        assert time_dir or not time_kw
         assert (obj_dir and roll_dir) or not pred_dir
         assert pred_dir or not pred_kw
         assert local_dir or not obj_dir
@@ -929,6 +951,9 @@ def main():
     if pred_dir:
         os.makedirs(pred_dir, exist_ok=True)
         open(os.path.join(pred_dir, "predict.jsonl"), "w").close()
+    if time_dir:
+        os.makedirs(time_dir, exist_ok=True)
+        open(os.path.join(time_dir, "time.jsonl"), "w").close()
     if lockstep:
         return main_lockstep(lockstep, sys.argv[1], calib, limit, rp, normalize, thin, thin_every, ply)
     p = Pipeline(calib.f, calib.cu, calib.cv, calib.base, rectify_params=rp, resident=resident, normalize=normalize,
@@ -957,11 +982,13 @@ def main():
         p.enable_roll(ROLL_CURVATURES, 2.0 * grid_cell, ROLL_POSES, **roll_kw)
     if pred_kw:
         p.local.set_predict(**pred_kw)
+    if time_dir:
+        p.local.set_time(**time_kw)
     if pose_dir:
         if roll_kw and not roll_dir:
             p.local.set_roll(**roll_kw)
         p.local.set_pose(**pose_kw)
-    found = explored = rolled = ranked = aligned = cut_frames = posed = 0
+    found = explored = rolled = ranked = aligned = cut_frames = posed = timed = waited = 0
     t0 = time.perf_counter()
     frames = 0
     for I1, I2, (tl, _) in kitti.Sequence(sys.argv[1]):
@@ -1030,6 +1057,18 @@ def main():
                 f.write(json.dumps({"frame": frames - 1, "set": int(s), "best": int(best), "best_pred": int(best_p), "cut_by_object": cut,
                                     "score": int(scores[best]) if best >= 0 else None, "score_pred": int(scores_p[best_p]) if best_p >= 0 else None,
                                     "pred_stats": list(p.local.pred_stats())}) + "\n")
+        if time_dir:
+            status, triples, cost = p.local.time_path(p.H_total[:3, 3].copy())
+            layers = p.local.time_params().layers
+            same = (triples[1:, :2] == triples[:-1, :2]).all(1) if len(triples) > 1 else np.zeros(0, bool)
+            waits = int((same & (triples[:-1, 2] < layers - 1)).sum())
+            timed += status == 0
+            waited += waits > 0
+            for t in sorted({0, layers // 2}):
+                view.write_ppm(os.path.join(time_dir, "time_%06d_t%03d.ppm" % (frames - 1, t)), p.local.render_time(t, triples))
+            with open(os.path.join(time_dir, "time.jsonl"), "a") as f:
+                f.write(json.dumps({"frame": frames - 1, "status": int(status), "length": int(len(triples)), "cost": int(cost), "waits": waits,
+                                    "triples": triples.tolist(), "time_stats": list(p.local.time_stats())}) + "\n")
         if front_dir:
             stats, status, cells, cost, img = p.frontier_step()
             explored += status == 0
@@ -1093,6 +1132,10 @@ def main():
         q = p.local.get_predict()
         print("prediction: %d slots of %d steps, margin %d cells growing %d/16 per slot: an arc cut by a predicted object in %d of %d frames; "
               "%d images and predict.jsonl in %s" % (q.slots, q.stride, q.margin, q.grow16, cut_frames, frames, frames, pred_dir))
+    if time_dir:
+        q = p.local.time_params()
+        print("time layer: %d layers, wait %d, release %d: a path in %d of %d frames, one that waits in %d; %d images and time.jsonl in %s" % (
+            q.layers, q.wait, q.release, timed, frames, waited, len({0, q.layers // 2}) * frames, time_dir))
     if front_dir:
         print("frontiers: goals from the kept components, a route in %d of %d frames; %d images and frontiers.jsonl in %s" % (
             explored, frames, frames, front_dir))
